@@ -12,9 +12,14 @@ run gives it.
 
 `value` = dofs of one step / (MEDIAN over --repeats windows of the time of exactly --steps steps), the window being
 trajectory steps [--warmup, --warmup + --steps); the device is put back to the start of the window before every repeat.
-`spike_window` is the same measurement around the step where the membrane fires (most ODE work), `with_solves` whole
-time steps including the device Krylov solves from a fixed trajectory step, `config3_leg` the same measurement on the
-995 328-tet mesh (where the row kernels are HBM-bound, not launch-bound), `dg_variant` a short run of the DG variant.
+A plain run records the trajectory up to the end of the window and times one window (--repeats 1): --steps is the number
+of timed steps.  Everything else is measured with --full only (--repeats 7 by default there): the per-kernel profile and
+roofline figures, the window with A_knp assembled twice, `spike_window` (the same measurement around the step where the
+membrane fires, most ODE work), `with_solves` (whole time steps including the device Krylov solves from a fixed trajectory
+step), the CPU baselines and their agreement check, `config3_leg` (the same measurement on the 995 328-tet mesh, where the
+row kernels are HBM-bound, not launch-bound) and `dg_variant` (a short run of the DG variant).
+--dump-outputs DIR writes what the timed path holds after the last timed step (fields, membrane ODE tables, the systems
+assembled in that step) as DIR/<name>.npy, float64, a fixed seeded sample of each array where they exceed 60 MB together.
 Any failure (a solve that does not converge, a communication hook, LSODA) exits non-zero: there is no fallback state.
 
 At N > 1 the mesh is partitioned into x-slabs (weak: N times longer box; --scaling strong: the fixed config-3 box),
@@ -22,7 +27,8 @@ every step exchanges the ghost-dof halo of the bulk fields (stream-ordered RCCL 
 are integrated redundantly), and the recorded trajectory comes from the distributed Krylov solves
 (knpemi_set_distributed: halo'd SpMV, all-reduced dot products, per-GPU AMG).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python bench.py --gpus N ...        (starts the N ranks itself, as a child `python -m torch.distributed.run`)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
@@ -49,6 +55,7 @@ if os.environ.get("KNPEMI_BENCH_TRAJ_MIN"):     # rehearsals of the N > 1 code p
     SPIKE_SEARCH = max(8, int(os.environ["KNPEMI_BENCH_TRAJ_MIN"]))
 WITH_SOLVES_START = 10   # trajectory step the with_solves pass starts from, whatever --steps / --warmup are
 AGREEMENT_LIMIT = 1e-6   # cpu_baseline.agreement above this ends the bench with a non-zero exit code
+DUMP_BYTES = 60_000_000  # --dump-outputs: arrays beyond this many bytes together are sampled
 
 WORKLOADS = {
     # name: (family, mesh kind, resolution factor) -- geometry of make_mesh_3D.py, 6 tets per hexahedron
@@ -283,6 +290,72 @@ def agreement(case, replay, final):
     return out
 
 
+def csr_values(M):
+    """Values of a CSR matrix in (row, column) order, whatever order the device keeps them in (the matrix is copied: the
+    device problems share their cached index arrays with the matrices they hand out)."""
+    M = M.copy()
+    M.sort_indices()
+    return M.data
+
+
+def cg_outputs(case, dp):
+    """What a caller of the timed path holds after its last step: the fields of every sub-domain, the membrane ODE tables and
+    the five objects assembled in that step."""
+    import numpy as np
+    from knpemi import _lib as L
+    dp.sync()
+    out = {}
+    for s, tag in enumerate(dp.tags):
+        n = int(dp.n_vert[s])
+        out[f"phi_{tag}"] = dp.pull_array(L.F_PHI, s, 0, n)
+        for k in range(dp.K - 1):
+            out[f"c_{tag}_{k}"] = dp.pull_array(L.F_C, s, k, n)
+        out[f"c_elim_{tag}"] = dp.pull_array(L.F_C_ELIM, s, 0, n)
+        if s > 0:
+            out[f"phi_M_{tag}"] = dp.pull_array(L.F_PHI_M, s, 0, int(dp.n_q[s]))
+    for i, (m, _, _) in enumerate(case.models):
+        st = np.ascontiguousarray(np.empty_like(m.states))
+        pa = np.ascontiguousarray(np.empty_like(m.parameters))
+        L.check(dp.lib.knpemi_ode_get_tables(dp.h, m._sub, m._model, L.dptr(st), L.dptr(pa)))
+        out[f"ode_states_{i}"], out[f"ode_parameters_{i}"] = st, pa
+    for name, which in (("A_emi", L.A_EMI), ("P_emi", L.P_EMI), ("A_knp", L.A_KNP)):
+        out[name] = csr_values(dp.csr(which))
+    out["b_emi"], out["b_knp"] = dp.rhs(L.B_EMI), dp.rhs(L.B_KNP)
+    return out
+
+
+def dg_outputs(dp):
+    """The same for the DG variant: fields, channel currents, ODE tables, the K systems assembled in the last step."""
+    dp.sync()
+    out = {"phi": dp.get_potential(), "phi_M": dp.get_membrane_potential()}
+    for k in range(dp.K - 1):
+        out[f"c_{k}"] = dp.get_concentration(k)
+    for k in range(dp.K):
+        out[f"I_ch_{k}"] = dp.get_channel_current(k)
+    out["ode_states"], out["ode_parameters"] = dp.ode_tables()
+    for w in range(dp.K):
+        out[f"A_{w}"], out[f"b_{w}"] = csr_values(dp.matrix(w)), dp.rhs(w)
+    return out
+
+
+def write_outputs(outdir, arrays, rank=0, world=1):
+    """--dump-outputs: every array as outdir/<name>.npy in float64 (<name>_rank<r>.npy at N > 1).  When the arrays of this
+    rank hold more than their share of DUMP_BYTES, each is replaced by the same fraction of its entries, at positions drawn
+    from a generator seeded with the array's name: the same sample in every run of the same arguments."""
+    import zlib
+    import numpy as np
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, DUMP_BYTES / world / max(total, 1))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        if keep < 1.0:
+            flat = a.reshape(-1)
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = flat[np.sort(rng.choice(flat.size, int(flat.size * keep), replace=False))]
+        np.save(os.path.join(outdir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 def device_solvers(case, its, maxit=1000, dp=None, min_it=None, method="bicgstab", emi_norm=None):
     """Solve callbacks of the stepper: knpemi_solve_emi (CG + AMG) / knpemi_solve_knp (BiCGStab or GMRES + AMG) at the
     reference's tolerances, starting from the extrapolated previous solutions.  `min_it` (with `dp`): fewest iterations of
@@ -435,11 +508,13 @@ def with_solves(case, replay, start, n_steps, torch, min_it=0, method="bicgstab"
                     "iterations_max": max(its["knp"]), **info["knp"]}}
 
 
-def run_dg(args, torch, steps=None, warmup=None, cpu=True, dist=None, rank=0, world=1, solves=None):
+def run_dg(args, torch, steps=None, warmup=None, cpu=True, dist=None, rank=0, world=1, solves=None, full=True, dump=None):
     """The DG(P1) + interior-penalty variant (csrc/kernels_dg.hip) on the workload's mesh: one step =
     membrane ODE sweep over the facet nodes + potential-system assembly + concentration-systems assembly + end-of-step
     update (+ the ghost-cell refresh at N > 1: x-slabs of an N times longer box, knpemi.dg.DGSlab), device-resident.
-    The timed steps hold the fields at the initial state; `with_solves` then runs whole steps with the device solves."""
+    The timed steps hold the fields at the initial state; `with_solves` then runs whole steps with the device solves.
+    `full` = False: the timed steps alone (no kernel events in them, no roofline, no solves, no CPU leg); `dump`: the
+    directory --dump-outputs writes the state after the last timed step to."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import dg_time
@@ -495,12 +570,15 @@ def run_dg(args, torch, steps=None, warmup=None, cpu=True, dist=None, rank=0, wo
         step(k)
     sync()
     dp.ode_stats()
-    dp.profile(8)             # every 8th launch of the two assembly kernels carries an event pair
+    if full:
+        dp.profile(8)         # every 8th launch of the two assembly kernels carries an event pair
     t0 = time.perf_counter()
     for k in range(steps):
         step(warmup + k)
     sync()
     elapsed = time.perf_counter() - t0
+    if dump:
+        write_outputs(dump, dg_outputs(dp), rank, world)
     n_owned_cells = dp.n_cells if slab is None else int(slab.owned_cells.sum())
     if dist is not None:
         red_dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
@@ -510,8 +588,9 @@ def run_dg(args, torch, steps=None, warmup=None, cpu=True, dist=None, rank=0, wo
         tot = torch.tensor([float(n_owned_cells)], dtype=torch.float64, device=red_dev)
         dist.all_reduce(tot)
         n_owned_cells = int(tot.item())
-    dp.profile(False)
-    (_, emi_us), (_, knp_us) = dp.profile_read(0), dp.profile_read(1)
+    if full:
+        dp.profile(False)
+        (_, emi_us), (_, knp_us) = dp.profile_read(0), dp.profile_read(1)
     n_rhs, _, n_failed = dp.ode_stats()
     if n_failed:
         raise SystemExit("LSODA failed on the device")
@@ -546,12 +625,15 @@ def run_dg(args, torch, steps=None, warmup=None, cpu=True, dist=None, rank=0, wo
                                  f"ghost dofs refreshed once per step: {slab.mode}"),
                    "state": "concentrations and potential held at the initial state in the timed steps, the membrane ODEs "
                             "stimulated (g_syn = 10 for x < 20 um); whole steps with the device solves in with_solves"},
+        "ode": {"rhs_evals_per_dof_per_step": n_rhs / max(1, dp.nmf * dp.nf) / steps},
+    }
+    if not full:
+        return out
+    out.update({
         "roofline": roof(1, "dg_knp_kernel" if kind == "tet" else "dg_knp_hex_kernel", knp_us),
         "roofline_potential_kernel": roof(0, "dg_emi_kernel" if kind == "tet" else "dg_emi_hex_kernel", emi_us),
         "kernels_us_per_step": {("dg_emi_kernel" if kind == "tet" else "dg_emi_hex_kernel"): emi_us,
-                                ("dg_knp_kernel" if kind == "tet" else "dg_knp_hex_kernel"): knp_us},
-        "ode": {"rhs_evals_per_dof_per_step": n_rhs / max(1, dp.nmf * dp.nf) / steps},
-    }
+                                ("dg_knp_kernel" if kind == "tet" else "dg_knp_hex_kernel"): knp_us}})
     n_solve = getattr(args, "solve_steps", 0)
     if world == 1 and (cpu if solves is None else solves) and n_solve > 0 and dp.n <= 1_400_000:
         # whole DG time steps: the two systems solved on the device (CG / BiCGStab + auxiliary-space AMG at the reference's
@@ -666,9 +748,11 @@ def load_kernel_trace(workload, kernel, variant="cg"):
     return None
 
 
-def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, spike=True, traj_min=0):
+def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, spike=True, traj_min=0, full=True, dump=None):
     """One workload on the recorded trajectory: median-timed window, per-kernel durations, row kernels alone.  Returns
-    (line fragment for rank 0, replay, case)."""
+    (line fragment for rank 0, replay, case).  `full` = False: the trajectory up to the end of the window and the timed
+    windows alone, without kernel events in them; `dump`: the directory --dump-outputs writes the state after the last
+    timed step to."""
     import numpy as np
     from knpemi import _lib as L
     case, stepper, halo = build_problem(workload, args, rank, world)
@@ -706,7 +790,7 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
 
     # ---- untimed trajectory pass: whole steps with the device Krylov solves from t = 0.  A failure here (a solve that
     # does not converge, a communication hook) ends the bench with a non-zero exit code: there is no fallback state.
-    n_traj = max(warmup + steps + 8, traj_min)
+    n_traj = max(warmup + steps + 8, traj_min) if full else warmup + steps
     traj_its = rhs_per_step = None
     replay = None
     if not frozen:
@@ -731,35 +815,38 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
                 stepper.step(halo)
 
     # ---- untimed profiling pass over the first steps of the window: every kernel bracketed by HIP events
-    restart(warmup)
-    sync()
-    L.check(lib.knpemi_profile(dp.h, (1 << len(L.KERNEL_NAMES)) - 1))
-    n_prof = min(PROFILE_STEPS, steps)
-    run_steps(n_prof)
-    sync()
     per_kernel = {}
-    for kid, name in enumerate(L.KERNEL_NAMES):
-        n, ms = C.c_int64(), C.c_double()
-        L.check(lib.knpemi_profile_read(dp.h, kid, C.byref(n), C.byref(ms)))
-        if n.value:
-            per_kernel[name] = ms.value / n.value * 1e3 * (n.value / n_prof)   # us per step (all launches)
-    L.check(lib.knpemi_profile(dp.h, 0))
-    rows = {k: v for k, v in per_kernel.items() if k in ("emi_rows_kernel", "knp_rows_kernel")}
-    dominant = max(rows, key=rows.get) if rows else "emi_rows_kernel"
-    dom_id = L.KERNEL_NAMES.index(dominant)
+    dom_id = None
+    if full:
+        restart(warmup)
+        sync()
+        L.check(lib.knpemi_profile(dp.h, (1 << len(L.KERNEL_NAMES)) - 1))
+        n_prof = min(PROFILE_STEPS, steps)
+        run_steps(n_prof)
+        sync()
+        for kid, name in enumerate(L.KERNEL_NAMES):
+            n, ms = C.c_int64(), C.c_double()
+            L.check(lib.knpemi_profile_read(dp.h, kid, C.byref(n), C.byref(ms)))
+            if n.value:
+                per_kernel[name] = ms.value / n.value * 1e3 * (n.value / n_prof)   # us per step (all launches)
+        L.check(lib.knpemi_profile(dp.h, 0))
+        rows = {k: v for k, v in per_kernel.items() if k in ("emi_rows_kernel", "knp_rows_kernel")}
+        dominant = max(rows, key=rows.get) if rows else "emi_rows_kernel"
+        dom_id = L.KERNEL_NAMES.index(dominant)
     stride = int(os.environ.get("KNPEMI_BENCH_PROFILE_STRIDE", "8"))
 
     # ---- timed windows.  One window = EXACTLY `steps` steps, trajectory steps [first, first + steps), between
     # barrier + synchronize on both sides; the state is put back to the start of the window before every repeat and
-    # `value` comes from the MEDIAN window.  Only the dominant row kernel keeps an event pair,
-    # on every 8th launch (an event pair on the critical path costs the step several microseconds).
+    # `value` comes from the MEDIAN window.  With --full the dominant row kernel keeps an event
+    # pair, on every 8th launch (an event pair on the critical path costs the step several microseconds).
     def timed_windows(first, reps):
         times, enq = [], []
         dom_n, dom_ms, n_rhs, n_lsoda = 0, 0.0, 0, 0
         for _ in range(reps):
             restart(first)
-            L.check(lib.knpemi_profile(dp.h, 1 << dom_id))
-            L.check(lib.knpemi_set_option(dp.h, L.OPT_PROFILE_STRIDE, stride))
+            if dom_id is not None:
+                L.check(lib.knpemi_profile(dp.h, 1 << dom_id))
+                L.check(lib.knpemi_set_option(dp.h, L.OPT_PROFILE_STRIDE, stride))
             ode_counters(case, dp)                      # reset
             sync()
             t0 = time.perf_counter()
@@ -773,19 +860,22 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
             if nf:
                 raise SystemExit("LSODA failed on the device")
             n_rhs, n_lsoda = n_rhs + nr, n_lsoda + ns
-            n, ms = C.c_int64(), C.c_double()
-            L.check(lib.knpemi_profile_read(dp.h, dom_id, C.byref(n), C.byref(ms)))
-            dom_n, dom_ms = dom_n + n.value, dom_ms + ms.value
-            L.check(lib.knpemi_profile(dp.h, 0))
-            L.check(lib.knpemi_set_option(dp.h, L.OPT_PROFILE_STRIDE, 1))
+            if dom_id is not None:
+                n, ms = C.c_int64(), C.c_double()
+                L.check(lib.knpemi_profile_read(dp.h, dom_id, C.byref(n), C.byref(ms)))
+                dom_n, dom_ms = dom_n + n.value, dom_ms + ms.value
+                L.check(lib.knpemi_profile(dp.h, 0))
+                L.check(lib.knpemi_set_option(dp.h, L.OPT_PROFILE_STRIDE, 1))
         return dict(times=times, median=float(np.median(times)), enqueue=float(np.median(enq)),
                     dom_us=dom_ms / max(dom_n, 1) * 1e3, rhs=n_rhs / reps, lsoda=n_lsoda / reps)
 
     main_w = timed_windows(warmup, repeats)
+    if dump:        # the device holds the state after the last step of the window (every repeat replays the same steps)
+        write_outputs(dump, cg_outputs(case, dp), rank, world)
     # the same window with A_knp assembled twice per step, as the reference does it (p = a: knpWeakForm.py:319, the second
     # assembly at pdeSolver.py:131-139; BASELINE.md section 2 and SURVEY section 8d promise both figures)
     twice_w = None
-    if not args.knp_twice:
+    if full and not args.knp_twice:
         stepper.assemble_knp_twice = True
         twice_w = timed_windows(warmup, max(3, repeats // 2))
         stepper.assemble_knp_twice = False
@@ -793,7 +883,7 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
     # the wave that integrates it: the sweep is as slow as its slowest wave).  Found with an untimed replay of the whole
     # trajectory, the sweep bracketed by events and read back after every step.
     spike_w = spike_first = ode_us_per_step = None
-    if spike and replay is not None and replay.n >= steps:
+    if full and spike and replay is not None and replay.n >= steps:
         kid = L.KERNEL_NAMES.index("ode_step_kernel")
         restart(0)
         L.check(lib.knpemi_profile(dp.h, 1 << kid))
@@ -829,23 +919,24 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
     # kernels reach alone (`roofline_row_kernels_alone`); the step times above are the overlapped schedule's.
     alone = {}
     overlapped = bool(stepper.overlap)
-    restart(warmup)
-    stepper.overlap = False
-    # (the facet kernel as a launch of its own in this pass: in the timed steps its work rides in the launch that writes the
-    # potential back, KNPEMI_OPT_FOLD_MEMBRANE)
-    L.check(lib.knpemi_set_option(dp.h, L.OPT_FOLD_MEMBRANE, 0))
-    L.check(lib.knpemi_profile(dp.h, (1 << L.KERNEL_NAMES.index("emi_rows_kernel")) | (1 << L.KERNEL_NAMES.index("knp_rows_kernel"))
-                               | (1 << L.KERNEL_NAMES.index("knp_membrane_kernel"))))
-    run_steps(min(8, steps))
-    sync()
-    L.check(lib.knpemi_set_option(dp.h, L.OPT_FOLD_MEMBRANE, 1))
-    for name in ("emi_rows_kernel", "knp_rows_kernel", "knp_membrane_kernel"):
-        n, ms = C.c_int64(), C.c_double()
-        L.check(lib.knpemi_profile_read(dp.h, L.KERNEL_NAMES.index(name), C.byref(n), C.byref(ms)))
-        if n.value:
-            alone[name] = ms.value / n.value * 1e3
-    L.check(lib.knpemi_profile(dp.h, 0))
-    stepper.overlap = overlapped
+    if full:
+        restart(warmup)
+        stepper.overlap = False
+        # (the facet kernel as a launch of its own in this pass: in the timed steps its work rides in the launch that writes
+        # the potential back, KNPEMI_OPT_FOLD_MEMBRANE)
+        L.check(lib.knpemi_set_option(dp.h, L.OPT_FOLD_MEMBRANE, 0))
+        L.check(lib.knpemi_profile(dp.h, (1 << L.KERNEL_NAMES.index("emi_rows_kernel")) | (1 << L.KERNEL_NAMES.index("knp_rows_kernel"))
+                                   | (1 << L.KERNEL_NAMES.index("knp_membrane_kernel"))))
+        run_steps(min(8, steps))
+        sync()
+        L.check(lib.knpemi_set_option(dp.h, L.OPT_FOLD_MEMBRANE, 1))
+        for name in ("emi_rows_kernel", "knp_rows_kernel", "knp_membrane_kernel"):
+            n, ms = C.c_int64(), C.c_double()
+            L.check(lib.knpemi_profile_read(dp.h, L.KERNEL_NAMES.index(name), C.byref(n), C.byref(ms)))
+            if n.value:
+                alone[name] = ms.value / n.value * 1e3
+        L.check(lib.knpemi_profile(dp.h, 0))
+        stepper.overlap = overlapped
 
     owned = getattr(s, "owned_dofs", None)
     dofs_local = 3 * (owned if owned is not None else int(dp.n_vert.sum()))
@@ -858,30 +949,8 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
         dofs_total = dofs_local
     out = None
     if rank == 0:
-        survey_b, design_b, sizes = algorithmic_bytes(case, dp)
         n_ode_dofs = sum(m.nodes for m, _, _ in case.models)
-        traffic_file, traffic = load_traffic(workload) if world == 1 else (None, {})
-
-        def roof(kernel, us):
-            tr = traffic.get(kernel)
-            by_counters = (2.0 * tr["FETCH_SIZE_KiB"] + tr["WRITE_SIZE_KiB"]) * 1024.0 if tr else None
-            ach = survey_b[kernel] / (us * 1e-6) / 1e9
-            return {"bound": "hbm", "kernel": kernel, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": ach / HBM_PEAK_GBS, "traffic": by_counters, "traffic_source": traffic_file if tr else None,
-                    # the same launch priced with the bytes the PMC counters saw instead of the SURVEY accounting
-                    "frac_by_counters": by_counters / (us * 1e-6) / 1e9 / HBM_PEAK_GBS if by_counters else None,
-                    "algorithmic_bytes_per_launch": survey_b[kernel], "avg_launch_us": us,
-                    "kernel_trace": load_kernel_trace(workload, kernel) if world == 1 else None,
-                    "bytes_this_design_touches": design_b[kernel],
-                    "frac_of_design_bytes": design_b[kernel] / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                    # a launch cannot be shorter than the launch floor: the fraction of peak a perfect kernel would
-                    # reach at this size (1.0 = large enough for HBM to be the bound)
-                    "launch_floor_us": LAUNCH_FLOOR_US,
-                    "frac_at_launch_floor": min(1.0, survey_b[kernel] / (LAUNCH_FLOOR_US * 1e-6) / 1e9 / HBM_PEAK_GBS)}
         med = main_w["median"]
-        mem_us = alone.pop("knp_membrane_kernel", 0.0)        # the facet kernel as its own launch (untimed pass above)
-        if "knp_membrane_kernel" in per_kernel:               # in the timed steps: phi write-back + facet integrals, one launch
-            per_kernel["emi_writeback_membrane_kernel"] = per_kernel.pop("knp_membrane_kernel")
         out = {
             "value": dofs_total / (med / steps), "unit": "dofs/s", "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": med / steps * 1e3,
@@ -893,7 +962,7 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
                        "max_ms_per_step": max(main_w["times"]) / steps * 1e3},
             "host_enqueue_ms_per_step": main_w["enqueue"] / steps * 1e3,
             "config": {"workload": f"{workload}: make_mesh_3D geometry r={case.r}, {case.kind}, "
-                                   f"{sizes['nc']} cells/GPU, {sizes['N']} sub-mesh vertices/GPU in "
+                                   f"{int(dp.n_cell.sum())} cells/GPU, {int(dp.n_vert.sum())} sub-mesh vertices/GPU in "
                                    f"{len(s.subdomain_list)} sub-domains, {n_ode_dofs} membrane ODE dofs/GPU, 3 ions "
                                    f"(K, Cl, Na eliminated), {case.describe}",
                        "dofs_per_step": dofs_total, "A_knp_assemblies_per_step": 2 if args.knp_twice else 1,
@@ -905,40 +974,67 @@ def measure(workload, args, torch, dist, rank, world, steps, warmup, repeats, sp
                                  f"untimed); the timed steps replay it, pasting each recorded solution where the solve "
                                  f"writes it"),
                        "partition": "x-slabs" if world > 1 else "none"},
-            "roofline": roof(dominant, main_w["dom_us"]),
-            "roofline_membrane_facet_kernel": roof("knp_membrane_kernel", mem_us) if mem_us > 0 else None,
-            "roofline_row_kernels_alone": {k: roof(k, v) for k, v in alone.items()} or None,
-            "kernels_us_per_step": per_kernel,
             "ode": {"rhs_evals_per_dof_per_step": main_w["rhs"] / max(1, n_ode_dofs) / steps,
-                    "lsoda_steps_per_dof_per_step": main_w["lsoda"] / max(1, n_ode_dofs) / steps,
-                    "kernel_us_per_step": per_kernel.get("ode_step_kernel"),
-                    "share_of_step": per_kernel.get("ode_step_kernel", 0.0) / (med / steps * 1e6)},
+                    "lsoda_steps_per_dof_per_step": main_w["lsoda"] / max(1, n_ode_dofs) / steps},
         }
-        if twice_w is not None:
-            tm = twice_w["median"]
-            out["reference_faithful_knp_assembled_twice"] = {
-                "what": "the same timed window with A_knp assembled twice per step (the reference passes p = a and "
-                        "LinearProblem assembles both: knpWeakForm.py:319, pdeSolver.py:131-139)",
-                "A_knp_assemblies_per_step": 2, "value": dofs_total / (tm / steps), "unit": "dofs/s",
-                "ms_per_step": tm / steps * 1e3, "repeats_ms_per_step": [t / steps * 1e3 for t in twice_w["times"]]}
-        if spike_w is not None:
-            sm = spike_w["median"]
-            out["spike_window"] = {
-                "what": f"the same measurement on the {steps} steps around the step with the longest ODE sweep (step "
-                        f"{int(np.argmax(ode_us_per_step))}: {max(ode_us_per_step):.0f} us): trajectory steps "
-                        f"[{spike_first}, {spike_first + steps})",
-                "ode_kernel_us_max": max(ode_us_per_step),
-                "ode_kernel_us_along_the_trajectory": [round(x, 1) for x in ode_us_per_step],
-                "ms_per_step": sm / steps * 1e3, "value": dofs_total / (sm / steps),
-                "repeats_ms_per_step": [t / steps * 1e3 for t in spike_w["times"]],
-                "ode_kernel_us_per_step": spike_w["ode_us"],
-                "rhs_evals_per_dof_per_step": spike_w["rhs"] / max(1, n_ode_dofs) / steps}
-        if rhs_per_step is not None:
-            out["ode"]["rhs_evals_per_dof_along_the_trajectory"] = [round(x, 1) for x in rhs_per_step]
         if halo is not None:
             out["config"]["halo"] = halo.mode
         if traj_its is not None:
             out["config"]["trajectory_iterations_avg"] = {k: sum(v) / max(1, len(v)) for k, v in traj_its.items()}
+    if rank != 0 or not full:
+        return out, replay, case, dofs_total
+    survey_b, design_b, _ = algorithmic_bytes(case, dp)
+    traffic_file, traffic = load_traffic(workload) if world == 1 else (None, {})
+
+    def roof(kernel, us):
+        tr = traffic.get(kernel)
+        by_counters = (2.0 * tr["FETCH_SIZE_KiB"] + tr["WRITE_SIZE_KiB"]) * 1024.0 if tr else None
+        ach = survey_b[kernel] / (us * 1e-6) / 1e9
+        return {"bound": "hbm", "kernel": kernel, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": ach / HBM_PEAK_GBS, "traffic": by_counters, "traffic_source": traffic_file if tr else None,
+                # the same launch priced with the bytes the PMC counters saw instead of the SURVEY accounting
+                "frac_by_counters": by_counters / (us * 1e-6) / 1e9 / HBM_PEAK_GBS if by_counters else None,
+                "algorithmic_bytes_per_launch": survey_b[kernel], "avg_launch_us": us,
+                "kernel_trace": load_kernel_trace(workload, kernel) if world == 1 else None,
+                "bytes_this_design_touches": design_b[kernel],
+                "frac_of_design_bytes": design_b[kernel] / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                # a launch cannot be shorter than the launch floor: the fraction of peak a perfect kernel would
+                # reach at this size (1.0 = large enough for HBM to be the bound)
+                "launch_floor_us": LAUNCH_FLOOR_US,
+                "frac_at_launch_floor": min(1.0, survey_b[kernel] / (LAUNCH_FLOOR_US * 1e-6) / 1e9 / HBM_PEAK_GBS)}
+    mem_us = alone.pop("knp_membrane_kernel", 0.0)        # the facet kernel as its own launch (untimed pass above)
+    if "knp_membrane_kernel" in per_kernel:               # in the timed steps: phi write-back + facet integrals, one launch
+        per_kernel["emi_writeback_membrane_kernel"] = per_kernel.pop("knp_membrane_kernel")
+    ode = out.pop("ode")
+    out.update({
+        "roofline": roof(dominant, main_w["dom_us"]),
+        "roofline_membrane_facet_kernel": roof("knp_membrane_kernel", mem_us) if mem_us > 0 else None,
+        "roofline_row_kernels_alone": {k: roof(k, v) for k, v in alone.items()} or None,
+        "kernels_us_per_step": per_kernel,
+        "ode": {**ode, "kernel_us_per_step": per_kernel.get("ode_step_kernel"),
+                "share_of_step": per_kernel.get("ode_step_kernel", 0.0) / (med / steps * 1e6)},
+    })
+    if twice_w is not None:
+        tm = twice_w["median"]
+        out["reference_faithful_knp_assembled_twice"] = {
+            "what": "the same timed window with A_knp assembled twice per step (the reference passes p = a and "
+                    "LinearProblem assembles both: knpWeakForm.py:319, pdeSolver.py:131-139)",
+            "A_knp_assemblies_per_step": 2, "value": dofs_total / (tm / steps), "unit": "dofs/s",
+            "ms_per_step": tm / steps * 1e3, "repeats_ms_per_step": [t / steps * 1e3 for t in twice_w["times"]]}
+    if spike_w is not None:
+        sm = spike_w["median"]
+        out["spike_window"] = {
+            "what": f"the same measurement on the {steps} steps around the step with the longest ODE sweep (step "
+                    f"{int(np.argmax(ode_us_per_step))}: {max(ode_us_per_step):.0f} us): trajectory steps "
+                    f"[{spike_first}, {spike_first + steps})",
+            "ode_kernel_us_max": max(ode_us_per_step),
+            "ode_kernel_us_along_the_trajectory": [round(x, 1) for x in ode_us_per_step],
+            "ms_per_step": sm / steps * 1e3, "value": dofs_total / (sm / steps),
+            "repeats_ms_per_step": [t / steps * 1e3 for t in spike_w["times"]],
+            "ode_kernel_us_per_step": spike_w["ode_us"],
+            "rhs_evals_per_dof_per_step": spike_w["rhs"] / max(1, n_ode_dofs) / steps}
+    if rhs_per_step is not None:
+        out["ode"]["rhs_evals_per_dof_along_the_trajectory"] = [round(x, 1) for x in rhs_per_step]
     return out, replay, case, dofs_total
 
 
@@ -947,8 +1043,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="repeats of the timed window (state restored before each); `value` is the median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repeats of the timed window (state restored before each); `value` is the median (default: 1, "
+                         "7 with --full)")
     ap.add_argument("--workload", default="config2", choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = box length proportional to N (config 2 per GPU), strong = the fixed config-3 box "
@@ -973,7 +1070,16 @@ def main():
                          "row kernels are HBM-bound rather than launch-bound)")
     ap.add_argument("--knp-twice", action="store_true",
                     help="assemble A_knp twice per step as the reference does (p = a, knpWeakForm.py:319)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed window: per-kernel profile and roofline figures, the window with A_knp assembled "
+                         "twice, the spike window, with_solves, the CPU baselines and their agreement check, the config3 "
+                         "leg and the DG variants (--cpu-steps, --solve-steps, --no-dg and --no-config3 apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step (fields, membrane ODE tables, the systems assembled in "
+                         "that step) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher (the reference is started with plain `mpirun` on an unchanged script,
@@ -1014,7 +1120,7 @@ def main():
             dist.init_process_group(backend)
 
     if args.variant == "dg":
-        out = run_dg(args, torch, dist=dist, rank=rank, world=world)
+        out = run_dg(args, torch, dist=dist, rank=rank, world=world, full=args.full, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps(out))
         if dist is not None:
@@ -1026,7 +1132,8 @@ def main():
 
     # the trajectory is long enough to contain the action potential of the stimulated end of the cell (SPIKE_SEARCH)
     out, replay, case, dofs_total = measure(args.workload, args, torch, dist, rank, world, args.steps, args.warmup,
-                                            args.repeats, spike=not args.frozen_state, traj_min=SPIKE_SEARCH)
+                                            args.repeats, spike=not args.frozen_state, traj_min=SPIKE_SEARCH, full=args.full,
+                                            dump=args.dump_outputs)
     if rank == 0:
         out = {"metric": "assembled dofs/s (volume + membrane-facet assembly + membrane ODE sweep) per timestep; "
                          "3D idealized mesh, fp64",
@@ -1035,7 +1142,7 @@ def main():
                "dtype": "f64", "data": "synthetic",
                **{k: v for k, v in out.items() if k not in ("value", "unit", "n_gpus", "steps", "warmup", "ms_per_step")}}
     ws = ws_min = ws_ref = None
-    if args.solve_steps > 0 and replay is not None:      # collective at N > 1: every rank takes part
+    if args.full and args.solve_steps > 0 and replay is not None:      # collective at N > 1: every rank takes part
         ws = with_solves(case, replay, WITH_SOLVES_START, args.solve_steps, torch)
         # the same with the reference's ksp_min_it = 5 of the concentration solve (pdeSolver.py:101): five GMRES iterations
         # apply operator and preconditioner five times, three BiCGStab iterations six times
@@ -1075,7 +1182,7 @@ def main():
                     **{k: ws_ref[k] for k in ("ms_per_step", "steps", "knp_min_iterations", "knp_method")},
                     "emi_iterations_avg": ws_ref["emi"]["iterations_avg"], "knp_iterations_avg": ws_ref["knp"]["iterations_avg"]}
         s = case.s
-        if args.cpu_steps > 0 and world == 1 and case.family == "idealized":
+        if args.full and args.cpu_steps > 0 and world == 1 and case.family == "idealized":
             avail = len(os.sched_getaffinity(0))
             # bounded sample: --cpu-steps refers to the config-2 size and shrinks with the problem size
             n_all = max(3, int(round(args.cpu_steps * min(1.0, 79251.0 / dofs_total))))
@@ -1119,7 +1226,7 @@ def main():
                           + "; one thread, as the reference's serial run"}
     tet = case.family == "idealized" and case.kind == "tet"
     del replay, case
-    if world == 1 and tet and args.workload == "config2" and not args.no_config3 and not args.frozen_state:
+    if args.full and world == 1 and tet and args.workload == "config2" and not args.no_config3 and not args.frozen_state:
         # The 995 328-tet mesh of BASELINE configs[2] on this one GPU: config 2 is launch-bound (a perfect row kernel
         # reaches < 0.5 of the HBM peak at the launch floor), this is the size at which the roofline fraction says
         # something about the kernels.  Same measurement, shorter: no spike window, no solves pass, no CPU leg.
@@ -1129,7 +1236,7 @@ def main():
                                                    "kernels_us_per_step", "ode", "reference_faithful_knp_assembled_twice")
                               if k in leg}
     if rank == 0:
-        if world == 1 and not args.no_dg and tet:
+        if args.full and world == 1 and not args.no_dg and tet:
             dg = run_dg(args, torch, steps=10, warmup=2, cpu=False, solves=True)
             out["dg_variant"] = {k: dg[k] for k in ("value", "unit", "ms_per_step", "config", "roofline",
                                                      "roofline_potential_kernel", "kernels_us_per_step", "with_solves")}

@@ -4,7 +4,7 @@
 # --kernel-trace only; the per-launch averages go to profiles/rNN_traffic.json (tools/traffic_summary.py applies the
 # gfx950 correction when bench.py reads them: bytes = 2 * FETCH_SIZE + WRITE_SIZE, KiB units).
 # usage (on the GPU box): tools/collect_traffic.sh <workload> [cg | dg [tetrahedron|hexahedron [general]]]
-#   cg: bench.py --workload <workload>;  dg: tools/dg_time.py -r <workload's refinement, e.g. r2> --cell <cell>
+#   cg: bench.py --full --workload <workload>;  dg: tools/dg_time.py -r <workload's refinement, e.g. r2> --cell <cell>
 set -e
 W=${1:-config2}; MODE=${2:-cg}; CELL=${3:-tetrahedron}; GEN=${4:-}
 cd /tmp && export TMPDIR=/tmp
@@ -19,7 +19,7 @@ for c in FETCH_SIZE WRITE_SIZE TCC_HIT_sum TCC_MISS_sum; do
         python3 $R/tools/dg_time.py -r ${W#r} --cell $CELL --reps 3 > $OUT.$c.log 2>&1 || echo "pass $c failed"
   else
     timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$c -- \
-        python3 $R/bench.py --workload $W --steps 5 --warmup 2 --repeats 1 --cpu-steps 0 --solve-steps 0 --no-dg --no-config3 > $OUT.$c.log 2>&1 || echo "pass $c failed"
+        python3 $R/bench.py --full --workload $W --steps 5 --warmup 2 --repeats 1 --cpu-steps 0 --solve-steps 0 --no-dg --no-config3 > $OUT.$c.log 2>&1 || echo "pass $c failed"
   fi
   echo "pass $c done"
 done

@@ -33,12 +33,12 @@ def line(path):
 
 rows = []
 # ---- kernel statistics ------------------------------------------------------------------------------------------
-for wl, cmd in (("driver", "python3 bench.py --steps 20 --warmup 5` (the driver's command: three legs in one process -- config 2, the 995 k-tet mesh, the DG variants -- so a kernel's row mixes their launches; the per-leg files follow)"),
-                ("config2", "python3 bench.py --steps 20 --warmup 5 --cpu-steps 0 --no-config3 --no-dg` (config 2 only: one population per kernel)"),
-                ("config3", "python3 bench.py --workload config3 --steps 20 --warmup 5 --cpu-steps 0 --solve-steps 0 --no-dg`"),
-                ("config2h", "python3 bench.py --workload config2h --steps 20 --warmup 5 --cpu-steps 0 --solve-steps 0 --no-dg --no-overlap`"),
-                ("dg", "python3 bench.py --variant dg --steps 50 --warmup 5 --solve-steps 0`"),
-                ("dg_config2h", "python3 bench.py --variant dg --workload config2h --steps 20 --warmup 3 --solve-steps 0`")):
+for wl, cmd in (("driver", "python3 bench.py --full --steps 20 --warmup 5` (the driver's command: three legs in one process -- config 2, the 995 k-tet mesh, the DG variants -- so a kernel's row mixes their launches; the per-leg files follow)"),
+                ("config2", "python3 bench.py --full --steps 20 --warmup 5 --cpu-steps 0 --no-config3 --no-dg` (config 2 only: one population per kernel)"),
+                ("config3", "python3 bench.py --full --workload config3 --steps 20 --warmup 5 --cpu-steps 0 --solve-steps 0 --no-dg`"),
+                ("config2h", "python3 bench.py --full --workload config2h --steps 20 --warmup 5 --cpu-steps 0 --solve-steps 0 --no-dg --no-overlap`"),
+                ("dg", "python3 bench.py --full --variant dg --steps 50 --warmup 5 --solve-steps 0`"),
+                ("dg_config2h", "python3 bench.py --full --variant dg --workload config2h --steps 20 --warmup 3 --solve-steps 0`")):
     name = f"{ROUND}_{wl}_kernel_stats.csv"
     if not cp(last(f"{G}/{ROUND}/stats_{wl}/*/*_kernel_stats.csv"), name):
         continue
@@ -52,15 +52,15 @@ for wl, cmd in (("driver", "python3 bench.py --steps 20 --warmup 5` (the driver'
     rows.append((f"`{name}`", f"`rocprofv3 --kernel-trace --stats --output-format csv -- {cmd}", "; ".join(picks[:14])))
 
 # ---- bench lines ------------------------------------------------------------------------------------------------
-for f, cmd in (("bench_config2", "python bench.py --steps 20 --warmup 5"),
-               ("bench_config3", "python bench.py --workload config3 --steps 20 --warmup 5 --cpu-steps 0 --no-dg"),
-               ("bench_config2h", "python bench.py --workload config2h --steps 20 --warmup 5 --cpu-steps 0 --no-dg"),
-               ("bench_config5s", "python bench.py --workload config5s --steps 20 --warmup 5 --cpu-steps 0 --no-dg"),
-               ("bench_r3", "python bench.py --workload r3 --steps 10 --warmup 5 --repeats 3 --cpu-steps 0 --solve-steps 0 --no-dg"),
-               ("bench_dg_config3", "python bench.py --variant dg --workload config3 --steps 20 --warmup 3"),
-               ("bench_dg_config2h", "python bench.py --variant dg --workload config2h --steps 20 --warmup 3 --solve-steps 0"),
-               ("bench_dg_config2h_general_kernels", "KNPEMI_DG_HEX_GENERAL=1 python bench.py --variant dg --workload config2h --steps 20 --warmup 3 --solve-steps 0"),
-               ("bench_config2_plain_solver_loops", "KNPEMI_NO_FUSED=1 python bench.py --steps 20 --warmup 5 --cpu-steps 0 --no-dg --no-config3")):
+for f, cmd in (("bench_config2", "python bench.py --full --steps 20 --warmup 5"),
+               ("bench_config3", "python bench.py --full --workload config3 --steps 20 --warmup 5 --cpu-steps 0 --no-dg"),
+               ("bench_config2h", "python bench.py --full --workload config2h --steps 20 --warmup 5 --cpu-steps 0 --no-dg"),
+               ("bench_config5s", "python bench.py --full --workload config5s --steps 20 --warmup 5 --cpu-steps 0 --no-dg"),
+               ("bench_r3", "python bench.py --full --workload r3 --steps 10 --warmup 5 --repeats 3 --cpu-steps 0 --solve-steps 0 --no-dg"),
+               ("bench_dg_config3", "python bench.py --full --variant dg --workload config3 --steps 20 --warmup 3"),
+               ("bench_dg_config2h", "python bench.py --full --variant dg --workload config2h --steps 20 --warmup 3 --solve-steps 0"),
+               ("bench_dg_config2h_general_kernels", "KNPEMI_DG_HEX_GENERAL=1 python bench.py --full --variant dg --workload config2h --steps 20 --warmup 3 --solve-steps 0"),
+               ("bench_config2_plain_solver_loops", "KNPEMI_NO_FUSED=1 python bench.py --full --steps 20 --warmup 5 --cpu-steps 0 --no-dg --no-config3")):
     if not cp(os.path.join(G, ROUND, f + ".json"), f"{ROUND}_{f}.json"):
         continue
     d = line(os.path.join(P, f"{ROUND}_{f}.json"))
