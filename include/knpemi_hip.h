@@ -252,6 +252,41 @@ int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, double dt, 
 int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n_rhs, int64_t* n_steps,
                      int32_t* n_failed);
 
+/* Membrane models without a mesh: the reference's MembraneModel(ode, ct, tag, Q) steps its model over the dofs of any
+ * CG-1 space on its own (odeSolver.py:8-50; its calibration tool builds an interval mesh for nothing else).  Creates a
+ * handle with n_models membrane models of nq[i] dofs each and no PDE problem.  Model i is addressed as sub = 1 + i,
+ * model = 0 (n_models <= KNPEMI_MAX_SUB - 1).  knpemi_ode_bind, knpemi_ode_bind_source, knpemi_ode_set_tables,
+ * knpemi_ode_get_tables, knpemi_ode_set_stimulus, knpemi_ode_step, knpemi_ode_stats, knpemi_ode_advance and
+ * knpemi_destroy work on it as on a PDE handle; no other entry point takes it.  knpemi_ode_step refuses the flags that
+ * read PDE fields (KNPEMI_ODE_SET_TRACES, KNPEMI_ODE_SET_V: KNPEMI_EINVAL); its phi_M write-back goes to a buffer of
+ * the handle, and there are no ions (ion_param is read for 0 ions; pass any non-NULL pointer). */
+int knpemi_ode_create(int device, int n_models, const int32_t* nq, knpemi_handle** out);
+/* Steady-state mode of knpemi_ode_advance: after a step, a dof is still when |y_j - y_j(previous step)| <=
+ * ss_atol + ss_rtol |y_j| for every state component j; after `window` consecutive still steps it is steady and frozen. */
+typedef struct knpemi_ode_ss {
+  double ss_rtol, ss_atol;
+  int32_t window;
+} knpemi_ode_ss;
+/* n_steps successive MembraneModel.step_lsoda(dt) calls (odeSolver.py:92-127, i.e. n_steps knpemi_ode_step launches
+ * with flags = 0 over [t, t + dt], t <- t + dt from t0), bit for bit, with the LSODA state kept in registers from one
+ * step to the next; the reference's calibration tool makes exactly this loop.  The run is split into launches of a
+ * bounded length (the first one is timed and sizes the rest; KNPEMI_ODE_ADVANCE_CHUNK=n in the environment forces n
+ * steps per launch).  Works on PDE handles too; the tables are current on the device afterwards (knpemi_ode_get_tables),
+ * phi_M / I_ch of a PDE handle are not written.  The stimulus of knpemi_ode_set_stimulus is applied at every step.
+ *   rec_idx[n_rec] (n_rec <= 8): state components recorded after every `every`-th step into the host buffer
+ *     history[n_steps / every][n_rec][nq] (history may be NULL: nothing recorded);
+ *   ss: steady-state mode, or NULL for a plain run.  steps_taken[q] = the number of steps after which dof q became
+ *     steady, -1 if it did not; frozen dofs keep their state, later records repeat it;
+ *   failed_step[q]: the step on which LSODA failed for dof q (the dof is frozen at its last good state), -1 if none.
+ *     Any failure returns KNPEMI_EODE (`assert success`, odeSolver.py:121) after every output is written.
+ * steps_taken / failed_step are int32[nq] or NULL.  RHS evaluations, internal steps and failures are added to the
+ * counters knpemi_ode_stats reads. */
+int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t0, double dt, int n_steps, double rtol, double atol,
+                       const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
+                       int32_t* steps_taken, int32_t* failed_step);
+/* Diagnostics (no reference counterpart): the steps per launch the last knpemi_ode_advance of this model chose. */
+int knpemi_ode_advance_chunk(knpemi_handle* h, int sub, int model);
+
 /* Diagnostics (no reference counterpart): with KNPEMI_ODE_STAMPS=1 in the environment the sweep runs a stamped build of
  * the kernel; per workgroup 12 cycle sums (loop head, TOP, PRED, RHS, CORR, ERR up to the order selection, prologue, -,
  * order selection, new coefficients + rescaling, rest of ERR, -) and 12 counts.  Returns

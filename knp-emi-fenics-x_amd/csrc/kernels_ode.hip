@@ -124,6 +124,129 @@ int kn_launch_ode_step(knpemi_handle* h, int slot, double t0, double dt, double 
   return launch_builtin(h->cur, m.model_id, ode_dev(h), a, cf, force_waves);
 }
 
+// ---- n steps per launch (knpemi_ode_advance) -------------------------------------------------------------------
+namespace {
+
+template <class M, int LANES>
+void launch_advance_model(hipStream_t st, const OdeArgs& a, const OdeAdvArgs& v, const LsodaCoef* cf) {
+  const int per_wave = a.dpw > 0 ? a.dpw : ODE_BLOCK / LANES;
+  dim3 grid(((size_t)a.nq + per_wave - 1) / per_wave), block(ODE_BLOCK);
+  if ((size_t)grid.x > 1536) hipLaunchKernelGGL((ode_advance_kernel<M, LANES, 2>), grid, block, 0, st, a, v, cf);
+  else hipLaunchKernelGGL((ode_advance_kernel<M, LANES, 1>), grid, block, 0, st, a, v, cf);
+}
+
+int launch_advance(knpemi_handle* h, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs& v, const LsodaCoef* cf) {
+  if (m.rtc_function) return kn_rtc_advance_launch(h, m, &a, sizeof(a), &v, sizeof(v), cf);
+  switch (m.model_id) {
+    case KNPEMI_MODEL_HH_SI: launch_advance_model<ModelHHSI, 4>(h->cur, a, v, cf); break;
+    case KNPEMI_MODEL_HH_MV: launch_advance_model<ModelHHMV, 4>(h->cur, a, v, cf); break;
+    default: launch_advance_model<ModelGlial, 1>(h->cur, a, v, cf); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    kn_set_error(std::string("ode_advance_kernel: ") + hipGetErrorString(e));
+    return KNPEMI_EHIP;
+  }
+  return KNPEMI_OK;
+}
+
+// Steps per launch.  A launch of a few tens of ms at most keeps a long run from holding the device for seconds; the
+// first launch runs a few steps and is timed, the rest are sized from it.  KNPEMI_ODE_ADVANCE_CHUNK forces a size.
+constexpr int ADV_PROBE_STEPS = 8, ADV_MAX_STEPS = 2048;
+constexpr double ADV_BUDGET_MS = 25.0;
+
+struct DevBuf {   // a temporary device allocation
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+}  // namespace
+
+int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
+                   const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
+                   int32_t* steps_taken, int32_t* failed_step) {
+  KnOdeModel& m = h->ode[slot];
+  m.adv_chunk = 0;
+  if (m.nq == 0 || n_steps == 0) return KNPEMI_OK;
+  const LsodaCoef* cf = nullptr;
+  int rc = ensure_coef(h, &cf);
+  if (rc) return rc;
+  const size_t nq = (size_t)m.nq;
+  if (!m.d_adv) {   // still-step counters, steps_taken, failed_step
+    void* d = nullptr;
+    KN_HIP(hipMalloc(&d, 3 * nq * sizeof(int)));
+    h->allocs.push_back(d);
+    m.d_adv = static_cast<int*>(d);
+  }
+  OdeArgs a{};
+  a.nq = m.nq; a.q0 = h->qoff[m.sub]; a.n_stim = m.n_stim; a.flags = 0; a.v_index = -1;
+  a.model_slot = slot; a.NQtot = h->dev.NQtot; a.n_ions = 0;
+  for (int i = 0; i < 8; ++i) { a.stim_idx[i] = m.stim_idx[i]; a.stim_val[i] = m.stim_val[i]; }
+  a.dt = dt; a.rtol = rtol; a.atol = atol;
+  a.states = m.d_states; a.params = m.d_params; a.mask = m.d_mask; a.stats = m.d_stats; a.stamps = nullptr;
+  a.dpw = m.rtc_function ? 0 : dofs_per_wave(m.nq, m.n_states == 4 ? 4 : 1, m.n_stat_blocks - 1);
+  OdeAdvArgs v{};
+  v.n_rec = history ? n_rec : 0;
+  v.every = every;
+  for (int i = 0; i < v.n_rec; ++i) v.rec_idx[i] = rec_idx[i];
+  v.window = ss ? ss->window : 0;
+  v.ss_rtol = ss ? ss->ss_rtol : 0.0;
+  v.ss_atol = ss ? ss->ss_atol : 0.0;
+  v.still = m.d_adv; v.steps_taken = m.d_adv + nq; v.failed_step = m.d_adv + 2 * nq;
+  KN_HIP(hipMemsetAsync(v.still, 0, nq * sizeof(int), h->cur));
+  KN_HIP(hipMemsetAsync(v.steps_taken, 0xFF, 2 * nq * sizeof(int), h->cur));   // -1
+  const size_t n_hist = v.n_rec > 0 ? (size_t)(n_steps / every) * v.n_rec * nq : 0;
+  DevBuf hist;
+  if (n_hist) {
+    KN_HIP(hipMalloc(&hist.p, n_hist * sizeof(double)));
+    v.hist = static_cast<double*>(hist.p);
+  }
+  const char* forced_env = getenv("KNPEMI_ODE_ADVANCE_CHUNK");
+  const int forced = forced_env ? atoi(forced_env) : 0;
+  int chunk = forced > 0 ? std::min(forced, ADV_MAX_STEPS) : ADV_PROBE_STEPS;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  KN_HIP(hipEventCreate(&e0));
+  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); kn_set_error("hipEventCreate failed"); return KNPEMI_EHIP; }
+  double t = t0;
+  for (int s = 0; s < n_steps && rc == KNPEMI_OK;) {
+    const int c = std::min(chunk, n_steps - s);
+    v.s0 = s; v.n_steps = c; a.t0 = t;
+    const bool probe = s == 0 && forced <= 0;
+    if (probe && hipEventRecord(e0, h->cur) != hipSuccess) rc = KNPEMI_EHIP;
+    if (rc == KNPEMI_OK) rc = launch_advance(h, m, a, v, cf);
+    if (rc == KNPEMI_OK && probe) {
+      float ms = 0.0f;
+      if (hipEventRecord(e1, h->cur) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+          hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
+        kn_set_error("knpemi_ode_advance: timing the first launch failed");
+        rc = KNPEMI_EHIP;
+      } else {
+        const double per_step = std::max((double)ms, 1e-3) / c;
+        chunk = std::max(1, std::min(ADV_MAX_STEPS, (int)(ADV_BUDGET_MS / per_step)));
+      }
+    }
+    for (int i = 0; i < c; ++i) t = t + dt;   // the caller's t <- t + dt, step by step
+    s += c;
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (rc) return rc;
+  m.adv_chunk = chunk;
+  if (n_hist) KN_HIP(hipMemcpyAsync(history, hist.p, n_hist * sizeof(double), hipMemcpyDeviceToHost, h->cur));
+  std::vector<int32_t> flags(2 * nq);
+  KN_HIP(hipMemcpyAsync(flags.data(), v.steps_taken, 2 * nq * sizeof(int32_t), hipMemcpyDeviceToHost, h->cur));
+  KN_HIP(hipStreamSynchronize(h->cur));
+  if (steps_taken) std::copy(flags.begin(), flags.begin() + nq, steps_taken);
+  if (failed_step) std::copy(flags.begin() + nq, flags.end(), failed_step);
+  size_t n_failed = 0;
+  for (size_t q = 0; q < nq; ++q) n_failed += flags[nq + q] >= 0;
+  if (n_failed) {
+    kn_set_error("LSODA failed on " + std::to_string(n_failed) + " membrane dof(s) (odeSolver.py:121 `assert success`)");
+    return KNPEMI_EODE;
+  }
+  return KNPEMI_OK;
+}
+
 // The same sweep over a caller-described table (the DG variant, kernels_dg.hip: membrane nodes of the broken space).
 int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef) {
   return launch_builtin(st, model_id, dv, a, static_cast<const LsodaCoef*>(coef), 0);

@@ -47,6 +47,9 @@ std::string wrapper_source(int ns, int np, int lanes, const std::string& user) {
   s += "    _Pragma(\"unroll\") for (int j = 0; j < NP; ++j) p[j] = par[j];\n  }\n};\n";
   s += "extern \"C\" __global__ __launch_bounds__(ODE_BLOCK, 1) void ode_user_kernel(OdeDev D, OdeArgs a, const LsodaCoef* cf) {\n";
   s += "  ode_step_body<ModelUser, " + std::to_string(lanes) + ", 1, false>(D, a, cf);\n}\n";
+  s += "extern \"C\" __global__ __launch_bounds__(ODE_BLOCK, 1) void ode_user_advance_kernel(OdeArgs a, OdeAdvArgs v, "
+       "const LsodaCoef* cf) {\n";
+  s += "  ode_advance_body<ModelUser, " + std::to_string(lanes) + ", 1>(a, v, cf);\n}\n";
   return s;
 }
 
@@ -130,14 +133,16 @@ int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, con
   }
   hipModule_t mod = nullptr;
   KN_HIP(hipModuleLoadData(&mod, code.data()));
-  hipFunction_t fn = nullptr;
-  if (hipModuleGetFunction(&fn, mod, "ode_user_kernel") != hipSuccess) {
+  hipFunction_t fn = nullptr, fn_adv = nullptr;
+  if (hipModuleGetFunction(&fn, mod, "ode_user_kernel") != hipSuccess ||
+      hipModuleGetFunction(&fn_adv, mod, "ode_user_advance_kernel") != hipSuccess) {
     (void)hipModuleUnload(mod);
-    kn_set_error("hipModuleGetFunction(ode_user_kernel) failed");
+    kn_set_error("hipModuleGetFunction(ode_user_kernel / ode_user_advance_kernel) failed");
     return KNPEMI_EHIP;
   }
   m.rtc_module = mod;
   m.rtc_function = fn;
+  m.rtc_advance_function = fn_adv;
   m.rtc_lanes = lanes_for(n_states);
   h->rtc_modules.push_back(mod);
   return KNPEMI_OK;
@@ -155,5 +160,21 @@ int kn_rtc_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, s
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
   const unsigned grid = (unsigned)(((size_t)p.a.nq * m.rtc_lanes + ODE_BLOCK - 1) / ODE_BLOCK);
   KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_function), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur, nullptr, config));
+  return KNPEMI_OK;
+}
+
+int kn_rtc_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, size_t args_bytes, const void* adv,
+                          size_t adv_bytes, const void* coef) {
+  // kernel parameters (OdeArgs, OdeAdvArgs, const LsodaCoef*) laid out as the compiler lays out the parameter list
+  struct Params { OdeArgs a; OdeAdvArgs v; const LsodaCoef* cf; } p;
+  if (args_bytes != sizeof(OdeArgs) || adv_bytes != sizeof(OdeAdvArgs)) { kn_set_error("rtc launch: argument size mismatch"); return KNPEMI_EINVAL; }
+  std::memcpy(&p.a, args, sizeof(OdeArgs));
+  std::memcpy(&p.v, adv, sizeof(OdeAdvArgs));
+  p.cf = static_cast<const LsodaCoef*>(coef);
+  size_t size = sizeof(p);
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  const unsigned grid = (unsigned)(((size_t)p.a.nq * m.rtc_lanes + ODE_BLOCK - 1) / ODE_BLOCK);
+  KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_advance_function), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur,
+                               nullptr, config));
   return KNPEMI_OK;
 }

@@ -954,6 +954,54 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   return KNPEMI_OK;
 }
 
+extern "C" int knpemi_ode_create(int device, int n_models, const int32_t* nq, knpemi_handle** out) {
+  if (!out || !nq) return fail(KNPEMI_EINVAL, "knpemi_ode_create: null argument");
+  *out = nullptr;
+  if (n_models < 1 || n_models > KN_MAXSUB - 1)
+    return fail(KNPEMI_EINVAL, "knpemi_ode_create: 1 to KNPEMI_MAX_SUB - 1 membrane models");
+  for (int i = 0; i < n_models; ++i)
+    if (nq[i] < 0) return fail(KNPEMI_EINVAL, "knpemi_ode_create: negative dof count");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(KNPEMI_EHIP, "knpemi_ode_create: no HIP device visible (the hot path has no CPU fallback)");
+  if (device < 0 || device >= ndev) return fail(KNPEMI_EINVAL, "knpemi_ode_create: bad device index");
+  KN_HIP(hipSetDevice(device));
+  auto* h = new knpemi_handle();
+  std::unique_ptr<knpemi_handle, void (*)(knpemi_handle*)> guard(h, knpemi_destroy);
+  h->device = device;
+  h->ode_only = true;
+  KN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  KN_HIP(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
+  KN_HIP(hipStreamCreateWithFlags(&h->aux2, hipStreamNonBlocking));
+  KN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+  KN_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+  KN_HIP(hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming));
+  KN_HIP(hipEventCreate(&h->ev0));
+  KN_HIP(hipEventCreate(&h->ev1));
+  h->cur = h->stream;
+  // sub-domain 0 stands for the absent extracellular space; model i is the one model of sub-domain 1 + i
+  const int S = n_models + 1;
+  h->n_sub = S; h->K = 0;
+  h->n_vert.assign(S, 0); h->n_cell.assign(S, 0); h->n_facet.assign(S, 0);
+  h->n_q.assign(S, 0); h->n_models.assign(S, 0);
+  for (int i = 0; i < n_models; ++i) { h->n_q[1 + i] = nq[i]; h->n_models[1 + i] = 1; }
+  auto prefix = [&](const std::vector<int>& n) {
+    std::vector<int> o(S + 1, 0);
+    for (int s = 0; s < S; ++s) o[s + 1] = o[s] + n[s];
+    return o;
+  };
+  h->voff = prefix(h->n_vert); h->coff = prefix(h->n_cell); h->qoff = prefix(h->n_q);
+  h->foff = prefix(h->n_facet); h->moff = prefix(h->n_models);
+  h->ode.resize(h->moff[S]);
+  KnDev& D = h->dev;
+  D.NQtot = h->qoff[S];
+  int rc;
+  if ((rc = dev_zeros(h, (size_t)std::max(1, D.NQtot), &D.phiM))) return rc;                          // phi_M write-back
+  if ((rc = dev_zeros(h, (size_t)n_models * KN_MAXK * std::max(1, D.NQtot), &D.Ich))) return rc;      // (no ions: unused)
+  *out = guard.release();
+  return KNPEMI_OK;
+}
+
 extern "C" void knpemi_destroy(knpemi_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
@@ -1602,6 +1650,8 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
   if (v_index < 0 || v_index >= m.n_states) return fail(KNPEMI_EINVAL, "knpemi_ode_step: bad V index");
   if (!(dt > 0) || !(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))
     return fail(KNPEMI_EINVAL, "knpemi_ode_step: bad dt / tolerances");
+  if (h->ode_only && (flags & (KNPEMI_ODE_SET_TRACES | KNPEMI_ODE_SET_V)))
+    return fail(KNPEMI_EINVAL, "knpemi_ode_step: a handle of knpemi_ode_create has no PDE fields to read");
   KN_HIP(hipSetDevice(h->device));
   h->gam_valid = false;      // phi_M and the channel currents change
   if (flags & (KNPEMI_ODE_ON_AUX_STREAM | KNPEMI_ODE_ON_AUX2_STREAM)) {
@@ -1617,6 +1667,39 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
     return KNPEMI_OK;
   }
   return kn_launch_ode_step(h, slot, t0, dt, rtol, atol, flags, ion_param, v_index);
+}
+
+extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t0, double dt, int n_steps, double rtol,
+                                  double atol, const int32_t* rec_idx, int n_rec, int every, double* history,
+                                  const knpemi_ode_ss* ss, int32_t* steps_taken, int32_t* failed_step) {
+  int slot = ode_slot(h, sub, model, 1);
+  if (slot < 0) return KNPEMI_EINVAL;
+  const KnOdeModel& m = h->ode[slot];
+  if (n_steps < 0 || !(dt > 0) || !(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))
+    return fail(KNPEMI_EINVAL, "knpemi_ode_advance: bad n_steps / dt / tolerances");
+  if (history) {
+    if (every < 1 || n_rec < 1 || n_rec > 8 || !rec_idx)
+      return fail(KNPEMI_EINVAL, "knpemi_ode_advance: recording needs every >= 1 and 1..8 state indices");
+    for (int i = 0; i < n_rec; ++i)
+      if (rec_idx[i] < 0 || rec_idx[i] >= m.n_states)
+        return fail(KNPEMI_EINVAL, "knpemi_ode_advance: recorded state index out of range");
+  } else {
+    every = 1;
+  }
+  if (ss && (ss->window < 1 || !(ss->ss_rtol >= 0) || !(ss->ss_atol >= 0)))
+    return fail(KNPEMI_EINVAL, "knpemi_ode_advance: steady-state window >= 1 and tolerances >= 0");
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->aux));   // a sweep of this model may still run on an auxiliary stream
+  KN_HIP(hipStreamSynchronize(h->aux2));
+  h->gam_valid = false;
+  return kn_ode_advance(h, slot, t0, dt, n_steps, rtol, atol, rec_idx, n_rec, every, history, ss, steps_taken,
+                        failed_step);
+}
+
+extern "C" int knpemi_ode_advance_chunk(knpemi_handle* h, int sub, int model) {
+  int slot = ode_slot(h, sub, model, 1);
+  if (slot < 0) return KNPEMI_EINVAL;
+  return h->ode[slot].adv_chunk;
 }
 
 extern "C" int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n_rhs, int64_t* n_steps, int32_t* n_failed) {

@@ -127,7 +127,10 @@ struct KnOdeModel {
   // model compiled at bind time from the plug-in's HIP source (kernels_rtc.hip); NULL for the shipped models
   void* rtc_module = nullptr;
   void* rtc_function = nullptr;
+  void* rtc_advance_function = nullptr;   // its multi-step entry (ode_user_advance_kernel)
   int rtc_lanes = 1;
+  int* d_adv = nullptr;                   // [3][nq] knpemi_ode_advance: still-step counters, steps_taken, failed_step
+  int adv_chunk = 0;                      // steps per launch the last knpemi_ode_advance chose
 };
 
 // blocks of the dense coarsest-level inverse, passed to the kernels by value: block b covers the unknowns start[b] ..
@@ -293,6 +296,7 @@ struct knpemi_handle {
   std::vector<void*> allocs;  // everything hipMalloc'ed
   std::vector<void*> rtc_modules;   // hipModule_t of run-time compiled membrane models
   std::vector<KnOdeModel> ode; // [moff[n_sub]]
+  bool ode_only = false;       // knpemi_ode_create: membrane models without a mesh (no PDE fields)
   // host copies of patterns for export
   std::vector<int> h_rowptr, h_colind, h_rowptrL, h_colindL;
   void* comm = nullptr;                              // RCCL communicator (comm_rccl.hip), NULL until knpemi_comm_init
@@ -406,6 +410,11 @@ int kn_launch_update_pde(knpemi_handle* h);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 int kn_rtc_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, size_t dev_bytes, const void* args,
                   size_t args_bytes, const void* coef);
+int kn_rtc_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, size_t args_bytes, const void* adv,
+                          size_t adv_bytes, const void* coef);
+int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
+                   const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
+                   int32_t* steps_taken, int32_t* failed_step);
 int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);
 int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);
 int kn_extrapolate_guess(knpemi_handle* h, int which);

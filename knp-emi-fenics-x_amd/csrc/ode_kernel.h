@@ -33,6 +33,20 @@ struct OdeArgs {
   unsigned long long* stamps;   // diagnostic build: [workgroup][24] phase cycle sums and counts
 };
 
+// the extra arguments of the multi-step launch (ode_advance_body); the steps run with flags = 0
+struct OdeAdvArgs {
+  int n_steps;           // steps of this launch
+  int s0;                // index of its first step within the whole run (records, steps_taken, failed_step)
+  int n_rec, every;      // record states rec_idx[0..n_rec) after every `every`-th step of the run
+  int rec_idx[8];
+  double* hist;          // [run step / every][n_rec][nq], or NULL
+  int window;            // steady-state mode: a dof is steady after `window` consecutive still steps (0: plain run)
+  double ss_rtol, ss_atol;
+  int* still;            // [nq] still steps in a row so far (carried from launch to launch)
+  int* steps_taken;      // [nq] -1, or the number of steps after which the dof was declared steady
+  int* failed_step;      // [nq] -1, or the step on which LSODA failed
+};
+
 #define KN_ODE_SET_V 1        // == KNPEMI_ODE_SET_V
 #define KN_ODE_SET_TRACES 2   // == KNPEMI_ODE_SET_TRACES
 
@@ -152,6 +166,130 @@ __device__ __forceinline__ void ode_step_body(const OdeDev& D, const OdeArgs& a,
   }
 }
 
+
+// n_steps consecutive knpemi_ode_step intervals [t, t + dt], t <- t + dt (the caller's time arithmetic), in one launch.
+// Every interval is a fresh LSODA integration in the order of ode_step_body with flags = 0 (stimulus into the parameter
+// row, prepare, integrate, finish) and with its lane layout, so the result is bit for bit that of n_steps sweeps; only
+// the state stays in registers from one step to the next.  This is a separate body, not a loop around ode_step_body: the
+// production sweep's code generation stays exactly as it is.
+// A dof is frozen -- no longer integrated, its state kept -- once it is steady (window > 0) or after an LSODA failure
+// (its last good state is kept); a wave ends its launch when all its dofs are frozen.
+template <class M, int LANES, int WAVES>
+__device__ __forceinline__ void ode_advance_body(const OdeArgs& a, const OdeAdvArgs& v, const LsodaCoef* __restrict__ cf) {
+  using Integrator = Lsoda<M::NS, M, LANES, false, ODE_BLOCK>;
+  constexpr int NI = Integrator::NI;
+  __shared__ double work[Integrator::WORK * ODE_BLOCK];
+  __shared__ LsodaCoef scf;
+  {
+    const double* src = reinterpret_cast<const double*>(cf);
+    double* dst = reinterpret_cast<double*>(&scf);
+    for (int i = threadIdx.x; i < (int)(sizeof(LsodaCoef) / sizeof(double)); i += ODE_BLOCK) dst[i] = src[i];
+    __syncthreads();
+  }
+  // lane layout of ode_step_body: `dpw` dofs per wave, the other lanes mirror them; lanes past the last dof repeat it
+  constexpr int FULL = ODE_BLOCK / LANES;
+  const int dpw = (a.dpw > 0 && a.dpw < FULL) ? a.dpw : FULL;
+  const int lane_in = threadIdx.x % (dpw * LANES);
+  const bool primary = threadIdx.x < dpw * LANES;
+  const int qw = blockIdx.x * dpw + lane_in / LANES;
+  const bool live = primary && qw < a.nq;
+  const int q = qw < a.nq ? qw : a.nq - 1, comp = threadIdx.x % LANES;
+  const bool owner = live && (LANES == 1 || comp == M::CURRENT_LANE);
+  const StridedRow<0> p{a.params + q, (size_t)a.nq};
+  double y[NI];
+#pragma unroll
+  for (int j = 0; j < NI; ++j) y[j] = a.states[(size_t)(comp + j) * a.nq + q];
+  const bool stim = a.n_stim > 0 && (!a.mask || a.mask[q]);
+  // frozen dofs stay frozen across launches
+  bool frozen = v.failed_step[q] >= 0 || (v.window > 0 && v.steps_taken[q] >= 0);
+  int still = v.window > 0 ? v.still[q] : 0;
+  unsigned long long n_rhs = 0, n_st = 0, n_bad = 0;
+  double t = a.t0;
+  int s = 0;
+  for (; s < v.n_steps; ++s) {
+    if (!KN_ANY(!frozen)) break;
+    const int sg = v.s0 + s;
+    if (!frozen) {
+      if (stim)
+        for (int i = 0; i < a.n_stim; ++i) p[a.stim_idx[i]] = a.stim_val[i];
+      double y0[NI];
+#pragma unroll
+      for (int j = 0; j < NI; ++j) y0[j] = y[j];
+      Integrator in;
+      in.f.prepare(p);
+      if constexpr (LANES > 1) kn_model_set_lane(in.f, comp, 0);
+      const int rc = in.integrate(&scf, work + threadIdx.x, y, t, t + a.dt, a.rtol, a.atol, 10000, comp);
+      if (owner) {
+        in.f.finish(p);
+        n_rhs += (unsigned)in.nfe;
+        n_st += (unsigned)in.nst;
+        n_bad += rc != 0 ? 1u : 0u;
+      }
+      // the lanes of a dof take one decision: the failure / stillness of the dof is the OR / AND over them
+      const double failed = kn_group_max<LANES>(rc != 0 ? 1.0 : 0.0);
+      if (failed != 0.0) {
+#pragma unroll
+        for (int j = 0; j < NI; ++j) y[j] = y0[j];
+        frozen = true;
+        if (live && comp == 0) v.failed_step[q] = sg;
+      } else if (v.window > 0) {
+        double moved = 0.0;
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+          moved = fabs(y[j] - y0[j]) <= v.ss_atol + v.ss_rtol * fabs(y[j]) ? moved : 1.0;
+        still = kn_group_max<LANES>(moved) == 0.0 ? still + 1 : 0;
+        if (still >= v.window) {
+          frozen = true;
+          if (live && comp == 0) v.steps_taken[q] = sg + 1;
+        }
+      }
+    }
+    if (v.hist && (sg + 1) % v.every == 0 && live) {
+      double* row = v.hist + (size_t)((sg + 1) / v.every - 1) * v.n_rec * a.nq + q;
+      for (int i = 0; i < v.n_rec; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+          if (comp + j == v.rec_idx[i]) row[(size_t)i * a.nq] = y[j];
+    }
+    t = t + a.dt;
+    // the next step's prepare() reads what this step's finish() stored in the row, from other lanes of the wave
+    __syncthreads();
+  }
+  // the wave is done early: its dofs' later records repeat their frozen states
+  if (v.hist && live)
+    for (; s < v.n_steps; ++s) {
+      const int sg = v.s0 + s;
+      if ((sg + 1) % v.every) continue;
+      double* row = v.hist + (size_t)((sg + 1) / v.every - 1) * v.n_rec * a.nq + q;
+      for (int i = 0; i < v.n_rec; ++i)
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+          if (comp + j == v.rec_idx[i]) row[(size_t)i * a.nq] = y[j];
+    }
+  // only the tables are written: phi_M / I_ch of a PDE problem are formed from them by the next sweep with flags
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < NI; ++j) a.states[(size_t)(comp + j) * a.nq + q] = y[j];
+    if (v.window > 0 && comp == 0) v.still[q] = still;
+  }
+#pragma unroll
+  for (int msk = 32; msk >= 1; msk >>= 1) {
+    n_rhs += __shfl_xor(n_rhs, msk);
+    n_st += __shfl_xor(n_st, msk);
+    n_bad += __shfl_xor(n_bad, msk);
+  }
+  if (threadIdx.x == 0) {
+    unsigned long long* st = a.stats + 3 * (size_t)blockIdx.x;
+    st[0] += n_rhs;
+    st[1] += n_st;
+    st[2] += n_bad;
+  }
+}
+
+template <class M, int LANES, int WAVES>
+__global__ __launch_bounds__(ODE_BLOCK, WAVES) void ode_advance_kernel(OdeArgs a, OdeAdvArgs v, const LsodaCoef* __restrict__ cf) {
+  ode_advance_body<M, LANES, WAVES>(a, v, cf);
+}
 
 template <class M, int LANES, int WAVES = 1, bool STAMPS = false>
 __global__ __launch_bounds__(ODE_BLOCK, WAVES) void ode_step_kernel(OdeDev D, OdeArgs a, const LsodaCoef* __restrict__ cf) {

@@ -59,6 +59,11 @@ class Params(C.Structure):
     ]
 
 
+class OdeSS(C.Structure):
+    """knpemi_ode_ss: steady-state mode of knpemi_ode_advance."""
+    _fields_ = [("ss_rtol", C.c_double), ("ss_atol", C.c_double), ("window", C.c_int32)]
+
+
 class DGDesc(C.Structure):
     _fields_ = [
         ("cell_kind", C.c_int32), ("n_sub", C.c_int32), ("n_ions", C.c_int32),
@@ -132,6 +137,11 @@ SIGNATURES = {
                                   C.c_double, C.c_int, c_int_p, C.c_int]),
     "knpemi_ode_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64),
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "knpemi_ode_create": (C.c_int, [C.c_int, C.c_int, c_int_p, C.POINTER(C.c_void_p)]),
+    "knpemi_ode_advance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                                     C.c_double, c_int_p, C.c_int, C.c_int, c_dbl_p, C.POINTER(OdeSS), c_int_p,
+                                     c_int_p]),
+    "knpemi_ode_advance_chunk": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "knpemi_debug_ode_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int]),
     "knpemi_debug_math": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_debug_launch_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dbl_p]),

@@ -83,6 +83,10 @@ class Mesh:
         return self.cells.shape[0]
 
     @property
+    def topology(self):
+        return Topology(self)
+
+    @property
     def facet_type(self):
         return CELL_INFO[self.cell_type]["facet_type"]
 
@@ -147,6 +151,32 @@ class Mesh:
         raise ValueError("only cells and facets are tabulated")
 
 
+class IndexMap:
+    """`dolfinx.common.IndexMap` subset: a serial mesh owns all its entities."""
+
+    def __init__(self, n):
+        self.size_local = int(n)
+        self.num_ghosts = 0
+
+
+class Topology:
+    """`mesh.topology` subset: `.dim` and `index_map(dim)`."""
+
+    def __init__(self, mesh):
+        self.mesh = mesh
+        self.dim = mesh.tdim
+
+    def index_map(self, dim):
+        return IndexMap(self.mesh.num_entities(dim))
+
+
+class GhostMode:
+    """`dolfinx.mesh.GhostMode` names; a serial mesh has no ghosts, so every mode gives the same mesh."""
+    none = "none"
+    shared_facet = "shared_facet"
+    shared_vertex = "shared_vertex"
+
+
 class MeshTags:
     """Subset of `dolfinx.mesh.MeshTags`: `.indices`, `.values`, `.dim`, `.find`."""
 
@@ -203,6 +233,18 @@ def _grid_points(p0, p1, n, axes=None):
         return np.stack([X.ravel(), Y.ravel()], axis=1)
     Z, Y, X = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
     return np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=1)
+
+
+def create_interval(comm, n, points, ghost_mode=None):
+    """`dolfinx.mesh.create_interval`: n equal cells on [points[0], points[1]], vertices numbered left to right."""
+    if ghost_mode not in (None, GhostMode.none, GhostMode.shared_facet, GhostMode.shared_vertex):
+        raise ValueError(f"unknown ghost mode {ghost_mode!r}")
+    n = int(n)
+    if n < 1:
+        raise ValueError("an interval mesh needs at least one cell")
+    x = np.linspace(float(points[0]), float(points[1]), n + 1).reshape(-1, 1)
+    cells = np.stack([np.arange(n), np.arange(1, n + 1)], axis=1)
+    return Mesh(x, cells, CellType.interval, comm)
 
 
 def create_rectangle(comm, points, n, cell_type=CellType.triangle):

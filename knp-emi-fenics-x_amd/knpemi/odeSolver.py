@@ -18,14 +18,54 @@ states, double* values, double* parameters)` with the cfunc's semantics, compile
 for gfx950 with hipRTC when the model is bound (csrc/kernels_rtc.hip) -- or has
 only what the reference's modules have, a Python `rhs_numba` / `rhs` made of
 assignments: `knpemi.rhs_codegen` translates its source text into that function.
+
+A model that no PDE problem has claimed runs on a handle of its own
+(`knpemi_ode_create`), as the reference's model steps over the dofs of any CG-1
+space; `advance` and `steady_state` run many steps in one launch
+(`ode_advance_kernel`).  Passed to `emi_system` / `knp_system` later, the model
+moves to that problem with its current tables.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
 from . import _lib as L
 
 _MODEL_IDS = {"hh_si": L.MODEL_HH_SI, "hh_mv": L.MODEL_HH_MV, "glial": L.MODEL_GLIAL}
+
+
+class OdeProblem:
+    """Membrane models without a mesh (knpemi_ode_create): model i is addressed as (sub = 1 + i, model = 0)."""
+
+    def __init__(self, nq, device=None):
+        lib = L.load()
+        if lib.knpemi_device_count() < 1:
+            raise RuntimeError("no HIP device visible: the knpemi hot path runs on MI355X only "
+                               "(there is no CPU fallback)")
+        if device is None:
+            import os
+            device = int(os.environ.get("LOCAL_RANK", "0")) % lib.knpemi_device_count()
+        self.lib = lib
+        nq = np.ascontiguousarray(nq, np.int32)
+        h = C.c_void_p()
+        L.check(lib.knpemi_ode_create(int(device), len(nq), L.iptr(nq), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h:
+            self.lib.knpemi_destroy(h)
+            self.h = None
+
+    def timer_start(self):
+        L.check(self.lib.knpemi_timer_start(self.h))
+
+    def timer_stop_ms(self):
+        ms = C.c_double()
+        L.check(self.lib.knpemi_timer_stop_ms(self.h, C.byref(ms)))
+        return ms.value
 
 
 class MembraneModel:
@@ -56,6 +96,7 @@ class MembraneModel:
         self._pending_flags = 0
         self._ion_param = None
         self._mask_cache = {}
+        self._standalone = None   # OdeProblem of a model no PDE problem has claimed
         print(f'\t{self.prefix} Number of ODE points on the membrane {nodes}')
 
     # --- device binding ------------------------------------------------------
@@ -86,7 +127,42 @@ class MembraneModel:
         for name in ion_names:
             idx += [self.ode.parameter_indices(f"{name}_e"), self.ode.parameter_indices(f"{name}_i"),
                     self.ode.parameter_indices(f"I_ch_{name}")]
-        self._ion_param = np.array(idx, np.int32)
+        # (a handle without a mesh has no ions; the ABI still wants a pointer)
+        self._ion_param = np.array(idx if idx else [0], np.int32)
+        if not isinstance(dp, OdeProblem):
+            self._standalone = None   # moved to a PDE problem: the host tables travel with every step
+
+    def _device(self):
+        """The bound problem; a model no PDE problem has claimed gets a handle of its own."""
+        if self._dp is None:
+            self._standalone = OdeProblem([self.nodes])
+            self._bind(self._standalone, 1, 0, [])
+        return self._dp
+
+    def _set_stimulus(self, stimulus, stimulus_locator):
+        dp, lib = self._dp, self._dp.lib
+        # keyed on the locator object itself (the cache holds a reference, so a fresh lambda can never reuse the id
+        # of a dead one and pick up its mask)
+        key = stimulus_locator
+        if key not in self._mask_cache:
+            if stimulus_locator is None:
+                mask = np.ones(self.nodes, np.uint8)
+            else:
+                mask = np.fromiter(map(stimulus_locator, self.dof_locations), dtype=bool).astype(np.uint8)
+            self._mask_cache = {key: np.ascontiguousarray(mask)}
+        mask = self._mask_cache[key]
+        sidx = np.array([self.ode.parameter_indices(k) for k in stimulus], np.int32)
+        sval = np.array([float(v) for v in stimulus.values()], np.float64)
+        L.check(lib.knpemi_ode_set_stimulus(dp.h, self._sub, self._model, mask.ctypes.data_as(L.c_u8_p),
+                                            len(sidx), L.iptr(sidx) if len(sidx) else None,
+                                            L.dptr(sval) if len(sval) else None))
+
+    def _read_stats(self, ms):
+        lib = self._dp.lib
+        nrhs, nst, nfail = C.c_int64(), C.c_int64(), C.c_int32()
+        rc = lib.knpemi_ode_stats(self._dp.h, self._sub, self._model, C.byref(nrhs), C.byref(nst), C.byref(nfail))
+        self.last_stats = dict(n_rhs=nrhs.value, n_steps=nst.value, n_failed=nfail.value, ms=ms)
+        return rc
 
     # --- PDE <-> ODE column copies (odeSolver.py:52-85, 130-188) -------------------
     def _table(self, what):
@@ -151,28 +227,11 @@ class MembraneModel:
     # ---- ODE integration ------
     def step_lsoda(self, dt, stimulus, stimulus_locator=None):
         '''Solve the ODEs forward by dt with optional stimulus (on the GPU)'''
-        if self._dp is None:
-            raise RuntimeError(
-                "MembraneModel is not attached to a device problem: build the forms with "
-                "emi_system()/knp_system() first (the ODE sweep has no CPU fallback)")
         if stimulus is None:
             stimulus = {}
-        dp, lib = self._dp, self._dp.lib
-        # keyed on the locator object itself (the cache holds a reference, so a fresh lambda can never reuse the id
-        # of a dead one and pick up its mask)
-        key = stimulus_locator
-        if key not in self._mask_cache:
-            if stimulus_locator is None:
-                mask = np.ones(self.nodes, np.uint8)
-            else:
-                mask = np.fromiter(map(stimulus_locator, self.dof_locations), dtype=bool).astype(np.uint8)
-            self._mask_cache = {key: np.ascontiguousarray(mask)}
-        mask = self._mask_cache[key]
-        sidx = np.array([self.ode.parameter_indices(k) for k in stimulus], np.int32)
-        sval = np.array([float(v) for v in stimulus.values()], np.float64)
-        L.check(lib.knpemi_ode_set_stimulus(dp.h, self._sub, self._model, mask.ctypes.data_as(L.c_u8_p),
-                                            len(sidx), L.iptr(sidx) if len(sidx) else None,
-                                            L.dptr(sval) if len(sval) else None))
+        dp = self._device()
+        lib = dp.lib
+        self._set_stimulus(stimulus, stimulus_locator)
         print(f'\t{self.prefix} Stepping {self.nodes} ODEs')
         states = np.ascontiguousarray(self.states, np.float64)
         params = np.ascontiguousarray(self.parameters, np.float64)
@@ -183,10 +242,7 @@ class MembraneModel:
                                     L.iptr(self._ion_param), int(self.V_index)))
         ms = dp.timer_stop_ms()
         self._pending_flags = 0
-        import ctypes as C
-        nrhs, nst, nfail = C.c_int64(), C.c_int64(), C.c_int32()
-        rc = lib.knpemi_ode_stats(dp.h, self._sub, self._model, C.byref(nrhs), C.byref(nst), C.byref(nfail))
-        self.last_stats = dict(n_rhs=nrhs.value, n_steps=nst.value, n_failed=nfail.value, ms=ms)
+        rc = self._read_stats(ms)
         L.check(lib.knpemi_ode_get_tables(dp.h, self._sub, self._model, L.dptr(states), L.dptr(params)))
         self.states[...] = states
         self.parameters[...] = params
@@ -194,3 +250,61 @@ class MembraneModel:
         self.time = self.time + dt
         print(f'\t{self.prefix} Stepped {self.nodes} ODES in {ms * 1e-3}s')
         return self.states
+
+    # ---- many steps per launch (no reference counterpart: its calibration tool loops over step_lsoda) ------
+    def advance(self, dt, n_steps, stimulus=None, stimulus_locator=None, record=None, every=1):
+        '''n_steps successive step_lsoda(dt, stimulus, stimulus_locator) calls, bit for bit, in launches of many steps.
+        `record`: state names recorded after every `every`-th step; returns {name: ndarray[n_steps // every, nodes]}.'''
+        _, hist = self._advance(dt, n_steps, stimulus, stimulus_locator, record, every, None)
+        return hist
+
+    def steady_state(self, dt, max_steps, rtol=1e-8, atol=1e-10, window=10, stimulus=None, stimulus_locator=None,
+                     record=None, every=1):
+        '''Step by dt until every node is steady: a node is still after a step when each state moved by at most
+        atol + rtol |y|, and steady after `window` still steps in a row; it is frozen from then on.  At most max_steps
+        steps.  Returns steps_taken[nodes] (the step count at which each node became steady, -1 if it did not), and
+        with `record` also the history as `advance` returns it.  `time` advances by the steps the run needed.'''
+        ss = L.OdeSS(ss_rtol=float(rtol), ss_atol=float(atol), window=int(window))
+        steps, hist = self._advance(dt, max_steps, stimulus, stimulus_locator, record, every, ss)
+        return steps if record is None else (steps, hist)
+
+    def _advance(self, dt, n_steps, stimulus, stimulus_locator, record, every, ss):
+        n_steps, every = int(n_steps), int(every)
+        if n_steps < 0 or every < 1:
+            raise ValueError("n_steps >= 0 and every >= 1")
+        names = list(record or [])
+        if len(names) > 8:
+            raise ValueError("at most 8 recorded states")
+        dp = self._device()
+        lib = dp.lib
+        self._set_stimulus(stimulus or {}, stimulus_locator)
+        states = np.ascontiguousarray(self.states, np.float64)
+        params = np.ascontiguousarray(self.parameters, np.float64)
+        L.check(lib.knpemi_ode_set_tables(dp.h, self._sub, self._model, L.dptr(states), L.dptr(params)))
+        rec = np.array([self.ode.state_indices(n) for n in names] or [0], np.int32)
+        hist = np.zeros((n_steps // every, len(names), self.nodes)) if names else None
+        steps = np.full(self.nodes, -1, np.int32)
+        failed = np.full(self.nodes, -1, np.int32)
+        dp.timer_start()
+        rc = lib.knpemi_ode_advance(dp.h, self._sub, self._model, float(self.time), float(dt), n_steps, self.rtol,
+                                    self.atol, L.iptr(rec), len(names), every,
+                                    L.dptr(hist) if hist is not None else None, C.byref(ss) if ss is not None else None,
+                                    L.iptr(steps), L.iptr(failed))
+        ms = dp.timer_stop_ms()
+        if rc not in (L.OK, L.EODE):
+            L.check(rc)
+        self._read_stats(ms)
+        L.check(lib.knpemi_ode_get_tables(dp.h, self._sub, self._model, L.dptr(states), L.dptr(params)))
+        self.states[...] = states
+        self.parameters[...] = params
+        # the time of the last step run: every node steady -> the step on which the last one became so
+        ran = int(steps.max()) if ss is not None and self.nodes and (steps >= 0).all() else n_steps
+        for _ in range(ran):
+            self.time = self.time + dt   # step_lsoda's arithmetic
+        out = {n: hist[:, i, :] for i, n in enumerate(names)} if names else {}
+        if rc == L.EODE:   # odeSolver.py:121 `assert success`
+            bad = np.flatnonzero(failed >= 0)
+            raise RuntimeError(f"LSODA failed on {len(bad)} membrane dof(s): dofs {bad[:10].tolist()} at steps "
+                               f"{failed[bad[:10]].tolist()}")
+        print(f'\t{self.prefix} Advanced {self.nodes} ODES by {n_steps} steps in {ms * 1e-3}s')
+        return steps, out
