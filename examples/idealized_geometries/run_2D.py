@@ -51,8 +51,28 @@ def read_mesh(mesh_file):
     return mesh, ct, ft
 
 
-def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None):
+# The points of the reference's figures (make_figures.py:250-257 in 2D, :267-273 in 3D; um).  2D: ECS above the cell,
+# ICS inside [1,61] x [1,3], membrane on its upper side y = 3.  3D: the ECS between axons 1 and 2 (y in (0.4, 0.5)),
+# inside axon 1 ([5,27] x [0.2,0.4] x [0.2,0.4]), and on its upper face z = 0.4.
+FIGURE_POINTS = {2: dict(ECS=(25.0, 3.5), ICS=(25.0, 2.0), mem=(25.0, 3.0)),
+                 3: dict(ECS=(25.0, 0.45, 0.65), ICS=(25.0, 0.3, 0.3), mem=(25.6, 0.34, 0.4))}
+
+
+def figure_observables(s):
+    """phi and the ions at the figures' ECS / ICS points, phi_M and the traces at their membrane point."""
+    from knpemi import Observables
+    obs = Observables(s.mesh, s.ct, s.ft, s.subdomain_list, s.ion_list)
+    P = {k: np.array(v) * 1e-6 for k, v in FIGURE_POINTS[s.mesh.gdim].items()}
+    obs.point("ECS", 0, P["ECS"])
+    obs.point("ICS", 1, P["ICS"])
+    obs.membrane_point("mem", 1, P["mem"])
+    return obs
+
+
+def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None, series=None):
+    """series: path of a .npz with the time series at the figures' points (figure_observables), or None."""
     s = Setup(kind, res, g_syn=g_syn, mesh_data=read_mesh(mesh_file) if mesh_file else None)
+    obs = figure_observables(s) if series else None
     problem_emi = create_solver_emi(s.a_emi, s.L_emi, s.phi, s.entity_maps, s.subdomain_list, None,
                                     direct=direct, p=s.p_emi, atol=1e-40, rtol=1e-5)
     problem_knp = create_solver_knp(s.a_knp, s.L_knp, s.c, s.entity_maps, s.subdomain_list, None,
@@ -69,6 +89,10 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
         update_pde_variables(s.c, s.c_prev, s.phi, s.phi_M_prev, s.physical_parameters, s.ion_list,
                              s.subdomain_list, s.mesh, s.ct)
         t += s.dt
+        if obs is not None:
+            obs.record_host(t, s.phi, s.c, s.phi_M_prev)
+    if obs is not None:
+        obs.save(series)
     if out:
         os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
         fields = {f.name: f.x._a for tag in s.subdomain_list for f in [s.phi[tag]] + s.c[tag]}
@@ -83,9 +107,10 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--iterative", action="store_true")
     ap.add_argument("--mesh-file", default=None, help="XDMF mesh written by make_mesh_2D.py (default: generate)")
+    ap.add_argument("--series", metavar="PATH", default=None, help="time series at the figures' points (.npz)")
     a = ap.parse_args()
     s, it_emi, it_knp = solve_system("2d", a.res, a.steps, direct=not a.iterative, mesh_file=a.mesh_file,
-                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"))
+                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), series=a.series)
     v = s.phi_M_prev[1].x._a
     print(f"phi_M after {a.steps} steps: min {v.min():.6f} V, max {v.max():.6f} V")
     print(f"average number of iterations emi solver: {sum(it_emi) / len(it_emi)}")

@@ -224,9 +224,30 @@ def write_results(p, outdir, k, t):
     np.savez_compressed(os.path.join(outdir, f"step_{k:06d}.npz"), t=t, **fields)
 
 
+def make_observables(p):
+    """Per-step series: the three field quantities of `history` and phi / ions at points of this mesh (the centroid of
+    the ECS cell, the neuron cell and the neuron membrane facet closest to the mesh's centre)."""
+    from knpemi import Observables
+    obs = Observables(p.mesh, p.ct, p.ft, p.subdomain_list, p.ion_list)
+    centre = 0.5 * (p.mesh.x.min(axis=0) + p.mesh.x.max(axis=0))
+
+    def central(m):
+        xc = m.x[m.cells].mean(axis=1)
+        return xc[np.argmin(np.linalg.norm(xc - centre, axis=1))]
+    obs.point("ECS", 0, central(p.subdomain_list[0]["mesh_sub"]))
+    obs.point("neuron", 1, central(p.subdomain_list[1]["mesh_sub"]))
+    obs.membrane_point("neuron_mem", 1, central(p.subdomain_list[1]["mesh_mem"]))
+    obs.reduce("phi_M_neuron", "phi_M", tag=1, op="nodal_mean")
+    obs.reduce("phi_M_glia", "phi_M", tag=2, op="nodal_mean")
+    obs.reduce("K_ecs_max", "c", ion="K", tag=0, op="max")
+    return obs
+
+
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
-                 extrapolate_guess=True):
+                 extrapolate_guess=True, series=None):
+    """series: path of a .npz of per-step observables (make_observables), or None."""
     p = Problem(config)
+    obs = make_observables(p) if series else None
     n_total = int(round(config["Tstop"] / float(DT)))
     n_steps = n_total if n_steps is None else min(n_steps, n_total)
     if outdir is None:
@@ -256,6 +277,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             for mm in p.subdomain_list[tag]["mem_models"]:
                 st.add_membrane_model(mm["ode"], p.stim_params["stimulus"], p.stim_params["stimulus_locator"])
         st.set_source(0, p.f_source_K.x._a)
+        if obs is not None:
+            st.observe(obs, every=1)
         for k in range(n_steps):
             st.step()
             t = t + DT
@@ -286,6 +309,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             update_pde_variables(p.c, p.c_prev, p.phi, p.phi_M_prev, p.physical_parameters, p.ion_list,
                                  p.subdomain_list, p.mesh, p.ct)
             t = t + DT
+            if obs is not None:
+                obs.record_host(t, p.phi, p.c, p.phi_M_prev)
             p.set_source(t)
             if (k % config["save_frequency"]) == 0 or k == n_steps - 1:
                 record(problem_emi.solver.getIterationNumber(), problem_knp.solver.getIterationNumber())
@@ -294,6 +319,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
                     xdmf_out.write(p, t)
     if xdmf_out:
         xdmf_out.close()
+    if obs is not None:
+        obs.save(series)
     history["wall_s"] = time.perf_counter() - t_wall
     history["steps"] = n_steps
     return p, history
@@ -307,9 +334,11 @@ if __name__ == "__main__":
     parser.add_argument("--device-resident", action="store_true", help="DeviceStepper + device Krylov solves")
     parser.add_argument("--direct", action="store_true", help="host LU solves (MUMPS stand-in)")
     parser.add_argument("--xdmf", action="store_true", help="also write results_sub_/results_mem_ XDMF time series")
+    parser.add_argument("--series", metavar="PATH", default=None,
+                        help="write per-step observables (points, mean phi_M, max ECS K) to this .npz")
     args = parser.parse_args()
     cfg = load_config(args.c)
     _, hist = solve_system(cfg, n_steps=args.steps, device_resident=args.device_resident, direct=args.direct,
-                           xdmf=args.xdmf)
+                           xdmf=args.xdmf, series=args.series)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

@@ -313,6 +313,32 @@ int knpemi_debug_geometry(knpemi_handle* h, int* flags);
  * electroneutrality, phi_M_prev <- tr(phi_i) - tr(phi_e). */
 int knpemi_update_pde(knpemi_handle* h);
 
+/* Observables: linear functionals and min/max reductions of the nodal fields, recorded on the device into a
+ * time-series buffer (knpemi.observables).  The reference evaluates fields at points of a checkpoint of every step
+ * (scifem.evaluate_function, examples/idealized_geometries/make_figures.py:24-117) and takes means / maxima of the
+ * downloaded arrays (local_astrocyte_depolarization/run_stim_duration.py:239-246).
+ * Observable o reads the field spec[4o + 0] of sub-domain spec[4o + 1], index spec[4o + 2] (the ids of
+ * knpemi_set_field) and applies op spec[4o + 3] to the entries ptr[o] .. ptr[o + 1] - 1 of (idx, w):
+ *   KNPEMI_OBS_SUM: (sum_e w[e] u[idx[e]]) / denom[o]   (points, integrals, means),
+ *   KNPEMI_OBS_MIN / KNPEMI_OBS_MAX: min / max_e u[idx[e]]   (w and denom unused).
+ * capacity: rows of n_obs doubles the device buffer holds.  Replaces any previous table and clears the buffer. */
+#define KNPEMI_OBS_SUM 0
+#define KNPEMI_OBS_MIN 1
+#define KNPEMI_OBS_MAX 2
+int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
+                       const double* w, const double* denom, int capacity);
+/* Enqueue the evaluation of every observable as one row on the main stream (after the end-of-step update:
+ * knpemi_update_pde, or the fused write-back of knpemi_solve_knp).  The row index is a counter in device memory that
+ * the launch advances; a full buffer writes nothing and counts the overflow.  Sums are formed in a fixed order: two
+ * identical runs give bit-identical rows.  Nothing is synchronised. */
+int knpemi_observe_record(knpemi_handle* h);
+/* Synchronise and copy out min(n_rows, device row count) rows (out: [n_rows][n_obs], may be NULL when n_rows is 0),
+ * the device row count and the overflow count; reset != 0 empties the buffer afterwards (the reference's host loop
+ * keeps its time series in Python lists: make_figures.py:24-117). */
+int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
+/* Drop the table and the buffer (knpemi_observe_record then fails with KNPEMI_EINVAL). */
+int knpemi_observe_clear(knpemi_handle* h);
+
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop
  *   (run_3D.py:356,362); with this option the write-back kernel of knpemi_solve_knp -- and of

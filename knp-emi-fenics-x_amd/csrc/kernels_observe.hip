@@ -1,0 +1,115 @@
+// Observables on gfx950: every linear functional / min / max of the nodal fields in ONE launch per recorded row.
+//
+// The reference evaluates its time series on the host from checkpoints (scifem.evaluate_function at fixed points,
+// examples/idealized_geometries/make_figures.py:24-117; means and maxima of the downloaded arrays,
+// local_astrocyte_depolarization/run_stim_duration.py:239-246).  Here a point is a sparse dot product over the <= 8
+// vertices of its cell and a reduction a dense one over a sub-domain; the host cuts every observable's entries into
+// chunks of OBS_CHUNK and gives each chunk one workgroup.  A workgroup reduces its chunk in a fixed order (strided
+// per-lane sums, then a fixed LDS tree), publishes the partial, and the last workgroup to arrive (ticket counter)
+// combines the partials of every observable in block order and appends the row.  No floating-point atomics: the
+// result does not depend on scheduling, so two identical runs give bit-identical series.
+//
+// The row index is a counter in device memory, advanced by that last workgroup with a plain store from one lane; the
+// launch carries no row number, so a captured and replayed step would still record into consecutive rows.  A full
+// buffer writes nothing and counts the row as dropped.
+#include <cmath>
+
+#include "knpemi_internal.h"
+
+#define OBS_THREADS 256
+#define OBS_CHUNK (OBS_THREADS * 8)     // entries per workgroup: 8 loads per lane in flight on the dense reductions
+
+namespace {
+
+int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    kn_set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return KNPEMI_EHIP;
+  }
+  return KNPEMI_OK;
+}
+
+struct ObsArgs {
+  int n_obs, capacity;
+  const int4* blk;
+  const int* blk_ptr;
+  const int* op;
+  const int* stride;
+  const double* const* base;
+  const double* denom;
+  const int* idx;
+  const double* w;
+  double* part;
+  unsigned long long* ctl;
+  double* rows;
+};
+
+__device__ inline double obs_combine(int op, double a, double b) {
+  return op == KNPEMI_OBS_SUM ? a + b : op == KNPEMI_OBS_MIN ? fmin(a, b) : fmax(a, b);
+}
+
+__device__ inline double obs_identity(int op) {
+  return op == KNPEMI_OBS_SUM ? 0.0 : op == KNPEMI_OBS_MIN ? INFINITY : -INFINITY;
+}
+
+__global__ __launch_bounds__(OBS_THREADS) void observe_kernel(ObsArgs A) {
+  __shared__ double sh[OBS_THREADS];
+  __shared__ int last;
+  __shared__ unsigned long long row;
+  const int4 b = A.blk[blockIdx.x];
+  const int o = b.x, op = A.op[o], stride = A.stride[o];
+  const double* __restrict__ u = A.base[o];
+  double acc = obs_identity(op);
+  // lane t takes entries b.y + t, b.y + t + 256, ...: consecutive lanes read consecutive entries (and, on the dense
+  // reductions, consecutive vertices)
+  if (op == KNPEMI_OBS_SUM) {
+    for (int e = b.y + threadIdx.x; e < b.z; e += OBS_THREADS) acc += A.w[e] * u[(size_t)A.idx[e] * stride];
+  } else {
+    for (int e = b.y + threadIdx.x; e < b.z; e += OBS_THREADS) acc = obs_combine(op, acc, u[(size_t)A.idx[e] * stride]);
+  }
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = OBS_THREADS / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) sh[threadIdx.x] = obs_combine(op, sh[threadIdx.x], sh[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(&A.part[blockIdx.x], sh[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __threadfence();
+    last = atomicAdd(&A.ctl[2], 1ull) == (unsigned long long)(gridDim.x - 1);
+  }
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  if (threadIdx.x == 0) row = A.ctl[0];     // last written by the previous launch
+  __syncthreads();
+  const bool room = row < (unsigned long long)A.capacity;
+  if (room) {
+    for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) {
+      const int qop = A.op[q];
+      double v = obs_identity(qop);
+      for (int p = A.blk_ptr[q]; p < A.blk_ptr[q + 1]; ++p)       // block order: independent of which block came last
+        v = obs_combine(qop, v, __hip_atomic_load(&A.part[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      if (qop == KNPEMI_OBS_SUM) v /= A.denom[q];
+      A.rows[(size_t)row * A.n_obs + q] = v;
+    }
+  }
+  if (threadIdx.x == 0) {
+    if (room) A.ctl[0] = row + 1;
+    else A.ctl[1] = A.ctl[1] + 1;
+    A.ctl[2] = 0;
+  }
+}
+
+}  // namespace
+
+int kn_launch_observe(knpemi_handle* h) {
+  const auto& O = h->obs;
+  if (O.n_blk == 0) return KNPEMI_OK;
+  ObsArgs a{O.n_obs, O.capacity, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ctl, O.rows};
+  hipLaunchKernelGGL(observe_kernel, dim3(O.n_blk), dim3(OBS_THREADS), 0, h->stream, a);
+  return check_launch("observe_kernel");
+}
+
+int kn_observe_chunk() { return OBS_CHUNK; }

@@ -1025,6 +1025,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   kn_fused_graphs_free(h);
   if (h->graph_emi.exec) (void)hipGraphExecDestroy(h->graph_emi.exec);
   if (h->graph_knp.exec) (void)hipGraphExecDestroy(h->graph_knp.exec);
+  for (void* p : h->obs.allocs) (void)hipFree(p);
   for (void* p : h->allocs) (void)hipFree(p);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
   for (auto& v : h->prof_ev) for (hipEvent_t e : v) (void)hipEventDestroy(e);
@@ -1747,6 +1748,123 @@ extern "C" int knpemi_update_pde(knpemi_handle* h) {
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_update_pde(h);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// observables (kernels_observe.hip)
+// ---------------------------------------------------------------------------------------------------
+int kn_observe_chunk();
+
+namespace {
+void observe_free(knpemi_handle* h) {
+  for (void* p : h->obs.allocs) (void)hipFree(p);
+  h->obs = knpemi_handle::KnObserve{};
+}
+
+template <class T>
+int obs_upload(knpemi_handle* h, const T* src, size_t n, T** out) {
+  void* p = nullptr;
+  KN_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+  h->obs.allocs.push_back(p);
+  if (n) KN_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+  *out = static_cast<T*>(p);
+  return 0;
+}
+}  // namespace
+
+extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
+                                  const int32_t* idx, const double* w, const double* denom, int capacity) {
+  if (!h || !spec || !ptr || !idx || !w || !denom) return fail(KNPEMI_EINVAL, "knpemi_observe_set: null argument");
+  if (h->ode_only) return fail(KNPEMI_EINVAL, "knpemi_observe_set: a handle of knpemi_ode_create has no fields");
+  if (n_obs < 1 || capacity < 1) return fail(KNPEMI_EINVAL, "knpemi_observe_set: n_obs and capacity must be positive");
+  if (ptr[0] != 0) return fail(KNPEMI_EINVAL, "knpemi_observe_set: ptr[0] must be 0");
+  const int chunk = kn_observe_chunk();
+  std::vector<int4> blk;
+  std::vector<int> blk_ptr(1, 0), op(n_obs), stride(n_obs);
+  std::vector<const double*> base(n_obs);
+  for (int o = 0; o < n_obs; ++o) {
+    const int32_t field = spec[4 * o], sub = spec[4 * o + 1], ix = spec[4 * o + 2], oo = spec[4 * o + 3];
+    if (oo != KNPEMI_OBS_SUM && oo != KNPEMI_OBS_MIN && oo != KNPEMI_OBS_MAX)
+      return fail(KNPEMI_EINVAL, "knpemi_observe_set: unknown op of observable " + std::to_string(o));
+    if (ptr[o + 1] <= ptr[o] || ptr[o + 1] > (int64_t)INT32_MAX)
+      return fail(KNPEMI_EINVAL, "knpemi_observe_set: observable " + std::to_string(o) + " has no entries");
+    FieldLoc L;
+    int rc = locate(h, field, sub, ix, &L);
+    if (rc) return rc;
+    for (int64_t e = ptr[o]; e < ptr[o + 1]; ++e)        // every read of the kernel stays inside the field
+      if (idx[e] < 0 || (size_t)idx[e] >= L.n)
+        return fail(KNPEMI_EINVAL, "knpemi_observe_set: index out of range in observable " + std::to_string(o));
+    op[o] = oo; stride[o] = L.stride; base[o] = L.base;
+    for (int64_t e = ptr[o]; e < ptr[o + 1]; e += chunk)
+      blk.push_back(make_int4(o, (int)e, (int)std::min<int64_t>(e + chunk, ptr[o + 1]), 0));
+    blk_ptr.push_back((int)blk.size());
+  }
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  observe_free(h);
+  auto& O = h->obs;
+  const size_t ne = (size_t)ptr[n_obs];
+  int rc;
+  if ((rc = obs_upload(h, blk.data(), blk.size(), &O.blk)) || (rc = obs_upload(h, blk_ptr.data(), blk_ptr.size(), &O.blk_ptr))
+      || (rc = obs_upload(h, op.data(), op.size(), &O.op)) || (rc = obs_upload(h, stride.data(), stride.size(), &O.stride))
+      || (rc = obs_upload(h, base.data(), base.size(), const_cast<const double***>(&O.base)))
+      || (rc = obs_upload(h, denom, (size_t)n_obs, &O.denom))
+      || (rc = obs_upload(h, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = obs_upload(h, w, ne, &O.w))) {
+    observe_free(h);
+    return rc;
+  }
+  void* p = nullptr;
+  const size_t row_bytes = (size_t)capacity * n_obs * sizeof(double);
+  if (hipMalloc(&p, blk.size() * sizeof(double)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, "knpemi_observe_set: partials"); }
+  O.allocs.push_back(p); O.part = static_cast<double*>(p);
+  if (hipMalloc(&p, 4 * sizeof(unsigned long long)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, "knpemi_observe_set: counters"); }
+  O.allocs.push_back(p); O.ctl = static_cast<unsigned long long*>(p);
+  if (hipMalloc(&p, row_bytes) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, "knpemi_observe_set: buffer"); }
+  O.allocs.push_back(p); O.rows = static_cast<double*>(p);
+  KN_HIP(hipMemsetAsync(O.ctl, 0, 4 * sizeof(unsigned long long), h->stream));
+  KN_HIP(hipMemsetAsync(O.rows, 0, row_bytes, h->stream));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  O.n_obs = n_obs; O.n_blk = (int)blk.size(); O.capacity = capacity;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_observe_record(knpemi_handle* h) {
+  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (h->obs.n_blk == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
+  KN_HIP(hipSetDevice(h->device));
+  return kn_launch_observe(h);
+}
+
+extern "C" int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow,
+                                   int reset) {
+  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  auto& O = h->obs;
+  if (O.n_blk == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_read: no observables set");
+  if (n_rows < 0 || (n_rows > 0 && !out)) return fail(KNPEMI_EINVAL, "knpemi_observe_read: bad output buffer");
+  KN_HIP(hipSetDevice(h->device));
+  unsigned long long ctl[4];
+  KN_HIP(hipMemcpyAsync(ctl, O.ctl, sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
+  if (n) {
+    KN_HIP(hipMemcpyAsync(out, O.rows, n * O.n_obs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    KN_HIP(hipStreamSynchronize(h->stream));
+  }
+  if (rows) *rows = (int64_t)ctl[0];
+  if (overflow) *overflow = (int64_t)ctl[1];
+  if (reset) {
+    KN_HIP(hipMemsetAsync(O.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
+    KN_HIP(hipStreamSynchronize(h->stream));
+  }
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_observe_clear(knpemi_handle* h) {
+  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  observe_free(h);
+  return KNPEMI_OK;
 }
 
 extern "C" int knpemi_set_distributed(knpemi_handle* h, const uint8_t* owned, void* reduce_buf_dev,

@@ -346,6 +346,22 @@ struct knpemi_handle {
   int lds_gam_max = 0;                 // most membrane entries of one row block
   bool blocks_clustered = false;       // row blocks are clusters of row chunks (default), not consecutive rows
   KnDist dist;
+  // observables (knpemi_observe_set, kernels_observe.hip); freed by knpemi_observe_clear / knpemi_destroy
+  struct KnObserve {
+    int n_obs = 0, n_blk = 0, capacity = 0;
+    int4* blk = nullptr;                 // [n_blk] {observable, first entry, end entry, 0}
+    int* blk_ptr = nullptr;              // [n_obs + 1] first block of every observable
+    int* op = nullptr;                   // [n_obs]
+    int* stride = nullptr;               // [n_obs]
+    const double** base = nullptr;       // [n_obs] field addresses (locate())
+    double* denom = nullptr;             // [n_obs] divisor of a sum (1, n for a nodal mean, the measure for an average)
+    int* idx = nullptr;                  // [entries]
+    double* w = nullptr;                 // [entries]
+    double* part = nullptr;              // [n_blk] block partials
+    unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last block
+    double* rows = nullptr;              // [capacity][n_obs]
+    std::vector<void*> allocs;
+  } obs;
   // per-kernel event profiling (knpemi_profile)
   uint32_t prof_mask = 0;
   std::vector<hipEvent_t> prof_ev[KNPEMI_N_KERNELS];  // begin/end pairs
@@ -413,6 +429,7 @@ int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_
 int kn_launch_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol,
                        int flags, const int32_t* ion_param, int v_index);
 int kn_launch_update_pde(knpemi_handle* h);
+int kn_launch_observe(knpemi_handle* h);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 int kn_rtc_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, size_t dev_bytes, const void* args,
                   size_t args_bytes, const void* coef);

@@ -25,6 +25,7 @@ WANT_P, NO_SPLITTING, SKIP_MEMBRANE_RHS, ON_AUX_STREAM, MEMBRANE_EARLY = 1, 2, 4
 ODE_SET_V, ODE_SET_TRACES, ODE_ON_AUX, ODE_ON_AUX2 = 1, 2, 4, 8
 OPT_FUSE_UPDATE, OPT_FUSE_MEMBRANE, OPT_PROFILE_STRIDE, OPT_KNP_MIN_IT, OPT_FOLD_MEMBRANE, OPT_KNP_METHOD = 1, 2, 3, 4, 5, 6
 OPT_EMI_NORM = 7
+OBS_SUM, OBS_MIN, OBS_MAX = 0, 1, 2
 K_ODE, K_EMI_ROWS, K_KNP_ROWS, K_KNP_MEMBRANE, K_UPDATE, K_EMI_MEMBRANE = range(6)
 KERNEL_NAMES = ["ode_step_kernel", "emi_rows_kernel", "knp_rows_kernel", "knp_membrane_kernel", "update_pde_kernel",
                 "emi_membrane_rhs_kernel"]
@@ -147,6 +148,12 @@ SIGNATURES = {
     "knpemi_debug_launch_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dbl_p]),
     "knpemi_debug_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "knpemi_update_pde": (C.c_int, [C.c_void_p]),
+    "knpemi_observe_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_int64), c_int_p, c_dbl_p, c_dbl_p,
+                                     C.c_int]),
+    "knpemi_observe_record": (C.c_int, [C.c_void_p]),
+    "knpemi_observe_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.c_int]),
+    "knpemi_observe_clear": (C.c_int, [C.c_void_p]),
     "knpemi_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "knpemi_trace": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_halo_width": (C.c_int, [C.c_void_p, C.c_int]),

@@ -76,6 +76,7 @@ class DeviceStepper:
         self.dt = float(a.dt)
         self.flags_emi = L.WANT_P | (0 if a.splitting_scheme else L.NO_SPLITTING)
         self.flags_knp = 0 if a.splitting_scheme else L.NO_SPLITTING
+        self._obs = None           # attached Observables (observe)
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -129,6 +130,38 @@ class DeviceStepper:
             self.add_membrane_model(m, stim, loc)
         self.k = 0
         self.ode_failures()            # clears the counters of the previous run
+        if self._obs is not None:      # a new series
+            L.check(self.lib.knpemi_observe_read(self.dp.h, 0, None, None, None, 1))
+            self._obs_pending = []
+            self._obs.clear()
+
+    # -- observables -------------------------------------------------------------------------------
+    def observe(self, obs, every=1, capacity=1024, t0=0.0):
+        """Record the observables `obs` (knpemi.observables.Observables) on the device after every `every`-th step,
+        at time t0 + k dt for step k.  Rows collect in a device buffer of `capacity` rows; the host keeps the times of
+        the rows it has enqueued and drains the buffer into `obs` (one synchronisation) whenever it holds `capacity`
+        of them, and when `obs.series()` is called."""
+        if every < 1 or capacity < 1:
+            raise ValueError("every and capacity must be positive")
+        if obs._drain is not None:
+            raise RuntimeError("these observables are attached to a stepper already")
+        obs.upload(self.dp, capacity)
+        self._obs, self._obs_every, self._obs_capacity, self._obs_t0 = obs, int(every), int(capacity), float(t0)
+        self._obs_pending = []
+        obs.clear()
+        obs._drain = self._observe_drain
+
+    def _observe_drain(self):
+        """Move the device rows into the host series; the device must hold exactly the rows enqueued."""
+        obs, n = self._obs, len(self._obs_pending)
+        buf = np.empty((max(n, 1), len(obs.items)), np.float64)
+        rows, over = C.c_int64(), C.c_int64()
+        L.check(self.lib.knpemi_observe_read(self.dp.h, n, L.dptr(buf), C.byref(rows), C.byref(over), 1))
+        if rows.value != n or over.value != 0:
+            raise RuntimeError(f"observables: the device holds {rows.value} row(s) (+{over.value} dropped), "
+                               f"the host enqueued {n}")
+        obs._append_rows(self._obs_pending, buf[:n])
+        self._obs_pending = []
 
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
@@ -165,6 +198,9 @@ class DeviceStepper:
     # -- one time step, everything enqueued on the handle's stream ---------------------------
     def step(self, halo=None):
         dp, lib = self.dp, self.lib
+        if halo is not None and self._obs is not None:
+            raise NotImplementedError("observables are not recorded on partitioned problems yet (every rank would "
+                                      "have to record the points it owns and rank 0 gather them)")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
@@ -240,6 +276,13 @@ class DeviceStepper:
         if halo is not None:
             halo.exchange_bulk()
         self.k += 1
+        if self._obs is not None and self.k % self._obs_every == 0:
+            # on the main stream behind the end-of-step update (update_pde_kernel or the fused KNP write-back); the next
+            # step's side-stream launches fork from the main stream after it (ev_fork), so none of them overtakes it
+            L.check(lib.knpemi_observe_record(dp.h))
+            self._obs_pending.append(self._obs_t0 + self.k * self.dt)
+            if len(self._obs_pending) == self._obs_capacity:
+                self._observe_drain()
 
     def ode_failures(self):
         n = 0

@@ -1,0 +1,80 @@
+"""Cost of recording observables in the device-resident loop (knpemi.observables, DeviceStepper.observe).
+
+Config 2 (tet r=1) with the device solves: ms per step without observables and with ten of them recorded every step
+(two points = eight functionals, plus two sub-domain-wide reductions: the nodal mean of phi_M and the ECS maximum of
+K).  Both legs start from the same state (DeviceStepper.reset), so they run the same solver iterations; the legs
+alternate and the median of the repeats is printed as one JSON line.  For the kernel's own time run this under
+`rocprofv3 --kernel-trace --stats` and read observe_kernel in the statistics.
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("knp-emi-fenics-x_amd", "examples/idealized_geometries", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+
+import numpy as np  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    args = ap.parse_args()
+    from setup_problem import Setup
+    from knpemi import Observables
+    from knpemi.stepper import DeviceStepper
+    with contextlib.redirect_stdout(io.StringIO()):
+        s = Setup("tet", 1, g_syn=10.0)
+    for t in s.subdomain_list:
+        for k in range(2):
+            s.c[t][k].x.array[:] = s.c_prev[t][k].x._a
+    st = DeviceStepper((s.a_emi, s.p_emi, s.L_emi), (s.a_knp, s.p_knp, s.L_knp), s.c, s.c_prev, s.phi, s.phi_M_prev,
+                       device_solves=(1e-6, 1e-7))
+    st.add_membrane_model(s.mem_models[0]["ode"], s.stim_params["stimulus"], s.stim_params["stimulus_locator"])
+    obs = Observables(s.mesh, s.ct, s.ft, s.subdomain_list, s.ion_list)
+    obs.point("ECS", 0, [16.1e-6, 0.45e-6, 0.13e-6])
+    obs.point("ICS", 1, [16.1e-6, 0.31e-6, 0.27e-6])
+    obs.reduce("phi_M_neuron", "phi_M", tag=1, op="nodal_mean")
+    obs.reduce("K_ecs_max", "c", ion="K", tag=0, op="max")
+
+    def leg(with_obs):
+        st.reset()
+        with contextlib.redirect_stdout(io.StringIO()):
+            for _ in range(args.warmup):
+                st.step()
+            st.dp.sync()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                st.step()
+            st.dp.sync()
+        ms = (time.perf_counter() - t0) * 1e3 / args.steps
+        if with_obs:
+            assert obs.series()["t"].shape == (args.warmup + args.steps,)
+        return ms
+
+    # a first, untimed pass of both legs: AMG set-up, solver mode choice, the ODE/assembly overlap decision
+    leg(False)
+    st.observe(obs, every=1, capacity=4096)
+    leg(True)
+    plain, observed = [], []
+    for _ in range(args.repeats):
+        st._obs, saved = None, st._obs          # detach for the plain leg (the table stays on the device)
+        plain.append(leg(False))
+        st._obs = saved
+        observed.append(leg(True))
+    n_e = sum(o.ids.shape[0] for o in obs.items)
+    print(json.dumps(dict(workload="config2", steps=args.steps, observables=len(obs.items), entries=int(n_e),
+                          ms_per_step_plain=float(np.median(plain)), ms_per_step_observed=float(np.median(observed)),
+                          us_per_recorded_step=float(np.median(np.array(observed) - np.array(plain)) * 1e3),
+                          plain=plain, observed=observed)))
+
+
+if __name__ == "__main__":
+    main()
