@@ -338,6 +338,23 @@ int knpemi_observe_record(knpemi_handle* h);
 int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
 /* Drop the table and the buffer (knpemi_observe_record then fails with KNPEMI_EINVAL). */
 int knpemi_observe_clear(knpemi_handle* h);
+/* The same table on one rank of a cell-partitioned run (knpemi.observables, DeviceStepper.observe(halo=...)): every rank
+ * passes the same observables in the same order, with the entries of what it counts -- the points it took, the integral
+ * weights of the cells it records, its owned vertices -- and the GLOBAL denominators.  An observable may have no entries
+ * here (ptr[o + 1] == ptr[o]), and a rank may have none at all.  xbuf_dev: the caller's device buffer of world * n_obs
+ * doubles (zeroed here).  knpemi_observe_record then enqueues on the main stream:
+ *   1. the partial pass: this rank's fold of every observable, without the denominator, into xbuf[rank * n_obs + o]
+ *      (the op's identity without entries);
+ *   2. the sum of the first world * n_obs doubles of xbuf over the ranks: allreduce(ctx, world * n_obs) when given,
+ *      else knpemi_comm_allreduce on the handle's communicator (knpemi_comm_init; required then).  Every slot has one
+ *      non-zero contributor, so the sum is an exact all-gather;
+ *   3. observe_combine_kernel: the slots folded in rank order, sums divided by denom, the row appended as above, the
+ *      other ranks' slots zeroed for the next record.
+ * Every rank appends the same row; knpemi_observe_read stays rank-local.  Points, minima and maxima equal those of one
+ * rank holding the whole mesh bit for bit; sums agree to rounding (a different order of summation). */
+int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
+                                   const int32_t* idx, const double* w, const double* denom, int capacity, int rank,
+                                   int world, void* xbuf_dev, int (*allreduce)(void* ctx, int n), void* ctx);
 
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop

@@ -12,6 +12,13 @@
 // The row index is a counter in device memory, advanced by that last workgroup with a plain store from one lane; the
 // launch carries no row number, so a captured and replayed step would still record into consecutive rows.  A full
 // buffer writes nothing and counts the row as dropped.
+//
+// Partitioned runs (knpemi_observe_set_partitioned): the last workgroup writes each observable's fold of its block
+// partials, without the denominator, into this rank's slot xbuf[rank * n_obs + q] instead of appending a row (an
+// observable without local entries, or a rank without any, writes the op's identity).  The caller sums xbuf over the
+// ranks -- every slot has one non-zero contributor, so the sum is an exact all-gather -- and observe_combine_kernel
+// folds the slots in rank order, divides by the denominators and appends the row.
+#include <algorithm>
 #include <cmath>
 
 #include "knpemi_internal.h"
@@ -31,7 +38,7 @@ int check_launch(const char* what) {
 }
 
 struct ObsArgs {
-  int n_obs, capacity;
+  int n_obs, capacity, n_blk;
   const int4* blk;
   const int* blk_ptr;
   const int* op;
@@ -41,6 +48,16 @@ struct ObsArgs {
   const int* idx;
   const double* w;
   double* part;
+  unsigned long long* ctl;
+  double* rows;
+  double* slot;              // partitioned: this rank's n_obs slots of xbuf; nullptr: append the row here
+};
+
+struct ObsCombineArgs {
+  int n_obs, capacity, world, rank;
+  const int* op;
+  const double* denom;
+  double* xbuf;              // [world][n_obs], summed over the ranks
   unsigned long long* ctl;
   double* rows;
 };
@@ -57,31 +74,46 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_kernel(ObsArgs A) {
   __shared__ double sh[OBS_THREADS];
   __shared__ int last;
   __shared__ unsigned long long row;
-  const int4 b = A.blk[blockIdx.x];
-  const int o = b.x, op = A.op[o], stride = A.stride[o];
-  const double* __restrict__ u = A.base[o];
-  double acc = obs_identity(op);
-  // lane t takes entries b.y + t, b.y + t + 256, ...: consecutive lanes read consecutive entries (and, on the dense
-  // reductions, consecutive vertices)
-  if (op == KNPEMI_OBS_SUM) {
-    for (int e = b.y + threadIdx.x; e < b.z; e += OBS_THREADS) acc += A.w[e] * u[(size_t)A.idx[e] * stride];
-  } else {
-    for (int e = b.y + threadIdx.x; e < b.z; e += OBS_THREADS) acc = obs_combine(op, acc, u[(size_t)A.idx[e] * stride]);
-  }
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = OBS_THREADS / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sh[threadIdx.x] = obs_combine(op, sh[threadIdx.x], sh[threadIdx.x + s]);
+  // a partitioned rank without entries runs one workgroup that has no block: it only publishes the identities
+  const bool has_blk = (int)blockIdx.x < A.n_blk;
+  if (has_blk) {
+    const int4 b = A.blk[blockIdx.x];
+    const int o = b.x, op = A.op[o], stride = A.stride[o];
+    const double* __restrict__ u = A.base[o];
+    double acc = obs_identity(op);
+    // lane t takes entries b.y + t, b.y + t + 256, ...: consecutive lanes read consecutive entries (and, on the dense
+    // reductions, consecutive vertices)
+    if (op == KNPEMI_OBS_SUM) {
+      for (int e = b.y + threadIdx.x; e < b.z; e += OBS_THREADS) acc += A.w[e] * u[(size_t)A.idx[e] * stride];
+    } else {
+      for (int e = b.y + threadIdx.x; e < b.z; e += OBS_THREADS) acc = obs_combine(op, acc, u[(size_t)A.idx[e] * stride]);
+    }
+    sh[threadIdx.x] = acc;
     __syncthreads();
+    for (int s = OBS_THREADS / 2; s > 0; s >>= 1) {
+      if (threadIdx.x < s) sh[threadIdx.x] = obs_combine(op, sh[threadIdx.x], sh[threadIdx.x + s]);
+      __syncthreads();
+    }
   }
   if (threadIdx.x == 0) {
-    __hip_atomic_store(&A.part[blockIdx.x], sh[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (has_blk) __hip_atomic_store(&A.part[blockIdx.x], sh[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __threadfence();
     last = atomicAdd(&A.ctl[2], 1ull) == (unsigned long long)(gridDim.x - 1);
   }
   __syncthreads();
   if (!last) return;
   __threadfence();
+  if (A.slot) {                             // partitioned: this rank's slots; the row is appended by the combine kernel
+    for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) {
+      const int qop = A.op[q];
+      double v = obs_identity(qop);
+      for (int p = A.blk_ptr[q]; p < A.blk_ptr[q + 1]; ++p)
+        v = obs_combine(qop, v, __hip_atomic_load(&A.part[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      A.slot[q] = v;
+    }
+    if (threadIdx.x == 0) A.ctl[2] = 0;
+    return;
+  }
   if (threadIdx.x == 0) row = A.ctl[0];     // last written by the previous launch
   __syncthreads();
   const bool room = row < (unsigned long long)A.capacity;
@@ -102,14 +134,47 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_kernel(ObsArgs A) {
   }
 }
 
+// One workgroup: fold the ranks' slots of every observable in rank order (the same order on every rank, so every rank
+// appends the same row), divide sums by the global denominator, append the row, then zero the other ranks' slots so
+// that the next sum over the ranks again has one non-zero contributor per slot.
+__global__ __launch_bounds__(OBS_THREADS) void observe_combine_kernel(ObsCombineArgs A) {
+  __shared__ unsigned long long row;
+  if (threadIdx.x == 0) row = A.ctl[0];
+  __syncthreads();
+  const bool room = row < (unsigned long long)A.capacity;
+  for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) {
+    const int qop = A.op[q];
+    double v = obs_identity(qop);
+    for (int r = 0; r < A.world; ++r) v = obs_combine(qop, v, A.xbuf[(size_t)r * A.n_obs + q]);
+    if (qop == KNPEMI_OBS_SUM) v /= A.denom[q];
+    if (room) A.rows[(size_t)row * A.n_obs + q] = v;
+  }
+  __syncthreads();                          // every slot read before any is zeroed
+  const int n = A.world * A.n_obs;
+  for (int i = threadIdx.x; i < n; i += OBS_THREADS)
+    if (i / A.n_obs != A.rank) A.xbuf[i] = 0.0;
+  if (threadIdx.x == 0) {
+    if (room) A.ctl[0] = row + 1;
+    else A.ctl[1] = A.ctl[1] + 1;
+  }
+}
+
 }  // namespace
 
 int kn_launch_observe(knpemi_handle* h) {
   const auto& O = h->obs;
-  if (O.n_blk == 0) return KNPEMI_OK;
-  ObsArgs a{O.n_obs, O.capacity, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ctl, O.rows};
-  hipLaunchKernelGGL(observe_kernel, dim3(O.n_blk), dim3(OBS_THREADS), 0, h->stream, a);
+  if (O.n_blk == 0 && !O.xbuf) return KNPEMI_OK;
+  ObsArgs a{O.n_obs, O.capacity, O.n_blk, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ctl,
+            O.rows, O.xbuf ? O.xbuf + (size_t)O.rank * O.n_obs : nullptr};
+  hipLaunchKernelGGL(observe_kernel, dim3(std::max(O.n_blk, 1)), dim3(OBS_THREADS), 0, h->stream, a);
   return check_launch("observe_kernel");
+}
+
+int kn_launch_observe_combine(knpemi_handle* h) {
+  const auto& O = h->obs;
+  ObsCombineArgs a{O.n_obs, O.capacity, O.world, O.rank, O.op, O.denom, O.xbuf, O.ctl, O.rows};
+  hipLaunchKernelGGL(observe_combine_kernel, dim3(1), dim3(OBS_THREADS), 0, h->stream, a);
+  return check_launch("observe_combine_kernel");
 }
 
 int kn_observe_chunk() { return OBS_CHUNK; }

@@ -1772,12 +1772,16 @@ int obs_upload(knpemi_handle* h, const T* src, size_t n, T** out) {
 }
 }  // namespace
 
-extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
-                                  const int32_t* idx, const double* w, const double* denom, int capacity) {
-  if (!h || !spec || !ptr || !idx || !w || !denom) return fail(KNPEMI_EINVAL, "knpemi_observe_set: null argument");
-  if (h->ode_only) return fail(KNPEMI_EINVAL, "knpemi_observe_set: a handle of knpemi_ode_create has no fields");
-  if (n_obs < 1 || capacity < 1) return fail(KNPEMI_EINVAL, "knpemi_observe_set: n_obs and capacity must be positive");
-  if (ptr[0] != 0) return fail(KNPEMI_EINVAL, "knpemi_observe_set: ptr[0] must be 0");
+namespace {
+// knpemi_observe_set and knpemi_observe_set_partitioned; the partitioned table may hold observables without entries
+int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
+                const double* w, const double* denom, int capacity, bool partitioned) {
+  const std::string fn(who);
+  if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_obs < 1 || capacity < 1) return fail(KNPEMI_EINVAL, fn + ": n_obs and capacity must be positive");
+  if (ptr[0] != 0) return fail(KNPEMI_EINVAL, fn + ": ptr[0] must be 0");
+  if (ptr[n_obs] > 0 && (!idx || !w)) return fail(KNPEMI_EINVAL, fn + ": null argument");
   const int chunk = kn_observe_chunk();
   std::vector<int4> blk;
   std::vector<int> blk_ptr(1, 0), op(n_obs), stride(n_obs);
@@ -1785,15 +1789,15 @@ extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* sp
   for (int o = 0; o < n_obs; ++o) {
     const int32_t field = spec[4 * o], sub = spec[4 * o + 1], ix = spec[4 * o + 2], oo = spec[4 * o + 3];
     if (oo != KNPEMI_OBS_SUM && oo != KNPEMI_OBS_MIN && oo != KNPEMI_OBS_MAX)
-      return fail(KNPEMI_EINVAL, "knpemi_observe_set: unknown op of observable " + std::to_string(o));
-    if (ptr[o + 1] <= ptr[o] || ptr[o + 1] > (int64_t)INT32_MAX)
-      return fail(KNPEMI_EINVAL, "knpemi_observe_set: observable " + std::to_string(o) + " has no entries");
+      return fail(KNPEMI_EINVAL, fn + ": unknown op of observable " + std::to_string(o));
+    if ((partitioned ? ptr[o + 1] < ptr[o] : ptr[o + 1] <= ptr[o]) || ptr[o + 1] > (int64_t)INT32_MAX)
+      return fail(KNPEMI_EINVAL, fn + ": observable " + std::to_string(o) + (partitioned ? " has a bad entry range" : " has no entries"));
     FieldLoc L;
     int rc = locate(h, field, sub, ix, &L);
     if (rc) return rc;
     for (int64_t e = ptr[o]; e < ptr[o + 1]; ++e)        // every read of the kernel stays inside the field
       if (idx[e] < 0 || (size_t)idx[e] >= L.n)
-        return fail(KNPEMI_EINVAL, "knpemi_observe_set: index out of range in observable " + std::to_string(o));
+        return fail(KNPEMI_EINVAL, fn + ": index out of range in observable " + std::to_string(o));
     op[o] = oo; stride[o] = L.stride; base[o] = L.base;
     for (int64_t e = ptr[o]; e < ptr[o + 1]; e += chunk)
       blk.push_back(make_int4(o, (int)e, (int)std::min<int64_t>(e + chunk, ptr[o + 1]), 0));
@@ -1815,11 +1819,11 @@ extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* sp
   }
   void* p = nullptr;
   const size_t row_bytes = (size_t)capacity * n_obs * sizeof(double);
-  if (hipMalloc(&p, blk.size() * sizeof(double)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, "knpemi_observe_set: partials"); }
+  if (hipMalloc(&p, std::max<size_t>(blk.size(), 1) * sizeof(double)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, fn + ": partials"); }
   O.allocs.push_back(p); O.part = static_cast<double*>(p);
-  if (hipMalloc(&p, 4 * sizeof(unsigned long long)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, "knpemi_observe_set: counters"); }
+  if (hipMalloc(&p, 4 * sizeof(unsigned long long)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, fn + ": counters"); }
   O.allocs.push_back(p); O.ctl = static_cast<unsigned long long*>(p);
-  if (hipMalloc(&p, row_bytes) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, "knpemi_observe_set: buffer"); }
+  if (hipMalloc(&p, row_bytes) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, fn + ": buffer"); }
   O.allocs.push_back(p); O.rows = static_cast<double*>(p);
   KN_HIP(hipMemsetAsync(O.ctl, 0, 4 * sizeof(unsigned long long), h->stream));
   KN_HIP(hipMemsetAsync(O.rows, 0, row_bytes, h->stream));
@@ -1827,19 +1831,55 @@ extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* sp
   O.n_obs = n_obs; O.n_blk = (int)blk.size(); O.capacity = capacity;
   return KNPEMI_OK;
 }
+}  // namespace
+
+extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
+                                  const int32_t* idx, const double* w, const double* denom, int capacity) {
+  return observe_set(h, "knpemi_observe_set", n_obs, spec, ptr, idx, w, denom, capacity, false);
+}
+
+extern "C" int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
+                                              const int32_t* idx, const double* w, const double* denom, int capacity,
+                                              int rank, int world, void* xbuf_dev, knpemi_allreduce_fn allreduce,
+                                              void* ctx) {
+  const char* fn = "knpemi_observe_set_partitioned";
+  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (world < 1 || rank < 0 || rank >= world) return fail(KNPEMI_EINVAL, std::string(fn) + ": bad rank / world");
+  if (!xbuf_dev) return fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer is required");
+  if (!allreduce && !h->comm)
+    return fail(KNPEMI_EINVAL, std::string(fn) + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
+  if (n_obs > 0 && (size_t)world * (size_t)n_obs > (size_t)INT32_MAX)
+    return fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer too large");
+  int rc = observe_set(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, true);
+  if (rc) return rc;
+  auto& O = h->obs;
+  O.xbuf = static_cast<double*>(xbuf_dev);
+  O.rank = rank; O.world = world; O.allreduce = allreduce; O.ctx = ctx;
+  KN_HIP(hipMemsetAsync(O.xbuf, 0, (size_t)world * n_obs * sizeof(double), h->stream));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  return KNPEMI_OK;
+}
 
 extern "C" int knpemi_observe_record(knpemi_handle* h) {
   if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (h->obs.n_blk == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
+  auto& O = h->obs;
+  if (O.n_obs == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
   KN_HIP(hipSetDevice(h->device));
-  return kn_launch_observe(h);
+  int rc = kn_launch_observe(h);
+  if (rc || !O.xbuf) return rc;
+  // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
+  const int n = O.world * O.n_obs;
+  rc = O.allreduce ? (O.allreduce(O.ctx, n) ? fail(KNPEMI_EHIP, "knpemi_observe_record: allreduce hook failed") : KNPEMI_OK)
+                   : knpemi_comm_allreduce(h, O.xbuf, n);
+  if (rc) return rc;
+  return kn_launch_observe_combine(h);
 }
 
 extern "C" int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow,
                                    int reset) {
   if (!h) return fail(KNPEMI_EINVAL, "null handle");
   auto& O = h->obs;
-  if (O.n_blk == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_read: no observables set");
+  if (O.n_obs == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_read: no observables set");
   if (n_rows < 0 || (n_rows > 0 && !out)) return fail(KNPEMI_EINVAL, "knpemi_observe_read: bad output buffer");
   KN_HIP(hipSetDevice(h->device));
   unsigned long long ctl[4];

@@ -360,6 +360,12 @@ struct knpemi_handle {
     double* part = nullptr;              // [n_blk] block partials
     unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last block
     double* rows = nullptr;              // [capacity][n_obs]
+    // partitioned runs (knpemi_observe_set_partitioned): the caller's [world][n_obs] exchange buffer, summed over the
+    // ranks by `allreduce` (or the library's communicator when it is null) between the partial and the combine launch
+    double* xbuf = nullptr;
+    int rank = 0, world = 1;
+    knpemi_allreduce_fn allreduce = nullptr;
+    void* ctx = nullptr;
     std::vector<void*> allocs;
   } obs;
   // per-kernel event profiling (knpemi_profile)
@@ -430,6 +436,7 @@ int kn_launch_ode_step(knpemi_handle* h, int slot, double t0, double dt, double 
                        int flags, const int32_t* ion_param, int v_index);
 int kn_launch_update_pde(knpemi_handle* h);
 int kn_launch_observe(knpemi_handle* h);
+int kn_launch_observe_combine(knpemi_handle* h);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 int kn_rtc_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, size_t dev_bytes, const void* args,
                   size_t args_bytes, const void* coef);

@@ -111,6 +111,9 @@ class Halo:
         self.dp = None
         self._dev = None
         self.mode = "not attached"
+        self.rank = None            # this rank (set by the subclasses)
+        self.n_local = None         # {"bulk": local vertex ids, "mem": local membrane dofs} of the device numbering
+        self._hook_error = None
 
     # -- host exchange (CPU tests, Vector.scatter_forward): `arr` = [n_global_ids, width] array ------------------
     def forward_host_array(self, kind, arr, dist):
@@ -281,6 +284,14 @@ class Halo:
             own[pl["recv"]] = 0
         return own
 
+    def vertex_owner(self, kind="bulk"):
+        """Owner rank of every local vertex ("bulk", device numbering) or membrane dof ("mem"), read off the plans
+        without communication: an entry is owned here unless a neighbour sends it, and then that neighbour owns it."""
+        own = np.full(self.n_local[kind], self.rank, np.int32)
+        for pl in self.plans[kind].values():
+            own[pl["recv"]] = pl["nb"]
+        return own
+
     def enable_solves(self):
         """knpemi_solve_emi / knpemi_solve_knp on this handle become solves of the GLOBAL systems
         (knpemi_set_distributed): halo'd SpMV, all-reduced dot products, per-rank AMG (block Jacobi)."""
@@ -297,14 +308,7 @@ class Halo:
                      L.B_KNP: self._device_plan_knp(knp_index)}
         self._red = torch.zeros(8 + 64, dtype=torch.float64, device=self._device)    # 8 scalars + the coarse vector
         self._hook_error = None
-
-        def allreduce(ctx, n):
-            try:
-                self._allreduce(n)
-                return 0
-            except Exception as exc:       # noqa: BLE001 -- must not propagate through the C frame
-                self._hook_error = exc
-                return -1
+        allreduce = self._allreduce_hook(self._red)
 
         def halo(ctx, vec, which):
             try:
@@ -348,20 +352,37 @@ class Halo:
                   for key, pl in self.plans["bulk"].items()}
         return self._device_plan(mapped, 1)
 
-    def _allreduce(self, n):
+    def _allreduce_hook(self, buf):
+        """knpemi_allreduce_fn body summing the first n doubles of the device tensor `buf` over the ranks; an exception
+        is kept in `_hook_error` (it must not propagate through the C frame) and reported as a failure."""
+        def allreduce(ctx, n):
+            try:
+                self._allreduce(n, buf)
+                return 0
+            except Exception as exc:       # noqa: BLE001
+                self._hook_error = exc
+                return -1
+        return allreduce
+
+    def allreduce_callback(self, buf):
+        """The hook of `_allreduce_hook` as a C function pointer (keep the returned callback object alive)."""
+        return self.L.ALLREDUCE_FN(self._allreduce_hook(buf))
+
+    def _allreduce(self, n, buf=None):
         dist, torch = self.dist, self.torch
+        buf = self._red if buf is None else buf
         if dist.get_backend() == "gloo":
             self.dp.sync()
-            host = self._red[:n].cpu()
+            host = buf[:n].cpu()
             dist.all_reduce(host)
-            self._red[:n].copy_(host)
+            buf[:n].copy_(host)
             torch.cuda.current_stream().synchronize()
         elif self._stream_ordered:
             with torch.cuda.stream(self._ext):
-                dist.all_reduce(self._red[:n])
+                dist.all_reduce(buf[:n])
         else:
             self.dp.sync()
-            dist.all_reduce(self._red[:n])
+            dist.all_reduce(buf[:n])
             torch.cuda.current_stream().synchronize()
 
     def _exchange_vector(self, vec, which):
@@ -382,6 +403,7 @@ class VertexHalo(Halo):
     def __init__(self, local: LocalPart, subdomain_list):
         super().__init__()
         self.local = local
+        self.rank = local.rank
         self.keys = {"bulk": {}, "mem": {}}       # kind -> {s: (global ids ascending, owners, device offset)}
         off = qoff = 0
         self.owned_dofs = 0
@@ -394,6 +416,7 @@ class VertexHalo(Halo):
                 qv = sd["mesh_mem"].parent_vertices
                 self.keys["mem"][s] = (local.vert_global[qv], local.vert_owner[qv], qoff)
                 qoff += len(qv)
+        self.n_local = {"bulk": off, "mem": qoff}
 
     def build(self, gather_objects):
         """`gather_objects(obj) -> [obj of rank 0, ..., obj of rank world-1]`."""

@@ -57,8 +57,10 @@ class SlabHalo(Halo):
     def __init__(self, layout, sub_keys, sub_offsets, q_keys, q_offsets):
         super().__init__()
         self.layout = layout
+        self.rank = layout.rank
         self.sub_keys, self.sub_offsets = sub_keys, sub_offsets
         self.q_keys, self.q_offsets = q_keys, q_offsets
+        self.n_local = {"bulk": sum(len(k[0]) for k in sub_keys.values()), "mem": sum(len(k[0]) for k in q_keys.values())}
 
     # -- set-up handshake: tell each neighbour which of its owned plane entries we hold as ghosts ----
     def _needs(self):

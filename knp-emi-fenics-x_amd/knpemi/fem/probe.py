@@ -131,11 +131,13 @@ class BucketGrid:
         return self.el[a:b]                 # ascending element numbers
 
 
-def _locate(grid, simplex, p, what):
+def _locate(grid, simplex, p, what, mask=None):
     p = np.asarray(p, np.float64).ravel()
     if p.shape[0] != grid.x.shape[1]:
         raise ValueError(f"point {p.tolist()} has {p.shape[0]} coordinates, the mesh {grid.x.shape[1]}")
     cand = grid.candidates(p)
+    if mask is not None:
+        cand = cand[mask[cand]]
     if cand.size:
         slack, W = _weights_in(grid.x[grid.cells[cand]], p, simplex)
         ok = np.flatnonzero(slack >= -TOL)
@@ -148,14 +150,15 @@ def _locate(grid, simplex, p, what):
 class Locator:
     """Point location in one (sub-)mesh: `weights(p)` -> (vertex ids, shape-function weights)."""
 
-    def __init__(self, mesh, what="the mesh"):
+    def __init__(self, mesh, what="the mesh", cell_mask=None):
         self.mesh = mesh
         self.simplex = mesh.cell_type in ("triangle", "tetrahedron", "interval")
         self.grid = BucketGrid(mesh.x, mesh.cells)
         self.what = what
+        self.mask = None if cell_mask is None else np.asarray(cell_mask, bool)    # only these cells may take a point
 
     def cell(self, p):
-        return _locate(self.grid, self.simplex, p, self.what)
+        return _locate(self.grid, self.simplex, p, self.what, self.mask)
 
     def weights(self, p):
         c, w = self.cell(p)
@@ -182,13 +185,16 @@ def membrane_weights(subdomain_list, tag, p):
 
 
 # -- reduction weights -------------------------------------------------------------------------------
-def integral_weights(mesh):
+def integral_weights(mesh, cell_mask=None):
     """w_j = integral of the j-th P1/Q1 basis function over the mesh (cells, or facets of a membrane
     sub-mesh): sum_j w_j u_j is the exact integral of u.  Simplices: |K| / (d + 1) per vertex; Q1: 2-point
     Gauss per direction on cells (exact: the integrand is of degree <= 3 per variable), 4-point on
-    quadrilateral facets (exact on planar ones)."""
+    quadrilateral facets (exact on planar ones).  cell_mask: integrate over these cells only (the cells one rank
+    of a partitioned run records)."""
     x = np.asarray(mesh.x, np.float64)
     cells = np.asarray(mesh.cells, np.int64)
+    if cell_mask is not None:
+        cells = cells[np.asarray(cell_mask, bool)]
     X = x[cells]
     nc, nv, g = X.shape
     w = np.zeros(x.shape[0])

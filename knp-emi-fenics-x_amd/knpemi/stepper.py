@@ -77,6 +77,7 @@ class DeviceStepper:
         self.flags_emi = L.WANT_P | (0 if a.splitting_scheme else L.NO_SPLITTING)
         self.flags_knp = 0 if a.splitting_scheme else L.NO_SPLITTING
         self._obs = None           # attached Observables (observe)
+        self._obs_halo = None      # the halo of a partitioned observe
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -136,16 +137,27 @@ class DeviceStepper:
             self._obs.clear()
 
     # -- observables -------------------------------------------------------------------------------
-    def observe(self, obs, every=1, capacity=1024, t0=0.0):
+    def observe(self, obs, every=1, capacity=1024, t0=0.0, halo=None):
         """Record the observables `obs` (knpemi.observables.Observables) on the device after every `every`-th step,
         at time t0 + k dt for step k.  Rows collect in a device buffer of `capacity` rows; the host keeps the times of
         the rows it has enqueued and drains the buffer into `obs` (one synchronisation) whenever it holds `capacity`
-        of them, and when `obs.series()` is called."""
+        of them, and when `obs.series()` is called.
+
+        halo: this rank's attached halo on a cell-partitioned problem (collective: every rank calls observe with the
+        same definitions, every and capacity).  Every rank then records the global row -- partial rows summed over the
+        ranks on the device at each record (Observables.partition) -- and `step(halo)` records with the same halo.
+        Draining stays rank-local."""
         if every < 1 or capacity < 1:
             raise ValueError("every and capacity must be positive")
         if obs._drain is not None:
             raise RuntimeError("these observables are attached to a stepper already")
-        obs.upload(self.dp, capacity)
+        self._obs_halo, self._obs_keep = halo, None
+        if halo is None:
+            obs.upload(self.dp, capacity)
+        else:
+            if halo.dp is not self.dp:
+                raise ValueError("observe(halo=...): attach the halo to this stepper's problem first (halo.attach)")
+            self._obs_keep = obs.upload_partitioned(self.dp, capacity, halo, every)
         self._obs, self._obs_every, self._obs_capacity, self._obs_t0 = obs, int(every), int(capacity), float(t0)
         self._obs_pending = []
         obs.clear()
@@ -198,9 +210,9 @@ class DeviceStepper:
     # -- one time step, everything enqueued on the handle's stream ---------------------------
     def step(self, halo=None):
         dp, lib = self.dp, self.lib
-        if halo is not None and self._obs is not None:
-            raise NotImplementedError("observables are not recorded on partitioned problems yet (every rank would "
-                                      "have to record the points it owns and rank 0 gather them)")
+        if halo is not None and self._obs is not None and halo is not self._obs_halo:
+            raise NotImplementedError("observables attached without a halo are not recorded on partitioned steps: "
+                                      "pass halo= to DeviceStepper.observe")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
@@ -279,7 +291,11 @@ class DeviceStepper:
         if self._obs is not None and self.k % self._obs_every == 0:
             # on the main stream behind the end-of-step update (update_pde_kernel or the fused KNP write-back); the next
             # step's side-stream launches fork from the main stream after it (ev_fork), so none of them overtakes it
-            L.check(lib.knpemi_observe_record(dp.h))
+            rc = lib.knpemi_observe_record(dp.h)
+            err = getattr(self._obs_halo, "_hook_error", None)
+            if rc != L.OK and err is not None:      # the all-reduce of a partitioned record failed in Python
+                raise err
+            L.check(rc)
             self._obs_pending.append(self._obs_t0 + self.k * self.dt)
             if len(self._obs_pending) == self._obs_capacity:
                 self._observe_drain()
