@@ -205,7 +205,7 @@ inline int split_aggregates(const HostCsr& A, const std::vector<double>& d, doub
   return cnt;
 }
 
-// Aggregation that keeps strongly POSITIVELY coupled unknowns apart (KnAmg::positive_conflict).  On the first coarse level of
+// Aggregation that keeps strongly POSITIVELY coupled unknowns apart (KnAmgConfig::positive_conflict).  On the first coarse level of
 // the DG systems on stretched hexahedra the two ends of a cell are coupled by +0.5 sqrt(a_ii a_jj) (the mass-like factor
 // of the long direction): the smooth error takes independent values there, but each end is negatively coupled to the
 // in-plane neighbours of the other one just above the strength threshold, and the plain greedy pass glues the two

@@ -198,8 +198,8 @@ void launch_spmv(hipStream_t st, int n, int avg_row, const int* rp, const int* c
 // y = (x ? x : 0) + omega_block B^-1 v on the finest level
 void block_apply(hipStream_t st, const KnAmg& G, int n, const double* v, const double* x, double* y) {
   dim3 g((n + 255) / 256);
-  if (G.block == 3) hipLaunchKernelGGL(amg_block_apply_kernel<3>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
-  else if (G.block == 4) hipLaunchKernelGGL(amg_block_apply_kernel<4>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
+  if (G.cfg.block == 3) hipLaunchKernelGGL(amg_block_apply_kernel<3>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
+  else if (G.cfg.block == 4) hipLaunchKernelGGL(amg_block_apply_kernel<4>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
   else hipLaunchKernelGGL(amg_block_apply_kernel<8>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
 }
 
@@ -298,11 +298,8 @@ int kn_amg_rebuild_step(knpemi_handle* h, KnAmg& G, int n, const int* d_rowptr, 
     if (int rc = amg_fetch(h, n, d_rowptr, d_colind, d_vals, A)) return rc;
     // the new hierarchy takes the configuration of the old one (copy), none of its levels
     a.next = KnAmg();
-    a.next.negative_strength = G.negative_strength; a.next.theta = G.theta; a.next.want_fused = G.want_fused;
-    a.next.first_agg = G.first_agg; a.next.first_na = G.first_na; a.next.split_first = G.split_first;
-    a.next.positive_conflict = G.positive_conflict; a.next.sub_fused = G.sub_fused; a.next.want_cycle = G.want_cycle;
-    a.next.filter_theta = G.filter_theta; a.next.first_tentative = G.first_tentative; a.next.split_theta = G.split_theta;
-    a.next.block = G.block; a.next.its_last = G.its_last; a.next.builds = G.builds;
+    a.next.cfg = G.cfg;
+    a.next.its_last = G.its_last; a.next.builds = G.builds;
     a.state.store(1);
     if (a.th.joinable()) a.th.join();
     const int device = h->device;
@@ -357,18 +354,18 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
         return KNPEMI_EINVAL;
       }
 
-  const double theta = G.theta;
+  const double theta = G.cfg.theta;
   const bool verbose = getenv("KNPEMI_AMG_VERBOSE") != nullptr;
   const auto t_start = std::chrono::steady_clock::now();
   // fused cycle: one level fewer is worth more than a cheaper coarsest solve (every level costs two launches per cycle)
-  const bool fused_loops = G.want_fused && G.block == 0 && !h_owned && G.first_na == 0;
+  const bool fused_loops = G.cfg.want_fused && G.cfg.block == 0 && !h_owned && G.cfg.first_na == 0;
   // (want_cycle: the merged operators for kn_fused_subcycle from level 0 on a partitioned problem, where the Krylov loop
   // itself stays the plain one)
-  const bool fused = fused_loops || (G.want_cycle && G.block == 0 && G.first_na == 0);
+  const bool fused = fused_loops || (G.cfg.want_cycle && G.cfg.block == 0 && G.cfg.first_na == 0);
   // (a non-singular system of several independent blocks may end on a larger dense level: dense_inverse works block by block)
   static const int nd_env = getenv("KNPEMI_AMG_NDENSE") ? atoi(getenv("KNPEMI_AMG_NDENSE")) : 0;
   // (block-smoothed hierarchies take the same limits: 5.20 -> 5.06 ms per DG step at config 2, 9.7 -> 9.0 CG iterations)
-  const int n_dense = nd_env > 0 ? nd_env : (fused || G.sub_fused) ? (singular ? 1024 : 2048) : 640, max_levels = 12;
+  const int n_dense = nd_env > 0 ? nd_env : (fused || G.cfg.sub_fused) ? (singular ? 1024 : 2048) : 640, max_levels = 12;
   G.fused_ok = false;
   int rc;
   G.singular = singular;
@@ -402,16 +399,16 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
     }
     L.omega = 4.0 / (3.0 * rho);
     L.avg_row = cur.n ? (int)(cur.ci.size() / (size_t)cur.n) : 0;
-    if (l == 0 && G.block > 0) {
-      if (cur.n % G.block || (G.block != 3 && G.block != 4 && G.block != 8)) {
+    if (l == 0 && G.cfg.block > 0) {
+      if (cur.n % G.cfg.block || (G.cfg.block != 3 && G.cfg.block != 4 && G.cfg.block != 8)) {
         kn_set_error("AMG set-up: bad smoother block size");
         return KNPEMI_EINVAL;
       }
-      const double rb = estimate_rho_block(cur, G.block);
+      const double rb = estimate_rho_block(cur, G.cfg.block);
       if (!(rb > 0)) { kn_set_error("AMG set-up: singular diagonal block"); return KNPEMI_ESOLVE; }
       G.omega_block = 4.0 / (3.0 * rb);
       void* pb = nullptr;
-      KN_HIP(hipMalloc(&pb, (size_t)cur.n * G.block * sizeof(double)));
+      KN_HIP(hipMalloc(&pb, (size_t)cur.n * G.cfg.block * sizeof(double)));
       G.allocs.push_back(pb);
       G.binv = static_cast<double*>(pb);
     }
@@ -424,15 +421,15 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
     if ((rc = upload(G, dinv, &L.dinv, st))) return rc;
     std::vector<int> agg;
     int na = 0;
-    if (l == 0 && G.first_na > 0 && (int)G.first_agg.size() == cur.n) {
-      agg = G.first_agg;
-      na = G.first_na;
-      if (G.split_first) na = split_aggregates(cur, d, G.split_theta, h_owned, agg, na);
+    if (l == 0 && G.cfg.first_na > 0 && (int)G.cfg.first_agg.size() == cur.n) {
+      agg = G.cfg.first_agg;
+      na = G.cfg.first_na;
+      if (G.cfg.split_first) na = split_aggregates(cur, d, G.cfg.split_theta, h_owned, agg, na);
     } else if (cur.n > n_dense) {
       // a threshold that leaves (almost) no strong connections stalls the coarsening: relax it for this level
       double th = theta;
       for (int attempt = 0; attempt < 6; ++attempt, th = attempt == 5 ? 0.0 : 0.5 * th) {
-        na = G.positive_conflict ? aggregate_apart(cur, d, th, 0.2, agg) : aggregate(cur, d, th, G.negative_strength, agg);
+        na = G.cfg.positive_conflict ? aggregate_apart(cur, d, th, 0.2, agg) : aggregate(cur, d, th, G.cfg.negative_strength, agg);
         if (na < cur.n * 0.7) break;
       }
     }
@@ -457,15 +454,15 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
     }
     // given aggregates (auxiliary space): the piecewise-constant prolongator IS the embedding of that space (every broken
     // dof takes the value of its vertex); smoothing it would only widen the stencil of every coarser operator
-    const bool given = l == 0 && G.first_na > 0 && (int)G.first_agg.size() == cur.n;
-    HostCsr P = smoothed_prolongator(cur, d, agg, na, given && G.first_tentative ? 0.0 : L.omega, G.filter_theta);
+    const bool given = l == 0 && G.cfg.first_na > 0 && (int)G.cfg.first_agg.size() == cur.n;
+    HostCsr P = smoothed_prolongator(cur, d, agg, na, given && G.cfg.first_tentative ? 0.0 : L.omega, G.cfg.filter_theta);
     HostCsr R = transpose(P);
     L.nc = na;
     L.p_row = std::max(1, (int)(P.ci.size() / (size_t)P.n));
     L.r_row = std::max(1, (int)(R.ci.size() / (size_t)R.n));
     if ((rc = upload_csr(G, P, L.P, st))) return rc;
     if ((rc = upload_csr(G, R, L.R, st))) return rc;
-    if (fused || (G.sub_fused && l >= 1)) {
+    if (fused || (G.cfg.sub_fused && l >= 1)) {
       // V(1,1) from a zero guess is  x = w D^-1 (r + t) + Pm e_c,  t = (I - w A D^-1) r,  e_c = cycle(Rm r)  with the
       // smoother folded into the transfer operators: restriction and residual, prolongation and post-smoothing become
       // one SpMV each (kernels_fused.hip)
@@ -503,7 +500,7 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
   G.op_complexity = G.lev[0].A.nnz ? (double)tot / G.lev[0].A.nnz : 1.0;
   G.fused_ok = fused_loops && G.lev.size() >= 2 && G.lev.back().dense_inv != nullptr;
   G.cycle_ok = fused && !fused_loops && G.lev.size() >= 2 && G.lev.back().dense_inv != nullptr;
-  G.sub_fused_ok = G.sub_fused && G.block > 0 && G.lev.size() >= 3 && G.lev.back().dense_inv != nullptr;
+  G.sub_fused_ok = G.cfg.sub_fused && G.cfg.block > 0 && G.lev.size() >= 3 && G.lev.back().dense_inv != nullptr;
   if (G.sub_fused_ok || G.cycle_ok) {
     void* z = nullptr;
     KN_HIP(hipMalloc(&z, 32 * sizeof(double)));
@@ -524,7 +521,7 @@ int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* d
   hipStream_t st = h->stream;
   const int nl = (int)G.lev.size();
   if (G.cycle_ok) return kn_fused_subcycle(h, G, 0, r, out);
-  if (G.sub_fused_ok && G.block > 0) {
+  if (G.sub_fused_ok && G.cfg.block > 0) {
     // finest level: block-Jacobi sweeps and residuals here, everything below through the merged transfer operators
     KnAmgLevel& L = G.lev[0];
     auto residual = [&](const double* x, double* y) {
@@ -557,7 +554,7 @@ int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* d
       }
       break;
     }
-    if (l == 0 && G.block > 0) {   // x = w B^-1 r, t = r - A x
+    if (l == 0 && G.cfg.block > 0) {   // x = w B^-1 r, t = r - A x
       block_apply(st, G, L.n, rl, nullptr, xl);
       if (h->bcols.bcol) launch_block_spmv<double>(st, h->bcols, L.n, L.A.rp, Av, xl, rl, L.t, nullptr);
       else launch_spmv<M_RES>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, xl, rl, nullptr, 0.0, L.t);
@@ -571,7 +568,7 @@ int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* d
     const double* Av = l == 0 ? vals : L.A.v;
     const double* dinv = l == 0 ? dinv0 : L.dinv;
     launch_spmv<M_ADD>(st, L.n, L.p_row, L.P.rp, L.P.ci, L.P.v, G.lev[l + 1].t, nullptr, nullptr, 0.0, xl);
-    if (l == 0 && G.block > 0) {   // out = x + w B^-1 (r - A x); the level's t is free again
+    if (l == 0 && G.cfg.block > 0) {   // out = x + w B^-1 (r - A x); the level's t is free again
       if (h->bcols.bcol) launch_block_spmv<double>(st, h->bcols, L.n, L.A.rp, Av, xl, rl, L.t, nullptr);
       else launch_spmv<M_RES>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, xl, rl, nullptr, 0.0, L.t);
       block_apply(st, G, L.n, L.t, xl, out);
@@ -581,16 +578,16 @@ int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* d
 }
 
 int kn_amg_refresh(knpemi_handle* h, KnAmg& G, const double* vals) {
-  if (!G.built || G.block <= 0 || G.lev.empty() || G.lev[0].nc == 0) return KNPEMI_OK;
+  if (!G.built || G.cfg.block <= 0 || G.lev.empty() || G.lev[0].nc == 0) return KNPEMI_OK;
   const KnAmgLevel& L = G.lev[0];
-  const int nb = L.n / G.block;
+  const int nb = L.n / G.cfg.block;
   dim3 g(((size_t)nb * 4 + 255) / 256), g8(((size_t)nb * 8 + 255) / 256);
   const KnBlockCols& B = h->bcols;
-  const int* bc = (B.bcol && B.nv == G.block) ? B.bcol : nullptr;
+  const int* bc = (B.bcol && B.nv == G.cfg.block) ? B.bcol : nullptr;
   const int cps = bc ? B.n / B.nv : 1;
-  if (G.block == 3) hipLaunchKernelGGL(amg_block_inv_kernel<3>, g, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
-  else if (G.block == 4) hipLaunchKernelGGL(amg_block_inv_kernel<4>, g, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
-  else if (G.block == 8) hipLaunchKernelGGL(amg_block_inv_kernel<8>, g8, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
+  if (G.cfg.block == 3) hipLaunchKernelGGL(amg_block_inv_kernel<3>, g, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
+  else if (G.cfg.block == 4) hipLaunchKernelGGL(amg_block_inv_kernel<4>, g, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
+  else if (G.cfg.block == 8) hipLaunchKernelGGL(amg_block_inv_kernel<8>, g8, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
   else { kn_set_error("AMG: smoother blocks of 3, 4 or 8 unknowns only"); return KNPEMI_EINVAL; }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { kn_set_error(std::string("amg_block_inv_kernel: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }

@@ -850,15 +850,7 @@ extern "C" void knpemi_dg_destroy(knpemi_dg* h) {
   for (void* p : h->allocs) (void)hipFree(p);
   kn_comm_free(h->comm);
   if (h->sol) {
-    kn_amg_async_join(h->sol->amg_emi);
-    kn_amg_async_join(h->sol->amg_knp);
-    kn_amg_free(h->sol->amg_emi);
-    kn_amg_free(h->sol->amg_knp);
-    if (h->sol->kry_pinned) (void)hipHostFree(h->sol->kry_pinned);
-    if (h->sol->pub_host) (void)hipHostFree(h->sol->pub_host);
-    kn_fused_graphs_free(h->sol);
-    if (h->sol->graph_emi.exec) (void)hipGraphExecDestroy(h->sol->graph_emi.exec);
-    if (h->sol->graph_knp.exec) (void)hipGraphExecDestroy(h->sol->graph_knp.exec);
+    kn_solver_free(h->sol);
     for (void* p : h->sol->allocs) (void)hipFree(p);
     delete h->sol;
   }
@@ -1314,6 +1306,19 @@ extern "C" int knpemi_dg_update(knpemi_dg* h, const double* c_new, int on_device
 
 namespace {
 
+// Given aggregates of the finest level of both hierarchies: `agg` (na of them) over the n dofs for the potential, one copy
+// per solved ion for the concentrations.  KNPEMI_DG_PLAIN_AMG=1: none, every level is aggregated by strength.
+void dg_first_aggregates(knpemi_handle* s, const std::vector<int>& agg, int na, int KS, int n) {
+  if (getenv("KNPEMI_DG_PLAIN_AMG")) return;
+  s->amg_emi.cfg.first_agg = agg;
+  s->amg_emi.cfg.first_na = na;
+  std::vector<int>& ka = s->amg_knp.cfg.first_agg;
+  ka.resize((size_t)KS * n);
+  for (int k = 0; k < KS; ++k)
+    for (int i = 0; i < n; ++i) ka[(size_t)k * n + i] = k * na + agg[i];
+  s->amg_knp.cfg.first_na = KS * na;
+}
+
 // The solver handle of a DG problem: stream, systems and the potential component of the dof records (same 64-byte
 // layout as the CG vertex records), nothing else.
 int dg_solver(knpemi_dg* h, knpemi_handle** out) {
@@ -1362,24 +1367,20 @@ int dg_solver(knpemi_dg* h, knpemi_handle** out) {
     if ((rc = dg_upload(h, bcol, &d_bcol))) return rc;
     s->bcols.bcol = d_bcol; s->bcols.nv = NV; s->bcols.nbmax = nbmax; s->bcols.n = n;
   }
-  s->amg_emi.first_agg = h->aux_of;
-  s->amg_emi.first_na = h->n_aux;
-  s->amg_knp.first_agg.resize((size_t)KS * n);
-  for (int k = 0; k < KS; ++k)
-    for (int i = 0; i < n; ++i) s->amg_knp.first_agg[(size_t)k * n + i] = k * h->n_aux + h->aux_of[i];
-  s->amg_knp.first_na = KS * h->n_aux;
-  s->amg_emi.block = s->amg_knp.block = h->NV;       // block-Jacobi smoothing over the dofs of a cell
-  // the vertex aggregates are split along the weakly penalised facets (KnAmg::split_first; KNPEMI_DG_AUX_UNSPLIT=1 keeps
-  // the continuous P1 space as the first coarse level)
-  s->amg_emi.split_first = s->amg_knp.split_first = !getenv("KNPEMI_DG_AUX_UNSPLIT");
-  s->amg_emi.first_tentative = s->amg_knp.first_tentative = !getenv("KNPEMI_DG_AUX_SMOOTHED");
-  s->amg_emi.positive_conflict = s->amg_knp.positive_conflict = !getenv("KNPEMI_DG_PLAIN_AGGREGATION");
-  s->amg_emi.filter_theta = s->amg_knp.filter_theta = 0.02;   // (as kernels_krylov.hip)
-  s->amg_emi.sub_fused = s->amg_knp.sub_fused = !getenv("KNPEMI_DG_NO_SUBCYCLE");   // merged transfer operators below the finest level
-  if (const char* ft = getenv("KNPEMI_AMG_FILTER")) s->amg_emi.filter_theta = s->amg_knp.filter_theta = atof(ft);
-  if (const char* th = getenv("KNPEMI_DG_THETA")) s->amg_emi.theta = s->amg_knp.theta = atof(th);
-  if (getenv("KNPEMI_DG_PLAIN_AMG")) { s->amg_emi.first_na = s->amg_knp.first_na = 0; }
-  if (getenv("KNPEMI_DG_POINT_JACOBI")) { s->amg_emi.block = s->amg_knp.block = 0; }
+  KnAmgConfig cfg;
+  cfg.block = h->NV;                                 // block-Jacobi smoothing over the dofs of a cell
+  // the vertex aggregates are split along the weakly penalised facets (KnAmgConfig::split_first; KNPEMI_DG_AUX_UNSPLIT=1
+  // keeps the continuous P1 space as the first coarse level)
+  cfg.split_first = !getenv("KNPEMI_DG_AUX_UNSPLIT");
+  cfg.first_tentative = !getenv("KNPEMI_DG_AUX_SMOOTHED");
+  cfg.positive_conflict = !getenv("KNPEMI_DG_PLAIN_AGGREGATION");
+  cfg.filter_theta = 0.02;                           // (as kernels_krylov.hip)
+  cfg.sub_fused = !getenv("KNPEMI_DG_NO_SUBCYCLE");  // merged transfer operators below the finest level
+  if (const char* ft = getenv("KNPEMI_AMG_FILTER")) cfg.filter_theta = atof(ft);
+  if (const char* th = getenv("KNPEMI_DG_THETA")) cfg.theta = atof(th);
+  if (getenv("KNPEMI_DG_POINT_JACOBI")) cfg.block = 0;
+  s->amg_emi.cfg = s->amg_knp.cfg = cfg;
+  dg_first_aggregates(s, h->aux_of, h->n_aux, KS, n);
   h->sol = s;
   *out = s;
   return KNPEMI_OK;
@@ -1434,14 +1435,7 @@ extern "C" int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, voi
   } else {
     agg = h->aux_of;
   }
-  if (!getenv("KNPEMI_DG_PLAIN_AMG")) {
-    s->amg_emi.first_agg = agg;
-    s->amg_emi.first_na = na;
-    s->amg_knp.first_agg.resize((size_t)KS * n);
-    for (int k = 0; k < KS; ++k)
-      for (int i = 0; i < n; ++i) s->amg_knp.first_agg[(size_t)k * n + i] = k * na + agg[i];
-    s->amg_knp.first_na = KS * na;
-  }
+  dg_first_aggregates(s, agg, na, KS, n);
   if (!owned) { d.on = false; return KNPEMI_OK; }
   if (!reduce_buf_dev || !allreduce || !halo)
     return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_distributed: reduction buffer and both communication hooks are required");

@@ -735,13 +735,16 @@ struct Loop {
                        C.dense_blk, C.r, C.x, red, np);
   }
 
+  // Partial sums the finest up kernel leaves with DOTS != 0 (CG's r.z): what the next direction kernel reads
+  int np_rz() const { return capped(blocks16(G.lev[0].n)); }
+
   // out = V-cycle(in) on the frozen hierarchy.  IN: how the finest level forms its input (down_kernel); np: partial sums
-  // its scalar needs; par: parity of the iteration.  CHECK: CG's convergence test in the coarsest kernel.  Returns the
-  // number of partial sums the finest kernels leave (IN_CG: r.r by the first, DOTS: r.z by the last).
+  // its scalar needs; par: parity of the iteration.  CHECK: CG's convergence test in the coarsest kernel, on the r.r
+  // partial sums the finest down kernel leaves with IN_CG.
   template <int IN, int DOTS, bool CHECK>
-  void cycle(const double* r, const double* u, const double* w, double* formed, double* x, double* out, int np, int par,
-             int* np_rr, int* np_rz) {
+  void cycle(const double* r, const double* u, const double* w, double* formed, double* x, double* out, int np, int par) {
     const int nl = (int)G.lev.size();
+    int np_rr = 0;
     for (int l = 0; l + 1 < nl; ++l) {
       KnAmgLevel& L = G.lev[l];
       DownArgs a{};
@@ -754,7 +757,7 @@ struct Loop {
       if (l == 0) {
         a.r = r; a.u = u; a.w = w; a.out = formed; a.x = x;
         const int nb = IN == IN_CG ? capped(down_blocks(L, l0)) : down_blocks(L, l0);
-        if (np_rr) *np_rr = nb;
+        if (IN == IN_CG) np_rr = nb;
         static const bool split = getenv("KNPEMI_FUSED_NO_SPLIT") == nullptr;
         if ((IN == IN_BI_P || IN == IN_BI_S) && split) {
           hipLaunchKernelGGL((form_kernel<IN>), dim3(capped((L.n + FT - 1) / FT)), dim3(FT), 0, st, a);
@@ -768,7 +771,7 @@ struct Loop {
         launch_down<IN_PLAIN>(LPR, down_blocks(L, LPR), a);
       }
     }
-    launch_dense<CHECK>(G.lev[nl - 1], np_rr ? *np_rr : 0);
+    launch_dense<CHECK>(G.lev[nl - 1], np_rr);
     for (int l = nl - 2; l >= 0; --l) {
       KnAmgLevel& L = G.lev[l];
       UpArgs a{};
@@ -779,9 +782,7 @@ struct Loop {
       a.red = red;
       if (l == 0) {
         a.r = IN == IN_PLAIN ? r : formed; a.x = out;
-        const int nb = DOTS != 0 ? capped(blocks16(L.n)) : blocks16(L.n);
-        if (np_rz) *np_rz = nb;
-        hipLaunchKernelGGL((up_kernel<DOTS>), dim3(nb), dim3(FT), 0, st, a);
+        hipLaunchKernelGGL((up_kernel<DOTS>), dim3(DOTS != 0 ? np_rz() : blocks16(L.n)), dim3(FT), 0, st, a);
       } else {
         a.r = L.r; a.x = L.x;
         hipLaunchKernelGGL((up_kernel<0>), dim3(blocks16(L.n)), dim3(FT), 0, st, a);
@@ -1004,25 +1005,14 @@ void record_mode(knpemi_handle* h, int sys, bool graph, double us_per_iteration)
 uint64_t mix(uint64_t k, uint64_t v) { return (k ^ v) * 0x9E3779B97F4A7C15ull + (k << 6) + (k >> 2); }
 uint64_t bits(double d) { uint64_t u; memcpy(&u, &d, sizeof u); return u; }
 
-template <class Enqueue>
-int run_chunk_graph(knpemi_handle* h, uint64_t key, Enqueue&& enqueue, bool use_graph) {
+// Enqueue a chunk, or (use_graph) launch its graph, captured at the first use of `key`
+int run_chunk_graph(knpemi_handle* h, uint64_t key, const std::function<int()>& enqueue, bool use_graph) {
   if (!use_graph) return enqueue();
   auto it = h->fused_graphs.find(key);
   if (it == h->fused_graphs.end()) {
-    if (h->fused_graphs.size() >= 96) {      // tolerances or hierarchies that keep changing: start over rather than grow
-      for (auto& kv : h->fused_graphs) (void)hipGraphExecDestroy(kv.second);
-      h->fused_graphs.clear();
-    }
-    hipGraph_t graph = nullptr;
-    KN_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue();
-    hipError_t e = hipStreamEndCapture(h->stream, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) { kn_set_error(std::string("fused loop, hipStreamEndCapture: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+    if (h->fused_graphs.size() >= 96) kn_fused_graphs_free(h);   // tolerances or hierarchies that keep changing: start over
     hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) { kn_set_error(std::string("fused loop, hipGraphInstantiate: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+    if (int rc = kn_capture(h, enqueue, &exec)) return rc;
     it = h->fused_graphs.emplace(key, exec).first;
   }
   KN_HIP(hipGraphLaunch(it->second, h->stream));
@@ -1038,6 +1028,71 @@ int lanes0(const KnAmg& G) { return G.lev[0].avg_row <= 24 ? 4 : LPR; }
     else hipLaunchKernelGGL(KERN16, grid, dim3(FT), 0, st, __VA_ARGS__);                \
   } while (0)
 
+// The state after a chunk (published by its last kernel, or copied): read and checked for non-finite input and residuals
+int chunk_state(knpemi_handle* h, const KnFusedSys& S, double* sc, bool published, const char* who) {
+  if (published) ++h->pub_expected;
+  if (int rc = read_state(h, S.sc, sc, published)) return rc;
+  if (int rc = bad_input(who, sc)) return rc;
+  if (!std::isfinite(sc[S_RR])) { kn_set_error(std::string(who) + " broke down (non-finite residual) " + describe(sc)); return KNPEMI_ESOLVE; }
+  return KNPEMI_OK;
+}
+
+// End of a fused solve: launch errors, the size of the next solve's first chunk, the caller's outputs
+int finish_solve(KnAmg& G, const double* sc, int it, const char* what, int* iters, double* rr_out, double* bb_out) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { kn_set_error(std::string(what) + ": " + hipGetErrorString(e)); return KNPEMI_EHIP; }
+  G.its_last = it;
+  *iters = it;
+  *rr_out = sc[S_RR];
+  *bb_out = sc[S_BB];
+  return KNPEMI_OK;
+}
+
+// A fused solve (CG, BiCGStab) as chunks of iterations, each one graph launch or direct launches (choose_mode).  The first
+// chunk is head() and as many iterations as the previous solve of the system took (at least min_it), every further chunk
+// one iteration; each ends with tail() (idempotent) and the publication of the state.  iterations(k, count) enqueues
+// iterations k .. k + count - 1 and the end-of-chunk test.  What a chunk launches depends on the key (`seed`: the solver's
+// own configuration), on whether it is the first, on its size and on the parity of k -- nothing else the host holds --, so
+// a replayed chunk needs no host code beyond k += count.  between(sc) runs when a chunk has not ended the solve, before the
+// next one is enqueued.  head_cost: the head's share of the first chunk's time in iterations (choose_mode's timing).
+int fused_chunks(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, int sys, const char* who, const char* what, uint64_t seed,
+                 double rtol, double atol, int maxit, int min_it, double head_cost, const std::function<int()>& head,
+                 const std::function<int(int, int)>& iterations, const std::function<int()>& tail,
+                 const std::function<int(const double*)>& between, int* iters, double* rr_out, double* bb_out) {
+  int rc;
+  Publish pub{};
+  const bool use_pub = publish_usable();
+  if (use_pub && (rc = ensure_publish(h, &pub))) return rc;
+  const ModeChoice mode = choose_mode(h, sys);
+  const auto t_start = std::chrono::steady_clock::now();
+  uint64_t base = mix(mix(mix(mix(seed, (uint64_t)(uintptr_t)S.work), (uint64_t)G.builds), bits(rtol)), bits(atol));
+  base = mix(mix(base, (uint64_t)S.n), use_pub ? 1 : 0);
+  double sc[S_NF];
+  int it = 0, k = 0, todo = std::max(first_chunk(G.its_last, maxit), min_it);
+  for (bool first = true;; first = false) {
+    const int k0 = k;
+    auto chunk = [&]() -> int {
+      if (first) if (int e = head()) return e;
+      if (int e = iterations(k0, todo)) return e;
+      if (int e = tail()) return e;
+      if (use_pub) enqueue_publish(h, pub, S.sc);
+      return KNPEMI_OK;
+    };
+    if ((rc = run_chunk_graph(h, mix(mix(mix(base, first ? 1 : 0), (uint64_t)todo), (uint64_t)(k0 & 1)), chunk, mode.graph)))
+      return rc;
+    k += todo;
+    if ((rc = chunk_state(h, S, sc, use_pub, who))) return rc;
+    if (first && mode.timed)
+      record_mode(h, sys, mode.graph,
+                  std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count() / (todo + head_cost));
+    it = (int)sc[S_IT];
+    if (sc[S_DONE] != 0.0 || it >= maxit) break;
+    if (between && (rc = between(sc))) return rc;
+    todo = 1;
+  }
+  return finish_solve(G, sc, it, what, iters, rr_out, bb_out);
+}
+
 }  // namespace
 
 void kn_fused_graphs_free(knpemi_handle* h) {
@@ -1052,13 +1107,16 @@ int kn_fused_cg(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b
                 double* rr_out, double* bb_out, double* phi, int phi_stride) {
   const int n = S.n;
   const size_t N = S.N;
-  double *x = S.work, *r = x + N, *z = r + N, *p = z + N, *q = p + N, *r2 = S.work + 7 * N, *p2 = S.work + 8 * N;
+  double *x = S.work, *z = x + 2 * N, *q = x + 4 * N;
+  // r, p of iteration k: rb[k & 1], pb[k & 1]; the iteration writes the next ones into the other buffers
+  double* const rb[2] = {x + N, S.work + 7 * N};
+  double* const pb[2] = {x + 3 * N, S.work + 8 * N};
   int rc = ensure_partials(h);
   if (rc) return rc;
   Loop L{h, G, S, Red{S.sc, h->fused_part}, h->stream, lanes0(G)};
   const int l0 = L.l0;
   const int nb_res = Loop::capped(L.blocks0(n)), nb_dir = Loop::capped(L.blocks0(n));
-  int np_rr = 0, np_rz = 0;
+  const int np_rz = L.np_rz();
   const int nb_vec = Loop::capped((n + FT - 1) / FT);
   const double inv_n = 1.0 / (double)n;
   // KNPEMI_OPT_FOLD_MEMBRANE: the write-back launch also integrates the membrane facets (the potential system of the CG
@@ -1070,99 +1128,56 @@ int kn_fused_cg(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b
     hipLaunchKernelGGL(emi_pre_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)phi, phi_stride, x, b, L.red);
     if (pre_norm) {
       // KSPCG's default test: |M^-1 r| <= max(atol, rtol |M^-1 b|).  The projected b goes to q (free until the first
-      // direction), M^-1 b to p2, its square norm replaces the sums of b in P_BS
+      // direction), M^-1 b to pb[1], its square norm replaces the sums of b in P_BS
       KN_LAUNCH_L0(l0, dim3(nb_res), h->stream, (residual_kernel<4, true>), (residual_kernel<16, true>), n, S.rowptr, S.colind,
-                   S.vals, (const double*)x, b, r, (double*)nullptr, L.red, nb_vec, inv_n, q);
-      L.cycle<IN_PLAIN, 0, false>(q, nullptr, nullptr, nullptr, nullptr, p2, 0, 0, nullptr, nullptr);
-      hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)p2, L.red, (int)P_BS);
+                   S.vals, (const double*)x, b, rb[0], (double*)nullptr, L.red, nb_vec, inv_n, q);
+      L.cycle<IN_PLAIN, 0, false>(q, nullptr, nullptr, nullptr, nullptr, pb[1], 0, 0);
+      hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)pb[1], L.red, (int)P_BS);
       hipLaunchKernelGGL(gm_start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_vec, rtol, atol, 0, 1, nb_res);
       // z_0 = M^-1 r_0 with r_0.z_0 and |z_0|^2: the first direction kernel tests the initial residual
-      L.cycle<IN_PLAIN, 3, false>(r, nullptr, nullptr, nullptr, nullptr, z, 0, 0, nullptr, &np_rz);
+      L.cycle<IN_PLAIN, 3, false>(rb[0], nullptr, nullptr, nullptr, nullptr, z, 0, 0);
       return KNPEMI_OK;
     }
     KN_LAUNCH_L0(l0, dim3(nb_res), h->stream, (residual_kernel<4, true>), (residual_kernel<16, true>), n, S.rowptr, S.colind,
-                 S.vals, (const double*)x, b, r, (double*)nullptr, L.red, nb_vec, inv_n, (double*)nullptr);
+                 S.vals, (const double*)x, b, rb[0], (double*)nullptr, L.red, nb_vec, inv_n, (double*)nullptr);
     hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_res, rtol, atol, 0, 0, 0);
     // z_0 = M^-1 r_0, r_0.z_0 (rho_old = 0: the first direction is z_0)
-    L.cycle<IN_PLAIN, 1, false>(r, nullptr, nullptr, nullptr, nullptr, z, 0, 0, nullptr, &np_rz);
+    L.cycle<IN_PLAIN, 1, false>(rb[0], nullptr, nullptr, nullptr, nullptr, z, 0, 0);
     return KNPEMI_OK;
   };
-  int k = 0;     // iterations enqueued so far: their parity decides which of the alternating buffers is which
-  auto iterations = [&](int count) -> int {
-    for (int j = 0; j < count; ++j, ++k) {
+  auto iterations = [&](int k0, int count) -> int {
+    for (int k = k0; k < k0 + count; ++k) {
+      double *r = rb[k & 1], *r2 = rb[(k + 1) & 1], *p = pb[k & 1], *p2 = pb[(k + 1) & 1];
       if (pre_norm) {
         KN_LAUNCH_L0(l0, dim3(nb_dir), h->stream, (cg_dir_kernel<4, true>), (cg_dir_kernel<16, true>), n, S.rowptr, S.colind, S.vals,
                      (const double*)z, (const double*)p, p2, q, L.red, np_rz, k & 1);
         // r_new = r - alpha q (stored in r2), x += alpha p_new; z = M^-1 r_new with r_new.z and |z|^2; the iteration is counted
-        L.cycle<IN_CG, 7, false>(r, q, p2, r2, x, z, nb_dir, k & 1, &np_rr, &np_rz);
+        L.cycle<IN_CG, 7, false>(r, q, p2, r2, x, z, nb_dir, k & 1);
       } else {
         KN_LAUNCH_L0(l0, dim3(nb_dir), h->stream, (cg_dir_kernel<4, false>), (cg_dir_kernel<16, false>), n, S.rowptr, S.colind, S.vals,
                      (const double*)z, (const double*)p, p2, q, L.red, np_rz, k & 1);
         // r_new = r - alpha q (stored in r2), x += alpha p_new, |r_new|^2 -> convergence; then z = M^-1 r_new, r_new.z
-        L.cycle<IN_CG, 1, true>(r, q, p2, r2, x, z, nb_dir, k & 1, &np_rr, &np_rz);
+        L.cycle<IN_CG, 1, true>(r, q, p2, r2, x, z, nb_dir, k & 1);
       }
-      std::swap(r, r2);
-      std::swap(p, p2);
     }
     // (the test the next direction kernel would make, for the host that reads the state after this chunk)
     if (pre_norm) hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, np_rz);
     return KNPEMI_OK;
   };
-  uint64_t base = mix(mix(mix(mix(0xC6ull, (uint64_t)(uintptr_t)S.work), (uint64_t)G.builds), bits(rtol)), bits(atol));
-  base = mix(mix(mix(base, (uint64_t)n), (uint64_t)(uintptr_t)b), (uint64_t)(uintptr_t)phi);
-  base = mix(mix(base, (uint64_t)(h->fold_membrane && !h->fuse_membrane)), (uint64_t)(h->emi_flags & KNPEMI_NO_SPLITTING));
-  base = mix(base, pre_norm ? 2 : 0);
-  double sc[S_NF];
-  int it = 0, todo = first_chunk(G.its_last, maxit);
-  bool first = true;
-  Publish pub{};
-  const bool use_pub = publish_usable();
-  if (use_pub && (rc = ensure_publish(h, &pub))) return rc;
-  base = mix(base, use_pub ? 1 : 0);
-  const ModeChoice mode = choose_mode(h, 0);
-  const auto t_start = std::chrono::steady_clock::now();
-  for (;;) {
-    const int k0 = k;
-    const uint64_t key = mix(mix(mix(base, first ? 1 : 0), (uint64_t)todo), (uint64_t)(k0 & 1));
-    auto chunk = [&]() -> int {
-      if (first) if (int e = head()) return e;
-      if (int e = iterations(todo)) return e;
-      // the solution orthogonal to the constants, into the phi component of the vertex records (idempotent)
-      hipLaunchKernelGGL(x_sum_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)x, L.red);
-      if (fold) {   // ... and, in the same launch, the membrane-facet integrals of b_knp for that potential
-        if (int e = kn_launch_emi_writeback_membrane(h, x, L.red.part + (size_t)P_XS * KN_PB, nb_vec, inv_n, S.sc + S_MEAN)) return e;
-      } else
-      hipLaunchKernelGGL(emi_post_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)x, phi, phi_stride, L.red, nb_vec, inv_n);
-      if (use_pub) enqueue_publish(h, pub, S.sc);
-      return KNPEMI_OK;
-    };
-    if (mode.graph && h->fused_graphs.count(key)) {
-      // replay: the host-side state advances as if the chunk had been enqueued
-      if (first) np_rz = Loop::capped(Loop::blocks16(G.lev[0].n));
-      if ((todo & 1)) { std::swap(r, r2); std::swap(p, p2); }
-      k += todo;
-      KN_HIP(hipGraphLaunch(h->fused_graphs[key], h->stream));
-    } else if ((rc = run_chunk_graph(h, key, chunk, mode.graph))) return rc;
-    if (use_pub) ++h->pub_expected;
-    if ((rc = read_state(h, S.sc, sc, use_pub))) return rc;
-    if (first && mode.timed)
-      record_mode(h, 0, mode.graph, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count() / (todo + 1.5));
-    first = false;
-    if ((rc = bad_input("EMI CG", sc))) return rc;
-    it = (int)sc[S_IT];
-    if (!std::isfinite(sc[S_RR])) { kn_set_error("EMI CG broke down (non-finite residual) " + describe(sc)); return KNPEMI_ESOLVE; }
-    if (sc[S_DONE] != 0.0 || it >= maxit) break;
-    todo = std::min(1, maxit - it);
-    if (todo <= 0) break;
-    (void)k0;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("fused CG: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+  // the solution orthogonal to the constants, into the phi component of the vertex records (idempotent)
+  auto tail = [&]() -> int {
+    hipLaunchKernelGGL(x_sum_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)x, L.red);
+    if (fold)   // ... and, in the same launch, the membrane-facet integrals of b_knp for that potential
+      return kn_launch_emi_writeback_membrane(h, x, L.red.part + (size_t)P_XS * KN_PB, nb_vec, inv_n, S.sc + S_MEAN);
+    hipLaunchKernelGGL(emi_post_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)x, phi, phi_stride, L.red, nb_vec, inv_n);
+    return KNPEMI_OK;
+  };
+  uint64_t seed = mix(mix(mix(0xC6ull, (uint64_t)(uintptr_t)b), (uint64_t)(uintptr_t)phi), (uint64_t)(h->fold_membrane && !h->fuse_membrane));
+  seed = mix(mix(seed, (uint64_t)(h->emi_flags & KNPEMI_NO_SPLITTING)), pre_norm ? 2 : 0);
+  if ((rc = fused_chunks(h, G, S, 0, "EMI CG", "fused CG", seed, rtol, atol, maxit, 0, 1.5, head, iterations, tail, nullptr, iters,
+                         rr_out, bb_out)))
+    return rc;
   if (fold) kn_gam_formed(h, (h->emi_flags & KNPEMI_NO_SPLITTING) ? 0 : 1);   // by the write-back of every chunk, replayed or not
-  G.its_last = it;
-  *iters = it;
-  *rr_out = sc[S_RR];
-  *bb_out = sc[S_BB];
   return KNPEMI_OK;
 }
 
@@ -1173,8 +1188,10 @@ int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const dou
   const int n = S.n;
   const int min_it = std::max(0, std::min(h->knp_min_it, maxit));
   const size_t N = S.N;
-  double *x = S.work, *r = x + N, *rhat = r + N, *p = rhat + N, *v = p + N, *s = v + N, *t = s + N;
+  double *x = S.work, *r = x + N, *rhat = r + N, *v = rhat + 2 * N, *s = v + N;
   double *phat = S.work + 8 * N, *shat = S.work + 9 * N;
+  // the search direction of iteration k: pt[k & 1]; the iteration forms the next one in the other buffer
+  double* const pt[2] = {rhat + N, S.work + 6 * N};
   int rc = ensure_partials(h);
   if (rc) return rc;
   Loop L{h, G, S, Red{S.sc, h->fused_part}, h->stream, lanes0(G)};
@@ -1187,16 +1204,15 @@ int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const dou
     hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_res, rtol, atol, 1, nb_update, min_it);
     return KNPEMI_OK;
   };
-  int k = 0;
-  auto iterations = [&](int count) -> int {
-    for (int j = 0; j < count; ++j, ++k) {
+  auto iterations = [&](int k0, int count) -> int {
+    for (int k = k0; k < k0 + count; ++k) {
       // p = r + beta (p - omega v) is formed by the finest down kernel, which reads p and v at neighbouring rows while
-      // it stores its own: the new direction goes to the buffer of t (free until the second SpMV) and the two names swap
-      L.cycle<IN_BI_P, 0, false>(r, p, v, t, nullptr, phat, nb_update, k & 1, nullptr, nullptr);
-      std::swap(p, t);
+      // it stores its own: the new direction goes to the other buffer, the old one is t (free once the new one exists)
+      double *p = pt[k & 1], *p_new = pt[(k + 1) & 1], *t = p;
+      L.cycle<IN_BI_P, 0, false>(r, p, v, p_new, nullptr, phat, nb_update, k & 1);
       KN_LAUNCH_L0(l0, dim3(nb_spmv), h->stream, (bi_spmv_kernel<0, 4>), (bi_spmv_kernel<0, 16>), n, S.rowptr, S.colind, S.vals,
                    (const double*)phat, v, (const double*)rhat, L.red);
-      L.cycle<IN_BI_S, 0, false>(r, v, nullptr, s, nullptr, shat, nb_spmv, k & 1, nullptr, nullptr);
+      L.cycle<IN_BI_S, 0, false>(r, v, nullptr, s, nullptr, shat, nb_spmv, k & 1);
       KN_LAUNCH_L0(l0, dim3(nb_spmv), h->stream, (bi_spmv_kernel<1, 4>), (bi_spmv_kernel<1, 16>), n, S.rowptr, S.colind, S.vals,
                    (const double*)shat, t, (const double*)s, L.red);
       hipLaunchKernelGGL(bi_update_kernel, dim3(nb_update), dim3(FT), 0, h->stream, n, x, r, (const double*)phat,
@@ -1205,57 +1221,17 @@ int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const dou
     hipLaunchKernelGGL(bi_check_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_update);
     return KNPEMI_OK;
   };
-  Publish pub{};
-  const bool use_pub = publish_usable();
-  if (use_pub && (rc = ensure_publish(h, &pub))) return rc;
-  const ModeChoice mode = choose_mode(h, 1);
-  const auto t_start = std::chrono::steady_clock::now();
-  uint64_t base = mix(mix(mix(mix(0xB1ull, (uint64_t)(uintptr_t)S.work), (uint64_t)G.builds), bits(rtol)), bits(atol));
-  base = mix(mix(mix(mix(base, (uint64_t)n), (uint64_t)(uintptr_t)b), (uint64_t)h->fuse_update), publish_usable() ? 1 : 0);
-  double sc[S_NF];
-  base = mix(base, (uint64_t)min_it);
-  int it = 0, restarts = 0, todo = std::max(first_chunk(G.its_last, maxit), min_it);
-  bool first = true;
-  for (;;) {
-    const uint64_t key = mix(mix(mix(base, first ? 1 : 0), (uint64_t)todo), (uint64_t)(k & 1));
-    auto chunk = [&]() -> int {
-      if (first) if (int e = head()) return e;
-      if (int e = iterations(todo)) return e;
-      if (int e = post()) return e;
-      if (use_pub) enqueue_publish(h, pub, S.sc);
-      return KNPEMI_OK;
-    };
-    if (mode.graph && h->fused_graphs.count(key)) {
-      if ((todo & 1)) std::swap(p, t);
-      k += todo;
-      KN_HIP(hipGraphLaunch(h->fused_graphs[key], h->stream));
-    } else if ((rc = run_chunk_graph(h, key, chunk, mode.graph))) return rc;
-    if (use_pub) ++h->pub_expected;
-    if ((rc = read_state(h, S.sc, sc, use_pub))) return rc;
-    if (first && mode.timed)
-      record_mode(h, 1, mode.graph, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count() / (todo + 0.5));
-    first = false;
-    if ((rc = bad_input("KNP BiCGStab", sc))) return rc;
-    it = (int)sc[S_IT];
-    if (!std::isfinite(sc[S_RR])) {
-      kn_set_error("KNP BiCGStab broke down (non-finite residual) " + describe(sc));
-      return KNPEMI_ESOLVE;
-    }
-    if (sc[S_DONE] != 0.0 || it >= maxit) break;
-    if ((int)sc[S_FLAG] & (F_RHO_ZERO | F_OMEGA_ZERO | F_RV_ZERO)) {
-      // a true breakdown with a residual left: restart from the current iterate with rhat = r, as PETSc's KSPBCGS does
-      if (++restarts > 3) { kn_set_error("KNP BiCGStab broke down repeatedly " + describe(sc)); return KNPEMI_ESOLVE; }
-      hipLaunchKernelGGL(bi_restart_kernel, dim3((std::max(n, KN_PB) + 255) / 256), dim3(256), 0, h->stream, n, rhat, r, L.red, nb_update);
-    }
-    todo = 1;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("fused BiCGStab: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  G.its_last = it;
-  *iters = it;
-  *rr_out = sc[S_RR];
-  *bb_out = sc[S_BB];
-  return KNPEMI_OK;
+  int restarts = 0;
+  auto breakdown = [&](const double* sc) -> int {
+    if (!((int)sc[S_FLAG] & (F_RHO_ZERO | F_OMEGA_ZERO | F_RV_ZERO))) return KNPEMI_OK;
+    // a true breakdown with a residual left: restart from the current iterate with rhat = r, as PETSc's KSPBCGS does
+    if (++restarts > 3) { kn_set_error("KNP BiCGStab broke down repeatedly " + describe(sc)); return KNPEMI_ESOLVE; }
+    hipLaunchKernelGGL(bi_restart_kernel, dim3((std::max(n, KN_PB) + 255) / 256), dim3(256), 0, h->stream, n, rhat, r, L.red, nb_update);
+    return KNPEMI_OK;
+  };
+  const uint64_t seed = mix(mix(mix(0xB1ull, (uint64_t)(uintptr_t)b), (uint64_t)h->fuse_update), (uint64_t)min_it);
+  return fused_chunks(h, G, S, 1, "KNP BiCGStab", "fused BiCGStab", seed, rtol, atol, maxit, min_it, 0.5, head, iterations, post,
+                      breakdown, iters, rr_out, bb_out);
 }
 
 // =====================================================================================================================
@@ -1471,11 +1447,11 @@ int kn_fused_gmres(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double
     KN_LAUNCH_L0(l0, dim3(nb_row), h->stream, (residual_kernel<4, false>), (residual_kernel<16, false>), n, S.rowptr, S.colind,
                  S.vals, (const double*)x, b, r, (double*)nullptr, L.red, 0, 0.0, (double*)nullptr);
     if (first) {
-      L.cycle<IN_PLAIN, 0, false>(b, nullptr, nullptr, nullptr, nullptr, tmp, 0, 0, nullptr, nullptr);
+      L.cycle<IN_PLAIN, 0, false>(b, nullptr, nullptr, nullptr, nullptr, tmp, 0, 0);
       hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)tmp, L.red, (int)P_BS);
     }
     hipLaunchKernelGGL(gm_start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_vec, rtol, atol, min_it, first ? 1 : 0, nb_row);
-    L.cycle<IN_PLAIN, 0, false>(r, nullptr, nullptr, nullptr, nullptr, w, 0, 0, nullptr, nullptr);
+    L.cycle<IN_PLAIN, 0, false>(r, nullptr, nullptr, nullptr, nullptr, w, 0, 0);
     hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)w, L.red, (int)P_PQ);
     first = false;
     int j = 0;
@@ -1485,16 +1461,14 @@ int kn_fused_gmres(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double
       for (int k = 0; k < todo && j < m_restart; ++k, ++j) {
         KN_LAUNCH_L0(l0, dim3(nb_row), h->stream, gm_spmv_kernel<4>, gm_spmv_kernel<16>, n, S.rowptr, S.colind, S.vals,
                      (const double*)w, V + (size_t)j * ldv, t, L.red, g, nb_vec, j, base);
-        L.cycle<IN_PLAIN, 0, false>(t, nullptr, nullptr, nullptr, nullptr, w, 0, 0, nullptr, nullptr);
+        L.cycle<IN_PLAIN, 0, false>(t, nullptr, nullptr, nullptr, nullptr, w, 0, 0);
         hipLaunchKernelGGL(gm_dots_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)w, (const double*)V, ldv, j, L.red, g);
         hipLaunchKernelGGL(gm_orth_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, w, (const double*)V, ldv, j, L.red, g, nb_vec);
       }
       hipLaunchKernelGGL(gm_check_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, g, nb_vec, j, base);
-      if (use_pub) { enqueue_publish(h, pub, S.sc); ++h->pub_expected; }
-      if ((rc = read_state(h, S.sc, sc, use_pub))) return rc;
-      if ((rc = bad_input("KNP GMRES", sc))) return rc;
+      if (use_pub) enqueue_publish(h, pub, S.sc);
+      if ((rc = chunk_state(h, S, sc, use_pub, "KNP GMRES"))) return rc;
       it = (int)sc[S_IT];
-      if (!std::isfinite(sc[S_RR])) { kn_set_error("KNP GMRES broke down (non-finite residual) " + describe(sc)); return KNPEMI_ESOLVE; }
       done = sc[S_DONE] != 0.0 || it >= maxit || j >= m_restart;
       todo = 1;
     }
@@ -1503,13 +1477,7 @@ int kn_fused_gmres(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double
     base = it;       // restart from the updated iterate
   }
   if ((rc = post())) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("fused GMRES: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  G.its_last = it;
-  *iters = it;
-  *rr_out = sc[S_RR];
-  *bb_out = sc[S_BB];
-  return KNPEMI_OK;
+  return finish_solve(G, sc, it, "fused GMRES", iters, rr_out, bb_out);
 }
 
 // ---- diagnostics: a chain of dependent trivial kernels on the handle's stream, timed on the host (knpemi_debug_launch_chain)

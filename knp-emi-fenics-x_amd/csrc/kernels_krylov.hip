@@ -418,23 +418,15 @@ __global__ void bicg_init_kernel(int n, double* __restrict__ p, double* __restri
 template <class Body>
 int run_chunk(knpemi_handle* h, knpemi_handle::KnGraph& g, uint64_t key, int chunk, Body&& body) {
   static const bool no_graph_env = getenv("KNPEMI_NO_GRAPH") != nullptr;
-  const bool no_graph = no_graph_env || h->dist.on;   // the communication hooks cannot be captured
-  int rc = KNPEMI_OK;
-  if (no_graph) {
+  auto loop = [&]() -> int {
+    int rc = KNPEMI_OK;
     for (int k = 0; k < chunk && !rc; ++k) rc = body();
     return rc;
-  }
+  };
+  if (no_graph_env || h->dist.on) return loop();   // the communication hooks cannot be captured
   if (!g.exec || g.key != key) {
     if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-    hipGraph_t graph = nullptr;
-    KN_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    for (int k = 0; k < chunk && !rc; ++k) rc = body();
-    hipError_t e = hipStreamEndCapture(h->stream, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) { kn_set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-    e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) { g.exec = nullptr; kn_set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+    if (int rc = kn_capture(h, loop, &g.exec)) return rc;
     g.key = key;
   }
   KN_HIP(hipGraphLaunch(g.exec, h->stream));
@@ -493,7 +485,75 @@ int check_start(const char* who, const double* sc) {
   return KNPEMI_OK;
 }
 
+// Hierarchy upkeep at the head of an AMG-preconditioned solve: the first build (also after a size change, and on a
+// partitioned problem once the hierarchy has aged), else the background rebuild of an aged one; then the block inverses
+// of the finest level.  `owned`: the rank's mask of the system's unknowns (partitioned problems).
+int amg_upkeep(knpemi_handle* h, KnAmg& G, int n, const int* rowptr, const int* colind, const double* vals, bool singular,
+               const std::vector<uint8_t>& owned) {
+  const KnDist& dist = h->dist;
+  int rc;
+  if (!G.built || G.n != n) {
+    KnAmgConfig& C = G.cfg;
+    C.negative_strength = true;
+    // (plain_knp marks the solver handle of a DG problem, which has made its own choices: kernels_dg.hip)
+    if (!h->plain_knp) {
+      // stretched Q1 cells couple the two ends of an edge along the long direction positively: aggregate_apart keeps them
+      // in different aggregates (config 2h: 9.35 / 3.95 -> 7.4 / 2.9 iterations per solve; on simplices the plain greedy
+      // pass is the better one, 5.3 / 2.35 against 5.75 / 2.6 at config 2)
+      if (h->NV == 8) C.positive_conflict = true;
+      // prolongator smoothing along the large couplings only (KnAmgConfig::filter_theta): the operator complexity falls
+      // from 2.5-2.8 to 1.5 on simplices, the iteration counts stay (995 k tets: 6.65 / 2.8 -> 6.75 / 2.85, 3.34 -> 2.37 ms
+      // per step with solves).  "Large" is by magnitude: the big positive entries of stretched Q1 cells stay in the
+      // smoothing (lumping them into the diagonal cost config 2h 7.4 -> 12.6 iterations).
+      C.filter_theta = 0.02;
+    }
+    if (getenv("KNPEMI_AMG_APART")) C.positive_conflict = atoi(getenv("KNPEMI_AMG_APART")) != 0;
+    if (const char* ft = getenv("KNPEMI_AMG_FILTER")) C.filter_theta = atof(ft);
+    C.want_fused = !dist.on && use_fused();
+    C.want_cycle = dist.on && use_fused() && !getenv("KNPEMI_DIST_PLAIN_CYCLE");
+    if ((rc = kn_amg_setup(h, G, n, rowptr, colind, vals, singular, dist.on ? owned.data() : nullptr))) return rc;
+    G.its_ref = -1;
+    ++G.builds;
+  } else if (!dist.on) {
+    if (rebuild_every() > 0 && ++G.solves % rebuild_every() == 0) G.rebuild_wanted = true;
+    if (G.rebuild_wanted && (rc = kn_amg_rebuild_step(h, G, n, rowptr, colind, vals, singular))) return rc;
+  }
+  return kn_amg_refresh(h, G, vals);
+}
+
+// frozen hierarchy: rebuild at the next solve once it has visibly aged (`it`: iterations of the solve just finished)
+void amg_age(knpemi_handle* h, KnAmg& G, int it) {
+  if (G.its_ref < 0) G.its_ref = it;
+  else if (it > 2 * G.its_ref + 4) { if (h->dist.on) G.built = false; else G.rebuild_wanted = true; }
+}
+
 }  // namespace
+
+int kn_capture(knpemi_handle* h, const std::function<int()>& enqueue, hipGraphExec_t* out) {
+  *out = nullptr;
+  hipGraph_t graph = nullptr;
+  KN_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  const int rc = enqueue();
+  hipError_t e = hipStreamEndCapture(h->stream, &graph);
+  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+  if (e != hipSuccess) { kn_set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+  e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (e != hipSuccess) { *out = nullptr; kn_set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+  return KNPEMI_OK;
+}
+
+void kn_solver_free(knpemi_handle* h) {
+  for (KnAmg* G : {&h->amg_emi, &h->amg_knp}) {
+    kn_amg_async_join(*G);
+    kn_amg_free(*G);
+  }
+  if (h->kry_pinned) (void)hipHostFree(h->kry_pinned);
+  if (h->pub_host) (void)hipHostFree(h->pub_host);
+  kn_fused_graphs_free(h);
+  for (knpemi_handle::KnGraph* g : {&h->graph_emi, &h->graph_knp})
+    if (g->exec) (void)hipGraphExecDestroy(g->exec);
+}
 
 // Workspace: 10 vectors of the larger system + ones + scalars + partials (allocated on first use).
 static int ensure_work(knpemi_handle* h, size_t n) {
@@ -655,33 +715,8 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   };
   KnAmg& G = h->amg_emi;
   const bool amg = h->pc_emi == KNPEMI_PC_AMG;
-  if (amg && (!G.built || G.n != n)) {
-    G.negative_strength = true;
-    // stretched Q1 cells couple the two ends of an edge along the long direction positively: aggregate_apart keeps them
-    // in different aggregates (config 2h: 9.35 / 3.95 -> 7.4 / 2.9 iterations per solve; on simplices the plain greedy
-    // pass is the better one, 5.3 / 2.35 against 5.75 / 2.6 at config 2).  The DG solver handle sets the flag itself.
-    // (plain_knp marks the solver handle of a DG problem, which has made its own choices: kernels_dg.hip)
-    if (h->plain_knp) {}
-    else if (h->NV == 8) G.positive_conflict = true;
-    // prolongator smoothing along the large couplings only (KnAmg::filter_theta): the operator complexity falls from
-    // 2.5-2.8 to 1.5 on simplices, the iteration counts stay (995 k tets: 6.65 / 2.8 -> 6.75 / 2.85, 3.34 -> 2.37 ms per
-    // step with solves).  "Large" is by magnitude: the big positive entries of stretched Q1 cells stay in the smoothing
-    // (lumping them into the diagonal cost config 2h 7.4 -> 12.6 iterations).
-    if (!h->plain_knp) G.filter_theta = 0.02;
-    if (getenv("KNPEMI_AMG_APART")) G.positive_conflict = atoi(getenv("KNPEMI_AMG_APART")) != 0;
-    if (const char* ft = getenv("KNPEMI_AMG_FILTER")) G.filter_theta = atof(ft);
-    G.want_fused = !dist.on && use_fused();
-    G.want_cycle = dist.on && use_fused() && !getenv("KNPEMI_DIST_PLAIN_CYCLE");
-    // the diagonal block of a rank that has ghosts has lost couplings: it is non-singular
-    if ((rc = kn_amg_setup(h, G, n, D.rowptr, D.colind, D.A_emi, !has_ghosts,
-                           dist.on ? dist.h_owned_emi.data() : nullptr))) return rc;
-    G.its_ref = -1;
-    ++G.builds;
-  } else if (amg && !dist.on) {
-    if (rebuild_every() > 0 && ++G.solves % rebuild_every() == 0) G.rebuild_wanted = true;
-    if (G.rebuild_wanted && (rc = kn_amg_rebuild_step(h, G, n, D.rowptr, D.colind, D.A_emi, !has_ghosts))) return rc;
-  }
-  if (amg && (rc = kn_amg_refresh(h, G, D.A_emi))) return rc;
+  // (the diagonal block of a rank that has ghosts has lost couplings: it is non-singular)
+  if (amg && (rc = amg_upkeep(h, G, n, D.rowptr, D.colind, D.A_emi, !has_ghosts, dist.h_owned_emi))) return rc;
   // two-level variant on a partitioned mesh: the ranks' AMG cycles do not see each other, a coarse space of one
   // constant per (rank, sub-domain) carries the error across the cuts (knpemi_set_distributed_coarse)
   const bool coarse = dist.on && amg && h->dist.nc > 0;
@@ -746,10 +781,7 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   if (relres) *relres = bnorm > 0 ? rn / bnorm : rn;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { kn_set_error(std::string("krylov (emi): ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  if (amg) {   // frozen hierarchy: rebuild at the next solve once it has visibly aged
-    if (G.its_ref < 0) G.its_ref = it;
-    else if (it > 2 * G.its_ref + 4) { if (dist.on) G.built = false; else G.rebuild_wanted = true; }
-  }
+  if (amg) amg_age(h, G, it);
   if (rn > target) { kn_set_error("EMI CG did not converge (ksp_error_if_not_converged)"); return KNPEMI_ESOLVE; }
   return KNPEMI_OK;
 }
@@ -798,32 +830,7 @@ int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
     // owners' 1 / a_ii instead, so that the recurrence residual stays b - A x (x is updated with the owners' dinv)
     if (!amg) if (int e = dist.halo(dist.ctx, dinv, KNPEMI_B_KNP)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
   }
-  if (amg && (!G.built || G.n != n)) {
-    G.negative_strength = true;
-    // stretched Q1 cells couple the two ends of an edge along the long direction positively: aggregate_apart keeps them
-    // in different aggregates (config 2h: 9.35 / 3.95 -> 7.4 / 2.9 iterations per solve; on simplices the plain greedy
-    // pass is the better one, 5.3 / 2.35 against 5.75 / 2.6 at config 2).  The DG solver handle sets the flag itself.
-    // (plain_knp marks the solver handle of a DG problem, which has made its own choices: kernels_dg.hip)
-    if (h->plain_knp) {}
-    else if (h->NV == 8) G.positive_conflict = true;
-    // prolongator smoothing along the large couplings only (KnAmg::filter_theta): the operator complexity falls from
-    // 2.5-2.8 to 1.5 on simplices, the iteration counts stay (995 k tets: 6.65 / 2.8 -> 6.75 / 2.85, 3.34 -> 2.37 ms per
-    // step with solves).  "Large" is by magnitude: the big positive entries of stretched Q1 cells stay in the smoothing
-    // (lumping them into the diagonal cost config 2h 7.4 -> 12.6 iterations).
-    if (!h->plain_knp) G.filter_theta = 0.02;
-    if (getenv("KNPEMI_AMG_APART")) G.positive_conflict = atoi(getenv("KNPEMI_AMG_APART")) != 0;
-    if (const char* ft = getenv("KNPEMI_AMG_FILTER")) G.filter_theta = atof(ft);
-    G.want_fused = !dist.on && use_fused();
-    G.want_cycle = dist.on && use_fused() && !getenv("KNPEMI_DIST_PLAIN_CYCLE");
-    if ((rc = kn_amg_setup(h, G, n, D.krowptr, D.kcolind, D.A_knp, false,
-                           dist.on ? dist.h_owned_knp.data() : nullptr))) return rc;
-    G.its_ref = -1;
-    ++G.builds;
-  } else if (amg && !dist.on) {
-    if (rebuild_every() > 0 && ++G.solves % rebuild_every() == 0) G.rebuild_wanted = true;
-    if (G.rebuild_wanted && (rc = kn_amg_rebuild_step(h, G, n, D.krowptr, D.kcolind, D.A_knp, false))) return rc;
-  }
-  if (amg && (rc = kn_amg_refresh(h, G, D.A_knp))) return rc;
+  if (amg && (rc = amg_upkeep(h, G, n, D.krowptr, D.kcolind, D.A_knp, false, dist.h_owned_knp))) return rc;
   double sc[S_N];
   const bool fused = amg && G.fused_ok && !dist.on && use_fused();
   int it = 0, restarts = 0;
@@ -904,10 +911,7 @@ int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   if (relres) *relres = bnorm > 0 ? rn / bnorm : rn;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { kn_set_error(std::string("krylov (knp): ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  if (amg) {
-    if (G.its_ref < 0) G.its_ref = it;
-    else if (it > 2 * G.its_ref + 4) { if (dist.on) G.built = false; else G.rebuild_wanted = true; }
-  }
+  if (amg) amg_age(h, G, it);
   if (rn > target) { kn_set_error("KNP BiCGStab did not converge (ksp_error_if_not_converged)"); return KNPEMI_ESOLVE; }
   return KNPEMI_OK;
 }

@@ -1016,15 +1016,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->aux) (void)hipStreamDestroy(h->aux);
   kn_comm_destroy(h);
-  kn_amg_async_join(h->amg_emi);
-  kn_amg_async_join(h->amg_knp);
-  kn_amg_free(h->amg_emi);
-  kn_amg_free(h->amg_knp);
-  if (h->kry_pinned) (void)hipHostFree(h->kry_pinned);
-  if (h->pub_host) (void)hipHostFree(h->pub_host);
-  kn_fused_graphs_free(h);
-  if (h->graph_emi.exec) (void)hipGraphExecDestroy(h->graph_emi.exec);
-  if (h->graph_knp.exec) (void)hipGraphExecDestroy(h->graph_knp.exec);
+  kn_solver_free(h);
   for (void* p : h->obs.allocs) (void)hipFree(p);
   for (void* p : h->allocs) (void)hipFree(p);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
@@ -1308,7 +1300,7 @@ extern "C" int knpemi_solver_setup(knpemi_handle* h, int which, int precond, dou
     return fail(KNPEMI_EINVAL, "knpemi_solver_setup: unknown preconditioner");
   KnAmg& G = which == KNPEMI_B_EMI ? h->amg_emi : h->amg_knp;
   (which == KNPEMI_B_EMI ? h->pc_emi : h->pc_knp) = precond;
-  G.theta = theta > 0 ? theta : 0.08;
+  G.cfg.theta = theta > 0 ? theta : 0.08;
   G.built = false;
   return KNPEMI_OK;
 }

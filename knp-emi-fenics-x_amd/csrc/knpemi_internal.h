@@ -161,22 +161,13 @@ struct KnAmgLevel {
   double *x = nullptr, *r = nullptr, *t = nullptr;
 };
 struct KnAmgAsync;     // a rebuild running on a host thread (kernels_amg.hip)
-struct KnAmg {
-  KnAmgAsync* async = nullptr;
-  bool rebuild_wanted = false;       // the hierarchy has aged (iteration count doubled): rebuild it in the background
-  int solves = 0;                    // solves with this hierarchy's system (KNPEMI_AMG_REBUILD_EVERY test hook)
-  std::vector<KnAmgLevel> lev;
-  std::vector<void*> allocs;
-  bool built = false, singular = false;
+// How a hierarchy is built: set by the owner of the system before the first build (kernels_krylov.hip: amg_upkeep, the DG
+// solver handle in kernels_dg.hip), read by the set-up and carried whole into a background rebuild.
+struct KnAmgConfig {
   bool negative_strength = false;    // strength of connection from -a_ij only (classical) instead of |a_ij|
-  int n = 0;
   double theta = 0.08;               // strength threshold
-  double op_complexity = 1.0;
   bool want_fused = false;           // also build the merged operators of the fused cycle (single rank, point smoother)
-  bool fused_ok = false;             // ... and they exist: every level but the last has Rm / Pm, the last one a dense inverse
-  int its_ref = -1;                  // iterations of the first solve after the build (rebuild trigger)
-  int its_last = 4;                  // iterations of the last fused solve: size of the next solve's first chunk
-  int builds = 0;
+  bool want_cycle = false;           // point-Jacobi hierarchy of a rank's diagonal block: the whole cycle that way
   // Optional aggregates of the finest level (auxiliary-space variant, DG systems: the broken dofs of a (sub-domain,
   // mesh vertex) form one aggregate, so the first coarse level is the continuous P1 space of the sub-domains and the
   // strength-based aggregation only starts there).  first_na == 0: aggregate every level by strength.
@@ -187,19 +178,36 @@ struct KnAmg {
   // ties coincident dofs together across the facets along the long direction a hundred times more strongly than across
   // the others, and the low-energy error of the DG systems is continuous only across the former.
   bool split_first = false;
+  double split_theta = 0.1;
   bool positive_conflict = false;    // aggregation keeps strongly positively coupled unknowns apart (aggregate_apart)
   // Block-smoothed hierarchies (DG): the levels below the finest run through the merged transfer operators of the fused
-  // cycle (kn_fused_subcycle): sub_fused asks for them at set-up, sub_fused_ok says they exist (dense coarsest level)
-  bool sub_fused = false, sub_fused_ok = false;
-  bool want_cycle = false, cycle_ok = false;   // point-Jacobi hierarchy of a rank's diagonal block: the whole cycle that way
-  double* zero_sc = nullptr;         // 32 zeroed doubles: the "not done" flag the fused kernels look at
+  // cycle (kn_fused_subcycle)
+  bool sub_fused = false;
   double filter_theta = 0.0;         // > 0: prolongator smoothing with the filtered operator (weak entries lumped)
   bool first_tentative = false;      // the prolongator of the given aggregates is not smoothed
-  double split_theta = 0.1;
   // Optional block-Jacobi smoother on the finest level: `block` consecutive unknowns (the dofs of a DG cell) form a
   // block whose inverse is refreshed from the current values before every solve (kn_amg_refresh).  0: point Jacobi.
   int block = 0;
-  double* binv = nullptr;            // [n / block][block][block]
+};
+struct KnAmg {
+  KnAmgConfig cfg;
+  KnAmgAsync* async = nullptr;
+  bool rebuild_wanted = false;       // the hierarchy has aged (iteration count doubled): rebuild it in the background
+  int solves = 0;                    // solves with this hierarchy's system (KNPEMI_AMG_REBUILD_EVERY test hook)
+  std::vector<KnAmgLevel> lev;
+  std::vector<void*> allocs;
+  bool built = false, singular = false;
+  int n = 0;
+  double op_complexity = 1.0;
+  bool fused_ok = false;             // cfg.want_fused and the merged operators exist: every level but the last has Rm / Pm,
+                                     // the last one a dense inverse
+  bool sub_fused_ok = false;         // cfg.sub_fused and the merged operators below the finest level exist
+  bool cycle_ok = false;             // cfg.want_cycle and the merged operators exist
+  int its_ref = -1;                  // iterations of the first solve after the build (rebuild trigger)
+  int its_last = 4;                  // iterations of the last fused solve: size of the next solve's first chunk
+  int builds = 0;
+  double* zero_sc = nullptr;         // 32 zeroed doubles: the "not done" flag the fused kernels look at
+  double* binv = nullptr;            // [n / cfg.block][cfg.block][cfg.block]
   double omega_block = 1.0;          // damping 4 / (3 rho(B^-1 A))
 };
 void kn_amg_free(KnAmg& G);
@@ -230,6 +238,11 @@ int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const dou
 int kn_fused_gmres(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
                    int* iters, double* rr, double* bb, const std::function<int()>& pre, const std::function<int()>& post);
 void kn_fused_graphs_free(knpemi_handle* h);
+// captures what `enqueue` launches on h->stream into *out (nullptr on failure): the one capture path of the Krylov loops
+int kn_capture(knpemi_handle* h, const std::function<int()>& enqueue, hipGraphExec_t* out);
+// frees the solver state of a handle: AMG hierarchies (background rebuilds joined), pinned and published host buffers,
+// captured graphs -- knpemi_destroy and knpemi_dg_destroy (its solver handle)
+void kn_solver_free(knpemi_handle* h);
 
 // Distributed solves (knpemi_set_distributed)
 struct KnDist {
@@ -315,7 +328,8 @@ struct knpemi_handle {
   double* guess_old[2] = {nullptr, nullptr};         // previous solutions (EMI, KNP) for knpemi_extrapolate_guess
   int guess_have[2] = {0, 0};                        // previous solutions stored so far (0, 1, 2)
   KnAmg amg_emi, amg_knp;
-  // captured iteration bodies of the Krylov loops (kernels_krylov.hip); key = configuration they were captured for
+  // captured iteration bodies of the plain Krylov loops (kernels_krylov.hip: run_chunk); key = configuration they were
+  // captured for.  Both kinds of graph are captured by kn_capture and freed by kn_solver_free.
   struct KnGraph { hipGraphExec_t exec = nullptr; uint64_t key = 0; };
   KnGraph graph_emi, graph_knp;
   // captured chunks of the fused loops (kernels_fused.hip: run_chunk_graph), keyed by everything their kernel arguments hold

@@ -416,15 +416,16 @@ def _in_child(call, env, timeout=600):
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
 
 
-def _stepper(knp_method="bicgstab"):
-    """A DeviceStepper with the device solves (end-of-step update fused into the KNP write-back) on the tet r=0 mesh."""
+def _stepper(knp_method="bicgstab", fuse_update=None):
+    """A DeviceStepper with the device solves (by default the end-of-step update fused into the KNP write-back) on the tet
+    r=0 mesh."""
     from knpemi.stepper import DeviceStepper
     s = Setup("tet", 0, g_syn=10.0)
     for t in s.subdomain_list:
         for k in range(2):
             s.c[t][k].x.array[:] = s.c_prev[t][k].x._a
     st = DeviceStepper((s.a_emi, s.p_emi, s.L_emi), (s.a_knp, s.p_knp, s.L_knp), s.c, s.c_prev, s.phi, s.phi_M_prev,
-                       device_solves=(1e-9, 1e-10), overlap=False, knp_method=knp_method)
+                       device_solves=(1e-9, 1e-10), overlap=False, knp_method=knp_method, fuse_update=fuse_update)
     st.add_membrane_model(s.mem_models[0]['ode'], s.stim_params['stimulus'], s.stim_params['stimulus_locator'])
     return s, st
 
@@ -469,6 +470,43 @@ def test_folded_integrals_are_not_reused_after_a_replayed_knp_solve(hip_lib, knp
     facet integrals of the fields before the solve."""
     _in_child(f"_knp_rhs_after_a_replayed_knp_solve({knp_method!r})",
               {"KNPEMI_FUSED_GRAPH": "1", "KNPEMI_FUSED_CHUNK": "1"})
+
+
+def _device_solve_run(emi_norm, fuse_update, out):
+    """Six DeviceStepper steps with the device solves (EMI CG with the `emi_norm` test, KNP BiCGStab): the fields and the
+    iteration count and relative residual of every solve into the file `out`."""
+    from knpemi.pdeSolver import set_emi_solver_options
+    s, st = _stepper("bicgstab", fuse_update=fuse_update)
+    set_emi_solver_options(st.dp, emi_norm)
+    for _ in range(6):
+        st.step()
+    st.download()
+    fields = [s.phi[t].x._a for t in s.subdomain_list]
+    fields += [d[t][k].x._a for d in (s.c, s.c_prev) for t in s.subdomain_list for k in range(2)]
+    fields += [s.phi_M_prev[t].x._a for t in s.subdomain_list if t > 0]
+    np.savez(out, fields=np.concatenate(fields), its=np.array([r[1] for r in st.iterations]),
+             relres=np.array([r[2] for r in st.iterations]))
+
+
+@pytest.mark.parametrize("emi_norm,fuse_update", [("true", True), ("true", False), ("preconditioned", True),
+                                                  ("preconditioned", False)])
+def test_replayed_solves_equal_direct_launches_bit_for_bit(hip_lib, tmp_path, emi_norm, fuse_update):
+    """The same six steps with the chunks of the device solves launched directly and replayed from captured graphs (the
+    fused loops with one iteration per chunk after the first, so that the later solves replay graphs of several chunks;
+    the plain loops with their captured iteration bodies): the fields and every solve's iteration count and relative
+    residual agree bit for bit."""
+    pairs = [({"KNPEMI_FUSED_GRAPH": "0"}, {"KNPEMI_FUSED_GRAPH": "1", "KNPEMI_FUSED_CHUNK": "1"}),
+             ({"KNPEMI_NO_FUSED": "1"}, {"KNPEMI_NO_FUSED": "1", "KNPEMI_NO_GRAPH": "1"})]
+    for i, pair in enumerate(pairs):
+        runs = []
+        for j, env in enumerate(pair):
+            out = str(tmp_path / f"run{i}{j}.npz")
+            _in_child(f"_device_solve_run({emi_norm!r}, {fuse_update!r}, {out!r})", env)
+            runs.append(np.load(out))
+        a, b = runs
+        assert len(a["its"]) == 12 and a["its"].sum() > 0, (pair, a["its"])
+        for key in ("its", "relres", "fields"):
+            assert np.array_equal(a[key], b[key]), (pair, key, a["its"], b["its"])
 
 
 def _folded_and_fresh_knp_rhs_agree(n_calls=30, seed=34):
