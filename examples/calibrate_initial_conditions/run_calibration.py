@@ -95,7 +95,7 @@ def state_names(module):
 
 
 def calibrate(name, max_steps=200000, rtol=1e-10, atol=1e-12, window=20, n_cells=10, record=None, every=1,
-              sweep=None):
+              sweep=None, method="lsoda", substeps=None):
     """Steady state of model `name`; returns (membrane, steps_taken, history).  sweep = (param, values) sets one value
     per node (n_cells is then len(values) - 1)."""
     module = load_model(name)
@@ -105,6 +105,7 @@ def calibrate(name, max_steps=200000, rtol=1e-10, atol=1e-12, window=20, n_cells
     membrane = make_membrane(module, n_cells, params)
     if sweep is not None:
         membrane.parameters[:, module.parameter_indices(sweep[0])] = sweep[1]
+    membrane.set_integrator(method, substeps)
     out = membrane.steady_state(dt, max_steps, rtol=rtol, atol=atol, window=window, record=record, every=every)
     steps, hist = out if record is not None else (out, None)
     return membrane, steps, hist
@@ -121,6 +122,9 @@ def main(argv=None):
     ap.add_argument("--history", help="write the recorded trajectory of every state to this .npz")
     ap.add_argument("--every", type=int, default=10, help="record every n-th step (--history)")
     ap.add_argument("--out", default="calibration.npz", help="rest states of a --sweep")
+    ap.add_argument("--method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda",
+                    help="membrane integrator (MembraneModel.set_integrator)")
+    ap.add_argument("--substeps", type=int, default=None, help="sub-steps per step of a fixed-step method (default 25)")
     a = ap.parse_args(argv)
     names = a.model or sorted(MODELS)
     sweep = None
@@ -132,7 +136,7 @@ def main(argv=None):
         module = load_model(name)
         record = state_names(module) if a.history else None
         membrane, steps, hist = calibrate(name, a.max_steps, a.rtol, a.atol, a.window, record=record,
-                                          every=a.every, sweep=sweep)
+                                          every=a.every, sweep=sweep, method=a.method, substeps=a.substeps)
         if (steps < 0).any():
             print(f"{name}: {int((steps < 0).sum())} node(s) not steady after {a.max_steps} steps", file=sys.stderr)
         print(f"# {name}: steady after {int(steps.max())} steps (t = {membrane.time:g})")

@@ -23,7 +23,7 @@ from knpemi import (create_solver_emi, create_solver_knp, update_ode_variables, 
 from setup_problem import Setup  # noqa: E402
 
 
-def solve_odes(s, k):
+def solve_odes(s, k, ode_method="lsoda", ode_substeps=None):
     """ Solve ODEs (membrane models) for each membrane tag in each subdomain """
     for tag, subdomain in s.subdomain_list.items():
         if tag == 0:
@@ -33,8 +33,11 @@ def solve_odes(s, k):
             ode_model = mem_model['ode']
             update_ode_variables(ode_model, s.c_prev, phi_M_prev_sub, s.ion_list, s.subdomain_list,
                                  s.mesh, s.ct, tag, k)
-            ode_model.step_lsoda(dt=s.dt, stimulus=s.stim_params['stimulus'],
-                                 stimulus_locator=s.stim_params['stimulus_locator'])
+            if k == 0:
+                ode_model.set_integrator(ode_method, ode_substeps)
+            # step_lsoda of the reference; `step` is the same call with the integrator of --ode-method
+            ode_model.step(dt=s.dt, stimulus=s.stim_params['stimulus'],
+                           stimulus_locator=s.stim_params['stimulus_locator'])
             ode_model.get_membrane_potential(phi_M_prev_sub)
             for ion, I_ch_k in mem_model['I_ch_k'].items():
                 ode_model.get_parameter("I_ch_" + ion, I_ch_k)
@@ -69,8 +72,11 @@ def figure_observables(s):
     return obs
 
 
-def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None, series=None):
-    """series: path of a .npz with the time series at the figures' points (figure_observables), or None."""
+def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None, series=None,
+                 ode_method="lsoda", ode_substeps=None):
+    """series: path of a .npz with the time series at the figures' points (figure_observables), or None.
+    ode_method / ode_substeps: the membrane integrator (MembraneModel.set_integrator); the reference's drivers name the
+    sub-step count `n_steps_ODE` (run_2D.py:176)."""
     s = Setup(kind, res, g_syn=g_syn, mesh_data=read_mesh(mesh_file) if mesh_file else None)
     obs = figure_observables(s) if series else None
     problem_emi = create_solver_emi(s.a_emi, s.L_emi, s.phi, s.entity_maps, s.subdomain_list, None,
@@ -81,7 +87,7 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
     t = 0.0
     for k in range(n_steps):
         print(f'Solving for t = {t:.4f} s')
-        solve_odes(s, k)
+        solve_odes(s, k, ode_method, ode_substeps)
         problem_emi.solve()
         problem_knp.solve()
         num_it_emi.append(problem_emi.solver.getIterationNumber())
@@ -108,9 +114,12 @@ if __name__ == "__main__":
     ap.add_argument("--iterative", action="store_true")
     ap.add_argument("--mesh-file", default=None, help="XDMF mesh written by make_mesh_2D.py (default: generate)")
     ap.add_argument("--series", metavar="PATH", default=None, help="time series at the figures' points (.npz)")
+    ap.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
+    ap.add_argument("--ode-substeps", type=int, default=None, help="sub-steps per time step of a fixed-step method (25)")
     a = ap.parse_args()
     s, it_emi, it_knp = solve_system("2d", a.res, a.steps, direct=not a.iterative, mesh_file=a.mesh_file,
-                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), series=a.series)
+                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), series=a.series,
+                                     ode_method=a.ode_method, ode_substeps=a.ode_substeps)
     v = s.phi_M_prev[1].x._a
     print(f"phi_M after {a.steps} steps: min {v.min():.6f} V, max {v.max():.6f} V")
     print(f"average number of iterations emi solver: {sum(it_emi) / len(it_emi)}")

@@ -168,7 +168,7 @@ class Problem:
         return changed
 
 
-def solve_odes(p, k):
+def solve_odes(p, k, ode_method="lsoda", ode_substeps=None):
     """run_stim_duration.py:92-123"""
     for tag, subdomain in p.subdomain_list.items():
         if tag == 0:
@@ -178,8 +178,11 @@ def solve_odes(p, k):
             ode_model = mem_model["ode"]
             update_ode_variables(ode_model, p.c_prev, phi_M_prev_sub, p.ion_list, p.subdomain_list, p.mesh, p.ct,
                                  tag, k)
-            ode_model.step_lsoda(dt=p.dt, stimulus=p.stim_params["stimulus"],
-                                 stimulus_locator=p.stim_params["stimulus_locator"])
+            if k == 0:
+                ode_model.set_integrator(ode_method, ode_substeps)
+            # step_lsoda of the reference; `step` is the same call with the integrator of --ode-method
+            ode_model.step(dt=p.dt, stimulus=p.stim_params["stimulus"],
+                           stimulus_locator=p.stim_params["stimulus_locator"])
             ode_model.get_membrane_potential(phi_M_prev_sub)
             for ion, I_ch_k in mem_model["I_ch_k"].items():
                 ode_model.get_parameter("I_ch_" + ion, I_ch_k)
@@ -244,8 +247,9 @@ def make_observables(p):
 
 
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
-                 extrapolate_guess=True, series=None):
-    """series: path of a .npz of per-step observables (make_observables), or None."""
+                 extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None):
+    """series: path of a .npz of per-step observables (make_observables), or None.
+    ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator)."""
     p = Problem(config)
     obs = make_observables(p) if series else None
     n_total = int(round(config["Tstop"] / float(DT)))
@@ -272,7 +276,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         from knpemi import _lib as L
         from knpemi.stepper import DeviceStepper
         st = DeviceStepper((p.a_emi, p.p_emi, p.L_emi), (p.a_knp, p.p_knp, p.L_knp), p.c, p.c_prev, p.phi,
-                           p.phi_M_prev, device_solves=(1e-6, 1e-7), extrapolate_guess=extrapolate_guess)
+                           p.phi_M_prev, device_solves=(1e-6, 1e-7), extrapolate_guess=extrapolate_guess,
+                           ode_method=ode_method, ode_substeps=ode_substeps)
         for tag in (1, 2):
             for mm in p.subdomain_list[tag]["mem_models"]:
                 st.add_membrane_model(mm["ode"], p.stim_params["stimulus"], p.stim_params["stimulus_locator"])
@@ -303,7 +308,7 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         for k in range(n_steps):
             if not quiet:
                 print(f"solving for t = {t:.2f} ms")
-            solve_odes(p, k)
+            solve_odes(p, k, ode_method, ode_substeps)
             problem_emi.solve()
             problem_knp.solve()
             update_pde_variables(p.c, p.c_prev, p.phi, p.phi_M_prev, p.physical_parameters, p.ion_list,
@@ -336,9 +341,13 @@ if __name__ == "__main__":
     parser.add_argument("--xdmf", action="store_true", help="also write results_sub_/results_mem_ XDMF time series")
     parser.add_argument("--series", metavar="PATH", default=None,
                         help="write per-step observables (points, mean phi_M, max ECS K) to this .npz")
+    parser.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
+    parser.add_argument("--ode-substeps", type=int, default=None,
+                        help="sub-steps per time step of a fixed-step method (default 25, the reference's n_steps_ODE)")
     args = parser.parse_args()
     cfg = load_config(args.c)
     _, hist = solve_system(cfg, n_steps=args.steps, device_resident=args.device_resident, direct=args.direct,
-                           xdmf=args.xdmf, series=args.series)
+                           xdmf=args.xdmf, series=args.series, ode_method=args.ode_method,
+                           ode_substeps=args.ode_substeps)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

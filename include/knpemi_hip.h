@@ -284,6 +284,24 @@ typedef struct knpemi_ode_ss {
 int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t0, double dt, int n_steps, double rtol, double atol,
                        const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
                        int32_t* steps_taken, int32_t* failed_step);
+/* The integrator of a membrane model slot: LSODA (default), or a fixed-step scheme with n_substeps equal sub-steps
+ * per knpemi_ode_step / knpemi_ode_advance interval -- forward Euler, classical RK4, first-order Rush-Larsen (gates by
+ * their exponential update, everything else by Euler).  This is the family the reference's drivers still carry a knob
+ * for: `n_steps_ODE = 25` in physical_parameters (examples/idealized_geometries/run_2D.py:176,205, run_3D.py:178,207),
+ * the sub-step count of its former splitting solver, which nothing reads since the move to LSODA.
+ * State of the slot; knpemi_ode_step and knpemi_ode_advance dispatch on it and ignore rtol / atol for a fixed-step
+ * method.  n_substeps in 1..10000 (ignored for KNPEMI_ODE_LSODA), anything else KNPEMI_EINVAL.  Works on PDE handles
+ * and on handles of knpemi_ode_create.  A model bound from source (knpemi_ode_bind_source) brings a right-hand side only,
+ * no gate rates: KNPEMI_ODE_RUSH_LARSEN on it is KNPEMI_EINVAL.
+ * Currents: a fixed-step method evaluates the right-hand side once more at (t0 + dt, y(t0 + dt)) and hands out those
+ * currents (LSODA: those of its last internal evaluation).  A dof whose state is not finite after the interval counts
+ * as failed in knpemi_ode_stats / knpemi_ode_advance exactly as an LSODA failure does. */
+#define KNPEMI_ODE_LSODA 0
+#define KNPEMI_ODE_EULER 1
+#define KNPEMI_ODE_RK4 2
+#define KNPEMI_ODE_RUSH_LARSEN 3
+int knpemi_ode_set_method(knpemi_handle* h, int sub, int model, int method, int n_substeps);
+int knpemi_ode_get_method(knpemi_handle* h, int sub, int model, int* method, int* n_substeps);
 /* Diagnostics (no reference counterpart): the steps per launch the last knpemi_ode_advance of this model chose. */
 int knpemi_ode_advance_chunk(knpemi_handle* h, int sub, int model);
 

@@ -136,6 +136,7 @@ void launch_advance_model(hipStream_t st, const OdeArgs& a, const OdeAdvArgs& v,
 }
 
 int launch_advance(knpemi_handle* h, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs& v, const LsodaCoef* cf) {
+  if (m.method != KNPEMI_ODE_LSODA) return kn_launch_ode_fixed_advance(h, m, &a, &v);   // kernels_ode_fixed.hip
   if (m.rtc_function) return kn_rtc_advance_launch(h, m, &a, sizeof(a), &v, sizeof(v), cf);
   switch (m.model_id) {
     case KNPEMI_MODEL_HH_SI: launch_advance_model<ModelHHSI, 4>(h->cur, a, v, cf); break;
@@ -241,7 +242,10 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   size_t n_failed = 0;
   for (size_t q = 0; q < nq; ++q) n_failed += flags[nq + q] >= 0;
   if (n_failed) {
-    kn_set_error("LSODA failed on " + std::to_string(n_failed) + " membrane dof(s) (odeSolver.py:121 `assert success`)");
+    if (m.method != KNPEMI_ODE_LSODA)
+      kn_set_error("the fixed-step integrator left a non-finite state on " + std::to_string(n_failed) + " membrane dof(s)");
+    else
+      kn_set_error("LSODA failed on " + std::to_string(n_failed) + " membrane dof(s) (odeSolver.py:121 `assert success`)");
     return KNPEMI_EODE;
   }
   return KNPEMI_OK;

@@ -15,41 +15,68 @@
 #include <mutex>
 
 #include "knpemi_internal.h"
-#include "ode_kernel.h"
+#include "fixed_step.h"
 
 namespace {
 
-// the two headers the generated translation unit includes, embedded at build time (csrc/Makefile)
+// the three headers the generated translation unit includes, embedded at build time (csrc/Makefile)
 const char* const SRC_LSODA_CORE =
 #include "rtc_lsoda_core.inc"
     ;
 const char* const SRC_ODE_KERNEL =
 #include "rtc_ode_kernel.inc"
     ;
+const char* const SRC_FIXED_STEP =
+#include "rtc_fixed_step.inc"
+    ;
 
 std::string wrapper_source(int ns, int np, int lanes, const std::string& user) {
   std::string s;
-  s += "#include \"ode_kernel.h\"\n";
+  s += "#include \"fixed_step.h\"\n";
   s += "// ---- plug-in source -------------------------------------------------------------\n";
   s += user;
-  s += "\n// ---- adapter: the model functor the integrator expects ---------------------------\n";
-  s += "struct ModelUser {\n";
-  s += "  static constexpr int NS = " + std::to_string(ns) + ", NP = " + std::to_string(np) + ", CURRENT_LANE = 0;\n";
-  s += "  double par[NP];\n";
-  s += "  template <class Row> __device__ void prepare(const Row& p) {\n";
-  s += "    _Pragma(\"unroll\") for (int j = 0; j < NP; ++j) par[j] = p[j];\n  }\n";
-  s += "  __device__ void rhs(double t, const double* y, double* dy) { ::rhs(t, y, dy, par); }\n";
-  s += "  // every lane of a system evaluates the whole right-hand side and keeps its own component\n";
-  s += "  __device__ double rhs_lane(int c, double t, const double* y) {\n";
-  s += "    double dy[NS];\n    ::rhs(t, y, dy, par);\n    double out = dy[0];\n";
-  s += "    _Pragma(\"unroll\") for (int k = 1; k < NS; ++k) out = (k == c) ? dy[k] : out;\n    return out;\n  }\n";
-  s += "  template <class Row> __device__ void finish(const Row& p) const {\n";
-  s += "    _Pragma(\"unroll\") for (int j = 0; j < NP; ++j) p[j] = par[j];\n  }\n};\n";
+  // the model functor the integrators expect, around the plug-in's `rhs` in namespace `scope`
+  auto adapter = [&](const std::string& scope) {
+    std::string s;
+    s += "\n// ---- adapter: the model functor the integrator expects ---------------------------\n";
+    s += "struct ModelUser {\n";
+    s += "  static constexpr int NS = " + std::to_string(ns) + ", NP = " + std::to_string(np) + ", CURRENT_LANE = 0;\n";
+    s += "  double par[NP];\n";
+    s += "  template <class Row> __device__ void prepare(const Row& p) {\n";
+    s += "    _Pragma(\"unroll\") for (int j = 0; j < NP; ++j) par[j] = p[j];\n  }\n";
+    s += "  __device__ void rhs(double t, const double* y, double* dy) { " + scope + "::rhs(t, y, dy, par); }\n";
+    s += "  // every lane of a system evaluates the whole right-hand side and keeps its own component\n";
+    s += "  __device__ double rhs_lane(int c, double t, const double* y) {\n";
+    s += "    double dy[NS];\n    " + scope + "::rhs(t, y, dy, par);\n    double out = dy[0];\n";
+    s += "    _Pragma(\"unroll\") for (int k = 1; k < NS; ++k) out = (k == c) ? dy[k] : out;\n    return out;\n  }\n";
+    s += "  template <class Row> __device__ void finish(const Row& p) const {\n";
+    s += "    _Pragma(\"unroll\") for (int j = 0; j < NP; ++j) p[j] = par[j];\n  }\n};\n";
+    return s;
+  };
+  s += adapter("");
   s += "extern \"C\" __global__ __launch_bounds__(ODE_BLOCK, 1) void ode_user_kernel(OdeDev D, OdeArgs a, const LsodaCoef* cf) {\n";
   s += "  ode_step_body<ModelUser, " + std::to_string(lanes) + ", 1, false>(D, a, cf);\n}\n";
   s += "extern \"C\" __global__ __launch_bounds__(ODE_BLOCK, 1) void ode_user_advance_kernel(OdeArgs a, OdeAdvArgs v, "
        "const LsodaCoef* cf) {\n";
   s += "  ode_advance_body<ModelUser, " + std::to_string(lanes) + ", 1>(a, v, cf);\n}\n";
+  // the fixed-step sweeps (fixed_step.h): a plug-in has a right-hand side but no gate rates, so Euler and RK4 only
+  // They promise bit-identical results from the single-step and the multi-step kernel, which holds only if no
+  // multiply-add is contracted in one and not in the other (the compiler decides by context): a second copy of the
+  // plug-in source with contraction off, in a namespace of its own; the LSODA kernels keep the first copy as it was.
+  s += "namespace kn_fs {\n#pragma clang fp contract(off)\n";
+  s += user;
+  s += "\n";
+  s += adapter("kn_fs");
+  s += "}  // namespace kn_fs\n";
+  const char* fs_name[2] = {"euler", "rk4"};
+  const char* fs_id[2] = {"KN_FS_EULER", "KN_FS_RK4"};
+  for (int k = 0; k < 2; ++k) {
+    s += std::string("extern \"C\" __global__ __launch_bounds__(ODE_BLOCK) void ode_user_fixed_") + fs_name[k] +
+         "_kernel(OdeDev D, OdeArgs a, int n_sub) {\n  ode_fixed_step_body<kn_fs::ModelUser, " + fs_id[k] + ">(D, a, n_sub);\n}\n";
+    s += std::string("extern \"C\" __global__ __launch_bounds__(ODE_BLOCK) void ode_user_fixed_") + fs_name[k] +
+         "_advance_kernel(OdeArgs a, OdeAdvArgs v, int n_sub) {\n  ode_fixed_advance_body<kn_fs::ModelUser, " + fs_id[k] +
+         ">(a, v, n_sub);\n}\n";
+  }
   return s;
 }
 
@@ -58,10 +85,10 @@ int lanes_for(int ns) { return (ns == 1 || ns == 2 || ns == 4 || ns == 8) ? ns :
 // compile for gfx950; `code` receives the code object, `log` the compiler's messages
 int compile(int ns, int np, const std::string& user, std::vector<char>* code, std::string* log) {
   const std::string src = wrapper_source(ns, np, lanes_for(ns), user);
-  const char* headers[2] = {SRC_LSODA_CORE, SRC_ODE_KERNEL};
-  const char* names[2] = {"lsoda_core.h", "ode_kernel.h"};
+  const char* headers[3] = {SRC_LSODA_CORE, SRC_ODE_KERNEL, SRC_FIXED_STEP};
+  const char* names[3] = {"lsoda_core.h", "ode_kernel.h", "fixed_step.h"};
   hiprtcProgram prog = nullptr;
-  if (hiprtcCreateProgram(&prog, src.c_str(), "knpemi_user_model.hip", 2, headers, names) != HIPRTC_SUCCESS) {
+  if (hiprtcCreateProgram(&prog, src.c_str(), "knpemi_user_model.hip", 3, headers, names) != HIPRTC_SUCCESS) {
     *log = "hiprtcCreateProgram failed";
     return KNPEMI_EHIP;
   }
@@ -140,6 +167,18 @@ int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, con
     kn_set_error("hipModuleGetFunction(ode_user_kernel / ode_user_advance_kernel) failed");
     return KNPEMI_EHIP;
   }
+  const char* fixed_names[2][2] = {{"ode_user_fixed_euler_kernel", "ode_user_fixed_euler_advance_kernel"},
+                                   {"ode_user_fixed_rk4_kernel", "ode_user_fixed_rk4_advance_kernel"}};
+  for (int k = 0; k < 2; ++k)
+    for (int j = 0; j < 2; ++j) {
+      hipFunction_t f = nullptr;
+      if (hipModuleGetFunction(&f, mod, fixed_names[k][j]) != hipSuccess) {
+        (void)hipModuleUnload(mod);
+        kn_set_error(std::string("hipModuleGetFunction(") + fixed_names[k][j] + ") failed");
+        return KNPEMI_EHIP;
+      }
+      m.rtc_fixed[k][j] = f;
+    }
   m.rtc_module = mod;
   m.rtc_function = fn;
   m.rtc_advance_function = fn_adv;
@@ -176,5 +215,40 @@ int kn_rtc_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* arg
   const unsigned grid = (unsigned)(((size_t)p.a.nq * m.rtc_lanes + ODE_BLOCK - 1) / ODE_BLOCK);
   KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_advance_function), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur,
                                nullptr, config));
+  return KNPEMI_OK;
+}
+
+// the fixed-step sweeps of a plug-in: one thread per dof, parameters (OdeDev, OdeArgs, int) / (OdeArgs, OdeAdvArgs, int)
+namespace {
+int fixed_index(const KnOdeModel& m) { return m.method == KNPEMI_ODE_EULER ? 0 : (m.method == KNPEMI_ODE_RK4 ? 1 : -1); }
+}  // namespace
+
+int kn_rtc_fixed_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, const void* args) {
+  const int k = fixed_index(m);
+  if (k < 0) { kn_set_error("a model bound from source runs lsoda, euler or rk4"); return KNPEMI_EINVAL; }
+  struct Params { OdeDev D; OdeArgs a; int n_sub; } p;
+  std::memcpy(&p.D, dev_view, sizeof(OdeDev));
+  std::memcpy(&p.a, args, sizeof(OdeArgs));
+  p.n_sub = m.n_substeps;
+  size_t size = sizeof(p);
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  const unsigned grid = (unsigned)(((size_t)p.a.nq + ODE_BLOCK - 1) / ODE_BLOCK);
+  KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_fixed[k][0]), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur, nullptr,
+                               config));
+  return KNPEMI_OK;
+}
+
+int kn_rtc_fixed_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, const void* adv) {
+  const int k = fixed_index(m);
+  if (k < 0) { kn_set_error("a model bound from source runs lsoda, euler or rk4"); return KNPEMI_EINVAL; }
+  struct Params { OdeArgs a; OdeAdvArgs v; int n_sub; } p;
+  std::memcpy(&p.a, args, sizeof(OdeArgs));
+  std::memcpy(&p.v, adv, sizeof(OdeAdvArgs));
+  p.n_sub = m.n_substeps;
+  size_t size = sizeof(p);
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  const unsigned grid = (unsigned)(((size_t)p.a.nq + ODE_BLOCK - 1) / ODE_BLOCK);
+  KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_fixed[k][1]), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur, nullptr,
+                               config));
   return KNPEMI_OK;
 }

@@ -1647,7 +1647,8 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
     if (ion_param[i] < 0 || ion_param[i] >= m.n_params)
       return fail(KNPEMI_EINVAL, "knpemi_ode_step: parameter index out of range");
   if (v_index < 0 || v_index >= m.n_states) return fail(KNPEMI_EINVAL, "knpemi_ode_step: bad V index");
-  if (!(dt > 0) || !(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))
+  const bool fixed = m.method != KNPEMI_ODE_LSODA;   // (a fixed-step method has no tolerances)
+  if (!(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
     return fail(KNPEMI_EINVAL, "knpemi_ode_step: bad dt / tolerances");
   if (h->ode_only && (flags & (KNPEMI_ODE_SET_TRACES | KNPEMI_ODE_SET_V)))
     return fail(KNPEMI_EINVAL, "knpemi_ode_step: a handle of knpemi_ode_create has no PDE fields to read");
@@ -1659,12 +1660,14 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
     KN_HIP(hipEventRecord(h->ev_fork, h->stream));
     KN_HIP(hipStreamWaitEvent(side, h->ev_fork, 0));
     h->cur = side;
-    int rc = kn_launch_ode_step(h, slot, t0, dt, rtol, atol, flags, ion_param, v_index);
+    int rc = fixed ? kn_launch_ode_fixed_step(h, slot, t0, dt, flags, ion_param, v_index)
+                   : kn_launch_ode_step(h, slot, t0, dt, rtol, atol, flags, ion_param, v_index);
     h->cur = h->stream;
     if (rc) return rc;
     KN_HIP(hipEventRecord(second ? h->ev_join2 : h->ev_join, side));
     return KNPEMI_OK;
   }
+  if (fixed) return kn_launch_ode_fixed_step(h, slot, t0, dt, flags, ion_param, v_index);
   return kn_launch_ode_step(h, slot, t0, dt, rtol, atol, flags, ion_param, v_index);
 }
 
@@ -1674,7 +1677,8 @@ extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
   const KnOdeModel& m = h->ode[slot];
-  if (n_steps < 0 || !(dt > 0) || !(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))
+  const bool fixed = m.method != KNPEMI_ODE_LSODA;
+  if (n_steps < 0 || !(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
     return fail(KNPEMI_EINVAL, "knpemi_ode_advance: bad n_steps / dt / tolerances");
   if (history) {
     if (every < 1 || n_rec < 1 || n_rec > 8 || !rec_idx)
@@ -1693,6 +1697,30 @@ extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t
   KN_HIP(hipStreamSynchronize(h->aux2));
   return kn_ode_advance(h, slot, t0, dt, n_steps, rtol, atol, rec_idx, n_rec, every, history, ss, steps_taken,
                         failed_step);
+}
+
+extern "C" int knpemi_ode_set_method(knpemi_handle* h, int sub, int model, int method, int n_substeps) {
+  int slot = ode_slot(h, sub, model, 1);
+  if (slot < 0) return KNPEMI_EINVAL;
+  KnOdeModel& m = h->ode[slot];
+  if (method < KNPEMI_ODE_LSODA || method > KNPEMI_ODE_RUSH_LARSEN)
+    return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: unknown method");
+  if (method != KNPEMI_ODE_LSODA && (n_substeps < 1 || n_substeps > 10000))
+    return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: n_substeps must be in 1..10000");
+  if (method == KNPEMI_ODE_RUSH_LARSEN && m.rtc_function)
+    return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: rush_larsen needs the gate rates of a model, and a model bound from "
+                               "source brings a right-hand side only (use euler or rk4)");
+  m.method = method;
+  m.n_substeps = method == KNPEMI_ODE_LSODA ? 0 : n_substeps;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_ode_get_method(knpemi_handle* h, int sub, int model, int* method, int* n_substeps) {
+  int slot = ode_slot(h, sub, model, 1);
+  if (slot < 0) return KNPEMI_EINVAL;
+  if (method) *method = h->ode[slot].method;
+  if (n_substeps) *n_substeps = h->ode[slot].n_substeps;
+  return KNPEMI_OK;
 }
 
 extern "C" int knpemi_ode_advance_chunk(knpemi_handle* h, int sub, int model) {
@@ -1717,6 +1745,8 @@ extern "C" int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n
   if (n_rhs) *n_rhs = (int64_t)st[0];
   if (n_steps) *n_steps = (int64_t)st[1];
   if (n_failed) *n_failed = (int32_t)st[2];
+  if (st[2] && mo.method != KNPEMI_ODE_LSODA)
+    return fail(KNPEMI_EODE, "the fixed-step integrator left a non-finite state on at least one membrane dof");
   if (st[2]) return fail(KNPEMI_EODE, "LSODA failed on at least one membrane dof (odeSolver.py:121 `assert success`)");
   return KNPEMI_OK;
 }

@@ -131,6 +131,9 @@ struct KnOdeModel {
   int rtc_lanes = 1;
   int* d_adv = nullptr;                   // [3][nq] knpemi_ode_advance: still-step counters, steps_taken, failed_step
   int adv_chunk = 0;                      // steps per launch the last knpemi_ode_advance chose
+  // integrator of the slot (knpemi_ode_set_method): KNPEMI_ODE_LSODA or a fixed-step scheme with n_substeps sub-steps
+  int method = 0, n_substeps = 0;
+  void* rtc_fixed[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // plug-in: [euler, rk4][step, advance] kernels
 };
 
 // blocks of the dense coarsest-level inverse, passed to the kernels by value: block b covers the unknowns start[b] ..
@@ -456,6 +459,12 @@ int kn_rtc_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, s
                   size_t args_bytes, const void* coef);
 int kn_rtc_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, size_t args_bytes, const void* adv,
                           size_t adv_bytes, const void* coef);
+// fixed-step integrators (kernels_ode_fixed.hip); `args` / `adv` are the OdeArgs / OdeAdvArgs of the launch
+int kn_launch_ode_fixed_step(knpemi_handle* h, int slot, double t0, double dt, int flags, const int32_t* ion_param,
+                             int v_index);
+int kn_launch_ode_fixed_advance(knpemi_handle* h, const KnOdeModel& m, const void* args, const void* adv);
+int kn_rtc_fixed_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, const void* args);
+int kn_rtc_fixed_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, const void* adv);
 int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
                    const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
                    int32_t* steps_taken, int32_t* failed_step);

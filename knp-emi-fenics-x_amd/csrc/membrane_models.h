@@ -70,6 +70,21 @@ struct ModelHHSI {
     I_K = i_K;
     dy[3] = (-i_K - i_Na) / Cm;
   }
+  // Gates for the Rush-Larsen scheme (fixed_step.h): components m, h, n obey dy/dt = a (1 - y) - b y with the rates of
+  // `rhs`, which depend on V only; V itself is stepped by Euler.
+  static constexpr unsigned GATES = 0x7u;
+  KN_HD void rates(double t, const double* y, double* a, double* b) const {
+    (void)t;
+    const double u = 1.0e3 * (y[3] + 65.0e-3);
+    a[0] = 0.1e3 * (25. - u) / (exp((25. - u) / 10.) - 1);
+    b[0] = 4.e3 * exp(-u / 18.);
+    a[1] = 0.07e3 * exp(-u / 20.);
+    b[1] = 1.e3 / (exp((30. - u) / 10.) + 1);
+    a[2] = 0.01e3 * (10. - u) / (exp((10. - u) / 10.) - 1.);
+    b[2] = 0.125e3 * exp(-u / 80.);
+    a[3] = 0.0;
+    b[3] = 0.0;
+  }
   // Component-wise evaluation for the one-lane-per-component integrator: lane c computes dy[c].  The
   // four lanes of a system run the same straight-line instruction stream; what differs per lane (offsets and scales
   // of the two exponent arguments, rate-law variant) is a handful of per-lane constants fixed by `set_lane` before the
@@ -152,6 +167,20 @@ struct ModelHHMV {
     I_K = i_K;
     dy[3] = (-i_K - i_Na) / Cm;
   }
+  // gates m, h, n for the Rush-Larsen scheme, see ModelHHSI::rates
+  static constexpr unsigned GATES = 0x7u;
+  KN_HD void rates(double t, const double* y, double* a, double* b) const {
+    (void)t;
+    const double u = y[3] + 65.0;
+    a[0] = 0.1 * (25. - u) / (exp((25. - u) / 10.) - 1);
+    b[0] = 4. * exp(-u / 18.);
+    a[1] = 0.07 * exp(-u / 20.);
+    b[1] = 1. / (exp((30. - u) / 10.) + 1);
+    a[2] = 0.01 * (10. - u) / (exp((10. - u) / 10.) - 1.);
+    b[2] = 0.125 * exp(-u / 80.);
+    a[3] = 0.0;
+    b[3] = 0.0;
+  }
   // component-wise evaluation, see ModelHHSI::rhs_lane
   static constexpr int CURRENT_LANE = 3;
   double l_a1, l_b1, l_a2, l_b2, l_ka, l_kb, l_k2, l_rCm;
@@ -227,6 +256,9 @@ struct ModelGlial {
     I_Cl = i_Cl;
     dy[0] = kn_div(-i_K - i_Na - i_Cl, Cm);
   }
+  // no gate: the Rush-Larsen scheme is forward Euler on this model (fixed_step.h)
+  static constexpr unsigned GATES = 0u;
+  KN_HD void rates(double, const double*, double* a, double* b) const { a[0] = 0.0; b[0] = 0.0; }
   static constexpr int CURRENT_LANE = 0;
   KN_HD double rhs_lane(int, double t, const double* y) const {
     double dy[1];

@@ -23,6 +23,9 @@ A_EMI, P_EMI, A_KNP = 0, 1, 2
 B_EMI, B_KNP = 0, 1
 WANT_P, NO_SPLITTING, SKIP_MEMBRANE_RHS, ON_AUX_STREAM, MEMBRANE_EARLY = 1, 2, 4, 8, 16
 ODE_SET_V, ODE_SET_TRACES, ODE_ON_AUX, ODE_ON_AUX2 = 1, 2, 4, 8
+ODE_LSODA, ODE_EULER, ODE_RK4, ODE_RUSH_LARSEN = 0, 1, 2, 3
+ODE_METHODS = {"lsoda": ODE_LSODA, "euler": ODE_EULER, "rk4": ODE_RK4, "rush_larsen": ODE_RUSH_LARSEN}
+ODE_DEFAULT_SUBSTEPS = 25   # the reference drivers' n_steps_ODE (run_2D.py:176)
 OPT_FUSE_UPDATE, OPT_FUSE_MEMBRANE, OPT_PROFILE_STRIDE, OPT_KNP_MIN_IT, OPT_FOLD_MEMBRANE, OPT_KNP_METHOD = 1, 2, 3, 4, 5, 6
 OPT_EMI_NORM = 7
 OBS_SUM, OBS_MIN, OBS_MAX = 0, 1, 2
@@ -143,6 +146,8 @@ SIGNATURES = {
                                      C.c_double, c_int_p, C.c_int, C.c_int, c_dbl_p, C.POINTER(OdeSS), c_int_p,
                                      c_int_p]),
     "knpemi_ode_advance_chunk": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "knpemi_ode_set_method": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "knpemi_ode_get_method": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "knpemi_debug_ode_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int]),
     "knpemi_debug_math": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_debug_launch_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dbl_p]),

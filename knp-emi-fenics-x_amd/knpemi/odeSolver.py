@@ -88,6 +88,7 @@ class MembraneModel:
         self.prefix = ode.__name__
         self.time = 0
         self.rtol, self.atol = 1.0e-8, 1.0e-10   # odeSolver.py:120
+        self.method, self.substeps = "lsoda", None   # set_integrator
         self.last_stats = None
         # device binding (set by DeviceProblem through emi_system / knp_system)
         self._dp = None
@@ -131,6 +132,7 @@ class MembraneModel:
         self._ion_param = np.array(idx if idx else [0], np.int32)
         if not isinstance(dp, OdeProblem):
             self._standalone = None   # moved to a PDE problem: the host tables travel with every step
+        self._apply_integrator()
 
     def _device(self):
         """The bound problem; a model no PDE problem has claimed gets a handle of its own."""
@@ -225,8 +227,44 @@ class MembraneModel:
         return self.ode.state_indices('V')
 
     # ---- ODE integration ------
+    def set_integrator(self, method="lsoda", substeps=None):
+        '''The integrator `step`, `advance` and `steady_state` use: "lsoda" (default, rtol / atol of the model), or a
+        fixed-step scheme with `substeps` equal sub-steps per step -- "euler", "rk4", "rush_larsen" (gates by their
+        exponential update, the rest by Euler).  substeps=None takes 25, the reference drivers' `n_steps_ODE`.
+        The currents a fixed-step method hands out are those at the end state of the step.'''
+        if method not in L.ODE_METHODS:
+            raise ValueError(f"unknown integrator {method!r}: one of {sorted(L.ODE_METHODS)}")
+        if method == "lsoda":
+            substeps = None
+        else:
+            substeps = L.ODE_DEFAULT_SUBSTEPS if substeps is None else int(substeps)
+            if not 1 <= substeps <= 10000:
+                raise ValueError("substeps must be in 1..10000")
+        old = self.method, self.substeps
+        self.method, self.substeps = method, substeps
+        if self._dp is not None:
+            try:
+                self._apply_integrator()
+            except L.KnpemiError:
+                self.method, self.substeps = old
+                raise
+
+    def _apply_integrator(self):
+        L.check(self._dp.lib.knpemi_ode_set_method(self._dp.h, self._sub, self._model, L.ODE_METHODS[self.method],
+                                                   int(self.substeps or 0)))
+
+    def step(self, dt, stimulus, stimulus_locator=None):
+        '''Solve the ODEs forward by dt with the integrator of `set_integrator` (on the GPU)'''
+        return self._step(dt, stimulus, stimulus_locator)
+
     def step_lsoda(self, dt, stimulus, stimulus_locator=None):
         '''Solve the ODEs forward by dt with optional stimulus (on the GPU)'''
+        if self.method != "lsoda":
+            raise RuntimeError(f"step_lsoda integrates with LSODA, but this model is configured for "
+                               f"{self.method!r} (set_integrator): call step(), which uses the configured integrator")
+        return self._step(dt, stimulus, stimulus_locator)
+
+    def _step(self, dt, stimulus, stimulus_locator):
         if stimulus is None:
             stimulus = {}
         dp = self._device()
@@ -246,14 +284,17 @@ class MembraneModel:
         L.check(lib.knpemi_ode_get_tables(dp.h, self._sub, self._model, L.dptr(states), L.dptr(params)))
         self.states[...] = states
         self.parameters[...] = params
-        assert rc == L.OK, "LSODA failed on at least one membrane dof"   # odeSolver.py:121
+        assert rc == L.OK, (
+            "LSODA failed on at least one membrane dof" if self.method == "lsoda"   # odeSolver.py:121
+            else f"{self.method} left a non-finite state on at least one membrane dof")
         self.time = self.time + dt
         print(f'\t{self.prefix} Stepped {self.nodes} ODES in {ms * 1e-3}s')
         return self.states
 
     # ---- many steps per launch (no reference counterpart: its calibration tool loops over step_lsoda) ------
     def advance(self, dt, n_steps, stimulus=None, stimulus_locator=None, record=None, every=1):
-        '''n_steps successive step_lsoda(dt, stimulus, stimulus_locator) calls, bit for bit, in launches of many steps.
+        '''n_steps successive step(dt, stimulus, stimulus_locator) calls (step_lsoda unless set_integrator chose another
+        method), bit for bit, in launches of many steps.
         `record`: state names recorded after every `every`-th step; returns {name: ndarray[n_steps // every, nodes]}.'''
         _, hist = self._advance(dt, n_steps, stimulus, stimulus_locator, record, every, None)
         return hist
@@ -304,7 +345,8 @@ class MembraneModel:
         out = {n: hist[:, i, :] for i, n in enumerate(names)} if names else {}
         if rc == L.EODE:   # odeSolver.py:121 `assert success`
             bad = np.flatnonzero(failed >= 0)
-            raise RuntimeError(f"LSODA failed on {len(bad)} membrane dof(s): dofs {bad[:10].tolist()} at steps "
+            what = "LSODA" if self.method == "lsoda" else f"the {self.method} integrator"
+            raise RuntimeError(f"{what} failed on {len(bad)} membrane dof(s): dofs {bad[:10].tolist()} at steps "
                                f"{failed[bad[:10]].tolist()}")
         print(f'\t{self.prefix} Advanced {self.nodes} ODES by {n_steps} steps in {ms * 1e-3}s')
         return steps, out

@@ -24,7 +24,8 @@ from . import _lib as L
 class DeviceStepper:
     def __init__(self, forms_emi, forms_knp, c, c_prev, phi, phi_M_prev, solve_emi=None, solve_knp=None,
                  assemble_knp_twice=False, overlap=True, device_solves=None, extrapolate_guess=True,
-                 fuse_update=None, fuse_membrane=False, early_membrane=False, knp_method="gmres"):
+                 fuse_update=None, fuse_membrane=False, early_membrane=False, knp_method="gmres",
+                 ode_method="lsoda", ode_substeps=None):
         a = forms_emi[0]
         self.dp = a.dp
         self.a = a
@@ -63,6 +64,11 @@ class DeviceStepper:
         self.k = 0
         self.models = []   # MembraneModel objects, in registration order
         self._model_setup = []   # (MembraneModel, stimulus, locator, initial time) for reset()
+        # integrator of every membrane model (MembraneModel.set_integrator): "lsoda", or "euler" / "rk4" / "rush_larsen"
+        # with ode_substeps sub-steps per time step (None: 25, the reference drivers' n_steps_ODE)
+        if ode_method not in L.ODE_METHODS:
+            raise ValueError(f"unknown ode_method {ode_method!r}: one of {sorted(L.ODE_METHODS)}")
+        self.ode_method, self.ode_substeps = ode_method, ode_substeps
         dp = self.dp
         dp.set_params(a.physical_params, a.ion_list, a.dt)
         L.check(self.lib.knpemi_set_option(dp.h, L.OPT_FUSE_UPDATE, 1 if self.fuse_update else 0))
@@ -105,6 +111,7 @@ class DeviceStepper:
     def add_membrane_model(self, ode_model, stimulus=None, stimulus_locator=None):
         """Register a bound MembraneModel: uploads its tables and stimulus once."""
         dp = self.dp
+        ode_model.set_integrator(self.ode_method, self.ode_substeps)
         stimulus = stimulus or {}
         if stimulus_locator is None:
             mask = np.ones(ode_model.nodes, np.uint8)
@@ -180,6 +187,8 @@ class DeviceStepper:
         failed on any membrane dof since the last check (the counters live on the device; this synchronises)."""
         n = self.ode_failures()
         if n:
+            if self.ode_method != "lsoda":
+                raise L.KnpemiError(L.EODE, f"{self.ode_method} left a non-finite state on {n} membrane dof(s)")
             raise L.KnpemiError(L.EODE, f"LSODA failed on {n} membrane dof(s) (odeSolver.py:121 `assert success`)")
 
     def download(self):

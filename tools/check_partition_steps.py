@@ -36,11 +36,11 @@ def membrane_models(s):
     return [(tag, mm) for tag, sd in s.subdomain_list.items() if tag > 0 for mm in sd.get('mem_models', [])]
 
 
-def run(s, K, halo, mem_halo, solves=None, jacobi=False):
+def run(s, K, halo, mem_halo, solves=None, jacobi=False, ode_method="lsoda", ode_substeps=None):
     from knpemi.stepper import DeviceStepper
     from knpemi import _lib as L
     st = DeviceStepper((s.a_emi, s.p_emi, s.L_emi), (s.a_knp, s.p_knp, s.L_knp), s.c, s.c_prev, s.phi, s.phi_M_prev,
-                       device_solves=solves)
+                       device_solves=solves, ode_method=ode_method, ode_substeps=ode_substeps)
     if jacobi:
         st.dp.solver_setup(L.B_EMI, L.PC_JACOBI)
         st.dp.solver_setup(L.B_KNP, L.PC_JACOBI)
@@ -115,6 +115,9 @@ def main():
     ap.add_argument("--family", default="idealized", choices=["idealized", "astro"],
                     help="astro: the three-sub-domain driver (ECS + neuron HH + glia Kir4.1/pump, pulsed ECS source) of "
                          "examples/local_astrocyte_depolarization on a general cell partition (rcb / slab)")
+    ap.add_argument("--ode-method", default="lsoda", choices=["lsoda", "euler", "rk4", "rush_larsen"],
+                    help="membrane integrator of both runs (DeviceStepper(ode_method=...))")
+    ap.add_argument("--ode-substeps", type=int, default=None)
     a = ap.parse_args()
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     torch.cuda.set_device(0)
@@ -147,7 +150,7 @@ def main():
             s = make_partitioned_problem(a.kind, a.resolution, rank, world, g_syn=10.0, method=a.method)
     L_x = s.global_length
     init_fields(s, L_x, scale, v_rest)
-    loc = run(s, a.steps, s.halo, not a.no_mem_halo, solves, a.jacobi)
+    loc = run(s, a.steps, s.halo, not a.no_mem_halo, solves, a.jacobi, a.ode_method, a.ode_substeps)
     its_local = loc.pop("iterations")
     rows = loc.pop("rows")
     hx = L_x / (2 * world * 16 * 2 ** a.resolution)
@@ -171,7 +174,7 @@ def main():
             else:
                 g = Setup(a.kind, a.resolution, g_syn=10.0, mesh_data=make_mesh_3D(a.resolution, ctype, l=2 * world))
         init_fields(g, L_x, scale, v_rest)
-        ref = run(g, a.steps, None, True, solves, a.jacobi)
+        ref = run(g, a.steps, None, True, solves, a.jacobi, a.ode_method, a.ode_substeps)
         its_ref = ref.pop("iterations")
         ref_rows = ref.pop("rows")
         key = lambda x: tuple(np.rint(x / (hx / 64)).astype(np.int64))
@@ -213,6 +216,7 @@ def main():
         else:
             # owner-computes rows + deterministic kernels: the partitioned run reproduces the single-rank run bit for bit
             assert max(worst.values()) == 0.0, worst
+        print(f"ode_method {a.ode_method}" + (f", {a.ode_substeps} sub-steps" if a.ode_substeps else ""))
         print("PARTITION STEPS OK")
     dist.barrier()
     dist.destroy_process_group()
