@@ -32,7 +32,7 @@
 #include <cstring>
 
 #include "dg_internal.h"
-#include "ode_kernel.h"
+#include "ode_host.h"
 
 namespace {
 
@@ -1617,7 +1617,7 @@ extern "C" int knpemi_dg_ode_bind(knpemi_dg* h, int model_id, int n_states, int 
   for (int pass = 0; pass < 2; ++pass) {
     const int cols = pass ? n_params : n_states;
     const double* src = pass ? params : states;
-    for (int r = 0; r < nq; ++r) for (int c = 0; c < cols; ++c) t[(size_t)c * nq + r] = src[(size_t)r * cols + c];
+    kn_transpose(src, t.data(), nq, cols);
     if (nq) KN_HIP(hipMemcpy(pass ? h->d_params : h->d_states, t.data(), (size_t)cols * nq * sizeof(double), hipMemcpyHostToDevice));
   }
   if ((rc = kn_lsoda_coef_upload(&h->d_coef))) return rc;
@@ -1631,14 +1631,12 @@ extern "C" int knpemi_dg_ode_step(knpemi_dg* h, double t0, double dt, double rto
   if (h->dev.nq == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
   const DgDev& D = h->dev;
-  OdeDev dv{D.rec, D.q2e, D.q2i, D.phiM, D.Ich};
-  OdeArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.nq = D.nq; a.q0 = 0; a.n_stim = 0; a.flags = flags & (KNPEMI_ODE_SET_V | KNPEMI_ODE_SET_TRACES); a.v_index = h->ode_v;
-  a.model_slot = 0; a.NQtot = D.nq; a.n_ions = h->K;
-  for (int i = 0; i < 3 * KN_MAXK; ++i) a.ion_param[i] = h->ode_ion_param[i];
-  a.t0 = t0; a.dt = dt; a.rtol = rtol; a.atol = atol;
-  a.states = h->d_states; a.params = h->d_params; a.mask = nullptr; a.stats = h->d_stats; a.stamps = nullptr;
+  const OdeDev dv{D.rec, D.q2e, D.q2i, D.phiM, D.Ich};
+  // the membrane nodes are one table of their own (offset 0, slot 0) without stimulus or mask; of the caller's flags
+  // only the exchange with the PDE fields reaches the kernel
+  const OdePde pde{flags & (KNPEMI_ODE_SET_V | KNPEMI_ODE_SET_TRACES), h->ode_v, h->K, h->ode_ion_param};
+  const OdeArgs a = kn_ode_args(OdeTables{D.nq, 0, D.nq, 0, h->d_states, h->d_params, nullptr, h->d_stats}, t0, dt, rtol,
+                                atol, &pde);
   return kn_launch_ode_raw(h->stream, h->ode_model, dv, a, h->d_coef);
 }
 
@@ -1653,7 +1651,7 @@ extern "C" int knpemi_dg_ode_get_tables(knpemi_dg* h, double* states, double* pa
     if (!dst || !nq) continue;
     const int cols = pass ? h->ode_np : h->ode_ns;
     KN_HIP(hipMemcpy(t.data(), pass ? h->d_params : h->d_states, (size_t)cols * nq * sizeof(double), hipMemcpyDeviceToHost));
-    for (int r = 0; r < nq; ++r) for (int c = 0; c < cols; ++c) dst[(size_t)r * cols + c] = t[(size_t)c * nq + r];
+    kn_transpose(t.data(), dst, cols, nq);
   }
   return KNPEMI_OK;
 }
@@ -1662,15 +1660,12 @@ extern "C" int knpemi_dg_ode_stats(knpemi_dg* h, int64_t* n_rhs, int64_t* n_step
   if (!h || h->ode_model < 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_stats: no membrane model bound");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
-  std::vector<unsigned long long> part(3 * (size_t)h->ode_blocks);
-  KN_HIP(hipMemcpyAsync(part.data(), h->d_stats, part.size() * sizeof(part[0]), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipMemsetAsync(h->d_stats, 0, part.size() * sizeof(part[0]), h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  unsigned long long st[3] = {0, 0, 0};
-  for (size_t i = 0; i < part.size(); ++i) st[i % 3] += part[i];
+  unsigned long long st[3];
+  const int rc = kn_ode_read_stats(h->stream, h->d_stats, h->ode_blocks, st);
+  if (rc) return rc;
   if (n_rhs) *n_rhs = (int64_t)st[0];
   if (n_steps) *n_steps = (int64_t)st[1];
   if (n_failed) *n_failed = (int64_t)st[2];
-  if (st[2]) return dg_fail(KNPEMI_EODE, "LSODA failed on at least one membrane node (odeSolver.py:121 `assert success`)");
+  if (st[2]) return dg_fail(KNPEMI_EODE, kn_ode_failure(true, "at least one membrane node"));
   return KNPEMI_OK;
 }

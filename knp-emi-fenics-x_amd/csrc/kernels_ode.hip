@@ -14,95 +14,153 @@
 // Tables are stored transposed on the device ([column][dof]) so that neighbouring threads read
 // neighbouring addresses; the ODE work itself is latency/compute bound (fp64 exp/log, divergent
 // step control), not HBM bound.
+//
+// Host side (ode_host.h): this file builds the arguments of every sweep (kn_ode_args) and decides every launch
+// (launch_sweep: plug-in or shipped model, LSODA here or a fixed-step kernel of kernels_ode_fixed.hip); kn_ode_step and
+// kn_ode_advance are the two entries, one per kernel shape.
 #include <algorithm>
 #include <cstdlib>
 
-#include "knpemi_internal.h"
-#include "membrane_models.h"
-#include "ode_kernel.h"
+#include "ode_host.h"
 
-namespace {
-
-OdeDev ode_dev(const knpemi_handle* h) {
+OdeDev kn_ode_dev(const knpemi_handle* h) {
   const KnDev& D = h->dev;
   return OdeDev{D.VR, D.q2e, D.q2i, D.phiM, D.Ich};
 }
 
+OdeArgs kn_ode_args(const OdeTables& T, double t0, double dt, double rtol, double atol, const OdePde* pde) {
+  OdeArgs a{};   // what no branch below sets stays zero: no stimulus, full waves (dpw), no stamps
+  a.nq = T.nq; a.q0 = T.q0; a.NQtot = T.NQtot; a.model_slot = T.model_slot;
+  a.states = T.states; a.params = T.params; a.mask = T.mask; a.stats = T.stats;
+  a.t0 = t0; a.dt = dt; a.rtol = rtol; a.atol = atol;
+  if (pde) {   // a step of the coupled problem reads traces / V from the PDE fields and writes phi_M / I_ch back
+    a.flags = pde->flags; a.v_index = pde->v_index; a.n_ions = pde->n_ions;
+    for (int i = 0; i < 3 * pde->n_ions; ++i) a.ion_param[i] = pde->ion_param[i];
+  } else {     // a standalone advance touches its own tables only: no flags, no ions, no V column to exchange
+    a.v_index = -1;
+  }
+  return a;
+}
+
+namespace {
+
 // Dofs per wavefront (ode_step_body): as few as keep the sweep at one wave per SIMD (1 024 SIMDs; the stats slots of the
 // handle's sweeps are sized for that), all 64 / LANES of them otherwise.  KNPEMI_ODE_DPW forces a value (0: full waves).
-int dofs_per_wave(int nq, int lanes, int max_blocks) {
+int dofs_per_wave(const KnOdeModel& m) {
+  if (m.rtc_module) return 0;   // a run-time compiled sweep is launched with full waves (launch_sweep)
   static const int forced = [] { const char* e = getenv("KNPEMI_ODE_DPW"); return e ? atoi(e) : -1; }();
-  const int full = ODE_BLOCK / lanes;
-  if (forced >= 0) return forced > 0 && forced < full && (nq + forced - 1) / forced <= max_blocks ? forced : 0;
   // Measured at config 2 (2 952 dofs; round 4, bench.py): 16 dofs per wave 77.5-81 us per sweep, 8: 83.1, 4: 83.1 (spike
   // window 106.7 / 110.8 / 104.6): fewer dofs per wave do NOT shorten the wave's stream measurably -- the trips of the 16
   // phase machines of a wave overlap almost completely -- and four times the waves cost more than they save.  Full waves
   // unless forced.
-  (void)max_blocks;
-  return 0;
+  if (forced <= 0) return 0;
+  int full = 0;
+  with_model(m.model_id, [&](auto tag) { full = ODE_BLOCK / tag.LANES; });
+  return forced < full && (m.nq + forced - 1) / forced <= m.n_stat_blocks - 1 ? forced : 0;
 }
 
-template <class M, int LANES>
-void launch_model(hipStream_t st, const OdeDev& dv, const OdeArgs& a, const LsodaCoef* cf, int force_waves) {
-  const int per_wave = a.dpw > 0 ? a.dpw : ODE_BLOCK / LANES;
-  dim3 grid(((size_t)a.nq + per_wave - 1) / per_wave), block(ODE_BLOCK);
-  // more waves than 1.5 x the chip's 1024 SIMDs: trade registers for a second resident wave per SIMD
-  const bool dense = force_waves ? force_waves == 2 : (size_t)grid.x > 1536;
-  if (a.stamps) hipLaunchKernelGGL((ode_step_kernel<M, LANES, 1, true>), grid, block, 0, st, dv, a, cf);
-  else if (dense) hipLaunchKernelGGL((ode_step_kernel<M, LANES, 2>), grid, block, 0, st, dv, a, cf);
-  else hipLaunchKernelGGL((ode_step_kernel<M, LANES, 1>), grid, block, 0, st, dv, a, cf);
+// the arguments of a sweep over the tables of model `slot` of the handle
+OdeArgs model_args(const knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde* pde) {
+  const KnOdeModel& m = h->ode[slot];
+  const bool lsoda = m.method == KNPEMI_ODE_LSODA;
+  // a fixed-step method has no tolerances, and its kernels run one thread per dof whatever dpw says
+  OdeArgs a = kn_ode_args(OdeTables{m.nq, h->qoff[m.sub], h->dev.NQtot, slot, m.d_states, m.d_params, m.d_mask, m.d_stats},
+                          t0, dt, lsoda ? rtol : 0.0, lsoda ? atol : 0.0, pde);
+  a.n_stim = m.n_stim;
+  for (int i = 0; i < 8; ++i) { a.stim_idx[i] = m.stim_idx[i]; a.stim_val[i] = m.stim_val[i]; }
+  if (lsoda) a.dpw = dofs_per_wave(m);
+  return a;
 }
 
-int launch_builtin(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const LsodaCoef* cf, int force_waves) {
-  switch (model_id) {
-    case KNPEMI_MODEL_HH_SI: launch_model<ModelHHSI, 4>(st, dv, a, cf, force_waves); break;
-    case KNPEMI_MODEL_HH_MV: launch_model<ModelHHMV, 4>(st, dv, a, cf, force_waves); break;
-    default: launch_model<ModelGlial, 1>(st, dv, a, cf, force_waves); break;
+dim3 lsoda_grid(const OdeArgs& a, int lanes) {
+  const int per_wave = a.dpw > 0 ? a.dpw : ODE_BLOCK / lanes;
+  return dim3(((size_t)a.nq + per_wave - 1) / per_wave);
+}
+
+// 64-thread workgroups: the sweep has only n_q (10^3..10^5) threads, so spread the waves over as many CUs as possible
+// instead of stacking four of them on one.  force_waves: KNPEMI_ODE_WAVES (1 or 2 resident waves per SIMD), 0: by size
+int launch_lsoda_step(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const LsodaCoef* cf, int force_waves) {
+  with_model(model_id, [&](auto tag) {
+    using M = typename decltype(tag)::Model;
+    constexpr int LANES = decltype(tag)::LANES;
+    const dim3 grid = lsoda_grid(a, LANES), block(ODE_BLOCK);
+    // more waves than 1.5 x the chip's 1024 SIMDs: trade registers for a second resident wave per SIMD
+    const bool dense = force_waves ? force_waves == 2 : (size_t)grid.x > 1536;
+    if (a.stamps) hipLaunchKernelGGL((ode_step_kernel<M, LANES, 1, true>), grid, block, 0, st, dv, a, cf);
+    else if (dense) hipLaunchKernelGGL((ode_step_kernel<M, LANES, 2>), grid, block, 0, st, dv, a, cf);
+    else hipLaunchKernelGGL((ode_step_kernel<M, LANES, 1>), grid, block, 0, st, dv, a, cf);
+  });
+  return kn_launch_check("ode_step_kernel");
+}
+
+int launch_lsoda_advance(hipStream_t st, int model_id, const OdeArgs& a, const OdeAdvArgs& v, const LsodaCoef* cf) {
+  with_model(model_id, [&](auto tag) {
+    using M = typename decltype(tag)::Model;
+    constexpr int LANES = decltype(tag)::LANES;
+    const dim3 grid = lsoda_grid(a, LANES), block(ODE_BLOCK);
+    if ((size_t)grid.x > 1536) hipLaunchKernelGGL((ode_advance_kernel<M, LANES, 2>), grid, block, 0, st, a, v, cf);
+    else hipLaunchKernelGGL((ode_advance_kernel<M, LANES, 1>), grid, block, 0, st, a, v, cf);
+  });
+  return kn_launch_check("ode_advance_kernel");
+}
+
+// The launch decision of every sweep of a handle: model source, integrator, kernel shape (v NULL: one step, which
+// exchanges with the PDE fields; else the n steps v describes).  On h->cur.
+int launch_sweep(knpemi_handle* h, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs* v, const LsodaCoef* cf) {
+  const bool lsoda = m.method == KNPEMI_ODE_LSODA;
+  const OdeDev dv = kn_ode_dev(h);
+  if (m.rtc_module) {   // plug-in compiled at bind time (kernels_rtc.hip)
+    const hipFunction_t fn = m.rtc_kernel[m.method][v != nullptr];
+    if (!fn) { kn_set_error("a model bound from source runs lsoda, euler or rk4"); return KNPEMI_EINVAL; }
+    // LSODA: rtc_lanes lanes per dof in full waves; fixed-step: one thread per dof
+    const unsigned grid = (unsigned)(((size_t)a.nq * (lsoda ? m.rtc_lanes : 1) + ODE_BLOCK - 1) / ODE_BLOCK);
+    if (lsoda) return v ? kn_rtc_launch(h->cur, fn, grid, a, *v, cf) : kn_rtc_launch(h->cur, fn, grid, dv, a, cf);
+    return v ? kn_rtc_launch(h->cur, fn, grid, a, *v, m.n_substeps) : kn_rtc_launch(h->cur, fn, grid, dv, a, m.n_substeps);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    kn_set_error(std::string("ode_step_kernel: ") + hipGetErrorString(e));
-    return KNPEMI_EHIP;
-  }
-  return KNPEMI_OK;
+  if (!lsoda) return v ? kn_launch_ode_fixed_advance(h->cur, m, a, *v) : kn_launch_ode_fixed_step(h->cur, m, dv, a);
+  if (v) return launch_lsoda_advance(h->cur, m.model_id, a, *v, cf);
+  // KNPEMI_ODE_WAVES applies to the single-step launch only
+  static const int force_waves = [] { const char* e = getenv("KNPEMI_ODE_WAVES"); return e ? atoi(e) : 0; }();
+  return launch_lsoda_step(h->cur, m.model_id, dv, a, cf, force_waves);
 }
 
-}  // namespace
-
-static int ensure_coef(knpemi_handle* h, const LsodaCoef** out) {
+// the handle's copy of the LSODA coefficient tables, uploaded on first use
+int lsoda_coef(knpemi_handle* h, const LsodaCoef** out) {
   if (!h->d_lsoda_coef) {
-    LsodaCoef c;
-    lsoda_fill_coef(&c);
     void* d = nullptr;
-    KN_HIP(hipMalloc(&d, sizeof(LsodaCoef)));
+    const int rc = kn_lsoda_coef_upload(&d);
+    if (rc) return rc;
     h->allocs.push_back(d);
-    KN_HIP(hipMemcpy(d, &c, sizeof(LsodaCoef), hipMemcpyHostToDevice));
     h->d_lsoda_coef = d;
   }
   *out = static_cast<const LsodaCoef*>(h->d_lsoda_coef);
   return KNPEMI_OK;
 }
 
-int kn_launch_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol,
-                       int flags, const int32_t* ion_param, int v_index) {
+}  // namespace
+
+int kn_lsoda_coef_upload(void** out) {
+  LsodaCoef c;
+  lsoda_fill_coef(&c);
+  void* d = nullptr;
+  KN_HIP(hipMalloc(&d, sizeof(LsodaCoef)));
+  KN_HIP(hipMemcpy(d, &c, sizeof(LsodaCoef), hipMemcpyHostToDevice));
+  *out = d;
+  return KNPEMI_OK;
+}
+
+// ---- one PDE step per launch (knpemi_ode_step) -------------------------------------------------------------------
+int kn_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde& pde) {
   KnOdeModel& m = h->ode[slot];
   if (m.nq == 0) return KNPEMI_OK;
   const LsodaCoef* cf = nullptr;
-  int rc = ensure_coef(h, &cf);
-  if (rc) return rc;
-  OdeArgs a;
-  a.nq = m.nq; a.q0 = h->qoff[m.sub]; a.n_stim = m.n_stim; a.flags = flags; a.v_index = v_index;
-  a.model_slot = slot; a.NQtot = h->dev.NQtot; a.n_ions = h->K;
-  for (int i = 0; i < 3 * KN_MAXK; ++i) a.ion_param[i] = i < 3 * h->K ? ion_param[i] : 0;
-  for (int i = 0; i < 8; ++i) { a.stim_idx[i] = m.stim_idx[i]; a.stim_val[i] = m.stim_val[i]; }
-  a.t0 = t0; a.dt = dt; a.rtol = rtol; a.atol = atol;
-  a.states = m.d_states; a.params = m.d_params; a.mask = m.d_mask; a.stats = m.d_stats;
-  a.dpw = dofs_per_wave(m.nq, m.rtc_function ? m.rtc_lanes : (m.n_states == 4 ? 4 : 1), m.n_stat_blocks - 1);
-  if (m.rtc_function) a.dpw = 0;      // (the run-time compiled sweep is launched with full waves, kernels_rtc.hip)
-  // KNPEMI_ODE_STAMPS=1: diagnostic build of the sweep with s_memtime stamps between the phases (tools/ode_stamps.py)
+  int rc;
+  if (m.method == KNPEMI_ODE_LSODA && (rc = lsoda_coef(h, &cf))) return rc;
+  OdeArgs a = model_args(h, slot, t0, dt, rtol, atol, &pde);
+  // KNPEMI_ODE_STAMPS=1: diagnostic build of the sweep with s_memtime stamps between the phases (tools/ode_stamps.py);
+  // only the LSODA kernels of the shipped models have one
   static const bool want_stamps = getenv("KNPEMI_ODE_STAMPS") != nullptr;
-  a.stamps = nullptr;
-  if (want_stamps) {
+  if (want_stamps && m.method == KNPEMI_ODE_LSODA && !m.rtc_module) {
     if (!m.d_stamps) {
       void* d = nullptr;
       KN_HIP(hipMalloc(&d, 24 * sizeof(unsigned long long) * (size_t)m.n_stat_blocks));
@@ -111,45 +169,14 @@ int kn_launch_ode_step(knpemi_handle* h, int slot, double t0, double dt, double 
     }
     a.stamps = m.d_stamps;
   }
-  // counters accumulate over launches; knpemi_ode_stats() reads and resets them
-  // 64-thread workgroups: the sweep has only n_q (10^3..10^5) threads, so spread the waves over as
-  // many CUs as possible instead of stacking four of them on one.
-  static const int force_waves = [] { const char* e = getenv("KNPEMI_ODE_WAVES"); return e ? atoi(e) : 0; }();
+  // counters accumulate over launches; knpemi_ode_stats() reads and resets them.  One profiling slot whatever the
+  // integrator: it is "the ODE kernel" of the step for DeviceStepper's stream choice
   KnProfScope prof(h, KNPEMI_K_ODE);
-  if (m.rtc_function) {   // plug-in compiled at bind time (kernels_rtc.hip)
-    const OdeDev dv = ode_dev(h);
-    a.stamps = nullptr;
-    return kn_rtc_launch(h, m, &dv, sizeof(dv), &a, sizeof(a), cf);
-  }
-  return launch_builtin(h->cur, m.model_id, ode_dev(h), a, cf, force_waves);
+  return launch_sweep(h, m, a, nullptr, cf);
 }
 
 // ---- n steps per launch (knpemi_ode_advance) -------------------------------------------------------------------
 namespace {
-
-template <class M, int LANES>
-void launch_advance_model(hipStream_t st, const OdeArgs& a, const OdeAdvArgs& v, const LsodaCoef* cf) {
-  const int per_wave = a.dpw > 0 ? a.dpw : ODE_BLOCK / LANES;
-  dim3 grid(((size_t)a.nq + per_wave - 1) / per_wave), block(ODE_BLOCK);
-  if ((size_t)grid.x > 1536) hipLaunchKernelGGL((ode_advance_kernel<M, LANES, 2>), grid, block, 0, st, a, v, cf);
-  else hipLaunchKernelGGL((ode_advance_kernel<M, LANES, 1>), grid, block, 0, st, a, v, cf);
-}
-
-int launch_advance(knpemi_handle* h, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs& v, const LsodaCoef* cf) {
-  if (m.method != KNPEMI_ODE_LSODA) return kn_launch_ode_fixed_advance(h, m, &a, &v);   // kernels_ode_fixed.hip
-  if (m.rtc_function) return kn_rtc_advance_launch(h, m, &a, sizeof(a), &v, sizeof(v), cf);
-  switch (m.model_id) {
-    case KNPEMI_MODEL_HH_SI: launch_advance_model<ModelHHSI, 4>(h->cur, a, v, cf); break;
-    case KNPEMI_MODEL_HH_MV: launch_advance_model<ModelHHMV, 4>(h->cur, a, v, cf); break;
-    default: launch_advance_model<ModelGlial, 1>(h->cur, a, v, cf); break;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    kn_set_error(std::string("ode_advance_kernel: ") + hipGetErrorString(e));
-    return KNPEMI_EHIP;
-  }
-  return KNPEMI_OK;
-}
 
 // Steps per launch.  A launch of a few tens of ms at most keeps a long run from holding the device for seconds; the
 // first launch runs a few steps and is timed, the rest are sized from it.  KNPEMI_ODE_ADVANCE_CHUNK forces a size.
@@ -169,9 +196,10 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   KnOdeModel& m = h->ode[slot];
   m.adv_chunk = 0;
   if (m.nq == 0 || n_steps == 0) return KNPEMI_OK;
+  const bool lsoda = m.method == KNPEMI_ODE_LSODA;
   const LsodaCoef* cf = nullptr;
-  int rc = ensure_coef(h, &cf);
-  if (rc) return rc;
+  int rc = KNPEMI_OK;
+  if (lsoda && (rc = lsoda_coef(h, &cf))) return rc;
   const size_t nq = (size_t)m.nq;
   if (!m.d_adv) {   // still-step counters, steps_taken, failed_step
     void* d = nullptr;
@@ -179,13 +207,7 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
     h->allocs.push_back(d);
     m.d_adv = static_cast<int*>(d);
   }
-  OdeArgs a{};
-  a.nq = m.nq; a.q0 = h->qoff[m.sub]; a.n_stim = m.n_stim; a.flags = 0; a.v_index = -1;
-  a.model_slot = slot; a.NQtot = h->dev.NQtot; a.n_ions = 0;
-  for (int i = 0; i < 8; ++i) { a.stim_idx[i] = m.stim_idx[i]; a.stim_val[i] = m.stim_val[i]; }
-  a.dt = dt; a.rtol = rtol; a.atol = atol;
-  a.states = m.d_states; a.params = m.d_params; a.mask = m.d_mask; a.stats = m.d_stats; a.stamps = nullptr;
-  a.dpw = m.rtc_function ? 0 : dofs_per_wave(m.nq, m.n_states == 4 ? 4 : 1, m.n_stat_blocks - 1);
+  OdeArgs a = model_args(h, slot, t0, dt, rtol, atol, nullptr);
   OdeAdvArgs v{};
   v.n_rec = history ? n_rec : 0;
   v.every = every;
@@ -214,7 +236,7 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
     v.s0 = s; v.n_steps = c; a.t0 = t;
     const bool probe = s == 0 && forced <= 0;
     if (probe && hipEventRecord(e0, h->cur) != hipSuccess) rc = KNPEMI_EHIP;
-    if (rc == KNPEMI_OK) rc = launch_advance(h, m, a, v, cf);
+    if (rc == KNPEMI_OK) rc = launch_sweep(h, m, a, &v, cf);
     if (rc == KNPEMI_OK && probe) {
       float ms = 0.0f;
       if (hipEventRecord(e1, h->cur) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
@@ -242,27 +264,24 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   size_t n_failed = 0;
   for (size_t q = 0; q < nq; ++q) n_failed += flags[nq + q] >= 0;
   if (n_failed) {
-    if (m.method != KNPEMI_ODE_LSODA)
-      kn_set_error("the fixed-step integrator left a non-finite state on " + std::to_string(n_failed) + " membrane dof(s)");
-    else
-      kn_set_error("LSODA failed on " + std::to_string(n_failed) + " membrane dof(s) (odeSolver.py:121 `assert success`)");
+    kn_set_error(kn_ode_failure(lsoda, std::to_string(n_failed) + " membrane dof(s)"));
     return KNPEMI_EODE;
   }
   return KNPEMI_OK;
 }
 
-// The same sweep over a caller-described table (the DG variant, kernels_dg.hip: membrane nodes of the broken space).
+// The same LSODA sweep over a caller-described table (the DG variant, kernels_dg.hip: membrane nodes of the broken space).
 int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef) {
-  return launch_builtin(st, model_id, dv, a, static_cast<const LsodaCoef*>(coef), 0);
+  return launch_lsoda_step(st, model_id, dv, a, static_cast<const LsodaCoef*>(coef), 0);
 }
 
-int kn_lsoda_coef_upload(void** out) {
-  LsodaCoef c;
-  lsoda_fill_coef(&c);
-  void* d = nullptr;
-  KN_HIP(hipMalloc(&d, sizeof(LsodaCoef)));
-  KN_HIP(hipMemcpy(d, &c, sizeof(LsodaCoef), hipMemcpyHostToDevice));
-  *out = d;
+int kn_ode_read_stats(hipStream_t st, unsigned long long* d_stats, int n_blocks, unsigned long long out[3]) {
+  std::vector<unsigned long long> part(3 * (size_t)n_blocks);
+  KN_HIP(hipMemcpyAsync(part.data(), d_stats, part.size() * sizeof(part[0]), hipMemcpyDeviceToHost, st));
+  KN_HIP(hipMemsetAsync(d_stats, 0, part.size() * sizeof(part[0]), st));
+  KN_HIP(hipStreamSynchronize(st));
+  out[0] = out[1] = out[2] = 0;
+  for (size_t i = 0; i < part.size(); ++i) out[i % 3] += part[i];
   return KNPEMI_OK;
 }
 

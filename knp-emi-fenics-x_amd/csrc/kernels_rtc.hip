@@ -8,14 +8,17 @@
 // (ode_kernel.h: the very code of the shipped models) and compiled for gfx950 when the model is bound; the result is
 // launched through the module API.  Parameters are an in/out row, exactly as for the cfunc: whatever the last
 // right-hand-side call stored there (the currents I_ch_*) is what the PDEs receive.
+//
+// This file compiles, caches and binds (kn_rtc_bind fills KnOdeModel::rtc_kernel[method][shape]) and has the one
+// module launch, kn_rtc_launch.  Which entry point runs, with which grid and parameters, is decided with every other
+// sweep in kernels_ode.hip (launch_sweep).
 #include <hip/hiprtc.h>
 
 #include <cstring>
 #include <map>
 #include <mutex>
 
-#include "knpemi_internal.h"
-#include "fixed_step.h"
+#include "ode_host.h"
 
 namespace {
 
@@ -160,95 +163,28 @@ int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, con
   }
   hipModule_t mod = nullptr;
   KN_HIP(hipModuleLoadData(&mod, code.data()));
-  hipFunction_t fn = nullptr, fn_adv = nullptr;
-  if (hipModuleGetFunction(&fn, mod, "ode_user_kernel") != hipSuccess ||
-      hipModuleGetFunction(&fn_adv, mod, "ode_user_advance_kernel") != hipSuccess) {
-    (void)hipModuleUnload(mod);
-    kn_set_error("hipModuleGetFunction(ode_user_kernel / ode_user_advance_kernel) failed");
-    return KNPEMI_EHIP;
-  }
-  const char* fixed_names[2][2] = {{"ode_user_fixed_euler_kernel", "ode_user_fixed_euler_advance_kernel"},
-                                   {"ode_user_fixed_rk4_kernel", "ode_user_fixed_rk4_advance_kernel"}};
-  for (int k = 0; k < 2; ++k)
+  // the entry points wrapper_source() generates, [method][step, advance]; a plug-in has no gate rates: no Rush-Larsen
+  const char* const names[4][2] = {{"ode_user_kernel", "ode_user_advance_kernel"},
+                                   {"ode_user_fixed_euler_kernel", "ode_user_fixed_euler_advance_kernel"},
+                                   {"ode_user_fixed_rk4_kernel", "ode_user_fixed_rk4_advance_kernel"},
+                                   {nullptr, nullptr}};
+  for (int k = 0; k < 4; ++k)
     for (int j = 0; j < 2; ++j) {
-      hipFunction_t f = nullptr;
-      if (hipModuleGetFunction(&f, mod, fixed_names[k][j]) != hipSuccess) {
+      m.rtc_kernel[k][j] = nullptr;
+      if (names[k][j] && hipModuleGetFunction(&m.rtc_kernel[k][j], mod, names[k][j]) != hipSuccess) {
         (void)hipModuleUnload(mod);
-        kn_set_error(std::string("hipModuleGetFunction(") + fixed_names[k][j] + ") failed");
+        kn_set_error(std::string("hipModuleGetFunction(") + names[k][j] + ") failed");
         return KNPEMI_EHIP;
       }
-      m.rtc_fixed[k][j] = f;
     }
   m.rtc_module = mod;
-  m.rtc_function = fn;
-  m.rtc_advance_function = fn_adv;
   m.rtc_lanes = lanes_for(n_states);
   h->rtc_modules.push_back(mod);
   return KNPEMI_OK;
 }
 
-int kn_rtc_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, size_t dev_bytes, const void* args,
-                  size_t args_bytes, const void* coef) {
-  // kernel parameters (OdeDev, OdeArgs, const LsodaCoef*) laid out as the compiler lays out the parameter list
-  struct Params { OdeDev D; OdeArgs a; const LsodaCoef* cf; } p;
-  if (dev_bytes != sizeof(OdeDev) || args_bytes != sizeof(OdeArgs)) { kn_set_error("rtc launch: argument size mismatch"); return KNPEMI_EINVAL; }
-  std::memcpy(&p.D, dev_view, sizeof(OdeDev));
-  std::memcpy(&p.a, args, sizeof(OdeArgs));
-  p.cf = static_cast<const LsodaCoef*>(coef);
-  size_t size = sizeof(p);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  const unsigned grid = (unsigned)(((size_t)p.a.nq * m.rtc_lanes + ODE_BLOCK - 1) / ODE_BLOCK);
-  KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_function), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur, nullptr, config));
-  return KNPEMI_OK;
-}
-
-int kn_rtc_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, size_t args_bytes, const void* adv,
-                          size_t adv_bytes, const void* coef) {
-  // kernel parameters (OdeArgs, OdeAdvArgs, const LsodaCoef*) laid out as the compiler lays out the parameter list
-  struct Params { OdeArgs a; OdeAdvArgs v; const LsodaCoef* cf; } p;
-  if (args_bytes != sizeof(OdeArgs) || adv_bytes != sizeof(OdeAdvArgs)) { kn_set_error("rtc launch: argument size mismatch"); return KNPEMI_EINVAL; }
-  std::memcpy(&p.a, args, sizeof(OdeArgs));
-  std::memcpy(&p.v, adv, sizeof(OdeAdvArgs));
-  p.cf = static_cast<const LsodaCoef*>(coef);
-  size_t size = sizeof(p);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  const unsigned grid = (unsigned)(((size_t)p.a.nq * m.rtc_lanes + ODE_BLOCK - 1) / ODE_BLOCK);
-  KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_advance_function), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur,
-                               nullptr, config));
-  return KNPEMI_OK;
-}
-
-// the fixed-step sweeps of a plug-in: one thread per dof, parameters (OdeDev, OdeArgs, int) / (OdeArgs, OdeAdvArgs, int)
-namespace {
-int fixed_index(const KnOdeModel& m) { return m.method == KNPEMI_ODE_EULER ? 0 : (m.method == KNPEMI_ODE_RK4 ? 1 : -1); }
-}  // namespace
-
-int kn_rtc_fixed_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, const void* args) {
-  const int k = fixed_index(m);
-  if (k < 0) { kn_set_error("a model bound from source runs lsoda, euler or rk4"); return KNPEMI_EINVAL; }
-  struct Params { OdeDev D; OdeArgs a; int n_sub; } p;
-  std::memcpy(&p.D, dev_view, sizeof(OdeDev));
-  std::memcpy(&p.a, args, sizeof(OdeArgs));
-  p.n_sub = m.n_substeps;
-  size_t size = sizeof(p);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  const unsigned grid = (unsigned)(((size_t)p.a.nq + ODE_BLOCK - 1) / ODE_BLOCK);
-  KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_fixed[k][0]), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur, nullptr,
-                               config));
-  return KNPEMI_OK;
-}
-
-int kn_rtc_fixed_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, const void* adv) {
-  const int k = fixed_index(m);
-  if (k < 0) { kn_set_error("a model bound from source runs lsoda, euler or rk4"); return KNPEMI_EINVAL; }
-  struct Params { OdeArgs a; OdeAdvArgs v; int n_sub; } p;
-  std::memcpy(&p.a, args, sizeof(OdeArgs));
-  std::memcpy(&p.v, adv, sizeof(OdeAdvArgs));
-  p.n_sub = m.n_substeps;
-  size_t size = sizeof(p);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  const unsigned grid = (unsigned)(((size_t)p.a.nq + ODE_BLOCK - 1) / ODE_BLOCK);
-  KN_HIP(hipModuleLaunchKernel(static_cast<hipFunction_t>(m.rtc_fixed[k][1]), grid, 1, 1, ODE_BLOCK, 1, 1, 0, h->cur, nullptr,
-                               config));
+int kn_rtc_launch(hipStream_t st, hipFunction_t fn, unsigned grid, void* params, size_t bytes) {
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, params, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
+  KN_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, ODE_BLOCK, 1, 1, 0, st, nullptr, config));
   return KNPEMI_OK;
 }

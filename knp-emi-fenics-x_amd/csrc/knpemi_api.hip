@@ -10,7 +10,7 @@
 #include <cstring>
 #include <numeric>
 
-#include "knpemi_internal.h"
+#include "ode_host.h"
 
 static thread_local std::string g_err;
 void kn_set_error(const std::string& msg) { g_err = msg; }
@@ -1516,6 +1516,20 @@ int ode_slot(knpemi_handle* h, int sub, int model, int need_bound) {
   }
   return slot;
 }
+
+// the tables of a newly bound model: states, parameters, statistics partials
+int ode_alloc_tables(knpemi_handle* h, KnOdeModel& m, int sub, int model_id, int n_states, int n_params) {
+  m.sub = sub; m.model_id = model_id; m.n_states = n_states; m.n_params = n_params;
+  m.nq = h->n_q[sub];
+  int rc;
+  if ((rc = dev_zeros(h, (size_t)n_states * m.nq, &m.d_states))) return rc;
+  if ((rc = dev_zeros(h, (size_t)n_params * m.nq, &m.d_params))) return rc;
+  // one slot per workgroup of the sweep (small sweeps run with fewer dofs per wave, up to one wave per SIMD: kernels_ode.hip)
+  m.n_stat_blocks = std::max((int)(((size_t)m.nq * n_states + 63) / 64), std::min(m.nq, 1024)) + 1;
+  if ((rc = dev_zeros(h, 3 * (size_t)m.n_stat_blocks, &m.d_stats))) return rc;
+  m.bound = 1;
+  return KNPEMI_OK;
+}
 }  // namespace
 
 extern "C" int knpemi_ode_bind(knpemi_handle* h, int sub, int model, int model_id, int n_states, int n_params) {
@@ -1528,16 +1542,7 @@ extern "C" int knpemi_ode_bind(knpemi_handle* h, int sub, int model, int model_i
   KN_HIP(hipSetDevice(h->device));
   KnOdeModel& m = h->ode[slot];
   if (m.bound) return fail(KNPEMI_EINVAL, "knpemi_ode_bind: model already bound");
-  m.sub = sub; m.model_id = model_id; m.n_states = n_states; m.n_params = n_params;
-  m.nq = h->n_q[sub];
-  int rc;
-  if ((rc = dev_zeros(h, (size_t)n_states * m.nq, &m.d_states))) return rc;
-  if ((rc = dev_zeros(h, (size_t)n_params * m.nq, &m.d_params))) return rc;
-  // one slot per workgroup of the sweep (small sweeps run with fewer dofs per wave, up to one wave per SIMD: kernels_ode.hip)
-  m.n_stat_blocks = std::max((int)(((size_t)m.nq * n_states + 63) / 64), std::min(m.nq, 1024)) + 1;
-  if ((rc = dev_zeros(h, 3 * (size_t)m.n_stat_blocks, &m.d_stats))) return rc;
-  m.bound = 1;
-  return KNPEMI_OK;
+  return ode_alloc_tables(h, m, sub, model_id, n_states, n_params);
 }
 
 extern "C" int knpemi_ode_bind_source(knpemi_handle* h, int sub, int model, int n_states, int n_params,
@@ -1551,19 +1556,7 @@ extern "C" int knpemi_ode_bind_source(knpemi_handle* h, int sub, int model, int 
   if (m.bound) return fail(KNPEMI_EINVAL, "knpemi_ode_bind_source: model already bound");
   int rc = kn_rtc_bind(h, m, n_states, n_params, rhs_source);
   if (rc) return rc;
-  m.sub = sub; m.model_id = -1; m.n_states = n_states; m.n_params = n_params;
-  m.nq = h->n_q[sub];
-  if ((rc = dev_zeros(h, (size_t)n_states * m.nq, &m.d_states))) return rc;
-  if ((rc = dev_zeros(h, (size_t)n_params * m.nq, &m.d_params))) return rc;
-  m.n_stat_blocks = std::max((int)(((size_t)m.nq * n_states + 63) / 64), std::min(m.nq, 1024)) + 1;
-  if ((rc = dev_zeros(h, 3 * (size_t)m.n_stat_blocks, &m.d_stats))) return rc;
-  m.bound = 1;
-  return KNPEMI_OK;
-}
-
-static void transpose(const double* src, double* dst, int rows, int cols) {
-  for (int r = 0; r < rows; ++r)
-    for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
+  return ode_alloc_tables(h, m, sub, -1, n_states, n_params);
 }
 
 extern "C" int knpemi_ode_set_tables(knpemi_handle* h, int sub, int model, const double* states, const double* params) {
@@ -1575,13 +1568,13 @@ extern "C" int knpemi_ode_set_tables(knpemi_handle* h, int sub, int model, const
   std::vector<double> t;
   if (states) {
     t.resize((size_t)m.nq * m.n_states);
-    transpose(states, t.data(), m.nq, m.n_states);
+    kn_transpose(states, t.data(), m.nq, m.n_states);
     KN_HIP(hipMemcpyAsync(m.d_states, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     KN_HIP(hipStreamSynchronize(h->stream));
   }
   if (params) {
     t.resize((size_t)m.nq * m.n_params);
-    transpose(params, t.data(), m.nq, m.n_params);
+    kn_transpose(params, t.data(), m.nq, m.n_params);
     KN_HIP(hipMemcpyAsync(m.d_params, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     KN_HIP(hipStreamSynchronize(h->stream));
   }
@@ -1599,13 +1592,13 @@ extern "C" int knpemi_ode_get_tables(knpemi_handle* h, int sub, int model, doubl
     t.resize((size_t)m.nq * m.n_states);
     KN_HIP(hipMemcpyAsync(t.data(), m.d_states, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     KN_HIP(hipStreamSynchronize(h->stream));
-    transpose(t.data(), states, m.n_states, m.nq);
+    kn_transpose(t.data(), states, m.n_states, m.nq);
   }
   if (params) {
     t.resize((size_t)m.nq * m.n_params);
     KN_HIP(hipMemcpyAsync(t.data(), m.d_params, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     KN_HIP(hipStreamSynchronize(h->stream));
-    transpose(t.data(), params, m.n_params, m.nq);
+    kn_transpose(t.data(), params, m.n_params, m.nq);
   }
   return KNPEMI_OK;
 }
@@ -1654,21 +1647,19 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
     return fail(KNPEMI_EINVAL, "knpemi_ode_step: a handle of knpemi_ode_create has no PDE fields to read");
   kn_inputs_changed(h);      // phi_M and the channel currents
   KN_HIP(hipSetDevice(h->device));
-  if (flags & (KNPEMI_ODE_ON_AUX_STREAM | KNPEMI_ODE_ON_AUX2_STREAM)) {
-    const bool second = (flags & KNPEMI_ODE_ON_AUX2_STREAM) != 0;
-    hipStream_t side = second ? h->aux2 : h->aux;
+  // beside the main stream's work on an auxiliary stream when asked for: fork, sweep, record the join event
+  const bool second = (flags & KNPEMI_ODE_ON_AUX2_STREAM) != 0;
+  hipStream_t side = second ? h->aux2 : ((flags & KNPEMI_ODE_ON_AUX_STREAM) ? h->aux : nullptr);
+  if (side) {
     KN_HIP(hipEventRecord(h->ev_fork, h->stream));
     KN_HIP(hipStreamWaitEvent(side, h->ev_fork, 0));
     h->cur = side;
-    int rc = fixed ? kn_launch_ode_fixed_step(h, slot, t0, dt, flags, ion_param, v_index)
-                   : kn_launch_ode_step(h, slot, t0, dt, rtol, atol, flags, ion_param, v_index);
-    h->cur = h->stream;
-    if (rc) return rc;
-    KN_HIP(hipEventRecord(second ? h->ev_join2 : h->ev_join, side));
-    return KNPEMI_OK;
   }
-  if (fixed) return kn_launch_ode_fixed_step(h, slot, t0, dt, flags, ion_param, v_index);
-  return kn_launch_ode_step(h, slot, t0, dt, rtol, atol, flags, ion_param, v_index);
+  const int rc = kn_ode_step(h, slot, t0, dt, rtol, atol, OdePde{flags, v_index, h->K, ion_param});
+  h->cur = h->stream;
+  if (rc) return rc;
+  if (side) KN_HIP(hipEventRecord(second ? h->ev_join2 : h->ev_join, side));
+  return KNPEMI_OK;
 }
 
 extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t0, double dt, int n_steps, double rtol,
@@ -1707,7 +1698,7 @@ extern "C" int knpemi_ode_set_method(knpemi_handle* h, int sub, int model, int m
     return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: unknown method");
   if (method != KNPEMI_ODE_LSODA && (n_substeps < 1 || n_substeps > 10000))
     return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: n_substeps must be in 1..10000");
-  if (method == KNPEMI_ODE_RUSH_LARSEN && m.rtc_function)
+  if (m.rtc_module && !m.rtc_kernel[method][0])   // (today: Rush-Larsen)
     return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: rush_larsen needs the gate rates of a model, and a model bound from "
                                "source brings a right-hand side only (use euler or rk4)");
   m.method = method;
@@ -1735,19 +1726,14 @@ extern "C" int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n
   unsigned long long st[3] = {0, 0, 0};
   KN_HIP(hipSetDevice(h->device));
   KnOdeModel& mo = h->ode[slot];
-  std::vector<unsigned long long> part(3 * (size_t)mo.n_stat_blocks);
   KN_HIP(hipStreamSynchronize(h->aux));   // the sweep may run on an auxiliary stream
   KN_HIP(hipStreamSynchronize(h->aux2));
-  KN_HIP(hipMemcpyAsync(part.data(), mo.d_stats, part.size() * sizeof(part[0]), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipMemsetAsync(mo.d_stats, 0, part.size() * sizeof(part[0]), h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  for (size_t i = 0; i < part.size(); ++i) st[i % 3] += part[i];
+  const int rc = kn_ode_read_stats(h->stream, mo.d_stats, mo.n_stat_blocks, st);
+  if (rc) return rc;
   if (n_rhs) *n_rhs = (int64_t)st[0];
   if (n_steps) *n_steps = (int64_t)st[1];
   if (n_failed) *n_failed = (int32_t)st[2];
-  if (st[2] && mo.method != KNPEMI_ODE_LSODA)
-    return fail(KNPEMI_EODE, "the fixed-step integrator left a non-finite state on at least one membrane dof");
-  if (st[2]) return fail(KNPEMI_EODE, "LSODA failed on at least one membrane dof (odeSolver.py:121 `assert success`)");
+  if (st[2]) return fail(KNPEMI_EODE, kn_ode_failure(mo.method == KNPEMI_ODE_LSODA, "at least one membrane dof"));
   return KNPEMI_OK;
 }
 

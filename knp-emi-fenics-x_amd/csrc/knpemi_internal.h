@@ -125,15 +125,14 @@ struct KnOdeModel {
   int n_stat_blocks = 0;
   unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (KNPEMI_ODE_STAMPS)
   // model compiled at bind time from the plug-in's HIP source (kernels_rtc.hip); NULL for the shipped models
-  void* rtc_module = nullptr;
-  void* rtc_function = nullptr;
-  void* rtc_advance_function = nullptr;   // its multi-step entry (ode_user_advance_kernel)
+  hipModule_t rtc_module = nullptr;
+  // its kernels, [KNPEMI_ODE_* method][0: one step, 1: n steps]; NULL: the plug-in cannot run that method (Rush-Larsen)
+  hipFunction_t rtc_kernel[4][2] = {};
   int rtc_lanes = 1;
   int* d_adv = nullptr;                   // [3][nq] knpemi_ode_advance: still-step counters, steps_taken, failed_step
   int adv_chunk = 0;                      // steps per launch the last knpemi_ode_advance chose
   // integrator of the slot (knpemi_ode_set_method): KNPEMI_ODE_LSODA or a fixed-step scheme with n_substeps sub-steps
   int method = 0, n_substeps = 0;
-  void* rtc_fixed[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // plug-in: [euler, rk4][step, advance] kernels
 };
 
 // blocks of the dense coarsest-level inverse, passed to the kernels by value: block b covers the unknowns start[b] ..
@@ -429,10 +428,6 @@ void kn_set_error(const std::string& msg);
     }                                                                                    \
   } while (0)
 
-struct OdeDev;
-struct OdeArgs;
-int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef);   // kernels_ode.hip
-int kn_lsoda_coef_upload(void** out);
 void kn_comm_destroy(knpemi_handle* h);   // comm_rccl.hip
 int kn_comm_create(int device, int rank, int world, const char* id_bytes, size_t len, void** out);
 void kn_comm_free(void* comm);
@@ -449,25 +444,11 @@ int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags);
 int kn_launch_knp_membrane(knpemi_handle* h, int flags);
 int kn_launch_emi_writeback_membrane(knpemi_handle* h, const double* x, const double* part, int np, double inv_n, double* mean_out);
 int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_row, double* d_out);
-int kn_launch_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol,
-                       int flags, const int32_t* ion_param, int v_index);
 int kn_launch_update_pde(knpemi_handle* h);
 int kn_launch_observe(knpemi_handle* h);
 int kn_launch_observe_combine(knpemi_handle* h);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
-int kn_rtc_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, size_t dev_bytes, const void* args,
-                  size_t args_bytes, const void* coef);
-int kn_rtc_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, size_t args_bytes, const void* adv,
-                          size_t adv_bytes, const void* coef);
-// fixed-step integrators (kernels_ode_fixed.hip); `args` / `adv` are the OdeArgs / OdeAdvArgs of the launch
-int kn_launch_ode_fixed_step(knpemi_handle* h, int slot, double t0, double dt, int flags, const int32_t* ion_param,
-                             int v_index);
-int kn_launch_ode_fixed_advance(knpemi_handle* h, const KnOdeModel& m, const void* args, const void* adv);
-int kn_rtc_fixed_launch(knpemi_handle* h, const KnOdeModel& m, const void* dev_view, const void* args);
-int kn_rtc_fixed_advance_launch(knpemi_handle* h, const KnOdeModel& m, const void* args, const void* adv);
-int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
-                   const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
-                   int32_t* steps_taken, int32_t* failed_step);
+// (the membrane ODE sweeps: ode_host.h)
 int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);
 int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);
 int kn_extrapolate_guess(knpemi_handle* h, int which);

@@ -1,0 +1,86 @@
+// Host side of the membrane ODE sweeps: what the translation units that launch or own a sweep share.  Host only: it
+// adds no device code to a file that includes it (the kernels are in ode_kernel.h and fixed_step.h).
+//
+// Where a launch is decided: kernels_ode.hip, launch_sweep -- plug-in or shipped model, LSODA or a
+// fixed-step method, one step or n steps.  Its arguments come from kn_ode_args, the one place that fills an OdeArgs.
+#pragma once
+
+#include "knpemi_internal.h"
+#include "membrane_models.h"
+
+// ---- launch arguments ---------------------------------------------------------------------------------------------
+// the tables of a sweep, as their owner describes them (knpemi_handle: a KnOdeModel; knpemi_dg: its membrane nodes)
+struct OdeTables {
+  int nq, q0, NQtot, model_slot;
+  double* states;
+  double* params;
+  const unsigned char* mask;   // stimulus mask or NULL
+  unsigned long long* stats;
+};
+// what a sweep exchanges with the PDE fields; a standalone advance has none of it
+struct OdePde {
+  int flags, v_index, n_ions;
+  const int32_t* ion_param;    // [3 * n_ions]
+};
+// every field of an OdeArgs is set here or value-initialised; `pde` NULL: a standalone advance
+OdeArgs kn_ode_args(const OdeTables& T, double t0, double dt, double rtol, double atol, const OdePde* pde);
+OdeDev kn_ode_dev(const knpemi_handle* h);
+
+// ---- shipped models -----------------------------------------------------------------------------------------------
+template <class M, int L>
+struct OdeModelTag {
+  using Model = M;
+  static constexpr int LANES = L;   // lanes per dof of the LSODA sweep (lsoda_core.h)
+};
+// calls f(OdeModelTag<Model, LANES>{}) for the shipped model `model_id`
+template <class F>
+void with_model(int model_id, F&& f) {
+  switch (model_id) {
+    case KNPEMI_MODEL_HH_SI: f(OdeModelTag<ModelHHSI, 4>{}); break;
+    case KNPEMI_MODEL_HH_MV: f(OdeModelTag<ModelHHMV, 4>{}); break;
+    default: f(OdeModelTag<ModelGlial, 1>{}); break;
+  }
+}
+// after a kernel launch: KNPEMI_OK, or KNPEMI_EHIP with "<kernel>: <HIP's message>"
+inline int kn_launch_check(const char* kernel) {
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return KNPEMI_OK;
+  kn_set_error(std::string(kernel) + ": " + hipGetErrorString(e));
+  return KNPEMI_EHIP;
+}
+
+// ---- the sweeps ---------------------------------------------------------------------------------------------------
+// kernels_ode.hip: one entry per kernel shape, integrator and model source chosen inside
+int kn_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde& pde);
+int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
+                   const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
+                   int32_t* steps_taken, int32_t* failed_step);
+// the LSODA step of a shipped model over a caller-described table (the DG variant: membrane nodes of the broken space)
+int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef);
+int kn_lsoda_coef_upload(void** out);   // LsodaCoef tables on the device; the caller owns *out
+// kernels_ode_fixed.hip: the fixed-step kernels of the shipped models (m.method, m.n_substeps)
+int kn_launch_ode_fixed_step(hipStream_t st, const KnOdeModel& m, const OdeDev& dv, const OdeArgs& a);
+int kn_launch_ode_fixed_advance(hipStream_t st, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs& v);
+
+// kernels_rtc.hip: a kernel of a plug-in, ODE_BLOCK threads per workgroup; `params` is the kernel's parameter list
+// laid out as the compiler lays it out
+int kn_rtc_launch(hipStream_t st, hipFunction_t fn, unsigned grid, void* params, size_t bytes);
+template <class A, class B, class C>
+int kn_rtc_launch(hipStream_t st, hipFunction_t fn, unsigned grid, const A& a, const B& b, const C& c) {
+  struct { A a; B b; C c; } p{a, b, c};
+  return kn_rtc_launch(st, fn, grid, &p, sizeof(p));
+}
+
+// ---- upkeep shared by the two owners of a sweep ---------------------------------------------------------------------
+// reads, resets and sums the per-workgroup partials: st = {rhs evaluations, steps, failures}
+int kn_ode_read_stats(hipStream_t st, unsigned long long* d_stats, int n_blocks, unsigned long long out[3]);
+// the message of a failed sweep; `where` e.g. "3 membrane dof(s)"
+inline std::string kn_ode_failure(bool lsoda, const std::string& where) {
+  return lsoda ? "LSODA failed on " + where + " (odeSolver.py:121 `assert success`)"
+               : "the fixed-step integrator left a non-finite state on " + where;
+}
+// host tables are row-major [dof][column], device tables [column][dof]: dst[c][r] = src[r][c]
+inline void kn_transpose(const double* src, double* dst, int rows, int cols) {
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
+}
