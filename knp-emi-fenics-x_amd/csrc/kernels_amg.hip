@@ -203,33 +203,20 @@ void block_apply(hipStream_t st, const KnAmg& G, int n, const double* v, const d
   else hipLaunchKernelGGL(amg_block_apply_kernel<8>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
 }
 
-template <class T>
-int upload(KnAmg& G, const std::vector<T>& src, T** dst, hipStream_t st) {
-  void* p = nullptr;
-  const size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-  KN_HIP(hipMalloc(&p, bytes));
-  G.allocs.push_back(p);
-  // blocking copy: the sources are temporaries of the set-up (which is host-bound anyway)
-  (void)st;
-  if (!src.empty()) KN_HIP(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  *dst = static_cast<T*>(p);
-  return KNPEMI_OK;
-}
-
-int upload_csr(KnAmg& G, const HostCsr& A, KnAmgCsr& D, hipStream_t st) {
+// (blocking copies: the sources are temporaries of the set-up, which is host-bound anyway)
+int upload_csr(KnAmg& G, const HostCsr& A, KnAmgCsr& D) {
   int rc;
   D.n = A.n; D.m = A.m; D.nnz = (int)A.ci.size();
-  if ((rc = upload(G, A.rp, &D.rp, st))) return rc;
-  if ((rc = upload(G, A.ci, &D.ci, st))) return rc;
-  return upload(G, A.v, &D.v, st);
+  if ((rc = kn_upload(G.allocs, A.rp, &D.rp))) return rc;
+  if ((rc = kn_upload(G.allocs, A.ci, &D.ci))) return rc;
+  return kn_upload(G.allocs, A.v, &D.v);
 }
 
 }  // namespace
 
 void kn_amg_free(KnAmg& G) {
   // (a background rebuild of this hierarchy, if any, keeps running: it owns its own KnAmg; kn_amg_async_join ends it)
-  for (void* p : G.allocs) (void)hipFree(p);
-  G.allocs.clear();
+  kn_free_all(G.allocs);
   G.zero_sc = nullptr; G.sub_fused_ok = false; G.cycle_ok = false;
   G.lev.clear();
   G.built = false;
@@ -242,14 +229,11 @@ static int amg_fetch(knpemi_handle* h, int n, const int* d_rowptr, const int* d_
   hipStream_t st = h->stream;
   A.n = A.m = n;
   A.rp.resize(n + 1);
-  KN_HIP(hipMemcpyAsync(A.rp.data(), d_rowptr, (n + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
-  KN_HIP(hipStreamSynchronize(st));
+  if (int rc = kn_to_host(st, A.rp.data(), d_rowptr, (size_t)n + 1)) return rc;
   const int nnz = A.rp[n];
   A.ci.resize(nnz); A.v.resize(nnz);
   KN_HIP(hipMemcpyAsync(A.ci.data(), d_colind, nnz * sizeof(int), hipMemcpyDeviceToHost, st));
-  KN_HIP(hipMemcpyAsync(A.v.data(), d_vals, nnz * sizeof(double), hipMemcpyDeviceToHost, st));
-  KN_HIP(hipStreamSynchronize(st));
-  return KNPEMI_OK;
+  return kn_to_host(st, A.v.data(), d_vals, (size_t)nnz);
 }
 
 static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
@@ -407,18 +391,15 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
       const double rb = estimate_rho_block(cur, G.cfg.block);
       if (!(rb > 0)) { kn_set_error("AMG set-up: singular diagonal block"); return KNPEMI_ESOLVE; }
       G.omega_block = 4.0 / (3.0 * rb);
-      void* pb = nullptr;
-      KN_HIP(hipMalloc(&pb, (size_t)cur.n * G.cfg.block * sizeof(double)));
-      G.allocs.push_back(pb);
-      G.binv = static_cast<double*>(pb);
+      if ((rc = kn_alloc(G.allocs, (size_t)cur.n * G.cfg.block, &G.binv))) return rc;
     }
     if (l == 0) {   // the finest operator is the caller's CSR of the current step
       L.A.n = L.A.m = cur.n; L.A.nnz = (int)cur.ci.size();
       L.A.rp = const_cast<int*>(d_rowptr); L.A.ci = const_cast<int*>(d_colind); L.A.v = const_cast<double*>(d_vals);
-    } else if ((rc = upload_csr(G, cur, L.A, st))) return rc;
+    } else if ((rc = upload_csr(G, cur, L.A))) return rc;
     std::vector<double> dinv(cur.n);
     for (int i = 0; i < cur.n; ++i) dinv[i] = d[i] != 0.0 ? 1.0 / d[i] : 1.0;
-    if ((rc = upload(G, dinv, &L.dinv, st))) return rc;
+    if ((rc = kn_upload(G.allocs, dinv, &L.dinv))) return rc;
     std::vector<int> agg;
     int na = 0;
     if (l == 0 && G.cfg.first_na > 0 && (int)G.cfg.first_agg.size() == cur.n) {
@@ -441,7 +422,7 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
       if (cur.n <= std::max(1024, n_dense)) {
         DenseInvBlocks inv;
         if (!dense_inverse_blocks(cur, singular, inv)) { kn_set_error("AMG set-up: singular coarsest operator"); return KNPEMI_ESOLVE; }
-        if ((rc = upload(G, inv.v, &L.dense_inv, st))) return rc;
+        if ((rc = kn_upload(G.allocs, inv.v, &L.dense_inv))) return rc;
         L.dense_blk.nb = inv.nb;
         for (int b = 0; b < inv.nb; ++b) { L.dense_blk.start[b] = inv.start[b]; L.dense_blk.size[b] = inv.size[b]; L.dense_blk.off[b] = inv.off[b]; }
       }
@@ -460,8 +441,8 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
     L.nc = na;
     L.p_row = std::max(1, (int)(P.ci.size() / (size_t)P.n));
     L.r_row = std::max(1, (int)(R.ci.size() / (size_t)R.n));
-    if ((rc = upload_csr(G, P, L.P, st))) return rc;
-    if ((rc = upload_csr(G, R, L.R, st))) return rc;
+    if ((rc = upload_csr(G, P, L.P))) return rc;
+    if ((rc = upload_csr(G, R, L.R))) return rc;
     if (fused || (G.cfg.sub_fused && l >= 1)) {
       // V(1,1) from a zero guess is  x = w D^-1 (r + t) + Pm e_c,  t = (I - w A D^-1) r,  e_c = cycle(Rm r)  with the
       // smoother folded into the transfer operators: restriction and residual, prolongation and post-smoothing become
@@ -476,9 +457,9 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
           }
       });
       const HostCsr Pm = spgemm(Sl, P), Rm = spgemm(R, Sr);
-      if ((rc = upload_csr(G, Pm, L.Pm, st))) return rc;
-      if ((rc = upload_csr(G, Rm, L.Rm, st))) return rc;
-      if (l == 0 && (rc = upload(G, cur.v, &L.frozen_v, st))) return rc;
+      if ((rc = upload_csr(G, Pm, L.Pm))) return rc;
+      if ((rc = upload_csr(G, Rm, L.Rm))) return rc;
+      if (l == 0 && (rc = kn_upload(G.allocs, cur.v, &L.frozen_v))) return rc;
     }
     G.lev.push_back(L);
     work += 3 * (size_t)cur.n;
@@ -487,10 +468,8 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
     cur = spgemm(R, spgemm(cur, P));
   }
   // per-level work vectors x, r, t (level 0 uses the caller's r and z for r and x)
-  void* p = nullptr;
-  KN_HIP(hipMalloc(&p, std::max<size_t>(work, 1) * sizeof(double)));
-  G.allocs.push_back(p);
-  double* w = static_cast<double*>(p);
+  double* w = nullptr;
+  if ((rc = kn_alloc(G.allocs, work, &w))) return rc;
   for (auto& L : G.lev) { L.x = w; L.r = w + L.n; L.t = w + 2 * (size_t)L.n; w += 3 * (size_t)L.n; }
   if (!background) KN_HIP(hipStreamSynchronize(st));      // (every upload of the build is a blocking copy)
   G.built = true;
@@ -502,11 +481,8 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
   G.cycle_ok = fused && !fused_loops && G.lev.size() >= 2 && G.lev.back().dense_inv != nullptr;
   G.sub_fused_ok = G.cfg.sub_fused && G.cfg.block > 0 && G.lev.size() >= 3 && G.lev.back().dense_inv != nullptr;
   if (G.sub_fused_ok || G.cycle_ok) {
-    void* z = nullptr;
-    KN_HIP(hipMalloc(&z, 32 * sizeof(double)));
-    G.allocs.push_back(z);
-    KN_HIP(hipMemset(z, 0, 32 * sizeof(double)));
-    G.zero_sc = static_cast<double*>(z);
+    if ((rc = kn_alloc(G.allocs, 32, &G.zero_sc))) return rc;
+    KN_HIP(hipMemset(G.zero_sc, 0, 32 * sizeof(double)));
   }
   return KNPEMI_OK;
 }
@@ -589,7 +565,5 @@ int kn_amg_refresh(knpemi_handle* h, KnAmg& G, const double* vals) {
   else if (G.cfg.block == 4) hipLaunchKernelGGL(amg_block_inv_kernel<4>, g, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
   else if (G.cfg.block == 8) hipLaunchKernelGGL(amg_block_inv_kernel<8>, g8, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
   else { kn_set_error("AMG: smoother blocks of 3, 4 or 8 unknowns only"); return KNPEMI_EINVAL; }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("amg_block_inv_kernel: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  return KNPEMI_OK;
+  return kn_launch_check("amg_block_inv_kernel");
 }

@@ -1852,15 +1852,6 @@ __global__ __launch_bounds__(256) void emi_membrane_rhs_kernel(KnDev D, const Kn
   if (live && sub == 0) D.b_emi[g] = D.b_emi[g] + gam;
 }
 
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    kn_set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return KNPEMI_EHIP;
-  }
-  return KNPEMI_OK;
-}
-
 template <class K>
 int set_lds_limit(K kernel, size_t bytes) {
   if (bytes > 64 * 1024) {
@@ -1888,7 +1879,7 @@ static int launch_emi_v2(knpemi_handle* h, int want_p, int split) {
 #define KN_CASE2(L, U)                                                                              \
     if ((rc = set_lds_limit(emi_rows_v2<GDIM, L, U>, lds))) return rc;                              \
     {                                                                                               \
-      KnProfScope prof(h, KNPEMI_K_EMI_ROWS);                                                       \
+      KnProfScope prof(h->prof, KNPEMI_K_EMI_ROWS, h->cur);                                         \
       hipLaunchKernelGGL((emi_rows_v2<GDIM, L, U>), grid, block, lds, h->cur, D, h->d_consts, acc_n, \
                          rec_n, want_p, split);                                                     \
     }
@@ -1916,7 +1907,7 @@ static int launch_emi_v2(knpemi_handle* h, int want_p, int split) {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(row_stamp_acc), acc.data(), acc.size() * sizeof(unsigned long long));
   }
 #endif
-  return check_launch("emi_rows_v2");
+  return kn_launch_check("emi_rows_v2");
 }
 
 template <int GDIM>
@@ -1934,9 +1925,9 @@ static int launch_knp_v2(knpemi_handle* h, int split, int pre) {
   const int mem = pre ? 2 : (gam_n > 0 ? 1 : 0);
 #define KN_CASE2(L, S, M, U)                                                                        \
     if ((rc = set_lds_limit(knp_rows_v2<GDIM, L, S, M, U>, lds))) return rc;                        \
-    KnProfScope prof(h, KNPEMI_K_KNP_ROWS);                                                         \
+    KnProfScope prof(h->prof, KNPEMI_K_KNP_ROWS, h->cur);                                           \
     hipLaunchKernelGGL((knp_rows_v2<GDIM, L, S, M, U>), grid, block, lds, h->cur, D, h->d_consts, acc_n, rec_n, gam_n, split); \
-    return check_launch("knp_rows_v2");
+    return kn_launch_check("knp_rows_v2");
 #define KN_CASE(L, S, M)                                                                            \
   if (h->lpr == L && KS == S && mem == M) {                                                         \
     if constexpr (GDIM == 3) { if (ut) { KN_CASE2(L, S, M, true) } else { KN_CASE2(L, S, M, false) } } \
@@ -1964,7 +1955,7 @@ static int launch_emi_hex_v2(knpemi_handle* h, int want_p, int split) {
 #define KN_CASE2(L, GEO)                                                                            \
     if ((rc = set_lds_limit(emi_rows_hex_v2<L, GEO>, lds))) return rc;                              \
     {                                                                                               \
-      KnProfScope prof(h, KNPEMI_K_EMI_ROWS);                                                       \
+      KnProfScope prof(h->prof, KNPEMI_K_EMI_ROWS, h->cur);                                         \
       hipLaunchKernelGGL((emi_rows_hex_v2<L, GEO>), grid, block, lds, h->cur, D, h->d_consts, acc_n, \
                          rec_n, want_p, split, h->hex_geo);                                         \
     }
@@ -1975,7 +1966,7 @@ static int launch_emi_hex_v2(knpemi_handle* h, int want_p, int split) {
   switch (h->lpr) { KN_CASE(1) KN_CASE(2) KN_CASE(4) KN_CASE(8) default: kn_set_error("bad lanes-per-row"); return KNPEMI_EINVAL; }
 #undef KN_CASE
 #undef KN_CASE2
-  return check_launch("emi_rows_hex_v2");
+  return kn_launch_check("emi_rows_hex_v2");
 }
 
 static int launch_knp_hex_v2(knpemi_handle* h, int split, int pre) {
@@ -1993,9 +1984,9 @@ static int launch_knp_hex_v2(knpemi_handle* h, int split, int pre) {
 #define KN_CASE(L, GEO, S, M)                                                                       \
   if (h->lpr == L && geo == GEO && KS == S && mem == M) {                                           \
     if ((rc = set_lds_limit(knp_rows_hex_v2<L, GEO, S, M>, lds))) return rc;                        \
-    KnProfScope prof(h, KNPEMI_K_KNP_ROWS);                                                         \
+    KnProfScope prof(h->prof, KNPEMI_K_KNP_ROWS, h->cur);                                           \
     hipLaunchKernelGGL((knp_rows_hex_v2<L, GEO, S, M>), grid, block, lds, h->cur, D, h->d_consts, acc_n, rec_n, gam_n, split, h->hex_geo); \
-    return check_launch("knp_rows_hex_v2");                                                         \
+    return kn_launch_check("knp_rows_hex_v2");                                                         \
   }
 #define KN_GEO(L, S, M) KN_CASE(L, 2, S, M) KN_CASE(L, 1, S, M) KN_CASE(L, 0, S, M)
   KN_GEO(4, 2, 0) KN_GEO(2, 2, 0) KN_GEO(8, 2, 0) KN_GEO(1, 2, 0) KN_GEO(4, 1, 0) KN_GEO(4, 3, 0)
@@ -2033,7 +2024,7 @@ int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_
   if (h->NF == 2) hipLaunchKernelGGL(membrane_mass_kernel<2>, grid, block, 0, h->stream, D, n_entries, v_cells, d_entry_row, d_out);
   else if (h->NF == 3) hipLaunchKernelGGL(membrane_mass_kernel<3>, grid, block, 0, h->stream, D, n_entries, v_cells, d_entry_row, d_out);
   else hipLaunchKernelGGL(membrane_mass_kernel<4>, grid, block, 0, h->stream, D, n_entries, v_cells, d_entry_row, d_out);
-  return check_launch("membrane_mass_kernel");
+  return kn_launch_check("membrane_mass_kernel");
 }
 
 int kn_launch_knp_membrane(knpemi_handle* h, int flags) {
@@ -2043,11 +2034,11 @@ int kn_launch_knp_membrane(knpemi_handle* h, int flags) {
   const int NF = h->NF;
   const size_t lds = (size_t)D.nq_gamma * (1 + NF + (NF == 4 ? 2 * NF : 0)) * sizeof(double);
   dim3 grid((2 * (size_t)D.nftot * KN_MEM_LQ + 255) / 256), block(256);
-  KnProfScope prof(h, KNPEMI_K_KNP_MEMBRANE);
+  KnProfScope prof(h->prof, KNPEMI_K_KNP_MEMBRANE, h->cur);
   if (NF == 2) hipLaunchKernelGGL((knp_membrane_kernel<2>), grid, block, lds, h->cur, D, h->d_consts, split);
   else if (NF == 3) hipLaunchKernelGGL((knp_membrane_kernel<3>), grid, block, lds, h->cur, D, h->d_consts, split);
   else hipLaunchKernelGGL((knp_membrane_kernel<4>), grid, block, lds, h->cur, D, h->d_consts, split);
-  return check_launch("knp_membrane_kernel");
+  return kn_launch_check("knp_membrane_kernel");
 }
 
 // phi <- x - mean and the membrane-facet integrals of b_knp for that potential, one launch (see the kernel).  np = 0: x is
@@ -2062,11 +2053,11 @@ int kn_launch_emi_writeback_membrane(knpemi_handle* h, const double* x, const do
   const int nbm = (int)((2 * (size_t)D.nftot * KN_MEM_LQ + 255) / 256);
   const int nbv = std::max(1, std::min(1024, (n + 255) / 256));
   dim3 grid(nbm + nbv), block(256);
-  KnProfScope prof(h, KNPEMI_K_KNP_MEMBRANE);
+  KnProfScope prof(h->prof, KNPEMI_K_KNP_MEMBRANE, h->cur);
   if (NF == 2) hipLaunchKernelGGL((emi_writeback_membrane_kernel<2>), grid, block, lds, h->cur, D, h->d_consts, split, nbm, x, n, part, np, inv_n, mean_out);
   else if (NF == 3) hipLaunchKernelGGL((emi_writeback_membrane_kernel<3>), grid, block, lds, h->cur, D, h->d_consts, split, nbm, x, n, part, np, inv_n, mean_out);
   else hipLaunchKernelGGL((emi_writeback_membrane_kernel<4>), grid, block, lds, h->cur, D, h->d_consts, split, nbm, x, n, part, np, inv_n, mean_out);
-  return check_launch("emi_writeback_membrane_kernel");
+  return kn_launch_check("emi_writeback_membrane_kernel");
 }
 
 int kn_launch_knp_membrane_pre(knpemi_handle* h, int flags) {
@@ -2076,11 +2067,11 @@ int kn_launch_knp_membrane_pre(knpemi_handle* h, int flags) {
   const int NF = h->NF;
   const size_t lds = (size_t)D.nq_gamma * (1 + NF + (NF == 4 ? 2 * NF : 0)) * sizeof(double);
   dim3 grid((2 * D.nftot + 255) / 256), block(256);
-  KnProfScope prof(h, KNPEMI_K_KNP_MEMBRANE);
+  KnProfScope prof(h->prof, KNPEMI_K_KNP_MEMBRANE, h->cur);
   if (NF == 2) hipLaunchKernelGGL((knp_membrane_pre_kernel<2>), grid, block, lds, h->cur, D, h->d_consts, split);
   else if (NF == 3) hipLaunchKernelGGL((knp_membrane_pre_kernel<3>), grid, block, lds, h->cur, D, h->d_consts, split);
   else hipLaunchKernelGGL((knp_membrane_pre_kernel<4>), grid, block, lds, h->cur, D, h->d_consts, split);
-  return check_launch("knp_membrane_pre_kernel");
+  return kn_launch_check("knp_membrane_pre_kernel");
 }
 
 int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags) {
@@ -2089,7 +2080,7 @@ int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags) {
   const int split = (flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
   const int lpr = h->lpr;      // the same lane groups as the row kernels, so that both forms produce the same bits
   dim3 grid(((size_t)D.M * lpr + 255) / 256), block(256);
-  KnProfScope prof(h, KNPEMI_K_EMI_MEMBRANE);
+  KnProfScope prof(h->prof, KNPEMI_K_EMI_MEMBRANE, h->cur);
 #define KN_ROBIN(NFV, L) hipLaunchKernelGGL((emi_membrane_rhs_kernel<NFV, L>), grid, block, 0, h->stream, D, h->d_consts, split)
 #define KN_ROBIN_L(NFV) \
   switch (lpr) { case 1: KN_ROBIN(NFV, 1); break; case 2: KN_ROBIN(NFV, 2); break; case 8: KN_ROBIN(NFV, 8); break; \
@@ -2097,50 +2088,50 @@ int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags) {
   if (h->NF == 2) { KN_ROBIN_L(2) } else if (h->NF == 3) { KN_ROBIN_L(3) } else { KN_ROBIN_L(4) }
 #undef KN_ROBIN_L
 #undef KN_ROBIN
-  return check_launch("emi_membrane_rhs_kernel");
+  return kn_launch_check("emi_membrane_rhs_kernel");
 }
 
 int kn_launch_update_pde(knpemi_handle* h) {
   const KnDev& D = h->dev;
   const int n = std::max(D.Ntot, D.NQtot);
   if (n == 0) return KNPEMI_OK;
-  KnProfScope prof(h, KNPEMI_K_UPDATE);
+  KnProfScope prof(h->prof, KNPEMI_K_UPDATE, h->cur);
   hipLaunchKernelGGL(update_pde_kernel, dim3((n + 255) / 256), dim3(256), 0, h->cur, D, h->d_consts);
-  return check_launch("update_pde_kernel");
+  return kn_launch_check("update_pde_kernel");
 }
 
 int kn_launch_knp_writeback_update(knpemi_handle* h, const double* x) {
   const KnDev& D = h->dev;
   const int n = std::max(D.Ntot, D.NQtot);
   if (n == 0) return KNPEMI_OK;
-  KnProfScope prof(h, KNPEMI_K_UPDATE);
+  KnProfScope prof(h->prof, KNPEMI_K_UPDATE, h->cur);
   hipLaunchKernelGGL(knp_writeback_update_kernel, dim3((n + 255) / 256), dim3(256), 0, h->cur, D, h->d_consts, x);
-  return check_launch("knp_writeback_update_kernel");
+  return kn_launch_check("knp_writeback_update_kernel");
 }
 
 int kn_launch_halo(knpemi_handle* h, int kind, int pack, const int32_t* idx, int n, double* buf) {
   if (n == 0) return KNPEMI_OK;
   hipLaunchKernelGGL(halo_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, kind, pack, idx, n,
                      h->moff[h->n_sub], buf);
-  return check_launch("halo_kernel");
+  return kn_launch_check("halo_kernel");
 }
 
 int kn_launch_field_scatter(knpemi_handle* h, const double* src, double* dst, int n, int dst_stride) {
   if (n == 0) return KNPEMI_OK;
   hipLaunchKernelGGL(scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, src, dst, n, dst_stride);
-  return check_launch("scatter_kernel");
+  return kn_launch_check("scatter_kernel");
 }
 
 int kn_launch_field_gather(knpemi_handle* h, const double* src, int src_stride, double* dst, int n) {
   if (n == 0) return KNPEMI_OK;
   hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, src, src_stride, dst, n);
-  return check_launch("gather_kernel");
+  return kn_launch_check("gather_kernel");
 }
 
 int kn_launch_vec_index(knpemi_handle* h, double* vec, const int32_t* idx, int n, double* buf, int gather) {
   if (n == 0) return KNPEMI_OK;
   hipLaunchKernelGGL(vec_index_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, vec, idx, n, buf, gather);
-  return check_launch("vec_index_kernel");
+  return kn_launch_check("vec_index_kernel");
 }
 
 int kn_launch_trace(knpemi_handle* h, const double* ue, const double* ui, int sub, double* qe, double* qi) {
@@ -2148,5 +2139,5 @@ int kn_launch_trace(knpemi_handle* h, const double* ue, const double* ui, int su
   if (nq == 0) return KNPEMI_OK;
   hipLaunchKernelGGL(trace_kernel, dim3((nq + 255) / 256), dim3(256), 0, h->stream, ue, ui,
                      h->dev.q2e, h->dev.q2i, h->qoff[sub], nq, h->voff[sub], qe, qi);
-  return check_launch("trace_kernel");
+  return kn_launch_check("trace_kernel");
 }

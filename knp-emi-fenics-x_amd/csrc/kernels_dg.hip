@@ -696,36 +696,25 @@ __global__ void dg_slot_kernel(double* rec, int slot, double* buf, int n, int to
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-struct knpemi_dg {
-  int device = 0, NV = 0, K = 0, n_sub = 0;
+struct knpemi_dg : KnDevice {
+  int NV = 0, K = 0, n_sub = 0;
   int NFC = 0, NFV = 0;            // facets per cell, vertices per facet (hexahedra: 6 and 4)
   int hex_box = 0;                 // hexahedra: every cell is an orthogonal parallelepiped (box-mesh kernels)
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   DgDev dev{};
   DgConsts consts{};
   DgConsts* d_consts = nullptr;
   int have_params = 0;
-  std::vector<void*> allocs;
   std::vector<int> h_rowptr, h_colind, h_q2e, h_q2i;
-  double* d_stage = nullptr;
-  size_t stage_len = 0;
   double* d_fsrc = nullptr;
   const int* d_colind = nullptr;
-  void* comm = nullptr;            // the library's RCCL communicator for the ghost-cell halo (comm_rccl.hip)
-  int comm_world = 1;
-  // per-launch event brackets of the two assembly kernels (knpemi_dg_profile)
-  int prof_on = 0;                 // 0 off, n >= 1: every n-th launch is bracketed
-  unsigned prof_count[2] = {0, 0};
-  std::vector<hipEvent_t> prof_ev[2];
-  size_t prof_used[2] = {0, 0};
+  // (prof: brackets of the two assembly kernels, 0 = EMI, 1 = KNP, on the main stream -- knpemi_dg_profile)
   // membrane ODE sweep
   int ode_model = -1, ode_ns = 0, ode_np = 0, ode_v = 0, ode_blocks = 0;
   int ode_ion_param[3 * KN_MAXK] = {0};
   double* d_states = nullptr;
   double* d_params = nullptr;
   unsigned long long* d_stats = nullptr;
-  void* d_coef = nullptr;
+  const void* d_coef = nullptr;
   // device solves (knpemi_dg_solve_emi / knpemi_dg_solve_knp): the Krylov + AMG code of the CG path run on the DG
   // systems through a handle that only carries what the solvers read
   std::vector<int> aux_of;         // continuous P1 dof (sub-domain, mesh vertex) of every broken dof
@@ -737,62 +726,8 @@ struct knpemi_dg {
 
 namespace {
 
-int dg_fail(int code, const std::string& msg) {
-  kn_set_error(msg);
-  return code;
-}
-
-template <class T>
-int dg_alloc(knpemi_dg* h, size_t n, T** out) {
-  void* p = nullptr;
-  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  KN_HIP(hipMalloc(&p, bytes));
-  h->allocs.push_back(p);
-  // zero on the handle's own (non-blocking) stream: a null-stream hipMemset is not ordered with it
-  KN_HIP(hipMemsetAsync(p, 0, bytes, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  *out = static_cast<T*>(p);
-  return 0;
-}
-
-template <class T>
-int dg_upload(knpemi_dg* h, const std::vector<T>& v, const T** out) {
-  T* p = nullptr;
-  int rc = dg_alloc(h, v.size(), &p);
-  if (rc) return rc;
-  if (!v.empty()) KN_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = p;
-  return 0;
-}
-
-int dg_check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dg_fail(KNPEMI_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-  return KNPEMI_OK;
-}
-
-struct DgProf {   // brackets one launch with an event pair on the handle's stream
-  knpemi_dg* h; int k; bool on;
-  DgProf(knpemi_dg* h_, int k_) : h(h_), k(k_), on(h_->prof_on != 0) {
-    if (on && h->prof_on > 1 && (h->prof_count[k]++ % (unsigned)h->prof_on) != 0) on = false;   // every n-th launch
-    if (!on) return;
-    auto& v = h->prof_ev[k];
-    if (h->prof_used[k] + 2 > v.size()) {
-      hipEvent_t a, b;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
-      v.push_back(a); v.push_back(b);
-    }
-    (void)hipEventRecord(v[h->prof_used[k]], h->stream);
-  }
-  ~DgProf() {
-    if (!on) return;
-    (void)hipEventRecord(h->prof_ev[k][h->prof_used[k] + 1], h->stream);
-    h->prof_used[k] += 2;
-  }
-};
-
 int launch_emi(knpemi_dg* h, int flags) {
-  DgProf prof(h, 0);
+  KnProfScope prof(h->prof, 0, h->stream);
   if (h->NV == 8) return kn_dg_hex_launch_emi(h->stream, h->dev, h->d_consts, !(flags & KNPEMI_NO_SPLITTING), h->hex_box);
   const int NV = h->NV, rpb = (DG_BLOCK / NV) * NV;
   const int nblocks = (h->dev.n_dof + rpb - 1) / rpb, chunk = (nblocks + 7) / 8;
@@ -817,7 +752,7 @@ int launch_emi(knpemi_dg* h, int flags) {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(dg_stamp_acc), acc.data(), acc.size() * sizeof(unsigned long long));
   }
 #endif
-  return dg_check_launch("dg_emi_kernel");
+  return kn_launch_check("dg_emi_kernel");
 }
 
 template <int NV>
@@ -829,11 +764,11 @@ int launch_knp_nv(knpemi_dg* h, int chunk, int split) {
     case 2: hipLaunchKernelGGL((dg_knp_kernel<NV, 2>), grid, block, ((size_t)rpb * dg_fs_knp<NV, 2>() + dg_scratch_doubles<NV, 1>()) * sizeof(double), h->stream, h->dev, h->d_consts, chunk, split); break;
     default: hipLaunchKernelGGL((dg_knp_kernel<NV, 3>), grid, block, ((size_t)rpb * dg_fs_knp<NV, 3>() + dg_scratch_doubles<NV, 1>()) * sizeof(double), h->stream, h->dev, h->d_consts, chunk, split); break;
   }
-  return dg_check_launch("dg_knp_kernel");
+  return kn_launch_check("dg_knp_kernel");
 }
 
 int launch_knp(knpemi_dg* h, int flags) {
-  DgProf prof(h, 1);
+  KnProfScope prof(h->prof, 1, h->stream);
   if (h->NV == 8) return kn_dg_hex_launch_knp(h->stream, h->dev, h->d_consts, h->K - 1, !(flags & KNPEMI_NO_SPLITTING), h->hex_box);
   const int NV = h->NV, rpb = (DG_BLOCK / NV) * NV;
   const int nblocks = (h->dev.n_dof + rpb - 1) / rpb, chunk = (nblocks + 7) / 8;
@@ -846,30 +781,24 @@ int launch_knp(knpemi_dg* h, int flags) {
 extern "C" void knpemi_dg_destroy(knpemi_dg* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : h->allocs) (void)hipFree(p);
-  kn_comm_free(h->comm);
-  if (h->sol) {
+  kn_device_release(h);
+  if (h->sol) {   // borrows the stream, owns its solver state and what the solves allocated
     kn_solver_free(h->sol);
-    for (void* p : h->sol->allocs) (void)hipFree(p);
+    kn_free_all(h->sol->allocs);
     delete h->sol;
   }
-  if (h->d_coef) (void)hipFree(h->d_coef);
-  for (auto& v : h->prof_ev) for (hipEvent_t e : v) (void)hipEventDestroy(e);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  kn_device_close(h);
   delete h;
 }
 
 extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg** out) {
-  if (!d || !out) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: null argument");
+  if (!d || !out) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: null argument");
   *out = nullptr;
   int NV, NFC, NF, GD;   // vertices and facets per cell, vertices per facet, dimension
   if (d->cell_kind == KNPEMI_TRIANGLE) { NV = 3; NFC = 3; NF = 2; GD = 2; }
   else if (d->cell_kind == KNPEMI_TETRAHEDRON) { NV = 4; NFC = 4; NF = 3; GD = 3; }
   else if (d->cell_kind == KNPEMI_HEXAHEDRON) { NV = 8; NFC = 6; NF = 4; GD = 3; }
-  else return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: unknown cell kind");
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: unknown cell kind");
   const bool hex = NV == 8;
   // local vertex of local facet f at facet position m.  Simplices: facet f is opposite vertex f, its vertices in
   // increasing local order.  Hexahedra (tensor numbering: bit a of a local vertex is its coordinate along axis a):
@@ -879,26 +808,19 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
     const int a = f >> 1, b = f & 1, a1 = a == 0 ? 1 : 0, a2 = a == 2 ? 1 : 2;
     return (b << a) | ((m & 1) << a1) | ((m >> 1) << a2);
   };
-  if (d->n_ions < 2 || d->n_ions > KN_MAXK) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: 2 to 4 ionic species are supported");
-  if (d->n_sub < 1 || d->n_sub > KN_MAXSUB) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: bad n_sub");
-  if (d->n_cells < 1 || d->n_cells * NV >= (int64_t)1 << 31) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: bad n_cells");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return dg_fail(KNPEMI_EHIP, "knpemi_dg_create: no HIP device visible (the hot path has no CPU fallback)");
-  if (device < 0 || device >= ndev) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: bad device index");
-  KN_HIP(hipSetDevice(device));
+  if (d->n_ions < 2 || d->n_ions > KN_MAXK) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: 2 to 4 ionic species are supported");
+  if (d->n_sub < 1 || d->n_sub > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: bad n_sub");
+  if (d->n_cells < 1 || d->n_cells * NV >= (int64_t)1 << 31) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: bad n_cells");
   auto* h = new knpemi_dg();
   std::unique_ptr<knpemi_dg, void (*)(knpemi_dg*)> guard(h, knpemi_dg_destroy);
-  h->device = device; h->NV = NV; h->K = d->n_ions; h->n_sub = d->n_sub;
+  if (int rc = kn_device_open(h, device, "knpemi_dg_create")) return rc;
+  h->NV = NV; h->K = d->n_ions; h->n_sub = d->n_sub;
   h->NFC = NFC; h->NFV = NF;
-  KN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  KN_HIP(hipEventCreate(&h->ev0));
-  KN_HIP(hipEventCreate(&h->ev1));
 
   const int nc = (int)d->n_cells, nmf = (int)d->n_mem_facets, n = nc * NV;
   std::vector<double> box_h;      // hexahedral box meshes: the cells' edge lengths along their local axes
   for (int c = 0; c < nc; ++c)
-    if (d->cell_sub[c] < 0 || d->cell_sub[c] >= d->n_sub) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: cell_sub out of range");
+    if (d->cell_sub[c] < 0 || d->cell_sub[c] >= d->n_sub) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: cell_sub out of range");
   if (hex) {
     // tensor-product vertex order (bit a of a local vertex = its coordinate along axis a): the trilinear map of a cell
     // given in another order (e.g. the counter-clockwise order of other formats) folds over, i.e. its Jacobian
@@ -910,7 +832,7 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
         for (int a = 0; a < 3; ++a) {
           const int v0 = d->cells[(size_t)c * 8 + j], v1 = d->cells[(size_t)c * 8 + (j ^ (1 << a))];
           if (v0 < 0 || v0 >= d->n_vertices || v1 < 0 || v1 >= d->n_vertices)
-            return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: vertex id out of range");
+            return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: vertex id out of range");
           const double sgn = ((j >> a) & 1) ? -1.0 : 1.0;
           for (int k = 0; k < 3; ++k) e[a][k] = sgn * (d->x[(size_t)v1 * 3 + k] - d->x[(size_t)v0 * 3 + k]);
         }
@@ -920,7 +842,7 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
         neg += det < 0.0;
       }
       if (pos != 8 && neg != 8)
-        return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: hexahedron " + std::to_string(c) +
+        return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: hexahedron " + std::to_string(c) +
                                           " is degenerate or not in tensor-product vertex order");
     }
     // box mesh (every mesh of the reference's 3-D driver, make_mesh_3D.py:100-102): all cells orthogonal parallelepipeds to
@@ -964,7 +886,7 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
   for (int c = 0; c < nc; ++c) {
     for (int a = 0; a < NV; ++a)
       if (d->cells[(size_t)c * NV + a] < 0 || d->cells[(size_t)c * NV + a] >= d->n_vertices)
-        return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: vertex id out of range");
+        return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: vertex id out of range");
     for (int f = 0; f < NFC; ++f) {
       std::array<int, 4> k = {-1, -1, -1, -1};
       for (int m = 0; m < NF; ++m) k[m] = d->cells[(size_t)c * NV + facet_vertex(f, m)];
@@ -1005,16 +927,16 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
     int mem = -1, cf[2], ncf = 0;
     for (size_t t = e; t < e1; ++t) {
       if (ents[t].id < 0) {
-        if (mem >= 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet listed twice");
+        if (mem >= 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet listed twice");
         mem = -1 - ents[t].id;
       } else {
-        if (ncf == 2) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: a facet is shared by more than two cells");
+        if (ncf == 2) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: a facet is shared by more than two cells");
         cf[ncf++] = ents[t].id;
       }
     }
     e = e1;
     if (ncf < 2) {
-      if (mem >= 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet is not shared by two cells");
+      if (mem >= 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet is not shared by two cells");
       continue;
     }
     const int c0 = cf[0] / NFC, f0 = cf[0] % NFC, c1 = cf[1] / NFC, f1 = cf[1] % NFC;
@@ -1022,11 +944,11 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
     int kind0 = 1, kind1 = 1;
     if (mem >= 0) {
       if (!((s0 == 0) != (s1 == 0)))
-        return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: a membrane facet must separate an ECS cell from a cell of a sub-domain > 0");
+        return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: a membrane facet must separate an ECS cell from a cell of a sub-domain > 0");
       kind0 = s0 == 0 ? 2 : 3;
       kind1 = s1 == 0 ? 2 : 3;
     } else if (s0 != s1) {
-      return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: facet between two sub-domains is not in mem_facets");
+      return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: facet between two sub-domains is not in mem_facets");
     }
     for (int side = 0; side < 2; ++side) {
       const int c = side ? c1 : c0, f = side ? f1 : f0, o = side ? c0 : c1, fo = side ? f0 : f1;
@@ -1035,13 +957,13 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
         const int a = facet_vertex(f, m);
         const int v = d->cells[(size_t)c * NV + a];
         const int lo_ = local_of(o, v);
-        if (lo_ < 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: two cells share a facet key but not its vertices");
+        if (lo_ < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: two cells share a facet key but not its vertices");
         // simplices: 2-bit fields indexed by the cell's local vertex; hexahedra: 3-bit / 2-bit fields by facet position
         w |= hex ? (unsigned)lo_ << (5 + 3 * m) : (unsigned)lo_ << (4 + 2 * a);
         if (mem >= 0) {
           int node = -1;
           for (int t = 0; t < NF; ++t) if (d->mem_facets[(size_t)mem * NF + t] == v) node = t;
-          if (node < 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet vertices do not match the cells'");
+          if (node < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet vertices do not match the cells'");
           w |= hex ? (unsigned)node << (17 + 2 * m) : (unsigned)node << (12 + 2 * a);
           (d->cell_sub[c] == 0 ? h->h_q2e : h->h_q2i)[(size_t)mem * NF + node] = c * NV + a;
         }
@@ -1050,7 +972,7 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
         const int ao = fo >> 1;
         for (int m = 0; m < NF; ++m)
           if ((int)((((w >> (5 + 3 * m)) & 7) >> ao) & 1) != (fo & 1))
-            return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: hexahedra are not in tensor-product vertex order");
+            return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: hexahedra are not in tensor-product vertex order");
       }
       nbr[(size_t)c * NFC + f] = o;
       finfo[(size_t)c * NFC + f] = w;
@@ -1064,7 +986,7 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
     int cnt = 1;
     for (int f = 0; f < NFC; ++f) cnt += nbr[(size_t)c * NFC + f] >= 0;
     for (int i = 0; i < NV; ++i) { nnz += (int64_t)cnt * NV; h->h_rowptr[(size_t)c * NV + i + 1] = (int)nnz; }
-    if (nnz >= ((int64_t)1 << 31) - 64) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: more than 2^31 matrix entries");
+    if (nnz >= ((int64_t)1 << 31) - 64) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: more than 2^31 matrix entries");
   }
   h->h_colind.resize((size_t)nnz);
   for (int c = 0; c < nc; ++c) {
@@ -1086,53 +1008,53 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
   D.n_cell = nc; D.n_dof = n; D.nq = nmf * NF; D.nnz = nnz;
   int rc;
   const double* crec = nullptr;
-  if ((rc = dg_upload(h, rec, &crec))) return rc;
+  if ((rc = kn_upload(h->allocs, rec, &crec))) return rc;
   D.rec = const_cast<double*>(crec);
-  if ((rc = dg_upload(h, nbr, &D.nbr))) return rc;
-  if ((rc = dg_upload(h, finfo, &D.finfo))) return rc;
-  if ((rc = dg_upload(h, mfid, &D.mfid))) return rc;
+  if ((rc = kn_upload(h->allocs, nbr, &D.nbr))) return rc;
+  if ((rc = kn_upload(h->allocs, finfo, &D.finfo))) return rc;
+  if ((rc = kn_upload(h->allocs, mfid, &D.mfid))) return rc;
   D.box_h = nullptr;
-  if (h->hex_box && (rc = dg_upload(h, box_h, &D.box_h))) return rc;
-  if ((rc = dg_upload(h, csub, &D.cell_sub))) return rc;
-  if ((rc = dg_upload(h, h->h_rowptr, &D.rowptr))) return rc;
-  if ((rc = dg_upload(h, h->h_q2e, &D.q2e))) return rc;
-  if ((rc = dg_upload(h, h->h_q2i, &D.q2i))) return rc;
-  if ((rc = dg_alloc(h, (size_t)nnz, &D.A_emi))) return rc;
-  if ((rc = dg_alloc(h, (size_t)n, &D.b_emi))) return rc;
-  if ((rc = dg_alloc(h, (size_t)(h->K - 1) * nnz, &D.A_knp))) return rc;
-  if ((rc = dg_alloc(h, (size_t)(h->K - 1) * n, &D.b_knp))) return rc;
-  if ((rc = dg_alloc(h, (size_t)D.nq, &D.phiM))) return rc;
-  if ((rc = dg_alloc(h, (size_t)KN_MAXK * std::max(D.nq, 1), &D.Ich))) return rc;
+  if (h->hex_box && (rc = kn_upload(h->allocs, box_h, &D.box_h))) return rc;
+  if ((rc = kn_upload(h->allocs, csub, &D.cell_sub))) return rc;
+  if ((rc = kn_upload(h->allocs, h->h_rowptr, &D.rowptr))) return rc;
+  if ((rc = kn_upload(h->allocs, h->h_q2e, &D.q2e))) return rc;
+  if ((rc = kn_upload(h->allocs, h->h_q2i, &D.q2i))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)nnz, &D.A_emi))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n, &D.b_emi))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)(h->K - 1) * nnz, &D.A_knp))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)(h->K - 1) * n, &D.b_knp))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)D.nq, &D.phiM))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)KN_MAXK * std::max(D.nq, 1), &D.Ich))) return rc;
   D.fsrc = nullptr;
   {
     std::vector<double> qt;
     D.nquad = kn_gamma_quadrature(NF, &qt);
-    if ((rc = dg_upload(h, qt, &D.qtab))) return rc;
+    if ((rc = kn_upload(h->allocs, qt, &D.qtab))) return rc;
   }
   h->stage_len = (size_t)std::max(n, 1) * (size_t)std::max(1, h->K - 1);
-  if ((rc = dg_alloc(h, h->stage_len, &h->d_stage))) return rc;
-  if ((rc = dg_alloc(h, 1, &h->d_consts))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, h->stage_len, &h->d_stage))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, 1, &h->d_consts))) return rc;
   for (size_t t = 0; t < h->h_q2e.size(); ++t)
-    if (h->h_q2e[t] < 0 || h->h_q2i[t] < 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet without two cells");
+    if (h->h_q2e[t] < 0 || h->h_q2i[t] < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: membrane facet without two cells");
   guard.release();
   *out = h;
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_set_params(knpemi_dg* h, const knpemi_dg_params* p) {
-  if (!h || !p) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: null argument");
-  if (!(p->dt > 0) || !(p->gamma > 0)) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: dt and gamma must be positive");
+  if (!h || !p) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: null argument");
+  if (!(p->dt > 0) || !(p->gamma > 0)) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: dt and gamma must be positive");
   KN_HIP(hipSetDevice(h->device));
   DgConsts& C = h->consts;
   std::memset(&C, 0, sizeof(C));
   C.n_sub = h->n_sub; C.K = h->K;
   C.F = p->F; C.psi = p->psi; C.C_M = p->C_M; C.dt = p->dt; C.inv_dt = 1.0 / p->dt; C.C_phi = p->C_M / p->dt; C.gamma = p->gamma;
   const double zK = p->z[h->K - 1];
-  if (zK == 0.0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: the eliminated ion needs a non-zero valence");
+  if (zK == 0.0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: the eliminated ion needs a non-zero valence");
   for (int k = 0; k < h->K; ++k) {
     C.z[k] = p->z[k];
     C.elim[k] = -(p->z[k] / zK);
-    if (k < h->K - 1 && p->z[k] == 0.0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: zero valence");
+    if (k < h->K - 1 && p->z[k] == 0.0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_params: zero valence");
   }
   for (int s = 0; s < h->n_sub; ++s) {
     for (int k = 0; k < h->K; ++k) {
@@ -1144,14 +1066,13 @@ extern "C" int knpemi_dg_set_params(knpemi_dg* h, const knpemi_dg_params* p) {
     }
     C.rho_term[s] = -(1.0 / zK) * p->rho_z * p->rho[s];
   }
-  KN_HIP(hipMemcpyAsync(h->d_consts, &C, sizeof(C), hipMemcpyHostToDevice, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
+  if (int rc = kn_to_device(h->stream, h->d_consts, &C, 1)) return rc;
   h->have_params = 1;
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_dims(knpemi_dg* h, int64_t* n_dofs, int64_t* nnz, int64_t* n_mem_nodes) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_dims: null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_dims: null handle");
   if (n_dofs) *n_dofs = h->dev.n_dof;
   if (nnz) *nnz = h->dev.nnz;
   if (n_mem_nodes) *n_mem_nodes = h->dev.nq;
@@ -1159,14 +1080,14 @@ extern "C" int knpemi_dg_dims(knpemi_dg* h, int64_t* n_dofs, int64_t* nnz, int64
 }
 
 extern "C" int knpemi_dg_get_pattern(knpemi_dg* h, int32_t* rowptr, int32_t* colind) {
-  if (!h || !rowptr || !colind) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_pattern: null argument");
+  if (!h || !rowptr || !colind) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_pattern: null argument");
   std::memcpy(rowptr, h->h_rowptr.data(), h->h_rowptr.size() * sizeof(int));
   std::memcpy(colind, h->h_colind.data(), h->h_colind.size() * sizeof(int));
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_get_membrane_dofs(knpemi_dg* h, int32_t* dof_e, int32_t* dof_i) {
-  if (!h || !dof_e || !dof_i) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_membrane_dofs: null argument");
+  if (!h || !dof_e || !dof_i) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_membrane_dofs: null argument");
   std::memcpy(dof_e, h->h_q2e.data(), h->h_q2e.size() * sizeof(int));
   std::memcpy(dof_i, h->h_q2i.data(), h->h_q2i.size() * sizeof(int));
   return KNPEMI_OK;
@@ -1179,103 +1100,94 @@ int dg_field(knpemi_dg* h, int field, int idx, double** ptr, size_t* len, int* s
   *slot = -1;
   switch (field) {
     case KNPEMI_DG_C:
-      if (idx < 0 || idx >= h->K) return dg_fail(KNPEMI_EINVAL, "knpemi_dg field: ion index out of range");
+      if (idx < 0 || idx >= h->K) return kn_fail(KNPEMI_EINVAL, "knpemi_dg field: ion index out of range");
       *slot = KN_CSLOT(idx); *ptr = D.rec; *len = D.n_dof; return 0;
     case KNPEMI_DG_PHI: *slot = 7; *ptr = D.rec; *len = D.n_dof; return 0;
     case KNPEMI_DG_PHI_M: *ptr = D.phiM; *len = D.nq; return 0;
     case KNPEMI_DG_I_CH:
-      if (idx < 0 || idx >= h->K) return dg_fail(KNPEMI_EINVAL, "knpemi_dg field: ion index out of range");
+      if (idx < 0 || idx >= h->K) return kn_fail(KNPEMI_EINVAL, "knpemi_dg field: ion index out of range");
       *ptr = D.Ich + (size_t)idx * D.nq; *len = D.nq; return 0;
     case KNPEMI_DG_SOURCE:
-      if (idx < 0 || idx >= h->K - 1) return dg_fail(KNPEMI_EINVAL, "knpemi_dg field: ion index out of range");
+      if (idx < 0 || idx >= h->K - 1) return kn_fail(KNPEMI_EINVAL, "knpemi_dg field: ion index out of range");
       if (!h->d_fsrc) {
-        int rc = dg_alloc(h, (size_t)(h->K - 1) * D.n_dof, &h->d_fsrc);
+        int rc = kn_zeros(h->allocs, h->stream, (size_t)(h->K - 1) * D.n_dof, &h->d_fsrc);
         if (rc) return rc;
         h->dev.fsrc = h->d_fsrc;
       }
       *ptr = h->d_fsrc + (size_t)idx * D.n_dof; *len = D.n_dof; return 0;
   }
-  return dg_fail(KNPEMI_EINVAL, "knpemi_dg field: unknown field");
+  return kn_fail(KNPEMI_EINVAL, "knpemi_dg field: unknown field");
 }
 }  // namespace
 
 extern "C" int knpemi_dg_set_field(knpemi_dg* h, int field, int idx, const double* host, size_t n) {
-  if (!h || !host) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_field: null argument");
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_field: null argument");
   KN_HIP(hipSetDevice(h->device));
   double* ptr; size_t len; int slot;
   int rc = dg_field(h, field, idx, &ptr, &len, &slot);
   if (rc) return rc;
-  if (n != len) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_field: length mismatch");
+  if (n != len) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_field: length mismatch");
   if (len == 0) return KNPEMI_OK;
-  if (slot < 0) {
-    KN_HIP(hipMemcpyAsync(ptr, host, len * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  } else {
-    KN_HIP(hipMemcpyAsync(h->d_stage, host, len * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(dg_slot_kernel, dim3((len + 255) / 256), dim3(256), 0, h->stream, ptr, slot, h->d_stage, (int)len, 1);
-    if ((rc = dg_check_launch("dg_slot_kernel"))) return rc;
-  }
+  if (slot < 0) return kn_to_device(h->stream, ptr, host, len);
+  KN_HIP(hipMemcpyAsync(h->d_stage, host, len * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dg_slot_kernel, dim3((len + 255) / 256), dim3(256), 0, h->stream, ptr, slot, h->d_stage, (int)len, 1);
+  if ((rc = kn_launch_check("dg_slot_kernel"))) return rc;
   KN_HIP(hipStreamSynchronize(h->stream));
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_get_field(knpemi_dg* h, int field, int idx, double* host, size_t n) {
-  if (!h || !host) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_field: null argument");
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_field: null argument");
   KN_HIP(hipSetDevice(h->device));
   double* ptr; size_t len; int slot;
   int rc = dg_field(h, field, idx, &ptr, &len, &slot);
   if (rc) return rc;
-  if (n != len) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_field: length mismatch");
+  if (n != len) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_field: length mismatch");
   if (len == 0) return KNPEMI_OK;
-  if (slot < 0) {
-    KN_HIP(hipMemcpyAsync(host, ptr, len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  } else {
+  const double* src = ptr;
+  if (slot >= 0) {
     hipLaunchKernelGGL(dg_slot_kernel, dim3((len + 255) / 256), dim3(256), 0, h->stream, ptr, slot, h->d_stage, (int)len, 0);
-    if ((rc = dg_check_launch("dg_slot_kernel"))) return rc;
-    KN_HIP(hipMemcpyAsync(host, h->d_stage, len * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kn_launch_check("dg_slot_kernel"))) return rc;
+    src = h->d_stage;
   }
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_host(h->stream, host, src, len);
 }
 
 extern "C" int knpemi_dg_assemble_emi(knpemi_dg* h, int flags) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_emi: null handle");
-  if (!h->have_params) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_emi: knpemi_dg_set_params has not been called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_emi: null handle");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_emi: knpemi_dg_set_params has not been called");
   KN_HIP(hipSetDevice(h->device));
   return launch_emi(h, flags);
 }
 
 extern "C" int knpemi_dg_assemble_knp(knpemi_dg* h, int flags) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_knp: null handle");
-  if (!h->have_params) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_knp: knpemi_dg_set_params has not been called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_knp: null handle");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_knp: knpemi_dg_set_params has not been called");
   KN_HIP(hipSetDevice(h->device));
   return launch_knp(h, flags);
 }
 
 extern "C" int knpemi_dg_get_values(knpemi_dg* h, int which, double* vals) {
-  if (!h || !vals || which < 0 || which > h->K - 1) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_values: bad argument");
+  if (!h || !vals || which < 0 || which > h->K - 1) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_values: bad argument");
   KN_HIP(hipSetDevice(h->device));
   const double* src = which == 0 ? h->dev.A_emi : h->dev.A_knp + (size_t)(which - 1) * h->dev.nnz;
-  KN_HIP(hipMemcpyAsync(vals, src, (size_t)h->dev.nnz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_host(h->stream, vals, src, (size_t)h->dev.nnz);
 }
 
 extern "C" int knpemi_dg_get_rhs(knpemi_dg* h, int which, double* b) {
-  if (!h || !b || which < 0 || which > h->K - 1) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_rhs: bad argument");
+  if (!h || !b || which < 0 || which > h->K - 1) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_rhs: bad argument");
   KN_HIP(hipSetDevice(h->device));
   const double* src = which == 0 ? h->dev.b_emi : h->dev.b_knp + (size_t)(which - 1) * h->dev.n_dof;
-  KN_HIP(hipMemcpyAsync(b, src, (size_t)h->dev.n_dof * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_host(h->stream, b, src, (size_t)h->dev.n_dof);
 }
 
 extern "C" int knpemi_dg_device_system(knpemi_dg* h, int which, const int32_t** rowptr, const int32_t** colind,
                                        const double** vals, const double** b) {
-  if (!h || which < 0 || which > h->K - 1) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_device_system: bad argument");
+  if (!h || which < 0 || which > h->K - 1) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_device_system: bad argument");
   if (colind) {   // uploaded on first request: the assembly kernels never read the column indices
     if (!h->d_colind) {
       KN_HIP(hipSetDevice(h->device));
-      int rc = dg_upload(h, h->h_colind, &h->d_colind);
+      int rc = kn_upload(h->allocs, h->h_colind, &h->d_colind);
       if (rc) return rc;
     }
     *colind = h->d_colind;
@@ -1287,8 +1199,8 @@ extern "C" int knpemi_dg_device_system(knpemi_dg* h, int which, const int32_t** 
 }
 
 extern "C" int knpemi_dg_update(knpemi_dg* h, const double* c_new, int on_device) {
-  if (!h || !c_new) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_update: null argument");
-  if (!h->have_params) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_update: knpemi_dg_set_params has not been called");
+  if (!h || !c_new) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_update: null argument");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_update: knpemi_dg_set_params has not been called");
   KN_HIP(hipSetDevice(h->device));
   const size_t len = (size_t)(h->K - 1) * h->dev.n_dof;
   const double* src = c_new;
@@ -1298,7 +1210,7 @@ extern "C" int knpemi_dg_update(knpemi_dg* h, const double* c_new, int on_device
   }
   const int nt = std::max(h->dev.n_dof, h->dev.nq);
   hipLaunchKernelGGL(dg_update_kernel, dim3((nt + 255) / 256), dim3(256), 0, h->stream, h->dev, h->d_consts, src, h->NV);
-  int rc = dg_check_launch("dg_update_kernel");
+  int rc = kn_launch_check("dg_update_kernel");
   if (rc) return rc;
   if (!on_device) KN_HIP(hipStreamSynchronize(h->stream));
   return KNPEMI_OK;
@@ -1326,9 +1238,9 @@ int dg_solver(knpemi_dg* h, knpemi_handle** out) {
   const DgDev& D = h->dev;
   const int n = D.n_dof, KS = h->K - 1;
   if ((int64_t)KS * D.nnz >= ((int64_t)1 << 31) - 64)
-    return dg_fail(KNPEMI_EINVAL, "knpemi_dg_solve: the block-diagonal concentration system has more than 2^31 entries");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_dg_solve: the block-diagonal concentration system has more than 2^31 entries");
   int rc;
-  if (!h->d_colind && (rc = dg_upload(h, h->h_colind, &h->d_colind))) return rc;
+  if (!h->d_colind && (rc = kn_upload(h->allocs, h->h_colind, &h->d_colind))) return rc;
   // block-diagonal pattern of the K - 1 concentration systems
   std::vector<int> krp((size_t)KS * n + 1), kci((size_t)KS * D.nnz);
   for (int k = 0; k < KS; ++k) {
@@ -1337,9 +1249,9 @@ int dg_solver(knpemi_dg* h, knpemi_handle** out) {
   }
   krp[(size_t)KS * n] = (int)(KS * D.nnz);
   const int *d_krp = nullptr, *d_kci = nullptr;
-  if ((rc = dg_upload(h, krp, &d_krp))) return rc;
-  if ((rc = dg_upload(h, kci, &d_kci))) return rc;
-  if ((rc = dg_alloc(h, (size_t)KS * n, &h->d_csol))) return rc;
+  if ((rc = kn_upload(h->allocs, krp, &d_krp))) return rc;
+  if ((rc = kn_upload(h->allocs, kci, &d_kci))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)KS * n, &h->d_csol))) return rc;
   auto* s = new knpemi_handle();
   s->device = h->device;
   s->stream = s->cur = h->stream;
@@ -1364,7 +1276,7 @@ int dg_solver(knpemi_dg* h, knpemi_handle** out) {
       for (int b = 0; b < nb; ++b) bcol[(size_t)c * nbmax + b] = h->h_colind[(size_t)a + (size_t)b * NV] / NV;
     }
     const int* d_bcol = nullptr;
-    if ((rc = dg_upload(h, bcol, &d_bcol))) return rc;
+    if ((rc = kn_upload(h->allocs, bcol, &d_bcol))) return rc;
     s->bcols.bcol = d_bcol; s->bcols.nv = NV; s->bcols.nbmax = nbmax; s->bcols.n = n;
   }
   KnAmgConfig cfg;
@@ -1404,7 +1316,7 @@ extern "C" void* knpemi_dg_solver_handle(knpemi_dg* h) {
 // switches back to single-rank solves.  Vector orders: KNPEMI_B_EMI one value per dof, KNPEMI_B_KNP [solved ion][dof].
 extern "C" int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, void* reduce_buf_dev, knpemi_allreduce_fn allreduce,
                                          knpemi_halo_fn halo, void* ctx) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_distributed: null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_distributed: null handle");
   KN_HIP(hipSetDevice(h->device));
   knpemi_handle* s = nullptr;
   int rc = dg_solver(h, &s);
@@ -1438,21 +1350,21 @@ extern "C" int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, voi
   dg_first_aggregates(s, agg, na, KS, n);
   if (!owned) { d.on = false; return KNPEMI_OK; }
   if (!reduce_buf_dev || !allreduce || !halo)
-    return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_distributed: reduction buffer and both communication hooks are required");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_distributed: reduction buffer and both communication hooks are required");
   d.h_owned_emi.assign(owned, owned + n);
   d.h_owned_knp.resize((size_t)KS * n);
   for (int k = 0; k < KS; ++k) std::copy(owned, owned + n, d.h_owned_knp.begin() + (size_t)k * n);
   const uint8_t* p = nullptr;
-  if ((rc = dg_upload(h, d.h_owned_emi, &p))) return rc;
+  if ((rc = kn_upload(h->allocs, d.h_owned_emi, &p))) return rc;
   d.d_owned_emi = const_cast<uint8_t*>(p);
-  if ((rc = dg_upload(h, d.h_owned_knp, &p))) return rc;
+  if ((rc = kn_upload(h->allocs, d.h_owned_knp, &p))) return rc;
   d.d_owned_knp = const_cast<uint8_t*>(p);
   d.d_red = static_cast<double*>(reduce_buf_dev);
   d.allreduce = allreduce; d.halo = halo; d.ctx = ctx;
   double cnt = 0.0;   // owned dofs over all ranks (mean of the constant null space)
   for (int i = 0; i < n; ++i) cnt += owned[i] ? 1.0 : 0.0;
   KN_HIP(hipMemcpyAsync(d.d_red, &cnt, sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (allreduce(ctx, 1)) return dg_fail(KNPEMI_EHIP, "knpemi_dg_set_distributed: allreduce hook failed");
+  if (allreduce(ctx, 1)) return kn_fail(KNPEMI_EHIP, "knpemi_dg_set_distributed: allreduce hook failed");
   KN_HIP(hipMemcpyAsync(&cnt, d.d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   KN_HIP(hipStreamSynchronize(h->stream));
   d.n_owned_global = cnt;
@@ -1468,7 +1380,7 @@ extern "C" int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, voi
 // smoother on the broken dofs.  The potential goes into the dof records, the concentrations stay in the solver's
 // buffer until knpemi_dg_update (update != 0 runs it right away).
 extern "C" int knpemi_dg_solve_emi(knpemi_dg* h, double rtol, double atol, int maxit, int* iters, double* relres) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_solve_emi: null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_solve_emi: null handle");
   KN_HIP(hipSetDevice(h->device));
   knpemi_handle* s = nullptr;
   int rc = dg_solver(h, &s);
@@ -1480,15 +1392,15 @@ extern "C" int knpemi_dg_solve_emi(knpemi_dg* h, double rtol, double atol, int m
 // Initial guesses of the two solves: the linear extrapolation 2 x_n - x_(n-1) of the last two solutions instead of the
 // last one (knpemi_extrapolate_guess of the CG path); only the starting point changes.
 extern "C" int knpemi_dg_set_extrapolation(knpemi_dg* h, int on) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_set_extrapolation: null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_extrapolation: null handle");
   h->extrapolate = on ? 1 : 0;
   if (h->sol) { h->sol->guess_have[0] = -1; h->sol->guess_have[1] = 0; }
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_solve_knp(knpemi_dg* h, double rtol, double atol, int maxit, int* iters, double* relres, int update) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_solve_knp: null handle");
-  if (update && !h->have_params) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_solve_knp: knpemi_dg_set_params has not been called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_solve_knp: null handle");
+  if (update && !h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_solve_knp: knpemi_dg_set_params has not been called");
   KN_HIP(hipSetDevice(h->device));
   knpemi_handle* s = nullptr;
   int rc = dg_solver(h, &s);
@@ -1503,34 +1415,32 @@ extern "C" int knpemi_dg_solve_knp(knpemi_dg* h, double rtol, double atol, int m
 }
 
 extern "C" int knpemi_dg_get_solution(knpemi_dg* h, double* c_host) {
-  if (!h || !c_host) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_solution: null argument");
-  if (!h->d_csol) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_get_solution: knpemi_dg_solve_knp has not been called");
+  if (!h || !c_host) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_solution: null argument");
+  if (!h->d_csol) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_get_solution: knpemi_dg_solve_knp has not been called");
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipMemcpyAsync(c_host, h->d_csol, (size_t)(h->K - 1) * h->dev.n_dof * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_host(h->stream, c_host, h->d_csol, (size_t)(h->K - 1) * h->dev.n_dof);
 }
 
 extern "C" int knpemi_dg_halo_pack(knpemi_dg* h, const int32_t* idx_dev, int n, double* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!idx_dev || !buf_dev))) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_halo_pack: bad argument");
+  if (!h || n < 0 || (n > 0 && (!idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_halo_pack: bad argument");
   if (n == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
   hipLaunchKernelGGL(dg_halo_kernel, dim3((5 * (size_t)n + 255) / 256), dim3(256), 0, h->stream, h->dev.rec, idx_dev, n, buf_dev, 0);
-  return dg_check_launch("dg_halo_kernel");
+  return kn_launch_check("dg_halo_kernel");
 }
 
 extern "C" int knpemi_dg_halo_unpack(knpemi_dg* h, const int32_t* idx_dev, int n, const double* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!idx_dev || !buf_dev))) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_halo_unpack: bad argument");
+  if (!h || n < 0 || (n > 0 && (!idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_halo_unpack: bad argument");
   if (n == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
   hipLaunchKernelGGL(dg_halo_kernel, dim3((5 * (size_t)n + 255) / 256), dim3(256), 0, h->stream, h->dev.rec, idx_dev, n,
                      const_cast<double*>(buf_dev), 1);
-  return dg_check_launch("dg_halo_kernel");
+  return kn_launch_check("dg_halo_kernel");
 }
 
 extern "C" int knpemi_dg_comm_init(knpemi_dg* h, int rank, int world, const char* id_bytes, size_t len) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_comm_init: null handle");
-  if (h->comm) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_comm_init: communicator already created");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_comm_init: null handle");
+  if (h->comm) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_comm_init: communicator already created");
   int rc = kn_comm_create(h->device, rank, world, id_bytes, len, &h->comm);
   if (rc) return rc;
   h->comm_world = world;
@@ -1540,21 +1450,21 @@ extern "C" int knpemi_dg_comm_init(knpemi_dg* h, int rank, int world, const char
 extern "C" int knpemi_dg_comm_sendrecv(knpemi_dg* h, const double* send_buf_dev, double* recv_buf_dev, int n_parts,
                                        const int32_t* peer, const int64_t* send_off, const int64_t* send_cnt,
                                        const int64_t* recv_off, const int64_t* recv_cnt) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_comm_sendrecv: null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_comm_sendrecv: null handle");
   return kn_comm_sendrecv(h->comm, h->comm_world, h->device, h->stream, send_buf_dev, recv_buf_dev, n_parts, peer, send_off,
                           send_cnt, recv_off, recv_cnt);
 }
 
 extern "C" int knpemi_dg_sync(knpemi_dg* h) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_sync: null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_sync: null handle");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_time_kernel(knpemi_dg* h, int which, int flags, int reps, double* avg_ms) {
-  if (!h || !avg_ms || reps < 1 || which < 0 || which > 1) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_time_kernel: bad argument");
-  if (!h->have_params) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_time_kernel: knpemi_dg_set_params has not been called");
+  if (!h || !avg_ms || reps < 1 || which < 0 || which > 1) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_time_kernel: bad argument");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_time_kernel: knpemi_dg_set_params has not been called");
   KN_HIP(hipSetDevice(h->device));
   int rc = which == 0 ? launch_emi(h, flags) : launch_knp(h, flags);   // warm-up
   if (rc) return rc;
@@ -1572,62 +1482,49 @@ extern "C" int knpemi_dg_time_kernel(knpemi_dg* h, int which, int flags, int rep
 extern "C" void* knpemi_dg_stream(knpemi_dg* h) { return h ? (void*)h->stream : nullptr; }
 
 extern "C" int knpemi_dg_profile(knpemi_dg* h, int on) {
-  if (!h) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_profile: null handle");
-  h->prof_on = on > 0 ? on : 0;
-  h->prof_count[0] = h->prof_count[1] = 0;
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_profile: null handle");
+  h->prof.mask = on > 0 ? 3u : 0u;   // both kernels, every on-th launch
+  h->prof.stride = on > 1 ? on : 1;
+  h->prof.count[0] = h->prof.count[1] = 0;
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_profile_read(knpemi_dg* h, int which, int64_t* launches, double* total_ms) {
-  if (!h || which < 0 || which > 1) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_profile_read: bad argument");
+  if (!h || which < 0 || which > 1) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_profile_read: bad argument");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
-  double tot = 0.0;
-  for (size_t i = 0; i + 1 < h->prof_used[which]; i += 2) {
-    float ms = 0.f;
-    KN_HIP(hipEventElapsedTime(&ms, h->prof_ev[which][i], h->prof_ev[which][i + 1]));
-    tot += ms;
-  }
-  if (launches) *launches = (int64_t)(h->prof_used[which] / 2);
-  if (total_ms) *total_ms = tot;
-  h->prof_used[which] = 0;
-  return KNPEMI_OK;
+  return kn_prof_read(h->prof, which, launches, total_ms);
 }
 
 // ---- membrane ODE sweep over the membrane nodes ------------------------------------------------------------------
 extern "C" int knpemi_dg_ode_bind(knpemi_dg* h, int model_id, int n_states, int n_params, const double* states,
                                   const double* params, const int32_t* ion_param, int v_index) {
-  if (!h || !states || !params || !ion_param) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: null argument");
+  if (!h || !states || !params || !ion_param) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: null argument");
   static const int ns_of[3] = {4, 4, 1}, np_of[3] = {22, 22, 23};
-  if (model_id < 0 || model_id > 2) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: unknown model id");
+  if (model_id < 0 || model_id > 2) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: unknown model id");
   if (n_states != ns_of[model_id] || n_params != np_of[model_id])
-    return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: state/parameter count does not match the model");
-  if (h->ode_model >= 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: model already bound");
-  if (v_index < 0 || v_index >= n_states) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: bad v_index");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: state/parameter count does not match the model");
+  if (h->ode_model >= 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: model already bound");
+  if (v_index < 0 || v_index >= n_states) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: bad v_index");
   for (int i = 0; i < 3 * h->K; ++i)
-    if (ion_param[i] < 0 || ion_param[i] >= n_params) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: parameter index out of range");
+    if (ion_param[i] < 0 || ion_param[i] >= n_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: parameter index out of range");
   KN_HIP(hipSetDevice(h->device));
   const int nq = h->dev.nq;
   int rc;
-  if ((rc = dg_alloc(h, (size_t)n_states * nq, &h->d_states))) return rc;
-  if ((rc = dg_alloc(h, (size_t)n_params * nq, &h->d_params))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_states * nq, &h->d_states))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_params * nq, &h->d_params))) return rc;
   h->ode_blocks = (int)(((size_t)nq * n_states + 63) / 64) + 1;
-  if ((rc = dg_alloc(h, 3 * (size_t)h->ode_blocks, &h->d_stats))) return rc;
-  std::vector<double> t((size_t)std::max(n_states, n_params) * std::max(nq, 1));
-  for (int pass = 0; pass < 2; ++pass) {
-    const int cols = pass ? n_params : n_states;
-    const double* src = pass ? params : states;
-    kn_transpose(src, t.data(), nq, cols);
-    if (nq) KN_HIP(hipMemcpy(pass ? h->d_params : h->d_states, t.data(), (size_t)cols * nq * sizeof(double), hipMemcpyHostToDevice));
-  }
-  if ((rc = kn_lsoda_coef_upload(&h->d_coef))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, 3 * (size_t)h->ode_blocks, &h->d_stats))) return rc;
+  if (nq && (rc = kn_table_upload(h->stream, states, h->d_states, nq, n_states))) return rc;
+  if (nq && (rc = kn_table_upload(h->stream, params, h->d_params, nq, n_params))) return rc;
+  if ((rc = kn_lsoda_coef_upload(h->allocs, &h->d_coef))) return rc;
   for (int i = 0; i < 3 * KN_MAXK; ++i) h->ode_ion_param[i] = i < 3 * h->K ? ion_param[i] : 0;
   h->ode_model = model_id; h->ode_ns = n_states; h->ode_np = n_params; h->ode_v = v_index;
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_ode_step(knpemi_dg* h, double t0, double dt, double rtol, double atol, int flags) {
-  if (!h || h->ode_model < 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_step: no membrane model bound");
+  if (!h || h->ode_model < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_step: no membrane model bound");
   if (h->dev.nq == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
   const DgDev& D = h->dev;
@@ -1641,23 +1538,18 @@ extern "C" int knpemi_dg_ode_step(knpemi_dg* h, double t0, double dt, double rto
 }
 
 extern "C" int knpemi_dg_ode_get_tables(knpemi_dg* h, double* states, double* params) {
-  if (!h || h->ode_model < 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_get_tables: no membrane model bound");
+  if (!h || h->ode_model < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_get_tables: no membrane model bound");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   const int nq = h->dev.nq;
-  std::vector<double> t((size_t)std::max(h->ode_ns, h->ode_np) * std::max(nq, 1));
-  for (int pass = 0; pass < 2; ++pass) {
-    double* dst = pass ? params : states;
-    if (!dst || !nq) continue;
-    const int cols = pass ? h->ode_np : h->ode_ns;
-    KN_HIP(hipMemcpy(t.data(), pass ? h->d_params : h->d_states, (size_t)cols * nq * sizeof(double), hipMemcpyDeviceToHost));
-    kn_transpose(t.data(), dst, cols, nq);
-  }
+  int rc;
+  if (states && nq && (rc = kn_table_download(h->stream, h->d_states, states, nq, h->ode_ns))) return rc;
+  if (params && nq && (rc = kn_table_download(h->stream, h->d_params, params, nq, h->ode_np))) return rc;
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_dg_ode_stats(knpemi_dg* h, int64_t* n_rhs, int64_t* n_steps, int64_t* n_failed) {
-  if (!h || h->ode_model < 0) return dg_fail(KNPEMI_EINVAL, "knpemi_dg_ode_stats: no membrane model bound");
+  if (!h || h->ode_model < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_stats: no membrane model bound");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   unsigned long long st[3];
@@ -1666,6 +1558,6 @@ extern "C" int knpemi_dg_ode_stats(knpemi_dg* h, int64_t* n_rhs, int64_t* n_step
   if (n_rhs) *n_rhs = (int64_t)st[0];
   if (n_steps) *n_steps = (int64_t)st[1];
   if (n_failed) *n_failed = (int64_t)st[2];
-  if (st[2]) return dg_fail(KNPEMI_EODE, kn_ode_failure(true, "at least one membrane node"));
+  if (st[2]) return kn_fail(KNPEMI_EODE, kn_ode_failure(true, "at least one membrane node"));
   return KNPEMI_OK;
 }

@@ -1341,15 +1341,6 @@ __global__ __launch_bounds__(DG_BLOCK, 2) void dg_knp_hex_box_kernel(DgDev D, co
   }
 }
 
-int hx_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    kn_set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return KNPEMI_EHIP;
-  }
-  return KNPEMI_OK;
-}
-
 }  // namespace
 
 int kn_dg_hex_launch_emi(hipStream_t st, const kn_dg::DgDev& D, const kn_dg::DgConsts* d_consts, int splitting, int box) {
@@ -1372,7 +1363,7 @@ int kn_dg_hex_launch_emi(hipStream_t st, const kn_dg::DgDev& D, const kn_dg::DgC
     (void)hipMemcpyToSymbol(HIP_SYMBOL(hx_stamp_acc), acc.data(), acc.size() * sizeof(unsigned long long));
   }
 #endif
-  return hx_check("dg_emi_hex_kernel");
+  return kn_launch_check("dg_emi_hex_kernel");
 }
 
 int kn_dg_hex_launch_knp(hipStream_t st, const kn_dg::DgDev& D, const kn_dg::DgConsts* d_consts, int KS, int splitting, int box) {
@@ -1384,12 +1375,12 @@ int kn_dg_hex_launch_knp(hipStream_t st, const kn_dg::DgDev& D, const kn_dg::DgC
       case 2: hipLaunchKernelGGL(dg_knp_hex_box_kernel<2>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
       default: hipLaunchKernelGGL(dg_knp_hex_box_kernel<3>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
     }
-    return hx_check("dg_knp_hex_box_kernel");
+    return kn_launch_check("dg_knp_hex_box_kernel");
   }
   switch (KS) {
     case 1: hipLaunchKernelGGL(dg_knp_hex_kernel<1>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
     case 2: hipLaunchKernelGGL(dg_knp_hex_kernel<2>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
     default: hipLaunchKernelGGL(dg_knp_hex_kernel<3>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
   }
-  return hx_check("dg_knp_hex_kernel");
+  return kn_launch_check("dg_knp_hex_kernel");
 }

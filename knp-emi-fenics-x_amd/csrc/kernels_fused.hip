@@ -827,9 +827,7 @@ int kn_fused_subcycle(knpemi_handle* h, KnAmg& G, int l0, const double* r0, doub
     a.red = red;
     hipLaunchKernelGGL((up_kernel<0>), dim3((int)(((size_t)L.n * LPR + FT - 1) / FT)), dim3(FT), 0, st, a);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("fused sub-cycle: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  return KNPEMI_OK;
+  return kn_launch_check("fused sub-cycle");
 }
 
 namespace {
@@ -838,11 +836,8 @@ namespace {
 int ensure_partials(knpemi_handle* h) {
   const size_t need = (size_t)P_N * KN_PB;
   if (h->fused_part_n >= need) return KNPEMI_OK;
-  void* p = nullptr;
-  KN_HIP(hipMalloc(&p, need * sizeof(double)));
-  h->allocs.push_back(p);
-  KN_HIP(hipMemsetAsync(p, 0, need * sizeof(double), h->stream));
-  h->fused_part = static_cast<double*>(p);
+  if (int rc = kn_alloc(h->allocs, need, &h->fused_part)) return rc;
+  KN_HIP(hipMemsetAsync(h->fused_part, 0, need * sizeof(double), h->stream));
   h->fused_part_n = need;
   return KNPEMI_OK;
 }
@@ -878,14 +873,9 @@ int ensure_publish(knpemi_handle* h, Publish* out) {
     std::memset(p, 0, 64 * sizeof(double));
     void* d = nullptr;
     KN_HIP(hipHostGetDevicePointer(&d, p, 0));
-    void* c = nullptr;
-    KN_HIP(hipMalloc(&c, sizeof(unsigned long long)));
-    h->allocs.push_back(c);
-    KN_HIP(hipMemsetAsync(c, 0, sizeof(unsigned long long), h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
+    if (int rc = kn_zeros(h->allocs, h->stream, 1, &h->pub_count)) return rc;
     h->pub_host = static_cast<double*>(p);
     h->pub_host_dev = static_cast<double*>(d);
-    h->pub_count = static_cast<unsigned long long*>(c);
     h->pub_expected = 0;
   }
   out->host_dev = h->pub_host_dev;
@@ -969,7 +959,7 @@ int first_chunk(int last_its, int maxit) {
 // problem (communication hooks): direct launches.
 bool graphs_usable(const knpemi_handle* h) {
   static const bool off = getenv("KNPEMI_NO_GRAPH") != nullptr || getenv("KNPEMI_FUSED_NO_GRAPH") != nullptr;
-  return !off && h->prof_mask == 0 && !h->dist.on;
+  return !off && h->prof.mask == 0 && !h->dist.on;
 }
 
 // Graph replay or direct launches?  Which is faster depends on the host: where a launch costs the host 4.4-5 us the ~45
@@ -1039,8 +1029,7 @@ int chunk_state(knpemi_handle* h, const KnFusedSys& S, double* sc, bool publishe
 
 // End of a fused solve: launch errors, the size of the next solve's first chunk, the caller's outputs
 int finish_solve(KnAmg& G, const double* sc, int it, const char* what, int* iters, double* rr_out, double* bb_out) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string(what) + ": " + hipGetErrorString(e)); return KNPEMI_EHIP; }
+  if (int rc = kn_launch_check(what)) return rc;
   G.its_last = it;
   *iters = it;
   *rr_out = sc[S_RR];
@@ -1394,20 +1383,15 @@ __global__ __launch_bounds__(FT) void gm_update_kernel(int n, double* __restrict
 
 int ensure_gmres(knpemi_handle* h, size_t n, GmState* out) {
   const size_t need = (size_t)GM_M * n;
+  int rc;
   if (h->gm_n < need) {
-    void* p = nullptr;
-    KN_HIP(hipMalloc(&p, need * sizeof(double)));
-    h->allocs.push_back(p);
-    h->gm_V = static_cast<double*>(p);
+    if ((rc = kn_alloc(h->allocs, need, &h->gm_V))) return rc;
     h->gm_n = need;
   }
   if (!h->gm_state) {
-    void* p = nullptr;
     const size_t doubles = GM_N + (size_t)(GM_M + 1) * KN_PB;
-    KN_HIP(hipMalloc(&p, doubles * sizeof(double)));
-    h->allocs.push_back(p);
-    KN_HIP(hipMemsetAsync(p, 0, doubles * sizeof(double), h->stream));
-    h->gm_state = static_cast<double*>(p);
+    if ((rc = kn_alloc(h->allocs, doubles, &h->gm_state))) return rc;
+    KN_HIP(hipMemsetAsync(h->gm_state, 0, doubles * sizeof(double), h->stream));
   }
   out->gm = h->gm_state;
   out->dots = h->gm_state + GM_N;

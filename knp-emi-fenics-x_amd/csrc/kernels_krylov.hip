@@ -558,17 +558,11 @@ void kn_solver_free(knpemi_handle* h) {
 // Workspace: 10 vectors of the larger system + ones + scalars + partials (allocated on first use).
 static int ensure_work(knpemi_handle* h, size_t n) {
   if (h->kry_n >= n) return KNPEMI_OK;
-  void* p = nullptr;
   const size_t doubles = 11 * n + 64 + 3 * RED_BLOCKS + 2;   // + ticket counter of dots_kernel
-  KN_HIP(hipMalloc(&p, doubles * sizeof(double)));
-  h->allocs.push_back(p);
-  KN_HIP(hipMemsetAsync(p, 0, doubles * sizeof(double), h->stream));
-  h->kry = static_cast<double*>(p);
+  if (int rc = kn_zeros(h->allocs, h->stream, doubles, &h->kry)) return rc;
   h->kry_n = n;
-  std::vector<double> ones(n, 1.0);
-  KN_HIP(hipMemcpyAsync(h->kry + 10 * n, ones.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  const std::vector<double> ones(n, 1.0);
+  return kn_to_device(h->stream, h->kry + 10 * n, ones.data(), n);
 }
 
 // r_c = Phi^T r into the reduction buffer (all-reduced): every rank ends up with the whole coarse vector
@@ -588,9 +582,9 @@ static int coarse_setup(Ctx& c, double* work_phi, double* work_y) {
   KnDist& d = h->dist;
   const int nc = d.nc, nl = d.nl;
   if (!d.d_coarse_inv) {
-    void* p = nullptr;
-    KN_HIP(hipMalloc(&p, (size_t)KN_COARSE_MAX * KN_COARSE_MAX * sizeof(double))); h->allocs.push_back(p); d.d_coarse_inv = static_cast<double*>(p);
-    KN_HIP(hipMalloc(&p, (KN_COARSE_MAX + 1) * sizeof(double))); h->allocs.push_back(p); d.d_coarse_z = static_cast<double*>(p);
+    int rc;
+    if ((rc = kn_alloc(h->allocs, (size_t)KN_COARSE_MAX * KN_COARSE_MAX, &d.d_coarse_inv))) return rc;
+    if ((rc = kn_alloc(h->allocs, KN_COARSE_MAX + 1, &d.d_coarse_z))) return rc;
     // (KNPEMI_DEBUG_POISON_COARSE: all-ones bytes = NaN, for the test that no entry past the nl written ones is read)
     KN_HIP(hipMemset(d.d_coarse_z, getenv("KNPEMI_DEBUG_POISON_COARSE") ? 0xFF : 0, (KN_COARSE_MAX + 1) * sizeof(double)));
   }
@@ -602,8 +596,7 @@ static int coarse_setup(Ctx& c, double* work_phi, double* work_y) {
                        (const double*)nullptr, work_phi, 1, rj == d.rank ? aj : -2);
     spmv(c, work_phi, work_y, nullptr);
     coarse_restrict(c, work_y);
-    KN_HIP(hipMemcpyAsync(col.data(), d.d_red + KN_COARSE_OFF, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
+    if (int rc = kn_to_host(h->stream, col.data(), d.d_red + KN_COARSE_OFF, nc)) return rc;
     if (c.comm_rc) { kn_set_error("coarse space set-up: a communication hook failed"); return KNPEMI_EHIP; }
     for (int i = 0; i < nc; ++i) Ac[(size_t)i * nc + j] = col[i];
   }
@@ -779,8 +772,7 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   if (c.comm_rc) { kn_set_error("EMI solve: a communication hook failed"); return KNPEMI_EHIP; }
   if (iters) *iters = it;
   if (relres) *relres = bnorm > 0 ? rn / bnorm : rn;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("krylov (emi): ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+  if ((rc = kn_launch_check("krylov (emi)"))) return rc;
   if (amg) amg_age(h, G, it);
   if (rn > target) { kn_set_error("EMI CG did not converge (ksp_error_if_not_converged)"); return KNPEMI_ESOLVE; }
   return KNPEMI_OK;
@@ -909,8 +901,7 @@ int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   if (!fused && (rc = post())) return rc;
   if (iters) *iters = it;
   if (relres) *relres = bnorm > 0 ? rn / bnorm : rn;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("krylov (knp): ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
+  if ((rc = kn_launch_check("krylov (knp)"))) return rc;
   if (amg) amg_age(h, G, it);
   if (rn > target) { kn_set_error("KNP BiCGStab did not converge (ksp_error_if_not_converged)"); return KNPEMI_ESOLVE; }
   return KNPEMI_OK;
@@ -923,9 +914,7 @@ int kn_launch_knp_order(knpemi_handle* h, double* x, int to_blocks) {
   if (n == 0) return KNPEMI_OK;
   hipLaunchKernelGGL(knp_order_kernel, grid1(n), dim3(256), 0, h->stream, D.Ntot, h->K - 1, h->n_sub, h->d_consts, x, D.csol,
                      to_blocks);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("knp_order_kernel: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  return KNPEMI_OK;
+  return kn_launch_check("knp_order_kernel");
 }
 
 // Initial guess of the next solve: instead of the previous solution (ksp_initial_guess_nonzero) the extrapolation of the
@@ -940,10 +929,7 @@ int kn_extrapolate_guess(knpemi_handle* h, int which) {
   // cell fires at config 2, 3.5 instead of 3.8 over the first 72 steps; KNPEMI_EXTRAPOLATE_ORDER=1: 2 x_n - x_(n-1)
   static const int order = getenv("KNPEMI_EXTRAPOLATE_ORDER") ? atoi(getenv("KNPEMI_EXTRAPOLATE_ORDER")) : 2;
   if (!h->guess_old[slot]) {
-    void* p = nullptr;
-    KN_HIP(hipMalloc(&p, 2 * (size_t)n * sizeof(double)));
-    h->allocs.push_back(p);
-    h->guess_old[slot] = static_cast<double*>(p);
+    if (int rc = kn_alloc(h->allocs, 2 * (size_t)n, &h->guess_old[slot])) return rc;
     h->guess_have[slot] = slot == 0 ? -1 : 0;
   }
   // the potential a run starts with is a guess, not a solution of the system (the concentrations it starts with are the
@@ -954,7 +940,5 @@ int kn_extrapolate_guess(knpemi_handle* h, int which) {
   hipLaunchKernelGGL(extrapolate_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, cur, slot == 0 ? KN_REC : 1,
                      h->guess_old[slot], order >= 2 ? h->guess_old[slot] + n : (double*)nullptr, h->guess_have[slot]);
   h->guess_have[slot] = std::min(2, h->guess_have[slot] + 1);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { kn_set_error(std::string("extrapolate_kernel: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
-  return KNPEMI_OK;
+  return kn_launch_check("extrapolate_kernel");
 }

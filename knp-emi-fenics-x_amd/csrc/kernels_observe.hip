@@ -28,15 +28,6 @@
 
 namespace {
 
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    kn_set_error(std::string(what) + ": " + hipGetErrorString(e));
-    return KNPEMI_EHIP;
-  }
-  return KNPEMI_OK;
-}
-
 struct ObsArgs {
   int n_obs, capacity, n_blk;
   const int4* blk;
@@ -167,14 +158,14 @@ int kn_launch_observe(knpemi_handle* h) {
   ObsArgs a{O.n_obs, O.capacity, O.n_blk, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ctl,
             O.rows, O.xbuf ? O.xbuf + (size_t)O.rank * O.n_obs : nullptr};
   hipLaunchKernelGGL(observe_kernel, dim3(std::max(O.n_blk, 1)), dim3(OBS_THREADS), 0, h->stream, a);
-  return check_launch("observe_kernel");
+  return kn_launch_check("observe_kernel");
 }
 
 int kn_launch_observe_combine(knpemi_handle* h) {
   const auto& O = h->obs;
   ObsCombineArgs a{O.n_obs, O.capacity, O.world, O.rank, O.op, O.denom, O.xbuf, O.ctl, O.rows};
   hipLaunchKernelGGL(observe_combine_kernel, dim3(1), dim3(OBS_THREADS), 0, h->stream, a);
-  return check_launch("observe_combine_kernel");
+  return kn_launch_check("observe_combine_kernel");
 }
 
 int kn_observe_chunk() { return OBS_CHUNK; }

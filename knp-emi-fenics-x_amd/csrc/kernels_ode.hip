@@ -126,27 +126,18 @@ int launch_sweep(knpemi_handle* h, const KnOdeModel& m, const OdeArgs& a, const 
 
 // the handle's copy of the LSODA coefficient tables, uploaded on first use
 int lsoda_coef(knpemi_handle* h, const LsodaCoef** out) {
-  if (!h->d_lsoda_coef) {
-    void* d = nullptr;
-    const int rc = kn_lsoda_coef_upload(&d);
-    if (rc) return rc;
-    h->allocs.push_back(d);
-    h->d_lsoda_coef = d;
-  }
+  if (!h->d_lsoda_coef)
+    if (int rc = kn_lsoda_coef_upload(h->allocs, &h->d_lsoda_coef)) return rc;
   *out = static_cast<const LsodaCoef*>(h->d_lsoda_coef);
   return KNPEMI_OK;
 }
 
 }  // namespace
 
-int kn_lsoda_coef_upload(void** out) {
+int kn_lsoda_coef_upload(std::vector<void*>& owner, const void** out) {
   LsodaCoef c;
   lsoda_fill_coef(&c);
-  void* d = nullptr;
-  KN_HIP(hipMalloc(&d, sizeof(LsodaCoef)));
-  KN_HIP(hipMemcpy(d, &c, sizeof(LsodaCoef), hipMemcpyHostToDevice));
-  *out = d;
-  return KNPEMI_OK;
+  return kn_upload(owner, &c, 1, out);
 }
 
 // ---- one PDE step per launch (knpemi_ode_step) -------------------------------------------------------------------
@@ -161,17 +152,12 @@ int kn_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, d
   // only the LSODA kernels of the shipped models have one
   static const bool want_stamps = getenv("KNPEMI_ODE_STAMPS") != nullptr;
   if (want_stamps && m.method == KNPEMI_ODE_LSODA && !m.rtc_module) {
-    if (!m.d_stamps) {
-      void* d = nullptr;
-      KN_HIP(hipMalloc(&d, 24 * sizeof(unsigned long long) * (size_t)m.n_stat_blocks));
-      h->allocs.push_back(d);
-      m.d_stamps = static_cast<unsigned long long*>(d);
-    }
+    if (!m.d_stamps && (rc = kn_alloc(h->allocs, 24 * (size_t)m.n_stat_blocks, &m.d_stamps))) return rc;
     a.stamps = m.d_stamps;
   }
   // counters accumulate over launches; knpemi_ode_stats() reads and resets them.  One profiling slot whatever the
   // integrator: it is "the ODE kernel" of the step for DeviceStepper's stream choice
-  KnProfScope prof(h, KNPEMI_K_ODE);
+  KnProfScope prof(h->prof, KNPEMI_K_ODE, h->cur);
   return launch_sweep(h, m, a, nullptr, cf);
 }
 
@@ -201,12 +187,7 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   int rc = KNPEMI_OK;
   if (lsoda && (rc = lsoda_coef(h, &cf))) return rc;
   const size_t nq = (size_t)m.nq;
-  if (!m.d_adv) {   // still-step counters, steps_taken, failed_step
-    void* d = nullptr;
-    KN_HIP(hipMalloc(&d, 3 * nq * sizeof(int)));
-    h->allocs.push_back(d);
-    m.d_adv = static_cast<int*>(d);
-  }
+  if (!m.d_adv && (rc = kn_alloc(h->allocs, 3 * nq, &m.d_adv))) return rc;   // still-step counters, steps_taken, failed_step
   OdeArgs a = model_args(h, slot, t0, dt, rtol, atol, nullptr);
   OdeAdvArgs v{};
   v.n_rec = history ? n_rec : 0;
@@ -257,8 +238,7 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   m.adv_chunk = chunk;
   if (n_hist) KN_HIP(hipMemcpyAsync(history, hist.p, n_hist * sizeof(double), hipMemcpyDeviceToHost, h->cur));
   std::vector<int32_t> flags(2 * nq);
-  KN_HIP(hipMemcpyAsync(flags.data(), v.steps_taken, 2 * nq * sizeof(int32_t), hipMemcpyDeviceToHost, h->cur));
-  KN_HIP(hipStreamSynchronize(h->cur));
+  if ((rc = kn_to_host(h->cur, flags.data(), v.steps_taken, 2 * nq))) return rc;
   if (steps_taken) std::copy(flags.begin(), flags.begin() + nq, steps_taken);
   if (failed_step) std::copy(flags.begin() + nq, flags.end(), failed_step);
   size_t n_failed = 0;
@@ -307,7 +287,7 @@ extern "C" int knpemi_debug_math(int op, int n, const double* a, const double* b
   check(hipMemcpy(d + n, (op == 1 || op == 3) ? a : b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
   if (rc == KNPEMI_OK) {
     hipLaunchKernelGGL(debug_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, n, d, d + n, d + 2 * (size_t)n);
-    check(hipGetLastError());
+    if (kn_launch_check("debug_math_kernel")) rc = KNPEMI_EHIP;
     check(hipMemcpy(out, d + 2 * (size_t)n, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   }
   (void)hipFree(d);

@@ -23,39 +23,6 @@ extern "C" int knpemi_device_count(void) {
   return n;
 }
 
-namespace {
-
-template <class T>
-int dev_upload(knpemi_handle* h, const std::vector<T>& v, const T** out) {
-  void* p = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  KN_HIP(hipMalloc(&p, bytes));
-  h->allocs.push_back(p);
-  if (!v.empty()) KN_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  *out = static_cast<const T*>(p);
-  return 0;
-}
-
-template <class T>
-int dev_zeros(knpemi_handle* h, size_t n, T** out) {
-  void* p = nullptr;
-  size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-  KN_HIP(hipMalloc(&p, bytes));
-  h->allocs.push_back(p);
-  // zero on the handle's own (non-blocking) stream: a null-stream hipMemset is not ordered with it
-  KN_HIP(hipMemsetAsync(p, 0, bytes, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  *out = static_cast<T*>(p);
-  return 0;
-}
-
-int fail(int code, const std::string& msg) {
-  kn_set_error(msg);
-  return code;
-}
-
-}  // namespace
-
 // Degree-6 rules on the membrane facet (UFL estimates degree 6 for the
 // rational KNP coupling integrand; Basix would pick Gauss-Jacobi with 4 points per direction on
 // intervals/quadrilaterals and the 12-point Xiao-Gimbutas rule on triangles).  Layout: nq weights
@@ -104,28 +71,21 @@ int kn_gamma_quadrature(int NF, std::vector<double>* out) {
 }
 
 extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_handle** out) {
-  if (!d || !out) return fail(KNPEMI_EINVAL, "knpemi_create: null argument");
+  if (!d || !out) return kn_fail(KNPEMI_EINVAL, "knpemi_create: null argument");
   *out = nullptr;
   if (d->n_ions < 2 || d->n_ions > KN_MAXK)
-    return fail(KNPEMI_EINVAL, "knpemi_create: 2 to 4 ionic species (the last one eliminated) are supported; the "
+    return kn_fail(KNPEMI_EINVAL, "knpemi_create: 2 to 4 ionic species (the last one eliminated) are supported; the "
                                "reference drivers use 3 (run_3D.py:256)");
-  if (d->n_sub < 1 || d->n_sub > KN_MAXSUB) return fail(KNPEMI_EINVAL, "knpemi_create: bad n_sub");
+  if (d->n_sub < 1 || d->n_sub > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, "knpemi_create: bad n_sub");
   int NV, NF;
   if (d->cell_kind == KNPEMI_TRIANGLE && d->gdim == 2) { NV = 3; NF = 2; }
   else if (d->cell_kind == KNPEMI_TETRAHEDRON && d->gdim == 3) { NV = 4; NF = 3; }
   else if (d->cell_kind == KNPEMI_HEXAHEDRON && d->gdim == 3) { NV = 8; NF = 4; }
-  else return fail(KNPEMI_EINVAL, "knpemi_create: cell_kind/gdim combination not supported");
-
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(KNPEMI_EHIP, "knpemi_create: no HIP device visible (the hot path has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(KNPEMI_EINVAL, "knpemi_create: bad device index");
-  KN_HIP(hipSetDevice(device));
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_create: cell_kind/gdim combination not supported");
 
   auto* h = new knpemi_handle();
   std::unique_ptr<knpemi_handle, void (*)(knpemi_handle*)> guard(h, knpemi_destroy);
-  h->device = device;
-  KN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  if (int rc = kn_device_open(h, device, "knpemi_create")) return rc;
   KN_HIP(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
   KN_HIP(hipStreamCreateWithFlags(&h->aux2, hipStreamNonBlocking));
   KN_HIP(hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming));
@@ -134,8 +94,6 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   h->cur = h->stream;
   KN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   KN_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  KN_HIP(hipEventCreate(&h->ev0));
-  KN_HIP(hipEventCreate(&h->ev1));
   h->gdim = d->gdim; h->cell_kind = d->cell_kind; h->NV = NV; h->NF = NF;
   h->n_sub = d->n_sub; h->K = d->n_ions;
   const int S = d->n_sub, K = d->n_ions;
@@ -146,7 +104,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
     h->n_q[s] = d->n_q ? d->n_q[s] : 0;
     h->n_facet[s] = d->n_facet ? d->n_facet[s] : 0;
     h->n_models[s] = d->n_models ? d->n_models[s] : 0;
-    if (h->n_models[s] > KNPEMI_MAX_MODELS) return fail(KNPEMI_EINVAL, "too many membrane models");
+    if (h->n_models[s] > KNPEMI_MAX_MODELS) return kn_fail(KNPEMI_EINVAL, "too many membrane models");
   }
   auto prefix = [&](const std::vector<int>& n) {
     std::vector<int> o(S + 1, 0);
@@ -164,7 +122,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   for (int s = 0; s < S; ++s) {
     for (int64_t i = 0; i < (int64_t)h->n_cell[s] * NV; ++i) {
       int v = d->cells[s][i];
-      if (v < 0 || v >= h->n_vert[s]) return fail(KNPEMI_EINVAL, "cell vertex id out of range");
+      if (v < 0 || v >= h->n_vert[s]) return kn_fail(KNPEMI_EINVAL, "cell vertex id out of range");
       cells[(size_t)h->coff[s] * NV + i] = v + h->voff[s];
     }
     for (int v = 0; v < h->n_vert[s]; ++v)
@@ -199,7 +157,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
       std::sort(tmp.begin(), tmp.end());
       tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
       colindL.insert(colindL.end(), tmp.begin(), tmp.end());
-      if (colindL.size() > (size_t)INT32_MAX) return fail(KNPEMI_EINVAL, "matrix too large for int32 CSR");
+      if (colindL.size() > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, "matrix too large for int32 CSR");
       rowptrL[g + 1] = (int)colindL.size();
     }
   }
@@ -217,13 +175,13 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
     for (int f = 0; f < h->n_facet[s]; ++f) {
       int fg = h->foff[s] + f;
       int m = d->facet_model ? d->facet_model[s][f] : -1;
-      if (m >= h->n_models[s]) return fail(KNPEMI_EINVAL, "facet_model out of range");
+      if (m >= h->n_models[s]) return kn_fail(KNPEMI_EINVAL, "facet_model out of range");
       fmodel[fg] = m < 0 ? -1 : h->moff[s] + m;
       for (int a = 0; a < NF; ++a) {
         int e = d->facet_e[s][(size_t)f * NF + a], i = d->facet_i[s][(size_t)f * NF + a];
         int q = d->facet_q[s][(size_t)f * NF + a];
         if (e < 0 || e >= h->n_vert[0] || i < 0 || i >= h->n_vert[s] || q < 0 || q >= h->n_q[s])
-          return fail(KNPEMI_EINVAL, "membrane facet index out of range");
+          return kn_fail(KNPEMI_EINVAL, "membrane facet index out of range");
         fe[(size_t)fg * NF + a] = e + h->voff[0];
         fi[(size_t)fg * NF + a] = i + h->voff[s];
         fq[(size_t)fg * NF + a] = q + h->qoff[s];
@@ -258,9 +216,9 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
       if (!ecs) for (size_t c = c0; c < cp; ++c) colind.push_back(coup[c].second);
       colind.insert(colind.end(), colindL.begin() + rowptrL[g], colindL.begin() + rowptrL[g + 1]);
       if (ecs) for (size_t c = c0; c < cp; ++c) colind.push_back(coup[c].second);
-      if (colind.size() > (size_t)INT32_MAX) return fail(KNPEMI_EINVAL, "matrix too large for int32 CSR");
+      if (colind.size() > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, "matrix too large for int32 CSR");
       rowptr[g + 1] = (int)colind.size();
-      if (rowptr[g + 1] - rowptr[g] > 255) return fail(KNPEMI_EINVAL, "matrix row longer than 255 entries");
+      if (rowptr[g + 1] - rowptr[g] > 255) return kn_fail(KNPEMI_EINVAL, "matrix row longer than 255 entries");
       lapoff[g] = (uint8_t)(ecs ? 0 : nco);
     }
   }
@@ -771,7 +729,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
           const int ne = m < 0 ? 0 : mptr[m + 1] - mptr[m];
           ri[0] = offE + (rowptr[g] - rowptr[g0]);
           ri[1] = ri[0] + lapoff[g];
-          if (ri[1] > 0xFFFF || ne > 0x7FFF) return fail(KNPEMI_EINVAL, "row block too large for the packed row descriptor");
+          if (ri[1] > 0xFFFF || ne > 0x7FFF) return kn_fail(KNPEMI_EINVAL, "row block too large for the packed row descriptor");
           ri[1] |= ne << 16;
           ri[2] = offL + (rowptrL[g] - rowptrL[g0]);
           ri[3] = m < 0 ? 0 : mptr[m];
@@ -791,7 +749,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
     for (int w = 0; w < SPB; ++w) {
       bi[8 + w] = (int)(sl_ptr[(size_t)b * SPB + w] / KN_SLICE);
       const int64_t np = (sl_ptr[(size_t)b * SPB + w + 1] - sl_ptr[(size_t)b * SPB + w]) / KN_SLICE;
-      if (np > 255) return fail(KNPEMI_EINVAL, "a vertex has too many incident cells for the pair layout");
+      if (np > 255) return kn_fail(KNPEMI_EINVAL, "a vertex has too many incident cells for the pair layout");
       steps |= (uint32_t)np << (8 * w);
     }
     bi[12] = (int)steps;
@@ -816,16 +774,16 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
       std::vector<int> ordered(u);
       std::sort(u.begin(), u.end());
       u.erase(std::unique(u.begin(), u.end()), u.end());
-      if (u.size() > 65535) return fail(KNPEMI_EINVAL, "row block touches more than 65535 vertices");
+      if (u.size() > 65535) return kn_fail(KNPEMI_EINVAL, "row block touches more than 65535 vertices");
       bi[7] = (int)blk_uverts.size();
       bi[13] = (int)u.size();
       h->lds_uniq_max = std::max(h->lds_uniq_max, (int)u.size());
       for (size_t i = 0; i < ordered.size(); ++i)
         ent_loc[ent_base + i] = (uint16_t)(std::lower_bound(u.begin(), u.end(), ordered[i]) - u.begin());
       ent_base += ordered.size();
-      if (ent_base > (size_t)INT32_MAX) return fail(KNPEMI_EINVAL, "mesh too large for int32 block lists");
+      if (ent_base > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, "mesh too large for int32 block lists");
       blk_uverts.insert(blk_uverts.end(), u.begin(), u.end());
-      if (blk_uverts.size() > (size_t)INT32_MAX) return fail(KNPEMI_EINVAL, "mesh too large for int32 block lists");
+      if (blk_uverts.size() > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, "mesh too large for int32 block lists");
     }
     h->lds_doubles_emi = std::max(h->lds_doubles_emi, offE);
     h->lds_doubles_knp = std::max(h->lds_doubles_knp, offL);
@@ -857,57 +815,57 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   D.nnz = (int64_t)colind.size(); D.nnzL = (int64_t)colindL.size();
   int rc;
   const double* vr_c = nullptr;
-  if ((rc = dev_upload(h, VR, &vr_c))) return rc;
+  if ((rc = kn_upload(h->allocs, VR, &vr_c))) return rc;
   D.VR = const_cast<double*>(vr_c);
-  if ((rc = dev_upload(h, cells, &D.cells))) return rc;
-  if ((rc = dev_upload(h, blk_rng, &D.blk_rng))) return rc;
-  if ((rc = dev_upload(h, blk_sub, &D.blk_sub))) return rc;
+  if ((rc = kn_upload(h->allocs, cells, &D.cells))) return rc;
+  if ((rc = kn_upload(h->allocs, blk_rng, &D.blk_rng))) return rc;
+  if ((rc = kn_upload(h->allocs, blk_sub, &D.blk_sub))) return rc;
   {
     const int* bi = nullptr; const int* ri = nullptr;
-    if ((rc = dev_upload(h, blk_info, &bi))) return rc;
-    if ((rc = dev_upload(h, row_info, &ri))) return rc;
+    if ((rc = kn_upload(h->allocs, blk_info, &bi))) return rc;
+    if ((rc = kn_upload(h->allocs, row_info, &ri))) return rc;
     D.blk_info = reinterpret_cast<const int4*>(bi);
-    if ((rc = dev_upload(h, blk_uverts, &D.blk_uverts))) return rc;
-    if ((rc = dev_upload(h, ent_loc, &D.ent_loc))) return rc;
+    if ((rc = kn_upload(h->allocs, blk_uverts, &D.blk_uverts))) return rc;
+    if ((rc = kn_upload(h->allocs, ent_loc, &D.ent_loc))) return rc;
     D.row_info = reinterpret_cast<const int4*>(ri);
   }
-  if ((rc = dev_upload(h, sl_ptr, &D.sl_ptr))) return rc;
-  if ((rc = dev_upload(h, pair_sl, &D.pair_sl))) return rc;
+  if ((rc = kn_upload(h->allocs, sl_ptr, &D.sl_ptr))) return rc;
+  if ((rc = kn_upload(h->allocs, pair_sl, &D.pair_sl))) return rc;
   D.tet_tab = nullptr;
-  if (h->tet_uniform && (rc = dev_upload(h, tet_tab, &D.tet_tab))) return rc;
-  if ((rc = dev_upload(h, pair_cell, &D.pair_cell))) return rc;
-  if ((rc = dev_upload(h, pair_slots, &D.pair_slots))) return rc;
-  if ((rc = dev_upload(h, rowptr, &D.rowptr))) return rc;
-  if ((rc = dev_upload(h, colind, &D.colind))) return rc;
-  if ((rc = dev_upload(h, lapoff, &D.lapoff))) return rc;
-  if ((rc = dev_upload(h, rowptrL, &D.rowptrL))) return rc;
-  if ((rc = dev_upload(h, colindL, &D.colindL))) return rc;
-  if ((rc = dev_upload(h, mptr, &D.mptr))) return rc;
-  if ((rc = dev_upload(h, mentry, &D.mentry))) return rc;
-  if ((rc = dev_upload(h, mslots, &D.mslots))) return rc;
-  if ((rc = dev_upload(h, mrow, &D.mrow))) return rc;
-  if ((rc = dev_upload(h, me_model, &D.me_model))) return rc;
-  if ((rc = dev_upload(h, me_q, &D.me_q))) return rc;
-  if ((rc = dev_upload(h, gam_pos, &D.gam_pos))) return rc;
-  if ((rc = dev_upload(h, pmass, &D.P_mass))) return rc;
+  if (h->tet_uniform && (rc = kn_upload(h->allocs, tet_tab, &D.tet_tab))) return rc;
+  if ((rc = kn_upload(h->allocs, pair_cell, &D.pair_cell))) return rc;
+  if ((rc = kn_upload(h->allocs, pair_slots, &D.pair_slots))) return rc;
+  if ((rc = kn_upload(h->allocs, rowptr, &D.rowptr))) return rc;
+  if ((rc = kn_upload(h->allocs, colind, &D.colind))) return rc;
+  if ((rc = kn_upload(h->allocs, lapoff, &D.lapoff))) return rc;
+  if ((rc = kn_upload(h->allocs, rowptrL, &D.rowptrL))) return rc;
+  if ((rc = kn_upload(h->allocs, colindL, &D.colindL))) return rc;
+  if ((rc = kn_upload(h->allocs, mptr, &D.mptr))) return rc;
+  if ((rc = kn_upload(h->allocs, mentry, &D.mentry))) return rc;
+  if ((rc = kn_upload(h->allocs, mslots, &D.mslots))) return rc;
+  if ((rc = kn_upload(h->allocs, mrow, &D.mrow))) return rc;
+  if ((rc = kn_upload(h->allocs, me_model, &D.me_model))) return rc;
+  if ((rc = kn_upload(h->allocs, me_q, &D.me_q))) return rc;
+  if ((rc = kn_upload(h->allocs, gam_pos, &D.gam_pos))) return rc;
+  if ((rc = kn_upload(h->allocs, pmass, &D.P_mass))) return rc;
   D.pmass0 = pmass0;
-  if ((rc = dev_upload(h, fe, &D.fe))) return rc;
-  if ((rc = dev_upload(h, fi, &D.fi))) return rc;
-  if ((rc = dev_upload(h, fq, &D.fq))) return rc;
-  if ((rc = dev_upload(h, fmodel, &D.fmodel))) return rc;
-  if ((rc = dev_upload(h, q2e, &D.q2e))) return rc;
-  if ((rc = dev_upload(h, q2i, &D.q2i))) return rc;
-  if ((rc = dev_zeros(h, (size_t)(K - 1) * Ntot, &D.csol))) return rc;
+  if ((rc = kn_upload(h->allocs, fe, &D.fe))) return rc;
+  if ((rc = kn_upload(h->allocs, fi, &D.fi))) return rc;
+  if ((rc = kn_upload(h->allocs, fq, &D.fq))) return rc;
+  if ((rc = kn_upload(h->allocs, fmodel, &D.fmodel))) return rc;
+  if ((rc = kn_upload(h->allocs, q2e, &D.q2e))) return rc;
+  if ((rc = kn_upload(h->allocs, q2i, &D.q2i))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)(K - 1) * Ntot, &D.csol))) return rc;
   D.fsrc = nullptr;
-  if ((rc = dev_zeros(h, (size_t)D.nnz, &D.A_emi))) return rc;
-  if ((rc = dev_zeros(h, (size_t)D.nnz, &D.P_emi))) return rc;
-  if ((rc = dev_zeros(h, (size_t)Ntot, &D.b_emi))) return rc;
-  if ((rc = dev_zeros(h, (size_t)(K - 1) * D.nnzL, &D.A_knp))) return rc;
-  if ((rc = dev_zeros(h, (size_t)(K - 1) * Ntot, &D.b_knp))) return rc;
-  if ((rc = dev_zeros(h, (size_t)NQtot, &D.phiM))) return rc;
-  if ((rc = dev_zeros(h, std::max<size_t>(1, mentry.size()) * (size_t)(K - 1), &D.gam_e))) return rc;
-  if ((rc = dev_zeros(h, std::max<size_t>(1, mentry.size()) * (size_t)(K - 1) * (1 + NF), &D.gpre))) return rc;
-  if ((rc = dev_zeros(h, (size_t)std::max(1, h->moff[S]) * KN_MAXK * std::max(1, NQtot), &D.Ich))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)D.nnz, &D.A_emi))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)D.nnz, &D.P_emi))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)Ntot, &D.b_emi))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)(K - 1) * D.nnzL, &D.A_knp))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)(K - 1) * Ntot, &D.b_knp))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)NQtot, &D.phiM))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, std::max<size_t>(1, mentry.size()) * (size_t)(K - 1), &D.gam_e))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, std::max<size_t>(1, mentry.size()) * (size_t)(K - 1) * (1 + NF), &D.gpre))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)std::max(1, h->moff[S]) * KN_MAXK * std::max(1, NQtot), &D.Ich))) return rc;
   {
     std::vector<int> krp((size_t)(K - 1) * Ntot + 1, 0), kci((size_t)(K - 1) * colindL.size());
     int64_t row = 0, pos = 0;
@@ -921,25 +879,25 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
         }
       }
     }
-    if ((rc = dev_upload(h, krp, &D.krowptr))) return rc;
-    if ((rc = dev_upload(h, kci, &D.kcolind))) return rc;
+    if ((rc = kn_upload(h->allocs, krp, &D.krowptr))) return rc;
+    if ((rc = kn_upload(h->allocs, kci, &D.kcolind))) return rc;
   }
   h->stage_len = (size_t)std::max(Ntot, 1) * (K - 1) + 2 * (size_t)std::max(NQtot, 1);
-  if ((rc = dev_zeros(h, h->stage_len, &h->d_stage))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, h->stage_len, &h->d_stage))) return rc;
 
   {
     std::vector<double> qt;
     D.nq_gamma = kn_gamma_quadrature(NF, &qt);
-    if ((rc = dev_upload(h, qt, &D.qtab))) return rc;
+    if ((rc = kn_upload(h->allocs, qt, &D.qtab))) return rc;
   }
 
   {   // facet-mass rows of the membrane entries: static geometry, computed once by the device code the kernels share
     const int n_entries = (int)mentry.size();
     double* mass = nullptr;
-    if ((rc = dev_zeros(h, std::max<size_t>(1, (size_t)n_entries * NF), &mass))) return rc;
+    if ((rc = kn_zeros(h->allocs, h->stream, std::max<size_t>(1, (size_t)n_entries * NF), &mass))) return rc;
     D.me_mass = mass;
     const int* d_rows = nullptr;
-    if ((rc = dev_upload(h, me_row, &d_rows))) return rc;
+    if ((rc = kn_upload(h->allocs, me_row, &d_rows))) return rc;
     if ((rc = kn_launch_membrane_mass(h, n_entries, d_rows, mass))) return rc;
     KN_HIP(hipStreamSynchronize(h->stream));
   }
@@ -955,29 +913,21 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
 }
 
 extern "C" int knpemi_ode_create(int device, int n_models, const int32_t* nq, knpemi_handle** out) {
-  if (!out || !nq) return fail(KNPEMI_EINVAL, "knpemi_ode_create: null argument");
+  if (!out || !nq) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_create: null argument");
   *out = nullptr;
   if (n_models < 1 || n_models > KN_MAXSUB - 1)
-    return fail(KNPEMI_EINVAL, "knpemi_ode_create: 1 to KNPEMI_MAX_SUB - 1 membrane models");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_create: 1 to KNPEMI_MAX_SUB - 1 membrane models");
   for (int i = 0; i < n_models; ++i)
-    if (nq[i] < 0) return fail(KNPEMI_EINVAL, "knpemi_ode_create: negative dof count");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(KNPEMI_EHIP, "knpemi_ode_create: no HIP device visible (the hot path has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail(KNPEMI_EINVAL, "knpemi_ode_create: bad device index");
-  KN_HIP(hipSetDevice(device));
+    if (nq[i] < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_create: negative dof count");
   auto* h = new knpemi_handle();
   std::unique_ptr<knpemi_handle, void (*)(knpemi_handle*)> guard(h, knpemi_destroy);
-  h->device = device;
+  if (int rc = kn_device_open(h, device, "knpemi_ode_create")) return rc;
   h->ode_only = true;
-  KN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   KN_HIP(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
   KN_HIP(hipStreamCreateWithFlags(&h->aux2, hipStreamNonBlocking));
   KN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   KN_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
   KN_HIP(hipEventCreateWithFlags(&h->ev_join2, hipEventDisableTiming));
-  KN_HIP(hipEventCreate(&h->ev0));
-  KN_HIP(hipEventCreate(&h->ev1));
   h->cur = h->stream;
   // sub-domain 0 stands for the absent extracellular space; model i is the one model of sub-domain 1 + i
   const int S = n_models + 1;
@@ -996,8 +946,8 @@ extern "C" int knpemi_ode_create(int device, int n_models, const int32_t* nq, kn
   KnDev& D = h->dev;
   D.NQtot = h->qoff[S];
   int rc;
-  if ((rc = dev_zeros(h, (size_t)std::max(1, D.NQtot), &D.phiM))) return rc;                          // phi_M write-back
-  if ((rc = dev_zeros(h, (size_t)n_models * KN_MAXK * std::max(1, D.NQtot), &D.Ich))) return rc;      // (no ions: unused)
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)std::max(1, D.NQtot), &D.phiM))) return rc;                          // phi_M write-back
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_models * KN_MAXK * std::max(1, D.NQtot), &D.Ich))) return rc;      // (no ions: unused)
   *out = guard.release();
   return KNPEMI_OK;
 }
@@ -1017,21 +967,17 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   if (h->aux) (void)hipStreamDestroy(h->aux);
   kn_comm_destroy(h);
   kn_solver_free(h);
-  for (void* p : h->obs.allocs) (void)hipFree(p);
-  for (void* p : h->allocs) (void)hipFree(p);
+  kn_free_all(h->obs.allocs);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
-  for (auto& v : h->prof_ev) for (hipEvent_t e : v) (void)hipEventDestroy(e);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  kn_device_close(h);
   delete h;
 }
 
 extern "C" int knpemi_set_params(knpemi_handle* h, const knpemi_params* p) {
-  if (!h || !p) return fail(KNPEMI_EINVAL, "knpemi_set_params: null argument");
+  if (!h || !p) return kn_fail(KNPEMI_EINVAL, "knpemi_set_params: null argument");
   kn_inputs_changed(h);
   if (!(p->dt > 0) || !(p->C_M > 0) || p->z[h->K - 1] == 0.0)
-    return fail(KNPEMI_EINVAL, "knpemi_set_params: dt, C_M must be positive and z_K non-zero");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_set_params: dt, C_M must be positive and z_K non-zero");
   KnConsts& C = h->consts;
   C.dt = p->dt; C.inv_dt = 1.0 / p->dt; C.F = p->F; C.psi = p->psi; C.C_M = p->C_M;
   C.C_phi = p->C_phi > 0.0 ? p->C_phi : p->C_M / p->dt;
@@ -1053,12 +999,8 @@ extern "C" int knpemi_set_params(knpemi_handle* h, const knpemi_params* p) {
     sc.rho_term = -(1.0 / p->z[K - 1]) * p->rho_z * p->rho[s];
   }
   KN_HIP(hipSetDevice(h->device));
-  if (!h->d_consts) {
-    void* p2 = nullptr;
-    KN_HIP(hipMalloc(&p2, sizeof(KnConsts)));
-    h->allocs.push_back(p2);
-    h->d_consts = static_cast<KnConsts*>(p2);
-  }
+  if (!h->d_consts)
+    if (int rc = kn_alloc(h->allocs, 1, &h->d_consts)) return rc;
   KN_HIP(hipStreamSynchronize(h->stream));
   KN_HIP(hipMemcpy(h->d_consts, &h->consts, sizeof(KnConsts), hipMemcpyHostToDevice));
   h->have_params = 1;
@@ -1066,7 +1008,7 @@ extern "C" int knpemi_set_params(knpemi_handle* h, const knpemi_params* p) {
 }
 
 extern "C" int knpemi_sync(knpemi_handle* h) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KN_HIP(hipStreamSynchronize(h->aux));
   KN_HIP(hipStreamSynchronize(h->aux2));
   KN_HIP(hipStreamSynchronize(h->stream));
@@ -1082,55 +1024,51 @@ namespace {
 struct FieldLoc { double* base; int stride; size_t n; };
 
 int locate(knpemi_handle* h, int field, int sub, int idx, FieldLoc* loc) {
-  if (sub < 0 || sub >= h->n_sub) return fail(KNPEMI_EINVAL, "field: bad sub-domain index");
+  if (sub < 0 || sub >= h->n_sub) return kn_fail(KNPEMI_EINVAL, "field: bad sub-domain index");
   const int K = h->K;
   KnDev& D = h->dev;
   const size_t v0 = h->voff[sub], nv = h->n_vert[sub], q0 = h->qoff[sub], nq = h->n_q[sub];
   switch (field) {
     case KNPEMI_F_PHI: *loc = {D.VR + v0 * KN_REC + 7, KN_REC, nv}; return 0;
     case KNPEMI_F_C_PREV:
-      if (idx < 0 || idx >= K - 1) return fail(KNPEMI_EINVAL, "field: bad ion index");
+      if (idx < 0 || idx >= K - 1) return kn_fail(KNPEMI_EINVAL, "field: bad ion index");
       *loc = {D.VR + v0 * KN_REC + KN_CSLOT(idx), KN_REC, nv}; return 0;
     case KNPEMI_F_C_ELIM: *loc = {D.VR + v0 * KN_REC + KN_CSLOT(K - 1), KN_REC, nv}; return 0;
     case KNPEMI_F_C:
-      if (idx < 0 || idx >= K - 1) return fail(KNPEMI_EINVAL, "field: bad ion index");
+      if (idx < 0 || idx >= K - 1) return kn_fail(KNPEMI_EINVAL, "field: bad ion index");
       *loc = {D.csol + (size_t)idx * D.Ntot + v0, 1, nv}; return 0;
     case KNPEMI_F_PHI_M:
-      if (sub == 0) return fail(KNPEMI_EINVAL, "field: the ECS has no membrane space");
+      if (sub == 0) return kn_fail(KNPEMI_EINVAL, "field: the ECS has no membrane space");
       *loc = {D.phiM + q0, 1, nq}; return 0;
     case KNPEMI_F_I_CH: {
       int m = idx / KN_MAXK, k = idx % KN_MAXK;
       if (sub == 0 || m < 0 || m >= h->n_models[sub] || k >= K)
-        return fail(KNPEMI_EINVAL, "field: bad I_ch index");
+        return kn_fail(KNPEMI_EINVAL, "field: bad I_ch index");
       *loc = {D.Ich + ((size_t)(h->moff[sub] + m) * KN_MAXK + k) * std::max(1, D.NQtot) + q0, 1, nq};
       return 0;
     }
     case KNPEMI_F_SOURCE:
-      if (sub != 0 || idx < 0 || idx >= K - 1) return fail(KNPEMI_EINVAL, "field: f_source lives on the ECS");
+      if (sub != 0 || idx < 0 || idx >= K - 1) return kn_fail(KNPEMI_EINVAL, "field: f_source lives on the ECS");
       if (!D.fsrc) {
-        int rc = dev_zeros(h, (size_t)(K - 1) * h->n_vert[0], &D.fsrc);
+        int rc = kn_zeros(h->allocs, h->stream, (size_t)(K - 1) * h->n_vert[0], &D.fsrc);
         if (rc) return rc;
       }
       *loc = {D.fsrc + (size_t)idx * h->n_vert[0], 1, nv}; return 0;
   }
-  return fail(KNPEMI_EINVAL, "field: unknown field id");
+  return kn_fail(KNPEMI_EINVAL, "field: unknown field id");
 }
 }  // namespace
 
 extern "C" int knpemi_set_field(knpemi_handle* h, int field, int sub, int idx, const double* host, size_t n) {
-  if (!h || !host) return fail(KNPEMI_EINVAL, "knpemi_set_field: null argument");
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, "knpemi_set_field: null argument");
   kn_inputs_changed(h);
   FieldLoc L;
   int rc = locate(h, field, sub, idx, &L);
   if (rc) return rc;
-  if (n != L.n) return fail(KNPEMI_EINVAL, "knpemi_set_field: length does not match the function space");
+  if (n != L.n) return kn_fail(KNPEMI_EINVAL, "knpemi_set_field: length does not match the function space");
   if (n == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
-  if (L.stride == 1) {
-    KN_HIP(hipMemcpyAsync(L.base, host, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-    return KNPEMI_OK;
-  }
+  if (L.stride == 1) return kn_to_device(h->stream, L.base, host, n);
   KN_HIP(hipMemcpyAsync(h->d_stage, host, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   rc = kn_launch_field_scatter(h, h->d_stage, L.base, (int)n, L.stride);
   if (rc) return rc;
@@ -1139,11 +1077,11 @@ extern "C" int knpemi_set_field(knpemi_handle* h, int field, int sub, int idx, c
 }
 
 extern "C" int knpemi_get_field(knpemi_handle* h, int field, int sub, int idx, double* host, size_t n) {
-  if (!h || !host) return fail(KNPEMI_EINVAL, "knpemi_get_field: null argument");
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, "knpemi_get_field: null argument");
   FieldLoc L;
   int rc = locate(h, field, sub, idx, &L);
   if (rc) return rc;
-  if (n != L.n) return fail(KNPEMI_EINVAL, "knpemi_get_field: length does not match the function space");
+  if (n != L.n) return kn_fail(KNPEMI_EINVAL, "knpemi_get_field: length does not match the function space");
   if (n == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
   const double* src = L.base;
@@ -1152,18 +1090,16 @@ extern "C" int knpemi_get_field(knpemi_handle* h, int field, int sub, int idx, d
     if (rc) return rc;
     src = h->d_stage;
   }
-  KN_HIP(hipMemcpyAsync(host, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_host(h->stream, host, src, n);
 }
 
 extern "C" int knpemi_trace(knpemi_handle* h, int sub, const double* u_e, const double* u_i, double* q_e,
                             double* q_i) {
-  if (!h || !u_e || !u_i || !q_e || !q_i) return fail(KNPEMI_EINVAL, "knpemi_trace: null argument");
-  if (sub < 1 || sub >= h->n_sub) return fail(KNPEMI_EINVAL, "knpemi_trace: sub must be a cellular sub-domain");
+  if (!h || !u_e || !u_i || !q_e || !q_i) return kn_fail(KNPEMI_EINVAL, "knpemi_trace: null argument");
+  if (sub < 1 || sub >= h->n_sub) return kn_fail(KNPEMI_EINVAL, "knpemi_trace: sub must be a cellular sub-domain");
   const int nq = h->n_q[sub], ne = h->n_vert[0], ni = h->n_vert[sub];
   if (nq == 0) return KNPEMI_OK;
-  if ((size_t)ne + ni + 2 * (size_t)nq > h->stage_len) return fail(KNPEMI_EINVAL, "knpemi_trace: staging buffer too small");
+  if ((size_t)ne + ni + 2 * (size_t)nq > h->stage_len) return kn_fail(KNPEMI_EINVAL, "knpemi_trace: staging buffer too small");
   KN_HIP(hipSetDevice(h->device));
   double* de = h->d_stage;
   double* di = de + ne;
@@ -1183,8 +1119,8 @@ extern "C" int knpemi_trace(knpemi_handle* h, int sub, const double* u_e, const 
 // assembly + CSR access
 // ---------------------------------------------------------------------------------------------------
 extern "C" int knpemi_assemble_emi(knpemi_handle* h, int flags) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (!h->have_params) return fail(KNPEMI_EINVAL, "knpemi_assemble_emi: knpemi_set_params not called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_assemble_emi: knpemi_set_params not called");
   KN_HIP(hipSetDevice(h->device));
   h->emi_flags = flags;
   if (flags & KNPEMI_ON_AUX_STREAM) {
@@ -1202,7 +1138,7 @@ extern "C" int knpemi_assemble_emi(knpemi_handle* h, int flags) {
 }
 
 extern "C" int knpemi_join(knpemi_handle* h) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
   KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
@@ -1210,15 +1146,15 @@ extern "C" int knpemi_join(knpemi_handle* h) {
 }
 
 extern "C" int knpemi_assemble_emi_membrane_rhs(knpemi_handle* h, int flags) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (!h->have_params) return fail(KNPEMI_EINVAL, "knpemi_assemble_emi_membrane_rhs: knpemi_set_params not called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_assemble_emi_membrane_rhs: knpemi_set_params not called");
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_emi_membrane_rhs(h, flags);
 }
 
 extern "C" int knpemi_assemble_knp_membrane_early(knpemi_handle* h, int flags) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (!h->have_params) return fail(KNPEMI_EINVAL, "knpemi_assemble_knp_membrane_early: knpemi_set_params not called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_assemble_knp_membrane_early: knpemi_set_params not called");
   KN_HIP(hipSetDevice(h->device));
   int rc;
   if (flags & KNPEMI_ON_AUX_STREAM) {
@@ -1237,8 +1173,8 @@ extern "C" int knpemi_assemble_knp_membrane_early(knpemi_handle* h, int flags) {
 }
 
 extern "C" int knpemi_assemble_knp(knpemi_handle* h, int flags) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (!h->have_params) return fail(KNPEMI_EINVAL, "knpemi_assemble_knp: knpemi_set_params not called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_assemble_knp: knpemi_set_params not called");
   KN_HIP(hipSetDevice(h->device));
   // phi_M and I_ch come from the ODE sweeps, which may run on the auxiliary streams: the assembly is ordered after them
   // whether or not the caller has called knpemi_join (a wait on a completed or never-recorded event costs nothing)
@@ -1263,8 +1199,8 @@ extern "C" int knpemi_assemble_knp(knpemi_handle* h, int flags) {
 }
 
 extern "C" int knpemi_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (!(rtol >= 0) || !(atol >= 0) || maxit < 0) return fail(KNPEMI_EINVAL, "knpemi_solve_emi: bad tolerances");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!(rtol >= 0) || !(atol >= 0) || maxit < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_solve_emi: bad tolerances");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));   // a matrix assembled on the auxiliary stream is complete
@@ -1273,8 +1209,8 @@ extern "C" int knpemi_solve_emi(knpemi_handle* h, double rtol, double atol, int 
 }
 
 extern "C" int knpemi_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (!(rtol >= 0) || !(atol >= 0) || maxit < 0) return fail(KNPEMI_EINVAL, "knpemi_solve_knp: bad tolerances");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!(rtol >= 0) || !(atol >= 0) || maxit < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_solve_knp: bad tolerances");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   // every writer of A_knp, b_knp and their inputs (the potential, phi_M, I_ch) is on the main stream or joined into it
@@ -1286,18 +1222,18 @@ extern "C" int knpemi_solve_knp(knpemi_handle* h, double rtol, double atol, int 
 }
 
 extern "C" int knpemi_extrapolate_guess(knpemi_handle* h, int which) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return fail(KNPEMI_EINVAL, "knpemi_extrapolate_guess: unknown system");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return kn_fail(KNPEMI_EINVAL, "knpemi_extrapolate_guess: unknown system");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   return kn_extrapolate_guess(h, which);
 }
 
 extern "C" int knpemi_solver_setup(knpemi_handle* h, int which, int precond, double theta) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return fail(KNPEMI_EINVAL, "knpemi_solver_setup: unknown system");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return kn_fail(KNPEMI_EINVAL, "knpemi_solver_setup: unknown system");
   if (precond != KNPEMI_PC_JACOBI && precond != KNPEMI_PC_AMG)
-    return fail(KNPEMI_EINVAL, "knpemi_solver_setup: unknown preconditioner");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_solver_setup: unknown preconditioner");
   KnAmg& G = which == KNPEMI_B_EMI ? h->amg_emi : h->amg_knp;
   (which == KNPEMI_B_EMI ? h->pc_emi : h->pc_knp) = precond;
   G.cfg.theta = theta > 0 ? theta : 0.08;
@@ -1306,8 +1242,8 @@ extern "C" int knpemi_solver_setup(knpemi_handle* h, int which, int precond, dou
 }
 
 extern "C" int knpemi_solver_info(knpemi_handle* h, int which, int* levels, double* op_complexity, int* builds) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return fail(KNPEMI_EINVAL, "knpemi_solver_info: unknown system");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return kn_fail(KNPEMI_EINVAL, "knpemi_solver_info: unknown system");
   const KnAmg& G = which == KNPEMI_B_EMI ? h->amg_emi : h->amg_knp;
   if (levels) *levels = (int)G.lev.size();
   if (op_complexity) *op_complexity = G.op_complexity;
@@ -1316,21 +1252,21 @@ extern "C" int knpemi_solver_info(knpemi_handle* h, int which, int* levels, doub
 }
 
 extern "C" int knpemi_csr_dims(knpemi_handle* h, int which, int64_t* n_rows, int64_t* nnz) {
-  if (!h || !n_rows || !nnz) return fail(KNPEMI_EINVAL, "knpemi_csr_dims: null argument");
+  if (!h || !n_rows || !nnz) return kn_fail(KNPEMI_EINVAL, "knpemi_csr_dims: null argument");
   if (which == KNPEMI_A_EMI || which == KNPEMI_P_EMI) { *n_rows = h->dev.Ntot; *nnz = h->dev.nnz; }
   else if (which == KNPEMI_A_KNP) { *n_rows = (int64_t)(h->K - 1) * h->dev.Ntot; *nnz = (h->K - 1) * h->dev.nnzL; }
-  else return fail(KNPEMI_EINVAL, "knpemi_csr_dims: unknown matrix");
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_csr_dims: unknown matrix");
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_get_csr_pattern(knpemi_handle* h, int which, int32_t* rowptr, int32_t* colind) {
-  if (!h || !rowptr || !colind) return fail(KNPEMI_EINVAL, "knpemi_get_csr_pattern: null argument");
+  if (!h || !rowptr || !colind) return kn_fail(KNPEMI_EINVAL, "knpemi_get_csr_pattern: null argument");
   if (which == KNPEMI_A_EMI || which == KNPEMI_P_EMI) {
     std::memcpy(rowptr, h->h_rowptr.data(), h->h_rowptr.size() * sizeof(int));
     std::memcpy(colind, h->h_colind.data(), h->h_colind.size() * sizeof(int));
     return KNPEMI_OK;
   }
-  if (which != KNPEMI_A_KNP) return fail(KNPEMI_EINVAL, "knpemi_get_csr_pattern: unknown matrix");
+  if (which != KNPEMI_A_KNP) return kn_fail(KNPEMI_EINVAL, "knpemi_get_csr_pattern: unknown matrix");
   // block (sub, ion): rows/cols shifted to [c[0][0], c[0][1], c[1][0], ...] (pdeSolver.py:117)
   const int KS = h->K - 1;
   int64_t row = 0, pos = 0;
@@ -1351,7 +1287,7 @@ extern "C" int knpemi_get_csr_pattern(knpemi_handle* h, int which, int32_t* rowp
 
 extern "C" int knpemi_device_csr(knpemi_handle* h, int which, const int32_t** rowptr,
                                  const int32_t** colind, const double** vals) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   if (which == KNPEMI_A_EMI || which == KNPEMI_P_EMI) {
     if (rowptr) *rowptr = h->dev.rowptr;
     if (colind) *colind = h->dev.colind;
@@ -1364,74 +1300,66 @@ extern "C" int knpemi_device_csr(knpemi_handle* h, int which, const int32_t** ro
     if (vals) *vals = h->dev.A_knp;
     return KNPEMI_OK;
   }
-  return fail(KNPEMI_EINVAL, "knpemi_device_csr: unknown matrix");
+  return kn_fail(KNPEMI_EINVAL, "knpemi_device_csr: unknown matrix");
 }
 
 extern "C" int knpemi_get_csr_values(knpemi_handle* h, int which, double* vals) {
-  if (!h || !vals) return fail(KNPEMI_EINVAL, "knpemi_get_csr_values: null argument");
+  if (!h || !vals) return kn_fail(KNPEMI_EINVAL, "knpemi_get_csr_values: null argument");
   const double* src; size_t n;
   if (which == KNPEMI_A_EMI) { src = h->dev.A_emi; n = h->dev.nnz; }
   else if (which == KNPEMI_P_EMI) { src = h->dev.P_emi; n = h->dev.nnz; }
   else if (which == KNPEMI_A_KNP) { src = h->dev.A_knp; n = (size_t)(h->K - 1) * h->dev.nnzL; }
-  else return fail(KNPEMI_EINVAL, "knpemi_get_csr_values: unknown matrix");
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_get_csr_values: unknown matrix");
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipMemcpyAsync(vals, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_host(h->stream, vals, src, n);
 }
 
 // Values of an operator / right-hand side supplied by the caller (host arrays in the layout knpemi_get_csr_values /
 // knpemi_get_rhs return): the counterpart of PETSc's MatSetValues / VecSetValues for a caller that brings its own system
 // to the device solves of this library, and what the solver tests use to put the Krylov loops on prescribed systems.
 extern "C" int knpemi_set_csr_values(knpemi_handle* h, int which, const double* vals) {
-  if (!h || !vals) return fail(KNPEMI_EINVAL, "knpemi_set_csr_values: null argument");
+  if (!h || !vals) return kn_fail(KNPEMI_EINVAL, "knpemi_set_csr_values: null argument");
   double* dst; size_t n;
   if (which == KNPEMI_A_EMI) { dst = h->dev.A_emi; n = h->dev.nnz; }
   else if (which == KNPEMI_P_EMI) { dst = h->dev.P_emi; n = h->dev.nnz; }
   else if (which == KNPEMI_A_KNP) { dst = h->dev.A_knp; n = (size_t)(h->K - 1) * h->dev.nnzL; }
-  else return fail(KNPEMI_EINVAL, "knpemi_set_csr_values: unknown matrix");
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_set_csr_values: unknown matrix");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));   // an assembly on the auxiliary stream writes the same array
-  KN_HIP(hipMemcpyAsync(dst, vals, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_device(h->stream, dst, vals, n);
 }
 
 extern "C" int knpemi_set_rhs(knpemi_handle* h, int which, const double* b) {
-  if (!h || !b) return fail(KNPEMI_EINVAL, "knpemi_set_rhs: null argument");
+  if (!h || !b) return kn_fail(KNPEMI_EINVAL, "knpemi_set_rhs: null argument");
   double* dst; size_t n;
   if (which == KNPEMI_B_EMI) { dst = h->dev.b_emi; n = h->dev.Ntot; }
   else if (which == KNPEMI_B_KNP) { dst = h->dev.b_knp; n = (size_t)(h->K - 1) * h->dev.Ntot; }
-  else return fail(KNPEMI_EINVAL, "knpemi_set_rhs: unknown vector");
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_set_rhs: unknown vector");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  KN_HIP(hipMemcpyAsync(dst, b, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_device(h->stream, dst, b, n);
 }
 
 extern "C" int knpemi_device_rhs(knpemi_handle* h, int which, const double** b) {
-  if (!h || !b) return fail(KNPEMI_EINVAL, "null argument");
+  if (!h || !b) return kn_fail(KNPEMI_EINVAL, "null argument");
   if (which == KNPEMI_B_EMI) *b = h->dev.b_emi;
   else if (which == KNPEMI_B_KNP) *b = h->dev.b_knp;
-  else return fail(KNPEMI_EINVAL, "knpemi_device_rhs: unknown vector");
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_device_rhs: unknown vector");
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_get_rhs(knpemi_handle* h, int which, double* b) {
-  if (!h || !b) return fail(KNPEMI_EINVAL, "knpemi_get_rhs: null argument");
+  if (!h || !b) return kn_fail(KNPEMI_EINVAL, "knpemi_get_rhs: null argument");
   const double* src; size_t n;
   if (which == KNPEMI_B_EMI) { src = h->dev.b_emi; n = h->dev.Ntot; }
   else if (which == KNPEMI_B_KNP) { src = h->dev.b_knp; n = (size_t)(h->K - 1) * h->dev.Ntot; }
-  else return fail(KNPEMI_EINVAL, "knpemi_get_rhs: unknown vector");
+  else return kn_fail(KNPEMI_EINVAL, "knpemi_get_rhs: unknown vector");
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipMemcpyAsync(b, src, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return kn_to_host(h->stream, b, src, n);
 }
 
 extern "C" int knpemi_set_solution(knpemi_handle* h, int which, const double* x, int on_device) {
-  if (!h || !x) return fail(KNPEMI_EINVAL, "knpemi_set_solution: null argument");
+  if (!h || !x) return kn_fail(KNPEMI_EINVAL, "knpemi_set_solution: null argument");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -1453,7 +1381,7 @@ extern "C" int knpemi_set_solution(knpemi_handle* h, int which, const double* x,
   } else if (which == KNPEMI_B_KNP) {
     const int KS = h->K - 1;
     if (on_device) {   // one launch, as the write-back of knpemi_solve_knp
-      if (!h->have_params) return fail(KNPEMI_EINVAL, "knpemi_set_solution: knpemi_set_params not called");
+      if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_set_solution: knpemi_set_params not called");
       int rc = h->fuse_update ? kn_launch_knp_writeback_update(h, x) : kn_launch_knp_order(h, const_cast<double*>(x), 0);
       if (rc) return rc;
     } else
@@ -1464,12 +1392,12 @@ extern "C" int knpemi_set_solution(knpemi_handle* h, int which, const double* x,
         KN_HIP(hipMemcpyAsync(D.csol + (size_t)k * D.Ntot + h->voff[s],
                               x + (size_t)KS * h->voff[s] + (size_t)k * nv, nv * sizeof(double), kind, h->stream));
       }
-  } else return fail(KNPEMI_EINVAL, "knpemi_set_solution: unknown system");
+  } else return kn_fail(KNPEMI_EINVAL, "knpemi_set_solution: unknown system");
   // KNPEMI_OPT_FUSE_UPDATE: whoever writes the KNP solution also performs the end-of-step update (the device write-back
   // above does it in the same launch); the host path launches it after its copies, so that a caller's own solver whose
   // result arrives through this entry point leaves c_prev, the eliminated ion and phi_M updated as well
   if (!on_device && which == KNPEMI_B_KNP && h->fuse_update) {
-    if (!h->have_params) return fail(KNPEMI_EINVAL, "knpemi_set_solution: knpemi_set_params not called");
+    if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_set_solution: knpemi_set_params not called");
     int rc = kn_launch_update_pde(h);
     if (rc) return rc;
   }
@@ -1478,7 +1406,7 @@ extern "C" int knpemi_set_solution(knpemi_handle* h, int which, const double* x,
 }
 
 extern "C" int knpemi_get_solution(knpemi_handle* h, int which, double* x) {
-  if (!h || !x) return fail(KNPEMI_EINVAL, "knpemi_get_solution: null argument");
+  if (!h || !x) return kn_fail(KNPEMI_EINVAL, "knpemi_get_solution: null argument");
   KN_HIP(hipSetDevice(h->device));
   KnDev& D = h->dev;
   if (which == KNPEMI_B_EMI) {
@@ -1495,7 +1423,7 @@ extern "C" int knpemi_get_solution(knpemi_handle* h, int which, double* x) {
                               D.csol + (size_t)k * D.Ntot + h->voff[s], nv * sizeof(double),
                               hipMemcpyDeviceToHost, h->stream));
       }
-  } else return fail(KNPEMI_EINVAL, "knpemi_get_solution: unknown system");
+  } else return kn_fail(KNPEMI_EINVAL, "knpemi_get_solution: unknown system");
   KN_HIP(hipStreamSynchronize(h->stream));
   return KNPEMI_OK;
 }
@@ -1522,11 +1450,11 @@ int ode_alloc_tables(knpemi_handle* h, KnOdeModel& m, int sub, int model_id, int
   m.sub = sub; m.model_id = model_id; m.n_states = n_states; m.n_params = n_params;
   m.nq = h->n_q[sub];
   int rc;
-  if ((rc = dev_zeros(h, (size_t)n_states * m.nq, &m.d_states))) return rc;
-  if ((rc = dev_zeros(h, (size_t)n_params * m.nq, &m.d_params))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_states * m.nq, &m.d_states))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_params * m.nq, &m.d_params))) return rc;
   // one slot per workgroup of the sweep (small sweeps run with fewer dofs per wave, up to one wave per SIMD: kernels_ode.hip)
   m.n_stat_blocks = std::max((int)(((size_t)m.nq * n_states + 63) / 64), std::min(m.nq, 1024)) + 1;
-  if ((rc = dev_zeros(h, 3 * (size_t)m.n_stat_blocks, &m.d_stats))) return rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, 3 * (size_t)m.n_stat_blocks, &m.d_stats))) return rc;
   m.bound = 1;
   return KNPEMI_OK;
 }
@@ -1536,12 +1464,12 @@ extern "C" int knpemi_ode_bind(knpemi_handle* h, int sub, int model, int model_i
   int slot = ode_slot(h, sub, model, 0);
   if (slot < 0) return KNPEMI_EINVAL;
   static const int ns_of[3] = {4, 4, 1}, np_of[3] = {22, 22, 23};
-  if (model_id < 0 || model_id > 2) return fail(KNPEMI_EINVAL, "knpemi_ode_bind: unknown model id");
+  if (model_id < 0 || model_id > 2) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind: unknown model id");
   if (n_states != ns_of[model_id] || n_params != np_of[model_id])
-    return fail(KNPEMI_EINVAL, "knpemi_ode_bind: state/parameter count does not match the model");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind: state/parameter count does not match the model");
   KN_HIP(hipSetDevice(h->device));
   KnOdeModel& m = h->ode[slot];
-  if (m.bound) return fail(KNPEMI_EINVAL, "knpemi_ode_bind: model already bound");
+  if (m.bound) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind: model already bound");
   return ode_alloc_tables(h, m, sub, model_id, n_states, n_params);
 }
 
@@ -1550,10 +1478,10 @@ extern "C" int knpemi_ode_bind_source(knpemi_handle* h, int sub, int model, int 
   int slot = ode_slot(h, sub, model, 0);
   if (slot < 0) return KNPEMI_EINVAL;
   if (!rhs_source || n_states < 1 || n_states > 16 || n_params < 1 || n_params > 128)
-    return fail(KNPEMI_EINVAL, "knpemi_ode_bind_source: bad argument (1..16 states, 1..128 parameters)");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind_source: bad argument (1..16 states, 1..128 parameters)");
   KN_HIP(hipSetDevice(h->device));
   KnOdeModel& m = h->ode[slot];
-  if (m.bound) return fail(KNPEMI_EINVAL, "knpemi_ode_bind_source: model already bound");
+  if (m.bound) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind_source: model already bound");
   int rc = kn_rtc_bind(h, m, n_states, n_params, rhs_source);
   if (rc) return rc;
   return ode_alloc_tables(h, m, sub, -1, n_states, n_params);
@@ -1565,19 +1493,9 @@ extern "C" int knpemi_ode_set_tables(knpemi_handle* h, int sub, int model, const
   KnOdeModel& m = h->ode[slot];
   if (m.nq == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
-  std::vector<double> t;
-  if (states) {
-    t.resize((size_t)m.nq * m.n_states);
-    kn_transpose(states, t.data(), m.nq, m.n_states);
-    KN_HIP(hipMemcpyAsync(m.d_states, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-  }
-  if (params) {
-    t.resize((size_t)m.nq * m.n_params);
-    kn_transpose(params, t.data(), m.nq, m.n_params);
-    KN_HIP(hipMemcpyAsync(m.d_params, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-  }
+  int rc;
+  if (states && (rc = kn_table_upload(h->stream, states, m.d_states, m.nq, m.n_states))) return rc;
+  if (params && (rc = kn_table_upload(h->stream, params, m.d_params, m.nq, m.n_params))) return rc;
   return KNPEMI_OK;
 }
 
@@ -1587,19 +1505,9 @@ extern "C" int knpemi_ode_get_tables(knpemi_handle* h, int sub, int model, doubl
   KnOdeModel& m = h->ode[slot];
   if (m.nq == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
-  std::vector<double> t;
-  if (states) {
-    t.resize((size_t)m.nq * m.n_states);
-    KN_HIP(hipMemcpyAsync(t.data(), m.d_states, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-    kn_transpose(t.data(), states, m.n_states, m.nq);
-  }
-  if (params) {
-    t.resize((size_t)m.nq * m.n_params);
-    KN_HIP(hipMemcpyAsync(t.data(), m.d_params, t.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-    kn_transpose(t.data(), params, m.n_params, m.nq);
-  }
+  int rc;
+  if (states && (rc = kn_table_download(h->stream, m.d_states, states, m.nq, m.n_states))) return rc;
+  if (params && (rc = kn_table_download(h->stream, m.d_params, params, m.nq, m.n_params))) return rc;
   return KNPEMI_OK;
 }
 
@@ -1608,18 +1516,18 @@ extern "C" int knpemi_ode_set_stimulus(knpemi_handle* h, int sub, int model, con
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
   KnOdeModel& m = h->ode[slot];
-  if (n_pairs < 0 || n_pairs > 8) return fail(KNPEMI_EINVAL, "knpemi_ode_set_stimulus: at most 8 stimulus entries");
+  if (n_pairs < 0 || n_pairs > 8) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_set_stimulus: at most 8 stimulus entries");
   KN_HIP(hipSetDevice(h->device));
   for (int i = 0; i < n_pairs; ++i) {
     if (param_idx[i] < 0 || param_idx[i] >= m.n_params)
-      return fail(KNPEMI_EINVAL, "knpemi_ode_set_stimulus: parameter index out of range");
+      return kn_fail(KNPEMI_EINVAL, "knpemi_ode_set_stimulus: parameter index out of range");
     m.stim_idx[i] = param_idx[i];
     m.stim_val[i] = values[i];
   }
   m.n_stim = n_pairs;
   if (mask && m.nq > 0) {
     if (!m.d_mask) {
-      int rc = dev_zeros(h, (size_t)m.nq, &m.d_mask);
+      int rc = kn_zeros(h->allocs, h->stream, (size_t)m.nq, &m.d_mask);
       if (rc) return rc;
     }
     KN_HIP(hipMemcpyAsync(m.d_mask, mask, (size_t)m.nq, hipMemcpyHostToDevice, h->stream));
@@ -1634,17 +1542,17 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
                                double atol, int flags, const int32_t* ion_param, int v_index) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  if (!ion_param) return fail(KNPEMI_EINVAL, "knpemi_ode_step: ion_param is required");
+  if (!ion_param) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: ion_param is required");
   KnOdeModel& m = h->ode[slot];
   for (int i = 0; i < 3 * h->K; ++i)
     if (ion_param[i] < 0 || ion_param[i] >= m.n_params)
-      return fail(KNPEMI_EINVAL, "knpemi_ode_step: parameter index out of range");
-  if (v_index < 0 || v_index >= m.n_states) return fail(KNPEMI_EINVAL, "knpemi_ode_step: bad V index");
+      return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: parameter index out of range");
+  if (v_index < 0 || v_index >= m.n_states) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: bad V index");
   const bool fixed = m.method != KNPEMI_ODE_LSODA;   // (a fixed-step method has no tolerances)
   if (!(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
-    return fail(KNPEMI_EINVAL, "knpemi_ode_step: bad dt / tolerances");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: bad dt / tolerances");
   if (h->ode_only && (flags & (KNPEMI_ODE_SET_TRACES | KNPEMI_ODE_SET_V)))
-    return fail(KNPEMI_EINVAL, "knpemi_ode_step: a handle of knpemi_ode_create has no PDE fields to read");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: a handle of knpemi_ode_create has no PDE fields to read");
   kn_inputs_changed(h);      // phi_M and the channel currents
   KN_HIP(hipSetDevice(h->device));
   // beside the main stream's work on an auxiliary stream when asked for: fork, sweep, record the join event
@@ -1670,18 +1578,18 @@ extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t
   const KnOdeModel& m = h->ode[slot];
   const bool fixed = m.method != KNPEMI_ODE_LSODA;
   if (n_steps < 0 || !(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
-    return fail(KNPEMI_EINVAL, "knpemi_ode_advance: bad n_steps / dt / tolerances");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_advance: bad n_steps / dt / tolerances");
   if (history) {
     if (every < 1 || n_rec < 1 || n_rec > 8 || !rec_idx)
-      return fail(KNPEMI_EINVAL, "knpemi_ode_advance: recording needs every >= 1 and 1..8 state indices");
+      return kn_fail(KNPEMI_EINVAL, "knpemi_ode_advance: recording needs every >= 1 and 1..8 state indices");
     for (int i = 0; i < n_rec; ++i)
       if (rec_idx[i] < 0 || rec_idx[i] >= m.n_states)
-        return fail(KNPEMI_EINVAL, "knpemi_ode_advance: recorded state index out of range");
+        return kn_fail(KNPEMI_EINVAL, "knpemi_ode_advance: recorded state index out of range");
   } else {
     every = 1;
   }
   if (ss && (ss->window < 1 || !(ss->ss_rtol >= 0) || !(ss->ss_atol >= 0)))
-    return fail(KNPEMI_EINVAL, "knpemi_ode_advance: steady-state window >= 1 and tolerances >= 0");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_advance: steady-state window >= 1 and tolerances >= 0");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->aux));   // a sweep of this model may still run on an auxiliary stream
@@ -1695,11 +1603,11 @@ extern "C" int knpemi_ode_set_method(knpemi_handle* h, int sub, int model, int m
   if (slot < 0) return KNPEMI_EINVAL;
   KnOdeModel& m = h->ode[slot];
   if (method < KNPEMI_ODE_LSODA || method > KNPEMI_ODE_RUSH_LARSEN)
-    return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: unknown method");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_set_method: unknown method");
   if (method != KNPEMI_ODE_LSODA && (n_substeps < 1 || n_substeps > 10000))
-    return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: n_substeps must be in 1..10000");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_set_method: n_substeps must be in 1..10000");
   if (m.rtc_module && !m.rtc_kernel[method][0])   // (today: Rush-Larsen)
-    return fail(KNPEMI_EINVAL, "knpemi_ode_set_method: rush_larsen needs the gate rates of a model, and a model bound from "
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_set_method: rush_larsen needs the gate rates of a model, and a model bound from "
                                "source brings a right-hand side only (use euler or rk4)");
   m.method = method;
   m.n_substeps = method == KNPEMI_ODE_LSODA ? 0 : n_substeps;
@@ -1733,7 +1641,7 @@ extern "C" int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n
   if (n_rhs) *n_rhs = (int64_t)st[0];
   if (n_steps) *n_steps = (int64_t)st[1];
   if (n_failed) *n_failed = (int32_t)st[2];
-  if (st[2]) return fail(KNPEMI_EODE, kn_ode_failure(mo.method == KNPEMI_ODE_LSODA, "at least one membrane dof"));
+  if (st[2]) return kn_fail(KNPEMI_EODE, kn_ode_failure(mo.method == KNPEMI_ODE_LSODA, "at least one membrane dof"));
   return KNPEMI_OK;
 }
 
@@ -1741,7 +1649,7 @@ extern "C" int knpemi_debug_ode_stamps(knpemi_handle* h, int sub, int model, uin
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
   KnOdeModel& m = h->ode[slot];
-  if (!m.d_stamps || !out) return fail(KNPEMI_EINVAL, "knpemi_debug_ode_stamps: run with KNPEMI_ODE_STAMPS=1");
+  if (!m.d_stamps || !out) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_ode_stamps: run with KNPEMI_ODE_STAMPS=1");
   const int nb = std::min(max_blocks, m.n_stat_blocks - 1);
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->aux));
@@ -1751,8 +1659,8 @@ extern "C" int knpemi_debug_ode_stamps(knpemi_handle* h, int sub, int model, uin
 }
 
 extern "C" int knpemi_update_pde(knpemi_handle* h) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (!h->have_params) return fail(KNPEMI_EINVAL, "knpemi_update_pde: knpemi_set_params not called");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_update_pde: knpemi_set_params not called");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_update_pde(h);
@@ -1765,31 +1673,19 @@ int kn_observe_chunk();
 
 namespace {
 void observe_free(knpemi_handle* h) {
-  for (void* p : h->obs.allocs) (void)hipFree(p);
+  kn_free_all(h->obs.allocs);
   h->obs = knpemi_handle::KnObserve{};
 }
 
-template <class T>
-int obs_upload(knpemi_handle* h, const T* src, size_t n, T** out) {
-  void* p = nullptr;
-  KN_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-  h->obs.allocs.push_back(p);
-  if (n) KN_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-  *out = static_cast<T*>(p);
-  return 0;
-}
-}  // namespace
-
-namespace {
 // knpemi_observe_set and knpemi_observe_set_partitioned; the partitioned table may hold observables without entries
 int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
                 const double* w, const double* denom, int capacity, bool partitioned) {
   const std::string fn(who);
-  if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return fail(KNPEMI_EINVAL, fn + ": null argument");
-  if (h->ode_only) return fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
-  if (n_obs < 1 || capacity < 1) return fail(KNPEMI_EINVAL, fn + ": n_obs and capacity must be positive");
-  if (ptr[0] != 0) return fail(KNPEMI_EINVAL, fn + ": ptr[0] must be 0");
-  if (ptr[n_obs] > 0 && (!idx || !w)) return fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_obs < 1 || capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": n_obs and capacity must be positive");
+  if (ptr[0] != 0) return kn_fail(KNPEMI_EINVAL, fn + ": ptr[0] must be 0");
+  if (ptr[n_obs] > 0 && (!idx || !w)) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
   const int chunk = kn_observe_chunk();
   std::vector<int4> blk;
   std::vector<int> blk_ptr(1, 0), op(n_obs), stride(n_obs);
@@ -1797,15 +1693,15 @@ int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spe
   for (int o = 0; o < n_obs; ++o) {
     const int32_t field = spec[4 * o], sub = spec[4 * o + 1], ix = spec[4 * o + 2], oo = spec[4 * o + 3];
     if (oo != KNPEMI_OBS_SUM && oo != KNPEMI_OBS_MIN && oo != KNPEMI_OBS_MAX)
-      return fail(KNPEMI_EINVAL, fn + ": unknown op of observable " + std::to_string(o));
+      return kn_fail(KNPEMI_EINVAL, fn + ": unknown op of observable " + std::to_string(o));
     if ((partitioned ? ptr[o + 1] < ptr[o] : ptr[o + 1] <= ptr[o]) || ptr[o + 1] > (int64_t)INT32_MAX)
-      return fail(KNPEMI_EINVAL, fn + ": observable " + std::to_string(o) + (partitioned ? " has a bad entry range" : " has no entries"));
+      return kn_fail(KNPEMI_EINVAL, fn + ": observable " + std::to_string(o) + (partitioned ? " has a bad entry range" : " has no entries"));
     FieldLoc L;
     int rc = locate(h, field, sub, ix, &L);
     if (rc) return rc;
     for (int64_t e = ptr[o]; e < ptr[o + 1]; ++e)        // every read of the kernel stays inside the field
       if (idx[e] < 0 || (size_t)idx[e] >= L.n)
-        return fail(KNPEMI_EINVAL, fn + ": index out of range in observable " + std::to_string(o));
+        return kn_fail(KNPEMI_EINVAL, fn + ": index out of range in observable " + std::to_string(o));
     op[o] = oo; stride[o] = L.stride; base[o] = L.base;
     for (int64_t e = ptr[o]; e < ptr[o + 1]; e += chunk)
       blk.push_back(make_int4(o, (int)e, (int)std::min<int64_t>(e + chunk, ptr[o + 1]), 0));
@@ -1817,22 +1713,18 @@ int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spe
   auto& O = h->obs;
   const size_t ne = (size_t)ptr[n_obs];
   int rc;
-  if ((rc = obs_upload(h, blk.data(), blk.size(), &O.blk)) || (rc = obs_upload(h, blk_ptr.data(), blk_ptr.size(), &O.blk_ptr))
-      || (rc = obs_upload(h, op.data(), op.size(), &O.op)) || (rc = obs_upload(h, stride.data(), stride.size(), &O.stride))
-      || (rc = obs_upload(h, base.data(), base.size(), const_cast<const double***>(&O.base)))
-      || (rc = obs_upload(h, denom, (size_t)n_obs, &O.denom))
-      || (rc = obs_upload(h, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = obs_upload(h, w, ne, &O.w))) {
+  auto& A = O.allocs;
+  if ((rc = kn_upload(A, blk, &O.blk)) || (rc = kn_upload(A, blk_ptr, &O.blk_ptr)) || (rc = kn_upload(A, op, &O.op))
+      || (rc = kn_upload(A, stride, &O.stride)) || (rc = kn_upload(A, base, &O.base))
+      || (rc = kn_upload(A, denom, (size_t)n_obs, &O.denom))
+      || (rc = kn_upload(A, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = kn_upload(A, w, ne, &O.w))) {
     observe_free(h);
     return rc;
   }
-  void* p = nullptr;
   const size_t row_bytes = (size_t)capacity * n_obs * sizeof(double);
-  if (hipMalloc(&p, std::max<size_t>(blk.size(), 1) * sizeof(double)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, fn + ": partials"); }
-  O.allocs.push_back(p); O.part = static_cast<double*>(p);
-  if (hipMalloc(&p, 4 * sizeof(unsigned long long)) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, fn + ": counters"); }
-  O.allocs.push_back(p); O.ctl = static_cast<unsigned long long*>(p);
-  if (hipMalloc(&p, row_bytes) != hipSuccess) { observe_free(h); return fail(KNPEMI_ENOMEM, fn + ": buffer"); }
-  O.allocs.push_back(p); O.rows = static_cast<double*>(p);
+  if (kn_alloc(A, blk.size(), &O.part)) { observe_free(h); return kn_fail(KNPEMI_ENOMEM, fn + ": partials"); }
+  if (kn_alloc(A, 4, &O.ctl)) { observe_free(h); return kn_fail(KNPEMI_ENOMEM, fn + ": counters"); }
+  if (kn_alloc(A, (size_t)capacity * n_obs, &O.rows)) { observe_free(h); return kn_fail(KNPEMI_ENOMEM, fn + ": buffer"); }
   KN_HIP(hipMemsetAsync(O.ctl, 0, 4 * sizeof(unsigned long long), h->stream));
   KN_HIP(hipMemsetAsync(O.rows, 0, row_bytes, h->stream));
   KN_HIP(hipStreamSynchronize(h->stream));
@@ -1851,13 +1743,13 @@ extern "C" int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const
                                               int rank, int world, void* xbuf_dev, knpemi_allreduce_fn allreduce,
                                               void* ctx) {
   const char* fn = "knpemi_observe_set_partitioned";
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
-  if (world < 1 || rank < 0 || rank >= world) return fail(KNPEMI_EINVAL, std::string(fn) + ": bad rank / world");
-  if (!xbuf_dev) return fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer is required");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (world < 1 || rank < 0 || rank >= world) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": bad rank / world");
+  if (!xbuf_dev) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer is required");
   if (!allreduce && !h->comm)
-    return fail(KNPEMI_EINVAL, std::string(fn) + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
+    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
   if (n_obs > 0 && (size_t)world * (size_t)n_obs > (size_t)INT32_MAX)
-    return fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer too large");
+    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer too large");
   int rc = observe_set(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, true);
   if (rc) return rc;
   auto& O = h->obs;
@@ -1869,15 +1761,15 @@ extern "C" int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const
 }
 
 extern "C" int knpemi_observe_record(knpemi_handle* h) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   auto& O = h->obs;
-  if (O.n_obs == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
+  if (O.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
   KN_HIP(hipSetDevice(h->device));
   int rc = kn_launch_observe(h);
   if (rc || !O.xbuf) return rc;
   // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
   const int n = O.world * O.n_obs;
-  rc = O.allreduce ? (O.allreduce(O.ctx, n) ? fail(KNPEMI_EHIP, "knpemi_observe_record: allreduce hook failed") : KNPEMI_OK)
+  rc = O.allreduce ? (O.allreduce(O.ctx, n) ? kn_fail(KNPEMI_EHIP, "knpemi_observe_record: allreduce hook failed") : KNPEMI_OK)
                    : knpemi_comm_allreduce(h, O.xbuf, n);
   if (rc) return rc;
   return kn_launch_observe_combine(h);
@@ -1885,19 +1777,16 @@ extern "C" int knpemi_observe_record(knpemi_handle* h) {
 
 extern "C" int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow,
                                    int reset) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   auto& O = h->obs;
-  if (O.n_obs == 0) return fail(KNPEMI_EINVAL, "knpemi_observe_read: no observables set");
-  if (n_rows < 0 || (n_rows > 0 && !out)) return fail(KNPEMI_EINVAL, "knpemi_observe_read: bad output buffer");
+  if (O.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_read: no observables set");
+  if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_read: bad output buffer");
   KN_HIP(hipSetDevice(h->device));
   unsigned long long ctl[4];
-  KN_HIP(hipMemcpyAsync(ctl, O.ctl, sizeof(ctl), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
+  int rc;
+  if ((rc = kn_to_host(h->stream, ctl, O.ctl, 4))) return rc;
   const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
-  if (n) {
-    KN_HIP(hipMemcpyAsync(out, O.rows, n * O.n_obs * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-  }
+  if (n && (rc = kn_to_host(h->stream, out, O.rows, n * O.n_obs))) return rc;
   if (rows) *rows = (int64_t)ctl[0];
   if (overflow) *overflow = (int64_t)ctl[1];
   if (reset) {
@@ -1908,7 +1797,7 @@ extern "C" int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, in
 }
 
 extern "C" int knpemi_observe_clear(knpemi_handle* h) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   observe_free(h);
@@ -1917,14 +1806,14 @@ extern "C" int knpemi_observe_clear(knpemi_handle* h) {
 
 extern "C" int knpemi_set_distributed(knpemi_handle* h, const uint8_t* owned, void* reduce_buf_dev,
                                       knpemi_allreduce_fn allreduce, knpemi_halo_fn halo, void* ctx) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   kn_inputs_changed(h);          // whether the write-back of the potential folds changes with it
   KnDist& d = h->dist;
   h->amg_emi.built = false;      // the preconditioner changes with the ownership
   h->amg_knp.built = false;
   if (!owned) { d.on = false; return KNPEMI_OK; }
   if (!reduce_buf_dev || !allreduce || !halo)
-    return fail(KNPEMI_EINVAL, "knpemi_set_distributed: reduction buffer and both communication hooks are required");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_set_distributed: reduction buffer and both communication hooks are required");
   KN_HIP(hipSetDevice(h->device));
   const int Ntot = h->dev.Ntot, KS = h->K - 1;
   d.h_owned_emi.assign(owned, owned + Ntot);
@@ -1936,9 +1825,9 @@ extern "C" int knpemi_set_distributed(knpemi_handle* h, const uint8_t* owned, vo
   }
   int rc;
   const uint8_t* p = nullptr;
-  if ((rc = dev_upload(h, d.h_owned_emi, &p))) return rc;
+  if ((rc = kn_upload(h->allocs, d.h_owned_emi, &p))) return rc;
   d.d_owned_emi = const_cast<uint8_t*>(p);
-  if ((rc = dev_upload(h, d.h_owned_knp, &p))) return rc;
+  if ((rc = kn_upload(h->allocs, d.h_owned_knp, &p))) return rc;
   d.d_owned_knp = const_cast<uint8_t*>(p);
   d.d_red = static_cast<double*>(reduce_buf_dev);
   d.allreduce = allreduce; d.halo = halo; d.ctx = ctx;
@@ -1946,7 +1835,7 @@ extern "C" int knpemi_set_distributed(knpemi_handle* h, const uint8_t* owned, vo
   double cnt = 0.0;
   for (int i = 0; i < Ntot; ++i) cnt += owned[i] ? 1.0 : 0.0;
   KN_HIP(hipMemcpyAsync(d.d_red, &cnt, sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (allreduce(ctx, 1)) return fail(KNPEMI_EHIP, "knpemi_set_distributed: allreduce hook failed");
+  if (allreduce(ctx, 1)) return kn_fail(KNPEMI_EHIP, "knpemi_set_distributed: allreduce hook failed");
   KN_HIP(hipMemcpyAsync(&cnt, d.d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   KN_HIP(hipStreamSynchronize(h->stream));
   d.n_owned_global = cnt;
@@ -1955,13 +1844,13 @@ extern "C" int knpemi_set_distributed(knpemi_handle* h, const uint8_t* owned, vo
 }
 
 extern "C" int knpemi_set_distributed_coarse(knpemi_handle* h, int rank, int world) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KnDist& d = h->dist;
   if (world <= 1) { d.nc = 0; d.coarse_built = false; return KNPEMI_OK; }
-  if (rank < 0 || rank >= world) return fail(KNPEMI_EINVAL, "knpemi_set_distributed_coarse: bad rank");
+  if (rank < 0 || rank >= world) return kn_fail(KNPEMI_EINVAL, "knpemi_set_distributed_coarse: bad rank");
   if (world * h->n_sub > KN_COARSE_MAX)
-    return fail(KNPEMI_EINVAL, "knpemi_set_distributed_coarse: more than 64 (rank, sub-domain) aggregates");
-  if (!d.on) return fail(KNPEMI_EINVAL, "knpemi_set_distributed_coarse: call knpemi_set_distributed first");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_set_distributed_coarse: more than 64 (rank, sub-domain) aggregates");
+  if (!d.on) return kn_fail(KNPEMI_EINVAL, "knpemi_set_distributed_coarse: call knpemi_set_distributed first");
   KN_HIP(hipSetDevice(h->device));
   d.rank = rank; d.world = world;
   // as many nodes per (rank, sub-domain) as the coarse size allows: k slices, k + 1 hat functions (k = 0: one constant)
@@ -2022,65 +1911,65 @@ extern "C" int knpemi_set_distributed_coarse(knpemi_handle* h, int rank, int wor
   int rc;
   const int* p = nullptr;
   const double* pd = nullptr;
-  if ((rc = dev_upload(h, agg_of, &p))) return rc;
+  if ((rc = kn_upload(h->allocs, agg_of, &p))) return rc;
   d.d_agg_of = const_cast<int*>(p);
-  if ((rc = dev_upload(h, agg_w, &pd))) return rc;
+  if ((rc = kn_upload(h->allocs, agg_w, &pd))) return rc;
   d.d_agg_w = const_cast<double*>(pd);
-  if ((rc = dev_upload(h, ptr, &p))) return rc;
+  if ((rc = kn_upload(h->allocs, ptr, &p))) return rc;
   d.d_agg_ptr = const_cast<int*>(p);
-  if ((rc = dev_upload(h, idx, &p))) return rc;
+  if ((rc = kn_upload(h->allocs, idx, &p))) return rc;
   d.d_agg_idx = const_cast<int*>(p);
-  if ((rc = dev_upload(h, wts, &pd))) return rc;
+  if ((rc = kn_upload(h->allocs, wts, &pd))) return rc;
   d.d_agg_wt = const_cast<double*>(pd);
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_vec_gather(knpemi_handle* h, const void* vec_dev, const int32_t* idx_dev, int n, void* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return fail(KNPEMI_EINVAL, "knpemi_vec_gather: bad argument");
+  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_vec_gather: bad argument");
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_vec_index(h, static_cast<double*>(const_cast<void*>(vec_dev)), idx_dev, n, static_cast<double*>(buf_dev), 1);
 }
 
 extern "C" int knpemi_vec_scatter(knpemi_handle* h, void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return fail(KNPEMI_EINVAL, "knpemi_vec_scatter: bad argument");
+  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_vec_scatter: bad argument");
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_vec_index(h, static_cast<double*>(vec_dev), idx_dev, n, static_cast<double*>(const_cast<void*>(buf_dev)), 0);
 }
 
 extern "C" int knpemi_set_option(knpemi_handle* h, int option, int value) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   // these decide which launches write the inputs of the stored facet integrals (knpemi_handle::inputs_gen) or form them
   if (option == KNPEMI_OPT_FUSE_UPDATE || option == KNPEMI_OPT_FUSE_MEMBRANE || option == KNPEMI_OPT_FOLD_MEMBRANE)
     kn_inputs_changed(h);
   if (option == KNPEMI_OPT_FUSE_UPDATE) { h->fuse_update = value ? 1 : 0; return KNPEMI_OK; }
   if (option == KNPEMI_OPT_FUSE_MEMBRANE) {
     if (value && h->blocks_clustered)
-      return fail(KNPEMI_EINVAL, "KNPEMI_OPT_FUSE_MEMBRANE needs row blocks of consecutive rows (create the handle with KNPEMI_BLOCK_CLASSIC=1)");
+      return kn_fail(KNPEMI_EINVAL, "KNPEMI_OPT_FUSE_MEMBRANE needs row blocks of consecutive rows (create the handle with KNPEMI_BLOCK_CLASSIC=1)");
     h->fuse_membrane = value ? 1 : 0;
     return KNPEMI_OK;
   }
   if (option == KNPEMI_OPT_PROFILE_STRIDE) {   // the next launch of every kernel is a bracketed one
-    h->prof_stride = value > 1 ? value : 1;
-    for (unsigned& c : h->prof_count) c = 0;
+    h->prof.stride = value > 1 ? value : 1;
+    for (unsigned& c : h->prof.count) c = 0;
     return KNPEMI_OK;
   }
   if (option == KNPEMI_OPT_KNP_METHOD) {
-    if (value != 0 && value != 1) return fail(KNPEMI_EINVAL, "KNPEMI_OPT_KNP_METHOD: 0 (BiCGStab) or 1 (GMRES)");
+    if (value != 0 && value != 1) return kn_fail(KNPEMI_EINVAL, "KNPEMI_OPT_KNP_METHOD: 0 (BiCGStab) or 1 (GMRES)");
     h->knp_method = value;
     return KNPEMI_OK;
   }
   if (option == KNPEMI_OPT_EMI_NORM) {
-    if (value != 0 && value != 1) return fail(KNPEMI_EINVAL, "KNPEMI_OPT_EMI_NORM: 0 (true residual) or 1 (preconditioned)");
+    if (value != 0 && value != 1) return kn_fail(KNPEMI_EINVAL, "KNPEMI_OPT_EMI_NORM: 0 (true residual) or 1 (preconditioned)");
     h->emi_norm_pre = value;
     return KNPEMI_OK;
   }
   if (option == KNPEMI_OPT_FOLD_MEMBRANE) { h->fold_membrane = value ? 1 : 0; return KNPEMI_OK; }
   if (option == KNPEMI_OPT_KNP_MIN_IT) {
-    if (value < 0) return fail(KNPEMI_EINVAL, "KNPEMI_OPT_KNP_MIN_IT: negative");
+    if (value < 0) return kn_fail(KNPEMI_EINVAL, "KNPEMI_OPT_KNP_MIN_IT: negative");
     h->knp_min_it = value;
     return KNPEMI_OK;
   }
-  return fail(KNPEMI_EINVAL, "knpemi_set_option: unknown option");
+  return kn_fail(KNPEMI_EINVAL, "knpemi_set_option: unknown option");
 }
 
 extern "C" int knpemi_halo_width(knpemi_handle* h, int kind) {
@@ -2090,55 +1979,46 @@ extern "C" int knpemi_halo_width(knpemi_handle* h, int kind) {
 
 extern "C" int knpemi_halo_pack(knpemi_handle* h, int kind, const int32_t* idx_dev, int n, double* buf_dev) {
   if (!h || (n > 0 && (!idx_dev || !buf_dev)) || n < 0 || kind < 0 || kind > 1)
-    return fail(KNPEMI_EINVAL, "knpemi_halo_pack: bad argument");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_halo_pack: bad argument");
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_halo(h, kind, 1, idx_dev, n, buf_dev);
 }
 
 extern "C" int knpemi_halo_unpack(knpemi_handle* h, int kind, const int32_t* idx_dev, int n, const double* buf_dev) {
   if (!h || (n > 0 && (!idx_dev || !buf_dev)) || n < 0 || kind < 0 || kind > 1)
-    return fail(KNPEMI_EINVAL, "knpemi_halo_unpack: bad argument");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_halo_unpack: bad argument");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_halo(h, kind, 0, idx_dev, n, const_cast<double*>(buf_dev));
 }
 
 extern "C" int knpemi_profile(knpemi_handle* h, uint32_t kernel_mask) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
-  h->prof_mask = kernel_mask;
-  for (int k = 0; k < KNPEMI_N_KERNELS; ++k) h->prof_used[k] = 0;
+  h->prof.mask = kernel_mask;
+  for (size_t& u : h->prof.used) u = 0;
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_profile_read(knpemi_handle* h, int kernel, int64_t* launches, double* total_ms) {
   if (!h || kernel < 0 || kernel >= KNPEMI_N_KERNELS || !launches || !total_ms)
-    return fail(KNPEMI_EINVAL, "knpemi_profile_read: bad argument");
+    return kn_fail(KNPEMI_EINVAL, "knpemi_profile_read: bad argument");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   KN_HIP(hipStreamSynchronize(h->aux));
   KN_HIP(hipStreamSynchronize(h->aux2));
-  double sum = 0.0;
-  for (size_t i = 0; i + 1 < h->prof_used[kernel]; i += 2) {
-    float f = 0.f;
-    KN_HIP(hipEventElapsedTime(&f, h->prof_ev[kernel][i], h->prof_ev[kernel][i + 1]));
-    sum += f;
-  }
-  *launches = (int64_t)(h->prof_used[kernel] / 2);
-  *total_ms = sum;
-  h->prof_used[kernel] = 0;
-  return KNPEMI_OK;
+  return kn_prof_read(h->prof, kernel, launches, total_ms);
 }
 
 extern "C" int knpemi_timer_start(knpemi_handle* h) {
-  if (!h) return fail(KNPEMI_EINVAL, "null handle");
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KN_HIP(hipEventRecord(h->ev0, h->stream));
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_timer_stop_ms(knpemi_handle* h, double* ms) {
-  if (!h || !ms) return fail(KNPEMI_EINVAL, "null argument");
+  if (!h || !ms) return kn_fail(KNPEMI_EINVAL, "null argument");
   KN_HIP(hipEventRecord(h->ev1, h->stream));
   KN_HIP(hipEventSynchronize(h->ev1));
   float f = 0.f;
@@ -2148,7 +2028,7 @@ extern "C" int knpemi_timer_stop_ms(knpemi_handle* h, double* ms) {
 }
 
 extern "C" int knpemi_debug_geometry(knpemi_handle* h, int* flags) {
-  if (!h || !flags) return fail(KNPEMI_EINVAL, "knpemi_debug_geometry: null argument");
+  if (!h || !flags) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_geometry: null argument");
   *flags = (h->tet_uniform ? 1 : 0) | (h->hex_affine ? 2 : 0) | (h->hex_uniform ? 4 : 0);
   return KNPEMI_OK;
 }

@@ -6,6 +6,7 @@
 #include "block_spmv.h"
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -282,9 +283,177 @@ struct KnVecPlan {
   std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;
 };
 
-struct knpemi_handle {
+// error plumbing ------------------------------------------------------------------------------
+void kn_set_error(const std::string& msg);
+#define KN_HIP(call)                                                                     \
+  do {                                                                                   \
+    hipError_t e_ = (call);                                                              \
+    if (e_ != hipSuccess) {                                                              \
+      kn_set_error(std::string(#call) + ": " + hipGetErrorString(e_));                   \
+      return KNPEMI_EHIP;                                                                \
+    }                                                                                    \
+  } while (0)
+inline int kn_fail(int code, const std::string& msg) {
+  kn_set_error(msg);
+  return code;
+}
+// after a kernel launch: KNPEMI_OK, or KNPEMI_EHIP with "<what>: <HIP's message>" (what: the kernel's name, or the text
+// the caller wants in front of HIP's)
+inline int kn_launch_check(const std::string& what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? KNPEMI_OK : kn_fail(KNPEMI_EHIP, what + ": " + hipGetErrorString(e));
+}
+
+// The device base of both handles (knpemi_handle here, knpemi_dg in kernels_dg.hip): what they own in the same way, and the
+// one set of helpers for it.  Host only.
+void kn_comm_free(void* comm);   // comm_rccl.hip
+
+// per-kernel event profiling (knpemi_profile, knpemi_dg_profile): begin/end event pairs around the launches of kernel k
+struct KnProf {
+  uint32_t mask = 0;                               // bit k: the launches of kernel k are bracketed
+  // every stride-th one only (an event pair around a kernel on the critical path costs the step several microseconds)
+  int stride = 1;
+  unsigned count[KNPEMI_N_KERNELS] = {};           // launches seen since the stride was set
+  std::vector<hipEvent_t> ev[KNPEMI_N_KERNELS];    // begin/end pairs
+  size_t used[KNPEMI_N_KERNELS] = {};              // events of ev[k] recorded since the last read
+};
+// RAII bracket around one kernel launch on stream `st`; no-op unless the kernel's bit is set in the mask
+struct KnProfScope {
+  KnProf& p; int k; hipStream_t st; bool on;
+  KnProfScope(KnProf& p_, int k_, hipStream_t st_) : p(p_), k(k_), st(st_), on((p_.mask >> k_) & 1u) {
+    if (on && p.stride > 1 && (p.count[k]++ % p.stride) != 0) on = false;
+    if (!on) return;
+    auto& v = p.ev[k];
+    if (p.used[k] + 2 > v.size()) {
+      hipEvent_t a, b;
+      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
+      v.push_back(a); v.push_back(b);
+    }
+    (void)hipEventRecord(v[p.used[k]], st);
+  }
+  ~KnProfScope() {
+    if (!on) return;
+    (void)hipEventRecord(p.ev[k][p.used[k] + 1], st);
+    p.used[k] += 2;
+  }
+};
+// launches and summed time of the finished brackets of kernel k, which are forgotten; the caller has synchronised
+inline int kn_prof_read(KnProf& p, int k, int64_t* launches, double* total_ms) {
+  double sum = 0.0;
+  for (size_t i = 0; i + 1 < p.used[k]; i += 2) {
+    float ms = 0.f;
+    KN_HIP(hipEventElapsedTime(&ms, p.ev[k][i], p.ev[k][i + 1]));
+    sum += ms;
+  }
+  if (launches) *launches = (int64_t)(p.used[k] / 2);
+  if (total_ms) *total_ms = sum;
+  p.used[k] = 0;
+  return KNPEMI_OK;
+}
+
+struct KnDevice {
   int device = 0;
   hipStream_t stream = nullptr;          // main stream
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;   // timer pair (knpemi_timer_*, knpemi_dg_time_kernel)
+  std::vector<void*> allocs;             // everything hipMalloc'ed for the handle's lifetime
+  double* d_stage = nullptr; size_t stage_len = 0;   // staging buffer for strided field I/O
+  void* comm = nullptr;                  // RCCL communicator (comm_rccl.hip), NULL until knpemi_comm_init / knpemi_dg_comm_init
+  int comm_world = 1;
+  KnProf prof;
+};
+// device-count check, hipSetDevice, the non-blocking main stream and the timer pair; `who` starts the error texts
+inline int kn_device_open(KnDevice* h, int device, const std::string& who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return kn_fail(KNPEMI_EHIP, who + ": no HIP device visible (the hot path has no CPU fallback)");
+  if (device < 0 || device >= ndev) return kn_fail(KNPEMI_EINVAL, who + ": bad device index");
+  KN_HIP(hipSetDevice(device));
+  h->device = device;
+  KN_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  KN_HIP(hipEventCreate(&h->ev0));
+  KN_HIP(hipEventCreate(&h->ev1));
+  return KNPEMI_OK;
+}
+inline void kn_free_all(std::vector<void*>& owner) {
+  for (void* p : owner) (void)hipFree(p);
+  owner.clear();
+}
+// The one teardown order: synchronise, free `allocs`, free the communicator (kn_device_release), then destroy the events and
+// the stream.  What only one kind of handle owns is freed by that handle's destroy before these steps; knpemi_dg, whose
+// solver handle borrows the stream and goes after the communicator, releases first and closes last.
+inline void kn_device_release(KnDevice* h) {
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  kn_free_all(h->allocs);
+  kn_comm_free(h->comm);
+  h->comm = nullptr;
+}
+inline void kn_device_close(KnDevice* h) {
+  kn_device_release(h);
+  for (auto& v : h->prof.ev) for (hipEvent_t e : v) (void)hipEventDestroy(e);
+  if (h->ev0) (void)hipEventDestroy(h->ev0);
+  if (h->ev1) (void)hipEventDestroy(h->ev1);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+}
+
+// Device memory: n (at least one) elements, recorded in `owner` -- a handle's `allocs`, or a list that is freed at another
+// time (KnObserve::allocs, KnAmg::allocs).
+template <class T>
+int kn_alloc(std::vector<void*>& owner, size_t n, T** out) {
+  void* p = nullptr;
+  KN_HIP(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+  owner.push_back(p);
+  *out = static_cast<T*>(p);
+  return KNPEMI_OK;
+}
+template <class T>
+int kn_zeros(std::vector<void*>& owner, hipStream_t st, size_t n, T** out) {
+  if (int rc = kn_alloc(owner, n, out)) return rc;
+  // zero on the handle's own (non-blocking) stream: a null-stream hipMemset is not ordered with it
+  KN_HIP(hipMemsetAsync(*out, 0, std::max<size_t>(n, 1) * sizeof(T), st));
+  KN_HIP(hipStreamSynchronize(st));
+  return KNPEMI_OK;
+}
+template <class T, class U>
+int kn_upload(std::vector<void*>& owner, const T* src, size_t n, U** out) {
+  T* p = nullptr;
+  if (int rc = kn_alloc(owner, n, &p)) return rc;
+  if (n) KN_HIP(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+  *out = p;
+  return KNPEMI_OK;
+}
+template <class T, class U>
+int kn_upload(std::vector<void*>& owner, const std::vector<T>& v, U** out) { return kn_upload(owner, v.data(), v.size(), out); }
+// synchronous copies on stream `st`: ordered with the work enqueued on it, done when they return
+template <class T>
+int kn_to_host(hipStream_t st, T* host, const T* dev, size_t n) {
+  KN_HIP(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  KN_HIP(hipStreamSynchronize(st));
+  return KNPEMI_OK;
+}
+template <class T>
+int kn_to_device(hipStream_t st, T* dev, const T* host, size_t n) {
+  KN_HIP(hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, st));
+  KN_HIP(hipStreamSynchronize(st));
+  return KNPEMI_OK;
+}
+// The membrane ODE tables: host tables are row-major [dof][column], device tables [column][dof]: dst[c][r] = src[r][c]
+inline void kn_transpose(const double* src, double* dst, int rows, int cols) {
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
+}
+inline int kn_table_upload(hipStream_t st, const double* host, double* dev, int nq, int cols) {
+  std::vector<double> t((size_t)nq * cols);
+  kn_transpose(host, t.data(), nq, cols);
+  return kn_to_device(st, dev, t.data(), t.size());
+}
+inline int kn_table_download(hipStream_t st, const double* dev, double* host, int nq, int cols) {
+  std::vector<double> t((size_t)nq * cols);
+  if (int rc = kn_to_host(st, t.data(), dev, t.size())) return rc;
+  kn_transpose(t.data(), host, cols, nq);
+  return KNPEMI_OK;
+}
+
+struct knpemi_handle : KnDevice {
   hipStream_t aux = nullptr;             // auxiliary stream (EMI matrix assembly beside the ODE sweep)
   hipStream_t aux2 = nullptr;            // second auxiliary stream (ODE sweeps of further membrane models)
   hipEvent_t ev_join2 = nullptr;
@@ -292,7 +461,6 @@ struct knpemi_handle {
   int pre_pending = 0;
   hipStream_t cur = nullptr;             // stream the row-kernel launchers enqueue on (stream or aux)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int gdim = 0, cell_kind = 0, NV = 0, NF = 0, n_sub = 0, K = 0;
   std::vector<int> n_vert, n_cell, n_q, n_facet, n_models;
   std::vector<int> voff, coff, qoff, foff, moff;
@@ -308,16 +476,13 @@ struct knpemi_handle {
   KnHexGeo hex_geo{};
   int lds_doubles_emi = 0, lds_doubles_knp = 0; // per-block LDS segment sizes (doubles)
   int lds_uniq_max = 0;                         // most distinct vertices touched by one row block
-  std::vector<void*> allocs;  // everything hipMalloc'ed
   std::vector<void*> rtc_modules;   // hipModule_t of run-time compiled membrane models
   std::vector<KnOdeModel> ode; // [moff[n_sub]]
   bool ode_only = false;       // knpemi_ode_create: membrane models without a mesh (no PDE fields)
   // host copies of patterns for export
   std::vector<int> h_rowptr, h_colind, h_rowptrL, h_colindL;
-  void* comm = nullptr;                              // RCCL communicator (comm_rccl.hip), NULL until knpemi_comm_init
-  int comm_rank = 0, comm_world = 1;
+  int comm_rank = 0;
   KnVecPlan vec_plan[2];                             // [KNPEMI_B_EMI], [KNPEMI_B_KNP]
-  double* d_stage = nullptr; size_t stage_len = 0;   // staging buffer for strided field I/O
   double* kry = nullptr; size_t kry_n = 0;           // Krylov workspace (kernels_krylov.hip)
   int kry_ones_masked = 0;                           // the workspace's `ones` vector currently holds the ownership mask
   void* kry_pinned = nullptr;                        // pinned host buffer the solvers' scalars are read through
@@ -357,8 +522,6 @@ struct knpemi_handle {
   int gam_split = 1;
   int fold_membrane = 1;               // KNPEMI_OPT_FOLD_MEMBRANE: form them in the write-back launch of the potential
   int emi_flags = 0;                   // flags of the last knpemi_assemble_emi (the splitting scheme the step runs with)
-  int prof_stride = 1;                 // KNPEMI_OPT_PROFILE_STRIDE
-  unsigned prof_count[16] = {0};
   int lds_gam_max = 0;                 // most membrane entries of one row block
   bool blocks_clustered = false;       // row blocks are clusters of row chunks (default), not consecutive rows
   KnDist dist;
@@ -384,53 +547,14 @@ struct knpemi_handle {
     void* ctx = nullptr;
     std::vector<void*> allocs;
   } obs;
-  // per-kernel event profiling (knpemi_profile)
-  uint32_t prof_mask = 0;
-  std::vector<hipEvent_t> prof_ev[KNPEMI_N_KERNELS];  // begin/end pairs
-  size_t prof_used[KNPEMI_N_KERNELS] = {};
 };
 
 inline void kn_inputs_changed(knpemi_handle* h) { ++h->inputs_gen; }
 inline void kn_gam_formed(knpemi_handle* h, int split) { h->gam_gen = h->inputs_gen; h->gam_split = split; }
 inline bool kn_gam_current(const knpemi_handle* h, int split) { return h->gam_gen == h->inputs_gen && h->gam_split == split; }
 
-// RAII bracket around one kernel launch; no-op unless the kernel's bit is set in prof_mask.
-struct KnProfScope {
-  knpemi_handle* h; int k; bool on;
-  KnProfScope(knpemi_handle* h_, int k_) : h(h_), k(k_), on((h_->prof_mask >> k_) & 1u) {
-    // KNPEMI_OPT_PROFILE_STRIDE: bracket every n-th launch only (an event pair around a kernel on the critical path
-    // costs the step several microseconds)
-    if (on && h->prof_stride > 1 && (h->prof_count[k]++ % h->prof_stride) != 0) on = false;
-    if (!on) return;
-    auto& v = h->prof_ev[k];
-    if (h->prof_used[k] + 2 > v.size()) {
-      hipEvent_t a, b;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
-      v.push_back(a); v.push_back(b);
-    }
-    (void)hipEventRecord(v[h->prof_used[k]], h->cur);
-  }
-  ~KnProfScope() {
-    if (!on) return;
-    (void)hipEventRecord(h->prof_ev[k][h->prof_used[k] + 1], h->cur);
-    h->prof_used[k] += 2;
-  }
-};
-
-// error plumbing ------------------------------------------------------------------------------
-void kn_set_error(const std::string& msg);
-#define KN_HIP(call)                                                                     \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      kn_set_error(std::string(#call) + ": " + hipGetErrorString(e_));                   \
-      return KNPEMI_EHIP;                                                                \
-    }                                                                                    \
-  } while (0)
-
 void kn_comm_destroy(knpemi_handle* h);   // comm_rccl.hip
 int kn_comm_create(int device, int rank, int world, const char* id_bytes, size_t len, void** out);
-void kn_comm_free(void* comm);
 int kn_comm_sendrecv(void* comm, int world, int device, hipStream_t stream, const double* send_buf_dev, double* recv_buf_dev,
                      int n_parts, const int32_t* peer, const int64_t* send_off, const int64_t* send_cnt,
                      const int64_t* recv_off, const int64_t* recv_cnt);

@@ -41,13 +41,6 @@ void with_model(int model_id, F&& f) {
     default: f(OdeModelTag<ModelGlial, 1>{}); break;
   }
 }
-// after a kernel launch: KNPEMI_OK, or KNPEMI_EHIP with "<kernel>: <HIP's message>"
-inline int kn_launch_check(const char* kernel) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return KNPEMI_OK;
-  kn_set_error(std::string(kernel) + ": " + hipGetErrorString(e));
-  return KNPEMI_EHIP;
-}
 
 // ---- the sweeps ---------------------------------------------------------------------------------------------------
 // kernels_ode.hip: one entry per kernel shape, integrator and model source chosen inside
@@ -57,7 +50,7 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
                    int32_t* steps_taken, int32_t* failed_step);
 // the LSODA step of a shipped model over a caller-described table (the DG variant: membrane nodes of the broken space)
 int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef);
-int kn_lsoda_coef_upload(void** out);   // LsodaCoef tables on the device; the caller owns *out
+int kn_lsoda_coef_upload(std::vector<void*>& owner, const void** out);   // LsodaCoef tables on the device, owned by `owner`
 // kernels_ode_fixed.hip: the fixed-step kernels of the shipped models (m.method, m.n_substeps)
 int kn_launch_ode_fixed_step(hipStream_t st, const KnOdeModel& m, const OdeDev& dv, const OdeArgs& a);
 int kn_launch_ode_fixed_advance(hipStream_t st, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs& v);
@@ -78,9 +71,4 @@ int kn_ode_read_stats(hipStream_t st, unsigned long long* d_stats, int n_blocks,
 inline std::string kn_ode_failure(bool lsoda, const std::string& where) {
   return lsoda ? "LSODA failed on " + where + " (odeSolver.py:121 `assert success`)"
                : "the fixed-step integrator left a non-finite state on " + where;
-}
-// host tables are row-major [dof][column], device tables [column][dof]: dst[c][r] = src[r][c]
-inline void kn_transpose(const double* src, double* dst, int rows, int cols) {
-  for (int r = 0; r < rows; ++r)
-    for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + r] = src[(size_t)r * cols + c];
 }
