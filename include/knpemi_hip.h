@@ -327,6 +327,14 @@ int knpemi_debug_launch_chain(knpemi_handle* h, int kind, int n, int links, int 
  * parallelepipeds, bit 2 = ... and all the same box (uniform hexahedral kernels). */
 int knpemi_debug_geometry(knpemi_handle* h, int* flags);
 
+/* Diagnostics (no reference counterpart): the sizes of the row-kernel layout knpemi_create built, so that a test can tell
+ * which code a mesh reaches.  Fills out[0 .. min(n, 8)): 0 = longest row of the EMI pattern (membrane coupling included),
+ * 1 = lanes per row, 2 = most (row, cell) pairs on one lane (more than 8: the loop after the prefetched pairs runs),
+ * 3 = most distinct vertices of one row block (more than 768: the staging loop for oversized blocks runs), 4 = most
+ * membrane entries on one row, 5 / 6 = dynamic LDS bytes of the latest EMI / KNP row launch (0 before the first),
+ * 7 = longest row of the Laplacian pattern (the one the 8-bit pair slots index; more than 31 excludes the lattice path). */
+int knpemi_debug_layout(knpemi_handle* h, int* out, int n);
+
 /* End-of-step update: update_pde_variables (utils.py:238-295): c_prev <- c, eliminated ion from
  * electroneutrality, phi_M_prev <- tr(phi_i) - tr(phi_e). */
 int knpemi_update_pde(knpemi_handle* h);

@@ -1874,6 +1874,7 @@ static int launch_emi_v2(knpemi_handle* h, int want_p, int split) {
   const bool ut = GDIM == 3 && h->tet_uniform && D.tet_tab;
   const size_t lds = ((size_t)acc_n + (ut ? 2 : 5) * (size_t)rec_n + 1 + (ut ? KN_TET_TAB : 0)) * sizeof(double) + 2 * (size_t)h->lds_doubles_knp + 16;
   if (lds > 160 * 1024) { kn_set_error("EMI row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
+  h->lds_bytes_emi = lds;
   dim3 grid(D.nblocks), block(KN_BLOCK);
   int rc = 0;
 #define KN_CASE2(L, U)                                                                              \
@@ -1920,6 +1921,7 @@ static int launch_knp_v2(knpemi_handle* h, int split, int pre) {
   const size_t lds = ((size_t)KS * acc_n + (ut ? KS + 1 : 4 + KS) * (size_t)rec_n + 1 + (ut ? KN_TET_TAB : 0) + (size_t)KS * gam_n) * sizeof(double)
                      + 2 * (size_t)h->lds_doubles_knp + 16;
   if (lds > 160 * 1024) { kn_set_error("KNP row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
+  h->lds_bytes_knp = lds;
   dim3 grid(D.nblocks), block(KN_BLOCK);
   int rc = 0;
   const int mem = pre ? 2 : (gam_n > 0 ? 1 : 0);
@@ -1950,6 +1952,7 @@ static int launch_emi_hex_v2(knpemi_handle* h, int want_p, int split) {
   const int geo = h->hex_uniform ? 2 : (h->hex_affine ? 1 : 0);
   const size_t lds = ((size_t)acc_n + (geo == 2 ? 2 : 5) * (size_t)rec_n + 1) * sizeof(double) + 2 * (size_t)h->lds_doubles_knp + 16;
   if (lds > 160 * 1024) { kn_set_error("EMI row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
+  h->lds_bytes_emi = lds;
   dim3 grid(D.nblocks), block(KN_BLOCK);
   int rc = 0;
 #define KN_CASE2(L, GEO)                                                                            \
@@ -1978,6 +1981,7 @@ static int launch_knp_hex_v2(knpemi_handle* h, int split, int pre) {
   const size_t lds = ((size_t)KS * acc_n + (geo == 2 ? KS + 1 : 4 + KS) * (size_t)rec_n + 1 + (size_t)KS * gam_n) * sizeof(double)
                      + 2 * (size_t)h->lds_doubles_knp + 16;
   if (lds > 160 * 1024) { kn_set_error("KNP row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
+  h->lds_bytes_knp = lds;
   dim3 grid(D.nblocks), block(KN_BLOCK);
   int rc = 0;
   const int mem = pre ? 2 : (gam_n > 0 ? 1 : 0);

@@ -526,7 +526,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
             double x = 0.0;
             for (int a = 0; a < 3; ++a) x += Ei[t][a] * (VR[(size_t)cv[i] * KN_REC + a] - VR[(size_t)cv[0] * KN_REC + a]);
             const double r = std::nearbyint(x);
-            if (std::fabs(x - r) > 1e-6 || std::fabs(r) > 1.0) { ok = false; break; }
+            if (std::fabs(x - r) > 1e-9 || std::fabs(r) > 1.0) { ok = false; break; }   // in grid cells, as the hexahedral check
             l[i][t] = (int)r;
           }
         if (!ok) break;
@@ -731,6 +731,9 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
           ri[1] = ri[0] + lapoff[g];
           if (ri[1] > 0xFFFF || ne > 0x7FFF) return kn_fail(KNPEMI_EINVAL, "row block too large for the packed row descriptor");
           ri[1] |= ne << 16;
+          h->lay_ne_max = std::max(h->lay_ne_max, ne);
+          h->lay_row_max = std::max(h->lay_row_max, rowptr[g + 1] - rowptr[g]);
+          h->lay_rowL_max = std::max(h->lay_rowL_max, rowptrL[g + 1] - rowptrL[g]);
           ri[2] = offL + (rowptrL[g] - rowptrL[g0]);
           ri[3] = m < 0 ? 0 : mptr[m];
         }
@@ -751,6 +754,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
       const int64_t np = (sl_ptr[(size_t)b * SPB + w + 1] - sl_ptr[(size_t)b * SPB + w]) / KN_SLICE;
       if (np > 255) return kn_fail(KNPEMI_EINVAL, "a vertex has too many incident cells for the pair layout");
       steps |= (uint32_t)np << (8 * w);
+      h->lay_np_max = std::max(h->lay_np_max, (int)np);
     }
     bi[12] = (int)steps;
     if (!h->blocks_clustered) {   // membrane entries of the block's rows (entries are sorted by row: one range)
@@ -2030,5 +2034,13 @@ extern "C" int knpemi_timer_stop_ms(knpemi_handle* h, double* ms) {
 extern "C" int knpemi_debug_geometry(knpemi_handle* h, int* flags) {
   if (!h || !flags) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_geometry: null argument");
   *flags = (h->tet_uniform ? 1 : 0) | (h->hex_affine ? 2 : 0) | (h->hex_uniform ? 4 : 0);
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_debug_layout(knpemi_handle* h, int* out, int n) {
+  if (!h || !out || n < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_layout: null argument");
+  const int v[8] = {h->lay_row_max, h->lpr, h->lay_np_max, h->lds_uniq_max, h->lay_ne_max,
+                    (int)h->lds_bytes_emi, (int)h->lds_bytes_knp, h->lay_rowL_max};
+  for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
   return KNPEMI_OK;
 }

@@ -476,6 +476,10 @@ struct knpemi_handle : KnDevice {
   KnHexGeo hex_geo{};
   int lds_doubles_emi = 0, lds_doubles_knp = 0; // per-block LDS segment sizes (doubles)
   int lds_uniq_max = 0;                         // most distinct vertices touched by one row block
+  // what knpemi_debug_layout reports: longest row of the EMI / Laplacian pattern, most pairs on one lane, most membrane
+  // entries on one row; dynamic LDS of the latest EMI / KNP row launch (0: not launched yet)
+  int lay_row_max = 0, lay_rowL_max = 0, lay_np_max = 0, lay_ne_max = 0;
+  size_t lds_bytes_emi = 0, lds_bytes_knp = 0;
   std::vector<void*> rtc_modules;   // hipModule_t of run-time compiled membrane models
   std::vector<KnOdeModel> ode; // [moff[n_sub]]
   bool ode_only = false;       // knpemi_ode_create: membrane models without a mesh (no PDE fields)

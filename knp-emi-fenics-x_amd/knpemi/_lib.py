@@ -152,6 +152,7 @@ SIGNATURES = {
     "knpemi_debug_math": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_debug_launch_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dbl_p]),
     "knpemi_debug_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "knpemi_debug_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "knpemi_update_pde": (C.c_int, [C.c_void_p]),
     "knpemi_observe_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_int64), c_int_p, c_dbl_p, c_dbl_p,
                                      C.c_int]),

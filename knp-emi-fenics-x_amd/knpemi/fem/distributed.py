@@ -450,15 +450,15 @@ class VertexHalo(Halo):
         return plans
 
 
-def make_partitioned_problem(kind, r, rank, world, g_syn=10.0, length=None, method="rcb", gather=None):
+def make_partitioned_problem(kind, r, rank, world, g_syn=10.0, length=None, method="rcb", gather=None, mesh_data=None):
     """The rank-local driver set-up (examples/idealized_geometries/setup_problem.Setup) of a partitioned idealized
     box: global mesh `make_mesh_3D(r, kind, l=length)` (default length 2 * world: weak scaling), cells partitioned
-    with `method` in {"rcb", "slab"}."""
+    with `method` in {"rcb", "slab"}.  `mesh_data` = (mesh, ct, ft): that global mesh instead (the same on every rank)."""
     from setup_problem import Setup
     from .idealized import make_mesh_3D
     cell_type = {"tet": "tetrahedron", "hex": "hexahedron"}[kind]
     l = 2 * world if length is None else int(length)
-    mesh, ct, ft = make_mesh_3D(r, cell_type, l=l)
+    mesh, ct, ft = mesh_data if mesh_data is not None else make_mesh_3D(r, cell_type, l=l)
     cent = mesh.x[mesh.cells].mean(axis=1)
     part = rcb_partition(cent, world) if method == "rcb" else slab_partition(cent, world)
     local = LocalPart(mesh, ct, ft, part, rank, world)

@@ -60,6 +60,17 @@ def test_general_partition_device_steps_equal_single_rank_bit_for_bit(kind, meth
 
 
 @pytest.mark.gpu
+def test_jittered_shuffled_tetrahedra_on_two_ranks_equal_single_rank_bit_for_bit():
+    """The same check on general tetrahedra: the r = 0 box with every vertex moved by up to 20 % of the smallest spacing and
+    vertices, cells and the vertex order inside every cell shuffled (tests/unstructured_meshes.py), cut in two by recursive
+    coordinate bisection.  The general row kernels and the strips of knpemi_create see each cell in another position on a
+    rank than on the whole mesh; owned rows of both right-hand sides and the owned membrane fields agree bit for bit."""
+    rcs, outs = _run_ranks(["--kind", "tet", "--steps", "3", "--method", "rcb", "--mesh", "jittered"])
+    assert rcs == [0, 0], "\n".join(outs)
+    assert "PARTITION STEPS OK" in outs[0], outs[0]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kind,method", [("tet", "rcb"), ("tet", "slabgen"), ("hex", "slab")])
 def test_two_rank_time_steps_with_distributed_solves(kind, method):
     """Whole time steps on a partitioned problem: knpemi_solve_emi / knpemi_solve_knp as distributed solves (halo'd

@@ -6,28 +6,13 @@ import numpy as np
 import pytest
 
 from helpers import Setup, csr_rel_err, rel_err
+from helpers import assemble_both as _assemble_both
+from helpers import check_facet_integrals_of_the_write_back_launch
 from knpemi import _lib as L
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-10   # stated fp64 tolerance for assembled operators
-
-
-def _assemble_both(s, splitting=True):
-    from knpemi.pdeSolver import create_solver_emi, create_solver_knp
-    o, P, params, ions = s.oracle()
-    c_all, phi, phiM, mm = s.oracle_fields()
-    for f in (s.a_emi, s.a_knp):
-        f.shared['splitting_scheme'] = splitting
-    emi = create_solver_emi(s.a_emi, s.L_emi, s.phi, s.entity_maps, s.subdomain_list, None,
-                            p=s.p_emi, direct=False)
-    knp = create_solver_knp(s.a_knp, s.L_knp, s.c, s.entity_maps, s.subdomain_list, None, p=s.p_knp)
-    A, b = emi.assemble()
-    Ak, bk = knp.assemble()
-    Ao, Po, bo = o.assemble_emi(P, params, ions, c_all, phiM, mm, splitting_scheme=splitting)
-    Ako, bko = o.assemble_knp(P, params, ions, c_all, phi, phiM, mm, s.dt, splitting_scheme=splitting)
-    return dict(A_emi=csr_rel_err(A, Ao), P_emi=csr_rel_err(emi.P, Po), b_emi=rel_err(b, bo),
-                A_knp=csr_rel_err(Ak, Ako), b_knp=rel_err(bk, bko)), (A, emi.P, b, Ak, bk)
 
 
 @pytest.mark.parametrize("kind,r", [("2d", 1), ("2d", 2), ("tet", 0), ("hex", 0)])
@@ -365,38 +350,9 @@ def test_facet_integrals_formed_in_the_potential_write_back_launch(hip_lib, kind
     steps; knpemi_solve_emi's own write-back in the solver tests) also forms the membrane-facet integrals of b_knp
     (knpWeakForm.py:168-214).  b_knp equals the one assembled with the facet kernel as a launch of its own bit for bit and
     matches the oracle; the stored integrals are dropped as soon as one of their inputs changes (phi_M here)."""
-    from knpemi.pdeSolver import create_solver_emi, create_solver_knp
     s = Setup(kind, r)
     s.perturb()
-    o, P, params, ions = s.oracle()
-    emi = create_solver_emi(s.a_emi, s.L_emi, s.phi, s.entity_maps, s.subdomain_list, None, p=s.p_emi, direct=False)
-    knp = create_solver_knp(s.a_knp, s.L_knp, s.c, s.entity_maps, s.subdomain_list, None, p=s.p_knp)
-    emi.assemble()
-    knp.assemble()                              # pushes every field; facet kernel as its own launch
-    dp = knp.dp
-    ref = dp.rhs(L.B_KNP).copy()
-    phi_all = np.concatenate([s.phi[t].x._a for t in s.subdomain_list])
-    hip = C.CDLL("libamdhip64.so")
-    dev = C.c_void_p()
-    assert hip.hipMalloc(C.byref(dev), C.c_size_t(phi_all.nbytes)) == 0
-    assert hip.hipMemcpy(dev, phi_all.ctypes.data_as(C.c_void_p), C.c_size_t(phi_all.nbytes), 1) == 0
-    out = {}
-    for fold in (1, 0):
-        L.check(dp.lib.knpemi_set_option(dp.h, L.OPT_FOLD_MEMBRANE, fold))
-        dp.set_rhs(L.B_KNP, np.full(len(ref), np.nan))
-        L.check(dp.lib.knpemi_set_solution(dp.h, L.B_EMI, dev, 1))         # paste on the device
-        L.check(dp.lib.knpemi_assemble_knp(dp.h, 0))
-        out[fold] = dp.rhs(L.B_KNP).copy()
-    assert np.array_equal(out[1], out[0]) and np.array_equal(out[1], ref)
-    # an input changes after the potential was written back: the stored integrals must not be used
-    L.check(dp.lib.knpemi_set_option(dp.h, L.OPT_FOLD_MEMBRANE, 1))
-    L.check(dp.lib.knpemi_set_solution(dp.h, L.B_EMI, dev, 1))
-    s.phi_M_prev[1].x.array[:] = s.phi_M_prev[1].x._a + 1e-3
-    _, fresh = knp.assemble()                   # pushes the new phi_M (knpemi_set_field), then assembles
-    c_all, phi, phiM, mm = s.oracle_fields()
-    _, bko = o.assemble_knp(P, params, ions, c_all, phi, phiM, mm, s.dt)
-    assert rel_err(fresh, bko) < TOL and not np.array_equal(fresh, ref)
-    hip.hipFree(dev)
+    check_facet_integrals_of_the_write_back_launch(s)
 
 
 # The facet integrals formed by the write-back of the potential are reused only while none of their inputs has changed.

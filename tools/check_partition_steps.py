@@ -118,6 +118,9 @@ def main():
     ap.add_argument("--ode-method", default="lsoda", choices=["lsoda", "euler", "rk4", "rush_larsen"],
                     help="membrane integrator of both runs (DeviceStepper(ode_method=...))")
     ap.add_argument("--ode-substeps", type=int, default=None)
+    ap.add_argument("--mesh", default="box", choices=["box", "jittered"],
+                    help="jittered (with --method rcb / slab, --kind tet): the box with every vertex moved and vertices, cells "
+                         "and the vertex order inside the cells shuffled (tests/unstructured_meshes.py: jittered_tet_box)")
     a = ap.parse_args()
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     torch.cuda.set_device(0)
@@ -139,6 +142,12 @@ def main():
                    z_L=-1.0, z_U=0.2e-4)
         if a.method == "slabgen":
             a.method = "slab"
+    mesh_data = None
+    if a.mesh == "jittered":
+        assert not astro and a.kind == "tet" and a.method != "slabgen"
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from unstructured_meshes import jittered_tet_box
+        mesh_data = jittered_tet_box(r=a.resolution, l=2 * world)      # seeded: the same mesh on every rank
     with contextlib.redirect_stdout(io.StringIO()):
         if astro:
             from knpemi.fem.distributed import make_partitioned_astro
@@ -147,7 +156,7 @@ def main():
             s = make_slab_problem(a.kind, a.resolution, rank, world, g_syn=10.0)
         else:
             from knpemi.fem.distributed import make_partitioned_problem
-            s = make_partitioned_problem(a.kind, a.resolution, rank, world, g_syn=10.0, method=a.method)
+            s = make_partitioned_problem(a.kind, a.resolution, rank, world, g_syn=10.0, method=a.method, mesh_data=mesh_data)
     L_x = s.global_length
     init_fields(s, L_x, scale, v_rest)
     loc = run(s, a.steps, s.halo, not a.no_mem_halo, solves, a.jacobi, a.ode_method, a.ode_substeps)
@@ -172,7 +181,13 @@ def main():
             if astro:
                 g = rsd.Problem(cfg)
             else:
-                g = Setup(a.kind, a.resolution, g_syn=10.0, mesh_data=make_mesh_3D(a.resolution, ctype, l=2 * world))
+                g = Setup(a.kind, a.resolution, g_syn=10.0,
+                          mesh_data=mesh_data or make_mesh_3D(a.resolution, ctype, l=2 * world))
+                if mesh_data is not None:
+                    import ctypes
+                    flags = ctypes.c_int(-1)
+                    g.a_emi.dp.lib.knpemi_debug_geometry(g.a_emi.dp.h, ctypes.byref(flags))
+                    assert not flags.value & 1, "the jittered mesh must run the general tetrahedron kernels"
         init_fields(g, L_x, scale, v_rest)
         ref = run(g, a.steps, None, True, solves, a.jacobi, a.ode_method, a.ode_substeps)
         its_ref = ref.pop("iterations")
