@@ -66,6 +66,87 @@ struct StridedRow {   // p[j] of dof q in a [column][dof] table: base + j * S
 };
 
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)
+// The parameter row of a dof as the sweep sees it: the row in the global table plus the wave's copy of it in LDS.
+// A store goes to both; a load comes from the copy.  The sweep stores the traces and the stimulus into the row and
+// `prepare` then reads the whole row, `finish` stores the currents and the write-back reads them again -- through
+// runtime column indices, so the compiler cannot forward the values, and in global memory each of the two is a store,
+// a wait for it and a dependent load: a memory round trip at the head and one at the tail of a sweep whose length is
+// the latency of one wave.  In LDS the same pair costs a hundred cycles.  The models keep indexing `p[j]`.
+// All lanes that work on a dof (its components, the lanes that mirror it, the lanes past the last dof that repeat it)
+// share ONE column of the copy, as they share the row in the table: what the owner's `finish` stores is what the other
+// lanes of the dof read next (ode_advance_body), exactly as through memory.  A dof belongs to one wave, a workgroup is
+// one wave, and a wave's LDS accesses complete in order: no barrier is needed between such a store and load.
+template <int COLS>
+struct StagedRow {
+  double* g;        // this dof's row in the transposed table: entry j at g[j * stride]
+  size_t stride;
+  double* l;        // its column of the LDS copy: entry j at l[j * COLS]
+  struct Ref {
+    double* g;
+    double* l;
+    __device__ __forceinline__ operator double() const { return *l; }
+    __device__ __forceinline__ void operator=(double v) const { *g = v; *l = v; }
+    __device__ __forceinline__ void operator=(const Ref& o) const { *this = (double)o; }
+  };
+  __device__ __forceinline__ Ref operator[](int j) const { return Ref{g + (size_t)j * stride, l + j * COLS}; }
+  // entry j of the copy alone (staging: the value was just loaded from the table)
+  __device__ __forceinline__ void stage(int j, double v) const { l[j * COLS] = v; }
+};
+
+// The copy takes NP columns-of-dofs doubles of LDS; a plug-in with a long parameter row at one thread per dof (up to 128
+// x 64 doubles) works on the table itself, as every sweep did before.
+template <class M, int LANES>
+struct OdeRowKind {
+  static constexpr int COLS = ODE_BLOCK / LANES;                         // dofs of a full wave
+  static constexpr bool STAGED = M::NP * COLS * 8 <= 12 * 1024;         // shipped models: 2.8 kB (HH), 11.5 kB (glial)
+  static constexpr int LDS_DOUBLES = STAGED ? M::NP * COLS : 1;
+};
+template <bool STAGED, int COLS>
+struct OdeRow : StagedRow<COLS> {
+  __device__ __forceinline__ OdeRow(double* g_, size_t stride_, double* lds, int col) : StagedRow<COLS>{g_, stride_, lds + col} {}
+  // issue the loads of the whole row (they travel with the sweep's other first loads) ...
+  template <int NP>
+  __device__ __forceinline__ void load(double (&r)[NP]) const {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) r[j] = this->g[(size_t)j * this->stride];
+  }
+  // ... and put them into the copy
+  template <int NP>
+  __device__ __forceinline__ void stage_all(const double (&r)[NP]) const {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) this->stage(j, r[j]);
+  }
+};
+template <int COLS>
+struct OdeRow<false, COLS> : StridedRow<0> {
+  __device__ __forceinline__ OdeRow(double* g_, size_t stride_, double*, int) : StridedRow<0>{g_, stride_} {}
+  template <int NP>
+  __device__ __forceinline__ void load(double (&)[NP]) const {}
+  template <int NP>
+  __device__ __forceinline__ void stage_all(const double (&)[NP]) const {}
+};
+
+// the workgroup's copy of LSODA's coefficient tables: loads first (beside the sweep's other first loads), LDS stores
+// later; the caller's barrier makes the copy visible
+constexpr int KN_COEF_DOUBLES = (int)(sizeof(LsodaCoef) / sizeof(double));
+constexpr int KN_COEF_PER_LANE = (KN_COEF_DOUBLES + ODE_BLOCK - 1) / ODE_BLOCK;
+__device__ __forceinline__ void kn_coef_load(const LsodaCoef* __restrict__ cf, double (&c)[KN_COEF_PER_LANE]) {
+  const double* src = reinterpret_cast<const double*>(cf);
+#pragma unroll
+  for (int i = 0; i < KN_COEF_PER_LANE; ++i) {
+    const int k = i * ODE_BLOCK + (int)threadIdx.x;
+    c[i] = ((i + 1) * ODE_BLOCK <= KN_COEF_DOUBLES || k < KN_COEF_DOUBLES) ? src[k] : 0.0;
+  }
+}
+__device__ __forceinline__ void kn_coef_store(LsodaCoef* scf, const double (&c)[KN_COEF_PER_LANE]) {
+  double* dst = reinterpret_cast<double*>(scf);
+#pragma unroll
+  for (int i = 0; i < KN_COEF_PER_LANE; ++i) {
+    const int k = i * ODE_BLOCK + (int)threadIdx.x;
+    if ((i + 1) * ODE_BLOCK <= KN_COEF_DOUBLES || k < KN_COEF_DOUBLES) dst[k] = c[i];
+  }
+}
+
 // LANES = M::NS: lane c of every group of NS adjacent lanes integrates component c of one membrane dof
 // (lsoda_core.h); LANES = 1: one thread per dof (one-state models).
 // WAVES = 2 caps the register budget at 256 per lane so that two waves share a SIMD.  It pays once there are more
@@ -76,15 +157,11 @@ __device__ __forceinline__ void ode_step_body(const OdeDev& D, const OdeArgs& a,
   constexpr int NI = Integrator::NI;
   // factorised iteration matrix + pivots of the BDF method, one column per lane (touched by stiff dofs only)
   __shared__ double work[Integrator::WORK * ODE_BLOCK];
-  // LSODA's coefficient tables (4 kB) are consulted with a per-lane order index whenever an order changes: keep the
+  // LSODA's coefficient tables (5 kB) are consulted with a per-lane order index whenever an order changes: keep the
   // workgroup's copy in LDS.  Everything else the non-stiff integrator touches lives in registers.
   __shared__ LsodaCoef scf;
-  {
-    const double* src = reinterpret_cast<const double*>(cf);
-    double* dst = reinterpret_cast<double*>(&scf);
-    for (int i = threadIdx.x; i < (int)(sizeof(LsodaCoef) / sizeof(double)); i += ODE_BLOCK) dst[i] = src[i];
-    __syncthreads();
-  }
+  using Kind = OdeRowKind<M, LANES>;
+  __shared__ double rowbuf[Kind::LDS_DOUBLES];   // the wave's copy of its dofs' parameter rows (StagedRow)
   // Dofs per wavefront.  A wave runs the UNION of the trips of its dofs' phase machines, and an instruction costs the same
   // whatever the exec mask: with 64 / LANES dofs per wave ~10 % of the stream is other dofs' trips.  While the sweep has fewer
   // waves than the chip has SIMDs (config 2: 185 on 1 024) the idle SIMDs buy that back: `dpw` dofs per wave, the other
@@ -100,35 +177,65 @@ __device__ __forceinline__ void ode_step_body(const OdeDev& D, const OdeArgs& a,
   const bool live = primary && qw < a.nq;
   const int q = qw < a.nq ? qw : a.nq - 1, comp = threadIdx.x % LANES;
   const int qg = a.q0 + q;
-  const StridedRow<0> p{a.params + q, (size_t)a.nq};   // this dof's parameter row in the transposed table
+  const int col = q - (int)blockIdx.x * dpw;   // the dof's place in its wave, 0 <= col < dpw
+  // this dof's parameter row in the transposed table, and its column of the wave's copy
+  const OdeRow<Kind::STAGED, FULL> p(a.params + q, (size_t)a.nq, rowbuf, col > 0 ? col : 0);
+  // Everything the head reads that depends on nothing but the arguments is requested at once -- coefficient tables,
+  // state, the whole parameter row, the vertex numbers, V, the mask: ONE memory latency -- then the two vertex records
+  // (a second one).  Before, the coefficient copy and its barrier came first, and the row was read back from memory after
+  // the stores of step 1 and 2 had landed: five latencies in a row at the head of every wave.
+  const bool traces = a.flags & KN_ODE_SET_TRACES, set_v = a.flags & KN_ODE_SET_V;
+  double coef[KN_COEF_PER_LANE], row[M::NP];
+  kn_coef_load(cf, coef);
   double y[NI];
 #pragma unroll
   for (int j = 0; j < NI; ++j) y[j] = a.states[(size_t)(comp + j) * a.nq + q];
-  // 1. concentration traces (record components 4..6 hold c_0, c_1, c_eliminated) -> parameter columns.
-  //    With several lanes per dof every lane writes the same values and later reads only its own stores.
-  if (a.flags & KN_ODE_SET_TRACES) {
-    const double* re = D.VR + (size_t)D.q2e[qg] * KN_ODE_REC;
-    const double* ri = D.VR + (size_t)D.q2i[qg] * KN_ODE_REC;
-    for (int k = 0; k < a.n_ions; ++k) {
-      p[a.ion_param[3 * k]] = re[KN_ODE_CSLOT(k)];
-      p[a.ion_param[3 * k + 1]] = ri[KN_ODE_CSLOT(k)];
-    }
+  p.load(row);
+  int ve = 0, vi = 0;
+  if (traces) { ve = D.q2e[qg]; vi = D.q2i[qg]; }
+  double v = 0.0;
+  if (set_v) v = D.phiM[qg];
+  int in_mask = 1;
+  if (a.n_stim > 0 && a.mask) in_mask = a.mask[q];
+  double ce[KN_ODE_MAXK] = {0.0, 0.0, 0.0, 0.0}, ci[KN_ODE_MAXK] = {0.0, 0.0, 0.0, 0.0};
+  if (traces) {
+    const double* re = D.VR + (size_t)ve * KN_ODE_REC;
+    const double* ri = D.VR + (size_t)vi * KN_ODE_REC;
+#pragma unroll
+    for (int k = 0; k < KN_ODE_MAXK; ++k)
+      if (k < a.n_ions) { ce[k] = re[KN_ODE_CSLOT(k)]; ci[k] = ri[KN_ODE_CSLOT(k)]; }
   }
-  if (a.flags & KN_ODE_SET_V) {
-    const double v = D.phiM[qg];
+  // (the mask byte is first looked at here, behind the loads of the records: tested where it is loaded, it is waited for
+  // there, a memory latency of its own)
+  asm volatile("" : "+v"(in_mask));
+  const bool stim = a.n_stim > 0 && in_mask;
+  kn_coef_store(&scf, coef);
+  p.stage_all(row);
+  // 1. concentration traces (record components 4..6 hold c_0, c_1, c_eliminated) -> parameter columns.
+  //    With several lanes per dof every lane writes the same values.
+  if (traces) {
+#pragma unroll
+    for (int k = 0; k < KN_ODE_MAXK; ++k)
+      if (k < a.n_ions) {
+        p[a.ion_param[3 * k]] = ce[k];
+        p[a.ion_param[3 * k + 1]] = ci[k];
+      }
+  }
+  if (set_v) {
 #pragma unroll
     for (int j = 0; j < NI; ++j) y[j] = (comp + j == a.v_index) ? v : y[j];
   }
   // 2. stimulus + LSODA (the parameter row is read once by prepare(); only the currents change)
-  if (a.n_stim > 0 && (!a.mask || a.mask[q]))
+  if (stim)
     for (int i = 0; i < a.n_stim; ++i) p[a.stim_idx[i]] = a.stim_val[i];
+  __syncthreads();   // the coefficient tables are in place
   Integrator s;
   if constexpr (STAMPS) s.st_last = __builtin_amdgcn_s_memtime();
   s.f.prepare(p);
   if constexpr (LANES > 1) kn_model_set_lane(s.f, comp, 0);
   const int rc = s.integrate(&scf, work + threadIdx.x, y, a.t0, a.t0 + a.dt, a.rtol, a.atol, 10000, comp);
   // 3. write back: state row, phi_M_prev <- V; the lane that owns V stores the currents (the reference's
-  //    RHS side effect) into the parameter row and the I_ch_k fields
+  //    RHS side effect) into the parameter row and the I_ch_k fields (read from the row's copy, not from memory)
   const bool owner = live && (LANES == 1 || comp == M::CURRENT_LANE);
   if (live) {
 #pragma unroll
@@ -142,8 +249,8 @@ __device__ __forceinline__ void ode_step_body(const OdeDev& D, const OdeArgs& a,
     for (int k = 0; k < a.n_ions; ++k)
       D.Ich[((size_t)a.model_slot * KN_ODE_MAXK + k) * a.NQtot + qg] = p[a.ion_param[3 * k + 2]];
   }
-  // counters: summed over the wave, then added to this workgroup's own slot -- no atomics (thousands of atomic adds
-  // to one word serialise at ~90 per microsecond: the tail of the sweep); knpemi_ode_stats() adds the slots up
+  // counters: summed over the wave, then added to this workgroup's own slot (thousands of atomic adds to ONE word
+  // serialise at ~90 per microsecond: the tail of the sweep); knpemi_ode_stats() adds the slots up
   unsigned n_rhs = owner ? (unsigned)s.nfe : 0u, n_st = owner ? (unsigned)s.nst : 0u, n_bad = (owner && rc != 0) ? 1u : 0u;
 #pragma unroll
   for (int msk = 32; msk >= 1; msk >>= 1) {
@@ -159,10 +266,12 @@ __device__ __forceinline__ void ode_step_body(const OdeDev& D, const OdeArgs& a,
       }
   }
   if (threadIdx.x == 0) {
+    // adds without a return value: the wave ends without waiting for the slot's old contents (a load, a memory latency at
+    // the very end of the sweep); no other workgroup touches this slot, so nothing serialises
     unsigned long long* st = a.stats + 3 * (size_t)blockIdx.x;
-    st[0] += n_rhs;
-    st[1] += n_st;
-    st[2] += n_bad;
+    atomicAdd(st + 0, (unsigned long long)n_rhs);
+    atomicAdd(st + 1, (unsigned long long)n_st);
+    atomicAdd(st + 2, (unsigned long long)n_bad);
   }
 }
 
@@ -180,12 +289,8 @@ __device__ __forceinline__ void ode_advance_body(const OdeArgs& a, const OdeAdvA
   constexpr int NI = Integrator::NI;
   __shared__ double work[Integrator::WORK * ODE_BLOCK];
   __shared__ LsodaCoef scf;
-  {
-    const double* src = reinterpret_cast<const double*>(cf);
-    double* dst = reinterpret_cast<double*>(&scf);
-    for (int i = threadIdx.x; i < (int)(sizeof(LsodaCoef) / sizeof(double)); i += ODE_BLOCK) dst[i] = src[i];
-    __syncthreads();
-  }
+  using Kind = OdeRowKind<M, LANES>;
+  __shared__ double rowbuf[Kind::LDS_DOUBLES];
   // lane layout of ode_step_body: `dpw` dofs per wave, the other lanes mirror them; lanes past the last dof repeat it
   constexpr int FULL = ODE_BLOCK / LANES;
   const int dpw = (a.dpw > 0 && a.dpw < FULL) ? a.dpw : FULL;
@@ -195,14 +300,22 @@ __device__ __forceinline__ void ode_advance_body(const OdeArgs& a, const OdeAdvA
   const bool live = primary && qw < a.nq;
   const int q = qw < a.nq ? qw : a.nq - 1, comp = threadIdx.x % LANES;
   const bool owner = live && (LANES == 1 || comp == M::CURRENT_LANE);
-  const StridedRow<0> p{a.params + q, (size_t)a.nq};
+  // the row and the wave's copy of it, as in ode_step_body: staged once, every step's stimulus and currents go to both
+  const int col = q - (int)blockIdx.x * dpw;
+  const OdeRow<Kind::STAGED, FULL> p(a.params + q, (size_t)a.nq, rowbuf, col > 0 ? col : 0);
+  double coef[KN_COEF_PER_LANE], row[M::NP];
+  kn_coef_load(cf, coef);
   double y[NI];
 #pragma unroll
   for (int j = 0; j < NI; ++j) y[j] = a.states[(size_t)(comp + j) * a.nq + q];
+  p.load(row);
   const bool stim = a.n_stim > 0 && (!a.mask || a.mask[q]);
   // frozen dofs stay frozen across launches
   bool frozen = v.failed_step[q] >= 0 || (v.window > 0 && v.steps_taken[q] >= 0);
   int still = v.window > 0 ? v.still[q] : 0;
+  kn_coef_store(&scf, coef);
+  p.stage_all(row);
+  __syncthreads();
   unsigned long long n_rhs = 0, n_st = 0, n_bad = 0;
   double t = a.t0;
   int s = 0;
@@ -252,7 +365,8 @@ __device__ __forceinline__ void ode_advance_body(const OdeArgs& a, const OdeAdvA
           if (comp + j == v.rec_idx[i]) row[(size_t)i * a.nq] = y[j];
     }
     t = t + a.dt;
-    // the next step's prepare() reads what this step's finish() stored in the row, from other lanes of the wave
+    // the next step's prepare() reads what this step's finish() stored in the row (its copy in LDS, or the table for a
+    // row too long to stage), from other lanes of the wave
     __syncthreads();
   }
   // the wave is done early: its dofs' later records repeat their frozen states
@@ -279,10 +393,12 @@ __device__ __forceinline__ void ode_advance_body(const OdeArgs& a, const OdeAdvA
     n_bad += __shfl_xor(n_bad, msk);
   }
   if (threadIdx.x == 0) {
+    // adds without a return value: the wave ends without waiting for the slot's old contents (a load, a memory latency at
+    // the very end of the sweep); no other workgroup touches this slot, so nothing serialises
     unsigned long long* st = a.stats + 3 * (size_t)blockIdx.x;
-    st[0] += n_rhs;
-    st[1] += n_st;
-    st[2] += n_bad;
+    atomicAdd(st + 0, (unsigned long long)n_rhs);
+    atomicAdd(st + 1, (unsigned long long)n_st);
+    atomicAdd(st + 2, (unsigned long long)n_bad);
   }
 }
 
