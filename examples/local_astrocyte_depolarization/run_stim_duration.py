@@ -246,12 +246,28 @@ def make_observables(p):
     return obs
 
 
+def make_events(p, threshold):
+    """Upward crossings of `threshold` (mV) on the membranes of neuron and glia, re-armed 20 mV below it, the latest 8
+    crossing times kept per dof: whether the cells follow the stimulus train."""
+    from knpemi import MembraneEvents
+    ev = MembraneEvents(p.subdomain_list)
+    for tag in (1, 2):
+        ev.watch(tag, threshold, reset=threshold - 20.0, keep=8)
+    return ev
+
+
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
-                 extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None):
+                 extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None, events=None,
+                 event_threshold=None):
     """series: path of a .npz of per-step observables (make_observables), or None.
+    events: path of a .npz of the membrane events of neuron and glia (make_events: upward crossings of event_threshold
+    per membrane dof, in mV; default: `event_threshold` of the config, else -20), or None.
     ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator)."""
     p = Problem(config)
     obs = make_observables(p) if series else None
+    if event_threshold is None:
+        event_threshold = float(config.get("event_threshold", -20.0))
+    ev = make_events(p, event_threshold) if events else None
     n_total = int(round(config["Tstop"] / float(DT)))
     n_steps = n_total if n_steps is None else min(n_steps, n_total)
     if outdir is None:
@@ -284,6 +300,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         st.set_source(0, p.f_source_K.x._a)
         if obs is not None:
             st.observe(obs, every=1)
+        if ev is not None:
+            st.detect(ev, every=1)
         for k in range(n_steps):
             st.step()
             t = t + DT
@@ -316,6 +334,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             t = t + DT
             if obs is not None:
                 obs.record_host(t, p.phi, p.c, p.phi_M_prev)
+            if ev is not None:
+                ev.record_host(t, p.phi_M_prev)
             p.set_source(t)
             if (k % config["save_frequency"]) == 0 or k == n_steps - 1:
                 record(problem_emi.solver.getIterationNumber(), problem_knp.solver.getIterationNumber())
@@ -326,6 +346,14 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         xdmf_out.close()
     if obs is not None:
         obs.save(series)
+    if ev is not None:
+        ev.save(events)
+        # the stimulated end: the membrane point nearest to the centre of the ECS source box
+        lo, hi = p.mesh.x.min(axis=0), p.mesh.x.max(axis=0)
+        box = [0.5 * (config[f"{a}_L"] + config[f"{a}_U"]) for a in "xyz"[:p.mesh.gdim]]
+        history["events"] = [ev.summary(tag, origin=np.clip(box, lo, hi)) for tag in ev.watched]
+        if not quiet:
+            print("\n".join(history["events"]))
     history["wall_s"] = time.perf_counter() - t_wall
     history["steps"] = n_steps
     return p, history
@@ -341,6 +369,10 @@ if __name__ == "__main__":
     parser.add_argument("--xdmf", action="store_true", help="also write results_sub_/results_mem_ XDMF time series")
     parser.add_argument("--series", metavar="PATH", default=None,
                         help="write per-step observables (points, mean phi_M, max ECS K) to this .npz")
+    parser.add_argument("--events", metavar="PATH", default=None,
+                        help="write the membrane events of neuron and glia per dof (count, activation times, peaks) to this .npz")
+    parser.add_argument("--event-threshold", type=float, default=None, metavar="V",
+                        help="crossing level of --events in mV (default: event_threshold of the config, else -20)")
     parser.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     parser.add_argument("--ode-substeps", type=int, default=None,
                         help="sub-steps per time step of a fixed-step method (default 25, the reference's n_steps_ODE)")
@@ -348,6 +380,6 @@ if __name__ == "__main__":
     cfg = load_config(args.c)
     _, hist = solve_system(cfg, n_steps=args.steps, device_resident=args.device_resident, direct=args.direct,
                            xdmf=args.xdmf, series=args.series, ode_method=args.ode_method,
-                           ode_substeps=args.ode_substeps)
+                           ode_substeps=args.ode_substeps, events=args.events, event_threshold=args.event_threshold)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

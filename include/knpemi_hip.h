@@ -256,10 +256,11 @@ int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n_rhs, int64
  * CG-1 space on its own (odeSolver.py:8-50; its calibration tool builds an interval mesh for nothing else).  Creates a
  * handle with n_models membrane models of nq[i] dofs each and no PDE problem.  Model i is addressed as sub = 1 + i,
  * model = 0 (n_models <= KNPEMI_MAX_SUB - 1).  knpemi_ode_bind, knpemi_ode_bind_source, knpemi_ode_set_tables,
- * knpemi_ode_get_tables, knpemi_ode_set_stimulus, knpemi_ode_step, knpemi_ode_stats, knpemi_ode_advance and
- * knpemi_destroy work on it as on a PDE handle; no other entry point takes it.  knpemi_ode_step refuses the flags that
- * read PDE fields (KNPEMI_ODE_SET_TRACES, KNPEMI_ODE_SET_V: KNPEMI_EINVAL); its phi_M write-back goes to a buffer of
- * the handle, and there are no ions (ion_param is read for 0 ions; pass any non-NULL pointer). */
+ * knpemi_ode_get_tables, knpemi_ode_set_stimulus, knpemi_ode_step, knpemi_ode_stats, knpemi_ode_advance, the
+ * knpemi_events_* calls and knpemi_destroy work on it as on a PDE handle; no other entry point takes it.
+ * knpemi_ode_step refuses the flags that read PDE fields (KNPEMI_ODE_SET_TRACES, KNPEMI_ODE_SET_V: KNPEMI_EINVAL); its
+ * phi_M write-back goes to a buffer of the handle, and there are no ions (ion_param is read for 0 ions; pass any
+ * non-NULL pointer). */
 int knpemi_ode_create(int device, int n_models, const int32_t* nq, knpemi_handle** out);
 /* Steady-state mode of knpemi_ode_advance: after a step, a dof is still when |y_j - y_j(previous step)| <=
  * ss_atol + ss_rtol |y_j| for every state component j; after `window` consecutive still steps it is steady and frozen. */
@@ -381,6 +382,49 @@ int knpemi_observe_clear(knpemi_handle* h);
 int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
                                    const int32_t* idx, const double* w, const double* denom, int capacity, int rank,
                                    int world, void* xbuf_dev, int (*allreduce)(void* ctx, int n), void* ctx);
+
+/* Membrane events: per membrane dof, when phi_M crossed a threshold upwards, how often, and its running peak
+ * (knpemi.events).  The reference has no such output: its users checkpoint phi_M at every step
+ * (examples/idealized_geometries/run_3D.py:57-60, 376) and post-process the checkpoints on the host (make_figures.py:
+ * 67-89 reads one point of each back); an activation map, a spike count per dof or a conduction velocity needs every one
+ * of those arrays.  Here every membrane dof of a watched cell keeps on the device
+ *   v_prev (the sample of the previous record), armed (u8: a crossing may be counted), count (i32: upward crossings),
+ *   t_first / t_last (time of the first / latest crossing, NaN while count == 0), v_peak / t_peak (largest sample and
+ *   the time of its first occurrence), ring[keep] (the latest `keep` crossing times: crossing n, 1-based, in slot
+ *   (n - 1) % keep, NaN where unused).
+ * knpemi_events_set watches the n_watch cell sub-domains sub[w] (1 <= sub[w] < n_sub, each at most once) with
+ * threshold[w] and reset[w] <= threshold[w] (reset == NULL: the thresholds) and ring length 0 <= keep <=
+ * KNPEMI_EVENTS_MAX_KEEP; anything else is KNPEMI_EINVAL.  Replaces any previous table and clears all state.  `keep`
+ * bounds only how many crossing TIMES a dof remembers; count, t_first and t_last are exact however often it fires.
+ * Works on handles of knpemi_ode_create too (sub = 1 + i): the samples are then the handle's phi_M write-back buffer,
+ * which knpemi_ode_step fills.  knpemi_ode_advance does not write phi_M, so nothing is recorded during it. */
+#define KNPEMI_EVENTS_MAX_KEEP 64
+int knpemi_events_set(knpemi_handle* h, int n_watch, const int32_t* sub, const double* threshold, const double* reset,
+                      int keep);
+/* Enqueue one record at time t on the main stream (after the end-of-step update as knpemi_observe_record, or after
+ * knpemi_ode_step on the main stream): one launch over the dofs of every watched sub-domain, nothing synchronised.  This
+ * replaces the reference's per-step checkpoint of phi_M (run_3D.py:376) as the input of firing statistics.
+ * With sample v = phi_M[q] and t_prev the time of the previous record:
+ *   first record after the set-up or a reset: v_prev <- v, armed <- (v < threshold), v_peak <- v, t_peak <- t;
+ *   later records, in this order (a non-finite v only replaces v_prev):
+ *     1. !armed && v < reset: armed <- 1;
+ *     2. armed && v >= threshold: t_c = t_prev + (t - t_prev) * ((threshold - v_prev) / (v - v_prev)); count += 1,
+ *        t_last <- t_c, t_first <- t_c at the first crossing, ring slot written, armed <- 0;
+ *     3. v > v_peak: v_peak <- v, t_peak <- t;
+ *     4. v_prev <- v.
+ * KNPEMI_EINVAL before knpemi_events_set, and when t is not finite or not greater than the previous record's t. */
+int knpemi_events_record(knpemi_handle* h, double t);
+/* Synchronise and copy out the maps of watched sub-domain `sub`: n_q[sub] entries each, ring as [keep][n_q[sub]] in slot
+ * order; every pointer may be NULL.  This is what the reference's users compute from the downloaded checkpoints of all
+ * steps.  KNPEMI_EINVAL before knpemi_events_set and for a sub-domain that is not watched. */
+int knpemi_events_read(knpemi_handle* h, int sub, int32_t* count, double* t_first, double* t_last, double* v_peak,
+                       double* t_peak, double* ring);
+/* All state back to "before the first record" (a second run from the same start; the reference would delete its
+ * checkpoint files); the table stays.  Enqueue only. */
+int knpemi_events_reset(knpemi_handle* h);
+/* Drop the table and the state buffers (knpemi_events_record then fails with KNPEMI_EINVAL); knpemi_destroy does the
+ * same. */
+int knpemi_events_clear(knpemi_handle* h);
 
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop

@@ -972,6 +972,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   kn_comm_destroy(h);
   kn_solver_free(h);
   kn_free_all(h->obs.allocs);
+  kn_free_all(h->events.allocs);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
   kn_device_close(h);
   delete h;
@@ -1805,6 +1806,115 @@ extern "C" int knpemi_observe_clear(knpemi_handle* h) {
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   observe_free(h);
+  return KNPEMI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// membrane events (kernels_events.hip)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+void events_free(knpemi_handle* h) {
+  kn_free_all(h->events.allocs);
+  h->events = knpemi_handle::KnEvents{};
+}
+}  // namespace
+
+extern "C" int knpemi_events_set(knpemi_handle* h, int n_watch, const int32_t* sub, const double* threshold,
+                                 const double* reset, int keep) {
+  const std::string fn = "knpemi_events_set";
+  if (!h || !sub || !threshold) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (n_watch < 1 || n_watch > KN_MAXSUB - 1) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB - 1 sub-domains");
+  if (keep < 0 || keep > KNPEMI_EVENTS_MAX_KEEP) return kn_fail(KNPEMI_EINVAL, fn + ": keep must be in 0..KNPEMI_EVENTS_MAX_KEEP");
+  KnEvTab T{};
+  bool watched[KN_MAXSUB] = {};
+  for (int w = 0; w < n_watch; ++w) {
+    const int s = sub[w];
+    if (s < 1 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": bad sub-domain index (the ECS has no membrane space)");
+    if (watched[s]) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain " + std::to_string(s) + " is listed twice");
+    const double thr = threshold[w], rst = reset ? reset[w] : thr;
+    if (!(rst <= thr)) return kn_fail(KNPEMI_EINVAL, fn + ": reset must not exceed the threshold");
+    watched[s] = true;
+    T.gstart[w + 1] = T.gstart[w] + h->n_q[s];
+    T.q0[w] = h->qoff[s];
+    T.sub[w] = s;
+    T.threshold[s] = thr;
+    T.reset[s] = rst;
+  }
+  T.n_watch = n_watch;
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  events_free(h);
+  auto& E = h->events;
+  auto& A = E.allocs;
+  const size_t nq = (size_t)h->dev.NQtot;
+  int rc;
+  if ((rc = kn_upload(A, &T, 1, &E.tab)) || (rc = kn_alloc(A, nq, &E.v_prev)) || (rc = kn_alloc(A, nq, &E.armed))
+      || (rc = kn_alloc(A, nq, &E.count)) || (rc = kn_alloc(A, nq, &E.t_first)) || (rc = kn_alloc(A, nq, &E.t_last))
+      || (rc = kn_alloc(A, nq, &E.v_peak)) || (rc = kn_alloc(A, nq, &E.t_peak))
+      || (rc = kn_alloc(A, nq * (size_t)keep, &E.ring))) {
+    events_free(h);
+    return rc;
+  }
+  E.n_watch = n_watch; E.keep = keep; E.n_grid = T.gstart[n_watch];
+  std::copy(watched, watched + KN_MAXSUB, E.watched);
+  if ((rc = kn_launch_events_reset(h))) { events_free(h); return rc; }
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_events_record(knpemi_handle* h, double t) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: no events set (knpemi_events_set)");
+  if (!std::isfinite(t) || (E.have_prev && !(t > E.t_prev)))
+    return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: t must be finite and greater than the previous record's");
+  KN_HIP(hipSetDevice(h->device));
+  if (int rc = kn_launch_events_record(h, E.have_prev ? 0 : 1, t, E.t_prev)) return rc;
+  E.have_prev = true;
+  E.t_prev = t;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_events_read(knpemi_handle* h, int sub, int32_t* count, double* t_first, double* t_last,
+                                  double* v_peak, double* t_peak, double* ring) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: no events set (knpemi_events_set)");
+  if (sub < 1 || sub >= h->n_sub || !E.watched[sub])
+    return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: sub-domain is not watched");
+  KN_HIP(hipSetDevice(h->device));
+  const size_t q0 = (size_t)h->qoff[sub], nq = (size_t)h->n_q[sub], nq_tot = (size_t)h->dev.NQtot;
+  if (nq) {
+    auto copy = [&](auto* host, const auto* dev, size_t n) -> int {
+      if (host) KN_HIP(hipMemcpyAsync(host, dev, n * sizeof(*host), hipMemcpyDeviceToHost, h->stream));
+      return KNPEMI_OK;
+    };
+    int rc;
+    if ((rc = copy(count, E.count + q0, nq)) || (rc = copy(t_first, E.t_first + q0, nq))
+        || (rc = copy(t_last, E.t_last + q0, nq)) || (rc = copy(v_peak, E.v_peak + q0, nq))
+        || (rc = copy(t_peak, E.t_peak + q0, nq)))
+      return rc;
+    for (int k = 0; ring && k < E.keep; ++k)          // row k of the ring: this sub-domain's piece of [keep][NQtot]
+      if ((rc = copy(ring + (size_t)k * nq, E.ring + (size_t)k * nq_tot + q0, nq))) return rc;
+  }
+  KN_HIP(hipStreamSynchronize(h->stream));
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_events_reset(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_reset: no events set (knpemi_events_set)");
+  KN_HIP(hipSetDevice(h->device));
+  E.have_prev = false;
+  E.t_prev = 0.0;
+  return kn_launch_events_reset(h);
+}
+
+extern "C" int knpemi_events_clear(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  events_free(h);
   return KNPEMI_OK;
 }
 

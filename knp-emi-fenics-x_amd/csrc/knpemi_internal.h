@@ -114,6 +114,17 @@ struct KnDev {
   int nq_gamma;
 };
 
+// Table of the watched sub-domains of the membrane events (kernels_events.hip), read by the record kernel: lane i of the
+// grid belongs to segment w with gstart[w] <= i < gstart[w + 1], its dof is q0[w] + i - gstart[w] of sub-domain sub[w]
+struct KnEvTab {
+  int n_watch;
+  int gstart[KN_MAXSUB + 1];
+  int q0[KN_MAXSUB];
+  int sub[KN_MAXSUB];
+  double threshold[KN_MAXSUB];   // indexed by the sub-domain
+  double reset[KN_MAXSUB];
+};
+
 struct KnOdeModel {
   int bound = 0, sub = 0, model_id = -1, n_states = 0, n_params = 0, nq = 0;
   double* d_states = nullptr;   // [n_states][nq]
@@ -551,6 +562,20 @@ struct knpemi_handle : KnDevice {
     void* ctx = nullptr;
     std::vector<void*> allocs;
   } obs;
+  // membrane events (knpemi_events_set, kernels_events.hip); freed by knpemi_events_clear / knpemi_destroy
+  struct KnEvents {
+    int n_watch = 0, keep = 0, n_grid = 0;
+    bool watched[KN_MAXSUB] = {};
+    bool have_prev = false;              // a record has been enqueued since the set-up / the last reset ...
+    double t_prev = 0.0;                 // ... at this time
+    KnEvTab* tab = nullptr;
+    // state over the concatenated membrane dofs ([NQtot]; the ring [keep][NQtot])
+    double* v_prev = nullptr;
+    uint8_t* armed = nullptr;
+    int* count = nullptr;
+    double *t_first = nullptr, *t_last = nullptr, *v_peak = nullptr, *t_peak = nullptr, *ring = nullptr;
+    std::vector<void*> allocs;
+  } events;
 };
 
 inline void kn_inputs_changed(knpemi_handle* h) { ++h->inputs_gen; }
@@ -575,6 +600,8 @@ int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_
 int kn_launch_update_pde(knpemi_handle* h);
 int kn_launch_observe(knpemi_handle* h);
 int kn_launch_observe_combine(knpemi_handle* h);
+int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev);
+int kn_launch_events_reset(knpemi_handle* h);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 // (the membrane ODE sweeps: ode_host.h)
 int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);

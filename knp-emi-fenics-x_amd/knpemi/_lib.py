@@ -29,6 +29,7 @@ ODE_DEFAULT_SUBSTEPS = 25   # the reference drivers' n_steps_ODE (run_2D.py:176)
 OPT_FUSE_UPDATE, OPT_FUSE_MEMBRANE, OPT_PROFILE_STRIDE, OPT_KNP_MIN_IT, OPT_FOLD_MEMBRANE, OPT_KNP_METHOD = 1, 2, 3, 4, 5, 6
 OPT_EMI_NORM = 7
 OBS_SUM, OBS_MIN, OBS_MAX = 0, 1, 2
+EVENTS_MAX_KEEP = 64
 K_ODE, K_EMI_ROWS, K_KNP_ROWS, K_KNP_MEMBRANE, K_UPDATE, K_EMI_MEMBRANE = range(6)
 KERNEL_NAMES = ["ode_step_kernel", "emi_rows_kernel", "knp_rows_kernel", "knp_membrane_kernel", "update_pde_kernel",
                 "emi_membrane_rhs_kernel"]
@@ -163,6 +164,11 @@ SIGNATURES = {
     "knpemi_observe_set_partitioned": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_int64), c_int_p, c_dbl_p,
                                                  c_dbl_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]),
+    "knpemi_events_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_dbl_p, C.c_int]),
+    "knpemi_events_record": (C.c_int, [C.c_void_p, C.c_double]),
+    "knpemi_events_read": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+    "knpemi_events_reset": (C.c_int, [C.c_void_p]),
+    "knpemi_events_clear": (C.c_int, [C.c_void_p]),
     "knpemi_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "knpemi_trace": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_halo_width": (C.c_int, [C.c_void_p, C.c_int]),

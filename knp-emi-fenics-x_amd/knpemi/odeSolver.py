@@ -98,6 +98,7 @@ class MembraneModel:
         self._ion_param = None
         self._mask_cache = {}
         self._standalone = None   # OdeProblem of a model no PDE problem has claimed
+        self._events = None       # MembraneEvents recorded after every step of a stand-alone model (detect)
         print(f'\t{self.prefix} Number of ODE points on the membrane {nodes}')
 
     # --- device binding ------------------------------------------------------
@@ -132,6 +133,9 @@ class MembraneModel:
         self._ion_param = np.array(idx if idx else [0], np.int32)
         if not isinstance(dp, OdeProblem):
             self._standalone = None   # moved to a PDE problem: the host tables travel with every step
+            if self._events is not None:   # ... and the events stay behind with the handle that recorded them
+                self._events._detach()
+                self._events = None
         self._apply_integrator()
 
     def _device(self):
@@ -140,6 +144,23 @@ class MembraneModel:
             self._standalone = OdeProblem([self.nodes])
             self._bind(self._standalone, 1, 0, [])
         return self._dp
+
+    def detect(self, ev):
+        """Record the membrane events `ev` (knpemi.events.MembraneEvents built from {self.tag: self.nodes}, the cell
+        watched) of a model no PDE problem has claimed: every `step` / `step_lsoda` records V at the model's new time.
+        `advance` and `steady_state` run many steps inside one launch without writing the samples: they record
+        nothing.  A model of a PDE problem records through `DeviceStepper.detect`."""
+        dp = self._device()
+        if not isinstance(dp, OdeProblem):
+            raise RuntimeError("this model belongs to a PDE problem: record its events with DeviceStepper.detect")
+        if self._events is not None:
+            raise RuntimeError("this model records membrane events already")
+        if ev.n_q.get(self.tag) != self.nodes:
+            raise ValueError(f"events for {{{self.tag}: {self.nodes}}} expected, got {ev.n_q}")
+        ev._x.setdefault(self.tag, self.dof_locations)
+        ev._attach(dp.lib, dp.h, {self.tag: self._sub})
+        ev.reset_host()
+        self._events = ev
 
     def _set_stimulus(self, stimulus, stimulus_locator):
         dp, lib = self._dp, self._dp.lib
@@ -279,6 +300,8 @@ class MembraneModel:
                                     self.rtol, self.atol, int(self._pending_flags),
                                     L.iptr(self._ion_param), int(self.V_index)))
         ms = dp.timer_stop_ms()
+        if self._events is not None:
+            L.check(lib.knpemi_events_record(dp.h, float(self.time + dt)))
         self._pending_flags = 0
         rc = self._read_stats(ms)
         L.check(lib.knpemi_ode_get_tables(dp.h, self._sub, self._model, L.dptr(states), L.dptr(params)))

@@ -84,6 +84,7 @@ class DeviceStepper:
         self.flags_knp = 0 if a.splitting_scheme else L.NO_SPLITTING
         self._obs = None           # attached Observables (observe)
         self._obs_halo = None      # the halo of a partitioned observe
+        self._ev = None            # attached MembraneEvents (detect)
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -142,6 +143,9 @@ class DeviceStepper:
             L.check(self.lib.knpemi_observe_read(self.dp.h, 0, None, None, None, 1))
             self._obs_pending = []
             self._obs.clear()
+        if self._ev is not None:       # new maps
+            L.check(self.lib.knpemi_events_reset(self.dp.h))
+            self._ev.reset_host()
 
     # -- observables -------------------------------------------------------------------------------
     def observe(self, obs, every=1, capacity=1024, t0=0.0, halo=None):
@@ -181,6 +185,21 @@ class DeviceStepper:
                                f"the host enqueued {n}")
         obs._append_rows(self._obs_pending, buf[:n])
         self._obs_pending = []
+
+    # -- membrane events ---------------------------------------------------------------------------
+    def detect(self, ev, every=1, t0=0.0):
+        """Record the membrane events `ev` (knpemi.events.MembraneEvents) on the device after every `every`-th step,
+        at time t0 + k dt for step k: one launch over the membrane dofs of every watched cell, nothing synchronised;
+        `ev.maps(tag)` reads the maps back.  Works unchanged on a cell-partitioned problem (`step(halo)`): the kernel
+        needs no halo, every rank holds the events of its local dofs, and `ev.maps(tag, halo=halo)` selects the owned
+        ones."""
+        if every < 1:
+            raise ValueError("every must be positive")
+        if self._ev is not None:
+            raise RuntimeError("this stepper records membrane events already")
+        ev._attach(self.lib, self.dp.h, self.dp.sub_index)
+        ev.reset_host()
+        self._ev, self._ev_every, self._ev_t0 = ev, int(every), float(t0)
 
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
@@ -308,6 +327,9 @@ class DeviceStepper:
             self._obs_pending.append(self._obs_t0 + self.k * self.dt)
             if len(self._obs_pending) == self._obs_capacity:
                 self._observe_drain()
+        if self._ev is not None and self.k % self._ev_every == 0:
+            # one more launch on the main stream, behind the end-of-step update for the same reason as the observables'
+            L.check(lib.knpemi_events_record(dp.h, self._ev_t0 + self.k * self.dt))
 
     def ode_failures(self):
         n = 0
