@@ -256,14 +256,27 @@ def make_events(p, threshold):
     return ev
 
 
+def make_fluxes(p):
+    """Fluxes of every ion and the current density in the ECS, the neuron and the glial cell: the net K transport of the
+    spatial-buffering experiment, split into diffusion and drift."""
+    from knpemi import IonFluxes
+    fl = IonFluxes(p.subdomain_list, p.ion_list, p.physical_parameters)
+    for tag in p.subdomain_list:
+        fl.watch(tag)
+    return fl
+
+
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
                  extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None, events=None,
-                 event_threshold=None):
+                 event_threshold=None, fluxes=None):
     """series: path of a .npz of per-step observables (make_observables), or None.
     events: path of a .npz of the membrane events of neuron and glia (make_events: upward crossings of event_threshold
     per membrane dof, in mV; default: `event_threshold` of the config, else -20), or None.
+    fluxes: path of a .npz of the per-step series of the ion fluxes and the current density of every sub-domain
+    (make_fluxes), or None.
     ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator)."""
     p = Problem(config)
+    fl = make_fluxes(p) if fluxes else None
     obs = make_observables(p) if series else None
     if event_threshold is None:
         event_threshold = float(config.get("event_threshold", -20.0))
@@ -302,6 +315,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             st.observe(obs, every=1)
         if ev is not None:
             st.detect(ev, every=1)
+        if fl is not None:
+            st.fluxes(fl, every=1)
         for k in range(n_steps):
             st.step()
             t = t + DT
@@ -336,6 +351,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
                 obs.record_host(t, p.phi, p.c, p.phi_M_prev)
             if ev is not None:
                 ev.record_host(t, p.phi_M_prev)
+            if fl is not None:
+                fl.record_host(t, p.phi, p.c_prev)
             p.set_source(t)
             if (k % config["save_frequency"]) == 0 or k == n_steps - 1:
                 record(problem_emi.solver.getIterationNumber(), problem_knp.solver.getIterationNumber())
@@ -346,6 +363,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         xdmf_out.close()
     if obs is not None:
         obs.save(series)
+    if fl is not None:
+        fl.save(fluxes)
     if ev is not None:
         ev.save(events)
         # the stimulated end: the membrane point nearest to the centre of the ECS source box
@@ -373,6 +392,9 @@ if __name__ == "__main__":
                         help="write the membrane events of neuron and glia per dof (count, activation times, peaks) to this .npz")
     parser.add_argument("--event-threshold", type=float, default=None, metavar="V",
                         help="crossing level of --events in mV (default: event_threshold of the config, else -20)")
+    parser.add_argument("--fluxes", metavar="PATH", default=None,
+                        help="write the per-step ion fluxes and current density of every sub-domain (integrals of the "
+                             "diffusive and the drift part, largest magnitude) to this .npz")
     parser.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     parser.add_argument("--ode-substeps", type=int, default=None,
                         help="sub-steps per time step of a fixed-step method (default 25, the reference's n_steps_ODE)")
@@ -380,6 +402,7 @@ if __name__ == "__main__":
     cfg = load_config(args.c)
     _, hist = solve_system(cfg, n_steps=args.steps, device_resident=args.device_resident, direct=args.direct,
                            xdmf=args.xdmf, series=args.series, ode_method=args.ode_method,
-                           ode_substeps=args.ode_substeps, events=args.events, event_threshold=args.event_threshold)
+                           ode_substeps=args.ode_substeps, events=args.events, event_threshold=args.event_threshold,
+                           fluxes=args.fluxes)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

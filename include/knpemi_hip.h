@@ -426,6 +426,51 @@ int knpemi_events_reset(knpemi_handle* h);
  * same. */
 int knpemi_events_clear(knpemi_handle* h);
 
+/* Ion fluxes and current density per cell (knpemi.fluxes).  The reference writes these quantities in its
+ * manufactured-solution scripts (tests/run_mms.py:270-301: J_k = -D_k grad c_k - z_k D_k psi c_k grad phi, total flux
+ * F sum_k z_k J_k); its drivers have no such output, a user differentiates downloaded checkpoints on the host.
+ * Definitions, for a cell T of sub-domain s and every ion k = 0 .. K-1, the eliminated one included:
+ *   c_k, g(u): value and gradient, at the cell's centroid, of the P1 / Q1 interpolant of the nodal field.  Simplices: the
+ *     mean of the vertex values and the constant gradient.  Hexahedra (tensor vertex order, x[1 << t]): the mean of the
+ *     eight values; the reference derivative along t is 1/4 sum_v +-u_v with the sign from bit t of v, mapped by the
+ *     Jacobian at the centre.
+ *   J_diff = -D_k^s g(c_k),  J_drift = -z_k psi D_k^s c_k g(phi),  J = J_diff + J_drift;
+ *   current density i = F sum_k z_k J_k, split the same way into i_diff and i_drift;
+ *   vol_T = |det| / d! on simplices, |det J(centre)| on hexahedra (midpoint rule); the orientation of a cell does not
+ *     matter.
+ * The fields are those of the device's vertex records: phi, c_prev of the solved ions and the eliminated ion's c, i.e.
+ * the new state once knpemi_update_pde / the fused write-back of knpemi_solve_knp has run.
+ * Series row: for every watched sub-domain in the order given, for every selected ion in ascending order
+ *   sum_T vol_T J_diff (gdim values), sum_T vol_T J_drift (gdim), max_T |J| (Euclidean norm),
+ * then, with the current selected, sum_T vol_T i (gdim) and max_T |i|.  On simplices the sums are the exact integrals of
+ * the discrete flux. */
+/* Watch the n_watch sub-domains sub[w] (0 <= sub[w] < n_sub, each at most once, the ECS included): bits 0 .. K-1 of
+ * ion_mask[w] select the ions, bit 8 the current (run_mms.py:270-301 evaluates all of them).  capacity: rows the device
+ * buffer holds.  Replaces any previous table and clears the buffer.  KNPEMI_EINVAL: a bad or repeated sub-domain, one
+ * without cells, an empty mask, mask bits at or above K (other than bit 8), capacity < 1. */
+int knpemi_flux_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity);
+/* Enqueue one record on the main stream (after the end-of-step update, as knpemi_observe_record): ONE launch over the
+ * cells of every watched sub-domain appends the series row (run_mms.py:270-301 for the integrand) and, with
+ * write_fields != 0, writes the per-cell vectors (buffers allocated at the first such record).  The row index is a
+ * counter in device memory that the launch advances; a full buffer writes nothing and counts the overflow.  Sums are
+ * formed in a fixed order: two identical runs give bit-identical rows, and the row does not depend on write_fields.
+ * KNPEMI_EINVAL before knpemi_flux_set and before knpemi_set_params. */
+int knpemi_flux_record(knpemi_handle* h, int write_fields);
+/* Synchronise and copy out min(n_rows, device row count) rows of the series (run_mms.py:270-301 per row), the device row
+ * count and the overflow count; reset != 0 empties the buffer afterwards. */
+int knpemi_flux_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
+/* Synchronise and copy out one per-cell field of the last record made with fields (run_mms.py:270-301: J_k, or the
+ * total flux for ion == -1): part 0 = diffusive, 1 = drift, as [gdim][n_cell[sub]] (component-major, the device layout);
+ * n = gdim * n_cell[sub].  KNPEMI_EINVAL for a sub-domain, ion or current that is not watched, a bad part or length,
+ * and before any record with fields. */
+int knpemi_flux_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n);
+/* A new series (run_mms.py:270-301 has none: it evaluates once): the buffer is emptied and the per-cell fields count as
+ * not yet recorded; the table stays.  Enqueue only. */
+int knpemi_flux_reset(knpemi_handle* h);
+/* Drop the table and the buffers (knpemi_flux_record then fails with KNPEMI_EINVAL; the quantities of
+ * run_mms.py:270-301 are no longer evaluated); knpemi_destroy does the same. */
+int knpemi_flux_clear(knpemi_handle* h);
+
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop
  *   (run_3D.py:356,362); with this option the write-back kernel of knpemi_solve_knp -- and of

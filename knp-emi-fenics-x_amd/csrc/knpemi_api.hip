@@ -973,6 +973,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   kn_solver_free(h);
   kn_free_all(h->obs.allocs);
   kn_free_all(h->events.allocs);
+  kn_free_all(h->flux.allocs);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
   kn_device_close(h);
   delete h;
@@ -1915,6 +1916,143 @@ extern "C" int knpemi_events_clear(knpemi_handle* h) {
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   events_free(h);
+  return KNPEMI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// ion fluxes and current density per cell (kernels_flux.hip)
+// ---------------------------------------------------------------------------------------------------
+extern "C" int kn_flux_chunk();
+
+namespace {
+void flux_free(knpemi_handle* h) {
+  kn_free_all(h->flux.allocs);
+  h->flux = knpemi_handle::KnFlux{};
+}
+inline int flux_popcount(int m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
+}  // namespace
+
+extern "C" int knpemi_flux_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
+  const std::string fn = "knpemi_flux_set";
+  if (!h || !sub || !ion_mask) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_watch < 1 || n_watch > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB sub-domains");
+  if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
+  const int K = h->K, gd = h->gdim, per_ion = 2 * gd + 1, chunk = kn_flux_chunk();
+  KnFluxTab T{};
+  int watch_of[KN_MAXSUB];
+  std::fill(watch_of, watch_of + KN_MAXSUB, -1);
+  long long fbase = 0;
+  int col = 0;
+  for (int w = 0; w < n_watch; ++w) {
+    const int s = sub[w], m = ion_mask[w];
+    if (s < 0 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": bad sub-domain index");
+    if (watch_of[s] >= 0) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain " + std::to_string(s) + " is listed twice");
+    if (h->n_cell[s] < 1) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain " + std::to_string(s) + " has no cells");
+    if (m == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty ion mask");
+    if (m & ~(KN_FLUX_CURRENT | ((1 << K) - 1)))
+      return kn_fail(KNPEMI_EINVAL, fn + ": ion mask has bits at or above the number of ions (bit 8: the current)");
+    watch_of[s] = w;
+    T.sub[w] = s; T.mask[w] = m; T.c0[w] = h->coff[s]; T.nc[w] = h->n_cell[s];
+    T.bstart[w + 1] = T.bstart[w] + (h->n_cell[s] + chunk - 1) / chunk;
+    T.fbase[w] = fbase;
+    fbase += (long long)(flux_popcount(m & 0xFF) + ((m & KN_FLUX_CURRENT) ? 1 : 0)) * 2 * gd * h->n_cell[s];
+    for (int k = 0; k < K; ++k) {
+      if (!((m >> k) & 1)) continue;
+      for (int j = 0; j < per_ion; ++j, ++col) {
+        T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(k * per_ion + j); T.col_max[col] = j == 2 * gd;
+      }
+    }
+    if (m & KN_FLUX_CURRENT)
+      for (int j = 0; j <= gd; ++j, ++col) {
+        T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(KN_MAXK * per_ion + j); T.col_max[col] = j == gd;
+      }
+  }
+  T.n_watch = n_watch; T.n_cols = col;
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  flux_free(h);
+  auto& X = h->flux;
+  auto& A = X.allocs;
+  const int n_blk = T.bstart[n_watch];
+  int rc;
+  if ((rc = kn_upload(A, &T, 1, &X.tab)) || (rc = kn_alloc(A, (size_t)n_blk * KN_FLUX_SLOTS, &X.part))
+      || (rc = kn_zeros(A, h->stream, 4, &X.ctl)) || (rc = kn_zeros(A, h->stream, (size_t)capacity * col, &X.rows))) {
+    flux_free(h);
+    return rc;
+  }
+  X.host = T; X.n_watch = n_watch; X.capacity = capacity; X.n_blk = n_blk; X.fld_len = (size_t)fbase;
+  std::copy(watch_of, watch_of + KN_MAXSUB, X.watch_of);
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_flux_record(knpemi_handle* h, int write_fields) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->flux;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_record: no fluxes set (knpemi_flux_set)");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_record: knpemi_set_params not called");
+  KN_HIP(hipSetDevice(h->device));
+  if (write_fields && !X.fld)
+    if (int rc = kn_alloc(X.allocs, X.fld_len, &X.fld)) return rc;
+  if (int rc = kn_launch_flux(h, write_fields)) return rc;
+  if (write_fields) X.fld_valid = true;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_flux_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->flux;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_read: no fluxes set (knpemi_flux_set)");
+  if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_read: bad output buffer");
+  KN_HIP(hipSetDevice(h->device));
+  unsigned long long ctl[4];
+  int rc;
+  if ((rc = kn_to_host(h->stream, ctl, X.ctl, 4))) return rc;
+  const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
+  if (n && (rc = kn_to_host(h->stream, out, X.rows, n * X.host.n_cols))) return rc;
+  if (rows) *rows = (int64_t)ctl[0];
+  if (overflow) *overflow = (int64_t)ctl[1];
+  if (reset) {
+    KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
+    KN_HIP(hipStreamSynchronize(h->stream));
+  }
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_flux_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n) {
+  const std::string fn = "knpemi_flux_fields";
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  auto& X = h->flux;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": no fluxes set (knpemi_flux_set)");
+  if (sub < 0 || sub >= h->n_sub || X.watch_of[sub] < 0) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain is not watched");
+  const int w = X.watch_of[sub], m = X.host.mask[w], gd = h->gdim;
+  if (part != 0 && part != 1) return kn_fail(KNPEMI_EINVAL, fn + ": part is 0 (diffusive) or 1 (drift)");
+  if (ion == -1 ? !(m & KN_FLUX_CURRENT) : (ion < 0 || ion >= h->K || !((m >> ion) & 1)))
+    return kn_fail(KNPEMI_EINVAL, fn + (ion == -1 ? ": the current of this sub-domain is not watched"
+                                                   : ": this ion of the sub-domain is not watched"));
+  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (knpemi_flux_record(h, 1))");
+  const size_t nc = (size_t)X.host.nc[w];
+  if (n != nc * gd) return kn_fail(KNPEMI_EINVAL, fn + ": length is not gdim * number of cells");
+  const int before = ion == -1 ? flux_popcount(m & 0xFF) : flux_popcount(m & ((1 << ion) - 1));
+  KN_HIP(hipSetDevice(h->device));
+  return kn_to_host(h->stream, host, X.fld + X.host.fbase[w] + (size_t)(2 * before + part) * gd * nc, n);
+}
+
+extern "C" int knpemi_flux_reset(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->flux;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_reset: no fluxes set (knpemi_flux_set)");
+  KN_HIP(hipSetDevice(h->device));
+  X.fld_valid = false;
+  KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_flux_clear(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  flux_free(h);
   return KNPEMI_OK;
 }
 

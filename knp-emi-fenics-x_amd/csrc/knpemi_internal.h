@@ -125,6 +125,28 @@ struct KnEvTab {
   double reset[KN_MAXSUB];
 };
 
+// Table of the watched sub-domains of the ion fluxes (kernels_flux.hip), read by the record kernel.  Workgroup b belongs to
+// watch w with bstart[w] <= b < bstart[w + 1] and takes the KN_FLUX_CHUNK cells c0[w] + (b - bstart[w]) * KN_FLUX_CHUNK ..
+// of the nc[w] cells of sub-domain sub[w].  A workgroup's partial has KN_FLUX_SLOTS doubles at fixed places: ion k at
+// k (2 gdim + 1) .. ({sum vol J_diff}, {sum vol J_drift}, max |J|), the current at K (2 gdim + 1) .. ({sum vol i}, max |i|).
+// Column q of the series row is slot col_slot[q] of watch col_watch[q], folded over that watch's workgroups by sum or
+// (col_max[q]) maximum.  The per-cell fields of watch w start at fbase[w] doubles: [component][nc[w]], the selected ions
+// in ascending order ({J_diff}, {J_drift} each), then the current ({i_diff}, {i_drift}).
+#define KN_FLUX_CHUNK 256
+#define KN_FLUX_SLOTS 32        // >= KN_MAXK (2 * 3 + 1) + 3 + 1
+#define KN_FLUX_MAXCOLS (KN_MAXSUB * KN_FLUX_SLOTS)
+#define KN_FLUX_CURRENT 0x100   // bit 8 of a watch's ion mask
+struct KnFluxTab {
+  int n_watch, n_cols;
+  int bstart[KN_MAXSUB + 1];
+  int sub[KN_MAXSUB];
+  int c0[KN_MAXSUB];
+  int nc[KN_MAXSUB];
+  int mask[KN_MAXSUB];
+  long long fbase[KN_MAXSUB];
+  uint8_t col_watch[KN_FLUX_MAXCOLS], col_slot[KN_FLUX_MAXCOLS], col_max[KN_FLUX_MAXCOLS];
+};
+
 struct KnOdeModel {
   int bound = 0, sub = 0, model_id = -1, n_states = 0, n_params = 0, nq = 0;
   double* d_states = nullptr;   // [n_states][nq]
@@ -576,6 +598,20 @@ struct knpemi_handle : KnDevice {
     double *t_first = nullptr, *t_last = nullptr, *v_peak = nullptr, *t_peak = nullptr, *ring = nullptr;
     std::vector<void*> allocs;
   } events;
+  // ion fluxes and current density per cell (knpemi_flux_set, kernels_flux.hip); freed by knpemi_flux_clear / knpemi_destroy
+  struct KnFlux {
+    int n_watch = 0, capacity = 0, n_blk = 0;
+    KnFluxTab host{};                    // the table as uploaded
+    int watch_of[KN_MAXSUB] = {};        // sub-domain -> watch, -1: not watched
+    KnFluxTab* tab = nullptr;
+    double* part = nullptr;              // [n_blk][KN_FLUX_SLOTS] workgroup partials
+    unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last workgroup
+    double* rows = nullptr;              // [capacity][n_cols]
+    double* fld = nullptr;               // per-cell fields, allocated at the first record that writes them
+    size_t fld_len = 0;
+    bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
+    std::vector<void*> allocs;
+  } flux;
 };
 
 inline void kn_inputs_changed(knpemi_handle* h) { ++h->inputs_gen; }
@@ -602,6 +638,7 @@ int kn_launch_observe(knpemi_handle* h);
 int kn_launch_observe_combine(knpemi_handle* h);
 int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev);
 int kn_launch_events_reset(knpemi_handle* h);
+int kn_launch_flux(knpemi_handle* h, int write_fields);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 // (the membrane ODE sweeps: ode_host.h)
 int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);

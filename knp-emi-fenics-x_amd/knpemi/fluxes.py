@@ -1,0 +1,285 @@
+"""Ion fluxes and current density per cell: which way the ions move, and how much of it is diffusion and how much drift.
+
+The reference writes these quantities in its manufactured-solution scripts only (`tests/run_mms.py:270-301`:
+`J_k = -D_k grad c_k - z_k D_k psi c_k grad phi`, total flux `F sum_k z_k J_k`).  `Observables` records linear
+functionals of the nodal fields and `MembraneEvents` the firing of the membranes; a flux is a product of fields
+(`c grad phi`) and needs a gradient, so neither can express it, and without this module a user downloads every field at
+every step and differentiates on the host.  Here one launch behind the end-of-step update (csrc/kernels_flux.hip,
+`DeviceStepper.fluxes`) evaluates the per-cell vectors from the vertex records the device already holds and appends their
+integrals and maxima to a time series; the host reads either only when asked.
+
+    fl = IonFluxes(subdomain_list, ion_list, physical_parameters)
+    fl.watch(tag=0)                                   # every ion and the current in the ECS
+    fl.watch(tag=1, ions=["K"], current=False)
+    stepper.fluxes(fl, every=1, fields=True)          # ... stepper.step() ...
+    ser = fl.series()                                 # "t", "0/K/diffusive" (n, gdim), "0/K/drift", "0/K/max", "0/current", ...
+    f = fl.fields(0)                                  # "K/diffusive" (n_cell, gdim), ..., "current"
+
+Definitions, the same for triangles, tetrahedra and hexahedra.  For a cell T of sub-domain s and every ion
+k = 0 .. K-1, the eliminated one included:
+
+  * c_k and g(u) are the value and the gradient, at the cell's centroid, of the P1 / Q1 interpolant of the nodal
+    field.  Simplices: c_k is the mean of the vertex values and g the constant gradient.  Hexahedra (tensor vertex
+    order, x[1 << t]): c_k is the mean of the eight values; the reference derivative along t is 1/4 sum_v +-u_v with
+    the sign taken from bit t of v, mapped by the Jacobian at the centre.
+  * J_diff = -D_k^s g(c_k),  J_drift = -z_k psi D_k^s c_k g(phi),  J = J_diff + J_drift.
+  * Current density i = F sum_k z_k J_k, split the same way into i_diff and i_drift.
+  * vol_T = |det| / d! on simplices and |det J(centre)| on hexahedra (the midpoint rule).  The orientation of a cell
+    does not matter: left-handed cells give the same answer.
+  * The fields are phi, c_prev of the solved ions and the eliminated ion's c as the device holds them: at the end of a
+    step that is the new state.
+
+Series row: per watched (sub-domain, ion) the integrals sum_T vol_T J_diff and sum_T vol_T J_drift (gdim values each)
+and max_T |J| (Euclidean norm); per watched sub-domain with `current=True` sum_T vol_T i and max_T |i|.  On simplices
+the sums are the exact integrals of the discrete flux.
+
+Cell-partitioned runs are not supported: a rank's sums would include its ghost cells.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .fem.function import as_float
+
+CURRENT_BIT = 0x100
+PARTS = ("diffusive", "drift")
+
+
+def _values(u):
+    """The nodal array of a `Function` (or the array itself)."""
+    x = getattr(u, "x", None)
+    if x is None:
+        return np.asarray(u, np.float64)
+    a = getattr(x, "_a", None)
+    return np.asarray(x.array if a is None else a, np.float64)
+
+
+def chunk():
+    """Cells per workgroup of the record kernel (kn_flux_chunk)."""
+    fn = L.load().kn_flux_chunk
+    fn.restype, fn.argtypes = C.c_int, []
+    return int(fn())
+
+
+def cell_geometry(x, cells, cell_type):
+    """(E, vol) of every cell: E[c, t] is edge vector t (simplices: x_(t+1) - x_0; hexahedra: column t of the Jacobian at
+    the centre, 1/4 sum_v +-x_v), vol the cell's measure by the module docstring's rule."""
+    xc = x[cells]
+    if cell_type == "hexahedron":
+        sign = np.array([[1.0 if (v >> t) & 1 else -1.0 for v in range(8)] for t in range(3)])
+        E = 0.25 * np.einsum("tv,cva->cta", sign, xc)
+        return E, np.abs(np.linalg.det(E))
+    d = cells.shape[1] - 1
+    E = xc[:, 1:] - xc[:, :1]
+    return E, np.abs(np.linalg.det(E)) / (2.0 if d == 2 else 6.0)
+
+
+def cell_value_and_gradient(E, cells, cell_type, u):
+    """(value, gradient) at the centroids of the interpolant of the nodal field u: the gradient solves E g = d with d
+    the field's differences along the edge vectors."""
+    uc = u[cells]
+    if cell_type == "hexahedron":
+        sign = np.array([[1.0 if (v >> t) & 1 else -1.0 for v in range(8)] for t in range(3)])
+        d = 0.25 * uc @ sign.T
+    else:
+        d = uc[:, 1:] - uc[:, :1]
+    return uc.mean(axis=1), np.linalg.solve(E, d[:, :, None])[:, :, 0]
+
+
+def norm(J):
+    """Euclidean norm of every row, the squares added in component order."""
+    n2 = J[:, 0] * J[:, 0]
+    for a in range(1, J.shape[1]):
+        n2 = n2 + J[:, a] * J[:, a]
+    return np.sqrt(n2)
+
+
+class IonFluxes:
+    def __init__(self, subdomain_list, ion_list, physical_params):
+        """subdomain_list: the problem's sub-domain dictionary (every entry carries its "mesh_sub"); ion_list: the ions
+        in the problem's order, the eliminated one last; physical_params: "F" and "psi" are read."""
+        self.tags = list(subdomain_list)
+        self.mesh = {t: subdomain_list[t]["mesh_sub"] for t in self.tags}
+        self.ion_list = ion_list
+        self.names = [ion["name"] for ion in ion_list]
+        self.K = len(ion_list)
+        self.z = [float(ion["z"]) for ion in ion_list]
+        self.D = {t: [as_float(ion["D"][t]) for ion in ion_list] for t in self.tags}
+        self.F, self.psi = as_float(physical_params["F"]), as_float(physical_params["psi"])
+        self.gdim = int(self.mesh[self.tags[0]].x.shape[1])
+        self.watched = {}                 # tag -> (ion indices, current)
+        self._geo = {}
+        self._t, self._rows = [], []
+        self._dev = None                  # (lib, handle, {tag: sub-domain index}) once attached
+        self._drain = None                # set by DeviceStepper.fluxes: moves device rows into _t / _rows
+        self._with_fields = False
+
+    # -- definition ------------------------------------------------------------------------------------
+    def watch(self, tag, ions=None, current=True):
+        """Watch sub-domain `tag`: the ions named in `ions` (names or indices; None: all, the eliminated one included)
+        and, with `current`, the current density."""
+        if self._dev is not None:
+            raise RuntimeError("fluxes are attached to a device problem: watch every sub-domain before fluxes()")
+        if tag not in self.mesh:
+            raise ValueError(f"no sub-domain with tag {tag}")
+        if tag in self.watched:
+            raise ValueError(f"sub-domain {tag} is watched already")
+        if ions is None:
+            ions = range(self.K)
+        idx = sorted({self.names.index(i) if isinstance(i, str) else int(i) for i in ions})
+        if any(not 0 <= k < self.K for k in idx):
+            raise ValueError("ion index out of range")
+        if not idx and not current:
+            raise ValueError("nothing to watch: no ion and no current")
+        self.watched[tag] = (idx, bool(current))
+
+    def _check_watched(self, tag):
+        if tag not in self.watched:
+            raise ValueError(f"sub-domain {tag} is not watched")
+
+    def mask(self, tag):
+        """Bits 0 .. K-1: the watched ions of `tag`, bit 8: the current (knpemi_flux_set)."""
+        idx, cur = self.watched[tag]
+        return sum(1 << k for k in idx) | (CURRENT_BIT if cur else 0)
+
+    def columns(self):
+        """[(key, width)] of the series row in the device's order."""
+        out, g = [], self.gdim
+        for tag, (idx, cur) in self.watched.items():
+            for k in idx:
+                n = self.names[k]
+                out += [(f"{tag}/{n}/diffusive", g), (f"{tag}/{n}/drift", g), (f"{tag}/{n}/max", 1)]
+            if cur:
+                out += [(f"{tag}/current", g), (f"{tag}/current_max", 1)]
+        return out
+
+    @property
+    def n_cols(self):
+        return sum(w for _, w in self.columns())
+
+    def n_cells(self, tag):
+        return int(self.mesh[tag].cells.shape[0])
+
+    # -- the device table (knpemi_flux_set) ----------------------------------------------------------------
+    def _attach(self, dp, capacity):
+        if self._dev is not None:
+            raise RuntimeError("these fluxes are attached to a device problem already")
+        if not self.watched:
+            raise ValueError("no sub-domain is watched")
+        tags = list(self.watched)
+        sub = np.array([dp.sub_index[t] for t in tags], np.int32)
+        mask = np.array([self.mask(t) for t in tags], np.int32)
+        L.check(dp.lib.knpemi_flux_set(dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity)))
+        self._dev = (dp.lib, dp.h, dict(dp.sub_index))
+
+    def _append_rows(self, times, rows):
+        self._t.extend(float(t) for t in times)
+        self._rows.extend(np.asarray(rows, np.float64).reshape(len(times), self.n_cols))
+
+    def clear(self):
+        self._t, self._rows = [], []
+
+    # -- host restatement ----------------------------------------------------------------------------------
+    def _geometry(self, tag):
+        if tag not in self._geo:
+            m = self.mesh[tag]
+            x, cells = np.asarray(m.x, np.float64), np.asarray(m.cells)
+            self._geo[tag] = (cells, m.cell_type) + cell_geometry(x, cells, m.cell_type)
+        return self._geo[tag]
+
+    def compute_host(self, phi, c, c_elim=None):
+        """(fields, row) from host data, written from the definitions of the module docstring: the numpy restatement of
+        the device kernel and the reference of the device tests.  phi[tag]: the potential of every watched sub-domain;
+        c[tag]: the nodal concentrations of its ions, K of them, or the K - 1 solved ones with the eliminated ion's
+        taken from c_elim[tag] (default: `ion_list[-1]["c_<tag>"]`).  `Function`s or arrays.
+        fields[tag]: what `fields(tag)` returns; row: the series row as {key: (gdim,) array or float}."""
+        fields, row = {}, {}
+        for tag, (idx, cur) in self.watched.items():
+            cells, kind, E, vol = self._geometry(tag)
+            ck = list(c[tag])
+            if len(ck) == self.K - 1:
+                ck.append(self.ion_list[-1][f"c_{tag}"] if c_elim is None else c_elim[tag])
+            if len(ck) != self.K:
+                raise ValueError(f"sub-domain {tag}: {len(ck)} concentrations for {self.K} ions")
+            _, gphi = cell_value_and_gradient(E, cells, kind, _values(phi[tag]))
+            out = {}
+            i_diff, i_drift = np.zeros_like(gphi), np.zeros_like(gphi)
+            for k in (range(self.K) if cur else idx):
+                cbar, gc = cell_value_and_gradient(E, cells, kind, _values(ck[k]))
+                Dk, zk = self.D[tag][k], self.z[k]
+                Jd = -Dk * gc
+                Jr = -(zk * self.psi * Dk) * cbar[:, None] * gphi
+                i_diff += self.F * zk * Jd
+                i_drift += self.F * zk * Jr
+                if k in idx:
+                    n = self.names[k]
+                    out[f"{n}/diffusive"], out[f"{n}/drift"] = Jd, Jr
+                    row[f"{tag}/{n}/diffusive"] = (vol[:, None] * Jd).sum(axis=0)
+                    row[f"{tag}/{n}/drift"] = (vol[:, None] * Jr).sum(axis=0)
+                    row[f"{tag}/{n}/max"] = float(norm(Jd + Jr).max())
+            if cur:
+                out["current/diffusive"], out["current/drift"], out["current"] = i_diff, i_drift, i_diff + i_drift
+                row[f"{tag}/current"] = (vol[:, None] * out["current"]).sum(axis=0)
+                row[f"{tag}/current_max"] = float(norm(out["current"]).max())
+            fields[tag] = out
+        return fields, row
+
+    def volumes(self, tag):
+        """vol_T of every cell of sub-domain `tag`."""
+        return self._geometry(tag)[3]
+
+    def row_vector(self, row):
+        """A row dictionary of `compute_host` as the flat row of the device buffer."""
+        return np.concatenate([np.atleast_1d(np.asarray(row[key], np.float64)) for key, _ in self.columns()])
+
+    def record_host(self, t, phi, c, c_elim=None):
+        """Append the row of `compute_host` to the series (host drivers)."""
+        self._t.append(float(t))
+        self._rows.append(self.row_vector(self.compute_host(phi, c, c_elim)[1]))
+
+    # -- output --------------------------------------------------------------------------------------------
+    def series(self):
+        """{"t": (n,), "<tag>/<ion>/diffusive": (n, gdim), "<tag>/<ion>/drift": (n, gdim), "<tag>/<ion>/max": (n,),
+        "<tag>/current": (n, gdim), "<tag>/current_max": (n,)}; drains the device buffer of an attached stepper (one
+        synchronisation)."""
+        if self._drain is not None:
+            self._drain()
+        rows = np.array(self._rows, np.float64).reshape(len(self._rows), self.n_cols)
+        out, j = {"t": np.array(self._t, np.float64)}, 0
+        for key, w in self.columns():
+            out[key] = rows[:, j:j + w].copy() if w > 1 else rows[:, j].copy()
+            j += w
+        return out
+
+    def fields(self, tag):
+        """Per-cell arrays (n_cell, gdim) of the last device record made with fields: "<ion>/diffusive" and
+        "<ion>/drift" for every watched ion, "current/diffusive", "current/drift" and their sum "current" where the
+        current is watched (one synchronisation)."""
+        self._check_watched(tag)
+        if self._dev is None:
+            raise RuntimeError("fields(): not attached to a device problem (DeviceStepper.fluxes); compute_host "
+                               "evaluates host data")
+        lib, h, sub_index = self._dev
+        idx, cur = self.watched[tag]
+        nc, g = self.n_cells(tag), self.gdim
+
+        def get(ion, part):
+            buf = np.empty((g, nc), np.float64)
+            L.check(lib.knpemi_flux_fields(h, sub_index[tag], ion, part, L.dptr(buf), buf.size))
+            return np.ascontiguousarray(buf.T)
+        out = {}
+        for k in idx:
+            for p, name in enumerate(PARTS):
+                out[f"{self.names[k]}/{name}"] = get(k, p)
+        if cur:
+            for p, name in enumerate(PARTS):
+                out[f"current/{name}"] = get(-1, p)
+            out["current"] = out["current/diffusive"] + out["current/drift"]
+        return out
+
+    def save(self, path):
+        """.npz of `series()`."""
+        np.savez(path, **self.series())

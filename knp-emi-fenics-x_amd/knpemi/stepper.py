@@ -85,6 +85,7 @@ class DeviceStepper:
         self._obs = None           # attached Observables (observe)
         self._obs_halo = None      # the halo of a partitioned observe
         self._ev = None            # attached MembraneEvents (detect)
+        self._fl = None            # attached IonFluxes (fluxes)
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -146,6 +147,10 @@ class DeviceStepper:
         if self._ev is not None:       # new maps
             L.check(self.lib.knpemi_events_reset(self.dp.h))
             self._ev.reset_host()
+        if self._fl is not None:       # a new series
+            L.check(self.lib.knpemi_flux_reset(self.dp.h))
+            self._fl_pending = []
+            self._fl.clear()
 
     # -- observables -------------------------------------------------------------------------------
     def observe(self, obs, every=1, capacity=1024, t0=0.0, halo=None):
@@ -201,6 +206,40 @@ class DeviceStepper:
         ev.reset_host()
         self._ev, self._ev_every, self._ev_t0 = ev, int(every), float(t0)
 
+    # -- ion fluxes ---------------------------------------------------------------------------------
+    def fluxes(self, fl, every=1, capacity=1024, t0=0.0, fields=False):
+        """Record the ion fluxes `fl` (knpemi.fluxes.IonFluxes) on the device after every `every`-th step, at time
+        t0 + k dt for step k: one launch over the cells of every watched sub-domain on the main stream, behind the
+        end-of-step update, where observables and events record.  Rows collect in a device buffer of `capacity` rows;
+        the host keeps the times of the rows it has enqueued and drains the buffer into `fl` (one synchronisation)
+        whenever it holds `capacity` of them, and when `fl.series()` is called.  fields: every record also writes the
+        per-cell vectors (`fl.fields(tag)` reads those of the latest record).
+        Partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost cells."""
+        if every < 1 or capacity < 1:
+            raise ValueError("every and capacity must be positive")
+        if self._fl is not None:
+            raise RuntimeError("this stepper records ion fluxes already")
+        if fl._drain is not None:
+            raise RuntimeError("these fluxes are attached to a stepper already")
+        fl._attach(self.dp, capacity)
+        self._fl, self._fl_every, self._fl_capacity, self._fl_t0 = fl, int(every), int(capacity), float(t0)
+        self._fl_fields = 1 if fields else 0
+        self._fl_pending = []
+        fl.clear()
+        fl._drain = self._fluxes_drain
+
+    def _fluxes_drain(self):
+        """Move the device rows into the host series; the device must hold exactly the rows enqueued."""
+        fl, n = self._fl, len(self._fl_pending)
+        buf = np.empty((max(n, 1), fl.n_cols), np.float64)
+        rows, over = C.c_int64(), C.c_int64()
+        L.check(self.lib.knpemi_flux_read(self.dp.h, n, L.dptr(buf), C.byref(rows), C.byref(over), 1))
+        if rows.value != n or over.value != 0:
+            raise RuntimeError(f"ion fluxes: the device holds {rows.value} row(s) (+{over.value} dropped), "
+                               f"the host enqueued {n}")
+        fl._append_rows(self._fl_pending, buf[:n])
+        self._fl_pending = []
+
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
         failed on any membrane dof since the last check (the counters live on the device; this synchronises)."""
@@ -241,6 +280,9 @@ class DeviceStepper:
         if halo is not None and self._obs is not None and halo is not self._obs_halo:
             raise NotImplementedError("observables attached without a halo are not recorded on partitioned steps: "
                                       "pass halo= to DeviceStepper.observe")
+        if halo is not None and self._fl is not None:
+            raise NotImplementedError("ion fluxes are not recorded on partitioned steps: a rank's sums would include "
+                                      "its ghost cells")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
@@ -330,6 +372,12 @@ class DeviceStepper:
         if self._ev is not None and self.k % self._ev_every == 0:
             # one more launch on the main stream, behind the end-of-step update for the same reason as the observables'
             L.check(lib.knpemi_events_record(dp.h, self._ev_t0 + self.k * self.dt))
+        if self._fl is not None and self.k % self._fl_every == 0:
+            # and one over the cells of the watched sub-domains, behind the same update
+            L.check(lib.knpemi_flux_record(dp.h, self._fl_fields))
+            self._fl_pending.append(self._fl_t0 + self.k * self.dt)
+            if len(self._fl_pending) == self._fl_capacity:
+                self._fluxes_drain()
 
     def ode_failures(self):
         n = 0
