@@ -89,19 +89,30 @@ def ion_fluxes(s):
     return fl
 
 
+def membrane_exchange(s):
+    """What every ion carries across the membrane of cell 1, the capacitive and the channel current."""
+    from knpemi import MembraneExchange
+    ex = MembraneExchange(s.subdomain_list, s.ion_list, s.physical_parameters, ft=s.ft)
+    ex.watch(1)
+    return ex
+
+
 def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None, series=None,
-                 ode_method="lsoda", ode_substeps=None, events=None, event_threshold=-20e-3, fluxes=None):
+                 ode_method="lsoda", ode_substeps=None, events=None, event_threshold=-20e-3, fluxes=None, exchange=None):
     """series: path of a .npz with the time series at the figures' points (figure_observables), or None.
     ode_method / ode_substeps: the membrane integrator (MembraneModel.set_integrator); the reference's drivers name the
     sub-step count `n_steps_ODE` (run_2D.py:176).
     events: path of a .npz with the membrane events of cell 1 (knpemi.MembraneEvents: upward crossings of
     event_threshold per membrane dof, activation times, peaks), or None.
     fluxes: path of a .npz with the series of the ion fluxes and the current density of every sub-domain
-    (knpemi.IonFluxes: integrals of the diffusive and the drift part, largest magnitude), or None."""
+    (knpemi.IonFluxes: integrals of the diffusive and the drift part, largest magnitude), or None.
+    exchange: path of a .npz with the series of the membrane exchange of cell 1 (knpemi.MembraneExchange: molar flux of
+    every ion out of the cell and into the ECS, capacitive and channel current, per step), or None."""
     s = Setup(kind, res, g_syn=g_syn, mesh_data=read_mesh(mesh_file) if mesh_file else None)
     obs = figure_observables(s) if series else None
     ev = membrane_events(s, event_threshold) if events else None
     fl = ion_fluxes(s) if fluxes else None
+    ex = membrane_exchange(s) if exchange else None
     problem_emi = create_solver_emi(s.a_emi, s.L_emi, s.phi, s.entity_maps, s.subdomain_list, None,
                                     direct=direct, p=s.p_emi, atol=1e-40, rtol=1e-5)
     problem_knp = create_solver_knp(s.a_knp, s.L_knp, s.c, s.entity_maps, s.subdomain_list, None,
@@ -112,6 +123,9 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
         print(f'Solving for t = {t:.4f} s')
         solve_odes(s, k, ode_method, ode_substeps)
         problem_emi.solve()
+        if ex is not None:      # the new potential with the old concentrations: what the KNP right-hand side is formed from
+            ex.record_host(t + s.dt, s.phi, s.c_prev, phi_M_prev=s.phi_M_prev, dt=s.dt,
+                           splitting=s.a_emi.splitting_scheme)
         problem_knp.solve()
         num_it_emi.append(problem_emi.solver.getIterationNumber())
         num_it_knp.append(problem_knp.solver.getIterationNumber())
@@ -126,6 +140,8 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
             fl.record_host(t, s.phi, s.c_prev)
     if fl is not None:
         fl.save(fluxes)
+    if ex is not None:
+        ex.save(exchange)
     if obs is not None:
         obs.save(series)
     if ev is not None:
@@ -150,13 +166,15 @@ if __name__ == "__main__":
     ap.add_argument("--events", metavar="PATH", default=None, help="membrane events of cell 1 per dof (.npz)")
     ap.add_argument("--event-threshold", type=float, default=-20e-3, metavar="V", help="crossing level of --events (V)")
     ap.add_argument("--fluxes", metavar="PATH", default=None, help="series of the ion fluxes of every sub-domain (.npz)")
+    ap.add_argument("--exchange", metavar="PATH", default=None,
+                    help="series of what every ion carries across the membrane of cell 1 (.npz)")
     ap.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     ap.add_argument("--ode-substeps", type=int, default=None, help="sub-steps per time step of a fixed-step method (25)")
     a = ap.parse_args()
     s, it_emi, it_knp = solve_system("2d", a.res, a.steps, direct=not a.iterative, mesh_file=a.mesh_file,
                                      out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), series=a.series,
                                      ode_method=a.ode_method, ode_substeps=a.ode_substeps, events=a.events,
-                                     event_threshold=a.event_threshold, fluxes=a.fluxes)
+                                     event_threshold=a.event_threshold, fluxes=a.fluxes, exchange=a.exchange)
     v = s.phi_M_prev[1].x._a
     print(f"phi_M after {a.steps} steps: min {v.min():.6f} V, max {v.max():.6f} V")
     print(f"average number of iterations emi solver: {sum(it_emi) / len(it_emi)}")

@@ -24,13 +24,15 @@ if __name__ == "__main__":
     ap.add_argument("--events", metavar="PATH", default=None, help="membrane events of cell 1 per dof (.npz)")
     ap.add_argument("--event-threshold", type=float, default=-20e-3, metavar="V", help="crossing level of --events (V)")
     ap.add_argument("--fluxes", metavar="PATH", default=None, help="series of the ion fluxes of every sub-domain (.npz)")
+    ap.add_argument("--exchange", metavar="PATH", default=None,
+                    help="series of what every ion carries across the membrane of cell 1 (.npz)")
     ap.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     ap.add_argument("--ode-substeps", type=int, default=None, help="sub-steps per time step of a fixed-step method (25)")
     a = ap.parse_args()
     s, it_emi, it_knp = solve_system("tet" if a.tets else "hex", a.res, a.steps, direct=not a.iterative,
                                      g_syn=0.0, mesh_file=a.mesh_file, out=os.path.join(HERE, "results", f"3D_{a.res}.npz"),
                                      series=a.series, ode_method=a.ode_method, ode_substeps=a.ode_substeps, events=a.events,
-                                     event_threshold=a.event_threshold, fluxes=a.fluxes)
+                                     event_threshold=a.event_threshold, fluxes=a.fluxes, exchange=a.exchange)
     v = s.phi_M_prev[1].x._a
     print(f"phi_M after {a.steps} steps: min {v.min():.6f} V, max {v.max():.6f} V")
     print(it_emi)

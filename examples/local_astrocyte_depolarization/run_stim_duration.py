@@ -266,17 +266,29 @@ def make_fluxes(p):
     return fl
 
 
+def make_exchange(p):
+    """What every ion carries across the membranes of the neuron and the glial cell: how much K the neuron releases
+    into the ECS and how much of it the glial cell takes up, the capacitive and the channel currents."""
+    from knpemi import MembraneExchange
+    ex = MembraneExchange(p.subdomain_list, p.ion_list, p.physical_parameters, ft=p.ft)
+    for tag in (1, 2):
+        ex.watch(tag)
+    return ex
+
+
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
                  extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None, events=None,
-                 event_threshold=None, fluxes=None):
+                 event_threshold=None, fluxes=None, exchange=None):
     """series: path of a .npz of per-step observables (make_observables), or None.
     events: path of a .npz of the membrane events of neuron and glia (make_events: upward crossings of event_threshold
     per membrane dof, in mV; default: `event_threshold` of the config, else -20), or None.
     fluxes: path of a .npz of the per-step series of the ion fluxes and the current density of every sub-domain
     (make_fluxes), or None.
+    exchange: path of a .npz of the per-step series of the membrane exchange of neuron and glia (make_exchange), or None.
     ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator)."""
     p = Problem(config)
     fl = make_fluxes(p) if fluxes else None
+    ex = make_exchange(p) if exchange else None
     obs = make_observables(p) if series else None
     if event_threshold is None:
         event_threshold = float(config.get("event_threshold", -20.0))
@@ -317,6 +329,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             st.detect(ev, every=1)
         if fl is not None:
             st.fluxes(fl, every=1)
+        if ex is not None:
+            st.exchange(ex, every=1)
         for k in range(n_steps):
             st.step()
             t = t + DT
@@ -343,6 +357,9 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
                 print(f"solving for t = {t:.2f} ms")
             solve_odes(p, k, ode_method, ode_substeps)
             problem_emi.solve()
+            if ex is not None:      # the new potential with the old concentrations: what the KNP right-hand side is formed from
+                ex.record_host(t + DT, p.phi, p.c_prev, phi_M_prev=p.phi_M_prev, dt=DT,
+                               splitting=p.a_emi.splitting_scheme)
             problem_knp.solve()
             update_pde_variables(p.c, p.c_prev, p.phi, p.phi_M_prev, p.physical_parameters, p.ion_list,
                                  p.subdomain_list, p.mesh, p.ct)
@@ -365,6 +382,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         obs.save(series)
     if fl is not None:
         fl.save(fluxes)
+    if ex is not None:
+        ex.save(exchange)
     if ev is not None:
         ev.save(events)
         # the stimulated end: the membrane point nearest to the centre of the ECS source box
@@ -395,6 +414,9 @@ if __name__ == "__main__":
     parser.add_argument("--fluxes", metavar="PATH", default=None,
                         help="write the per-step ion fluxes and current density of every sub-domain (integrals of the "
                              "diffusive and the drift part, largest magnitude) to this .npz")
+    parser.add_argument("--exchange", metavar="PATH", default=None,
+                        help="write the per-step membrane exchange of neuron and glia (molar flux of every ion out of the "
+                             "cell and into the ECS, capacitive and channel current) to this .npz")
     parser.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     parser.add_argument("--ode-substeps", type=int, default=None,
                         help="sub-steps per time step of a fixed-step method (default 25, the reference's n_steps_ODE)")
@@ -403,6 +425,6 @@ if __name__ == "__main__":
     _, hist = solve_system(cfg, n_steps=args.steps, device_resident=args.device_resident, direct=args.direct,
                            xdmf=args.xdmf, series=args.series, ode_method=args.ode_method,
                            ode_substeps=args.ode_substeps, events=args.events, event_threshold=args.event_threshold,
-                           fluxes=args.fluxes)
+                           fluxes=args.fluxes, exchange=args.exchange)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

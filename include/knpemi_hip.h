@@ -471,6 +471,51 @@ int knpemi_flux_reset(knpemi_handle* h);
  * run_mms.py:270-301 are no longer evaluated); knpemi_destroy does the same. */
 int knpemi_flux_clear(knpemi_handle* h);
 
+/* Membrane ion exchange per cell (knpemi.exchange): what crosses the membranes.  The membrane term of the reference's KNP
+ * right-hand side (knpWeakForm.py:168-214) is minus the transmembrane molar flux of each ion, tested against the facet
+ * functions; the reference integrates it into b and keeps nothing else of it.  Definitions, at a point of a membrane facet
+ * of cell sub-domain s, on side e (ECS) or i (cell), for every ion k = 0 .. K-1, the eliminated one included:
+ *   j_k^side = (I_ch,k + alpha_k^side (I_cap - S I_ch,tot)) / (F z_k)   [mol / (m^2 s)], positive out of the cell;
+ *   I_cap = C_M (phi_M - phi_M_prev) / dt with phi_M = phi_i - phi_e of the potential the device holds;
+ *   alpha_k^side = D_k z_k^2 c_k / sum_j D_j z_j^2 c_j with D and c (c_prev, the eliminated ion's c) of that side;
+ *   I_ch,tot = sum_j I_ch,j; S = 1 with the splitting scheme, 0 without (the flags of the last knpemi_assemble_knp;
+ *   splitting before the first).
+ * Integrals use the degree-6 facet rule of the assembly; a facet without a membrane model contributes nothing.  The sum of
+ * block (s, k) of the membrane part of b_knp is -int j_k^i dS, that of block (0, k) +sum_cells int j_k^e dS.
+ * Series row: for every watched cell in the order given, for every selected ion in ascending order
+ *   int j_k^e dS, int j_k^i dS [mol/s], int I_ch,k dS [A],
+ * then, with the current columns selected, int I_cap dS, int I_ch,tot dS [A] and the membrane area. */
+/* Watch the n_watch cell sub-domains sub[w] (1 <= sub[w] < n_sub, each at most once): bits 0 .. K-1 of ion_mask[w]
+ * select the ions, bit 8 the current columns (knpWeakForm.py:168-214 holds all of them).  capacity: rows the device buffer
+ * holds.  Replaces any previous table and clears the buffer; a refused call leaves the table alone.  KNPEMI_EINVAL: the
+ * ECS (sub-domain 0), an unknown or repeated cell, one without membrane facets, an empty mask, mask bits at or above K
+ * (other than bit 8), capacity < 1. */
+int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity);
+/* Enqueue one record on the main stream: ONE launch over the membrane facets of every watched cell, both sides, appends
+ * the series row (knpWeakForm.py:168-214 for the integrand) and, with write_fields != 0, writes the per-facet means
+ * (buffers allocated at the first such record).  It reads what the membrane part of knpemi_assemble_knp reads; in a time
+ * step it belongs directly behind that call and before the KNP solve, the only moment the device holds the new potential,
+ * the old c_prev, the post-ODE phi_M_prev and the new I_ch together.  The row index is a counter in device memory that the
+ * launch advances; a full buffer writes nothing and counts the overflow.  Sums are formed in a fixed order: two identical
+ * runs give bit-identical rows, and the row does not depend on write_fields.  KNPEMI_EINVAL before knpemi_exchange_set
+ * and before knpemi_set_params. */
+int knpemi_exchange_record(knpemi_handle* h, int write_fields);
+/* Synchronise and copy out min(n_rows, device row count) rows of the series (knpWeakForm.py:168-214 per row), the device
+ * row count and the overflow count; reset != 0 empties the buffer afterwards. */
+int knpemi_exchange_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
+/* Synchronise and copy out one per-facet field of the last record made with fields (knpWeakForm.py:168-214: the
+ * integrand's mean over the facet, integral / area): for ion >= 0 part 0 = j^e, 1 = j^i, 2 = I_ch,ion; for ion == -1
+ * part 0 = I_cap, 1 = the facet's area.  n = n_facet[sub]; facets in the order of the problem description.  A facet
+ * without a membrane model holds zeros, its area included.  KNPEMI_EINVAL for a cell, ion or current that is not watched,
+ * a bad part or length, and before any record with fields. */
+int knpemi_exchange_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n);
+/* A new series (knpWeakForm.py:168-214 keeps none): the buffer is emptied and the per-facet fields count as not yet
+ * recorded; the table stays.  Enqueue only. */
+int knpemi_exchange_reset(knpemi_handle* h);
+/* Drop the table and the buffers (knpemi_exchange_record then fails with KNPEMI_EINVAL; the fluxes of
+ * knpWeakForm.py:168-214 are no longer kept); knpemi_destroy does the same. */
+int knpemi_exchange_clear(knpemi_handle* h);
+
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop
  *   (run_3D.py:356,362); with this option the write-back kernel of knpemi_solve_knp -- and of

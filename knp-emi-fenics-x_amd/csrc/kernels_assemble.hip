@@ -13,6 +13,7 @@
 //   KNP  a, L    : src/knpemi/knpWeakForm.py:123-216
 //   update       : src/knpemi/utils.py:238-295
 #include "knpemi_internal.h"
+#include "membrane_facet.h"
 
 // The operators leave the row kernels as streaming stores: they are read next by another kernel and would only push the vertex
 // records, which neighbouring row blocks re-read, out of the L2 (round 4, A/B on one box: 2-4 % per row kernel at 995 k tets and
@@ -27,33 +28,6 @@ __device__ __forceinline__ int logical_block(int bid, int nb) {
   // blocks so neighbouring rows (which share vertices and cells) meet in the same L2.
   const int q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
   return xcd * q + (xcd < r ? xcd : r) + idx;
-}
-
-struct Rec {
-  double x, y, z, c[KN_MAXK], phi;   // c[k]: ion k (record slot KN_CSLOT(k))
-};
-
-__device__ __forceinline__ Rec load_rec(const double* __restrict__ VR, int v) {
-  const double4* p = reinterpret_cast<const double4*>(VR) + 2 * (size_t)v;
-  const double4 a = p[0], b = p[1];
-  Rec r;
-  r.x = a.x; r.y = a.y; r.z = a.z; r.c[0] = b.x; r.c[1] = b.y; r.c[2] = b.z; r.c[3] = a.w; r.phi = b.w;
-  return r;
-}
-
-// Gradient dot products d[j] = grad(lambda_li) . grad(lambda_j) and the cell measure of a P1
-// simplex (closed form; FFCx reaches the same numbers with a 1-point rule).
-template <int NF>
-__device__ __forceinline__ double facet_measure(const Rec (&p)[NF]) {
-  if constexpr (NF == 2) {
-    const double dx = p[1].x - p[0].x, dy = p[1].y - p[0].y;
-    return sqrt(dx * dx + dy * dy);
-  } else {
-    const double ax = p[1].x - p[0].x, ay = p[1].y - p[0].y, az = p[1].z - p[0].z;
-    const double bx = p[2].x - p[0].x, by = p[2].y - p[0].y, bz = p[2].z - p[0].z;
-    const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-    return 0.5 * sqrt(nx * nx + ny * ny + nz * nz);
-  }
 }
 
 // surface Jacobian of a bilinear quadrilateral facet (lexicographic vertices) at (xi, eta)
@@ -92,14 +66,6 @@ __device__ __forceinline__ void facet_mass_row(const Rec (&p)[NF], int a, double
 #pragma unroll
     for (int b = 0; b < NF; ++b) M[b] = (b == a) ? 2.0 * m : m;
   }
-}
-
-// 1 / a from the hardware estimate and two Newton steps (relative error of a few 1e-16): five instructions instead of the
-// eleven of the IEEE division sequence, once per (row, cell) pair and per quadrature point of the Q1 kernels.
-__device__ __forceinline__ double kn_rcp(double a) {
-  double r = __builtin_amdgcn_rcp(a);
-  r = fma(fma(-a, r, 1.0), r, r);
-  return fma(fma(-a, r, 1.0), r, r);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1367,47 +1333,7 @@ __global__ __launch_bounds__(KN_BLOCK, GEO == 2 ? 4 : (GEO == 1 ? 3 : 2)) void k
 // NF x 2 (ions) partial integrals to `gam_contrib`; the row kernel adds them into b_knp in a fixed
 // order, so nothing is accumulated atomically.
 // ---------------------------------------------------------------------------------------------
-// everything one side of a membrane facet contributes to the integrand: loaded once per (facet, side)
-template <int NF>
-struct FacetData {
-  Rec pe[NF], pi[NF];
-  double pm[NF], Ik[NF][KN_MAXK], It[NF];
-  double meas, sgn;
-  const KnSubConst* so;    // own-side constants
-  bool cell_side;
-};
-
-// phi_x != NULL: the potential is taken from that vector (one value per vertex, e.g. the solver's solution before it is
-// written into the records -- a constant shift of it cancels in the jump) instead of the records' component 7
-template <int NF>
-__device__ __forceinline__ void load_facet(const KnDev& D, const KnConsts& C, int fg, bool cell_side, int ms,
-                                           FacetData<NF>& f, const double* __restrict__ phi_x = nullptr) {
-  const int K = C.K;
-  int si = 0;  // sub-domain of the cell side of this facet
-#pragma unroll
-  for (int bb = 0; bb < NF; ++bb) {
-    const int vi = D.fi[(size_t)fg * NF + bb], ve = D.fe[(size_t)fg * NF + bb];
-    f.pe[bb] = load_rec(D.VR, ve);
-    f.pi[bb] = load_rec(D.VR, vi);
-    if (phi_x) { f.pe[bb].phi = phi_x[ve]; f.pi[bb].phi = phi_x[vi]; }
-    const int q = D.fq[(size_t)fg * NF + bb];
-    f.pm[bb] = D.phiM[q];
-    const double* ich = D.Ich + (size_t)ms * KN_MAXK * D.NQtot + q;
-    double it = 0.0;
-#pragma unroll
-    for (int k = 0; k < KN_MAXK; ++k) {
-      f.Ik[bb][k] = k < K ? ich[(size_t)k * D.NQtot] : 0.0;
-      it += f.Ik[bb][k];
-    }
-    f.It[bb] = it;
-    if (bb == 0) for (int tt = 1; tt < C.n_sub; ++tt) si += vi >= C.voff[tt];
-  }
-  f.so = &C.sc[cell_side ? si : 0];
-  f.meas = 0.0;
-  if constexpr (NF != 4) f.meas = facet_measure<NF>(f.pe);
-  f.sgn = cell_side ? 1.0 : -1.0;
-  f.cell_side = cell_side;
-}
+// (FacetData, load_facet and the fields at a quadrature point, facet_point_fields: membrane_facet.h)
 
 // weight x integrand of the K - 1 solved ions at quadrature point q (knpWeakForm.py:178-214):
 //   fk[k] = w_q * sgn * (C_k g_k - C_k [phi]),  C_k = alpha_k C_M / (F z_k dt),  alpha_k = D_k z_k^2 c_k / sum_j D_j z_j^2 c_j
@@ -1415,38 +1341,12 @@ template <int NF>
 __device__ __forceinline__ void facet_point(const FacetData<NF>& f, const KnConsts& C, int q, const double* qw,
                                             const double* qN, const double* qdN, int splitting, double (&fk)[KN_MAXK - 1]) {
   const int KS = C.K - 1;
-  double cq[KN_MAXK], iq[KN_MAXK], ph_e = 0, ph_i = 0, pmq = 0, it = 0;
-#pragma unroll
-  for (int k = 0; k < KN_MAXK; ++k) { cq[k] = 0.0; iq[k] = 0.0; }
-#pragma unroll
-  for (int bb = 0; bb < NF; ++bb) {
-    const double N = qN[q * NF + bb];
-    const Rec& o = f.cell_side ? f.pi[bb] : f.pe[bb];
-#pragma unroll
-    for (int k = 0; k < KN_MAXK; ++k) { cq[k] += N * o.c[k]; iq[k] += N * f.Ik[bb][k]; }
-    ph_e += N * f.pe[bb].phi; ph_i += N * f.pi[bb].phi;
-    pmq += N * f.pm[bb]; it += N * f.It[bb];
-  }
-  double wq;
-  if constexpr (NF == 4) {
-    // surface Jacobian of the bilinear facet at this point
-    double ux = 0, uy = 0, uz = 0, vx = 0, vy = 0, vz = 0;
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      const double da = qdN[(q * 4 + bb) * 2], db = qdN[(q * 4 + bb) * 2 + 1];
-      ux += da * f.pe[bb].x; uy += da * f.pe[bb].y; uz += da * f.pe[bb].z;
-      vx += db * f.pe[bb].x; vy += db * f.pe[bb].y; vz += db * f.pe[bb].z;
-    }
-    const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
-    wq = qw[q] * sqrt(nx * nx + ny * ny + nz * nz);
-  } else {
-    wq = qw[q] * f.meas * (NF == 2 ? 1.0 : 2.0);  // reference measure 1 (interval), 1/2 (triangle)
-  }
-  double asum = 0.0;      // sum over ALL K ions (knpWeakForm.py:97); az2D = 0 beyond K
-#pragma unroll
-  for (int k = 0; k < KN_MAXK; ++k) asum += f.so->az2D[k] * cq[k];
-  const double jump = ph_i - ph_e;
-  const double rasum = kn_rcp(asum);
+  FacetPoint P;
+  facet_point_fields<NF>(f, q, qw, qN, qdN, P);
+  const double (&cq)[KN_MAXK] = P.cq, (&iq)[KN_MAXK] = P.iq;
+  const double pmq = P.pmq, it = P.it, wq = P.wq;
+  const double jump = P.ph_i - P.ph_e;
+  const double rasum = kn_rcp(P.asum);
 #pragma unroll
   for (int k = 0; k < KN_MAXK - 1; ++k) {
     fk[k] = 0.0;
@@ -1510,13 +1410,7 @@ __device__ __forceinline__ void facet_point_split(const FacetData<NF>& f, const 
 
 // Stand-alone form (diagnostics, KNPEMI_OPT_FUSE_MEMBRANE = 0): one thread per (facet, side) tests the integrand
 // against all NF facet functions and writes NF x (K - 1) partial integrals to gam_e.
-// KN_MEM_LQ adjacent lanes share one (facet, side): each takes every KN_MEM_LQ-th quadrature point and the partial
-// integrals meet in a shuffle reduction.  The membrane is a 2-D set: with one thread per (facet, side) a config-2 launch
-// has 46 workgroups whose threads walk 12 points of ~150 instructions one after the other; spreading the points
-// turns that latency chain into four times as many, four times shorter waves.
-#ifndef KN_MEM_LQ
-#define KN_MEM_LQ 4
-#endif
+// (KN_MEM_LQ adjacent lanes share one (facet, side): membrane_facet.h)
 // One workgroup's share of the facet integrals; `bid` = its index among the `nb` workgroups that do this work (after the
 // XCD-aware remap: consecutive facets share vertex records, so each XCD takes one contiguous run of facets and fetches a
 // record once instead of once per XCD that meets it: 2.5 MB instead of ... of HBM-side traffic at config 2).

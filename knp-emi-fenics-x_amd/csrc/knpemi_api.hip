@@ -974,6 +974,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   kn_free_all(h->obs.allocs);
   kn_free_all(h->events.allocs);
   kn_free_all(h->flux.allocs);
+  kn_free_all(h->exchange.allocs);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
   kn_device_close(h);
   delete h;
@@ -1186,6 +1187,7 @@ extern "C" int knpemi_assemble_knp(knpemi_handle* h, int flags) {
   // whether or not the caller has called knpemi_join (a wait on a completed or never-recorded event costs nothing)
   KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
   KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+  h->knp_flags = flags;
   if (flags & KNPEMI_MEMBRANE_EARLY) {   // the integrals were prepared by knpemi_assemble_knp_membrane_early
     if (h->pre_pending) {
       KN_HIP(hipStreamWaitEvent(h->stream, h->ev_pre, 0));
@@ -2053,6 +2055,144 @@ extern "C" int knpemi_flux_clear(knpemi_handle* h) {
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
   flux_free(h);
+  return KNPEMI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// membrane ion exchange per cell (kernels_exchange.hip)
+// ---------------------------------------------------------------------------------------------------
+extern "C" int kn_exchange_chunk();
+
+namespace {
+void exchange_free(knpemi_handle* h) {
+  kn_free_all(h->exchange.allocs);
+  h->exchange = knpemi_handle::KnExchange{};
+}
+}  // namespace
+
+extern "C" int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
+  const std::string fn = "knpemi_exchange_set";
+  if (!h || !sub || !ion_mask) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_watch < 1 || n_watch > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB cells");
+  if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
+  const int K = h->K, chunk = kn_exchange_chunk();
+  KnExTab T{};
+  int watch_of[KN_MAXSUB];
+  std::fill(watch_of, watch_of + KN_MAXSUB, -1);
+  long long fbase = 0;
+  int col = 0;
+  for (int w = 0; w < n_watch; ++w) {
+    const int s = sub[w], m = ion_mask[w];
+    if (s == 0) return kn_fail(KNPEMI_EINVAL, fn + ": the ECS (sub-domain 0) has no membrane of its own: watch the cells");
+    if (s < 0 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": unknown cell (bad sub-domain index)");
+    if (watch_of[s] >= 0) return kn_fail(KNPEMI_EINVAL, fn + ": cell " + std::to_string(s) + " is listed twice");
+    if (h->n_facet[s] < 1) return kn_fail(KNPEMI_EINVAL, fn + ": cell " + std::to_string(s) + " has no membrane facets");
+    if (m == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty ion mask");
+    if (m & ~(KN_EX_CURRENT | ((1 << K) - 1)))
+      return kn_fail(KNPEMI_EINVAL, fn + ": ion mask has bits at or above the number of ions (bit 8: the current columns)");
+    watch_of[s] = w;
+    T.sub[w] = s; T.mask[w] = m; T.f0[w] = h->foff[s]; T.nf[w] = h->n_facet[s];
+    T.bstart[w + 1] = T.bstart[w] + (h->n_facet[s] + chunk - 1) / chunk;
+    T.fbase[w] = fbase;
+    fbase += (long long)(3 * flux_popcount(m & 0xFF) + ((m & KN_EX_CURRENT) ? 2 : 0)) * h->n_facet[s];
+    for (int k = 0; k < K; ++k) {
+      if (!((m >> k) & 1)) continue;
+      for (int j = 0; j < 3; ++j, ++col) { T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(3 * k + j); }
+    }
+    if (m & KN_EX_CURRENT)
+      for (int j = 0; j < 3; ++j, ++col) { T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(3 * KN_MAXK + j); }
+  }
+  T.n_watch = n_watch; T.n_cols = col;
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  exchange_free(h);
+  auto& X = h->exchange;
+  auto& A = X.allocs;
+  const int n_blk = T.bstart[n_watch];
+  int rc;
+  if ((rc = kn_upload(A, &T, 1, &X.tab)) || (rc = kn_alloc(A, (size_t)n_blk * KN_EX_SLOTS, &X.part))
+      || (rc = kn_zeros(A, h->stream, 4, &X.ctl)) || (rc = kn_zeros(A, h->stream, (size_t)capacity * col, &X.rows))) {
+    exchange_free(h);
+    return rc;
+  }
+  X.host = T; X.n_watch = n_watch; X.capacity = capacity; X.n_blk = n_blk; X.fld_len = (size_t)fbase;
+  std::copy(watch_of, watch_of + KN_MAXSUB, X.watch_of);
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_exchange_record(knpemi_handle* h, int write_fields) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->exchange;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_record: no exchange set (knpemi_exchange_set)");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_record: knpemi_set_params not called");
+  KN_HIP(hipSetDevice(h->device));
+  // phi_M and I_ch come from the ODE sweeps, which may run on the auxiliary streams (as in knpemi_assemble_knp)
+  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+  if (write_fields && !X.fld)
+    if (int rc = kn_alloc(X.allocs, X.fld_len, &X.fld)) return rc;
+  if (int rc = kn_launch_exchange(h, write_fields)) return rc;
+  if (write_fields) X.fld_valid = true;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_exchange_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->exchange;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_read: no exchange set (knpemi_exchange_set)");
+  if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_read: bad output buffer");
+  KN_HIP(hipSetDevice(h->device));
+  unsigned long long ctl[4];
+  int rc;
+  if ((rc = kn_to_host(h->stream, ctl, X.ctl, 4))) return rc;
+  const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
+  if (n && (rc = kn_to_host(h->stream, out, X.rows, n * X.host.n_cols))) return rc;
+  if (rows) *rows = (int64_t)ctl[0];
+  if (overflow) *overflow = (int64_t)ctl[1];
+  if (reset) {
+    KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
+    KN_HIP(hipStreamSynchronize(h->stream));
+  }
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_exchange_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n) {
+  const std::string fn = "knpemi_exchange_fields";
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  auto& X = h->exchange;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": no exchange set (knpemi_exchange_set)");
+  if (sub < 0 || sub >= h->n_sub || X.watch_of[sub] < 0) return kn_fail(KNPEMI_EINVAL, fn + ": cell is not watched");
+  const int w = X.watch_of[sub], m = X.host.mask[w];
+  if (ion == -1 ? !(m & KN_EX_CURRENT) : (ion < 0 || ion >= h->K || !((m >> ion) & 1)))
+    return kn_fail(KNPEMI_EINVAL, fn + (ion == -1 ? ": the current columns of this cell are not watched"
+                                                   : ": this ion of the cell is not watched"));
+  if (part < 0 || part > (ion == -1 ? 1 : 2))
+    return kn_fail(KNPEMI_EINVAL, fn + ": part is 0 (ECS side), 1 (cell side) or 2 (channel current) of an ion, "
+                                       "0 (capacitive current) or 1 (area) with ion == -1");
+  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (knpemi_exchange_record(h, 1))");
+  const size_t nf = (size_t)X.host.nf[w];
+  if (n != nf) return kn_fail(KNPEMI_EINVAL, fn + ": length is not the number of membrane facets of the cell");
+  const int comp = ion == -1 ? 3 * flux_popcount(m & 0xFF) + part : 3 * flux_popcount(m & ((1 << ion) - 1)) + part;
+  KN_HIP(hipSetDevice(h->device));
+  return kn_to_host(h->stream, host, X.fld + X.host.fbase[w] + (size_t)comp * nf, n);
+}
+
+extern "C" int knpemi_exchange_reset(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->exchange;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_reset: no exchange set (knpemi_exchange_set)");
+  KN_HIP(hipSetDevice(h->device));
+  X.fld_valid = false;
+  KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_exchange_clear(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  exchange_free(h);
   return KNPEMI_OK;
 }
 

@@ -147,6 +147,27 @@ struct KnFluxTab {
   uint8_t col_watch[KN_FLUX_MAXCOLS], col_slot[KN_FLUX_MAXCOLS], col_max[KN_FLUX_MAXCOLS];
 };
 
+// Table of the watched cells of the membrane exchange (kernels_exchange.hip), read by the record kernel.  Workgroup b belongs
+// to watch w with bstart[w] <= b < bstart[w + 1] and takes kn_exchange_chunk() facets, both sides of each, from
+// f0[w] + (b - bstart[w]) * chunk on, of the nf[w] membrane facets of cell sub-domain sub[w].  A workgroup's partial has
+// KN_EX_SLOTS doubles at fixed places: ion k at 3 k .. (int j_k^e, int j_k^i, int I_ch,k), then at 3 KN_MAXK .. int I_cap,
+// int I_ch,tot and the area.  Column q of the series row is slot col_slot[q] of watch col_watch[q], summed over that
+// watch's workgroups in their order.  The per-facet means of watch w start at fbase[w] doubles: [component][nf[w]], the
+// selected ions in ascending order (j^e, j^i, I_ch,k each), then, with the current columns, I_cap and the area.
+#define KN_EX_SLOTS 16          // >= 3 KN_MAXK + 3
+#define KN_EX_MAXCOLS (KN_MAXSUB * KN_EX_SLOTS)
+#define KN_EX_CURRENT 0x100     // bit 8 of a watch's ion mask
+struct KnExTab {
+  int n_watch, n_cols;
+  int bstart[KN_MAXSUB + 1];
+  int sub[KN_MAXSUB];
+  int f0[KN_MAXSUB];
+  int nf[KN_MAXSUB];
+  int mask[KN_MAXSUB];
+  long long fbase[KN_MAXSUB];
+  uint8_t col_watch[KN_EX_MAXCOLS], col_slot[KN_EX_MAXCOLS];
+};
+
 struct KnOdeModel {
   int bound = 0, sub = 0, model_id = -1, n_states = 0, n_params = 0, nq = 0;
   double* d_states = nullptr;   // [n_states][nq]
@@ -612,6 +633,21 @@ struct knpemi_handle : KnDevice {
     bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
     std::vector<void*> allocs;
   } flux;
+  // membrane ion exchange per cell (knpemi_exchange_set, kernels_exchange.hip); freed by knpemi_exchange_clear / knpemi_destroy
+  struct KnExchange {
+    int n_watch = 0, capacity = 0, n_blk = 0;
+    KnExTab host{};                      // the table as uploaded
+    int watch_of[KN_MAXSUB] = {};        // sub-domain -> watch, -1: not watched
+    KnExTab* tab = nullptr;
+    double* part = nullptr;              // [n_blk][KN_EX_SLOTS] workgroup partials
+    unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last workgroup
+    double* rows = nullptr;              // [capacity][n_cols]
+    double* fld = nullptr;               // per-facet means, allocated at the first record that writes them
+    size_t fld_len = 0;
+    bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
+    std::vector<void*> allocs;
+  } exchange;
+  int knp_flags = 0;                   // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
 };
 
 inline void kn_inputs_changed(knpemi_handle* h) { ++h->inputs_gen; }
@@ -639,6 +675,7 @@ int kn_launch_observe_combine(knpemi_handle* h);
 int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev);
 int kn_launch_events_reset(knpemi_handle* h);
 int kn_launch_flux(knpemi_handle* h, int write_fields);
+int kn_launch_exchange(knpemi_handle* h, int write_fields);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 // (the membrane ODE sweeps: ode_host.h)
 int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);

@@ -86,6 +86,7 @@ class DeviceStepper:
         self._obs_halo = None      # the halo of a partitioned observe
         self._ev = None            # attached MembraneEvents (detect)
         self._fl = None            # attached IonFluxes (fluxes)
+        self._ex = None            # attached MembraneExchange (exchange)
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -151,6 +152,10 @@ class DeviceStepper:
             L.check(self.lib.knpemi_flux_reset(self.dp.h))
             self._fl_pending = []
             self._fl.clear()
+        if self._ex is not None:       # a new series
+            L.check(self.lib.knpemi_exchange_reset(self.dp.h))
+            self._ex_pending = []
+            self._ex.clear()
 
     # -- observables -------------------------------------------------------------------------------
     def observe(self, obs, every=1, capacity=1024, t0=0.0, halo=None):
@@ -240,6 +245,44 @@ class DeviceStepper:
         fl._append_rows(self._fl_pending, buf[:n])
         self._fl_pending = []
 
+    # -- membrane ion exchange --------------------------------------------------------------------------
+    def exchange(self, ex, every=1, capacity=1024, t0=0.0, fields=False):
+        """Record the membrane exchange `ex` (knpemi.exchange.MembraneExchange) on the device in every `every`-th
+        step: one launch over the membrane facets of the watched cells on the main stream, directly behind the last
+        KNP assembly of the step and before the KNP solve -- the only moment the device holds the new potential, the old
+        c_prev, the post-ODE phi_M_prev and the new I_ch together (the fused KNP write-back and the end-of-step update
+        overwrite three of them).  The row of step k (counted from 0) carries the time t0 + (k + 1) dt, the end of the
+        step whose mean rate it is.  Rows collect in a device buffer of `capacity` rows; the host keeps the times of the
+        rows it has enqueued and drains the buffer into `ex` (one synchronisation) whenever it holds `capacity` of them,
+        and when `ex.series()` is called.  fields: every record also writes the per-facet means (`ex.fields(tag)`
+        reads those of the latest record).
+        Partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost facets."""
+        if every < 1 or capacity < 1:
+            raise ValueError("every and capacity must be positive")
+        if self._ex is not None:
+            raise RuntimeError("this stepper records a membrane exchange already")
+        if ex._drain is not None:
+            raise RuntimeError("this exchange is attached to a stepper already")
+        ex._attach(self.dp, capacity)
+        self._ex, self._ex_every, self._ex_capacity, self._ex_t0 = ex, int(every), int(capacity), float(t0)
+        self._ex_fields = 1 if fields else 0
+        self._ex_pending = []
+        ex.clear()
+        ex._dt, ex._every = self.dt, int(every)
+        ex._drain = self._exchange_drain
+
+    def _exchange_drain(self):
+        """Move the device rows into the host series; the device must hold exactly the rows enqueued."""
+        ex, n = self._ex, len(self._ex_pending)
+        buf = np.empty((max(n, 1), ex.n_cols), np.float64)
+        rows, over = C.c_int64(), C.c_int64()
+        L.check(self.lib.knpemi_exchange_read(self.dp.h, n, L.dptr(buf), C.byref(rows), C.byref(over), 1))
+        if rows.value != n or over.value != 0:
+            raise RuntimeError(f"membrane exchange: the device holds {rows.value} row(s) (+{over.value} dropped), "
+                               f"the host enqueued {n}")
+        ex._append_rows(self._ex_pending, buf[:n])
+        self._ex_pending = []
+
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
         failed on any membrane dof since the last check (the counters live on the device; this synchronises)."""
@@ -283,6 +326,9 @@ class DeviceStepper:
         if halo is not None and self._fl is not None:
             raise NotImplementedError("ion fluxes are not recorded on partitioned steps: a rank's sums would include "
                                       "its ghost cells")
+        if halo is not None and self._ex is not None:
+            raise NotImplementedError("the membrane exchange is not recorded on partitioned steps: a rank's sums would "
+                                      "include its ghost facets")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
@@ -351,6 +397,12 @@ class DeviceStepper:
         L.check(lib.knpemi_assemble_knp(dp.h, knp_flags))
         if self.assemble_knp_twice:   # the reference assembles p = a a second time (knpWeakForm.py:319)
             L.check(lib.knpemi_assemble_knp(dp.h, knp_flags))
+        if self._ex is not None and (self.k + 1) % self._ex_every == 0:
+            # behind the assembly, before the solve: the fields the membrane part of b_knp has just been formed from
+            L.check(lib.knpemi_exchange_record(dp.h, self._ex_fields))
+            self._ex_pending.append(self._ex_t0 + (self.k + 1) * self.dt)
+            if len(self._ex_pending) == self._ex_capacity:
+                self._exchange_drain()
         if self.solve_knp is not None:
             self.solve_knp(dp)
         if not (self.fuse_update and self.solve_knp is not None):

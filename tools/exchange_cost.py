@@ -1,0 +1,103 @@
+"""Cost of recording the membrane exchange in the device-resident loop (knpemi.exchange, DeviceStepper.exchange).
+
+Config 2 (tet r=1) or the 995 328-tet mesh (`--workload config3`) with the device solves: ms per whole step with nothing
+attached, with the series row of every ion and the currents of the cell recorded every step, and with the per-facet means
+written as well.  All legs start from the same state (DeviceStepper.reset), so they run the same solver iterations; the
+legs alternate and the median of the windows is printed as one JSON line.  The launch sits between the KNP assembly and
+the KNP solve, on the critical path of the step; the membrane is a 2-D set, so the launch is a few dozen workgroups that
+wait for their gathers, like knp_membrane_kernel, and its cost is a launch's latency, not bandwidth.  For the kernel's own
+time run this under `rocprofv3 --kernel-trace --stats` and pass the statistics file of that run to a second, unprofiled
+call with `--stats`: it adds the average duration of exchange_kernel.
+"""
+import argparse
+import contextlib
+import csv
+import io
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("knp-emi-fenics-x_amd", "examples/idealized_geometries", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+
+import numpy as np  # noqa: E402
+
+
+def kernel_stats(path):
+    """{"series": (calls, average us), "fields": ...} of exchange_kernel<NF, fields> from a rocprofv3 statistics CSV."""
+    out = {}
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            name = row.get("Name", "")
+            if "exchange_kernel" not in name:
+                continue
+            leg = "fields" if ("true" in name or "Lb1" in name or ", 1>" in name) else "series"
+            out[leg] = (int(row["Calls"]), float(row["AverageNs"]) / 1e3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=["config2", "config3"], default="config2")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--stats", default=None, help="rocprofv3 kernel statistics (.csv) of a profiled run of this tool")
+    args = ap.parse_args()
+    from setup_problem import Setup
+    from knpemi import MembraneExchange
+    from knpemi.stepper import DeviceStepper
+    with contextlib.redirect_stdout(io.StringIO()):
+        s = Setup("tet", 1 if args.workload == "config2" else 2, g_syn=10.0)
+    for t in s.subdomain_list:
+        for k in range(2):
+            s.c[t][k].x.array[:] = s.c_prev[t][k].x._a
+    st = DeviceStepper((s.a_emi, s.p_emi, s.L_emi), (s.a_knp, s.p_knp, s.L_knp), s.c, s.c_prev, s.phi, s.phi_M_prev,
+                       device_solves=(1e-6, 1e-7))
+    st.add_membrane_model(s.mem_models[0]["ode"], s.stim_params["stimulus"], s.stim_params["stimulus_locator"])
+    ex = MembraneExchange(s.subdomain_list, s.ion_list, s.physical_parameters)
+    ex.watch(1)
+
+    def leg():
+        st.reset()
+        with contextlib.redirect_stdout(io.StringIO()):
+            for _ in range(args.warmup):
+                st.step()
+            st.dp.sync()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                st.step()
+            st.dp.sync()
+        return (time.perf_counter() - t0) * 1e3 / args.steps
+
+    # a first, untimed pass of every leg: AMG set-up, solver mode choice, the ODE/assembly overlap decision, the
+    # allocation of the field buffers
+    leg()
+    st.exchange(ex, every=1, capacity=4096)
+    modes = dict(plain=None, series=0, fields=1)
+    for m in (0, 1):
+        st._ex_fields = m
+        leg()
+    ms = {k: [] for k in modes}
+    for _ in range(args.repeats):
+        for name, m in modes.items():       # detach for the plain leg (the table stays on the device)
+            st._ex = None if m is None else ex
+            st._ex_fields = m or 0
+            ms[name].append(leg())
+    st._ex = ex
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    out = dict(workload=args.workload, steps=args.steps, windows=args.repeats, facets=ex.n_facets(1), columns=ex.n_cols,
+               ms_per_step_plain=med["plain"], ms_per_step_series=med["series"], ms_per_step_fields=med["fields"],
+               us_per_step_series=float(np.median(np.array(ms["series"]) - np.array(ms["plain"])) * 1e3),
+               us_per_step_fields=float(np.median(np.array(ms["fields"]) - np.array(ms["plain"])) * 1e3),
+               windows_ms=ms)
+    if args.stats:
+        for name, (calls, us) in kernel_stats(args.stats).items():
+            out[f"kernel_{name}"] = dict(calls=calls, average_us=us)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
