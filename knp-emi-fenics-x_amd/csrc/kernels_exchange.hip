@@ -16,7 +16,7 @@
 // the degree-6 facet table qtab -- through the SAME device code (membrane_facet.h: FacetData, load_facet,
 // facet_point_fields), in the same lane layout: KN_MEM_LQ adjacent lanes share one (facet, side), each takes every
 // KN_MEM_LQ-th quadrature point and the lanes meet in a shuffle reduction.  The grid covers the facets of the watched
-// cells only (KnExTab: workgroup b belongs to one watch), both sides of each; a facet without a membrane model
+// cells only (KnWatchTab: workgroup b belongs to one watch), both sides of each; a facet without a membrane model
 // (fmodel < 0) contributes nothing.
 //
 // Per (facet, side): int j_k^s dS and int I_ch,k dS for the watched ions only (the mask is uniform over a workgroup);
@@ -28,35 +28,30 @@
 // Series row: per watched (cell, ion) int j^e, int j^i [mol/s] and int I_ch,k [A]; with the current columns int I_cap,
 // int I_ch,tot [A] and the membrane area.  The reduction follows flux_kernel: a fixed tree inside the workgroup (xor
 // butterfly over the 64 lanes of a wave, then the four waves in order), one partial of KN_EX_SLOTS doubles per workgroup,
-// and the last workgroup to arrive (ticket counter) folds the partials of every column in workgroup order and appends the
-// row.  No floating-point atomics: two identical runs give identical bits, and the row does not depend on write_fields.
-// The row counter lives in device memory and is advanced by that workgroup with a plain store from one lane, so a
-// replayed launch records into consecutive rows; a full buffer writes nothing and counts the row as dropped.
+// and the tail of record_tail.h: the last workgroup to arrive folds the partials of every column in workgroup order and
+// appends the row, or counts it as dropped when the buffer is full.  The row does not depend on write_fields.
 //
 // The membrane is a 2-D set: a launch is a few dozen workgroups that wait for their gathers, like knp_membrane_kernel.
 #include "knpemi_internal.h"
 #include "membrane_facet.h"
+#include "record_tail.h"
 
 #define EX_THREADS 256
 #define EX_WAVES (EX_THREADS / 64)
 #define EX_CHUNK (EX_THREADS / (2 * KN_MEM_LQ))      // facets per workgroup
 #define EX_QTAB (16 * (1 + 4 + 8))                   // the largest facet table (quadrilaterals: 16 points)
+#define EX_FOLD_DEPTH 16                             // loads the fold of the partials has in flight (kn_fold_column)
 
 namespace {
 
 struct ExArgs {
   int K, capacity, splitting;
-  const KnExTab* tab;
+  const KnWatchTab* tab;
   double* part;
   unsigned long long* ctl;
   double* rows;
   double* fld;
 };
-
-__device__ inline double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 template <int NF, bool FIELDS>
 __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnConsts* __restrict__ Cp, ExArgs A) {
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
   __shared__ int last;
   __shared__ unsigned long long row;
   const KnConsts& C = *Cp;
-  const KnExTab& T = *A.tab;
+  const KnWatchTab& T = *A.tab;
   const int K = A.K;
   const int nq = D.nq_gamma;
   const int ntab = nq * (1 + NF + (NF == 4 ? 2 * NF : 0));
@@ -78,14 +73,14 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
 
   int w = 0;
   while (w + 1 < T.n_watch && (int)blockIdx.x >= T.bstart[w + 1]) ++w;      // at most KN_MAXSUB - 1 steps, uniform
-  const int mask = T.mask[w], nf = T.nf[w];
-  const bool cur = (mask & KN_EX_CURRENT) != 0;
+  const int mask = T.mask[w], nf = T.count[w];
+  const bool cur = (mask & KN_WATCH_CURRENT) != 0;
   const int gt = ((int)blockIdx.x - T.bstart[w]) * EX_THREADS + (int)threadIdx.x;
   const int t = gt / KN_MEM_LQ, lq = gt % KN_MEM_LQ;
   // lanes past the watch's last (facet, side) repeat the last one and contribute nothing: the shuffles see whole groups
   const bool live = t < 2 * nf;
   const int tt = live ? t : 2 * nf - 1;
-  const int fl = tt >> 1, fg = T.f0[w] + fl;
+  const int fl = tt >> 1, fg = T.first[w] + fl;
   const bool cell_side = tt & 1;
   const int ms = D.fmodel[fg];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -141,15 +136,15 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
     put(lead_i, comp + 1, aj[k] * inv_area);
     put(lead_i, comp + 2, ai[k] * inv_area);
     comp += 3;
-    const double se = wave_sum(lead_e ? aj[k] : 0.0), si = wave_sum(lead_i ? aj[k] : 0.0);
-    const double sc = wave_sum(lead_i ? ai[k] : 0.0);
+    const double se = kn_wave_sum(lead_e ? aj[k] : 0.0), si = kn_wave_sum(lead_i ? aj[k] : 0.0);
+    const double sc = kn_wave_sum(lead_i ? ai[k] : 0.0);
     if (lane == 0) { sh[wave][3 * k] = se; sh[wave][3 * k + 1] = si; sh[wave][3 * k + 2] = sc; }
   }
   if (cur) {
     put(lead_i, comp, acap * inv_area);
     put(lead_i, comp + 1, area);
-    const double sc = wave_sum(lead_i ? acap : 0.0), st = wave_sum(lead_i ? atot : 0.0);
-    const double sa = wave_sum(lead_i ? area : 0.0);
+    const double sc = kn_wave_sum(lead_i ? acap : 0.0), st = kn_wave_sum(lead_i ? atot : 0.0);
+    const double sa = kn_wave_sum(lead_i ? area : 0.0);
     if (lane == 0) { sh[wave][3 * KN_MAXK] = sc; sh[wave][3 * KN_MAXK + 1] = st; sh[wave][3 * KN_MAXK + 2] = sa; }
   }
   __syncthreads();
@@ -160,41 +155,20 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
     double v = sh[0][j];
 #pragma unroll
     for (int q = 1; q < EX_WAVES; ++q) v += sh[q][j];
-    __hip_atomic_store(&A.part[(size_t)blockIdx.x * KN_EX_SLOTS + j], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
+    kn_part_store(&A.part[(size_t)blockIdx.x * KN_EX_SLOTS + j], v);
   }
-  if (threadIdx.x == 0) last = atomicAdd(&A.ctl[2], 1ull) == (unsigned long long)(gridDim.x - 1);
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  if (threadIdx.x == 0) row = A.ctl[0];     // last written by the previous launch
-  __syncthreads();
-  const bool room = row < (unsigned long long)A.capacity;
+  if (!kn_arrive_last(A.ctl, threadIdx.x < KN_EX_SLOTS, &last)) return;
+  const bool room = kn_claim_row(A.ctl, A.capacity, &row);
   if (room) {
     for (int q = threadIdx.x; q < T.n_cols; q += EX_THREADS) {
-      const int cw = T.col_watch[q], slot = T.col_slot[q];
-      // workgroup order: independent of which came last.  Sixteen loads are in flight before the first is added: one
-      // load per addition is a chain of L2 round trips, 60 us per record at config 2 (184 partials)
-      const double* __restrict__ pp = A.part + slot;
-      const int p1 = T.bstart[cw + 1];
-      int p = T.bstart[cw];
-      double v = 0.0;
-      for (; p + 16 <= p1; p += 16) {
-        double x[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          x[i] = __hip_atomic_load(pp + (size_t)(p + i) * KN_EX_SLOTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v += x[i];
-      }
-      for (; p < p1; ++p) v += __hip_atomic_load(pp + (size_t)p * KN_EX_SLOTS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      A.rows[(size_t)row * T.n_cols + q] = v;
+      const int cw = T.col_watch[q];      // every column is a sum: col_max is all zero here
+      A.rows[(size_t)row * T.n_cols + q] =
+          kn_fold_column<KN_EX_SLOTS, EX_FOLD_DEPTH>(A.part, T.col_slot[q], T.bstart[cw], T.bstart[cw + 1], false);
     }
   }
   if (threadIdx.x == 0) {
-    if (room) A.ctl[0] = row + 1;
-    else A.ctl[1] = A.ctl[1] + 1;
-    A.ctl[2] = 0;
+    kn_commit_row(A.ctl, row, room);
+    kn_reset_ticket(A.ctl);
   }
 }
 
@@ -212,7 +186,7 @@ int kn_launch_exchange(knpemi_handle* h, int write_fields) {
   if (h->dev.nq_gamma * (1 + h->NF + (h->NF == 4 ? 2 * h->NF : 0)) > EX_QTAB)
     return kn_fail(KNPEMI_EINVAL, "exchange_kernel: the facet quadrature table does not fit its LDS copy (EX_QTAB)");
   const int split = (h->knp_flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
-  const ExArgs a{h->K, X.capacity, split, X.tab, X.part, X.ctl, X.rows, write_fields ? X.fld : nullptr};
+  const ExArgs a{h->K, X.ser.capacity, split, X.tab, X.part, X.ser.ctl, X.ser.rows, write_fields ? X.fld : nullptr};
   const bool fields = write_fields != 0;
   if (h->NF == 2) launch<2>(h, a, X.n_blk, fields);
   else if (h->NF == 3) launch<3>(h, a, X.n_blk, fields);
@@ -221,3 +195,4 @@ int kn_launch_exchange(knpemi_handle* h, int write_fields) {
 }
 
 extern "C" int kn_exchange_chunk() { return EX_CHUNK; }
+extern "C" int kn_exchange_fold_depth() { return EX_FOLD_DEPTH; }

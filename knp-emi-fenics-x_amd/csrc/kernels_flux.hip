@@ -27,26 +27,28 @@
 // With write_fields the vectors go to structure-of-arrays buffers [component][cell] through non-temporal stores:
 // consecutive lanes write consecutive doubles, and nothing of it is read again by the device.
 //
-// Series row (KnFluxTab): per watched (sub-domain, ion) sum_T vol_T J_diff, sum_T vol_T J_drift (gdim values each) and
-// max_T |J|; per watched sub-domain with the current sum_T vol_T i and max_T |i|.  The reduction follows
-// observe_kernel: a fixed tree inside the workgroup (xor butterfly over the 64 lanes of a wave, then the four waves in
-// order), one partial of KN_FLUX_SLOTS doubles per workgroup, and the last workgroup to arrive (ticket counter) folds
-// the partials of every column in workgroup order and appends the row.  No floating-point atomics: two identical runs
-// give identical bits.  The row counter lives in device memory and is advanced by that workgroup with a plain store
-// from one lane, so a replayed launch records into consecutive rows; a full buffer writes nothing and counts the row
-// as dropped.
+// Series row (KnWatchTab): per watched (sub-domain, ion) sum_T vol_T J_diff, sum_T vol_T J_drift (gdim values each) and
+// max_T |J|; per watched sub-domain with the current sum_T vol_T i and max_T |i|.  The reduction is a fixed tree inside
+// the workgroup (xor butterfly over the 64 lanes of a wave, then the four waves in order), one partial of KN_FLUX_SLOTS
+// doubles per workgroup, and the tail of record_tail.h: the last workgroup to arrive folds the partials of every
+// column in workgroup order and appends the row, or counts it as dropped when the buffer is full.
 #include <cmath>
 
 #include "knpemi_internal.h"
+#include "record_tail.h"
 
 #define FLUX_THREADS KN_FLUX_CHUNK      // one lane per cell
 #define FLUX_WAVES (FLUX_THREADS / 64)
+// loads the fold of the partials has in flight (kn_fold_column): the largest depth that leaves the allocation of every
+// instantiation where its body puts it -- 13 raises the triangles' from 68 to 70 VGPRs, 14 takes one of their 7 waves
+// per SIMD, 16 two
+#define FLUX_FOLD_DEPTH 12
 
 namespace {
 
 struct FluxArgs {
   int K, capacity;
-  const KnFluxTab* tab;
+  const KnWatchTab* tab;
   const KnConsts* consts;
   const int* cells;
   const double* VR;
@@ -60,15 +62,6 @@ template <int KIND> struct FluxCell {
   static constexpr int GD = KIND == KNPEMI_TRIANGLE ? 2 : 3;
   static constexpr int NV = KIND == KNPEMI_TRIANGLE ? 3 : KIND == KNPEMI_TETRAHEDRON ? 4 : 8;
 };
-
-__device__ inline double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ inline double wave_max(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
 
 // the five fields of a record in the order phi, c_0 .. c_3 (KN_CSLOT)
 struct FluxRec { double x[3]; double u[5]; };
@@ -144,17 +137,17 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
   __shared__ double sh[FLUX_WAVES][KN_FLUX_SLOTS];
   __shared__ int last;
   __shared__ unsigned long long row;
-  const KnFluxTab& T = *A.tab;
+  const KnWatchTab& T = *A.tab;
   const int K = A.K;
   int w = 0;
   while (w + 1 < T.n_watch && (int)blockIdx.x >= T.bstart[w + 1]) ++w;      // at most KN_MAXSUB - 1 steps, uniform
-  const int s = T.sub[w], mask = T.mask[w], nc = T.nc[w];
-  const bool cur = (mask & KN_FLUX_CURRENT) != 0;
+  const int s = T.sub[w], mask = T.mask[w], nc = T.count[w];
+  const bool cur = (mask & KN_WATCH_CURRENT) != 0;
   const int lc = ((int)blockIdx.x - T.bstart[w]) * FLUX_THREADS + (int)threadIdx.x;
   const bool valid = lc < nc;
   // a lane past the sub-domain's last cell repeats that cell (it takes part in the wave reductions) and contributes
   // nothing
-  const size_t cell = (size_t)T.c0[w] + (size_t)(valid ? lc : nc - 1);
+  const size_t cell = (size_t)T.first[w] + (size_t)(valid ? lc : nc - 1);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (threadIdx.x < FLUX_WAVES * KN_FLUX_SLOTS) (&sh[0][0])[threadIdx.x] = 0.0;
   __syncthreads();
@@ -219,11 +212,11 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
     for (int a = 0; a < GD; ++a) {
       put(comp + a, Jd[a]);
       put(comp + GD + a, Jr[a]);
-      const double sd = wave_sum(vol * Jd[a]), sr = wave_sum(vol * Jr[a]);
+      const double sd = kn_wave_sum(vol * Jd[a]), sr = kn_wave_sum(vol * Jr[a]);
       if (lane == 0) { sh[wave][k * PER_ION + a] = sd; sh[wave][k * PER_ION + GD + a] = sr; }
     }
     comp += 2 * GD;
-    const double mx = wave_max(valid ? sqrt(n2) : 0.0);
+    const double mx = kn_wave_max(valid ? sqrt(n2) : 0.0);
     if (lane == 0) sh[wave][k * PER_ION + 2 * GD] = mx;
   }
   if (cur) {
@@ -234,10 +227,10 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
       put(comp + GD + a, i_drift[a]);
       const double i = i_diff[a] + i_drift[a];
       n2 += i * i;
-      const double si = wave_sum(vol * i);
+      const double si = kn_wave_sum(vol * i);
       if (lane == 0) sh[wave][KN_MAXK * PER_ION + a] = si;
     }
-    const double mx = wave_max(valid ? sqrt(n2) : 0.0);
+    const double mx = kn_wave_max(valid ? sqrt(n2) : 0.0);
     if (lane == 0) sh[wave][KN_MAXK * PER_ION + GD] = mx;
   }
   __syncthreads();
@@ -249,33 +242,20 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
     double v = sh[0][j];
 #pragma unroll
     for (int q = 1; q < FLUX_WAVES; ++q) v = is_max ? fmax(v, sh[q][j]) : v + sh[q][j];
-    __hip_atomic_store(&A.part[(size_t)blockIdx.x * KN_FLUX_SLOTS + j], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
+    kn_part_store(&A.part[(size_t)blockIdx.x * KN_FLUX_SLOTS + j], v);
   }
-  if (threadIdx.x == 0) last = atomicAdd(&A.ctl[2], 1ull) == (unsigned long long)(gridDim.x - 1);
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  if (threadIdx.x == 0) row = A.ctl[0];     // last written by the previous launch
-  __syncthreads();
-  const bool room = row < (unsigned long long)A.capacity;
+  if (!kn_arrive_last(A.ctl, threadIdx.x < KN_FLUX_SLOTS, &last)) return;
+  const bool room = kn_claim_row(A.ctl, A.capacity, &row);
   if (room) {
     for (int q = threadIdx.x; q < T.n_cols; q += FLUX_THREADS) {
-      const int cw = T.col_watch[q], slot = T.col_slot[q];
-      const bool is_max = T.col_max[q] != 0;
-      double v = 0.0;
-      for (int p = T.bstart[cw]; p < T.bstart[cw + 1]; ++p) {       // workgroup order: independent of which came last
-        const double x = __hip_atomic_load(&A.part[(size_t)p * KN_FLUX_SLOTS + slot], __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT);
-        v = is_max ? fmax(v, x) : v + x;
-      }
-      A.rows[(size_t)row * T.n_cols + q] = v;
+      const int cw = T.col_watch[q];
+      A.rows[(size_t)row * T.n_cols + q] =
+          kn_fold_column<KN_FLUX_SLOTS, FLUX_FOLD_DEPTH>(A.part, T.col_slot[q], T.bstart[cw], T.bstart[cw + 1], T.col_max[q] != 0);
     }
   }
   if (threadIdx.x == 0) {
-    if (room) A.ctl[0] = row + 1;
-    else A.ctl[1] = A.ctl[1] + 1;
-    A.ctl[2] = 0;
+    kn_commit_row(A.ctl, row, room);
+    kn_reset_ticket(A.ctl);
   }
 }
 
@@ -290,7 +270,7 @@ void launch(knpemi_handle* h, const FluxArgs& a, int n_blk, bool fields) {
 int kn_launch_flux(knpemi_handle* h, int write_fields) {
   const auto& X = h->flux;
   if (X.n_blk == 0) return KNPEMI_OK;
-  const FluxArgs a{h->K, X.capacity, X.tab, h->d_consts, h->dev.cells, h->dev.VR, X.part, X.ctl, X.rows,
+  const FluxArgs a{h->K, X.ser.capacity, X.tab, h->d_consts, h->dev.cells, h->dev.VR, X.part, X.ser.ctl, X.ser.rows,
                    write_fields ? X.fld : nullptr};
   const bool fields = write_fields != 0;
   if (h->cell_kind == KNPEMI_TRIANGLE) launch<KNPEMI_TRIANGLE>(h, a, X.n_blk, fields);
@@ -300,3 +280,4 @@ int kn_launch_flux(knpemi_handle* h, int write_fields) {
 }
 
 extern "C" int kn_flux_chunk() { return KN_FLUX_CHUNK; }
+extern "C" int kn_flux_fold_depth() { return FLUX_FOLD_DEPTH; }

@@ -5,13 +5,9 @@
 // local_astrocyte_depolarization/run_stim_duration.py:239-246).  Here a point is a sparse dot product over the <= 8
 // vertices of its cell and a reduction a dense one over a sub-domain; the host cuts every observable's entries into
 // chunks of OBS_CHUNK and gives each chunk one workgroup.  A workgroup reduces its chunk in a fixed order (strided
-// per-lane sums, then a fixed LDS tree), publishes the partial, and the last workgroup to arrive (ticket counter)
-// combines the partials of every observable in block order and appends the row.  No floating-point atomics: the
-// result does not depend on scheduling, so two identical runs give bit-identical series.
-//
-// The row index is a counter in device memory, advanced by that last workgroup with a plain store from one lane; the
-// launch carries no row number, so a captured and replayed step would still record into consecutive rows.  A full
-// buffer writes nothing and counts the row as dropped.
+// per-lane sums, then a fixed LDS tree) and publishes the partial; the tail is that of record_tail.h: the last
+// workgroup to arrive combines the partials of every observable in block order, with the observable's own op and
+// identity, and appends the row, or counts it as dropped when the buffer is full.
 //
 // Partitioned runs (knpemi_observe_set_partitioned): the last workgroup writes each observable's fold of its block
 // partials, without the denominator, into this rank's slot xbuf[rank * n_obs + q] instead of appending a row (an
@@ -22,6 +18,7 @@
 #include <cmath>
 
 #include "knpemi_internal.h"
+#include "record_tail.h"
 
 #define OBS_THREADS 256
 #define OBS_CHUNK (OBS_THREADS * 8)     // entries per workgroup: 8 loads per lane in flight on the dense reductions
@@ -86,42 +83,31 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_kernel(ObsArgs A) {
       __syncthreads();
     }
   }
-  if (threadIdx.x == 0) {
-    if (has_blk) __hip_atomic_store(&A.part[blockIdx.x], sh[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    last = atomicAdd(&A.ctl[2], 1ull) == (unsigned long long)(gridDim.x - 1);
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
+  if (threadIdx.x == 0 && has_blk) kn_part_store(&A.part[blockIdx.x], sh[0]);
+  if (!kn_arrive_last(A.ctl, threadIdx.x == 0, &last)) return;
+  // this observable's block partials in block order: independent of which block came last
+  auto fold = [&](int q, int qop) {
+    double v = obs_identity(qop);
+    for (int p = A.blk_ptr[q]; p < A.blk_ptr[q + 1]; ++p) v = obs_combine(qop, v, kn_part_load(&A.part[p]));
+    return v;
+  };
   if (A.slot) {                             // partitioned: this rank's slots; the row is appended by the combine kernel
-    for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) {
-      const int qop = A.op[q];
-      double v = obs_identity(qop);
-      for (int p = A.blk_ptr[q]; p < A.blk_ptr[q + 1]; ++p)
-        v = obs_combine(qop, v, __hip_atomic_load(&A.part[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      A.slot[q] = v;
-    }
-    if (threadIdx.x == 0) A.ctl[2] = 0;
+    for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) A.slot[q] = fold(q, A.op[q]);
+    if (threadIdx.x == 0) kn_reset_ticket(A.ctl);
     return;
   }
-  if (threadIdx.x == 0) row = A.ctl[0];     // last written by the previous launch
-  __syncthreads();
-  const bool room = row < (unsigned long long)A.capacity;
+  const bool room = kn_claim_row(A.ctl, A.capacity, &row);
   if (room) {
     for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) {
       const int qop = A.op[q];
-      double v = obs_identity(qop);
-      for (int p = A.blk_ptr[q]; p < A.blk_ptr[q + 1]; ++p)       // block order: independent of which block came last
-        v = obs_combine(qop, v, __hip_atomic_load(&A.part[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      double v = fold(q, qop);
       if (qop == KNPEMI_OBS_SUM) v /= A.denom[q];
       A.rows[(size_t)row * A.n_obs + q] = v;
     }
   }
   if (threadIdx.x == 0) {
-    if (room) A.ctl[0] = row + 1;
-    else A.ctl[1] = A.ctl[1] + 1;
-    A.ctl[2] = 0;
+    kn_commit_row(A.ctl, row, room);
+    kn_reset_ticket(A.ctl);
   }
 }
 
@@ -130,13 +116,11 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_kernel(ObsArgs A) {
 // that the next sum over the ranks again has one non-zero contributor per slot.
 __global__ __launch_bounds__(OBS_THREADS) void observe_combine_kernel(ObsCombineArgs A) {
   __shared__ unsigned long long row;
-  if (threadIdx.x == 0) row = A.ctl[0];
-  __syncthreads();
-  const bool room = row < (unsigned long long)A.capacity;
+  const bool room = kn_claim_row(A.ctl, A.capacity, &row);
   for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) {
     const int qop = A.op[q];
     double v = obs_identity(qop);
-    for (int r = 0; r < A.world; ++r) v = obs_combine(qop, v, A.xbuf[(size_t)r * A.n_obs + q]);
+    for (int k = 0; k < A.world; ++k) v = obs_combine(qop, v, A.xbuf[(size_t)k * A.n_obs + q]);
     if (qop == KNPEMI_OBS_SUM) v /= A.denom[q];
     if (room) A.rows[(size_t)row * A.n_obs + q] = v;
   }
@@ -144,10 +128,7 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_combine_kernel(ObsCombine
   const int n = A.world * A.n_obs;
   for (int i = threadIdx.x; i < n; i += OBS_THREADS)
     if (i / A.n_obs != A.rank) A.xbuf[i] = 0.0;
-  if (threadIdx.x == 0) {
-    if (room) A.ctl[0] = row + 1;
-    else A.ctl[1] = A.ctl[1] + 1;
-  }
+  if (threadIdx.x == 0) kn_commit_row(A.ctl, row, room);      // one workgroup: no ticket
 }
 
 }  // namespace
@@ -155,15 +136,15 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_combine_kernel(ObsCombine
 int kn_launch_observe(knpemi_handle* h) {
   const auto& O = h->obs;
   if (O.n_blk == 0 && !O.xbuf) return KNPEMI_OK;
-  ObsArgs a{O.n_obs, O.capacity, O.n_blk, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ctl,
-            O.rows, O.xbuf ? O.xbuf + (size_t)O.rank * O.n_obs : nullptr};
+  ObsArgs a{O.n_obs, O.ser.capacity, O.n_blk, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ser.ctl,
+            O.ser.rows, O.xbuf ? O.xbuf + (size_t)O.rank * O.n_obs : nullptr};
   hipLaunchKernelGGL(observe_kernel, dim3(std::max(O.n_blk, 1)), dim3(OBS_THREADS), 0, h->stream, a);
   return kn_launch_check("observe_kernel");
 }
 
 int kn_launch_observe_combine(knpemi_handle* h) {
   const auto& O = h->obs;
-  ObsCombineArgs a{O.n_obs, O.capacity, O.world, O.rank, O.op, O.denom, O.xbuf, O.ctl, O.rows};
+  ObsCombineArgs a{O.n_obs, O.ser.capacity, O.world, O.rank, O.op, O.denom, O.xbuf, O.ser.ctl, O.ser.rows};
   hipLaunchKernelGGL(observe_combine_kernel, dim3(1), dim3(OBS_THREADS), 0, h->stream, a);
   return kn_launch_check("observe_combine_kernel");
 }

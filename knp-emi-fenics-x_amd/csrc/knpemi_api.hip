@@ -971,10 +971,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   if (h->aux) (void)hipStreamDestroy(h->aux);
   kn_comm_destroy(h);
   kn_solver_free(h);
-  kn_free_all(h->obs.allocs);
-  kn_free_all(h->events.allocs);
-  kn_free_all(h->flux.allocs);
-  kn_free_all(h->exchange.allocs);
+  kn_record_free(h);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
   kn_device_close(h);
   delete h;
@@ -1027,10 +1024,7 @@ extern "C" void* knpemi_stream(knpemi_handle* h) { return h ? (void*)h->stream :
 // ---------------------------------------------------------------------------------------------------
 // field I/O
 // ---------------------------------------------------------------------------------------------------
-namespace {
-struct FieldLoc { double* base; int stride; size_t n; };
-
-int locate(knpemi_handle* h, int field, int sub, int idx, FieldLoc* loc) {
+int kn_locate(knpemi_handle* h, int field, int sub, int idx, KnFieldLoc* loc) {
   if (sub < 0 || sub >= h->n_sub) return kn_fail(KNPEMI_EINVAL, "field: bad sub-domain index");
   const int K = h->K;
   KnDev& D = h->dev;
@@ -1064,13 +1058,12 @@ int locate(knpemi_handle* h, int field, int sub, int idx, FieldLoc* loc) {
   }
   return kn_fail(KNPEMI_EINVAL, "field: unknown field id");
 }
-}  // namespace
 
 extern "C" int knpemi_set_field(knpemi_handle* h, int field, int sub, int idx, const double* host, size_t n) {
   if (!h || !host) return kn_fail(KNPEMI_EINVAL, "knpemi_set_field: null argument");
   kn_inputs_changed(h);
-  FieldLoc L;
-  int rc = locate(h, field, sub, idx, &L);
+  KnFieldLoc L;
+  int rc = kn_locate(h, field, sub, idx, &L);
   if (rc) return rc;
   if (n != L.n) return kn_fail(KNPEMI_EINVAL, "knpemi_set_field: length does not match the function space");
   if (n == 0) return KNPEMI_OK;
@@ -1085,8 +1078,8 @@ extern "C" int knpemi_set_field(knpemi_handle* h, int field, int sub, int idx, c
 
 extern "C" int knpemi_get_field(knpemi_handle* h, int field, int sub, int idx, double* host, size_t n) {
   if (!h || !host) return kn_fail(KNPEMI_EINVAL, "knpemi_get_field: null argument");
-  FieldLoc L;
-  int rc = locate(h, field, sub, idx, &L);
+  KnFieldLoc L;
+  int rc = kn_locate(h, field, sub, idx, &L);
   if (rc) return rc;
   if (n != L.n) return kn_fail(KNPEMI_EINVAL, "knpemi_get_field: length does not match the function space");
   if (n == 0) return KNPEMI_OK;
@@ -1672,528 +1665,6 @@ extern "C" int knpemi_update_pde(knpemi_handle* h) {
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
   return kn_launch_update_pde(h);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// observables (kernels_observe.hip)
-// ---------------------------------------------------------------------------------------------------
-int kn_observe_chunk();
-
-namespace {
-void observe_free(knpemi_handle* h) {
-  kn_free_all(h->obs.allocs);
-  h->obs = knpemi_handle::KnObserve{};
-}
-
-// knpemi_observe_set and knpemi_observe_set_partitioned; the partitioned table may hold observables without entries
-int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
-                const double* w, const double* denom, int capacity, bool partitioned) {
-  const std::string fn(who);
-  if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
-  if (n_obs < 1 || capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": n_obs and capacity must be positive");
-  if (ptr[0] != 0) return kn_fail(KNPEMI_EINVAL, fn + ": ptr[0] must be 0");
-  if (ptr[n_obs] > 0 && (!idx || !w)) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  const int chunk = kn_observe_chunk();
-  std::vector<int4> blk;
-  std::vector<int> blk_ptr(1, 0), op(n_obs), stride(n_obs);
-  std::vector<const double*> base(n_obs);
-  for (int o = 0; o < n_obs; ++o) {
-    const int32_t field = spec[4 * o], sub = spec[4 * o + 1], ix = spec[4 * o + 2], oo = spec[4 * o + 3];
-    if (oo != KNPEMI_OBS_SUM && oo != KNPEMI_OBS_MIN && oo != KNPEMI_OBS_MAX)
-      return kn_fail(KNPEMI_EINVAL, fn + ": unknown op of observable " + std::to_string(o));
-    if ((partitioned ? ptr[o + 1] < ptr[o] : ptr[o + 1] <= ptr[o]) || ptr[o + 1] > (int64_t)INT32_MAX)
-      return kn_fail(KNPEMI_EINVAL, fn + ": observable " + std::to_string(o) + (partitioned ? " has a bad entry range" : " has no entries"));
-    FieldLoc L;
-    int rc = locate(h, field, sub, ix, &L);
-    if (rc) return rc;
-    for (int64_t e = ptr[o]; e < ptr[o + 1]; ++e)        // every read of the kernel stays inside the field
-      if (idx[e] < 0 || (size_t)idx[e] >= L.n)
-        return kn_fail(KNPEMI_EINVAL, fn + ": index out of range in observable " + std::to_string(o));
-    op[o] = oo; stride[o] = L.stride; base[o] = L.base;
-    for (int64_t e = ptr[o]; e < ptr[o + 1]; e += chunk)
-      blk.push_back(make_int4(o, (int)e, (int)std::min<int64_t>(e + chunk, ptr[o + 1]), 0));
-    blk_ptr.push_back((int)blk.size());
-  }
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  observe_free(h);
-  auto& O = h->obs;
-  const size_t ne = (size_t)ptr[n_obs];
-  int rc;
-  auto& A = O.allocs;
-  if ((rc = kn_upload(A, blk, &O.blk)) || (rc = kn_upload(A, blk_ptr, &O.blk_ptr)) || (rc = kn_upload(A, op, &O.op))
-      || (rc = kn_upload(A, stride, &O.stride)) || (rc = kn_upload(A, base, &O.base))
-      || (rc = kn_upload(A, denom, (size_t)n_obs, &O.denom))
-      || (rc = kn_upload(A, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = kn_upload(A, w, ne, &O.w))) {
-    observe_free(h);
-    return rc;
-  }
-  const size_t row_bytes = (size_t)capacity * n_obs * sizeof(double);
-  if (kn_alloc(A, blk.size(), &O.part)) { observe_free(h); return kn_fail(KNPEMI_ENOMEM, fn + ": partials"); }
-  if (kn_alloc(A, 4, &O.ctl)) { observe_free(h); return kn_fail(KNPEMI_ENOMEM, fn + ": counters"); }
-  if (kn_alloc(A, (size_t)capacity * n_obs, &O.rows)) { observe_free(h); return kn_fail(KNPEMI_ENOMEM, fn + ": buffer"); }
-  KN_HIP(hipMemsetAsync(O.ctl, 0, 4 * sizeof(unsigned long long), h->stream));
-  KN_HIP(hipMemsetAsync(O.rows, 0, row_bytes, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  O.n_obs = n_obs; O.n_blk = (int)blk.size(); O.capacity = capacity;
-  return KNPEMI_OK;
-}
-}  // namespace
-
-extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
-                                  const int32_t* idx, const double* w, const double* denom, int capacity) {
-  return observe_set(h, "knpemi_observe_set", n_obs, spec, ptr, idx, w, denom, capacity, false);
-}
-
-extern "C" int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
-                                              const int32_t* idx, const double* w, const double* denom, int capacity,
-                                              int rank, int world, void* xbuf_dev, knpemi_allreduce_fn allreduce,
-                                              void* ctx) {
-  const char* fn = "knpemi_observe_set_partitioned";
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  if (world < 1 || rank < 0 || rank >= world) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": bad rank / world");
-  if (!xbuf_dev) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer is required");
-  if (!allreduce && !h->comm)
-    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
-  if (n_obs > 0 && (size_t)world * (size_t)n_obs > (size_t)INT32_MAX)
-    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer too large");
-  int rc = observe_set(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, true);
-  if (rc) return rc;
-  auto& O = h->obs;
-  O.xbuf = static_cast<double*>(xbuf_dev);
-  O.rank = rank; O.world = world; O.allreduce = allreduce; O.ctx = ctx;
-  KN_HIP(hipMemsetAsync(O.xbuf, 0, (size_t)world * n_obs * sizeof(double), h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_observe_record(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& O = h->obs;
-  if (O.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
-  KN_HIP(hipSetDevice(h->device));
-  int rc = kn_launch_observe(h);
-  if (rc || !O.xbuf) return rc;
-  // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
-  const int n = O.world * O.n_obs;
-  rc = O.allreduce ? (O.allreduce(O.ctx, n) ? kn_fail(KNPEMI_EHIP, "knpemi_observe_record: allreduce hook failed") : KNPEMI_OK)
-                   : knpemi_comm_allreduce(h, O.xbuf, n);
-  if (rc) return rc;
-  return kn_launch_observe_combine(h);
-}
-
-extern "C" int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow,
-                                   int reset) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& O = h->obs;
-  if (O.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_read: no observables set");
-  if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_read: bad output buffer");
-  KN_HIP(hipSetDevice(h->device));
-  unsigned long long ctl[4];
-  int rc;
-  if ((rc = kn_to_host(h->stream, ctl, O.ctl, 4))) return rc;
-  const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
-  if (n && (rc = kn_to_host(h->stream, out, O.rows, n * O.n_obs))) return rc;
-  if (rows) *rows = (int64_t)ctl[0];
-  if (overflow) *overflow = (int64_t)ctl[1];
-  if (reset) {
-    KN_HIP(hipMemsetAsync(O.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-  }
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_observe_clear(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  observe_free(h);
-  return KNPEMI_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// membrane events (kernels_events.hip)
-// ---------------------------------------------------------------------------------------------------
-namespace {
-void events_free(knpemi_handle* h) {
-  kn_free_all(h->events.allocs);
-  h->events = knpemi_handle::KnEvents{};
-}
-}  // namespace
-
-extern "C" int knpemi_events_set(knpemi_handle* h, int n_watch, const int32_t* sub, const double* threshold,
-                                 const double* reset, int keep) {
-  const std::string fn = "knpemi_events_set";
-  if (!h || !sub || !threshold) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  if (n_watch < 1 || n_watch > KN_MAXSUB - 1) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB - 1 sub-domains");
-  if (keep < 0 || keep > KNPEMI_EVENTS_MAX_KEEP) return kn_fail(KNPEMI_EINVAL, fn + ": keep must be in 0..KNPEMI_EVENTS_MAX_KEEP");
-  KnEvTab T{};
-  bool watched[KN_MAXSUB] = {};
-  for (int w = 0; w < n_watch; ++w) {
-    const int s = sub[w];
-    if (s < 1 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": bad sub-domain index (the ECS has no membrane space)");
-    if (watched[s]) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain " + std::to_string(s) + " is listed twice");
-    const double thr = threshold[w], rst = reset ? reset[w] : thr;
-    if (!(rst <= thr)) return kn_fail(KNPEMI_EINVAL, fn + ": reset must not exceed the threshold");
-    watched[s] = true;
-    T.gstart[w + 1] = T.gstart[w] + h->n_q[s];
-    T.q0[w] = h->qoff[s];
-    T.sub[w] = s;
-    T.threshold[s] = thr;
-    T.reset[s] = rst;
-  }
-  T.n_watch = n_watch;
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  events_free(h);
-  auto& E = h->events;
-  auto& A = E.allocs;
-  const size_t nq = (size_t)h->dev.NQtot;
-  int rc;
-  if ((rc = kn_upload(A, &T, 1, &E.tab)) || (rc = kn_alloc(A, nq, &E.v_prev)) || (rc = kn_alloc(A, nq, &E.armed))
-      || (rc = kn_alloc(A, nq, &E.count)) || (rc = kn_alloc(A, nq, &E.t_first)) || (rc = kn_alloc(A, nq, &E.t_last))
-      || (rc = kn_alloc(A, nq, &E.v_peak)) || (rc = kn_alloc(A, nq, &E.t_peak))
-      || (rc = kn_alloc(A, nq * (size_t)keep, &E.ring))) {
-    events_free(h);
-    return rc;
-  }
-  E.n_watch = n_watch; E.keep = keep; E.n_grid = T.gstart[n_watch];
-  std::copy(watched, watched + KN_MAXSUB, E.watched);
-  if ((rc = kn_launch_events_reset(h))) { events_free(h); return rc; }
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_events_record(knpemi_handle* h, double t) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& E = h->events;
-  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: no events set (knpemi_events_set)");
-  if (!std::isfinite(t) || (E.have_prev && !(t > E.t_prev)))
-    return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: t must be finite and greater than the previous record's");
-  KN_HIP(hipSetDevice(h->device));
-  if (int rc = kn_launch_events_record(h, E.have_prev ? 0 : 1, t, E.t_prev)) return rc;
-  E.have_prev = true;
-  E.t_prev = t;
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_events_read(knpemi_handle* h, int sub, int32_t* count, double* t_first, double* t_last,
-                                  double* v_peak, double* t_peak, double* ring) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& E = h->events;
-  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: no events set (knpemi_events_set)");
-  if (sub < 1 || sub >= h->n_sub || !E.watched[sub])
-    return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: sub-domain is not watched");
-  KN_HIP(hipSetDevice(h->device));
-  const size_t q0 = (size_t)h->qoff[sub], nq = (size_t)h->n_q[sub], nq_tot = (size_t)h->dev.NQtot;
-  if (nq) {
-    auto copy = [&](auto* host, const auto* dev, size_t n) -> int {
-      if (host) KN_HIP(hipMemcpyAsync(host, dev, n * sizeof(*host), hipMemcpyDeviceToHost, h->stream));
-      return KNPEMI_OK;
-    };
-    int rc;
-    if ((rc = copy(count, E.count + q0, nq)) || (rc = copy(t_first, E.t_first + q0, nq))
-        || (rc = copy(t_last, E.t_last + q0, nq)) || (rc = copy(v_peak, E.v_peak + q0, nq))
-        || (rc = copy(t_peak, E.t_peak + q0, nq)))
-      return rc;
-    for (int k = 0; ring && k < E.keep; ++k)          // row k of the ring: this sub-domain's piece of [keep][NQtot]
-      if ((rc = copy(ring + (size_t)k * nq, E.ring + (size_t)k * nq_tot + q0, nq))) return rc;
-  }
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_events_reset(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& E = h->events;
-  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_reset: no events set (knpemi_events_set)");
-  KN_HIP(hipSetDevice(h->device));
-  E.have_prev = false;
-  E.t_prev = 0.0;
-  return kn_launch_events_reset(h);
-}
-
-extern "C" int knpemi_events_clear(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  events_free(h);
-  return KNPEMI_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// ion fluxes and current density per cell (kernels_flux.hip)
-// ---------------------------------------------------------------------------------------------------
-extern "C" int kn_flux_chunk();
-
-namespace {
-void flux_free(knpemi_handle* h) {
-  kn_free_all(h->flux.allocs);
-  h->flux = knpemi_handle::KnFlux{};
-}
-inline int flux_popcount(int m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
-}  // namespace
-
-extern "C" int knpemi_flux_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
-  const std::string fn = "knpemi_flux_set";
-  if (!h || !sub || !ion_mask) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
-  if (n_watch < 1 || n_watch > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB sub-domains");
-  if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
-  const int K = h->K, gd = h->gdim, per_ion = 2 * gd + 1, chunk = kn_flux_chunk();
-  KnFluxTab T{};
-  int watch_of[KN_MAXSUB];
-  std::fill(watch_of, watch_of + KN_MAXSUB, -1);
-  long long fbase = 0;
-  int col = 0;
-  for (int w = 0; w < n_watch; ++w) {
-    const int s = sub[w], m = ion_mask[w];
-    if (s < 0 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": bad sub-domain index");
-    if (watch_of[s] >= 0) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain " + std::to_string(s) + " is listed twice");
-    if (h->n_cell[s] < 1) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain " + std::to_string(s) + " has no cells");
-    if (m == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty ion mask");
-    if (m & ~(KN_FLUX_CURRENT | ((1 << K) - 1)))
-      return kn_fail(KNPEMI_EINVAL, fn + ": ion mask has bits at or above the number of ions (bit 8: the current)");
-    watch_of[s] = w;
-    T.sub[w] = s; T.mask[w] = m; T.c0[w] = h->coff[s]; T.nc[w] = h->n_cell[s];
-    T.bstart[w + 1] = T.bstart[w] + (h->n_cell[s] + chunk - 1) / chunk;
-    T.fbase[w] = fbase;
-    fbase += (long long)(flux_popcount(m & 0xFF) + ((m & KN_FLUX_CURRENT) ? 1 : 0)) * 2 * gd * h->n_cell[s];
-    for (int k = 0; k < K; ++k) {
-      if (!((m >> k) & 1)) continue;
-      for (int j = 0; j < per_ion; ++j, ++col) {
-        T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(k * per_ion + j); T.col_max[col] = j == 2 * gd;
-      }
-    }
-    if (m & KN_FLUX_CURRENT)
-      for (int j = 0; j <= gd; ++j, ++col) {
-        T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(KN_MAXK * per_ion + j); T.col_max[col] = j == gd;
-      }
-  }
-  T.n_watch = n_watch; T.n_cols = col;
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  flux_free(h);
-  auto& X = h->flux;
-  auto& A = X.allocs;
-  const int n_blk = T.bstart[n_watch];
-  int rc;
-  if ((rc = kn_upload(A, &T, 1, &X.tab)) || (rc = kn_alloc(A, (size_t)n_blk * KN_FLUX_SLOTS, &X.part))
-      || (rc = kn_zeros(A, h->stream, 4, &X.ctl)) || (rc = kn_zeros(A, h->stream, (size_t)capacity * col, &X.rows))) {
-    flux_free(h);
-    return rc;
-  }
-  X.host = T; X.n_watch = n_watch; X.capacity = capacity; X.n_blk = n_blk; X.fld_len = (size_t)fbase;
-  std::copy(watch_of, watch_of + KN_MAXSUB, X.watch_of);
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_flux_record(knpemi_handle* h, int write_fields) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& X = h->flux;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_record: no fluxes set (knpemi_flux_set)");
-  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_record: knpemi_set_params not called");
-  KN_HIP(hipSetDevice(h->device));
-  if (write_fields && !X.fld)
-    if (int rc = kn_alloc(X.allocs, X.fld_len, &X.fld)) return rc;
-  if (int rc = kn_launch_flux(h, write_fields)) return rc;
-  if (write_fields) X.fld_valid = true;
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_flux_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& X = h->flux;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_read: no fluxes set (knpemi_flux_set)");
-  if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_read: bad output buffer");
-  KN_HIP(hipSetDevice(h->device));
-  unsigned long long ctl[4];
-  int rc;
-  if ((rc = kn_to_host(h->stream, ctl, X.ctl, 4))) return rc;
-  const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
-  if (n && (rc = kn_to_host(h->stream, out, X.rows, n * X.host.n_cols))) return rc;
-  if (rows) *rows = (int64_t)ctl[0];
-  if (overflow) *overflow = (int64_t)ctl[1];
-  if (reset) {
-    KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-  }
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_flux_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n) {
-  const std::string fn = "knpemi_flux_fields";
-  if (!h || !host) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  auto& X = h->flux;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": no fluxes set (knpemi_flux_set)");
-  if (sub < 0 || sub >= h->n_sub || X.watch_of[sub] < 0) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain is not watched");
-  const int w = X.watch_of[sub], m = X.host.mask[w], gd = h->gdim;
-  if (part != 0 && part != 1) return kn_fail(KNPEMI_EINVAL, fn + ": part is 0 (diffusive) or 1 (drift)");
-  if (ion == -1 ? !(m & KN_FLUX_CURRENT) : (ion < 0 || ion >= h->K || !((m >> ion) & 1)))
-    return kn_fail(KNPEMI_EINVAL, fn + (ion == -1 ? ": the current of this sub-domain is not watched"
-                                                   : ": this ion of the sub-domain is not watched"));
-  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (knpemi_flux_record(h, 1))");
-  const size_t nc = (size_t)X.host.nc[w];
-  if (n != nc * gd) return kn_fail(KNPEMI_EINVAL, fn + ": length is not gdim * number of cells");
-  const int before = ion == -1 ? flux_popcount(m & 0xFF) : flux_popcount(m & ((1 << ion) - 1));
-  KN_HIP(hipSetDevice(h->device));
-  return kn_to_host(h->stream, host, X.fld + X.host.fbase[w] + (size_t)(2 * before + part) * gd * nc, n);
-}
-
-extern "C" int knpemi_flux_reset(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& X = h->flux;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_reset: no fluxes set (knpemi_flux_set)");
-  KN_HIP(hipSetDevice(h->device));
-  X.fld_valid = false;
-  KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_flux_clear(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  flux_free(h);
-  return KNPEMI_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// membrane ion exchange per cell (kernels_exchange.hip)
-// ---------------------------------------------------------------------------------------------------
-extern "C" int kn_exchange_chunk();
-
-namespace {
-void exchange_free(knpemi_handle* h) {
-  kn_free_all(h->exchange.allocs);
-  h->exchange = knpemi_handle::KnExchange{};
-}
-}  // namespace
-
-extern "C" int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
-  const std::string fn = "knpemi_exchange_set";
-  if (!h || !sub || !ion_mask) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
-  if (n_watch < 1 || n_watch > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB cells");
-  if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
-  const int K = h->K, chunk = kn_exchange_chunk();
-  KnExTab T{};
-  int watch_of[KN_MAXSUB];
-  std::fill(watch_of, watch_of + KN_MAXSUB, -1);
-  long long fbase = 0;
-  int col = 0;
-  for (int w = 0; w < n_watch; ++w) {
-    const int s = sub[w], m = ion_mask[w];
-    if (s == 0) return kn_fail(KNPEMI_EINVAL, fn + ": the ECS (sub-domain 0) has no membrane of its own: watch the cells");
-    if (s < 0 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": unknown cell (bad sub-domain index)");
-    if (watch_of[s] >= 0) return kn_fail(KNPEMI_EINVAL, fn + ": cell " + std::to_string(s) + " is listed twice");
-    if (h->n_facet[s] < 1) return kn_fail(KNPEMI_EINVAL, fn + ": cell " + std::to_string(s) + " has no membrane facets");
-    if (m == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty ion mask");
-    if (m & ~(KN_EX_CURRENT | ((1 << K) - 1)))
-      return kn_fail(KNPEMI_EINVAL, fn + ": ion mask has bits at or above the number of ions (bit 8: the current columns)");
-    watch_of[s] = w;
-    T.sub[w] = s; T.mask[w] = m; T.f0[w] = h->foff[s]; T.nf[w] = h->n_facet[s];
-    T.bstart[w + 1] = T.bstart[w] + (h->n_facet[s] + chunk - 1) / chunk;
-    T.fbase[w] = fbase;
-    fbase += (long long)(3 * flux_popcount(m & 0xFF) + ((m & KN_EX_CURRENT) ? 2 : 0)) * h->n_facet[s];
-    for (int k = 0; k < K; ++k) {
-      if (!((m >> k) & 1)) continue;
-      for (int j = 0; j < 3; ++j, ++col) { T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(3 * k + j); }
-    }
-    if (m & KN_EX_CURRENT)
-      for (int j = 0; j < 3; ++j, ++col) { T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)(3 * KN_MAXK + j); }
-  }
-  T.n_watch = n_watch; T.n_cols = col;
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  exchange_free(h);
-  auto& X = h->exchange;
-  auto& A = X.allocs;
-  const int n_blk = T.bstart[n_watch];
-  int rc;
-  if ((rc = kn_upload(A, &T, 1, &X.tab)) || (rc = kn_alloc(A, (size_t)n_blk * KN_EX_SLOTS, &X.part))
-      || (rc = kn_zeros(A, h->stream, 4, &X.ctl)) || (rc = kn_zeros(A, h->stream, (size_t)capacity * col, &X.rows))) {
-    exchange_free(h);
-    return rc;
-  }
-  X.host = T; X.n_watch = n_watch; X.capacity = capacity; X.n_blk = n_blk; X.fld_len = (size_t)fbase;
-  std::copy(watch_of, watch_of + KN_MAXSUB, X.watch_of);
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_exchange_record(knpemi_handle* h, int write_fields) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& X = h->exchange;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_record: no exchange set (knpemi_exchange_set)");
-  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_record: knpemi_set_params not called");
-  KN_HIP(hipSetDevice(h->device));
-  // phi_M and I_ch come from the ODE sweeps, which may run on the auxiliary streams (as in knpemi_assemble_knp)
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
-  if (write_fields && !X.fld)
-    if (int rc = kn_alloc(X.allocs, X.fld_len, &X.fld)) return rc;
-  if (int rc = kn_launch_exchange(h, write_fields)) return rc;
-  if (write_fields) X.fld_valid = true;
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_exchange_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& X = h->exchange;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_read: no exchange set (knpemi_exchange_set)");
-  if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_read: bad output buffer");
-  KN_HIP(hipSetDevice(h->device));
-  unsigned long long ctl[4];
-  int rc;
-  if ((rc = kn_to_host(h->stream, ctl, X.ctl, 4))) return rc;
-  const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
-  if (n && (rc = kn_to_host(h->stream, out, X.rows, n * X.host.n_cols))) return rc;
-  if (rows) *rows = (int64_t)ctl[0];
-  if (overflow) *overflow = (int64_t)ctl[1];
-  if (reset) {
-    KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
-  }
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_exchange_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n) {
-  const std::string fn = "knpemi_exchange_fields";
-  if (!h || !host) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  auto& X = h->exchange;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": no exchange set (knpemi_exchange_set)");
-  if (sub < 0 || sub >= h->n_sub || X.watch_of[sub] < 0) return kn_fail(KNPEMI_EINVAL, fn + ": cell is not watched");
-  const int w = X.watch_of[sub], m = X.host.mask[w];
-  if (ion == -1 ? !(m & KN_EX_CURRENT) : (ion < 0 || ion >= h->K || !((m >> ion) & 1)))
-    return kn_fail(KNPEMI_EINVAL, fn + (ion == -1 ? ": the current columns of this cell are not watched"
-                                                   : ": this ion of the cell is not watched"));
-  if (part < 0 || part > (ion == -1 ? 1 : 2))
-    return kn_fail(KNPEMI_EINVAL, fn + ": part is 0 (ECS side), 1 (cell side) or 2 (channel current) of an ion, "
-                                       "0 (capacitive current) or 1 (area) with ion == -1");
-  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (knpemi_exchange_record(h, 1))");
-  const size_t nf = (size_t)X.host.nf[w];
-  if (n != nf) return kn_fail(KNPEMI_EINVAL, fn + ": length is not the number of membrane facets of the cell");
-  const int comp = ion == -1 ? 3 * flux_popcount(m & 0xFF) + part : 3 * flux_popcount(m & ((1 << ion) - 1)) + part;
-  KN_HIP(hipSetDevice(h->device));
-  return kn_to_host(h->stream, host, X.fld + X.host.fbase[w] + (size_t)comp * nf, n);
-}
-
-extern "C" int knpemi_exchange_reset(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  auto& X = h->exchange;
-  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_reset: no exchange set (knpemi_exchange_set)");
-  KN_HIP(hipSetDevice(h->device));
-  X.fld_valid = false;
-  KN_HIP(hipMemsetAsync(X.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
-  return KNPEMI_OK;
-}
-
-extern "C" int knpemi_exchange_clear(knpemi_handle* h) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  exchange_free(h);
-  return KNPEMI_OK;
 }
 
 extern "C" int knpemi_set_distributed(knpemi_handle* h, const uint8_t* owned, void* reduce_buf_dev,

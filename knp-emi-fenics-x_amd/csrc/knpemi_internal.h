@@ -125,47 +125,32 @@ struct KnEvTab {
   double reset[KN_MAXSUB];
 };
 
-// Table of the watched sub-domains of the ion fluxes (kernels_flux.hip), read by the record kernel.  Workgroup b belongs to
-// watch w with bstart[w] <= b < bstart[w + 1] and takes the KN_FLUX_CHUNK cells c0[w] + (b - bstart[w]) * KN_FLUX_CHUNK ..
-// of the nc[w] cells of sub-domain sub[w].  A workgroup's partial has KN_FLUX_SLOTS doubles at fixed places: ion k at
-// k (2 gdim + 1) .. ({sum vol J_diff}, {sum vol J_drift}, max |J|), the current at K (2 gdim + 1) .. ({sum vol i}, max |i|).
-// Column q of the series row is slot col_slot[q] of watch col_watch[q], folded over that watch's workgroups by sum or
-// (col_max[q]) maximum.  The per-cell fields of watch w start at fbase[w] doubles: [component][nc[w]], the selected ions
-// in ascending order ({J_diff}, {J_drift} each), then the current ({i_diff}, {i_drift}).
+// Table of the watches of a recorder with per-item fields and a series row: the ion fluxes (kernels_flux.hip; an item is a
+// cell, a watch a sub-domain) and the membrane exchange (kernels_exchange.hip; an item is a membrane facet, a watch a cell),
+// read by the record kernel.  Workgroup b belongs to watch w with bstart[w] <= b < bstart[w + 1] and takes one chunk
+// (KN_FLUX_CHUNK cells; kn_exchange_chunk() facets, both sides of each) of the count[w] items of sub-domain sub[w], from
+// first[w] + (b - bstart[w]) * chunk on.  A workgroup's partial has KN_FLUX_SLOTS / KN_EX_SLOTS doubles at fixed places:
+//   fluxes    ion k at k (2 gdim + 1) .. ({sum vol J_diff}, {sum vol J_drift}, max |J|), the current at
+//             KN_MAXK (2 gdim + 1) .. ({sum vol i}, max |i|);
+//   exchange  ion k at 3 k .. (int j_k^e, int j_k^i, int I_ch,k), then at 3 KN_MAXK .. int I_cap, int I_ch,tot, the area.
+// Column q of the series row is slot col_slot[q] of watch col_watch[q], folded over that watch's workgroups in their
+// order by sum or (col_max[q]; the fluxes' maxima only) maximum.  The per-item fields of watch w start at fbase[w]
+// doubles: [component][count[w]], the selected ions in ascending order (fluxes: {J_diff}, {J_drift}; exchange: j^e, j^i,
+// I_ch,k), then the current (fluxes: {i_diff}, {i_drift}; exchange: I_cap and the area).
 #define KN_FLUX_CHUNK 256
 #define KN_FLUX_SLOTS 32        // >= KN_MAXK (2 * 3 + 1) + 3 + 1
-#define KN_FLUX_MAXCOLS (KN_MAXSUB * KN_FLUX_SLOTS)
-#define KN_FLUX_CURRENT 0x100   // bit 8 of a watch's ion mask
-struct KnFluxTab {
-  int n_watch, n_cols;
-  int bstart[KN_MAXSUB + 1];
-  int sub[KN_MAXSUB];
-  int c0[KN_MAXSUB];
-  int nc[KN_MAXSUB];
-  int mask[KN_MAXSUB];
-  long long fbase[KN_MAXSUB];
-  uint8_t col_watch[KN_FLUX_MAXCOLS], col_slot[KN_FLUX_MAXCOLS], col_max[KN_FLUX_MAXCOLS];
-};
-
-// Table of the watched cells of the membrane exchange (kernels_exchange.hip), read by the record kernel.  Workgroup b belongs
-// to watch w with bstart[w] <= b < bstart[w + 1] and takes kn_exchange_chunk() facets, both sides of each, from
-// f0[w] + (b - bstart[w]) * chunk on, of the nf[w] membrane facets of cell sub-domain sub[w].  A workgroup's partial has
-// KN_EX_SLOTS doubles at fixed places: ion k at 3 k .. (int j_k^e, int j_k^i, int I_ch,k), then at 3 KN_MAXK .. int I_cap,
-// int I_ch,tot and the area.  Column q of the series row is slot col_slot[q] of watch col_watch[q], summed over that
-// watch's workgroups in their order.  The per-facet means of watch w start at fbase[w] doubles: [component][nf[w]], the
-// selected ions in ascending order (j^e, j^i, I_ch,k each), then, with the current columns, I_cap and the area.
 #define KN_EX_SLOTS 16          // >= 3 KN_MAXK + 3
-#define KN_EX_MAXCOLS (KN_MAXSUB * KN_EX_SLOTS)
-#define KN_EX_CURRENT 0x100     // bit 8 of a watch's ion mask
-struct KnExTab {
+#define KN_WATCH_MAXCOLS (KN_MAXSUB * KN_FLUX_SLOTS)
+#define KN_WATCH_CURRENT 0x100  // bit 8 of a watch's ion mask
+struct KnWatchTab {
   int n_watch, n_cols;
   int bstart[KN_MAXSUB + 1];
   int sub[KN_MAXSUB];
-  int f0[KN_MAXSUB];
-  int nf[KN_MAXSUB];
+  int first[KN_MAXSUB];
+  int count[KN_MAXSUB];
   int mask[KN_MAXSUB];
   long long fbase[KN_MAXSUB];
-  uint8_t col_watch[KN_EX_MAXCOLS], col_slot[KN_EX_MAXCOLS];
+  uint8_t col_watch[KN_WATCH_MAXCOLS], col_slot[KN_WATCH_MAXCOLS], col_max[KN_WATCH_MAXCOLS];
 };
 
 struct KnOdeModel {
@@ -583,20 +568,26 @@ struct knpemi_handle : KnDevice {
   int lds_gam_max = 0;                 // most membrane entries of one row block
   bool blocks_clustered = false;       // row blocks are clusters of row chunks (default), not consecutive rows
   KnDist dist;
-  // observables (knpemi_observe_set, kernels_observe.hip); freed by knpemi_observe_clear / knpemi_destroy
+  // The recorders (knpemi_record.hip); each is freed by its knpemi_*_clear, all of them by kn_record_free.
+  // A series buffer: the rows a record kernel appends (record_tail.h) until the host reads them.
+  struct KnSeries {
+    unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last workgroup
+    double* rows = nullptr;              // [capacity][n_cols]
+    int capacity = 0, n_cols = 0;
+  };
+  // observables (knpemi_observe_set, kernels_observe.hip)
   struct KnObserve {
-    int n_obs = 0, n_blk = 0, capacity = 0;
+    int n_obs = 0, n_blk = 0;
     int4* blk = nullptr;                 // [n_blk] {observable, first entry, end entry, 0}
     int* blk_ptr = nullptr;              // [n_obs + 1] first block of every observable
     int* op = nullptr;                   // [n_obs]
     int* stride = nullptr;               // [n_obs]
-    const double** base = nullptr;       // [n_obs] field addresses (locate())
+    const double** base = nullptr;       // [n_obs] field addresses (kn_locate)
     double* denom = nullptr;             // [n_obs] divisor of a sum (1, n for a nodal mean, the measure for an average)
     int* idx = nullptr;                  // [entries]
     double* w = nullptr;                 // [entries]
     double* part = nullptr;              // [n_blk] block partials
-    unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last block
-    double* rows = nullptr;              // [capacity][n_obs]
+    KnSeries ser;
     // partitioned runs (knpemi_observe_set_partitioned): the caller's [world][n_obs] exchange buffer, summed over the
     // ranks by `allreduce` (or the library's communicator when it is null) between the partial and the combine launch
     double* xbuf = nullptr;
@@ -605,7 +596,7 @@ struct knpemi_handle : KnDevice {
     void* ctx = nullptr;
     std::vector<void*> allocs;
   } obs;
-  // membrane events (knpemi_events_set, kernels_events.hip); freed by knpemi_events_clear / knpemi_destroy
+  // membrane events (knpemi_events_set, kernels_events.hip)
   struct KnEvents {
     int n_watch = 0, keep = 0, n_grid = 0;
     bool watched[KN_MAXSUB] = {};
@@ -619,34 +610,20 @@ struct knpemi_handle : KnDevice {
     double *t_first = nullptr, *t_last = nullptr, *v_peak = nullptr, *t_peak = nullptr, *ring = nullptr;
     std::vector<void*> allocs;
   } events;
-  // ion fluxes and current density per cell (knpemi_flux_set, kernels_flux.hip); freed by knpemi_flux_clear / knpemi_destroy
-  struct KnFlux {
-    int n_watch = 0, capacity = 0, n_blk = 0;
-    KnFluxTab host{};                    // the table as uploaded
+  // ion fluxes and current density per cell (knpemi_flux_set, kernels_flux.hip) and membrane ion exchange per cell
+  // (knpemi_exchange_set, kernels_exchange.hip): a watch table, workgroup partials, per-item fields and a series
+  struct KnWatched {
+    int n_watch = 0, n_blk = 0;
+    KnWatchTab host{};                   // the table as uploaded
     int watch_of[KN_MAXSUB] = {};        // sub-domain -> watch, -1: not watched
-    KnFluxTab* tab = nullptr;
-    double* part = nullptr;              // [n_blk][KN_FLUX_SLOTS] workgroup partials
-    unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last workgroup
-    double* rows = nullptr;              // [capacity][n_cols]
-    double* fld = nullptr;               // per-cell fields, allocated at the first record that writes them
+    KnWatchTab* tab = nullptr;
+    double* part = nullptr;              // [n_blk][slots] workgroup partials
+    KnSeries ser;
+    double* fld = nullptr;               // per-item fields, allocated at the first record that writes them
     size_t fld_len = 0;
     bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
     std::vector<void*> allocs;
-  } flux;
-  // membrane ion exchange per cell (knpemi_exchange_set, kernels_exchange.hip); freed by knpemi_exchange_clear / knpemi_destroy
-  struct KnExchange {
-    int n_watch = 0, capacity = 0, n_blk = 0;
-    KnExTab host{};                      // the table as uploaded
-    int watch_of[KN_MAXSUB] = {};        // sub-domain -> watch, -1: not watched
-    KnExTab* tab = nullptr;
-    double* part = nullptr;              // [n_blk][KN_EX_SLOTS] workgroup partials
-    unsigned long long* ctl = nullptr;   // [4]: rows written, rows dropped (buffer full), ticket of the last workgroup
-    double* rows = nullptr;              // [capacity][n_cols]
-    double* fld = nullptr;               // per-facet means, allocated at the first record that writes them
-    size_t fld_len = 0;
-    bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
-    std::vector<void*> allocs;
-  } exchange;
+  } flux, exchange;
   int knp_flags = 0;                   // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
 };
 
@@ -660,6 +637,10 @@ int kn_comm_sendrecv(void* comm, int world, int device, hipStream_t stream, cons
                      int n_parts, const int32_t* peer, const int64_t* send_off, const int64_t* send_cnt,
                      const int64_t* recv_off, const int64_t* recv_cnt);
 int kn_gamma_quadrature(int NF, std::vector<double>* out);   // degree-6 membrane-facet rule (knpemi_api.hip)
+// where a field of knpemi_set_field / knpemi_get_field lives on the device (knpemi_api.hip)
+struct KnFieldLoc { double* base; int stride; size_t n; };
+int kn_locate(knpemi_handle* h, int field, int sub, int idx, KnFieldLoc* loc);
+void kn_record_free(knpemi_handle* h);    // every recorder's device memory (knpemi_record.hip)
 
 // kernel launchers (kernels_*.hip) ------------------------------------------------------------
 int kn_launch_emi_rows(knpemi_handle* h, int flags);

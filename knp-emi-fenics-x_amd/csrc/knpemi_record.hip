@@ -1,0 +1,481 @@
+// The on-device recorders behind the C ABI (include/knpemi_hip.h): observables (kernels_observe.hip), membrane events
+// (kernels_events.hip), ion fluxes per cell (kernels_flux.hip) and the membrane exchange per cell (kernels_exchange.hip).
+//
+// Three of them append rows to a series buffer (KnSeries; the device side is record_tail.h).  The fluxes and the exchange
+// are one recorder over different items -- the cells of a watched sub-domain, the membrane facets of a watched cell: they
+// share KnWatched, KnWatchTab and every routine but the launch, and a WatchKind names what differs.  The membrane events
+// keep per-dof maps and no series.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "knpemi_internal.h"
+
+int kn_observe_chunk();
+extern "C" int kn_flux_chunk();
+extern "C" int kn_exchange_chunk();
+
+namespace {
+using KnSeries = knpemi_handle::KnSeries;
+using KnWatched = knpemi_handle::KnWatched;
+
+int series_alloc(std::vector<void*>& owner, hipStream_t st, int capacity, int n_cols, KnSeries* S) {
+  if (int rc = kn_zeros(owner, st, 4, &S->ctl)) return rc;
+  if (int rc = kn_zeros(owner, st, (size_t)capacity * n_cols, &S->rows)) return rc;
+  S->capacity = capacity; S->n_cols = n_cols;
+  return KNPEMI_OK;
+}
+
+// a new series: rows written and rows dropped back to 0, stream-ordered (no synchronisation)
+int series_rewind(knpemi_handle* h, KnSeries& S) {
+  KN_HIP(hipMemsetAsync(S.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
+  return KNPEMI_OK;
+}
+
+// knpemi_*_read: the first min(n_rows, rows written) rows and the two counters; reset: rewind, synchronised
+int series_read(knpemi_handle* h, KnSeries& S, bool set, const char* fn, const char* none, int n_rows, double* out,
+                int64_t* rows, int64_t* overflow, int reset) {
+  if (!set) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": " + none);
+  if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": bad output buffer");
+  KN_HIP(hipSetDevice(h->device));
+  unsigned long long ctl[4];
+  int rc;
+  if ((rc = kn_to_host(h->stream, ctl, S.ctl, 4))) return rc;
+  const size_t n = std::min<size_t>((size_t)n_rows, (size_t)ctl[0]);
+  if (n && (rc = kn_to_host(h->stream, out, S.rows, n * S.n_cols))) return rc;
+  if (rows) *rows = (int64_t)ctl[0];
+  if (overflow) *overflow = (int64_t)ctl[1];
+  if (reset) {
+    if ((rc = series_rewind(h, S))) return rc;
+    KN_HIP(hipStreamSynchronize(h->stream));
+  }
+  return KNPEMI_OK;
+}
+
+// free what a recorder's `allocs` holds and forget it; knpemi_*_clear waits for the enqueued records first
+template <class R>
+void recorder_free(R& rec) {
+  kn_free_all(rec.allocs);
+  rec = R{};
+}
+template <class R>
+int recorder_clear(knpemi_handle* h, R knpemi_handle::*which) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  recorder_free(h->*which);
+  return KNPEMI_OK;
+}
+}  // namespace
+
+void kn_record_free(knpemi_handle* h) {
+  for (auto* a : {&h->obs.allocs, &h->events.allocs, &h->flux.allocs, &h->exchange.allocs}) kn_free_all(*a);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// observables (kernels_observe.hip)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// knpemi_observe_set and knpemi_observe_set_partitioned; the partitioned table may hold observables without entries
+int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
+                const double* w, const double* denom, int capacity, bool partitioned) {
+  const std::string fn(who);
+  if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_obs < 1 || capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": n_obs and capacity must be positive");
+  if (ptr[0] != 0) return kn_fail(KNPEMI_EINVAL, fn + ": ptr[0] must be 0");
+  if (ptr[n_obs] > 0 && (!idx || !w)) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  const int chunk = kn_observe_chunk();
+  std::vector<int4> blk;
+  std::vector<int> blk_ptr(1, 0), op(n_obs), stride(n_obs);
+  std::vector<const double*> base(n_obs);
+  for (int o = 0; o < n_obs; ++o) {
+    const int32_t field = spec[4 * o], sub = spec[4 * o + 1], ix = spec[4 * o + 2], oo = spec[4 * o + 3];
+    if (oo != KNPEMI_OBS_SUM && oo != KNPEMI_OBS_MIN && oo != KNPEMI_OBS_MAX)
+      return kn_fail(KNPEMI_EINVAL, fn + ": unknown op of observable " + std::to_string(o));
+    if ((partitioned ? ptr[o + 1] < ptr[o] : ptr[o + 1] <= ptr[o]) || ptr[o + 1] > (int64_t)INT32_MAX)
+      return kn_fail(KNPEMI_EINVAL, fn + ": observable " + std::to_string(o) + (partitioned ? " has a bad entry range" : " has no entries"));
+    KnFieldLoc L;
+    int rc = kn_locate(h, field, sub, ix, &L);
+    if (rc) return rc;
+    for (int64_t e = ptr[o]; e < ptr[o + 1]; ++e)        // every read of the kernel stays inside the field
+      if (idx[e] < 0 || (size_t)idx[e] >= L.n)
+        return kn_fail(KNPEMI_EINVAL, fn + ": index out of range in observable " + std::to_string(o));
+    op[o] = oo; stride[o] = L.stride; base[o] = L.base;
+    for (int64_t e = ptr[o]; e < ptr[o + 1]; e += chunk)
+      blk.push_back(make_int4(o, (int)e, (int)std::min<int64_t>(e + chunk, ptr[o + 1]), 0));
+    blk_ptr.push_back((int)blk.size());
+  }
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  recorder_free(h->obs);
+  auto& O = h->obs;
+  const size_t ne = (size_t)ptr[n_obs];
+  int rc;
+  auto& A = O.allocs;
+  if ((rc = kn_upload(A, blk, &O.blk)) || (rc = kn_upload(A, blk_ptr, &O.blk_ptr)) || (rc = kn_upload(A, op, &O.op))
+      || (rc = kn_upload(A, stride, &O.stride)) || (rc = kn_upload(A, base, &O.base))
+      || (rc = kn_upload(A, denom, (size_t)n_obs, &O.denom))
+      || (rc = kn_upload(A, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = kn_upload(A, w, ne, &O.w))) {
+    recorder_free(h->obs);
+    return rc;
+  }
+  if (kn_alloc(A, blk.size(), &O.part)) { recorder_free(h->obs); return kn_fail(KNPEMI_ENOMEM, fn + ": partials"); }
+  if (series_alloc(A, h->stream, capacity, n_obs, &O.ser)) { recorder_free(h->obs); return kn_fail(KNPEMI_ENOMEM, fn + ": buffer"); }
+  O.n_obs = n_obs; O.n_blk = (int)blk.size();
+  return KNPEMI_OK;
+}
+}  // namespace
+
+extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
+                                  const int32_t* idx, const double* w, const double* denom, int capacity) {
+  return observe_set(h, "knpemi_observe_set", n_obs, spec, ptr, idx, w, denom, capacity, false);
+}
+
+extern "C" int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
+                                              const int32_t* idx, const double* w, const double* denom, int capacity,
+                                              int rank, int world, void* xbuf_dev, knpemi_allreduce_fn allreduce,
+                                              void* ctx) {
+  const char* fn = "knpemi_observe_set_partitioned";
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (world < 1 || rank < 0 || rank >= world) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": bad rank / world");
+  if (!xbuf_dev) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer is required");
+  if (!allreduce && !h->comm)
+    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
+  if (n_obs > 0 && (size_t)world * (size_t)n_obs > (size_t)INT32_MAX)
+    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer too large");
+  int rc = observe_set(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, true);
+  if (rc) return rc;
+  auto& O = h->obs;
+  O.xbuf = static_cast<double*>(xbuf_dev);
+  O.rank = rank; O.world = world; O.allreduce = allreduce; O.ctx = ctx;
+  KN_HIP(hipMemsetAsync(O.xbuf, 0, (size_t)world * n_obs * sizeof(double), h->stream));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_observe_record(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& O = h->obs;
+  if (O.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
+  KN_HIP(hipSetDevice(h->device));
+  int rc = kn_launch_observe(h);
+  if (rc || !O.xbuf) return rc;
+  // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
+  const int n = O.world * O.n_obs;
+  rc = O.allreduce ? (O.allreduce(O.ctx, n) ? kn_fail(KNPEMI_EHIP, "knpemi_observe_record: allreduce hook failed") : KNPEMI_OK)
+                   : knpemi_comm_allreduce(h, O.xbuf, n);
+  if (rc) return rc;
+  return kn_launch_observe_combine(h);
+}
+
+extern "C" int knpemi_observe_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow,
+                                   int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  return series_read(h, h->obs.ser, h->obs.n_obs != 0, "knpemi_observe_read", "no observables set", n_rows, out, rows, overflow, reset);
+}
+
+extern "C" int knpemi_observe_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::obs); }
+
+// ---------------------------------------------------------------------------------------------------
+// membrane events (kernels_events.hip)
+// ---------------------------------------------------------------------------------------------------
+extern "C" int knpemi_events_set(knpemi_handle* h, int n_watch, const int32_t* sub, const double* threshold,
+                                 const double* reset, int keep) {
+  const std::string fn = "knpemi_events_set";
+  if (!h || !sub || !threshold) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (n_watch < 1 || n_watch > KN_MAXSUB - 1) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB - 1 sub-domains");
+  if (keep < 0 || keep > KNPEMI_EVENTS_MAX_KEEP) return kn_fail(KNPEMI_EINVAL, fn + ": keep must be in 0..KNPEMI_EVENTS_MAX_KEEP");
+  KnEvTab T{};
+  bool watched[KN_MAXSUB] = {};
+  for (int w = 0; w < n_watch; ++w) {
+    const int s = sub[w];
+    if (s < 1 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": bad sub-domain index (the ECS has no membrane space)");
+    if (watched[s]) return kn_fail(KNPEMI_EINVAL, fn + ": sub-domain " + std::to_string(s) + " is listed twice");
+    const double thr = threshold[w], rst = reset ? reset[w] : thr;
+    if (!(rst <= thr)) return kn_fail(KNPEMI_EINVAL, fn + ": reset must not exceed the threshold");
+    watched[s] = true;
+    T.gstart[w + 1] = T.gstart[w] + h->n_q[s];
+    T.q0[w] = h->qoff[s];
+    T.sub[w] = s;
+    T.threshold[s] = thr;
+    T.reset[s] = rst;
+  }
+  T.n_watch = n_watch;
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  recorder_free(h->events);
+  auto& E = h->events;
+  auto& A = E.allocs;
+  const size_t nq = (size_t)h->dev.NQtot;
+  int rc;
+  if ((rc = kn_upload(A, &T, 1, &E.tab)) || (rc = kn_alloc(A, nq, &E.v_prev)) || (rc = kn_alloc(A, nq, &E.armed))
+      || (rc = kn_alloc(A, nq, &E.count)) || (rc = kn_alloc(A, nq, &E.t_first)) || (rc = kn_alloc(A, nq, &E.t_last))
+      || (rc = kn_alloc(A, nq, &E.v_peak)) || (rc = kn_alloc(A, nq, &E.t_peak))
+      || (rc = kn_alloc(A, nq * (size_t)keep, &E.ring))) {
+    recorder_free(h->events);
+    return rc;
+  }
+  E.n_watch = n_watch; E.keep = keep; E.n_grid = T.gstart[n_watch];
+  std::copy(watched, watched + KN_MAXSUB, E.watched);
+  if ((rc = kn_launch_events_reset(h))) { recorder_free(h->events); return rc; }
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_events_record(knpemi_handle* h, double t) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: no events set (knpemi_events_set)");
+  if (!std::isfinite(t) || (E.have_prev && !(t > E.t_prev)))
+    return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: t must be finite and greater than the previous record's");
+  KN_HIP(hipSetDevice(h->device));
+  if (int rc = kn_launch_events_record(h, E.have_prev ? 0 : 1, t, E.t_prev)) return rc;
+  E.have_prev = true;
+  E.t_prev = t;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_events_read(knpemi_handle* h, int sub, int32_t* count, double* t_first, double* t_last,
+                                  double* v_peak, double* t_peak, double* ring) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: no events set (knpemi_events_set)");
+  if (sub < 1 || sub >= h->n_sub || !E.watched[sub])
+    return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: sub-domain is not watched");
+  KN_HIP(hipSetDevice(h->device));
+  const size_t q0 = (size_t)h->qoff[sub], nq = (size_t)h->n_q[sub], nq_tot = (size_t)h->dev.NQtot;
+  if (nq) {
+    auto copy = [&](auto* host, const auto* dev, size_t n) -> int {
+      if (host) KN_HIP(hipMemcpyAsync(host, dev, n * sizeof(*host), hipMemcpyDeviceToHost, h->stream));
+      return KNPEMI_OK;
+    };
+    int rc;
+    if ((rc = copy(count, E.count + q0, nq)) || (rc = copy(t_first, E.t_first + q0, nq))
+        || (rc = copy(t_last, E.t_last + q0, nq)) || (rc = copy(v_peak, E.v_peak + q0, nq))
+        || (rc = copy(t_peak, E.t_peak + q0, nq)))
+      return rc;
+    for (int k = 0; ring && k < E.keep; ++k)          // row k of the ring: this sub-domain's piece of [keep][NQtot]
+      if ((rc = copy(ring + (size_t)k * nq, E.ring + (size_t)k * nq_tot + q0, nq))) return rc;
+  }
+  KN_HIP(hipStreamSynchronize(h->stream));
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_events_reset(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_reset: no events set (knpemi_events_set)");
+  KN_HIP(hipSetDevice(h->device));
+  E.have_prev = false;
+  E.t_prev = 0.0;
+  return kn_launch_events_reset(h);
+}
+
+extern "C" int knpemi_events_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::events); }
+
+// ---------------------------------------------------------------------------------------------------
+// ion fluxes and current density per cell (kernels_flux.hip), membrane ion exchange per cell (kernels_exchange.hip)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// what differs between the two: the names in the messages, the items, and the sizes
+struct WatchKind {
+  const char* name;        // the entry points are knpemi_<name>_*
+  const char* none;        // the message of a call before knpemi_<name>_set
+  const char* watch;       // what one watch is ...
+  const char* items;       // ... and what its items are
+  const char* bad_sub;     // the message of a sub-domain index out of range
+  const char* current;     // what bit 8 of an ion mask selects
+  bool ecs;                // sub-domain 0 may be watched
+  int slots;               // doubles per workgroup partial
+  KnWatched knpemi_handle::*state;
+  int (*launch)(knpemi_handle*, int);
+  bool after_ode;          // the record reads phi_M and I_ch, which the ODE sweeps may write on the auxiliary streams
+};
+const WatchKind FLUX{"flux", "no fluxes set (knpemi_flux_set)", "sub-domain", "cells", "bad sub-domain index", "the current",
+                     true, KN_FLUX_SLOTS, &knpemi_handle::flux, kn_launch_flux, false};
+const WatchKind EXCHANGE{"exchange", "no exchange set (knpemi_exchange_set)", "cell", "membrane facets",
+                         "unknown cell (bad sub-domain index)", "the current columns", false, KN_EX_SLOTS,
+                         &knpemi_handle::exchange, kn_launch_exchange, true};
+
+inline std::string entry(const WatchKind& k, const char* what) { return std::string("knpemi_") + k.name + "_" + what; }
+inline int popcount(int m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
+inline int ions_below(int m, int ion) { return popcount(m & (ion == -1 ? 0xFF : (1 << ion) - 1)); }
+
+// knpemi_<name>_set.  off / count: first item and number of items of every sub-domain; chunk: items per workgroup;
+// ion_fld / cur_fld: field doubles per item of a watched ion / of the current; cols(mask, emit): the columns of one
+// watch, in row order, as emit(slot, is_max).  A refused call leaves the previous table alone.
+template <class Cols>
+int watched_set(knpemi_handle* h, const WatchKind& k, const std::vector<int>& off, const std::vector<int>& count, int chunk,
+                int ion_fld, int cur_fld, Cols cols, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
+  const std::string fn = entry(k, "set");
+  if (!h || !sub || !ion_mask) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_watch < 1 || n_watch > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB " + k.watch + "s");
+  if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
+  KnWatchTab T{};
+  int watch_of[KN_MAXSUB];
+  std::fill(watch_of, watch_of + KN_MAXSUB, -1);
+  long long fbase = 0;
+  int col = 0;
+  for (int w = 0; w < n_watch; ++w) {
+    const int s = sub[w], m = ion_mask[w];
+    if (s == 0 && !k.ecs) return kn_fail(KNPEMI_EINVAL, fn + ": the ECS (sub-domain 0) has no membrane of its own: watch the cells");
+    if (s < 0 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.bad_sub);
+    if (watch_of[s] >= 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.watch + " " + std::to_string(s) + " is listed twice");
+    if (count[s] < 1) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.watch + " " + std::to_string(s) + " has no " + k.items);
+    if (m == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty ion mask");
+    if (m & ~(KN_WATCH_CURRENT | ((1 << h->K) - 1)))
+      return kn_fail(KNPEMI_EINVAL, fn + ": ion mask has bits at or above the number of ions (bit 8: " + k.current + ")");
+    watch_of[s] = w;
+    T.sub[w] = s; T.mask[w] = m; T.first[w] = off[s]; T.count[w] = count[s];
+    T.bstart[w + 1] = T.bstart[w] + (count[s] + chunk - 1) / chunk;
+    T.fbase[w] = fbase;
+    fbase += (long long)(ion_fld * popcount(m & 0xFF) + ((m & KN_WATCH_CURRENT) ? cur_fld : 0)) * count[s];
+    cols(m, [&](int slot, bool is_max) {
+      T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)slot; T.col_max[col] = is_max;
+      ++col;
+    });
+  }
+  T.n_watch = n_watch; T.n_cols = col;
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  KnWatched& X = h->*k.state;
+  recorder_free(X);
+  const int n_blk = T.bstart[n_watch];
+  int rc;
+  if ((rc = kn_upload(X.allocs, &T, 1, &X.tab)) || (rc = kn_alloc(X.allocs, (size_t)n_blk * k.slots, &X.part))
+      || (rc = series_alloc(X.allocs, h->stream, capacity, col, &X.ser))) {
+    recorder_free(X);
+    return rc;
+  }
+  X.host = T; X.n_watch = n_watch; X.n_blk = n_blk; X.fld_len = (size_t)fbase;
+  std::copy(watch_of, watch_of + KN_MAXSUB, X.watch_of);
+  return KNPEMI_OK;
+}
+
+// knpemi_<name>_record: the field buffer is allocated by the first record that writes it
+int watched_record(knpemi_handle* h, const WatchKind& k, int write_fields) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  KnWatched& X = h->*k.state;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, entry(k, "record") + ": " + k.none);
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, entry(k, "record") + ": knpemi_set_params not called");
+  KN_HIP(hipSetDevice(h->device));
+  if (k.after_ode) {     // as in knpemi_assemble_knp
+    KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+  }
+  if (write_fields && !X.fld)
+    if (int rc = kn_alloc(X.allocs, X.fld_len, &X.fld)) return rc;
+  if (int rc = k.launch(h, write_fields)) return rc;
+  if (write_fields) X.fld_valid = true;
+  return KNPEMI_OK;
+}
+
+// knpemi_<name>_reset: a new series, stream-ordered; the fields of the old one are forgotten
+int watched_reset(knpemi_handle* h, const WatchKind& k) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  KnWatched& X = h->*k.state;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, entry(k, "reset") + ": " + k.none);
+  KN_HIP(hipSetDevice(h->device));
+  X.fld_valid = false;
+  return series_rewind(h, X.ser);
+}
+
+// knpemi_<name>_fields, first half: the watch of `sub` in *w
+int fields_watch(knpemi_handle* h, const WatchKind& k, int sub, const double* host, int* w) {
+  const std::string fn = entry(k, "fields");
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  const KnWatched& X = h->*k.state;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.none);
+  if (sub < 0 || sub >= h->n_sub || X.watch_of[sub] < 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.watch + " is not watched");
+  *w = X.watch_of[sub];
+  return KNPEMI_OK;
+}
+// ... the ion (-1: the current) is one of watch w
+int fields_ion(knpemi_handle* h, const WatchKind& k, int w, int ion) {
+  const int m = (h->*k.state).host.mask[w];
+  if (ion == -1 ? !(m & KN_WATCH_CURRENT) : (ion < 0 || ion >= h->K || !((m >> ion) & 1)))
+    return kn_fail(KNPEMI_EINVAL, entry(k, "fields") + ": " + (ion == -1 ? k.current : "this ion") + " of the " + k.watch
+                                      + " is not watched");
+  return KNPEMI_OK;
+}
+// ... and second half: n doubles from `offset` of watch w's fields; `want`: the length they have, `length`: in words
+int fields_copy(knpemi_handle* h, const WatchKind& k, int w, size_t offset, double* host, size_t n, size_t want,
+                const char* length) {
+  const std::string fn = entry(k, "fields");
+  const KnWatched& X = h->*k.state;
+  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (" + entry(k, "record") + "(h, 1))");
+  if (n != want) return kn_fail(KNPEMI_EINVAL, fn + ": length is not " + length);
+  KN_HIP(hipSetDevice(h->device));
+  return kn_to_host(h->stream, host, X.fld + X.host.fbase[w] + offset, n);
+}
+}  // namespace
+
+extern "C" int knpemi_flux_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_set: null argument");
+  const int K = h->K, gd = h->gdim, per_ion = 2 * gd + 1;
+  // per watched ion {sum vol J_diff}, {sum vol J_drift}, max |J|; with the current {sum vol i}, max |i|
+  auto cols = [&](int m, auto emit) {
+    for (int k = 0; k < K; ++k)
+      if ((m >> k) & 1)
+        for (int j = 0; j < per_ion; ++j) emit(k * per_ion + j, j == 2 * gd);
+    if (m & KN_WATCH_CURRENT)
+      for (int j = 0; j <= gd; ++j) emit(KN_MAXK * per_ion + j, j == gd);
+  };
+  return watched_set(h, FLUX, h->coff, h->n_cell, kn_flux_chunk(), 2 * gd, 2 * gd, cols, n_watch, sub, ion_mask, capacity);
+}
+
+extern "C" int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_set: null argument");
+  const int K = h->K;
+  // per watched ion int j^e, int j^i, int I_ch,k; with the current columns int I_cap, int I_ch,tot and the area: all sums
+  auto cols = [&](int m, auto emit) {
+    for (int k = 0; k < K; ++k)
+      if ((m >> k) & 1)
+        for (int j = 0; j < 3; ++j) emit(3 * k + j, false);
+    if (m & KN_WATCH_CURRENT)
+      for (int j = 0; j < 3; ++j) emit(3 * KN_MAXK + j, false);
+  };
+  return watched_set(h, EXCHANGE, h->foff, h->n_facet, kn_exchange_chunk(), 3, 2, cols, n_watch, sub, ion_mask, capacity);
+}
+
+extern "C" int knpemi_flux_record(knpemi_handle* h, int write_fields) { return watched_record(h, FLUX, write_fields); }
+extern "C" int knpemi_exchange_record(knpemi_handle* h, int write_fields) { return watched_record(h, EXCHANGE, write_fields); }
+
+extern "C" int knpemi_flux_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  return series_read(h, h->flux.ser, h->flux.n_watch != 0, "knpemi_flux_read", FLUX.none, n_rows, out, rows, overflow, reset);
+}
+extern "C" int knpemi_exchange_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  return series_read(h, h->exchange.ser, h->exchange.n_watch != 0, "knpemi_exchange_read", EXCHANGE.none, n_rows, out, rows,
+                     overflow, reset);
+}
+
+extern "C" int knpemi_flux_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n) {
+  int w;
+  if (int rc = fields_watch(h, FLUX, sub, host, &w)) return rc;
+  if (part != 0 && part != 1) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_fields: part is 0 (diffusive) or 1 (drift)");
+  if (int rc = fields_ion(h, FLUX, w, ion)) return rc;
+  const size_t nc = (size_t)h->flux.host.count[w], gd = (size_t)h->gdim;
+  const size_t comp = 2 * (size_t)ions_below(h->flux.host.mask[w], ion) + part;      // {diffusive}, {drift} per ion
+  return fields_copy(h, FLUX, w, comp * gd * nc, host, n, nc * gd, "gdim * number of cells");
+}
+
+extern "C" int knpemi_exchange_fields(knpemi_handle* h, int sub, int ion, int part, double* host, size_t n) {
+  int w;
+  if (int rc = fields_watch(h, EXCHANGE, sub, host, &w)) return rc;
+  if (int rc = fields_ion(h, EXCHANGE, w, ion)) return rc;
+  if (part < 0 || part > (ion == -1 ? 1 : 2))
+    return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_fields: part is 0 (ECS side), 1 (cell side) or 2 (channel current) of an "
+                                  "ion, 0 (capacitive current) or 1 (area) with ion == -1");
+  const size_t nf = (size_t)h->exchange.host.count[w];
+  const size_t comp = 3 * (size_t)ions_below(h->exchange.host.mask[w], ion) + part;  // three components per ion
+  return fields_copy(h, EXCHANGE, w, comp * nf, host, n, nf, "the number of membrane facets of the cell");
+}
+
+extern "C" int knpemi_flux_reset(knpemi_handle* h) { return watched_reset(h, FLUX); }
+extern "C" int knpemi_exchange_reset(knpemi_handle* h) { return watched_reset(h, EXCHANGE); }
+extern "C" int knpemi_flux_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::flux); }
+extern "C" int knpemi_exchange_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::exchange); }

@@ -43,17 +43,9 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib as L
+from .recording import nodal_values as _values
 
 MAP_KEYS = ("count", "t_first", "t_last", "v_peak", "t_peak", "times")
-
-
-def _values(u):
-    """The nodal array of a `Function` (or the array itself)."""
-    x = getattr(u, "x", None)
-    if x is None:
-        return np.asarray(u, np.float64)
-    a = getattr(x, "_a", None)
-    return np.asarray(x.array if a is None else a, np.float64)
 
 
 def ring_to_times(ring, count):

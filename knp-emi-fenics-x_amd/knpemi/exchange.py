@@ -54,32 +54,22 @@ Cell-partitioned runs are not supported: a rank's sums would include its ghost f
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib as L
 from .fem.function import as_float
+from .recording import CURRENT_BIT, WatchedIons, lib_int, nodal_values as _values  # noqa: F401
 
-CURRENT_BIT = 0x100
 ION_PARTS = ("ecs", "ics", "channel")
 
 
-def _values(u, n=None):
-    """The nodal array of a `Function`, the array itself, or a constant spread over n values."""
-    x = getattr(u, "x", None)
-    if x is not None:
-        a = getattr(x, "_a", None)
-        return np.asarray(x.array if a is None else a, np.float64)
-    a = np.asarray(u, np.float64)
-    return np.full(n, float(a)) if a.ndim == 0 else a
-
-
 def chunk():
-    """Membrane facets per workgroup of the record kernel (kn_exchange_chunk)."""
-    fn = L.load().kn_exchange_chunk
-    fn.restype, fn.argtypes = C.c_int, []
-    return int(fn())
+    """Membrane facets per workgroup of the record kernel."""
+    return lib_int("kn_exchange_chunk")
+
+
+def fold_depth():
+    """Workgroup partials the record kernel's fold of a column has in flight."""
+    return lib_int("kn_exchange_fold_depth")
 
 
 def facet_rule(nf):
@@ -120,7 +110,9 @@ def facet_weights(X, w, dN):
     return w[None, :] * np.linalg.norm(np.cross(u, v), axis=2)
 
 
-class MembraneExchange:
+class MembraneExchange(WatchedIons):
+    _NAME, _WATCH, _SELF = "exchange", "cell", "this exchange is"
+
     def __init__(self, subdomain_list, ion_list, physical_params, ft=None):
         """subdomain_list: the problem's sub-domain dictionary (the ECS, tag 0, first; every cell carries "mesh_sub",
         "mesh_mem" and its "mem_models"); ion_list: the ions in the problem's order, the eliminated one last;
@@ -130,20 +122,13 @@ class MembraneExchange:
         self.tags = list(subdomain_list)
         if self.tags[0] != 0:
             raise ValueError("the first sub-domain must be the ECS with tag 0")
+        self._init_watched(ion_list)
         self.subdomain_list = subdomain_list
         self.cells = [t for t in self.tags[1:] if "mesh_mem" in subdomain_list[t]]
-        self.ion_list = ion_list
-        self.names = [ion["name"] for ion in ion_list]
-        self.K = len(ion_list)
-        self.z = [float(ion["z"]) for ion in ion_list]
         self.D = {t: [as_float(ion["D"][t]) for ion in ion_list] for t in self.tags}
         self.F, self.C_M = as_float(physical_params["F"]), as_float(physical_params["C_M"])
         self.ft = ft
-        self.watched = {}                 # tag -> (ion indices, current)
         self._geo = {}
-        self._t, self._rows = [], []
-        self._dev = None                  # (lib, handle, {tag: sub-domain index}) once attached
-        self._drain = None                # set by DeviceStepper.exchange: moves device rows into _t / _rows
         self._dt, self._every = None, 1   # step and record interval of the series (amounts, budget)
 
     # -- definition ------------------------------------------------------------------------------------
@@ -156,28 +141,11 @@ class MembraneExchange:
             raise ValueError(f"no sub-domain with tag {tag}")
         if tag not in self.cells:
             raise ValueError("the ECS (tag 0) has no membrane of its own: give the tag of a cell")
-        if tag in self.watched:
-            raise ValueError(f"cell {tag} is watched already")
-        if ions is None:
-            ions = range(self.K)
-        idx = sorted({self.names.index(i) if isinstance(i, str) else int(i) for i in ions})
-        if any(not 0 <= k < self.K for k in idx):
-            raise ValueError("ion index out of range")
-        if not idx and not current:
-            raise ValueError("nothing to watch: no ion and no current")
-        self.watched[tag] = (idx, bool(current))
-
-    def _check_watched(self, tag):
-        if tag not in self.watched:
-            raise ValueError(f"cell {tag} is not watched")
-
-    def mask(self, tag):
-        """Bits 0 .. K-1: the watched ions of `tag`, bit 8: the current columns (knpemi_exchange_set)."""
-        idx, cur = self.watched[tag]
-        return sum(1 << k for k in idx) | (CURRENT_BIT if cur else 0)
+        self._watch_ions(tag, ions, current)
 
     def columns(self):
-        """[(key, width)] of the series row in the device's order; every width is 1."""
+        """[(key, width)] of the series row in the device's order, every width 1: "<tag>/<ion>/ecs", "<tag>/<ion>/ics"
+        [mol/s], "<tag>/<ion>/channel" [A], "<tag>/capacitive", "<tag>/channel" [A] and "<tag>/area"."""
         out = []
         for tag, (idx, cur) in self.watched.items():
             for k in idx:
@@ -186,31 +154,8 @@ class MembraneExchange:
                 out += [(f"{tag}/capacitive", 1), (f"{tag}/channel", 1), (f"{tag}/area", 1)]
         return out
 
-    @property
-    def n_cols(self):
-        return len(self.columns())
-
     def n_facets(self, tag):
         return int(self.subdomain_list[tag]["mesh_mem"].cells.shape[0])
-
-    # -- the device table (knpemi_exchange_set) ------------------------------------------------------------
-    def _attach(self, dp, capacity):
-        if self._dev is not None:
-            raise RuntimeError("this exchange is attached to a device problem already")
-        if not self.watched:
-            raise ValueError("no cell is watched")
-        tags = list(self.watched)
-        sub = np.array([dp.sub_index[t] for t in tags], np.int32)
-        mask = np.array([self.mask(t) for t in tags], np.int32)
-        L.check(dp.lib.knpemi_exchange_set(dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity)))
-        self._dev = (dp.lib, dp.h, dict(dp.sub_index))
-
-    def _append_rows(self, times, rows):
-        self._t.extend(float(t) for t in times)
-        self._rows.extend(np.asarray(rows, np.float64).reshape(len(times), self.n_cols))
-
-    def clear(self):
-        self._t, self._rows = [], []
 
     # -- host restatement ----------------------------------------------------------------------------------
     def _geometry(self, tag):
@@ -301,10 +246,6 @@ class MembraneExchange:
             fields[tag] = out
         return fields, row
 
-    def row_vector(self, row):
-        """A row dictionary of `compute_host` as the flat row of the device buffer."""
-        return np.array([row[key] for key, _ in self.columns()], np.float64)
-
     def record_host(self, t, phi, c_prev, c_elim=None, phi_M_prev=None, I_ch=None, dt=None, splitting=True):
         """Append the row of `compute_host` to the series (host drivers): call it between the KNP assembly and the
         end-of-step update, with t the end of the step."""
@@ -313,34 +254,14 @@ class MembraneExchange:
         self._rows.append(self.row_vector(self.compute_host(phi, c_prev, c_elim, phi_M_prev, I_ch, dt, splitting)[1]))
 
     # -- output --------------------------------------------------------------------------------------------
-    def series(self):
-        """{"t": (n,), "<tag>/<ion>/ecs", "<tag>/<ion>/ics" [mol/s], "<tag>/<ion>/channel" [A], "<tag>/capacitive",
-        "<tag>/channel" [A], "<tag>/area": (n,) each}; drains the device buffer of an attached stepper (one
-        synchronisation)."""
-        if self._drain is not None:
-            self._drain()
-        rows = np.array(self._rows, np.float64).reshape(len(self._rows), self.n_cols)
-        out = {"t": np.array(self._t, np.float64)}
-        for j, (key, _) in enumerate(self.columns()):
-            out[key] = rows[:, j].copy()
-        return out
-
     def fields(self, tag):
         """Per-facet means of the last device record made with fields: "<ion>/ecs", "<ion>/ics", "<ion>/channel" for
         every watched ion, "capacitive" and "area" where the currents are watched, and "facet", the facet's index into
         the cell's `mesh_mem` (one synchronisation)."""
         self._check_watched(tag)
-        if self._dev is None:
-            raise RuntimeError("fields(): not attached to a device problem (DeviceStepper.exchange); compute_host "
-                               "evaluates host data")
-        lib, h, sub_index = self._dev
-        idx, cur = self.watched[tag]
         nf = self.n_facets(tag)
-
-        def get(ion, part):
-            buf = np.empty(nf, np.float64)
-            L.check(lib.knpemi_exchange_fields(h, sub_index[tag], ion, part, L.dptr(buf), buf.size))
-            return buf
+        get = self._getter(tag, nf, "DeviceStepper.exchange")
+        idx, cur = self.watched[tag]
         out = {}
         for k in idx:
             for p, name in enumerate(ION_PARTS):
@@ -411,7 +332,3 @@ class MembraneExchange:
             if set(cells) == set(self.cells) and self.mass_key(0, name) in obs_series:
                 out[f"0/{name}"] = rate(0, name) - sum(ser[f"{tag}/{name}/ecs"] for tag in cells)
         return out
-
-    def save(self, path):
-        """.npz of `series()`."""
-        np.savez(path, **self.series())

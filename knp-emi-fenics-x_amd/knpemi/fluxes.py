@@ -37,31 +37,22 @@ Cell-partitioned runs are not supported: a rank's sums would include its ghost c
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib as L
 from .fem.function import as_float
+from .recording import CURRENT_BIT, WatchedIons, lib_int, nodal_values as _values  # noqa: F401
 
-CURRENT_BIT = 0x100
 PARTS = ("diffusive", "drift")
 
 
-def _values(u):
-    """The nodal array of a `Function` (or the array itself)."""
-    x = getattr(u, "x", None)
-    if x is None:
-        return np.asarray(u, np.float64)
-    a = getattr(x, "_a", None)
-    return np.asarray(x.array if a is None else a, np.float64)
-
-
 def chunk():
-    """Cells per workgroup of the record kernel (kn_flux_chunk)."""
-    fn = L.load().kn_flux_chunk
-    fn.restype, fn.argtypes = C.c_int, []
-    return int(fn())
+    """Cells per workgroup of the record kernel."""
+    return lib_int("kn_flux_chunk")
+
+
+def fold_depth():
+    """Workgroup partials the record kernel's fold of a column has in flight."""
+    return lib_int("kn_flux_fold_depth")
 
 
 def cell_geometry(x, cells, cell_type):
@@ -97,25 +88,19 @@ def norm(J):
     return np.sqrt(n2)
 
 
-class IonFluxes:
+class IonFluxes(WatchedIons):
+    _NAME, _WATCH, _SELF = "flux", "sub-domain", "these fluxes are"
+
     def __init__(self, subdomain_list, ion_list, physical_params):
         """subdomain_list: the problem's sub-domain dictionary (every entry carries its "mesh_sub"); ion_list: the ions
         in the problem's order, the eliminated one last; physical_params: "F" and "psi" are read."""
+        self._init_watched(ion_list)
         self.tags = list(subdomain_list)
         self.mesh = {t: subdomain_list[t]["mesh_sub"] for t in self.tags}
-        self.ion_list = ion_list
-        self.names = [ion["name"] for ion in ion_list]
-        self.K = len(ion_list)
-        self.z = [float(ion["z"]) for ion in ion_list]
         self.D = {t: [as_float(ion["D"][t]) for ion in ion_list] for t in self.tags}
         self.F, self.psi = as_float(physical_params["F"]), as_float(physical_params["psi"])
         self.gdim = int(self.mesh[self.tags[0]].x.shape[1])
-        self.watched = {}                 # tag -> (ion indices, current)
         self._geo = {}
-        self._t, self._rows = [], []
-        self._dev = None                  # (lib, handle, {tag: sub-domain index}) once attached
-        self._drain = None                # set by DeviceStepper.fluxes: moves device rows into _t / _rows
-        self._with_fields = False
 
     # -- definition ------------------------------------------------------------------------------------
     def watch(self, tag, ions=None, current=True):
@@ -125,28 +110,11 @@ class IonFluxes:
             raise RuntimeError("fluxes are attached to a device problem: watch every sub-domain before fluxes()")
         if tag not in self.mesh:
             raise ValueError(f"no sub-domain with tag {tag}")
-        if tag in self.watched:
-            raise ValueError(f"sub-domain {tag} is watched already")
-        if ions is None:
-            ions = range(self.K)
-        idx = sorted({self.names.index(i) if isinstance(i, str) else int(i) for i in ions})
-        if any(not 0 <= k < self.K for k in idx):
-            raise ValueError("ion index out of range")
-        if not idx and not current:
-            raise ValueError("nothing to watch: no ion and no current")
-        self.watched[tag] = (idx, bool(current))
-
-    def _check_watched(self, tag):
-        if tag not in self.watched:
-            raise ValueError(f"sub-domain {tag} is not watched")
-
-    def mask(self, tag):
-        """Bits 0 .. K-1: the watched ions of `tag`, bit 8: the current (knpemi_flux_set)."""
-        idx, cur = self.watched[tag]
-        return sum(1 << k for k in idx) | (CURRENT_BIT if cur else 0)
+        self._watch_ions(tag, ions, current)
 
     def columns(self):
-        """[(key, width)] of the series row in the device's order."""
+        """[(key, width)] of the series row in the device's order: "<tag>/<ion>/diffusive" and "<tag>/<ion>/drift" (gdim
+        wide), "<tag>/<ion>/max", "<tag>/current" (gdim wide) and "<tag>/current_max"."""
         out, g = [], self.gdim
         for tag, (idx, cur) in self.watched.items():
             for k in idx:
@@ -156,31 +124,8 @@ class IonFluxes:
                 out += [(f"{tag}/current", g), (f"{tag}/current_max", 1)]
         return out
 
-    @property
-    def n_cols(self):
-        return sum(w for _, w in self.columns())
-
     def n_cells(self, tag):
         return int(self.mesh[tag].cells.shape[0])
-
-    # -- the device table (knpemi_flux_set) ----------------------------------------------------------------
-    def _attach(self, dp, capacity):
-        if self._dev is not None:
-            raise RuntimeError("these fluxes are attached to a device problem already")
-        if not self.watched:
-            raise ValueError("no sub-domain is watched")
-        tags = list(self.watched)
-        sub = np.array([dp.sub_index[t] for t in tags], np.int32)
-        mask = np.array([self.mask(t) for t in tags], np.int32)
-        L.check(dp.lib.knpemi_flux_set(dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity)))
-        self._dev = (dp.lib, dp.h, dict(dp.sub_index))
-
-    def _append_rows(self, times, rows):
-        self._t.extend(float(t) for t in times)
-        self._rows.extend(np.asarray(rows, np.float64).reshape(len(times), self.n_cols))
-
-    def clear(self):
-        self._t, self._rows = [], []
 
     # -- host restatement ----------------------------------------------------------------------------------
     def _geometry(self, tag):
@@ -231,55 +176,25 @@ class IonFluxes:
         """vol_T of every cell of sub-domain `tag`."""
         return self._geometry(tag)[3]
 
-    def row_vector(self, row):
-        """A row dictionary of `compute_host` as the flat row of the device buffer."""
-        return np.concatenate([np.atleast_1d(np.asarray(row[key], np.float64)) for key, _ in self.columns()])
-
     def record_host(self, t, phi, c, c_elim=None):
         """Append the row of `compute_host` to the series (host drivers)."""
         self._t.append(float(t))
         self._rows.append(self.row_vector(self.compute_host(phi, c, c_elim)[1]))
 
     # -- output --------------------------------------------------------------------------------------------
-    def series(self):
-        """{"t": (n,), "<tag>/<ion>/diffusive": (n, gdim), "<tag>/<ion>/drift": (n, gdim), "<tag>/<ion>/max": (n,),
-        "<tag>/current": (n, gdim), "<tag>/current_max": (n,)}; drains the device buffer of an attached stepper (one
-        synchronisation)."""
-        if self._drain is not None:
-            self._drain()
-        rows = np.array(self._rows, np.float64).reshape(len(self._rows), self.n_cols)
-        out, j = {"t": np.array(self._t, np.float64)}, 0
-        for key, w in self.columns():
-            out[key] = rows[:, j:j + w].copy() if w > 1 else rows[:, j].copy()
-            j += w
-        return out
-
     def fields(self, tag):
         """Per-cell arrays (n_cell, gdim) of the last device record made with fields: "<ion>/diffusive" and
         "<ion>/drift" for every watched ion, "current/diffusive", "current/drift" and their sum "current" where the
         current is watched (one synchronisation)."""
         self._check_watched(tag)
-        if self._dev is None:
-            raise RuntimeError("fields(): not attached to a device problem (DeviceStepper.fluxes); compute_host "
-                               "evaluates host data")
-        lib, h, sub_index = self._dev
+        get = self._getter(tag, (self.gdim, self.n_cells(tag)), "DeviceStepper.fluxes")
         idx, cur = self.watched[tag]
-        nc, g = self.n_cells(tag), self.gdim
-
-        def get(ion, part):
-            buf = np.empty((g, nc), np.float64)
-            L.check(lib.knpemi_flux_fields(h, sub_index[tag], ion, part, L.dptr(buf), buf.size))
-            return np.ascontiguousarray(buf.T)
         out = {}
         for k in idx:
             for p, name in enumerate(PARTS):
-                out[f"{self.names[k]}/{name}"] = get(k, p)
+                out[f"{self.names[k]}/{name}"] = np.ascontiguousarray(get(k, p).T)
         if cur:
             for p, name in enumerate(PARTS):
-                out[f"current/{name}"] = get(-1, p)
+                out[f"current/{name}"] = np.ascontiguousarray(get(-1, p).T)
             out["current"] = out["current/diffusive"] + out["current/drift"]
         return out
-
-    def save(self, path):
-        """.npz of `series()`."""
-        np.savez(path, **self.series())

@@ -38,6 +38,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .recording import RowSeries
 from .fem.probe import Locator, integral_weights, membrane_weights, point_weights
 
 OPS = ("integral", "nodal_mean", "average", "min", "max")
@@ -57,7 +58,7 @@ class _Obs:
         self.src = src
 
 
-class Observables:
+class Observables(RowSeries):
     def __init__(self, mesh, ct, ft, subdomain_list, ion_list, partitioned=False):
         """partitioned: the mesh is one rank's local mesh -- points are located at set-up (`partition`), where a
         point found on no rank raises on every rank."""
@@ -71,9 +72,7 @@ class Observables:
         self.sub_index = {t: s for s, t in enumerate(self.tags)}
         self.ion_names = [ion["name"] for ion in ion_list]
         self.items = []
-        self._t = []
-        self._rows = []
-        self._drain = None            # set by DeviceStepper.observe: moves device rows into _t / _rows
+        self._init_series()
         self._integral = {}
 
     # -- definition ------------------------------------------------------------------------------------
@@ -171,6 +170,10 @@ class Observables:
     @property
     def keys(self):
         return [o.key for o in self.items]
+
+    def columns(self):
+        """[(key, 1)] of the series row: one column per observable."""
+        return [(o.key, 1) for o in self.items]
 
     # -- the device table (knpemi_observe_set) ----------------------------------------------------------
     def table(self, sub_index=None):
@@ -370,27 +373,6 @@ class Observables:
         """Append the row of time t evaluated from host arrays (the host drivers' path)."""
         self._t.append(float(t))
         self._rows.append(self.evaluate_host(phi, c, phi_M_prev))
-
-    # -- output ------------------------------------------------------------------------------------------
-    def _append_rows(self, times, rows):
-        self._t.extend(float(t) for t in times)
-        self._rows.extend(np.asarray(rows, np.float64).reshape(len(times), len(self.items)))
-
-    def clear(self):
-        self._t, self._rows = [], []
-
-    def series(self):
-        """{"t": (n,), key: (n,) for every observable}; reads the device buffer of an attached stepper first."""
-        if self._drain is not None:
-            self._drain()
-        rows = np.array(self._rows, np.float64).reshape(len(self._rows), len(self.items))
-        out = {"t": np.array(self._t, np.float64)}
-        for j, key in enumerate(self.keys):
-            out[key] = rows[:, j].copy()
-        return out
-
-    def save(self, path):
-        np.savez(path, **self.series())
 
 
 def combine_partials(obs, rows_by_rank):

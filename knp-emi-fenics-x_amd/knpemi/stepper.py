@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .recording import Tap
 
 
 class DeviceStepper:
@@ -82,11 +83,10 @@ class DeviceStepper:
         self.dt = float(a.dt)
         self.flags_emi = L.WANT_P | (0 if a.splitting_scheme else L.NO_SPLITTING)
         self.flags_knp = 0 if a.splitting_scheme else L.NO_SPLITTING
-        self._obs = None           # attached Observables (observe)
+        # the attached recorders (knpemi.recording.Tap) by the method that attached them: "exchange" records behind the
+        # last KNP assembly of a step, "observe", "detect" and "fluxes", in this order, behind the end-of-step update
+        self.taps = {}
         self._obs_halo = None      # the halo of a partitioned observe
-        self._ev = None            # attached MembraneEvents (detect)
-        self._fl = None            # attached IonFluxes (fluxes)
-        self._ex = None            # attached MembraneExchange (exchange)
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -141,21 +141,8 @@ class DeviceStepper:
             self.add_membrane_model(m, stim, loc)
         self.k = 0
         self.ode_failures()            # clears the counters of the previous run
-        if self._obs is not None:      # a new series
-            L.check(self.lib.knpemi_observe_read(self.dp.h, 0, None, None, None, 1))
-            self._obs_pending = []
-            self._obs.clear()
-        if self._ev is not None:       # new maps
-            L.check(self.lib.knpemi_events_reset(self.dp.h))
-            self._ev.reset_host()
-        if self._fl is not None:       # a new series
-            L.check(self.lib.knpemi_flux_reset(self.dp.h))
-            self._fl_pending = []
-            self._fl.clear()
-        if self._ex is not None:       # a new series
-            L.check(self.lib.knpemi_exchange_reset(self.dp.h))
-            self._ex_pending = []
-            self._ex.clear()
+        for tap in self.taps.values():      # new series, new maps
+            tap.reset()
 
     # -- observables -------------------------------------------------------------------------------
     def observe(self, obs, every=1, capacity=1024, t0=0.0, halo=None):
@@ -179,22 +166,24 @@ class DeviceStepper:
             if halo.dp is not self.dp:
                 raise ValueError("observe(halo=...): attach the halo to this stepper's problem first (halo.attach)")
             self._obs_keep = obs.upload_partitioned(self.dp, capacity, halo, every)
-        self._obs, self._obs_every, self._obs_capacity, self._obs_t0 = obs, int(every), int(capacity), float(t0)
-        self._obs_pending = []
-        obs.clear()
-        obs._drain = self._observe_drain
 
-    def _observe_drain(self):
-        """Move the device rows into the host series; the device must hold exactly the rows enqueued."""
-        obs, n = self._obs, len(self._obs_pending)
-        buf = np.empty((max(n, 1), len(obs.items)), np.float64)
-        rows, over = C.c_int64(), C.c_int64()
-        L.check(self.lib.knpemi_observe_read(self.dp.h, n, L.dptr(buf), C.byref(rows), C.byref(over), 1))
-        if rows.value != n or over.value != 0:
-            raise RuntimeError(f"observables: the device holds {rows.value} row(s) (+{over.value} dropped), "
-                               f"the host enqueued {n}")
-        obs._append_rows(self._obs_pending, buf[:n])
-        self._obs_pending = []
+        def record(t, fields):
+            rc = self.lib.knpemi_observe_record(self.dp.h)
+            err = getattr(halo, "_hook_error", None)
+            if rc != L.OK and err is not None:      # the all-reduce of a partitioned record failed in Python
+                raise err
+            L.check(rc)
+        read = self._reader(self.lib.knpemi_observe_read)
+        self.taps["observe"] = Tap(obs, "observables", every, record, t0, capacity=capacity, read=read,
+                                   n_cols=obs.n_cols, rewind=lambda: read(0, None))
+
+    def _reader(self, fn):
+        """read(n, buf) -> (rows, dropped) of a tap, from the recorder's knpemi_*_read with reset."""
+        def read(n, buf):
+            rows, over = C.c_int64(), C.c_int64()
+            L.check(fn(self.dp.h, n, None if buf is None else L.dptr(buf), C.byref(rows), C.byref(over), 1))
+            return rows.value, over.value
+        return read
 
     # -- membrane events ---------------------------------------------------------------------------
     def detect(self, ev, every=1, t0=0.0):
@@ -205,11 +194,16 @@ class DeviceStepper:
         ones."""
         if every < 1:
             raise ValueError("every must be positive")
-        if self._ev is not None:
+        if "detect" in self.taps:
             raise RuntimeError("this stepper records membrane events already")
         ev._attach(self.lib, self.dp.h, self.dp.sub_index)
         ev.reset_host()
-        self._ev, self._ev_every, self._ev_t0 = ev, int(every), float(t0)
+
+        def rewind():
+            L.check(self.lib.knpemi_events_reset(self.dp.h))
+            ev.reset_host()
+        self.taps["detect"] = Tap(ev, "membrane events", every, rewind=rewind, t0=t0,
+                                  record=lambda t, fields: L.check(self.lib.knpemi_events_record(self.dp.h, t)))
 
     # -- ion fluxes ---------------------------------------------------------------------------------
     def fluxes(self, fl, every=1, capacity=1024, t0=0.0, fields=False):
@@ -222,28 +216,20 @@ class DeviceStepper:
         Partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost cells."""
         if every < 1 or capacity < 1:
             raise ValueError("every and capacity must be positive")
-        if self._fl is not None:
+        if "fluxes" in self.taps:
             raise RuntimeError("this stepper records ion fluxes already")
         if fl._drain is not None:
             raise RuntimeError("these fluxes are attached to a stepper already")
-        fl._attach(self.dp, capacity)
-        self._fl, self._fl_every, self._fl_capacity, self._fl_t0 = fl, int(every), int(capacity), float(t0)
-        self._fl_fields = 1 if fields else 0
-        self._fl_pending = []
-        fl.clear()
-        fl._drain = self._fluxes_drain
+        self._watched_tap("fluxes", "flux", fl, "ion fluxes", every, capacity, t0, fields)
 
-    def _fluxes_drain(self):
-        """Move the device rows into the host series; the device must hold exactly the rows enqueued."""
-        fl, n = self._fl, len(self._fl_pending)
-        buf = np.empty((max(n, 1), fl.n_cols), np.float64)
-        rows, over = C.c_int64(), C.c_int64()
-        L.check(self.lib.knpemi_flux_read(self.dp.h, n, L.dptr(buf), C.byref(rows), C.byref(over), 1))
-        if rows.value != n or over.value != 0:
-            raise RuntimeError(f"ion fluxes: the device holds {rows.value} row(s) (+{over.value} dropped), "
-                               f"the host enqueued {n}")
-        fl._append_rows(self._fl_pending, buf[:n])
-        self._fl_pending = []
+    def _watched_tap(self, name, kind, rec, label, every, capacity, t0, fields, offset=0):
+        """Attach the watches of `rec` (IonFluxes, MembraneExchange: knpemi_<kind>_*) and build their tap."""
+        lib, h = self.lib, self.dp.h
+        record, reset = getattr(lib, f"knpemi_{kind}_record"), getattr(lib, f"knpemi_{kind}_reset")
+        rec._attach(self.dp, capacity)
+        self.taps[name] = Tap(rec, label, every, lambda t, f: L.check(record(h, f)), t0, offset, capacity,
+                              self._reader(getattr(lib, f"knpemi_{kind}_read")), rec.n_cols, lambda: L.check(reset(h)),
+                              fields)
 
     # -- membrane ion exchange --------------------------------------------------------------------------
     def exchange(self, ex, every=1, capacity=1024, t0=0.0, fields=False):
@@ -259,29 +245,13 @@ class DeviceStepper:
         Partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost facets."""
         if every < 1 or capacity < 1:
             raise ValueError("every and capacity must be positive")
-        if self._ex is not None:
+        if "exchange" in self.taps:
             raise RuntimeError("this stepper records a membrane exchange already")
         if ex._drain is not None:
             raise RuntimeError("this exchange is attached to a stepper already")
-        ex._attach(self.dp, capacity)
-        self._ex, self._ex_every, self._ex_capacity, self._ex_t0 = ex, int(every), int(capacity), float(t0)
-        self._ex_fields = 1 if fields else 0
-        self._ex_pending = []
-        ex.clear()
+        # offset 1: the record sits inside step k, counted from 0, and carries the time of the step's end
+        self._watched_tap("exchange", "exchange", ex, "membrane exchange", every, capacity, t0, fields, offset=1)
         ex._dt, ex._every = self.dt, int(every)
-        ex._drain = self._exchange_drain
-
-    def _exchange_drain(self):
-        """Move the device rows into the host series; the device must hold exactly the rows enqueued."""
-        ex, n = self._ex, len(self._ex_pending)
-        buf = np.empty((max(n, 1), ex.n_cols), np.float64)
-        rows, over = C.c_int64(), C.c_int64()
-        L.check(self.lib.knpemi_exchange_read(self.dp.h, n, L.dptr(buf), C.byref(rows), C.byref(over), 1))
-        if rows.value != n or over.value != 0:
-            raise RuntimeError(f"membrane exchange: the device holds {rows.value} row(s) (+{over.value} dropped), "
-                               f"the host enqueued {n}")
-        ex._append_rows(self._ex_pending, buf[:n])
-        self._ex_pending = []
 
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
@@ -320,13 +290,13 @@ class DeviceStepper:
     # -- one time step, everything enqueued on the handle's stream ---------------------------
     def step(self, halo=None):
         dp, lib = self.dp, self.lib
-        if halo is not None and self._obs is not None and halo is not self._obs_halo:
+        if halo is not None and "observe" in self.taps and halo is not self._obs_halo:
             raise NotImplementedError("observables attached without a halo are not recorded on partitioned steps: "
                                       "pass halo= to DeviceStepper.observe")
-        if halo is not None and self._fl is not None:
+        if halo is not None and "fluxes" in self.taps:
             raise NotImplementedError("ion fluxes are not recorded on partitioned steps: a rank's sums would include "
                                       "its ghost cells")
-        if halo is not None and self._ex is not None:
+        if halo is not None and "exchange" in self.taps:
             raise NotImplementedError("the membrane exchange is not recorded on partitioned steps: a rank's sums would "
                                       "include its ghost facets")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
@@ -397,12 +367,9 @@ class DeviceStepper:
         L.check(lib.knpemi_assemble_knp(dp.h, knp_flags))
         if self.assemble_knp_twice:   # the reference assembles p = a a second time (knpWeakForm.py:319)
             L.check(lib.knpemi_assemble_knp(dp.h, knp_flags))
-        if self._ex is not None and (self.k + 1) % self._ex_every == 0:
+        if "exchange" in self.taps:
             # behind the assembly, before the solve: the fields the membrane part of b_knp has just been formed from
-            L.check(lib.knpemi_exchange_record(dp.h, self._ex_fields))
-            self._ex_pending.append(self._ex_t0 + (self.k + 1) * self.dt)
-            if len(self._ex_pending) == self._ex_capacity:
-                self._exchange_drain()
+            self.taps["exchange"].tick(self.k, self.dt)
         if self.solve_knp is not None:
             self.solve_knp(dp)
         if not (self.fuse_update and self.solve_knp is not None):
@@ -410,26 +377,12 @@ class DeviceStepper:
         if halo is not None:
             halo.exchange_bulk()
         self.k += 1
-        if self._obs is not None and self.k % self._obs_every == 0:
-            # on the main stream behind the end-of-step update (update_pde_kernel or the fused KNP write-back); the next
-            # step's side-stream launches fork from the main stream after it (ev_fork), so none of them overtakes it
-            rc = lib.knpemi_observe_record(dp.h)
-            err = getattr(self._obs_halo, "_hook_error", None)
-            if rc != L.OK and err is not None:      # the all-reduce of a partitioned record failed in Python
-                raise err
-            L.check(rc)
-            self._obs_pending.append(self._obs_t0 + self.k * self.dt)
-            if len(self._obs_pending) == self._obs_capacity:
-                self._observe_drain()
-        if self._ev is not None and self.k % self._ev_every == 0:
-            # one more launch on the main stream, behind the end-of-step update for the same reason as the observables'
-            L.check(lib.knpemi_events_record(dp.h, self._ev_t0 + self.k * self.dt))
-        if self._fl is not None and self.k % self._fl_every == 0:
-            # and one over the cells of the watched sub-domains, behind the same update
-            L.check(lib.knpemi_flux_record(dp.h, self._fl_fields))
-            self._fl_pending.append(self._fl_t0 + self.k * self.dt)
-            if len(self._fl_pending) == self._fl_capacity:
-                self._fluxes_drain()
+        # On the main stream behind the end-of-step update (update_pde_kernel or the fused KNP write-back); the next
+        # step's side-stream launches fork from the main stream after it (ev_fork), so none of them overtakes these: the
+        # observables' launch, the events' over the membrane dofs, the fluxes' over the cells of the watched sub-domains.
+        for name in ("observe", "detect", "fluxes"):
+            if name in self.taps:
+                self.taps[name].tick(self.k, self.dt)
 
     def ode_failures(self):
         n = 0

@@ -18,8 +18,9 @@ from knpemi import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-# the shared set-ups and "small": the unit square with a 4 x 4 cell of 16 membrane facets, a single workgroup
-SETUPS = xc.SETUPS + ("small",)
+# the shared set-ups, "small": the unit square with a 4 x 4 cell of 16 membrane facets, a single workgroup, and "2d_r3":
+# the 2-D set-up at r = 3, whose 496 facets fill exactly as many workgroups as the fold of the partials has loads in flight
+SETUPS = xc.SETUPS + ("small", "2d_r3")
 BUDGET_FLOOR = 5.7e-11      # 10 x the CPU floor measured in test_exchange_host.test_mass_budget_of_one_step
 
 
@@ -29,6 +30,8 @@ def _stepper(s, **kw):
 
 
 def _build(name):
+    if name == "2d_r3":
+        return xc.build("2d", r=3)
     if name != "small":
         return xc.build(name)
     from knpemi.fem import make_mesh_mms
@@ -86,14 +89,22 @@ def test_fields_and_row_match_the_restatement(hip_lib, name, splitting):
 def test_setups_cover_the_workgroup_cases(hip_lib):
     """From the facet counts and the kernel's facets per workgroup: one watched cell spans several workgroups, one fits
     in a single workgroup, and one leaves its last workgroup partly filled (whole KN_MEM_LQ-lane groups that repeat the
-    last (facet, side) and contribute nothing)."""
-    chunk = exchange.chunk()
-    counts = []
-    for name in ("2d", "tet", "small"):
+    last (facet, side) and contribute nothing).  From the workgroup counts and the depth of the fold of the partials
+    (exchange.fold_depth() loads in flight, then one by one): one watch has exactly `depth` workgroups, one fewer, and
+    one more than `depth` with a remainder."""
+    chunk, depth = exchange.chunk(), exchange.fold_depth()
+    counts = {}
+    for name in ("2d", "2d_r3", "tet", "hex", "small"):
         s, ex, _ = _recorded(name)
-        counts += [ex.n_facets(t) for t in ex.watched]
-    assert any(n > 2 * chunk for n in counts) and any(n <= chunk for n in counts)
-    assert any(n > chunk and n % chunk for n in counts) and any(n < chunk for n in counts)
+        counts[name] = [ex.n_facets(t) for t in ex.watched]
+    flat = [n for c in counts.values() for n in c]
+    assert any(n > 2 * chunk for n in flat) and any(n <= chunk for n in flat)
+    assert any(n > chunk and n % chunk for n in flat) and any(n < chunk for n in flat)
+    groups = [-(-n // chunk) for n in flat]
+    print("facets", counts, "workgroups", groups, "depth", depth)
+    assert any(g == depth for g in groups) and any(g < depth for g in groups)
+    assert any(g > depth and g % depth for g in groups)
+    assert counts["2d_r3"] == [496] and counts["tet"] == [1472] and counts["hex"] == [736]
 
 
 def _ion_count_problem(K):

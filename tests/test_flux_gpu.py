@@ -17,7 +17,9 @@ from knpemi import _lib as L
 
 pytestmark = pytest.mark.gpu
 
-SETUPS = ("2d", "tet", "hex", "three", "jittered", "fan3d")
+# "2d_r3" and "mms44": the sizes at which the fold of the workgroup partials takes another path (see
+# test_setups_cover_the_workgroup_cases)
+SETUPS = ("2d", "2d_r3", "mms44", "tet", "hex", "three", "jittered", "fan3d")
 
 
 def _stepper(s, **kw):
@@ -35,6 +37,11 @@ def _build(name):
         if name in ("jittered", "fan3d"):
             data = um.jittered_tet_box() if name == "jittered" else um.fan_mesh(3)
             s = Setup("tet", 0, mesh_data=data)
+        elif name == "2d_r3":
+            s = Setup("2d", 3)
+        elif name == "mms44":
+            from knpemi.fem import make_mesh_mms
+            s = Setup("2d", 1, mesh_data=make_mesh_mms(44))
         else:
             s = Setup(name, {"2d": 1, "tet": 0, "hex": 0}[name])
         s.perturb()
@@ -109,14 +116,25 @@ def test_fields_and_row_match_the_restatement(hip_lib, name):
 
 def test_setups_cover_the_workgroup_cases(hip_lib):
     """From the cell counts and the kernel's cells per workgroup: one watched sub-domain spans several workgroups, one
-    fits in a single workgroup, one has a partial last wave."""
-    chunk = fluxes.chunk()
+    fits in a single workgroup, one has a partial last wave.  From the workgroup counts and the depth of the fold of the
+    partials (fluxes.fold_depth() loads in flight, then one by one): one watch has exactly `depth` workgroups, one
+    fewer, and one more than `depth` with a remainder."""
+    chunk, depth = fluxes.chunk(), fluxes.fold_depth()
     counts = []
-    for name in ("2d", "tet"):
+    for name in ("2d", "2d_r3", "mms44", "tet"):
         s, _, fl, _, _ = _recorded(name)
         counts += [fl.n_cells(t) for t in s.subdomain_list]
     assert any(n > 2 * chunk for n in counts) and any(n <= chunk for n in counts) and any(n % 64 for n in counts)
     assert any(n > chunk and n % chunk for n in counts)
+    groups = [-(-n // chunk) for n in counts]
+    print("cells", counts, "workgroups", groups, "depth", depth)
+    assert any(g == depth for g in groups) and any(g < depth for g in groups)
+    assert any(g > depth and g % depth for g in groups)
+    # the counts of the set-ups themselves
+    s, _, fl, _, _ = _recorded("2d_r3")
+    assert [-(-fl.n_cells(t) // chunk) for t in s.subdomain_list] == [4096 // 256, 3840 // 256]
+    s, _, fl, _, _ = _recorded("tet")
+    assert [-(-fl.n_cells(t) // chunk) for t in s.subdomain_list] == [-(-13440 // 256), -(-2112 // 256)]
 
 
 def _ion_count_problem(K):

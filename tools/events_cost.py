@@ -65,13 +65,13 @@ def main():
     st.observe(obs, every=1, capacity=4096)
     leg()
     fired = int(ev.fired(1).sum())
-    attached = dict(plain=(None, None), events=(ev, None), events_observed=(ev, obs))
+    attached = dict(plain=(False, False), events=(True, False), events_observed=(True, True))
     ms = {k: [] for k in attached}
     for _ in range(args.repeats):
-        for name, (e, o) in attached.items():       # detach what the leg does not record (the tables stay on the device)
-            st._ev, st._obs = e, o
+        for name, (e, o) in attached.items():       # switch off what the leg does not record (the tables stay on the device)
+            st.taps["detect"].enabled, st.taps["observe"].enabled = e, o
             ms[name].append(leg())
-    st._ev, st._obs = ev, obs
+    st.taps["detect"].enabled = st.taps["observe"].enabled = True
     med = {k: float(np.median(v)) for k, v in ms.items()}
     print(json.dumps(dict(workload="config2", steps=args.steps, windows=args.repeats, membrane_dofs=int(ev.n_q[1]),
                           fired_dofs=fired, observables=len(obs.items),

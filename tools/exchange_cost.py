@@ -76,17 +76,17 @@ def main():
     # allocation of the field buffers
     leg()
     st.exchange(ex, every=1, capacity=4096)
-    modes = dict(plain=None, series=0, fields=1)
-    for m in (0, 1):
-        st._ex_fields = m
+    tap = st.taps["exchange"]
+    modes = dict(plain=None, series=False, fields=True)
+    for m in (False, True):
+        tap.fields = m
         leg()
     ms = {k: [] for k in modes}
     for _ in range(args.repeats):
-        for name, m in modes.items():       # detach for the plain leg (the table stays on the device)
-            st._ex = None if m is None else ex
-            st._ex_fields = m or 0
+        for name, m in modes.items():       # switched off for the plain leg (the table stays on the device)
+            tap.enabled, tap.fields = m is not None, bool(m)
             ms[name].append(leg())
-    st._ex = ex
+    tap.enabled = True
     med = {k: float(np.median(v)) for k, v in ms.items()}
     out = dict(workload=args.workload, steps=args.steps, windows=args.repeats, facets=ex.n_facets(1), columns=ex.n_cols,
                ms_per_step_plain=med["plain"], ms_per_step_series=med["series"], ms_per_step_fields=med["fields"],

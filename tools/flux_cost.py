@@ -79,17 +79,17 @@ def main():
     # allocation of the field buffers
     leg()
     st.fluxes(fl, every=1, capacity=4096)
-    modes = dict(plain=None, series=0, fields=1)
-    for m in (0, 1):
-        st._fl_fields = m
+    tap = st.taps["fluxes"]
+    modes = dict(plain=None, series=False, fields=True)
+    for m in (False, True):
+        tap.fields = m
         leg()
     ms = {k: [] for k in modes}
     for _ in range(args.repeats):
-        for name, m in modes.items():       # detach for the plain leg (the table stays on the device)
-            st._fl = None if m is None else fl
-            st._fl_fields = m or 0
+        for name, m in modes.items():       # switched off for the plain leg (the table stays on the device)
+            tap.enabled, tap.fields = m is not None, bool(m)
             ms[name].append(leg())
-    st._fl = fl
+    tap.enabled = True
     med = {k: float(np.median(v)) for k, v in ms.items()}
     n_cells = sum(fl.n_cells(t) for t in fl.watched)
     nv, g = 4, 3

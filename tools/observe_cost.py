@@ -65,9 +65,9 @@ def main():
     leg(True)
     plain, observed = [], []
     for _ in range(args.repeats):
-        st._obs, saved = None, st._obs          # detach for the plain leg (the table stays on the device)
+        st.taps["observe"].enabled = False      # off for the plain leg (the table stays on the device)
         plain.append(leg(False))
-        st._obs = saved
+        st.taps["observe"].enabled = True
         observed.append(leg(True))
     n_e = sum(o.ids.shape[0] for o in obs.items)
     print(json.dumps(dict(workload="config2", steps=args.steps, observables=len(obs.items), entries=int(n_e),
