@@ -375,7 +375,7 @@ int knpemi_observe_clear(knpemi_handle* h);
  *   2. the sum of the first world * n_obs doubles of xbuf over the ranks: allreduce(ctx, world * n_obs) when given,
  *      else knpemi_comm_allreduce on the handle's communicator (knpemi_comm_init; required then).  Every slot has one
  *      non-zero contributor, so the sum is an exact all-gather;
- *   3. observe_combine_kernel: the slots folded in rank order, sums divided by denom, the row appended as above, the
+ *   3. record_combine_kernel: the slots folded in rank order, sums divided by denom, the row appended as above, the
  *      other ranks' slots zeroed for the next record.
  * Every rank appends the same row; knpemi_observe_read stays rank-local.  Points, minima and maxima equal those of one
  * rank holding the whole mesh bit for bit; sums agree to rounding (a different order of summation). */
@@ -470,6 +470,26 @@ int knpemi_flux_reset(knpemi_handle* h);
 /* Drop the table and the buffers (knpemi_flux_record then fails with KNPEMI_EINVAL; the quantities of
  * run_mms.py:270-301 are no longer evaluated); knpemi_destroy does the same. */
 int knpemi_flux_clear(knpemi_handle* h);
+/* knpemi_flux_set on one rank of a cell-partitioned run (knpemi.fluxes, DeviceStepper.fluxes(halo=...); the integrand is
+ * that of run_mms.py:270-301).  Every rank passes the same watches and capacity.  recorded: one byte per local cell, the
+ * cells of sub[0] first, then those of sub[1], ...: 1 = this rank records the cell (every cell of the global mesh is
+ * recorded by exactly one rank; the others hold it in their ghost layer, with valid records after the bulk halo).  A
+ * watched sub-domain may have no local cell.  rank, world, xbuf_dev (world * n_cols doubles, zeroed here), allreduce and
+ * ctx as in knpemi_observe_set_partitioned.  knpemi_flux_record then enqueues on the main stream
+ *   1. the record launch: the per-cell vectors of EVERY local cell with write_fields, and this rank's sums and maxima
+ *      over its recorded cells, folded in workgroup order, into xbuf[rank * n_cols + q] (zeros without local cells);
+ *   2. the sum of xbuf over the ranks: allreduce(ctx, world * n_cols) when given, else knpemi_comm_allreduce on the
+ *      handle's communicator (required then).  Every slot has one non-zero contributor: an exact all-gather;
+ *   3. record_combine_kernel: the slots of every column folded in rank order -- sums summed, maxima maximised from 0 --
+ *      the row appended or counted as dropped, the other ranks' slots zeroed for the next record.
+ * Every rank appends the same row, and repeated runs the same bits.  Maxima equal those of one rank holding the whole
+ * mesh bit for bit; sums agree to rounding (a different order of summation).  knpemi_flux_read, _fields (the local
+ * cells), _reset and _clear are unchanged.  KNPEMI_EINVAL as knpemi_flux_set, and for a NULL mask or buffer, a bad rank
+ * or world, and no hook with no communicator; a refused call leaves the previous table alone. */
+int
+knpemi_flux_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity,
+                            const uint8_t* recorded, int rank, int world, void* xbuf_dev,
+                            int (*allreduce)(void* ctx, int n), void* ctx);
 
 /* Membrane ion exchange per cell (knpemi.exchange): what crosses the membranes.  The membrane term of the reference's KNP
  * right-hand side (knpWeakForm.py:168-214) is minus the transmembrane molar flux of each ion, tested against the facet
@@ -515,6 +535,20 @@ int knpemi_exchange_reset(knpemi_handle* h);
 /* Drop the table and the buffers (knpemi_exchange_record then fails with KNPEMI_EINVAL; the fluxes of
  * knpWeakForm.py:168-214 are no longer kept); knpemi_destroy does the same. */
 int knpemi_exchange_clear(knpemi_handle* h);
+/* knpemi_exchange_set on one rank of a cell-partitioned run (knpemi.exchange, DeviceStepper.exchange(halo=...); the
+ * integrand is that of knpWeakForm.py:168-214).  Every rank passes the same watches and capacity.  recorded: one byte per
+ * local membrane facet, the facets of sub[0] first, then those of sub[1], ...: 1 = this rank records the facet (every
+ * facet of the global membrane is recorded by exactly one rank; the ghost layer's facets have valid inputs after the bulk
+ * halo and their membrane dofs are integrated redundantly).  A watched cell may have no local facet.  The other arguments
+ * and the three stages of knpemi_exchange_record -- record launch into xbuf[rank * n_cols + q] with the per-facet means
+ * of EVERY local facet, sum over the ranks, record_combine_kernel -- are those of knpemi_flux_set_partitioned; every
+ * column is a sum.  Every rank appends the same row; knpemi_exchange_read, _fields (the local facets), _reset and _clear
+ * are unchanged.  KNPEMI_EINVAL as knpemi_exchange_set, and for a NULL mask or buffer, a bad rank or world, and no hook
+ * with no communicator; a refused call leaves the previous table alone. */
+int
+knpemi_exchange_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity,
+                                const uint8_t* recorded, int rank, int world, void* xbuf_dev,
+                                int (*allreduce)(void* ctx, int n), void* ctx);
 
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop

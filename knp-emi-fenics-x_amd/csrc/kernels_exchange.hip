@@ -31,6 +31,14 @@
 // and the tail of record_tail.h: the last workgroup to arrive folds the partials of every column in workgroup order and
 // appends the row, or counts it as dropped when the buffer is full.  The row does not depend on write_fields.
 //
+// Partitioned runs (knpemi_exchange_set_partitioned; PART): a rank's facets include those of its ghost layer, whose inputs
+// are valid after the bulk halo and whose membrane dofs are integrated redundantly.  One byte per facet says whether
+// this rank records it: a facet that is not recorded gets its means written like any other and enters no sum.  The
+// KN_MEM_LQ lanes of a (facet, side) read the same byte, neighbouring groups neighbouring bytes.  The last workgroup
+// writes the folded columns into this rank's slots of the exchange buffer and leaves the row counters alone: the caller
+// sums the buffer over the ranks and record_combine_kernel (kernels_observe.hip) appends the row.  PART is a template
+// flag: the single-rank instantiations are the code they were without it.
+//
 // The membrane is a 2-D set: a launch is a few dozen workgroups that wait for their gathers, like knp_membrane_kernel.
 #include "knpemi_internal.h"
 #include "membrane_facet.h"
@@ -51,9 +59,11 @@ struct ExArgs {
   unsigned long long* ctl;
   double* rows;
   double* fld;
+  const uint8_t* recorded;   // PART: [facets of every watch] 1 = this rank records the facet
+  double* slot;              // PART: this rank's n_cols slots of the exchange buffer
 };
 
-template <int NF, bool FIELDS>
+template <int NF, bool FIELDS, bool PART>
 __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnConsts* __restrict__ Cp, ExArgs A) {
   __shared__ double qt[EX_QTAB];
   __shared__ double sh[EX_WAVES][KN_EX_SLOTS];
@@ -123,6 +133,10 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
   // one lane per (facet, side) carries the integrals on; the cell side also carries what both sides share
   const bool lead = live && lq == 0;
   const bool lead_i = lead && cell_side, lead_e = lead && !cell_side;
+  // sum_i / sum_e: the lanes whose integrals enter the sums
+  bool rec = true;
+  if constexpr (PART) rec = A.recorded[(size_t)T.ibase[w] + fl] != 0;
+  const bool sum_i = lead_i && rec, sum_e = lead_e && rec;
   const double inv_area = area > 0.0 ? 1.0 / area : 0.0;
   double* __restrict__ fld = FIELDS ? A.fld + T.fbase[w] + fl : nullptr;      // this facet's place in component 0
   auto put = [&](bool who, int comp, double v) {
@@ -136,15 +150,15 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
     put(lead_i, comp + 1, aj[k] * inv_area);
     put(lead_i, comp + 2, ai[k] * inv_area);
     comp += 3;
-    const double se = kn_wave_sum(lead_e ? aj[k] : 0.0), si = kn_wave_sum(lead_i ? aj[k] : 0.0);
-    const double sc = kn_wave_sum(lead_i ? ai[k] : 0.0);
+    const double se = kn_wave_sum(sum_e ? aj[k] : 0.0), si = kn_wave_sum(sum_i ? aj[k] : 0.0);
+    const double sc = kn_wave_sum(sum_i ? ai[k] : 0.0);
     if (lane == 0) { sh[wave][3 * k] = se; sh[wave][3 * k + 1] = si; sh[wave][3 * k + 2] = sc; }
   }
   if (cur) {
     put(lead_i, comp, acap * inv_area);
     put(lead_i, comp + 1, area);
-    const double sc = kn_wave_sum(lead_i ? acap : 0.0), st = kn_wave_sum(lead_i ? atot : 0.0);
-    const double sa = kn_wave_sum(lead_i ? area : 0.0);
+    const double sc = kn_wave_sum(sum_i ? acap : 0.0), st = kn_wave_sum(sum_i ? atot : 0.0);
+    const double sa = kn_wave_sum(sum_i ? area : 0.0);
     if (lane == 0) { sh[wave][3 * KN_MAXK] = sc; sh[wave][3 * KN_MAXK + 1] = st; sh[wave][3 * KN_MAXK + 2] = sa; }
   }
   __syncthreads();
@@ -158,13 +172,18 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
     kn_part_store(&A.part[(size_t)blockIdx.x * KN_EX_SLOTS + j], v);
   }
   if (!kn_arrive_last(A.ctl, threadIdx.x < KN_EX_SLOTS, &last)) return;
+  auto fold = [&](int q) {
+    const int cw = T.col_watch[q];      // every column is a sum: col_max is all zero here
+    return kn_fold_column<KN_EX_SLOTS, EX_FOLD_DEPTH>(A.part, T.col_slot[q], T.bstart[cw], T.bstart[cw + 1], false);
+  };
+  if constexpr (PART) {      // this rank's slots; a watch without local facets folds nothing: 0
+    for (int q = threadIdx.x; q < T.n_cols; q += EX_THREADS) A.slot[q] = fold(q);
+    if (threadIdx.x == 0) kn_reset_ticket(A.ctl);
+    return;
+  }
   const bool room = kn_claim_row(A.ctl, A.capacity, &row);
   if (room) {
-    for (int q = threadIdx.x; q < T.n_cols; q += EX_THREADS) {
-      const int cw = T.col_watch[q];      // every column is a sum: col_max is all zero here
-      A.rows[(size_t)row * T.n_cols + q] =
-          kn_fold_column<KN_EX_SLOTS, EX_FOLD_DEPTH>(A.part, T.col_slot[q], T.bstart[cw], T.bstart[cw + 1], false);
-    }
+    for (int q = threadIdx.x; q < T.n_cols; q += EX_THREADS) A.rows[(size_t)row * T.n_cols + q] = fold(q);
   }
   if (threadIdx.x == 0) {
     kn_commit_row(A.ctl, row, room);
@@ -172,21 +191,27 @@ __global__ __launch_bounds__(EX_THREADS) void exchange_kernel(KnDev D, const KnC
   }
 }
 
+template <int NF, bool PART>
+void launch_as(knpemi_handle* h, const ExArgs& a, int n_blk, bool fields) {
+  if (fields) hipLaunchKernelGGL((exchange_kernel<NF, true, PART>), dim3(n_blk), dim3(EX_THREADS), 0, h->stream, h->dev, h->d_consts, a);
+  else hipLaunchKernelGGL((exchange_kernel<NF, false, PART>), dim3(n_blk), dim3(EX_THREADS), 0, h->stream, h->dev, h->d_consts, a);
+}
 template <int NF>
 void launch(knpemi_handle* h, const ExArgs& a, int n_blk, bool fields) {
-  if (fields) hipLaunchKernelGGL((exchange_kernel<NF, true>), dim3(n_blk), dim3(EX_THREADS), 0, h->stream, h->dev, h->d_consts, a);
-  else hipLaunchKernelGGL((exchange_kernel<NF, false>), dim3(n_blk), dim3(EX_THREADS), 0, h->stream, h->dev, h->d_consts, a);
+  if (a.slot) launch_as<NF, true>(h, a, n_blk, fields);
+  else launch_as<NF, false>(h, a, n_blk, fields);
 }
 
 }  // namespace
 
 int kn_launch_exchange(knpemi_handle* h, int write_fields) {
   const auto& X = h->exchange;
-  if (X.n_blk == 0) return KNPEMI_OK;
+  if (X.n_blk == 0) return KNPEMI_OK;      // partitioned, no local facet: this rank's slots stay the zeros of the set-up
   if (h->dev.nq_gamma * (1 + h->NF + (h->NF == 4 ? 2 * h->NF : 0)) > EX_QTAB)
     return kn_fail(KNPEMI_EINVAL, "exchange_kernel: the facet quadrature table does not fit its LDS copy (EX_QTAB)");
   const int split = (h->knp_flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
-  const ExArgs a{h->K, X.ser.capacity, split, X.tab, X.part, X.ser.ctl, X.ser.rows, write_fields ? X.fld : nullptr};
+  const ExArgs a{h->K, X.ser.capacity, split, X.tab, X.part, X.ser.ctl, X.ser.rows, write_fields ? X.fld : nullptr,
+                 X.recorded, X.xbuf ? X.xbuf + (size_t)X.rank * X.ser.n_cols : nullptr};
   const bool fields = write_fields != 0;
   if (h->NF == 2) launch<2>(h, a, X.n_blk, fields);
   else if (h->NF == 3) launch<3>(h, a, X.n_blk, fields);

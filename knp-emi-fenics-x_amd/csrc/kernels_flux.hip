@@ -32,6 +32,14 @@
 // the workgroup (xor butterfly over the 64 lanes of a wave, then the four waves in order), one partial of KN_FLUX_SLOTS
 // doubles per workgroup, and the tail of record_tail.h: the last workgroup to arrive folds the partials of every
 // column in workgroup order and appends the row, or counts it as dropped when the buffer is full.
+//
+// Partitioned runs (knpemi_flux_set_partitioned; PART): a rank's cells include its ghost layer, whose records are valid
+// after the bulk halo.  One byte per cell says whether this rank records it: a cell that is not recorded gets its fields
+// written like any other and enters no sum (vol = 0, as a lane past the last cell) and no maximum.  The byte of lane t
+// sits next to that of lane t + 1, a coalesced load beside the cell's vertex ids.  The last workgroup writes the folded
+// columns into this rank's slots of the exchange buffer and leaves the row counters alone: the caller sums the buffer
+// over the ranks and record_combine_kernel (kernels_observe.hip) appends the row.  PART is a template flag: the
+// single-rank instantiations are the code they were without it.
 #include <cmath>
 
 #include "knpemi_internal.h"
@@ -56,6 +64,8 @@ struct FluxArgs {
   unsigned long long* ctl;
   double* rows;
   double* fld;
+  const uint8_t* recorded;   // PART: [cells of every watch] 1 = this rank records the cell
+  double* slot;              // PART: this rank's n_cols slots of the exchange buffer
 };
 
 template <int KIND> struct FluxCell {
@@ -130,7 +140,7 @@ __device__ inline void gather_cell(const int* __restrict__ cells, const double* 
   }
 }
 
-template <int KIND, bool FIELDS>
+template <int KIND, bool FIELDS, bool PART>
 __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
   constexpr int GD = FluxCell<KIND>::GD, NV = FluxCell<KIND>::NV;
   constexpr int PER_ION = 2 * GD + 1;
@@ -145,6 +155,9 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
   const bool cur = (mask & KN_WATCH_CURRENT) != 0;
   const int lc = ((int)blockIdx.x - T.bstart[w]) * FLUX_THREADS + (int)threadIdx.x;
   const bool valid = lc < nc;
+  // rec: the cell enters the sums and the maxima
+  bool rec = valid;
+  if constexpr (PART) rec = valid && A.recorded[(size_t)T.ibase[w] + lc] != 0;
   // a lane past the sub-domain's last cell repeats that cell (it takes part in the wave reductions) and contributes
   // nothing
   const size_t cell = (size_t)T.first[w] + (size_t)(valid ? lc : nc - 1);
@@ -170,7 +183,7 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
     det = E[0][0] * cof[0][0] + E[0][1] * cof[0][1] + E[0][2] * cof[0][2];
   }
   const double inv_det = 1.0 / det;
-  const double vol = valid ? fabs(det) * (NV == 8 ? 1.0 : NV == 4 ? 1.0 / 6.0 : 0.5) : 0.0;
+  const double vol = rec ? fabs(det) * (NV == 8 ? 1.0 : NV == 4 ? 1.0 / 6.0 : 0.5) : 0.0;
   auto grad = [&](int f, double (&g)[GD]) {
 #pragma unroll
     for (int a = 0; a < GD; ++a) {
@@ -216,7 +229,7 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
       if (lane == 0) { sh[wave][k * PER_ION + a] = sd; sh[wave][k * PER_ION + GD + a] = sr; }
     }
     comp += 2 * GD;
-    const double mx = kn_wave_max(valid ? sqrt(n2) : 0.0);
+    const double mx = kn_wave_max(rec ? sqrt(n2) : 0.0);
     if (lane == 0) sh[wave][k * PER_ION + 2 * GD] = mx;
   }
   if (cur) {
@@ -230,7 +243,7 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
       const double si = kn_wave_sum(vol * i);
       if (lane == 0) sh[wave][KN_MAXK * PER_ION + a] = si;
     }
-    const double mx = kn_wave_max(valid ? sqrt(n2) : 0.0);
+    const double mx = kn_wave_max(rec ? sqrt(n2) : 0.0);
     if (lane == 0) sh[wave][KN_MAXK * PER_ION + GD] = mx;
   }
   __syncthreads();
@@ -245,13 +258,18 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
     kn_part_store(&A.part[(size_t)blockIdx.x * KN_FLUX_SLOTS + j], v);
   }
   if (!kn_arrive_last(A.ctl, threadIdx.x < KN_FLUX_SLOTS, &last)) return;
+  auto fold = [&](int q) {
+    const int cw = T.col_watch[q];
+    return kn_fold_column<KN_FLUX_SLOTS, FLUX_FOLD_DEPTH>(A.part, T.col_slot[q], T.bstart[cw], T.bstart[cw + 1], T.col_max[q] != 0);
+  };
+  if constexpr (PART) {      // this rank's slots; a watch without local cells folds nothing: 0
+    for (int q = threadIdx.x; q < T.n_cols; q += FLUX_THREADS) A.slot[q] = fold(q);
+    if (threadIdx.x == 0) kn_reset_ticket(A.ctl);
+    return;
+  }
   const bool room = kn_claim_row(A.ctl, A.capacity, &row);
   if (room) {
-    for (int q = threadIdx.x; q < T.n_cols; q += FLUX_THREADS) {
-      const int cw = T.col_watch[q];
-      A.rows[(size_t)row * T.n_cols + q] =
-          kn_fold_column<KN_FLUX_SLOTS, FLUX_FOLD_DEPTH>(A.part, T.col_slot[q], T.bstart[cw], T.bstart[cw + 1], T.col_max[q] != 0);
-    }
+    for (int q = threadIdx.x; q < T.n_cols; q += FLUX_THREADS) A.rows[(size_t)row * T.n_cols + q] = fold(q);
   }
   if (threadIdx.x == 0) {
     kn_commit_row(A.ctl, row, room);
@@ -259,19 +277,24 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
   }
 }
 
+template <int KIND, bool PART>
+void launch_as(knpemi_handle* h, const FluxArgs& a, int n_blk, bool fields) {
+  if (fields) hipLaunchKernelGGL((flux_kernel<KIND, true, PART>), dim3(n_blk), dim3(FLUX_THREADS), 0, h->stream, a);
+  else hipLaunchKernelGGL((flux_kernel<KIND, false, PART>), dim3(n_blk), dim3(FLUX_THREADS), 0, h->stream, a);
+}
 template <int KIND>
 void launch(knpemi_handle* h, const FluxArgs& a, int n_blk, bool fields) {
-  if (fields) hipLaunchKernelGGL((flux_kernel<KIND, true>), dim3(n_blk), dim3(FLUX_THREADS), 0, h->stream, a);
-  else hipLaunchKernelGGL((flux_kernel<KIND, false>), dim3(n_blk), dim3(FLUX_THREADS), 0, h->stream, a);
+  if (a.slot) launch_as<KIND, true>(h, a, n_blk, fields);
+  else launch_as<KIND, false>(h, a, n_blk, fields);
 }
 
 }  // namespace
 
 int kn_launch_flux(knpemi_handle* h, int write_fields) {
   const auto& X = h->flux;
-  if (X.n_blk == 0) return KNPEMI_OK;
+  if (X.n_blk == 0) return KNPEMI_OK;      // partitioned, no local cell: this rank's slots stay the zeros of the set-up
   const FluxArgs a{h->K, X.ser.capacity, X.tab, h->d_consts, h->dev.cells, h->dev.VR, X.part, X.ser.ctl, X.ser.rows,
-                   write_fields ? X.fld : nullptr};
+                   write_fields ? X.fld : nullptr, X.recorded, X.xbuf ? X.xbuf + (size_t)X.rank * X.ser.n_cols : nullptr};
   const bool fields = write_fields != 0;
   if (h->cell_kind == KNPEMI_TRIANGLE) launch<KNPEMI_TRIANGLE>(h, a, X.n_blk, fields);
   else if (h->cell_kind == KNPEMI_TETRAHEDRON) launch<KNPEMI_TETRAHEDRON>(h, a, X.n_blk, fields);

@@ -12,7 +12,7 @@
 // Partitioned runs (knpemi_observe_set_partitioned): the last workgroup writes each observable's fold of its block
 // partials, without the denominator, into this rank's slot xbuf[rank * n_obs + q] instead of appending a row (an
 // observable without local entries, or a rank without any, writes the op's identity).  The caller sums xbuf over the
-// ranks -- every slot has one non-zero contributor, so the sum is an exact all-gather -- and observe_combine_kernel
+// ranks -- every slot has one non-zero contributor, so the sum is an exact all-gather -- and record_combine_kernel
 // folds the slots in rank order, divides by the denominators and appends the row.
 #include <algorithm>
 #include <cmath>
@@ -41,11 +41,14 @@ struct ObsArgs {
   double* slot;              // partitioned: this rank's n_obs slots of xbuf; nullptr: append the row here
 };
 
-struct ObsCombineArgs {
-  int n_obs, capacity, world, rank;
-  const int* op;
-  const double* denom;
-  double* xbuf;              // [world][n_obs], summed over the ranks
+// the combine launch of a partitioned record, shared with the fluxes and the membrane exchange (kernels_flux.hip,
+// kernels_exchange.hip): their columns have no op table but the watch table's col_max, and no denominators
+struct CombineArgs {
+  int n_cols, capacity, world, rank;
+  const int* op;             // the observables' ops; nullptr: col_max decides, sums and maxima start from 0
+  const double* denom;       // divisor of a sum; nullptr: none
+  const uint8_t* col_max;
+  double* xbuf;              // [world][n_cols], summed over the ranks
   unsigned long long* ctl;
   double* rows;
 };
@@ -111,23 +114,24 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_kernel(ObsArgs A) {
   }
 }
 
-// One workgroup: fold the ranks' slots of every observable in rank order (the same order on every rank, so every rank
-// appends the same row), divide sums by the global denominator, append the row, then zero the other ranks' slots so
-// that the next sum over the ranks again has one non-zero contributor per slot.
-__global__ __launch_bounds__(OBS_THREADS) void observe_combine_kernel(ObsCombineArgs A) {
+// One workgroup: fold the ranks' slots of every column in rank order (the same order on every rank, so every rank
+// appends the same row) -- with the observable's op from its identity, or by col_max as a sum or a maximum from 0 --
+// divide the observables' sums by the global denominator, append the row, then zero the other ranks' slots so that the
+// next sum over the ranks again has one non-zero contributor per slot.
+__global__ __launch_bounds__(OBS_THREADS) void record_combine_kernel(CombineArgs A) {
   __shared__ unsigned long long row;
   const bool room = kn_claim_row(A.ctl, A.capacity, &row);
-  for (int q = threadIdx.x; q < A.n_obs; q += OBS_THREADS) {
-    const int qop = A.op[q];
-    double v = obs_identity(qop);
-    for (int k = 0; k < A.world; ++k) v = obs_combine(qop, v, A.xbuf[(size_t)k * A.n_obs + q]);
-    if (qop == KNPEMI_OBS_SUM) v /= A.denom[q];
-    if (room) A.rows[(size_t)row * A.n_obs + q] = v;
+  for (int q = threadIdx.x; q < A.n_cols; q += OBS_THREADS) {
+    const int qop = A.op ? A.op[q] : A.col_max[q] ? KNPEMI_OBS_MAX : KNPEMI_OBS_SUM;
+    double v = A.op ? obs_identity(qop) : 0.0;
+    for (int k = 0; k < A.world; ++k) v = obs_combine(qop, v, A.xbuf[(size_t)k * A.n_cols + q]);
+    if (A.denom && qop == KNPEMI_OBS_SUM) v /= A.denom[q];
+    if (room) A.rows[(size_t)row * A.n_cols + q] = v;
   }
   __syncthreads();                          // every slot read before any is zeroed
-  const int n = A.world * A.n_obs;
+  const int n = A.world * A.n_cols;
   for (int i = threadIdx.x; i < n; i += OBS_THREADS)
-    if (i / A.n_obs != A.rank) A.xbuf[i] = 0.0;
+    if (i / A.n_cols != A.rank) A.xbuf[i] = 0.0;
   if (threadIdx.x == 0) kn_commit_row(A.ctl, row, room);      // one workgroup: no ticket
 }
 
@@ -142,11 +146,17 @@ int kn_launch_observe(knpemi_handle* h) {
   return kn_launch_check("observe_kernel");
 }
 
+int kn_launch_record_combine(knpemi_handle* h, const char* who, int n_cols, int capacity, int world, int rank, const int* op,
+                             const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows) {
+  CombineArgs a{n_cols, capacity, world, rank, op, denom, col_max, xbuf, ctl, rows};
+  hipLaunchKernelGGL(record_combine_kernel, dim3(1), dim3(OBS_THREADS), 0, h->stream, a);
+  return kn_launch_check(who);
+}
+
 int kn_launch_observe_combine(knpemi_handle* h) {
   const auto& O = h->obs;
-  ObsCombineArgs a{O.n_obs, O.ser.capacity, O.world, O.rank, O.op, O.denom, O.xbuf, O.ser.ctl, O.ser.rows};
-  hipLaunchKernelGGL(observe_combine_kernel, dim3(1), dim3(OBS_THREADS), 0, h->stream, a);
-  return kn_launch_check("observe_combine_kernel");
+  return kn_launch_record_combine(h, "record_combine_kernel (observables)", O.n_obs, O.ser.capacity, O.world, O.rank, O.op,
+                                  O.denom, nullptr, O.xbuf, O.ser.ctl, O.ser.rows);
 }
 
 int kn_observe_chunk() { return OBS_CHUNK; }

@@ -137,6 +137,8 @@ struct KnEvTab {
 // order by sum or (col_max[q]; the fluxes' maxima only) maximum.  The per-item fields of watch w start at fbase[w]
 // doubles: [component][count[w]], the selected ions in ascending order (fluxes: {J_diff}, {J_drift}; exchange: j^e, j^i,
 // I_ch,k), then the current (fluxes: {i_diff}, {i_drift}; exchange: I_cap and the area).
+// Partitioned runs (knpemi_<name>_set_partitioned): count[w] may be 0 (no workgroup then) and item i of watch w has the
+// byte ibase[w] + i of the recorded mask; the other kernels do not read ibase.
 #define KN_FLUX_CHUNK 256
 #define KN_FLUX_SLOTS 32        // >= KN_MAXK (2 * 3 + 1) + 3 + 1
 #define KN_EX_SLOTS 16          // >= 3 KN_MAXK + 3
@@ -149,6 +151,7 @@ struct KnWatchTab {
   int first[KN_MAXSUB];
   int count[KN_MAXSUB];
   int mask[KN_MAXSUB];
+  int ibase[KN_MAXSUB];
   long long fbase[KN_MAXSUB];
   uint8_t col_watch[KN_WATCH_MAXCOLS], col_slot[KN_WATCH_MAXCOLS], col_max[KN_WATCH_MAXCOLS];
 };
@@ -622,6 +625,13 @@ struct knpemi_handle : KnDevice {
     double* fld = nullptr;               // per-item fields, allocated at the first record that writes them
     size_t fld_len = 0;
     bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
+    // partitioned runs (knpemi_<name>_set_partitioned): one byte per item in watch order (1: this rank's sums and maxima
+    // count it), and the caller's [world][n_cols] exchange buffer, summed over the ranks as KnObserve's
+    uint8_t* recorded = nullptr;
+    double* xbuf = nullptr;
+    int rank = 0, world = 1;
+    knpemi_allreduce_fn allreduce = nullptr;
+    void* ctx = nullptr;
     std::vector<void*> allocs;
   } flux, exchange;
   int knp_flags = 0;                   // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
@@ -653,6 +663,10 @@ int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_
 int kn_launch_update_pde(knpemi_handle* h);
 int kn_launch_observe(knpemi_handle* h);
 int kn_launch_observe_combine(knpemi_handle* h);
+// the combine launch of a partitioned record (kernels_observe.hip): op / denom of the observables, or op == nullptr and
+// col_max of a watch table (sums and maxima from 0)
+int kn_launch_record_combine(knpemi_handle* h, const char* who, int n_cols, int capacity, int world, int rank, const int* op,
+                             const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows);
 int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev);
 int kn_launch_events_reset(knpemi_handle* h);
 int kn_launch_flux(knpemi_handle* h, int write_fields);

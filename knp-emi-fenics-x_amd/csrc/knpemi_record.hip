@@ -4,9 +4,12 @@
 // Three of them append rows to a series buffer (KnSeries; the device side is record_tail.h).  The fluxes and the exchange
 // are one recorder over different items -- the cells of a watched sub-domain, the membrane facets of a watched cell: they
 // share KnWatched, KnWatchTab and every routine but the launch, and a WatchKind names what differs.  The membrane events
-// keep per-dof maps and no series.
+// keep per-dof maps and no series.  On a cell partition the three series recorders follow one scheme: the record launch
+// writes the rank's partial row into its slots of an exchange buffer, the buffer is summed over the ranks, and
+// record_combine_kernel (kernels_observe.hip) folds the slots in rank order and appends the row.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -291,39 +294,59 @@ struct WatchKind {
   KnWatched knpemi_handle::*state;
   int (*launch)(knpemi_handle*, int);
   bool after_ode;          // the record reads phi_M and I_ch, which the ODE sweeps may write on the auxiliary streams
+  const char* combine;     // the combine launch of a partitioned record in error messages
 };
 const WatchKind FLUX{"flux", "no fluxes set (knpemi_flux_set)", "sub-domain", "cells", "bad sub-domain index", "the current",
-                     true, KN_FLUX_SLOTS, &knpemi_handle::flux, kn_launch_flux, false};
+                     true, KN_FLUX_SLOTS, &knpemi_handle::flux, kn_launch_flux, false, "record_combine_kernel (fluxes)"};
 const WatchKind EXCHANGE{"exchange", "no exchange set (knpemi_exchange_set)", "cell", "membrane facets",
                          "unknown cell (bad sub-domain index)", "the current columns", false, KN_EX_SLOTS,
-                         &knpemi_handle::exchange, kn_launch_exchange, true};
+                         &knpemi_handle::exchange, kn_launch_exchange, true, "record_combine_kernel (exchange)"};
 
 inline std::string entry(const WatchKind& k, const char* what) { return std::string("knpemi_") + k.name + "_" + what; }
 inline int popcount(int m) { int n = 0; for (; m; m &= m - 1) ++n; return n; }
 inline int ions_below(int m, int ion) { return popcount(m & (ion == -1 ? 0xFF : (1 << ion) - 1)); }
 
-// knpemi_<name>_set.  off / count: first item and number of items of every sub-domain; chunk: items per workgroup;
+// what knpemi_<name>_set_partitioned adds to knpemi_<name>_set
+struct WatchPart {
+  const uint8_t* recorded;
+  int rank, world;
+  void* xbuf_dev;
+  knpemi_allreduce_fn allreduce;
+  void* ctx;
+};
+
+// knpemi_<name>_set and, with `part`, knpemi_<name>_set_partitioned: a watch may then have no local item (no workgroup,
+// zeros in this rank's slots).  off / count: first item and number of items of every sub-domain; chunk: items per workgroup;
 // ion_fld / cur_fld: field doubles per item of a watched ion / of the current; cols(mask, emit): the columns of one
 // watch, in row order, as emit(slot, is_max).  A refused call leaves the previous table alone.
 template <class Cols>
 int watched_set(knpemi_handle* h, const WatchKind& k, const std::vector<int>& off, const std::vector<int>& count, int chunk,
-                int ion_fld, int cur_fld, Cols cols, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
-  const std::string fn = entry(k, "set");
+                int ion_fld, int cur_fld, Cols cols, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity,
+                const WatchPart* part = nullptr) {
+  const std::string fn = entry(k, part ? "set_partitioned" : "set");
   if (!h || !sub || !ion_mask) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (part) {
+    if (part->world < 1 || part->rank < 0 || part->rank >= part->world) return kn_fail(KNPEMI_EINVAL, fn + ": bad rank / world");
+    if ((size_t)part->world * KN_WATCH_MAXCOLS > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, fn + ": exchange buffer too large");
+    if (!part->recorded) return kn_fail(KNPEMI_EINVAL, fn + ": the recorded mask is required");
+    if (!part->xbuf_dev) return kn_fail(KNPEMI_EINVAL, fn + ": exchange buffer is required");
+    if (!part->allreduce && !h->comm)
+      return kn_fail(KNPEMI_EINVAL, fn + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
+  }
   if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
   if (n_watch < 1 || n_watch > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB " + k.watch + "s");
   if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
   KnWatchTab T{};
   int watch_of[KN_MAXSUB];
   std::fill(watch_of, watch_of + KN_MAXSUB, -1);
-  long long fbase = 0;
+  long long fbase = 0, n_items = 0;
   int col = 0;
   for (int w = 0; w < n_watch; ++w) {
     const int s = sub[w], m = ion_mask[w];
     if (s == 0 && !k.ecs) return kn_fail(KNPEMI_EINVAL, fn + ": the ECS (sub-domain 0) has no membrane of its own: watch the cells");
     if (s < 0 || s >= h->n_sub) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.bad_sub);
     if (watch_of[s] >= 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.watch + " " + std::to_string(s) + " is listed twice");
-    if (count[s] < 1) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.watch + " " + std::to_string(s) + " has no " + k.items);
+    if (count[s] < (part ? 0 : 1)) return kn_fail(KNPEMI_EINVAL, fn + ": " + k.watch + " " + std::to_string(s) + " has no " + k.items);
     if (m == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty ion mask");
     if (m & ~(KN_WATCH_CURRENT | ((1 << h->K) - 1)))
       return kn_fail(KNPEMI_EINVAL, fn + ": ion mask has bits at or above the number of ions (bit 8: " + k.current + ")");
@@ -331,6 +354,8 @@ int watched_set(knpemi_handle* h, const WatchKind& k, const std::vector<int>& of
     T.sub[w] = s; T.mask[w] = m; T.first[w] = off[s]; T.count[w] = count[s];
     T.bstart[w + 1] = T.bstart[w] + (count[s] + chunk - 1) / chunk;
     T.fbase[w] = fbase;
+    T.ibase[w] = (int)n_items;
+    n_items += count[s];
     fbase += (long long)(ion_fld * popcount(m & 0xFF) + ((m & KN_WATCH_CURRENT) ? cur_fld : 0)) * count[s];
     cols(m, [&](int slot, bool is_max) {
       T.col_watch[col] = (uint8_t)w; T.col_slot[col] = (uint8_t)slot; T.col_max[col] = is_max;
@@ -338,6 +363,7 @@ int watched_set(knpemi_handle* h, const WatchKind& k, const std::vector<int>& of
     });
   }
   T.n_watch = n_watch; T.n_cols = col;
+  if (n_items > (long long)INT32_MAX) return kn_fail(KNPEMI_EINVAL, fn + ": too many " + k.items);
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
   KnWatched& X = h->*k.state;
@@ -348,6 +374,17 @@ int watched_set(knpemi_handle* h, const WatchKind& k, const std::vector<int>& of
       || (rc = series_alloc(X.allocs, h->stream, capacity, col, &X.ser))) {
     recorder_free(X);
     return rc;
+  }
+  if (part) {
+    if (n_items && (rc = kn_upload(X.allocs, part->recorded, (size_t)n_items, &X.recorded))) { recorder_free(X); return rc; }
+    X.xbuf = static_cast<double*>(part->xbuf_dev);
+    X.rank = part->rank; X.world = part->world; X.allreduce = part->allreduce; X.ctx = part->ctx;
+    // all zero: this rank's slots are written by the records (never, without local items), the others' by the sum
+    if (hipMemsetAsync(X.xbuf, 0, (size_t)part->world * col * sizeof(double), h->stream) != hipSuccess
+        || hipStreamSynchronize(h->stream) != hipSuccess) {
+      recorder_free(X);
+      return kn_fail(KNPEMI_EHIP, fn + ": the exchange buffer cannot be zeroed");
+    }
   }
   X.host = T; X.n_watch = n_watch; X.n_blk = n_blk; X.fld_len = (size_t)fbase;
   std::copy(watch_of, watch_of + KN_MAXSUB, X.watch_of);
@@ -366,10 +403,18 @@ int watched_record(knpemi_handle* h, const WatchKind& k, int write_fields) {
     KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
   }
   if (write_fields && !X.fld)
-    if (int rc = kn_alloc(X.allocs, X.fld_len, &X.fld)) return rc;
+    if (int rc = kn_alloc(X.allocs, std::max<size_t>(X.fld_len, 1), &X.fld)) return rc;
   if (int rc = k.launch(h, write_fields)) return rc;
   if (write_fields) X.fld_valid = true;
-  return KNPEMI_OK;
+  if (!X.xbuf) return KNPEMI_OK;
+  // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
+  const int n = X.world * X.ser.n_cols;
+  int rc = X.allreduce ? (X.allreduce(X.ctx, n) ? kn_fail(KNPEMI_EHIP, entry(k, "record") + ": allreduce hook failed") : KNPEMI_OK)
+                       : knpemi_comm_allreduce(h, X.xbuf, n);
+  if (rc) return rc;
+  return kn_launch_record_combine(h, k.combine, X.ser.n_cols, X.ser.capacity, X.world, X.rank, nullptr, nullptr,
+                                  reinterpret_cast<const uint8_t*>(X.tab) + offsetof(KnWatchTab, col_max), X.xbuf, X.ser.ctl,
+                                  X.ser.rows);
 }
 
 // knpemi_<name>_reset: a new series, stream-ordered; the fields of the old one are forgotten
@@ -407,13 +452,15 @@ int fields_copy(knpemi_handle* h, const WatchKind& k, int w, size_t offset, doub
   const KnWatched& X = h->*k.state;
   if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (" + entry(k, "record") + "(h, 1))");
   if (n != want) return kn_fail(KNPEMI_EINVAL, fn + ": length is not " + length);
+  if (n == 0) return KNPEMI_OK;      // partitioned: no local item
   KN_HIP(hipSetDevice(h->device));
   return kn_to_host(h->stream, host, X.fld + X.host.fbase[w] + offset, n);
 }
 }  // namespace
 
-extern "C" int knpemi_flux_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_flux_set: null argument");
+namespace {
+int flux_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity, const WatchPart* part) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, entry(FLUX, part ? "set_partitioned" : "set") + ": null argument");
   const int K = h->K, gd = h->gdim, per_ion = 2 * gd + 1;
   // per watched ion {sum vol J_diff}, {sum vol J_drift}, max |J|; with the current {sum vol i}, max |i|
   auto cols = [&](int m, auto emit) {
@@ -423,11 +470,11 @@ extern "C" int knpemi_flux_set(knpemi_handle* h, int n_watch, const int32_t* sub
     if (m & KN_WATCH_CURRENT)
       for (int j = 0; j <= gd; ++j) emit(KN_MAXK * per_ion + j, j == gd);
   };
-  return watched_set(h, FLUX, h->coff, h->n_cell, kn_flux_chunk(), 2 * gd, 2 * gd, cols, n_watch, sub, ion_mask, capacity);
+  return watched_set(h, FLUX, h->coff, h->n_cell, kn_flux_chunk(), 2 * gd, 2 * gd, cols, n_watch, sub, ion_mask, capacity, part);
 }
 
-extern "C" int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
-  if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_exchange_set: null argument");
+int exchange_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity, const WatchPart* part) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, entry(EXCHANGE, part ? "set_partitioned" : "set") + ": null argument");
   const int K = h->K;
   // per watched ion int j^e, int j^i, int I_ch,k; with the current columns int I_cap, int I_ch,tot and the area: all sums
   auto cols = [&](int m, auto emit) {
@@ -437,7 +484,27 @@ extern "C" int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t*
     if (m & KN_WATCH_CURRENT)
       for (int j = 0; j < 3; ++j) emit(3 * KN_MAXK + j, false);
   };
-  return watched_set(h, EXCHANGE, h->foff, h->n_facet, kn_exchange_chunk(), 3, 2, cols, n_watch, sub, ion_mask, capacity);
+  return watched_set(h, EXCHANGE, h->foff, h->n_facet, kn_exchange_chunk(), 3, 2, cols, n_watch, sub, ion_mask, capacity, part);
+}
+}  // namespace
+
+extern "C" int knpemi_flux_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
+  return flux_set(h, n_watch, sub, ion_mask, capacity, nullptr);
+}
+extern "C" int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask, int capacity) {
+  return exchange_set(h, n_watch, sub, ion_mask, capacity, nullptr);
+}
+extern "C" int knpemi_flux_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask,
+                                           int capacity, const uint8_t* recorded, int rank, int world, void* xbuf_dev,
+                                           knpemi_allreduce_fn allreduce, void* ctx) {
+  const WatchPart part{recorded, rank, world, xbuf_dev, allreduce, ctx};
+  return flux_set(h, n_watch, sub, ion_mask, capacity, &part);
+}
+extern "C" int knpemi_exchange_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask,
+                                               int capacity, const uint8_t* recorded, int rank, int world, void* xbuf_dev,
+                                               knpemi_allreduce_fn allreduce, void* ctx) {
+  const WatchPart part{recorded, rank, world, xbuf_dev, allreduce, ctx};
+  return exchange_set(h, n_watch, sub, ion_mask, capacity, &part);
 }
 
 extern "C" int knpemi_flux_record(knpemi_handle* h, int write_fields) { return watched_record(h, FLUX, write_fields); }

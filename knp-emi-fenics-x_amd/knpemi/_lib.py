@@ -175,12 +175,16 @@ SIGNATURES = {
     "knpemi_flux_fields": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_size_t]),
     "knpemi_flux_reset": (C.c_int, [C.c_void_p]),
     "knpemi_flux_clear": (C.c_int, [C.c_void_p]),
+    "knpemi_flux_set_partitioned": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_int, c_u8_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "knpemi_exchange_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_int]),
     "knpemi_exchange_record": (C.c_int, [C.c_void_p, C.c_int]),
     "knpemi_exchange_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     "knpemi_exchange_fields": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_size_t]),
     "knpemi_exchange_reset": (C.c_int, [C.c_void_p]),
     "knpemi_exchange_clear": (C.c_int, [C.c_void_p]),
+    "knpemi_exchange_set_partitioned": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_int, c_u8_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "knpemi_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "knpemi_trace": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_halo_width": (C.c_int, [C.c_void_p, C.c_int]),

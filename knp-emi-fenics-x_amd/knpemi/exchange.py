@@ -50,14 +50,18 @@ the mass term.  The discrete scheme therefore conserves every solved ion exactly
 
 with M = int c dx (`Observables.reduce(op="integral")`).  `budget` returns the defects of these identities.
 
-Cell-partitioned runs are not supported: a rank's sums would include its ghost facets.
+Cell-partitioned runs (`DeviceStepper.exchange(ex, halo=halo)`, `WatchedIons.partition`): every membrane facet of the
+global mesh is recorded by one rank, the lowest owner among its vertices; the facets of a rank's ghost layer get their
+per-facet means and enter none of its sums.  Every rank holds the global series, equal to that of one rank holding the
+whole mesh up to the order of summation, so `budget` works unchanged with the series of a partitioned `Observables`;
+`fields(tag, halo=halo)` returns the means of the local facets with the mask of the ones this rank records.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from .fem.function import as_float
-from .recording import CURRENT_BIT, WatchedIons, lib_int, nodal_values as _values  # noqa: F401
+from .recording import CURRENT_BIT, WatchedIons, combine_partials, lib_int, nodal_values as _values  # noqa: F401
 
 ION_PARTS = ("ecs", "ics", "channel")
 
@@ -157,6 +161,18 @@ class MembraneExchange(WatchedIons):
     def n_facets(self, tag):
         return int(self.subdomain_list[tag]["mesh_mem"].cells.shape[0])
 
+    def _item_owners(self, halo):
+        own, out, off = halo.vertex_owner("mem"), {}, 0
+        for tag in self.tags[1:]:                  # the device numbers the membrane dofs cell after cell
+            mem = self.subdomain_list[tag].get("mesh_mem")
+            n = 0 if mem is None else int(mem.x.shape[0])
+            if tag in self.watched:
+                out[tag] = (mem, own[off:off + n])
+            off += n
+        if off != own.shape[0]:
+            raise ValueError("exchange: the halo does not number the membrane dofs of these cells")
+        return out
+
     # -- host restatement ----------------------------------------------------------------------------------
     def _geometry(self, tag):
         """Of the membrane of cell `tag`: vertex ids of the facets on the ECS side, the cell side and the membrane mesh,
@@ -181,14 +197,16 @@ class MembraneExchange(WatchedIons):
             self._geo[tag] = (e, i, q, N, wq, fmodel)
         return self._geo[tag]
 
-    def compute_host(self, phi, c_prev, c_elim=None, phi_M_prev=None, I_ch=None, dt=None, splitting=True):
+    def compute_host(self, phi, c_prev, c_elim=None, phi_M_prev=None, I_ch=None, dt=None, splitting=True, recorded=None):
         """(fields, row) from host data, written from the definitions of the module docstring: the numpy restatement of
         the device kernel and the reference of the device tests.  phi[tag]: the potential just solved for, in the ECS
         and in every watched cell; c_prev[tag]: the nodal concentrations, K of them, or the K - 1 solved ones with the
         eliminated ion's taken from c_elim[tag] (default: `ion_list[-1]["c_<tag>"]`); phi_M_prev[tag]: the membrane
         potential after the ODE step; I_ch[tag]: per membrane model of the cell {ion name: channel current on the
         membrane dofs} (default: the `I_ch_k` of `subdomain_list[tag]["mem_models"]`).  `Function`s or arrays.
-        fields[tag]: what `fields(tag)` returns; row: the series row as {key: float}."""
+        fields[tag]: what `fields(tag)` returns; row: the series row as {key: float}.
+        recorded: {tag: bool per facet} -- the partial row of one rank of a partition (`partition`): the sums run over
+        the recorded facets only; the fields are those of every facet."""
         if dt is None or phi_M_prev is None:
             raise ValueError("compute_host needs phi_M_prev and dt")
         dt, S = as_float(dt), 1.0 if splitting else 0.0
@@ -205,6 +223,7 @@ class MembraneExchange(WatchedIons):
         fields, row = {}, {}
         for tag, (idx, cur) in self.watched.items():
             e, i, q, N, wq, fmodel = self._geometry(tag)
+            rec = slice(None) if recorded is None else np.asarray(recorded[tag], bool)
             at = lambda nodal, ids: np.einsum("qa,fa->fq", N, nodal[ids])      # noqa: E731
             wq = wq * (fmodel >= 0)[:, None]
             area = wq.sum(axis=1)
@@ -229,7 +248,7 @@ class MembraneExchange(WatchedIons):
             def keep(key, integrand):
                 per_facet = (wq * integrand).sum(axis=1)
                 out[key] = per_facet * inv_area
-                row[f"{tag}/{key}"] = float(per_facet.sum())
+                row[f"{tag}/{key}"] = float(per_facet[rec].sum())
             for k in idx:
                 n, Fz = self.names[k], self.F * self.z[k]
                 a_e = self.D[0][k] * self.z[k] ** 2 * cq_e[k] / asum_e
@@ -239,9 +258,9 @@ class MembraneExchange(WatchedIons):
                 keep(f"{n}/channel", Ik[k])
             if cur:
                 keep("capacitive", I_cap)
-                row[f"{tag}/channel"] = float((wq * I_tot).sum())
+                row[f"{tag}/channel"] = float((wq * I_tot)[rec].sum())
                 out["area"] = area
-                row[f"{tag}/area"] = float(area.sum())
+                row[f"{tag}/area"] = float(area[rec].sum())
             out["facet"] = np.arange(q.shape[0])
             fields[tag] = out
         return fields, row
@@ -254,10 +273,11 @@ class MembraneExchange(WatchedIons):
         self._rows.append(self.row_vector(self.compute_host(phi, c_prev, c_elim, phi_M_prev, I_ch, dt, splitting)[1]))
 
     # -- output --------------------------------------------------------------------------------------------
-    def fields(self, tag):
+    def fields(self, tag, halo=None):
         """Per-facet means of the last device record made with fields: "<ion>/ecs", "<ion>/ics", "<ion>/channel" for
         every watched ion, "capacitive" and "area" where the currents are watched, and "facet", the facet's index into
-        the cell's `mesh_mem` (one synchronisation)."""
+        the cell's `mesh_mem` (one synchronisation).  halo: on a cell-partitioned run the arrays cover this rank's local
+        facets, those of the ghost layer included, and "recorded" is the mask of the facets this rank records."""
         self._check_watched(tag)
         nf = self.n_facets(tag)
         get = self._getter(tag, nf, "DeviceStepper.exchange")
@@ -269,6 +289,8 @@ class MembraneExchange(WatchedIons):
         if cur:
             out["capacitive"], out["area"] = get(-1, 0), get(-1, 1)
         out["facet"] = np.arange(nf)
+        if halo is not None:
+            out["recorded"] = self._recorded_of(tag, halo, nf)
         return out
 
     def amounts(self):

@@ -33,14 +33,18 @@ Series row: per watched (sub-domain, ion) the integrals sum_T vol_T J_diff and s
 and max_T |J| (Euclidean norm); per watched sub-domain with `current=True` sum_T vol_T i and max_T |i|.  On simplices
 the sums are the exact integrals of the discrete flux.
 
-Cell-partitioned runs are not supported: a rank's sums would include its ghost cells.
+Cell-partitioned runs (`DeviceStepper.fluxes(fl, halo=halo)`, `WatchedIons.partition`): every cell of the global mesh is
+recorded by one rank, the lowest owner among its vertices; a rank's ghost cells get their per-cell vectors and enter none
+of its sums and maxima.  Every rank holds the global series -- maxima bit for bit those of one rank holding the whole
+mesh, sums to rounding -- and `fields(tag, halo=halo)` the vectors of its local cells with the mask of the ones it
+records.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from .fem.function import as_float
-from .recording import CURRENT_BIT, WatchedIons, lib_int, nodal_values as _values  # noqa: F401
+from .recording import CURRENT_BIT, WatchedIons, combine_partials, lib_int, nodal_values as _values  # noqa: F401
 
 PARTS = ("diffusive", "drift")
 
@@ -127,6 +131,20 @@ class IonFluxes(WatchedIons):
     def n_cells(self, tag):
         return int(self.mesh[tag].cells.shape[0])
 
+    def max_columns(self):
+        return np.concatenate([np.full(w, key.endswith("max")) for key, w in self.columns()])
+
+    def _item_owners(self, halo):
+        own, out, off = halo.vertex_owner("bulk"), {}, 0
+        for tag in self.tags:                      # the device numbers the vertices sub-domain after sub-domain
+            n = int(self.mesh[tag].x.shape[0])
+            if tag in self.watched:
+                out[tag] = (self.mesh[tag], own[off:off + n])
+            off += n
+        if off != own.shape[0]:
+            raise ValueError("fluxes: the halo does not number the vertices of these sub-domains")
+        return out
+
     # -- host restatement ----------------------------------------------------------------------------------
     def _geometry(self, tag):
         if tag not in self._geo:
@@ -135,15 +153,19 @@ class IonFluxes(WatchedIons):
             self._geo[tag] = (cells, m.cell_type) + cell_geometry(x, cells, m.cell_type)
         return self._geo[tag]
 
-    def compute_host(self, phi, c, c_elim=None):
+    def compute_host(self, phi, c, c_elim=None, recorded=None):
         """(fields, row) from host data, written from the definitions of the module docstring: the numpy restatement of
         the device kernel and the reference of the device tests.  phi[tag]: the potential of every watched sub-domain;
         c[tag]: the nodal concentrations of its ions, K of them, or the K - 1 solved ones with the eliminated ion's
         taken from c_elim[tag] (default: `ion_list[-1]["c_<tag>"]`).  `Function`s or arrays.
-        fields[tag]: what `fields(tag)` returns; row: the series row as {key: (gdim,) array or float}."""
+        fields[tag]: what `fields(tag)` returns; row: the series row as {key: (gdim,) array or float}.
+        recorded: {tag: bool per cell} -- the partial row of one rank of a partition (`partition`): the sums and the
+        maxima (from 0) run over the recorded cells only; the fields are those of every cell."""
         fields, row = {}, {}
         for tag, (idx, cur) in self.watched.items():
             cells, kind, E, vol = self._geometry(tag)
+            rec = slice(None) if recorded is None else np.asarray(recorded[tag], bool)
+            top = (lambda a: float(a.max())) if recorded is None else (lambda a: float(a.max(initial=0.0)))
             ck = list(c[tag])
             if len(ck) == self.K - 1:
                 ck.append(self.ion_list[-1][f"c_{tag}"] if c_elim is None else c_elim[tag])
@@ -162,13 +184,13 @@ class IonFluxes(WatchedIons):
                 if k in idx:
                     n = self.names[k]
                     out[f"{n}/diffusive"], out[f"{n}/drift"] = Jd, Jr
-                    row[f"{tag}/{n}/diffusive"] = (vol[:, None] * Jd).sum(axis=0)
-                    row[f"{tag}/{n}/drift"] = (vol[:, None] * Jr).sum(axis=0)
-                    row[f"{tag}/{n}/max"] = float(norm(Jd + Jr).max())
+                    row[f"{tag}/{n}/diffusive"] = (vol[:, None] * Jd)[rec].sum(axis=0)
+                    row[f"{tag}/{n}/drift"] = (vol[:, None] * Jr)[rec].sum(axis=0)
+                    row[f"{tag}/{n}/max"] = top(norm(Jd + Jr)[rec])
             if cur:
                 out["current/diffusive"], out["current/drift"], out["current"] = i_diff, i_drift, i_diff + i_drift
-                row[f"{tag}/current"] = (vol[:, None] * out["current"]).sum(axis=0)
-                row[f"{tag}/current_max"] = float(norm(out["current"]).max())
+                row[f"{tag}/current"] = (vol[:, None] * out["current"])[rec].sum(axis=0)
+                row[f"{tag}/current_max"] = top(norm(out["current"])[rec])
             fields[tag] = out
         return fields, row
 
@@ -182,10 +204,11 @@ class IonFluxes(WatchedIons):
         self._rows.append(self.row_vector(self.compute_host(phi, c, c_elim)[1]))
 
     # -- output --------------------------------------------------------------------------------------------
-    def fields(self, tag):
+    def fields(self, tag, halo=None):
         """Per-cell arrays (n_cell, gdim) of the last device record made with fields: "<ion>/diffusive" and
         "<ion>/drift" for every watched ion, "current/diffusive", "current/drift" and their sum "current" where the
-        current is watched (one synchronisation)."""
+        current is watched (one synchronisation).  halo: on a cell-partitioned run the arrays cover this rank's local
+        cells, ghosts included, and "recorded" is the mask of the cells this rank records."""
         self._check_watched(tag)
         get = self._getter(tag, (self.gdim, self.n_cells(tag)), "DeviceStepper.fluxes")
         idx, cur = self.watched[tag]
@@ -197,4 +220,6 @@ class IonFluxes(WatchedIons):
             for p, name in enumerate(PARTS):
                 out[f"current/{name}"] = np.ascontiguousarray(get(-1, p).T)
             out["current"] = out["current/diffusive"] + out["current/drift"]
+        if halo is not None:
+            out["recorded"] = self._recorded_of(tag, halo, self.n_cells(tag))
         return out

@@ -377,7 +377,7 @@ class Observables(RowSeries):
 
 def combine_partials(obs, rows_by_rank):
     """The row of a partitioned run from the ranks' slot rows (`Observables.evaluate_partial_host`, one per rank in
-    rank order), folded as observe_combine_kernel does: in rank order with each observable's op, sums divided by the
+    rank order), folded as record_combine_kernel does: in rank order with each observable's op, sums divided by the
     global denominator."""
     rows = np.asarray(rows_by_rank, np.float64)
     out = np.empty(rows.shape[1])

@@ -1,6 +1,13 @@
 """What the on-device recorders share on the host: `RowSeries`, the times and rows of a series (`Observables`,
-`IonFluxes`, `MembraneExchange`); `WatchedIons`, the (tag, ions, current) watches of the last two; `Tap`, one recorder
-attached to a `DeviceStepper` (`MembraneEvents` too).
+`IonFluxes`, `MembraneExchange`); `WatchedIons`, the (tag, ions, current) watches of the last two and their tables on a
+cell partition; `Tap`, one recorder attached to a `DeviceStepper` (`MembraneEvents` too).
+
+Cell-partitioned runs of `WatchedIons`.  A rank's local mesh holds its cells and a ghost layer, so a sum over the local
+items (the cells of a sub-domain, the membrane facets of a cell) would count the ghosts twice.  `partition` gives every
+item one recorder with the rule of `Observables.partition` -- the lowest owner among the item's vertices -- as a byte mask
+per watch.  The record kernel writes the per-item fields of every local item and keeps the unrecorded ones out of its
+sums and maxima; the ranks' partial rows are summed on the device slot by slot (an exact all-gather) and folded in rank
+order, sums summed and maxima maximised from 0 (`combine_partials`), so every rank appends the same row.
 
 The drain rule: rows collect in a device buffer of `capacity` rows; the host keeps the time of every row it has
 enqueued and moves the buffer into the series (one synchronisation) whenever it holds `capacity` of them and when
@@ -112,7 +119,59 @@ class WatchedIons(RowSeries):
         idx, cur = self.watched[tag]
         return sum(1 << k for k in idx) | (CURRENT_BIT if cur else 0)
 
-    def _attach(self, dp, capacity):
+    def max_columns(self):
+        """Per scalar column of the row: True where it is a maximum (from 0), False where a sum."""
+        return np.zeros(self.n_cols, bool)
+
+    def _item_owners(self, halo):
+        """{tag: (item mesh, owner rank of every vertex of it)} of the watches on this rank of a partition; the mesh is
+        None where the rank holds no item of the watch."""
+        raise NotImplementedError
+
+    def partition(self, halo, gather=None, every=1, capacity=1024):
+        """The recorded masks of this rank of a cell-partitioned run, set in `self._ptab`: {"rank", "world", "recorded":
+        {tag: bool per local item}}.  An item is recorded by the lowest owner among its vertices
+        (`halo.vertex_owner`), as `Observables.partition` decides.  halo: the rank's `knpemi.fem.distributed.Halo`
+        with its plans built; gather(obj) -> [obj of every rank] (default: torch.distributed.all_gather_object).
+        Collective: every rank calls it once with the same watches, ion masks, every and capacity, or every rank raises
+        ValueError."""
+        if not self.watched:
+            raise ValueError(f"no {self._WATCH} is watched")
+        if gather is None:
+            import torch.distributed as dist
+
+            def gather(obj):
+                out = [None] * dist.get_world_size()
+                dist.all_gather_object(out, obj)
+                return out
+        rank = int(halo.rank)
+        recorded = {}
+        for tag, (mesh, ow) in self._item_owners(halo).items():
+            if mesh is None or mesh.cells.shape[0] == 0:
+                recorded[tag] = np.zeros(0, bool)
+            else:
+                recorded[tag] = ow[np.asarray(mesh.cells)].min(axis=1) == rank
+        mine = dict(watches=[(t, self.mask(t)) for t in self.watched], every=int(every), capacity=int(capacity))
+        allr = gather(mine)
+        for r, other in enumerate(allr):
+            for what in ("watches", "every", "capacity"):
+                if other[what] != allr[0][what]:
+                    raise ValueError(f"{self._NAME} recorders differ between ranks: {what} of rank {r} is "
+                                     f"{other[what]!r}, of rank 0 {allr[0][what]!r} (every rank must watch the same "
+                                     f"{self._WATCH}s with the same ions in the same order and pass the same every and "
+                                     "capacity)")
+        self._ptab = dict(rank=rank, world=len(allr), recorded=recorded)
+        return self._ptab
+
+    def recorded_mask(self):
+        """The masks of `partition`, concatenated in watch order: one uint8 per local item."""
+        rec = self._ptab["recorded"]
+        return np.ascontiguousarray(np.concatenate([rec[t] for t in self.watched]).astype(np.uint8))
+
+    def _attach(self, dp, capacity, halo=None, every=1):
+        """knpemi_<_NAME>_set, or with a halo `partition` and knpemi_<_NAME>_set_partitioned: the exchange buffer is a
+        device tensor, summed by the library's communicator when the halo runs on it, else by the halo's all-reduce
+        (gloo or torch RCCL).  Returns the objects the handle refers to (keep them alive while it records)."""
         if self._dev is not None:
             raise RuntimeError(f"{self._SELF} attached to a device problem already")
         if not self.watched:
@@ -120,8 +179,32 @@ class WatchedIons(RowSeries):
         tags = list(self.watched)
         sub = np.array([dp.sub_index[t] for t in tags], np.int32)
         mask = np.array([self.mask(t) for t in tags], np.int32)
-        L.check(getattr(dp.lib, f"knpemi_{self._NAME}_set")(dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity)))
+        keep = None
+        if halo is None:
+            L.check(getattr(dp.lib, f"knpemi_{self._NAME}_set")(dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity)))
+        else:
+            import torch
+            self.partition(halo, None, every, capacity)
+            rec = self.recorded_mask()
+            rec = rec if rec.size else np.zeros(1, np.uint8)      # a rank without items still passes a mask
+            world = self._ptab["world"]
+            xbuf = torch.zeros(world * self.n_cols, dtype=torch.float64, device=torch.device("cuda", dp.device))
+            cb = None if getattr(halo, "_native", False) else halo.allreduce_callback(xbuf)
+            L.check(getattr(dp.lib, f"knpemi_{self._NAME}_set_partitioned")(
+                dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity), rec.ctypes.data_as(L.c_u8_p),
+                self._ptab["rank"], world, xbuf.data_ptr(), C.cast(cb, C.c_void_p) if cb is not None else None, None))
+            keep = (xbuf, cb)
         self._dev = (dp.lib, dp.h, dict(dp.sub_index))
+        return keep
+
+    def _recorded_of(self, tag, halo, n):
+        """The "recorded" entry of fields(tag, halo=halo): this rank's mask over the n local items."""
+        ptab = getattr(self, "_ptab", None)
+        if ptab is None:
+            raise RuntimeError(f"fields(halo=...): {self._SELF} not partitioned (attach with halo=, or call partition)")
+        if int(halo.rank) != ptab["rank"] or ptab["recorded"][tag].shape[0] != n:
+            raise ValueError("fields(halo=...): not the halo of this recorder's partition")
+        return ptab["recorded"][tag].copy()
 
     def _getter(self, tag, shape, where):
         """get(ion, part) -> the array of `shape` that knpemi_<_NAME>_fields holds for watch `tag`."""
@@ -136,6 +219,18 @@ class WatchedIons(RowSeries):
             L.check(fields(h, sub_index[tag], ion, part, L.dptr(buf), buf.size))
             return buf
         return get
+
+
+def combine_partials(rec, rows_by_rank):
+    """The row of a partitioned run from the ranks' partial rows (`compute_host(recorded=...)` through `row_vector`, one
+    per rank in rank order), folded as record_combine_kernel does: from 0 in rank order, `rec.max_columns()` by maximum,
+    the other columns by sum."""
+    rows = np.asarray(rows_by_rank, np.float64)
+    is_max = rec.max_columns()
+    out = np.zeros(rows.shape[1])
+    for r in range(rows.shape[0]):
+        out = np.where(is_max, np.maximum(out, rows[r]), out + rows[r])
+    return out
 
 
 class Tap:

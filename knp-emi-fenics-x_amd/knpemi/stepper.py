@@ -87,6 +87,7 @@ class DeviceStepper:
         # last KNP assembly of a step, "observe", "detect" and "fluxes", in this order, behind the end-of-step update
         self.taps = {}
         self._obs_halo = None      # the halo of a partitioned observe
+        self._tap_halo = {}        # "fluxes" / "exchange": the halo they were attached with, and what the handle refers to
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -206,33 +207,48 @@ class DeviceStepper:
                                   record=lambda t, fields: L.check(self.lib.knpemi_events_record(self.dp.h, t)))
 
     # -- ion fluxes ---------------------------------------------------------------------------------
-    def fluxes(self, fl, every=1, capacity=1024, t0=0.0, fields=False):
+    def fluxes(self, fl, every=1, capacity=1024, t0=0.0, fields=False, halo=None):
         """Record the ion fluxes `fl` (knpemi.fluxes.IonFluxes) on the device after every `every`-th step, at time
         t0 + k dt for step k: one launch over the cells of every watched sub-domain on the main stream, behind the
         end-of-step update, where observables and events record.  Rows collect in a device buffer of `capacity` rows;
         the host keeps the times of the rows it has enqueued and drains the buffer into `fl` (one synchronisation)
         whenever it holds `capacity` of them, and when `fl.series()` is called.  fields: every record also writes the
         per-cell vectors (`fl.fields(tag)` reads those of the latest record).
-        Partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost cells."""
+
+        halo: this rank's attached halo on a cell-partitioned problem (collective: every rank calls fluxes with the same
+        watches, every and capacity).  Every rank then records the global row -- every cell counted by one rank, the
+        partial rows summed over the ranks on the device at each record (WatchedIons.partition) -- and `step(halo)`
+        records with the same halo; `fl.fields(tag, halo=halo)` reads the local cells.  Draining stays rank-local.
+        Without it, partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost cells."""
         if every < 1 or capacity < 1:
             raise ValueError("every and capacity must be positive")
         if "fluxes" in self.taps:
             raise RuntimeError("this stepper records ion fluxes already")
         if fl._drain is not None:
             raise RuntimeError("these fluxes are attached to a stepper already")
-        self._watched_tap("fluxes", "flux", fl, "ion fluxes", every, capacity, t0, fields)
+        self._watched_tap("fluxes", "flux", fl, "ion fluxes", every, capacity, t0, fields, halo=halo)
 
-    def _watched_tap(self, name, kind, rec, label, every, capacity, t0, fields, offset=0):
-        """Attach the watches of `rec` (IonFluxes, MembraneExchange: knpemi_<kind>_*) and build their tap."""
+    def _watched_tap(self, name, kind, rec, label, every, capacity, t0, fields, offset=0, halo=None):
+        """Attach the watches of `rec` (IonFluxes, MembraneExchange: knpemi_<kind>_*), with a halo their partitioned
+        table, and build their tap."""
         lib, h = self.lib, self.dp.h
         record, reset = getattr(lib, f"knpemi_{kind}_record"), getattr(lib, f"knpemi_{kind}_reset")
-        rec._attach(self.dp, capacity)
-        self.taps[name] = Tap(rec, label, every, lambda t, f: L.check(record(h, f)), t0, offset, capacity,
+        if halo is not None and halo.dp is not self.dp:
+            raise ValueError(f"{name}(halo=...): attach the halo to this stepper's problem first (halo.attach)")
+        self._tap_halo[name] = (halo, rec._attach(self.dp, capacity, halo, every))
+
+        def enqueue(t, f):
+            rc = record(h, f)
+            err = getattr(halo, "_hook_error", None)
+            if rc != L.OK and err is not None:      # the all-reduce of a partitioned record failed in Python
+                raise err
+            L.check(rc)
+        self.taps[name] = Tap(rec, label, every, enqueue, t0, offset, capacity,
                               self._reader(getattr(lib, f"knpemi_{kind}_read")), rec.n_cols, lambda: L.check(reset(h)),
                               fields)
 
     # -- membrane ion exchange --------------------------------------------------------------------------
-    def exchange(self, ex, every=1, capacity=1024, t0=0.0, fields=False):
+    def exchange(self, ex, every=1, capacity=1024, t0=0.0, fields=False, halo=None):
         """Record the membrane exchange `ex` (knpemi.exchange.MembraneExchange) on the device in every `every`-th
         step: one launch over the membrane facets of the watched cells on the main stream, directly behind the last
         KNP assembly of the step and before the KNP solve -- the only moment the device holds the new potential, the old
@@ -242,7 +258,12 @@ class DeviceStepper:
         rows it has enqueued and drains the buffer into `ex` (one synchronisation) whenever it holds `capacity` of them,
         and when `ex.series()` is called.  fields: every record also writes the per-facet means (`ex.fields(tag)`
         reads those of the latest record).
-        Partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost facets."""
+
+        halo: this rank's attached halo on a cell-partitioned problem (collective, as `fluxes`): every membrane facet is
+        counted by one rank, every rank records the global row, `step(halo)` records with the same halo and
+        `ex.fields(tag, halo=halo)` reads the local facets.  `ex.budget` then pairs the series with that of
+        `observe(obs, halo=halo)`.
+        Without it, partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost facets."""
         if every < 1 or capacity < 1:
             raise ValueError("every and capacity must be positive")
         if "exchange" in self.taps:
@@ -250,7 +271,7 @@ class DeviceStepper:
         if ex._drain is not None:
             raise RuntimeError("this exchange is attached to a stepper already")
         # offset 1: the record sits inside step k, counted from 0, and carries the time of the step's end
-        self._watched_tap("exchange", "exchange", ex, "membrane exchange", every, capacity, t0, fields, offset=1)
+        self._watched_tap("exchange", "exchange", ex, "membrane exchange", every, capacity, t0, fields, offset=1, halo=halo)
         ex._dt, ex._every = self.dt, int(every)
 
     def check_ode_failures(self):
@@ -293,12 +314,13 @@ class DeviceStepper:
         if halo is not None and "observe" in self.taps and halo is not self._obs_halo:
             raise NotImplementedError("observables attached without a halo are not recorded on partitioned steps: "
                                       "pass halo= to DeviceStepper.observe")
-        if halo is not None and "fluxes" in self.taps:
-            raise NotImplementedError("ion fluxes are not recorded on partitioned steps: a rank's sums would include "
-                                      "its ghost cells")
-        if halo is not None and "exchange" in self.taps:
-            raise NotImplementedError("the membrane exchange is not recorded on partitioned steps: a rank's sums would "
-                                      "include its ghost facets")
+        if halo is not None and "fluxes" in self.taps and halo is not self._tap_halo["fluxes"][0]:
+            raise NotImplementedError("ion fluxes attached without a halo are not recorded on partitioned steps (a "
+                                      "rank's sums would include its ghost cells): pass halo= to DeviceStepper.fluxes")
+        if halo is not None and "exchange" in self.taps and halo is not self._tap_halo["exchange"][0]:
+            raise NotImplementedError("a membrane exchange attached without a halo is not recorded on partitioned steps "
+                                      "(a rank's sums would include its ghost facets): pass halo= to "
+                                      "DeviceStepper.exchange")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
