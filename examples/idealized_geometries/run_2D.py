@@ -97,8 +97,20 @@ def membrane_exchange(s):
     return ex
 
 
+def field_maps(s, threshold):
+    """Per-vertex maps of ECS K+ (peak, time integral, arrival at `threshold`, exposure and excess over it, and the ECS
+    volume beyond it as a series) and peak / trough of phi_M on every cell."""
+    from knpemi import FieldMaps
+    fm = FieldMaps(s.subdomain_list, s.ion_list)
+    fm.watch("K_ecs", "c", tag=0, ion="K", threshold=threshold, stats=("peak", "integral", "threshold"), series=True)
+    for tag in list(s.subdomain_list)[1:]:
+        fm.watch(f"phi_M_{tag}", "phi_M", tag=tag, stats=("peak", "trough"))
+    return fm
+
+
 def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None, series=None,
-                 ode_method="lsoda", ode_substeps=None, events=None, event_threshold=-20e-3, fluxes=None, exchange=None):
+                 ode_method="lsoda", ode_substeps=None, events=None, event_threshold=-20e-3, fluxes=None, exchange=None,
+                 maps=None, maps_threshold=None):
     """series: path of a .npz with the time series at the figures' points (figure_observables), or None.
     ode_method / ode_substeps: the membrane integrator (MembraneModel.set_integrator); the reference's drivers name the
     sub-step count `n_steps_ODE` (run_2D.py:176).
@@ -107,12 +119,18 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
     fluxes: path of a .npz with the series of the ion fluxes and the current density of every sub-domain
     (knpemi.IonFluxes: integrals of the diffusive and the drift part, largest magnitude), or None.
     exchange: path of a .npz with the series of the membrane exchange of cell 1 (knpemi.MembraneExchange: molar flux of
-    every ion out of the cell and into the ECS, capacitive and channel current, per step), or None."""
+    every ion out of the cell and into the ECS, capacitive and channel current, per step), or None.
+    maps: path of a .npz with the field maps (field_maps: per-vertex peak, integral, arrival and exposure of ECS K+ over
+    maps_threshold, in mM -- default: 0.001 mM above the initial ECS concentration, which the ECS next to the stimulated end
+    passes within the first 20 steps -- and peak / trough of phi_M), or None."""
     s = Setup(kind, res, g_syn=g_syn, mesh_data=read_mesh(mesh_file) if mesh_file else None)
     obs = figure_observables(s) if series else None
     ev = membrane_events(s, event_threshold) if events else None
     fl = ion_fluxes(s) if fluxes else None
     ex = membrane_exchange(s) if exchange else None
+    if maps_threshold is None:
+        maps_threshold = float(s.ion_list[0]["c_init"][0]) + 1e-3
+    fm = field_maps(s, maps_threshold) if maps else None
     problem_emi = create_solver_emi(s.a_emi, s.L_emi, s.phi, s.entity_maps, s.subdomain_list, None,
                                     direct=direct, p=s.p_emi, atol=1e-40, rtol=1e-5)
     problem_knp = create_solver_knp(s.a_knp, s.L_knp, s.c, s.entity_maps, s.subdomain_list, None,
@@ -138,6 +156,12 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
             ev.record_host(t, s.phi_M_prev)
         if fl is not None:
             fl.record_host(t, s.phi, s.c_prev)
+        if fm is not None:
+            fm.record_host(t, s.phi, s.c, s.phi_M_prev)
+    if fm is not None:
+        fm.save(maps)
+        for name in fm.watches:
+            print(fm.summary(name))
     if fl is not None:
         fl.save(fluxes)
     if ex is not None:
@@ -156,25 +180,38 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
     return s, num_it_emi, num_it_knp
 
 
-if __name__ == "__main__":
+def build_parser(res=1, steps=10, mesh_script="make_mesh_2D.py"):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--res", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--res", type=int, default=res)
+    ap.add_argument("--steps", type=int, default=steps)
     ap.add_argument("--iterative", action="store_true")
-    ap.add_argument("--mesh-file", default=None, help="XDMF mesh written by make_mesh_2D.py (default: generate)")
+    ap.add_argument("--mesh-file", default=None, help=f"XDMF mesh written by {mesh_script} (default: generate)")
     ap.add_argument("--series", metavar="PATH", default=None, help="time series at the figures' points (.npz)")
     ap.add_argument("--events", metavar="PATH", default=None, help="membrane events of cell 1 per dof (.npz)")
     ap.add_argument("--event-threshold", type=float, default=-20e-3, metavar="V", help="crossing level of --events (V)")
     ap.add_argument("--fluxes", metavar="PATH", default=None, help="series of the ion fluxes of every sub-domain (.npz)")
     ap.add_argument("--exchange", metavar="PATH", default=None,
                     help="series of what every ion carries across the membrane of cell 1 (.npz)")
+    ap.add_argument("--maps", metavar="PATH", default=None,
+                    help="per-vertex maps of ECS K+ (peak, integral, arrival, exposure) and peak / trough of phi_M (.npz)")
+    ap.add_argument("--maps-threshold", type=float, default=None, metavar="MM",
+                    help="level of --maps for ECS K+ in mM (default: 0.001 above the initial concentration)")
     ap.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     ap.add_argument("--ode-substeps", type=int, default=None, help="sub-steps per time step of a fixed-step method (25)")
-    a = ap.parse_args()
+    return ap
+
+
+def recorder_arguments(a):
+    """The recorder options of a parsed command line as keyword arguments of solve_system."""
+    return dict(series=a.series, ode_method=a.ode_method, ode_substeps=a.ode_substeps, events=a.events,
+                event_threshold=a.event_threshold, fluxes=a.fluxes, exchange=a.exchange, maps=a.maps,
+                maps_threshold=a.maps_threshold)
+
+
+if __name__ == "__main__":
+    a = build_parser().parse_args()
     s, it_emi, it_knp = solve_system("2d", a.res, a.steps, direct=not a.iterative, mesh_file=a.mesh_file,
-                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), series=a.series,
-                                     ode_method=a.ode_method, ode_substeps=a.ode_substeps, events=a.events,
-                                     event_threshold=a.event_threshold, fluxes=a.fluxes, exchange=a.exchange)
+                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), **recorder_arguments(a))
     v = s.phi_M_prev[1].x._a
     print(f"phi_M after {a.steps} steps: min {v.min():.6f} V, max {v.max():.6f} V")
     print(f"average number of iterations emi solver: {sum(it_emi) / len(it_emi)}")

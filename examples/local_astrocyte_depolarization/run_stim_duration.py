@@ -276,15 +276,29 @@ def make_exchange(p):
     return ex
 
 
+def make_maps(p, threshold):
+    """Per-vertex maps of the spatial-buffering experiment: peak, time integral, arrival at `threshold` (mM), exposure and
+    excess of ECS K+ with the ECS volume beyond the level as a series, and peak / trough of phi_M of neuron and glia (what
+    results/compare_1D_3D.py:89-105 normalises the glial potential by)."""
+    from knpemi import FieldMaps
+    fm = FieldMaps(p.subdomain_list, p.ion_list)
+    fm.watch("K_ecs", "c", tag=0, ion="K", threshold=threshold, stats=("peak", "integral", "threshold"), series=True)
+    for tag in (1, 2):
+        fm.watch(f"phi_M_{tag}", "phi_M", tag=tag, stats=("peak", "trough"))
+    return fm
+
+
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
                  extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None, events=None,
-                 event_threshold=None, fluxes=None, exchange=None):
+                 event_threshold=None, fluxes=None, exchange=None, maps=None, maps_threshold=None):
     """series: path of a .npz of per-step observables (make_observables), or None.
     events: path of a .npz of the membrane events of neuron and glia (make_events: upward crossings of event_threshold
     per membrane dof, in mV; default: `event_threshold` of the config, else -20), or None.
     fluxes: path of a .npz of the per-step series of the ion fluxes and the current density of every sub-domain
     (make_fluxes), or None.
     exchange: path of a .npz of the per-step series of the membrane exchange of neuron and glia (make_exchange), or None.
+    maps: path of a .npz of the field maps (make_maps; level of ECS K+ maps_threshold in mM, default: `maps_threshold` of
+    the config, else 0.05 above the initial ECS concentration), or None.
     ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator)."""
     p = Problem(config)
     fl = make_fluxes(p) if fluxes else None
@@ -293,6 +307,9 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
     if event_threshold is None:
         event_threshold = float(config.get("event_threshold", -20.0))
     ev = make_events(p, event_threshold) if events else None
+    if maps_threshold is None:
+        maps_threshold = float(config.get("maps_threshold", float(p.c_prev[0][0].x._a.max()) + 0.05))
+    fm = make_maps(p, maps_threshold) if maps else None
     n_total = int(round(config["Tstop"] / float(DT)))
     n_steps = n_total if n_steps is None else min(n_steps, n_total)
     if outdir is None:
@@ -331,6 +348,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             st.fluxes(fl, every=1)
         if ex is not None:
             st.exchange(ex, every=1)
+        if fm is not None:
+            st.track(fm, every=1)
         for k in range(n_steps):
             st.step()
             t = t + DT
@@ -370,6 +389,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
                 ev.record_host(t, p.phi_M_prev)
             if fl is not None:
                 fl.record_host(t, p.phi, p.c_prev)
+            if fm is not None:
+                fm.record_host(t, p.phi, p.c, p.phi_M_prev)
             p.set_source(t)
             if (k % config["save_frequency"]) == 0 or k == n_steps - 1:
                 record(problem_emi.solver.getIterationNumber(), problem_knp.solver.getIterationNumber())
@@ -384,6 +405,11 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         fl.save(fluxes)
     if ex is not None:
         ex.save(exchange)
+    if fm is not None:
+        fm.save(maps)
+        history["maps"] = [fm.summary(name) for name in fm.watches]
+        if not quiet:
+            print("\n".join(history["maps"]))
     if ev is not None:
         ev.save(events)
         # the stimulated end: the membrane point nearest to the centre of the ECS source box
@@ -397,7 +423,7 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
     return p, history
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-c", metavar="config", help="name in config_files/ (or a path to a .yml)", type=str,
                         default="baseline")
@@ -420,11 +446,21 @@ if __name__ == "__main__":
     parser.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     parser.add_argument("--ode-substeps", type=int, default=None,
                         help="sub-steps per time step of a fixed-step method (default 25, the reference's n_steps_ODE)")
-    args = parser.parse_args()
+    parser.add_argument("--maps", metavar="PATH", default=None,
+                        help="write the per-vertex maps of ECS K+ (peak, integral, arrival, exposure) and peak / trough of "
+                             "phi_M of neuron and glia to this .npz")
+    parser.add_argument("--maps-threshold", type=float, default=None, metavar="MM",
+                        help="level of --maps for ECS K+ in mM (default: maps_threshold of the config, else 0.05 above the "
+                             "initial concentration)")
+    return parser
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
     cfg = load_config(args.c)
     _, hist = solve_system(cfg, n_steps=args.steps, device_resident=args.device_resident, direct=args.direct,
                            xdmf=args.xdmf, series=args.series, ode_method=args.ode_method,
                            ode_substeps=args.ode_substeps, events=args.events, event_threshold=args.event_threshold,
-                           fluxes=args.fluxes, exchange=args.exchange)
+                           fluxes=args.fluxes, exchange=args.exchange, maps=args.maps, maps_threshold=args.maps_threshold)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

@@ -550,6 +550,89 @@ knpemi_exchange_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* su
                                 const uint8_t* recorded, int rank, int world, void* xbuf_dev,
                                 int (*allreduce)(void* ctx, int n), void* ctx);
 
+/* Field maps: per vertex of a bulk field, or per membrane dof, the running peak, trough, time integral, arrival time,
+ * exposure and excess over a level, kept on the device over a whole run (knpemi.maps).  The reference's astrocyte study
+ * normalises the glial membrane potential in space by its maximum and minimum over the run
+ * (examples/local_astrocyte_depolarization/results/compare_1D_3D.py:89-105, compare_tort.py:114-130,
+ * make_figures.py:336-352) and plots ECS concentrations in space at chosen times (make_figures.py:135); its users get
+ * such maps by checkpointing every field at every step and post-processing on the host.
+ * A watch is a field -- KNPEMI_F_PHI, KNPEMI_F_C (idx: a solved ion), KNPEMI_F_C_ELIM or KNPEMI_F_PHI_M -- of sub-domain
+ * `sub`, an optional threshold thr, a direction s = +1 ("beyond" = at or above) or -1 (KNPEMI_MAPS_BELOW: at or below)
+ * and a selection of the statistics KNPEMI_MAPS_PEAK, _TROUGH, _INTEGRAL, _THRESHOLD.  Its items are the vertices of
+ * the sub-domain, or the membrane dofs of cell `sub` for phi_M.
+ * State per item after the set-up or a reset: v_prev, v_max, t_max, v_min, t_min, t_arrival are NaN; integral, exposure,
+ * excess and count (int32) are 0.
+ * One record at time t (previous record's time t_prev, D = t - t_prev) with sample v, for each item, in this order:
+ *   v not finite: v_prev <- v.  Nothing else changes.
+ *   v_prev not finite (the first record, or the record after a non-finite sample): no interval is accounted for; peak
+ *     and trough are updated as in step 3; with the threshold statistic and s (v - thr) >= 0: count += 1, and
+ *     t_arrival <- t when count == 1 (a field already beyond the level counts as arrived at the first sight of it);
+ *     v_prev <- v.
+ *   otherwise, with a = s (v_prev - thr) and b = s (v - thr):
+ *     1. integral:  integral += 0.5 D (v_prev + v)   (trapezoid);
+ *     2. threshold, with theta = a / (a - b) where used:
+ *          onset (a < 0 <= b): t_c = t_prev + D theta; count += 1; t_arrival <- t_c when count == 1;
+ *            exposure += (1 - theta) D; excess += 0.5 (1 - theta) D b;
+ *          stays beyond (a >= 0 && b >= 0): exposure += D; excess += 0.5 D (a + b);
+ *          offset (a >= 0 > b): exposure += theta D; excess += 0.5 theta D a;
+ *     3. peak and trough: !(v <= v_max) -> v_max <- v, t_max <- t.  !(v >= v_min) -> v_min <- v, t_min <- t (strict
+ *        improvement, or the first value);
+ *     4. v_prev <- v.
+ * A statistic that is not selected keeps its initial value, has no array and costs no memory traffic.
+ * Series: every watch with KNPEMI_MAPS_SERIES (needs KNPEMI_MAPS_THRESHOLD) contributes two columns per record, in watch
+ * order: the sum of the item weights over the items with s (v - thr) >= 0 (the measure of the region beyond the level)
+ * and the number of such items (a double, exact). */
+#define KNPEMI_MAPS_MAX_WATCH 32
+#define KNPEMI_MAPS_MAX_PER_SPACE 8
+#define KNPEMI_MAPS_PEAK 1
+#define KNPEMI_MAPS_TROUGH 2
+#define KNPEMI_MAPS_INTEGRAL 4
+#define KNPEMI_MAPS_THRESHOLD 8
+#define KNPEMI_MAPS_SERIES 16
+#define KNPEMI_MAPS_BELOW 32
+#define KNPEMI_MAP_V_MAX 0
+#define KNPEMI_MAP_T_MAX 1
+#define KNPEMI_MAP_V_MIN 2
+#define KNPEMI_MAP_T_MIN 3
+#define KNPEMI_MAP_INTEGRAL 4
+#define KNPEMI_MAP_T_ARRIVAL 5
+#define KNPEMI_MAP_EXPOSURE 6
+#define KNPEMI_MAP_EXCESS 7
+#define KNPEMI_MAP_COUNT 8
+/* Set the n_watch watches spec[w] = {field, sub, idx, flags} (1 <= n_watch <= KNPEMI_MAPS_MAX_WATCH, at most
+ * KNPEMI_MAPS_MAX_PER_SPACE on the vertices of one sub-domain or the membrane of one cell) with the levels threshold[w]
+ * (read with KNPEMI_MAPS_THRESHOLD only; may be NULL without one) -- the maps of compare_1D_3D.py:89-105 are peak and
+ * trough of phi_M.  weight: the item weights (lumped nodal measures) of the series watches, concatenated in watch order;
+ * capacity: rows of the series buffer.  Without a series watch both are ignored and no buffer exists.  Replaces any
+ * previous table and puts all state to "before the first record"; a refused call leaves the previous table in place.
+ * KNPEMI_EINVAL: null arguments, an unknown field, sub / idx out of range, phi_M on the ECS, a watch listed twice (the
+ * same spec and level), no statistic, KNPEMI_MAPS_THRESHOLD with a non-finite level, KNPEMI_MAPS_SERIES or
+ * KNPEMI_MAPS_BELOW without KNPEMI_MAPS_THRESHOLD, a series watch with weight == NULL or capacity < 1, too many watches,
+ * a handle of knpemi_ode_create. */
+int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spec, const double* threshold, const double* weight,
+                    int capacity);
+/* Enqueue one record at time t on the main stream (behind the end-of-step update, as knpemi_events_record): ONE launch
+ * over the items of every watched space applies the rules above -- this replaces the per-step checkpoints behind
+ * make_figures.py:336-352 -- and, with a series watch, appends the series row (a full buffer writes nothing and counts
+ * the overflow; sums are formed in a fixed order, two identical runs give identical bits).  KNPEMI_EINVAL before
+ * knpemi_maps_set, and when t is not finite or not greater than the previous record's t. */
+int knpemi_maps_record(knpemi_handle* h, double t);
+/* Synchronise and copy out one map of watch `watch` (its index in knpemi_maps_set): which = KNPEMI_MAP_V_MAX ...
+ * KNPEMI_MAP_EXCESS as n doubles, KNPEMI_MAP_COUNT as n int32; n = the number of items of the watch.  These are the
+ * arrays compare_tort.py:114-130 takes the maximum and minimum of over all checkpoints.  KNPEMI_EINVAL before
+ * knpemi_maps_set, for a bad watch, which or length, and for a statistic that was not selected. */
+int knpemi_maps_read(knpemi_handle* h, int watch, int which, void* host, size_t n);
+/* Synchronise and copy out min(n_rows, device row count) rows of the series (the region beyond the level over time, read
+ * off the frames of make_figures.py:135 in the reference), the device row count and the overflow count; reset != 0
+ * empties the buffer afterwards.  KNPEMI_EINVAL before knpemi_maps_set and without a series watch. */
+int knpemi_maps_series_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
+/* All state back to "before the first record", the series rewound (a second run from the same start; the reference
+ * would delete the checkpoints of compare_1D_3D.py:89-105); the table stays.  Enqueue only. */
+int knpemi_maps_reset(knpemi_handle* h);
+/* Drop the table, the state and the buffer (knpemi_maps_record then fails with KNPEMI_EINVAL; the maps of
+ * make_figures.py:336-352 are no longer kept); knpemi_destroy does the same. */
+int knpemi_maps_clear(knpemi_handle* h);
+
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop
  *   (run_3D.py:356,362); with this option the write-back kernel of knpemi_solve_knp -- and of

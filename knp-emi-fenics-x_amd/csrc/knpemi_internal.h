@@ -156,6 +156,37 @@ struct KnWatchTab {
   uint8_t col_watch[KN_WATCH_MAXCOLS], col_slot[KN_WATCH_MAXCOLS], col_max[KN_WATCH_MAXCOLS];
 };
 
+// Table of the field maps (kernels_maps.hip), read by the record and the reset kernel.  Watches are grouped by space: the
+// vertices of a sub-domain, or the membrane dofs of a cell.  Workgroup b belongs to space p with bstart[p] <= b <
+// bstart[p + 1] and takes 256 consecutive items of its n_items[p]; a lane serves the watches wstart[p] .. wstart[p + 1] - 1
+// of its item.  A bulk lane reads slots 3 .. 7 of its vertex record (vertex first[p] + item) once when need_rec[p]; a watch
+// with dense == NULL takes slot `slot` of it, any other reads dense[item] (the solver's c, phi_M).  State arrays are
+// per watch, [n_items] each, NULL where the statistic is not selected (v_prev: with the integral or the threshold only --
+// peak and trough do not depend on it).  A series watch has the item weights `weight` and the slots 2 j, 2 j + 1 (measure, n)
+// of its workgroups' partials, j its number among the series watches of the space; column q of the row folds slot
+// col_slot[q] over the workgroups of space col_space[q].
+#define KN_MAPS_MAXSPACE (2 * KN_MAXSUB)
+#define KN_MAPS_SLOTS (2 * KNPEMI_MAPS_MAX_PER_SPACE)
+#define KN_MAPS_MAXCOLS (2 * KNPEMI_MAPS_MAX_WATCH)
+struct KnMapWatch {
+  const double* dense;
+  int slot, flags, ser;          // ser: j of a series watch, else -1
+  double thr, sgn;
+  double *v_prev, *v_max, *t_max, *v_min, *t_min, *integral, *t_arrival, *exposure, *excess;
+  int* count;
+  const double* weight;
+};
+struct KnMapTab {
+  int n_space, n_watch, n_cols;
+  int bstart[KN_MAPS_MAXSPACE + 1];
+  int wstart[KN_MAPS_MAXSPACE + 1];
+  int n_items[KN_MAPS_MAXSPACE];
+  int first[KN_MAPS_MAXSPACE];
+  int need_rec[KN_MAPS_MAXSPACE];
+  uint8_t col_space[KN_MAPS_MAXCOLS], col_slot[KN_MAPS_MAXCOLS];
+  KnMapWatch w[KNPEMI_MAPS_MAX_WATCH];
+};
+
 struct KnOdeModel {
   int bound = 0, sub = 0, model_id = -1, n_states = 0, n_params = 0, nq = 0;
   double* d_states = nullptr;   // [n_states][nq]
@@ -634,6 +665,20 @@ struct knpemi_handle : KnDevice {
     void* ctx = nullptr;
     std::vector<void*> allocs;
   } flux, exchange;
+  // field maps (knpemi_maps_set, kernels_maps.hip): per-item state arrays of every watch and, with a series watch, workgroup
+  // partials and a series
+  struct KnMaps {
+    int n_watch = 0, n_blk = 0;
+    bool have_prev = false;              // a record has been enqueued since the set-up / the last reset ...
+    double t_prev = 0.0;                 // ... at this time
+    KnMapTab host{};                     // the table as uploaded
+    int slot_of[KNPEMI_MAPS_MAX_WATCH] = {};   // watch of knpemi_maps_set -> entry of the table (grouped by space)
+    int items_of[KNPEMI_MAPS_MAX_WATCH] = {};  // ... and its number of items
+    KnMapTab* tab = nullptr;
+    double* part = nullptr;              // [n_blk][KN_MAPS_SLOTS] workgroup partials (series watches only)
+    KnSeries ser;
+    std::vector<void*> allocs;
+  } maps;
   int knp_flags = 0;                   // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
 };
 
@@ -669,6 +714,8 @@ int kn_launch_record_combine(knpemi_handle* h, const char* who, int n_cols, int 
                              const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows);
 int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev);
 int kn_launch_events_reset(knpemi_handle* h);
+int kn_launch_maps_record(knpemi_handle* h, double t, double t_prev);
+int kn_launch_maps_reset(knpemi_handle* h);
 int kn_launch_flux(knpemi_handle* h, int write_fields);
 int kn_launch_exchange(knpemi_handle* h, int write_fields);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);

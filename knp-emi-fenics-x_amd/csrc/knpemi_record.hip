@@ -1,5 +1,6 @@
 // The on-device recorders behind the C ABI (include/knpemi_hip.h): observables (kernels_observe.hip), membrane events
-// (kernels_events.hip), ion fluxes per cell (kernels_flux.hip) and the membrane exchange per cell (kernels_exchange.hip).
+// (kernels_events.hip), ion fluxes per cell (kernels_flux.hip), the membrane exchange per cell (kernels_exchange.hip) and
+// the field maps (kernels_maps.hip: per-item maps as the events, and a series with a series watch).
 //
 // Three of them append rows to a series buffer (KnSeries; the device side is record_tail.h).  The fluxes and the exchange
 // are one recorder over different items -- the cells of a watched sub-domain, the membrane facets of a watched cell: they
@@ -73,7 +74,7 @@ int recorder_clear(knpemi_handle* h, R knpemi_handle::*which) {
 }  // namespace
 
 void kn_record_free(knpemi_handle* h) {
-  for (auto* a : {&h->obs.allocs, &h->events.allocs, &h->flux.allocs, &h->exchange.allocs}) kn_free_all(*a);
+  for (auto* a : {&h->obs.allocs, &h->events.allocs, &h->flux.allocs, &h->exchange.allocs, &h->maps.allocs}) kn_free_all(*a);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -546,3 +547,198 @@ extern "C" int knpemi_flux_reset(knpemi_handle* h) { return watched_reset(h, FLU
 extern "C" int knpemi_exchange_reset(knpemi_handle* h) { return watched_reset(h, EXCHANGE); }
 extern "C" int knpemi_flux_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::flux); }
 extern "C" int knpemi_exchange_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::exchange); }
+
+// ---------------------------------------------------------------------------------------------------
+// field maps (kernels_maps.hip)
+// ---------------------------------------------------------------------------------------------------
+extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spec, const double* threshold,
+                               const double* weight, int capacity) {
+  const std::string fn = "knpemi_maps_set";
+  if (!h || !spec) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_watch < 1 || n_watch > KNPEMI_MAPS_MAX_WATCH) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAPS_MAX_WATCH watches");
+  const int all = KNPEMI_MAPS_PEAK | KNPEMI_MAPS_TROUGH | KNPEMI_MAPS_INTEGRAL | KNPEMI_MAPS_THRESHOLD;
+  // the space of a watch: the vertices of sub-domain s (s), or the membrane dofs of cell s (KN_MAXSUB + s)
+  int space[KNPEMI_MAPS_MAX_WATCH], per_space[KN_MAPS_MAXSPACE] = {};
+  KnFieldLoc loc[KNPEMI_MAPS_MAX_WATCH];
+  bool any_series = false;
+  for (int w = 0; w < n_watch; ++w) {
+    const int32_t field = spec[4 * w], sub = spec[4 * w + 1], ix = spec[4 * w + 2], fl = spec[4 * w + 3];
+    const std::string who = fn + ": watch " + std::to_string(w);
+    if (field != KNPEMI_F_PHI && field != KNPEMI_F_C && field != KNPEMI_F_C_ELIM && field != KNPEMI_F_PHI_M)
+      return kn_fail(KNPEMI_EINVAL, who + ": unknown field (phi, c, the eliminated ion's c or phi_M)");
+    if (int rc = kn_locate(h, field, sub, ix, &loc[w])) return rc;      // sub / idx out of range, phi_M on the ECS
+    if (loc[w].n > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, who + ": too many items");
+    if (fl & ~(all | KNPEMI_MAPS_SERIES | KNPEMI_MAPS_BELOW)) return kn_fail(KNPEMI_EINVAL, who + ": unknown flag bits");
+    if (!(fl & all)) return kn_fail(KNPEMI_EINVAL, who + ": no statistic selected");
+    if (!(fl & KNPEMI_MAPS_THRESHOLD) && (fl & (KNPEMI_MAPS_SERIES | KNPEMI_MAPS_BELOW)))
+      return kn_fail(KNPEMI_EINVAL, who + ": a series and the direction need the threshold statistic");
+    if (fl & KNPEMI_MAPS_THRESHOLD) {
+      if (!threshold) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+      if (!std::isfinite(threshold[w])) return kn_fail(KNPEMI_EINVAL, who + ": the threshold is not finite");
+    }
+    if (fl & KNPEMI_MAPS_SERIES) {
+      any_series = true;
+      if (!weight) return kn_fail(KNPEMI_EINVAL, fn + ": null argument (a series watch needs the item weights)");
+      if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive with a series watch");
+    }
+    for (int u = 0; u < w; ++u)
+      if (std::equal(spec + 4 * u, spec + 4 * u + 4, spec + 4 * w)
+          && (!(fl & KNPEMI_MAPS_THRESHOLD) || threshold[u] == threshold[w]))
+        return kn_fail(KNPEMI_EINVAL, who + " is listed twice");
+    space[w] = field == KNPEMI_F_PHI_M ? KN_MAXSUB + sub : sub;
+    if (++per_space[space[w]] > KNPEMI_MAPS_MAX_PER_SPACE)
+      return kn_fail(KNPEMI_EINVAL, fn + ": more than KNPEMI_MAPS_MAX_PER_SPACE watches on one space");
+  }
+  // the table, grouped by space; nothing of the previous recorder is touched before every allocation has succeeded
+  knpemi_handle::KnMaps N;
+  KnMapTab& T = N.host;
+  std::vector<size_t> w_off(n_watch, 0);      // a series watch's place in `weight`
+  {
+    size_t o = 0;
+    for (int w = 0; w < n_watch; ++w)
+      if (spec[4 * w + 3] & KNPEMI_MAPS_SERIES) { w_off[w] = o; o += loc[w].n; }
+  }
+  KN_HIP(hipSetDevice(h->device));
+  int k = 0, col_of[KNPEMI_MAPS_MAX_WATCH];
+  std::fill(col_of, col_of + KNPEMI_MAPS_MAX_WATCH, -1);
+  for (int sp = 0; sp < KN_MAPS_MAXSPACE; ++sp) {
+    if (!per_space[sp]) continue;
+    const int p = T.n_space++;
+    const bool mem = sp >= KN_MAXSUB;
+    const int sub = mem ? sp - KN_MAXSUB : sp;
+    T.n_items[p] = mem ? h->n_q[sub] : h->n_vert[sub];
+    T.first[p] = mem ? 0 : h->voff[sub];
+    T.bstart[p + 1] = T.bstart[p] + (T.n_items[p] + 255) / 256;
+    T.wstart[p] = k;
+    int n_ser = 0;
+    for (int w = 0; w < n_watch; ++w) {
+      if (space[w] != sp) continue;
+      const int fl = spec[4 * w + 3];
+      const size_t n = loc[w].n;
+      KnMapWatch& W = T.w[k];
+      W = KnMapWatch{};
+      if (loc[w].stride == 1) {
+        W.dense = loc[w].base;
+      } else {      // a slot of the vertex records: every read of the kernel stays inside the record of a vertex of `sub`
+        W.slot = (int)((loc[w].base - h->dev.VR) % KN_REC);
+        if (loc[w].stride != KN_REC || W.slot < 3 || n != (size_t)T.n_items[p])
+          return kn_free_all(N.allocs), kn_fail(KNPEMI_EINVAL, fn + ": field layout not understood");
+        T.need_rec[p] = 1;
+      }
+      if (n != (size_t)T.n_items[p]) return kn_free_all(N.allocs), kn_fail(KNPEMI_EINVAL, fn + ": field length is not the space's");
+      W.flags = fl;
+      W.ser = -1;
+      W.thr = (fl & KNPEMI_MAPS_THRESHOLD) ? threshold[w] : 0.0;
+      W.sgn = (fl & KNPEMI_MAPS_BELOW) ? -1.0 : 1.0;
+      int rc = KNPEMI_OK;
+      auto want = [&](bool on, auto** out) { if (on && !rc) rc = kn_alloc(N.allocs, n, out); };
+      want(fl & (KNPEMI_MAPS_INTEGRAL | KNPEMI_MAPS_THRESHOLD), &W.v_prev);
+      want(fl & KNPEMI_MAPS_PEAK, &W.v_max); want(fl & KNPEMI_MAPS_PEAK, &W.t_max);
+      want(fl & KNPEMI_MAPS_TROUGH, &W.v_min); want(fl & KNPEMI_MAPS_TROUGH, &W.t_min);
+      want(fl & KNPEMI_MAPS_INTEGRAL, &W.integral);
+      want(fl & KNPEMI_MAPS_THRESHOLD, &W.t_arrival); want(fl & KNPEMI_MAPS_THRESHOLD, &W.exposure);
+      want(fl & KNPEMI_MAPS_THRESHOLD, &W.excess); want(fl & KNPEMI_MAPS_THRESHOLD, &W.count);
+      if (!rc && (fl & KNPEMI_MAPS_SERIES)) {
+        W.ser = n_ser++;
+        double* dw = nullptr;
+        rc = kn_upload(N.allocs, weight + w_off[w], n, &dw);
+        W.weight = dw;
+      }
+      if (rc) return kn_free_all(N.allocs), rc;
+      N.slot_of[w] = k;
+      N.items_of[w] = (int)n;
+      col_of[w] = W.ser;
+      ++k;
+    }
+    T.wstart[p + 1] = k;
+  }
+  T.n_watch = n_watch;
+  for (int w = 0; w < n_watch; ++w) {      // the columns, in the order of the watches as given
+    if (col_of[w] < 0) continue;
+    int p = 0;
+    while (N.slot_of[w] >= T.wstart[p + 1]) ++p;
+    for (int j = 0; j < 2; ++j) {
+      T.col_space[T.n_cols] = (uint8_t)p;
+      T.col_slot[T.n_cols++] = (uint8_t)(2 * col_of[w] + j);
+    }
+  }
+  N.n_watch = n_watch;
+  N.n_blk = T.bstart[T.n_space];
+  int rc = kn_upload(N.allocs, &T, 1, &N.tab);
+  if (!rc && any_series) {
+    rc = kn_alloc(N.allocs, (size_t)N.n_blk * KN_MAPS_SLOTS, &N.part);
+    if (!rc) rc = series_alloc(N.allocs, h->stream, capacity, T.n_cols, &N.ser);
+  }
+  if (rc) return kn_free_all(N.allocs), rc;
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  recorder_free(h->maps);
+  h->maps = N;
+  if ((rc = kn_launch_maps_reset(h))) { recorder_free(h->maps); return rc; }
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_maps_record(knpemi_handle* h, double t) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& M = h->maps;
+  if (M.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_maps_record: no maps set (knpemi_maps_set)");
+  if (!std::isfinite(t) || (M.have_prev && !(t > M.t_prev)))
+    return kn_fail(KNPEMI_EINVAL, "knpemi_maps_record: t must be finite and greater than the previous record's");
+  KN_HIP(hipSetDevice(h->device));
+  // the first record's interval is never used: every v_prev is NaN then
+  if (int rc = kn_launch_maps_record(h, t, M.have_prev ? M.t_prev : t)) return rc;
+  M.have_prev = true;
+  M.t_prev = t;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_maps_read(knpemi_handle* h, int watch, int which, void* host, size_t n) {
+  const std::string fn = "knpemi_maps_read";
+  if (!h || !host) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  auto& M = h->maps;
+  if (M.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": no maps set (knpemi_maps_set)");
+  if (watch < 0 || watch >= M.n_watch) return kn_fail(KNPEMI_EINVAL, fn + ": bad watch index");
+  const KnMapWatch& W = M.host.w[M.slot_of[watch]];
+  const double* d = nullptr;
+  switch (which) {
+    case KNPEMI_MAP_V_MAX: d = W.v_max; break;
+    case KNPEMI_MAP_T_MAX: d = W.t_max; break;
+    case KNPEMI_MAP_V_MIN: d = W.v_min; break;
+    case KNPEMI_MAP_T_MIN: d = W.t_min; break;
+    case KNPEMI_MAP_INTEGRAL: d = W.integral; break;
+    case KNPEMI_MAP_T_ARRIVAL: d = W.t_arrival; break;
+    case KNPEMI_MAP_EXPOSURE: d = W.exposure; break;
+    case KNPEMI_MAP_EXCESS: d = W.excess; break;
+    case KNPEMI_MAP_COUNT: break;
+    default: return kn_fail(KNPEMI_EINVAL, fn + ": which is KNPEMI_MAP_V_MAX ... KNPEMI_MAP_COUNT");
+  }
+  if (which == KNPEMI_MAP_COUNT ? !W.count : !d) return kn_fail(KNPEMI_EINVAL, fn + ": this statistic of the watch was not selected");
+  if (n != (size_t)M.items_of[watch]) return kn_fail(KNPEMI_EINVAL, fn + ": length is not the number of items of the watch");
+  KN_HIP(hipSetDevice(h->device));
+  if (n == 0) return KNPEMI_OK;
+  if (which == KNPEMI_MAP_COUNT) return kn_to_host(h->stream, static_cast<int*>(host), (const int*)W.count, n);
+  return kn_to_host(h->stream, static_cast<double*>(host), d, n);
+}
+
+extern "C" int knpemi_maps_series_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow,
+                                       int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& M = h->maps;
+  if (M.n_watch != 0 && M.host.n_cols == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_maps_series_read: no watch has a series");
+  return series_read(h, M.ser, M.n_watch != 0, "knpemi_maps_series_read", "no maps set (knpemi_maps_set)", n_rows, out, rows,
+                     overflow, reset);
+}
+
+extern "C" int knpemi_maps_reset(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& M = h->maps;
+  if (M.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_maps_reset: no maps set (knpemi_maps_set)");
+  KN_HIP(hipSetDevice(h->device));
+  M.have_prev = false;
+  M.t_prev = 0.0;
+  if (M.host.n_cols > 0)
+    if (int rc = series_rewind(h, M.ser)) return rc;
+  return kn_launch_maps_reset(h);
+}
+
+extern "C" int knpemi_maps_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::maps); }

@@ -30,6 +30,9 @@ OPT_FUSE_UPDATE, OPT_FUSE_MEMBRANE, OPT_PROFILE_STRIDE, OPT_KNP_MIN_IT, OPT_FOLD
 OPT_EMI_NORM = 7
 OBS_SUM, OBS_MIN, OBS_MAX = 0, 1, 2
 EVENTS_MAX_KEEP = 64
+MAPS_MAX_WATCH, MAPS_MAX_PER_SPACE = 32, 8
+MAPS_PEAK, MAPS_TROUGH, MAPS_INTEGRAL, MAPS_THRESHOLD, MAPS_SERIES, MAPS_BELOW = 1, 2, 4, 8, 16, 32
+MAP_V_MAX, MAP_T_MAX, MAP_V_MIN, MAP_T_MIN, MAP_INTEGRAL, MAP_T_ARRIVAL, MAP_EXPOSURE, MAP_EXCESS, MAP_COUNT = range(9)
 K_ODE, K_EMI_ROWS, K_KNP_ROWS, K_KNP_MEMBRANE, K_UPDATE, K_EMI_MEMBRANE = range(6)
 KERNEL_NAMES = ["ode_step_kernel", "emi_rows_kernel", "knp_rows_kernel", "knp_membrane_kernel", "update_pde_kernel",
                 "emi_membrane_rhs_kernel"]
@@ -185,6 +188,13 @@ SIGNATURES = {
     "knpemi_exchange_clear": (C.c_int, [C.c_void_p]),
     "knpemi_exchange_set_partitioned": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_int, c_u8_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "knpemi_maps_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_dbl_p, C.c_int]),
+    "knpemi_maps_record": (C.c_int, [C.c_void_p, C.c_double]),
+    "knpemi_maps_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "knpemi_maps_series_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                          C.c_int]),
+    "knpemi_maps_reset": (C.c_int, [C.c_void_p]),
+    "knpemi_maps_clear": (C.c_int, [C.c_void_p]),
     "knpemi_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "knpemi_trace": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_halo_width": (C.c_int, [C.c_void_p, C.c_int]),

@@ -84,7 +84,8 @@ class DeviceStepper:
         self.flags_emi = L.WANT_P | (0 if a.splitting_scheme else L.NO_SPLITTING)
         self.flags_knp = 0 if a.splitting_scheme else L.NO_SPLITTING
         # the attached recorders (knpemi.recording.Tap) by the method that attached them: "exchange" records behind the
-        # last KNP assembly of a step, "observe", "detect" and "fluxes", in this order, behind the end-of-step update
+        # last KNP assembly of a step, "observe", "detect", "fluxes" and "track", in this order, behind the end-of-step
+        # update
         self.taps = {}
         self._obs_halo = None      # the halo of a partitioned observe
         self._tap_halo = {}        # "fluxes" / "exchange": the halo they were attached with, and what the handle refers to
@@ -274,6 +275,33 @@ class DeviceStepper:
         self._watched_tap("exchange", "exchange", ex, "membrane exchange", every, capacity, t0, fields, offset=1, halo=halo)
         ex._dt, ex._every = self.dt, int(every)
 
+    # -- field maps -----------------------------------------------------------------------------------
+    def track(self, fm, every=1, capacity=1024, t0=0.0):
+        """Record the field maps `fm` (knpemi.maps.FieldMaps) on the device after every `every`-th step, at time
+        t0 + k dt for step k: one launch over the items of every watched space on the main stream, behind the end-of-step
+        update and the other recorders, nothing synchronised; `fm.maps(name)` reads the maps back.  With a series watch
+        the launch also appends a row to a device buffer of `capacity` rows, drained into `fm` as the other series are
+        (whenever it holds `capacity` rows, and when `fm.series()` is called); without one there is no buffer.
+        Works unchanged on a cell-partitioned problem (`step(halo)`) without a series watch: the kernel needs no halo,
+        every rank holds the maps of its local items, and `fm.maps(name, halo=halo)` selects the owned ones.  With a
+        series watch partitioned steps are refused: a rank's sums would include its ghost items."""
+        if every < 1 or capacity < 1:
+            raise ValueError("every and capacity must be positive")
+        if "track" in self.taps:
+            raise RuntimeError("this stepper records field maps already")
+        if fm._drain is not None:
+            raise RuntimeError("these maps are attached to a stepper already")
+        fm._attach(self.dp, capacity)
+        fm.reset_host()
+        lib, h = self.lib, self.dp.h
+
+        def rewind():
+            L.check(lib.knpemi_maps_reset(h))
+            fm.reset_host()
+        read = self._reader(lib.knpemi_maps_series_read) if fm.has_series else None
+        self.taps["track"] = Tap(fm, "field maps", every, lambda t, fields: L.check(lib.knpemi_maps_record(h, t)), t0,
+                                 capacity=capacity if read else None, read=read, n_cols=fm.n_cols, rewind=rewind)
+
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
         failed on any membrane dof since the last check (the counters live on the device; this synchronises)."""
@@ -321,6 +349,9 @@ class DeviceStepper:
             raise NotImplementedError("a membrane exchange attached without a halo is not recorded on partitioned steps "
                                       "(a rank's sums would include its ghost facets): pass halo= to "
                                       "DeviceStepper.exchange")
+        if halo is not None and "track" in self.taps and self.taps["track"].target.has_series:
+            raise NotImplementedError("field maps with a series watch are not recorded on partitioned steps (a rank's "
+                                      "sums would include its ghost items): track maps without series=True")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
@@ -402,7 +433,8 @@ class DeviceStepper:
         # On the main stream behind the end-of-step update (update_pde_kernel or the fused KNP write-back); the next
         # step's side-stream launches fork from the main stream after it (ev_fork), so none of them overtakes these: the
         # observables' launch, the events' over the membrane dofs, the fluxes' over the cells of the watched sub-domains.
-        for name in ("observe", "detect", "fluxes"):
+        # the field maps' over the items of the watched spaces.
+        for name in ("observe", "detect", "fluxes", "track"):
             if name in self.taps:
                 self.taps[name].tick(self.k, self.dt)
 
