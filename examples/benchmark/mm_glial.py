@@ -79,6 +79,48 @@ def rhs(t, states, values, parameters):
     return values
 
 
+# What the right-hand side computes on its way, by name: the monitored quantities of this model (the set the glial model
+# shipped inside the library hands out), in the order of `monitored`.
+MONITOR_NAMES = ["E_Na", "E_K", "E_Cl", "i_pump", "g_Kir", "i_Kir", "i_Na_leak", "i_Cl_leak", "I_Na", "I_K", "I_Cl"]
+
+
+def monitor(states, t, parameters, monitored):
+    """The named intermediates of `rhs` above at (t, states, parameters), Gotran's `monitor` signature.  MembraneModel
+    translates this text into the device function of the model's monitor program (knpemi.rhs_codegen)."""
+    (psi, g_leak_Cl, g_leak_Na, g_leak_K, _z_Na, z_K, z_Cl, _Cm, _stim, _iNa, _iK, _iCl, K_e, K_i, Na_e, Na_i, Cl_e,
+     Cl_i, m_K, m_Na, I_max) = parameters
+    V = states[0]
+    E_Na = 1 / psi * 1 / z_K * math.log(Na_e / Na_i)
+    E_K = 1 / psi * 1 / z_K * math.log(K_e / K_i)
+    E_Cl = 1 / psi * 1 / z_Cl * math.log(Cl_e / Cl_i)
+    K_e_init, K_i_init = 3.092970607490389, 99.3100014897692
+    i_pump = I_max * (K_e / (K_e + m_K)) * (Na_i ** 1.5 / (Na_i ** 1.5 + m_Na ** 1.5))
+    E_K_init = 1 / psi * math.log(K_e_init / K_i_init)
+    dphi = V - E_K
+    A = 1 + math.exp(18.4 / 42.4)
+    B = 1 + math.exp(-(0.1186e3 + E_K_init) / 0.0441e3)
+    Cc = 1 + math.exp((dphi + 0.0185e3) / 0.0425e3)
+    D = 1 + math.exp(-(0.1186e3 + V) / 0.0441e3)
+    g_Kir = math.sqrt(K_e / K_e_init) * (A * B) / (Cc * D)
+    i_Kir = g_leak_K * g_Kir * (V - E_K)
+    monitored[0] = E_Na
+    monitored[1] = E_K
+    monitored[2] = E_Cl
+    monitored[3] = i_pump
+    monitored[4] = g_Kir
+    monitored[5] = i_Kir
+    monitored[6] = g_leak_Na * (V - E_Na)
+    monitored[7] = g_leak_Cl * (V - E_Cl)
+    monitored[8] = g_leak_Na * (V - E_Na) + 3 * i_pump
+    monitored[9] = i_Kir - 2 * i_pump
+    monitored[10] = g_leak_Cl * (V - E_Cl)
+    return monitored
+
+
+def monitor_indices(*monitored):
+    return _indices(MONITOR_NAMES, monitored, "monitored")
+
+
 def _init(names, defaults, overrides, what):
     out = np.array([defaults.get(n, 0.0) for n in names], dtype=np.float64)
     for name, value in overrides.items():

@@ -8,6 +8,7 @@ drivers' parameter blocks take.
     python run_calibration.py                                 # every shipped model
     python run_calibration.py --model hh_mv --history hist.npz
     python run_calibration.py --model glial --sweep K_e=3:12:64 --out sweep.npz
+    python run_calibration.py --model glial --currents        # Kir, pump and leak currents of the rest state
 
 `--sweep NAME=lo:hi:n` gives parameter NAME n values from lo to hi, one per node, and writes one rest state per value.
 """
@@ -125,6 +126,9 @@ def main(argv=None):
     ap.add_argument("--method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda",
                     help="membrane integrator (MembraneModel.set_integrator)")
     ap.add_argument("--substeps", type=int, default=None, help="sub-steps per step of a fixed-step method (default 25)")
+    ap.add_argument("--currents", action="store_true",
+                    help="print the currents by mechanism, the Nernst potentials and the conductances of the rest state "
+                         "(MembraneModel.monitor; shipped models)")
     a = ap.parse_args(argv)
     names = a.model or sorted(MODELS)
     sweep = None
@@ -144,6 +148,12 @@ def main(argv=None):
             row = membrane.states[0]
             for s in state_names(module):
                 print(f"{s}_init = {float(row[module.state_indices(s)])!r}")
+            if a.currents:      # what the reference's run_calibration.py:148-212 plots over the run: here at its end
+                if membrane.monitor_names():
+                    for q, v in membrane.monitor().items():
+                        print(f"{q} = {float(v[0])!r}")
+                else:
+                    print(f"# {name}: the model brings no monitor", file=sys.stderr)
         else:
             fn = a.out if len(names) == 1 else f"{os.path.splitext(a.out)[0]}_{name}.npz"
             np.savez(fn, **{sweep[0]: sweep[1]}, states=membrane.states, steps_taken=steps,

@@ -108,9 +108,29 @@ def field_maps(s, threshold):
     return fm
 
 
+def membrane_monitors(s):
+    """The monitored quantities of the membrane model of cell 1 (Nernst potentials, conductances, currents by mechanism,
+    gates) at the figures' membrane point -- make_figures.py:146-149 of the reference re-derives E_Na and E_K there from
+    checkpoints -- and their average, minimum and maximum over the membrane."""
+    from knpemi import MembraneMonitor
+    mon = MembraneMonitor(s.subdomain_list, s.ion_list, ft=s.ft)
+    mon.watch(1)
+    mon.point("mem", 1, np.array(FIGURE_POINTS[s.mesh.gdim]["mem"]) * 1e-6)
+    for op in ("average", "min", "max"):
+        mon.reduce(op, 1, op=op)
+    return mon
+
+
+def monitor_state(s):
+    """What MembraneMonitor.record_host takes at the end of a step: the concentrations the next sweep's traces are taken
+    from, and phi_M; the tables are the models' own."""
+    return dict(c={t: list(s.c_prev[t]) + [s.ion_list[-1][f"c_{t}"]] for t in s.subdomain_list},
+                phi_M={t: s.phi_M_prev[t] for t in list(s.subdomain_list)[1:]})
+
+
 def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None, series=None,
                  ode_method="lsoda", ode_substeps=None, events=None, event_threshold=-20e-3, fluxes=None, exchange=None,
-                 maps=None, maps_threshold=None):
+                 maps=None, maps_threshold=None, monitor=None):
     """series: path of a .npz with the time series at the figures' points (figure_observables), or None.
     ode_method / ode_substeps: the membrane integrator (MembraneModel.set_integrator); the reference's drivers name the
     sub-step count `n_steps_ODE` (run_2D.py:176).
@@ -122,7 +142,8 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
     every ion out of the cell and into the ECS, capacitive and channel current, per step), or None.
     maps: path of a .npz with the field maps (field_maps: per-vertex peak, integral, arrival and exposure of ECS K+ over
     maps_threshold, in mM -- default: 0.001 mM above the initial ECS concentration, which the ECS next to the stimulated end
-    passes within the first 20 steps -- and peak / trough of phi_M), or None."""
+    passes within the first 20 steps -- and peak / trough of phi_M), or None.
+    monitor: path of a .npz with the series of the membrane monitors (membrane_monitors), or None."""
     s = Setup(kind, res, g_syn=g_syn, mesh_data=read_mesh(mesh_file) if mesh_file else None)
     obs = figure_observables(s) if series else None
     ev = membrane_events(s, event_threshold) if events else None
@@ -131,6 +152,7 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
     if maps_threshold is None:
         maps_threshold = float(s.ion_list[0]["c_init"][0]) + 1e-3
     fm = field_maps(s, maps_threshold) if maps else None
+    mon = membrane_monitors(s) if monitor else None
     problem_emi = create_solver_emi(s.a_emi, s.L_emi, s.phi, s.entity_maps, s.subdomain_list, None,
                                     direct=direct, p=s.p_emi, atol=1e-40, rtol=1e-5)
     problem_knp = create_solver_knp(s.a_knp, s.L_knp, s.c, s.entity_maps, s.subdomain_list, None,
@@ -158,6 +180,10 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
             fl.record_host(t, s.phi, s.c_prev)
         if fm is not None:
             fm.record_host(t, s.phi, s.c, s.phi_M_prev)
+        if mon is not None:
+            mon.record_host(t, monitor_state(s))
+    if mon is not None:
+        mon.save(monitor)
     if fm is not None:
         fm.save(maps)
         for name in fm.watches:
@@ -196,6 +222,8 @@ def build_parser(res=1, steps=10, mesh_script="make_mesh_2D.py"):
                     help="per-vertex maps of ECS K+ (peak, integral, arrival, exposure) and peak / trough of phi_M (.npz)")
     ap.add_argument("--maps-threshold", type=float, default=None, metavar="MM",
                     help="level of --maps for ECS K+ in mM (default: 0.001 above the initial concentration)")
+    ap.add_argument("--monitor", metavar="PATH", default=None,
+                    help="series of the membrane model's monitored quantities at the membrane point and over the membrane (.npz)")
     ap.add_argument("--ode-method", choices=["lsoda", "euler", "rk4", "rush_larsen"], default="lsoda")
     ap.add_argument("--ode-substeps", type=int, default=None, help="sub-steps per time step of a fixed-step method (25)")
     return ap
@@ -205,7 +233,7 @@ def recorder_arguments(a):
     """The recorder options of a parsed command line as keyword arguments of solve_system."""
     return dict(series=a.series, ode_method=a.ode_method, ode_substeps=a.ode_substeps, events=a.events,
                 event_threshold=a.event_threshold, fluxes=a.fluxes, exchange=a.exchange, maps=a.maps,
-                maps_threshold=a.maps_threshold)
+                maps_threshold=a.maps_threshold, monitor=a.monitor)
 
 
 if __name__ == "__main__":

@@ -288,9 +288,31 @@ def make_maps(p, threshold):
     return fm
 
 
+def make_monitors(p):
+    """The monitored quantities of the membrane models at the membrane facet of the neuron and of the glial cell closest to
+    the mesh's centre, and their averages over the two membranes.  The glial point carries E_K, E_Na, E_Cl, i_Kir and
+    i_pump: the five text files the reference's make_figures.py:279-327 derives from checkpoints of every step."""
+    from knpemi import MembraneMonitor
+    mon = MembraneMonitor(p.subdomain_list, p.ion_list, ft=p.ft)
+    centre = 0.5 * (p.mesh.x.min(axis=0) + p.mesh.x.max(axis=0))
+    for tag, name in ((1, "neuron"), (2, "glia")):
+        mem = p.subdomain_list[tag]["mesh_mem"]
+        xc = mem.x[mem.cells].mean(axis=1)
+        mon.watch(tag)
+        mon.point(name, tag, xc[np.argmin(np.linalg.norm(xc - centre, axis=1))])
+        mon.reduce(f"{name}_mean", tag, op="average")
+    return mon
+
+
+def monitor_state(p):
+    """What MembraneMonitor.record_host takes at the end of a step of the host loop."""
+    return dict(c={t: list(p.c_prev[t]) + [p.ion_list[-1][f"c_{t}"]] for t in p.subdomain_list},
+                phi_M={t: p.phi_M_prev[t] for t in list(p.subdomain_list)[1:]})
+
+
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
                  extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None, events=None,
-                 event_threshold=None, fluxes=None, exchange=None, maps=None, maps_threshold=None):
+                 event_threshold=None, fluxes=None, exchange=None, maps=None, maps_threshold=None, monitor=None):
     """series: path of a .npz of per-step observables (make_observables), or None.
     events: path of a .npz of the membrane events of neuron and glia (make_events: upward crossings of event_threshold
     per membrane dof, in mV; default: `event_threshold` of the config, else -20), or None.
@@ -299,8 +321,10 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
     exchange: path of a .npz of the per-step series of the membrane exchange of neuron and glia (make_exchange), or None.
     maps: path of a .npz of the field maps (make_maps; level of ECS K+ maps_threshold in mM, default: `maps_threshold` of
     the config, else 0.05 above the initial ECS concentration), or None.
+    monitor: path of a .npz of the per-step series of the membrane monitors of neuron and glia (make_monitors), or None.
     ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator)."""
     p = Problem(config)
+    mon = make_monitors(p) if monitor else None
     fl = make_fluxes(p) if fluxes else None
     ex = make_exchange(p) if exchange else None
     obs = make_observables(p) if series else None
@@ -350,6 +374,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             st.exchange(ex, every=1)
         if fm is not None:
             st.track(fm, every=1)
+        if mon is not None:
+            st.monitor(mon, every=1)
         for k in range(n_steps):
             st.step()
             t = t + DT
@@ -391,6 +417,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
                 fl.record_host(t, p.phi, p.c_prev)
             if fm is not None:
                 fm.record_host(t, p.phi, p.c, p.phi_M_prev)
+            if mon is not None:
+                mon.record_host(t, monitor_state(p))
             p.set_source(t)
             if (k % config["save_frequency"]) == 0 or k == n_steps - 1:
                 record(problem_emi.solver.getIterationNumber(), problem_knp.solver.getIterationNumber())
@@ -405,6 +433,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
         fl.save(fluxes)
     if ex is not None:
         ex.save(exchange)
+    if mon is not None:
+        mon.save(monitor)
     if fm is not None:
         fm.save(maps)
         history["maps"] = [fm.summary(name) for name in fm.watches]
@@ -452,6 +482,9 @@ def build_parser():
     parser.add_argument("--maps-threshold", type=float, default=None, metavar="MM",
                         help="level of --maps for ECS K+ in mM (default: maps_threshold of the config, else 0.05 above the "
                              "initial concentration)")
+    parser.add_argument("--monitor", metavar="PATH", default=None,
+                        help="write the per-step membrane monitors of neuron and glia (Nernst potentials, Kir, pump and the "
+                             "other currents by mechanism at a membrane point and averaged) to this .npz")
     return parser
 
 
@@ -461,6 +494,7 @@ if __name__ == "__main__":
     _, hist = solve_system(cfg, n_steps=args.steps, device_resident=args.device_resident, direct=args.direct,
                            xdmf=args.xdmf, series=args.series, ode_method=args.ode_method,
                            ode_substeps=args.ode_substeps, events=args.events, event_threshold=args.event_threshold,
-                           fluxes=args.fluxes, exchange=args.exchange, maps=args.maps, maps_threshold=args.maps_threshold)
+                           fluxes=args.fluxes, exchange=args.exchange, maps=args.maps, maps_threshold=args.maps_threshold,
+                           monitor=args.monitor)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

@@ -633,6 +633,86 @@ int knpemi_maps_reset(knpemi_handle* h);
  * make_figures.py:336-352 are no longer kept); knpemi_destroy does the same. */
 int knpemi_maps_clear(knpemi_handle* h);
 
+/* Membrane monitors: the named intermediates of a membrane model's right-hand side -- Nernst potentials, conductances,
+ * the currents split by mechanism, the gates' steady states and time constants -- evaluated per membrane dof from what
+ * the device holds (knpemi.monitor; csrc/membrane_monitors.h lists the quantities of the shipped models).  The
+ * reference's figure scripts restate the models' formulas and constants by hand and evaluate them from checkpoints of
+ * every step (examples/local_astrocyte_depolarization/make_figures.py:169-195, 279-327: E_K, E_Na, E_Cl, i_kir, i_pump at
+ * a glial membrane point; examples/idealized_geometries/make_figures.py:146-149: E_Na, E_K;
+ * calibrate_initial_conditions/run_calibration.py:148-212: the Kir and pump currents at rest).
+ * The state a monitor sees.  On a handle of knpemi_create it is the state the next sweep would start from: the monitor
+ * works on a private copy of the dof's parameter row in which the <ion>_e / <ion>_i columns hold the traces of the
+ * concentrations the vertex records hold now (as KNPEMI_ODE_SET_TRACES writes them) and on a state in which V is phi_M of
+ * the dof (as KNPEMI_ODE_SET_V); the gates come from the state table, every other column, the stimulus columns included,
+ * is as the parameter table holds it, and t is the record's time.  On a handle of knpemi_ode_create there are no fields:
+ * row and state are as the tables hold them.  Nothing is written to a table, to phi_M, to I_ch or to a vertex record.  A
+ * non-finite value is stored as it is and makes the columns it enters non-finite.
+ * A watch is one bound model slot (sub, model) with a mask of its quantities (bit i: quantity i of the catalogue).
+ * Column kinds of the series row: KNPEMI_MON_POINT, sum_j w_j v(q_j) over the up to 4 dofs of the membrane facet that
+ * holds a point; and over the dofs q of the watch with weight w_q > 0 (w_q: the integral of the dof's hat function over
+ * the facets that carry the model) KNPEMI_MON_INTEGRAL = sum_q w_q v_q, KNPEMI_MON_AVERAGE = that / sum_q w_q,
+ * KNPEMI_MON_MIN and KNPEMI_MON_MAX. */
+#define KNPEMI_MON_MAX 32
+#define KNPEMI_MON_MAX_WATCH 16
+#define KNPEMI_MON_POINT 0
+#define KNPEMI_MON_INTEGRAL 1
+#define KNPEMI_MON_AVERAGE 2
+#define KNPEMI_MON_MIN 3
+#define KNPEMI_MON_MAX_OP 4
+/* The catalogue of shipped model model_id (KNPEMI_MODEL_*): the number of quantities (0 for an unknown id) and the name
+ * of quantity i (NULL out of range) -- the names the files E_K_*.txt ... of make_figures.py:279-327 carry. */
+int knpemi_monitor_count(int model_id);
+const char* knpemi_monitor_name(int model_id, int i);
+/* The monitor of a plug-in model: `__device__ void monitor(double t, const double* states, const double* parameters,
+ * double* monitored)` as HIP source, n_monitored (1 .. KNPEMI_MON_MAX) quantities -- what a Gotran-generated module's
+ * `monitor` computes and make_figures.py:169-195 restates by hand.  It is compiled with hipRTC as a program of its own,
+ * under the record kernel's body (the program of the sweeps is compiled from the same text as before), and from then on
+ * slot (sub, model) -- bound with knpemi_ode_bind_source -- can be watched and evaluated like a shipped model, with
+ * quantity i = monitored[i]; `states` and `parameters` are the state a monitor sees.  A record launches once per run of
+ * consecutive watches that share a program.  knpemi_monitor_compile_source compiles only and needs no device (the compiler's
+ * messages go to log, which may be NULL).  KNPEMI_EINVAL: null arguments, a slot that is not bound from source or has a
+ * monitor already, sizes out of range, a source that does not compile (knpemi_last_error holds the messages). */
+int knpemi_monitor_bind_source(knpemi_handle* h, int sub, int model, int n_monitored, const char* monitor_source);
+int knpemi_monitor_compile_source(int n_states, int n_params, int n_monitored, const char* monitor_source, char* log,
+                                  size_t log_len);
+/* Set the watches spec[w] = {sub, model, mask, v_index} (1 <= n_watch <= KNPEMI_MON_MAX_WATCH; v_index: the state
+ * component that is V, -1: none) with ion_param[w][2 k], [2 k + 1] = the parameter columns <ion k>_e, <ion k>_i (read on
+ * a handle of knpemi_create; K ions per watch) and the dense dof weights `weights`, concatenated in watch order (n_q of
+ * the sub-domain each).  The row has n_cols >= 0 columns col_spec[c] = {kind, watch, quantity, point}; point p (of n_pts)
+ * belongs to watch pt_watch[p] and has the dofs pt_q[4 p ..] (local to the sub-domain, -1: unused) with the weights
+ * pt_w[4 p ..] -- the glial membrane point of make_figures.py:169-195.  capacity: rows of the series buffer.  Replaces
+ * any previous table.  KNPEMI_EINVAL: null arguments, a slot that is unbound or bound from source without a monitor, a mask that is empty or
+ * has bits at or beyond the model's count, a sub-domain without membrane dofs, a watch listed twice, a v_index or
+ * parameter column out of range, a column with an unknown kind, watch, point or a quantity its watch does not select, a
+ * reduction over weights that sum to nothing, a dof out of range; a refused call leaves the previous table alone. */
+int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* spec, const int32_t* ion_param, const double* weights,
+                       int n_cols, const int32_t* col_spec, int n_pts, const int32_t* pt_watch, const int32_t* pt_q,
+                       const double* pt_w, int capacity);
+/* Enqueue one record at time t on the main stream: ONE launch over the dofs of the watched slots evaluates the selected
+ * quantities, with fields != 0 writes them per dof, and appends the series row (a full buffer writes nothing and counts
+ * the overflow; sums are formed in a fixed order, two identical runs give identical bits) -- this replaces the per-step
+ * checkpoints behind make_figures.py:279-327.  KNPEMI_EINVAL before knpemi_monitor_set and for a non-finite t. */
+int knpemi_monitor_record(knpemi_handle* h, double t, int fields);
+/* Synchronise and copy out min(n_rows, device row count) rows (the time series compare_tort.py plots), the device row
+ * count and the overflow count; reset != 0 empties the buffer afterwards. */
+int knpemi_monitor_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
+/* Synchronise and copy out quantity `quantity` of watch `watch` per dof (n = n_q of its sub-domain) as the latest record
+ * with fields wrote it (the spatial profiles of make_figures.py:336-352 for a monitored quantity).  KNPEMI_EINVAL before
+ * such a record, for a bad watch, a quantity the watch does not select, or a wrong length. */
+int knpemi_monitor_fields(knpemi_handle* h, int watch, int quantity, double* out, size_t n);
+/* A new series, stream-ordered; the fields of the old one are forgotten.  The table stays. */
+int knpemi_monitor_reset(knpemi_handle* h);
+/* Drop the table and the buffers; knpemi_destroy does the same. */
+int knpemi_monitor_clear(knpemi_handle* h);
+/* Evaluate the quantities in `mask` of slot (sub, model) at time t now: one launch, synchronise, copy out
+ * out[bits set][n_q], n = their product (the rest currents of run_calibration.py:148-212).  states / params: host tables
+ * [n_q][columns] to evaluate instead of the slot's device tables (both or neither; they are copied to scratch memory,
+ * the slot's tables stay as they are).  ion_param ([2 K], as in knpemi_monitor_set) != NULL on a handle of knpemi_create:
+ * the traces and phi_M are taken from the fields as in a record; NULL: row and state as the tables hold them.  Works on
+ * both kinds of handle. */
+int knpemi_monitor_eval(knpemi_handle* h, int sub, int model, double t, uint32_t mask, const double* states,
+                        const double* params, const int32_t* ion_param, int v_index, double* out, size_t n);
+
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop
  *   (run_3D.py:356,362); with this option the write-back kernel of knpemi_solve_knp -- and of

@@ -32,6 +32,16 @@ const char* const SRC_ODE_KERNEL =
 const char* const SRC_FIXED_STEP =
 #include "rtc_fixed_step.inc"
     ;
+// ... and the three more the monitor program of a plug-in includes (monitor_kernel.h: the record kernel's body)
+const char* const SRC_MONITOR_TABLE =
+#include "rtc_monitor_table.inc"
+    ;
+const char* const SRC_RECORD_TAIL =
+#include "rtc_record_tail.inc"
+    ;
+const char* const SRC_MONITOR_KERNEL =
+#include "rtc_monitor_kernel.inc"
+    ;
 
 std::string wrapper_source(int ns, int np, int lanes, const std::string& user) {
   std::string s;
@@ -186,5 +196,133 @@ int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, con
 int kn_rtc_launch(hipStream_t st, hipFunction_t fn, unsigned grid, void* params, size_t bytes) {
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, params, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
   KN_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, ODE_BLOCK, 1, 1, 0, st, nullptr, config));
+  return KNPEMI_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The monitor of a plug-in: `__device__ void monitor(double t, const double* states, const double* parameters, double*
+// monitored)` as HIP source (module attribute MONITOR_HIP, or translated from a Gotran-style Python `monitor` by
+// knpemi.rhs_codegen), the counterpart of the Gotran modules' `monitor` the reference's figure scripts restate by hand
+// (make_figures.py:169-195).  It is pasted under the record kernel's body (monitor_kernel.h: the very code of the shipped
+// models' monitors) and compiled as a program of its own -- the sweeps' program is compiled from the same text as before.
+namespace {
+
+std::string monitor_wrapper_source(int ns, int np, int nm, const std::string& user) {
+  std::string s;
+  s += "#include \"monitor_kernel.h\"\n";
+  s += "#pragma clang fp contract(off)\n";
+  s += "// ---- plug-in source -------------------------------------------------------------\n";
+  s += user;
+  s += "\n// ---- adapter: what the record kernel's body evaluates per dof -----------------------\n";
+  s += "struct MonUser {\n";
+  s += "  static constexpr int NS = " + std::to_string(ns) + ", NP = " + std::to_string(np) + ", NM = " + std::to_string(nm) + ";\n";
+  s += "  __device__ __forceinline__ static void eval(const OdeDev& D, const KnMonWatch& W, int q, double t, double (&out)[KN_MON_MAX]) {\n";
+  s += "    double y[NS], row[NP], m[NM];\n";
+  s += "    mon_load<NS, NP>(D, W, q, y, row);\n";
+  s += "    _Pragma(\"unroll\") for (int i = 0; i < NM; ++i) m[i] = 0.0;\n";
+  s += "    monitor(t, y, row, m);\n";
+  s += "    _Pragma(\"unroll\") for (int i = 0; i < NM; ++i) out[i] = m[i];\n  }\n};\n";
+  s += "extern \"C\" __global__ __launch_bounds__(MON_THREADS) void monitor_user_kernel(OdeDev D, KnMonArgs A) {\n";
+  s += "  monitor_body<MonUser, false>(D, A);\n}\n";
+  s += "extern \"C\" __global__ __launch_bounds__(MON_THREADS) void monitor_user_fields_kernel(OdeDev D, KnMonArgs A) {\n";
+  s += "  monitor_body<MonUser, true>(D, A);\n}\n";
+  return s;
+}
+
+int compile_monitor(int ns, int np, int nm, const std::string& user, std::vector<char>* code, std::string* log) {
+  const std::string src = monitor_wrapper_source(ns, np, nm, user);
+  const char* headers[5] = {SRC_LSODA_CORE, SRC_ODE_KERNEL, SRC_MONITOR_TABLE, SRC_RECORD_TAIL, SRC_MONITOR_KERNEL};
+  const char* names[5] = {"lsoda_core.h", "ode_kernel.h", "monitor_table.h", "record_tail.h", "monitor_kernel.h"};
+  hiprtcProgram prog = nullptr;
+  if (hiprtcCreateProgram(&prog, src.c_str(), "knpemi_user_monitor.hip", 5, headers, names) != HIPRTC_SUCCESS) {
+    *log = "hiprtcCreateProgram failed";
+    return KNPEMI_EHIP;
+  }
+  // as kernels_monitor.o (Makefile): no multiply-add contracted
+  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
+  const hiprtcResult res = hiprtcCompileProgram(prog, 4, opts);
+  size_t n = 0;
+  if (hiprtcGetProgramLogSize(prog, &n) == HIPRTC_SUCCESS && n > 1) {
+    log->assign(n, '\0');
+    (void)hiprtcGetProgramLog(prog, &(*log)[0]);
+  }
+  if (res != HIPRTC_SUCCESS) {
+    *log = std::string("hipRTC: ") + hiprtcGetErrorString(res) + "\n" + *log;
+    (void)hiprtcDestroyProgram(&prog);
+    return KNPEMI_EINVAL;
+  }
+  size_t sz = 0;
+  if (hiprtcGetCodeSize(prog, &sz) != HIPRTC_SUCCESS) { (void)hiprtcDestroyProgram(&prog); *log = "hiprtcGetCodeSize failed"; return KNPEMI_EHIP; }
+  code->resize(sz);
+  if (hiprtcGetCode(prog, code->data()) != HIPRTC_SUCCESS) { (void)hiprtcDestroyProgram(&prog); *log = "hiprtcGetCode failed"; return KNPEMI_EHIP; }
+  (void)hiprtcDestroyProgram(&prog);
+  return KNPEMI_OK;
+}
+
+std::string monitor_key(int ns, int np, int nm, const char* src) {
+  return "monitor/" + std::to_string(ns) + "/" + std::to_string(np) + "/" + std::to_string(nm) + "/" + src;
+}
+bool monitor_sizes_ok(int ns, int np, int nm) { return ns >= 1 && ns <= 16 && np >= 1 && np <= 128 && nm >= 1 && nm <= KN_MON_MAX; }
+
+}  // namespace
+
+// Compile only (no device needed), like knpemi_ode_compile_source.
+extern "C" int knpemi_monitor_compile_source(int n_states, int n_params, int n_monitored, const char* monitor_source, char* log,
+                                             size_t log_len) {
+  if (!monitor_source || !monitor_sizes_ok(n_states, n_params, n_monitored)) {
+    kn_set_error("knpemi_monitor_compile_source: bad argument (1..16 states, 1..128 parameters, 1..KNPEMI_MON_MAX quantities)");
+    return KNPEMI_EINVAL;
+  }
+  std::string msg;
+  std::vector<char> code;
+  const int rc = compile_monitor(n_states, n_params, n_monitored, monitor_source, &code, &msg);
+  if (log && log_len) {
+    const size_t n = std::min(log_len - 1, msg.size());
+    std::memcpy(log, msg.data(), n);
+    log[n] = '\0';
+  }
+  if (rc) { kn_set_error("membrane monitor source did not compile:\n" + msg); return rc; }
+  std::lock_guard<std::mutex> lock(g_cache_mutex);
+  g_code_cache[monitor_key(n_states, n_params, n_monitored, monitor_source)] = std::move(code);
+  return KNPEMI_OK;
+}
+
+int kn_rtc_monitor_bind(knpemi_handle* h, KnOdeModel& m, int n_monitored, const char* monitor_source) {
+  if (!monitor_sizes_ok(m.n_states, m.n_params, n_monitored))
+    return kn_fail(KNPEMI_EINVAL, "knpemi_monitor_bind_source: 1..KNPEMI_MON_MAX monitored quantities");
+  const std::string key = monitor_key(m.n_states, m.n_params, n_monitored, monitor_source);
+  std::vector<char> code;
+  {
+    std::lock_guard<std::mutex> lock(g_cache_mutex);
+    auto it = g_code_cache.find(key);
+    if (it != g_code_cache.end()) code = it->second;
+  }
+  if (code.empty()) {
+    std::string msg;
+    const int rc = compile_monitor(m.n_states, m.n_params, n_monitored, monitor_source, &code, &msg);
+    if (rc) { kn_set_error("membrane monitor source did not compile:\n" + msg); return rc; }
+    std::lock_guard<std::mutex> lock(g_cache_mutex);
+    g_code_cache[key] = code;
+  }
+  hipModule_t mod = nullptr;
+  KN_HIP(hipModuleLoadData(&mod, code.data()));
+  hipFunction_t fn[2] = {nullptr, nullptr};
+  const char* const names[2] = {"monitor_user_kernel", "monitor_user_fields_kernel"};
+  for (int j = 0; j < 2; ++j)
+    if (hipModuleGetFunction(&fn[j], mod, names[j]) != hipSuccess) {
+      (void)hipModuleUnload(mod);
+      return kn_fail(KNPEMI_EHIP, std::string("hipModuleGetFunction(") + names[j] + ") failed");
+    }
+  m.mon_kernel[0] = fn[0]; m.mon_kernel[1] = fn[1];
+  m.n_monitored = n_monitored;
+  h->rtc_modules.push_back(mod);
+  return KNPEMI_OK;
+}
+
+int kn_rtc_launch_monitor(hipStream_t st, hipFunction_t fn, unsigned grid, unsigned block, const OdeDev& dv, const KnMonArgs& a) {
+  struct { OdeDev d; KnMonArgs a; } p{dv, a};
+  size_t bytes = sizeof(p);
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &p, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
+  KN_HIP(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, st, nullptr, config));
   return KNPEMI_OK;
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/knpemi_hip.h"
+#include "monitor_table.h"
 
 #define KN_MAXK KNPEMI_MAX_IONS
 #define KN_MAXSUB KNPEMI_MAX_SUB
@@ -187,6 +188,8 @@ struct KnMapTab {
   KnMapWatch w[KNPEMI_MAPS_MAX_WATCH];
 };
 
+// (the table of the membrane monitors, KnMonTab: monitor_table.h, shared with the run-time compiled monitor programs)
+
 struct KnOdeModel {
   int bound = 0, sub = 0, model_id = -1, n_states = 0, n_params = 0, nq = 0;
   double* d_states = nullptr;   // [n_states][nq]
@@ -207,6 +210,10 @@ struct KnOdeModel {
   int adv_chunk = 0;                      // steps per launch the last knpemi_ode_advance chose
   // integrator of the slot (knpemi_ode_set_method): KNPEMI_ODE_LSODA or a fixed-step scheme with n_substeps sub-steps
   int method = 0, n_substeps = 0;
+  // the monitor program of a plug-in (knpemi_monitor_bind_source; kernels_rtc.hip): [0] series only, [1] with fields;
+  // NULL: the slot has no monitor of its own (shipped models: the library's kernel)
+  hipFunction_t mon_kernel[2] = {};
+  int n_monitored = 0;
 };
 
 // blocks of the dense coarsest-level inverse, passed to the kernels by value: block b covers the unknowns start[b] ..
@@ -679,7 +686,27 @@ struct knpemi_handle : KnDevice {
     KnSeries ser;
     std::vector<void*> allocs;
   } maps;
-  int knp_flags = 0;                   // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
+  // membrane monitors (knpemi_monitor_set, kernels_monitor.hip): a watch table, the columns and points of the series row,
+  // workgroup partials, per-dof fields and a series
+  struct KnMon {
+    int n_watch = 0, n_blk = 0;
+    KnMonTab host{};                     // the table as uploaded
+    int slot_of[KN_MON_MAXW] = {};       // watch -> model slot (moff[sub] + model)
+    hipFunction_t fn[KN_MON_MAXW][2] = {};   // watch -> the kernels of its plug-in's monitor program, NULL: the library's
+    KnMonTab* tab = nullptr;
+    int4* cols = nullptr;                // [n_cols] {kind, watch, quantity, point}
+    int* pt_q = nullptr;                 // [n_pts][4] dofs of a point within its watch, -1: unused
+    int* pt_watch = nullptr;             // [n_pts]
+    double* pt_w = nullptr;              // [n_pts][4]
+    double* pt_val = nullptr;            // [n_pts][4][KN_MON_MAX] what the last workgroup evaluates at the points' dofs
+    double* part = nullptr;              // [n_blk][KN_MON_SLOTS] workgroup partials
+    KnSeries ser;
+    double* fld = nullptr;               // per-dof fields, allocated at the first record that writes them
+    size_t fld_len = 0;
+    bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
+    std::vector<void*> allocs;
+  } mon;
+  int knp_flags = 0;                  // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
 };
 
 inline void kn_inputs_changed(knpemi_handle* h) { ++h->inputs_gen; }
@@ -718,6 +745,15 @@ int kn_launch_maps_record(knpemi_handle* h, double t, double t_prev);
 int kn_launch_maps_reset(knpemi_handle* h);
 int kn_launch_flux(knpemi_handle* h, int write_fields);
 int kn_launch_exchange(knpemi_handle* h, int write_fields);
+int kn_launch_monitor(knpemi_handle* h, double t, int write_fields);
+// one watch, fields only, no series row: d_tab a device copy of a table with one watch, fld its [bits of mask][nq] output
+// fn: the fields kernel of a plug-in's monitor program, NULL: the library's kernel (a shipped model)
+int kn_launch_monitor_eval(knpemi_handle* h, const KnMonTab* d_tab, int nq, double t, double* fld, hipFunction_t fn);
+// kernels_rtc.hip: the monitor program of a plug-in (knpemi_monitor_bind_source) and the launch of one of its kernels
+int kn_rtc_monitor_bind(knpemi_handle* h, KnOdeModel& m, int n_monitored, const char* monitor_source);
+struct OdeDev;
+int kn_rtc_launch_monitor(hipStream_t st, hipFunction_t fn, unsigned grid, unsigned block, const OdeDev& dv,
+                          const KnMonArgs& a);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 // (the membrane ODE sweeps: ode_host.h)
 int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);

@@ -1,6 +1,7 @@
 // The on-device recorders behind the C ABI (include/knpemi_hip.h): observables (kernels_observe.hip), membrane events
 // (kernels_events.hip), ion fluxes per cell (kernels_flux.hip), the membrane exchange per cell (kernels_exchange.hip) and
-// the field maps (kernels_maps.hip: per-item maps as the events, and a series with a series watch).
+// the field maps (kernels_maps.hip: per-item maps as the events, and a series with a series watch), and the membrane
+// monitors (kernels_monitor.hip: a series and per-dof fields of the models' named intermediates).
 //
 // Three of them append rows to a series buffer (KnSeries; the device side is record_tail.h).  The fluxes and the exchange
 // are one recorder over different items -- the cells of a watched sub-domain, the membrane facets of a watched cell: they
@@ -19,6 +20,7 @@
 int kn_observe_chunk();
 extern "C" int kn_flux_chunk();
 extern "C" int kn_exchange_chunk();
+extern "C" int kn_monitor_chunk();
 
 namespace {
 using KnSeries = knpemi_handle::KnSeries;
@@ -74,7 +76,8 @@ int recorder_clear(knpemi_handle* h, R knpemi_handle::*which) {
 }  // namespace
 
 void kn_record_free(knpemi_handle* h) {
-  for (auto* a : {&h->obs.allocs, &h->events.allocs, &h->flux.allocs, &h->exchange.allocs, &h->maps.allocs}) kn_free_all(*a);
+  for (auto* a : {&h->obs.allocs, &h->events.allocs, &h->flux.allocs, &h->exchange.allocs, &h->maps.allocs, &h->mon.allocs})
+    kn_free_all(*a);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -742,3 +745,231 @@ extern "C" int knpemi_maps_reset(knpemi_handle* h) {
 }
 
 extern "C" int knpemi_maps_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::maps); }
+
+// ---------------------------------------------------------------------------------------------------
+// membrane monitors (kernels_monitor.hip)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+const char* const MON_NONE = "no monitors set (knpemi_monitor_set)";
+
+// the watch of slot (sub, model) with the quantities `mask`: checks the slot, the mask, v_index and (pde) the parameter
+// columns of the ions; *slot: the model slot.  weight, wsum, rmask and fbase are the caller's.
+int mon_watch(knpemi_handle* h, const std::string& fn, int sub, int model, uint32_t mask, int v_index, const int32_t* ion_param,
+              KnMonWatch* W, int* slot) {
+  if (sub == 0 && !h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": the ECS (sub-domain 0) has no membrane: watch a model of a cell");
+  if (sub < 1 || sub >= h->n_sub || model < 0 || model >= h->n_models[sub])
+    return kn_fail(KNPEMI_EINVAL, fn + ": membrane model index out of range");
+  const KnOdeModel& m = h->ode[h->moff[sub] + model];
+  if (!m.bound) return kn_fail(KNPEMI_EINVAL, fn + ": membrane model not bound (knpemi_ode_bind)");
+  if (m.rtc_module && !m.mon_kernel[0])
+    return kn_fail(KNPEMI_EINVAL, fn + ": a model bound from source has no monitor (knpemi_monitor_bind_source)");
+  const int count = m.rtc_module ? m.n_monitored : knpemi_monitor_count(m.model_id);
+  if (mask == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty quantity mask");
+  if (count < 32 && (mask >> count)) return kn_fail(KNPEMI_EINVAL, fn + ": quantity mask has bits at or beyond the model's count");
+  if (m.nq < 1) return kn_fail(KNPEMI_EINVAL, fn + ": the sub-domain has no membrane dofs");
+  if (v_index < -1 || v_index >= m.n_states) return kn_fail(KNPEMI_EINVAL, fn + ": v_index out of range");
+  *W = KnMonWatch{};
+  W->model_id = m.model_id; W->nq = m.nq; W->q0 = h->qoff[sub]; W->v_index = v_index; W->mask = mask;
+  W->states = m.d_states; W->params = m.d_params;
+  W->pde = (!h->ode_only && ion_param) ? 1 : 0;
+  if (W->pde) {
+    W->n_ions = h->K;
+    for (int k = 0; k < h->K; ++k) {
+      const int je = ion_param[2 * k], ji = ion_param[2 * k + 1];
+      if (je < 0 || je >= m.n_params || ji < 0 || ji >= m.n_params || je == ji)
+        return kn_fail(KNPEMI_EINVAL, fn + ": parameter column of an ion out of range");
+      W->ion_e[k] = je; W->ion_i[k] = ji;
+    }
+  }
+  *slot = h->moff[sub] + model;
+  return KNPEMI_OK;
+}
+
+// the record reads phi_M and the tables, which the ODE sweeps may write on the auxiliary streams (as knpemi_assemble_knp)
+int mon_after_ode(knpemi_handle* h) {
+  if (h->ev_join) KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+  if (h->ev_join2) KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+  return KNPEMI_OK;
+}
+}  // namespace
+
+extern "C" int knpemi_monitor_bind_source(knpemi_handle* h, int sub, int model, int n_monitored, const char* monitor_source) {
+  const std::string fn = "knpemi_monitor_bind_source";
+  if (!h || !monitor_source) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (sub < 1 || sub >= h->n_sub || model < 0 || model >= h->n_models[sub])
+    return kn_fail(KNPEMI_EINVAL, fn + ": membrane model index out of range");
+  KnOdeModel& m = h->ode[h->moff[sub] + model];
+  if (!m.bound || !m.rtc_module)
+    return kn_fail(KNPEMI_EINVAL, fn + ": the slot is not bound from source (knpemi_ode_bind_source); the shipped models "
+                                       "bring their monitors");
+  if (m.mon_kernel[0]) return kn_fail(KNPEMI_EINVAL, fn + ": the slot has a monitor already");
+  KN_HIP(hipSetDevice(h->device));
+  return kn_rtc_monitor_bind(h, m, n_monitored, monitor_source);
+}
+
+extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* spec, const int32_t* ion_param,
+                                  const double* weights, int n_cols, const int32_t* col_spec, int n_pts,
+                                  const int32_t* pt_watch, const int32_t* pt_q, const double* pt_w, int capacity) {
+  const std::string fn = "knpemi_monitor_set";
+  if (!h || !spec || !weights || (n_cols > 0 && !col_spec) || (n_pts > 0 && (!pt_watch || !pt_q || !pt_w)))
+    return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (!h->ode_only && !ion_param) return kn_fail(KNPEMI_EINVAL, fn + ": null argument (the ions' parameter columns)");
+  if (n_watch < 1 || n_watch > KN_MON_MAXW) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MON_MAX_WATCH watches");
+  if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
+  if (n_cols < 0 || n_pts < 0 || n_pts > (1 << 20)) return kn_fail(KNPEMI_EINVAL, fn + ": bad number of columns or points");
+  knpemi_handle::KnMon N;
+  KnMonTab& T = N.host;
+  std::vector<size_t> woff(n_watch);
+  size_t wo = 0;
+  long long fbase = 0;
+  for (int w = 0; w < n_watch; ++w) {
+    int slot = -1;
+    if (int rc = mon_watch(h, fn, spec[4 * w], spec[4 * w + 1], (uint32_t)spec[4 * w + 2], spec[4 * w + 3],
+                           h->ode_only ? nullptr : ion_param + (size_t)w * 2 * h->K, &T.w[w], &slot))
+      return rc;
+    for (int u = 0; u < w; ++u)
+      if (N.slot_of[u] == slot) return kn_fail(KNPEMI_EINVAL, fn + ": watch " + std::to_string(w) + " is listed twice");
+    N.slot_of[w] = slot;
+    N.fn[w][0] = h->ode[slot].mon_kernel[0];
+    N.fn[w][1] = h->ode[slot].mon_kernel[1];
+    KnMonWatch& W = T.w[w];
+    woff[w] = wo;
+    double wsum = 0.0;
+    for (int q = 0; q < W.nq; ++q) {
+      const double x = weights[wo + q];
+      if (!(x >= 0.0) || !std::isfinite(x)) return kn_fail(KNPEMI_EINVAL, fn + ": a dof weight is negative or not finite");
+      wsum += x;
+    }
+    wo += (size_t)W.nq;
+    W.wsum = wsum;
+    W.fbase = fbase;
+    fbase += (long long)popcount((int)(W.mask & 0x7FFFFFFFu)) * W.nq + ((W.mask >> 31) ? W.nq : 0);
+    T.bstart[w + 1] = T.bstart[w] + (W.nq + kn_monitor_chunk() - 1) / kn_monitor_chunk();
+  }
+  for (int p = 0; p < n_pts; ++p) {
+    if (pt_watch[p] < 0 || pt_watch[p] >= n_watch) return kn_fail(KNPEMI_EINVAL, fn + ": a point's watch is out of range");
+    bool any = false;
+    for (int j = 0; j < 4; ++j) {
+      const int q = pt_q[4 * p + j];
+      if (q < -1 || q >= T.w[pt_watch[p]].nq) return kn_fail(KNPEMI_EINVAL, fn + ": a point's dof is out of range");
+      if (q >= 0 && !std::isfinite(pt_w[4 * p + j])) return kn_fail(KNPEMI_EINVAL, fn + ": a point's weight is not finite");
+      any = any || q >= 0;
+    }
+    if (!any) return kn_fail(KNPEMI_EINVAL, fn + ": a point without dofs");
+  }
+  std::vector<int4> cols((size_t)n_cols);
+  for (int c = 0; c < n_cols; ++c) {
+    const int kind = col_spec[4 * c], w = col_spec[4 * c + 1], qty = col_spec[4 * c + 2], pt = col_spec[4 * c + 3];
+    const std::string who = fn + ": column " + std::to_string(c);
+    if (kind < KNPEMI_MON_POINT || kind > KNPEMI_MON_MAX_OP) return kn_fail(KNPEMI_EINVAL, who + ": unknown kind");
+    if (w < 0 || w >= n_watch) return kn_fail(KNPEMI_EINVAL, who + ": watch out of range");
+    if (qty < 0 || qty >= KN_MON_MAX || !((T.w[w].mask >> qty) & 1u))
+      return kn_fail(KNPEMI_EINVAL, who + ": the quantity is not selected by its watch");
+    if (kind == KNPEMI_MON_POINT) {
+      if (pt < 0 || pt >= n_pts || pt_watch[pt] != w) return kn_fail(KNPEMI_EINVAL, who + ": not a point of its watch");
+    } else {
+      if (!(T.w[w].wsum > 0.0)) return kn_fail(KNPEMI_EINVAL, who + ": the weights of its watch sum to nothing");
+      T.w[w].rmask |= 1u << qty;
+    }
+    cols[c] = make_int4(kind, w, qty, kind == KNPEMI_MON_POINT ? pt : 0);
+  }
+  T.n_watch = n_watch; T.n_cols = n_cols; T.n_pts = n_pts;
+  N.n_watch = n_watch; N.n_blk = T.bstart[n_watch]; N.fld_len = (size_t)fbase;
+  KN_HIP(hipSetDevice(h->device));
+  auto& A = N.allocs;
+  int rc = KNPEMI_OK;
+  for (int w = 0; w < n_watch && !rc; ++w) rc = kn_upload(A, weights + woff[w], (size_t)T.w[w].nq, &T.w[w].weight);
+  if (!rc) rc = kn_upload(A, &T, 1, &N.tab);
+  if (!rc) rc = kn_upload(A, cols, &N.cols);
+  if (!rc) rc = kn_upload(A, pt_watch, (size_t)n_pts, &N.pt_watch);
+  if (!rc) rc = kn_upload(A, pt_q, 4 * (size_t)n_pts, &N.pt_q);
+  if (!rc) rc = kn_upload(A, pt_w, 4 * (size_t)n_pts, &N.pt_w);
+  if (!rc) rc = kn_alloc(A, 4 * (size_t)n_pts * KN_MON_MAX, &N.pt_val);
+  if (!rc) rc = kn_alloc(A, (size_t)N.n_blk * KN_MON_SLOTS, &N.part);
+  if (!rc) rc = series_alloc(A, h->stream, capacity, n_cols, &N.ser);
+  if (rc) return kn_free_all(N.allocs), rc;
+  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
+  recorder_free(h->mon);
+  h->mon = N;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_monitor_record(knpemi_handle* h, double t, int fields) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->mon;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_monitor_record: ") + MON_NONE);
+  if (!std::isfinite(t)) return kn_fail(KNPEMI_EINVAL, "knpemi_monitor_record: t must be finite");
+  KN_HIP(hipSetDevice(h->device));
+  if (int rc = mon_after_ode(h)) return rc;
+  if (fields && !X.fld)
+    if (int rc = kn_alloc(X.allocs, std::max<size_t>(X.fld_len, 1), &X.fld)) return rc;
+  if (int rc = kn_launch_monitor(h, t, fields)) return rc;
+  if (fields) X.fld_valid = true;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_monitor_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  return series_read(h, h->mon.ser, h->mon.n_watch != 0, "knpemi_monitor_read", MON_NONE, n_rows, out, rows, overflow, reset);
+}
+
+extern "C" int knpemi_monitor_fields(knpemi_handle* h, int watch, int quantity, double* out, size_t n) {
+  const std::string fn = "knpemi_monitor_fields";
+  if (!h || !out) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  const auto& X = h->mon;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + MON_NONE);
+  if (watch < 0 || watch >= X.n_watch) return kn_fail(KNPEMI_EINVAL, fn + ": bad watch index");
+  const KnMonWatch& W = X.host.w[watch];
+  if (quantity < 0 || quantity >= KN_MON_MAX || !((W.mask >> quantity) & 1u))
+    return kn_fail(KNPEMI_EINVAL, fn + ": the quantity is not selected by the watch");
+  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (knpemi_monitor_record(h, t, 1))");
+  if (n != (size_t)W.nq) return kn_fail(KNPEMI_EINVAL, fn + ": length is not the number of membrane dofs of the sub-domain");
+  KN_HIP(hipSetDevice(h->device));
+  const size_t comp = (size_t)popcount((int)(W.mask & ((1u << quantity) - 1u)));
+  return kn_to_host(h->stream, out, X.fld + W.fbase + comp * (size_t)W.nq, n);
+}
+
+extern "C" int knpemi_monitor_reset(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& X = h->mon;
+  if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_monitor_reset: ") + MON_NONE);
+  KN_HIP(hipSetDevice(h->device));
+  X.fld_valid = false;
+  return series_rewind(h, X.ser);
+}
+
+extern "C" int knpemi_monitor_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::mon); }
+
+extern "C" int knpemi_monitor_eval(knpemi_handle* h, int sub, int model, double t, uint32_t mask, const double* states,
+                                   const double* params, const int32_t* ion_param, int v_index, double* out, size_t n) {
+  const std::string fn = "knpemi_monitor_eval";
+  if (!h || !out) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if ((states == nullptr) != (params == nullptr)) return kn_fail(KNPEMI_EINVAL, fn + ": give both host tables or neither");
+  if (!std::isfinite(t)) return kn_fail(KNPEMI_EINVAL, fn + ": t must be finite");
+  KnMonTab T{};
+  KnMonWatch& W = T.w[0];
+  int slot = -1;
+  if (int rc = mon_watch(h, fn, sub, model, mask, v_index, ion_param, &W, &slot)) return rc;
+  const KnOdeModel& m = h->ode[slot];
+  const size_t nq = (size_t)W.nq, nb = (size_t)popcount((int)(mask & 0x7FFFFFFFu)) + (mask >> 31);
+  if (n != nb * nq) return kn_fail(KNPEMI_EINVAL, fn + ": length is not (bits set) * (membrane dofs)");
+  KN_HIP(hipSetDevice(h->device));
+  struct Tmp { std::vector<void*> a; ~Tmp() { kn_free_all(a); } } tmp;
+  int rc;
+  if (states) {
+    double *ds = nullptr, *dp = nullptr;
+    if ((rc = kn_alloc(tmp.a, nq * m.n_states, &ds)) || (rc = kn_alloc(tmp.a, nq * m.n_params, &dp))
+        || (rc = kn_table_upload(h->stream, states, ds, W.nq, m.n_states))
+        || (rc = kn_table_upload(h->stream, params, dp, W.nq, m.n_params)))
+      return rc;
+    W.states = ds; W.params = dp;
+  }
+  T.n_watch = 1;
+  T.bstart[1] = (W.nq + kn_monitor_chunk() - 1) / kn_monitor_chunk();
+  KnMonTab* d_tab = nullptr;
+  double* fld = nullptr;
+  if ((rc = kn_upload(tmp.a, &T, 1, &d_tab)) || (rc = kn_alloc(tmp.a, n, &fld)) || (rc = mon_after_ode(h))
+      || (rc = kn_launch_monitor_eval(h, d_tab, W.nq, t, fld, m.mon_kernel[1])))
+    return rc;
+  return kn_to_host(h->stream, out, fld, n);   // synchronises: the scratch memory is no longer read
+}

@@ -13,7 +13,9 @@
 //      (kn_reset_ticket), with plain stores.
 // ctl is the series buffer's [4] counters: rows written, rows dropped (buffer full), ticket.
 #pragma once
+#if !defined(__HIPCC_RTC__)   // (hipRTC provides the runtime's device declarations itself: monitor programs of plug-ins)
 #include <hip/hip_runtime.h>
+#endif
 
 __device__ inline double kn_wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

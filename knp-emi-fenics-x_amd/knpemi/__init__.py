@@ -4,16 +4,18 @@ Re-exports the twelve public names of the reference package (`src/knpemi/__init_
 `__all__` names several functions that do not exist; the list below is the set that can actually be imported
 from it.  The device-resident loop of this implementation lives in `knpemi.stepper`; `Observables`
 (`knpemi.observables`), `MembraneEvents` (`knpemi.events`), `IonFluxes` (`knpemi.fluxes`), `MembraneExchange`
-(`knpemi.exchange`) and `FieldMaps` (`knpemi.maps`) are its own additions: time series of point values and field
-statistics, per-dof firing maps of the membranes, per-cell ion fluxes and current densities with their integrals, what
-every ion carries across the membrane of a cell, with the mass budget it closes, and per-vertex peak, arrival and
-exposure maps of phi, c and phi_M.
+(`knpemi.exchange`), `FieldMaps` (`knpemi.maps`) and `MembraneMonitor` (`knpemi.monitor`) are its own additions: time
+series of point values and field statistics, per-dof firing maps of the membranes, per-cell ion fluxes and current
+densities with their integrals, what every ion carries across the membrane of a cell, with the mass budget it closes,
+and per-vertex peak, arrival and exposure maps of phi, c and phi_M, and the membrane models' named intermediates
+(Nernst potentials, currents by mechanism) at points, over a membrane and per dof.
 """
 from .emiWeakForm import create_functions_emi, emi_system
 from .events import MembraneEvents
 from .exchange import MembraneExchange
 from .fluxes import IonFluxes
 from .maps import FieldMaps
+from .monitor import MembraneMonitor
 from .knpWeakForm import create_functions_knp, knp_system
 from .observables import Observables
 from .odeSolver import MembraneModel
@@ -22,7 +24,7 @@ from .utils import (interpolate_to_membrane, set_initial_conditions, setup_membr
                     update_pde_variables)
 
 __all__ = sorted([
-    "FieldMaps", "IonFluxes", "MembraneEvents", "MembraneExchange", "MembraneModel", "Observables", "create_functions_emi", "create_functions_knp", "create_solver_emi", "create_solver_knp",
+    "FieldMaps", "IonFluxes", "MembraneEvents", "MembraneExchange", "MembraneModel", "MembraneMonitor", "Observables", "create_functions_emi", "create_functions_knp", "create_solver_emi", "create_solver_knp",
     "emi_system", "interpolate_to_membrane", "knp_system", "set_initial_conditions", "setup_membrane_model",
     "update_ode_variables", "update_pde_variables",
 ])

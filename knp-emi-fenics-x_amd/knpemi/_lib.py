@@ -33,6 +33,8 @@ EVENTS_MAX_KEEP = 64
 MAPS_MAX_WATCH, MAPS_MAX_PER_SPACE = 32, 8
 MAPS_PEAK, MAPS_TROUGH, MAPS_INTEGRAL, MAPS_THRESHOLD, MAPS_SERIES, MAPS_BELOW = 1, 2, 4, 8, 16, 32
 MAP_V_MAX, MAP_T_MAX, MAP_V_MIN, MAP_T_MIN, MAP_INTEGRAL, MAP_T_ARRIVAL, MAP_EXPOSURE, MAP_EXCESS, MAP_COUNT = range(9)
+MON_MAX, MON_MAX_WATCH = 32, 16
+MON_POINT, MON_INTEGRAL, MON_AVERAGE, MON_MIN, MON_MAX_OP = range(5)
 K_ODE, K_EMI_ROWS, K_KNP_ROWS, K_KNP_MEMBRANE, K_UPDATE, K_EMI_MEMBRANE = range(6)
 KERNEL_NAMES = ["ode_step_kernel", "emi_rows_kernel", "knp_rows_kernel", "knp_membrane_kernel", "update_pde_kernel",
                 "emi_membrane_rhs_kernel"]
@@ -195,6 +197,19 @@ SIGNATURES = {
                                           C.c_int]),
     "knpemi_maps_reset": (C.c_int, [C.c_void_p]),
     "knpemi_maps_clear": (C.c_int, [C.c_void_p]),
+    "knpemi_monitor_count": (C.c_int, [C.c_int]),
+    "knpemi_monitor_name": (C.c_char_p, [C.c_int, C.c_int]),
+    "knpemi_monitor_bind_source": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p]),
+    "knpemi_monitor_compile_source": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "knpemi_monitor_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_dbl_p, C.c_int, c_int_p, C.c_int, c_int_p,
+                                     c_int_p, c_dbl_p, C.c_int]),
+    "knpemi_monitor_record": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
+    "knpemi_monitor_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
+    "knpemi_monitor_fields": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dbl_p, C.c_size_t]),
+    "knpemi_monitor_reset": (C.c_int, [C.c_void_p]),
+    "knpemi_monitor_clear": (C.c_int, [C.c_void_p]),
+    "knpemi_monitor_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint32, c_dbl_p, c_dbl_p, c_int_p,
+                                      C.c_int, c_dbl_p, C.c_size_t]),
     "knpemi_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "knpemi_trace": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_halo_width": (C.c_int, [C.c_void_p, C.c_int]),

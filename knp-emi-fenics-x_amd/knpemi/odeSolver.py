@@ -99,6 +99,8 @@ class MembraneModel:
         self._mask_cache = {}
         self._standalone = None   # OdeProblem of a model no PDE problem has claimed
         self._events = None       # MembraneEvents recorded after every step of a stand-alone model (detect)
+        self._monitor_cache = None   # (names, device source of a plug-in's monitor), filled on first use
+        self.monitor_refused = None  # why a plug-in's Python `monitor` could not be translated, if it could not
         print(f'\t{self.prefix} Number of ODE points on the membrane {nodes}')
 
     # --- device binding ------------------------------------------------------
@@ -119,6 +121,11 @@ class MembraneModel:
             # the plug-in's own right-hand side, compiled for gfx950 now (a few seconds, cached per process)
             L.check(dp.lib.knpemi_ode_bind_source(dp.h, sub, model, self.states.shape[1], self.parameters.shape[1],
                                                   source.encode()))
+            # the plug-in's monitor, if it brings one (MONITOR_HIP, or a Python `monitor` translated), with its names:
+            # a hipRTC program of its own
+            names, mon_source = self._plug_in_monitor()
+            if mon_source is not None:
+                L.check(dp.lib.knpemi_monitor_bind_source(dp.h, sub, model, len(names), mon_source.encode()))
         else:
             raise NotImplementedError(
                 f"membrane model module '{self.prefix}' has neither a MODEL_ID naming a shipped device RHS "
@@ -161,6 +168,51 @@ class MembraneModel:
         ev._attach(dp.lib, dp.h, {self.tag: self._sub})
         ev.reset_host()
         self._events = ev
+
+    def monitor_names(self):
+        """The monitored quantities of the model, from the library's catalogue; [] for a model that brings none."""
+        if getattr(self.ode, "MODEL_ID", None) in _MODEL_IDS:
+            if self._monitor_cache is None:
+                from .monitor import catalogue
+                self._monitor_cache = (catalogue(self.ode.MODEL_ID), None)
+            return list(self._monitor_cache[0])
+        return list(self._plug_in_monitor()[0])
+
+    def _plug_in_monitor(self):
+        """(names, device source) of the monitor a plug-in brings, ([], None) if it brings none; translated once per model.
+        A Python `monitor` with a construct the translation refuses leaves the model without a monitor -- its right-hand
+        side is bound all the same -- and `monitor_refused` says why."""
+        if self._monitor_cache is None:
+            from .rhs_codegen import hip_monitor_from_module, monitor_names_of
+            try:
+                source = hip_monitor_from_module(self.ode)
+            except NotImplementedError as e:
+                source, self.monitor_refused = None, str(e)
+            self._monitor_cache = (monitor_names_of(self.ode) if source is not None else [], source)
+        return self._monitor_cache
+
+    def monitor(self, names=None, t=None):
+        """{name: (nodes,)}: the named intermediates of the right-hand side (`monitor_names`; None: all) at time t
+        (None: the model's time), evaluated on the device from the HOST tables as they stand: one launch of the monitor
+        kernel over a scratch copy of them (knpemi_monitor_eval).  The tables of the handle are not touched."""
+        all_names = self.monitor_names()
+        if not all_names:
+            why = f": its Python `monitor` cannot be translated ({self.monitor_refused})" if self.monitor_refused else ""
+            raise ValueError(f"membrane model '{self.prefix}' brings no monitor" + why)
+        names = list(all_names if names is None else names)
+        unknown = [n for n in names if n not in all_names]
+        if unknown:
+            raise ValueError(f"unknown quantity {unknown[0]!r}: one of {all_names}")
+        idx = sorted({all_names.index(n) for n in names})
+        dp = self._device()
+        states = np.ascontiguousarray(self.states, np.float64)
+        params = np.ascontiguousarray(self.parameters, np.float64)
+        out = np.empty((len(idx), self.nodes), np.float64)
+        L.check(dp.lib.knpemi_monitor_eval(dp.h, self._sub, self._model, float(self.time if t is None else t),
+                                           sum(1 << i for i in idx), L.dptr(states), L.dptr(params), None,
+                                           int(self.V_index), L.dptr(out), out.size))
+        by_index = {i: out[j] for j, i in enumerate(idx)}
+        return {n: by_index[all_names.index(n)] for n in names}
 
     def _set_stimulus(self, stimulus, stimulus_locator):
         dp, lib = self._dp, self._dp.lib

@@ -16,6 +16,10 @@ comparisons (as 0.0 / 1.0 factors, the way `(t < 125e-3)` is used), conditional 
 `math.` / `np.` / `numpy.` functions with a C counterpart and the matching number of arguments (`math.log(x, base)` becomes
 a quotient of logarithms), numeric literals, string statements (the commented-out blocks
 Gotran modules carry) and a trailing `return`.  Anything else raises `NotImplementedError` naming the construct.
+
+A Gotran-style `monitor(states, t, parameters, monitored)` is translated the same way (`hip_monitor_from_python`) into the
+`__device__ void monitor(t, states, parameters, monitored)` that `knpemi_monitor_bind_source` compiles: the same
+constructs, with stores into `monitored[literal]` only.
 """
 from __future__ import annotations
 
@@ -66,12 +70,14 @@ class _Emitter:
     def __init__(self, argnames, n_states=None, n_params=None):
         self.t, self.states, self.values, self.parameters = argnames
         self.sizes = {"states": n_states, "values": n_states, "parameters": n_params}
+        self.out = "values"            # the C name of the output array, and the arrays a statement may store into
+        self.stores = ("values", "parameters")
         self.declared = set()
         self.lines = []
 
     # -- expressions --------------------------------------------------------------------------------------------
     def array(self, name):
-        return {self.states: "states", self.values: "values", self.parameters: "parameters"}.get(name)
+        return {self.states: "states", self.values: self.out, self.parameters: "parameters"}.get(name)
 
     def expr(self, e):
         if isinstance(e, ast.Constant):
@@ -92,7 +98,7 @@ class _Emitter:
             arr = self.array(e.value.id) if isinstance(e.value, ast.Name) else None
             idx = _const_int(e.slice)
             if arr is None or idx is None:
-                raise NotImplementedError("only states[i] / values[i] / parameters[i] with a literal index are indexed")
+                raise NotImplementedError(f"only states[i] / {self.out}[i] / parameters[i] with a literal index are indexed")
             size = self.sizes[arr]
             if idx < 0 or (size is not None and idx >= size):
                 raise NotImplementedError(f"index {idx} of `{arr}` is out of range" + (f" (0 .. {size - 1})" if size else ""))
@@ -160,7 +166,7 @@ class _Emitter:
             self.lines.append(f"  {decl}v_{target.id} = {rhs};")
         elif isinstance(target, ast.Subscript):
             arr = self.array(target.value.id) if isinstance(target.value, ast.Name) else None
-            if arr not in ("values", "parameters"):
+            if arr not in self.stores:
                 raise NotImplementedError(f"store into `{ast.unparse(target)}`")
             self.lines.append(f"  {self.expr(target)} = {rhs};")
         else:
@@ -228,6 +234,56 @@ def hip_source_from_python(source, func=None, n_states=None, n_params=None):
     head = (f"// generated by knpemi.rhs_codegen from the Python function `{fd.name}`\n"
             "__device__ inline void rhs(double t, const double* states, double* values, double* parameters) {\n  (void)t;\n")
     return head + "\n".join(em.lines) + "\n}\n"
+
+
+def hip_monitor_from_python(source, func="monitor", n_states=None, n_params=None, n_monitored=None):
+    """HIP source of `monitor` from the Python source text of a Gotran-style `monitor(states, t, parameters, monitored)`:
+    the constructs of a right-hand side, with stores into `monitored[literal]` only (a monitor changes neither the state
+    nor the parameter row); anything else is refused by name.  `n_monitored`, when known, bounds the literal indices."""
+    tree = ast.parse(textwrap.dedent(source))
+    fd = _function_def(tree, func)
+    args = [a.arg for a in fd.args.args]
+    if len(args) != 4:
+        raise NotImplementedError(f"`{fd.name}` does not have the signature (states, t, parameters, monitored)")
+    states, t, parameters, monitored = args
+    em = _Emitter((t, states, monitored, parameters), n_states, n_params)
+    em.out, em.stores = "monitored", ("monitored",)
+    em.sizes["monitored"] = n_monitored
+    for st in fd.body:
+        em.statement(st)
+    head = (f"// generated by knpemi.rhs_codegen from the Python function `{fd.name}`\n"
+            "__device__ inline void monitor(double t, const double* states, const double* parameters, double* monitored) {\n"
+            "  (void)t;\n")
+    return head + "\n".join(em.lines) + "\n}\n"
+
+
+def monitor_names_of(ode):
+    """The names of a plug-in's monitored quantities, in the order of `monitored`: the module's `MONITOR_NAMES` list or
+    `monitor_names()`; [] for a module that brings no monitor."""
+    names = getattr(ode, "MONITOR_NAMES", None)
+    if names is None and callable(getattr(ode, "monitor_names", None)):
+        names = ode.monitor_names()
+    return list(names or [])
+
+
+def hip_monitor_from_module(ode):
+    """The module's monitor as device source -- its own `MONITOR_HIP`, or its Python `monitor` translated -- or None if it
+    brings neither (or no names to go with it)."""
+    names = monitor_names_of(ode)
+    if not names:
+        return None
+    src = getattr(ode, "MONITOR_HIP", None)
+    if src is not None:
+        return src
+    fn = getattr(ode, "monitor", None)
+    if fn is None:
+        return None
+    try:
+        text = inspect.getsource(getattr(fn, "py_func", fn))
+    except (OSError, TypeError):
+        return None
+    return hip_monitor_from_python(text, getattr(fn, "__name__", "monitor"), len(ode.init_state_values()),
+                                   len(ode.init_parameter_values()), len(names))
 
 
 def hip_source_from_module(ode):

@@ -302,6 +302,28 @@ class DeviceStepper:
         self.taps["track"] = Tap(fm, "field maps", every, lambda t, fields: L.check(lib.knpemi_maps_record(h, t)), t0,
                                  capacity=capacity if read else None, read=read, n_cols=fm.n_cols, rewind=rewind)
 
+    # -- membrane monitors ------------------------------------------------------------------------------
+    def monitor(self, mon, every=1, capacity=1024, t0=0.0, fields=False):
+        """Record the membrane monitors `mon` (knpemi.monitor.MembraneMonitor) on the device after every `every`-th
+        step, at time t0 + k dt for step k: one launch over the membrane dofs of the watched model slots on the main
+        stream, behind the end-of-step update and the other recorders.  It sees the state the next sweep would start
+        from and writes nothing but its own buffers.  Rows collect in a device buffer of `capacity` rows, drained into
+        `mon` as the other series are (whenever it holds `capacity` rows, and when `mon.series()` is called).  fields:
+        every record also writes the per-dof arrays (`mon.values(tag)` reads those of the latest record).
+        Partitioned steps (`step(halo)`) are refused: a rank's reductions would include its ghost dofs."""
+        if every < 1 or capacity < 1:
+            raise ValueError("every and capacity must be positive")
+        if "monitor" in self.taps:
+            raise RuntimeError("this stepper records membrane monitors already")
+        if mon._drain is not None:
+            raise RuntimeError("this monitor is attached to a stepper already")
+        mon._attach(self.dp, capacity)
+        lib, h = self.lib, self.dp.h
+        self.taps["monitor"] = Tap(mon, "membrane monitors", every,
+                                   lambda t, f: L.check(lib.knpemi_monitor_record(h, float(t), f)), t0,
+                                   capacity=capacity, read=self._reader(lib.knpemi_monitor_read), n_cols=mon.n_cols,
+                                   rewind=lambda: L.check(lib.knpemi_monitor_reset(h)), fields=fields)
+
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
         failed on any membrane dof since the last check (the counters live on the device; this synchronises)."""
@@ -352,6 +374,9 @@ class DeviceStepper:
         if halo is not None and "track" in self.taps and self.taps["track"].target.has_series:
             raise NotImplementedError("field maps with a series watch are not recorded on partitioned steps (a rank's "
                                       "sums would include its ghost items): track maps without series=True")
+        if halo is not None and "monitor" in self.taps:
+            raise NotImplementedError("membrane monitors are not recorded on partitioned steps (a rank's reductions would "
+                                      "include its ghost dofs): run DeviceStepper.monitor on one rank")
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
@@ -433,8 +458,8 @@ class DeviceStepper:
         # On the main stream behind the end-of-step update (update_pde_kernel or the fused KNP write-back); the next
         # step's side-stream launches fork from the main stream after it (ev_fork), so none of them overtakes these: the
         # observables' launch, the events' over the membrane dofs, the fluxes' over the cells of the watched sub-domains.
-        # the field maps' over the items of the watched spaces.
-        for name in ("observe", "detect", "fluxes", "track"):
+        # the field maps' over the items of the watched spaces, the monitors' over the dofs of the watched model slots.
+        for name in ("observe", "detect", "fluxes", "track", "monitor"):
             if name in self.taps:
                 self.taps[name].tick(self.k, self.dt)
 
