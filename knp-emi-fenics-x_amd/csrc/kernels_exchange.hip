@@ -210,8 +210,8 @@ int kn_launch_exchange(knpemi_handle* h, int write_fields) {
   if (h->dev.nq_gamma * (1 + h->NF + (h->NF == 4 ? 2 * h->NF : 0)) > EX_QTAB)
     return kn_fail(KNPEMI_EINVAL, "exchange_kernel: the facet quadrature table does not fit its LDS copy (EX_QTAB)");
   const int split = (h->knp_flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
-  const ExArgs a{h->K, X.ser.capacity, split, X.tab, X.part, X.ser.ctl, X.ser.rows, write_fields ? X.fld : nullptr,
-                 X.recorded, X.xbuf ? X.xbuf + (size_t)X.rank * X.ser.n_cols : nullptr};
+  const ExArgs a{h->K, X.ser.capacity, split, X.tab, X.part, X.ser.ctl, X.ser.rows, write_fields ? X.fields.fld : nullptr,
+                 X.recorded, X.slots.xbuf ? X.slots.xbuf + (size_t)X.slots.rank * X.ser.n_cols : nullptr};
   const bool fields = write_fields != 0;
   if (h->NF == 2) launch<2>(h, a, X.n_blk, fields);
   else if (h->NF == 3) launch<3>(h, a, X.n_blk, fields);

@@ -294,7 +294,8 @@ int kn_launch_flux(knpemi_handle* h, int write_fields) {
   const auto& X = h->flux;
   if (X.n_blk == 0) return KNPEMI_OK;      // partitioned, no local cell: this rank's slots stay the zeros of the set-up
   const FluxArgs a{h->K, X.ser.capacity, X.tab, h->d_consts, h->dev.cells, h->dev.VR, X.part, X.ser.ctl, X.ser.rows,
-                   write_fields ? X.fld : nullptr, X.recorded, X.xbuf ? X.xbuf + (size_t)X.rank * X.ser.n_cols : nullptr};
+                   write_fields ? X.fields.fld : nullptr, X.recorded,
+                   X.slots.xbuf ? X.slots.xbuf + (size_t)X.slots.rank * X.ser.n_cols : nullptr};
   const bool fields = write_fields != 0;
   if (h->cell_kind == KNPEMI_TRIANGLE) launch<KNPEMI_TRIANGLE>(h, a, X.n_blk, fields);
   else if (h->cell_kind == KNPEMI_TETRAHEDRON) launch<KNPEMI_TETRAHEDRON>(h, a, X.n_blk, fields);

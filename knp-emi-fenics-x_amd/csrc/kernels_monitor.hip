@@ -81,7 +81,7 @@ int kn_launch_monitor(knpemi_handle* h, double t, int write_fields) {
   const auto& X = h->mon;
   const int f = write_fields ? 1 : 0;
   KnMonArgs a{X.tab, reinterpret_cast<const int*>(X.cols), X.pt_watch, X.pt_q, X.pt_w, X.pt_val, X.part, X.ser.ctl, X.ser.rows,
-              write_fields ? X.fld : nullptr, X.ser.capacity, 0, X.n_blk, t};
+              write_fields ? X.fields.fld : nullptr, X.ser.capacity, 0, X.n_blk, t};
   const KnMonTab& T = X.host;
   for (int w0 = 0; w0 < T.n_watch;) {      // runs of consecutive watches of one program
     int w1 = w0 + 1;

@@ -139,9 +139,9 @@ __global__ __launch_bounds__(OBS_THREADS) void record_combine_kernel(CombineArgs
 
 int kn_launch_observe(knpemi_handle* h) {
   const auto& O = h->obs;
-  if (O.n_blk == 0 && !O.xbuf) return KNPEMI_OK;
+  if (O.n_blk == 0 && !O.slots.xbuf) return KNPEMI_OK;
   ObsArgs a{O.n_obs, O.ser.capacity, O.n_blk, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ser.ctl,
-            O.ser.rows, O.xbuf ? O.xbuf + (size_t)O.rank * O.n_obs : nullptr};
+            O.ser.rows, O.slots.xbuf ? O.slots.xbuf + (size_t)O.slots.rank * O.n_obs : nullptr};
   hipLaunchKernelGGL(observe_kernel, dim3(std::max(O.n_blk, 1)), dim3(OBS_THREADS), 0, h->stream, a);
   return kn_launch_check("observe_kernel");
 }
@@ -155,8 +155,8 @@ int kn_launch_record_combine(knpemi_handle* h, const char* who, int n_cols, int 
 
 int kn_launch_observe_combine(knpemi_handle* h) {
   const auto& O = h->obs;
-  return kn_launch_record_combine(h, "record_combine_kernel (observables)", O.n_obs, O.ser.capacity, O.world, O.rank, O.op,
-                                  O.denom, nullptr, O.xbuf, O.ser.ctl, O.ser.rows);
+  return kn_launch_record_combine(h, "record_combine_kernel (observables)", O.n_obs, O.ser.capacity, O.slots.world, O.slots.rank, O.op,
+                                  O.denom, nullptr, O.slots.xbuf, O.ser.ctl, O.ser.rows);
 }
 
 int kn_observe_chunk() { return OBS_CHUNK; }

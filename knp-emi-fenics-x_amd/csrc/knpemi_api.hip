@@ -1140,9 +1140,7 @@ extern "C" int knpemi_assemble_emi(knpemi_handle* h, int flags) {
 extern "C" int knpemi_join(knpemi_handle* h) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
-  return KNPEMI_OK;
+  return kn_wait_ode_joins(h);
 }
 
 extern "C" int knpemi_assemble_emi_membrane_rhs(knpemi_handle* h, int flags) {
@@ -1178,8 +1176,7 @@ extern "C" int knpemi_assemble_knp(knpemi_handle* h, int flags) {
   KN_HIP(hipSetDevice(h->device));
   // phi_M and I_ch come from the ODE sweeps, which may run on the auxiliary streams: the assembly is ordered after them
   // whether or not the caller has called knpemi_join (a wait on a completed or never-recorded event costs nothing)
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+  if (int rc = kn_wait_ode_joins(h)) return rc;
   h->knp_flags = flags;
   if (flags & KNPEMI_MEMBRANE_EARLY) {   // the integrals were prepared by knpemi_assemble_knp_membrane_early
     if (h->pre_pending) {
@@ -1204,8 +1201,8 @@ extern "C" int knpemi_solve_emi(knpemi_handle* h, double rtol, double atol, int 
   if (!(rtol >= 0) || !(atol >= 0) || maxit < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_solve_emi: bad tolerances");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));   // a matrix assembled on the auxiliary stream is complete
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));  // ... and so is every sweep whose output the right-hand side holds
+  // a matrix assembled on the auxiliary stream is complete, and so is every sweep whose output the right-hand side holds
+  if (int rc = kn_wait_ode_joins(h)) return rc;
   return kn_solve_emi(h, rtol, atol, maxit, iters, relres);
 }
 
@@ -1217,8 +1214,7 @@ extern "C" int knpemi_solve_knp(knpemi_handle* h, double rtol, double atol, int 
   // every writer of A_knp, b_knp and their inputs (the potential, phi_M, I_ch) is on the main stream or joined into it
   // before the set-up's device-to-host copy and the first iteration read them (round-3 advisor finding: this entry point
   // waited on neither join event)
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+  if (int rc = kn_wait_ode_joins(h)) return rc;
   return kn_solve_knp(h, rtol, atol, maxit, iters, relres);
 }
 
@@ -1374,8 +1370,7 @@ extern "C" int knpemi_set_solution(knpemi_handle* h, int which, const double* x,
     // a solution pasted on the device stands for the write-back of knpemi_solve_emi: the same launch, facet integrals of
     // b_knp included (KNPEMI_OPT_FOLD_MEMBRANE), which read phi_M and I_ch: ordered after the sweeps on the side streams
     if (on_device && h->fold_membrane && h->have_params && !h->fuse_membrane && !h->dist.on) {
-      KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-      KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+      if (int rc = kn_wait_ode_joins(h)) return rc;
       if (int rc = kn_launch_emi_writeback_membrane(h, src, nullptr, 0, 0.0, nullptr)) return rc;
       kn_gam_formed(h, (h->emi_flags & KNPEMI_NO_SPLITTING) ? 0 : 1);
     } else if (int rc = kn_launch_field_scatter(h, src, D.VR + 7, D.Ntot, KN_REC)) return rc;

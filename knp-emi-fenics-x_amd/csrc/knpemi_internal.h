@@ -616,6 +616,27 @@ struct knpemi_handle : KnDevice {
     double* rows = nullptr;              // [capacity][n_cols]
     int capacity = 0, n_cols = 0;
   };
+  // A partitioned record's place among the ranks (knpemi_*_set_partitioned): the caller's [world][n_cols] exchange buffer,
+  // summed over the ranks by `allreduce` (or the library's communicator when it is null) between the record launch, which
+  // writes this rank's slots, and the combine launch.  xbuf == nullptr: not partitioned.
+  struct KnRankSlots {
+    double* xbuf = nullptr;
+    int rank = 0, world = 1;
+    knpemi_allreduce_fn allreduce = nullptr;
+    void* ctx = nullptr;
+  };
+  // The time of the previous record of a recorder that integrates over the interval between two records.
+  struct KnRecordClock {
+    bool have_prev = false;              // a record has been enqueued since the set-up / the last reset ...
+    double t_prev = 0.0;                 // ... at this time
+  };
+  // Per-item fields: allocated at the first record that writes them, read back while a record since the set-up / the last
+  // reset has written them.
+  struct KnItemFields {
+    double* fld = nullptr;
+    size_t fld_len = 0;
+    bool fld_valid = false;
+  };
   // observables (knpemi_observe_set, kernels_observe.hip)
   struct KnObserve {
     int n_obs = 0, n_blk = 0;
@@ -629,20 +650,14 @@ struct knpemi_handle : KnDevice {
     double* w = nullptr;                 // [entries]
     double* part = nullptr;              // [n_blk] block partials
     KnSeries ser;
-    // partitioned runs (knpemi_observe_set_partitioned): the caller's [world][n_obs] exchange buffer, summed over the
-    // ranks by `allreduce` (or the library's communicator when it is null) between the partial and the combine launch
-    double* xbuf = nullptr;
-    int rank = 0, world = 1;
-    knpemi_allreduce_fn allreduce = nullptr;
-    void* ctx = nullptr;
+    KnRankSlots slots;                   // knpemi_observe_set_partitioned: [world][n_obs]
     std::vector<void*> allocs;
   } obs;
   // membrane events (knpemi_events_set, kernels_events.hip)
   struct KnEvents {
     int n_watch = 0, keep = 0, n_grid = 0;
     bool watched[KN_MAXSUB] = {};
-    bool have_prev = false;              // a record has been enqueued since the set-up / the last reset ...
-    double t_prev = 0.0;                 // ... at this time
+    KnRecordClock clock;
     KnEvTab* tab = nullptr;
     // state over the concatenated membrane dofs ([NQtot]; the ring [keep][NQtot])
     double* v_prev = nullptr;
@@ -660,24 +675,18 @@ struct knpemi_handle : KnDevice {
     KnWatchTab* tab = nullptr;
     double* part = nullptr;              // [n_blk][slots] workgroup partials
     KnSeries ser;
-    double* fld = nullptr;               // per-item fields, allocated at the first record that writes them
-    size_t fld_len = 0;
-    bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
+    KnItemFields fields;
     // partitioned runs (knpemi_<name>_set_partitioned): one byte per item in watch order (1: this rank's sums and maxima
-    // count it), and the caller's [world][n_cols] exchange buffer, summed over the ranks as KnObserve's
+    // count it), and the rank's slots of [world][n_cols]
     uint8_t* recorded = nullptr;
-    double* xbuf = nullptr;
-    int rank = 0, world = 1;
-    knpemi_allreduce_fn allreduce = nullptr;
-    void* ctx = nullptr;
+    KnRankSlots slots;
     std::vector<void*> allocs;
   } flux, exchange;
   // field maps (knpemi_maps_set, kernels_maps.hip): per-item state arrays of every watch and, with a series watch, workgroup
   // partials and a series
   struct KnMaps {
     int n_watch = 0, n_blk = 0;
-    bool have_prev = false;              // a record has been enqueued since the set-up / the last reset ...
-    double t_prev = 0.0;                 // ... at this time
+    KnRecordClock clock;
     KnMapTab host{};                     // the table as uploaded
     int slot_of[KNPEMI_MAPS_MAX_WATCH] = {};   // watch of knpemi_maps_set -> entry of the table (grouped by space)
     int items_of[KNPEMI_MAPS_MAX_WATCH] = {};  // ... and its number of items
@@ -701,13 +710,19 @@ struct knpemi_handle : KnDevice {
     double* pt_val = nullptr;            // [n_pts][4][KN_MON_MAX] what the last workgroup evaluates at the points' dofs
     double* part = nullptr;              // [n_blk][KN_MON_SLOTS] workgroup partials
     KnSeries ser;
-    double* fld = nullptr;               // per-dof fields, allocated at the first record that writes them
-    size_t fld_len = 0;
-    bool fld_valid = false;              // a record with fields has been enqueued since the set-up / the last reset
+    KnItemFields fields;                 // per dof
     std::vector<void*> allocs;
   } mon;
   int knp_flags = 0;                  // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
 };
+
+// The main stream waits for the membrane ODE sweeps on the auxiliary streams: what follows reads phi_M, I_ch or the models'
+// tables.  (An ODE-only handle has no side streams and no events.)
+static inline int kn_wait_ode_joins(knpemi_handle* h) {
+  if (h->ev_join) KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+  if (h->ev_join2) KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
+  return KNPEMI_OK;
+}
 
 inline void kn_inputs_changed(knpemi_handle* h) { ++h->inputs_gen; }
 inline void kn_gam_formed(knpemi_handle* h, int split) { h->gam_gen = h->inputs_gen; h->gam_split = split; }

@@ -3,12 +3,17 @@
 // the field maps (kernels_maps.hip: per-item maps as the events, and a series with a series watch), and the membrane
 // monitors (kernels_monitor.hip: a series and per-dof fields of the models' named intermediates).
 //
-// Three of them append rows to a series buffer (KnSeries; the device side is record_tail.h).  The fluxes and the exchange
-// are one recorder over different items -- the cells of a watched sub-domain, the membrane facets of a watched cell: they
-// share KnWatched, KnWatchTab and every routine but the launch, and a WatchKind names what differs.  The membrane events
-// keep per-dof maps and no series.  On a cell partition the three series recorders follow one scheme: the record launch
-// writes the rank's partial row into its slots of an exchange buffer, the buffer is summed over the ranks, and
-// record_combine_kernel (kernels_observe.hip) folds the slots in rank order and appends the row.
+// All but the events append rows to a series buffer (KnSeries; the device side is record_tail.h; the maps only with a
+// series watch).  The fluxes and the exchange are one recorder over different items -- the cells of a watched sub-domain,
+// the membrane facets of a watched cell: they share KnWatched, KnWatchTab and every routine but the launch, and a
+// WatchKind names what differs.  The membrane events keep per-dof maps and no series.
+//
+// What several recorders need is written once, as a small struct of the handle and its routines below: the install rule of
+// every knpemi_*_set (New, recorder_install), the rank slots of a partitioned record (KnRankSlots: observables, fluxes,
+// exchange -- the record launch writes the rank's partial row into its slots of an exchange buffer, slots_sum sums the
+// buffer over the ranks, and record_combine_kernel (kernels_observe.hip) folds the slots in rank order and appends the
+// row), the clock of the recorders that integrate between two records (KnRecordClock: events, maps) and the per-item
+// fields (KnItemFields: fluxes, exchange, monitors).
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -73,6 +78,74 @@ int recorder_clear(knpemi_handle* h, R knpemi_handle::*which) {
   recorder_free(h->*which);
   return KNPEMI_OK;
 }
+// The install rule of every knpemi_*_set: the new recorder is built in a local New<R>, whose allocations go to its own
+// `allocs`.  A return before recorder_install frees that list, and the previous recorder is untouched and still records;
+// recorder_install frees the previous one, which an enqueued record may still read, behind a synchronisation and copies
+// the new one in.
+template <class R>
+struct New : R {
+  ~New() { kn_free_all(this->allocs); }
+};
+template <class R>
+int recorder_install(knpemi_handle* h, R knpemi_handle::*which, New<R>& next) {
+  KN_HIP(hipStreamSynchronize(h->stream));
+  recorder_free(h->*which);
+  h->*which = next;
+  next.allocs.clear();
+  return KNPEMI_OK;
+}
+
+// -- a partitioned record's rank slots (KnRankSlots); max_cols: the caller's bound on the columns of one rank
+using KnRankSlots = knpemi_handle::KnRankSlots;
+int slots_check(const knpemi_handle* h, const std::string& fn, const KnRankSlots& s, size_t max_cols) {
+  if (s.world < 1 || s.rank < 0 || s.rank >= s.world) return kn_fail(KNPEMI_EINVAL, fn + ": bad rank / world");
+  if (!s.xbuf) return kn_fail(KNPEMI_EINVAL, fn + ": exchange buffer is required");
+  if (!s.allreduce && !h->comm)
+    return kn_fail(KNPEMI_EINVAL, fn + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
+  if ((size_t)s.world * max_cols > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, fn + ": exchange buffer too large");
+  return KNPEMI_OK;
+}
+// all zero: this rank's slots are written by the records (never, without local items), the others' by the sum
+int slots_attach(knpemi_handle* h, KnRankSlots* to, const KnRankSlots& s, int n_cols) {
+  *to = s;
+  KN_HIP(hipMemsetAsync(s.xbuf, 0, (size_t)s.world * n_cols * sizeof(double), h->stream));
+  KN_HIP(hipStreamSynchronize(h->stream));
+  return KNPEMI_OK;
+}
+// between the record launch, which has written this rank's slots, and the combine launch: the sum over the ranks
+int slots_sum(knpemi_handle* h, const std::string& fn, const KnRankSlots& s, int n_cols) {
+  const int n = s.world * n_cols;
+  if (!s.allreduce) return knpemi_comm_allreduce(h, s.xbuf, n);
+  return s.allreduce(s.ctx, n) ? kn_fail(KNPEMI_EHIP, fn + ": allreduce hook failed") : KNPEMI_OK;
+}
+
+// -- the record clock (KnRecordClock)
+using KnRecordClock = knpemi_handle::KnRecordClock;
+int clock_accept(const KnRecordClock& c, const char* fn, double t) {
+  if (!std::isfinite(t) || (c.have_prev && !(t > c.t_prev)))
+    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": t must be finite and greater than the previous record's");
+  return KNPEMI_OK;
+}
+void clock_advance(KnRecordClock& c, double t) { c = {true, t}; }
+void clock_restart(KnRecordClock& c) { c = {}; }
+
+// -- per-item fields (KnItemFields)
+using KnItemFields = knpemi_handle::KnItemFields;
+// a record launch: the first one that writes the fields allocates them, in the recorder's `owner`
+template <class Launch>
+int fields_record(KnItemFields& F, std::vector<void*>& owner, int write_fields, Launch launch) {
+  if (write_fields && !F.fld)
+    if (int rc = kn_alloc(owner, std::max<size_t>(F.fld_len, 1), &F.fld)) return rc;
+  if (int rc = launch()) return rc;
+  if (write_fields) F.fld_valid = true;
+  return KNPEMI_OK;
+}
+// a new series: the fields of the old one are forgotten
+void fields_forget(KnItemFields& F) { F.fld_valid = false; }
+// knpemi_*_fields; record_call: the call that writes them
+int fields_recorded(const KnItemFields& F, const std::string& fn, const std::string& record_call) {
+  return F.fld_valid ? KNPEMI_OK : kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (" + record_call + ")");
+}
 }  // namespace
 
 void kn_record_free(knpemi_handle* h) {
@@ -84,10 +157,11 @@ void kn_record_free(knpemi_handle* h) {
 // observables (kernels_observe.hip)
 // ---------------------------------------------------------------------------------------------------
 namespace {
-// knpemi_observe_set and knpemi_observe_set_partitioned; the partitioned table may hold observables without entries
+// knpemi_observe_set and, with `part`, knpemi_observe_set_partitioned, whose table may hold observables without entries
 int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
-                const double* w, const double* denom, int capacity, bool partitioned) {
+                const double* w, const double* denom, int capacity, const KnRankSlots* part = nullptr) {
   const std::string fn(who);
+  const bool partitioned = part != nullptr;
   if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
   if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
   if (n_obs < 1 || capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": n_obs and capacity must be positive");
@@ -115,29 +189,26 @@ int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spe
     blk_ptr.push_back((int)blk.size());
   }
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  recorder_free(h->obs);
-  auto& O = h->obs;
+  New<knpemi_handle::KnObserve> O;
   const size_t ne = (size_t)ptr[n_obs];
   int rc;
   auto& A = O.allocs;
   if ((rc = kn_upload(A, blk, &O.blk)) || (rc = kn_upload(A, blk_ptr, &O.blk_ptr)) || (rc = kn_upload(A, op, &O.op))
       || (rc = kn_upload(A, stride, &O.stride)) || (rc = kn_upload(A, base, &O.base))
       || (rc = kn_upload(A, denom, (size_t)n_obs, &O.denom))
-      || (rc = kn_upload(A, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = kn_upload(A, w, ne, &O.w))) {
-    recorder_free(h->obs);
+      || (rc = kn_upload(A, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = kn_upload(A, w, ne, &O.w)))
     return rc;
-  }
-  if (kn_alloc(A, blk.size(), &O.part)) { recorder_free(h->obs); return kn_fail(KNPEMI_ENOMEM, fn + ": partials"); }
-  if (series_alloc(A, h->stream, capacity, n_obs, &O.ser)) { recorder_free(h->obs); return kn_fail(KNPEMI_ENOMEM, fn + ": buffer"); }
+  if (kn_alloc(A, blk.size(), &O.part)) return kn_fail(KNPEMI_ENOMEM, fn + ": partials");
+  if (series_alloc(A, h->stream, capacity, n_obs, &O.ser)) return kn_fail(KNPEMI_ENOMEM, fn + ": buffer");
   O.n_obs = n_obs; O.n_blk = (int)blk.size();
-  return KNPEMI_OK;
+  if (part && (rc = slots_attach(h, &O.slots, *part, n_obs))) return rc;
+  return recorder_install(h, &knpemi_handle::obs, O);
 }
 }  // namespace
 
 extern "C" int knpemi_observe_set(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
                                   const int32_t* idx, const double* w, const double* denom, int capacity) {
-  return observe_set(h, "knpemi_observe_set", n_obs, spec, ptr, idx, w, denom, capacity, false);
+  return observe_set(h, "knpemi_observe_set", n_obs, spec, ptr, idx, w, denom, capacity);
 }
 
 extern "C" int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const int32_t* spec, const int64_t* ptr,
@@ -146,20 +217,9 @@ extern "C" int knpemi_observe_set_partitioned(knpemi_handle* h, int n_obs, const
                                               void* ctx) {
   const char* fn = "knpemi_observe_set_partitioned";
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  if (world < 1 || rank < 0 || rank >= world) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": bad rank / world");
-  if (!xbuf_dev) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer is required");
-  if (!allreduce && !h->comm)
-    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
-  if (n_obs > 0 && (size_t)world * (size_t)n_obs > (size_t)INT32_MAX)
-    return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": exchange buffer too large");
-  int rc = observe_set(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, true);
-  if (rc) return rc;
-  auto& O = h->obs;
-  O.xbuf = static_cast<double*>(xbuf_dev);
-  O.rank = rank; O.world = world; O.allreduce = allreduce; O.ctx = ctx;
-  KN_HIP(hipMemsetAsync(O.xbuf, 0, (size_t)world * n_obs * sizeof(double), h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  const KnRankSlots part{static_cast<double*>(xbuf_dev), rank, world, allreduce, ctx};
+  if (int rc = slots_check(h, fn, part, (size_t)std::max(n_obs, 0))) return rc;
+  return observe_set(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, &part);
 }
 
 extern "C" int knpemi_observe_record(knpemi_handle* h) {
@@ -168,12 +228,9 @@ extern "C" int knpemi_observe_record(knpemi_handle* h) {
   if (O.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
   KN_HIP(hipSetDevice(h->device));
   int rc = kn_launch_observe(h);
-  if (rc || !O.xbuf) return rc;
+  if (rc || !O.slots.xbuf) return rc;
   // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
-  const int n = O.world * O.n_obs;
-  rc = O.allreduce ? (O.allreduce(O.ctx, n) ? kn_fail(KNPEMI_EHIP, "knpemi_observe_record: allreduce hook failed") : KNPEMI_OK)
-                   : knpemi_comm_allreduce(h, O.xbuf, n);
-  if (rc) return rc;
+  if ((rc = slots_sum(h, "knpemi_observe_record", O.slots, O.n_obs))) return rc;
   return kn_launch_observe_combine(h);
 }
 
@@ -211,35 +268,30 @@ extern "C" int knpemi_events_set(knpemi_handle* h, int n_watch, const int32_t* s
   }
   T.n_watch = n_watch;
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  recorder_free(h->events);
-  auto& E = h->events;
+  New<knpemi_handle::KnEvents> E;
   auto& A = E.allocs;
   const size_t nq = (size_t)h->dev.NQtot;
   int rc;
   if ((rc = kn_upload(A, &T, 1, &E.tab)) || (rc = kn_alloc(A, nq, &E.v_prev)) || (rc = kn_alloc(A, nq, &E.armed))
       || (rc = kn_alloc(A, nq, &E.count)) || (rc = kn_alloc(A, nq, &E.t_first)) || (rc = kn_alloc(A, nq, &E.t_last))
       || (rc = kn_alloc(A, nq, &E.v_peak)) || (rc = kn_alloc(A, nq, &E.t_peak))
-      || (rc = kn_alloc(A, nq * (size_t)keep, &E.ring))) {
-    recorder_free(h->events);
+      || (rc = kn_alloc(A, nq * (size_t)keep, &E.ring)))
     return rc;
-  }
   E.n_watch = n_watch; E.keep = keep; E.n_grid = T.gstart[n_watch];
   std::copy(watched, watched + KN_MAXSUB, E.watched);
-  if ((rc = kn_launch_events_reset(h))) { recorder_free(h->events); return rc; }
-  return KNPEMI_OK;
+  if ((rc = recorder_install(h, &knpemi_handle::events, E))) return rc;
+  if ((rc = kn_launch_events_reset(h))) recorder_free(h->events);
+  return rc;
 }
 
 extern "C" int knpemi_events_record(knpemi_handle* h, double t) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   auto& E = h->events;
   if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: no events set (knpemi_events_set)");
-  if (!std::isfinite(t) || (E.have_prev && !(t > E.t_prev)))
-    return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: t must be finite and greater than the previous record's");
+  if (int rc = clock_accept(E.clock, "knpemi_events_record", t)) return rc;
   KN_HIP(hipSetDevice(h->device));
-  if (int rc = kn_launch_events_record(h, E.have_prev ? 0 : 1, t, E.t_prev)) return rc;
-  E.have_prev = true;
-  E.t_prev = t;
+  if (int rc = kn_launch_events_record(h, E.clock.have_prev ? 0 : 1, t, E.clock.t_prev)) return rc;
+  clock_advance(E.clock, t);
   return KNPEMI_OK;
 }
 
@@ -274,8 +326,7 @@ extern "C" int knpemi_events_reset(knpemi_handle* h) {
   auto& E = h->events;
   if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_reset: no events set (knpemi_events_set)");
   KN_HIP(hipSetDevice(h->device));
-  E.have_prev = false;
-  E.t_prev = 0.0;
+  clock_restart(E.clock);
   return kn_launch_events_reset(h);
 }
 
@@ -313,10 +364,7 @@ inline int ions_below(int m, int ion) { return popcount(m & (ion == -1 ? 0xFF : 
 // what knpemi_<name>_set_partitioned adds to knpemi_<name>_set
 struct WatchPart {
   const uint8_t* recorded;
-  int rank, world;
-  void* xbuf_dev;
-  knpemi_allreduce_fn allreduce;
-  void* ctx;
+  KnRankSlots slots;
 };
 
 // knpemi_<name>_set and, with `part`, knpemi_<name>_set_partitioned: a watch may then have no local item (no workgroup,
@@ -330,12 +378,8 @@ int watched_set(knpemi_handle* h, const WatchKind& k, const std::vector<int>& of
   const std::string fn = entry(k, part ? "set_partitioned" : "set");
   if (!h || !sub || !ion_mask) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
   if (part) {
-    if (part->world < 1 || part->rank < 0 || part->rank >= part->world) return kn_fail(KNPEMI_EINVAL, fn + ": bad rank / world");
-    if ((size_t)part->world * KN_WATCH_MAXCOLS > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, fn + ": exchange buffer too large");
+    if (int rc = slots_check(h, fn, part->slots, KN_WATCH_MAXCOLS)) return rc;
     if (!part->recorded) return kn_fail(KNPEMI_EINVAL, fn + ": the recorded mask is required");
-    if (!part->xbuf_dev) return kn_fail(KNPEMI_EINVAL, fn + ": exchange buffer is required");
-    if (!part->allreduce && !h->comm)
-      return kn_fail(KNPEMI_EINVAL, fn + ": no all-reduce hook and no library communicator (knpemi_comm_init)");
   }
   if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
   if (n_watch < 1 || n_watch > KN_MAXSUB) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAX_SUB " + k.watch + "s");
@@ -369,56 +413,37 @@ int watched_set(knpemi_handle* h, const WatchKind& k, const std::vector<int>& of
   T.n_watch = n_watch; T.n_cols = col;
   if (n_items > (long long)INT32_MAX) return kn_fail(KNPEMI_EINVAL, fn + ": too many " + k.items);
   KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  KnWatched& X = h->*k.state;
-  recorder_free(X);
+  New<KnWatched> X;
   const int n_blk = T.bstart[n_watch];
   int rc;
   if ((rc = kn_upload(X.allocs, &T, 1, &X.tab)) || (rc = kn_alloc(X.allocs, (size_t)n_blk * k.slots, &X.part))
-      || (rc = series_alloc(X.allocs, h->stream, capacity, col, &X.ser))) {
-    recorder_free(X);
+      || (rc = series_alloc(X.allocs, h->stream, capacity, col, &X.ser)))
     return rc;
-  }
   if (part) {
-    if (n_items && (rc = kn_upload(X.allocs, part->recorded, (size_t)n_items, &X.recorded))) { recorder_free(X); return rc; }
-    X.xbuf = static_cast<double*>(part->xbuf_dev);
-    X.rank = part->rank; X.world = part->world; X.allreduce = part->allreduce; X.ctx = part->ctx;
-    // all zero: this rank's slots are written by the records (never, without local items), the others' by the sum
-    if (hipMemsetAsync(X.xbuf, 0, (size_t)part->world * col * sizeof(double), h->stream) != hipSuccess
-        || hipStreamSynchronize(h->stream) != hipSuccess) {
-      recorder_free(X);
-      return kn_fail(KNPEMI_EHIP, fn + ": the exchange buffer cannot be zeroed");
-    }
+    if (n_items && (rc = kn_upload(X.allocs, part->recorded, (size_t)n_items, &X.recorded))) return rc;
+    if ((rc = slots_attach(h, &X.slots, part->slots, col))) return rc;
   }
-  X.host = T; X.n_watch = n_watch; X.n_blk = n_blk; X.fld_len = (size_t)fbase;
+  X.host = T; X.n_watch = n_watch; X.n_blk = n_blk; X.fields.fld_len = (size_t)fbase;
   std::copy(watch_of, watch_of + KN_MAXSUB, X.watch_of);
-  return KNPEMI_OK;
+  return recorder_install(h, k.state, X);
 }
 
-// knpemi_<name>_record: the field buffer is allocated by the first record that writes it
+// knpemi_<name>_record
 int watched_record(knpemi_handle* h, const WatchKind& k, int write_fields) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KnWatched& X = h->*k.state;
   if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, entry(k, "record") + ": " + k.none);
   if (!h->have_params) return kn_fail(KNPEMI_EINVAL, entry(k, "record") + ": knpemi_set_params not called");
   KN_HIP(hipSetDevice(h->device));
-  if (k.after_ode) {     // as in knpemi_assemble_knp
-    KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-    KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
-  }
-  if (write_fields && !X.fld)
-    if (int rc = kn_alloc(X.allocs, std::max<size_t>(X.fld_len, 1), &X.fld)) return rc;
-  if (int rc = k.launch(h, write_fields)) return rc;
-  if (write_fields) X.fld_valid = true;
-  if (!X.xbuf) return KNPEMI_OK;
+  if (k.after_ode)
+    if (int rc = kn_wait_ode_joins(h)) return rc;
+  if (int rc = fields_record(X.fields, X.allocs, write_fields, [&] { return k.launch(h, write_fields); })) return rc;
+  if (!X.slots.xbuf) return KNPEMI_OK;
   // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
-  const int n = X.world * X.ser.n_cols;
-  int rc = X.allreduce ? (X.allreduce(X.ctx, n) ? kn_fail(KNPEMI_EHIP, entry(k, "record") + ": allreduce hook failed") : KNPEMI_OK)
-                       : knpemi_comm_allreduce(h, X.xbuf, n);
-  if (rc) return rc;
-  return kn_launch_record_combine(h, k.combine, X.ser.n_cols, X.ser.capacity, X.world, X.rank, nullptr, nullptr,
-                                  reinterpret_cast<const uint8_t*>(X.tab) + offsetof(KnWatchTab, col_max), X.xbuf, X.ser.ctl,
-                                  X.ser.rows);
+  if (int rc = slots_sum(h, entry(k, "record"), X.slots, X.ser.n_cols)) return rc;
+  return kn_launch_record_combine(h, k.combine, X.ser.n_cols, X.ser.capacity, X.slots.world, X.slots.rank, nullptr, nullptr,
+                                  reinterpret_cast<const uint8_t*>(X.tab) + offsetof(KnWatchTab, col_max), X.slots.xbuf,
+                                  X.ser.ctl, X.ser.rows);
 }
 
 // knpemi_<name>_reset: a new series, stream-ordered; the fields of the old one are forgotten
@@ -427,7 +452,7 @@ int watched_reset(knpemi_handle* h, const WatchKind& k) {
   KnWatched& X = h->*k.state;
   if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, entry(k, "reset") + ": " + k.none);
   KN_HIP(hipSetDevice(h->device));
-  X.fld_valid = false;
+  fields_forget(X.fields);
   return series_rewind(h, X.ser);
 }
 
@@ -454,11 +479,11 @@ int fields_copy(knpemi_handle* h, const WatchKind& k, int w, size_t offset, doub
                 const char* length) {
   const std::string fn = entry(k, "fields");
   const KnWatched& X = h->*k.state;
-  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (" + entry(k, "record") + "(h, 1))");
+  if (int rc = fields_recorded(X.fields, fn, entry(k, "record") + "(h, 1)")) return rc;
   if (n != want) return kn_fail(KNPEMI_EINVAL, fn + ": length is not " + length);
   if (n == 0) return KNPEMI_OK;      // partitioned: no local item
   KN_HIP(hipSetDevice(h->device));
-  return kn_to_host(h->stream, host, X.fld + X.host.fbase[w] + offset, n);
+  return kn_to_host(h->stream, host, X.fields.fld + X.host.fbase[w] + offset, n);
 }
 }  // namespace
 
@@ -501,13 +526,13 @@ extern "C" int knpemi_exchange_set(knpemi_handle* h, int n_watch, const int32_t*
 extern "C" int knpemi_flux_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask,
                                            int capacity, const uint8_t* recorded, int rank, int world, void* xbuf_dev,
                                            knpemi_allreduce_fn allreduce, void* ctx) {
-  const WatchPart part{recorded, rank, world, xbuf_dev, allreduce, ctx};
+  const WatchPart part{recorded, {static_cast<double*>(xbuf_dev), rank, world, allreduce, ctx}};
   return flux_set(h, n_watch, sub, ion_mask, capacity, &part);
 }
 extern "C" int knpemi_exchange_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* sub, const int32_t* ion_mask,
                                                int capacity, const uint8_t* recorded, int rank, int world, void* xbuf_dev,
                                                knpemi_allreduce_fn allreduce, void* ctx) {
-  const WatchPart part{recorded, rank, world, xbuf_dev, allreduce, ctx};
+  const WatchPart part{recorded, {static_cast<double*>(xbuf_dev), rank, world, allreduce, ctx}};
   return exchange_set(h, n_watch, sub, ion_mask, capacity, &part);
 }
 
@@ -593,8 +618,8 @@ extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spe
     if (++per_space[space[w]] > KNPEMI_MAPS_MAX_PER_SPACE)
       return kn_fail(KNPEMI_EINVAL, fn + ": more than KNPEMI_MAPS_MAX_PER_SPACE watches on one space");
   }
-  // the table, grouped by space; nothing of the previous recorder is touched before every allocation has succeeded
-  knpemi_handle::KnMaps N;
+  // the table, grouped by space
+  New<knpemi_handle::KnMaps> N;
   KnMapTab& T = N.host;
   std::vector<size_t> w_off(n_watch, 0);      // a series watch's place in `weight`
   {
@@ -626,10 +651,10 @@ extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spe
       } else {      // a slot of the vertex records: every read of the kernel stays inside the record of a vertex of `sub`
         W.slot = (int)((loc[w].base - h->dev.VR) % KN_REC);
         if (loc[w].stride != KN_REC || W.slot < 3 || n != (size_t)T.n_items[p])
-          return kn_free_all(N.allocs), kn_fail(KNPEMI_EINVAL, fn + ": field layout not understood");
+          return kn_fail(KNPEMI_EINVAL, fn + ": field layout not understood");
         T.need_rec[p] = 1;
       }
-      if (n != (size_t)T.n_items[p]) return kn_free_all(N.allocs), kn_fail(KNPEMI_EINVAL, fn + ": field length is not the space's");
+      if (n != (size_t)T.n_items[p]) return kn_fail(KNPEMI_EINVAL, fn + ": field length is not the space's");
       W.flags = fl;
       W.ser = -1;
       W.thr = (fl & KNPEMI_MAPS_THRESHOLD) ? threshold[w] : 0.0;
@@ -648,7 +673,7 @@ extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spe
         rc = kn_upload(N.allocs, weight + w_off[w], n, &dw);
         W.weight = dw;
       }
-      if (rc) return kn_free_all(N.allocs), rc;
+      if (rc) return rc;
       N.slot_of[w] = k;
       N.items_of[w] = (int)n;
       col_of[w] = W.ser;
@@ -673,25 +698,20 @@ extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spe
     rc = kn_alloc(N.allocs, (size_t)N.n_blk * KN_MAPS_SLOTS, &N.part);
     if (!rc) rc = series_alloc(N.allocs, h->stream, capacity, T.n_cols, &N.ser);
   }
-  if (rc) return kn_free_all(N.allocs), rc;
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  recorder_free(h->maps);
-  h->maps = N;
-  if ((rc = kn_launch_maps_reset(h))) { recorder_free(h->maps); return rc; }
-  return KNPEMI_OK;
+  if (rc || (rc = recorder_install(h, &knpemi_handle::maps, N))) return rc;
+  if ((rc = kn_launch_maps_reset(h))) recorder_free(h->maps);
+  return rc;
 }
 
 extern "C" int knpemi_maps_record(knpemi_handle* h, double t) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   auto& M = h->maps;
   if (M.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_maps_record: no maps set (knpemi_maps_set)");
-  if (!std::isfinite(t) || (M.have_prev && !(t > M.t_prev)))
-    return kn_fail(KNPEMI_EINVAL, "knpemi_maps_record: t must be finite and greater than the previous record's");
+  if (int rc = clock_accept(M.clock, "knpemi_maps_record", t)) return rc;
   KN_HIP(hipSetDevice(h->device));
   // the first record's interval is never used: every v_prev is NaN then
-  if (int rc = kn_launch_maps_record(h, t, M.have_prev ? M.t_prev : t)) return rc;
-  M.have_prev = true;
-  M.t_prev = t;
+  if (int rc = kn_launch_maps_record(h, t, M.clock.have_prev ? M.clock.t_prev : t)) return rc;
+  clock_advance(M.clock, t);
   return KNPEMI_OK;
 }
 
@@ -737,8 +757,7 @@ extern "C" int knpemi_maps_reset(knpemi_handle* h) {
   auto& M = h->maps;
   if (M.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_maps_reset: no maps set (knpemi_maps_set)");
   KN_HIP(hipSetDevice(h->device));
-  M.have_prev = false;
-  M.t_prev = 0.0;
+  clock_restart(M.clock);
   if (M.host.n_cols > 0)
     if (int rc = series_rewind(h, M.ser)) return rc;
   return kn_launch_maps_reset(h);
@@ -784,13 +803,6 @@ int mon_watch(knpemi_handle* h, const std::string& fn, int sub, int model, uint3
   *slot = h->moff[sub] + model;
   return KNPEMI_OK;
 }
-
-// the record reads phi_M and the tables, which the ODE sweeps may write on the auxiliary streams (as knpemi_assemble_knp)
-int mon_after_ode(knpemi_handle* h) {
-  if (h->ev_join) KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  if (h->ev_join2) KN_HIP(hipStreamWaitEvent(h->stream, h->ev_join2, 0));
-  return KNPEMI_OK;
-}
 }  // namespace
 
 extern "C" int knpemi_monitor_bind_source(knpemi_handle* h, int sub, int model, int n_monitored, const char* monitor_source) {
@@ -817,7 +829,7 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
   if (n_watch < 1 || n_watch > KN_MON_MAXW) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MON_MAX_WATCH watches");
   if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
   if (n_cols < 0 || n_pts < 0 || n_pts > (1 << 20)) return kn_fail(KNPEMI_EINVAL, fn + ": bad number of columns or points");
-  knpemi_handle::KnMon N;
+  New<knpemi_handle::KnMon> N;
   KnMonTab& T = N.host;
   std::vector<size_t> woff(n_watch);
   size_t wo = 0;
@@ -874,7 +886,7 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
     cols[c] = make_int4(kind, w, qty, kind == KNPEMI_MON_POINT ? pt : 0);
   }
   T.n_watch = n_watch; T.n_cols = n_cols; T.n_pts = n_pts;
-  N.n_watch = n_watch; N.n_blk = T.bstart[n_watch]; N.fld_len = (size_t)fbase;
+  N.n_watch = n_watch; N.n_blk = T.bstart[n_watch]; N.fields.fld_len = (size_t)fbase;
   KN_HIP(hipSetDevice(h->device));
   auto& A = N.allocs;
   int rc = KNPEMI_OK;
@@ -887,11 +899,7 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
   if (!rc) rc = kn_alloc(A, 4 * (size_t)n_pts * KN_MON_MAX, &N.pt_val);
   if (!rc) rc = kn_alloc(A, (size_t)N.n_blk * KN_MON_SLOTS, &N.part);
   if (!rc) rc = series_alloc(A, h->stream, capacity, n_cols, &N.ser);
-  if (rc) return kn_free_all(N.allocs), rc;
-  KN_HIP(hipStreamSynchronize(h->stream));     // a previous table may still be read by an enqueued record
-  recorder_free(h->mon);
-  h->mon = N;
-  return KNPEMI_OK;
+  return rc ? rc : recorder_install(h, &knpemi_handle::mon, N);
 }
 
 extern "C" int knpemi_monitor_record(knpemi_handle* h, double t, int fields) {
@@ -900,12 +908,9 @@ extern "C" int knpemi_monitor_record(knpemi_handle* h, double t, int fields) {
   if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_monitor_record: ") + MON_NONE);
   if (!std::isfinite(t)) return kn_fail(KNPEMI_EINVAL, "knpemi_monitor_record: t must be finite");
   KN_HIP(hipSetDevice(h->device));
-  if (int rc = mon_after_ode(h)) return rc;
-  if (fields && !X.fld)
-    if (int rc = kn_alloc(X.allocs, std::max<size_t>(X.fld_len, 1), &X.fld)) return rc;
-  if (int rc = kn_launch_monitor(h, t, fields)) return rc;
-  if (fields) X.fld_valid = true;
-  return KNPEMI_OK;
+  // the record reads phi_M and the tables, which the ODE sweeps may write on the auxiliary streams
+  if (int rc = kn_wait_ode_joins(h)) return rc;
+  return fields_record(X.fields, X.allocs, fields, [&] { return kn_launch_monitor(h, t, fields); });
 }
 
 extern "C" int knpemi_monitor_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
@@ -922,11 +927,11 @@ extern "C" int knpemi_monitor_fields(knpemi_handle* h, int watch, int quantity, 
   const KnMonWatch& W = X.host.w[watch];
   if (quantity < 0 || quantity >= KN_MON_MAX || !((W.mask >> quantity) & 1u))
     return kn_fail(KNPEMI_EINVAL, fn + ": the quantity is not selected by the watch");
-  if (!X.fld_valid) return kn_fail(KNPEMI_EINVAL, fn + ": no record with fields yet (knpemi_monitor_record(h, t, 1))");
+  if (int rc = fields_recorded(X.fields, fn, "knpemi_monitor_record(h, t, 1)")) return rc;
   if (n != (size_t)W.nq) return kn_fail(KNPEMI_EINVAL, fn + ": length is not the number of membrane dofs of the sub-domain");
   KN_HIP(hipSetDevice(h->device));
   const size_t comp = (size_t)popcount((int)(W.mask & ((1u << quantity) - 1u)));
-  return kn_to_host(h->stream, out, X.fld + W.fbase + comp * (size_t)W.nq, n);
+  return kn_to_host(h->stream, out, X.fields.fld + W.fbase + comp * (size_t)W.nq, n);
 }
 
 extern "C" int knpemi_monitor_reset(knpemi_handle* h) {
@@ -934,7 +939,7 @@ extern "C" int knpemi_monitor_reset(knpemi_handle* h) {
   auto& X = h->mon;
   if (X.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_monitor_reset: ") + MON_NONE);
   KN_HIP(hipSetDevice(h->device));
-  X.fld_valid = false;
+  fields_forget(X.fields);
   return series_rewind(h, X.ser);
 }
 
@@ -968,7 +973,7 @@ extern "C" int knpemi_monitor_eval(knpemi_handle* h, int sub, int model, double 
   T.bstart[1] = (W.nq + kn_monitor_chunk() - 1) / kn_monitor_chunk();
   KnMonTab* d_tab = nullptr;
   double* fld = nullptr;
-  if ((rc = kn_upload(tmp.a, &T, 1, &d_tab)) || (rc = kn_alloc(tmp.a, n, &fld)) || (rc = mon_after_ode(h))
+  if ((rc = kn_upload(tmp.a, &T, 1, &d_tab)) || (rc = kn_alloc(tmp.a, n, &fld)) || (rc = kn_wait_ode_joins(h))
       || (rc = kn_launch_monitor_eval(h, d_tab, W.nq, t, fld, m.mon_kernel[1])))
     return rc;
   return kn_to_host(h->stream, out, fld, n);   // synchronises: the scratch memory is no longer read

@@ -21,6 +21,7 @@ import os
 
 import numpy as np
 
+from ..recording import gather_objects
 from .mesh import MeshTags, extract_submesh, match_facets
 
 
@@ -463,15 +464,8 @@ def make_partitioned_problem(kind, r, rank, world, g_syn=10.0, length=None, meth
     part = rcb_partition(cent, world) if method == "rcb" else slab_partition(cent, world)
     local = LocalPart(mesh, ct, ft, part, rank, world)
     s = Setup(kind, r, g_syn=g_syn, mesh_data=(local.mesh, local.ct, local.ft), build_forms=True)
-    if gather is None:
-        import torch.distributed as dist
-
-        def gather(obj):
-            out = [None] * world
-            dist.all_gather_object(out, obj)
-            return out
     s.halo = VertexHalo(local, s.subdomain_list)
-    s.halo.build(gather)
+    s.halo.build(gather or gather_objects)
     s.owned_dofs = s.halo.owned_dofs
     s.local = local
     s.global_length = l * 16e-6
@@ -491,15 +485,8 @@ def make_partitioned_astro(cfg, rank, world, method="rcb", gather=None):
     part = rcb_partition(cent, world) if method == "rcb" else slab_partition(cent, world)
     local = LocalPart(mesh, ct, ft, part, rank, world)
     s = rsd.Problem(cfg, mesh_data=(local.mesh, local.ct, local.ft))
-    if gather is None:
-        import torch.distributed as dist
-
-        def gather(obj):
-            out = [None] * world
-            dist.all_gather_object(out, obj)
-            return out
     s.halo = VertexHalo(local, s.subdomain_list)
-    s.halo.build(gather)
+    s.halo.build(gather or gather_objects)
     s.owned_dofs = s.halo.owned_dofs
     s.local = local
     s.global_length = float(mesh.x[:, 0].max())

@@ -18,6 +18,7 @@ import os
 
 import numpy as np
 
+from ..recording import gather_objects
 from .distributed import Halo
 from .idealized import make_mesh_3D_slab
 
@@ -137,16 +138,10 @@ def make_slab_problem(kind, r, rank, world, g_syn=10.0, length=None):
     """The rank-local driver set-up (examples/idealized_geometries/setup_problem.Setup): x-slab `rank` of the box of
     length 16 * length um at resolution r (default length 2 * world: the weak-scaling family; length = 2 is the
     reference's own box, cut into `world` slabs: strong scaling)."""
-    import torch.distributed as dist
     from setup_problem import Setup
     lay, mesh_data = make_slab_layout_and_mesh(kind, r, rank, world, length)
     s = Setup(kind, r, g_syn=g_syn, mesh_data=mesh_data, build_forms=True)
-
-    def gather(obj):
-        out = [None] * world
-        dist.all_gather_object(out, obj)
-        return out
-    s.halo, owned = build_halo(lay, s.subdomain_list, gather)
+    s.halo, owned = build_halo(lay, s.subdomain_list, gather_objects)
     s.owned_dofs = owned
     s.layout = lay
     s.global_length = lay.l * 16e-6

@@ -38,7 +38,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .recording import RowSeries
+from .recording import RowSeries, agree_across_ranks, gather_objects, rank_slots
 from .fem.probe import Locator, integral_weights, membrane_weights, point_weights
 
 OPS = ("integral", "nodal_mean", "average", "min", "max")
@@ -199,17 +199,10 @@ class Observables(RowSeries):
     def partition(self, halo, gather=None, every=1, capacity=1024):
         """The table of this rank of a cell-partitioned run (see the module docstring), set in `self._ptab`.
         halo: the rank's `knpemi.fem.distributed.Halo` with its plans built; gather(obj) -> [obj of every rank]
-        (default: torch.distributed.all_gather_object).  Collective: every rank calls it once, with the same
+        (default: `recording.gather_objects`).  Collective: every rank calls it once, with the same
         definitions in the same order and the same every / capacity, or every rank raises ValueError."""
         if not self.items:
             raise ValueError("no observables defined")
-        if gather is None:
-            import torch.distributed as dist
-
-            def gather(obj):
-                out = [None] * dist.get_world_size()
-                dist.all_gather_object(out, obj)
-                return out
         rank = int(halo.rank)
         own_b, own_m = halo.vertex_owner("bulk"), halo.vertex_owner("mem")
         owner, rec, off, qoff = {}, {}, 0, 0
@@ -267,14 +260,11 @@ class Observables(RowSeries):
                 share.append(float(w.sum()))
         mine = dict(keys=self.keys, every=int(every), capacity=int(capacity), found=[f is not None for f in found],
                     share=share)
-        allr = gather(mine)
+        allr = (gather or gather_objects)(mine)
         world = len(allr)
-        for r, other in enumerate(allr):
-            for what in ("keys", "every", "capacity"):
-                if other[what] != allr[0][what]:
-                    raise ValueError(f"observables differ between ranks: {what} of rank {r} is {other[what]!r}, "
-                                     f"of rank 0 {allr[0][what]!r} (every rank must define the same observables in "
-                                     "the same order and pass the same every and capacity)")
+        agree_across_ranks(allr, ("keys", "every", "capacity"), "observables",
+                           "every rank must define the same observables in the same order and pass the same every and "
+                           "capacity")
         taker = []
         for k, (membrane, tag, x) in enumerate(self._points):
             ranks = [r for r in range(world) if allr[r]["found"][k]]
@@ -315,20 +305,16 @@ class Observables(RowSeries):
         return spec, ptr, idx, w, denom
 
     def upload_partitioned(self, dp, capacity, halo, every=1):
-        """`partition`, then knpemi_observe_set_partitioned with the exchange buffer as a device tensor: the library's
-        communicator sums it when the halo runs on it, else the halo's all-reduce (gloo or torch RCCL).  Returns the
-        objects the handle refers to (keep them alive while it records)."""
-        import torch
+        """`partition`, then knpemi_observe_set_partitioned (`rank_slots`).  Returns the objects the handle refers to
+        (keep them alive while it records)."""
         self.partition(halo, None, every, capacity)
         spec, ptr, idx, w, denom = self.partitioned_table(dp.sub_index)
         n, world = len(self.items), self._ptab["world"]
-        xbuf = torch.zeros(world * n, dtype=torch.float64, device=torch.device("cuda", dp.device))
-        cb = None if getattr(halo, "_native", False) else halo.allreduce_callback(xbuf)
+        slots, keep = rank_slots(dp, halo, world, n)
         L.check(dp.lib.knpemi_observe_set_partitioned(
             dp.h, n, L.iptr(spec.ravel()), ptr.ctypes.data_as(C.POINTER(C.c_int64)), L.iptr(idx) if idx.size else None,
-            L.dptr(w) if w.size else None, L.dptr(denom), int(capacity), self._ptab["rank"], world, xbuf.data_ptr(),
-            C.cast(cb, C.c_void_p) if cb is not None else None, None))
-        return xbuf, cb
+            L.dptr(w) if w.size else None, L.dptr(denom), int(capacity), self._ptab["rank"], world, *slots))
+        return keep
 
     def _fields(self, o, phi, c, phi_M_prev):
         if o.field == L.F_PHI:

@@ -42,6 +42,34 @@ def nodal_values(u, n=None):
     return np.full(n, float(a)) if a.ndim == 0 and n is not None else a
 
 
+def gather_objects(obj):
+    """[obj of every rank]: the default `gather` of a recorder's `partition` (torch.distributed.all_gather_object)."""
+    import torch.distributed as dist
+    out = [None] * dist.get_world_size()
+    dist.all_gather_object(out, obj)
+    return out
+
+
+def agree_across_ranks(allr, fields, who, advice):
+    """ValueError unless the gathered dictionaries `allr` (one per rank) hold the same `fields`."""
+    for r, other in enumerate(allr):
+        for what in fields:
+            if other[what] != allr[0][what]:
+                raise ValueError(f"{who} differ between ranks: {what} of rank {r} is {other[what]!r}, of rank 0 "
+                                 f"{allr[0][what]!r} ({advice})")
+
+
+def rank_slots(dp, halo, world, n_cols):
+    """The exchange buffer of a partitioned recorder, a device tensor of [world][n_cols] doubles: the library's
+    communicator sums it when the halo runs on it, else the halo's all-reduce (gloo or torch RCCL).  Returns the last
+    three arguments of knpemi_*_set_partitioned (xbuf_dev, allreduce, ctx) and the objects the handle then refers to
+    (keep them alive while it records)."""
+    import torch
+    xbuf = torch.zeros(world * n_cols, dtype=torch.float64, device=torch.device("cuda", dp.device))
+    cb = None if getattr(halo, "_native", False) else halo.allreduce_callback(xbuf)
+    return (xbuf.data_ptr(), C.cast(cb, C.c_void_p) if cb is not None else None, None), (xbuf, cb)
+
+
 class RowSeries:
     """Times and rows of a recorder whose row has the columns `columns()`: [(key, width)] in the device's order."""
 
@@ -132,18 +160,11 @@ class WatchedIons(RowSeries):
         """The recorded masks of this rank of a cell-partitioned run, set in `self._ptab`: {"rank", "world", "recorded":
         {tag: bool per local item}}.  An item is recorded by the lowest owner among its vertices
         (`halo.vertex_owner`), as `Observables.partition` decides.  halo: the rank's `knpemi.fem.distributed.Halo`
-        with its plans built; gather(obj) -> [obj of every rank] (default: torch.distributed.all_gather_object).
+        with its plans built; gather(obj) -> [obj of every rank] (default: `gather_objects`).
         Collective: every rank calls it once with the same watches, ion masks, every and capacity, or every rank raises
         ValueError."""
         if not self.watched:
             raise ValueError(f"no {self._WATCH} is watched")
-        if gather is None:
-            import torch.distributed as dist
-
-            def gather(obj):
-                out = [None] * dist.get_world_size()
-                dist.all_gather_object(out, obj)
-                return out
         rank = int(halo.rank)
         recorded = {}
         for tag, (mesh, ow) in self._item_owners(halo).items():
@@ -152,14 +173,10 @@ class WatchedIons(RowSeries):
             else:
                 recorded[tag] = ow[np.asarray(mesh.cells)].min(axis=1) == rank
         mine = dict(watches=[(t, self.mask(t)) for t in self.watched], every=int(every), capacity=int(capacity))
-        allr = gather(mine)
-        for r, other in enumerate(allr):
-            for what in ("watches", "every", "capacity"):
-                if other[what] != allr[0][what]:
-                    raise ValueError(f"{self._NAME} recorders differ between ranks: {what} of rank {r} is "
-                                     f"{other[what]!r}, of rank 0 {allr[0][what]!r} (every rank must watch the same "
-                                     f"{self._WATCH}s with the same ions in the same order and pass the same every and "
-                                     "capacity)")
+        allr = (gather or gather_objects)(mine)
+        agree_across_ranks(allr, ("watches", "every", "capacity"), f"{self._NAME} recorders",
+                           f"every rank must watch the same {self._WATCH}s with the same ions in the same order and pass "
+                           "the same every and capacity")
         self._ptab = dict(rank=rank, world=len(allr), recorded=recorded)
         return self._ptab
 
@@ -169,9 +186,8 @@ class WatchedIons(RowSeries):
         return np.ascontiguousarray(np.concatenate([rec[t] for t in self.watched]).astype(np.uint8))
 
     def _attach(self, dp, capacity, halo=None, every=1):
-        """knpemi_<_NAME>_set, or with a halo `partition` and knpemi_<_NAME>_set_partitioned: the exchange buffer is a
-        device tensor, summed by the library's communicator when the halo runs on it, else by the halo's all-reduce
-        (gloo or torch RCCL).  Returns the objects the handle refers to (keep them alive while it records)."""
+        """knpemi_<_NAME>_set, or with a halo `partition` and knpemi_<_NAME>_set_partitioned (`rank_slots`).  Returns the
+        objects the handle refers to (keep them alive while it records)."""
         if self._dev is not None:
             raise RuntimeError(f"{self._SELF} attached to a device problem already")
         if not self.watched:
@@ -183,17 +199,14 @@ class WatchedIons(RowSeries):
         if halo is None:
             L.check(getattr(dp.lib, f"knpemi_{self._NAME}_set")(dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity)))
         else:
-            import torch
             self.partition(halo, None, every, capacity)
             rec = self.recorded_mask()
             rec = rec if rec.size else np.zeros(1, np.uint8)      # a rank without items still passes a mask
             world = self._ptab["world"]
-            xbuf = torch.zeros(world * self.n_cols, dtype=torch.float64, device=torch.device("cuda", dp.device))
-            cb = None if getattr(halo, "_native", False) else halo.allreduce_callback(xbuf)
+            slots, keep = rank_slots(dp, halo, world, self.n_cols)
             L.check(getattr(dp.lib, f"knpemi_{self._NAME}_set_partitioned")(
                 dp.h, len(tags), L.iptr(sub), L.iptr(mask), int(capacity), rec.ctypes.data_as(L.c_u8_p),
-                self._ptab["rank"], world, xbuf.data_ptr(), C.cast(cb, C.c_void_p) if cb is not None else None, None))
-            keep = (xbuf, cb)
+                self._ptab["rank"], world, *slots))
         self._dev = (dp.lib, dp.h, dict(dp.sub_index))
         return keep
 
@@ -238,18 +251,28 @@ class Tap:
     t0 + (k + offset) dt: offset 0 at the end of step k (counted from 1), 1 inside step k (counted from 0) for a row that
     carries the time of the step's end.  record(t, fields) enqueues the launch; read(n, buf) -> (rows, dropped) fills buf
     with the device's first n rows and starts its buffer over (None: no series); rewind() starts a new series on the
-    device.  `enabled` and `fields` may be switched between steps (tools/*_cost.py)."""
+    device.  `enabled` and `fields` may be switched between steps (tools/recorder_cost.py).
+
+    halo: the halo the recorder was attached with, or None; partition_refusal: the NotImplementedError text of a
+    partitioned step (`DeviceStepper.step(halo)`) with another halo than that, None for a recorder that needs no halo;
+    keep: what the handle refers to while the recorder is attached (the exchange buffer, the all-reduce callback)."""
 
     def __init__(self, target, label, every, record, t0=0.0, offset=0, capacity=None, read=None, n_cols=0, rewind=None,
-                 fields=False):
+                 fields=False, halo=None, partition_refusal=None, keep=None):
         self.target, self.label, self.every, self.t0, self.offset = target, label, int(every), float(t0), int(offset)
         self.record, self.read, self.rewind = record, read, rewind
+        self.halo, self.partition_refusal, self.keep = halo, partition_refusal, keep
         self.capacity, self.n_cols = capacity if capacity is None else int(capacity), int(n_cols)
         self.enabled, self.fields = True, bool(fields)
         self.pending = []                 # times of the rows the device holds
         if read is not None:
             target.clear()
             target._drain = self.drain
+
+    def refuse_partitioned(self, halo):
+        """NotImplementedError when the steps run with `halo` and this recorder cannot record them."""
+        if halo is not None and halo is not self.halo and self.partition_refusal is not None:
+            raise NotImplementedError(self.partition_refusal)
 
     def tick(self, k, dt):
         if not self.enabled or (k + self.offset) % self.every:

@@ -87,8 +87,6 @@ class DeviceStepper:
         # last KNP assembly of a step, "observe", "detect", "fluxes" and "track", in this order, behind the end-of-step
         # update
         self.taps = {}
-        self._obs_halo = None      # the halo of a partitioned observe
-        self._tap_halo = {}        # "fluxes" / "exchange": the halo they were attached with, and what the handle refers to
         self.upload()
 
     # -- host <-> device ------------------------------------------------------------------
@@ -157,27 +155,43 @@ class DeviceStepper:
         same definitions, every and capacity).  Every rank then records the global row -- partial rows summed over the
         ranks on the device at each record (Observables.partition) -- and `step(halo)` records with the same halo.
         Draining stays rank-local."""
-        if every < 1 or capacity < 1:
-            raise ValueError("every and capacity must be positive")
-        if obs._drain is not None:
-            raise RuntimeError("these observables are attached to a stepper already")
-        self._obs_halo, self._obs_keep = halo, None
-        if halo is None:
-            obs.upload(self.dp, capacity)
-        else:
-            if halo.dp is not self.dp:
-                raise ValueError("observe(halo=...): attach the halo to this stepper's problem first (halo.attach)")
-            self._obs_keep = obs.upload_partitioned(self.dp, capacity, halo, every)
+        lib, dp = self.lib, self.dp
+        read = self._reader(lib.knpemi_observe_read)
+        self._attach("observe", obs, "observables", every, capacity, t0, halo=halo, read=read,
+                     attached="these observables are attached to a stepper already",
+                     set_up=lambda: (obs.upload(dp, capacity) if halo is None
+                                     else obs.upload_partitioned(dp, capacity, halo, every)),
+                     record=lambda t, f: lib.knpemi_observe_record(dp.h), rewind=lambda: read(0, None),
+                     partition_refusal="observables attached without a halo are not recorded on partitioned steps: "
+                                       "pass halo= to DeviceStepper.observe")
 
-        def record(t, fields):
-            rc = self.lib.knpemi_observe_record(self.dp.h)
+    def _attach(self, name, rec, label, every, capacity, t0, *, set_up, record, rewind, busy=None, attached=None,
+                read=None, fields=False, offset=0, halo=None, partition_refusal=None):
+        """The attach path of every recorder: the checks (capacity None: a recorder without a row buffer; busy / attached:
+        the messages of a second recorder of this kind on the stepper / of a recorder that drains into a stepper
+        already), set_up() -> what the handle then refers to, and the tap `self.taps[name]`.  record(t, fields) returns
+        the status of knpemi_*_record."""
+        if capacity is None and every < 1:
+            raise ValueError("every must be positive")
+        if capacity is not None and (every < 1 or capacity < 1):
+            raise ValueError("every and capacity must be positive")
+        if busy is not None and name in self.taps:
+            raise RuntimeError(busy)
+        if attached is not None and rec._drain is not None:
+            raise RuntimeError(attached)
+        if halo is not None and halo.dp is not self.dp:
+            raise ValueError(f"{name}(halo=...): attach the halo to this stepper's problem first (halo.attach)")
+        keep = set_up()
+
+        def enqueue(t, f):
+            rc = record(t, f)
             err = getattr(halo, "_hook_error", None)
             if rc != L.OK and err is not None:      # the all-reduce of a partitioned record failed in Python
                 raise err
             L.check(rc)
-        read = self._reader(self.lib.knpemi_observe_read)
-        self.taps["observe"] = Tap(obs, "observables", every, record, t0, capacity=capacity, read=read,
-                                   n_cols=obs.n_cols, rewind=lambda: read(0, None))
+        self.taps[name] = Tap(rec, label, every, enqueue, t0, offset, capacity if read is not None else None, read,
+                              rec.n_cols if read is not None else 0, rewind, fields, halo=halo,
+                              partition_refusal=partition_refusal, keep=keep)
 
     def _reader(self, fn):
         """read(n, buf) -> (rows, dropped) of a tap, from the recorder's knpemi_*_read with reset."""
@@ -194,18 +208,18 @@ class DeviceStepper:
         `ev.maps(tag)` reads the maps back.  Works unchanged on a cell-partitioned problem (`step(halo)`): the kernel
         needs no halo, every rank holds the events of its local dofs, and `ev.maps(tag, halo=halo)` selects the owned
         ones."""
-        if every < 1:
-            raise ValueError("every must be positive")
-        if "detect" in self.taps:
-            raise RuntimeError("this stepper records membrane events already")
-        ev._attach(self.lib, self.dp.h, self.dp.sub_index)
-        ev.reset_host()
+        lib, dp = self.lib, self.dp
+
+        def set_up():
+            ev._attach(lib, dp.h, dp.sub_index)
+            ev.reset_host()
 
         def rewind():
-            L.check(self.lib.knpemi_events_reset(self.dp.h))
+            L.check(lib.knpemi_events_reset(dp.h))
             ev.reset_host()
-        self.taps["detect"] = Tap(ev, "membrane events", every, rewind=rewind, t0=t0,
-                                  record=lambda t, fields: L.check(self.lib.knpemi_events_record(self.dp.h, t)))
+        self._attach("detect", ev, "membrane events", every, None, t0, set_up=set_up, rewind=rewind,
+                     busy="this stepper records membrane events already",
+                     record=lambda t, f: lib.knpemi_events_record(dp.h, t))
 
     # -- ion fluxes ---------------------------------------------------------------------------------
     def fluxes(self, fl, every=1, capacity=1024, t0=0.0, fields=False, halo=None):
@@ -221,32 +235,21 @@ class DeviceStepper:
         partial rows summed over the ranks on the device at each record (WatchedIons.partition) -- and `step(halo)`
         records with the same halo; `fl.fields(tag, halo=halo)` reads the local cells.  Draining stays rank-local.
         Without it, partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost cells."""
-        if every < 1 or capacity < 1:
-            raise ValueError("every and capacity must be positive")
-        if "fluxes" in self.taps:
-            raise RuntimeError("this stepper records ion fluxes already")
-        if fl._drain is not None:
-            raise RuntimeError("these fluxes are attached to a stepper already")
-        self._watched_tap("fluxes", "flux", fl, "ion fluxes", every, capacity, t0, fields, halo=halo)
+        self._attach_watched("fluxes", "flux", fl, "ion fluxes", every, capacity, t0, fields, halo,
+                             busy="this stepper records ion fluxes already",
+                             attached="these fluxes are attached to a stepper already",
+                             partition_refusal="ion fluxes attached without a halo are not recorded on partitioned steps "
+                                               "(a rank's sums would include its ghost cells): pass halo= to "
+                                               "DeviceStepper.fluxes")
 
-    def _watched_tap(self, name, kind, rec, label, every, capacity, t0, fields, offset=0, halo=None):
-        """Attach the watches of `rec` (IonFluxes, MembraneExchange: knpemi_<kind>_*), with a halo their partitioned
-        table, and build their tap."""
+    def _attach_watched(self, name, kind, rec, label, every, capacity, t0, fields, halo, offset=0, **messages):
+        """`_attach` for the watches of `rec` (IonFluxes, MembraneExchange: knpemi_<kind>_*), with a halo their
+        partitioned table."""
         lib, h = self.lib, self.dp.h
         record, reset = getattr(lib, f"knpemi_{kind}_record"), getattr(lib, f"knpemi_{kind}_reset")
-        if halo is not None and halo.dp is not self.dp:
-            raise ValueError(f"{name}(halo=...): attach the halo to this stepper's problem first (halo.attach)")
-        self._tap_halo[name] = (halo, rec._attach(self.dp, capacity, halo, every))
-
-        def enqueue(t, f):
-            rc = record(h, f)
-            err = getattr(halo, "_hook_error", None)
-            if rc != L.OK and err is not None:      # the all-reduce of a partitioned record failed in Python
-                raise err
-            L.check(rc)
-        self.taps[name] = Tap(rec, label, every, enqueue, t0, offset, capacity,
-                              self._reader(getattr(lib, f"knpemi_{kind}_read")), rec.n_cols, lambda: L.check(reset(h)),
-                              fields)
+        self._attach(name, rec, label, every, capacity, t0, fields=fields, offset=offset, halo=halo,
+                     set_up=lambda: rec._attach(self.dp, capacity, halo, every), record=lambda t, f: record(h, f),
+                     read=self._reader(getattr(lib, f"knpemi_{kind}_read")), rewind=lambda: L.check(reset(h)), **messages)
 
     # -- membrane ion exchange --------------------------------------------------------------------------
     def exchange(self, ex, every=1, capacity=1024, t0=0.0, fields=False, halo=None):
@@ -265,14 +268,13 @@ class DeviceStepper:
         `ex.fields(tag, halo=halo)` reads the local facets.  `ex.budget` then pairs the series with that of
         `observe(obs, halo=halo)`.
         Without it, partitioned steps (`step(halo)`) are refused: a rank's sums would include its ghost facets."""
-        if every < 1 or capacity < 1:
-            raise ValueError("every and capacity must be positive")
-        if "exchange" in self.taps:
-            raise RuntimeError("this stepper records a membrane exchange already")
-        if ex._drain is not None:
-            raise RuntimeError("this exchange is attached to a stepper already")
         # offset 1: the record sits inside step k, counted from 0, and carries the time of the step's end
-        self._watched_tap("exchange", "exchange", ex, "membrane exchange", every, capacity, t0, fields, offset=1, halo=halo)
+        self._attach_watched("exchange", "exchange", ex, "membrane exchange", every, capacity, t0, fields, halo, offset=1,
+                             busy="this stepper records a membrane exchange already",
+                             attached="this exchange is attached to a stepper already",
+                             partition_refusal="a membrane exchange attached without a halo is not recorded on "
+                                               "partitioned steps (a rank's sums would include its ghost facets): pass "
+                                               "halo= to DeviceStepper.exchange")
         ex._dt, ex._every = self.dt, int(every)
 
     # -- field maps -----------------------------------------------------------------------------------
@@ -285,22 +287,24 @@ class DeviceStepper:
         Works unchanged on a cell-partitioned problem (`step(halo)`) without a series watch: the kernel needs no halo,
         every rank holds the maps of its local items, and `fm.maps(name, halo=halo)` selects the owned ones.  With a
         series watch partitioned steps are refused: a rank's sums would include its ghost items."""
-        if every < 1 or capacity < 1:
-            raise ValueError("every and capacity must be positive")
-        if "track" in self.taps:
-            raise RuntimeError("this stepper records field maps already")
-        if fm._drain is not None:
-            raise RuntimeError("these maps are attached to a stepper already")
-        fm._attach(self.dp, capacity)
-        fm.reset_host()
-        lib, h = self.lib, self.dp.h
+        lib, dp = self.lib, self.dp
+
+        def set_up():
+            fm._attach(dp, capacity)
+            fm.reset_host()
 
         def rewind():
-            L.check(lib.knpemi_maps_reset(h))
+            L.check(lib.knpemi_maps_reset(dp.h))
             fm.reset_host()
-        read = self._reader(lib.knpemi_maps_series_read) if fm.has_series else None
-        self.taps["track"] = Tap(fm, "field maps", every, lambda t, fields: L.check(lib.knpemi_maps_record(h, t)), t0,
-                                 capacity=capacity if read else None, read=read, n_cols=fm.n_cols, rewind=rewind)
+        series = fm.has_series
+        self._attach("track", fm, "field maps", every, capacity, t0, set_up=set_up, rewind=rewind,
+                     busy="this stepper records field maps already",
+                     attached="these maps are attached to a stepper already",
+                     record=lambda t, f: lib.knpemi_maps_record(dp.h, t),
+                     read=self._reader(lib.knpemi_maps_series_read) if series else None,
+                     partition_refusal="field maps with a series watch are not recorded on partitioned steps (a rank's "
+                                       "sums would include its ghost items): track maps without series=True"
+                                       if series else None)
 
     # -- membrane monitors ------------------------------------------------------------------------------
     def monitor(self, mon, every=1, capacity=1024, t0=0.0, fields=False):
@@ -311,18 +315,15 @@ class DeviceStepper:
         `mon` as the other series are (whenever it holds `capacity` rows, and when `mon.series()` is called).  fields:
         every record also writes the per-dof arrays (`mon.values(tag)` reads those of the latest record).
         Partitioned steps (`step(halo)`) are refused: a rank's reductions would include its ghost dofs."""
-        if every < 1 or capacity < 1:
-            raise ValueError("every and capacity must be positive")
-        if "monitor" in self.taps:
-            raise RuntimeError("this stepper records membrane monitors already")
-        if mon._drain is not None:
-            raise RuntimeError("this monitor is attached to a stepper already")
-        mon._attach(self.dp, capacity)
-        lib, h = self.lib, self.dp.h
-        self.taps["monitor"] = Tap(mon, "membrane monitors", every,
-                                   lambda t, f: L.check(lib.knpemi_monitor_record(h, float(t), f)), t0,
-                                   capacity=capacity, read=self._reader(lib.knpemi_monitor_read), n_cols=mon.n_cols,
-                                   rewind=lambda: L.check(lib.knpemi_monitor_reset(h)), fields=fields)
+        lib, dp = self.lib, self.dp
+        self._attach("monitor", mon, "membrane monitors", every, capacity, t0, fields=fields,
+                     busy="this stepper records membrane monitors already",
+                     attached="this monitor is attached to a stepper already",
+                     set_up=lambda: mon._attach(dp, capacity), read=self._reader(lib.knpemi_monitor_read),
+                     record=lambda t, f: lib.knpemi_monitor_record(dp.h, float(t), f),
+                     rewind=lambda: L.check(lib.knpemi_monitor_reset(dp.h)),
+                     partition_refusal="membrane monitors are not recorded on partitioned steps (a rank's reductions "
+                                       "would include its ghost dofs): run DeviceStepper.monitor on one rank")
 
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
@@ -361,22 +362,8 @@ class DeviceStepper:
     # -- one time step, everything enqueued on the handle's stream ---------------------------
     def step(self, halo=None):
         dp, lib = self.dp, self.lib
-        if halo is not None and "observe" in self.taps and halo is not self._obs_halo:
-            raise NotImplementedError("observables attached without a halo are not recorded on partitioned steps: "
-                                      "pass halo= to DeviceStepper.observe")
-        if halo is not None and "fluxes" in self.taps and halo is not self._tap_halo["fluxes"][0]:
-            raise NotImplementedError("ion fluxes attached without a halo are not recorded on partitioned steps (a "
-                                      "rank's sums would include its ghost cells): pass halo= to DeviceStepper.fluxes")
-        if halo is not None and "exchange" in self.taps and halo is not self._tap_halo["exchange"][0]:
-            raise NotImplementedError("a membrane exchange attached without a halo is not recorded on partitioned steps "
-                                      "(a rank's sums would include its ghost facets): pass halo= to "
-                                      "DeviceStepper.exchange")
-        if halo is not None and "track" in self.taps and self.taps["track"].target.has_series:
-            raise NotImplementedError("field maps with a series watch are not recorded on partitioned steps (a rank's "
-                                      "sums would include its ghost items): track maps without series=True")
-        if halo is not None and "monitor" in self.taps:
-            raise NotImplementedError("membrane monitors are not recorded on partitioned steps (a rank's reductions would "
-                                      "include its ghost dofs): run DeviceStepper.monitor on one rank")
+        for tap in self.taps.values():
+            tap.refuse_partitioned(halo)
         if halo is not None and (self.solve_emi is not None or self.solve_knp is not None) \
                 and not getattr(halo, "supports_solves", False):
             raise NotImplementedError(
