@@ -15,7 +15,11 @@ the reference's `results_sub_<tag>.xdmf` / `results_mem_<tag>.xdmf` time series.
 P1 field on the ECS (the reference evaluates the UFL conditional at quadrature points: identical when the region
 is a union of cells, a one-cell ramp otherwise).
 
-    python run_stim_duration.py -c baseline [--steps N] [--device-resident] [--direct]
+    python run_stim_duration.py -c baseline [--steps N] [--device-resident] [--direct] [--snapshots]
+
+`--snapshots` saves through `knpemi.Snapshots` (the same `step_*.npz` and XDMF files): with `--device-resident` the fields
+are packed on the device, copied out by a stream of its own and written by a thread, and `download()` runs once, at the
+end of the run; in the host loop the same sinks are fed from the host arrays.
 """
 import argparse
 import os
@@ -227,6 +231,19 @@ def write_results(p, outdir, k, t):
     np.savez_compressed(os.path.join(outdir, f"step_{k:06d}.npz"), t=t, **fields)
 
 
+def make_snapshots(p, outdir, xdmf, k_offset=0, extra_sink=None):
+    """What `write_results` saves (and, with xdmf, what `XdmfResults` writes) as a `knpemi.Snapshots` recorder: `.npz` per
+    saved step, named by step k + k_offset, written off the stepping thread.  extra_sink: called before the files are
+    written."""
+    from knpemi.snapshots import NpzSink, Snapshots, XdmfSink
+    sinks = ([extra_sink] if extra_sink is not None else []) + [NpzSink(outdir, compressed=True, k_offset=k_offset)]
+    if xdmf:
+        sinks.append(XdmfSink(p, outdir))
+    snap = Snapshots(p.mesh, p.ct, p.ft, p.subdomain_list, p.ion_list, sink=sinks)
+    snap.watch_results()
+    return snap
+
+
 def make_observables(p):
     """Per-step series: the three field quantities of `history` and phi / ions at points of this mesh (the centroid of
     the ECS cell, the neuron cell and the neuron membrane facet closest to the mesh's centre)."""
@@ -312,7 +329,8 @@ def monitor_state(p):
 
 def solve_system(config, n_steps=None, device_resident=False, direct=False, outdir=None, quiet=False, xdmf=False,
                  extrapolate_guess=True, series=None, ode_method="lsoda", ode_substeps=None, events=None,
-                 event_threshold=None, fluxes=None, exchange=None, maps=None, maps_threshold=None, monitor=None):
+                 event_threshold=None, fluxes=None, exchange=None, maps=None, maps_threshold=None, monitor=None,
+                 snapshots=False):
     """series: path of a .npz of per-step observables (make_observables), or None.
     events: path of a .npz of the membrane events of neuron and glia (make_events: upward crossings of event_threshold
     per membrane dof, in mV; default: `event_threshold` of the config, else -20), or None.
@@ -322,7 +340,9 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
     maps: path of a .npz of the field maps (make_maps; level of ECS K+ maps_threshold in mM, default: `maps_threshold` of
     the config, else 0.05 above the initial ECS concentration), or None.
     monitor: path of a .npz of the per-step series of the membrane monitors of neuron and glia (make_monitors), or None.
-    ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator)."""
+    ode_method / ode_substeps: the membrane integrator of both cells (MembraneModel.set_integrator).
+    snapshots: save through `knpemi.Snapshots` (make_snapshots) instead of `write_results` / `XdmfResults`: the same files;
+    device-resident, without a download per saved step (the saved steps' `history` values come from the frames)."""
     p = Problem(config)
     mon = make_monitors(p) if monitor else None
     fl = make_fluxes(p) if fluxes else None
@@ -339,7 +359,8 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
     if outdir is None:
         outdir = os.path.join(HERE, "results", str(config["fname"]))
     os.makedirs(outdir, exist_ok=True)
-    xdmf_out = XdmfResults(p, outdir) if xdmf else None
+    xdmf_out = XdmfResults(p, outdir) if xdmf and not snapshots else None
+    snap = None
     history = dict(t=[], source=[], phi_M_neuron=[], phi_M_glia=[], K_ecs_max=[], its_emi=[], its_knp=[])
     t = 0.0
 
@@ -376,12 +397,33 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             st.track(fm, every=1)
         if mon is not None:
             st.monitor(mon, every=1)
+        if snapshots:
+            def from_frame(tf, kf, frame):      # on the writer thread, in record order: what `record` reads off the fields
+                history["phi_M_neuron"].append(float(frame["phi_M_1"].mean()))
+                history["phi_M_glia"].append(float(frame["phi_M_2"].mean()))
+                history["K_ecs_max"].append(float(frame[f"{p.ion_list[0]['name']}_0"].max()))
+                if not quiet:
+                    print(f"t = {tf:.2f} ms  phi_M neuron {history['phi_M_neuron'][-1]:.4f} "
+                          f"glia {history['phi_M_glia'][-1]:.4f} mV")
+            # the stepper counts the steps from 1, the files are named by the loop's k
+            snap = make_snapshots(p, outdir, xdmf, k_offset=-1, extra_sink=from_frame)
+            st.snapshot(snap, every=1, depth=4)
         for k in range(n_steps):
+            save = (k % config["save_frequency"]) == 0 or k == n_steps - 1
+            if snap is not None:
+                st.taps["snapshot"].enabled = save
+                if save:
+                    snap.retime(k + 1, t + DT)      # the files carry the loop's accumulated time
             st.step()
             t = t + DT
             if p.set_source(t):
                 st.set_source(0, p.f_source_K.x._a)
-            if (k % config["save_frequency"]) == 0 or k == n_steps - 1:
+            if save and snap is not None:
+                history["t"].append(t)
+                history["source"].append(float(p.f_source_K.x._a.max()))
+                history["its_emi"].append(st.iterations[-2][1])
+                history["its_knp"].append(st.iterations[-1][1])
+            elif save:
                 st.download()
                 e, kk = st.iterations[-2][1], st.iterations[-1][1]
                 record(e, kk)
@@ -391,6 +433,9 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
                 if not quiet:
                     print(f"t = {t:.2f} ms  source {'on ' if history['source'][-1] else 'off'}  "
                           f"phi_M neuron {history['phi_M_neuron'][-1]:.4f} glia {history['phi_M_glia'][-1]:.4f} mV")
+        if snap is not None:
+            snap.close()
+            st.download()
         st.dp.sync()
     else:
         problem_emi = create_solver_emi(p.a_emi, p.L_emi, p.phi, p.entity_maps, p.subdomain_list, None,
@@ -422,9 +467,16 @@ def solve_system(config, n_steps=None, device_resident=False, direct=False, outd
             p.set_source(t)
             if (k % config["save_frequency"]) == 0 or k == n_steps - 1:
                 record(problem_emi.solver.getIterationNumber(), problem_knp.solver.getIterationNumber())
-                write_results(p, outdir, k, t)
+                if snapshots:
+                    if snap is None:
+                        snap = make_snapshots(p, outdir, xdmf)
+                    snap.record_host(t, k, p.phi, p.c, p.c_prev, p.phi_M_prev)
+                else:
+                    write_results(p, outdir, k, t)
                 if xdmf_out:
                     xdmf_out.write(p, t)
+        if snap is not None:
+            snap.close()
     if xdmf_out:
         xdmf_out.close()
     if obs is not None:
@@ -461,6 +513,9 @@ def build_parser():
     parser.add_argument("--device-resident", action="store_true", help="DeviceStepper + device Krylov solves")
     parser.add_argument("--direct", action="store_true", help="host LU solves (MUMPS stand-in)")
     parser.add_argument("--xdmf", action="store_true", help="also write results_sub_/results_mem_ XDMF time series")
+    parser.add_argument("--snapshots", action="store_true",
+                        help="save through knpemi.Snapshots: the same files, written off the stepping thread; with "
+                             "--device-resident the fields are packed on the device and downloaded once, at the end")
     parser.add_argument("--series", metavar="PATH", default=None,
                         help="write per-step observables (points, mean phi_M, max ECS K) to this .npz")
     parser.add_argument("--events", metavar="PATH", default=None,
@@ -495,6 +550,6 @@ if __name__ == "__main__":
                            xdmf=args.xdmf, series=args.series, ode_method=args.ode_method,
                            ode_substeps=args.ode_substeps, events=args.events, event_threshold=args.event_threshold,
                            fluxes=args.fluxes, exchange=args.exchange, maps=args.maps, maps_threshold=args.maps_threshold,
-                           monitor=args.monitor)
+                           monitor=args.monitor, snapshots=args.snapshots)
     print(f"{hist['steps']} steps in {hist['wall_s']:.2f} s; phi_M neuron {hist['phi_M_neuron'][-1]:.4f} mV, "
           f"glia {hist['phi_M_glia'][-1]:.4f} mV, max ECS K {hist['K_ecs_max'][-1]:.4f} mM")

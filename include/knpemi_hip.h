@@ -713,6 +713,65 @@ int knpemi_monitor_clear(knpemi_handle* h);
 int knpemi_monitor_eval(knpemi_handle* h, int sub, int model, double t, uint32_t mask, const double* states,
                         const double* params, const int32_t* ion_param, int v_index, double* out, size_t n);
 
+/* Field snapshots: every watched field packed into ONE contiguous frame on the device, copied to pinned host memory by a
+ * stream of its own and handed to the host when the copy is done (knpemi.snapshots).  The reference's astrocyte study
+ * writes every field every save_frequency steps (examples/local_astrocyte_depolarization/run_stim_duration.py:52-90,
+ * 446-460, 487-494: results_sub_<tag>.xdmf, results_mem_<tag>.xdmf and the ADIOS2 checkpoints); with the fields resident
+ * on the device that took one knpemi_get_field per field -- a strided gather and a blocking copy each -- on the stepping
+ * thread.  Here the main stream never waits for the host, and no frame is dropped or overwritten.
+ * A watch is spec[w] = {field, sub, idx, flags}: KNPEMI_F_PHI, _C, _C_PREV, _C_ELIM, _PHI_M, _I_CH as knpemi_set_field
+ * takes them, or KNPEMI_F_ODE_STATE with idx = model * KNPEMI_SNAPSHOT_STATE_STRIDE + state: state component `state`
+ * (< KNPEMI_SNAPSHOT_STATE_STRIDE) of the bound model slot (sub, model), as the device's state table holds it.  flags:
+ * KNPEMI_SNAPSHOT_F32 stores (float)v, round-to-nearest-even (numpy: np.float32(v)); otherwise the double is stored
+ * as it is, bit for bit.  Watches group by space -- the vertices of sub-domain `sub` (phi, c, c_prev, the eliminated
+ * ion), or the membrane dofs of cell `sub` (phi_M, I_ch, states).  A space may carry a selection, an ascending list of
+ * distinct item indices (the box plotting/plot_roi.py clips to): every watch of the space then stores only those items,
+ * in list order.
+ * Frame layout: the watches in the order given, watch w at byte offset[w], a multiple of KNPEMI_SNAPSHOT_ALIGN (the 256
+ * bytes one wavefront stores of a float watch, so every wavefront's store covers whole 128-byte lines), n_items[w] values
+ * of 4 or 8 bytes; the bytes between two watches are not defined.  knpemi_snapshot_layout reports it.
+ * Ring: `depth` slots, each a device frame, a pinned host frame and a "copied" event; a slot is FREE or IN FLIGHT. */
+#define KNPEMI_F_ODE_STATE 7
+#define KNPEMI_SNAPSHOT_MAX_WATCH 64
+#define KNPEMI_SNAPSHOT_STATE_STRIDE 256
+#define KNPEMI_SNAPSHOT_F32 1
+#define KNPEMI_SNAPSHOT_ALIGN 256
+#define KNPEMI_EBUSY (-6)    /* knpemi_snapshot_record: the slot is in flight; knpemi_snapshot_take: the copy has not finished */
+/* Set the n_watch watches (1 <= n_watch <= KNPEMI_SNAPSHOT_MAX_WATCH) and the n_space_sel >= 0 selections: selection j
+ * belongs to space sel_space[j] (sub-domain s: s for its vertices, KNPEMI_MAX_SUB + s for its membrane dofs) and lists
+ * sel_idx[sel_off[j] .. sel_off[j + 1]).  depth: slots of the ring.  Creates the copy stream and the events; replaces any
+ * previous table (frames in flight are dropped); a refused call leaves the previous table in place -- what replaces the
+ * set-up of the writers in run_stim_duration.py:446-460.  KNPEMI_EINVAL: null arguments, an unknown field or flag, sub,
+ * idx, model slot or state out of range, a slot that is not bound, phi_M, I_ch or a state on the ECS, a watch listed twice,
+ * a selection that is empty, unsorted, repeated or out of range, of a space nothing watches, or the second of one space,
+ * depth < 1, too many watches, a handle of knpemi_ode_create. */
+int knpemi_snapshot_set(knpemi_handle* h, int n_watch, const int32_t* spec, int n_space_sel, const int32_t* sel_space,
+                        const int64_t* sel_off, const int32_t* sel_idx, int depth);
+/* offset[w], n_items[w] (n_watch each; either may be NULL) and the frame's size in bytes: what a reader of a frame needs
+ * instead of the function-space bookkeeping behind run_stim_duration.py:52-90.  KNPEMI_EINVAL before knpemi_snapshot_set. */
+int knpemi_snapshot_layout(knpemi_handle* h, int64_t* offset, int64_t* n_items, int64_t* frame_bytes);
+/* Enqueue frame number seq (0, 1, ... since the set-up or the last reset) at time t into slot seq % depth: ONE pack
+ * launch on the main stream behind whatever it holds, an event, and behind that event on the copy stream the copy of the
+ * frame to pinned host memory and the slot's "copied" event -- the checkpoint write of run_stim_duration.py:487-494
+ * without a host synchronisation.  A slot that is IN FLIGHT: nothing is enqueued, nothing changes, KNPEMI_EBUSY.
+ * KNPEMI_EINVAL before knpemi_snapshot_set and for a non-finite t. */
+int knpemi_snapshot_record(knpemi_handle* h, double t);
+/* Hand out the oldest frame IN FLIGHT: wait == 0 polls its "copied" event and returns KNPEMI_EBUSY, touching nothing,
+ * while the copy runs; wait != 0 waits for that one event (no stream is synchronised).  Then the pinned frame is copied
+ * to out (bytes must be the frame's size), the slot becomes FREE and *t, *seq (may be NULL) are the frame's.  Returns 1
+ * -- not an error, nothing written -- with nothing in flight.  This is the read of a checkpoint the reference's figure
+ * scripts do (make_figures.py:135). */
+int knpemi_snapshot_take(knpemi_handle* h, int wait, void* out, size_t bytes, double* t, int64_t* seq);
+/* The number of frames IN FLIGHT (0 before knpemi_snapshot_set): the checkpoints of run_stim_duration.py:487-494 not yet
+ * on the host. */
+int knpemi_snapshot_pending(knpemi_handle* h);
+/* Wait for the copy stream, free every slot and restart seq at 0 (a second run from the same start; the reference would
+ * delete the checkpoints of run_stim_duration.py:487-494); the table stays. */
+int knpemi_snapshot_reset(knpemi_handle* h);
+/* Synchronise both streams and drop the table, the ring, the copy stream and the events (knpemi_snapshot_record then
+ * fails with KNPEMI_EINVAL; the writers of run_stim_duration.py:446-460 are closed); knpemi_destroy does the same. */
+int knpemi_snapshot_clear(knpemi_handle* h);
+
 /* Options of a handle (device-resident loops).
  * KNPEMI_OPT_FUSE_UPDATE (0/1): update_pde_variables follows problem_knp.solve() directly in the reference's loop
  *   (run_3D.py:356,362); with this option the write-back kernel of knpemi_solve_knp -- and of
@@ -831,7 +890,8 @@ int knpemi_comm_halo_hook(void* ctx, void* vec_dev, int which);
 #define KNPEMI_K_KNP_MEMBRANE 3  /* knp_membrane_kernel  */
 #define KNPEMI_K_UPDATE 4        /* update_pde_kernel    */
 #define KNPEMI_K_EMI_MEMBRANE 5  /* emi_membrane_rhs_kernel */
-#define KNPEMI_N_KERNELS 6
+#define KNPEMI_K_SNAPSHOT 6      /* snapshot_pack_kernel */
+#define KNPEMI_N_KERNELS 7
 int knpemi_profile(knpemi_handle* h, uint32_t kernel_mask);
 int knpemi_profile_read(knpemi_handle* h, int kernel, int64_t* launches, double* total_ms);
 

@@ -188,6 +188,28 @@ struct KnMapTab {
   KnMapWatch w[KNPEMI_MAPS_MAX_WATCH];
 };
 
+// Table of the field snapshots (kernels_snapshot.hip), read by the pack kernel.  Spaces, bstart, wstart, first and need_rec
+// as in KnMapTab; n_items[p] is the number of items the space STORES: with a selection sel[p] (ascending item indices,
+// device memory) lane i reads item sel[p][i], without one (NULL) item i, and writes position i of every watch of the space.
+// A watch reads dense[item] (the solver's c, phi_M, I_ch, a row of a state table) or, dense == NULL, slot `slot` of the
+// vertex record, and stores the double, or with f32 (float)v, at byte `off` of the frame (a multiple of
+// KNPEMI_SNAPSHOT_ALIGN).
+struct KnSnapWatch {
+  const double* dense;
+  int slot, f32;
+  long long off;
+};
+struct KnSnapTab {
+  int n_space, n_watch;
+  int bstart[KN_MAPS_MAXSPACE + 1];
+  int wstart[KN_MAPS_MAXSPACE + 1];
+  int n_items[KN_MAPS_MAXSPACE];
+  int first[KN_MAPS_MAXSPACE];
+  int need_rec[KN_MAPS_MAXSPACE];
+  const int* sel[KN_MAPS_MAXSPACE];
+  KnSnapWatch w[KNPEMI_SNAPSHOT_MAX_WATCH];
+};
+
 // (the table of the membrane monitors, KnMonTab: monitor_table.h, shared with the run-time compiled monitor programs)
 
 struct KnOdeModel {
@@ -713,7 +735,27 @@ struct knpemi_handle : KnDevice {
     KnItemFields fields;                 // per dof
     std::vector<void*> allocs;
   } mon;
-  int knp_flags = 0;                  // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
+  // field snapshots (knpemi_snapshot_set, kernels_snapshot.hip): the table, the selections, and a ring of `depth` slots --
+  // a device frame, a pinned host frame and a "copied" event each -- fed by a copy stream of its own.  Slot seq % depth
+  // takes frame seq; the frames [tail, seq) are IN FLIGHT, so a slot is FREE exactly when seq - tail < depth.  The
+  // stream, the events and the pinned frames are not in `allocs`: recorder_free(KnSnap&) (knpemi_record.hip) frees them.
+  struct KnSnap {
+    int n_watch = 0, n_blk = 0, depth = 0;
+    KnSnapTab host{};                    // the table as uploaded
+    int slot_of[KNPEMI_SNAPSHOT_MAX_WATCH] = {};       // watch of knpemi_snapshot_set -> entry of the table
+    long long items_of[KNPEMI_SNAPSHOT_MAX_WATCH] = {};
+    KnSnapTab* tab = nullptr;
+    size_t frame_bytes = 0;
+    long long move_bytes = 0;            // what one launch must move by the algorithm (kn_snapshot_bytes)
+    hipStream_t copy = nullptr;
+    hipEvent_t ev_packed = nullptr;      // the pack launch's end on the main stream; the copy stream waits for it
+    std::vector<char*> dev, pinned;      // [depth] frames
+    std::vector<hipEvent_t> copied;      // [depth]
+    std::vector<double> t_of;            // [depth] the time of the frame a slot holds
+    int64_t seq = 0, tail = 0;
+    std::vector<void*> allocs;
+  } snap;
+  int knp_flags = 0;                 // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with
 };
 
 // The main stream waits for the membrane ODE sweeps on the auxiliary streams: what follows reads phi_M, I_ch or the models'
@@ -758,6 +800,7 @@ int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev
 int kn_launch_events_reset(knpemi_handle* h);
 int kn_launch_maps_record(knpemi_handle* h, double t, double t_prev);
 int kn_launch_maps_reset(knpemi_handle* h);
+int kn_launch_snapshot_pack(knpemi_handle* h, char* frame);
 int kn_launch_flux(knpemi_handle* h, int write_fields);
 int kn_launch_exchange(knpemi_handle* h, int write_fields);
 int kn_launch_monitor(knpemi_handle* h, double t, int write_fields);

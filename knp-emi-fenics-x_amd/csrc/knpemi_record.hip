@@ -70,6 +70,17 @@ void recorder_free(R& rec) {
   kn_free_all(rec.allocs);
   rec = R{};
 }
+// the snapshots own more than device memory: the copy stream (waited for first: a copy may be in flight), the events and
+// the pinned frames
+void recorder_free(knpemi_handle::KnSnap& S) {
+  if (S.copy) (void)hipStreamSynchronize(S.copy);
+  for (hipEvent_t e : S.copied) (void)hipEventDestroy(e);
+  if (S.ev_packed) (void)hipEventDestroy(S.ev_packed);
+  for (char* p : S.pinned) (void)hipHostFree(p);
+  if (S.copy) (void)hipStreamDestroy(S.copy);
+  kn_free_all(S.allocs);
+  S = knpemi_handle::KnSnap{};
+}
 template <class R>
 int recorder_clear(knpemi_handle* h, R knpemi_handle::*which) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
@@ -79,19 +90,19 @@ int recorder_clear(knpemi_handle* h, R knpemi_handle::*which) {
   return KNPEMI_OK;
 }
 // The install rule of every knpemi_*_set: the new recorder is built in a local New<R>, whose allocations go to its own
-// `allocs`.  A return before recorder_install frees that list, and the previous recorder is untouched and still records;
-// recorder_install frees the previous one, which an enqueued record may still read, behind a synchronisation and copies
+// `allocs`.  A return before recorder_install frees what it owns, and the previous recorder is untouched and still records;
+// recorder_install frees the previous one, which an enqueued record may still read, behind a synchronisation and moves
 // the new one in.
 template <class R>
 struct New : R {
-  ~New() { kn_free_all(this->allocs); }
+  ~New() { recorder_free(static_cast<R&>(*this)); }
 };
 template <class R>
 int recorder_install(knpemi_handle* h, R knpemi_handle::*which, New<R>& next) {
   KN_HIP(hipStreamSynchronize(h->stream));
   recorder_free(h->*which);
   h->*which = next;
-  next.allocs.clear();
+  static_cast<R&>(next) = R{};      // the handle owns it now
   return KNPEMI_OK;
 }
 
@@ -151,6 +162,7 @@ int fields_recorded(const KnItemFields& F, const std::string& fn, const std::str
 void kn_record_free(knpemi_handle* h) {
   for (auto* a : {&h->obs.allocs, &h->events.allocs, &h->flux.allocs, &h->exchange.allocs, &h->maps.allocs, &h->mon.allocs})
     kn_free_all(*a);
+  recorder_free(h->snap);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -977,4 +989,240 @@ extern "C" int knpemi_monitor_eval(knpemi_handle* h, int sub, int model, double 
       || (rc = kn_launch_monitor_eval(h, d_tab, W.nq, t, fld, m.mon_kernel[1])))
     return rc;
   return kn_to_host(h->stream, out, fld, n);   // synchronises: the scratch memory is no longer read
+}
+
+// ---------------------------------------------------------------------------------------------------
+// field snapshots (kernels_snapshot.hip)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+const char* const SNAP_NONE = "no snapshots set (knpemi_snapshot_set)";
+size_t snap_align(size_t n) { return (n + KNPEMI_SNAPSHOT_ALIGN - 1) / KNPEMI_SNAPSHOT_ALIGN * KNPEMI_SNAPSHOT_ALIGN; }
+}  // namespace
+
+extern "C" int knpemi_snapshot_set(knpemi_handle* h, int n_watch, const int32_t* spec, int n_space_sel, const int32_t* sel_space,
+                                   const int64_t* sel_off, const int32_t* sel_idx, int depth) {
+  using KnSnap = knpemi_handle::KnSnap;
+  const std::string fn = "knpemi_snapshot_set";
+  if (!h || !spec || (n_space_sel > 0 && (!sel_space || !sel_off || !sel_idx))) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  if (n_watch < 1 || n_watch > KNPEMI_SNAPSHOT_MAX_WATCH)
+    return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_SNAPSHOT_MAX_WATCH watches");
+  if (depth < 1 || depth > (1 << 16)) return kn_fail(KNPEMI_EINVAL, fn + ": depth must be positive (and at most 65536)");
+  if (n_space_sel < 0 || n_space_sel > KN_MAPS_MAXSPACE) return kn_fail(KNPEMI_EINVAL, fn + ": bad number of selections");
+  // the space of a watch: the vertices of sub-domain s (s), or the membrane dofs of cell s (KN_MAXSUB + s)
+  int space[KNPEMI_SNAPSHOT_MAX_WATCH], per_space[KN_MAPS_MAXSPACE] = {};
+  KnFieldLoc loc[KNPEMI_SNAPSHOT_MAX_WATCH];
+  for (int w = 0; w < n_watch; ++w) {
+    const int32_t field = spec[4 * w], sub = spec[4 * w + 1], ix = spec[4 * w + 2], fl = spec[4 * w + 3];
+    const std::string who = fn + ": watch " + std::to_string(w);
+    bool mem = false;
+    switch (field) {
+      case KNPEMI_F_PHI: case KNPEMI_F_C: case KNPEMI_F_C_PREV: case KNPEMI_F_C_ELIM:
+        if (int rc = kn_locate(h, field, sub, ix, &loc[w])) return rc;      // sub / idx out of range
+        break;
+      case KNPEMI_F_I_CH:
+        if (ix < 0) return kn_fail(KNPEMI_EINVAL, who + ": bad I_ch index");
+        [[fallthrough]];
+      case KNPEMI_F_PHI_M:
+        if (int rc = kn_locate(h, field, sub, ix, &loc[w])) return rc;      // ... and phi_M, I_ch on the ECS
+        mem = true;
+        break;
+      case KNPEMI_F_ODE_STATE: {
+        if (sub < 1 || sub >= h->n_sub) return kn_fail(KNPEMI_EINVAL, who + ": a state lives on the membrane of a cell (sub >= 1)");
+        const int model = ix / KNPEMI_SNAPSHOT_STATE_STRIDE, state = ix % KNPEMI_SNAPSHOT_STATE_STRIDE;
+        if (ix < 0 || model >= h->n_models[sub]) return kn_fail(KNPEMI_EINVAL, who + ": membrane model index out of range");
+        const KnOdeModel& m = h->ode[h->moff[sub] + model];
+        if (!m.bound || !m.d_states) return kn_fail(KNPEMI_EINVAL, who + ": membrane model not bound (knpemi_ode_bind)");
+        if (state >= m.n_states) return kn_fail(KNPEMI_EINVAL, who + ": state index out of range");
+        if (m.nq != h->n_q[sub]) return kn_fail(KNPEMI_EINVAL, who + ": the state table does not cover the membrane dofs");
+        loc[w] = {m.d_states + (size_t)state * m.nq, 1, (size_t)m.nq};
+        mem = true;
+        break;
+      }
+      default:
+        return kn_fail(KNPEMI_EINVAL, who + ": unknown field (phi, c, c_prev, the eliminated ion's c, phi_M, I_ch or a state)");
+    }
+    if (fl & ~KNPEMI_SNAPSHOT_F32) return kn_fail(KNPEMI_EINVAL, who + ": unknown flag bits");
+    for (int u = 0; u < w; ++u)
+      if (std::equal(spec + 4 * u, spec + 4 * u + 4, spec + 4 * w)) return kn_fail(KNPEMI_EINVAL, who + " is listed twice");
+    space[w] = mem ? KN_MAXSUB + sub : sub;
+    ++per_space[space[w]];
+    const size_t n_src = (size_t)(mem ? h->n_q[sub] : h->n_vert[sub]);
+    if (loc[w].n != n_src || n_src > (size_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, who + ": field length is not the space's");
+  }
+  // the selections: ascending distinct items of a watched space, one list per space at most
+  const int32_t* sel_of[KN_MAPS_MAXSPACE] = {};
+  int sel_n[KN_MAPS_MAXSPACE] = {};
+  for (int j = 0; j < n_space_sel; ++j) {
+    const int sp = sel_space[j];
+    const std::string who = fn + ": selection " + std::to_string(j);
+    if (sp < 0 || sp >= KN_MAPS_MAXSPACE || !per_space[sp]) return kn_fail(KNPEMI_EINVAL, who + ": not a watched space");
+    if (sel_of[sp]) return kn_fail(KNPEMI_EINVAL, who + ": the space has a selection already");
+    const int64_t lo = sel_off[j], hi = sel_off[j + 1];
+    const int sub = sp >= KN_MAXSUB ? sp - KN_MAXSUB : sp;
+    const int64_t n_src = sp >= KN_MAXSUB ? h->n_q[sub] : h->n_vert[sub];
+    if (lo < 0 || hi <= lo || hi - lo > n_src) return kn_fail(KNPEMI_EINVAL, who + ": empty, or longer than the space");
+    for (int64_t e = lo; e < hi; ++e)
+      if (sel_idx[e] < 0 || sel_idx[e] >= n_src || (e > lo && sel_idx[e] <= sel_idx[e - 1]))
+        return kn_fail(KNPEMI_EINVAL, who + ": indices must be ascending, distinct and inside the space");
+    sel_of[sp] = sel_idx + lo;
+    sel_n[sp] = (int)(hi - lo);
+  }
+  // the frame: the watches in the order given, each at a multiple of KNPEMI_SNAPSHOT_ALIGN
+  New<KnSnap> N;
+  KnSnapTab& T = N.host;
+  size_t off[KNPEMI_SNAPSHOT_MAX_WATCH], end = 0;
+  for (int w = 0; w < n_watch; ++w) {
+    const size_t n = sel_of[space[w]] ? (size_t)sel_n[space[w]] : loc[w].n;
+    off[w] = snap_align(end);
+    end = off[w] + n * ((spec[4 * w + 3] & KNPEMI_SNAPSHOT_F32) ? 4 : 8);
+    N.items_of[w] = (long long)n;
+  }
+  N.frame_bytes = std::max<size_t>(snap_align(end), KNPEMI_SNAPSHOT_ALIGN);
+  KN_HIP(hipSetDevice(h->device));
+  // the table, grouped by space
+  int k = 0;
+  for (int sp = 0; sp < KN_MAPS_MAXSPACE; ++sp) {
+    if (!per_space[sp]) continue;
+    const int p = T.n_space++;
+    const bool mem = sp >= KN_MAXSUB;
+    const int sub = mem ? sp - KN_MAXSUB : sp;
+    T.n_items[p] = sel_of[sp] ? sel_n[sp] : (mem ? h->n_q[sub] : h->n_vert[sub]);
+    T.first[p] = mem ? 0 : h->voff[sub];
+    T.bstart[p + 1] = T.bstart[p] + (T.n_items[p] + 255) / 256;
+    T.wstart[p] = k;
+    if (sel_of[sp])
+      if (int rc = kn_upload(N.allocs, sel_of[sp], (size_t)sel_n[sp], &T.sel[p])) return rc;
+    for (int w = 0; w < n_watch; ++w) {
+      if (space[w] != sp) continue;
+      KnSnapWatch& W = T.w[k];
+      W = KnSnapWatch{};
+      const bool f32 = spec[4 * w + 3] & KNPEMI_SNAPSHOT_F32;
+      if (loc[w].stride == 1) {
+        W.dense = loc[w].base;
+        N.move_bytes += 8LL * T.n_items[p];
+      } else {      // a slot of the vertex records: every read of the kernel stays inside the record of a vertex of `sub`
+        W.slot = (int)((loc[w].base - h->dev.VR) % KN_REC);
+        if (loc[w].stride != KN_REC || W.slot < 3) return kn_fail(KNPEMI_EINVAL, fn + ": field layout not understood");
+        T.need_rec[p] = 1;
+      }
+      W.f32 = f32 ? 1 : 0;
+      W.off = (long long)off[w];
+      N.move_bytes += (f32 ? 4LL : 8LL) * T.n_items[p];
+      N.slot_of[w] = k++;
+    }
+    if (T.need_rec[p]) N.move_bytes += 40LL * T.n_items[p];
+    T.wstart[p + 1] = k;
+  }
+  T.n_watch = n_watch;
+  N.n_watch = n_watch;
+  N.n_blk = T.bstart[T.n_space];
+  N.depth = depth;
+  if (int rc = kn_upload(N.allocs, &T, 1, &N.tab)) return rc;
+  // the ring; a return from here on frees what exists of it (recorder_free)
+  KN_HIP(hipStreamCreateWithFlags(&N.copy, hipStreamNonBlocking));
+  KN_HIP(hipEventCreateWithFlags(&N.ev_packed, hipEventDisableTiming));
+  N.t_of.assign((size_t)depth, 0.0);
+  for (int s = 0; s < depth; ++s) {
+    char* d = nullptr;
+    if (int rc = kn_alloc(N.allocs, N.frame_bytes, &d)) return rc;
+    N.dev.push_back(d);
+    void* host = nullptr;
+    KN_HIP(hipHostMalloc(&host, N.frame_bytes, hipHostMallocDefault));
+    N.pinned.push_back(static_cast<char*>(host));
+    hipEvent_t e = nullptr;
+    KN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    N.copied.push_back(e);
+  }
+  return recorder_install(h, &knpemi_handle::snap, N);
+}
+
+extern "C" int knpemi_snapshot_layout(knpemi_handle* h, int64_t* offset, int64_t* n_items, int64_t* frame_bytes) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  const auto& S = h->snap;
+  if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_snapshot_layout: ") + SNAP_NONE);
+  for (int w = 0; w < S.n_watch; ++w) {
+    if (offset) offset[w] = (int64_t)S.host.w[S.slot_of[w]].off;
+    if (n_items) n_items[w] = (int64_t)S.items_of[w];
+  }
+  if (frame_bytes) *frame_bytes = (int64_t)S.frame_bytes;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_snapshot_record(knpemi_handle* h, double t) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& S = h->snap;
+  if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_snapshot_record: ") + SNAP_NONE);
+  if (!std::isfinite(t)) return kn_fail(KNPEMI_EINVAL, "knpemi_snapshot_record: t must be finite");
+  if (S.seq - S.tail >= S.depth)
+    return kn_fail(KNPEMI_EBUSY, "knpemi_snapshot_record: every slot is in flight (knpemi_snapshot_take frees the oldest)");
+  KN_HIP(hipSetDevice(h->device));
+  const size_t slot = (size_t)(S.seq % S.depth);
+  // the pack reads phi_M, I_ch and the state tables, which the ODE sweeps may write on the auxiliary streams.  The slot is
+  // FREE: the host has taken its previous frame, so that copy is done and the device frame may be overwritten
+  if (int rc = kn_wait_ode_joins(h)) return rc;
+  if (int rc = kn_launch_snapshot_pack(h, S.dev[slot])) return rc;
+  KN_HIP(hipEventRecord(S.ev_packed, h->stream));
+  KN_HIP(hipStreamWaitEvent(S.copy, S.ev_packed, 0));
+  KN_HIP(hipMemcpyAsync(S.pinned[slot], S.dev[slot], S.frame_bytes, hipMemcpyDeviceToHost, S.copy));
+  KN_HIP(hipEventRecord(S.copied[slot], S.copy));
+  S.t_of[slot] = t;
+  ++S.seq;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_snapshot_take(knpemi_handle* h, int wait, void* out, size_t bytes, double* t, int64_t* seq) {
+  const std::string fn = "knpemi_snapshot_take";
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& S = h->snap;
+  if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + SNAP_NONE);
+  if (S.tail == S.seq) return 1;
+  if (!out || bytes != S.frame_bytes) return kn_fail(KNPEMI_EINVAL, fn + ": the buffer must hold one frame (knpemi_snapshot_layout)");
+  KN_HIP(hipSetDevice(h->device));
+  const size_t slot = (size_t)(S.tail % S.depth);
+  if (!wait) {
+    const hipError_t e = hipEventQuery(S.copied[slot]);
+    if (e == hipErrorNotReady) {
+      (void)hipGetLastError();      // not an error: the next launch check must not see it
+      return kn_fail(KNPEMI_EBUSY, fn + ": the oldest frame's copy has not finished");
+    }
+    KN_HIP(e);
+  } else {
+    KN_HIP(hipEventSynchronize(S.copied[slot]));
+  }
+  std::memcpy(out, S.pinned[slot], bytes);
+  if (t) *t = S.t_of[slot];
+  if (seq) *seq = S.tail;
+  ++S.tail;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_snapshot_pending(knpemi_handle* h) { return h ? (int)(h->snap.seq - h->snap.tail) : 0; }
+
+extern "C" int knpemi_snapshot_reset(knpemi_handle* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& S = h->snap;
+  if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_snapshot_reset: ") + SNAP_NONE);
+  KN_HIP(hipSetDevice(h->device));
+  KN_HIP(hipStreamSynchronize(S.copy));
+  S.seq = S.tail = 0;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_snapshot_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::snap); }
+
+// the bytes one pack launch must move by the algorithm: 40 read per bulk item of a space with a record field, 8 per item
+// of every dense watch, and the 4 or 8 written per item of every watch (the selection's indices are not counted)
+extern "C" long long kn_snapshot_bytes(knpemi_handle* h) { return h ? h->snap.move_bytes : 0; }
+
+// tools/recorder_cost.py: n pack launches back to back into the device frame of the next slot, which must be FREE; no
+// copy, no frame recorded
+extern "C" int kn_snapshot_pack_only(knpemi_handle* h, int n) {
+  if (!h || h->snap.n_watch == 0 || n < 0) return kn_fail(KNPEMI_EINVAL, std::string("kn_snapshot_pack_only: ") + SNAP_NONE);
+  auto& S = h->snap;
+  if (S.seq - S.tail >= S.depth) return kn_fail(KNPEMI_EBUSY, "kn_snapshot_pack_only: every slot is in flight");
+  KN_HIP(hipSetDevice(h->device));
+  for (int i = 0; i < n; ++i)
+    if (int rc = kn_launch_snapshot_pack(h, S.dev[(size_t)(S.seq % S.depth)])) return rc;
+  return KNPEMI_OK;
 }

@@ -13,12 +13,12 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KNPEMI_HIP_LIB") or os.path.join(_HERE, "libknpemi_hip.so")   # override: build experiments
 
-OK, EINVAL, EHIP, ENOMEM, EODE, ESOLVE = 0, -1, -2, -3, -4, -5
+OK, EINVAL, EHIP, ENOMEM, EODE, ESOLVE, EBUSY = 0, -1, -2, -3, -4, -5, -6
 PC_JACOBI, PC_AMG = 0, 1
 TRIANGLE, TETRAHEDRON, HEXAHEDRON = 0, 1, 2
 MODEL_HH_SI, MODEL_HH_MV, MODEL_GLIAL = 0, 1, 2
 MAX_IONS, MAX_SUB, MAX_MODELS = 4, 8, 4
-F_PHI, F_C, F_C_PREV, F_C_ELIM, F_PHI_M, F_I_CH, F_SOURCE = range(7)
+F_PHI, F_C, F_C_PREV, F_C_ELIM, F_PHI_M, F_I_CH, F_SOURCE, F_ODE_STATE = range(8)
 A_EMI, P_EMI, A_KNP = 0, 1, 2
 B_EMI, B_KNP = 0, 1
 WANT_P, NO_SPLITTING, SKIP_MEMBRANE_RHS, ON_AUX_STREAM, MEMBRANE_EARLY = 1, 2, 4, 8, 16
@@ -34,10 +34,11 @@ MAPS_MAX_WATCH, MAPS_MAX_PER_SPACE = 32, 8
 MAPS_PEAK, MAPS_TROUGH, MAPS_INTEGRAL, MAPS_THRESHOLD, MAPS_SERIES, MAPS_BELOW = 1, 2, 4, 8, 16, 32
 MAP_V_MAX, MAP_T_MAX, MAP_V_MIN, MAP_T_MIN, MAP_INTEGRAL, MAP_T_ARRIVAL, MAP_EXPOSURE, MAP_EXCESS, MAP_COUNT = range(9)
 MON_MAX, MON_MAX_WATCH = 32, 16
+SNAPSHOT_MAX_WATCH, SNAPSHOT_STATE_STRIDE, SNAPSHOT_F32, SNAPSHOT_ALIGN = 64, 256, 1, 256
 MON_POINT, MON_INTEGRAL, MON_AVERAGE, MON_MIN, MON_MAX_OP = range(5)
-K_ODE, K_EMI_ROWS, K_KNP_ROWS, K_KNP_MEMBRANE, K_UPDATE, K_EMI_MEMBRANE = range(6)
+K_ODE, K_EMI_ROWS, K_KNP_ROWS, K_KNP_MEMBRANE, K_UPDATE, K_EMI_MEMBRANE, K_SNAPSHOT = range(7)
 KERNEL_NAMES = ["ode_step_kernel", "emi_rows_kernel", "knp_rows_kernel", "knp_membrane_kernel", "update_pde_kernel",
-                "emi_membrane_rhs_kernel"]
+                "emi_membrane_rhs_kernel", "snapshot_pack_kernel"]
 
 c_int_p = C.POINTER(C.c_int32)
 c_dbl_p = C.POINTER(C.c_double)
@@ -210,6 +211,13 @@ SIGNATURES = {
     "knpemi_monitor_clear": (C.c_int, [C.c_void_p]),
     "knpemi_monitor_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint32, c_dbl_p, c_dbl_p, c_int_p,
                                       C.c_int, c_dbl_p, C.c_size_t]),
+    "knpemi_snapshot_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_int, c_int_p, C.POINTER(C.c_int64), c_int_p, C.c_int]),
+    "knpemi_snapshot_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "knpemi_snapshot_record": (C.c_int, [C.c_void_p, C.c_double]),
+    "knpemi_snapshot_take": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, c_dbl_p, C.POINTER(C.c_int64)]),
+    "knpemi_snapshot_pending": (C.c_int, [C.c_void_p]),
+    "knpemi_snapshot_reset": (C.c_int, [C.c_void_p]),
+    "knpemi_snapshot_clear": (C.c_int, [C.c_void_p]),
     "knpemi_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "knpemi_trace": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_halo_width": (C.c_int, [C.c_void_p, C.c_int]),

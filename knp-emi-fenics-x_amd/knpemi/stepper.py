@@ -84,8 +84,8 @@ class DeviceStepper:
         self.flags_emi = L.WANT_P | (0 if a.splitting_scheme else L.NO_SPLITTING)
         self.flags_knp = 0 if a.splitting_scheme else L.NO_SPLITTING
         # the attached recorders (knpemi.recording.Tap) by the method that attached them: "exchange" records behind the
-        # last KNP assembly of a step, "observe", "detect", "fluxes" and "track", in this order, behind the end-of-step
-        # update
+        # last KNP assembly of a step, "observe", "detect", "fluxes", "track", "monitor" and "snapshot", in this order,
+        # behind the end-of-step update
         self.taps = {}
         self.upload()
 
@@ -325,6 +325,26 @@ class DeviceStepper:
                      partition_refusal="membrane monitors are not recorded on partitioned steps (a rank's reductions "
                                        "would include its ghost dofs): run DeviceStepper.monitor on one rank")
 
+    # -- field snapshots --------------------------------------------------------------------------------
+    def snapshot(self, snap, every=1, depth=4, t0=0.0):
+        """Snapshot the watched fields of `snap` (knpemi.snapshots.Snapshots) after every `every`-th step, at time
+        t0 + k dt for step k: one pack launch on the main stream, behind the end-of-step update and every other recorder,
+        then the copy of the frame to pinned host memory on a stream of its own; nothing waits for the host.  The ring
+        holds `depth` frames; a tick first hands the frames whose copy is done to the writer, and only a full ring makes
+        it wait, for the oldest frame alone (`snap.stalls`).  `snap.flush()` brings every recorded frame to the sinks.
+        Works unchanged on a cell-partitioned problem (`step(halo)`): the kernel needs no halo and every rank snapshots
+        its local items; `snap.select_owned(halo)` stores the owned ones only."""
+        lib, dp = self.lib, self.dp
+        if depth < 1:
+            raise ValueError("depth must be positive")
+
+        def rewind():
+            snap._rewind()
+        self._attach("snapshot", snap, "field snapshots", every, None, t0, rewind=rewind,
+                     busy="this stepper takes field snapshots already",
+                     attached="these snapshots are attached to a stepper already",
+                     set_up=lambda: snap._attach(dp, int(depth)), record=lambda t, f: snap._tick(t, self.k))
+
     def check_ode_failures(self):
         """`assert success` of odeSolver.py:121 for the device-resident loop: raises KnpemiError(EODE) when LSODA
         failed on any membrane dof since the last check (the counters live on the device; this synchronises)."""
@@ -446,7 +466,8 @@ class DeviceStepper:
         # step's side-stream launches fork from the main stream after it (ev_fork), so none of them overtakes these: the
         # observables' launch, the events' over the membrane dofs, the fluxes' over the cells of the watched sub-domains.
         # the field maps' over the items of the watched spaces, the monitors' over the dofs of the watched model slots.
-        for name in ("observe", "detect", "fluxes", "track", "monitor"):
+        # The snapshot's pack launch comes last: its frame holds what every other recorder of the step has seen.
+        for name in ("observe", "detect", "fluxes", "track", "monitor", "snapshot"):
             if name in self.taps:
                 self.taps[name].tick(self.k, self.dt)
 

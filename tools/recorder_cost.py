@@ -1,5 +1,6 @@
 """Cost of one on-device recorder in the device-resident loop: `--recorder observe | events | fluxes | exchange | maps |
-monitor` (knpemi.observables, .events, .fluxes, .exchange, .maps, .monitor and the DeviceStepper method that attaches each).
+monitor | snapshot` (knpemi.observables, .events, .fluxes, .exchange, .maps, .monitor, .snapshots and the DeviceStepper
+method that attaches each).
 
 Config 2 (tet r=1) or the 995 328-tet mesh (`--workload config3`) with the device solves: ms per whole step with nothing
 recorded (the leg `plain`: the tap switched off, the table stays on the device) and with the recorder's other legs, every
@@ -26,6 +27,17 @@ The recorders:
             every item: an upper bound), v_max / v_min read, the weight of a series watch -- and the rate they make;
   monitor   cell 1: every quantity of the model at two membrane points, and its average, minimum and maximum over the
             membrane: the series row, and with the per-dof fields.
+  snapshot  `Snapshots.watch_results()` as doubles (`f8`) and as floats (`f4`), every step, depth 4, into a sink that drops
+            the frames: pack launch, copy to pinned memory and the take on the host.  Also the pack launch on its own,
+            with streaming and with plain stores: `--records` launches back to back between two device events as us per
+            launch (launch gaps included), the kernel's own time from the library's event profile (KNPEMI_K_SNAPSHOT), and
+            the bytes one launch must move by the algorithm (kn_snapshot_bytes) as a fraction of the HBM peak.
+
+`--save-path` instead compares two ways of saving a run: the three-sub-domain problem of the stim driver
+(examples/local_astrocyte_depolarization, `--resolution`) with the device solves, `--steps` steps saving every
+`--save-every`-th: `download` (DeviceStepper.download + the driver's write_results, on the stepping thread), `snapshots`
+(Snapshots.watch_results + NpzSink, flushed at the end of the window) and `plain` (nothing saved); the legs alternate in
+one process and the median of the windows is printed.
 """
 import argparse
 import contextlib
@@ -205,10 +217,180 @@ def build_maps(s, st, args):
     return ("plain",) + names, switch, extra
 
 
+def build_snapshot(s, st, args):
+    from knpemi import _lib as L
+    from knpemi.snapshots import Snapshots
+    dp, lib = st.dp, st.lib
+    lib.kn_snapshot_bytes.restype, lib.kn_snapshot_bytes.argtypes = C.c_longlong, [C.c_void_p]
+    lib.kn_snapshot_pack_only.restype, lib.kn_snapshot_pack_only.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    lib.kn_snapshot_stream_stores.restype, lib.kn_snapshot_stream_stores.argtypes = C.c_int, [C.c_int]
+    count = [0]
+
+    def drop(t, k, frame):
+        count[0] += 1
+    tabs = {}
+    for name in ("f8", "f4"):
+        tabs[name] = Snapshots(s.mesh, s.ct, s.ft, s.subdomain_list, s.ion_list, sink=drop)
+        tabs[name].watch_results(dtype=name)
+    st.snapshot(tabs["f8"], every=1, depth=4)
+    tap = st.taps["snapshot"]
+    current = ["f8"]
+    stalls = dict(f8=0, f4=0)
+
+    def use(name):
+        """Replace the device table by that of `name`; the tap records into whichever is current."""
+        old = tabs[current[0]]
+        old.flush()
+        stalls[current[0]] += old.stalls
+        old._detach()
+        tabs[name]._attach(dp, 4)
+        tap.target = tabs[name]
+        current[0] = name
+
+    def record(t, f):
+        L.check(tabs[current[0]]._tick(t, st.k))
+
+    def rewind():      # every window starts with DeviceStepper.reset, which restarts the counters
+        stalls[current[0]] += tabs[current[0]].stalls
+        tabs[current[0]]._rewind()
+    tap.record, tap.rewind = record, rewind
+
+    def switch(leg):
+        tap.enabled = leg != "plain"
+        if tap.enabled and leg != current[0]:
+            use(leg)
+
+    def extra(ms):
+        launch = {}
+        default = lib.kn_snapshot_stream_stores(-1)
+        for name in ("f8", "f4"):
+            use(name)
+            b = int(lib.kn_snapshot_bytes(dp.h))
+            launch[name] = dict(algorithmic_bytes=b, frame_bytes=tabs[name]._layout[1])
+            for mode, label in ((1, "stream"), (0, "plain")):
+                lib.kn_snapshot_stream_stores(mode)
+                L.check(lib.kn_snapshot_pack_only(dp.h, 20))
+                us = []
+                for _ in range(args.repeats):
+                    dp.sync()
+                    L.check(lib.knpemi_timer_start(dp.h))
+                    L.check(lib.kn_snapshot_pack_only(dp.h, args.records))
+                    out = C.c_double()
+                    L.check(lib.knpemi_timer_stop_ms(dp.h, C.byref(out)))
+                    us.append(out.value * 1e3 / args.records)
+                # the kernel's own time: an event pair around every launch
+                L.check(lib.knpemi_profile(dp.h, 1 << L.K_SNAPSHOT))
+                L.check(lib.kn_snapshot_pack_only(dp.h, 50))
+                n, tot = C.c_int64(), C.c_double()
+                L.check(lib.knpemi_profile_read(dp.h, L.K_SNAPSHOT, C.byref(n), C.byref(tot)))
+                L.check(lib.knpemi_profile(dp.h, 0))
+                med, kern = float(np.median(us)), tot.value * 1e3 / max(n.value, 1)
+                launch[name][label] = dict(us_per_launch=med, windows_us=us, kernel_us_event_pair=kern,
+                                           gbytes_per_s=b / (med * 1e-6) / 1e9, hbm_fraction=b / (med * 1e-6) / HBM_PEAK,
+                                           hbm_fraction_event_pair=b / (kern * 1e-6) / HBM_PEAK)
+            lib.kn_snapshot_stream_stores(default)
+        return dict(watches=len(tabs["f8"].watches), frames_dropped_into_the_sink=count[0], stalls=stalls, launch=launch,
+                    default_stores="stream" if default else "plain",
+                    algorithmic_bytes=dict(f8=launch["f8"]["algorithmic_bytes"], f4=launch["f4"]["algorithmic_bytes"]))
+    return ("plain", "f8", "f4"), switch, extra
+
+
+def save_path(args):
+    """The --save-path comparison (module docstring); prints one JSON line."""
+    import importlib.util
+    import shutil
+    import tempfile
+    from knpemi.snapshots import NpzSink, Snapshots
+    from knpemi.stepper import DeviceStepper
+    spec = importlib.util.spec_from_file_location("run_stim_duration", os.path.join(
+        ROOT, "examples", "local_astrocyte_depolarization", "run_stim_duration.py"))
+    drv = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(drv)
+    cfg = drv.load_config("baseline")
+    cfg["mesh"]["resolution_factor"] = args.resolution
+    with contextlib.redirect_stdout(io.StringIO()):
+        p = drv.Problem(cfg)
+    st = DeviceStepper((p.a_emi, p.p_emi, p.L_emi), (p.a_knp, p.p_knp, p.L_knp), p.c, p.c_prev, p.phi, p.phi_M_prev,
+                       device_solves=(1e-6, 1e-7))
+    for tag in (1, 2):
+        for mm in p.subdomain_list[tag]["mem_models"]:
+            st.add_membrane_model(mm["ode"], p.stim_params["stimulus"], p.stim_params["stimulus_locator"])
+    st.set_source(0, p.f_source_K.x._a)
+    outdir = tempfile.mkdtemp(prefix="knpemi_save_path_")
+    compressed = not args.uncompressed
+    snap = Snapshots(p.mesh, p.ct, p.ft, p.subdomain_list, p.ion_list, sink=NpzSink(outdir, compressed=compressed, k_offset=-1))
+    snap.watch_results()
+    st.snapshot(snap, every=args.save_every, depth=args.depth)
+    tap = st.taps["snapshot"]
+    if compressed:
+        write = drv.write_results
+    else:
+        def write(p, outdir, k, t):      # the arrays of write_results, without the compression
+            fields = {}
+            for tag in p.subdomain_list:
+                fields[f"phi_{tag}"] = p.phi[tag].x._a
+                for ion, f in zip(p.ion_list[:-1], p.c[tag]):
+                    fields[f"{ion['name']}_{tag}"] = f.x._a
+                fields[f"{p.ion_list[-1]['name']}_{tag}"] = p.ion_list[-1][f"c_{tag}"].x._a
+                if tag > 0:
+                    fields[f"phi_M_{tag}"] = p.phi_M_prev[tag].x._a
+            np.savez(os.path.join(outdir, f"step_{k:06d}.npz"), t=t, **fields)
+    legs = ("plain", "download", "snapshots") if args.save_path == "both" else ("plain", args.save_path)
+    stalls, waits = [], []
+
+    def leg(which):
+        st.reset()
+        tap.enabled = which == "snapshots"
+        with contextlib.redirect_stdout(io.StringIO()):
+            for _ in range(args.warmup):
+                st.step()
+            snap.flush()
+            st.dp.sync()
+            before, waited = snap.stalls, snap.waits
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                st.step()
+                if which == "download" and st.k % args.save_every == 0:
+                    st.download()
+                    write(p, outdir, st.k - 1, st.k * st.dt)
+            if which == "snapshots":
+                snap.flush()
+            st.dp.sync()
+        ms = (time.perf_counter() - t0) * 1e3 / args.steps
+        if which == "snapshots":
+            stalls.append(snap.stalls - before)
+            waits.append(snap.waits - waited)
+        return ms
+    try:
+        for name in legs:
+            leg(name)
+        ms = {name: [] for name in legs}
+        for _ in range(args.repeats):
+            for name in legs:
+                ms[name].append(leg(name))
+        files = len(os.listdir(outdir))
+    finally:
+        snap.close()
+        shutil.rmtree(outdir, ignore_errors=True)
+    out = dict(save_path=args.save_path, resolution=args.resolution, steps=args.steps, save_every=args.save_every,
+               depth=args.depth, compressed=compressed, windows=args.repeats, frame_bytes=snap._layout[1] if snap._layout else None,
+               vertices={t: int(sd["mesh_sub"].num_vertices) for t, sd in p.subdomain_list.items()}, files=files,
+               stalls_per_window=stalls, writer_queue_full_per_window=waits)
+    for name in legs:
+        out[f"ms_per_step_{name}"] = float(np.median(ms[name]))
+    for name in legs[1:]:
+        out[f"us_per_step_{name}"] = float(np.median(np.array(ms[name]) - np.array(ms["plain"])) * 1e3)
+    out["windows_ms"] = ms
+    print(json.dumps(out))
+
+
 RECORDERS = dict(observe=build_observe, events=build_events, fluxes=build_fluxes, exchange=build_exchange, maps=build_maps,
                  monitor=build_monitor)
 KERNEL = dict(observe="observe_kernel", events="events_record_kernel", fluxes="flux_kernel", exchange="exchange_kernel",
               maps="maps_record_kernel", monitor="monitor_kernel")
+# The snapshots are not a series recorder -- frames through a ring instead of rows in a buffer -- and are kept beside the six
+FRAME_RECORDERS = dict(snapshot=build_snapshot)
+FRAME_KERNEL = dict(snapshot="snapshot_pack_kernel")
 
 
 def kernel_stats(path, match):
@@ -226,7 +408,13 @@ def kernel_stats(path, match):
 
 def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--recorder", choices=list(RECORDERS), required=True)
+    ap.add_argument("--recorder", choices=list(RECORDERS) + list(FRAME_RECORDERS), default=None)
+    ap.add_argument("--save-path", choices=["download", "snapshots", "both"], default=None,
+                    help="compare the ways of saving a run instead (module docstring); both: the two, alternating")
+    ap.add_argument("--save-every", type=int, default=5, help="--save-path: save every n-th step (the driver's save_frequency)")
+    ap.add_argument("--depth", type=int, default=4, help="--save-path: slots of the snapshot ring")
+    ap.add_argument("--resolution", type=int, default=1, help="--save-path: resolution_factor of the driver's mesh")
+    ap.add_argument("--uncompressed", action="store_true", help="--save-path: .npz without compression, both ways")
     ap.add_argument("--workload", choices=["config2", "config3"], default="config2")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -239,6 +427,10 @@ def parser():
 
 def main():
     args = parser().parse_args()
+    if args.save_path:
+        return save_path(args)
+    if not args.recorder:
+        raise SystemExit("give --recorder or --save-path")
     from setup_problem import Setup
     from knpemi.stepper import DeviceStepper
     with contextlib.redirect_stdout(io.StringIO()):
@@ -265,7 +457,7 @@ def main():
     # a first, untimed pass of every leg: AMG set-up, solver mode choice, the ODE/assembly overlap decision, the
     # allocation of the field buffers
     leg()
-    legs, switch, extra = RECORDERS[args.recorder](s, st, args)
+    legs, switch, extra = {**RECORDERS, **FRAME_RECORDERS}[args.recorder](s, st, args)
     for name in legs[1:]:
         switch(name)
         leg()
@@ -282,7 +474,9 @@ def main():
         out[f"us_per_step_{name}"] = float(np.median(np.array(ms[name]) - np.array(ms["plain"])) * 1e3)
     out.update(extra(ms), windows_ms=ms)
     if args.stats:
-        for name, (calls, us) in kernel_stats(args.stats, KERNEL[args.recorder]).items():
+        for name, (calls, us) in kernel_stats(args.stats, {**KERNEL, **FRAME_KERNEL}[args.recorder]).items():
+            if args.recorder in FRAME_RECORDERS:      # the template argument of the pack kernel is the kind of store
+                name = dict(fields="stream", series="plain")[name]
             out[f"kernel_{name}"] = dict(calls=calls, average_us=us)
             if name in out.get("algorithmic_bytes", {}):
                 out[f"kernel_{name}"]["hbm_fraction"] = out["algorithmic_bytes"][name] / (us * 1e-6) / HBM_PEAK
