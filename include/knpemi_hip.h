@@ -98,7 +98,9 @@ typedef struct {
   const int32_t* n_vert;             /* [n_sub] vertices (owned + ghost) of each sub-mesh */
   const int32_t* n_cell;             /* [n_sub] */
   const double* const* x;            /* [n_sub] -> n_vert*gdim, row-major */
-  const int32_t* const* cells;       /* [n_sub] -> n_cell*nv sub-mesh vertex ids */
+  const int32_t* const* cells;       /* [n_sub] -> n_cell*nv sub-mesh vertex ids (hexahedra: local vertex j at the reference
+                                        point whose coordinate along axis a is bit a of j; any of the 48 such orders of a
+                                        cell, left-handed ones included; a folded cell is refused) */
   const int32_t* n_q;                /* [n_sub] membrane dofs of Q_sub (0 for the ECS) */
   const int32_t* n_facet;            /* [n_sub] membrane facets of the cell (0 for the ECS) */
   const int32_t* const* facet_e;     /* [n_sub] -> n_facet*nf ECS sub-mesh vertex ids */

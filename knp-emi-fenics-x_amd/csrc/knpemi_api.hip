@@ -130,6 +130,32 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
         VR[(size_t)(h->voff[s] + v) * KN_REC + c] = d->x[s][(size_t)v * d->gdim + c];
   }
 
+  // ---- hexahedra: tensor-product vertex order (bit a of a local vertex = its coordinate along axis a) --------------
+  // Any of the 48 such orders of a cell is taken, left-handed ones included; the trilinear map of a cell given in another
+  // order (e.g. the counter-clockwise order of other formats) folds over, i.e. its Jacobian determinant changes sign
+  // between the corners (the test of knpemi_dg_create)
+  if (NV == 8)
+    for (int s = 0; s < S; ++s)
+      for (int c = h->coff[s]; c < h->coff[s + 1]; ++c) {
+        int pos = 0, neg = 0;
+        for (int j = 0; j < 8; ++j) {
+          double e[3][3];
+          for (int a = 0; a < 3; ++a) {
+            const double* x0 = &VR[(size_t)cells[(size_t)c * 8 + j] * KN_REC];
+            const double* x1 = &VR[(size_t)cells[(size_t)c * 8 + (j ^ (1 << a))] * KN_REC];
+            const double sgn = ((j >> a) & 1) ? -1.0 : 1.0;
+            for (int k = 0; k < 3; ++k) e[a][k] = sgn * (x1[k] - x0[k]);
+          }
+          const double det = e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0]) +
+                             e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
+          pos += det > 0.0;
+          neg += det < 0.0;
+        }
+        if (pos != 8 && neg != 8)
+          return kn_fail(KNPEMI_EINVAL, "knpemi_create: hexahedron " + std::to_string(c - h->coff[s]) + " of sub-domain " +
+                                            std::to_string(s) + " is degenerate or not in tensor-product vertex order");
+      }
+
   // ---- vertex -> cell adjacency (counting sort) ---------------------------------------------------
   std::vector<int64_t> v2c_ptr(Ntot + 1, 0);
   for (size_t i = 0; i < cells.size(); ++i) v2c_ptr[cells[i] + 1]++;
