@@ -15,7 +15,6 @@ Broken dof (cell c, local vertex j) = c * nv + j; fields are arrays of shape (n_
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 import scipy.sparse as sp
@@ -266,7 +265,6 @@ class DGSlab:
 
     def __init__(self, r, l, rank, world, n_ions=3, device=0, cell="tetrahedron"):
         from .fem.idealized import make_mesh_3D_slab
-        from .fem.distributed import Halo
         nx = l * 16 * 2 ** r
         cuts = [(nx * k) // world for k in range(world + 1)]
         self.a, self.b = cuts[rank], cuts[rank + 1]                 # owned hexahedron layers [a, b)
@@ -291,48 +289,19 @@ class DGSlab:
         if rank < world - 1:
             plan["high"] = dict(nb=rank + 1, send=dofs_of_layer(self.b - 1), recv=dofs_of_layer(self.b))
         self.plan = plan
-        self._halo = Halo()          # reuses its packed-buffer plan and transport (mode agreed once, at attach)
+        self.transport = None        # knpemi.fem.transport.Transport on the DG handle (mode agreed once, at attach)
         self._d = None
+        self._hook_error = None
+
+    @property
+    def mode(self):
+        return "not attached" if self.transport is None else self.transport.mode
 
     def attach(self):
-        import torch
-        import torch.distributed as dist
-        h, dp = self._halo, self.dp
-        h.dp, h.L, h.torch, h.dist = dp, L, torch, dist
-        dev = torch.device("cuda", dp.device)
-        h._device = dev
-        stream_ordered = os.environ.get("KNPEMI_HALO_SYNC") is None
-        try:
-            h._ext = torch.cuda.ExternalStream(dp.lib.knpemi_dg_stream(dp.h), device=dev)
-        except (RuntimeError, TypeError):
-            h._ext, stream_ordered = None, False
-        self._native = False
-        if dist.get_backend() == "gloo":
-            h.mode = "gloo host-staged"
-        else:
-            # first choice: the library's own RCCL communicator on the DG handle's stream (knpemi_dg_comm_*), voted on
-            native = os.environ.get("KNPEMI_HALO_TORCH") is None and os.environ.get("KNPEMI_HALO_SYNC") is None
-            if native:
-                buf = C.create_string_buffer(128)
-                ok = dp.lib.knpemi_comm_unique_id(buf, 128) == 0 if dist.get_rank() == 0 else True
-                box = [buf.raw if ok else None]
-                dist.broadcast_object_list(box, src=0)
-                native = box[0] is not None
-                if native:
-                    rc = dp.lib.knpemi_dg_comm_init(dp.h, dist.get_rank(), dist.get_world_size(), box[0], 128)
-                    flag = torch.tensor([1 if rc == 0 else 0], dtype=torch.int32, device=dev)
-                    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-                    native = bool(int(flag.item()))
-            if native:
-                self._native = True
-                h.mode = "library RCCL (knpemi_dg_comm_sendrecv)"
-            else:
-                flag = torch.tensor([1 if stream_ordered else 0], dtype=torch.int32, device=dev)
-                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-                h.mode = "stream-ordered RCCL" if int(flag.item()) else "host-synchronised RCCL"
-        h._stream_ordered = h.mode == "stream-ordered RCCL"
-        self.mode = h.mode
-        self._d = h._device_plan(self.plan, 5)
+        from .fem.transport import Transport, dg_endpoint
+        self.transport = Transport(dg_endpoint(self.dp), self)
+        self.transport.negotiate()
+        self._d = self.transport.plan(self.plan, 5)
 
     def enable_solves(self):
         """`solve_emi` / `solve_knp` of this rank's DGProblem become solves of the GLOBAL systems
@@ -341,7 +310,7 @@ class DGSlab:
         `torch.distributed` ones of the field halo (stream-ordered RCCL, host-synchronised RCCL, gloo host-staged)."""
         if self._d is None and self.world > 1:
             raise RuntimeError("DGSlab.enable_solves: call attach() first")
-        h, dp, torch = self._halo, self.dp, self._halo.torch
+        dp, tr = self.dp, self.transport
         KS, n = dp.K - 1, dp.n
         sh = dp.lib.knpemi_dg_solver_handle(dp.h)
         if not sh:
@@ -349,38 +318,24 @@ class DGSlab:
         self._solver_handle = C.c_void_p(sh)
         knp = lambda g: np.concatenate([np.asarray(g, np.int64) + k * n for k in range(KS)])
         mapped = {key: dict(nb=pl["nb"], send=knp(pl["send"]), recv=knp(pl["recv"])) for key, pl in self.plan.items()}
-        self._vec = {L.B_EMI: h._device_plan(self.plan, 1), L.B_KNP: h._device_plan(mapped, 1)}
-        h._red = torch.zeros(8 + 64, dtype=torch.float64, device=h._device)
+        self._vec = {L.B_EMI: tr.plan(self.plan, 1), L.B_KNP: tr.plan(mapped, 1)}
+        self._red = tr.torch.zeros(8 + 64, dtype=tr.torch.float64, device=tr.ep.device)
         self._hook_error = None
 
-        def allreduce(ctx, m):
-            try:
-                h._allreduce(m)
-                return 0
-            except Exception as exc:       # noqa: BLE001 -- must not propagate through the C frame
-                self._hook_error = exc
-                return -1
-
         def halo(ctx, vec, which):
-            try:
-                d = self._vec[which]
-                if d is not None:
-                    L.check(dp.lib.knpemi_vec_gather(self._solver_handle, vec, d["send_idx"].data_ptr(), d["send_idx"].numel(),
-                                                     d["send_buf"].data_ptr()))
-                    native, self._halo._native = getattr(self._halo, "_native", False), False   # (field halo may be library RCCL)
-                    try:
-                        self._halo._transfer(d)
-                    finally:
-                        self._halo._native = native
-                    L.check(dp.lib.knpemi_vec_scatter(self._solver_handle, vec, d["recv_idx"].data_ptr(), d["recv_idx"].numel(),
-                                                      d["recv_buf"].data_ptr()))
-                return 0
-            except Exception as exc:       # noqa: BLE001
-                self._hook_error = exc
-                return -1
+            d = self._vec[which]
+            if d is not None:
+                L.check(dp.lib.knpemi_vec_gather(self._solver_handle, vec, d["send_idx"].data_ptr(), d["send_idx"].numel(),
+                                                 d["send_buf"].data_ptr()))
+                # the solver's vectors never go through the library's communicator: where the field halo runs on it
+                # (mode "library RCCL"), they take the host-synchronised torch.distributed path.  Kept as it was.
+                tr.transfer(d, library=False)
+                L.check(dp.lib.knpemi_vec_scatter(self._solver_handle, vec, d["recv_idx"].data_ptr(), d["recv_idx"].numel(),
+                                                  d["recv_buf"].data_ptr()))
         own = np.ascontiguousarray(np.repeat(self.owned_cells.astype(np.uint8), dp.nv))
-        self._cb = (L.ALLREDUCE_FN(allreduce), L.HALO_FN(halo))    # keep the callbacks alive
-        L.check(dp.lib.knpemi_dg_set_distributed(dp.h, own.ctypes.data_as(L.c_u8_p), h._red.data_ptr(),
+        self._cb = (L.ALLREDUCE_FN(tr.guarded(lambda ctx, m: tr.allreduce(m, self._red))),     # keep the callbacks alive
+                    L.HALO_FN(tr.guarded(halo)))
+        L.check(dp.lib.knpemi_dg_set_distributed(dp.h, own.ctypes.data_as(L.c_u8_p), self._red.data_ptr(),
                                                  C.cast(self._cb[0], C.c_void_p), C.cast(self._cb[1], C.c_void_p), None))
 
     def exchange(self):
@@ -389,12 +344,5 @@ class DGSlab:
         if d is None:
             return
         L.check(dp.lib.knpemi_dg_halo_pack(dp.h, d["send_idx"].data_ptr(), d["send_idx"].numel(), d["send_buf"].data_ptr()))
-        if self._native:
-            i64 = C.POINTER(C.c_int64)
-            L.check(dp.lib.knpemi_dg_comm_sendrecv(
-                dp.h, d["send_buf"].data_ptr(), d["recv_buf"].data_ptr(), len(d["peer"]), L.iptr(d["peer"]),
-                d["send_off"].ctypes.data_as(i64), d["send_cnt"].ctypes.data_as(i64),
-                d["recv_off"].ctypes.data_as(i64), d["recv_cnt"].ctypes.data_as(i64)))
-        else:
-            self._halo._transfer(d)
+        self.transport.transfer(d)
         L.check(dp.lib.knpemi_dg_halo_unpack(dp.h, d["recv_idx"].data_ptr(), d["recv_idx"].numel(), d["recv_buf"].data_ptr()))

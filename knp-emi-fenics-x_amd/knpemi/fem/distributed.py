@@ -21,8 +21,10 @@ import os
 
 import numpy as np
 
+from .. import _lib as L
 from ..recording import gather_objects
 from .mesh import MeshTags, extract_submesh, match_facets
+from .transport import Transport, cg_endpoint
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -103,18 +105,29 @@ class LocalPart:
 class Halo:
     """Forward (owner -> ghost) halo of one rank.  `plans[kind]` (kind in {'bulk', 'mem'}) maps a label to
     dict(nb=neighbour rank, send=index array, recv=index array) in the global device numbering of the DeviceProblem
-    (vertex ids across sub-meshes, Q-dof ids)."""
+    (vertex ids across sub-meshes, Q-dof ids).  What is exchanged is decided here (the plans, the pack / unpack kernels,
+    the hooks of the distributed solves); how the packed buffers move between the ranks is the business of `transport`
+    (`knpemi.fem.transport.Transport`, bound to the CG handle in `attach`), which also owns the exchange `mode`."""
 
     supports_solves = False
 
     def __init__(self):
         self.plans = None
         self.dp = None
+        self.transport = None
         self._dev = None
-        self.mode = "not attached"
         self.rank = None            # this rank (set by the subclasses)
         self.n_local = None         # {"bulk": local vertex ids, "mem": local membrane dofs} of the device numbering
         self._hook_error = None
+
+    @property
+    def mode(self):
+        return "not attached" if self.transport is None else self.transport.mode
+
+    @property
+    def library_comm(self):
+        """The exchange runs on the library's own communicator (which then also sums the recorders' rank slots)."""
+        return self.transport is not None and self.transport.library
 
     # -- host exchange (CPU tests, Vector.scatter_forward): `arr` = [n_global_ids, width] array ------------------
     def forward_host_array(self, kind, arr, dist):
@@ -133,140 +146,22 @@ class Halo:
 
     # -- device exchange ---------------------------------------------------------------------------------------
     def attach(self, dp):
-        import torch
-        import torch.distributed as dist
-        from .. import _lib as L
-        self.dp, self.L, self.torch, self.dist = dp, L, torch, dist
-        dev = torch.device("cuda", dp.device)
-        self._device = dev
-        n_slots = int(dp.n_models.sum())
-        self.width = {"bulk": int(dp.lib.knpemi_halo_width(dp.h, 0)), "mem": int(dp.lib.knpemi_halo_width(dp.h, 1))}
-        # The exchange mode is chosen ONCE, here, and agreed on by all ranks; a communication error during a run
-        # propagates (the rank exits non-zero) instead of switching modes under a half-posted batch.
-        #   "stream-ordered RCCL": pack kernel -> send/recv -> unpack kernel on the library's stream, no host sync
-        #   "host-synchronised RCCL": KNPEMI_HALO_SYNC=1, or torch cannot wrap the library's stream
-        #   "gloo host-staged": single-GPU rehearsals and CPU tests
-        stream_ordered = os.environ.get("KNPEMI_HALO_SYNC") is None
-        try:
-            self._ext = torch.cuda.ExternalStream(dp.lib.knpemi_stream(dp.h), device=dev)
-        except (RuntimeError, TypeError):
-            self._ext, stream_ordered = None, False
-        self._native = False
-        if dist.get_backend() == "gloo":
-            self.mode = "gloo host-staged"
-        else:
-            # first choice: RCCL called by the library itself (knpemi_comm_*: pack -> ncclSend/ncclRecv group -> unpack
-            # on the library's stream, a few microseconds of host time per exchange instead of ~50 through
-            # torch.distributed's Python layer).  All ranks must agree, so every step of the set-up is voted on.
-            # KNPEMI_HALO_SYNC=1 asks for the host-synchronised exchange, which only the torch transport has
-            native = os.environ.get("KNPEMI_HALO_TORCH") is None and os.environ.get("KNPEMI_HALO_SYNC") is None
-            if native:
-                native = self._native_comm_init(dp, dev)
-            if native:
-                self.mode = "library RCCL (knpemi_comm_sendrecv)"
-                self._native = True
-            else:
-                flag = torch.tensor([1 if stream_ordered else 0], dtype=torch.int32, device=dev)
-                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-                self.mode = "stream-ordered RCCL" if int(flag.item()) else "host-synchronised RCCL"
-        self._stream_ordered = self.mode == "stream-ordered RCCL"
+        self.dp = dp
+        self.transport = Transport(cg_endpoint(dp), self)
+        self.transport.negotiate()
         self._dev = {}
-        for kind in ("bulk", "mem"):
-            self._dev[kind] = self._device_plan(self.plans[kind], self.width[kind])
-
-    def _vote(self, ok, dev):
-        flag = self.torch.tensor([1 if ok else 0], dtype=self.torch.int32, device=dev)
-        self.dist.all_reduce(flag, op=self.dist.ReduceOp.MIN)
-        return bool(int(flag.item()))
-
-    def _native_comm_init(self, dp, dev):
-        """Create the library's own RCCL communicator: rank 0 draws the unique id, torch.distributed carries it."""
-        dist, L = self.dist, self.L
-        rank, world = dist.get_rank(), dist.get_world_size()
-        buf = C.create_string_buffer(128)
-        ok = True
-        if rank == 0:
-            ok = dp.lib.knpemi_comm_unique_id(buf, 128) == 0
-        box = [buf.raw if ok else None]
-        dist.broadcast_object_list(box, src=0)
-        if box[0] is None:
-            return False
-        rc = dp.lib.knpemi_comm_init(dp.h, rank, world, box[0], 128)
-        return self._vote(rc == 0, dev)
-
-    def _device_plan(self, plan, w, index_map=None):
-        """One packed buffer per direction: all neighbours' entries are packed / unpacked by a single kernel launch,
-        the point-to-point operations work on slices of it."""
-        torch, dev = self.torch, self._device
-        sides = list(plan.values())
-        if not sides:
-            return None
-        f = (lambda a: a) if index_map is None else index_map
-        send_idx = np.concatenate([f(pl["send"]) for pl in sides]).astype(np.int32)
-        recv_idx = np.concatenate([f(pl["recv"]) for pl in sides]).astype(np.int32)
-        m = 1 if index_map is None else len(f(np.zeros(1, np.int64)))
-        d = dict(send_idx=torch.from_numpy(send_idx).to(dev), recv_idx=torch.from_numpy(recv_idx).to(dev),
-                 send_buf=torch.empty(len(send_idx) * w, dtype=torch.float64, device=dev),
-                 recv_buf=torch.empty(len(recv_idx) * w, dtype=torch.float64, device=dev), parts=[])
-        so = ro = 0
-        for pl in sides:
-            ns, nr = len(pl["send"]) * w * m, len(pl["recv"]) * w * m
-            d["parts"].append((pl["nb"], slice(so, so + ns), slice(ro, ro + nr)))
-            so, ro = so + ns, ro + nr
-        # the same parts as flat arrays for knpemi_comm_sendrecv
-        d["peer"] = np.array([p[0] for p in d["parts"]], np.int32)
-        for key, idx, attr in (("send_off", 1, "start"), ("recv_off", 2, "start")):
-            d[key] = np.array([getattr(p[idx], attr) for p in d["parts"]], np.int64)
-        d["send_cnt"] = np.array([p[1].stop - p[1].start for p in d["parts"]], np.int64)
-        d["recv_cnt"] = np.array([p[2].stop - p[2].start for p in d["parts"]], np.int64)
-        return d
-
-    def _transfer(self, d):
-        """send_buf -> neighbours -> recv_buf, ordered on the library's stream (see `mode`)."""
-        dp, dist, torch = self.dp, self.dist, self.torch
-        if getattr(self, "_native", False):
-            i64 = C.POINTER(C.c_int64)
-            self.L.check(dp.lib.knpemi_comm_sendrecv(
-                dp.h, d["send_buf"].data_ptr(), d["recv_buf"].data_ptr(), len(d["peer"]), self.L.iptr(d["peer"]),
-                d["send_off"].ctypes.data_as(i64), d["send_cnt"].ctypes.data_as(i64),
-                d["recv_off"].ctypes.data_as(i64), d["recv_cnt"].ctypes.data_as(i64)))
-        elif dist.get_backend() != "gloo":
-            ops = []
-            for nb, ss, rs in d["parts"]:
-                ops += [dist.P2POp(dist.isend, d["send_buf"][ss], nb), dist.P2POp(dist.irecv, d["recv_buf"][rs], nb)]
-            if self._stream_ordered:
-                # RCCL: torch's current stream is the library's stream (ExternalStream), so the send/recv kernels are
-                # ordered after the pack kernel and `wait()` orders the unpack kernel after them: no host
-                # synchronisation anywhere in the exchange (tools/check_async_halo.py rehearses this with real RCCL)
-                with torch.cuda.stream(self._ext):
-                    for req in dist.batch_isend_irecv(ops):
-                        req.wait()
-            else:
-                dp.sync()                        # packed data is complete before RCCL reads it
-                for req in dist.batch_isend_irecv(ops):
-                    req.wait()
-                torch.cuda.current_stream().synchronize()
-        else:                           # single-GPU rehearsal: stage through host memory
-            dp.sync()
-            sb = d["send_buf"].cpu()
-            rb = torch.empty(d["recv_buf"].shape, dtype=torch.float64)
-            ops = []
-            for nb, ss, rs in d["parts"]:
-                ops += [dist.P2POp(dist.isend, sb[ss], nb), dist.P2POp(dist.irecv, rb[rs], nb)]
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-            d["recv_buf"].copy_(rb)
-            torch.cuda.current_stream().synchronize()
+        for k, kind in enumerate(("bulk", "mem")):
+            self._dev[kind] = self.transport.plan(self.plans[kind], int(dp.lib.knpemi_halo_width(dp.h, k)))
 
     def _exchange(self, kind):
-        L, dp = self.L, self.dp
+        dp = self.dp
         d = self._dev.get(kind)
         if d is None:
             return
         k = 0 if kind == "bulk" else 1
         L.check(dp.lib.knpemi_halo_pack(dp.h, k, d["send_idx"].data_ptr(), d["send_idx"].numel(),
                                         d["send_buf"].data_ptr()))
-        self._transfer(d)
+        self.transport.transfer(d)
         L.check(dp.lib.knpemi_halo_unpack(dp.h, k, d["recv_idx"].data_ptr(), d["recv_idx"].numel(),
                                           d["recv_buf"].data_ptr()))
 
@@ -296,7 +191,8 @@ class Halo:
     def enable_solves(self):
         """knpemi_solve_emi / knpemi_solve_knp on this handle become solves of the GLOBAL systems
         (knpemi_set_distributed): halo'd SpMV, all-reduced dot products, per-rank AMG (block Jacobi)."""
-        L, dp, torch = self.L, self.dp, self.torch
+        dp, tr = self.dp, self.transport
+        torch, dist, dev = tr.torch, tr.dist, tr.ep.device
         KS = dp.K - 1
         voff, nvs = dp.voff, dp.n_vert
 
@@ -305,29 +201,22 @@ class Halo:
             s = np.searchsorted(voff[1:], g, side="right")
             base = KS * voff[s] + (g - voff[s])
             return np.concatenate([base + k * nvs[s] for k in range(KS)])
-        self._vec = {L.B_EMI: self._device_plan(self.plans["bulk"], 1),
-                     L.B_KNP: self._device_plan_knp(knp_index)}
-        self._red = torch.zeros(8 + 64, dtype=torch.float64, device=self._device)    # 8 scalars + the coarse vector
+        # per neighbour the KS blocks must stay together in the packed buffer: the KNP plan is built from mapped indices
+        mapped = {key: dict(nb=pl["nb"], send=knp_index(pl["send"]), recv=knp_index(pl["recv"]))
+                  for key, pl in self.plans["bulk"].items()}
+        self._vec = {L.B_EMI: tr.plan(self.plans["bulk"], 1), L.B_KNP: tr.plan(mapped, 1)}
+        self._red = torch.zeros(8 + 64, dtype=torch.float64, device=dev)    # 8 scalars + the coarse vector
         self._hook_error = None
-        allreduce = self._allreduce_hook(self._red)
-
-        def halo(ctx, vec, which):
-            try:
-                self._exchange_vector(vec, which)
-                return 0
-            except Exception as exc:       # noqa: BLE001
-                self._hook_error = exc
-                return -1
         own = np.ascontiguousarray(self.owned_mask())
-        if getattr(self, "_native", False):
+        if tr.library:
             # the solves stay inside the library: its own all-reduce and vector halo are the hooks, the handle the context
             i64 = C.POINTER(C.c_int64)
             for which, d in self._vec.items():
                 if d is None:
-                    d = dict(send_idx=torch.zeros(0, dtype=torch.int32, device=self._device),
-                             recv_idx=torch.zeros(0, dtype=torch.int32, device=self._device),
-                             send_buf=torch.zeros(1, dtype=torch.float64, device=self._device),
-                             recv_buf=torch.zeros(1, dtype=torch.float64, device=self._device),
+                    d = dict(send_idx=torch.zeros(0, dtype=torch.int32, device=dev),
+                             recv_idx=torch.zeros(0, dtype=torch.int32, device=dev),
+                             send_buf=torch.zeros(1, dtype=torch.float64, device=dev),
+                             recv_buf=torch.zeros(1, dtype=torch.float64, device=dev),
                              peer=np.zeros(0, np.int32), send_off=np.zeros(0, np.int64), send_cnt=np.zeros(0, np.int64),
                              recv_off=np.zeros(0, np.int64), recv_cnt=np.zeros(0, np.int64))
                     self._vec[which] = d
@@ -340,60 +229,27 @@ class Halo:
             L.check(dp.lib.knpemi_set_distributed(dp.h, own.ctypes.data_as(L.c_u8_p), self._red.data_ptr(),
                                                   hooks[0], hooks[1], dp.h))
         else:
-            self._cb = (L.ALLREDUCE_FN(allreduce), L.HALO_FN(halo))    # keep the callbacks alive
+            self._cb = (self.allreduce_callback(self._red),                 # keep the callbacks alive
+                        L.HALO_FN(tr.guarded(lambda ctx, vec, which: self._exchange_vector(vec, which))))
             L.check(dp.lib.knpemi_set_distributed(dp.h, own.ctypes.data_as(L.c_u8_p), self._red.data_ptr(),
                                                   C.cast(self._cb[0], C.c_void_p), C.cast(self._cb[1], C.c_void_p), None))
-        if os.environ.get("KNPEMI_NO_COARSE") is None and self.dist.get_world_size() * len(dp.n_vert) <= 64:
-            L.check(dp.lib.knpemi_set_distributed_coarse(dp.h, self.dist.get_rank(), self.dist.get_world_size()))
+        if os.environ.get("KNPEMI_NO_COARSE") is None and dist.get_world_size() * len(dp.n_vert) <= 64:
+            L.check(dp.lib.knpemi_set_distributed_coarse(dp.h, dist.get_rank(), dist.get_world_size()))
         self.supports_solves = True
 
-    def _device_plan_knp(self, knp_index):
-        # per neighbour the KS blocks must stay together in the packed buffer: build the plan from mapped indices
-        mapped = {key: dict(nb=pl["nb"], send=knp_index(pl["send"]), recv=knp_index(pl["recv"]))
-                  for key, pl in self.plans["bulk"].items()}
-        return self._device_plan(mapped, 1)
-
-    def _allreduce_hook(self, buf):
-        """knpemi_allreduce_fn body summing the first n doubles of the device tensor `buf` over the ranks; an exception
-        is kept in `_hook_error` (it must not propagate through the C frame) and reported as a failure."""
-        def allreduce(ctx, n):
-            try:
-                self._allreduce(n, buf)
-                return 0
-            except Exception as exc:       # noqa: BLE001
-                self._hook_error = exc
-                return -1
-        return allreduce
-
     def allreduce_callback(self, buf):
-        """The hook of `_allreduce_hook` as a C function pointer (keep the returned callback object alive)."""
-        return self.L.ALLREDUCE_FN(self._allreduce_hook(buf))
-
-    def _allreduce(self, n, buf=None):
-        dist, torch = self.dist, self.torch
-        buf = self._red if buf is None else buf
-        if dist.get_backend() == "gloo":
-            self.dp.sync()
-            host = buf[:n].cpu()
-            dist.all_reduce(host)
-            buf[:n].copy_(host)
-            torch.cuda.current_stream().synchronize()
-        elif self._stream_ordered:
-            with torch.cuda.stream(self._ext):
-                dist.all_reduce(buf[:n])
-        else:
-            self.dp.sync()
-            dist.all_reduce(buf[:n])
-            torch.cuda.current_stream().synchronize()
+        """knpemi_allreduce_fn summing the first n doubles of the device tensor `buf` over the ranks, as a C function
+        pointer (keep the returned callback object alive); a failure is kept in `_hook_error`."""
+        return L.ALLREDUCE_FN(self.transport.guarded(lambda ctx, n: self.transport.allreduce(n, buf)))
 
     def _exchange_vector(self, vec, which):
-        L, dp = self.L, self.dp
+        dp = self.dp
         d = self._vec[which]
         if d is None:
             return
         L.check(dp.lib.knpemi_vec_gather(dp.h, vec, d["send_idx"].data_ptr(), d["send_idx"].numel(),
                                          d["send_buf"].data_ptr()))
-        self._transfer(d)
+        self.transport.transfer(d)
         L.check(dp.lib.knpemi_vec_scatter(dp.h, vec, d["recv_idx"].data_ptr(), d["recv_idx"].numel(),
                                           d["recv_buf"].data_ptr()))
 

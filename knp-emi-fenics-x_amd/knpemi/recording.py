@@ -66,7 +66,7 @@ def rank_slots(dp, halo, world, n_cols):
     (keep them alive while it records)."""
     import torch
     xbuf = torch.zeros(world * n_cols, dtype=torch.float64, device=torch.device("cuda", dp.device))
-    cb = None if getattr(halo, "_native", False) else halo.allreduce_callback(xbuf)
+    cb = None if halo.library_comm else halo.allreduce_callback(xbuf)
     return (xbuf.data_ptr(), C.cast(cb, C.c_void_p) if cb is not None else None, None), (xbuf, cb)
 
 

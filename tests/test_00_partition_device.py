@@ -6,45 +6,21 @@ row of b_emi / b_knp with a single-rank run of the whole box, bit for bit (tools
 Runs first (file name): the children are started before this process has touched the GPU.
 """
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from partition_ranks import ROOT, free_port, run_ranks
 
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _run_ranks(args, world=2, timeout=420, tool="check_partition_steps.py"):
-    port = _free_port()
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", tool)] + args,
-                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    outs = []
-    try:
-        for p in procs:
-            outs.append(p.communicate(timeout=timeout)[0])
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [p.returncode for p in procs], outs
+TOOL = "check_partition_steps.py"
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["tet", "hex"])
 @pytest.mark.parametrize("mem_halo", [True, False])
 def test_two_rank_device_steps_equal_single_rank_bit_for_bit(kind, mem_halo):
-    rcs, outs = _run_ranks(["--kind", kind, "--steps", "6"] + ([] if mem_halo else ["--no-mem-halo"]))
+    rcs, outs = run_ranks(TOOL, ["--kind", kind, "--steps", "6"] + ([] if mem_halo else ["--no-mem-halo"]))
     assert rcs == [0, 0], "\n".join(outs)
     assert "PARTITION STEPS OK" in outs[0], outs[0]
 
@@ -54,7 +30,7 @@ def test_two_rank_device_steps_equal_single_rank_bit_for_bit(kind, mem_halo):
 def test_general_partition_device_steps_equal_single_rank_bit_for_bit(kind, method, world):
     """The same check with the general cell partitioner (recursive coordinate bisection / layer slabs on the global
     mesh, id-keyed halo: knpemi.fem.distributed), also on three ranks."""
-    rcs, outs = _run_ranks(["--kind", kind, "--steps", "4", "--method", method], world=world)
+    rcs, outs = run_ranks(TOOL, ["--kind", kind, "--steps", "4", "--method", method], world=world)
     assert rcs == [0] * world, "\n".join(outs)
     assert "PARTITION STEPS OK" in outs[0], outs[0]
 
@@ -65,7 +41,7 @@ def test_jittered_shuffled_tetrahedra_on_two_ranks_equal_single_rank_bit_for_bit
     vertices, cells and the vertex order inside every cell shuffled (tests/unstructured_meshes.py), cut in two by recursive
     coordinate bisection.  The general row kernels and the strips of knpemi_create see each cell in another position on a
     rank than on the whole mesh; owned rows of both right-hand sides and the owned membrane fields agree bit for bit."""
-    rcs, outs = _run_ranks(["--kind", "tet", "--steps", "3", "--method", "rcb", "--mesh", "jittered"])
+    rcs, outs = run_ranks(TOOL, ["--kind", "tet", "--steps", "3", "--method", "rcb", "--mesh", "jittered"])
     assert rcs == [0, 0], "\n".join(outs)
     assert "PARTITION STEPS OK" in outs[0], outs[0]
 
@@ -77,7 +53,7 @@ def test_two_rank_time_steps_with_distributed_solves(kind, method):
     SpMV, all-reduced dot products, each rank's AMG V-cycle on its diagonal block) give the fields, membrane
     potentials, currents and ODE states of the single-rank run to solver tolerance (pdeSolver.py:24-35,74-78,99-110
     run the reference's KSP solves on the mesh communicator)."""
-    rcs, outs = _run_ranks(["--kind", kind, "--steps", "4", "--method", method, "--solves"])
+    rcs, outs = run_ranks(TOOL, ["--kind", kind, "--steps", "4", "--method", method, "--solves"])
     assert rcs == [0, 0], "\n".join(outs)
     assert "PARTITION STEPS OK" in outs[0], outs[0]
 
@@ -91,7 +67,7 @@ def test_three_subdomain_driver_on_a_cell_partition(method, world, solves):
     partitioned run reproduces the single-rank run bit for bit (three sub-domain halos, ghost membrane dofs of both
     models integrated redundantly); with the distributed solves to solver tolerance."""
     args = ["--family", "astro", "--kind", "tet", "--steps", "4", "--method", method] + (["--solves"] if solves else [])
-    rcs, outs = _run_ranks(args, world=world)
+    rcs, outs = run_ranks(TOOL, args, world=world)
     assert rcs == [0] * world, "\n".join(outs)
     assert "PARTITION STEPS OK" in outs[0], outs[0]
 
@@ -100,7 +76,7 @@ def test_three_subdomain_driver_on_a_cell_partition(method, world, solves):
 def test_two_rank_solves_with_jacobi_preconditioning_match_single_rank():
     """KNPEMI_PC_JACOBI on a partitioned problem: the scaled SpMV A (D^-1 p) needs the owners' 1 / a_ii on the ghost
     columns (round-2 advisor finding: ghost rows are identity rows, their local inverse diagonal is 1)."""
-    rcs, outs = _run_ranks(["--kind", "tet", "--steps", "3", "--method", "rcb", "--solves", "--jacobi"])
+    rcs, outs = run_ranks(TOOL, ["--kind", "tet", "--steps", "3", "--method", "rcb", "--solves", "--jacobi"])
     assert rcs == [0, 0], "\n".join(outs)
     assert "PARTITION STEPS OK" in outs[0], outs[0]
 
@@ -121,9 +97,8 @@ def test_coarse_space_of_the_distributed_emi_solve_lowers_the_iteration_count(mo
     for off in ("", "1"):
         if off:
             monkeypatch.setenv("KNPEMI_NO_COARSE", "1")
-        rcs, outs = _run_ranks(["--kind", "tet", "--steps", "6", "--method", "slabgen", "--solves", "--resolution", "1",
-                           "--rtol", "1e-5", "1e-7", "--tol", "1e-2"],
-                               world=3)
+        rcs, outs = run_ranks(TOOL, ["--kind", "tet", "--steps", "6", "--method", "slabgen", "--solves", "--resolution", "1",
+                                     "--rtol", "1e-5", "1e-7", "--tol", "1e-2"], world=3)
         assert rcs == [0, 0, 0], "\n".join(outs)
         assert "PARTITION STEPS OK" in outs[0], outs[0]
         mean[off] = float(re.search(r"EMI iterations per solve, mean: ([0-9.]+)", outs[0]).group(1))
@@ -139,7 +114,7 @@ def test_dg_variant_cell_partition_equals_single_rank_bit_for_bit(world, cell):
     sweep, both assemblies, update, ghost refresh through knpemi_dg_halo_pack/unpack with the ghosts poisoned before
     every exchange) the matrix rows, right-hand sides and fields of the owned cells and the potentials, currents and
     ODE states of the owned membrane nodes equal those of the whole box on one rank, bit for bit."""
-    rcs, outs = _run_ranks(["--steps", "3", "--cell", cell], world=world, tool="check_dg_partition.py")
+    rcs, outs = run_ranks("check_dg_partition.py", ["--steps", "3", "--cell", cell], world=world)
     assert rcs == [0] * world, "\n".join(outs)
     assert "DG PARTITION OK" in outs[0], outs[0]
 
@@ -151,7 +126,7 @@ def test_dg_variant_distributed_solves_match_single_rank(cell):
     concentration systems of the DG variant solved GLOBALLY on two slabs -- owned rows, ghost refresh of every SpMV argument,
     all-reduced dot products, per-rank auxiliary-space AMG -- agree with the single-rank solves of the whole box to solver
     accuracy (the reference runs these KSP solves under MPI)."""
-    rcs, outs = _run_ranks(["--steps", "2", "--cell", cell, "--solves"], world=2, tool="check_dg_partition.py")
+    rcs, outs = run_ranks("check_dg_partition.py", ["--steps", "2", "--cell", cell, "--solves"], world=2)
     assert rcs == [0, 0], "\n".join(outs)
     assert "DG PARTITION OK" in outs[0] and "distributed solves" in outs[0], outs[0]
 
@@ -162,7 +137,7 @@ def test_rccl_halo_transport_rehearsal_on_one_gpu():
     stream-ordered exchange through torch.distributed and the library's own transport (knpemi_comm_init / _sendrecv /
     _allreduce) deliver the packed halo without any host synchronisation, over 300 + 5 exchanges; the Krylov solves run
     through the library's own hooks (knpemi_comm_allreduce_hook / knpemi_comm_halo_hook) and solve the same systems."""
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_async_halo.py")], env=env, capture_output=True,
                        text=True, timeout=420)
     out = p.stdout + p.stderr

@@ -7,7 +7,7 @@ Runs early (file name): the children are started before this process has touched
 """
 import pytest
 
-from test_00_partition_device import _run_ranks
+from partition_ranks import run_ranks
 
 
 @pytest.mark.gpu
@@ -15,7 +15,7 @@ from test_00_partition_device import _run_ranks
 def test_two_rank_rk4_steps_equal_single_rank_bit_for_bit(family, method):
     args = ["--kind", "tet", "--steps", "4", "--method", method, "--family", family, "--ode-method", "rk4",
             "--ode-substeps", "25"]
-    rcs, outs = _run_ranks(args)
+    rcs, outs = run_ranks("check_partition_steps.py", args)
     assert rcs == [0, 0], "\n".join(outs)
     assert "PARTITION STEPS OK" in outs[0], outs[0]
     assert "ode_method rk4" in outs[0], outs[0]

@@ -6,42 +6,13 @@ rank holding the whole mesh -- points, minima and maxima bit for bit, sums withi
 
 Runs early (file name): the children are started before this process has touched the GPU.
 """
-import os
-import socket
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOOL = os.path.join(ROOT, "tools", "check_partition_observables.py")
+from partition_ranks import run_ranks
+
+TOOL = "check_partition_observables.py"
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _run_ranks(args, world=2, timeout=420):
-    port = _free_port()
-    procs = []
-    for rank in range(world):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, TOOL] + args, env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT, text=True))
-    outs = []
-    try:
-        for p in procs:
-            outs.append(p.communicate(timeout=timeout)[0])
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-    return [p.returncode for p in procs], outs
 
 
 @pytest.mark.parametrize("kind,method,world,every,capacity", [
@@ -49,8 +20,8 @@ def _run_ranks(args, world=2, timeout=420):
 def test_partitioned_series_equal_single_rank(kind, method, world, every, capacity):
     """Without solves: the partitioned steps are bit-identical to the single-rank ones (test_00_partition_device), so
     the series differ only by the order of summation.  A capacity below the number of records drains mid-run."""
-    rcs, outs = _run_ranks(["--kind", kind, "--method", method, "--steps", "6", "--every", str(every),
-                            "--capacity", str(capacity)], world=world)
+    rcs, outs = run_ranks(TOOL, ["--kind", kind, "--method", method, "--steps", "6", "--every", str(every),
+                                 "--capacity", str(capacity)], world=world)
     assert rcs == [0] * world, "\n".join(outs)
     assert "PARTITION OBSERVABLES OK" in outs[0], outs[0]
 
@@ -58,8 +29,8 @@ def test_partitioned_series_equal_single_rank(kind, method, world, every, capaci
 def test_three_subdomain_driver_series():
     """The astrocyte driver's set-up (ECS + neuron + glia, two membrane models, pulsed ECS source) on an RCB partition,
     with points and membrane points in both cells."""
-    rcs, outs = _run_ranks(["--family", "astro", "--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1",
-                            "--capacity", "3"])
+    rcs, outs = run_ranks(TOOL, ["--family", "astro", "--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1",
+                                 "--capacity", "3"])
     assert rcs == [0, 0], "\n".join(outs)
     assert "PARTITION OBSERVABLES OK" in outs[0], outs[0]
 
@@ -67,13 +38,13 @@ def test_three_subdomain_driver_series():
 def test_partitioned_series_with_distributed_solves():
     """Whole time steps with the distributed Krylov solves: the series agree with the single-rank run to the solver
     tolerance of check_partition_steps.py --solves."""
-    rcs, outs = _run_ranks(["--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1", "--solves"])
+    rcs, outs = run_ranks(TOOL, ["--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1", "--solves"])
     assert rcs == [0, 0], "\n".join(outs)
     assert "PARTITION OBSERVABLES OK" in outs[0], outs[0]
 
 
 def test_two_partitioned_runs_are_bit_identical():
-    rcs, outs = _run_ranks(["--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1", "--repeat"])
+    rcs, outs = run_ranks(TOOL, ["--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1", "--repeat"])
     assert rcs == [0, 0], "\n".join(outs)
     assert "two partitioned runs give identical series" in outs[0] and "PARTITION OBSERVABLES OK" in outs[0], outs[0]
 
@@ -81,7 +52,7 @@ def test_two_partitioned_runs_are_bit_identical():
 def test_library_rccl_record_matches_unpartitioned_rows():
     """One rank, nccl backend: the halo runs on the library's communicator and every record sums the exchange buffer
     with knpemi_comm_allreduce; the rows equal those of the plain observe bit for bit."""
-    rcs, outs = _run_ranks(["--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1", "--capacity", "3",
-                            "--rccl"], world=1)
+    rcs, outs = run_ranks(TOOL, ["--kind", "tet", "--method", "rcb", "--steps", "4", "--every", "1", "--capacity", "3",
+                                 "--rccl"], world=1)
     assert rcs == [0], outs[0]
     assert "library RCCL" in outs[0] and "PARTITION OBSERVABLES OK" in outs[0], outs[0]

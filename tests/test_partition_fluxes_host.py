@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from partition_ranks import free_port
 import test_partition_observables_host as po
 
 DT = 1e-4
@@ -176,7 +177,7 @@ CASES += [("tet", "far", 2), ("hex", "far", 2)]
 @pytest.mark.parametrize("kind,method,world", CASES)
 def test_partial_rows_combine_to_the_single_rank_row(tmp_path, kind, method, world):
     import torch.multiprocessing as mp
-    mp.spawn(_worker, args=(world, po._free_port(), kind, method, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), kind, method, str(tmp_path)), nprocs=world, join=True)
     assert (tmp_path / "ok_0").exists()
 
 
@@ -230,7 +231,7 @@ def _error_worker(rank, world, port, case, out_dir):
                                        ("exchange_capacity", "capacity of rank 1")])
 def test_ranks_that_disagree_raise_on_every_rank(tmp_path, case, text):
     import torch.multiprocessing as mp
-    mp.spawn(_error_worker, args=(2, po._free_port(), case, str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_error_worker, args=(2, free_port(), case, str(tmp_path)), nprocs=2, join=True)
     for r in range(2):
         msg = (tmp_path / f"msg_{r}").read_text()
         assert text in msg, (r, msg)

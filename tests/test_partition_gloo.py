@@ -2,20 +2,15 @@
 import contextlib
 import io
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 
+from partition_ranks import free_port
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _field(x, k):
@@ -115,7 +110,7 @@ def _worker(rank, world, port, kind, out_dir):
 @pytest.mark.parametrize("kind", ["tet", "hex"])
 def test_slab_partition_world2_gloo(tmp_path, kind):
     import torch.multiprocessing as mp
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(2, port, kind, str(tmp_path)), nprocs=2, join=True)
     assert (tmp_path / "ok_0").exists() and (tmp_path / "ok_1").exists()
 
@@ -125,7 +120,7 @@ def test_slab_partition_world8_gloo(tmp_path):
     checks -- ownership partitions the dofs, the forward halo delivers the owners' values, owned rows equal the rows of the
     global assembly -- with eight ranks, interior ranks having two neighbours."""
     import torch.multiprocessing as mp
-    port = _free_port()
+    port = free_port()
     mp.spawn(_worker, args=(8, port, "tet", str(tmp_path)), nprocs=8, join=True)
     assert all((tmp_path / f"ok_{r}").exists() for r in range(8))
 
@@ -233,6 +228,6 @@ def _general_worker(rank, world, port, method, out_dir):
 @pytest.mark.parametrize("world,method", [(2, "rcb"), (4, "rcb"), (3, "slab")])
 def test_general_partition_on_shuffled_mesh_gloo(tmp_path, world, method):
     import torch.multiprocessing as mp
-    port = _free_port()
+    port = free_port()
     mp.spawn(_general_worker, args=(world, port, method, str(tmp_path)), nprocs=world, join=True)
     assert all((tmp_path / f"ok_{r}").exists() for r in range(world))

@@ -5,11 +5,12 @@ minima and maxima bit for bit, sums to rounding."""
 import contextlib
 import io
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
+
+from partition_ranks import free_port
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -18,12 +19,6 @@ POINTS = {
     2: dict(ECS=[25e-6, 3.5e-6], ICS=[25e-6, 2e-6], mem=[25.3e-6, 3e-6]),
     3: dict(ECS=[16.1e-6, 0.45e-6, 0.13e-6], ICS=[16.1e-6, 0.31e-6, 0.27e-6], mem=[16.1e-6, 0.4e-6, 0.33e-6]),
 }
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _paths():
@@ -209,7 +204,7 @@ def _worker(rank, world, port, kind, method, out_dir):
     ("hex", "rcb", 2), ("hex", "slab", 2), ("hex", "slabgen", 4), ("2d", "rcb", 3), ("2d", "slab", 4)])
 def test_partial_rows_combine_to_the_single_rank_row(tmp_path, kind, method, world):
     import torch.multiprocessing as mp
-    mp.spawn(_worker, args=(world, _free_port(), kind, method, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), kind, method, str(tmp_path)), nprocs=world, join=True)
     assert (tmp_path / "ok_0").exists()
 
 
@@ -246,7 +241,7 @@ def _error_worker(rank, world, port, case, out_dir):
                                        ("keys", "keys of rank 1"), ("every", "every of rank 1")])
 def test_bad_definitions_raise_on_every_rank(tmp_path, case, text):
     import torch.multiprocessing as mp
-    mp.spawn(_error_worker, args=(2, _free_port(), case, str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_error_worker, args=(2, free_port(), case, str(tmp_path)), nprocs=2, join=True)
     for r in range(2):
         msg = (tmp_path / f"msg_{r}").read_text()
         assert text in msg, (r, msg)

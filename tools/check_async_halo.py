@@ -6,13 +6,10 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "knp-emi-fenics-x_amd"))
-sys.path.insert(0, os.path.join(ROOT, "examples", "idealized_geometries"))
-os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+import partition_common as pc
+
 os.environ.setdefault("MASTER_PORT", "29577")
-torch.cuda.set_device(0)
-dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+pc.start("nccl", rank=0, world=1)
 from knpemi import _lib as L
 from setup_problem import Setup
 with contextlib.redirect_stdout(io.StringIO()):
@@ -191,5 +188,5 @@ with torch.cuda.stream(ext):
 dp.sync()
 torch.cuda.synchronize()
 print(f"stream-ordered: host enqueue {t_host / 200 * 1e6:.1f} us per exchange, on the stream {e0.elapsed_time(e1) / 200 * 1e3:.1f} us", flush=True)
-dist.destroy_process_group()
+pc.finish(barrier=False)
 sys.exit(0 if ok else 1)

@@ -13,9 +13,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "knp-emi-fenics-x_amd"))
-sys.path.insert(0, os.path.join(ROOT, "examples", "idealized_geometries"))
+import partition_common as pc
 
 
 def setup(dp):
@@ -72,10 +70,8 @@ def main():
                     help="after the steps: the two systems solved on the partition (knpemi_dg_set_distributed) against the "
                          "single-rank solves of the whole box")
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    backend = os.environ.get("KNPEMI_BENCH_BACKEND", "gloo")
-    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
-    dist.init_process_group(backend)
+    rank, world = pc.start(os.environ.get("KNPEMI_BENCH_BACKEND", "gloo"),
+                           device=int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count(), device_id=False)
     from knpemi.dg import DGProblem, DGSlab
     from knpemi.fem.idealized import make_mesh_3D
     dev = torch.cuda.current_device()
@@ -149,8 +145,7 @@ def main():
         if slab._hook_error is not None:
             raise slab._hook_error
         own = np.flatnonzero(slab.owned_cells)
-        parts = [None] * world
-        dist.all_gather_object(parts, (gcell[own], phi_l[own], c_l[:, own]))
+        parts = pc.gather((gcell[own], phi_l[own], c_l[:, own]))
         phi_x = np.zeros((g.n_cells, g.nv))
         c_x = np.zeros((2, g.n_cells, g.nv))
         for gc, ph, cc in parts:
@@ -175,8 +170,7 @@ def main():
         if sol_msg:
             print(sol_msg)
         print("DG PARTITION OK" if int(flag.item()) else "DG PARTITION MISMATCH")
-    dist.barrier()
-    dist.destroy_process_group()
+    pc.finish()
     sys.exit(0 if int(flag.item()) else 1)
 
 

@@ -10,15 +10,12 @@ largest phi_M any dof reaches, and broadcasts it.  Every rank then steps its par
 owned maps (`MembraneEvents.maps(tag, halo=halo)`) to rank 0.  Their union, matched to the single-rank dofs by the
 coordinates, must hold every dof exactly once, and every map must equal the single-rank map bit for bit.
 """
-import argparse, contextlib, io, os, sys
+import argparse, contextlib, io
 import numpy as np
-import torch
+
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "knp-emi-fenics-x_amd"))
-sys.path.insert(0, os.path.join(ROOT, "examples", "idealized_geometries"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import partition_common as pc
 
 from check_partition_steps import init_fields, membrane_models  # noqa: E402
 
@@ -54,10 +51,7 @@ def main():
     ap.add_argument("--method", default="rcb", choices=["slab", "rcb"])
     ap.add_argument("--steps", type=int, default=6)
     a = ap.parse_args()
-    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    torch.cuda.set_device(0)
-    addr = f"tcp://{os.environ.get('MASTER_ADDR', '127.0.0.1')}:{os.environ['MASTER_PORT']}"
-    dist.init_process_group("gloo", init_method=addr, rank=rank, world_size=world)
+    rank, world = pc.start()
     from knpemi.fem import make_mesh_3D
     from knpemi.fem.distributed import make_partitioned_problem
     from setup_problem import Setup
@@ -92,8 +86,7 @@ def main():
     mine = ev.maps(1, halo=s.halo)
     print(f"rank {rank}: transport {s.halo.mode}, {mine['count'].shape[0]} owned of {ev.n_q[1]} local membrane dofs",
           flush=True)
-    parts = [None] * world
-    dist.all_gather_object(parts, mine)
+    parts = pc.gather(mine)
     if rank == 0:
         union = {k: np.concatenate([p[k] for p in parts]) for k in single}
         key = lambda x: [r.tobytes() for r in np.ascontiguousarray(x)]      # noqa: E731
@@ -109,8 +102,7 @@ def main():
               f"{single['v_peak'].min()!r} .. {single['v_peak'].max()!r}")
         print("maps compared:", sorted(single), "records", a.steps)
         print("PARTITION EVENTS OK", flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    pc.finish()
 
 
 if __name__ == "__main__":

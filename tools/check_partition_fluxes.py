@@ -31,12 +31,11 @@ twice) as this rehearsal runs them: with gloo the all-reduce synchronises the st
 """
 import argparse, contextlib, io, json, os, sys, time
 import numpy as np
-import torch
+
 import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in ("knp-emi-fenics-x_amd", os.path.join("examples", "idealized_geometries"), "tools", "tests"):
-    sys.path.insert(0, os.path.join(ROOT, p))
+import partition_common as pc
+sys.path.insert(0, os.path.join(pc.ROOT, "tests"))
 
 from check_partition_steps import init_fields, membrane_models  # noqa: E402
 # the hand-made partition, sum |term| of every sum column and 2^-53: shared with the host test of the same checks
@@ -223,13 +222,7 @@ def main():
     ap.add_argument("--rccl", action="store_true", help="one rank, nccl backend, the library's own communicator")
     ap.add_argument("--cost", type=int, default=0, metavar="N", help="time windows of N steps with the taps off and on")
     a = ap.parse_args()
-    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    torch.cuda.set_device(0)
-    addr = f"tcp://{os.environ.get('MASTER_ADDR', '127.0.0.1')}:{os.environ['MASTER_PORT']}"
-    if a.rccl:
-        dist.init_process_group("nccl", init_method=addr, rank=rank, world_size=world, device_id=torch.device("cuda", 0))
-    else:
-        dist.init_process_group("gloo", init_method=addr, rank=rank, world_size=world)
+    rank, world = pc.start("nccl" if a.rccl else "gloo")
     from knpemi.fem import make_mesh_3D
     from knpemi.fem.distributed import LocalPart, VertexHalo, make_partitioned_astro, make_partitioned_problem
     from knpemi.fem.partition import make_slab_problem
@@ -237,13 +230,9 @@ def main():
     solves = tuple(a.rtol) if a.solves else None
     astro = a.family == "astro"
     scale, v_rest = (100.0, -70.0) if astro else (1.0, -0.0744)
-
-    def gather(obj):
-        out = [None] * world
-        dist.all_gather_object(out, obj)
-        return out
+    gather = pc.gather
     if astro:
-        sys.path.insert(0, os.path.join(ROOT, "examples", "local_astrocyte_depolarization"))
+        sys.path.insert(0, os.path.join(pc.ROOT, "examples", "local_astrocyte_depolarization"))
         import run_stim_duration as rsd
         cfg = dict(rsd.DEFAULTS)
         cfg["mesh"] = dict(kind="box3d", resolution_factor=0, cell_type="tetrahedron" if a.kind == "tet" else "hexahedron",
@@ -364,8 +353,7 @@ def main():
             print("items matched by centroid, fields bit for bit:", n)
         print("rows compared:", ref_fl["t"].shape[0], "every", a.every, "capacity", a.capacity)
         print("PARTITION FLUXES OK", flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    pc.finish()
 
 
 if __name__ == "__main__":

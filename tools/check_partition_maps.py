@@ -12,15 +12,10 @@ every rank that holds it.  Every rank hands its owned maps (`FieldMaps.maps(name
 matched to the single-rank items by the coordinates, must hold every item exactly once, and every map must equal the
 single-rank map bit for bit.  A `FieldMaps` with a series watch is refused by `step(halo)`.
 """
-import argparse, contextlib, io, math, os, sys
+import argparse, contextlib, io, math
 import numpy as np
-import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "knp-emi-fenics-x_amd"))
-sys.path.insert(0, os.path.join(ROOT, "examples", "idealized_geometries"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import partition_common as pc
 
 from check_partition_events import stepper  # noqa: E402
 from check_partition_steps import init_fields  # noqa: E402
@@ -68,10 +63,7 @@ def main():
     ap.add_argument("--method", default="rcb", choices=["slab", "rcb"])
     ap.add_argument("--records", type=int, default=8)
     a = ap.parse_args()
-    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    torch.cuda.set_device(0)
-    addr = f"tcp://{os.environ.get('MASTER_ADDR', '127.0.0.1')}:{os.environ['MASTER_PORT']}"
-    dist.init_process_group("gloo", init_method=addr, rank=rank, world_size=world)
+    rank, world = pc.start()
     from knpemi.fem import make_mesh_3D
     from knpemi.fem.distributed import make_partitioned_problem
     from setup_problem import Setup
@@ -93,8 +85,7 @@ def main():
     mine = {name: fm.maps(name, halo=s.halo) for name in fm.watches}
     print(f"rank {rank}: transport {s.halo.mode}, owned items " +
           ", ".join(f"{n} {m['locations'].shape[0]} of {fm.watches[n].n}" for n, m in mine.items()), flush=True)
-    parts = [None] * world
-    dist.all_gather_object(parts, mine)
+    parts = pc.gather(mine)
     if rank == 0:
         key = lambda x: [r.tobytes() for r in np.ascontiguousarray(x)]      # noqa: E731
         for name, ref in single.items():
@@ -129,8 +120,7 @@ def main():
         raise AssertionError("step(halo) accepted field maps with a series watch")
     if rank == 0:
         print("PARTITION MAPS OK", flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    pc.finish()
 
 
 if __name__ == "__main__":

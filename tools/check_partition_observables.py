@@ -13,13 +13,8 @@ communicator: the record goes through knpemi_comm_allreduce and the rows must eq
 """
 import argparse, contextlib, io, os, sys
 import numpy as np
-import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "knp-emi-fenics-x_amd"))
-sys.path.insert(0, os.path.join(ROOT, "examples", "idealized_geometries"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import partition_common as pc
 
 from check_partition_steps import init_fields, membrane_models  # noqa: E402
 
@@ -125,13 +120,7 @@ def main():
     ap.add_argument("--repeat", action="store_true", help="a second partitioned run must give the identical series")
     ap.add_argument("--rccl", action="store_true", help="one rank, nccl backend, the library's own communicator")
     a = ap.parse_args()
-    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    torch.cuda.set_device(0)
-    addr = f"tcp://{os.environ.get('MASTER_ADDR', '127.0.0.1')}:{os.environ['MASTER_PORT']}"
-    if a.rccl:
-        dist.init_process_group("nccl", init_method=addr, rank=rank, world_size=world, device_id=torch.device("cuda", 0))
-    else:
-        dist.init_process_group("gloo", init_method=addr, rank=rank, world_size=world)
+    rank, world = pc.start("nccl" if a.rccl else "gloo")
     from knpemi.fem import make_mesh_3D
     from knpemi.fem.distributed import make_partitioned_astro, make_partitioned_problem, rcb_partition, slab_partition
     from knpemi.fem.partition import make_slab_problem
@@ -141,7 +130,7 @@ def main():
     scale, v_rest = (100.0, -70.0) if astro else (1.0, -0.0744)
     cells = (1, 2) if astro else (1,)
     if astro:
-        sys.path.insert(0, os.path.join(ROOT, "examples", "local_astrocyte_depolarization"))
+        sys.path.insert(0, os.path.join(pc.ROOT, "examples", "local_astrocyte_depolarization"))
         import run_stim_duration as rsd
         cfg = dict(rsd.DEFAULTS)
         cfg["mesh"] = dict(kind="box3d", resolution_factor=0, cell_type="tetrahedron" if a.kind == "tet" else "hexahedron",
@@ -174,8 +163,7 @@ def main():
         for k in series[0]:
             assert np.array_equal(series[0][k], series[1][k]), ("repeat", k)
         print("two partitioned runs give identical series", flush=True)
-    gathered = [None] * world
-    dist.all_gather_object(gathered, series[0])
+    gathered = pc.gather(series[0])
     for r, other in enumerate(gathered):            # every rank holds the same (global) series
         for k in series[0]:
             assert np.array_equal(other[k], series[0][k]), ("rank", r, k)
@@ -209,8 +197,7 @@ def main():
             assert max(worst.values()) <= (0.0 if a.rccl else 1e-13), worst
         print("rows compared:", ref[0]["t"].shape[0], "every", a.every, "capacity", a.capacity)
         print("PARTITION OBSERVABLES OK", flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    pc.finish()
 
 
 if __name__ == "__main__":

@@ -10,15 +10,10 @@ items the rank owns.  Every rank hands its frames and their `global_ids` to rank
 the whole mesh exactly once, and, put in the order of the global numbers, equal the frame of one rank holding the whole
 mesh bit for bit.
 """
-import argparse, contextlib, io, os, sys
+import argparse, contextlib, io
 import numpy as np
-import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "knp-emi-fenics-x_amd"))
-sys.path.insert(0, os.path.join(ROOT, "examples", "idealized_geometries"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import partition_common as pc
 
 from check_partition_events import stepper  # noqa: E402
 from check_partition_maps import LEVEL, sample  # noqa: E402
@@ -67,10 +62,7 @@ def main():
     ap.add_argument("--method", default="rcb", choices=["slab", "rcb"])
     ap.add_argument("--records", type=int, default=3)
     a = ap.parse_args()
-    rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
-    torch.cuda.set_device(0)
-    addr = f"tcp://{os.environ.get('MASTER_ADDR', '127.0.0.1')}:{os.environ['MASTER_PORT']}"
-    dist.init_process_group("gloo", init_method=addr, rank=rank, world_size=world)
+    rank, world = pc.start()
     from knpemi.fem import make_mesh_3D
     from knpemi.fem.distributed import make_partitioned_problem
     from setup_problem import Setup
@@ -92,8 +84,7 @@ def main():
     ids = {name: snap.global_ids(name, s.halo) for name in snap.watches}
     print(f"rank {rank}: transport {s.halo.mode}, owned items " +
           ", ".join(f"{n} {ids[n].shape[0]} of {snap._n_space(*w.space)}" for n, w in snap.watches.items()), flush=True)
-    parts = [None] * world
-    dist.all_gather_object(parts, (ids, [(t, k, {n: np.array(v) for n, v in f.items()}) for t, k, f in frames]))
+    parts = pc.gather((ids, [(t, k, {n: np.array(v) for n, v in f.items()}) for t, k, f in frames]))
     if rank == 0:
         assert len(single) == a.records
         for j, (t, k, ref) in enumerate(single):
@@ -111,8 +102,7 @@ def main():
         print(f"{len(single)} frames of {list(single[0][2])} compared, "
               f"{[int(v.shape[0]) for v in single[0][2].values()]} items", flush=True)
         print("PARTITION SNAPSHOTS OK", flush=True)
-    dist.barrier()
-    dist.destroy_process_group()
+    pc.finish()
 
 
 if __name__ == "__main__":

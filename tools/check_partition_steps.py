@@ -7,12 +7,8 @@ linear solves) and compares its OWNED membrane fields / ODE states with a single
 """
 import argparse, contextlib, io, os, sys
 import numpy as np
-import torch
-import torch.distributed as dist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "knp-emi-fenics-x_amd"))
-sys.path.insert(0, os.path.join(ROOT, "examples", "idealized_geometries"))
+import partition_common as pc
 
 
 def init_fields(s, L_x, scale=1.0, v_rest=-0.0744):
@@ -122,10 +118,7 @@ def main():
                     help="jittered (with --method rcb / slab, --kind tet): the box with every vertex moved and vertices, cells "
                          "and the vertex order inside the cells shuffled (tests/unstructured_meshes.py: jittered_tet_box)")
     a = ap.parse_args()
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    torch.cuda.set_device(0)
-    dist.init_process_group("gloo", init_method=f"tcp://{os.environ.get('MASTER_ADDR', '127.0.0.1')}:"
-                                                f"{os.environ['MASTER_PORT']}", rank=rank, world_size=world)
+    rank, world = pc.start()
     from knpemi.fem.partition import make_slab_problem
     from knpemi.fem import make_mesh_3D
     from setup_problem import Setup
@@ -133,7 +126,7 @@ def main():
     astro = a.family == "astro"
     scale, v_rest = (100.0, -70.0) if astro else (1.0, -0.0744)
     if astro:
-        sys.path.insert(0, os.path.join(ROOT, "examples", "local_astrocyte_depolarization"))
+        sys.path.insert(0, os.path.join(pc.ROOT, "examples", "local_astrocyte_depolarization"))
         import run_stim_duration as rsd
         cfg = dict(rsd.DEFAULTS)
         cfg["mesh"] = dict(kind="box3d", resolution_factor=a.resolution, cell_type="tetrahedron" if a.kind == "tet" else "hexahedron",
@@ -145,7 +138,7 @@ def main():
     mesh_data = None
     if a.mesh == "jittered":
         assert not astro and a.kind == "tet" and a.method != "slabgen"
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        sys.path.insert(0, os.path.join(pc.ROOT, "tests"))
         from unstructured_meshes import jittered_tet_box
         mesh_data = jittered_tet_box(r=a.resolution, l=2 * world)      # seeded: the same mesh on every rank
     with contextlib.redirect_stdout(io.StringIO()):
@@ -173,8 +166,7 @@ def main():
         halo = s.halo
         own = np.concatenate([ow == rank for _, (gid, ow, _) in sorted(halo.keys["mem"].items())])
         rown = np.concatenate([ow == rank for _, (gid, ow, _) in sorted(halo.keys["bulk"].items())])
-    gathered = [None] * world
-    dist.all_gather_object(gathered, ({k: v[own] for k, v in loc.items()}, {k: v[rown] for k, v in rows.items()}))
+    gathered = pc.gather(({k: v[own] for k, v in loc.items()}, {k: v[rown] for k, v in rows.items()}))
     if rank == 0:
         with contextlib.redirect_stdout(io.StringIO()):
             ctype = {"tet": "tetrahedron", "hex": "hexahedron"}[a.kind]
@@ -233,8 +225,7 @@ def main():
             assert max(worst.values()) == 0.0, worst
         print(f"ode_method {a.ode_method}" + (f", {a.ode_substeps} sub-steps" if a.ode_substeps else ""))
         print("PARTITION STEPS OK")
-    dist.barrier()
-    dist.destroy_process_group()
+    pc.finish()
 
 
 if __name__ == "__main__":
