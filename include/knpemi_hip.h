@@ -634,6 +634,23 @@ int knpemi_maps_reset(knpemi_handle* h);
 /* Drop the table, the state and the buffer (knpemi_maps_record then fails with KNPEMI_EINVAL; the maps of
  * make_figures.py:336-352 are no longer kept); knpemi_destroy does the same. */
 int knpemi_maps_clear(knpemi_handle* h);
+/* knpemi_maps_set with at least one series watch on one rank of a cell-partitioned run (knpemi.maps,
+ * DeviceStepper.track(halo=...); the curve is the region beyond the level over time of make_figures.py:135).  Every rank
+ * passes the same watches, levels and capacity.  weight: as in knpemi_maps_set, but lumped from the cells (membrane
+ * facets) this rank records only -- every cell of the global mesh is recorded by exactly one rank -- so the ranks' measures
+ * add up to the global one and a rank's weights may all be zero.  owned: one byte per item of every series watch,
+ * concatenated as weight: 1 = the rank owns the item and its n column counts it (every item is owned by exactly one rank).
+ * rank, world, xbuf_dev (world * n_cols doubles, zeroed here), allreduce and ctx as in knpemi_observe_set_partitioned.  The
+ * per-item maps of every watch are kept for EVERY local item as without a partition.  knpemi_maps_record then enqueues the
+ * record launch, which writes the rank's (measure, n) columns into xbuf[rank * n_cols + q] (zeros without local items)
+ * instead of a row, the sum of xbuf over the ranks, and record_combine_kernel, which sums the slots of every column in rank
+ * order and appends the row or counts it as dropped.  Every rank appends the same row; n equals that of one rank holding the
+ * whole mesh exactly, the measure to rounding (another order of summation).  knpemi_maps_read, _series_read, _reset and
+ * _clear are unchanged.  KNPEMI_EINVAL as knpemi_maps_set, and without a series watch, for a NULL mask or buffer, a bad
+ * rank or world, and no hook with no communicator; a refused call leaves the previous table alone. */
+int knpemi_maps_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* spec, const double* threshold,
+                                const double* weight, int capacity, const uint8_t* owned, int rank, int world, void* xbuf_dev,
+                                int (*allreduce)(void* ctx, int n), void* ctx);
 
 /* Membrane monitors: the named intermediates of a membrane model's right-hand side -- Nernst potentials, conductances,
  * the currents split by mechanism, the gates' steady states and time constants -- evaluated per membrane dof from what
@@ -706,6 +723,32 @@ int knpemi_monitor_fields(knpemi_handle* h, int watch, int quantity, double* out
 int knpemi_monitor_reset(knpemi_handle* h);
 /* Drop the table and the buffers; knpemi_destroy does the same. */
 int knpemi_monitor_clear(knpemi_handle* h);
+/* knpemi_monitor_set on one rank of a cell-partitioned run (knpemi.monitor, DeviceStepper.monitor(halo=...); the
+ * quantities are those of make_figures.py:279-327).  Every rank passes the same watches, columns, points and capacity.
+ * weights: the dof weights integrated over the membrane facets this rank records only (every facet of the global
+ * membrane is recorded by exactly one rank, which holds all of its dofs with current values: the ghost layer's membrane
+ * dofs are integrated redundantly); they may sum to nothing, and a watched slot may have no local dof.  wsum_global[w]: the
+ * sum of watch w's weights over the ranks, the same bits on every rank, the divisor of its averages.  A point is taken by
+ * one rank; every other rank passes -1 for its four dofs.  rank, world, xbuf_dev (world * n_cols doubles, zeroed here),
+ * allreduce and ctx as in knpemi_observe_set_partitioned.  knpemi_monitor_record then enqueues on the main stream
+ *   1. the record launch(es): the per-dof values of EVERY local dof with fields, and this rank's columns -- sums and
+ *      extrema over its dofs with weight > 0 folded in workgroup order, the averages undivided, a point it does not take 0
+ *      -- into xbuf[rank * n_cols + c] (the operations' identities without a local dof);
+ *   2. the sum of xbuf over the ranks (allreduce, else knpemi_comm_allreduce): an exact all-gather;
+ *   3. record_combine_kernel: the slots of every column folded in rank order -- points, integrals and averages summed from
+ *      0, minima and maxima from +-inf, keeping a NaN as the record kernel does -- the averages divided by wsum_global, the
+ *      row appended or counted as dropped, the other ranks' slots zeroed for the next record.
+ * Every rank appends the same row.  Points, minima and maxima equal those of one rank holding the whole mesh bit for bit;
+ * integrals and averages agree to rounding (another order of summation).  knpemi_monitor_read, _fields (the local dofs),
+ * _reset and _clear are unchanged.  KNPEMI_EINVAL as knpemi_monitor_set -- but for local weights that sum to nothing, a
+ * slot without local dofs and a point without dofs, which are accepted -- and for a NULL wsum_global or buffer, a global
+ * weight sum that is negative or not finite, n_cols < 1, a bad rank or world, no hook with no communicator, a handle of
+ * knpemi_ode_create; a refused call leaves the previous table alone. */
+int knpemi_monitor_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* spec, const int32_t* ion_param,
+                                   const double* weights, int n_cols, const int32_t* col_spec, int n_pts,
+                                   const int32_t* pt_watch, const int32_t* pt_q, const double* pt_w, int capacity,
+                                   const double* wsum_global, int rank, int world, void* xbuf_dev,
+                                   int (*allreduce)(void* ctx, int n), void* ctx);
 /* Evaluate the quantities in `mask` of slot (sub, model) at time t now: one launch, synchronise, copy out
  * out[bits set][n_q], n = their product (the rest currents of run_calibration.py:148-212).  states / params: host tables
  * [n_q][columns] to evaluate instead of the slot's device tables (both or neither; they are copied to scratch memory,

@@ -39,6 +39,11 @@
 // Series tail (record_tail.h): a workgroup's partial holds (measure, n) of the series watches of its space, the four waves
 // summed in order; the last workgroup folds every column over the workgroups of the column's space in their order and
 // appends the row.  Without a series watch the kernel is instantiated without the tail: no ticket, no buffer.
+// Partitioned runs (knpemi_maps_set_partitioned): the item weights of a series watch are lumped from the cells (facets)
+// this rank records, n counts the items the rank owns (one byte per item), and the last workgroup writes the folded columns
+// into this rank's slots of the exchange buffer instead of appending a row; the caller sums the buffer over the ranks and
+// record_combine_kernel (kernels_observe.hip) sums the ranks' slots in rank order and appends the row.  That is a third
+// instantiation (PART): the two single-rank ones do not know of it.
 // This file is built with -ffp-contract=off: the increments are the expressions as written.
 #include <cmath>
 
@@ -62,6 +67,7 @@ struct MapsArgs {
   double* part;
   unsigned long long* ctl;
   double* rows;
+  double* slot;              // partitioned: this rank's n_cols slots of the exchange buffer; nullptr: append the row here
 };
 
 // the space of workgroup b: at most KN_MAPS_MAXSPACE - 1 steps, uniform
@@ -71,7 +77,8 @@ __device__ inline int space_of(const KnMapTab& T, int b) {
   return p;
 }
 
-template <bool SERIES>
+// PART: the series of a partitioned run (a template flag: the single-rank instantiations are the code they were)
+template <bool SERIES, bool PART = false>
 __global__ __launch_bounds__(MAPS_THREADS) void maps_record_kernel(MapsArgs A) {
   __shared__ double sh[MAPS_WAVES][KN_MAPS_SLOTS];
   __shared__ int last;
@@ -160,7 +167,10 @@ __global__ __launch_bounds__(MAPS_THREADS) void maps_record_kernel(MapsArgs A) {
     if constexpr (SERIES) {
       if (W.ser >= 0) {                // uniform over the workgroup
         const bool beyond = valid && fin && b >= 0.0;
-        const double sw = kn_wave_sum(beyond ? W.weight[i] : 0.0), sn = kn_wave_sum(beyond ? 1.0 : 0.0);
+        // partitioned: the weights carry the recorded cells (facets), n counts the items this rank owns
+        bool counted = beyond;
+        if constexpr (PART) counted = beyond && W.owned[i];
+        const double sw = kn_wave_sum(beyond ? W.weight[i] : 0.0), sn = kn_wave_sum(counted ? 1.0 : 0.0);
         if (lane == 0) { sh[wave][2 * W.ser] = sw; sh[wave][2 * W.ser + 1] = sn; }
       }
     }
@@ -177,6 +187,15 @@ __global__ __launch_bounds__(MAPS_THREADS) void maps_record_kernel(MapsArgs A) {
       kn_part_store(&A.part[(size_t)blockIdx.x * KN_MAPS_SLOTS + j], v);
     }
     if (!kn_arrive_last(A.ctl, threadIdx.x < KN_MAPS_SLOTS, &last)) return;
+    if constexpr (PART) {
+      // the columns go to this rank's slots and no row is claimed: record_combine_kernel sums the ranks' slots and appends it
+      for (int q = threadIdx.x; q < T.n_cols; q += MAPS_THREADS) {
+        const int cp = T.col_space[q];
+        A.slot[q] = kn_fold_column<KN_MAPS_SLOTS, MAPS_FOLD_DEPTH>(A.part, T.col_slot[q], T.bstart[cp], T.bstart[cp + 1], false);
+      }
+      if (threadIdx.x == 0) kn_reset_ticket(A.ctl);
+      return;
+    }
     const bool room = kn_claim_row(A.ctl, A.capacity, &row);
     if (room) {
       for (int q = threadIdx.x; q < T.n_cols; q += MAPS_THREADS) {
@@ -211,7 +230,8 @@ __global__ __launch_bounds__(MAPS_THREADS) void maps_reset_kernel(MapsArgs A) {
 
 MapsArgs maps_args(knpemi_handle* h, double t, double t_prev) {
   const auto& M = h->maps;
-  return MapsArgs{t, t_prev, M.tab, h->dev.VR, M.ser.capacity, M.part, M.ser.ctl, M.ser.rows};
+  return MapsArgs{t, t_prev, M.tab, h->dev.VR, M.ser.capacity, M.part, M.ser.ctl, M.ser.rows,
+                  M.slots.xbuf ? M.slots.xbuf + (size_t)M.slots.rank * M.host.n_cols : nullptr};
 }
 
 }  // namespace
@@ -219,7 +239,9 @@ MapsArgs maps_args(knpemi_handle* h, double t, double t_prev) {
 int kn_launch_maps_record(knpemi_handle* h, double t, double t_prev) {
   const auto& M = h->maps;
   if (M.n_blk == 0) return KNPEMI_OK;
-  if (M.host.n_cols > 0)
+  if (M.slots.xbuf)
+    hipLaunchKernelGGL((maps_record_kernel<true, true>), dim3(M.n_blk), dim3(MAPS_THREADS), 0, h->stream, maps_args(h, t, t_prev));
+  else if (M.host.n_cols > 0)
     hipLaunchKernelGGL(maps_record_kernel<true>, dim3(M.n_blk), dim3(MAPS_THREADS), 0, h->stream, maps_args(h, t, t_prev));
   else
     hipLaunchKernelGGL(maps_record_kernel<false>, dim3(M.n_blk), dim3(MAPS_THREADS), 0, h->stream, maps_args(h, t, t_prev));

@@ -29,6 +29,14 @@
 // launch per run of consecutive watches of one program -- one launch for a table of shipped models; the workgroups of all
 // launches of a record share the partials, the ticket and the tail.
 //
+// Partitioned runs (knpemi_monitor_set_partitioned): the dof weights are integrated over the facets this rank records, so
+// the sums and extrema over "the dofs with w_q > 0" need no ownership test.  With rank slots (KnMonArgs::slot, a run-time
+// branch: the hipRTC instantiation compiles from the same header) the last workgroup writes the folded columns, the
+// averages undivided, into this rank's slots of the exchange buffer instead of appending a row; the caller sums the
+// buffer over the ranks and record_combine_kernel (kernels_observe.hip) folds the ranks' slots with the column's
+// operation, keeping a NaN as mon_min / mon_max do, divides the averages by the global sum of weights and appends the
+// row.  A watch without a local dof has no workgroup; a run of launches without workgroups is skipped.
+//
 // This kernel is launch-latency bound: config 2 has 2 952 membrane dofs, 12 workgroups.
 //
 // Built with -ffp-contract=off (Makefile) so that the device and the host build of membrane_monitors.h share the order of
@@ -80,14 +88,17 @@ int launch(knpemi_handle* h, const KnMonArgs& a, int n_blk, bool fields, hipFunc
 int kn_launch_monitor(knpemi_handle* h, double t, int write_fields) {
   const auto& X = h->mon;
   const int f = write_fields ? 1 : 0;
-  KnMonArgs a{X.tab, reinterpret_cast<const int*>(X.cols), X.pt_watch, X.pt_q, X.pt_w, X.pt_val, X.part, X.ser.ctl, X.ser.rows,
-              write_fields ? X.fields.fld : nullptr, X.ser.capacity, 0, X.n_blk, t};
   const KnMonTab& T = X.host;
+  KnMonArgs a{X.tab, reinterpret_cast<const int*>(X.cols), X.pt_watch, X.pt_q, X.pt_w, X.pt_val, X.part, X.ser.ctl, X.ser.rows,
+              write_fields ? X.fields.fld : nullptr, X.slots.xbuf ? X.slots.xbuf + (size_t)X.slots.rank * T.n_cols : nullptr,
+              X.ser.capacity, 0, X.n_blk, t};
   for (int w0 = 0; w0 < T.n_watch;) {      // runs of consecutive watches of one program
     int w1 = w0 + 1;
     while (w1 < T.n_watch && X.fn[w1][f] == X.fn[w0][f]) ++w1;
     a.blk0 = T.bstart[w0];
-    if (int rc = launch(h, a, T.bstart[w1] - T.bstart[w0], f != 0, X.fn[w0][f])) {
+    const int n_blk = T.bstart[w1] - T.bstart[w0];
+    if (n_blk == 0) { w0 = w1; continue; }      // partitioned: watches without a local dof
+    if (int rc = launch(h, a, n_blk, f != 0, X.fn[w0][f])) {
       // the launches of this record that did not happen took no ticket: start the next record's count from zero
       (void)hipMemsetAsync(X.ser.ctl + 2, 0, sizeof(unsigned long long), h->stream);
       return rc;
@@ -99,7 +110,7 @@ int kn_launch_monitor(knpemi_handle* h, double t, int write_fields) {
 
 int kn_launch_monitor_eval(knpemi_handle* h, const KnMonTab* d_tab, int nq, double t, double* fld, hipFunction_t fn) {
   const int n_blk = (nq + MON_THREADS - 1) / MON_THREADS;
-  const KnMonArgs a{d_tab, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fld, 0, 0, n_blk, t};
+  const KnMonArgs a{d_tab, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fld, nullptr, 0, 0, n_blk, t};
   return launch(h, a, n_blk, true, fn);
 }
 

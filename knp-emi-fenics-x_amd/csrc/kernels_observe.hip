@@ -42,12 +42,15 @@ struct ObsArgs {
 };
 
 // the combine launch of a partitioned record, shared with the fluxes and the membrane exchange (kernels_flux.hip,
-// kernels_exchange.hip): their columns have no op table but the watch table's col_max, and no denominators
+// kernels_exchange.hip): their columns have no op table but the watch table's col_max, and no denominators; with the maps'
+// series (kernels_maps.hip: every column a sum) and with the membrane monitors (kernels_monitor.hip: an op and a divisor
+// per column, and minima and maxima that keep a NaN)
 struct CombineArgs {
   int n_cols, capacity, world, rank;
-  const int* op;             // the observables' ops; nullptr: col_max decides, sums and maxima start from 0
+  const int* op;             // the columns' ops; nullptr: col_max decides, sums and maxima start from 0
   const double* denom;       // divisor of a sum; nullptr: none
-  const uint8_t* col_max;
+  const uint8_t* col_max;    // nullptr (and no op): every column is a sum
+  bool keep_nan;             // minimum and maximum keep a NaN (the monitors' mon_min / mon_max), not fmin / fmax
   double* xbuf;              // [world][n_cols], summed over the ranks
   unsigned long long* ctl;
   double* rows;
@@ -55,6 +58,11 @@ struct CombineArgs {
 
 __device__ inline double obs_combine(int op, double a, double b) {
   return op == KNPEMI_OBS_SUM ? a + b : op == KNPEMI_OBS_MIN ? fmin(a, b) : fmax(a, b);
+}
+
+// the monitors' fold: a NaN on either side stays (monitor_kernel.h, mon_min / mon_max)
+__device__ inline double obs_combine_keep_nan(int op, double a, double b) {
+  return op == KNPEMI_OBS_SUM ? a + b : op == KNPEMI_OBS_MIN ? ((a < b || a != a) ? a : b) : ((a > b || a != a) ? a : b);
 }
 
 __device__ inline double obs_identity(int op) {
@@ -122,9 +130,12 @@ __global__ __launch_bounds__(OBS_THREADS) void record_combine_kernel(CombineArgs
   __shared__ unsigned long long row;
   const bool room = kn_claim_row(A.ctl, A.capacity, &row);
   for (int q = threadIdx.x; q < A.n_cols; q += OBS_THREADS) {
-    const int qop = A.op ? A.op[q] : A.col_max[q] ? KNPEMI_OBS_MAX : KNPEMI_OBS_SUM;
+    const int qop = A.op ? A.op[q] : (A.col_max && A.col_max[q]) ? KNPEMI_OBS_MAX : KNPEMI_OBS_SUM;
     double v = A.op ? obs_identity(qop) : 0.0;
-    for (int k = 0; k < A.world; ++k) v = obs_combine(qop, v, A.xbuf[(size_t)k * A.n_cols + q]);
+    for (int k = 0; k < A.world; ++k) {
+      const double x = A.xbuf[(size_t)k * A.n_cols + q];
+      v = A.keep_nan ? obs_combine_keep_nan(qop, v, x) : obs_combine(qop, v, x);
+    }
     if (A.denom && qop == KNPEMI_OBS_SUM) v /= A.denom[q];
     if (room) A.rows[(size_t)row * A.n_cols + q] = v;
   }
@@ -147,8 +158,9 @@ int kn_launch_observe(knpemi_handle* h) {
 }
 
 int kn_launch_record_combine(knpemi_handle* h, const char* who, int n_cols, int capacity, int world, int rank, const int* op,
-                             const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows) {
-  CombineArgs a{n_cols, capacity, world, rank, op, denom, col_max, xbuf, ctl, rows};
+                             const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows,
+                             bool keep_nan) {
+  CombineArgs a{n_cols, capacity, world, rank, op, denom, col_max, keep_nan, xbuf, ctl, rows};
   hipLaunchKernelGGL(record_combine_kernel, dim3(1), dim3(OBS_THREADS), 0, h->stream, a);
   return kn_launch_check(who);
 }

@@ -165,7 +165,8 @@ struct KnWatchTab {
 // per watch, [n_items] each, NULL where the statistic is not selected (v_prev: with the integral or the threshold only --
 // peak and trough do not depend on it).  A series watch has the item weights `weight` and the slots 2 j, 2 j + 1 (measure, n)
 // of its workgroups' partials, j its number among the series watches of the space; column q of the row folds slot
-// col_slot[q] over the workgroups of space col_space[q].
+// col_slot[q] over the workgroups of space col_space[q].  Partitioned (knpemi_maps_set_partitioned): `weight` is lumped from
+// the items' cells (facets) this rank records, and n counts the items with owned[item] != 0.
 #define KN_MAPS_MAXSPACE (2 * KN_MAXSUB)
 #define KN_MAPS_SLOTS (2 * KNPEMI_MAPS_MAX_PER_SPACE)
 #define KN_MAPS_MAXCOLS (2 * KNPEMI_MAPS_MAX_WATCH)
@@ -176,6 +177,7 @@ struct KnMapWatch {
   double *v_prev, *v_max, *t_max, *v_min, *t_min, *integral, *t_arrival, *exposure, *excess;
   int* count;
   const double* weight;
+  const uint8_t* owned;          // partitioned series watch: 1 where this rank's n counts the item; NULL: every item
 };
 struct KnMapTab {
   int n_space, n_watch, n_cols;
@@ -715,6 +717,7 @@ struct knpemi_handle : KnDevice {
     KnMapTab* tab = nullptr;
     double* part = nullptr;              // [n_blk][KN_MAPS_SLOTS] workgroup partials (series watches only)
     KnSeries ser;
+    KnRankSlots slots;                   // knpemi_maps_set_partitioned: [world][n_cols], every column a sum
     std::vector<void*> allocs;
   } maps;
   // membrane monitors (knpemi_monitor_set, kernels_monitor.hip): a watch table, the columns and points of the series row,
@@ -733,6 +736,11 @@ struct knpemi_handle : KnDevice {
     double* part = nullptr;              // [n_blk][KN_MON_SLOTS] workgroup partials
     KnSeries ser;
     KnItemFields fields;                 // per dof
+    // partitioned runs (knpemi_monitor_set_partitioned): the rank's slots of [world][n_cols] and, per column, the fold
+    // over the ranks (KNPEMI_OBS_SUM / _MIN / _MAX) and the divisor of its sum (the global weight sum of an average, else 1)
+    KnRankSlots slots;
+    int* col_op = nullptr;               // [n_cols]
+    double* col_denom = nullptr;         // [n_cols]
     std::vector<void*> allocs;
   } mon;
   // field snapshots (knpemi_snapshot_set, kernels_snapshot.hip): the table, the selections, and a ring of `depth` slots --
@@ -793,9 +801,11 @@ int kn_launch_update_pde(knpemi_handle* h);
 int kn_launch_observe(knpemi_handle* h);
 int kn_launch_observe_combine(knpemi_handle* h);
 // the combine launch of a partitioned record (kernels_observe.hip): op / denom of the observables, or op == nullptr and
-// col_max of a watch table (sums and maxima from 0)
+// col_max of a watch table (sums and maxima from 0; both NULL: every column a sum).  keep_nan: minimum and maximum keep a NaN
+// as the monitors' mon_min / mon_max do (fmin / fmax, the observables' fold, drop it)
 int kn_launch_record_combine(knpemi_handle* h, const char* who, int n_cols, int capacity, int world, int rank, const int* op,
-                             const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows);
+                             const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows,
+                             bool keep_nan = false);
 int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev);
 int kn_launch_events_reset(knpemi_handle* h);
 int kn_launch_maps_record(knpemi_handle* h, double t, double t_prev);

@@ -10,9 +10,9 @@
 //
 // What several recorders need is written once, as a small struct of the handle and its routines below: the install rule of
 // every knpemi_*_set (New, recorder_install), the rank slots of a partitioned record (KnRankSlots: observables, fluxes,
-// exchange -- the record launch writes the rank's partial row into its slots of an exchange buffer, slots_sum sums the
-// buffer over the ranks, and record_combine_kernel (kernels_observe.hip) folds the slots in rank order and appends the
-// row), the clock of the recorders that integrate between two records (KnRecordClock: events, maps) and the per-item
+// exchange, monitors, the maps' series -- the record launch writes the rank's partial row into its slots of an exchange
+// buffer, slots_sum sums the buffer over the ranks, and record_combine_kernel (kernels_observe.hip) folds the slots in
+// rank order and appends the row), the clock of the recorders that integrate between two records (KnRecordClock: events, maps) and the per-item
 // fields (KnItemFields: fluxes, exchange, monitors).
 #include <algorithm>
 #include <cmath>
@@ -591,9 +591,17 @@ extern "C" int knpemi_exchange_clear(knpemi_handle* h) { return recorder_clear(h
 // ---------------------------------------------------------------------------------------------------
 // field maps (kernels_maps.hip)
 // ---------------------------------------------------------------------------------------------------
-extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spec, const double* threshold,
-                               const double* weight, int capacity) {
-  const std::string fn = "knpemi_maps_set";
+namespace {
+// what knpemi_maps_set_partitioned adds to knpemi_maps_set
+struct MapsPart {
+  const uint8_t* owned;      // one byte per item of every series watch, concatenated as `weight`
+  KnRankSlots slots;
+};
+
+// knpemi_maps_set and, with `part`, knpemi_maps_set_partitioned
+int maps_set(knpemi_handle* h, const char* who, int n_watch, const int32_t* spec, const double* threshold, const double* weight,
+             int capacity, const MapsPart* part = nullptr) {
+  const std::string fn(who);
   if (!h || !spec) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
   if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
   if (n_watch < 1 || n_watch > KNPEMI_MAPS_MAX_WATCH) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MAPS_MAX_WATCH watches");
@@ -629,6 +637,11 @@ extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spe
     space[w] = field == KNPEMI_F_PHI_M ? KN_MAXSUB + sub : sub;
     if (++per_space[space[w]] > KNPEMI_MAPS_MAX_PER_SPACE)
       return kn_fail(KNPEMI_EINVAL, fn + ": more than KNPEMI_MAPS_MAX_PER_SPACE watches on one space");
+  }
+  if (part) {
+    if (!any_series) return kn_fail(KNPEMI_EINVAL, fn + ": no watch has a series (knpemi_maps_set records the maps of a partitioned run)");
+    if (!part->owned) return kn_fail(KNPEMI_EINVAL, fn + ": the owned mask is required");
+    if (int rc = slots_check(h, fn, part->slots, KN_MAPS_MAXCOLS)) return rc;
   }
   // the table, grouped by space
   New<knpemi_handle::KnMaps> N;
@@ -684,6 +697,11 @@ extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spe
         double* dw = nullptr;
         rc = kn_upload(N.allocs, weight + w_off[w], n, &dw);
         W.weight = dw;
+        if (!rc && part) {
+          uint8_t* own = nullptr;
+          rc = kn_upload(N.allocs, part->owned + w_off[w], n, &own);
+          W.owned = own;
+        }
       }
       if (rc) return rc;
       N.slot_of[w] = k;
@@ -709,10 +727,24 @@ extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spe
   if (!rc && any_series) {
     rc = kn_alloc(N.allocs, (size_t)N.n_blk * KN_MAPS_SLOTS, &N.part);
     if (!rc) rc = series_alloc(N.allocs, h->stream, capacity, T.n_cols, &N.ser);
+    if (!rc && part) rc = slots_attach(h, &N.slots, part->slots, T.n_cols);
   }
   if (rc || (rc = recorder_install(h, &knpemi_handle::maps, N))) return rc;
   if ((rc = kn_launch_maps_reset(h))) recorder_free(h->maps);
   return rc;
+}
+}  // namespace
+
+extern "C" int knpemi_maps_set(knpemi_handle* h, int n_watch, const int32_t* spec, const double* threshold,
+                               const double* weight, int capacity) {
+  return maps_set(h, "knpemi_maps_set", n_watch, spec, threshold, weight, capacity);
+}
+
+extern "C" int knpemi_maps_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* spec, const double* threshold,
+                                           const double* weight, int capacity, const uint8_t* owned, int rank, int world,
+                                           void* xbuf_dev, knpemi_allreduce_fn allreduce, void* ctx) {
+  const MapsPart part{owned, {static_cast<double*>(xbuf_dev), rank, world, allreduce, ctx}};
+  return maps_set(h, "knpemi_maps_set_partitioned", n_watch, spec, threshold, weight, capacity, &part);
 }
 
 extern "C" int knpemi_maps_record(knpemi_handle* h, double t) {
@@ -724,7 +756,12 @@ extern "C" int knpemi_maps_record(knpemi_handle* h, double t) {
   // the first record's interval is never used: every v_prev is NaN then
   if (int rc = kn_launch_maps_record(h, t, M.clock.have_prev ? M.clock.t_prev : t)) return rc;
   clock_advance(M.clock, t);
-  return KNPEMI_OK;
+  if (!M.slots.xbuf) return KNPEMI_OK;
+  // partitioned: this rank's slots are written (never, without a local item: zeros); sum the exchange buffer over the ranks,
+  // then sum the slots and append
+  if (int rc = slots_sum(h, "knpemi_maps_record", M.slots, M.ser.n_cols)) return rc;
+  return kn_launch_record_combine(h, "record_combine_kernel (maps)", M.ser.n_cols, M.ser.capacity, M.slots.world, M.slots.rank,
+                                  nullptr, nullptr, nullptr, M.slots.xbuf, M.ser.ctl, M.ser.rows);
 }
 
 extern "C" int knpemi_maps_read(knpemi_handle* h, int watch, int which, void* host, size_t n) {
@@ -784,9 +821,10 @@ namespace {
 const char* const MON_NONE = "no monitors set (knpemi_monitor_set)";
 
 // the watch of slot (sub, model) with the quantities `mask`: checks the slot, the mask, v_index and (pde) the parameter
-// columns of the ions; *slot: the model slot.  weight, wsum, rmask and fbase are the caller's.
+// columns of the ions; *slot: the model slot.  weight, wsum, rmask and fbase are the caller's.  partitioned: the slot may
+// have no membrane dof on this rank.
 int mon_watch(knpemi_handle* h, const std::string& fn, int sub, int model, uint32_t mask, int v_index, const int32_t* ion_param,
-              KnMonWatch* W, int* slot) {
+              KnMonWatch* W, int* slot, bool partitioned = false) {
   if (sub == 0 && !h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": the ECS (sub-domain 0) has no membrane: watch a model of a cell");
   if (sub < 1 || sub >= h->n_sub || model < 0 || model >= h->n_models[sub])
     return kn_fail(KNPEMI_EINVAL, fn + ": membrane model index out of range");
@@ -797,7 +835,7 @@ int mon_watch(knpemi_handle* h, const std::string& fn, int sub, int model, uint3
   const int count = m.rtc_module ? m.n_monitored : knpemi_monitor_count(m.model_id);
   if (mask == 0) return kn_fail(KNPEMI_EINVAL, fn + ": empty quantity mask");
   if (count < 32 && (mask >> count)) return kn_fail(KNPEMI_EINVAL, fn + ": quantity mask has bits at or beyond the model's count");
-  if (m.nq < 1) return kn_fail(KNPEMI_EINVAL, fn + ": the sub-domain has no membrane dofs");
+  if (m.nq < (partitioned ? 0 : 1)) return kn_fail(KNPEMI_EINVAL, fn + ": the sub-domain has no membrane dofs");
   if (v_index < -1 || v_index >= m.n_states) return kn_fail(KNPEMI_EINVAL, fn + ": v_index out of range");
   *W = KnMonWatch{};
   W->model_id = m.model_id; W->nq = m.nq; W->q0 = h->qoff[sub]; W->v_index = v_index; W->mask = mask;
@@ -831,16 +869,31 @@ extern "C" int knpemi_monitor_bind_source(knpemi_handle* h, int sub, int model, 
   return kn_rtc_monitor_bind(h, m, n_monitored, monitor_source);
 }
 
-extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* spec, const int32_t* ion_param,
-                                  const double* weights, int n_cols, const int32_t* col_spec, int n_pts,
-                                  const int32_t* pt_watch, const int32_t* pt_q, const double* pt_w, int capacity) {
-  const std::string fn = "knpemi_monitor_set";
+namespace {
+// what knpemi_monitor_set_partitioned adds to knpemi_monitor_set
+struct MonPart {
+  const double* wsum_global;      // [n_watch] the weight sums over the ranks
+  KnRankSlots slots;
+};
+
+// knpemi_monitor_set and, with `part`, knpemi_monitor_set_partitioned: a watch may then have no local dof (no workgroup)
+// or local weights that sum to nothing, and a point no local dof (another rank takes it)
+int monitor_set(knpemi_handle* h, const char* who, int n_watch, const int32_t* spec, const int32_t* ion_param,
+                const double* weights, int n_cols, const int32_t* col_spec, int n_pts, const int32_t* pt_watch,
+                const int32_t* pt_q, const double* pt_w, int capacity, const MonPart* part = nullptr) {
+  const std::string fn(who);
   if (!h || !spec || !weights || (n_cols > 0 && !col_spec) || (n_pts > 0 && (!pt_watch || !pt_q || !pt_w)))
     return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
   if (!h->ode_only && !ion_param) return kn_fail(KNPEMI_EINVAL, fn + ": null argument (the ions' parameter columns)");
   if (n_watch < 1 || n_watch > KN_MON_MAXW) return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_MON_MAX_WATCH watches");
   if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
   if (n_cols < 0 || n_pts < 0 || n_pts > (1 << 20)) return kn_fail(KNPEMI_EINVAL, fn + ": bad number of columns or points");
+  if (part) {
+    if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no partition");
+    if (!part->wsum_global) return kn_fail(KNPEMI_EINVAL, fn + ": null argument (the global weight sums)");
+    if (n_cols < 1) return kn_fail(KNPEMI_EINVAL, fn + ": a partitioned record needs a column");
+    if (int rc = slots_check(h, fn, part->slots, (size_t)n_cols)) return rc;
+  }
   New<knpemi_handle::KnMon> N;
   KnMonTab& T = N.host;
   std::vector<size_t> woff(n_watch);
@@ -849,13 +902,15 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
   for (int w = 0; w < n_watch; ++w) {
     int slot = -1;
     if (int rc = mon_watch(h, fn, spec[4 * w], spec[4 * w + 1], (uint32_t)spec[4 * w + 2], spec[4 * w + 3],
-                           h->ode_only ? nullptr : ion_param + (size_t)w * 2 * h->K, &T.w[w], &slot))
+                           h->ode_only ? nullptr : ion_param + (size_t)w * 2 * h->K, &T.w[w], &slot, part != nullptr))
       return rc;
     for (int u = 0; u < w; ++u)
       if (N.slot_of[u] == slot) return kn_fail(KNPEMI_EINVAL, fn + ": watch " + std::to_string(w) + " is listed twice");
     N.slot_of[w] = slot;
-    N.fn[w][0] = h->ode[slot].mon_kernel[0];
-    N.fn[w][1] = h->ode[slot].mon_kernel[1];
+    if (T.w[w].nq > 0) {
+      N.fn[w][0] = h->ode[slot].mon_kernel[0];
+      N.fn[w][1] = h->ode[slot].mon_kernel[1];
+    }
     KnMonWatch& W = T.w[w];
     woff[w] = wo;
     double wsum = 0.0;
@@ -865,7 +920,11 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
       wsum += x;
     }
     wo += (size_t)W.nq;
-    W.wsum = wsum;
+    // (no comparison with the local sum: the caller adds the ranks' sums in another order than this loop, and the two
+    // differ in their last bits in either direction where one rank records a whole cell)
+    if (part && (!(part->wsum_global[w] >= 0.0) || !std::isfinite(part->wsum_global[w])))
+      return kn_fail(KNPEMI_EINVAL, fn + ": the global weight sum of watch " + std::to_string(w) + " is negative or not finite");
+    W.wsum = part ? part->wsum_global[w] : wsum;
     W.fbase = fbase;
     fbase += (long long)popcount((int)(W.mask & 0x7FFFFFFFu)) * W.nq + ((W.mask >> 31) ? W.nq : 0);
     T.bstart[w + 1] = T.bstart[w] + (W.nq + kn_monitor_chunk() - 1) / kn_monitor_chunk();
@@ -879,9 +938,11 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
       if (q >= 0 && !std::isfinite(pt_w[4 * p + j])) return kn_fail(KNPEMI_EINVAL, fn + ": a point's weight is not finite");
       any = any || q >= 0;
     }
-    if (!any) return kn_fail(KNPEMI_EINVAL, fn + ": a point without dofs");
+    if (!any && !part) return kn_fail(KNPEMI_EINVAL, fn + ": a point without dofs");
   }
   std::vector<int4> cols((size_t)n_cols);
+  std::vector<int> col_op((size_t)n_cols, KNPEMI_OBS_SUM);
+  std::vector<double> col_denom((size_t)n_cols, 1.0);
   for (int c = 0; c < n_cols; ++c) {
     const int kind = col_spec[4 * c], w = col_spec[4 * c + 1], qty = col_spec[4 * c + 2], pt = col_spec[4 * c + 3];
     const std::string who = fn + ": column " + std::to_string(c);
@@ -896,6 +957,8 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
       T.w[w].rmask |= 1u << qty;
     }
     cols[c] = make_int4(kind, w, qty, kind == KNPEMI_MON_POINT ? pt : 0);
+    col_op[c] = kind == KNPEMI_MON_MIN ? KNPEMI_OBS_MIN : (kind == KNPEMI_MON_MAX_OP ? KNPEMI_OBS_MAX : KNPEMI_OBS_SUM);
+    if (kind == KNPEMI_MON_AVERAGE) col_denom[c] = T.w[w].wsum;
   }
   T.n_watch = n_watch; T.n_cols = n_cols; T.n_pts = n_pts;
   N.n_watch = n_watch; N.n_blk = T.bstart[n_watch]; N.fields.fld_len = (size_t)fbase;
@@ -911,7 +974,38 @@ extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* 
   if (!rc) rc = kn_alloc(A, 4 * (size_t)n_pts * KN_MON_MAX, &N.pt_val);
   if (!rc) rc = kn_alloc(A, (size_t)N.n_blk * KN_MON_SLOTS, &N.part);
   if (!rc) rc = series_alloc(A, h->stream, capacity, n_cols, &N.ser);
+  if (!rc && part) {
+    if ((rc = kn_upload(A, col_op, &N.col_op)) || (rc = kn_upload(A, col_denom, &N.col_denom))
+        || (rc = slots_attach(h, &N.slots, part->slots, n_cols)))
+      return rc;
+    if (N.n_blk == 0) {      // no record launch ever writes this rank's slots: they hold the operations' identities
+      std::vector<double> id((size_t)n_cols);
+      for (int c = 0; c < n_cols; ++c)
+        id[c] = col_op[c] == KNPEMI_OBS_MIN ? INFINITY : (col_op[c] == KNPEMI_OBS_MAX ? -INFINITY : 0.0);
+      KN_HIP(hipMemcpyAsync(N.slots.xbuf + (size_t)N.slots.rank * n_cols, id.data(), id.size() * sizeof(double),
+                            hipMemcpyHostToDevice, h->stream));
+      KN_HIP(hipStreamSynchronize(h->stream));
+    }
+  }
   return rc ? rc : recorder_install(h, &knpemi_handle::mon, N);
+}
+}  // namespace
+
+extern "C" int knpemi_monitor_set(knpemi_handle* h, int n_watch, const int32_t* spec, const int32_t* ion_param,
+                                  const double* weights, int n_cols, const int32_t* col_spec, int n_pts,
+                                  const int32_t* pt_watch, const int32_t* pt_q, const double* pt_w, int capacity) {
+  return monitor_set(h, "knpemi_monitor_set", n_watch, spec, ion_param, weights, n_cols, col_spec, n_pts, pt_watch, pt_q, pt_w,
+                     capacity);
+}
+
+extern "C" int knpemi_monitor_set_partitioned(knpemi_handle* h, int n_watch, const int32_t* spec, const int32_t* ion_param,
+                                              const double* weights, int n_cols, const int32_t* col_spec, int n_pts,
+                                              const int32_t* pt_watch, const int32_t* pt_q, const double* pt_w, int capacity,
+                                              const double* wsum_global, int rank, int world, void* xbuf_dev,
+                                              knpemi_allreduce_fn allreduce, void* ctx) {
+  const MonPart part{wsum_global, {static_cast<double*>(xbuf_dev), rank, world, allreduce, ctx}};
+  return monitor_set(h, "knpemi_monitor_set_partitioned", n_watch, spec, ion_param, weights, n_cols, col_spec, n_pts, pt_watch,
+                     pt_q, pt_w, capacity, &part);
 }
 
 extern "C" int knpemi_monitor_record(knpemi_handle* h, double t, int fields) {
@@ -922,7 +1016,13 @@ extern "C" int knpemi_monitor_record(knpemi_handle* h, double t, int fields) {
   KN_HIP(hipSetDevice(h->device));
   // the record reads phi_M and the tables, which the ODE sweeps may write on the auxiliary streams
   if (int rc = kn_wait_ode_joins(h)) return rc;
-  return fields_record(X.fields, X.allocs, fields, [&] { return kn_launch_monitor(h, t, fields); });
+  if (int rc = fields_record(X.fields, X.allocs, fields, [&] { return kn_launch_monitor(h, t, fields); })) return rc;
+  if (!X.slots.xbuf) return KNPEMI_OK;
+  // partitioned: this rank's slots are written (without a local dof they hold the identities); sum the exchange buffer over
+  // the ranks, then fold, divide the averages and append
+  if (int rc = slots_sum(h, "knpemi_monitor_record", X.slots, X.ser.n_cols)) return rc;
+  return kn_launch_record_combine(h, "record_combine_kernel (monitors)", X.ser.n_cols, X.ser.capacity, X.slots.world,
+                                  X.slots.rank, X.col_op, X.col_denom, nullptr, X.slots.xbuf, X.ser.ctl, X.ser.rows, true);
 }
 
 extern "C" int knpemi_monitor_read(knpemi_handle* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {

@@ -179,8 +179,12 @@ __device__ __forceinline__ void monitor_body(const OdeDev& D, const KnMonArgs& A
     }
   }
   if (!mon_arrive_last(A.ctl, A.n_blk_total, &last)) return;
-  const bool room = kn_claim_row(A.ctl, A.capacity, &row);
+  // partitioned (A.slot, uniform over the launch): the columns go to this rank's slots, the average undivided, and no row
+  // is claimed -- record_combine_kernel folds the ranks' slots, divides and appends the row
+  double* const slot = A.slot;
+  const bool room = slot ? true : kn_claim_row(A.ctl, A.capacity, &row);
   if (room) {                                           // uniform over the workgroup
+    double* const dst = slot ? slot : A.rows + (size_t)row * T.n_cols;
     for (int c = threadIdx.x; c < T.n_cols; c += MON_THREADS) {
       const int kind = A.cols[4 * c], cw = A.cols[4 * c + 1], cq = A.cols[4 * c + 2], cp = A.cols[4 * c + 3];
       double v = 0.0;
@@ -192,13 +196,13 @@ __device__ __forceinline__ void monitor_body(const OdeDev& D, const KnMonArgs& A
       } else {                                          // _INTEGRAL 1, _AVERAGE 2, _MIN 3, _MAX_OP 4
         const int op = kind == 3 ? 1 : (kind == 4 ? 2 : 0);
         v = mon_fold<MON_FOLD_DEPTH>(A.part, 3 * cq + op, T.bstart[cw], T.bstart[cw + 1], op);
-        if (kind == 2) v = v / T.w[cw].wsum;
+        if (kind == 2 && !slot) v = v / T.w[cw].wsum;
       }
-      A.rows[(size_t)row * T.n_cols + c] = v;
+      dst[c] = v;
     }
   }
   if (threadIdx.x == 0) {
-    kn_commit_row(A.ctl, row, room);
+    if (!slot) kn_commit_row(A.ctl, row, room);
     kn_reset_ticket(A.ctl);
   }
 }

@@ -35,7 +35,10 @@ struct KnMonTab {
 // A record is one launch per run of consecutive watches that share a program -- the library's kernel for the shipped
 // models, the hipRTC program of a plug-in's monitor for the slots bound from it; a table of shipped models is ONE launch.
 // Workgroup blockIdx.x of a launch is workgroup blk0 + blockIdx.x of the record; the workgroup that draws the last of the
-// record's n_blk_total tickets writes the row.
+// record's n_blk_total tickets writes the row.  Partitioned (slot != NULL; knpemi_monitor_set_partitioned): it writes the
+// folded columns -- the average undivided -- into slot[0 .. n_cols) and claims no row: the caller sums the exchange buffer
+// over the ranks and record_combine_kernel (kernels_observe.hip) folds the ranks' slots, divides and appends the row.  A
+// watch may then have nq == 0 (no workgroup; its columns fold to the operation's identity).
 struct KnMonArgs {
   const KnMonTab* tab;
   const int* cols;             // [n_cols][4] {kind, watch, quantity, point}
@@ -47,6 +50,7 @@ struct KnMonArgs {
   unsigned long long* ctl;     // the series buffer's counters; NULL: no series row (knpemi_monitor_eval)
   double* rows;
   double* fld;
+  double* slot;                // partitioned: this rank's n_cols slots of the exchange buffer; NULL: append the row to `rows`
   int capacity, blk0, n_blk_total;
   double t;
 };

@@ -192,6 +192,8 @@ SIGNATURES = {
     "knpemi_exchange_set_partitioned": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, C.c_int, c_u8_p, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "knpemi_maps_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_dbl_p, C.c_int]),
+    "knpemi_maps_set_partitioned": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_dbl_p, c_dbl_p, C.c_int, c_u8_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "knpemi_maps_record": (C.c_int, [C.c_void_p, C.c_double]),
     "knpemi_maps_read": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "knpemi_maps_series_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -204,6 +206,9 @@ SIGNATURES = {
     "knpemi_monitor_compile_source": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]),
     "knpemi_monitor_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_dbl_p, C.c_int, c_int_p, C.c_int, c_int_p,
                                      c_int_p, c_dbl_p, C.c_int]),
+    "knpemi_monitor_set_partitioned": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_dbl_p, C.c_int, c_int_p, C.c_int,
+                                                 c_int_p, c_int_p, c_dbl_p, C.c_int, c_dbl_p, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     "knpemi_monitor_record": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
     "knpemi_monitor_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     "knpemi_monitor_fields": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dbl_p, C.c_size_t]),

@@ -61,7 +61,8 @@ from __future__ import annotations
 import numpy as np
 
 from .fem.function import as_float
-from .recording import CURRENT_BIT, WatchedIons, combine_partials, lib_int, nodal_values as _values  # noqa: F401
+from .recording import (CURRENT_BIT, WatchedIons, combine_partials, item_owners, lib_int,  # noqa: F401
+                        membrane_meshes, nodal_values as _values)
 
 ION_PARTS = ("ecs", "ics", "channel")
 
@@ -162,16 +163,9 @@ class MembraneExchange(WatchedIons):
         return int(self.subdomain_list[tag]["mesh_mem"].cells.shape[0])
 
     def _item_owners(self, halo):
-        own, out, off = halo.vertex_owner("mem"), {}, 0
-        for tag in self.tags[1:]:                  # the device numbers the membrane dofs cell after cell
-            mem = self.subdomain_list[tag].get("mesh_mem")
-            n = 0 if mem is None else int(mem.x.shape[0])
-            if tag in self.watched:
-                out[tag] = (mem, own[off:off + n])
-            off += n
-        if off != own.shape[0]:
-            raise ValueError("exchange: the halo does not number the membrane dofs of these cells")
-        return out
+        mems = membrane_meshes(self.subdomain_list)
+        own = item_owners(mems, halo, "mem", "exchange: the halo does not number the membrane dofs of these cells")
+        return {tag: (mems[tag], own[tag]) for tag in mems if tag in self.watched}
 
     # -- host restatement ----------------------------------------------------------------------------------
     def _geometry(self, tag):

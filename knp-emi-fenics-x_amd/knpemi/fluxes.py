@@ -44,7 +44,8 @@ from __future__ import annotations
 import numpy as np
 
 from .fem.function import as_float
-from .recording import CURRENT_BIT, WatchedIons, combine_partials, lib_int, nodal_values as _values  # noqa: F401
+from .recording import (CURRENT_BIT, WatchedIons, combine_partials, item_owners, lib_int,  # noqa: F401
+                        nodal_values as _values)
 
 PARTS = ("diffusive", "drift")
 
@@ -135,15 +136,8 @@ class IonFluxes(WatchedIons):
         return np.concatenate([np.full(w, key.endswith("max")) for key, w in self.columns()])
 
     def _item_owners(self, halo):
-        own, out, off = halo.vertex_owner("bulk"), {}, 0
-        for tag in self.tags:                      # the device numbers the vertices sub-domain after sub-domain
-            n = int(self.mesh[tag].x.shape[0])
-            if tag in self.watched:
-                out[tag] = (self.mesh[tag], own[off:off + n])
-            off += n
-        if off != own.shape[0]:
-            raise ValueError("fluxes: the halo does not number the vertices of these sub-domains")
-        return out
+        own = item_owners(self.mesh, halo, "bulk", "fluxes: the halo does not number the vertices of these sub-domains")
+        return {tag: (self.mesh[tag], own[tag]) for tag in self.tags if tag in self.watched}
 
     # -- host restatement ----------------------------------------------------------------------------------
     def _geometry(self, tag):

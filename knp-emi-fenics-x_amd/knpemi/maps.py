@@ -42,9 +42,13 @@ A statistic that is not selected keeps its initial value and costs no memory tra
 measures (`fem.probe.integral_weights`) of the items with s (v - thr) >= 0 -- the volume, area or length beyond the
 level -- and `<name>/n`, their number.
 
-Cell-partitioned runs need no communication: ghost values are current after the bulk halo exchange and ghost membrane
-dofs are integrated redundantly with identical bits.  `maps(name, halo=halo)` returns the items this rank owns; the
-union over the ranks is the global map.  A series would sum ghosts too: `step(halo)` refuses a `FieldMaps` with one.
+Cell-partitioned runs.  The per-item maps need no communication: ghost values are current after the bulk halo exchange
+and ghost membrane dofs are integrated redundantly with identical bits.  `maps(name, halo=halo)` returns the items this
+rank owns; the union over the ranks is the global map.  A series would sum ghosts too, so it is recorded with
+`stepper.track(fm, halo=halo)` (`partition`): `measure` uses item weights lumped from the cells (phi_M: membrane facets)
+the rank records -- the lowest owner among a cell's vertices, the rule of `Observables.partition` -- `n` counts the items
+the rank owns, and both columns are summed over the ranks on the device at every record, so every rank holds the global
+row (`n` exactly, `measure` to rounding).  Attached without a halo, `step(halo)` refuses a `FieldMaps` with a series.
 """
 from __future__ import annotations
 
@@ -55,7 +59,8 @@ import numpy as np
 from . import _lib as L
 from .events import conduction_velocity
 from .fem.probe import integral_weights
-from .recording import RowSeries, nodal_values as _values
+from .recording import (RowSeries, agree_across_ranks, gather_objects, item_owners, membrane_meshes,
+                        nodal_values as _values, rank_slots, recorded_items)
 
 STATS = ("peak", "trough", "integral", "threshold")
 STAT_BITS = dict(peak=L.MAPS_PEAK, trough=L.MAPS_TROUGH, integral=L.MAPS_INTEGRAL, threshold=L.MAPS_THRESHOLD)
@@ -171,15 +176,83 @@ class FieldMaps(RowSeries):
         wt = [w.w for w in ws if w.series]
         return spec.reshape(-1, 4), thr, np.ascontiguousarray(np.concatenate(wt)) if wt else None
 
-    def _attach(self, dp, capacity):
+    def _attach(self, dp, capacity, halo=None, every=1):
+        """knpemi_maps_set on the device problem dp, or with a halo (and a series watch) `partition` and
+        knpemi_maps_set_partitioned (`rank_slots`).  Returns the objects the handle refers to (keep them alive while it
+        records)."""
         if self._dev is not None:
             raise RuntimeError("these maps are attached to a device problem already")
         if not self.watches:
             raise ValueError("nothing is watched")
         spec, thr, wt = self.table(dp.sub_index)
-        L.check(dp.lib.knpemi_maps_set(dp.h, spec.shape[0], L.iptr(spec.ravel()), L.dptr(thr),
-                                       L.dptr(wt) if wt is not None else None, int(capacity)))
+        keep = None
+        if halo is None:
+            L.check(dp.lib.knpemi_maps_set(dp.h, spec.shape[0], L.iptr(spec.ravel()), L.dptr(thr),
+                                           L.dptr(wt) if wt is not None else None, int(capacity)))
+        else:
+            tab = self.partition(halo, None, every, capacity)
+            names = [n for n, w in self.watches.items() if w.series]
+            wt = np.ascontiguousarray(np.concatenate([tab["weights"][n] for n in names]), np.float64)
+            own = np.ascontiguousarray(np.concatenate([tab["owned"][n] for n in names]).astype(np.uint8))
+            wt, own = (wt, own) if wt.size else (np.zeros(1), np.zeros(1, np.uint8))      # a rank without items
+            slots, keep = rank_slots(dp, halo, tab["world"], self.n_cols)
+            L.check(dp.lib.knpemi_maps_set_partitioned(dp.h, spec.shape[0], L.iptr(spec.ravel()), L.dptr(thr), L.dptr(wt),
+                                                       int(capacity), own.ctypes.data_as(L.c_u8_p), tab["rank"],
+                                                       tab["world"], *slots))
         self._dev = (dp.lib, dp.h)
+        return keep
+
+    # -- cell-partitioned runs: the series ---------------------------------------------------------------
+    def partition(self, halo, gather=None, every=1, capacity=1024):
+        """The series tables of this rank of a cell-partitioned run, set in `self._ptab`: {"rank", "world", "weights":
+        {name: item weights lumped from the cells (phi_M: membrane facets) this rank records}, "owned": {name: bool per
+        item}} for every series watch.  A cell is recorded by the lowest owner among its vertices (the rule of
+        `Observables.partition`), so the ranks' measures add up to the global one; n counts the items a rank owns.  halo:
+        the rank's `knpemi.fem.distributed.Halo` with its plans built; gather(obj) -> [obj of every rank] (default:
+        `recording.gather_objects`).  Collective: every rank calls it once with the same watches, every and capacity, or
+        every rank raises ValueError."""
+        if not self.has_series:
+            raise ValueError("no watch has a series: the maps of a partitioned run need no partition")
+        rank = int(halo.rank)
+        message = "maps: the halo does not number the items of these sub-domains"
+        series = [w for w in self.watches.values() if w.series]
+        bulk = item_owners({t: sd["mesh_sub"] for t, sd in self.subdomain_list.items()}, halo, "bulk", message) \
+            if any(w.quantity != "phi_M" for w in series) else {}
+        mem = item_owners(membrane_meshes(self.subdomain_list), halo, "mem", message) \
+            if any(w.quantity == "phi_M" for w in series) else {}
+        weights, owned = {}, {}
+        for name, w in self.watches.items():
+            if not w.series:
+                continue
+            owner = (mem if w.quantity == "phi_M" else bulk)[w.tag]
+            mesh = self._mesh(w)
+            weights[name] = integral_weights(mesh, cell_mask=recorded_items(mesh, owner, rank)) if w.n else np.zeros(0)
+            owned[name] = owner == rank
+        mine = dict(watches=[(w.name, w.quantity, w.tag, w.ion, w.thr, w.sgn, w.stats, w.series) for w in self.watches.values()],
+                    every=int(every), capacity=int(capacity))
+        allr = (gather or gather_objects)(mine)
+        agree_across_ranks(allr, ("watches", "every", "capacity"), "field maps",
+                           "every rank must define the same watches in the same order and pass the same every and capacity")
+        self._ptab = dict(rank=rank, world=len(allr), weights=weights, owned=owned)
+        return self._ptab
+
+    def max_columns(self):
+        """Per column of the series row: every one is a sum (`recording.combine_partials`)."""
+        return np.zeros(self.n_cols, bool)
+
+    def series_partial_host(self, phi, c, phi_M_prev):
+        """This rank's slot row of the series of a partitioned run (after `partition`) from host data, as the record
+        kernel writes it: per series watch the rank's weights summed over the items beyond the level, and the number of
+        such items the rank owns."""
+        row = []
+        for name, w in self.watches.items():
+            if not w.series:
+                continue
+            v = self._sample(w, phi, c, phi_M_prev)
+            with np.errstate(invalid="ignore"):
+                beyond = np.isfinite(v) & (w.sgn * (v - w.thr) >= 0.0)
+            row += [float(np.sum(self._ptab["weights"][name][beyond])), float((beyond & self._ptab["owned"][name]).sum())]
+        return np.array(row)
 
     def _detach(self):
         self._dev = None

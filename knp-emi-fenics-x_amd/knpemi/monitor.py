@@ -29,6 +29,19 @@ Columns.  A point column is sum_j w_j v(q_j) over the dofs of the membrane facet
 (`fem.probe`).  Reductions run over the dofs q of the model's membrane with weight w_q > 0, w_q the integral of the dof's
 hat function over the facets that carry the model: "integral" = sum_q w_q v_q, "average" = integral / sum_q w_q, "min",
 "max".  Units are the model's own.  A non-finite value is kept and makes the columns it enters non-finite.
+
+Cell-partitioned runs (`MembraneMonitor(..., partitioned=True)`, `stepper.monitor(mon, halo=halo)`).  A rank's local mesh
+holds its cells and a ghost layer, whose membrane dofs are integrated redundantly with identical bits.  `partition` gives
+every membrane facet one recorder -- the lowest owner among its vertices, the rule of `Observables.partition` -- and the
+weights carry it: on a rank w_q is the integral of the hat function over the facets that carry the model AND that the rank
+records, so the kernel's rule "the dofs with w_q > 0" needs no ownership test, and a rank's weights may all be zero.  Every
+rank sums w_q v_q and takes minimum and maximum over its dofs with w_q > 0; the partial rows are exchanged on the device and
+folded in rank order (`recording.combine_partials` restates it): integrals and averages summed -- the average then divided
+by the global sum of weights, the ranks' sums added in rank order -- minima and maxima folded keeping a NaN.  Every facet
+that carries the model is recorded by exactly one rank, so each of its dofs has w_q > 0 on some rank, and a dof two ranks
+see has the same bits on both: the fold of the extrema is the global extremum bit for bit.  A point goes to the lowest
+rank whose recorded facets hold it (its column is summed: the other ranks contribute 0).  `values(tag, halo=halo)` returns
+the dofs the rank owns.
 """
 from __future__ import annotations
 
@@ -36,7 +49,8 @@ import numpy as np
 
 from . import _lib as L
 from .fem.probe import Locator, integral_weights
-from .recording import RowSeries, lib_int, nodal_values as _values
+from .recording import (FOLD_MAX, FOLD_MIN, FOLD_SUM, RowSeries, agree_across_ranks, gather_objects, item_owners, lib_int,
+                        membrane_meshes, nodal_values as _values, rank_slots, recorded_items)
 
 OPS = {"integral": L.MON_INTEGRAL, "average": L.MON_AVERAGE, "min": L.MON_MIN, "max": L.MON_MAX_OP}
 _MODEL_IDS = {"hh_si": L.MODEL_HH_SI, "hh_mv": L.MODEL_HH_MV, "glial": L.MODEL_GLIAL}
@@ -124,12 +138,17 @@ def evaluate_host(model_id, t, states, params):
 
 
 class MembraneMonitor(RowSeries):
-    def __init__(self, subdomain_list, ion_list, ft=None):
+    def __init__(self, subdomain_list, ion_list, ft=None, partitioned=False):
         """subdomain_list: the problem's sub-domain dictionary (the ECS, tag 0, first; every cell carries "mesh_sub",
         "mesh_mem" and its "mem_models"); ion_list: the ions in the problem's order, the eliminated one last.  ft: the
         facet tags of the parent mesh, needed where a cell has several membrane models or facets that belong to none: a
         facet goes to the first model whose `ode.tag` is its tag (as the device problem decides).  Without it every
-        facet of a cell belongs to the cell's first model."""
+        facet of a cell belongs to the cell's first model.  partitioned: the sub-domain list is that of one rank of a cell
+        partition: a point is located by `partition` (this rank may not hold it), and a reduction may run over a model
+        no local facet carries."""
+        self.partitioned = bool(partitioned)
+        self._point_x = []         # the coordinates of the points, as given
+        self._ptab = None          # the table of `partition`
         self.tags = list(subdomain_list)
         if self.tags[0] != 0:
             raise ValueError("the first sub-domain must be the ECS with tag 0")
@@ -214,15 +233,27 @@ class MembraneMonitor(RowSeries):
         self._defining()
         key = self._watched_key(tag, model)
         self._name_free(name)
-        _, _, fmask = self._geometry(*key)
-        mem = self.subdomain_list[tag]["mesh_mem"]
-        q, w = Locator(mem, f"the membrane of model {model} of cell {tag}", cell_mask=fmask).weights(x)
-        if len(q) > 4:
-            raise ValueError("a membrane facet has at most 4 vertices")
+        if self.partitioned:       # located by `partition`
+            q, w = np.zeros(0, np.int64), np.zeros(0)
+        else:
+            q, w = self._locate(key, x)
+        self._point_x.append(np.array(x, np.float64))
         names = self.names(*key)
         self._points.append((name, key, np.asarray(q, np.int64), np.asarray(w, np.float64)))
         for i in self.watched[key]:
             self._cols.append((f"{name}/{names[i]}", L.MON_POINT, key, i, len(self._points) - 1))
+
+    def _locate(self, key, x, recorded=None):
+        """(dofs, weights) of the membrane point x in the facets that carry the model of `key` (and, recorded, that this
+        rank records); ValueError when none holds it."""
+        tag, model = key
+        fmask = self._geometry(*key)[2]
+        mem = self.subdomain_list[tag]["mesh_mem"]
+        q, w = Locator(mem, f"the membrane of model {model} of cell {tag}",
+                       cell_mask=fmask if recorded is None else fmask & recorded).weights(x)
+        if len(q) > 4:
+            raise ValueError("a membrane facet has at most 4 vertices")
+        return q, w
 
     def reduce(self, name, tag, op="average", model=0, quantities=None):
         """Columns "<name>/<quantity>": `op` ("integral", "average", "min", "max") over the membrane of slot (tag, model)
@@ -232,7 +263,7 @@ class MembraneMonitor(RowSeries):
             raise ValueError(f"unknown op {op!r}: one of {sorted(OPS)}")
         key = self._watched_key(tag, model)
         self._name_free(name)
-        if not self.weights(*key).sum() > 0.0:
+        if not self.partitioned and not self.weights(*key).sum() > 0.0:      # (partitioned: `partition` checks the global sum)
             raise ValueError(f"no membrane facet carries model {model} of cell {tag}")
         names = self.names(*key)
         for i in self._indices(key, quantities, among=self.watched[key]):
@@ -264,9 +295,112 @@ class MembraneMonitor(RowSeries):
             self._geo[key] = (q2e, q2i, fmodel == int(model))
         return self._geo[key]
 
-    def weights(self, tag, model=0):
-        """w_q: the integral of every membrane dof's hat function over the facets that carry the model."""
+    def weights(self, tag, model=0, halo=None):
+        """w_q: the integral of every membrane dof's hat function over the facets that carry the model; halo: over those
+        of them this rank of the partition records (after `partition` with that halo)."""
+        if halo is not None:
+            return self._partitioned(halo, "weights")["weights"][(tag, int(model))].copy()
         return integral_weights(self.subdomain_list[tag]["mesh_mem"], cell_mask=self._geometry(tag, model)[2])
+
+    # -- cell-partitioned runs ------------------------------------------------------------------------------
+    def _definition(self):
+        """What every rank of a partition must agree on."""
+        return dict(watches=[(key, self.mask(*key)) for key in self.watched],
+                    columns=[(ckey, kind, key, i, p) for ckey, kind, key, i, p in self._cols],
+                    points=[(name, key, x.tolist()) for (name, key, _, _), x in zip(self._points, self._point_x)])
+
+    def partition(self, halo, gather=None, every=1, capacity=1024):
+        """The table of this rank of a cell-partitioned run (see the module docstring), set in `self._ptab`: {"rank",
+        "world", "recorded": {tag: bool per local membrane facet}, "owner": {tag: owner rank per local membrane dof},
+        "weights": {(tag, model): the rank's w_q}, "wsum": {(tag, model): the global sum of weights}, "taker": [rank per
+        point]}; the points this rank takes get their dofs and weights, the others none.  halo: the rank's
+        `knpemi.fem.distributed.Halo` with its plans built; gather(obj) -> [obj of every rank] (default:
+        `recording.gather_objects`).  Collective: every rank calls it once with the same watches, points, reductions, every
+        and capacity, or every rank raises ValueError; so does a point no rank holds and a reduction over a model no facet
+        of any rank carries."""
+        if not self.partitioned:
+            raise ValueError("partition: construct the monitor with partitioned=True")
+        if not self.watched:
+            raise ValueError("nothing is watched")
+        rank = int(halo.rank)
+        owner = item_owners(membrane_meshes(self.subdomain_list), halo, "mem",
+                            "membrane monitors: the halo does not number the membrane dofs of these cells")
+        recorded = {tag: recorded_items(self.subdomain_list[tag]["mesh_mem"], owner[tag], rank) for tag in self.cells}
+        weights = {}
+        for key in self.watched:
+            mem = self.subdomain_list[key[0]]["mesh_mem"]
+            weights[key] = integral_weights(mem, cell_mask=self._geometry(*key)[2] & recorded[key[0]]) \
+                if mem.num_vertices else np.zeros(0)
+        found = []
+        for (name, key, _, _), x in zip(self._points, self._point_x):
+            try:
+                found.append(self._locate(key, x, recorded[key[0]]))
+            except ValueError:
+                found.append(None)
+        mine = dict(self._definition(), every=int(every), capacity=int(capacity), found=[f is not None for f in found],
+                    share=[float(weights[key].sum()) for key in self.watched])
+        allr = (gather or gather_objects)(mine)
+        world = len(allr)
+        agree_across_ranks(allr, ("watches", "points", "columns", "every", "capacity"), "membrane monitors",
+                           "every rank must define the same watches, points and reductions in the same order and pass the "
+                           "same every and capacity")
+        taker = []
+        for p, (name, key, _, _) in enumerate(self._points):
+            ranks = [r for r in range(world) if allr[r]["found"][p]]
+            if not ranks:
+                raise ValueError(f"point {self._point_x[p].tolist()} is not on the membrane of model {key[1]} of cell "
+                                 f"{key[0]} on any rank")
+            taker.append(ranks[0])
+        wsum = {}
+        for j, key in enumerate(self.watched):
+            tot = allr[0]["share"][j]
+            for r in range(1, world):                   # rank order: the same bits on every rank
+                tot += allr[r]["share"][j]
+            wsum[key] = tot
+        for ckey, kind, key, _, _ in self._cols:
+            if kind != L.MON_POINT and not wsum[key] > 0.0:
+                raise ValueError(f"no membrane facet of any rank carries model {key[1]} of cell {key[0]} ({ckey})")
+        for p, (name, key, _, _) in enumerate(self._points):
+            q, w = found[p] if taker[p] == rank else (np.zeros(0, np.int64), np.zeros(0))
+            self._points[p] = (name, key, np.asarray(q, np.int64), np.asarray(w, np.float64))
+        self._ptab = dict(rank=rank, world=world, recorded=recorded, owner=owner, weights=weights, wsum=wsum, taker=taker)
+        return self._ptab
+
+    def _partitioned(self, halo, what):
+        if self._ptab is None:
+            raise RuntimeError(f"{what}(halo=...): the monitor is not partitioned (attach with halo=, or call partition)")
+        if int(halo.rank) != self._ptab["rank"]:
+            raise ValueError(f"{what}(halo=...): not the halo of this monitor's partition")
+        return self._ptab
+
+    def column_folds(self):
+        """(FOLD_* per column, divisor per column) of `recording.combine_partials`: how the device folds the ranks' slots."""
+        how = [FOLD_MIN if kind == L.MON_MIN else (FOLD_MAX if kind == L.MON_MAX_OP else FOLD_SUM) for _, kind, *_ in self._cols]
+        denom = [self._ptab["wsum"][key] if kind == L.MON_AVERAGE else 1.0 for _, kind, key, _, _ in self._cols]
+        return np.array(how), np.array(denom, np.float64)
+
+    def evaluate_partial_host(self, t, state=None):
+        """This rank's slot row of a partitioned run (after `partition`) with numpy, as the record kernel writes it: a
+        point it takes, else 0; w_q v_q summed over its dofs with w_q > 0 (the average undivided), their minimum and
+        maximum, the operation's identity without such a dof.  state: as `compute_host`."""
+        if self._ptab is None:
+            raise RuntimeError("evaluate_partial_host: call partition first")
+        values = self._values_host(t, state or {})
+        row = np.empty(len(self._cols))
+        for c, (ckey, kind, key, i, p) in enumerate(self._cols):
+            v = values[key][self.names(*key)[i]]
+            if kind == L.MON_POINT:
+                row[c] = self._point_value(p, v)
+                continue
+            w = self._ptab["weights"][key]
+            on = w > 0.0
+            if kind == L.MON_MIN:
+                row[c] = np.min(v[on]) if on.any() else np.inf
+            elif kind == L.MON_MAX_OP:
+                row[c] = np.max(v[on]) if on.any() else -np.inf
+            else:
+                row[c] = np.sum(w[on] * v[on]) if on.any() else 0.0
+        return row
 
     def n_dofs(self, tag):
         return int(self.subdomain_list[tag]["mesh_mem"].x.shape[0])
@@ -278,23 +412,12 @@ class MembraneMonitor(RowSeries):
         "phi_M": {tag: the membrane potential}, "tables": {(tag, model): (states, parameters)}}; `Function`s or arrays;
         what is missing is taken from the host objects of the sub-domain list ("tables": the models' host tables).  The
         rule of the module docstring: traces into the <ion>_e / <ion>_i columns of a copy of the table, V = phi_M."""
-        state = state or {}
-        values, row = {}, {}
-        for key, idx in self.watched.items():
-            tag, model = key
-            st, pa = self.rows_host(tag, model, state)
-            v = self._evaluate_host(tag, model, t, st, pa)
-            names = self.names(tag, model)
-            values[key] = {names[i]: v[i] for i in idx}
+        values, row = self._values_host(t, state or {}), {}
         wcache = {}
         for ckey, kind, key, i, p in self._cols:
             v = values[key][self.names(*key)[i]]
             if kind == L.MON_POINT:
-                _, _, q, w = self._points[p]
-                acc = 0.0
-                for qq, ww in zip(q, w):
-                    acc = acc + ww * v[qq]
-                row[ckey] = float(acc)
+                row[ckey] = self._point_value(p, v)
                 continue
             if key not in wcache:
                 wcache[key] = self.weights(*key)
@@ -308,6 +431,25 @@ class MembraneMonitor(RowSeries):
                 s = float(np.sum(w[on] * v[on]))
                 row[ckey] = s / float(np.sum(w)) if kind == L.MON_AVERAGE else s
         return values, row
+
+    def _values_host(self, t, state):
+        """{(tag, model): {name: (n_q,)}} of every watched quantity with numpy."""
+        values = {}
+        for key, idx in self.watched.items():
+            tag, model = key
+            st, pa = self.rows_host(tag, model, state)
+            v = self._evaluate_host(tag, model, t, st, pa)
+            names = self.names(tag, model)
+            values[key] = {names[i]: v[i] for i in idx}
+        return values
+
+    def _point_value(self, p, v):
+        """sum_j w_j v(q_j) of point p in the order of the facet's dofs (0 for a point another rank takes)."""
+        _, _, q, w = self._points[p]
+        acc = 0.0
+        for qq, ww in zip(q, w):
+            acc = acc + ww * v[qq]
+        return float(acc)
 
     def _evaluate_host(self, tag, model, t, st, pa):
         """(quantities, dofs) on the host: the numpy restatement of a shipped model, the plug-in's own Python `monitor`
@@ -354,12 +496,17 @@ class MembraneMonitor(RowSeries):
     def mask(self, tag, model=0):
         return sum(1 << i for i in self.watched[(tag, int(model))])
 
-    def _attach(self, dp, capacity):
-        """knpemi_monitor_set on the device problem dp."""
+    def _attach(self, dp, capacity, halo=None, every=1):
+        """knpemi_monitor_set on the device problem dp, or with a halo `partition` and knpemi_monitor_set_partitioned
+        (`rank_slots`).  Returns the objects the handle refers to (keep them alive while it records)."""
         if self._dev is not None:
             raise RuntimeError("this monitor is attached to a device problem already")
         if not self.watched:
             raise ValueError("nothing is watched")
+        if halo is not None:
+            if not self._cols:
+                raise ValueError("a partitioned monitor records a series: define a point or a reduction")
+            self.partition(halo, None, every, capacity)
         keys = list(self.watched)
         spec, ionp, wts = [], [], []
         for tag, model in keys:
@@ -369,7 +516,7 @@ class MembraneMonitor(RowSeries):
             spec += [dp.sub_index[tag], model, self.mask(tag, model), int(mm.V_index)]
             for name in self.ion_names:
                 ionp += [mm.ode.parameter_indices(f"{name}_e"), mm.ode.parameter_indices(f"{name}_i")]
-            wts.append(self.weights(tag, model))
+            wts.append(self.weights(tag, model, halo))
         cols = np.array([[kind, keys.index(key), i, p] for _, kind, key, i, p in self._cols] or [[0, 0, 0, 0]], np.int32)
         n_pts = len(self._points)
         pt_watch = np.array([keys.index(key) for _, key, _, _ in self._points] or [0], np.int32)
@@ -379,14 +526,25 @@ class MembraneMonitor(RowSeries):
             pt_q[p, :len(q)], pt_w[p, :len(q)] = q, w
         spec, ionp = np.array(spec, np.int32), np.array(ionp, np.int32)
         wts = np.ascontiguousarray(np.concatenate(wts), np.float64)
-        L.check(dp.lib.knpemi_monitor_set(dp.h, len(keys), L.iptr(spec), L.iptr(ionp), L.dptr(wts), len(self._cols),
-                                          L.iptr(cols), n_pts, L.iptr(pt_watch), L.iptr(pt_q), L.dptr(pt_w),
-                                          int(capacity)))
+        wts = wts if wts.size else np.zeros(1)                # a rank without a dof still passes an array
+        args = (dp.h, len(keys), L.iptr(spec), L.iptr(ionp), L.dptr(wts), len(self._cols), L.iptr(cols), n_pts,
+                L.iptr(pt_watch), L.iptr(pt_q), L.dptr(pt_w), int(capacity))
+        keep = None
+        if halo is None:
+            L.check(dp.lib.knpemi_monitor_set(*args))
+        else:
+            wsum = np.array([self._ptab["wsum"][key] for key in keys], np.float64)
+            world = self._ptab["world"]
+            slots, keep = rank_slots(dp, halo, world, len(self._cols))
+            L.check(dp.lib.knpemi_monitor_set_partitioned(*args, L.dptr(wsum), self._ptab["rank"], world, *slots))
         self._dev = (dp.lib, dp.h)
+        return keep
 
-    def values(self, tag, model=0):
+    def values(self, tag, model=0, halo=None):
         """{name: (n_q,)}: the watched quantities of slot (tag, model) per membrane dof, as the latest device record
-        taken with fields=True wrote them (one synchronisation)."""
+        taken with fields=True wrote them (one synchronisation).  halo: on a cell-partitioned problem only the dofs this
+        rank owns (`Halo.vertex_owner("mem")`), with "dofs" (their local indices) and "locations" (their coordinates);
+        the union over the ranks is the single-rank array."""
         key = self._watched_key(tag, model)
         if self._dev is None:
             raise RuntimeError("values(): not attached to a device problem (DeviceStepper.monitor); compute_host "
@@ -396,6 +554,11 @@ class MembraneMonitor(RowSeries):
         out = {}
         for i in self.watched[key]:
             buf = np.empty(self.n_dofs(tag), np.float64)
-            L.check(lib.knpemi_monitor_fields(h, w, i, L.dptr(buf), buf.size))
+            L.check(lib.knpemi_monitor_fields(h, w, i, L.dptr(buf if buf.size else np.zeros(1)), buf.size))
             out[names[i]] = buf
+        if halo is not None:
+            mine = np.flatnonzero(self._partitioned(halo, "values")["owner"][tag] == int(halo.rank))
+            out = {k: v[mine] for k, v in out.items()}
+            out["dofs"] = mine
+            out["locations"] = np.array(self.subdomain_list[tag]["mesh_mem"].x, np.float64)[mine]
         return out

@@ -38,7 +38,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .recording import RowSeries, agree_across_ranks, gather_objects, rank_slots
+from .recording import RowSeries, agree_across_ranks, gather_objects, item_owners, rank_slots, recorded_items
 from .fem.probe import Locator, integral_weights, membrane_weights, point_weights
 
 OPS = ("integral", "nodal_mean", "average", "min", "max")
@@ -204,22 +204,14 @@ class Observables(RowSeries):
         if not self.items:
             raise ValueError("no observables defined")
         rank = int(halo.rank)
-        own_b, own_m = halo.vertex_owner("bulk"), halo.vertex_owner("mem")
-        owner, rec, off, qoff = {}, {}, 0, 0
-        for tag, sd in self.subdomain_list.items():
-            m = sd["mesh_sub"]
-            owner[(False, tag)] = own_b[off:off + m.num_vertices]
-            off += m.num_vertices
-            if tag > 0:
-                g = sd["mesh_mem"]
-                owner[(True, tag)] = own_m[qoff:qoff + g.num_vertices]
-                qoff += g.num_vertices
-        if off != own_b.shape[0] or qoff != own_m.shape[0]:
-            raise ValueError("observables: the halo does not number the vertices of these sub-domains")
-        for key, ow in owner.items():
-            mesh = self.subdomain_list[key[1]]["mesh_mem" if key[0] else "mesh_sub"]
-            # the recorder of a cell (membrane facet): the lowest owner among its vertices
-            rec[key] = (ow[mesh.cells].min(axis=1) == rank) if mesh.num_cells else np.zeros(0, bool)
+        message = "observables: the halo does not number the vertices of these sub-domains"
+        subs = self.subdomain_list
+        owner = {(False, tag): ow for tag, ow in
+                 item_owners({tag: sd["mesh_sub"] for tag, sd in subs.items()}, halo, "bulk", message).items()}
+        owner.update({(True, tag): ow for tag, ow in
+                      item_owners({tag: sd["mesh_mem"] for tag, sd in subs.items() if tag > 0}, halo, "mem", message).items()})
+        # the recorder of a cell (membrane facet): the lowest owner among its vertices
+        rec = {key: recorded_items(subs[key[1]]["mesh_mem" if key[0] else "mesh_sub"], ow, rank) for key, ow in owner.items()}
         # points: this rank's weights in the cells it records, or None
         found = []
         for membrane, tag, x in self._points:

@@ -9,6 +9,10 @@ per watch.  The record kernel writes the per-item fields of every local item and
 sums and maxima; the ranks' partial rows are summed on the device slot by slot (an exact all-gather) and folded in rank
 order, sums summed and maxima maximised from 0 (`combine_partials`), so every rank appends the same row.
 
+`MembraneMonitor` and the series of `FieldMaps` follow the same rule through their weights (`item_owners`,
+`recorded_items`): a rank integrates its dof (item) weights over the facets (cells) it records, so its partial sums need no
+mask; `combine_partials` folds their rows too, with the recorder's own `column_folds()`.
+
 The drain rule: rows collect in a device buffer of `capacity` rows; the host keeps the time of every row it has
 enqueued and moves the buffer into the series (one synchronisation) whenever it holds `capacity` of them and when
 `series()` is called.  The device must then hold exactly the rows enqueued: a different count, or a row dropped for want
@@ -168,10 +172,7 @@ class WatchedIons(RowSeries):
         rank = int(halo.rank)
         recorded = {}
         for tag, (mesh, ow) in self._item_owners(halo).items():
-            if mesh is None or mesh.cells.shape[0] == 0:
-                recorded[tag] = np.zeros(0, bool)
-            else:
-                recorded[tag] = ow[np.asarray(mesh.cells)].min(axis=1) == rank
+            recorded[tag] = recorded_items(mesh, ow, rank)
         mine = dict(watches=[(t, self.mask(t)) for t in self.watched], every=int(every), capacity=int(capacity))
         allr = (gather or gather_objects)(mine)
         agree_across_ranks(allr, ("watches", "every", "capacity"), f"{self._NAME} recorders",
@@ -234,15 +235,60 @@ class WatchedIons(RowSeries):
         return get
 
 
+def item_owners(meshes, halo, kind, message):
+    """{tag: owner rank of every vertex of meshes[tag]} on this rank of a cell partition, read off the halo's plans
+    (`Halo.vertex_owner(kind)`) without communication.  meshes: {tag: mesh or None} in the device's numbering -- kind
+    "bulk": the sub-meshes of the sub-domains in their order; "mem": the membrane meshes of the cells in theirs.
+    ValueError(message) when the halo numbers another set of vertices."""
+    own, out, off = np.asarray(halo.vertex_owner(kind)), {}, 0
+    for tag, mesh in meshes.items():
+        n = 0 if mesh is None else int(mesh.x.shape[0])
+        out[tag] = own[off:off + n]
+        off += n
+    if off != own.shape[0]:
+        raise ValueError(message)
+    return out
+
+
+def membrane_meshes(subdomain_list):
+    """{tag: membrane mesh or None} of the cells (every sub-domain but the first, the ECS) in their order."""
+    return {tag: subdomain_list[tag].get("mesh_mem") for tag in list(subdomain_list)[1:]}
+
+
+def recorded_items(mesh, owner, rank):
+    """One bool per cell (membrane facet) of `mesh`: this rank records it -- the lowest owner among its vertices."""
+    if mesh is None or np.asarray(mesh.cells).shape[0] == 0:
+        return np.zeros(0, bool)
+    return owner[np.asarray(mesh.cells)].min(axis=1) == rank
+
+
+# how record_combine_kernel folds a column over the ranks: a sum from 0, a maximum from 0 (the fluxes' norms), or the
+# monitors' minimum from +inf and maximum from -inf
+FOLD_SUM, FOLD_MAX0, FOLD_MIN, FOLD_MAX = 0, 1, 2, 3
+
+
 def combine_partials(rec, rows_by_rank):
-    """The row of a partitioned run from the ranks' partial rows (`compute_host(recorded=...)` through `row_vector`, one
-    per rank in rank order), folded as record_combine_kernel does: from 0 in rank order, `rec.max_columns()` by maximum,
-    the other columns by sum."""
+    """The row of a partitioned run from the ranks' partial rows (one per rank in rank order: `compute_host(recorded=...)`
+    through `row_vector`, `MembraneMonitor.evaluate_partial_host`, `FieldMaps.series_partial_host`), folded as
+    record_combine_kernel does, in rank order.  A recorder with `column_folds()` -> (FOLD_* per column, divisors or None)
+    says how; without it `rec.max_columns()` are maxima from 0 and the other columns sums.  Minimum and maximum keep a NaN
+    of either side."""
     rows = np.asarray(rows_by_rank, np.float64)
-    is_max = rec.max_columns()
-    out = np.zeros(rows.shape[1])
-    for r in range(rows.shape[0]):
-        out = np.where(is_max, np.maximum(out, rows[r]), out + rows[r])
+    folds = getattr(rec, "column_folds", None)
+    if folds is None:
+        how, denom = np.where(rec.max_columns(), FOLD_MAX0, FOLD_SUM), None
+    else:
+        how, denom = folds()
+        how = np.asarray(how)
+    out = np.where(how == FOLD_MIN, np.inf, np.where(how == FOLD_MAX, -np.inf, 0.0))
+    with np.errstate(invalid="ignore"):
+        for r in range(rows.shape[0]):
+            x = rows[r]
+            lo = np.where((out < x) | (out != out), out, x)
+            hi = np.where((out > x) | (out != out), out, x)
+            out = np.where(how == FOLD_SUM, out + x, np.where(how == FOLD_MIN, lo, hi))
+        if denom is not None:
+            out = np.where(how == FOLD_SUM, out / np.asarray(denom, np.float64), out)
     return out
 
 

@@ -278,26 +278,34 @@ class DeviceStepper:
         ex._dt, ex._every = self.dt, int(every)
 
     # -- field maps -----------------------------------------------------------------------------------
-    def track(self, fm, every=1, capacity=1024, t0=0.0):
+    def track(self, fm, every=1, capacity=1024, t0=0.0, halo=None):
         """Record the field maps `fm` (knpemi.maps.FieldMaps) on the device after every `every`-th step, at time
         t0 + k dt for step k: one launch over the items of every watched space on the main stream, behind the end-of-step
         update and the other recorders, nothing synchronised; `fm.maps(name)` reads the maps back.  With a series watch
         the launch also appends a row to a device buffer of `capacity` rows, drained into `fm` as the other series are
         (whenever it holds `capacity` rows, and when `fm.series()` is called); without one there is no buffer.
         Works unchanged on a cell-partitioned problem (`step(halo)`) without a series watch: the kernel needs no halo,
-        every rank holds the maps of its local items, and `fm.maps(name, halo=halo)` selects the owned ones.  With a
-        series watch partitioned steps are refused: a rank's sums would include its ghost items."""
+        every rank holds the maps of its local items, and `fm.maps(name, halo=halo)` selects the owned ones.
+
+        halo: this rank's attached halo on a cell-partitioned problem, for maps with a series watch (collective: every rank
+        calls track with the same watches, every and capacity).  Every rank then records the global series row -- the
+        measure from the cells (facets) one rank records, n from the items one rank owns, the partial rows summed over the
+        ranks on the device at each record (FieldMaps.partition) -- and `step(halo)` records with the same halo.
+        Without it, partitioned steps are refused with a series watch: a rank's sums would include its ghost items."""
         lib, dp = self.lib, self.dp
+        series = fm.has_series
+        if halo is not None and not series:
+            raise ValueError("track(halo=...): no watch has a series; maps without one need no halo")
 
         def set_up():
-            fm._attach(dp, capacity)
+            keep = fm._attach(dp, capacity, halo, every)
             fm.reset_host()
+            return keep
 
         def rewind():
             L.check(lib.knpemi_maps_reset(dp.h))
             fm.reset_host()
-        series = fm.has_series
-        self._attach("track", fm, "field maps", every, capacity, t0, set_up=set_up, rewind=rewind,
+        self._attach("track", fm, "field maps", every, capacity, t0, set_up=set_up, rewind=rewind, halo=halo,
                      busy="this stepper records field maps already",
                      attached="these maps are attached to a stepper already",
                      record=lambda t, f: lib.knpemi_maps_record(dp.h, t),
@@ -307,19 +315,25 @@ class DeviceStepper:
                                        if series else None)
 
     # -- membrane monitors ------------------------------------------------------------------------------
-    def monitor(self, mon, every=1, capacity=1024, t0=0.0, fields=False):
+    def monitor(self, mon, every=1, capacity=1024, t0=0.0, fields=False, halo=None):
         """Record the membrane monitors `mon` (knpemi.monitor.MembraneMonitor) on the device after every `every`-th
         step, at time t0 + k dt for step k: one launch over the membrane dofs of the watched model slots on the main
         stream, behind the end-of-step update and the other recorders.  It sees the state the next sweep would start
         from and writes nothing but its own buffers.  Rows collect in a device buffer of `capacity` rows, drained into
         `mon` as the other series are (whenever it holds `capacity` rows, and when `mon.series()` is called).  fields:
         every record also writes the per-dof arrays (`mon.values(tag)` reads those of the latest record).
-        Partitioned steps (`step(halo)`) are refused: a rank's reductions would include its ghost dofs."""
+
+        halo: this rank's attached halo on a cell-partitioned problem (collective: every rank calls monitor with the same
+        watches, points, reductions, every and capacity; `mon` is built with partitioned=True).  Every rank then records
+        the global row -- every membrane facet counted by one rank, the partial rows exchanged and folded on the device at
+        each record (MembraneMonitor.partition) -- and `step(halo)` records with the same halo; `mon.values(tag, halo=halo)`
+        reads the owned dofs.  Draining stays rank-local.
+        Without it, partitioned steps (`step(halo)`) are refused: a rank's reductions would include its ghost dofs."""
         lib, dp = self.lib, self.dp
-        self._attach("monitor", mon, "membrane monitors", every, capacity, t0, fields=fields,
+        self._attach("monitor", mon, "membrane monitors", every, capacity, t0, fields=fields, halo=halo,
                      busy="this stepper records membrane monitors already",
                      attached="this monitor is attached to a stepper already",
-                     set_up=lambda: mon._attach(dp, capacity), read=self._reader(lib.knpemi_monitor_read),
+                     set_up=lambda: mon._attach(dp, capacity, halo, every), read=self._reader(lib.knpemi_monitor_read),
                      record=lambda t, f: lib.knpemi_monitor_record(dp.h, float(t), f),
                      rewind=lambda: L.check(lib.knpemi_monitor_reset(dp.h)),
                      partition_refusal="membrane monitors are not recorded on partitioned steps (a rank's reductions "
