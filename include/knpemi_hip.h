@@ -249,6 +249,17 @@ int knpemi_ode_set_stimulus(knpemi_handle* h, int sub, int model, const uint8_t*
 #define KNPEMI_ODE_ON_AUX2_STREAM 8
 int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, double dt, double rtol,
                     double atol, int flags, const int32_t* ion_param, int v_index);
+/* knpemi_ode_step and knpemi_assemble_emi(emi_flags | KNPEMI_SKIP_MEMBRANE_RHS), both on the main stream (no auxiliary-stream
+ * flag in either set of flags: KNPEMI_EINVAL).  A, P and the volume part of b_emi depend on the concentrations only, not
+ * on what the sweep writes, and a small sweep leaves most of the chip idle: where the problem is eligible ONE launch holds
+ * the sweep's workgroups and the row blocks (*fused = 1), else the two launches follow each other (*fused = 0); the results
+ * are bit for bit the same.  Eligible: a model that ships with the library, integrated by LSODA; the only model of the
+ * handle; no partition; tetrahedra; a sweep of at most 3/4 of the device's compute units in workgroups, and row blocks for
+ * at most 7 rounds on the units left over.  KNPEMI_FUSED_SWEEP=0 in the environment: never fused.
+ * Either way the membrane Robin term of b_emi is pending: call knpemi_assemble_emi_membrane_rhs(emi_flags) next.  The
+ * profiling bracket of the fused launch is KNPEMI_K_ODE. */
+int knpemi_ode_step_emi(knpemi_handle* h, int sub, int model, double t0, double dt, double rtol,
+                        double atol, int flags, const int32_t* ion_param, int v_index, int emi_flags, int* fused);
 /* RHS evaluations / internal steps / failed dofs summed over all knpemi_ode_step launches since
  * the previous call (the counters are reset by this call). */
 int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n_rhs, int64_t* n_steps,
@@ -331,7 +342,7 @@ int knpemi_debug_launch_chain(knpemi_handle* h, int kind, int n, int links, int 
 int knpemi_debug_geometry(knpemi_handle* h, int* flags);
 
 /* Diagnostics (no reference counterpart): the sizes of the row-kernel layout knpemi_create built, so that a test can tell
- * which code a mesh reaches.  Fills out[0 .. min(n, 8)): 0 = longest row of the EMI pattern (membrane coupling included),
+ * which code a mesh reaches.  Fills out[0 .. min(n, 9)): 8 = row blocks (workgroups of a row kernel), 0 = longest row of the EMI pattern (membrane coupling included),
  * 1 = lanes per row, 2 = most (row, cell) pairs on one lane (more than 8: the loop after the prefetched pairs runs),
  * 3 = most distinct vertices of one row block (more than 768: the staging loop for oversized blocks runs), 4 = most
  * membrane entries on one row, 5 / 6 = dynamic LDS bytes of the latest EMI / KNP row launch (0 before the first),

@@ -161,6 +161,60 @@ int kn_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, d
   return launch_sweep(h, m, a, nullptr, cf);
 }
 
+// ---- one PDE step and the potential system's matrix per launch (knpemi_ode_step_emi) ------------------------------
+namespace {
+
+// Row-block rounds the free CUs may run under the sweep, one block per CU and round.  Measured at config 2:
+// 413 row blocks on the 64 CUs that 192 sweep workgroups leave, 6.5 rounds, end under the shortest sweep of the recorded
+// trajectory -- the fused launch takes 68.4 us where the sweep alone takes 67.6, 91.6 against 91.4 on average.  Nothing
+// longer has been measured, so nothing longer is taken: 7.
+constexpr int SWEEP_EMI_ROUNDS = 7;
+// KNPEMI_FUSED_SWEEP: 0 never, 1 whenever eligible; unset: the default below
+constexpr bool SWEEP_EMI_DEFAULT = true;
+
+// Whether the sweep of `m` (n_sweep workgroups) and the EMI row blocks go into one launch.  Everything not listed takes
+// the two launches: a shipped model under LSODA with the production kernel (no plug-in, no phase stamps, no forced second
+// wave per SIMD), the only model of an unpartitioned handle, rows the fused kernel is instantiated for, a sweep on at most
+// 3/4 of the CUs (one wave per CU each) and row blocks for at most SWEEP_EMI_ROUNDS rounds on the CUs left over.
+bool sweep_emi_eligible(knpemi_handle* h, const KnOdeModel& m, int n_sweep) {
+  const char* want = getenv("KNPEMI_FUSED_SWEEP");
+  if (want ? atoi(want) == 0 : !SWEEP_EMI_DEFAULT) return false;
+  if (m.rtc_module || m.method != KNPEMI_ODE_LSODA || getenv("KNPEMI_ODE_STAMPS") || getenv("KNPEMI_ODE_WAVES")) return false;
+  if (h->ode_only || h->dist.on || !kn_sweep_emi_rows_ok(h)) return false;
+  int bound = 0;
+  for (const KnOdeModel& o : h->ode) bound += o.bound;
+  if (bound != 1) return false;
+  if (h->n_cus == 0 && hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) {
+    (void)hipGetLastError();
+    h->n_cus = -1;
+  }
+  const int n_ode = (n_sweep + 7) & ~7;
+  if (h->n_cus <= 0 || 4 * n_ode > 3 * h->n_cus) return false;
+  return h->dev.nblocks <= SWEEP_EMI_ROUNDS * (h->n_cus - n_ode);
+}
+
+}  // namespace
+
+int kn_ode_step_emi(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde& pde,
+                    int emi_flags, int* fused) {
+  *fused = 0;
+  KnOdeModel& m = h->ode[slot];
+  if (m.nq > 0 && m.method == KNPEMI_ODE_LSODA && !m.rtc_module) {
+    OdeArgs a = model_args(h, slot, t0, dt, rtol, atol, &pde);
+    int lanes = 1;
+    with_model(m.model_id, [&](auto tag) { lanes = tag.LANES; });
+    const int n_sweep = (int)lsoda_grid(a, lanes).x;
+    if (sweep_emi_eligible(h, m, n_sweep)) {
+      const LsodaCoef* cf = nullptr;
+      if (int rc = lsoda_coef(h, &cf)) return rc;
+      if (int rc = kn_launch_sweep_emi(h, m.model_id, kn_ode_dev(h), a, cf, n_sweep, emi_flags, fused)) return rc;
+      if (*fused) return KNPEMI_OK;
+    }
+  }
+  if (int rc = kn_ode_step(h, slot, t0, dt, rtol, atol, pde)) return rc;
+  return kn_launch_emi_rows(h, emi_flags | KNPEMI_SKIP_MEMBRANE_RHS);
+}
+
 // ---- n steps per launch (knpemi_ode_advance) -------------------------------------------------------------------
 namespace {
 

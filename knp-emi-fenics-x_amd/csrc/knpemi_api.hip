@@ -1592,6 +1592,31 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
   return KNPEMI_OK;
 }
 
+extern "C" int knpemi_ode_step_emi(knpemi_handle* h, int sub, int model, double t0, double dt, double rtol,
+                                   double atol, int flags, const int32_t* ion_param, int v_index, int emi_flags, int* fused) {
+  int slot = ode_slot(h, sub, model, 1);
+  if (slot < 0) return KNPEMI_EINVAL;
+  if (!ion_param || !fused) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: ion_param and fused are required");
+  *fused = 0;
+  KnOdeModel& m = h->ode[slot];
+  for (int i = 0; i < 3 * h->K; ++i)
+    if (ion_param[i] < 0 || ion_param[i] >= m.n_params)
+      return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: parameter index out of range");
+  if (v_index < 0 || v_index >= m.n_states) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: bad V index");
+  const bool fixed = m.method != KNPEMI_ODE_LSODA;
+  if (!(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: bad dt / tolerances");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: a handle of knpemi_ode_create has no potential system");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: knpemi_set_params not called");
+  // both halves on the main stream: running them side by side is what the single launch is for
+  if ((flags & (KNPEMI_ODE_ON_AUX_STREAM | KNPEMI_ODE_ON_AUX2_STREAM)) || (emi_flags & KNPEMI_ON_AUX_STREAM))
+    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: no auxiliary-stream flags");
+  kn_inputs_changed(h);      // phi_M and the channel currents
+  KN_HIP(hipSetDevice(h->device));
+  h->emi_flags = emi_flags | KNPEMI_SKIP_MEMBRANE_RHS;
+  return kn_ode_step_emi(h, slot, t0, dt, rtol, atol, OdePde{flags, v_index, h->K, ion_param}, emi_flags, fused);
+}
+
 extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t0, double dt, int n_steps, double rtol,
                                   double atol, const int32_t* rec_idx, int n_rec, int every, double* history,
                                   const knpemi_ode_ss* ss, int32_t* steps_taken, int32_t* failed_step) {
@@ -1919,8 +1944,8 @@ extern "C" int knpemi_debug_geometry(knpemi_handle* h, int* flags) {
 
 extern "C" int knpemi_debug_layout(knpemi_handle* h, int* out, int n) {
   if (!h || !out || n < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_layout: null argument");
-  const int v[8] = {h->lay_row_max, h->lpr, h->lay_np_max, h->lds_uniq_max, h->lay_ne_max,
-                    (int)h->lds_bytes_emi, (int)h->lds_bytes_knp, h->lay_rowL_max};
-  for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+  const int v[9] = {h->lay_row_max, h->lpr, h->lay_np_max, h->lds_uniq_max, h->lay_ne_max,
+                    (int)h->lds_bytes_emi, (int)h->lds_bytes_knp, h->lay_rowL_max, h->dev.nblocks};
+  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
   return KNPEMI_OK;
 }

@@ -587,6 +587,7 @@ struct knpemi_handle : KnDevice {
   std::vector<void*> rtc_modules;   // hipModule_t of run-time compiled membrane models
   std::vector<KnOdeModel> ode; // [moff[n_sub]]
   bool ode_only = false;       // knpemi_ode_create: membrane models without a mesh (no PDE fields)
+  int n_cus = 0;               // compute units of the device, asked on first use (kernels_ode.hip: sweep_emi_eligible); -1: unknown
   // host copies of patterns for export
   std::vector<int> h_rowptr, h_colind, h_rowptrL, h_colindL;
   int comm_rank = 0;
@@ -791,6 +792,10 @@ void kn_record_free(knpemi_handle* h);    // every recorder's device memory (knp
 
 // kernel launchers (kernels_*.hip) ------------------------------------------------------------
 int kn_launch_emi_rows(knpemi_handle* h, int flags);
+// launch shape of the simplex EMI row block (emi_rows.h): accumulator doubles, staged records, lattice tetrahedra or not,
+// dynamic LDS bytes -- one rule for emi_rows_v2 and for the row blocks of the fused launch (kernels_sweep_emi.hip)
+struct KnEmiRowShape { int acc_n = 0, rec_n = 0; bool ut = false; size_t lds = 0; };
+KnEmiRowShape kn_emi_rows_shape(const knpemi_handle* h);
 int kn_launch_knp_rows(knpemi_handle* h, int flags);
 int kn_launch_knp_membrane_pre(knpemi_handle* h, int flags);
 int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags);

@@ -48,6 +48,16 @@ int kn_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, d
 int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
                    const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
                    int32_t* steps_taken, int32_t* failed_step);
+// The step of model `slot` and the potential system's A, P and volume part of b (knpemi_assemble_emi with emi_flags |
+// KNPEMI_SKIP_MEMBRANE_RHS), both on h->cur.  *fused = 1: one launch held both (kernels_sweep_emi.hip; the eligibility rule
+// is in kernels_ode.hip), 0: kn_ode_step and kn_launch_emi_rows, one after the other.
+int kn_ode_step_emi(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde& pde,
+                    int emi_flags, int* fused);
+// kernels_sweep_emi.hip: the rows of the handle are of a kind the fused launch is instantiated for; the launch itself, for
+// a sweep of n_sweep workgroups (*launched = 0 and nothing enqueued: not instantiated, or the LDS of both does not fit)
+bool kn_sweep_emi_rows_ok(const knpemi_handle* h);
+int kn_launch_sweep_emi(knpemi_handle* h, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef, int n_sweep,
+                        int emi_flags, int* launched);
 // the LSODA step of a shipped model over a caller-described table (the DG variant: membrane nodes of the broken space)
 int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef);
 int kn_lsoda_coef_upload(std::vector<void*>& owner, const void** out);   // LsodaCoef tables on the device, owned by `owner`

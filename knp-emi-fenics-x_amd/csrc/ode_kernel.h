@@ -151,7 +151,11 @@ __device__ __forceinline__ void kn_coef_store(LsodaCoef* scf, const double (&c)[
 // (lsoda_core.h); LANES = 1: one thread per dof (one-state models).
 // WAVES = 2 caps the register budget at 256 per lane so that two waves share a SIMD.  It pays once there are more
 // waves than SIMDs (large membranes); small sweeps run one wave per SIMD with the full register file.
-template <class M, int LANES, int WAVES, bool STAMPS>
+// LONE_WAVE: the wave that runs the body is the only one of its workgroup that does (the fused launch of
+// kernels_sweep_emi.hip: 256-thread workgroups whose other waves have returned).  What the workgroup shares in LDS is then
+// written and read by this wave alone, whose LDS accesses complete in order: the barrier below becomes an ordering of the
+// wave's own accesses, not a hardware barrier that siblings which have left would have to reach.
+template <class M, int LANES, int WAVES, bool STAMPS, bool LONE_WAVE = false>
 __device__ __forceinline__ void ode_step_body(const OdeDev& D, const OdeArgs& a, const LsodaCoef* __restrict__ cf) {
   using Integrator = Lsoda<M::NS, M, LANES, STAMPS, ODE_BLOCK>;
   constexpr int NI = Integrator::NI;
@@ -228,7 +232,13 @@ __device__ __forceinline__ void ode_step_body(const OdeDev& D, const OdeArgs& a,
   // 2. stimulus + LSODA (the parameter row is read once by prepare(); only the currents change)
   if (stim)
     for (int i = 0; i < a.n_stim; ++i) p[a.stim_idx[i]] = a.stim_val[i];
-  __syncthreads();   // the coefficient tables are in place
+  if constexpr (LONE_WAVE) {   // the coefficient tables are in place: this wave's own stores, ordered before its loads
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __syncthreads();   // the coefficient tables are in place
+  }
   Integrator s;
   if constexpr (STAMPS) s.st_last = __builtin_amdgcn_s_memtime();
   s.f.prepare(p);

@@ -146,6 +146,8 @@ SIGNATURES = {
     "knpemi_ode_set_stimulus": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_u8_p, C.c_int, c_int_p, c_dbl_p]),
     "knpemi_ode_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                   C.c_double, C.c_int, c_int_p, C.c_int]),
+    "knpemi_ode_step_emi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_int, c_int_p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "knpemi_ode_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64),
                                    C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "knpemi_ode_create": (C.c_int, [C.c_int, C.c_int, c_int_p, C.POINTER(C.c_void_p)]),

@@ -62,6 +62,12 @@ class DeviceStepper:
         self.ode_on_aux = None
         import os
         self.overlap_threshold_ms = float(os.environ.get("KNPEMI_OVERLAP_THRESHOLD_MS", "0.025"))     # (0: always side by side)
+        # With one membrane model the overlapped step first asks the library for ONE launch that holds the sweep and
+        # the matrix (knpemi_ode_step_emi; eligibility is the library's, KNPEMI_FUSED_SWEEP=0 disables it).  fused_sweep:
+        # None = not asked yet, False = the library declined (the streams above take over); last_fused: what the
+        # latest step's call reported (None: the step made no such call).
+        self.fused_sweep = None
+        self.last_fused = None
         self.k = 0
         self.models = []   # MembraneModel objects, in registration order
         self._model_setup = []   # (MembraneModel, stimulus, locator, initial time) for reset()
@@ -130,6 +136,7 @@ class DeviceStepper:
         L.check(self.lib.knpemi_ode_set_tables(dp.h, ode_model._sub, ode_model._model, L.dptr(st), L.dptr(pa)))
         if ode_model not in self.models:
             self.models.append(ode_model)
+            self.fused_sweep = None        # another set of models: the library decides again
             self._model_setup.append((ode_model, dict(stimulus), stimulus_locator, float(ode_model.time)))
 
     def reset(self):
@@ -404,6 +411,27 @@ class DeviceStepper:
                 "this halo does not distribute the linear solves: knpemi_solve_emi/knp on a partitioned problem "
                 "need the halo'd SpMV and the all-reduced dot products (knpemi.fem.partition.DistributedSolves)")
         flags = L.ODE_SET_TRACES | (L.ODE_SET_V if self.k > 0 else 0)
+        self.last_fused = None
+        if self.overlap and len(self.models) == 1 and self.fused_sweep is not False:
+            # the sweep and the EMI matrix (A, P, volume part of b: they do not depend on the sweep's output) in one
+            # launch where the library finds the problem eligible, one after the other on the main stream where not;
+            # no stream calibration in such a step: there is no emi_rows bracket to read
+            m = self.models[0]
+            fused = C.c_int(0)
+            L.check(lib.knpemi_ode_step_emi(dp.h, m._sub, m._model, float(m.time), self.dt, m.rtol, m.atol, flags,
+                                            L.iptr(m._ion_param), int(m.V_index), self.flags_emi, C.byref(fused)))
+            m.time = m.time + self.dt
+            self.last_fused = fused.value
+            self.fused_sweep = bool(fused.value)     # declined: the next steps run the two on two streams
+            L.check(lib.knpemi_assemble_emi_membrane_rhs(dp.h, self.flags_emi))
+        else:
+            self._sweeps_and_emi(flags)
+        self._rest_of_step(halo)
+
+    def _sweeps_and_emi(self, flags):
+        """The membrane sweeps and the assembly of the potential system as launches of their own: side by side on two
+        streams (overlap) or in the reference's order on one."""
+        dp, lib = self.dp, self.lib
         calibrate = self.overlap and self.ode_on_aux is None and self.models
         if calibrate:
             L.check(lib.knpemi_profile(dp.h, (1 << L.KERNEL_NAMES.index("ode_step_kernel"))
@@ -454,6 +482,10 @@ class DeviceStepper:
                     self.overlap = False
         else:
             L.check(lib.knpemi_assemble_emi(dp.h, self.flags_emi))
+
+    def _rest_of_step(self, halo):
+        """Everything behind the potential system's assembly: the solves, the concentration system, the update, the taps."""
+        dp, lib = self.dp, self.lib
         knp_flags = self.flags_knp
         if self.early_membrane:
             # everything of the membrane integrals that does not need the new potential: now, beside the EMI solve
