@@ -3,6 +3,7 @@
 #pragma once
 
 #include "knpemi_internal.h"
+#include "kn_pick.h"
 
 namespace kn_dg {
 
@@ -102,6 +103,13 @@ __device__ __forceinline__ double fast_rsqrt(double a) {
 __device__ __forceinline__ int dg_block_index(int b, int chunk) { return (b & 7) * chunk + (b >> 3); }
 
 }  // namespace kn_dg
+
+// The DG kernels are built for 3, 4 and 8 vertices per cell and KS = K - 1 = 1..3 solved ions; the launchers pick the
+// instantiation with kn_pick and answer anything else (unreachable with a handle knpemi_dg_create made) with this
+inline int kn_dg_not_built(const char* kernel, int NV, int KS) {
+  return kn_fail(KNPEMI_EINVAL, std::string(kernel) + ": not built for " + std::to_string(NV) + " vertices per cell and " +
+                                    std::to_string(KS) + " solved ion(s)");
+}
 
 // Q1 hexahedra (kernels_dg_hex.hip): one launch each, on `st`; KS = K - 1 solved ions; box != 0: every cell is an
 // orthogonal parallelepiped (the closed-frame kernels), 0: general trilinear cells

@@ -13,6 +13,7 @@
 //   KNP  a, L    : src/knpemi/knpWeakForm.py:123-216
 //   update       : src/knpemi/utils.py:238-295
 #include "knpemi_internal.h"
+#include "kn_pick.h"
 #include "membrane_facet.h"
 // what the simplex EMI row block is made of (logical_block, the membrane part of an EMI row, the block descriptors and the
 // staging of the records, which the other row kernels here use too) and the block itself: shared with the fused launch
@@ -149,6 +150,21 @@ __device__ __forceinline__ RecU<KS> lds_recu(const double* recs, int i) {
   for (int k = 0; k < KS; ++k) r.f[k] = p[k];
   r.c = p[KS];
   return r;
+}
+
+// ---- which row kernels are built ----------------------------------------------------------------------------------------
+// The launchers (kn_launch_emi_rows, kn_launch_knp_rows) instantiate exactly what these predicates admit and refuse the
+// rest by name.  L: lanes per row -- 2 (triangles) or 4 by default, KNPEMI_LPR for experiments; KS = K - 1 = 1..3 solved
+// ions; MEM: the membrane path of knp_rows (below).  A new value of an axis: list it in the launcher's kn_pick and admit it here.
+constexpr bool emi_rows_built(int L) { return L == 1 || L == 2 || L == 4 || L == 8; }
+// simplices, geometry variant `geo` of KnRowShape: general everywhere, the lattice form for tetrahedra
+constexpr bool simplex_geo_built(int gdim, int geo) { return geo == 0 || (geo == 2 && gdim == 3); }
+// every ion count and membrane path for the default lanes per row only; the others with two solved ions, default path
+constexpr bool knp_rows_built(int L, int KS, int MEM) {
+  return (L == 2 || L == 4) ? KS >= 1 && KS <= 3 && MEM >= 0 && MEM <= 2 : (L == 1 || L == 8) && KS == 2 && MEM == 0;
+}
+constexpr bool knp_rows_hex_built(int L, int KS, int MEM) {
+  return L == 4 ? KS >= 1 && KS <= 3 && MEM >= 0 && MEM <= 2 : (L == 1 || L == 2 || L == 8) && KS == 2 && MEM == 0;
 }
 
 // one simplex EMI row block per workgroup (emi_rows.h).  UT: lattice tetrahedra of a uniform grid
@@ -1366,182 +1382,112 @@ __global__ __launch_bounds__(256) void emi_membrane_rhs_kernel(KnDev D, const Kn
   if (live && sub == 0) D.b_emi[g] = D.b_emi[g] + gam;
 }
 
-template <class K>
-int set_lds_limit(K kernel, size_t bytes) {
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-      kn_set_error(std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
-      return KNPEMI_EHIP;
-    }
+// dynamic LDS of the membrane-facet kernels: per point of the degree-6 rule the weight and the NF shape values, on
+// quadrilateral facets the two tangent derivatives of the shape functions as well
+size_t membrane_quad_lds(const knpemi_handle* h) {
+  const int NF = h->NF;
+  return (size_t)h->dev.nq_gamma * (1 + NF + (NF == 4 ? 2 * NF : 0)) * sizeof(double);
+}
+
+// A launch of a membrane kernel, which are built for NF = 2..4 vertices per facet: f(integral_constant<NF>) launches, the
+// check follows.  (Any other NF is unreachable with a handle knpemi_create made, and an error, not some default.)
+template <class F>
+int launch_nf(const knpemi_handle* h, const char* name, F&& f) {
+  if (!kn_pick<2, 3, 4>(h->NF, f))
+    return kn_fail(KNPEMI_EINVAL, std::string(name) + ": not built for " + std::to_string(h->NF) + " vertices per facet");
+  return kn_launch_check(name);
+}
+
+// One row launch of `system`, whatever the kernel: the 160 KiB refusal, the record of the LDS bytes, then `pick`, which
+// finds the instantiation for the handle (nested kn_pick under the kernel's ..._built predicate) and hands its name, the
+// kernel (as a RowKernel<...>) and the arguments behind (D, consts) to `go` -- the raised dynamic-LDS limit, the profile bracket, the launch on
+// h->cur; no call of `go`: nothing is built for the handle, refused by name.  Last the launch check.  mem: knp_rows' MEM.
+template <auto KERNEL> struct RowKernel { static constexpr auto value = KERNEL; };
+template <class Pick>
+int launch_rows(knpemi_handle* h, int system, const KnRowShape& s, int mem, Pick&& pick) {
+  const bool knp = system == KN_ROWS_KNP;
+  if (s.lds > 160 * 1024)
+    return kn_fail(KNPEMI_EINVAL, std::string(knp ? "KNP" : "EMI") + " row block does not fit in 160 KiB of LDS");
+  (knp ? h->lds_bytes_knp : h->lds_bytes_emi) = s.lds;
+  int rc = KNPEMI_OK;
+  const char* name = nullptr;
+  pick([&](const char* kernel_name, auto k, auto... args) {
+    constexpr auto kernel = decltype(k)::value;   // a constant, not a pointer handed down: the launch calls its stub directly
+    name = kernel_name;
+    if ((rc = kn_set_lds_limit(reinterpret_cast<const void*>(kernel), s.lds))) return;
+    KnProfScope prof(h->prof, knp ? KNPEMI_K_KNP_ROWS : KNPEMI_K_EMI_ROWS, h->cur);
+    hipLaunchKernelGGL(kernel, dim3(h->dev.nblocks), dim3(KN_BLOCK), s.lds, h->cur, h->dev, h->d_consts, args...);
+  });
+  if (!name) {
+    static const char* const path[] = {"default", "fused (KNPEMI_OPT_FUSE_MEMBRANE)", "early (KNPEMI_MEMBRANE_EARLY)"};
+    return kn_fail(KNPEMI_EINVAL,
+                   std::string(knp ? "knp_rows: unsupported lanes-per-row / ion-count / membrane-option combination: "
+                                   : "emi_rows: bad lanes-per-row: ") +
+                       std::to_string(h->lpr) + " lanes per row, " + std::to_string(h->K - 1) + " solved ion(s), " +
+                       path[mem] + " membrane path, " + (h->NV == 8 ? "hexahedra" : (h->gdim == 2 ? "triangles" : "tetrahedra")));
   }
-  return KNPEMI_OK;
+  return rc ? rc : kn_launch_check(name);
 }
 
 }  // namespace
 
-KnEmiRowShape kn_emi_rows_shape(const knpemi_handle* h) {
-  KnEmiRowShape s;
-  s.acc_n = (h->lds_doubles_emi + 1) & ~1;
+KnRowShape kn_rows_shape(const knpemi_handle* h, int system) {
+  const bool knp = system == KN_ROWS_KNP;
+  const size_t S = knp ? h->K - 1 : 1;   // fields a row block solves for: accumulators, and values per staged record
+  const bool lattice_tets = h->NV != 8 && h->gdim == 3 && h->tet_uniform && h->dev.tet_tab;
+  KnRowShape s;
+  s.acc_n = ((knp ? h->lds_doubles_knp : h->lds_doubles_emi) + 1) & ~1;
   s.rec_n = h->lds_uniq_max;
-  s.ut = h->gdim == 3 && h->tet_uniform && h->dev.tet_tab;
-  s.lds = ((size_t)s.acc_n + (s.ut ? 2 : 5) * (size_t)s.rec_n + 1 + (s.ut ? KN_TET_TAB : 0)) * sizeof(double) + 2 * (size_t)h->lds_doubles_knp + 16;
+  s.gam_n = knp && h->fuse_membrane ? std::max(1, h->lds_gam_max) : 0;
+  s.geo = h->NV == 8 ? (h->hex_uniform ? 2 : (h->hex_affine ? 1 : 0)) : (lattice_tets ? 2 : 0);
+  // accumulators | staged records (without coordinates where the cells are a lattice's) and a double of padding | the shape
+  // table of the lattice tetrahedra | fused membrane integrals | the entries' 16-bit locations
+  s.lds = (S * s.acc_n + (s.geo == 2 ? S + 1 : 4 + S) * (size_t)s.rec_n + 1 + (lattice_tets ? KN_TET_TAB : 0) +
+           S * s.gam_n) * sizeof(double) + 2 * (size_t)h->lds_doubles_knp + 16;
   return s;
 }
 
-template <int GDIM>
-static int launch_emi_v2(knpemi_handle* h, int want_p, int split) {
-  const KnDev& D = h->dev;
-  const KnEmiRowShape shape = kn_emi_rows_shape(h);
-  const int acc_n = shape.acc_n, rec_n = shape.rec_n;
-  const bool ut = shape.ut;
-  const size_t lds = shape.lds;
-  if (lds > 160 * 1024) { kn_set_error("EMI row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
-  h->lds_bytes_emi = lds;
-  dim3 grid(D.nblocks), block(KN_BLOCK);
-  int rc = 0;
-#define KN_CASE2(L, U)                                                                              \
-    if ((rc = set_lds_limit(emi_rows_v2<GDIM, L, U>, lds))) return rc;                              \
-    {                                                                                               \
-      KnProfScope prof(h->prof, KNPEMI_K_EMI_ROWS, h->cur);                                         \
-      hipLaunchKernelGGL((emi_rows_v2<GDIM, L, U>), grid, block, lds, h->cur, D, h->d_consts, acc_n, \
-                         rec_n, want_p, split);                                                     \
-    }
-#define KN_CASE(L)                                                                                  \
-  case L:                                                                                           \
-    if constexpr (GDIM == 3) { if (ut) { KN_CASE2(L, true) } else { KN_CASE2(L, false) } }          \
-    else { KN_CASE2(L, false) }                                                                     \
-    break;
-  switch (h->lpr) { KN_CASE(1) KN_CASE(2) KN_CASE(4) KN_CASE(8) default: kn_set_error("bad lanes-per-row"); return KNPEMI_EINVAL; }
-#undef KN_CASE
-#undef KN_CASE2
-#ifdef KN_ROW_STAMPS
-  static int launches = 0;
-  if (++launches % 16 == 0) {
-    static std::vector<unsigned long long> acc(1024 * 8);
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(acc.data(), HIP_SYMBOL(row_stamp_acc), acc.size() * sizeof(unsigned long long));
-    const double blocks = 16.0 * D.nblocks;
-    double ph[5] = {0}, total = 0.0;
-    for (int sl = 0; sl < 1024; ++sl) for (int i = 0; i < 5; ++i) ph[i] += (double)acc[sl * 8 + i];
-    for (int i = 0; i < 5; ++i) total += ph[i];
-    fprintf(stderr, "[row stamps] emi_rows_v2, cycles per workgroup, 16 launches of %d workgroups: total %.1f\n", D.nblocks, total / blocks);
-    for (int i = 0; i < 5; ++i) fprintf(stderr, "[row stamps]   phase %d: %8.1f\n", i, ph[i] / blocks);
-    std::fill(acc.begin(), acc.end(), 0ull);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(row_stamp_acc), acc.data(), acc.size() * sizeof(unsigned long long));
-  }
-#endif
-  return kn_launch_check("emi_rows_v2");
-}
-
-template <int GDIM>
-static int launch_knp_v2(knpemi_handle* h, int split, int pre) {
-  const KnDev& D = h->dev;
-  const int acc_n = (h->lds_doubles_knp + 1) & ~1, rec_n = h->lds_uniq_max;
-  const int KS = h->K - 1;
-  const int gam_n = h->fuse_membrane ? std::max(1, h->lds_gam_max) : 0;
-  const bool ut = GDIM == 3 && h->tet_uniform && D.tet_tab;
-  const size_t lds = ((size_t)KS * acc_n + (ut ? KS + 1 : 4 + KS) * (size_t)rec_n + 1 + (ut ? KN_TET_TAB : 0) + (size_t)KS * gam_n) * sizeof(double)
-                     + 2 * (size_t)h->lds_doubles_knp + 16;
-  if (lds > 160 * 1024) { kn_set_error("KNP row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
-  h->lds_bytes_knp = lds;
-  dim3 grid(D.nblocks), block(KN_BLOCK);
-  int rc = 0;
-  const int mem = pre ? 2 : (gam_n > 0 ? 1 : 0);
-#define KN_CASE2(L, S, M, U)                                                                        \
-    if ((rc = set_lds_limit(knp_rows_v2<GDIM, L, S, M, U>, lds))) return rc;                        \
-    KnProfScope prof(h->prof, KNPEMI_K_KNP_ROWS, h->cur);                                           \
-    hipLaunchKernelGGL((knp_rows_v2<GDIM, L, S, M, U>), grid, block, lds, h->cur, D, h->d_consts, acc_n, rec_n, gam_n, split); \
-    return kn_launch_check("knp_rows_v2");
-#define KN_CASE(L, S, M)                                                                            \
-  if (h->lpr == L && KS == S && mem == M) {                                                         \
-    if constexpr (GDIM == 3) { if (ut) { KN_CASE2(L, S, M, true) } else { KN_CASE2(L, S, M, false) } } \
-    else { KN_CASE2(L, S, M, false) }                                                               \
-  }
-  // lanes per row: 2 (triangles) or 4 by default, KNPEMI_LPR for experiments; K - 1 = 1..3 solved ions; the optional
-  // membrane paths (fused, early) for the default lanes-per-row only
-  KN_CASE(2, 2, 0) KN_CASE(4, 2, 0) KN_CASE(1, 2, 0) KN_CASE(8, 2, 0) KN_CASE(2, 1, 0) KN_CASE(4, 1, 0) KN_CASE(2, 3, 0) KN_CASE(4, 3, 0)
-  KN_CASE(2, 2, 1) KN_CASE(4, 2, 1) KN_CASE(2, 1, 1) KN_CASE(4, 1, 1) KN_CASE(2, 3, 1) KN_CASE(4, 3, 1)
-  KN_CASE(2, 2, 2) KN_CASE(4, 2, 2) KN_CASE(2, 1, 2) KN_CASE(4, 1, 2) KN_CASE(2, 3, 2) KN_CASE(4, 3, 2)
-#undef KN_CASE
-#undef KN_CASE2
-  kn_set_error("knp_rows: unsupported lanes-per-row / ion-count / membrane-option combination");
-  return KNPEMI_EINVAL;
-}
-
-static int launch_emi_hex_v2(knpemi_handle* h, int want_p, int split) {
-  const KnDev& D = h->dev;
-  const int acc_n = (h->lds_doubles_emi + 1) & ~1, rec_n = h->lds_uniq_max;
-  const int geo = h->hex_uniform ? 2 : (h->hex_affine ? 1 : 0);
-  const size_t lds = ((size_t)acc_n + (geo == 2 ? 2 : 5) * (size_t)rec_n + 1) * sizeof(double) + 2 * (size_t)h->lds_doubles_knp + 16;
-  if (lds > 160 * 1024) { kn_set_error("EMI row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
-  h->lds_bytes_emi = lds;
-  dim3 grid(D.nblocks), block(KN_BLOCK);
-  int rc = 0;
-#define KN_CASE2(L, GEO)                                                                            \
-    if ((rc = set_lds_limit(emi_rows_hex_v2<L, GEO>, lds))) return rc;                              \
-    {                                                                                               \
-      KnProfScope prof(h->prof, KNPEMI_K_EMI_ROWS, h->cur);                                         \
-      hipLaunchKernelGGL((emi_rows_hex_v2<L, GEO>), grid, block, lds, h->cur, D, h->d_consts, acc_n, \
-                         rec_n, want_p, split, h->hex_geo);                                         \
-    }
-#define KN_CASE(L)                                                                                  \
-  case L:                                                                                           \
-    if (geo == 2) { KN_CASE2(L, 2) } else if (geo == 1) { KN_CASE2(L, 1) } else { KN_CASE2(L, 0) }  \
-    break;
-  switch (h->lpr) { KN_CASE(1) KN_CASE(2) KN_CASE(4) KN_CASE(8) default: kn_set_error("bad lanes-per-row"); return KNPEMI_EINVAL; }
-#undef KN_CASE
-#undef KN_CASE2
-  return kn_launch_check("emi_rows_hex_v2");
-}
-
-static int launch_knp_hex_v2(knpemi_handle* h, int split, int pre) {
-  const KnDev& D = h->dev;
-  const int acc_n = (h->lds_doubles_knp + 1) & ~1, rec_n = h->lds_uniq_max;
-  const int KS = h->K - 1;
-  const int gam_n = h->fuse_membrane ? std::max(1, h->lds_gam_max) : 0;
-  const int geo = h->hex_uniform ? 2 : (h->hex_affine ? 1 : 0);
-  const size_t lds = ((size_t)KS * acc_n + (geo == 2 ? KS + 1 : 4 + KS) * (size_t)rec_n + 1 + (size_t)KS * gam_n) * sizeof(double)
-                     + 2 * (size_t)h->lds_doubles_knp + 16;
-  if (lds > 160 * 1024) { kn_set_error("KNP row block does not fit in 160 KiB of LDS"); return KNPEMI_EINVAL; }
-  h->lds_bytes_knp = lds;
-  dim3 grid(D.nblocks), block(KN_BLOCK);
-  int rc = 0;
-  const int mem = pre ? 2 : (gam_n > 0 ? 1 : 0);
-#define KN_CASE(L, GEO, S, M)                                                                       \
-  if (h->lpr == L && geo == GEO && KS == S && mem == M) {                                           \
-    if ((rc = set_lds_limit(knp_rows_hex_v2<L, GEO, S, M>, lds))) return rc;                        \
-    KnProfScope prof(h->prof, KNPEMI_K_KNP_ROWS, h->cur);                                           \
-    hipLaunchKernelGGL((knp_rows_hex_v2<L, GEO, S, M>), grid, block, lds, h->cur, D, h->d_consts, acc_n, rec_n, gam_n, split, h->hex_geo); \
-    return kn_launch_check("knp_rows_hex_v2");                                                         \
-  }
-#define KN_GEO(L, S, M) KN_CASE(L, 2, S, M) KN_CASE(L, 1, S, M) KN_CASE(L, 0, S, M)
-  KN_GEO(4, 2, 0) KN_GEO(2, 2, 0) KN_GEO(8, 2, 0) KN_GEO(1, 2, 0) KN_GEO(4, 1, 0) KN_GEO(4, 3, 0)
-  KN_GEO(4, 2, 1) KN_GEO(4, 1, 1) KN_GEO(4, 3, 1)
-  KN_GEO(4, 2, 2) KN_GEO(4, 1, 2) KN_GEO(4, 3, 2)
-#undef KN_GEO
-#undef KN_CASE
-  kn_set_error("knp_rows (hexahedra): unsupported lanes-per-row / ion-count / membrane-option combination");
-  return KNPEMI_EINVAL;
-}
-
 int kn_launch_emi_rows(knpemi_handle* h, int flags) {
-  const KnDev& D = h->dev;
-  if (D.nblocks == 0) return KNPEMI_OK;
+  if (h->dev.nblocks == 0) return KNPEMI_OK;
   const int want_p = (flags & KNPEMI_WANT_P) ? 1 : 0;
   const int split = ((flags & KNPEMI_NO_SPLITTING) ? 0 : 1) | ((flags & KNPEMI_SKIP_MEMBRANE_RHS) ? 2 : 0);
-  if (h->NV == 8) return launch_emi_hex_v2(h, want_p, split);
-  return h->gdim == 2 ? launch_emi_v2<2>(h, want_p, split) : launch_emi_v2<3>(h, want_p, split);
+  const KnRowShape s = kn_rows_shape(h, KN_ROWS_EMI);
+  // vertices per cell (3, 4: simplices of dimension NV - 1, 8: hexahedra) x lanes per row x geometry variant
+  const int rc = launch_rows(h, KN_ROWS_EMI, s, 0, [&](auto go) {
+    kn_pick<3, 4, 8>(h->NV, [&](auto nv) { kn_pick<1, 2, 4, 8>(h->lpr, [&](auto l) { kn_pick<0, 1, 2>(s.geo, [&](auto geo) {
+      constexpr int NV = decltype(nv)::value, L = decltype(l)::value, GEO = decltype(geo)::value;
+      if constexpr (NV == 8 && emi_rows_built(L))
+        go("emi_rows_hex_v2", RowKernel<emi_rows_hex_v2<L, GEO>>{}, s.acc_n, s.rec_n, want_p, split, h->hex_geo);
+      else if constexpr (NV != 8 && emi_rows_built(L) && simplex_geo_built(NV - 1, GEO))
+        go("emi_rows_v2", RowKernel<emi_rows_v2<NV - 1, L, GEO == 2>>{}, s.acc_n, s.rec_n, want_p, split);
+    }); }); });
+  });
+#ifdef KN_ROW_STAMPS
+  static int launches = 0;
+  if (h->NV != 8)
+    kn_stamps_report(&row_stamp_acc, 8, 5, 16, ++launches, h->dev.nblocks, "[row stamps]", "emi_rows_v2", "cycles", "workgroup");
+#endif
+  return rc;
 }
 
 int kn_launch_knp_rows(knpemi_handle* h, int flags) {
-  const KnDev& D = h->dev;
-  if (D.nblocks == 0) return KNPEMI_OK;
+  if (h->dev.nblocks == 0) return KNPEMI_OK;
   const int split = (flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
-  const int pre = (flags & KNPEMI_MEMBRANE_EARLY) ? 1 : 0;   // membrane integrals from knp_membrane_pre_kernel
-  if (h->NV == 8) return launch_knp_hex_v2(h, split, pre);
-  return h->gdim == 2 ? launch_knp_v2<2>(h, split, pre) : launch_knp_v2<3>(h, split, pre);
+  const KnRowShape s = kn_rows_shape(h, KN_ROWS_KNP);
+  // the membrane integrals of b_knp: from knp_membrane_pre_kernel (2), evaluated in the row block (1), from gam_e (0)
+  const int mem = (flags & KNPEMI_MEMBRANE_EARLY) ? 2 : (s.gam_n > 0 ? 1 : 0);
+  return launch_rows(h, KN_ROWS_KNP, s, mem, [&](auto go) {
+    kn_pick<3, 4, 8>(h->NV, [&](auto nv) { kn_pick<1, 2, 4, 8>(h->lpr, [&](auto l) { kn_pick<0, 1, 2>(s.geo, [&](auto geo) {
+      kn_pick<1, 2, 3>(h->K - 1, [&](auto ks) { kn_pick<0, 1, 2>(mem, [&](auto m) {
+        constexpr int NV = decltype(nv)::value, L = decltype(l)::value, GEO = decltype(geo)::value;
+        constexpr int KS = decltype(ks)::value, MEM = decltype(m)::value;
+        if constexpr (NV == 8 && knp_rows_hex_built(L, KS, MEM))
+          go("knp_rows_hex_v2", RowKernel<knp_rows_hex_v2<L, GEO, KS, MEM>>{}, s.acc_n, s.rec_n, s.gam_n, split, h->hex_geo);
+        else if constexpr (NV != 8 && knp_rows_built(L, KS, MEM) && simplex_geo_built(NV - 1, GEO))
+          go("knp_rows_v2", RowKernel<knp_rows_v2<NV - 1, L, KS, MEM, GEO == 2>>{}, s.acc_n, s.rec_n, s.gam_n, split);
+      }); });
+    }); }); });
+  });
 }
 
 int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_row, double* d_out) {
@@ -1549,24 +1495,21 @@ int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_
   const KnDev& D = h->dev;
   dim3 grid((n_entries + 255) / 256), block(256);
   const int v_cells = h->voff[1];
-  if (h->NF == 2) hipLaunchKernelGGL(membrane_mass_kernel<2>, grid, block, 0, h->stream, D, n_entries, v_cells, d_entry_row, d_out);
-  else if (h->NF == 3) hipLaunchKernelGGL(membrane_mass_kernel<3>, grid, block, 0, h->stream, D, n_entries, v_cells, d_entry_row, d_out);
-  else hipLaunchKernelGGL(membrane_mass_kernel<4>, grid, block, 0, h->stream, D, n_entries, v_cells, d_entry_row, d_out);
-  return kn_launch_check("membrane_mass_kernel");
+  return launch_nf(h, "membrane_mass_kernel", [&](auto nf) {
+    hipLaunchKernelGGL(membrane_mass_kernel<decltype(nf)::value>, grid, block, 0, h->stream, D, n_entries, v_cells, d_entry_row, d_out);
+  });
 }
 
 int kn_launch_knp_membrane(knpemi_handle* h, int flags) {
   const KnDev& D = h->dev;
   if (D.nftot == 0) return KNPEMI_OK;
   const int split = (flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
-  const int NF = h->NF;
-  const size_t lds = (size_t)D.nq_gamma * (1 + NF + (NF == 4 ? 2 * NF : 0)) * sizeof(double);
+  const size_t lds = membrane_quad_lds(h);
   dim3 grid((2 * (size_t)D.nftot * KN_MEM_LQ + 255) / 256), block(256);
   KnProfScope prof(h->prof, KNPEMI_K_KNP_MEMBRANE, h->cur);
-  if (NF == 2) hipLaunchKernelGGL((knp_membrane_kernel<2>), grid, block, lds, h->cur, D, h->d_consts, split);
-  else if (NF == 3) hipLaunchKernelGGL((knp_membrane_kernel<3>), grid, block, lds, h->cur, D, h->d_consts, split);
-  else hipLaunchKernelGGL((knp_membrane_kernel<4>), grid, block, lds, h->cur, D, h->d_consts, split);
-  return kn_launch_check("knp_membrane_kernel");
+  return launch_nf(h, "knp_membrane_kernel", [&](auto nf) {
+    hipLaunchKernelGGL(knp_membrane_kernel<decltype(nf)::value>, grid, block, lds, h->cur, D, h->d_consts, split);
+  });
 }
 
 // phi <- x - mean and the membrane-facet integrals of b_knp for that potential, one launch (see the kernel).  np = 0: x is
@@ -1576,30 +1519,27 @@ int kn_launch_emi_writeback_membrane(knpemi_handle* h, const double* x, const do
   const int n = D.Ntot;
   if (n == 0) return KNPEMI_OK;
   const int split = (h->emi_flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
-  const int NF = h->NF;
-  const size_t lds = (size_t)D.nq_gamma * (1 + NF + (NF == 4 ? 2 * NF : 0)) * sizeof(double);
+  const size_t lds = membrane_quad_lds(h);
   const int nbm = (int)((2 * (size_t)D.nftot * KN_MEM_LQ + 255) / 256);
   const int nbv = std::max(1, std::min(1024, (n + 255) / 256));
   dim3 grid(nbm + nbv), block(256);
   KnProfScope prof(h->prof, KNPEMI_K_KNP_MEMBRANE, h->cur);
-  if (NF == 2) hipLaunchKernelGGL((emi_writeback_membrane_kernel<2>), grid, block, lds, h->cur, D, h->d_consts, split, nbm, x, n, part, np, inv_n, mean_out);
-  else if (NF == 3) hipLaunchKernelGGL((emi_writeback_membrane_kernel<3>), grid, block, lds, h->cur, D, h->d_consts, split, nbm, x, n, part, np, inv_n, mean_out);
-  else hipLaunchKernelGGL((emi_writeback_membrane_kernel<4>), grid, block, lds, h->cur, D, h->d_consts, split, nbm, x, n, part, np, inv_n, mean_out);
-  return kn_launch_check("emi_writeback_membrane_kernel");
+  return launch_nf(h, "emi_writeback_membrane_kernel", [&](auto nf) {
+    hipLaunchKernelGGL(emi_writeback_membrane_kernel<decltype(nf)::value>, grid, block, lds, h->cur, D, h->d_consts, split, nbm,
+                       x, n, part, np, inv_n, mean_out);
+  });
 }
 
 int kn_launch_knp_membrane_pre(knpemi_handle* h, int flags) {
   const KnDev& D = h->dev;
   if (D.nftot == 0) return KNPEMI_OK;
   const int split = (flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
-  const int NF = h->NF;
-  const size_t lds = (size_t)D.nq_gamma * (1 + NF + (NF == 4 ? 2 * NF : 0)) * sizeof(double);
+  const size_t lds = membrane_quad_lds(h);
   dim3 grid((2 * D.nftot + 255) / 256), block(256);
   KnProfScope prof(h->prof, KNPEMI_K_KNP_MEMBRANE, h->cur);
-  if (NF == 2) hipLaunchKernelGGL((knp_membrane_pre_kernel<2>), grid, block, lds, h->cur, D, h->d_consts, split);
-  else if (NF == 3) hipLaunchKernelGGL((knp_membrane_pre_kernel<3>), grid, block, lds, h->cur, D, h->d_consts, split);
-  else hipLaunchKernelGGL((knp_membrane_pre_kernel<4>), grid, block, lds, h->cur, D, h->d_consts, split);
-  return kn_launch_check("knp_membrane_pre_kernel");
+  return launch_nf(h, "knp_membrane_pre_kernel", [&](auto nf) {
+    hipLaunchKernelGGL(knp_membrane_pre_kernel<decltype(nf)::value>, grid, block, lds, h->cur, D, h->d_consts, split);
+  });
 }
 
 int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags) {
@@ -1609,14 +1549,16 @@ int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags) {
   const int lpr = h->lpr;      // the same lane groups as the row kernels, so that both forms produce the same bits
   dim3 grid(((size_t)D.M * lpr + 255) / 256), block(256);
   KnProfScope prof(h->prof, KNPEMI_K_EMI_MEMBRANE, h->cur);
-#define KN_ROBIN(NFV, L) hipLaunchKernelGGL((emi_membrane_rhs_kernel<NFV, L>), grid, block, 0, h->stream, D, h->d_consts, split)
-#define KN_ROBIN_L(NFV) \
-  switch (lpr) { case 1: KN_ROBIN(NFV, 1); break; case 2: KN_ROBIN(NFV, 2); break; case 8: KN_ROBIN(NFV, 8); break; \
-                 default: KN_ROBIN(NFV, 4); }
-  if (h->NF == 2) { KN_ROBIN_L(2) } else if (h->NF == 3) { KN_ROBIN_L(3) } else { KN_ROBIN_L(4) }
-#undef KN_ROBIN_L
-#undef KN_ROBIN
-  return kn_launch_check("emi_membrane_rhs_kernel");
+  bool built = false;
+  const int rc = launch_nf(h, "emi_membrane_rhs_kernel", [&](auto nf) {
+    built = kn_pick<1, 2, 4, 8>(lpr, [&](auto l) {
+      hipLaunchKernelGGL((emi_membrane_rhs_kernel<decltype(nf)::value, decltype(l)::value>), grid, block, 0, h->stream, D,
+                         h->d_consts, split);
+    });
+  });
+  if (rc == KNPEMI_OK && !built)
+    return kn_fail(KNPEMI_EINVAL, "emi_membrane_rhs_kernel: not built for " + std::to_string(lpr) + " lanes per row");
+  return rc;
 }
 
 int kn_launch_update_pde(knpemi_handle* h) {

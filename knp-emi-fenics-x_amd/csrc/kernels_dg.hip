@@ -149,6 +149,11 @@ __device__ __forceinline__ void copy_out(double* __restrict__ dst, const double*
 template <int NV> constexpr int dg_fs_emi() { return (6 + 2 * NV) | 1; }   // n[3] area inv_h JNn | gNn[nv] | kN[nv]
 // n[3] area inv_h gphiNn | interior facet: gNn[nv]; membrane facet: G[facet vertex][k], the membrane integrals
 template <int NV, int KS> constexpr int dg_fs_knp() { return (6 + ((NV - 1) * KS > NV ? (NV - 1) * KS : NV)) | 1; }
+// dynamic LDS of a workgroup: the facet summaries of its rows, the scratch behind them.  KS = 0: dg_emi_kernel
+template <int NV, int KS> constexpr size_t dg_lds_bytes() {
+  constexpr int rpb = (DG_BLOCK / NV) * NV, fs = KS == 0 ? dg_fs_emi<NV>() : dg_fs_knp<NV, KS>();
+  return ((size_t)rpb * fs + dg_scratch_doubles<NV, 1>()) * sizeof(double);
+}
 
 // Diagnostic build (make CXXFLAGS+=-DKN_DG_STAMPS): dg_emi_kernel adds up s_memtime differences between its phases (one
 // atomic per phase and wave, spread over 1024 slots); the launcher prints the averages every 8 launches.
@@ -731,40 +736,18 @@ int launch_emi(knpemi_dg* h, int flags) {
   if (h->NV == 8) return kn_dg_hex_launch_emi(h->stream, h->dev, h->d_consts, !(flags & KNPEMI_NO_SPLITTING), h->hex_box);
   const int NV = h->NV, rpb = (DG_BLOCK / NV) * NV;
   const int nblocks = (h->dev.n_dof + rpb - 1) / rpb, chunk = (nblocks + 7) / 8;
-  const size_t lds = ((size_t)rpb * (NV == 3 ? dg_fs_emi<3>() : dg_fs_emi<4>()) +
-                      (NV == 3 ? dg_scratch_doubles<3, 1>() : dg_scratch_doubles<4, 1>())) * sizeof(double);
   const int split = !(flags & KNPEMI_NO_SPLITTING);
-  if (NV == 3) hipLaunchKernelGGL(dg_emi_kernel<3>, dim3(8 * chunk), dim3(DG_BLOCK), lds, h->stream, h->dev, h->d_consts, chunk, split);
-  else hipLaunchKernelGGL(dg_emi_kernel<4>, dim3(8 * chunk), dim3(DG_BLOCK), lds, h->stream, h->dev, h->d_consts, chunk, split);
+  if (!kn_pick<3, 4>(NV, [&](auto nv) {
+        constexpr int V = decltype(nv)::value;
+        constexpr size_t lds = dg_lds_bytes<V, 0>();
+        hipLaunchKernelGGL(dg_emi_kernel<V>, dim3(8 * chunk), dim3(DG_BLOCK), lds, h->stream, h->dev, h->d_consts, chunk, split);
+      }))
+    return kn_dg_not_built("dg_emi_kernel", NV, 0);
 #ifdef KN_DG_STAMPS
   static int launches = 0;
-  if (++launches % 8 == 0) {
-    static std::vector<unsigned long long> acc(1024 * 16);
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(acc.data(), HIP_SYMBOL(dg_stamp_acc), acc.size() * sizeof(unsigned long long));
-    const double waves = 8.0 * nblocks;
-    double ph[5] = {0}, total = 0.0;
-    for (int sl = 0; sl < 1024; ++sl) for (int i = 0; i < 5; ++i) ph[i] += (double)acc[sl * 16 + i];
-    for (int i = 0; i < 5; ++i) total += ph[i];
-    fprintf(stderr, "[dg stamps] dg_emi_kernel, cycles per wave, 8 launches of %d waves: total %.1f\n", nblocks, total / waves);
-    for (int i = 0; i < 5; ++i) fprintf(stderr, "[dg stamps]   phase %d: %8.1f\n", i, ph[i] / waves);
-    std::fill(acc.begin(), acc.end(), 0ull);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(dg_stamp_acc), acc.data(), acc.size() * sizeof(unsigned long long));
-  }
+  kn_stamps_report(&dg_stamp_acc, 16, 5, 8, ++launches, nblocks, "[dg stamps]", "dg_emi_kernel", "cycles", "wave");
 #endif
   return kn_launch_check("dg_emi_kernel");
-}
-
-template <int NV>
-int launch_knp_nv(knpemi_dg* h, int chunk, int split) {
-  constexpr int rpb = (DG_BLOCK / NV) * NV;
-  const dim3 grid(8 * chunk), block(DG_BLOCK);
-  switch (h->K - 1) {
-    case 1: hipLaunchKernelGGL((dg_knp_kernel<NV, 1>), grid, block, ((size_t)rpb * dg_fs_knp<NV, 1>() + dg_scratch_doubles<NV, 1>()) * sizeof(double), h->stream, h->dev, h->d_consts, chunk, split); break;
-    case 2: hipLaunchKernelGGL((dg_knp_kernel<NV, 2>), grid, block, ((size_t)rpb * dg_fs_knp<NV, 2>() + dg_scratch_doubles<NV, 1>()) * sizeof(double), h->stream, h->dev, h->d_consts, chunk, split); break;
-    default: hipLaunchKernelGGL((dg_knp_kernel<NV, 3>), grid, block, ((size_t)rpb * dg_fs_knp<NV, 3>() + dg_scratch_doubles<NV, 1>()) * sizeof(double), h->stream, h->dev, h->d_consts, chunk, split); break;
-  }
-  return kn_launch_check("dg_knp_kernel");
 }
 
 int launch_knp(knpemi_dg* h, int flags) {
@@ -773,7 +756,15 @@ int launch_knp(knpemi_dg* h, int flags) {
   const int NV = h->NV, rpb = (DG_BLOCK / NV) * NV;
   const int nblocks = (h->dev.n_dof + rpb - 1) / rpb, chunk = (nblocks + 7) / 8;
   const int split = !(flags & KNPEMI_NO_SPLITTING);
-  return NV == 3 ? launch_knp_nv<3>(h, chunk, split) : launch_knp_nv<4>(h, chunk, split);
+  bool built = false;
+  kn_pick<3, 4>(NV, [&](auto nv) {
+    built = kn_pick<1, 2, 3>(h->K - 1, [&](auto ks) {
+      constexpr int V = decltype(nv)::value, KS = decltype(ks)::value;
+      constexpr size_t lds = dg_lds_bytes<V, KS>();
+      hipLaunchKernelGGL((dg_knp_kernel<V, KS>), dim3(8 * chunk), dim3(DG_BLOCK), lds, h->stream, h->dev, h->d_consts, chunk, split);
+    });
+  });
+  return built ? kn_launch_check("dg_knp_kernel") : kn_dg_not_built("dg_knp_kernel", NV, h->K - 1);
 }
 
 }  // namespace

@@ -1349,19 +1349,9 @@ int kn_dg_hex_launch_emi(hipStream_t st, const kn_dg::DgDev& D, const kn_dg::DgC
   else hipLaunchKernelGGL(dg_emi_hex_kernel, dim3(8 * chunk), dim3(DG_BLOCK), 0, st, D, d_consts, chunk, splitting);
 #ifdef KN_HX_STAMPS
   static int launches = 0;
-  if (box && ++launches % 8 == 0) {
-    static std::vector<unsigned long long> acc(1024 * 32);
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(acc.data(), HIP_SYMBOL(hx_stamp_acc), acc.size() * sizeof(unsigned long long));
-    const double waves = 8.0 * nblocks;
-    double ph[18] = {0}, total = 0.0;
-    for (int sl = 0; sl < 1024; ++sl) for (int i = 0; i < 18; ++i) ph[i] += (double)acc[sl * 32 + i];
-    for (int i = 0; i < 18; ++i) total += ph[i];
-    fprintf(stderr, "[hx stamps] dg_emi_hex_box_kernel, s_memtime ticks (100 MHz) per wave, 8 launches of %d waves: total %.1f\n", nblocks, total / waves);
-    for (int i = 0; i < 18; ++i) fprintf(stderr, "[hx stamps]   phase %2d: %8.1f\n", i, ph[i] / waves);
-    std::fill(acc.begin(), acc.end(), 0ull);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(hx_stamp_acc), acc.data(), acc.size() * sizeof(unsigned long long));
-  }
+  if (box)
+    kn_stamps_report(&hx_stamp_acc, 32, 18, 8, ++launches, nblocks, "[hx stamps]", "dg_emi_hex_box_kernel",
+                     "s_memtime ticks (100 MHz)", "wave");
 #endif
   return kn_launch_check("dg_emi_hex_kernel");
 }
@@ -1369,18 +1359,12 @@ int kn_dg_hex_launch_emi(hipStream_t st, const kn_dg::DgDev& D, const kn_dg::DgC
 int kn_dg_hex_launch_knp(hipStream_t st, const kn_dg::DgDev& D, const kn_dg::DgConsts* d_consts, int KS, int splitting, int box) {
   const int nblocks = (D.n_cell + HX_CELLS - 1) / HX_CELLS, chunk = (nblocks + 7) / 8;
   const dim3 grid(8 * chunk), block(DG_BLOCK);
-  if (box) {
-    switch (KS) {
-      case 1: hipLaunchKernelGGL(dg_knp_hex_box_kernel<1>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
-      case 2: hipLaunchKernelGGL(dg_knp_hex_box_kernel<2>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
-      default: hipLaunchKernelGGL(dg_knp_hex_box_kernel<3>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
-    }
-    return kn_launch_check("dg_knp_hex_box_kernel");
-  }
-  switch (KS) {
-    case 1: hipLaunchKernelGGL(dg_knp_hex_kernel<1>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
-    case 2: hipLaunchKernelGGL(dg_knp_hex_kernel<2>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
-    default: hipLaunchKernelGGL(dg_knp_hex_kernel<3>, grid, block, 0, st, D, d_consts, chunk, splitting); break;
-  }
-  return kn_launch_check("dg_knp_hex_kernel");
+  const char* name = box ? "dg_knp_hex_box_kernel" : "dg_knp_hex_kernel";
+  if (!kn_pick<1, 2, 3>(KS, [&](auto ks) {
+        constexpr int S = decltype(ks)::value;
+        if (box) hipLaunchKernelGGL(dg_knp_hex_box_kernel<S>, grid, block, 0, st, D, d_consts, chunk, splitting);
+        else hipLaunchKernelGGL(dg_knp_hex_kernel<S>, grid, block, 0, st, D, d_consts, chunk, splitting);
+      }))
+    return kn_dg_not_built(name, HX_NV, KS);
+  return kn_launch_check(name);
 }

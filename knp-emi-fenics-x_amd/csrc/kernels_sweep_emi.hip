@@ -40,8 +40,7 @@ constexpr size_t LDS_PER_CU = 160 * 1024;
 // the dynamic part the row block's -- fits a CU, and a CU holds ONE workgroup of the kernel (registers or LDS; the HH
 // models' sweep takes 262 registers, a row block compiled with it as many): a row block then never lands on a sweep
 // wave's CU, where it would take issue slots from the stream the step waits for.  The glial sweep fits 255 registers:
-// two workgroups per CU unless the row block's LDS forbids it, so that model is mostly declined here.  The dynamic limit
-// is raised as set_lds_limit (kernels_assemble.hip) does for the row kernels.
+// two workgroups per CU unless the row block's LDS forbids it, so that model is mostly declined here.
 template <auto KERNEL>
 int prepare_kernel(size_t dyn, bool* fits) {
   static size_t static_lds = 0, asked_dyn = 0;
@@ -54,7 +53,7 @@ int prepare_kernel(size_t dyn, bool* fits) {
   }
   *fits = static_lds + dyn <= LDS_PER_CU;
   if (!*fits) return KNPEMI_OK;
-  if (dyn > 64 * 1024) KN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  if (int rc = kn_set_lds_limit(fn, dyn)) return rc;
   if (per_cu == 0 || asked_dyn != dyn) {
     KN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, KN_BLOCK, dyn));
     asked_dyn = dyn;
@@ -75,7 +74,7 @@ int kn_launch_sweep_emi(knpemi_handle* h, int model_id, const OdeDev& dv, const 
   *launched = 0;
   if (!kn_sweep_emi_rows_ok(h)) return KNPEMI_OK;
   const KnDev& D = h->dev;
-  const KnEmiRowShape shape = kn_emi_rows_shape(h);
+  const KnRowShape shape = kn_rows_shape(h, KN_ROWS_EMI);
   const int want_p = (emi_flags & KNPEMI_WANT_P) ? 1 : 0;
   const int split = ((emi_flags & KNPEMI_NO_SPLITTING) ? 0 : 1) | 2;   // 2: without the membrane Robin term
   const int n_ode = (n_sweep + 7) & ~7;
@@ -95,7 +94,7 @@ int kn_launch_sweep_emi(knpemi_handle* h, int model_id, const OdeDev& dv, const 
                          shape.rec_n, want_p, split);
       *launched = 1;
     };
-    if (shape.ut) go(std::true_type{});
+    if (shape.geo == 2) go(std::true_type{});
     else go(std::false_type{});
   });
   if (rc || !*launched) return rc;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -407,6 +408,34 @@ inline int kn_launch_check(const std::string& what) {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? KNPEMI_OK : kn_fail(KNPEMI_EHIP, what + ": " + hipGetErrorString(e));
 }
+// before a launch with `bytes` of dynamic LDS: above 64 KiB the kernel's limit has to be raised first
+inline int kn_set_lds_limit(const void* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return KNPEMI_OK;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  return e == hipSuccess ? KNPEMI_OK
+                         : kn_fail(KNPEMI_EHIP, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
+}
+// Read-back of the diagnostic builds (KN_ROW_STAMPS, KN_DG_STAMPS, KN_HX_STAMPS): `symbol` is a __device__ array of 1024
+// slots, slot_stride counters apart, of which the first n_phases hold the ticks the kernel added up per phase.  On every
+// `every`-th launch (`launch` counts them from 1): synchronise, print the averages per unit (`n_units` workgroups or waves a
+// launch) under `label`, zero the counters.
+inline void kn_stamps_report(const void* symbol, int slot_stride, int n_phases, int every, int launch, int n_units,
+                             const char* label, const char* kernel, const char* units, const char* unit) {
+  if (launch % every != 0) return;
+  std::vector<unsigned long long> acc((size_t)1024 * slot_stride);
+  const size_t bytes = acc.size() * sizeof(unsigned long long);
+  (void)hipDeviceSynchronize();
+  (void)hipMemcpyFromSymbol(acc.data(), symbol, bytes);
+  const double n = (double)every * n_units;
+  std::vector<double> ph(n_phases, 0.0);
+  double total = 0.0;
+  for (int sl = 0; sl < 1024; ++sl) for (int i = 0; i < n_phases; ++i) ph[i] += (double)acc[(size_t)sl * slot_stride + i];
+  for (int i = 0; i < n_phases; ++i) total += ph[i];
+  fprintf(stderr, "%s %s, %s per %s, %d launches of %d %ss: total %.1f\n", label, kernel, units, unit, every, n_units, unit, total / n);
+  for (int i = 0; i < n_phases; ++i) fprintf(stderr, "%s   phase %*d: %8.1f\n", label, n_phases > 9 ? 2 : 1, i, ph[i] / n);
+  std::fill(acc.begin(), acc.end(), 0ull);
+  (void)hipMemcpyToSymbol(symbol, acc.data(), bytes);
+}
 
 // The device base of both handles (knpemi_handle here, knpemi_dg in kernels_dg.hip): what they own in the same way, and the
 // one set of helpers for it.  Host only.
@@ -792,10 +821,14 @@ void kn_record_free(knpemi_handle* h);    // every recorder's device memory (knp
 
 // kernel launchers (kernels_*.hip) ------------------------------------------------------------
 int kn_launch_emi_rows(knpemi_handle* h, int flags);
-// launch shape of the simplex EMI row block (emi_rows.h): accumulator doubles, staged records, lattice tetrahedra or not,
-// dynamic LDS bytes -- one rule for emi_rows_v2 and for the row blocks of the fused launch (kernels_sweep_emi.hip)
-struct KnEmiRowShape { int acc_n = 0, rec_n = 0; bool ut = false; size_t lds = 0; };
-KnEmiRowShape kn_emi_rows_shape(const knpemi_handle* h);
+// Launch shape of a row block, of either system (KN_ROWS_EMI, KN_ROWS_KNP) on simplices and hexahedra: accumulator
+// doubles per solved field, staged records, fused membrane integrals (KNP with KNPEMI_OPT_FUSE_MEMBRANE, else 0), the
+// geometry variant -- 2: lattice cells (tetrahedra or boxes of a uniform grid: records without coordinates), 1: affine
+// hexahedra, 0: general -- and the dynamic LDS bytes.  One rule for the four row kernels and for the row blocks of the fused
+// launch (kernels_sweep_emi.hip).
+enum { KN_ROWS_EMI = 0, KN_ROWS_KNP = 1 };
+struct KnRowShape { int acc_n = 0, rec_n = 0, gam_n = 0, geo = 0; size_t lds = 0; };
+KnRowShape kn_rows_shape(const knpemi_handle* h, int system);
 int kn_launch_knp_rows(knpemi_handle* h, int flags);
 int kn_launch_knp_membrane_pre(knpemi_handle* h, int flags);
 int kn_launch_emi_membrane_rhs(knpemi_handle* h, int flags);

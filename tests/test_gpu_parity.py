@@ -1684,62 +1684,18 @@ def test_ion_counts_other_than_three_match_oracle(hip_lib, kind, r, n_ions):
     uses three species.  K = 2 (one solved + one eliminated) and K = 4 (three solved, one of them divalent): operators,
     right-hand sides in both splitting modes, and the end-of-step update (eliminated ion from electroneutrality)
     against the oracle, which is generic in K."""
-    import contextlib
-    import io
-    from helpers import C_M, FARADAY, PSI, make_mesh
-    from knpemi import (create_functions_emi, create_functions_knp, emi_system, knp_system, set_initial_conditions,
-                        update_pde_variables)
-    from knpemi.fem import Constant, Function, extract_submesh
+    from helpers import ion_count_problem, make_mesh
+    from knpemi import update_pde_variables
     from knpemi.pdeSolver import create_solver_emi, create_solver_knp
-    import adapters
-    spec = {2: [("K", 1.0, 3.3, 124.2, 1.96e-9), ("Na", 1.0, 100.7, 12.8, 1.33e-9)],
-            4: [("K", 1.0, 3.3, 124.2, 1.96e-9), ("Cl", -1.0, 104.0, 137.0, 2.03e-9), ("Ca", 2.0, 1.2, 1e-1, 0.71e-9),
-                ("Na", 1.0, 100.7, 12.8, 1.33e-9)]}[n_ions]
-    mesh, ct, ft = make_mesh(kind, r)
-    dt = 1e-4
-
-    class Dummy:        # the forms only read the facet tag of a membrane model (emiWeakForm.py:162)
-        tag = 1
+    mesh_data = make_mesh(kind, r)
     for splitting in (True, False):
-        subs = {}
-        for t in (0, 1):
-            sm, e2p, v2p, _, _ = extract_submesh(mesh, ct, t)
-            subs[t] = dict(tag=t, name=f"sub{t}", mesh_sub=sm, sub_to_parent=e2p, sub_vertex_to_parent=v2p)
-        g, g2p, _, _, _ = extract_submesh(mesh, ft, [1])
-        subs[1].update(mesh_mem=g, mem_to_parent=g2p, membrane_tags=[1])
-        rho = {'z': -1, 0: Constant(subs[0]['mesh_sub'], 0.05), 1: Constant(subs[1]['mesh_sub'], 0.2)}
-        pp = {'dt': Constant(mesh, dt), 'F': Constant(mesh, FARADAY), 'psi': Constant(mesh, PSI),
-              'C_phi': Constant(mesh, C_M / dt), 'C_M': Constant(mesh, C_M), 'rho': rho}
-        ions = [dict(name=n, z=z, D={0: Constant(None, D), 1: Constant(None, 1.1 * D)},
-                     c_init={0: Constant(None, ce), 1: Constant(None, ci)}) for n, z, ce, ci, D in spec]
-        with contextlib.redirect_stdout(io.StringIO()):
-            phi, phi_M_prev = create_functions_emi(subs, degree=1)
-            c, c_prev = create_functions_knp(subs, ions, degree=1)
-            set_initial_conditions(ions, subs, c_prev)
-        Q = phi_M_prev[1].function_space
-        subs[1]['mem_models'] = [{'ode': Dummy(), 'I_ch_k': {ion['name']: Function(Q, name=f"I_{ion['name']}") for ion in ions}}]
-        rng = np.random.default_rng(11)
-        for t in (0, 1):
-            ions[-1][f'c_{t}'].x.array[:] = spec[-1][2 + t]
-            for f in c_prev[t] + [ions[-1][f'c_{t}']]:
-                f.x.array[:] *= 1.0 + 1e-2 * rng.uniform(-1, 1, f.x.array.shape[0])
-            phi[t].x.array[:] = 1e-3 * rng.uniform(-1, 1, phi[t].x.array.shape[0])
-            for f in c[t]:
-                f.x.array[:] = rng.uniform(1.0, 100.0, f.x.array.shape[0])
-        phi_M_prev[1].x.array[:] = -0.07 + 1e-3 * rng.uniform(-1, 1, phi_M_prev[1].x.array.shape[0])
-        for f in subs[1]['mem_models'][0]['I_ch_k'].values():
-            f.x.array[:] = 1e-2 * rng.uniform(-1, 1, f.x.array.shape[0])
-        a_emi, p_emi, L_emi = emi_system(mesh, ct, ft, pp, ions, subs, phi, phi_M_prev, c_prev, dt,
-                                         splitting_scheme=splitting)
-        a_knp, p_knp, L_knp = knp_system(mesh, ct, ft, pp, ions, subs, phi, phi_M_prev, c, c_prev, dt,
-                                         splitting_scheme=splitting)
-        s = type("S", (), {})()
-        s.__dict__.update(mesh=mesh, ct=ct, ft=ft, subdomain_list=subs, ion_list=ions, physical_parameters=pp, dt=dt,
-                          phi=phi, phi_M_prev=phi_M_prev, c=c, c_prev=c_prev)
-        o, P, params, oions = adapters.oracle_problem(s, {0: [], 1: [1]})
-        c_all, ophi, phiM, mm = adapters.oracle_fields(s)
-        emi = create_solver_emi(a_emi, L_emi, phi, [], subs, None, p=p_emi, direct=False)
-        knp = create_solver_knp(a_knp, L_knp, c, [], subs, None, p=p_knp)
+        s = ion_count_problem(mesh_data, n_ions, splitting)
+        mesh, ct, subs, ions, pp, rho, dt = s.mesh, s.ct, s.subdomain_list, s.ion_list, s.physical_parameters, s.rho, s.dt
+        phi, phi_M_prev, c, c_prev = s.phi, s.phi_M_prev, s.c, s.c_prev
+        o, P, params, oions = s.oracle
+        c_all, ophi, phiM, mm = s.oracle_fields
+        emi = create_solver_emi(s.a_emi, s.L_emi, phi, [], subs, None, p=s.p_emi, direct=False)
+        knp = create_solver_knp(s.a_knp, s.L_knp, c, [], subs, None, p=s.p_knp)
         A, b = emi.assemble()
         Ak, bk = knp.assemble()
         Ao, Po, bo = o.assemble_emi(P, params, oions, c_all, phiM, mm, splitting_scheme=splitting)
