@@ -1036,11 +1036,14 @@ int knpemi_dg_solve_emi(knpemi_dg* h, double rtol, double atol, int maxit, int* 
  * solves become solves of the global systems exactly as knpemi_set_distributed arranges for the CG path -- owned rows
  * only, halo of every SpMV argument, all-reduced dot products, per-rank auxiliary-space AMG.  `owned`: one byte per local
  * broken dof, 1 = dof of an owned cell (NULL: back to single-rank solves); vector orders for `halo`: KNPEMI_B_EMI one value
- * per dof, KNPEMI_B_KNP [solved ion][dof].  knpemi_dg_solver_handle returns the knpemi_handle the solves run on, for
- * knpemi_vec_gather / knpemi_vec_scatter in the halo hook (NULL on error). */
+ * per dof, KNPEMI_B_KNP [solved ion][dof]. */
 int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, void* reduce_buf_dev, knpemi_allreduce_fn allreduce,
                               knpemi_halo_fn halo, void* ctx);
-void* knpemi_dg_solver_handle(knpemi_dg* h);
+/* For the halo hook: knpemi_vec_gather / knpemi_vec_scatter on the DG handle's stream -- buf[i] = vec[idx[i]], and
+ * vec[idx[i]] = buf[i], over the n entries of idx (doubles and int32 in device memory).  n == 0 launches nothing;
+ * KNPEMI_EINVAL for a null handle, n < 0, or a null pointer with n > 0. */
+int knpemi_dg_vec_gather(knpemi_dg* h, const void* vec_dev, const int32_t* idx_dev, int n, void* buf_dev);
+int knpemi_dg_vec_scatter(knpemi_dg* h, void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev);
 int knpemi_dg_solve_knp(knpemi_dg* h, double rtol, double atol, int maxit, int* iters, double* relres, int update);
 int knpemi_dg_get_solution(knpemi_dg* h, double* c_host);
 /* on != 0: both solves start from 2 x_n - x_(n-1) (the last two solutions) instead of x_n, as knpemi_extrapolate_guess

@@ -205,8 +205,8 @@ extern "C" int knpemi_comm_set_vector_plan(knpemi_handle* h, int which, const in
 // knpemi_allreduce_fn with ctx = the handle: sums the first n doubles of the registered reduction buffer
 extern "C" int knpemi_comm_allreduce_hook(void* ctx, int n) {
   knpemi_handle* h = static_cast<knpemi_handle*>(ctx);
-  if (!h || !h->dist.d_red) return KNPEMI_EINVAL;
-  return knpemi_comm_allreduce(h, h->dist.d_red, n);
+  if (!h || !h->solver.dist.d_red) return KNPEMI_EINVAL;
+  return knpemi_comm_allreduce(h, h->solver.dist.d_red, n);
 }
 
 // knpemi_halo_fn with ctx = the handle: ghost refresh of a solver vector through the registered plan

@@ -225,8 +225,8 @@ void kn_amg_free(KnAmg& G) {
 // Build the hierarchy for the n x n device CSR (rowptr, colind, vals).  `singular`: the operator has the
 // constant null space (EMI).
 // host copy of the device CSR, ordered after everything the handle's stream holds
-static int amg_fetch(knpemi_handle* h, int n, const int* d_rowptr, const int* d_colind, const double* d_vals, HostCsr& A) {
-  hipStream_t st = h->stream;
+static int amg_fetch(KnSolver& sv, int n, const int* d_rowptr, const int* d_colind, const double* d_vals, HostCsr& A) {
+  hipStream_t st = sv.own->stream;
   A.n = A.m = n;
   A.rp.resize(n + 1);
   if (int rc = kn_to_host(st, A.rp.data(), d_rowptr, (size_t)n + 1)) return rc;
@@ -236,18 +236,18 @@ static int amg_fetch(knpemi_handle* h, int n, const int* d_rowptr, const int* d_
   return kn_to_host(st, A.v.data(), d_vals, (size_t)nnz);
 }
 
-static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
+static int amg_build(KnSolver& sv, KnAmg& G, HostCsr&& A, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
                      bool singular, const uint8_t* h_owned, bool background);
 
 void kn_amg_async_join(KnAmg& G);
-int kn_amg_setup(knpemi_handle* h, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
+int kn_amg_setup(KnSolver& sv, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
                  bool singular, const uint8_t* h_owned) {
   kn_amg_async_join(G);       // a background rebuild of the hierarchy this call replaces ends first
   G.rebuild_wanted = false;
   kn_amg_free(G);
   HostCsr A;
-  if (int rc = amg_fetch(h, n, d_rowptr, d_colind, d_vals, A)) return rc;
-  return amg_build(h, G, std::move(A), n, d_rowptr, d_colind, d_vals, singular, h_owned, false);
+  if (int rc = amg_fetch(sv, n, d_rowptr, d_colind, d_vals, A)) return rc;
+  return amg_build(sv, G, std::move(A), n, d_rowptr, d_colind, d_vals, singular, h_owned, false);
 }
 
 // ---- rebuild of an aged hierarchy in the background ---------------------------------------------------------------
@@ -272,24 +272,24 @@ void kn_amg_async_join(KnAmg& G) {
 
 // Called at the head of a solve when G.rebuild_wanted: starts the background build, or swaps a finished one in.  Returns
 // KNPEMI_OK and leaves G usable in every case.
-int kn_amg_rebuild_step(knpemi_handle* h, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
+int kn_amg_rebuild_step(KnSolver& sv, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
                         bool singular) {
   if (!G.async) G.async = new KnAmgAsync();
   KnAmgAsync& a = *G.async;
   const int st = a.state.load();
   if (st == 0) {
     HostCsr A;
-    if (int rc = amg_fetch(h, n, d_rowptr, d_colind, d_vals, A)) return rc;
+    if (int rc = amg_fetch(sv, n, d_rowptr, d_colind, d_vals, A)) return rc;
     // the new hierarchy takes the configuration of the old one (copy), none of its levels
     a.next = KnAmg();
     a.next.cfg = G.cfg;
     a.next.its_last = G.its_last; a.next.builds = G.builds;
     a.state.store(1);
     if (a.th.joinable()) a.th.join();
-    const int device = h->device;
-    a.th = std::thread([h, &a, device, n, d_rowptr, d_colind, d_vals, singular](HostCsr Ah) {
+    const int device = sv.own->device;
+    a.th = std::thread([&sv, &a, device, n, d_rowptr, d_colind, d_vals, singular](HostCsr Ah) {
       int rc = hipSetDevice(device) == hipSuccess ? KNPEMI_OK : KNPEMI_EHIP;
-      if (!rc) rc = amg_build(h, a.next, std::move(Ah), n, d_rowptr, d_colind, d_vals, singular, nullptr, true);
+      if (!rc) rc = amg_build(sv, a.next, std::move(Ah), n, d_rowptr, d_colind, d_vals, singular, nullptr, true);
       if (rc) { a.error = knpemi_last_error(); kn_amg_free(a.next); }
       a.state.store(rc ? 3 : 2);
     }, std::move(A));
@@ -313,9 +313,9 @@ int kn_amg_rebuild_step(knpemi_handle* h, KnAmg& G, int n, const int* d_rowptr, 
   return KNPEMI_OK;
 }
 
-static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
+static int amg_build(KnSolver& sv, KnAmg& G, HostCsr&& A_in, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
                      bool singular, const uint8_t* h_owned, bool background) {
-  hipStream_t st = h->stream;
+  hipStream_t st = sv.own->stream;
   HostCsr A = std::move(A_in);
   if (h_owned) {
     // partitioned problem: the hierarchy is built for this rank's diagonal block -- couplings between owned and
@@ -339,6 +339,9 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
       }
 
   const double theta = G.cfg.theta;
+  // overrides of the owner's choices, read at every build: KNPEMI_AMG_APART, KNPEMI_AMG_FILTER
+  const bool apart = getenv("KNPEMI_AMG_APART") ? atoi(getenv("KNPEMI_AMG_APART")) != 0 : G.cfg.positive_conflict;
+  const double filter_theta = getenv("KNPEMI_AMG_FILTER") ? atof(getenv("KNPEMI_AMG_FILTER")) : G.cfg.filter_theta;
   const bool verbose = getenv("KNPEMI_AMG_VERBOSE") != nullptr;
   const auto t_start = std::chrono::steady_clock::now();
   // fused cycle: one level fewer is worth more than a cheaper coarsest solve (every level costs two launches per cycle)
@@ -410,7 +413,7 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
       // a threshold that leaves (almost) no strong connections stalls the coarsening: relax it for this level
       double th = theta;
       for (int attempt = 0; attempt < 6; ++attempt, th = attempt == 5 ? 0.0 : 0.5 * th) {
-        na = G.cfg.positive_conflict ? aggregate_apart(cur, d, th, 0.2, agg) : aggregate(cur, d, th, G.cfg.negative_strength, agg);
+        na = apart ? aggregate_apart(cur, d, th, 0.2, agg) : aggregate(cur, d, th, G.cfg.negative_strength, agg);
         if (na < cur.n * 0.7) break;
       }
     }
@@ -436,7 +439,7 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
     // given aggregates (auxiliary space): the piecewise-constant prolongator IS the embedding of that space (every broken
     // dof takes the value of its vertex); smoothing it would only widen the stencil of every coarser operator
     const bool given = l == 0 && G.cfg.first_na > 0 && (int)G.cfg.first_agg.size() == cur.n;
-    HostCsr P = smoothed_prolongator(cur, d, agg, na, given && G.cfg.first_tentative ? 0.0 : L.omega, G.cfg.filter_theta);
+    HostCsr P = smoothed_prolongator(cur, d, agg, na, given && G.cfg.first_tentative ? 0.0 : L.omega, filter_theta);
     HostCsr R = transpose(P);
     L.nc = na;
     L.p_row = std::max(1, (int)(P.ci.size() / (size_t)P.n));
@@ -492,22 +495,22 @@ static int amg_build(knpemi_handle* h, KnAmg& G, HostCsr&& A_in, int n, const in
 // pre-smoothed iterate and receives the coarse correction, t the residual on the way down and the
 // post-smoothed result on the way up (read by the parent's prolongation): 4 launches per level, no copies,
 // fixed buffers (the sequence can be captured in a hipGraph).
-int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* dinv0, const double* r, double* scratch,
+int kn_amg_apply(KnSolver& sv, KnAmg& G, const double* vals, const double* dinv0, const double* r, double* scratch,
                  double* out) {
-  hipStream_t st = h->stream;
+  hipStream_t st = sv.own->stream;
   const int nl = (int)G.lev.size();
-  if (G.cycle_ok) return kn_fused_subcycle(h, G, 0, r, out);
+  if (G.cycle_ok) return kn_fused_subcycle(sv, G, 0, r, out);
   if (G.sub_fused_ok && G.cfg.block > 0) {
     // finest level: block-Jacobi sweeps and residuals here, everything below through the merged transfer operators
     KnAmgLevel& L = G.lev[0];
     auto residual = [&](const double* x, double* y) {
-      if (h->bcols.bcol) launch_block_spmv<double>(st, h->bcols, L.n, L.A.rp, vals, x, r, y, nullptr);
+      if (sv.bcols.bcol) launch_block_spmv<double>(st, sv.bcols, L.n, L.A.rp, vals, x, r, y, nullptr);
       else launch_spmv<M_RES>(st, L.n, L.avg_row, L.A.rp, L.A.ci, vals, x, r, nullptr, 0.0, y);
     };
     block_apply(st, G, L.n, r, nullptr, scratch);                       // x = w B^-1 r
     residual(scratch, L.t);                                             // t = r - A x
     launch_spmv<M_AX>(st, L.nc, L.r_row, L.R.rp, L.R.ci, L.R.v, L.t, nullptr, nullptr, 0.0, G.lev[1].r);
-    if (int e = kn_fused_subcycle(h, G, 1)) return e;
+    if (int e = kn_fused_subcycle(sv, G, 1)) return e;
     launch_spmv<M_ADD>(st, L.n, L.p_row, L.P.rp, L.P.ci, L.P.v, G.lev[1].x, nullptr, nullptr, 0.0, scratch);
     residual(scratch, L.t);
     block_apply(st, G, L.n, L.t, scratch, out);                         // out = x + w B^-1 (r - A x)
@@ -532,7 +535,7 @@ int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* d
     }
     if (l == 0 && G.cfg.block > 0) {   // x = w B^-1 r, t = r - A x
       block_apply(st, G, L.n, rl, nullptr, xl);
-      if (h->bcols.bcol) launch_block_spmv<double>(st, h->bcols, L.n, L.A.rp, Av, xl, rl, L.t, nullptr);
+      if (sv.bcols.bcol) launch_block_spmv<double>(st, sv.bcols, L.n, L.A.rp, Av, xl, rl, L.t, nullptr);
       else launch_spmv<M_RES>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, xl, rl, nullptr, 0.0, L.t);
     } else launch_spmv<M_PRE>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, nullptr, rl, dinv, L.omega, L.t, xl);
     launch_spmv<M_AX>(st, L.nc, L.r_row, L.R.rp, L.R.ci, L.R.v, L.t, nullptr, nullptr, 0.0, G.lev[l + 1].r);
@@ -545,7 +548,7 @@ int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* d
     const double* dinv = l == 0 ? dinv0 : L.dinv;
     launch_spmv<M_ADD>(st, L.n, L.p_row, L.P.rp, L.P.ci, L.P.v, G.lev[l + 1].t, nullptr, nullptr, 0.0, xl);
     if (l == 0 && G.cfg.block > 0) {   // out = x + w B^-1 (r - A x); the level's t is free again
-      if (h->bcols.bcol) launch_block_spmv<double>(st, h->bcols, L.n, L.A.rp, Av, xl, rl, L.t, nullptr);
+      if (sv.bcols.bcol) launch_block_spmv<double>(st, sv.bcols, L.n, L.A.rp, Av, xl, rl, L.t, nullptr);
       else launch_spmv<M_RES>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, xl, rl, nullptr, 0.0, L.t);
       block_apply(st, G, L.n, L.t, xl, out);
     } else launch_spmv<M_JAC>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, xl, rl, dinv, L.omega, l == 0 ? out : L.t);
@@ -553,17 +556,17 @@ int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* d
   return KNPEMI_OK;
 }
 
-int kn_amg_refresh(knpemi_handle* h, KnAmg& G, const double* vals) {
+int kn_amg_refresh(KnSolver& sv, KnAmg& G, const double* vals) {
   if (!G.built || G.cfg.block <= 0 || G.lev.empty() || G.lev[0].nc == 0) return KNPEMI_OK;
   const KnAmgLevel& L = G.lev[0];
   const int nb = L.n / G.cfg.block;
   dim3 g(((size_t)nb * 4 + 255) / 256), g8(((size_t)nb * 8 + 255) / 256);
-  const KnBlockCols& B = h->bcols;
+  const KnBlockCols& B = sv.bcols;
   const int* bc = (B.bcol && B.nv == G.cfg.block) ? B.bcol : nullptr;
   const int cps = bc ? B.n / B.nv : 1;
-  if (G.cfg.block == 3) hipLaunchKernelGGL(amg_block_inv_kernel<3>, g, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
-  else if (G.cfg.block == 4) hipLaunchKernelGGL(amg_block_inv_kernel<4>, g, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
-  else if (G.cfg.block == 8) hipLaunchKernelGGL(amg_block_inv_kernel<8>, g8, dim3(256), 0, h->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
+  if (G.cfg.block == 3) hipLaunchKernelGGL(amg_block_inv_kernel<3>, g, dim3(256), 0, sv.own->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
+  else if (G.cfg.block == 4) hipLaunchKernelGGL(amg_block_inv_kernel<4>, g, dim3(256), 0, sv.own->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
+  else if (G.cfg.block == 8) hipLaunchKernelGGL(amg_block_inv_kernel<8>, g8, dim3(256), 0, sv.own->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
   else { kn_set_error("AMG: smoother blocks of 3, 4 or 8 unknowns only"); return KNPEMI_EINVAL; }
   return kn_launch_check("amg_block_inv_kernel");
 }

@@ -1586,21 +1586,21 @@ int kn_launch_halo(knpemi_handle* h, int kind, int pack, const int32_t* idx, int
   return kn_launch_check("halo_kernel");
 }
 
-int kn_launch_field_scatter(knpemi_handle* h, const double* src, double* dst, int n, int dst_stride) {
+int kn_launch_field_scatter(hipStream_t st, const double* src, double* dst, int n, int dst_stride) {
   if (n == 0) return KNPEMI_OK;
-  hipLaunchKernelGGL(scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, src, dst, n, dst_stride);
+  hipLaunchKernelGGL(scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, dst, n, dst_stride);
   return kn_launch_check("scatter_kernel");
 }
 
-int kn_launch_field_gather(knpemi_handle* h, const double* src, int src_stride, double* dst, int n) {
+int kn_launch_field_gather(hipStream_t st, const double* src, int src_stride, double* dst, int n) {
   if (n == 0) return KNPEMI_OK;
-  hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, src, src_stride, dst, n);
+  hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, src_stride, dst, n);
   return kn_launch_check("gather_kernel");
 }
 
-int kn_launch_vec_index(knpemi_handle* h, double* vec, const int32_t* idx, int n, double* buf, int gather) {
+int kn_launch_vec_index(hipStream_t st, double* vec, const int32_t* idx, int n, double* buf, int gather) {
   if (n == 0) return KNPEMI_OK;
-  hipLaunchKernelGGL(vec_index_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, vec, idx, n, buf, gather);
+  hipLaunchKernelGGL(vec_index_kernel, dim3((n + 255) / 256), dim3(256), 0, st, vec, idx, n, buf, gather);
   return kn_launch_check("vec_index_kernel");
 }
 

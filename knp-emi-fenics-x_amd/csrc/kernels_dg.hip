@@ -720,12 +720,11 @@ struct knpemi_dg : KnDevice {
   double* d_params = nullptr;
   unsigned long long* d_stats = nullptr;
   const void* d_coef = nullptr;
-  // device solves (knpemi_dg_solve_emi / knpemi_dg_solve_knp): the Krylov + AMG code of the CG path run on the DG
-  // systems through a handle that only carries what the solvers read
+  // device solves (knpemi_dg_solve_emi / knpemi_dg_solve_knp): the Krylov + AMG code of the CG path on the DG systems
   std::vector<int> aux_of;         // continuous P1 dof (sub-domain, mesh vertex) of every broken dof
   int n_aux = 0;
-  knpemi_handle* sol = nullptr;
-  double* d_csol = nullptr;        // [K-1][n_dofs] solved concentrations
+  KnSolver solver{this};           // views and configuration: dg_solver, on first use
+  double* d_csol = nullptr;        // [K-1][n_dofs] solved concentrations; != NULL: the solver is set up
   int extrapolate = 0;             // knpemi_dg_set_extrapolation
 };
 
@@ -772,12 +771,7 @@ int launch_knp(knpemi_dg* h, int flags) {
 extern "C" void knpemi_dg_destroy(knpemi_dg* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  kn_device_release(h);
-  if (h->sol) {   // borrows the stream, owns its solver state and what the solves allocated
-    kn_solver_free(h->sol);
-    kn_free_all(h->sol->allocs);
-    delete h->sol;
-  }
+  kn_solver_free(h->solver);
   kn_device_close(h);
   delete h;
 }
@@ -1211,21 +1205,22 @@ namespace {
 
 // Given aggregates of the finest level of both hierarchies: `agg` (na of them) over the n dofs for the potential, one copy
 // per solved ion for the concentrations.  KNPEMI_DG_PLAIN_AMG=1: none, every level is aggregated by strength.
-void dg_first_aggregates(knpemi_handle* s, const std::vector<int>& agg, int na, int KS, int n) {
+void dg_first_aggregates(KnSolver& s, const std::vector<int>& agg, int na, int KS, int n) {
   if (getenv("KNPEMI_DG_PLAIN_AMG")) return;
-  s->amg_emi.cfg.first_agg = agg;
-  s->amg_emi.cfg.first_na = na;
-  std::vector<int>& ka = s->amg_knp.cfg.first_agg;
+  s.amg_emi.cfg.first_agg = agg;
+  s.amg_emi.cfg.first_na = na;
+  std::vector<int>& ka = s.amg_knp.cfg.first_agg;
   ka.resize((size_t)KS * n);
   for (int k = 0; k < KS; ++k)
     for (int i = 0; i < n; ++i) ka[(size_t)k * n + i] = k * na + agg[i];
-  s->amg_knp.cfg.first_na = KS * na;
+  s.amg_knp.cfg.first_na = KS * na;
 }
 
-// The solver handle of a DG problem: stream, systems and the potential component of the dof records (same 64-byte
-// layout as the CG vertex records), nothing else.
-int dg_solver(knpemi_dg* h, knpemi_handle** out) {
-  if (h->sol) { *out = h->sol; return KNPEMI_OK; }
+// The solver of a DG problem, set up on first use: the two systems, the potential component of the dof records (same
+// 64-byte layout as the CG vertex records) and the AMG choices.  The concentrations are solved in d_csol's own order and
+// the potential is written back by the solver's own launch: no hooks.
+int dg_solver(knpemi_dg* h) {
+  if (h->d_csol) return KNPEMI_OK;
   const DgDev& D = h->dev;
   const int n = D.n_dof, KS = h->K - 1;
   if ((int64_t)KS * D.nnz >= ((int64_t)1 << 31) - 64)
@@ -1242,19 +1237,7 @@ int dg_solver(knpemi_dg* h, knpemi_handle** out) {
   const int *d_krp = nullptr, *d_kci = nullptr;
   if ((rc = kn_upload(h->allocs, krp, &d_krp))) return rc;
   if ((rc = kn_upload(h->allocs, kci, &d_kci))) return rc;
-  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)KS * n, &h->d_csol))) return rc;
-  auto* s = new knpemi_handle();
-  s->device = h->device;
-  s->stream = s->cur = h->stream;
-  s->K = h->K; s->n_sub = h->n_sub;
-  s->dev.Ntot = n;
-  s->dev.VR = D.rec;
-  s->dev.rowptr = D.rowptr; s->dev.colind = h->d_colind;
-  s->dev.A_emi = D.A_emi; s->dev.b_emi = D.b_emi;
-  s->dev.krowptr = d_krp; s->dev.kcolind = d_kci;
-  s->dev.A_knp = D.A_knp; s->dev.b_knp = D.b_knp;
-  s->dev.csol = h->d_csol;
-  s->plain_knp = true;
+  KnSolver& s = h->solver;
   // block columns of the systems (the cell and its facet neighbours, increasing, as the CSR pattern was built): the solver's
   // SpMVs read these instead of one column index per entry (block_spmv.h); KNPEMI_DG_NO_BLOCK_SPMV=1 keeps the CSR kernels
   if (!getenv("KNPEMI_DG_NO_BLOCK_SPMV")) {
@@ -1268,7 +1251,7 @@ int dg_solver(knpemi_dg* h, knpemi_handle** out) {
     }
     const int* d_bcol = nullptr;
     if ((rc = kn_upload(h->allocs, bcol, &d_bcol))) return rc;
-    s->bcols.bcol = d_bcol; s->bcols.nv = NV; s->bcols.nbmax = nbmax; s->bcols.n = n;
+    s.bcols.bcol = d_bcol; s.bcols.nv = NV; s.bcols.nbmax = nbmax; s.bcols.n = n;
   }
   KnAmgConfig cfg;
   cfg.block = h->NV;                                 // block-Jacobi smoothing over the dofs of a cell
@@ -1277,27 +1260,36 @@ int dg_solver(knpemi_dg* h, knpemi_handle** out) {
   cfg.split_first = !getenv("KNPEMI_DG_AUX_UNSPLIT");
   cfg.first_tentative = !getenv("KNPEMI_DG_AUX_SMOOTHED");
   cfg.positive_conflict = !getenv("KNPEMI_DG_PLAIN_AGGREGATION");
-  cfg.filter_theta = 0.02;                           // (as kernels_krylov.hip)
+  cfg.filter_theta = 0.02;                           // (as the CG path: kn_solver_attach)
   cfg.sub_fused = !getenv("KNPEMI_DG_NO_SUBCYCLE");  // merged transfer operators below the finest level
-  if (const char* ft = getenv("KNPEMI_AMG_FILTER")) cfg.filter_theta = atof(ft);
   if (const char* th = getenv("KNPEMI_DG_THETA")) cfg.theta = atof(th);
   if (getenv("KNPEMI_DG_POINT_JACOBI")) cfg.block = 0;
-  s->amg_emi.cfg = s->amg_knp.cfg = cfg;
+  s.amg_emi.cfg = s.amg_knp.cfg = cfg;
   dg_first_aggregates(s, h->aux_of, h->n_aux, KS, n);
-  h->sol = s;
-  *out = s;
+  s.ks = KS;
+  s.emi = {n, D.rowptr, h->d_colind, D.A_emi, D.b_emi};
+  s.knp = {KS * n, d_krp, d_kci, D.A_knp, D.b_knp};
+  s.phi = D.rec + 7;
+  s.phi_stride = KN_REC;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)KS * n, &s.csol))) return rc;
+  h->d_csol = s.csol;                                // (last: marks the solver as set up)
   return KNPEMI_OK;
 }
 
 }  // namespace
 
-// The solver handle of a DG problem (a knpemi_handle that carries the stream, the two CSR systems and the dof records):
-// knpemi_vec_gather / knpemi_vec_scatter take it for the ghost refresh of a solver vector on a cell partition.
-extern "C" void* knpemi_dg_solver_handle(knpemi_dg* h) {
-  if (!h) { kn_set_error("knpemi_dg_solver_handle: null handle"); return nullptr; }
-  if (hipSetDevice(h->device) != hipSuccess) return nullptr;
-  knpemi_handle* s = nullptr;
-  return dg_solver(h, &s) == KNPEMI_OK ? s : nullptr;
+// Ghost refresh of a solver vector on a cell partition (knpemi.dg.DGSlab): knpemi_vec_gather / knpemi_vec_scatter on the
+// DG handle's stream
+extern "C" int knpemi_dg_vec_gather(knpemi_dg* h, const void* vec_dev, const int32_t* idx_dev, int n, void* buf_dev) {
+  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_vec_gather: bad argument");
+  KN_HIP(hipSetDevice(h->device));
+  return kn_launch_vec_index(h->stream, static_cast<double*>(const_cast<void*>(vec_dev)), idx_dev, n, static_cast<double*>(buf_dev), 1);
+}
+
+extern "C" int knpemi_dg_vec_scatter(knpemi_dg* h, void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev) {
+  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_vec_scatter: bad argument");
+  KN_HIP(hipSetDevice(h->device));
+  return kn_launch_vec_index(h->stream, static_cast<double*>(vec_dev), idx_dev, n, static_cast<double*>(const_cast<void*>(buf_dev)), 0);
 }
 
 // Cell partition (knpemi.dg.DGSlab): knpemi_dg_solve_emi / knpemi_dg_solve_knp become solves of the GLOBAL systems, as
@@ -1309,13 +1301,10 @@ extern "C" int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, voi
                                          knpemi_halo_fn halo, void* ctx) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_distributed: null handle");
   KN_HIP(hipSetDevice(h->device));
-  knpemi_handle* s = nullptr;
-  int rc = dg_solver(h, &s);
+  int rc = dg_solver(h);
   if (rc) return rc;
-  KnDist& d = s->dist;
+  KnSolver& s = h->solver;
   const int n = h->dev.n_dof, KS = h->K - 1;
-  s->amg_emi.built = false;      // the preconditioner changes with the ownership
-  s->amg_knp.built = false;
   // first aggregates of the auxiliary space: all broken dofs at one (sub-domain, mesh vertex) -- on a partition the dofs of
   // ghost cells (identity rows of the rank's diagonal block) get aggregates of their own
   std::vector<int> agg((size_t)n);
@@ -1339,29 +1328,13 @@ extern "C" int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, voi
     agg = h->aux_of;
   }
   dg_first_aggregates(s, agg, na, KS, n);
-  if (!owned) { d.on = false; return KNPEMI_OK; }
-  if (!reduce_buf_dev || !allreduce || !halo)
-    return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_distributed: reduction buffer and both communication hooks are required");
-  d.h_owned_emi.assign(owned, owned + n);
-  d.h_owned_knp.resize((size_t)KS * n);
-  for (int k = 0; k < KS; ++k) std::copy(owned, owned + n, d.h_owned_knp.begin() + (size_t)k * n);
-  const uint8_t* p = nullptr;
-  if ((rc = kn_upload(h->allocs, d.h_owned_emi, &p))) return rc;
-  d.d_owned_emi = const_cast<uint8_t*>(p);
-  if ((rc = kn_upload(h->allocs, d.h_owned_knp, &p))) return rc;
-  d.d_owned_knp = const_cast<uint8_t*>(p);
-  d.d_red = static_cast<double*>(reduce_buf_dev);
-  d.allreduce = allreduce; d.halo = halo; d.ctx = ctx;
-  double cnt = 0.0;   // owned dofs over all ranks (mean of the constant null space)
-  for (int i = 0; i < n; ++i) cnt += owned[i] ? 1.0 : 0.0;
-  KN_HIP(hipMemcpyAsync(d.d_red, &cnt, sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (allreduce(ctx, 1)) return kn_fail(KNPEMI_EHIP, "knpemi_dg_set_distributed: allreduce hook failed");
-  KN_HIP(hipMemcpyAsync(&cnt, d.d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  d.n_owned_global = cnt;
-  d.nc = 0;            // (no cross-rank coarse space for the DG systems)
-  d.on = true;
-  return KNPEMI_OK;
+  std::vector<uint8_t> owned_knp;   // the concentration system's order: [solved ion][dof]
+  if (owned) {
+    owned_knp.resize((size_t)KS * n);
+    for (int k = 0; k < KS; ++k) std::copy(owned, owned + n, owned_knp.begin() + (size_t)k * n);
+  }
+  s.dist.nc = 0;       // (no cross-rank coarse space for the DG systems)
+  return kn_dist_enable(s, owned, std::move(owned_knp), reduce_buf_dev, allreduce, halo, ctx, "knpemi_dg_set_distributed");
 }
 
 // Device solves of the two DG systems (pdeSolver.py:24-35,74-78,99-110 with the iterative options): CG on the
@@ -1373,11 +1346,10 @@ extern "C" int knpemi_dg_set_distributed(knpemi_dg* h, const uint8_t* owned, voi
 extern "C" int knpemi_dg_solve_emi(knpemi_dg* h, double rtol, double atol, int maxit, int* iters, double* relres) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_solve_emi: null handle");
   KN_HIP(hipSetDevice(h->device));
-  knpemi_handle* s = nullptr;
-  int rc = dg_solver(h, &s);
+  int rc = dg_solver(h);
   if (rc) return rc;
-  if (h->extrapolate && (rc = kn_extrapolate_guess(s, KNPEMI_B_EMI))) return rc;   // phi <- 2 phi_n - phi_(n-1)
-  return kn_solve_emi(s, rtol, atol, maxit, iters, relres);
+  if (h->extrapolate && (rc = kn_extrapolate_guess(h->solver, KNPEMI_B_EMI))) return rc;   // phi <- 2 phi_n - phi_(n-1)
+  return kn_solve_emi(h->solver, rtol, atol, maxit, iters, relres);
 }
 
 // Initial guesses of the two solves: the linear extrapolation 2 x_n - x_(n-1) of the last two solutions instead of the
@@ -1385,7 +1357,8 @@ extern "C" int knpemi_dg_solve_emi(knpemi_dg* h, double rtol, double atol, int m
 extern "C" int knpemi_dg_set_extrapolation(knpemi_dg* h, int on) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_set_extrapolation: null handle");
   h->extrapolate = on ? 1 : 0;
-  if (h->sol) { h->sol->guess_have[0] = -1; h->sol->guess_have[1] = 0; }
+  h->solver.guess_have[0] = -1;   // the histories start over (kn_extrapolate_guess)
+  h->solver.guess_have[1] = 0;
   return KNPEMI_OK;
 }
 
@@ -1393,14 +1366,13 @@ extern "C" int knpemi_dg_solve_knp(knpemi_dg* h, double rtol, double atol, int m
   if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_solve_knp: null handle");
   if (update && !h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_solve_knp: knpemi_dg_set_params has not been called");
   KN_HIP(hipSetDevice(h->device));
-  knpemi_handle* s = nullptr;
-  int rc = dg_solver(h, &s);
+  int rc = dg_solver(h);
   if (rc) return rc;
   const int n = h->dev.n_dof;
   for (int k = 0; k < h->K - 1; ++k)   // initial guess: the previous concentrations (ksp_initial_guess_nonzero)
-    if ((rc = kn_launch_field_gather(s, h->dev.rec + KN_CSLOT(k), KN_REC, h->d_csol + (size_t)k * n, n))) return rc;
-  if (h->extrapolate && (rc = kn_extrapolate_guess(s, KNPEMI_B_KNP))) return rc;
-  if ((rc = kn_solve_knp(s, rtol, atol, maxit, iters, relres))) return rc;
+    if ((rc = kn_launch_field_gather(h->stream, h->dev.rec + KN_CSLOT(k), KN_REC, h->d_csol + (size_t)k * n, n))) return rc;
+  if (h->extrapolate && (rc = kn_extrapolate_guess(h->solver, KNPEMI_B_KNP))) return rc;
+  if ((rc = kn_solve_knp(h->solver, rtol, atol, maxit, iters, relres))) return rc;
   if (update) return knpemi_dg_update(h, h->d_csol, 1);
   return KNPEMI_OK;
 }

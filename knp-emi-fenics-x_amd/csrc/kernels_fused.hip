@@ -710,7 +710,7 @@ __global__ void bi_restart_kernel(int n, double* __restrict__ rhat, const double
 }
 
 struct Loop {
-  knpemi_handle* h;
+  KnSolver& sv;
   KnAmg& G;
   const KnFusedSys& S;
   Red red;
@@ -798,8 +798,8 @@ struct Loop {
 // G.lev[l0].r, result in G.lev[l0].x.  The kernels are those of the fused loops; their early-out flag reads a zeroed
 // scalar block (G.zero_sc), no dot products are involved.  l0 = 0 (the rank-local cycle of a partitioned problem): input
 // r0, result out0, the finest operator is the frozen one the hierarchy was built from.
-int kn_fused_subcycle(knpemi_handle* h, KnAmg& G, int l0, const double* r0, double* out0) {
-  hipStream_t st = h->stream;
+int kn_fused_subcycle(KnSolver& sv, KnAmg& G, int l0, const double* r0, double* out0) {
+  hipStream_t st = sv.own->stream;
   const Red red{G.zero_sc, nullptr};
   const int nl = (int)G.lev.size();
   for (int l = l0; l + 1 < nl; ++l) {
@@ -833,12 +833,12 @@ int kn_fused_subcycle(knpemi_handle* h, KnAmg& G, int l0, const double* r0, doub
 namespace {
 
 // scalars + partial-sum arrays of the fused loops
-int ensure_partials(knpemi_handle* h) {
+int ensure_partials(KnSolver& sv) {
   const size_t need = (size_t)P_N * KN_PB;
-  if (h->fused_part_n >= need) return KNPEMI_OK;
-  if (int rc = kn_alloc(h->allocs, need, &h->fused_part)) return rc;
-  KN_HIP(hipMemsetAsync(h->fused_part, 0, need * sizeof(double), h->stream));
-  h->fused_part_n = need;
+  if (sv.fused_part_n >= need) return KNPEMI_OK;
+  if (int rc = kn_alloc(sv.own->allocs, need, &sv.fused_part)) return rc;
+  KN_HIP(hipMemsetAsync(sv.fused_part, 0, need * sizeof(double), sv.own->stream));
+  sv.fused_part_n = need;
   return KNPEMI_OK;
 }
 
@@ -866,20 +866,20 @@ __global__ void publish_kernel(Publish p, const double* __restrict__ sc) {
   if (threadIdx.x == 0 && blockIdx.x == 0) publish_state(p, sc);
 }
 
-int ensure_publish(knpemi_handle* h, Publish* out) {
-  if (!h->pub_host) {
+int ensure_publish(KnSolver& sv, Publish* out) {
+  if (!sv.pub_host) {
     void* p = nullptr;
     KN_HIP(hipHostMalloc(&p, 64 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
     std::memset(p, 0, 64 * sizeof(double));
     void* d = nullptr;
     KN_HIP(hipHostGetDevicePointer(&d, p, 0));
-    if (int rc = kn_zeros(h->allocs, h->stream, 1, &h->pub_count)) return rc;
-    h->pub_host = static_cast<double*>(p);
-    h->pub_host_dev = static_cast<double*>(d);
-    h->pub_expected = 0;
+    if (int rc = kn_zeros(sv.own->allocs, sv.own->stream, 1, &sv.pub_count)) return rc;
+    sv.pub_host = static_cast<double*>(p);
+    sv.pub_host_dev = static_cast<double*>(d);
+    sv.pub_expected = 0;
   }
-  out->host_dev = h->pub_host_dev;
-  out->count = h->pub_count;
+  out->host_dev = sv.pub_host_dev;
+  out->count = sv.pub_count;
   return KNPEMI_OK;
 }
 
@@ -889,15 +889,15 @@ bool publish_usable() {
 }
 
 // enqueue the publication of the state (the caller counts it) ...
-void enqueue_publish(knpemi_handle* h, const Publish& p, const double* sc_dev) {
-  hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, h->stream, p, sc_dev);
+void enqueue_publish(KnSolver& sv, const Publish& p, const double* sc_dev) {
+  hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, sv.own->stream, p, sc_dev);
 }
 
-// ... and wait for publication number h->pub_expected
-int read_state(knpemi_handle* h, const double* sc_dev, double* host, bool published) {
+// ... and wait for publication number sv.pub_expected
+int read_state(KnSolver& sv, const double* sc_dev, double* host, bool published) {
   if (published) {
-    const double want = (double)h->pub_expected;
-    volatile double* seq = h->pub_host + S_NF;
+    const double want = (double)sv.pub_expected;
+    volatile double* seq = sv.pub_host + S_NF;
     const auto t0 = std::chrono::steady_clock::now();
     int spins = 0;
     bool seen = false;
@@ -905,19 +905,19 @@ int read_state(knpemi_handle* h, const double* sc_dev, double* host, bool publis
       if (*seq >= want) { seen = true; break; }
       if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
         // long solves are legitimate (large meshes): keep polling, but let the runtime report a dead stream
-        if (hipStreamQuery(h->stream) != hipErrorNotReady) break;
+        if (hipStreamQuery(sv.own->stream) != hipErrorNotReady) break;
       }
     }
     if (seen) {
       std::atomic_thread_fence(std::memory_order_acquire);
-      for (int i = 0; i < S_NF; ++i) host[i] = const_cast<const volatile double*>(h->pub_host)[i];
+      for (int i = 0; i < S_NF; ++i) host[i] = const_cast<const volatile double*>(sv.pub_host)[i];
       return KNPEMI_OK;
     }
   }
-  if (!h->kry_pinned) KN_HIP(hipHostMalloc(&h->kry_pinned, 64 * sizeof(double), hipHostMallocDefault));
-  KN_HIP(hipMemcpyAsync(h->kry_pinned, sc_dev, S_NF * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < S_NF; ++i) host[i] = static_cast<double*>(h->kry_pinned)[i];
+  if (!sv.kry_pinned) KN_HIP(hipHostMalloc(&sv.kry_pinned, 64 * sizeof(double), hipHostMallocDefault));
+  KN_HIP(hipMemcpyAsync(sv.kry_pinned, sc_dev, S_NF * sizeof(double), hipMemcpyDeviceToHost, sv.own->stream));
+  KN_HIP(hipStreamSynchronize(sv.own->stream));
+  for (int i = 0; i < S_NF; ++i) host[i] = static_cast<double*>(sv.kry_pinned)[i];
   return KNPEMI_OK;
 }
 
@@ -957,9 +957,9 @@ int first_chunk(int last_its, int maxit) {
 // (system, hierarchy build, first / later chunk, number of iterations, parity, tolerances) and replayed afterwards.
 // KNPEMI_NO_GRAPH=1, an active event profile (knpemi_profile brackets record events on the stream) or a partitioned
 // problem (communication hooks): direct launches.
-bool graphs_usable(const knpemi_handle* h) {
+bool graphs_usable(const KnSolver& sv) {
   static const bool off = getenv("KNPEMI_NO_GRAPH") != nullptr || getenv("KNPEMI_FUSED_NO_GRAPH") != nullptr;
-  return !off && h->prof.mask == 0 && !h->dist.on;
+  return !off && sv.own->prof.mask == 0 && !sv.dist.on;
 }
 
 // Graph replay or direct launches?  Which is faster depends on the host: where a launch costs the host 4.4-5 us the ~45
@@ -969,18 +969,18 @@ bool graphs_usable(const knpemi_handle* h) {
 // time the first chunk (enqueue -> state on the host) per enqueued iteration, afterwards the faster one stays.
 // KNPEMI_FUSED_GRAPH=1 / 0 forces the choice.
 struct ModeChoice { bool graph; bool timed; };
-ModeChoice choose_mode(knpemi_handle* h, int sys) {
-  if (!graphs_usable(h)) return {false, false};
+ModeChoice choose_mode(KnSolver& sv, int sys) {
+  if (!graphs_usable(sv)) return {false, false};
   static const char* forced = getenv("KNPEMI_FUSED_GRAPH");
   if (forced) return {atoi(forced) != 0, false};
-  knpemi_handle::FusedMode& m = h->fused_mode[sys];
+  KnSolver::FusedMode& m = sv.fused_mode[sys];
   if (m.decided) return {m.graph, false};
   const int s = m.solves++;
   if (s < 2) return {true, false};            // the graphs get captured and instantiated
   return {(s & 1) == 0, true};
 }
-void record_mode(knpemi_handle* h, int sys, bool graph, double us_per_iteration) {
-  knpemi_handle::FusedMode& m = h->fused_mode[sys];
+void record_mode(KnSolver& sv, int sys, bool graph, double us_per_iteration) {
+  KnSolver::FusedMode& m = sv.fused_mode[sys];
   m.t[graph ? 0 : 1] += us_per_iteration;
   ++m.n[graph ? 0 : 1];
   if (m.n[0] >= 4 && m.n[1] >= 4) {
@@ -996,16 +996,16 @@ uint64_t mix(uint64_t k, uint64_t v) { return (k ^ v) * 0x9E3779B97F4A7C15ull + 
 uint64_t bits(double d) { uint64_t u; memcpy(&u, &d, sizeof u); return u; }
 
 // Enqueue a chunk, or (use_graph) launch its graph, captured at the first use of `key`
-int run_chunk_graph(knpemi_handle* h, uint64_t key, const std::function<int()>& enqueue, bool use_graph) {
+int run_chunk_graph(KnSolver& sv, uint64_t key, const std::function<int()>& enqueue, bool use_graph) {
   if (!use_graph) return enqueue();
-  auto it = h->fused_graphs.find(key);
-  if (it == h->fused_graphs.end()) {
-    if (h->fused_graphs.size() >= 96) kn_fused_graphs_free(h);   // tolerances or hierarchies that keep changing: start over
+  auto it = sv.fused_graphs.find(key);
+  if (it == sv.fused_graphs.end()) {
+    if (sv.fused_graphs.size() >= 96) kn_fused_graphs_free(sv);   // tolerances or hierarchies that keep changing: start over
     hipGraphExec_t exec = nullptr;
-    if (int rc = kn_capture(h, enqueue, &exec)) return rc;
-    it = h->fused_graphs.emplace(key, exec).first;
+    if (int rc = kn_capture(sv, enqueue, &exec)) return rc;
+    it = sv.fused_graphs.emplace(key, exec).first;
   }
-  KN_HIP(hipGraphLaunch(it->second, h->stream));
+  KN_HIP(hipGraphLaunch(it->second, sv.own->stream));
   return KNPEMI_OK;
 }
 
@@ -1019,9 +1019,9 @@ int lanes0(const KnAmg& G) { return G.lev[0].avg_row <= 24 ? 4 : LPR; }
   } while (0)
 
 // The state after a chunk (published by its last kernel, or copied): read and checked for non-finite input and residuals
-int chunk_state(knpemi_handle* h, const KnFusedSys& S, double* sc, bool published, const char* who) {
-  if (published) ++h->pub_expected;
-  if (int rc = read_state(h, S.sc, sc, published)) return rc;
+int chunk_state(KnSolver& sv, const KnFusedSys& S, double* sc, bool published, const char* who) {
+  if (published) ++sv.pub_expected;
+  if (int rc = read_state(sv, S.sc, sc, published)) return rc;
   if (int rc = bad_input(who, sc)) return rc;
   if (!std::isfinite(sc[S_RR])) { kn_set_error(std::string(who) + " broke down (non-finite residual) " + describe(sc)); return KNPEMI_ESOLVE; }
   return KNPEMI_OK;
@@ -1044,15 +1044,15 @@ int finish_solve(KnAmg& G, const double* sc, int it, const char* what, int* iter
 // own configuration), on whether it is the first, on its size and on the parity of k -- nothing else the host holds --, so
 // a replayed chunk needs no host code beyond k += count.  between(sc) runs when a chunk has not ended the solve, before the
 // next one is enqueued.  head_cost: the head's share of the first chunk's time in iterations (choose_mode's timing).
-int fused_chunks(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, int sys, const char* who, const char* what, uint64_t seed,
+int fused_chunks(KnSolver& sv, KnAmg& G, const KnFusedSys& S, int sys, const char* who, const char* what, uint64_t seed,
                  double rtol, double atol, int maxit, int min_it, double head_cost, const std::function<int()>& head,
                  const std::function<int(int, int)>& iterations, const std::function<int()>& tail,
                  const std::function<int(const double*)>& between, int* iters, double* rr_out, double* bb_out) {
   int rc;
   Publish pub{};
   const bool use_pub = publish_usable();
-  if (use_pub && (rc = ensure_publish(h, &pub))) return rc;
-  const ModeChoice mode = choose_mode(h, sys);
+  if (use_pub && (rc = ensure_publish(sv, &pub))) return rc;
+  const ModeChoice mode = choose_mode(sv, sys);
   const auto t_start = std::chrono::steady_clock::now();
   uint64_t base = mix(mix(mix(mix(seed, (uint64_t)(uintptr_t)S.work), (uint64_t)G.builds), bits(rtol)), bits(atol));
   base = mix(mix(base, (uint64_t)S.n), use_pub ? 1 : 0);
@@ -1064,15 +1064,15 @@ int fused_chunks(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, int sys, const
       if (first) if (int e = head()) return e;
       if (int e = iterations(k0, todo)) return e;
       if (int e = tail()) return e;
-      if (use_pub) enqueue_publish(h, pub, S.sc);
+      if (use_pub) enqueue_publish(sv, pub, S.sc);
       return KNPEMI_OK;
     };
-    if ((rc = run_chunk_graph(h, mix(mix(mix(base, first ? 1 : 0), (uint64_t)todo), (uint64_t)(k0 & 1)), chunk, mode.graph)))
+    if ((rc = run_chunk_graph(sv, mix(mix(mix(base, first ? 1 : 0), (uint64_t)todo), (uint64_t)(k0 & 1)), chunk, mode.graph)))
       return rc;
     k += todo;
-    if ((rc = chunk_state(h, S, sc, use_pub, who))) return rc;
+    if ((rc = chunk_state(sv, S, sc, use_pub, who))) return rc;
     if (first && mode.timed)
-      record_mode(h, sys, mode.graph,
+      record_mode(sv, sys, mode.graph,
                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_start).count() / (todo + head_cost));
     it = (int)sc[S_IT];
     if (sc[S_DONE] != 0.0 || it >= maxit) break;
@@ -1084,52 +1084,51 @@ int fused_chunks(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, int sys, const
 
 }  // namespace
 
-void kn_fused_graphs_free(knpemi_handle* h) {
-  for (auto& kv : h->fused_graphs) (void)hipGraphExecDestroy(kv.second);
-  h->fused_graphs.clear();
+void kn_fused_graphs_free(KnSolver& sv) {
+  for (auto& kv : sv.fused_graphs) (void)hipGraphExecDestroy(kv.second);
+  sv.fused_graphs.clear();
 }
 
-// CG on A_emi phi = b_emi - mean(b_emi); workspace vectors as in kn_solve_emi.  The initial guess is gathered from `phi`
-// (component of the vertex records, stride doubles apart), the solution minus its mean is written back there: both are
-// part of the captured graph of a chunk (the write-back is idempotent and follows every chunk).
-int kn_fused_cg(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit, int* iters,
-                double* rr_out, double* bb_out, double* phi, int phi_stride) {
+// CG on A_emi phi = b_emi - mean(b_emi); workspace vectors as in kn_solve_emi.  The initial guess is gathered from
+// KnSolver::phi, the solution minus its mean is written back there, by this file's kernel or by the owner's phi_store: both
+// are part of the captured graph of a chunk (the write-back is idempotent and follows every chunk).
+int kn_fused_cg(KnSolver& sv, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit, int* iters,
+                double* rr_out, double* bb_out) {
+  double* const phi = sv.phi;
+  const int phi_stride = sv.phi_stride;
   const int n = S.n;
   const size_t N = S.N;
   double *x = S.work, *z = x + 2 * N, *q = x + 4 * N;
   // r, p of iteration k: rb[k & 1], pb[k & 1]; the iteration writes the next ones into the other buffers
   double* const rb[2] = {x + N, S.work + 7 * N};
   double* const pb[2] = {x + 3 * N, S.work + 8 * N};
-  int rc = ensure_partials(h);
+  int rc = ensure_partials(sv);
   if (rc) return rc;
-  Loop L{h, G, S, Red{S.sc, h->fused_part}, h->stream, lanes0(G)};
+  Loop L{sv, G, S, Red{S.sc, sv.fused_part}, sv.own->stream, lanes0(G)};
   const int l0 = L.l0;
   const int nb_res = Loop::capped(L.blocks0(n)), nb_dir = Loop::capped(L.blocks0(n));
   const int np_rz = L.np_rz();
   const int nb_vec = Loop::capped((n + FT - 1) / FT);
   const double inv_n = 1.0 / (double)n;
-  // KNPEMI_OPT_FOLD_MEMBRANE: the write-back launch also integrates the membrane facets (the potential system of the CG
-  // path only: its unknowns are the vertex records' phi)
-  const bool fold = h->fold_membrane && !h->fuse_membrane && h->have_params && !h->plain_knp && phi == h->dev.VR + 7;
-  const bool pre_norm = h->emi_norm_pre;
+  const bool pre_norm = sv.emi_norm_pre;
   auto head = [&]() -> int {
     // x0 = current phi (ksp_initial_guess_nonzero), b = b_emi projected onto zero mean (constant null space)
-    hipLaunchKernelGGL(emi_pre_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)phi, phi_stride, x, b, L.red);
+    hipLaunchKernelGGL(emi_pre_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, (const double*)phi, phi_stride, x, b, L.red);
     if (pre_norm) {
       // KSPCG's default test: |M^-1 r| <= max(atol, rtol |M^-1 b|).  The projected b goes to q (free until the first
       // direction), M^-1 b to pb[1], its square norm replaces the sums of b in P_BS
-      KN_LAUNCH_L0(l0, dim3(nb_res), h->stream, (residual_kernel<4, true>), (residual_kernel<16, true>), n, S.rowptr, S.colind,
+      KN_LAUNCH_L0(l0, dim3(nb_res), sv.own->stream, (residual_kernel<4, true>), (residual_kernel<16, true>), n, S.rowptr, S.colind,
                    S.vals, (const double*)x, b, rb[0], (double*)nullptr, L.red, nb_vec, inv_n, q);
       L.cycle<IN_PLAIN, 0, false>(q, nullptr, nullptr, nullptr, nullptr, pb[1], 0, 0);
-      hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)pb[1], L.red, (int)P_BS);
-      hipLaunchKernelGGL(gm_start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_vec, rtol, atol, 0, 1, nb_res);
+      hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, (const double*)pb[1], L.red, (int)P_BS);
+      hipLaunchKernelGGL(gm_start_kernel, dim3(1), dim3(FT), 0, sv.own->stream, L.red, nb_vec, rtol, atol, 0, 1, nb_res);
       // z_0 = M^-1 r_0 with r_0.z_0 and |z_0|^2: the first direction kernel tests the initial residual
       L.cycle<IN_PLAIN, 3, false>(rb[0], nullptr, nullptr, nullptr, nullptr, z, 0, 0);
       return KNPEMI_OK;
     }
-    KN_LAUNCH_L0(l0, dim3(nb_res), h->stream, (residual_kernel<4, true>), (residual_kernel<16, true>), n, S.rowptr, S.colind,
+    KN_LAUNCH_L0(l0, dim3(nb_res), sv.own->stream, (residual_kernel<4, true>), (residual_kernel<16, true>), n, S.rowptr, S.colind,
                  S.vals, (const double*)x, b, rb[0], (double*)nullptr, L.red, nb_vec, inv_n, (double*)nullptr);
-    hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_res, rtol, atol, 0, 0, 0);
+    hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, sv.own->stream, L.red, nb_res, rtol, atol, 0, 0, 0);
     // z_0 = M^-1 r_0, r_0.z_0 (rho_old = 0: the first direction is z_0)
     L.cycle<IN_PLAIN, 1, false>(rb[0], nullptr, nullptr, nullptr, nullptr, z, 0, 0);
     return KNPEMI_OK;
@@ -1138,59 +1137,57 @@ int kn_fused_cg(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b
     for (int k = k0; k < k0 + count; ++k) {
       double *r = rb[k & 1], *r2 = rb[(k + 1) & 1], *p = pb[k & 1], *p2 = pb[(k + 1) & 1];
       if (pre_norm) {
-        KN_LAUNCH_L0(l0, dim3(nb_dir), h->stream, (cg_dir_kernel<4, true>), (cg_dir_kernel<16, true>), n, S.rowptr, S.colind, S.vals,
+        KN_LAUNCH_L0(l0, dim3(nb_dir), sv.own->stream, (cg_dir_kernel<4, true>), (cg_dir_kernel<16, true>), n, S.rowptr, S.colind, S.vals,
                      (const double*)z, (const double*)p, p2, q, L.red, np_rz, k & 1);
         // r_new = r - alpha q (stored in r2), x += alpha p_new; z = M^-1 r_new with r_new.z and |z|^2; the iteration is counted
         L.cycle<IN_CG, 7, false>(r, q, p2, r2, x, z, nb_dir, k & 1);
       } else {
-        KN_LAUNCH_L0(l0, dim3(nb_dir), h->stream, (cg_dir_kernel<4, false>), (cg_dir_kernel<16, false>), n, S.rowptr, S.colind, S.vals,
+        KN_LAUNCH_L0(l0, dim3(nb_dir), sv.own->stream, (cg_dir_kernel<4, false>), (cg_dir_kernel<16, false>), n, S.rowptr, S.colind, S.vals,
                      (const double*)z, (const double*)p, p2, q, L.red, np_rz, k & 1);
         // r_new = r - alpha q (stored in r2), x += alpha p_new, |r_new|^2 -> convergence; then z = M^-1 r_new, r_new.z
         L.cycle<IN_CG, 1, true>(r, q, p2, r2, x, z, nb_dir, k & 1);
       }
     }
     // (the test the next direction kernel would make, for the host that reads the state after this chunk)
-    if (pre_norm) hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, np_rz);
+    if (pre_norm) hipLaunchKernelGGL(cg_check_kernel, dim3(1), dim3(FT), 0, sv.own->stream, L.red, np_rz);
     return KNPEMI_OK;
   };
   // the solution orthogonal to the constants, into the phi component of the vertex records (idempotent)
   auto tail = [&]() -> int {
-    hipLaunchKernelGGL(x_sum_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)x, L.red);
-    if (fold)   // ... and, in the same launch, the membrane-facet integrals of b_knp for that potential
-      return kn_launch_emi_writeback_membrane(h, x, L.red.part + (size_t)P_XS * KN_PB, nb_vec, inv_n, S.sc + S_MEAN);
-    hipLaunchKernelGGL(emi_post_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)x, phi, phi_stride, L.red, nb_vec, inv_n);
+    hipLaunchKernelGGL(x_sum_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, (const double*)x, L.red);
+    if (sv.phi_store) return sv.phi_store(x, L.red.part + (size_t)P_XS * KN_PB, nb_vec, inv_n, S.sc + S_MEAN);
+    hipLaunchKernelGGL(emi_post_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, (const double*)x, phi, phi_stride, L.red, nb_vec, inv_n);
     return KNPEMI_OK;
   };
-  uint64_t seed = mix(mix(mix(0xC6ull, (uint64_t)(uintptr_t)b), (uint64_t)(uintptr_t)phi), (uint64_t)(h->fold_membrane && !h->fuse_membrane));
-  seed = mix(mix(seed, (uint64_t)(h->emi_flags & KNPEMI_NO_SPLITTING)), pre_norm ? 2 : 0);
-  if ((rc = fused_chunks(h, G, S, 0, "EMI CG", "fused CG", seed, rtol, atol, maxit, 0, 1.5, head, iterations, tail, nullptr, iters,
+  const uint64_t seed = mix(mix(mix(mix(0xC6ull, (uint64_t)(uintptr_t)b), (uint64_t)(uintptr_t)phi), sv.emi_key), pre_norm ? 2 : 0);
+  if ((rc = fused_chunks(sv, G, S, 0, "EMI CG", "fused CG", seed, rtol, atol, maxit, 0, 1.5, head, iterations, tail, nullptr, iters,
                          rr_out, bb_out)))
     return rc;
-  if (fold) kn_gam_formed(h, (h->emi_flags & KNPEMI_NO_SPLITTING) ? 0 : 1);   // by the write-back of every chunk, replayed or not
+  sv.phi_stored = (bool)sv.phi_store;   // by the write-back of every chunk, replayed or not
   return KNPEMI_OK;
 }
 
 // Right-preconditioned BiCGStab on S x = b from the x in the workspace; vectors as in kn_solve_knp; pre / post as above.
-int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
+int kn_fused_bicgstab(KnSolver& sv, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
                       int* iters, double* rr_out, double* bb_out, const std::function<int()>& pre,
                       const std::function<int()>& post) {
   const int n = S.n;
-  const int min_it = std::max(0, std::min(h->knp_min_it, maxit));
+  const int min_it = std::max(0, std::min(sv.knp_min_it, maxit));
   const size_t N = S.N;
   double *x = S.work, *r = x + N, *rhat = r + N, *v = rhat + 2 * N, *s = v + N;
   double *phat = S.work + 8 * N, *shat = S.work + 9 * N;
   // the search direction of iteration k: pt[k & 1]; the iteration forms the next one in the other buffer
   double* const pt[2] = {rhat + N, S.work + 6 * N};
-  int rc = ensure_partials(h);
+  int rc = ensure_partials(sv);
   if (rc) return rc;
-  Loop L{h, G, S, Red{S.sc, h->fused_part}, h->stream, lanes0(G)};
+  Loop L{sv, G, S, Red{S.sc, sv.fused_part}, sv.own->stream, lanes0(G)};
   const int l0 = L.l0;
   const int nb_res = Loop::capped(L.blocks0(n)), nb_spmv = Loop::capped(L.blocks0(n)), nb_update = Loop::capped((n + FT - 1) / FT);
   auto head = [&]() -> int {
     if (int e = pre()) return e;
-    KN_LAUNCH_L0(l0, dim3(nb_res), h->stream, (residual_kernel<4, false>), (residual_kernel<16, false>), n, S.rowptr, S.colind,
+    KN_LAUNCH_L0(l0, dim3(nb_res), sv.own->stream, (residual_kernel<4, false>), (residual_kernel<16, false>), n, S.rowptr, S.colind,
                  S.vals, (const double*)x, b, r, rhat, L.red, 0, 0.0, (double*)nullptr);
-    hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_res, rtol, atol, 1, nb_update, min_it);
+    hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, sv.own->stream, L.red, nb_res, rtol, atol, 1, nb_update, min_it);
     return KNPEMI_OK;
   };
   auto iterations = [&](int k0, int count) -> int {
@@ -1199,15 +1196,15 @@ int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const dou
       // it stores its own: the new direction goes to the other buffer, the old one is t (free once the new one exists)
       double *p = pt[k & 1], *p_new = pt[(k + 1) & 1], *t = p;
       L.cycle<IN_BI_P, 0, false>(r, p, v, p_new, nullptr, phat, nb_update, k & 1);
-      KN_LAUNCH_L0(l0, dim3(nb_spmv), h->stream, (bi_spmv_kernel<0, 4>), (bi_spmv_kernel<0, 16>), n, S.rowptr, S.colind, S.vals,
+      KN_LAUNCH_L0(l0, dim3(nb_spmv), sv.own->stream, (bi_spmv_kernel<0, 4>), (bi_spmv_kernel<0, 16>), n, S.rowptr, S.colind, S.vals,
                    (const double*)phat, v, (const double*)rhat, L.red);
       L.cycle<IN_BI_S, 0, false>(r, v, nullptr, s, nullptr, shat, nb_spmv, k & 1);
-      KN_LAUNCH_L0(l0, dim3(nb_spmv), h->stream, (bi_spmv_kernel<1, 4>), (bi_spmv_kernel<1, 16>), n, S.rowptr, S.colind, S.vals,
+      KN_LAUNCH_L0(l0, dim3(nb_spmv), sv.own->stream, (bi_spmv_kernel<1, 4>), (bi_spmv_kernel<1, 16>), n, S.rowptr, S.colind, S.vals,
                    (const double*)shat, t, (const double*)s, L.red);
-      hipLaunchKernelGGL(bi_update_kernel, dim3(nb_update), dim3(FT), 0, h->stream, n, x, r, (const double*)phat,
+      hipLaunchKernelGGL(bi_update_kernel, dim3(nb_update), dim3(FT), 0, sv.own->stream, n, x, r, (const double*)phat,
                          (const double*)shat, (const double*)s, (const double*)t, (const double*)rhat, L.red, nb_spmv);
     }
-    hipLaunchKernelGGL(bi_check_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_update);
+    hipLaunchKernelGGL(bi_check_kernel, dim3(1), dim3(FT), 0, sv.own->stream, L.red, nb_update);
     return KNPEMI_OK;
   };
   int restarts = 0;
@@ -1215,11 +1212,11 @@ int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const dou
     if (!((int)sc[S_FLAG] & (F_RHO_ZERO | F_OMEGA_ZERO | F_RV_ZERO))) return KNPEMI_OK;
     // a true breakdown with a residual left: restart from the current iterate with rhat = r, as PETSc's KSPBCGS does
     if (++restarts > 3) { kn_set_error("KNP BiCGStab broke down repeatedly " + describe(sc)); return KNPEMI_ESOLVE; }
-    hipLaunchKernelGGL(bi_restart_kernel, dim3((std::max(n, KN_PB) + 255) / 256), dim3(256), 0, h->stream, n, rhat, r, L.red, nb_update);
+    hipLaunchKernelGGL(bi_restart_kernel, dim3((std::max(n, KN_PB) + 255) / 256), dim3(256), 0, sv.own->stream, n, rhat, r, L.red, nb_update);
     return KNPEMI_OK;
   };
-  const uint64_t seed = mix(mix(mix(0xB1ull, (uint64_t)(uintptr_t)b), (uint64_t)h->fuse_update), (uint64_t)min_it);
-  return fused_chunks(h, G, S, 1, "KNP BiCGStab", "fused BiCGStab", seed, rtol, atol, maxit, min_it, 0.5, head, iterations, post,
+  const uint64_t seed = mix(mix(mix(0xB1ull, (uint64_t)(uintptr_t)b), sv.knp_key), (uint64_t)min_it);
+  return fused_chunks(sv, G, S, 1, "KNP BiCGStab", "fused BiCGStab", seed, rtol, atol, maxit, min_it, 0.5, head, iterations, post,
                       breakdown, iters, rr_out, bb_out);
 }
 
@@ -1381,43 +1378,43 @@ __global__ __launch_bounds__(FT) void gm_update_kernel(int n, double* __restrict
   }
 }
 
-int ensure_gmres(knpemi_handle* h, size_t n, GmState* out) {
+int ensure_gmres(KnSolver& sv, size_t n, GmState* out) {
   const size_t need = (size_t)GM_M * n;
   int rc;
-  if (h->gm_n < need) {
-    if ((rc = kn_alloc(h->allocs, need, &h->gm_V))) return rc;
-    h->gm_n = need;
+  if (sv.gm_n < need) {
+    if ((rc = kn_alloc(sv.own->allocs, need, &sv.gm_V))) return rc;
+    sv.gm_n = need;
   }
-  if (!h->gm_state) {
+  if (!sv.gm_state) {
     const size_t doubles = GM_N + (size_t)(GM_M + 1) * KN_PB;
-    if ((rc = kn_alloc(h->allocs, doubles, &h->gm_state))) return rc;
-    KN_HIP(hipMemsetAsync(h->gm_state, 0, doubles * sizeof(double), h->stream));
+    if ((rc = kn_alloc(sv.own->allocs, doubles, &sv.gm_state))) return rc;
+    KN_HIP(hipMemsetAsync(sv.gm_state, 0, doubles * sizeof(double), sv.own->stream));
   }
-  out->gm = h->gm_state;
-  out->dots = h->gm_state + GM_N;
+  out->gm = sv.gm_state;
+  out->dots = sv.gm_state + GM_N;
   return KNPEMI_OK;
 }
 
 }  // namespace
 
-int kn_fused_gmres(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
+int kn_fused_gmres(KnSolver& sv, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
                    int* iters, double* rr_out, double* bb_out, const std::function<int()>& pre, const std::function<int()>& post) {
   const int n = S.n;
   const size_t N = S.N;
   double *x = S.work, *r = x + N, *w = r + N, *t = w + N, *tmp = t + N;
-  int rc = ensure_partials(h);
+  int rc = ensure_partials(sv);
   if (rc) return rc;
   GmState g{};
-  if ((rc = ensure_gmres(h, (size_t)n, &g))) return rc;
-  double* V = h->gm_V;
+  if ((rc = ensure_gmres(sv, (size_t)n, &g))) return rc;
+  double* V = sv.gm_V;
   const size_t ldv = (size_t)n;
-  Loop L{h, G, S, Red{S.sc, h->fused_part}, h->stream, lanes0(G)};
+  Loop L{sv, G, S, Red{S.sc, sv.fused_part}, sv.own->stream, lanes0(G)};
   const int l0 = L.l0;
   const int nb_row = Loop::capped(L.blocks0(n)), nb_vec = Loop::capped((n + FT - 1) / FT);
-  const int min_it = std::max(0, std::min(h->knp_min_it, maxit));
+  const int min_it = std::max(0, std::min(sv.knp_min_it, maxit));
   Publish pub{};
   const bool use_pub = publish_usable();
-  if (use_pub && (rc = ensure_publish(h, &pub))) return rc;
+  if (use_pub && (rc = ensure_publish(sv, &pub))) return rc;
   double sc[S_NF];
   int it = 0, base = 0;
   bool first = true;
@@ -1425,38 +1422,38 @@ int kn_fused_gmres(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double
   static const int m_restart = [] { const char* e = getenv("KNPEMI_GMRES_RESTART"); const int v = e ? atoi(e) : GM_M; return v >= 2 && v <= GM_M ? v : GM_M; }();
   if ((rc = pre())) return rc;
   // (the kernels of the cycle look at the early-out flag: clear what the previous solve left before the first of them runs)
-  KN_HIP(hipMemsetAsync(S.sc + S_DONE, 0, sizeof(double), h->stream));
+  KN_HIP(hipMemsetAsync(S.sc + S_DONE, 0, sizeof(double), sv.own->stream));
   for (;;) {      // restart cycles
     // r = b - A x; w = M^-1 r; first cycle: also |M^-1 b| for the target
-    KN_LAUNCH_L0(l0, dim3(nb_row), h->stream, (residual_kernel<4, false>), (residual_kernel<16, false>), n, S.rowptr, S.colind,
+    KN_LAUNCH_L0(l0, dim3(nb_row), sv.own->stream, (residual_kernel<4, false>), (residual_kernel<16, false>), n, S.rowptr, S.colind,
                  S.vals, (const double*)x, b, r, (double*)nullptr, L.red, 0, 0.0, (double*)nullptr);
     if (first) {
       L.cycle<IN_PLAIN, 0, false>(b, nullptr, nullptr, nullptr, nullptr, tmp, 0, 0);
-      hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)tmp, L.red, (int)P_BS);
+      hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, (const double*)tmp, L.red, (int)P_BS);
     }
-    hipLaunchKernelGGL(gm_start_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, nb_vec, rtol, atol, min_it, first ? 1 : 0, nb_row);
+    hipLaunchKernelGGL(gm_start_kernel, dim3(1), dim3(FT), 0, sv.own->stream, L.red, nb_vec, rtol, atol, min_it, first ? 1 : 0, nb_row);
     L.cycle<IN_PLAIN, 0, false>(r, nullptr, nullptr, nullptr, nullptr, w, 0, 0);
-    hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)w, L.red, (int)P_PQ);
+    hipLaunchKernelGGL(gm_sqnorm_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, (const double*)w, L.red, (int)P_PQ);
     first = false;
     int j = 0;
     int todo = std::max(1, std::min({std::max(first_chunk(G.its_last, maxit), min_it) - base, m_restart, maxit - base}));
     bool done = false;
     while (!done) {
       for (int k = 0; k < todo && j < m_restart; ++k, ++j) {
-        KN_LAUNCH_L0(l0, dim3(nb_row), h->stream, gm_spmv_kernel<4>, gm_spmv_kernel<16>, n, S.rowptr, S.colind, S.vals,
+        KN_LAUNCH_L0(l0, dim3(nb_row), sv.own->stream, gm_spmv_kernel<4>, gm_spmv_kernel<16>, n, S.rowptr, S.colind, S.vals,
                      (const double*)w, V + (size_t)j * ldv, t, L.red, g, nb_vec, j, base);
         L.cycle<IN_PLAIN, 0, false>(t, nullptr, nullptr, nullptr, nullptr, w, 0, 0);
-        hipLaunchKernelGGL(gm_dots_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, (const double*)w, (const double*)V, ldv, j, L.red, g);
-        hipLaunchKernelGGL(gm_orth_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, w, (const double*)V, ldv, j, L.red, g, nb_vec);
+        hipLaunchKernelGGL(gm_dots_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, (const double*)w, (const double*)V, ldv, j, L.red, g);
+        hipLaunchKernelGGL(gm_orth_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, w, (const double*)V, ldv, j, L.red, g, nb_vec);
       }
-      hipLaunchKernelGGL(gm_check_kernel, dim3(1), dim3(FT), 0, h->stream, L.red, g, nb_vec, j, base);
-      if (use_pub) enqueue_publish(h, pub, S.sc);
-      if ((rc = chunk_state(h, S, sc, use_pub, "KNP GMRES"))) return rc;
+      hipLaunchKernelGGL(gm_check_kernel, dim3(1), dim3(FT), 0, sv.own->stream, L.red, g, nb_vec, j, base);
+      if (use_pub) enqueue_publish(sv, pub, S.sc);
+      if ((rc = chunk_state(sv, S, sc, use_pub, "KNP GMRES"))) return rc;
       it = (int)sc[S_IT];
       done = sc[S_DONE] != 0.0 || it >= maxit || j >= m_restart;
       todo = 1;
     }
-    hipLaunchKernelGGL(gm_update_kernel, dim3(nb_vec), dim3(FT), 0, h->stream, n, x, (const double*)V, ldv, L.red, g, base);
+    hipLaunchKernelGGL(gm_update_kernel, dim3(nb_vec), dim3(FT), 0, sv.own->stream, n, x, (const double*)V, ldv, L.red, g, base);
     if (sc[S_DONE] != 0.0 || it >= maxit) break;
     base = it;       // restart from the updated iterate
   }
@@ -1475,39 +1472,40 @@ __global__ __launch_bounds__(256) void chain_copy_kernel(const double* __restric
 
 extern "C" int knpemi_debug_launch_chain(knpemi_handle* h, int kind, int n, int links, int reps, int use_graph, double* us_per_kernel) {
   if (!h || !us_per_kernel || links < 1 || reps < 1 || n < 1) { kn_set_error("knpemi_debug_launch_chain: bad arguments"); return KNPEMI_EINVAL; }
-  KN_HIP(hipSetDevice(h->device));
-  int rc = ensure_partials(h);
+  KnSolver& sv = h->solver;
+  KN_HIP(hipSetDevice(sv.own->device));
+  int rc = ensure_partials(sv);
   if (rc) return rc;
   void* buf = nullptr;
   KN_HIP(hipMalloc(&buf, (size_t)(2 * n + 64) * sizeof(double)));
-  KN_HIP(hipMemsetAsync(buf, 0, (size_t)(2 * n + 64) * sizeof(double), h->stream));
+  KN_HIP(hipMemsetAsync(buf, 0, (size_t)(2 * n + 64) * sizeof(double), sv.own->stream));
   double* a = static_cast<double*>(buf);
   double* b = a + n;
-  const Red red{a + 2 * n, h->fused_part};
+  const Red red{a + 2 * n, sv.fused_part};
   auto launch = [&](int k) {
-    if (kind == 0) hipLaunchKernelGGL(chain_empty_kernel, dim3(1), dim3(64), 0, h->stream, a);
-    else if (kind == 1) hipLaunchKernelGGL(chain_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, (k & 1) ? b : a, (k & 1) ? a : b, n);
-    else hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, h->stream, red, 512, 1e-5, 1e-40, 0, 0, 0);
+    if (kind == 0) hipLaunchKernelGGL(chain_empty_kernel, dim3(1), dim3(64), 0, sv.own->stream, a);
+    else if (kind == 1) hipLaunchKernelGGL(chain_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, sv.own->stream, (k & 1) ? b : a, (k & 1) ? a : b, n);
+    else hipLaunchKernelGGL(start_kernel, dim3(1), dim3(FT), 0, sv.own->stream, red, 512, 1e-5, 1e-40, 0, 0, 0);
   };
   for (int k = 0; k < links; ++k) launch(k);
-  KN_HIP(hipStreamSynchronize(h->stream));
+  KN_HIP(hipStreamSynchronize(sv.own->stream));
   hipGraphExec_t exec = nullptr;
   if (use_graph) {
     hipGraph_t g = nullptr;
-    KN_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    KN_HIP(hipStreamBeginCapture(sv.own->stream, hipStreamCaptureModeThreadLocal));
     for (int k = 0; k < links; ++k) launch(k);
-    KN_HIP(hipStreamEndCapture(h->stream, &g));
+    KN_HIP(hipStreamEndCapture(sv.own->stream, &g));
     KN_HIP(hipGraphInstantiate(&exec, g, nullptr, nullptr, 0));
     (void)hipGraphDestroy(g);
-    for (int w = 0; w < 5; ++w) KN_HIP(hipGraphLaunch(exec, h->stream));
-    KN_HIP(hipStreamSynchronize(h->stream));
+    for (int w = 0; w < 5; ++w) KN_HIP(hipGraphLaunch(exec, sv.own->stream));
+    KN_HIP(hipStreamSynchronize(sv.own->stream));
   }
   const auto t0 = std::chrono::steady_clock::now();
   for (int r = 0; r < reps; ++r) {
-    if (exec) KN_HIP(hipGraphLaunch(exec, h->stream));
+    if (exec) KN_HIP(hipGraphLaunch(exec, sv.own->stream));
     else for (int k = 0; k < links; ++k) launch(k);
   }
-  KN_HIP(hipStreamSynchronize(h->stream));
+  KN_HIP(hipStreamSynchronize(sv.own->stream));
   *us_per_kernel = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() / ((double)reps * links);
   if (exec) (void)hipGraphExecDestroy(exec);
   (void)hipFree(buf);

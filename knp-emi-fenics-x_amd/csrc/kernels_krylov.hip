@@ -326,7 +326,7 @@ __global__ void coarse_prolong_kernel(int n, const int* __restrict__ agg_of, con
 }
 
 struct Ctx {
-  knpemi_handle* h;
+  KnSolver& sv;
   int n;
   const int* rowptr; const int* colind; const double* vals;
   double* sc; double* partial;
@@ -338,8 +338,8 @@ struct Ctx {
 };
 
 // lanes per row from the average row length (read once per system and handle)
-int spmv_lanes(knpemi_handle* h, int which, const int* rowptr, int n) {
-  int& l = h->spmv_lpr[which == KNPEMI_B_KNP ? 1 : 0];
+int spmv_lanes(KnSolver& sv, int which, const int* rowptr, int n) {
+  int& l = sv.spmv_lpr[which == KNPEMI_B_KNP ? 1 : 0];
   if (l == 0) {
     int nnz = 0;
     if (hipMemcpy(&nnz, rowptr + n, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return 16;
@@ -353,23 +353,23 @@ inline dim3 grid1(int n) { return dim3((n + 255) / 256); }
 void spmv(Ctx& c, const double* x, double* y, const double* dinv, const double* b = nullptr, double* dinv_out = nullptr) {
   dim3 g(((size_t)c.n * c.lpr + 255) / 256);
   if (c.owned) {   // the argument's ghost entries take their owners' values first
-    const KnDist& d = c.h->dist;
+    const KnDist& d = c.sv.dist;
     if (int e = d.halo(d.ctx, const_cast<double*>(x), c.which)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
   }
-  if (c.h->bcols.bcol && !dinv && !dinv_out) {   // DG systems: block columns instead of one column index per entry
-    launch_block_spmv<double>(c.h->stream, c.h->bcols, c.n, c.rowptr, c.vals, x, b, y, c.owned);
+  if (c.sv.bcols.bcol && !dinv && !dinv_out) {   // DG systems: block columns instead of one column index per entry
+    launch_block_spmv<double>(c.sv.own->stream, c.sv.bcols, c.n, c.rowptr, c.vals, x, b, y, c.owned);
     return;
   }
   if (c.lpr == 4) {
-    if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 4>), g, dim3(256), 0, c.h->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y,
+    if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 4>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y,
                                  (const double*)nullptr, c.owned);
-    else hipLaunchKernelGGL((spmv_kernel<false, 4>), g, dim3(256), 0, c.h->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y, b,
+    else hipLaunchKernelGGL((spmv_kernel<false, 4>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y, b,
                             c.owned, dinv_out);
     return;
   }
-  if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 16>), g, dim3(256), 0, c.h->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y,
+  if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 16>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y,
                                (const double*)nullptr, c.owned);
-  else hipLaunchKernelGGL((spmv_kernel<false, 16>), g, dim3(256), 0, c.h->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y, b,
+  else hipLaunchKernelGGL((spmv_kernel<false, 16>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y, b,
                           c.owned, dinv_out);
 }
 
@@ -377,31 +377,31 @@ void dots(Ctx& c, int nd, const double* a0, const double* b0, const double* a1, 
           const double* b2, int op, int d0 = 0, int d1 = 0, int d2 = 0, double scale = 1.0) {
   // 16 entries per thread: every block costs ~50 ns at the ticket counter, whatever it sums
   const int nb = std::min(RED_BLOCKS, (c.n + 16 * RED_THREADS - 1) / (16 * RED_THREADS));
-  double* red = c.owned ? c.h->dist.d_red : nullptr;
-  hipLaunchKernelGGL(dots_kernel, dim3(nb), dim3(RED_THREADS), 0, c.h->stream, c.n, nd, a0, b0, a1, b1, a2, b2, c.partial,
+  double* red = c.owned ? c.sv.dist.d_red : nullptr;
+  hipLaunchKernelGGL(dots_kernel, dim3(nb), dim3(RED_THREADS), 0, c.sv.own->stream, c.n, nd, a0, b0, a1, b1, a2, b2, c.partial,
                      reinterpret_cast<unsigned*>(c.partial + 3 * RED_BLOCKS), c.sc, op, d0, d1, d2, scale, red);
   if (red) {   // every vector is zero on its ghost entries, so the local sums run over the owned unknowns only
-    const KnDist& d = c.h->dist;
+    const KnDist& d = c.sv.dist;
     if (int e = d.allreduce(d.ctx, nd)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
-    hipLaunchKernelGGL(dots_apply_kernel, dim3(1), dim3(1), 0, c.h->stream, c.sc, red, op, nd, d0, d1, d2, scale);
+    hipLaunchKernelGGL(dots_apply_kernel, dim3(1), dim3(1), 0, c.sv.own->stream, c.sc, red, op, nd, d0, d1, d2, scale);
   }
 }
 
 void mask(const Ctx& c, double* a, int as_ones = 0) {
-  if (c.owned) hipLaunchKernelGGL(mask_kernel, grid1(c.n), dim3(256), 0, c.h->stream, c.n, c.owned, a, as_ones);
+  if (c.owned) hipLaunchKernelGGL(mask_kernel, grid1(c.n), dim3(256), 0, c.sv.own->stream, c.n, c.owned, a, as_ones);
 }
 
 void vec(const Ctx& c, int op, double* a, double* b, const double* cc, const double* d) {
-  hipLaunchKernelGGL(vec_kernel, grid1(c.n), dim3(256), 0, c.h->stream, c.n, op, c.sc, a, b, cc, d, (const double*)nullptr);
+  hipLaunchKernelGGL(vec_kernel, grid1(c.n), dim3(256), 0, c.sv.own->stream, c.n, op, c.sc, a, b, cc, d, (const double*)nullptr);
 }
 
 // the solver's scalars on the host: through a pinned buffer (a copy into pageable memory is staged by the runtime)
 int read_scalars(const Ctx& c, double* host, int count) {
-  knpemi_handle* h = c.h;
-  if (!h->kry_pinned) KN_HIP(hipHostMalloc(&h->kry_pinned, 64 * sizeof(double), hipHostMallocDefault));
-  KN_HIP(hipMemcpyAsync(h->kry_pinned, c.sc, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  for (int i = 0; i < count; ++i) host[i] = static_cast<double*>(h->kry_pinned)[i];
+  KnSolver& sv = c.sv;
+  if (!sv.kry_pinned) KN_HIP(hipHostMalloc(&sv.kry_pinned, 64 * sizeof(double), hipHostMallocDefault));
+  KN_HIP(hipMemcpyAsync(sv.kry_pinned, c.sc, count * sizeof(double), hipMemcpyDeviceToHost, sv.own->stream));
+  KN_HIP(hipStreamSynchronize(sv.own->stream));
+  for (int i = 0; i < count; ++i) host[i] = static_cast<double*>(sv.kry_pinned)[i];
   return KNPEMI_OK;
 }
 
@@ -416,20 +416,20 @@ __global__ void bicg_init_kernel(int n, double* __restrict__ p, double* __restri
 // systems: ~20 launches of a few microseconds per iteration) and replayed; the graph is keyed on everything its
 // kernel arguments depend on.  KNPEMI_NO_GRAPH=1 launches the kernels directly.
 template <class Body>
-int run_chunk(knpemi_handle* h, knpemi_handle::KnGraph& g, uint64_t key, int chunk, Body&& body) {
+int run_chunk(KnSolver& sv, KnSolver::KnGraph& g, uint64_t key, int chunk, Body&& body) {
   static const bool no_graph_env = getenv("KNPEMI_NO_GRAPH") != nullptr;
   auto loop = [&]() -> int {
     int rc = KNPEMI_OK;
     for (int k = 0; k < chunk && !rc; ++k) rc = body();
     return rc;
   };
-  if (no_graph_env || h->dist.on) return loop();   // the communication hooks cannot be captured
+  if (no_graph_env || sv.dist.on) return loop();   // the communication hooks cannot be captured
   if (!g.exec || g.key != key) {
     if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-    if (int rc = kn_capture(h, loop, &g.exec)) return rc;
+    if (int rc = kn_capture(sv, loop, &g.exec)) return rc;
     g.key = key;
   }
-  KN_HIP(hipGraphLaunch(g.exec, h->stream));
+  KN_HIP(hipGraphLaunch(g.exec, sv.own->stream));
   return KNPEMI_OK;
 }
 
@@ -450,8 +450,8 @@ inline bool debug_krylov() {
   return on;
 }
 
-inline uint64_t graph_key(const knpemi_handle* h, const KnAmg& G, bool amg, int chunk, int n) {
-  uint64_t k = reinterpret_cast<uint64_t>(h->kry);
+inline uint64_t graph_key(const KnSolver& sv, const KnAmg& G, bool amg, int chunk, int n) {
+  uint64_t k = reinterpret_cast<uint64_t>(sv.kry);
   k = k * 1000003u + (uint64_t)G.builds;
   k = k * 1000003u + (amg ? 1u : 0u);
   k = k * 1000003u + (uint64_t)chunk;
@@ -488,53 +488,39 @@ int check_start(const char* who, const double* sc) {
 // Hierarchy upkeep at the head of an AMG-preconditioned solve: the first build (also after a size change, and on a
 // partitioned problem once the hierarchy has aged), else the background rebuild of an aged one; then the block inverses
 // of the finest level.  `owned`: the rank's mask of the system's unknowns (partitioned problems).
-int amg_upkeep(knpemi_handle* h, KnAmg& G, int n, const int* rowptr, const int* colind, const double* vals, bool singular,
+int amg_upkeep(KnSolver& sv, KnAmg& G, int n, const int* rowptr, const int* colind, const double* vals, bool singular,
                const std::vector<uint8_t>& owned) {
-  const KnDist& dist = h->dist;
+  const KnDist& dist = sv.dist;
   int rc;
   if (!G.built || G.n != n) {
-    KnAmgConfig& C = G.cfg;
+    KnAmgConfig& C = G.cfg;   // the owner's choices, and what follows from the partition
     C.negative_strength = true;
-    // (plain_knp marks the solver handle of a DG problem, which has made its own choices: kernels_dg.hip)
-    if (!h->plain_knp) {
-      // stretched Q1 cells couple the two ends of an edge along the long direction positively: aggregate_apart keeps them
-      // in different aggregates (config 2h: 9.35 / 3.95 -> 7.4 / 2.9 iterations per solve; on simplices the plain greedy
-      // pass is the better one, 5.3 / 2.35 against 5.75 / 2.6 at config 2)
-      if (h->NV == 8) C.positive_conflict = true;
-      // prolongator smoothing along the large couplings only (KnAmgConfig::filter_theta): the operator complexity falls
-      // from 2.5-2.8 to 1.5 on simplices, the iteration counts stay (995 k tets: 6.65 / 2.8 -> 6.75 / 2.85, 3.34 -> 2.37 ms
-      // per step with solves).  "Large" is by magnitude: the big positive entries of stretched Q1 cells stay in the
-      // smoothing (lumping them into the diagonal cost config 2h 7.4 -> 12.6 iterations).
-      C.filter_theta = 0.02;
-    }
-    if (getenv("KNPEMI_AMG_APART")) C.positive_conflict = atoi(getenv("KNPEMI_AMG_APART")) != 0;
-    if (const char* ft = getenv("KNPEMI_AMG_FILTER")) C.filter_theta = atof(ft);
     C.want_fused = !dist.on && use_fused();
     C.want_cycle = dist.on && use_fused() && !getenv("KNPEMI_DIST_PLAIN_CYCLE");
-    if ((rc = kn_amg_setup(h, G, n, rowptr, colind, vals, singular, dist.on ? owned.data() : nullptr))) return rc;
+    if ((rc = kn_amg_setup(sv, G, n, rowptr, colind, vals, singular, dist.on ? owned.data() : nullptr))) return rc;
     G.its_ref = -1;
     ++G.builds;
   } else if (!dist.on) {
     if (rebuild_every() > 0 && ++G.solves % rebuild_every() == 0) G.rebuild_wanted = true;
-    if (G.rebuild_wanted && (rc = kn_amg_rebuild_step(h, G, n, rowptr, colind, vals, singular))) return rc;
+    if (G.rebuild_wanted && (rc = kn_amg_rebuild_step(sv, G, n, rowptr, colind, vals, singular))) return rc;
   }
-  return kn_amg_refresh(h, G, vals);
+  return kn_amg_refresh(sv, G, vals);
 }
 
 // frozen hierarchy: rebuild at the next solve once it has visibly aged (`it`: iterations of the solve just finished)
-void amg_age(knpemi_handle* h, KnAmg& G, int it) {
+void amg_age(KnSolver& sv, KnAmg& G, int it) {
   if (G.its_ref < 0) G.its_ref = it;
-  else if (it > 2 * G.its_ref + 4) { if (h->dist.on) G.built = false; else G.rebuild_wanted = true; }
+  else if (it > 2 * G.its_ref + 4) { if (sv.dist.on) G.built = false; else G.rebuild_wanted = true; }
 }
 
 }  // namespace
 
-int kn_capture(knpemi_handle* h, const std::function<int()>& enqueue, hipGraphExec_t* out) {
+int kn_capture(KnSolver& sv, const std::function<int()>& enqueue, hipGraphExec_t* out) {
   *out = nullptr;
   hipGraph_t graph = nullptr;
-  KN_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+  KN_HIP(hipStreamBeginCapture(sv.own->stream, hipStreamCaptureModeThreadLocal));
   const int rc = enqueue();
-  hipError_t e = hipStreamEndCapture(h->stream, &graph);
+  hipError_t e = hipStreamEndCapture(sv.own->stream, &graph);
   if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
   if (e != hipSuccess) { kn_set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e)); return KNPEMI_EHIP; }
   e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
@@ -543,33 +529,63 @@ int kn_capture(knpemi_handle* h, const std::function<int()>& enqueue, hipGraphEx
   return KNPEMI_OK;
 }
 
-void kn_solver_free(knpemi_handle* h) {
-  for (KnAmg* G : {&h->amg_emi, &h->amg_knp}) {
+void kn_solver_free(KnSolver& sv) {
+  if (sv.own->stream) (void)hipStreamSynchronize(sv.own->stream);   // nothing in flight replays a graph or publishes its state
+  for (KnAmg* G : {&sv.amg_emi, &sv.amg_knp}) {
     kn_amg_async_join(*G);
     kn_amg_free(*G);
   }
-  if (h->kry_pinned) (void)hipHostFree(h->kry_pinned);
-  if (h->pub_host) (void)hipHostFree(h->pub_host);
-  kn_fused_graphs_free(h);
-  for (knpemi_handle::KnGraph* g : {&h->graph_emi, &h->graph_knp})
+  if (sv.kry_pinned) (void)hipHostFree(sv.kry_pinned);
+  if (sv.pub_host) (void)hipHostFree(sv.pub_host);
+  kn_fused_graphs_free(sv);
+  for (KnSolver::KnGraph* g : {&sv.graph_emi, &sv.graph_knp})
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
 }
 
+int kn_dist_enable(KnSolver& sv, const uint8_t* owned_emi, std::vector<uint8_t>&& owned_knp, void* reduce_buf_dev,
+                   knpemi_allreduce_fn allreduce, knpemi_halo_fn halo, void* ctx, const char* who) {
+  KnDist& d = sv.dist;
+  sv.amg_emi.built = false;      // the preconditioner changes with the ownership
+  sv.amg_knp.built = false;
+  if (!owned_emi) { d.on = false; return KNPEMI_OK; }
+  if (!reduce_buf_dev || !allreduce || !halo)
+    return kn_fail(KNPEMI_EINVAL, std::string(who) + ": reduction buffer and both communication hooks are required");
+  const int n = sv.emi.n;
+  hipStream_t st = sv.own->stream;
+  d.h_owned_emi.assign(owned_emi, owned_emi + n);
+  d.h_owned_knp = std::move(owned_knp);
+  int rc;
+  if ((rc = kn_upload(sv.own->allocs, d.h_owned_emi, &d.d_owned_emi))) return rc;
+  if ((rc = kn_upload(sv.own->allocs, d.h_owned_knp, &d.d_owned_knp))) return rc;
+  d.d_red = static_cast<double*>(reduce_buf_dev);
+  d.allreduce = allreduce; d.halo = halo; d.ctx = ctx;
+  // number of owned unknowns of the EMI system over all ranks (mean of the constant null space)
+  double cnt = 0.0;
+  for (int i = 0; i < n; ++i) cnt += owned_emi[i] ? 1.0 : 0.0;
+  KN_HIP(hipMemcpyAsync(d.d_red, &cnt, sizeof(double), hipMemcpyHostToDevice, st));
+  if (allreduce(ctx, 1)) return kn_fail(KNPEMI_EHIP, std::string(who) + ": allreduce hook failed");
+  KN_HIP(hipMemcpyAsync(&cnt, d.d_red, sizeof(double), hipMemcpyDeviceToHost, st));
+  KN_HIP(hipStreamSynchronize(st));
+  d.n_owned_global = cnt;
+  d.on = true;
+  return KNPEMI_OK;
+}
+
 // Workspace: 10 vectors of the larger system + ones + scalars + partials (allocated on first use).
-static int ensure_work(knpemi_handle* h, size_t n) {
-  if (h->kry_n >= n) return KNPEMI_OK;
+static int ensure_work(KnSolver& sv, size_t n) {
+  if (sv.kry_n >= n) return KNPEMI_OK;
   const size_t doubles = 11 * n + 64 + 3 * RED_BLOCKS + 2;   // + ticket counter of dots_kernel
-  if (int rc = kn_zeros(h->allocs, h->stream, doubles, &h->kry)) return rc;
-  h->kry_n = n;
+  if (int rc = kn_zeros(sv.own->allocs, sv.own->stream, doubles, &sv.kry)) return rc;
+  sv.kry_n = n;
   const std::vector<double> ones(n, 1.0);
-  return kn_to_device(h->stream, h->kry + 10 * n, ones.data(), n);
+  return kn_to_device(sv.own->stream, sv.kry + 10 * n, ones.data(), n);
 }
 
 // r_c = Phi^T r into the reduction buffer (all-reduced): every rank ends up with the whole coarse vector
 static void coarse_restrict(Ctx& c, const double* r) {
-  knpemi_handle* h = c.h;
-  KnDist& d = h->dist;
-  hipLaunchKernelGGL(coarse_restrict_kernel, dim3(d.nl), dim3(256), 0, h->stream, r, d.d_agg_ptr, d.d_agg_idx, d.d_agg_wt, d.nl,
+  KnSolver& sv = c.sv;
+  KnDist& d = sv.dist;
+  hipLaunchKernelGGL(coarse_restrict_kernel, dim3(d.nl), dim3(256), 0, sv.own->stream, r, d.d_agg_ptr, d.d_agg_idx, d.d_agg_wt, d.nl,
                      d.rank, d.world, d.d_red);
   if (int e = d.allreduce(d.ctx, KN_COARSE_OFF + d.nc)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
 }
@@ -578,13 +594,13 @@ static void coarse_restrict(Ctx& c, const double* r) {
 // restriction), then on the host the inverse of A_c + alpha 1 1^T (A_c has the constants in its kernel;
 // the residuals it is applied to have zero mean) with empty aggregates decoupled.
 static int coarse_setup(Ctx& c, double* work_phi, double* work_y) {
-  knpemi_handle* h = c.h;
-  KnDist& d = h->dist;
+  KnSolver& sv = c.sv;
+  KnDist& d = sv.dist;
   const int nc = d.nc, nl = d.nl;
   if (!d.d_coarse_inv) {
     int rc;
-    if ((rc = kn_alloc(h->allocs, (size_t)KN_COARSE_MAX * KN_COARSE_MAX, &d.d_coarse_inv))) return rc;
-    if ((rc = kn_alloc(h->allocs, KN_COARSE_MAX + 1, &d.d_coarse_z))) return rc;
+    if ((rc = kn_alloc(sv.own->allocs, (size_t)KN_COARSE_MAX * KN_COARSE_MAX, &d.d_coarse_inv))) return rc;
+    if ((rc = kn_alloc(sv.own->allocs, KN_COARSE_MAX + 1, &d.d_coarse_z))) return rc;
     // (KNPEMI_DEBUG_POISON_COARSE: all-ones bytes = NaN, for the test that no entry past the nl written ones is read)
     KN_HIP(hipMemset(d.d_coarse_z, getenv("KNPEMI_DEBUG_POISON_COARSE") ? 0xFF : 0, (KN_COARSE_MAX + 1) * sizeof(double)));
   }
@@ -592,11 +608,11 @@ static int coarse_setup(Ctx& c, double* work_phi, double* work_y) {
   for (int j = 0; j < nc; ++j) {
     const int rj = j / nl, aj = j % nl;
     // phi_j: 1 on the owned unknowns of aggregate aj of rank rj (ghost copies are filled by the SpMV's halo), 0 elsewhere
-    hipLaunchKernelGGL(coarse_prolong_kernel, grid1(c.n), dim3(256), 0, h->stream, c.n, d.d_agg_of, d.d_agg_w,
+    hipLaunchKernelGGL(coarse_prolong_kernel, grid1(c.n), dim3(256), 0, sv.own->stream, c.n, d.d_agg_of, d.d_agg_w,
                        (const double*)nullptr, work_phi, 1, rj == d.rank ? aj : -2);
     spmv(c, work_phi, work_y, nullptr);
     coarse_restrict(c, work_y);
-    if (int rc = kn_to_host(h->stream, col.data(), d.d_red + KN_COARSE_OFF, nc)) return rc;
+    if (int rc = kn_to_host(sv.own->stream, col.data(), d.d_red + KN_COARSE_OFF, nc)) return rc;
     if (c.comm_rc) { kn_set_error("coarse space set-up: a communication hook failed"); return KNPEMI_EHIP; }
     for (int i = 0; i < nc; ++i) Ac[(size_t)i * nc + j] = col[i];
   }
@@ -639,25 +655,26 @@ static int coarse_setup(Ctx& c, double* work_phi, double* work_y) {
 
 // z += Phi A_c^+ Phi^T r  (additive two-level correction next to the per-rank AMG)
 static void coarse_correct(Ctx& c, const double* r, double* z) {
-  knpemi_handle* h = c.h;
-  KnDist& d = h->dist;
+  KnSolver& sv = c.sv;
+  KnDist& d = sv.dist;
   coarse_restrict(c, r);
-  hipLaunchKernelGGL(coarse_solve_kernel, dim3(1), dim3(KN_COARSE_MAX), 0, h->stream, d.d_coarse_inv, d.d_red, d.nl, d.rank, d.nc,
+  hipLaunchKernelGGL(coarse_solve_kernel, dim3(1), dim3(KN_COARSE_MAX), 0, sv.own->stream, d.d_coarse_inv, d.d_red, d.nl, d.rank, d.nc,
                      d.d_coarse_z);
-  hipLaunchKernelGGL(coarse_prolong_kernel, grid1(c.n), dim3(256), 0, h->stream, c.n, d.d_agg_of, d.d_agg_w, d.d_coarse_z, z, 0, 0);
+  hipLaunchKernelGGL(coarse_prolong_kernel, grid1(c.n), dim3(256), 0, sv.own->stream, c.n, d.d_agg_of, d.d_agg_w, d.d_coarse_z, z, 0, 0);
 }
 
-// Jacobi-PCG on A_emi x = b_emi, x = phi (record component 7, gathered into a contiguous vector first).
-int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres) {
-  KnDev& D = h->dev;
-  const int n = D.Ntot;
-  int rc = ensure_work(h, (size_t)std::max(1, h->K - 1) * D.Ntot);
+// Jacobi-PCG on A_emi x = b_emi, x = phi (KnSolver::phi: a component of the records, gathered into a contiguous vector first).
+int kn_solve_emi(KnSolver& sv, double rtol, double atol, int maxit, int* iters, double* relres) {
+  const KnSysView& D = sv.emi;
+  const int n = D.n;
+  sv.phi_stored = false;
+  int rc = ensure_work(sv, (size_t)std::max(1, sv.ks) * D.n);
   if (rc) return rc;
-  const size_t N = h->kry_n;
-  double *x = h->kry, *r = x + N, *z = r + N, *p = z + N, *q = p + N, *b = q + N, *dinv = b + N, *ones = h->kry + 10 * N;
-  Ctx c{h, n, D.rowptr, D.colind, D.A_emi, h->kry + 11 * N, h->kry + 11 * N + 64};
-  c.lpr = spmv_lanes(h, KNPEMI_B_EMI, D.rowptr, n);
-  const KnDist& dist = h->dist;
+  const size_t N = sv.kry_n;
+  double *x = sv.kry, *r = x + N, *z = r + N, *p = z + N, *q = p + N, *b = q + N, *dinv = b + N, *ones = sv.kry + 10 * N;
+  Ctx c{sv, n, D.rowptr, D.colind, D.A, sv.kry + 11 * N, sv.kry + 11 * N + 64};
+  c.lpr = spmv_lanes(sv, KNPEMI_B_EMI, D.rowptr, n);
+  const KnDist& dist = sv.dist;
   bool has_ghosts = false;
   double n_mean = (double)n;
   if (dist.on) {   // partitioned problem: this rank's rows of the global system
@@ -665,32 +682,32 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
     c.which = KNPEMI_B_EMI;
     n_mean = dist.n_owned_global;
     for (uint8_t o : dist.h_owned_emi) has_ghosts |= !o;
-    hipLaunchKernelGGL(ghost_identity_kernel, grid1(n), dim3(256), 0, h->stream, n, c.rowptr, c.colind, c.owned, D.A_emi);
+    hipLaunchKernelGGL(ghost_identity_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.owned, D.A);
   }
-  if (h->kry_ones_masked != (dist.on ? 1 : 0)) {   // `ones` counts the owned unknowns
+  if (sv.kry_ones_masked != (dist.on ? 1 : 0)) {   // `ones` counts the owned unknowns
     if (dist.on) mask(c, ones, 1);
     else {
       std::vector<double> one(n, 1.0);
       KN_HIP(hipMemcpy(ones, one.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     }
-    h->kry_ones_masked = dist.on ? 1 : 0;
+    sv.kry_ones_masked = dist.on ? 1 : 0;
   }
   // x0 = current phi (ksp_initial_guess_nonzero), b = b_emi projected onto zero mean (constant null space).  With the
   // fused loop these launches open the captured graph of the solve's first chunk (kernels_fused.hip), hence the lambda.
   auto pre = [&]() -> int {
-    if (int e = kn_launch_field_gather(h, D.VR + 7, KN_REC, x, n)) return e;
+    if (int e = kn_launch_field_gather(sv.own->stream, sv.phi, sv.phi_stride, x, n)) return e;
     if (dist.on) {
-      vec(c, V_COPY, b, nullptr, D.b_emi, nullptr);
+      vec(c, V_COPY, b, nullptr, D.b, nullptr);
       mask(c, b);
       dots(c, 1, b, ones, nullptr, nullptr, nullptr, nullptr, OP_MEAN, 0, 0, 0, 1.0 / n_mean);
       vec(c, V_SHIFT, b, nullptr, nullptr, nullptr);
       mask(c, b);
     } else {   // single rank: the mean of b_emi itself, then copy and shift in one pass (same arithmetic)
-      dots(c, 1, D.b_emi, ones, nullptr, nullptr, nullptr, nullptr, OP_MEAN, 0, 0, 0, 1.0 / n_mean);
-      vec(c, V_COPY_SHIFT, b, nullptr, D.b_emi, nullptr);
+      dots(c, 1, D.b, ones, nullptr, nullptr, nullptr, nullptr, OP_MEAN, 0, 0, 0, 1.0 / n_mean);
+      vec(c, V_COPY_SHIFT, b, nullptr, D.b, nullptr);
     }
     // (single rank: the inverse diagonal comes out of the first residual below)
-    if (dist.on) hipLaunchKernelGGL(diag_inv_kernel, grid1(n), dim3(256), 0, h->stream, n, c.rowptr, c.colind, c.vals, dinv);
+    if (dist.on) hipLaunchKernelGGL(diag_inv_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.vals, dinv);
     return KNPEMI_OK;
   };
   // solution orthogonal to constants, then into the phi component of the vertex records (ghosts included: they take
@@ -700,25 +717,25 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
     if (dist.on) {
       if (int e = dist.halo(dist.ctx, x, KNPEMI_B_EMI)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
       vec(c, V_SHIFT, x, nullptr, nullptr, nullptr);
-      if (int e = kn_launch_field_scatter(h, x, D.VR + 7, n, KN_REC)) return e;
+      if (int e = kn_launch_field_scatter(sv.own->stream, x, sv.phi, n, sv.phi_stride)) return e;
     } else if (n > 0) {
-      hipLaunchKernelGGL(scatter_shift_kernel, grid1(n), dim3(256), 0, h->stream, x, D.VR + 7, n, KN_REC, c.sc);
+      hipLaunchKernelGGL(scatter_shift_kernel, grid1(n), dim3(256), 0, sv.own->stream, x, sv.phi, n, sv.phi_stride, c.sc);
     }
     return KNPEMI_OK;
   };
-  KnAmg& G = h->amg_emi;
-  const bool amg = h->pc_emi == KNPEMI_PC_AMG;
+  KnAmg& G = sv.amg_emi;
+  const bool amg = sv.pc_emi == KNPEMI_PC_AMG;
   // (the diagonal block of a rank that has ghosts has lost couplings: it is non-singular)
-  if (amg && (rc = amg_upkeep(h, G, n, D.rowptr, D.colind, D.A_emi, !has_ghosts, dist.h_owned_emi))) return rc;
+  if (amg && (rc = amg_upkeep(sv, G, n, D.rowptr, D.colind, D.A, !has_ghosts, dist.h_owned_emi))) return rc;
   // two-level variant on a partitioned mesh: the ranks' AMG cycles do not see each other, a coarse space of one
   // constant per (rank, sub-domain) carries the error across the cuts (knpemi_set_distributed_coarse)
-  const bool coarse = dist.on && amg && h->dist.nc > 0;
-  if (coarse && (!h->dist.coarse_built || G.its_ref < 0)) {
+  const bool coarse = dist.on && amg && sv.dist.nc > 0;
+  if (coarse && (!sv.dist.coarse_built || G.its_ref < 0)) {
     if ((rc = coarse_setup(c, p, q))) return rc;               // p, q are free before the first search direction
   }
   auto precond = [&]() -> int {
     if (amg) {
-      int e = kn_amg_apply(h, G, D.A_emi, dinv, r, q, z);      // q = A p is free here
+      int e = kn_amg_apply(sv, G, D.A, dinv, r, q, z);      // q = A p is free here
       if (e) return e;
       if (coarse) coarse_correct(c, r, z);
       return KNPEMI_OK;
@@ -731,8 +748,8 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   const bool fused = amg && G.fused_ok && !dist.on && use_fused();
   int it = 0;
   if (fused) {   // residual, target and the loop in 2 + (2 levels - 1) launches per iteration (kernels_fused.hip)
-    const KnFusedSys S{n, c.rowptr, c.colind, c.vals, c.sc, h->kry, N};
-    if ((rc = kn_fused_cg(h, G, S, D.b_emi, rtol, atol, maxit, &it, &sc[S_RR], &sc[S_BB], D.VR + 7, KN_REC))) return rc;
+    const KnFusedSys S{n, c.rowptr, c.colind, c.vals, c.sc, sv.kry, N};
+    if ((rc = kn_fused_cg(sv, G, S, D.b, rtol, atol, maxit, &it, &sc[S_RR], &sc[S_BB]))) return rc;
   } else {
     if ((rc = pre())) return rc;
     spmv(c, x, r, nullptr, b, dist.on ? nullptr : dinv);         // r = b - A x
@@ -757,10 +774,10 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
     vec(c, V_CG_P, p, nullptr, z, nullptr);
     return KNPEMI_OK;
   };
-  const uint64_t gkey = graph_key(h, G, amg, chunk, n);
+  const uint64_t gkey = graph_key(sv, G, amg, chunk, n);
   while (!fused && rn > target && it < maxit) {
     const int todo = std::min(chunk, maxit - it);
-    if (todo == chunk) { if ((rc = run_chunk(h, h->graph_emi, gkey, chunk, iteration))) return rc; }
+    if (todo == chunk) { if ((rc = run_chunk(sv, sv.graph_emi, gkey, chunk, iteration))) return rc; }
     else for (int k = 0; k < todo; ++k) if ((rc = iteration())) return rc;
     it += todo;
     if ((rc = read_scalars(c, sc, S_N))) return rc;
@@ -773,71 +790,69 @@ int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   if (iters) *iters = it;
   if (relres) *relres = bnorm > 0 ? rn / bnorm : rn;
   if ((rc = kn_launch_check("krylov (emi)"))) return rc;
-  if (amg) amg_age(h, G, it);
+  if (amg) amg_age(sv, G, it);
   if (rn > target) { kn_set_error("EMI CG did not converge (ksp_error_if_not_converged)"); return KNPEMI_ESOLVE; }
   return KNPEMI_OK;
 }
 
 // Jacobi-BiCGStab on the block-diagonal KNP system; x = c (csol, converted to the block order).
-int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres) {
-  KnDev& D = h->dev;
-  const int KS = h->K - 1;
-  const int n = KS * D.Ntot;
-  int rc = ensure_work(h, (size_t)std::max(1, h->K - 1) * D.Ntot);
+int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, double* relres) {
+  const KnSysView& D = sv.knp;
+  const int n = D.n;
+  int rc = ensure_work(sv, (size_t)std::max(1, sv.ks) * sv.emi.n);
   if (rc) return rc;
-  if (!D.krowptr) { kn_set_error("KNP monolithic pattern missing"); return KNPEMI_EINVAL; }
-  const size_t N = h->kry_n;
-  double *x = h->kry, *r = x + N, *rhat = r + N, *p = rhat + N, *v = p + N, *s = v + N, *t = s + N, *dinv = t + N;
-  double *phat = h->kry + 8 * N, *shat = h->kry + 9 * N;
-  Ctx c{h, n, D.krowptr, D.kcolind, D.A_knp, h->kry + 11 * N, h->kry + 11 * N + 64};
-  c.lpr = spmv_lanes(h, KNPEMI_B_KNP, D.krowptr, n);
-  const KnDist& dist = h->dist;
+  if (!D.rowptr) { kn_set_error("KNP monolithic pattern missing"); return KNPEMI_EINVAL; }
+  const size_t N = sv.kry_n;
+  double *x = sv.kry, *r = x + N, *rhat = r + N, *p = rhat + N, *v = p + N, *s = v + N, *t = s + N, *dinv = t + N;
+  double *phat = sv.kry + 8 * N, *shat = sv.kry + 9 * N;
+  Ctx c{sv, n, D.rowptr, D.colind, D.A, sv.kry + 11 * N, sv.kry + 11 * N + 64};
+  c.lpr = spmv_lanes(sv, KNPEMI_B_KNP, D.rowptr, n);
+  const KnDist& dist = sv.dist;
   if (dist.on) {
     c.owned = dist.d_owned_knp;
     c.which = KNPEMI_B_KNP;
-    hipLaunchKernelGGL(ghost_identity_kernel, grid1(n), dim3(256), 0, h->stream, n, c.rowptr, c.colind, c.owned, D.A_knp);
-    mask(c, D.b_knp);      // the ghost rows of the right-hand side are not assembled
+    hipLaunchKernelGGL(ghost_identity_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.owned, D.A);
+    mask(c, D.b);      // the ghost rows of the right-hand side are not assembled
   }
-  // x0 = previous concentrations in the block order [c[0][0], c[0][1], c[1][0], ...] (first launch of the solve: with the
-  // fused loop it opens the captured graph of the first chunk)
+  // x0 = previous concentrations in the solver's order (first launch of the solve: with the fused loop it opens the
+  // captured graph of the first chunk)
   auto pre = [&]() -> int {
-    if (h->plain_knp) vec(c, V_COPY, x, nullptr, D.csol, nullptr);
-    else hipLaunchKernelGGL(knp_order_kernel, grid1(n), dim3(256), 0, h->stream, D.Ntot, KS, h->n_sub, h->d_consts, x, D.csol, 1);
+    if (sv.knp_load) return sv.knp_load(x);
+    vec(c, V_COPY, x, nullptr, sv.csol, nullptr);
     return KNPEMI_OK;
   };
-  // the solution back into csol / the vertex records (+ the end-of-step update when it is fused); idempotent
+  // the solution back into csol, or wherever the owner takes it; idempotent
   auto post = [&]() -> int {
-    if (h->plain_knp) vec(c, V_COPY, D.csol, nullptr, x, nullptr);
-    else if (h->fuse_update) { if (int e = kn_launch_knp_writeback_update(h, x)) return e; }
-    else hipLaunchKernelGGL(knp_order_kernel, grid1(n), dim3(256), 0, h->stream, D.Ntot, KS, h->n_sub, h->d_consts, x, D.csol, 0);
+    if (sv.knp_store) return sv.knp_store(x);
+    vec(c, V_COPY, sv.csol, nullptr, x, nullptr);
     return KNPEMI_OK;
   };
-  const bool fused_planned = h->pc_knp == KNPEMI_PC_AMG && !dist.on && use_fused();
+  const bool fused_planned = sv.pc_knp == KNPEMI_PC_AMG && !dist.on && use_fused();
   if (!fused_planned && (rc = pre())) return rc;
-  KnAmg& G = h->amg_knp;
-  const bool amg = h->pc_knp == KNPEMI_PC_AMG;
+  KnAmg& G = sv.amg_knp;
+  const bool amg = sv.pc_knp == KNPEMI_PC_AMG;
   if (dist.on) {
-    hipLaunchKernelGGL(diag_inv_kernel, grid1(n), dim3(256), 0, h->stream, n, c.rowptr, c.colind, c.vals, dinv);
+    hipLaunchKernelGGL(diag_inv_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.vals, dinv);
     // Jacobi: the scaled SpMV A (dinv .* p) reads dinv on ghost columns, where the identity rows above left 1: take the
     // owners' 1 / a_ii instead, so that the recurrence residual stays b - A x (x is updated with the owners' dinv)
     if (!amg) if (int e = dist.halo(dist.ctx, dinv, KNPEMI_B_KNP)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
   }
-  if (amg && (rc = amg_upkeep(h, G, n, D.krowptr, D.kcolind, D.A_knp, false, dist.h_owned_knp))) return rc;
+  if (amg && (rc = amg_upkeep(sv, G, n, D.rowptr, D.colind, D.A, false, dist.h_owned_knp))) return rc;
   double sc[S_N];
   const bool fused = amg && G.fused_ok && !dist.on && use_fused();
   int it = 0, restarts = 0;
   if (fused) {   // residual, target and 3 + 2 cycles launches per iteration (kernels_fused.hip)
-    const KnFusedSys S{n, c.rowptr, c.colind, c.vals, c.sc, h->kry, N};
-    if (h->knp_method == 1) {      // GMRES(30) as PETSc runs the reference's options (KNPEMI_OPT_KNP_METHOD)
-      if ((rc = kn_fused_gmres(h, G, S, D.b_knp, rtol, atol, maxit, &it, &sc[S_RR], &sc[S_BB], pre, post))) return rc;
+    const KnFusedSys S{n, c.rowptr, c.colind, c.vals, c.sc, sv.kry, N};
+    if (sv.knp_method == 1) {      // GMRES(30) as PETSc runs the reference's options (KNPEMI_OPT_KNP_METHOD)
+      if ((rc = kn_fused_gmres(sv, G, S, D.b, rtol, atol, maxit, &it, &sc[S_RR], &sc[S_BB], pre, post))) return rc;
     } else
-    if ((rc = kn_fused_bicgstab(h, G, S, D.b_knp, rtol, atol, maxit, &it, &sc[S_RR], &sc[S_BB], pre, post))) return rc;
+    if ((rc = kn_fused_bicgstab(sv, G, S, D.b, rtol, atol, maxit, &it, &sc[S_RR], &sc[S_BB], pre, post))) return rc;
   } else {
     if (fused_planned && (rc = pre())) return rc;      // (the hierarchy did not qualify for the fused loop after all)
-    spmv(c, x, r, nullptr, D.b_knp, dist.on ? nullptr : dinv);   // r = b - A x
+    spmv(c, x, r, nullptr, D.b, dist.on ? nullptr : dinv);   // r = b - A x
     vec(c, V_COPY, rhat, nullptr, r, nullptr);
-    hipLaunchKernelGGL(bicg_init_kernel, grid1(std::max(n, (int)S_N)), dim3(256), 0, h->stream, n, p, v, c.sc);
-    dots(c, 2, r, r, D.b_knp, D.b_knp, nullptr, nullptr, OP_START);
+    hipLaunchKernelGGL(bicg_init_kernel, grid1(std::max(n, (int)S_N)), dim3(256), 0, sv.own->stream, n, p, v, c.sc);
+    dots(c, 2, r, r, D.b, D.b, nullptr, nullptr, OP_START);
     if ((rc = read_scalars(c, sc, S_N))) return rc;
     if ((rc = check_start("KNP BiCGStab", sc))) return rc;
   }
@@ -851,31 +866,31 @@ int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
       dots(c, 1, rhat, r, nullptr, nullptr, nullptr, nullptr, OP_BI_RHO);
       vec(c, V_BI_P, p, nullptr, r, v);
       if (amg) {
-        if ((rc = kn_amg_apply(h, G, D.A_knp, dinv, p, t, phat))) return rc;   // t is free here
+        if ((rc = kn_amg_apply(sv, G, D.A, dinv, p, t, phat))) return rc;   // t is free here
         spmv(c, phat, v, nullptr);
       } else spmv(c, p, v, dinv);                           // v = A M^-1 p
       dots(c, 1, rhat, v, nullptr, nullptr, nullptr, nullptr, OP_BI_ALPHA);
       vec(c, V_BI_S, s, nullptr, r, v);
       if (amg) {
-        if ((rc = kn_amg_apply(h, G, D.A_knp, dinv, s, t, shat))) return rc;
+        if ((rc = kn_amg_apply(sv, G, D.A, dinv, s, t, shat))) return rc;
         spmv(c, shat, t, nullptr);
       } else spmv(c, s, t, dinv);                           // t = A M^-1 s
       dots(c, 2, t, s, t, t, nullptr, nullptr, OP_BI_OMEGA);
       if (amg)
-        hipLaunchKernelGGL(bicg_update_kernel, grid1(n), dim3(256), 0, h->stream, n, c.sc, x, r, phat, shat, s, t,
+        hipLaunchKernelGGL(bicg_update_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.sc, x, r, phat, shat, s, t,
                            (const double*)nullptr);
       else
-        hipLaunchKernelGGL(bicg_update_kernel, grid1(n), dim3(256), 0, h->stream, n, c.sc, x, r, p, s, s, t, dinv);
+        hipLaunchKernelGGL(bicg_update_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.sc, x, r, p, s, s, t, dinv);
       dots(c, 1, r, r, nullptr, nullptr, nullptr, nullptr, OP_STORE3, S_RR);
     return rc;
   };
-  const uint64_t gkey = graph_key(h, G, amg, chunk, n);
+  const uint64_t gkey = graph_key(sv, G, amg, chunk, n);
   // ksp_min_it (pdeSolver.py:101).  With KNPEMI_OPT_KNP_METHOD = 1 it counts GMRES iterations; where this BiCGStab loop runs
   // instead (partitioned problems, Jacobi preconditioning) an iteration applies operator and preconditioner twice
-  const int min_it = std::max(0, std::min(h->knp_method == 1 ? (h->knp_min_it + 1) / 2 : h->knp_min_it, maxit));
+  const int min_it = std::max(0, std::min(sv.knp_method == 1 ? (sv.knp_min_it + 1) / 2 : sv.knp_min_it, maxit));
   while (!fused && (rn > target || (it < min_it && rn != 0.0)) && it < maxit) {
     const int todo = std::min(chunk, maxit - it);
-    if (todo == chunk) { if ((rc = run_chunk(h, h->graph_knp, gkey, chunk, iteration))) return rc; }
+    if (todo == chunk) { if ((rc = run_chunk(sv, sv.graph_knp, gkey, chunk, iteration))) return rc; }
     else for (int k = 0; k < todo; ++k) if ((rc = iteration())) return rc;
     it += todo;
     if ((rc = read_scalars(c, sc, S_N))) return rc;
@@ -893,7 +908,7 @@ int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
         return KNPEMI_ESOLVE;
       }
       vec(c, V_COPY, rhat, nullptr, r, nullptr);
-      hipLaunchKernelGGL(bicg_init_kernel, grid1(std::max(n, (int)S_N)), dim3(256), 0, h->stream, n, p, v, c.sc);
+      hipLaunchKernelGGL(bicg_init_kernel, grid1(std::max(n, (int)S_N)), dim3(256), 0, sv.own->stream, n, p, v, c.sc);
     }
   }
   if (dist.on) if (int e = dist.halo(dist.ctx, x, KNPEMI_B_KNP)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
@@ -902,7 +917,7 @@ int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* ite
   if (iters) *iters = it;
   if (relres) *relres = bnorm > 0 ? rn / bnorm : rn;
   if ((rc = kn_launch_check("krylov (knp)"))) return rc;
-  if (amg) amg_age(h, G, it);
+  if (amg) amg_age(sv, G, it);
   if (rn > target) { kn_set_error("KNP BiCGStab did not converge (ksp_error_if_not_converged)"); return KNPEMI_ESOLVE; }
   return KNPEMI_OK;
 }
@@ -918,27 +933,26 @@ int kn_launch_knp_order(knpemi_handle* h, double* x, int to_blocks) {
 }
 
 // Initial guess of the next solve: instead of the previous solution (ksp_initial_guess_nonzero) the extrapolation of the
-// last solutions -- 3 x_n - 3 x_(n-1) + x_(n-2) once three are known, 2 x_n - x_(n-1) before -- written into phi (record
-// component 7) / csol in place.  Only the starting point changes; the solves still stop on the same residual criterion.
-int kn_extrapolate_guess(knpemi_handle* h, int which) {
-  KnDev& D = h->dev;
+// last solutions -- 3 x_n - 3 x_(n-1) + x_(n-2) once three are known, 2 x_n - x_(n-1) before -- written into phi / csol
+// in place.  Only the starting point changes; the solves still stop on the same residual criterion.
+int kn_extrapolate_guess(KnSolver& sv, int which) {
   const int slot = which == KNPEMI_B_EMI ? 0 : 1;
-  const int n = slot == 0 ? D.Ntot : (h->K - 1) * D.Ntot;
+  const int n = slot == 0 ? sv.emi.n : sv.knp.n;
   if (n == 0) return KNPEMI_OK;
   // order 2 (default) extrapolates through the last three solutions: 5.3 instead of 5.85 CG iterations per step while the
   // cell fires at config 2, 3.5 instead of 3.8 over the first 72 steps; KNPEMI_EXTRAPOLATE_ORDER=1: 2 x_n - x_(n-1)
   static const int order = getenv("KNPEMI_EXTRAPOLATE_ORDER") ? atoi(getenv("KNPEMI_EXTRAPOLATE_ORDER")) : 2;
-  if (!h->guess_old[slot]) {
-    if (int rc = kn_alloc(h->allocs, 2 * (size_t)n, &h->guess_old[slot])) return rc;
-    h->guess_have[slot] = slot == 0 ? -1 : 0;
+  if (!sv.guess_old[slot]) {
+    if (int rc = kn_alloc(sv.own->allocs, 2 * (size_t)n, &sv.guess_old[slot])) return rc;
+    sv.guess_have[slot] = slot == 0 ? -1 : 0;
   }
   // the potential a run starts with is a guess, not a solution of the system (the concentrations it starts with are the
   // initial condition, i.e. the first point of the trajectory): no history from it -- 2 x_1 - x_0 with that x_0 cost the
   // second and third solves of a run twice their iterations
-  if (h->guess_have[slot] < 0) { h->guess_have[slot] = 0; return KNPEMI_OK; }
-  double* cur = slot == 0 ? D.VR + 7 : D.csol;
-  hipLaunchKernelGGL(extrapolate_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, cur, slot == 0 ? KN_REC : 1,
-                     h->guess_old[slot], order >= 2 ? h->guess_old[slot] + n : (double*)nullptr, h->guess_have[slot]);
-  h->guess_have[slot] = std::min(2, h->guess_have[slot] + 1);
+  if (sv.guess_have[slot] < 0) { sv.guess_have[slot] = 0; return KNPEMI_OK; }
+  double* cur = slot == 0 ? sv.phi : sv.csol;
+  hipLaunchKernelGGL(extrapolate_kernel, dim3((n + 255) / 256), dim3(256), 0, sv.own->stream, n, cur, slot == 0 ? sv.phi_stride : 1,
+                     sv.guess_old[slot], order >= 2 ? sv.guess_old[slot] + n : (double*)nullptr, sv.guess_have[slot]);
+  sv.guess_have[slot] = std::min(2, sv.guess_have[slot] + 1);
   return kn_launch_check("extrapolate_kernel");
 }

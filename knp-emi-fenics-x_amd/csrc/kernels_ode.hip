@@ -180,7 +180,7 @@ bool sweep_emi_eligible(knpemi_handle* h, const KnOdeModel& m, int n_sweep) {
   const char* want = getenv("KNPEMI_FUSED_SWEEP");
   if (want ? atoi(want) == 0 : !SWEEP_EMI_DEFAULT) return false;
   if (m.rtc_module || m.method != KNPEMI_ODE_LSODA || getenv("KNPEMI_ODE_STAMPS") || getenv("KNPEMI_ODE_WAVES")) return false;
-  if (h->ode_only || h->dist.on || !kn_sweep_emi_rows_ok(h)) return false;
+  if (h->ode_only || h->solver.dist.on || !kn_sweep_emi_rows_ok(h)) return false;
   int bound = 0;
   for (const KnOdeModel& o : h->ode) bound += o.bound;
   if (bound != 1) return false;

@@ -70,6 +70,35 @@ int kn_gamma_quadrature(int NF, std::vector<double>* out) {
   return 16;
 }
 
+// The handle's systems, hooks and AMG choices for its solver (KnSolver): the concentrations are solved in the reference's
+// block order, the potential is component 7 of the vertex records.
+static void kn_solver_attach(knpemi_handle* h) {
+  const KnDev& D = h->dev;
+  KnSolver& sv = h->solver;
+  sv.ks = h->K - 1;
+  sv.emi = {D.Ntot, D.rowptr, D.colind, D.A_emi, D.b_emi};
+  sv.knp = {sv.ks * D.Ntot, D.krowptr, D.kcolind, D.A_knp, D.b_knp};
+  sv.csol = D.csol;
+  sv.phi = D.VR + 7;
+  sv.phi_stride = KN_REC;
+  sv.knp_load = [h](double* x) { return kn_launch_knp_order(h, x, 1); };
+  // (+ the end-of-step update when it is fused)
+  sv.knp_store = [h](const double* x) {
+    return h->fuse_update ? kn_launch_knp_writeback_update(h, x) : kn_launch_knp_order(h, const_cast<double*>(x), 0);
+  };
+  for (KnAmg* G : {&sv.amg_emi, &sv.amg_knp}) {
+    // stretched Q1 cells couple the two ends of an edge along the long direction positively: aggregate_apart keeps them
+    // in different aggregates (config 2h: 9.35 / 3.95 -> 7.4 / 2.9 iterations per solve; on simplices the plain greedy
+    // pass is the better one, 5.3 / 2.35 against 5.75 / 2.6 at config 2)
+    G->cfg.positive_conflict = h->NV == 8;
+    // prolongator smoothing along the large couplings only (KnAmgConfig::filter_theta): the operator complexity falls
+    // from 2.5-2.8 to 1.5 on simplices, the iteration counts stay (995 k tets: 6.65 / 2.8 -> 6.75 / 2.85, 3.34 -> 2.37 ms
+    // per step with solves).  "Large" is by magnitude: the big positive entries of stretched Q1 cells stay in the
+    // smoothing (lumping them into the diagonal cost config 2h 7.4 -> 12.6 iterations).
+    G->cfg.filter_theta = 0.02;
+  }
+}
+
 extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_handle** out) {
   if (!d || !out) return kn_fail(KNPEMI_EINVAL, "knpemi_create: null argument");
   *out = nullptr;
@@ -938,6 +967,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   for (int s = S + 1; s <= KN_MAXSUB; ++s) { C.voff[s] = h->voff[S]; C.qoff[s] = h->qoff[S]; }
   C.splitting = 1;
 
+  kn_solver_attach(h);
   *out = guard.release();
   return KNPEMI_OK;
 }
@@ -996,7 +1026,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->aux) (void)hipStreamDestroy(h->aux);
   kn_comm_destroy(h);
-  kn_solver_free(h);
+  kn_solver_free(h->solver);
   kn_record_free(h);
   for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
   kn_device_close(h);
@@ -1096,7 +1126,7 @@ extern "C" int knpemi_set_field(knpemi_handle* h, int field, int sub, int idx, c
   KN_HIP(hipSetDevice(h->device));
   if (L.stride == 1) return kn_to_device(h->stream, L.base, host, n);
   KN_HIP(hipMemcpyAsync(h->d_stage, host, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  rc = kn_launch_field_scatter(h, h->d_stage, L.base, (int)n, L.stride);
+  rc = kn_launch_field_scatter(h->stream, h->d_stage, L.base, (int)n, L.stride);
   if (rc) return rc;
   KN_HIP(hipStreamSynchronize(h->stream));
   return KNPEMI_OK;
@@ -1112,7 +1142,7 @@ extern "C" int knpemi_get_field(knpemi_handle* h, int field, int sub, int idx, d
   KN_HIP(hipSetDevice(h->device));
   const double* src = L.base;
   if (L.stride != 1) {
-    rc = kn_launch_field_gather(h, L.base, L.stride, h->d_stage, (int)n);
+    rc = kn_launch_field_gather(h->stream, L.base, L.stride, h->d_stage, (int)n);
     if (rc) return rc;
     src = h->d_stage;
   }
@@ -1229,7 +1259,18 @@ extern "C" int knpemi_solve_emi(knpemi_handle* h, double rtol, double atol, int 
   KN_HIP(hipSetDevice(h->device));
   // a matrix assembled on the auxiliary stream is complete, and so is every sweep whose output the right-hand side holds
   if (int rc = kn_wait_ode_joins(h)) return rc;
-  return kn_solve_emi(h, rtol, atol, maxit, iters, relres);
+  // KNPEMI_OPT_FOLD_MEMBRANE: the launch that writes the potential back also integrates the membrane facets of b_knp
+  KnSolver& sv = h->solver;
+  const int split = (h->emi_flags & KNPEMI_NO_SPLITTING) ? 0 : 1;
+  if (h->fold_membrane && !h->fuse_membrane && h->have_params)
+    sv.phi_store = [h](const double* x, const double* part, int np, double inv_n, double* mean_out) {
+      return kn_launch_emi_writeback_membrane(h, x, part, np, inv_n, mean_out);
+    };
+  else sv.phi_store = nullptr;
+  sv.emi_key = sv.phi_store ? 2 + split : 0;
+  const int rc = kn_solve_emi(sv, rtol, atol, maxit, iters, relres);
+  if (sv.phi_stored) kn_gam_formed(h, split);
+  return rc;
 }
 
 extern "C" int knpemi_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres) {
@@ -1241,7 +1282,8 @@ extern "C" int knpemi_solve_knp(knpemi_handle* h, double rtol, double atol, int 
   // before the set-up's device-to-host copy and the first iteration read them (round-3 advisor finding: this entry point
   // waited on neither join event)
   if (int rc = kn_wait_ode_joins(h)) return rc;
-  return kn_solve_knp(h, rtol, atol, maxit, iters, relres);
+  h->solver.knp_key = h->fuse_update;
+  return kn_solve_knp(h->solver, rtol, atol, maxit, iters, relres);
 }
 
 extern "C" int knpemi_extrapolate_guess(knpemi_handle* h, int which) {
@@ -1249,7 +1291,7 @@ extern "C" int knpemi_extrapolate_guess(knpemi_handle* h, int which) {
   if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return kn_fail(KNPEMI_EINVAL, "knpemi_extrapolate_guess: unknown system");
   kn_inputs_changed(h);
   KN_HIP(hipSetDevice(h->device));
-  return kn_extrapolate_guess(h, which);
+  return kn_extrapolate_guess(h->solver, which);
 }
 
 extern "C" int knpemi_solver_setup(knpemi_handle* h, int which, int precond, double theta) {
@@ -1257,8 +1299,8 @@ extern "C" int knpemi_solver_setup(knpemi_handle* h, int which, int precond, dou
   if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return kn_fail(KNPEMI_EINVAL, "knpemi_solver_setup: unknown system");
   if (precond != KNPEMI_PC_JACOBI && precond != KNPEMI_PC_AMG)
     return kn_fail(KNPEMI_EINVAL, "knpemi_solver_setup: unknown preconditioner");
-  KnAmg& G = which == KNPEMI_B_EMI ? h->amg_emi : h->amg_knp;
-  (which == KNPEMI_B_EMI ? h->pc_emi : h->pc_knp) = precond;
+  KnAmg& G = which == KNPEMI_B_EMI ? h->solver.amg_emi : h->solver.amg_knp;
+  (which == KNPEMI_B_EMI ? h->solver.pc_emi : h->solver.pc_knp) = precond;
   G.cfg.theta = theta > 0 ? theta : 0.08;
   G.built = false;
   return KNPEMI_OK;
@@ -1267,7 +1309,7 @@ extern "C" int knpemi_solver_setup(knpemi_handle* h, int which, int precond, dou
 extern "C" int knpemi_solver_info(knpemi_handle* h, int which, int* levels, double* op_complexity, int* builds) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   if (which != KNPEMI_B_EMI && which != KNPEMI_B_KNP) return kn_fail(KNPEMI_EINVAL, "knpemi_solver_info: unknown system");
-  const KnAmg& G = which == KNPEMI_B_EMI ? h->amg_emi : h->amg_knp;
+  const KnAmg& G = which == KNPEMI_B_EMI ? h->solver.amg_emi : h->solver.amg_knp;
   if (levels) *levels = (int)G.lev.size();
   if (op_complexity) *op_complexity = G.op_complexity;
   if (builds) *builds = G.builds;
@@ -1395,17 +1437,16 @@ extern "C" int knpemi_set_solution(knpemi_handle* h, int which, const double* x,
     }
     // a solution pasted on the device stands for the write-back of knpemi_solve_emi: the same launch, facet integrals of
     // b_knp included (KNPEMI_OPT_FOLD_MEMBRANE), which read phi_M and I_ch: ordered after the sweeps on the side streams
-    if (on_device && h->fold_membrane && h->have_params && !h->fuse_membrane && !h->dist.on) {
+    if (on_device && h->fold_membrane && h->have_params && !h->fuse_membrane && !h->solver.dist.on) {
       if (int rc = kn_wait_ode_joins(h)) return rc;
       if (int rc = kn_launch_emi_writeback_membrane(h, src, nullptr, 0, 0.0, nullptr)) return rc;
       kn_gam_formed(h, (h->emi_flags & KNPEMI_NO_SPLITTING) ? 0 : 1);
-    } else if (int rc = kn_launch_field_scatter(h, src, D.VR + 7, D.Ntot, KN_REC)) return rc;
+    } else if (int rc = kn_launch_field_scatter(h->stream, src, D.VR + 7, D.Ntot, KN_REC)) return rc;
   } else if (which == KNPEMI_B_KNP) {
     const int KS = h->K - 1;
     if (on_device) {   // one launch, as the write-back of knpemi_solve_knp
       if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_set_solution: knpemi_set_params not called");
-      int rc = h->fuse_update ? kn_launch_knp_writeback_update(h, x) : kn_launch_knp_order(h, const_cast<double*>(x), 0);
-      if (rc) return rc;
+      if (int rc = h->solver.knp_store(x)) return rc;
     } else
     for (int s = 0; s < h->n_sub; ++s)
       for (int k = 0; k < KS; ++k) {
@@ -1432,7 +1473,7 @@ extern "C" int knpemi_get_solution(knpemi_handle* h, int which, double* x) {
   KN_HIP(hipSetDevice(h->device));
   KnDev& D = h->dev;
   if (which == KNPEMI_B_EMI) {
-    int rc = kn_launch_field_gather(h, D.VR + 7, KN_REC, h->d_stage, D.Ntot);
+    int rc = kn_launch_field_gather(h->stream, D.VR + 7, KN_REC, h->d_stage, D.Ntot);
     if (rc) return rc;
     KN_HIP(hipMemcpyAsync(x, h->d_stage, (size_t)D.Ntot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   } else if (which == KNPEMI_B_KNP) {
@@ -1717,44 +1758,23 @@ extern "C" int knpemi_set_distributed(knpemi_handle* h, const uint8_t* owned, vo
                                       knpemi_allreduce_fn allreduce, knpemi_halo_fn halo, void* ctx) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   kn_inputs_changed(h);          // whether the write-back of the potential folds changes with it
-  KnDist& d = h->dist;
-  h->amg_emi.built = false;      // the preconditioner changes with the ownership
-  h->amg_knp.built = false;
-  if (!owned) { d.on = false; return KNPEMI_OK; }
-  if (!reduce_buf_dev || !allreduce || !halo)
-    return kn_fail(KNPEMI_EINVAL, "knpemi_set_distributed: reduction buffer and both communication hooks are required");
   KN_HIP(hipSetDevice(h->device));
   const int Ntot = h->dev.Ntot, KS = h->K - 1;
-  d.h_owned_emi.assign(owned, owned + Ntot);
-  d.h_owned_knp.assign((size_t)KS * Ntot, 0);
-  for (int s = 0; s < h->n_sub; ++s) {
-    const int v0 = h->voff[s], nv = h->n_vert[s];
-    for (int k = 0; k < KS; ++k)
-      for (int v = 0; v < nv; ++v) d.h_owned_knp[(size_t)KS * v0 + (size_t)k * nv + v] = owned[v0 + v];
+  std::vector<uint8_t> owned_knp;   // the concentration system's order: [sub-domain][ion][vertex]
+  if (owned) {
+    owned_knp.assign((size_t)KS * Ntot, 0);
+    for (int s = 0; s < h->n_sub; ++s) {
+      const int v0 = h->voff[s], nv = h->n_vert[s];
+      for (int k = 0; k < KS; ++k)
+        for (int v = 0; v < nv; ++v) owned_knp[(size_t)KS * v0 + (size_t)k * nv + v] = owned[v0 + v];
+    }
   }
-  int rc;
-  const uint8_t* p = nullptr;
-  if ((rc = kn_upload(h->allocs, d.h_owned_emi, &p))) return rc;
-  d.d_owned_emi = const_cast<uint8_t*>(p);
-  if ((rc = kn_upload(h->allocs, d.h_owned_knp, &p))) return rc;
-  d.d_owned_knp = const_cast<uint8_t*>(p);
-  d.d_red = static_cast<double*>(reduce_buf_dev);
-  d.allreduce = allreduce; d.halo = halo; d.ctx = ctx;
-  // number of owned unknowns of the EMI system over all ranks (mean of the constant null space)
-  double cnt = 0.0;
-  for (int i = 0; i < Ntot; ++i) cnt += owned[i] ? 1.0 : 0.0;
-  KN_HIP(hipMemcpyAsync(d.d_red, &cnt, sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (allreduce(ctx, 1)) return kn_fail(KNPEMI_EHIP, "knpemi_set_distributed: allreduce hook failed");
-  KN_HIP(hipMemcpyAsync(&cnt, d.d_red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  KN_HIP(hipStreamSynchronize(h->stream));
-  d.n_owned_global = cnt;
-  d.on = true;
-  return KNPEMI_OK;
+  return kn_dist_enable(h->solver, owned, std::move(owned_knp), reduce_buf_dev, allreduce, halo, ctx, "knpemi_set_distributed");
 }
 
 extern "C" int knpemi_set_distributed_coarse(knpemi_handle* h, int rank, int world) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
-  KnDist& d = h->dist;
+  KnDist& d = h->solver.dist;
   if (world <= 1) { d.nc = 0; d.coarse_built = false; return KNPEMI_OK; }
   if (rank < 0 || rank >= world) return kn_fail(KNPEMI_EINVAL, "knpemi_set_distributed_coarse: bad rank");
   if (world * h->n_sub > KN_COARSE_MAX)
@@ -1836,13 +1856,13 @@ extern "C" int knpemi_set_distributed_coarse(knpemi_handle* h, int rank, int wor
 extern "C" int knpemi_vec_gather(knpemi_handle* h, const void* vec_dev, const int32_t* idx_dev, int n, void* buf_dev) {
   if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_vec_gather: bad argument");
   KN_HIP(hipSetDevice(h->device));
-  return kn_launch_vec_index(h, static_cast<double*>(const_cast<void*>(vec_dev)), idx_dev, n, static_cast<double*>(buf_dev), 1);
+  return kn_launch_vec_index(h->stream, static_cast<double*>(const_cast<void*>(vec_dev)), idx_dev, n, static_cast<double*>(buf_dev), 1);
 }
 
 extern "C" int knpemi_vec_scatter(knpemi_handle* h, void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev) {
   if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_vec_scatter: bad argument");
   KN_HIP(hipSetDevice(h->device));
-  return kn_launch_vec_index(h, static_cast<double*>(vec_dev), idx_dev, n, static_cast<double*>(const_cast<void*>(buf_dev)), 0);
+  return kn_launch_vec_index(h->stream, static_cast<double*>(vec_dev), idx_dev, n, static_cast<double*>(const_cast<void*>(buf_dev)), 0);
 }
 
 extern "C" int knpemi_set_option(knpemi_handle* h, int option, int value) {
@@ -1864,18 +1884,18 @@ extern "C" int knpemi_set_option(knpemi_handle* h, int option, int value) {
   }
   if (option == KNPEMI_OPT_KNP_METHOD) {
     if (value != 0 && value != 1) return kn_fail(KNPEMI_EINVAL, "KNPEMI_OPT_KNP_METHOD: 0 (BiCGStab) or 1 (GMRES)");
-    h->knp_method = value;
+    h->solver.knp_method = value;
     return KNPEMI_OK;
   }
   if (option == KNPEMI_OPT_EMI_NORM) {
     if (value != 0 && value != 1) return kn_fail(KNPEMI_EINVAL, "KNPEMI_OPT_EMI_NORM: 0 (true residual) or 1 (preconditioned)");
-    h->emi_norm_pre = value;
+    h->solver.emi_norm_pre = value;
     return KNPEMI_OK;
   }
   if (option == KNPEMI_OPT_FOLD_MEMBRANE) { h->fold_membrane = value ? 1 : 0; return KNPEMI_OK; }
   if (option == KNPEMI_OPT_KNP_MIN_IT) {
     if (value < 0) return kn_fail(KNPEMI_EINVAL, "KNPEMI_OPT_KNP_MIN_IT: negative");
-    h->knp_min_it = value;
+    h->solver.knp_min_it = value;
     return KNPEMI_OK;
   }
   return kn_fail(KNPEMI_EINVAL, "knpemi_set_option: unknown option");

@@ -269,8 +269,9 @@ struct KnAmgLevel {
   double *x = nullptr, *r = nullptr, *t = nullptr;
 };
 struct KnAmgAsync;     // a rebuild running on a host thread (kernels_amg.hip)
-// How a hierarchy is built: set by the owner of the system before the first build (kernels_krylov.hip: amg_upkeep, the DG
-// solver handle in kernels_dg.hip), read by the set-up and carried whole into a background rebuild.
+// How a hierarchy is built: set by the owner of the system (knpemi_api.hip: kn_solver_attach; kernels_dg.hip: dg_solver)
+// and, for what depends on the run, at the build (kernels_krylov.hip: amg_upkeep); read by the set-up and carried whole
+// into a background rebuild.
 struct KnAmgConfig {
   bool negative_strength = false;    // strength of connection from -a_ij only (classical) instead of |a_ij|
   double theta = 0.08;               // strength threshold
@@ -320,39 +321,7 @@ struct KnAmg {
 };
 void kn_amg_free(KnAmg& G);
 void kn_amg_async_join(KnAmg& G);    // ends (waits for) a background rebuild; before the hierarchy or its handle goes away
-struct knpemi_handle;
-int kn_amg_setup(knpemi_handle* h, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
-                 bool singular, const uint8_t* h_owned = nullptr);
-// G.rebuild_wanted: start the rebuild of an aged hierarchy on a host thread from a snapshot of the operator, or swap a
-// finished one in; G stays usable throughout
-int kn_amg_rebuild_step(knpemi_handle* h, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
-                        bool singular);
-int kn_amg_apply(knpemi_handle* h, KnAmg& G, const double* vals, const double* dinv0, const double* r, double* scratch,
-                 double* out);
-int kn_amg_refresh(knpemi_handle* h, KnAmg& G, const double* vals);   // block inverses of the current finest operator
-// fused solver loops (kernels_fused.hip): the iteration of kn_solve_emi / kn_solve_knp in 6 / 13 launches
-struct KnFusedSys {
-  int n; const int* rowptr; const int* colind; const double* vals;   // the system of the current time step
-  double* sc; double* work;   // the solver's device scalars and vector workspace (kernels_krylov.hip layout)
-  size_t N;                   // stride of the workspace vectors
-};
-int kn_fused_subcycle(knpemi_handle* h, KnAmg& G, int l0, const double* r0 = nullptr, double* out0 = nullptr);
-// pre / post: what the caller has to run before the first residual / after the last iteration (both become part of the
-// captured graph of a chunk; post must be idempotent, it follows every chunk)
-int kn_fused_cg(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
-                int* iters, double* rr, double* bb, double* phi, int phi_stride);
-int kn_fused_bicgstab(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
-                      int* iters, double* rr, double* bb, const std::function<int()>& pre, const std::function<int()>& post);
-int kn_fused_gmres(knpemi_handle* h, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
-                   int* iters, double* rr, double* bb, const std::function<int()>& pre, const std::function<int()>& post);
-void kn_fused_graphs_free(knpemi_handle* h);
-// captures what `enqueue` launches on h->stream into *out (nullptr on failure): the one capture path of the Krylov loops
-int kn_capture(knpemi_handle* h, const std::function<int()>& enqueue, hipGraphExec_t* out);
-// frees the solver state of a handle: AMG hierarchies (background rebuilds joined), pinned and published host buffers,
-// captured graphs -- knpemi_destroy and knpemi_dg_destroy (its solver handle)
-void kn_solver_free(knpemi_handle* h);
-
-// Distributed solves (knpemi_set_distributed)
+// Distributed solves (knpemi_set_distributed, knpemi_dg_set_distributed: kn_dist_enable)
 struct KnDist {
   bool on = false;
   std::vector<uint8_t> h_owned_emi, h_owned_knp;   // host masks in the unknown order of the two systems
@@ -377,6 +346,90 @@ struct KnDist {
 };
 #define KN_COARSE_MAX 64
 #define KN_COARSE_OFF 8                            // coarse vector sits behind the 8 scalars of the reduction buffer
+
+// The device solves (kernels_krylov.hip, kernels_fused.hip, kernels_amg.hip): everything they read and keep, and nothing
+// else.  knpemi_handle and knpemi_dg each embed one; the owner fills the views, the hooks and the AMG configuration
+// (knpemi_create; kernels_dg.hip: dg_solver), the solver files never see the owner's type.
+struct KnDevice;
+struct KnSysView { int n = 0; const int* rowptr = nullptr; const int* colind = nullptr; double* A = nullptr; double* b = nullptr; };
+struct KnSolver {
+  explicit KnSolver(KnDevice* owner) : own(owner) {}
+  KnDevice* own;                       // device, main stream, `allocs` (what the solves allocate lives as long as the owner), prof
+  // views of the owner's two systems: the potential, and the block-diagonal system of the `ks` solved ions
+  KnSysView emi, knp;
+  int ks = 0;
+  double* csol = nullptr;              // [ks][emi.n] the concentrations, the iterate and the result of kn_solve_knp
+  double* phi = nullptr;               // the potential, iterate and result of kn_solve_emi: phi[i * phi_stride]
+  int phi_stride = 1;
+  // What the owner does around a solve, as data it supplies.  An empty hook stands for the plain form on the right.
+  std::function<int(double* x)> knp_load;          // csol into the solver's order of the unknowns          x = csol
+  std::function<int(const double* x)> knp_store;   // ... and the solution out of it (idempotent)           csol = x
+  // The fused CG's write-back of the potential (idempotent): x minus its mean -- the `np` block sums `part` times inv_n,
+  // which also goes to *mean_out -- into phi, with whatever the owner forms in the same launch.  The owner sets or clears
+  // it before a solve and finds in phi_stored whether that solve has run it.           phi[i * phi_stride] = x[i] - mean
+  std::function<int(const double* x, const double* part, int np, double inv_n, double* mean_out)> phi_store;
+  bool phi_stored = false;
+  uint64_t emi_key = 0, knp_key = 0;   // the part of a fused-graph key that depends on what the hooks launch
+  double* kry = nullptr; size_t kry_n = 0;           // Krylov workspace (kernels_krylov.hip)
+  int kry_ones_masked = 0;                           // the workspace's `ones` vector currently holds the ownership mask
+  void* kry_pinned = nullptr;                        // pinned host buffer the solvers' scalars are read through
+  // state of the fused loops published by the device into mapped host memory (kernels_fused.hip: publish_state)
+  double* pub_host = nullptr; double* pub_host_dev = nullptr; unsigned long long* pub_count = nullptr;
+  unsigned long long pub_expected = 0;
+  KnBlockCols bcols;                 // block structure of a DG problem's systems, else empty
+  int spmv_lpr[2] = {0, 0};          // lanes per row of the Krylov SpMV of the two systems (from the average row length)
+  double* fused_part = nullptr; size_t fused_part_n = 0;   // block partials of the dot products fused into the solver kernels
+  double* guess_old[2] = {nullptr, nullptr};         // previous solutions (EMI, KNP) for knpemi_extrapolate_guess
+  int guess_have[2] = {0, 0};                        // previous solutions stored so far (0, 1, 2)
+  KnAmg amg_emi, amg_knp;
+  // captured iteration bodies of the plain Krylov loops (kernels_krylov.hip: run_chunk); key = configuration they were
+  // captured for.  Both kinds of graph are captured by kn_capture and freed by kn_solver_free.
+  struct KnGraph { hipGraphExec_t exec = nullptr; uint64_t key = 0; };
+  KnGraph graph_emi, graph_knp;
+  // captured chunks of the fused loops (kernels_fused.hip: run_chunk_graph), keyed by everything their kernel arguments hold
+  std::unordered_map<uint64_t, hipGraphExec_t> fused_graphs;
+  // graph replay or direct launches for the chunks of the fused loops, decided per system from timed solves (choose_mode)
+  struct FusedMode { bool decided = false, graph = true; int solves = 0; double t[2] = {0.0, 0.0}; int n[2] = {0, 0}; };
+  FusedMode fused_mode[2];
+  int pc_emi = KNPEMI_PC_AMG, pc_knp = KNPEMI_PC_AMG;
+  int knp_min_it = 0;                  // KNPEMI_OPT_KNP_MIN_IT (ksp_min_it of the concentration solve, pdeSolver.py:101)
+  int emi_norm_pre = 0;                // KNPEMI_OPT_EMI_NORM: 1 = CG tests the preconditioned residual norm (KSPCG's default)
+  int knp_method = 0;                  // KNPEMI_OPT_KNP_METHOD: 0 BiCGStab on the true residual, 1 GMRES(30) as PETSc runs it
+  double* gm_V = nullptr; size_t gm_n = 0;   // Krylov basis of the GMRES solve
+  double* gm_state = nullptr;                // its Hessenberg column, rotations, triangular factor, dot-product partial sums
+  KnDist dist;
+};
+int kn_amg_setup(KnSolver& sv, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
+                 bool singular, const uint8_t* h_owned = nullptr);
+// G.rebuild_wanted: start the rebuild of an aged hierarchy on a host thread from a snapshot of the operator, or swap a
+// finished one in; G stays usable throughout
+int kn_amg_rebuild_step(KnSolver& sv, KnAmg& G, int n, const int* d_rowptr, const int* d_colind, const double* d_vals,
+                        bool singular);
+int kn_amg_apply(KnSolver& sv, KnAmg& G, const double* vals, const double* dinv0, const double* r, double* scratch,
+                 double* out);
+int kn_amg_refresh(KnSolver& sv, KnAmg& G, const double* vals);   // block inverses of the current finest operator
+// fused solver loops (kernels_fused.hip): the iteration of kn_solve_emi / kn_solve_knp in 6 / 13 launches
+struct KnFusedSys {
+  int n; const int* rowptr; const int* colind; const double* vals;   // the system of the current time step
+  double* sc; double* work;   // the solver's device scalars and vector workspace (kernels_krylov.hip layout)
+  size_t N;                   // stride of the workspace vectors
+};
+int kn_fused_subcycle(KnSolver& sv, KnAmg& G, int l0, const double* r0 = nullptr, double* out0 = nullptr);
+// pre / post: what the caller has to run before the first residual / after the last iteration (both become part of the
+// captured graph of a chunk; post must be idempotent, it follows every chunk).  The CG's are single launches of its own
+// file that read KnSolver::phi; its post is KnSolver::phi_store where the owner has set one.
+int kn_fused_cg(KnSolver& sv, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
+                int* iters, double* rr, double* bb);
+int kn_fused_bicgstab(KnSolver& sv, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
+                      int* iters, double* rr, double* bb, const std::function<int()>& pre, const std::function<int()>& post);
+int kn_fused_gmres(KnSolver& sv, KnAmg& G, const KnFusedSys& S, const double* b, double rtol, double atol, int maxit,
+                   int* iters, double* rr, double* bb, const std::function<int()>& pre, const std::function<int()>& post);
+void kn_fused_graphs_free(KnSolver& sv);
+// captures what `enqueue` launches on the owner's stream into *out (nullptr on failure): the one capture path of the Krylov loops
+int kn_capture(KnSolver& sv, const std::function<int()>& enqueue, hipGraphExec_t* out);
+// frees the solver state that is not in the owner's `allocs`: AMG hierarchies (background rebuilds joined), pinned and
+// published host buffers, captured graphs -- knpemi_destroy and knpemi_dg_destroy, before kn_device_close
+void kn_solver_free(KnSolver& sv);
 
 // ghost refresh of a solver vector without Python (comm_rccl.hip)
 struct KnVecPlan {
@@ -512,8 +565,8 @@ inline void kn_free_all(std::vector<void*>& owner) {
   owner.clear();
 }
 // The one teardown order: synchronise, free `allocs`, free the communicator (kn_device_release), then destroy the events and
-// the stream.  What only one kind of handle owns is freed by that handle's destroy before these steps; knpemi_dg, whose
-// solver handle borrows the stream and goes after the communicator, releases first and closes last.
+// the stream.  What only one kind of handle owns is freed by that handle's destroy before these steps, and so is the
+// solver state of either (kn_solver_free), whose graphs and mapped buffers belong to that stream.
 inline void kn_device_release(KnDevice* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   kn_free_all(h->allocs);
@@ -621,35 +674,8 @@ struct knpemi_handle : KnDevice {
   std::vector<int> h_rowptr, h_colind, h_rowptrL, h_colindL;
   int comm_rank = 0;
   KnVecPlan vec_plan[2];                             // [KNPEMI_B_EMI], [KNPEMI_B_KNP]
-  double* kry = nullptr; size_t kry_n = 0;           // Krylov workspace (kernels_krylov.hip)
-  int kry_ones_masked = 0;                           // the workspace's `ones` vector currently holds the ownership mask
-  void* kry_pinned = nullptr;                        // pinned host buffer the solvers' scalars are read through
-  // state of the fused loops published by the device into mapped host memory (kernels_fused.hip: publish_state)
-  double* pub_host = nullptr; double* pub_host_dev = nullptr; unsigned long long* pub_count = nullptr;
-  unsigned long long pub_expected = 0;
-  KnBlockCols bcols;                 // block structure of a DG problem's systems (solver handle of knpemi_dg), else empty
-  int spmv_lpr[2] = {0, 0};          // lanes per row of the Krylov SpMV of the two systems (from the average row length)
-  double* fused_part = nullptr; size_t fused_part_n = 0;   // block partials of the dot products fused into the solver kernels
-  double* guess_old[2] = {nullptr, nullptr};         // previous solutions (EMI, KNP) for knpemi_extrapolate_guess
-  int guess_have[2] = {0, 0};                        // previous solutions stored so far (0, 1, 2)
-  KnAmg amg_emi, amg_knp;
-  // captured iteration bodies of the plain Krylov loops (kernels_krylov.hip: run_chunk); key = configuration they were
-  // captured for.  Both kinds of graph are captured by kn_capture and freed by kn_solver_free.
-  struct KnGraph { hipGraphExec_t exec = nullptr; uint64_t key = 0; };
-  KnGraph graph_emi, graph_knp;
-  // captured chunks of the fused loops (kernels_fused.hip: run_chunk_graph), keyed by everything their kernel arguments hold
-  std::unordered_map<uint64_t, hipGraphExec_t> fused_graphs;
-  // graph replay or direct launches for the chunks of the fused loops, decided per system from timed solves (choose_mode)
-  struct FusedMode { bool decided = false, graph = true; int solves = 0; double t[2] = {0.0, 0.0}; int n[2] = {0, 0}; };
-  FusedMode fused_mode[2];
-  int pc_emi = KNPEMI_PC_AMG, pc_knp = KNPEMI_PC_AMG;
+  KnSolver solver{this};               // the device solves of the two systems (views and hooks: knpemi_api.hip, kn_solver_attach)
   int fuse_update = 0;                 // KNPEMI_OPT_FUSE_UPDATE
-  int knp_min_it = 0;                  // KNPEMI_OPT_KNP_MIN_IT (ksp_min_it of the concentration solve, pdeSolver.py:101)
-  int emi_norm_pre = 0;                // KNPEMI_OPT_EMI_NORM: 1 = CG tests the preconditioned residual norm (KSPCG's default)
-  int knp_method = 0;                  // KNPEMI_OPT_KNP_METHOD: 0 BiCGStab on the true residual, 1 GMRES(30) as PETSc runs it
-  double* gm_V = nullptr; size_t gm_n = 0;   // Krylov basis of the GMRES solve
-  double* gm_state = nullptr;                // its Hessenberg column, rotations, triangular factor, dot-product partial sums
-  bool plain_knp = false;              // the KNP solve's unknown order is dev.csol's own ([K-1][Ntot]; DG variant)
   int fuse_membrane = 0;               // KNPEMI_OPT_FUSE_MEMBRANE
   // Membrane-facet integrals of b_knp formed by the launch that writes the potential back (kn_launch_emi_writeback_membrane),
   // reused by knpemi_assemble_knp while current.  One rule, in host code that graph replay cannot skip: every entry point
@@ -662,7 +688,6 @@ struct knpemi_handle : KnDevice {
   int emi_flags = 0;                   // flags of the last knpemi_assemble_emi (the splitting scheme the step runs with)
   int lds_gam_max = 0;                 // most membrane entries of one row block
   bool blocks_clustered = false;       // row blocks are clusters of row chunks (default), not consecutive rows
-  KnDist dist;
   // The recorders (knpemi_record.hip); each is freed by its knpemi_*_clear, all of them by kn_record_free.
   // A series buffer: the rows a record kernel appends (record_tail.h) until the host reads them.
   struct KnSeries {
@@ -862,13 +887,17 @@ int kn_rtc_launch_monitor(hipStream_t st, hipFunction_t fn, unsigned grid, unsig
                           const KnMonArgs& a);
 int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 // (the membrane ODE sweeps: ode_host.h)
-int kn_solve_emi(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);
-int kn_solve_knp(knpemi_handle* h, double rtol, double atol, int maxit, int* iters, double* relres);
-int kn_extrapolate_guess(knpemi_handle* h, int which);
+int kn_solve_emi(KnSolver& sv, double rtol, double atol, int maxit, int* iters, double* relres);
+int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, double* relres);
+int kn_extrapolate_guess(KnSolver& sv, int which);
+// Distributed solves on or (owned_emi == nullptr) off for either handle: uploads the two ownership masks (the caller's
+// unknown orders), counts the owned unknowns of the potential system over the ranks, keeps the hooks.  `who`: the entry point
+int kn_dist_enable(KnSolver& sv, const uint8_t* owned_emi, std::vector<uint8_t>&& owned_knp, void* reduce_buf_dev,
+                   knpemi_allreduce_fn allreduce, knpemi_halo_fn halo, void* ctx, const char* who);
 int kn_launch_knp_order(knpemi_handle* h, double* x, int to_blocks);
 int kn_launch_knp_writeback_update(knpemi_handle* h, const double* x);
 int kn_launch_halo(knpemi_handle* h, int kind, int pack, const int32_t* idx, int n, double* buf);
-int kn_launch_field_scatter(knpemi_handle* h, const double* src, double* dst, int n, int dst_stride);
-int kn_launch_field_gather(knpemi_handle* h, const double* src, int src_stride, double* dst, int n);
+int kn_launch_field_scatter(hipStream_t st, const double* src, double* dst, int n, int dst_stride);
+int kn_launch_field_gather(hipStream_t st, const double* src, int src_stride, double* dst, int n);
 int kn_launch_trace(knpemi_handle* h, const double* ue, const double* ui, int sub, double* qe, double* qi);
-int kn_launch_vec_index(knpemi_handle* h, double* vec, const int32_t* idx, int n, double* buf, int gather);
+int kn_launch_vec_index(hipStream_t st, double* vec, const int32_t* idx, int n, double* buf, int gather);

@@ -312,10 +312,6 @@ class DGSlab:
             raise RuntimeError("DGSlab.enable_solves: call attach() first")
         dp, tr = self.dp, self.transport
         KS, n = dp.K - 1, dp.n
-        sh = dp.lib.knpemi_dg_solver_handle(dp.h)
-        if not sh:
-            L.check(-1)
-        self._solver_handle = C.c_void_p(sh)
         knp = lambda g: np.concatenate([np.asarray(g, np.int64) + k * n for k in range(KS)])
         mapped = {key: dict(nb=pl["nb"], send=knp(pl["send"]), recv=knp(pl["recv"])) for key, pl in self.plan.items()}
         self._vec = {L.B_EMI: tr.plan(self.plan, 1), L.B_KNP: tr.plan(mapped, 1)}
@@ -325,13 +321,13 @@ class DGSlab:
         def halo(ctx, vec, which):
             d = self._vec[which]
             if d is not None:
-                L.check(dp.lib.knpemi_vec_gather(self._solver_handle, vec, d["send_idx"].data_ptr(), d["send_idx"].numel(),
-                                                 d["send_buf"].data_ptr()))
+                L.check(dp.lib.knpemi_dg_vec_gather(dp.h, vec, d["send_idx"].data_ptr(), d["send_idx"].numel(),
+                                                    d["send_buf"].data_ptr()))
                 # the solver's vectors never go through the library's communicator: where the field halo runs on it
                 # (mode "library RCCL"), they take the host-synchronised torch.distributed path.  Kept as it was.
                 tr.transfer(d, library=False)
-                L.check(dp.lib.knpemi_vec_scatter(self._solver_handle, vec, d["recv_idx"].data_ptr(), d["recv_idx"].numel(),
-                                                  d["recv_buf"].data_ptr()))
+                L.check(dp.lib.knpemi_dg_vec_scatter(dp.h, vec, d["recv_idx"].data_ptr(), d["recv_idx"].numel(),
+                                                     d["recv_buf"].data_ptr()))
         own = np.ascontiguousarray(np.repeat(self.owned_cells.astype(np.uint8), dp.nv))
         self._cb = (L.ALLREDUCE_FN(tr.guarded(lambda ctx, m: tr.allreduce(m, self._red))),     # keep the callbacks alive
                     L.HALO_FN(tr.guarded(halo)))
