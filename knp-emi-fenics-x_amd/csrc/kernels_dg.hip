@@ -713,13 +713,11 @@ struct knpemi_dg : KnDevice {
   double* d_fsrc = nullptr;
   const int* d_colind = nullptr;
   // (prof: brackets of the two assembly kernels, 0 = EMI, 1 = KNP, on the main stream -- knpemi_dg_profile)
-  // membrane ODE sweep
-  int ode_model = -1, ode_ns = 0, ode_np = 0, ode_v = 0, ode_blocks = 0;
-  int ode_ion_param[3 * KN_MAXK] = {0};
-  double* d_states = nullptr;
-  double* d_params = nullptr;
-  unsigned long long* d_stats = nullptr;
-  const void* d_coef = nullptr;
+  // membrane ODE sweep over the membrane nodes: one slot, offset 0 (view: knpemi_dg_create), and what that slot exchanges
+  // with the fields, fixed at knpemi_dg_ode_bind: V's state column and the ions' parameter columns
+  KnSweeps sweeps{this};
+  int sweep_v = 0;
+  int32_t sweep_ion_param[3 * KN_MAXK] = {0};
   // device solves (knpemi_dg_solve_emi / knpemi_dg_solve_knp): the Krylov + AMG code of the CG path on the DG systems
   std::vector<int> aux_of;         // continuous P1 dof (sub-domain, mesh vertex) of every broken dof
   int n_aux = 0;
@@ -772,6 +770,7 @@ extern "C" void knpemi_dg_destroy(knpemi_dg* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   kn_solver_free(h->solver);
+  kn_sweeps_free(h->sweeps);
   kn_device_close(h);
   delete h;
 }
@@ -807,26 +806,12 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
   for (int c = 0; c < nc; ++c)
     if (d->cell_sub[c] < 0 || d->cell_sub[c] >= d->n_sub) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: cell_sub out of range");
   if (hex) {
-    // tensor-product vertex order (bit a of a local vertex = its coordinate along axis a): the trilinear map of a cell
-    // given in another order (e.g. the counter-clockwise order of other formats) folds over, i.e. its Jacobian
-    // determinant changes sign between the corners
+    // tensor-product vertex order (kn_hex_tensor_order)
     for (int c = 0; c < nc; ++c) {
-      int pos = 0, neg = 0;
-      for (int j = 0; j < 8; ++j) {
-        double e[3][3];
-        for (int a = 0; a < 3; ++a) {
-          const int v0 = d->cells[(size_t)c * 8 + j], v1 = d->cells[(size_t)c * 8 + (j ^ (1 << a))];
-          if (v0 < 0 || v0 >= d->n_vertices || v1 < 0 || v1 >= d->n_vertices)
-            return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: vertex id out of range");
-          const double sgn = ((j >> a) & 1) ? -1.0 : 1.0;
-          for (int k = 0; k < 3; ++k) e[a][k] = sgn * (d->x[(size_t)v1 * 3 + k] - d->x[(size_t)v0 * 3 + k]);
-        }
-        const double det = e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0]) +
-                           e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
-        pos += det > 0.0;
-        neg += det < 0.0;
-      }
-      if (pos != 8 && neg != 8)
+      for (int j = 0; j < 8; ++j)
+        if (d->cells[(size_t)c * 8 + j] < 0 || d->cells[(size_t)c * 8 + j] >= d->n_vertices)
+          return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: vertex id out of range");
+      if (!kn_hex_tensor_order(d->x, 3, d->cells + (size_t)c * 8))
         return kn_fail(KNPEMI_EINVAL, "knpemi_dg_create: hexahedron " + std::to_string(c) +
                                           " is degenerate or not in tensor-product vertex order");
     }
@@ -1011,6 +996,13 @@ extern "C" int knpemi_dg_create(const knpemi_dg_desc* d, int device, knpemi_dg**
   if ((rc = kn_zeros(h->allocs, h->stream, (size_t)D.nq, &D.phiM))) return rc;
   if ((rc = kn_zeros(h->allocs, h->stream, (size_t)KN_MAXK * std::max(D.nq, 1), &D.Ich))) return rc;
   D.fsrc = nullptr;
+  {   // what the membrane sweep exchanges with: the dof records, the membrane nodes as one table
+    KnSweeps& sw = h->sweeps;
+    sw.rec = D.rec; sw.q2e = D.q2e; sw.q2i = D.q2i; sw.phiM = D.phiM; sw.Ich = D.Ich;
+    sw.NQtot = D.nq; sw.n_ions = h->K;
+    sw.have_pde = true;
+    sw.ode.resize(1);
+  }
   {
     std::vector<double> qt;
     D.nquad = kn_gamma_quadrature(NF, &qt);
@@ -1281,15 +1273,11 @@ int dg_solver(knpemi_dg* h) {
 // Ghost refresh of a solver vector on a cell partition (knpemi.dg.DGSlab): knpemi_vec_gather / knpemi_vec_scatter on the
 // DG handle's stream
 extern "C" int knpemi_dg_vec_gather(knpemi_dg* h, const void* vec_dev, const int32_t* idx_dev, int n, void* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_vec_gather: bad argument");
-  KN_HIP(hipSetDevice(h->device));
-  return kn_launch_vec_index(h->stream, static_cast<double*>(const_cast<void*>(vec_dev)), idx_dev, n, static_cast<double*>(buf_dev), 1);
+  return kn_vec_index(h, "knpemi_dg_vec_gather", vec_dev, idx_dev, n, buf_dev, 1);
 }
 
 extern "C" int knpemi_dg_vec_scatter(knpemi_dg* h, void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_vec_scatter: bad argument");
-  KN_HIP(hipSetDevice(h->device));
-  return kn_launch_vec_index(h->stream, static_cast<double*>(vec_dev), idx_dev, n, static_cast<double*>(const_cast<void*>(buf_dev)), 0);
+  return kn_vec_index(h, "knpemi_dg_vec_scatter", vec_dev, idx_dev, n, buf_dev, 0);
 }
 
 // Cell partition (knpemi.dg.DGSlab): knpemi_dg_solve_emi / knpemi_dg_solve_knp become solves of the GLOBAL systems, as
@@ -1459,68 +1447,47 @@ extern "C" int knpemi_dg_profile_read(knpemi_dg* h, int which, int64_t* launches
   return kn_prof_read(h->prof, which, launches, total_ms);
 }
 
-// ---- membrane ODE sweep over the membrane nodes ------------------------------------------------------------------
+// ---- membrane ODE sweep over the membrane nodes: slot 0 of h->sweeps ----------------------------------------------------
 extern "C" int knpemi_dg_ode_bind(knpemi_dg* h, int model_id, int n_states, int n_params, const double* states,
                                   const double* params, const int32_t* ion_param, int v_index) {
   if (!h || !states || !params || !ion_param) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: null argument");
-  static const int ns_of[3] = {4, 4, 1}, np_of[3] = {22, 22, 23};
-  if (model_id < 0 || model_id > 2) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: unknown model id");
-  if (n_states != ns_of[model_id] || n_params != np_of[model_id])
-    return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: state/parameter count does not match the model");
-  if (h->ode_model >= 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: model already bound");
+  int rc = kn_ode_check_shipped(h->sweeps, 0, model_id, n_states, n_params, "knpemi_dg_ode_bind");
+  if (rc) return rc;
   if (v_index < 0 || v_index >= n_states) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: bad v_index");
   for (int i = 0; i < 3 * h->K; ++i)
     if (ion_param[i] < 0 || ion_param[i] >= n_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_bind: parameter index out of range");
   KN_HIP(hipSetDevice(h->device));
-  const int nq = h->dev.nq;
-  int rc;
-  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_states * nq, &h->d_states))) return rc;
-  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_params * nq, &h->d_params))) return rc;
-  h->ode_blocks = (int)(((size_t)nq * n_states + 63) / 64) + 1;
-  if ((rc = kn_zeros(h->allocs, h->stream, 3 * (size_t)h->ode_blocks, &h->d_stats))) return rc;
-  if (nq && (rc = kn_table_upload(h->stream, states, h->d_states, nq, n_states))) return rc;
-  if (nq && (rc = kn_table_upload(h->stream, params, h->d_params, nq, n_params))) return rc;
-  if ((rc = kn_lsoda_coef_upload(h->allocs, &h->d_coef))) return rc;
-  for (int i = 0; i < 3 * KN_MAXK; ++i) h->ode_ion_param[i] = i < 3 * h->K ? ion_param[i] : 0;
-  h->ode_model = model_id; h->ode_ns = n_states; h->ode_np = n_params; h->ode_v = v_index;
-  return KNPEMI_OK;
+  if ((rc = kn_ode_alloc_tables(h->sweeps, h->stream, 0, 0, h->dev.nq, model_id, n_states, n_params))) return rc;
+  for (int i = 0; i < 3 * KN_MAXK; ++i) h->sweep_ion_param[i] = i < 3 * h->K ? ion_param[i] : 0;
+  h->sweep_v = v_index;
+  return kn_ode_set_tables(h->sweeps, h->stream, 0, states, params);
 }
 
 extern "C" int knpemi_dg_ode_step(knpemi_dg* h, double t0, double dt, double rtol, double atol, int flags) {
-  if (!h || h->ode_model < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_step: no membrane model bound");
-  if (h->dev.nq == 0) return KNPEMI_OK;
+  if (!h || !h->sweeps.ode[0].bound) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_step: no membrane model bound");
   KN_HIP(hipSetDevice(h->device));
-  const DgDev& D = h->dev;
-  const OdeDev dv{D.rec, D.q2e, D.q2i, D.phiM, D.Ich};
-  // the membrane nodes are one table of their own (offset 0, slot 0) without stimulus or mask; of the caller's flags
-  // only the exchange with the PDE fields reaches the kernel
-  const OdePde pde{flags & (KNPEMI_ODE_SET_V | KNPEMI_ODE_SET_TRACES), h->ode_v, h->K, h->ode_ion_param};
-  const OdeArgs a = kn_ode_args(OdeTables{D.nq, 0, D.nq, 0, h->d_states, h->d_params, nullptr, h->d_stats}, t0, dt, rtol,
-                                atol, &pde);
-  return kn_launch_ode_raw(h->stream, h->ode_model, dv, a, h->d_coef);
+  // no stimulus, no mask; of the caller's flags only the exchange with the PDE fields reaches the kernel.  No profiling
+  // slot: the handle's two are the assembly kernels'
+  const OdePde pde{flags & (KNPEMI_ODE_SET_V | KNPEMI_ODE_SET_TRACES), h->sweep_v, h->K, h->sweep_ion_param};
+  return kn_ode_step(h->sweeps, h->stream, -1, 0, t0, dt, rtol, atol, pde);
 }
 
 extern "C" int knpemi_dg_ode_get_tables(knpemi_dg* h, double* states, double* params) {
-  if (!h || h->ode_model < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_get_tables: no membrane model bound");
+  if (!h || !h->sweeps.ode[0].bound) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_get_tables: no membrane model bound");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
-  const int nq = h->dev.nq;
-  int rc;
-  if (states && nq && (rc = kn_table_download(h->stream, h->d_states, states, nq, h->ode_ns))) return rc;
-  if (params && nq && (rc = kn_table_download(h->stream, h->d_params, params, nq, h->ode_np))) return rc;
-  return KNPEMI_OK;
+  return kn_ode_get_tables(h->sweeps, h->stream, 0, states, params);
 }
 
 extern "C" int knpemi_dg_ode_stats(knpemi_dg* h, int64_t* n_rhs, int64_t* n_steps, int64_t* n_failed) {
-  if (!h || h->ode_model < 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_stats: no membrane model bound");
+  if (!h || !h->sweeps.ode[0].bound) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_ode_stats: no membrane model bound");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
-  unsigned long long st[3];
-  const int rc = kn_ode_read_stats(h->stream, h->d_stats, h->ode_blocks, st);
-  if (rc) return rc;
+  unsigned long long st[3] = {0, 0, 0};
+  const int rc = kn_ode_stats(h->sweeps, h->stream, 0, "at least one membrane node", st);
+  if (rc && rc != KNPEMI_EODE) return rc;
   if (n_rhs) *n_rhs = (int64_t)st[0];
   if (n_steps) *n_steps = (int64_t)st[1];
   if (n_failed) *n_failed = (int64_t)st[2];
-  if (st[2]) return kn_fail(KNPEMI_EODE, kn_ode_failure(true, "at least one membrane node"));
-  return KNPEMI_OK;
+  return rc;
 }

@@ -76,7 +76,7 @@ __global__ __launch_bounds__(MON_THREADS) void monitor_kernel(OdeDev D, KnMonArg
 
 // one launch of `n_blk` workgroups from workgroup a.blk0 of the record on: the library's kernel, or (fn) a plug-in's
 int launch(knpemi_handle* h, const KnMonArgs& a, int n_blk, bool fields, hipFunction_t fn) {
-  const OdeDev dv = kn_ode_dev(h);
+  const OdeDev dv = kn_ode_dev(h->sweeps);
   if (fn) return kn_rtc_launch_monitor(h->stream, fn, (unsigned)n_blk, MON_THREADS, dv, a);
   if (fields) hipLaunchKernelGGL((monitor_kernel<true>), dim3(n_blk), dim3(MON_THREADS), 0, h->stream, dv, a);
   else hipLaunchKernelGGL((monitor_kernel<false>), dim3(n_blk), dim3(MON_THREADS), 0, h->stream, dv, a);

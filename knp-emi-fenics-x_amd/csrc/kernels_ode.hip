@@ -17,16 +17,12 @@
 //
 // Host side (ode_host.h): this file builds the arguments of every sweep (kn_ode_args) and decides every launch
 // (launch_sweep: plug-in or shipped model, LSODA here or a fixed-step kernel of kernels_ode_fixed.hip); kn_ode_step and
-// kn_ode_advance are the two entries, one per kernel shape.
+// kn_ode_advance are the two entries, one per kernel shape.  All of it works on a KnSweeps, whichever handle embeds it;
+// only the step that shares its launch with the potential system's rows (kn_ode_step_emi) needs the CG handle's rows.
 #include <algorithm>
 #include <cstdlib>
 
 #include "ode_host.h"
-
-OdeDev kn_ode_dev(const knpemi_handle* h) {
-  const KnDev& D = h->dev;
-  return OdeDev{D.VR, D.q2e, D.q2i, D.phiM, D.Ich};
-}
 
 OdeArgs kn_ode_args(const OdeTables& T, double t0, double dt, double rtol, double atol, const OdePde* pde) {
   OdeArgs a{};   // what no branch below sets stays zero: no stimulus, full waves (dpw), no stamps
@@ -59,12 +55,12 @@ int dofs_per_wave(const KnOdeModel& m) {
   return forced < full && (m.nq + forced - 1) / forced <= m.n_stat_blocks - 1 ? forced : 0;
 }
 
-// the arguments of a sweep over the tables of model `slot` of the handle
-OdeArgs model_args(const knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde* pde) {
-  const KnOdeModel& m = h->ode[slot];
+// the arguments of a sweep over the tables of `slot`
+OdeArgs model_args(const KnSweeps& sw, int slot, double t0, double dt, double rtol, double atol, const OdePde* pde) {
+  const KnOdeModel& m = sw.ode[slot];
   const bool lsoda = m.method == KNPEMI_ODE_LSODA;
   // a fixed-step method has no tolerances, and its kernels run one thread per dof whatever dpw says
-  OdeArgs a = kn_ode_args(OdeTables{m.nq, h->qoff[m.sub], h->dev.NQtot, slot, m.d_states, m.d_params, m.d_mask, m.d_stats},
+  OdeArgs a = kn_ode_args(OdeTables{m.nq, m.q0, sw.NQtot, slot, m.d_states, m.d_params, m.d_mask, m.d_stats},
                           t0, dt, lsoda ? rtol : 0.0, lsoda ? atol : 0.0, pde);
   a.n_stim = m.n_stim;
   for (int i = 0; i < 8; ++i) { a.stim_idx[i] = m.stim_idx[i]; a.stim_val[i] = m.stim_val[i]; }
@@ -104,61 +100,60 @@ int launch_lsoda_advance(hipStream_t st, int model_id, const OdeArgs& a, const O
   return kn_launch_check("ode_advance_kernel");
 }
 
-// The launch decision of every sweep of a handle: model source, integrator, kernel shape (v NULL: one step, which
-// exchanges with the PDE fields; else the n steps v describes).  On h->cur.
-int launch_sweep(knpemi_handle* h, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs* v, const LsodaCoef* cf) {
+// The launch decision of every sweep of either handle: model source, integrator, kernel shape (v NULL: one step, which
+// exchanges with the PDE fields; else the n steps v describes).  On `st`.
+int launch_sweep(const KnSweeps& sw, hipStream_t st, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs* v,
+                 const LsodaCoef* cf) {
   const bool lsoda = m.method == KNPEMI_ODE_LSODA;
-  const OdeDev dv = kn_ode_dev(h);
+  const OdeDev dv = kn_ode_dev(sw);
   if (m.rtc_module) {   // plug-in compiled at bind time (kernels_rtc.hip)
     const hipFunction_t fn = m.rtc_kernel[m.method][v != nullptr];
     if (!fn) { kn_set_error("a model bound from source runs lsoda, euler or rk4"); return KNPEMI_EINVAL; }
     // LSODA: rtc_lanes lanes per dof in full waves; fixed-step: one thread per dof
     const unsigned grid = (unsigned)(((size_t)a.nq * (lsoda ? m.rtc_lanes : 1) + ODE_BLOCK - 1) / ODE_BLOCK);
-    if (lsoda) return v ? kn_rtc_launch(h->cur, fn, grid, a, *v, cf) : kn_rtc_launch(h->cur, fn, grid, dv, a, cf);
-    return v ? kn_rtc_launch(h->cur, fn, grid, a, *v, m.n_substeps) : kn_rtc_launch(h->cur, fn, grid, dv, a, m.n_substeps);
+    if (lsoda) return v ? kn_rtc_launch(st, fn, grid, a, *v, cf) : kn_rtc_launch(st, fn, grid, dv, a, cf);
+    return v ? kn_rtc_launch(st, fn, grid, a, *v, m.n_substeps) : kn_rtc_launch(st, fn, grid, dv, a, m.n_substeps);
   }
-  if (!lsoda) return v ? kn_launch_ode_fixed_advance(h->cur, m, a, *v) : kn_launch_ode_fixed_step(h->cur, m, dv, a);
-  if (v) return launch_lsoda_advance(h->cur, m.model_id, a, *v, cf);
+  if (!lsoda) return v ? kn_launch_ode_fixed_advance(st, m, a, *v) : kn_launch_ode_fixed_step(st, m, dv, a);
+  if (v) return launch_lsoda_advance(st, m.model_id, a, *v, cf);
   // KNPEMI_ODE_WAVES applies to the single-step launch only
   static const int force_waves = [] { const char* e = getenv("KNPEMI_ODE_WAVES"); return e ? atoi(e) : 0; }();
-  return launch_lsoda_step(h->cur, m.model_id, dv, a, cf, force_waves);
+  return launch_lsoda_step(st, m.model_id, dv, a, cf, force_waves);
 }
 
-// the handle's copy of the LSODA coefficient tables, uploaded on first use
-int lsoda_coef(knpemi_handle* h, const LsodaCoef** out) {
-  if (!h->d_lsoda_coef)
-    if (int rc = kn_lsoda_coef_upload(h->allocs, &h->d_lsoda_coef)) return rc;
-  *out = static_cast<const LsodaCoef*>(h->d_lsoda_coef);
+// the owner's copy of the LSODA coefficient tables, uploaded on first use
+int lsoda_coef(KnSweeps& sw, const LsodaCoef** out) {
+  if (!sw.d_lsoda_coef) {
+    LsodaCoef c;
+    lsoda_fill_coef(&c);
+    if (int rc = kn_upload(sw.own->allocs, &c, 1, &sw.d_lsoda_coef)) return rc;
+  }
+  *out = static_cast<const LsodaCoef*>(sw.d_lsoda_coef);
   return KNPEMI_OK;
 }
 
 }  // namespace
 
-int kn_lsoda_coef_upload(std::vector<void*>& owner, const void** out) {
-  LsodaCoef c;
-  lsoda_fill_coef(&c);
-  return kn_upload(owner, &c, 1, out);
-}
-
-// ---- one PDE step per launch (knpemi_ode_step) -------------------------------------------------------------------
-int kn_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde& pde) {
-  KnOdeModel& m = h->ode[slot];
+// ---- one PDE step per launch (knpemi_ode_step, knpemi_dg_ode_step) -------------------------------------------------
+int kn_ode_step(KnSweeps& sw, hipStream_t st, int prof_slot, int slot, double t0, double dt, double rtol, double atol,
+                const OdePde& pde) {
+  KnOdeModel& m = sw.ode[slot];
   if (m.nq == 0) return KNPEMI_OK;
   const LsodaCoef* cf = nullptr;
   int rc;
-  if (m.method == KNPEMI_ODE_LSODA && (rc = lsoda_coef(h, &cf))) return rc;
-  OdeArgs a = model_args(h, slot, t0, dt, rtol, atol, &pde);
+  if (m.method == KNPEMI_ODE_LSODA && (rc = lsoda_coef(sw, &cf))) return rc;
+  OdeArgs a = model_args(sw, slot, t0, dt, rtol, atol, &pde);
   // KNPEMI_ODE_STAMPS=1: diagnostic build of the sweep with s_memtime stamps between the phases (tools/ode_stamps.py);
   // only the LSODA kernels of the shipped models have one
   static const bool want_stamps = getenv("KNPEMI_ODE_STAMPS") != nullptr;
   if (want_stamps && m.method == KNPEMI_ODE_LSODA && !m.rtc_module) {
-    if (!m.d_stamps && (rc = kn_alloc(h->allocs, 24 * (size_t)m.n_stat_blocks, &m.d_stamps))) return rc;
+    if (!m.d_stamps && (rc = kn_alloc(sw.own->allocs, 24 * (size_t)m.n_stat_blocks, &m.d_stamps))) return rc;
     a.stamps = m.d_stamps;
   }
-  // counters accumulate over launches; knpemi_ode_stats() reads and resets them.  One profiling slot whatever the
+  // counters accumulate over launches; kn_ode_stats() reads and resets them.  One profiling slot whatever the
   // integrator: it is "the ODE kernel" of the step for DeviceStepper's stream choice
-  KnProfScope prof(h->prof, KNPEMI_K_ODE, h->cur);
-  return launch_sweep(h, m, a, nullptr, cf);
+  KnProfScope prof(sw.own->prof, prof_slot, st);
+  return launch_sweep(sw, st, m, a, nullptr, cf);
 }
 
 // ---- one PDE step and the potential system's matrix per launch (knpemi_ode_step_emi) ------------------------------
@@ -180,9 +175,9 @@ bool sweep_emi_eligible(knpemi_handle* h, const KnOdeModel& m, int n_sweep) {
   const char* want = getenv("KNPEMI_FUSED_SWEEP");
   if (want ? atoi(want) == 0 : !SWEEP_EMI_DEFAULT) return false;
   if (m.rtc_module || m.method != KNPEMI_ODE_LSODA || getenv("KNPEMI_ODE_STAMPS") || getenv("KNPEMI_ODE_WAVES")) return false;
-  if (h->ode_only || h->solver.dist.on || !kn_sweep_emi_rows_ok(h)) return false;
+  if (!h->sweeps.have_pde || h->solver.dist.on || !kn_sweep_emi_rows_ok(h)) return false;
   int bound = 0;
-  for (const KnOdeModel& o : h->ode) bound += o.bound;
+  for (const KnOdeModel& o : h->sweeps.ode) bound += o.bound;
   if (bound != 1) return false;
   if (h->n_cus == 0 && hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) {
     (void)hipGetLastError();
@@ -198,20 +193,21 @@ bool sweep_emi_eligible(knpemi_handle* h, const KnOdeModel& m, int n_sweep) {
 int kn_ode_step_emi(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde& pde,
                     int emi_flags, int* fused) {
   *fused = 0;
-  KnOdeModel& m = h->ode[slot];
+  KnSweeps& sw = h->sweeps;
+  KnOdeModel& m = sw.ode[slot];
   if (m.nq > 0 && m.method == KNPEMI_ODE_LSODA && !m.rtc_module) {
-    OdeArgs a = model_args(h, slot, t0, dt, rtol, atol, &pde);
+    OdeArgs a = model_args(sw, slot, t0, dt, rtol, atol, &pde);
     int lanes = 1;
     with_model(m.model_id, [&](auto tag) { lanes = tag.LANES; });
     const int n_sweep = (int)lsoda_grid(a, lanes).x;
     if (sweep_emi_eligible(h, m, n_sweep)) {
       const LsodaCoef* cf = nullptr;
-      if (int rc = lsoda_coef(h, &cf)) return rc;
-      if (int rc = kn_launch_sweep_emi(h, m.model_id, kn_ode_dev(h), a, cf, n_sweep, emi_flags, fused)) return rc;
+      if (int rc = lsoda_coef(sw, &cf)) return rc;
+      if (int rc = kn_launch_sweep_emi(h, m.model_id, kn_ode_dev(sw), a, cf, n_sweep, emi_flags, fused)) return rc;
       if (*fused) return KNPEMI_OK;
     }
   }
-  if (int rc = kn_ode_step(h, slot, t0, dt, rtol, atol, pde)) return rc;
+  if (int rc = kn_ode_step(sw, h->cur, KNPEMI_K_ODE, slot, t0, dt, rtol, atol, pde)) return rc;
   return kn_launch_emi_rows(h, emi_flags | KNPEMI_SKIP_MEMBRANE_RHS);
 }
 
@@ -230,19 +226,19 @@ struct DevBuf {   // a temporary device allocation
 
 }  // namespace
 
-int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
+int kn_ode_advance(KnSweeps& sw, hipStream_t st, int slot, double t0, double dt, int n_steps, double rtol, double atol,
                    const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
                    int32_t* steps_taken, int32_t* failed_step) {
-  KnOdeModel& m = h->ode[slot];
+  KnOdeModel& m = sw.ode[slot];
   m.adv_chunk = 0;
   if (m.nq == 0 || n_steps == 0) return KNPEMI_OK;
   const bool lsoda = m.method == KNPEMI_ODE_LSODA;
   const LsodaCoef* cf = nullptr;
   int rc = KNPEMI_OK;
-  if (lsoda && (rc = lsoda_coef(h, &cf))) return rc;
+  if (lsoda && (rc = lsoda_coef(sw, &cf))) return rc;
   const size_t nq = (size_t)m.nq;
-  if (!m.d_adv && (rc = kn_alloc(h->allocs, 3 * nq, &m.d_adv))) return rc;   // still-step counters, steps_taken, failed_step
-  OdeArgs a = model_args(h, slot, t0, dt, rtol, atol, nullptr);
+  if (!m.d_adv && (rc = kn_alloc(sw.own->allocs, 3 * nq, &m.d_adv))) return rc;   // still-step counters, steps_taken, failed_step
+  OdeArgs a = model_args(sw, slot, t0, dt, rtol, atol, nullptr);
   OdeAdvArgs v{};
   v.n_rec = history ? n_rec : 0;
   v.every = every;
@@ -251,8 +247,8 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   v.ss_rtol = ss ? ss->ss_rtol : 0.0;
   v.ss_atol = ss ? ss->ss_atol : 0.0;
   v.still = m.d_adv; v.steps_taken = m.d_adv + nq; v.failed_step = m.d_adv + 2 * nq;
-  KN_HIP(hipMemsetAsync(v.still, 0, nq * sizeof(int), h->cur));
-  KN_HIP(hipMemsetAsync(v.steps_taken, 0xFF, 2 * nq * sizeof(int), h->cur));   // -1
+  KN_HIP(hipMemsetAsync(v.still, 0, nq * sizeof(int), st));
+  KN_HIP(hipMemsetAsync(v.steps_taken, 0xFF, 2 * nq * sizeof(int), st));   // -1
   const size_t n_hist = v.n_rec > 0 ? (size_t)(n_steps / every) * v.n_rec * nq : 0;
   DevBuf hist;
   if (n_hist) {
@@ -270,11 +266,11 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
     const int c = std::min(chunk, n_steps - s);
     v.s0 = s; v.n_steps = c; a.t0 = t;
     const bool probe = s == 0 && forced <= 0;
-    if (probe && hipEventRecord(e0, h->cur) != hipSuccess) rc = KNPEMI_EHIP;
-    if (rc == KNPEMI_OK) rc = launch_sweep(h, m, a, &v, cf);
+    if (probe && hipEventRecord(e0, st) != hipSuccess) rc = KNPEMI_EHIP;
+    if (rc == KNPEMI_OK) rc = launch_sweep(sw, st, m, a, &v, cf);
     if (rc == KNPEMI_OK && probe) {
       float ms = 0.0f;
-      if (hipEventRecord(e1, h->cur) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+      if (hipEventRecord(e1, st) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
           hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
         kn_set_error("knpemi_ode_advance: timing the first launch failed");
         rc = KNPEMI_EHIP;
@@ -290,9 +286,9 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   (void)hipEventDestroy(e1);
   if (rc) return rc;
   m.adv_chunk = chunk;
-  if (n_hist) KN_HIP(hipMemcpyAsync(history, hist.p, n_hist * sizeof(double), hipMemcpyDeviceToHost, h->cur));
+  if (n_hist) KN_HIP(hipMemcpyAsync(history, hist.p, n_hist * sizeof(double), hipMemcpyDeviceToHost, st));
   std::vector<int32_t> flags(2 * nq);
-  if ((rc = kn_to_host(h->cur, flags.data(), v.steps_taken, 2 * nq))) return rc;
+  if ((rc = kn_to_host(st, flags.data(), v.steps_taken, 2 * nq))) return rc;
   if (steps_taken) std::copy(flags.begin(), flags.begin() + nq, steps_taken);
   if (failed_step) std::copy(flags.begin() + nq, flags.end(), failed_step);
   size_t n_failed = 0;
@@ -304,18 +300,65 @@ int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps
   return KNPEMI_OK;
 }
 
-// The same LSODA sweep over a caller-described table (the DG variant, kernels_dg.hip: membrane nodes of the broken space).
-int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef) {
-  return launch_lsoda_step(st, model_id, dv, a, static_cast<const LsodaCoef*>(coef), 0);
+// ---- upkeep of a slot: one body under the entry points of both handles (ode_host.h) ---------------------------------
+int kn_ode_check_shipped(const KnSweeps& sw, int slot, int model_id, int n_states, int n_params, const std::string& who) {
+  if (model_id < 0 || model_id > 2) return kn_fail(KNPEMI_EINVAL, who + ": unknown model id");
+  int ns = 0, np = 0;
+  with_model(model_id, [&](auto tag) { ns = decltype(tag)::Model::NS; np = decltype(tag)::Model::NP; });
+  if (n_states != ns || n_params != np) return kn_fail(KNPEMI_EINVAL, who + ": state/parameter count does not match the model");
+  if (sw.ode[slot].bound) return kn_fail(KNPEMI_EINVAL, who + ": model already bound");
+  return KNPEMI_OK;
 }
 
-int kn_ode_read_stats(hipStream_t st, unsigned long long* d_stats, int n_blocks, unsigned long long out[3]) {
-  std::vector<unsigned long long> part(3 * (size_t)n_blocks);
-  KN_HIP(hipMemcpyAsync(part.data(), d_stats, part.size() * sizeof(part[0]), hipMemcpyDeviceToHost, st));
-  KN_HIP(hipMemsetAsync(d_stats, 0, part.size() * sizeof(part[0]), st));
+int kn_ode_check_exchange(const KnSweeps& sw, int slot, const int32_t* ion_param, int v_index, const std::string& who) {
+  const KnOdeModel& m = sw.ode[slot];
+  for (int i = 0; i < 3 * sw.n_ions; ++i)
+    if (ion_param[i] < 0 || ion_param[i] >= m.n_params) return kn_fail(KNPEMI_EINVAL, who + ": parameter index out of range");
+  if (v_index < 0 || v_index >= m.n_states) return kn_fail(KNPEMI_EINVAL, who + ": bad V index");
+  return KNPEMI_OK;
+}
+
+int kn_ode_alloc_tables(KnSweeps& sw, hipStream_t st, int slot, int q0, int nq, int model_id, int n_states, int n_params) {
+  KnOdeModel& m = sw.ode[slot];
+  std::vector<void*>& owner = sw.own->allocs;
+  m.q0 = q0; m.nq = nq; m.model_id = model_id; m.n_states = n_states; m.n_params = n_params;
+  int rc;
+  if ((rc = kn_zeros(owner, st, (size_t)n_states * nq, &m.d_states))) return rc;
+  if ((rc = kn_zeros(owner, st, (size_t)n_params * nq, &m.d_params))) return rc;
+  // one slot per workgroup of the sweep (a forced KNPEMI_ODE_DPW runs fewer dofs per wave, up to one wave per SIMD)
+  m.n_stat_blocks = std::max((int)(((size_t)nq * n_states + 63) / 64), std::min(nq, 1024)) + 1;
+  if ((rc = kn_zeros(owner, st, 3 * (size_t)m.n_stat_blocks, &m.d_stats))) return rc;
+  m.bound = 1;
+  return KNPEMI_OK;
+}
+
+int kn_ode_set_tables(KnSweeps& sw, hipStream_t st, int slot, const double* states, const double* params) {
+  const KnOdeModel& m = sw.ode[slot];
+  if (m.nq == 0) return KNPEMI_OK;
+  int rc;
+  if (states && (rc = kn_table_upload(st, states, m.d_states, m.nq, m.n_states))) return rc;
+  if (params && (rc = kn_table_upload(st, params, m.d_params, m.nq, m.n_params))) return rc;
+  return KNPEMI_OK;
+}
+
+int kn_ode_get_tables(KnSweeps& sw, hipStream_t st, int slot, double* states, double* params) {
+  const KnOdeModel& m = sw.ode[slot];
+  if (m.nq == 0) return KNPEMI_OK;
+  int rc;
+  if (states && (rc = kn_table_download(st, m.d_states, states, m.nq, m.n_states))) return rc;
+  if (params && (rc = kn_table_download(st, m.d_params, params, m.nq, m.n_params))) return rc;
+  return KNPEMI_OK;
+}
+
+int kn_ode_stats(KnSweeps& sw, hipStream_t st, int slot, const std::string& where, unsigned long long out[3]) {
+  const KnOdeModel& m = sw.ode[slot];
+  std::vector<unsigned long long> part(3 * (size_t)m.n_stat_blocks);
+  KN_HIP(hipMemcpyAsync(part.data(), m.d_stats, part.size() * sizeof(part[0]), hipMemcpyDeviceToHost, st));
+  KN_HIP(hipMemsetAsync(m.d_stats, 0, part.size() * sizeof(part[0]), st));
   KN_HIP(hipStreamSynchronize(st));
   out[0] = out[1] = out[2] = 0;
   for (size_t i = 0; i < part.size(); ++i) out[i % 3] += part[i];
+  if (out[2]) return kn_fail(KNPEMI_EODE, kn_ode_failure(m.method == KNPEMI_ODE_LSODA, where));
   return KNPEMI_OK;
 }
 

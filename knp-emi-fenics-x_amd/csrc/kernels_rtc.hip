@@ -156,7 +156,7 @@ extern "C" int knpemi_ode_compile_source(int n_states, int n_params, const char*
   return KNPEMI_OK;
 }
 
-int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source) {
+int kn_rtc_bind(KnSweeps& sw, KnOdeModel& m, int n_states, int n_params, const char* rhs_source) {
   const std::string key = std::to_string(n_states) + "/" + std::to_string(n_params) + "/" + rhs_source;
   std::vector<char> code;
   {
@@ -189,7 +189,7 @@ int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, con
     }
   m.rtc_module = mod;
   m.rtc_lanes = lanes_for(n_states);
-  h->rtc_modules.push_back(mod);
+  sw.rtc_modules.push_back(mod);
   return KNPEMI_OK;
 }
 
@@ -287,7 +287,7 @@ extern "C" int knpemi_monitor_compile_source(int n_states, int n_params, int n_m
   return KNPEMI_OK;
 }
 
-int kn_rtc_monitor_bind(knpemi_handle* h, KnOdeModel& m, int n_monitored, const char* monitor_source) {
+int kn_rtc_monitor_bind(KnSweeps& sw, KnOdeModel& m, int n_monitored, const char* monitor_source) {
   if (!monitor_sizes_ok(m.n_states, m.n_params, n_monitored))
     return kn_fail(KNPEMI_EINVAL, "knpemi_monitor_bind_source: 1..KNPEMI_MON_MAX monitored quantities");
   const std::string key = monitor_key(m.n_states, m.n_params, n_monitored, monitor_source);
@@ -315,7 +315,7 @@ int kn_rtc_monitor_bind(knpemi_handle* h, KnOdeModel& m, int n_monitored, const 
     }
   m.mon_kernel[0] = fn[0]; m.mon_kernel[1] = fn[1];
   m.n_monitored = n_monitored;
-  h->rtc_modules.push_back(mod);
+  sw.rtc_modules.push_back(mod);
   return KNPEMI_OK;
 }
 

@@ -99,6 +99,16 @@ static void kn_solver_attach(knpemi_handle* h) {
   }
 }
 
+// The view of the handle's fields its membrane sweeps exchange with (KnSweeps); a handle of knpemi_ode_create has phi_M and
+// I_ch only.
+static void kn_sweeps_attach(knpemi_handle* h) {
+  const KnDev& D = h->dev;
+  KnSweeps& sw = h->sweeps;
+  sw.rec = D.VR; sw.q2e = D.q2e; sw.q2i = D.q2i; sw.phiM = D.phiM; sw.Ich = D.Ich;
+  sw.NQtot = D.NQtot; sw.n_ions = h->K;
+  sw.have_pde = !h->ode_only;
+}
+
 extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_handle** out) {
   if (!d || !out) return kn_fail(KNPEMI_EINVAL, "knpemi_create: null argument");
   *out = nullptr;
@@ -143,7 +153,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   h->voff = prefix(h->n_vert); h->coff = prefix(h->n_cell); h->qoff = prefix(h->n_q);
   h->foff = prefix(h->n_facet); h->moff = prefix(h->n_models);
   const int Ntot = h->voff[S], nctot = h->coff[S], NQtot = h->qoff[S], nftot = h->foff[S];
-  h->ode.resize(h->moff[S]);
+  h->sweeps.ode.resize(h->moff[S]);
 
   // ---- global cells, vertex records -----------------------------------------------------------
   std::vector<int> cells((size_t)nctot * NV);
@@ -162,28 +172,13 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   // ---- hexahedra: tensor-product vertex order (bit a of a local vertex = its coordinate along axis a) --------------
   // Any of the 48 such orders of a cell is taken, left-handed ones included; the trilinear map of a cell given in another
   // order (e.g. the counter-clockwise order of other formats) folds over, i.e. its Jacobian determinant changes sign
-  // between the corners (the test of knpemi_dg_create)
+  // between the corners (kn_hex_tensor_order, the test of knpemi_dg_create too)
   if (NV == 8)
     for (int s = 0; s < S; ++s)
-      for (int c = h->coff[s]; c < h->coff[s + 1]; ++c) {
-        int pos = 0, neg = 0;
-        for (int j = 0; j < 8; ++j) {
-          double e[3][3];
-          for (int a = 0; a < 3; ++a) {
-            const double* x0 = &VR[(size_t)cells[(size_t)c * 8 + j] * KN_REC];
-            const double* x1 = &VR[(size_t)cells[(size_t)c * 8 + (j ^ (1 << a))] * KN_REC];
-            const double sgn = ((j >> a) & 1) ? -1.0 : 1.0;
-            for (int k = 0; k < 3; ++k) e[a][k] = sgn * (x1[k] - x0[k]);
-          }
-          const double det = e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0]) +
-                             e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
-          pos += det > 0.0;
-          neg += det < 0.0;
-        }
-        if (pos != 8 && neg != 8)
+      for (int c = h->coff[s]; c < h->coff[s + 1]; ++c)
+        if (!kn_hex_tensor_order(VR.data(), KN_REC, &cells[(size_t)c * 8]))
           return kn_fail(KNPEMI_EINVAL, "knpemi_create: hexahedron " + std::to_string(c - h->coff[s]) + " of sub-domain " +
                                             std::to_string(s) + " is degenerate or not in tensor-product vertex order");
-      }
 
   // ---- vertex -> cell adjacency (counting sort) ---------------------------------------------------
   std::vector<int64_t> v2c_ptr(Ntot + 1, 0);
@@ -968,6 +963,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   C.splitting = 1;
 
   kn_solver_attach(h);
+  kn_sweeps_attach(h);
   *out = guard.release();
   return KNPEMI_OK;
 }
@@ -1002,12 +998,13 @@ extern "C" int knpemi_ode_create(int device, int n_models, const int32_t* nq, kn
   };
   h->voff = prefix(h->n_vert); h->coff = prefix(h->n_cell); h->qoff = prefix(h->n_q);
   h->foff = prefix(h->n_facet); h->moff = prefix(h->n_models);
-  h->ode.resize(h->moff[S]);
+  h->sweeps.ode.resize(h->moff[S]);
   KnDev& D = h->dev;
   D.NQtot = h->qoff[S];
   int rc;
   if ((rc = kn_zeros(h->allocs, h->stream, (size_t)std::max(1, D.NQtot), &D.phiM))) return rc;                          // phi_M write-back
   if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_models * KN_MAXK * std::max(1, D.NQtot), &D.Ich))) return rc;      // (no ions: unused)
+  kn_sweeps_attach(h);
   *out = guard.release();
   return KNPEMI_OK;
 }
@@ -1028,7 +1025,7 @@ extern "C" void knpemi_destroy(knpemi_handle* h) {
   kn_comm_destroy(h);
   kn_solver_free(h->solver);
   kn_record_free(h);
-  for (void* m : h->rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
+  kn_sweeps_free(h->sweeps);
   kn_device_close(h);
   delete h;
 }
@@ -1501,39 +1498,20 @@ int ode_slot(knpemi_handle* h, int sub, int model, int need_bound) {
     return -1;
   }
   int slot = h->moff[sub] + model;
-  if (need_bound && !h->ode[slot].bound) {
+  if (need_bound && !h->sweeps.ode[slot].bound) {
     kn_set_error("membrane model not bound (knpemi_ode_bind)");
     return -1;
   }
   return slot;
-}
-
-// the tables of a newly bound model: states, parameters, statistics partials
-int ode_alloc_tables(knpemi_handle* h, KnOdeModel& m, int sub, int model_id, int n_states, int n_params) {
-  m.sub = sub; m.model_id = model_id; m.n_states = n_states; m.n_params = n_params;
-  m.nq = h->n_q[sub];
-  int rc;
-  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_states * m.nq, &m.d_states))) return rc;
-  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)n_params * m.nq, &m.d_params))) return rc;
-  // one slot per workgroup of the sweep (small sweeps run with fewer dofs per wave, up to one wave per SIMD: kernels_ode.hip)
-  m.n_stat_blocks = std::max((int)(((size_t)m.nq * n_states + 63) / 64), std::min(m.nq, 1024)) + 1;
-  if ((rc = kn_zeros(h->allocs, h->stream, 3 * (size_t)m.n_stat_blocks, &m.d_stats))) return rc;
-  m.bound = 1;
-  return KNPEMI_OK;
 }
 }  // namespace
 
 extern "C" int knpemi_ode_bind(knpemi_handle* h, int sub, int model, int model_id, int n_states, int n_params) {
   int slot = ode_slot(h, sub, model, 0);
   if (slot < 0) return KNPEMI_EINVAL;
-  static const int ns_of[3] = {4, 4, 1}, np_of[3] = {22, 22, 23};
-  if (model_id < 0 || model_id > 2) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind: unknown model id");
-  if (n_states != ns_of[model_id] || n_params != np_of[model_id])
-    return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind: state/parameter count does not match the model");
+  if (int rc = kn_ode_check_shipped(h->sweeps, slot, model_id, n_states, n_params, "knpemi_ode_bind")) return rc;
   KN_HIP(hipSetDevice(h->device));
-  KnOdeModel& m = h->ode[slot];
-  if (m.bound) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind: model already bound");
-  return ode_alloc_tables(h, m, sub, model_id, n_states, n_params);
+  return kn_ode_alloc_tables(h->sweeps, h->stream, slot, h->qoff[sub], h->n_q[sub], model_id, n_states, n_params);
 }
 
 extern "C" int knpemi_ode_bind_source(knpemi_handle* h, int sub, int model, int n_states, int n_params,
@@ -1543,42 +1521,32 @@ extern "C" int knpemi_ode_bind_source(knpemi_handle* h, int sub, int model, int 
   if (!rhs_source || n_states < 1 || n_states > 16 || n_params < 1 || n_params > 128)
     return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind_source: bad argument (1..16 states, 1..128 parameters)");
   KN_HIP(hipSetDevice(h->device));
-  KnOdeModel& m = h->ode[slot];
+  KnOdeModel& m = h->sweeps.ode[slot];
   if (m.bound) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_bind_source: model already bound");
-  int rc = kn_rtc_bind(h, m, n_states, n_params, rhs_source);
+  int rc = kn_rtc_bind(h->sweeps, m, n_states, n_params, rhs_source);
   if (rc) return rc;
-  return ode_alloc_tables(h, m, sub, -1, n_states, n_params);
+  return kn_ode_alloc_tables(h->sweeps, h->stream, slot, h->qoff[sub], h->n_q[sub], -1, n_states, n_params);
 }
 
 extern "C" int knpemi_ode_set_tables(knpemi_handle* h, int sub, int model, const double* states, const double* params) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  KnOdeModel& m = h->ode[slot];
-  if (m.nq == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
-  int rc;
-  if (states && (rc = kn_table_upload(h->stream, states, m.d_states, m.nq, m.n_states))) return rc;
-  if (params && (rc = kn_table_upload(h->stream, params, m.d_params, m.nq, m.n_params))) return rc;
-  return KNPEMI_OK;
+  return kn_ode_set_tables(h->sweeps, h->stream, slot, states, params);
 }
 
 extern "C" int knpemi_ode_get_tables(knpemi_handle* h, int sub, int model, double* states, double* params) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  KnOdeModel& m = h->ode[slot];
-  if (m.nq == 0) return KNPEMI_OK;
   KN_HIP(hipSetDevice(h->device));
-  int rc;
-  if (states && (rc = kn_table_download(h->stream, m.d_states, states, m.nq, m.n_states))) return rc;
-  if (params && (rc = kn_table_download(h->stream, m.d_params, params, m.nq, m.n_params))) return rc;
-  return KNPEMI_OK;
+  return kn_ode_get_tables(h->sweeps, h->stream, slot, states, params);
 }
 
 extern "C" int knpemi_ode_set_stimulus(knpemi_handle* h, int sub, int model, const uint8_t* mask,
                                        int n_pairs, const int32_t* param_idx, const double* values) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  KnOdeModel& m = h->ode[slot];
+  KnOdeModel& m = h->sweeps.ode[slot];
   if (n_pairs < 0 || n_pairs > 8) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_set_stimulus: at most 8 stimulus entries");
   KN_HIP(hipSetDevice(h->device));
   for (int i = 0; i < n_pairs; ++i) {
@@ -1606,15 +1574,11 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
   if (!ion_param) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: ion_param is required");
-  KnOdeModel& m = h->ode[slot];
-  for (int i = 0; i < 3 * h->K; ++i)
-    if (ion_param[i] < 0 || ion_param[i] >= m.n_params)
-      return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: parameter index out of range");
-  if (v_index < 0 || v_index >= m.n_states) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: bad V index");
-  const bool fixed = m.method != KNPEMI_ODE_LSODA;   // (a fixed-step method has no tolerances)
+  if (int rc = kn_ode_check_exchange(h->sweeps, slot, ion_param, v_index, "knpemi_ode_step")) return rc;
+  const bool fixed = h->sweeps.ode[slot].method != KNPEMI_ODE_LSODA;   // (a fixed-step method has no tolerances)
   if (!(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
     return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: bad dt / tolerances");
-  if (h->ode_only && (flags & (KNPEMI_ODE_SET_TRACES | KNPEMI_ODE_SET_V)))
+  if (!h->sweeps.have_pde && (flags & (KNPEMI_ODE_SET_TRACES | KNPEMI_ODE_SET_V)))
     return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step: a handle of knpemi_ode_create has no PDE fields to read");
   kn_inputs_changed(h);      // phi_M and the channel currents
   KN_HIP(hipSetDevice(h->device));
@@ -1624,11 +1588,10 @@ extern "C" int knpemi_ode_step(knpemi_handle* h, int sub, int model, double t0, 
   if (side) {
     KN_HIP(hipEventRecord(h->ev_fork, h->stream));
     KN_HIP(hipStreamWaitEvent(side, h->ev_fork, 0));
-    h->cur = side;
   }
-  const int rc = kn_ode_step(h, slot, t0, dt, rtol, atol, OdePde{flags, v_index, h->K, ion_param});
-  h->cur = h->stream;
-  if (rc) return rc;
+  if (int rc = kn_ode_step(h->sweeps, side ? side : h->stream, KNPEMI_K_ODE, slot, t0, dt, rtol, atol,
+                           OdePde{flags, v_index, h->K, ion_param}))
+    return rc;
   if (side) KN_HIP(hipEventRecord(second ? h->ev_join2 : h->ev_join, side));
   return KNPEMI_OK;
 }
@@ -1639,12 +1602,8 @@ extern "C" int knpemi_ode_step_emi(knpemi_handle* h, int sub, int model, double 
   if (slot < 0) return KNPEMI_EINVAL;
   if (!ion_param || !fused) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: ion_param and fused are required");
   *fused = 0;
-  KnOdeModel& m = h->ode[slot];
-  for (int i = 0; i < 3 * h->K; ++i)
-    if (ion_param[i] < 0 || ion_param[i] >= m.n_params)
-      return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: parameter index out of range");
-  if (v_index < 0 || v_index >= m.n_states) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: bad V index");
-  const bool fixed = m.method != KNPEMI_ODE_LSODA;
+  if (int rc = kn_ode_check_exchange(h->sweeps, slot, ion_param, v_index, "knpemi_ode_step_emi")) return rc;
+  const bool fixed = h->sweeps.ode[slot].method != KNPEMI_ODE_LSODA;
   if (!(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
     return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: bad dt / tolerances");
   if (h->ode_only) return kn_fail(KNPEMI_EINVAL, "knpemi_ode_step_emi: a handle of knpemi_ode_create has no potential system");
@@ -1663,7 +1622,7 @@ extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t
                                   const knpemi_ode_ss* ss, int32_t* steps_taken, int32_t* failed_step) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  const KnOdeModel& m = h->ode[slot];
+  const KnOdeModel& m = h->sweeps.ode[slot];
   const bool fixed = m.method != KNPEMI_ODE_LSODA;
   if (n_steps < 0 || !(dt > 0) || (!fixed && (!(rtol >= 0) || !(atol >= 0) || (rtol == 0 && atol == 0))))
     return kn_fail(KNPEMI_EINVAL, "knpemi_ode_advance: bad n_steps / dt / tolerances");
@@ -1682,14 +1641,14 @@ extern "C" int knpemi_ode_advance(knpemi_handle* h, int sub, int model, double t
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->aux));   // a sweep of this model may still run on an auxiliary stream
   KN_HIP(hipStreamSynchronize(h->aux2));
-  return kn_ode_advance(h, slot, t0, dt, n_steps, rtol, atol, rec_idx, n_rec, every, history, ss, steps_taken,
-                        failed_step);
+  return kn_ode_advance(h->sweeps, h->stream, slot, t0, dt, n_steps, rtol, atol, rec_idx, n_rec, every, history, ss,
+                        steps_taken, failed_step);
 }
 
 extern "C" int knpemi_ode_set_method(knpemi_handle* h, int sub, int model, int method, int n_substeps) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  KnOdeModel& m = h->ode[slot];
+  KnOdeModel& m = h->sweeps.ode[slot];
   if (method < KNPEMI_ODE_LSODA || method > KNPEMI_ODE_RUSH_LARSEN)
     return kn_fail(KNPEMI_EINVAL, "knpemi_ode_set_method: unknown method");
   if (method != KNPEMI_ODE_LSODA && (n_substeps < 1 || n_substeps > 10000))
@@ -1705,15 +1664,15 @@ extern "C" int knpemi_ode_set_method(knpemi_handle* h, int sub, int model, int m
 extern "C" int knpemi_ode_get_method(knpemi_handle* h, int sub, int model, int* method, int* n_substeps) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  if (method) *method = h->ode[slot].method;
-  if (n_substeps) *n_substeps = h->ode[slot].n_substeps;
+  if (method) *method = h->sweeps.ode[slot].method;
+  if (n_substeps) *n_substeps = h->sweeps.ode[slot].n_substeps;
   return KNPEMI_OK;
 }
 
 extern "C" int knpemi_ode_advance_chunk(knpemi_handle* h, int sub, int model) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  return h->ode[slot].adv_chunk;
+  return h->sweeps.ode[slot].adv_chunk;
 }
 
 extern "C" int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n_rhs, int64_t* n_steps, int32_t* n_failed) {
@@ -1721,22 +1680,20 @@ extern "C" int knpemi_ode_stats(knpemi_handle* h, int sub, int model, int64_t* n
   if (slot < 0) return KNPEMI_EINVAL;
   unsigned long long st[3] = {0, 0, 0};
   KN_HIP(hipSetDevice(h->device));
-  KnOdeModel& mo = h->ode[slot];
   KN_HIP(hipStreamSynchronize(h->aux));   // the sweep may run on an auxiliary stream
   KN_HIP(hipStreamSynchronize(h->aux2));
-  const int rc = kn_ode_read_stats(h->stream, mo.d_stats, mo.n_stat_blocks, st);
-  if (rc) return rc;
+  const int rc = kn_ode_stats(h->sweeps, h->stream, slot, "at least one membrane dof", st);
+  if (rc && rc != KNPEMI_EODE) return rc;
   if (n_rhs) *n_rhs = (int64_t)st[0];
   if (n_steps) *n_steps = (int64_t)st[1];
   if (n_failed) *n_failed = (int32_t)st[2];
-  if (st[2]) return kn_fail(KNPEMI_EODE, kn_ode_failure(mo.method == KNPEMI_ODE_LSODA, "at least one membrane dof"));
-  return KNPEMI_OK;
+  return rc;
 }
 
 extern "C" int knpemi_debug_ode_stamps(knpemi_handle* h, int sub, int model, uint64_t* out, int max_blocks) {
   int slot = ode_slot(h, sub, model, 1);
   if (slot < 0) return KNPEMI_EINVAL;
-  KnOdeModel& m = h->ode[slot];
+  KnOdeModel& m = h->sweeps.ode[slot];
   if (!m.d_stamps || !out) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_ode_stamps: run with KNPEMI_ODE_STAMPS=1");
   const int nb = std::min(max_blocks, m.n_stat_blocks - 1);
   KN_HIP(hipSetDevice(h->device));
@@ -1853,16 +1810,19 @@ extern "C" int knpemi_set_distributed_coarse(knpemi_handle* h, int rank, int wor
   return KNPEMI_OK;
 }
 
-extern "C" int knpemi_vec_gather(knpemi_handle* h, const void* vec_dev, const int32_t* idx_dev, int n, void* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_vec_gather: bad argument");
+int kn_vec_index(KnDevice* h, const char* who, const void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev, int gather) {
+  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, std::string(who) + ": bad argument");
   KN_HIP(hipSetDevice(h->device));
-  return kn_launch_vec_index(h->stream, static_cast<double*>(const_cast<void*>(vec_dev)), idx_dev, n, static_cast<double*>(buf_dev), 1);
+  return kn_launch_vec_index(h->stream, static_cast<double*>(const_cast<void*>(vec_dev)), idx_dev, n,
+                             static_cast<double*>(const_cast<void*>(buf_dev)), gather);
+}
+
+extern "C" int knpemi_vec_gather(knpemi_handle* h, const void* vec_dev, const int32_t* idx_dev, int n, void* buf_dev) {
+  return kn_vec_index(h, "knpemi_vec_gather", vec_dev, idx_dev, n, buf_dev, 1);
 }
 
 extern "C" int knpemi_vec_scatter(knpemi_handle* h, void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev) {
-  if (!h || n < 0 || (n > 0 && (!vec_dev || !idx_dev || !buf_dev))) return kn_fail(KNPEMI_EINVAL, "knpemi_vec_scatter: bad argument");
-  KN_HIP(hipSetDevice(h->device));
-  return kn_launch_vec_index(h->stream, static_cast<double*>(vec_dev), idx_dev, n, static_cast<double*>(const_cast<void*>(buf_dev)), 0);
+  return kn_vec_index(h, "knpemi_vec_scatter", vec_dev, idx_dev, n, buf_dev, 0);
 }
 
 extern "C" int knpemi_set_option(knpemi_handle* h, int option, int value) {

@@ -216,13 +216,14 @@ struct KnSnapTab {
 // (the table of the membrane monitors, KnMonTab: monitor_table.h, shared with the run-time compiled monitor programs)
 
 struct KnOdeModel {
-  int bound = 0, sub = 0, model_id = -1, n_states = 0, n_params = 0, nq = 0;
+  int bound = 0, model_id = -1, n_states = 0, n_params = 0, nq = 0;
+  int q0 = 0;                   // offset of its dofs in phiM / Ich
   double* d_states = nullptr;   // [n_states][nq]
   double* d_params = nullptr;   // [n_params][nq]
   uint8_t* d_mask = nullptr;    // [nq] or NULL
   int n_stim = 0;
-  int stim_idx[8];
-  double stim_val[8];
+  int stim_idx[8] = {};
+  double stim_val[8] = {};
   unsigned long long* d_stats = nullptr; // [n_stat_blocks][3]: rhs evals, steps, failures per workgroup of the sweep
   int n_stat_blocks = 0;
   unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (KNPEMI_ODE_STAMPS)
@@ -431,6 +432,30 @@ int kn_capture(KnSolver& sv, const std::function<int()>& enqueue, hipGraphExec_t
 // published host buffers, captured graphs -- knpemi_destroy and knpemi_dg_destroy, before kn_device_close
 void kn_solver_free(KnSolver& sv);
 
+// The membrane ODE sweeps (kernels_ode.hip, kernels_ode_fixed.hip, the bind halves of kernels_rtc.hip): everything they read
+// and keep, and nothing else.  knpemi_handle and knpemi_dg each embed one; the owner fills the view (knpemi_create,
+// knpemi_ode_create, knpemi_dg_create) and maps its models to slots, the sweep files never see the owner's type.  The
+// stream and the profiling slot of a launch are the caller's and come with every call.
+struct KnSweeps {
+  explicit KnSweeps(KnDevice* owner) : own(owner) {}
+  KnDevice* own;                       // device, `allocs` (what a bind allocates lives as long as the owner), prof
+  // view of the PDE side a sweep exchanges with (OdeDev is built from it: kn_ode_dev, ode_host.h)
+  const double* rec = nullptr;         // [..][KN_REC] vertex (DG: dof) records
+  const int* q2e = nullptr; const int* q2i = nullptr;   // [NQtot] record of every membrane dof on either side
+  double* phiM = nullptr;              // [NQtot]
+  double* Ich = nullptr;               // [slot][ion][NQtot]
+  int NQtot = 0, n_ions = 0;
+  bool have_pde = false;               // there are fields to read traces and V from (not: knpemi_ode_create)
+  std::vector<KnOdeModel> ode;         // the slots; knpemi_handle: [moff[n_sub]], knpemi_dg: one, offset 0
+  const void* d_lsoda_coef = nullptr;  // LsodaCoef tables, uploaded by the first LSODA sweep (kernels_ode.hip)
+  std::vector<void*> rtc_modules;      // hipModule_t of run-time compiled membrane models and monitor programs
+};
+// unloads the modules; the device memory is in the owner's `allocs` -- knpemi_destroy and knpemi_dg_destroy, before kn_device_close
+inline void kn_sweeps_free(KnSweeps& sw) {
+  for (void* m : sw.rtc_modules) (void)hipModuleUnload(static_cast<hipModule_t>(m));
+  sw.rtc_modules.clear();
+}
+
 // ghost refresh of a solver vector without Python (comm_rccl.hip)
 struct KnVecPlan {
   bool set = false;
@@ -503,10 +528,10 @@ struct KnProf {
   std::vector<hipEvent_t> ev[KNPEMI_N_KERNELS];    // begin/end pairs
   size_t used[KNPEMI_N_KERNELS] = {};              // events of ev[k] recorded since the last read
 };
-// RAII bracket around one kernel launch on stream `st`; no-op unless the kernel's bit is set in the mask
+// RAII bracket around one kernel launch on stream `st`; no-op unless the kernel's bit is set in the mask (k < 0: no slot)
 struct KnProfScope {
   KnProf& p; int k; hipStream_t st; bool on;
-  KnProfScope(KnProf& p_, int k_, hipStream_t st_) : p(p_), k(k_), st(st_), on((p_.mask >> k_) & 1u) {
+  KnProfScope(KnProf& p_, int k_, hipStream_t st_) : p(p_), k(k_), st(st_), on(k_ >= 0 && ((p_.mask >> k_) & 1u)) {
     if (on && p.stride > 1 && (p.count[k]++ % p.stride) != 0) on = false;
     if (!on) return;
     auto& v = p.ev[k];
@@ -639,6 +664,28 @@ inline int kn_table_download(hipStream_t st, const double* dev, double* host, in
   return KNPEMI_OK;
 }
 
+// Hexahedra come in tensor-product vertex order (bit a of a local vertex = its coordinate along axis a): whether the cell
+// with the vertices cell8[0..7], vertex v at x[v * x_stride .. + 2], is in one of the 48 such orders (left-handed ones
+// included) and not degenerate.  The trilinear map of a cell given in another order (e.g. the counter-clockwise order of
+// other formats) folds over, i.e. its Jacobian determinant changes sign between the corners.
+inline bool kn_hex_tensor_order(const double* x, int x_stride, const int* cell8) {
+  int pos = 0, neg = 0;
+  for (int j = 0; j < 8; ++j) {
+    double e[3][3];
+    for (int a = 0; a < 3; ++a) {
+      const double* x0 = x + (size_t)cell8[j] * x_stride;
+      const double* x1 = x + (size_t)cell8[j ^ (1 << a)] * x_stride;
+      const double sgn = ((j >> a) & 1) ? -1.0 : 1.0;
+      for (int k = 0; k < 3; ++k) e[a][k] = sgn * (x1[k] - x0[k]);
+    }
+    const double det = e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0]) +
+                       e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
+    pos += det > 0.0;
+    neg += det < 0.0;
+  }
+  return pos == 8 || neg == 8;
+}
+
 struct knpemi_handle : KnDevice {
   hipStream_t aux = nullptr;             // auxiliary stream (EMI matrix assembly beside the ODE sweep)
   hipStream_t aux2 = nullptr;            // second auxiliary stream (ODE sweeps of further membrane models)
@@ -652,7 +699,6 @@ struct knpemi_handle : KnDevice {
   std::vector<int> voff, coff, qoff, foff, moff;
   KnConsts consts{};
   KnConsts* d_consts = nullptr;        // device copy read by the kernels
-  const void* d_lsoda_coef = nullptr;  // LsodaCoef tables (kernels_ode.hip)
   KnDev dev{};
   int have_params = 0;
   int lpr = 1;                         // lanes per row of the row kernels (1, 2, 4 or 8)
@@ -666,8 +712,7 @@ struct knpemi_handle : KnDevice {
   // entries on one row; dynamic LDS of the latest EMI / KNP row launch (0: not launched yet)
   int lay_row_max = 0, lay_rowL_max = 0, lay_np_max = 0, lay_ne_max = 0;
   size_t lds_bytes_emi = 0, lds_bytes_knp = 0;
-  std::vector<void*> rtc_modules;   // hipModule_t of run-time compiled membrane models
-  std::vector<KnOdeModel> ode; // [moff[n_sub]]
+  KnSweeps sweeps{this};       // the membrane ODE sweeps; slot of (sub-domain, model): moff[sub] + model
   bool ode_only = false;       // knpemi_ode_create: membrane models without a mesh (no PDE fields)
   int n_cus = 0;               // compute units of the device, asked on first use (kernels_ode.hip: sweep_emi_eligible); -1: unknown
   // host copies of patterns for export
@@ -881,11 +926,11 @@ int kn_launch_monitor(knpemi_handle* h, double t, int write_fields);
 // fn: the fields kernel of a plug-in's monitor program, NULL: the library's kernel (a shipped model)
 int kn_launch_monitor_eval(knpemi_handle* h, const KnMonTab* d_tab, int nq, double t, double* fld, hipFunction_t fn);
 // kernels_rtc.hip: the monitor program of a plug-in (knpemi_monitor_bind_source) and the launch of one of its kernels
-int kn_rtc_monitor_bind(knpemi_handle* h, KnOdeModel& m, int n_monitored, const char* monitor_source);
+int kn_rtc_monitor_bind(KnSweeps& sw, KnOdeModel& m, int n_monitored, const char* monitor_source);
 struct OdeDev;
 int kn_rtc_launch_monitor(hipStream_t st, hipFunction_t fn, unsigned grid, unsigned block, const OdeDev& dv,
                           const KnMonArgs& a);
-int kn_rtc_bind(knpemi_handle* h, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
+int kn_rtc_bind(KnSweeps& sw, KnOdeModel& m, int n_states, int n_params, const char* rhs_source);
 // (the membrane ODE sweeps: ode_host.h)
 int kn_solve_emi(KnSolver& sv, double rtol, double atol, int maxit, int* iters, double* relres);
 int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, double* relres);
@@ -901,3 +946,6 @@ int kn_launch_field_scatter(hipStream_t st, const double* src, double* dst, int 
 int kn_launch_field_gather(hipStream_t st, const double* src, int src_stride, double* dst, int n);
 int kn_launch_trace(knpemi_handle* h, const double* ue, const double* ui, int sub, double* qe, double* qi);
 int kn_launch_vec_index(hipStream_t st, double* vec, const int32_t* idx, int n, double* buf, int gather);
+// knpemi_vec_gather / _scatter and knpemi_dg_vec_gather / _scatter: buf[i] = vec[idx[i]] (gather) or the reverse, on the
+// handle's main stream; `who`: the entry point (knpemi_api.hip)
+int kn_vec_index(KnDevice* h, const char* who, const void* vec_dev, const int32_t* idx_dev, int n, const void* buf_dev, int gather);

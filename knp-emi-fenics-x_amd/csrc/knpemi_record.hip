@@ -828,7 +828,7 @@ int mon_watch(knpemi_handle* h, const std::string& fn, int sub, int model, uint3
   if (sub == 0 && !h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": the ECS (sub-domain 0) has no membrane: watch a model of a cell");
   if (sub < 1 || sub >= h->n_sub || model < 0 || model >= h->n_models[sub])
     return kn_fail(KNPEMI_EINVAL, fn + ": membrane model index out of range");
-  const KnOdeModel& m = h->ode[h->moff[sub] + model];
+  const KnOdeModel& m = h->sweeps.ode[h->moff[sub] + model];
   if (!m.bound) return kn_fail(KNPEMI_EINVAL, fn + ": membrane model not bound (knpemi_ode_bind)");
   if (m.rtc_module && !m.mon_kernel[0])
     return kn_fail(KNPEMI_EINVAL, fn + ": a model bound from source has no monitor (knpemi_monitor_bind_source)");
@@ -860,13 +860,13 @@ extern "C" int knpemi_monitor_bind_source(knpemi_handle* h, int sub, int model, 
   if (!h || !monitor_source) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
   if (sub < 1 || sub >= h->n_sub || model < 0 || model >= h->n_models[sub])
     return kn_fail(KNPEMI_EINVAL, fn + ": membrane model index out of range");
-  KnOdeModel& m = h->ode[h->moff[sub] + model];
+  KnOdeModel& m = h->sweeps.ode[h->moff[sub] + model];
   if (!m.bound || !m.rtc_module)
     return kn_fail(KNPEMI_EINVAL, fn + ": the slot is not bound from source (knpemi_ode_bind_source); the shipped models "
                                        "bring their monitors");
   if (m.mon_kernel[0]) return kn_fail(KNPEMI_EINVAL, fn + ": the slot has a monitor already");
   KN_HIP(hipSetDevice(h->device));
-  return kn_rtc_monitor_bind(h, m, n_monitored, monitor_source);
+  return kn_rtc_monitor_bind(h->sweeps, m, n_monitored, monitor_source);
 }
 
 namespace {
@@ -908,8 +908,8 @@ int monitor_set(knpemi_handle* h, const char* who, int n_watch, const int32_t* s
       if (N.slot_of[u] == slot) return kn_fail(KNPEMI_EINVAL, fn + ": watch " + std::to_string(w) + " is listed twice");
     N.slot_of[w] = slot;
     if (T.w[w].nq > 0) {
-      N.fn[w][0] = h->ode[slot].mon_kernel[0];
-      N.fn[w][1] = h->ode[slot].mon_kernel[1];
+      N.fn[w][0] = h->sweeps.ode[slot].mon_kernel[0];
+      N.fn[w][1] = h->sweeps.ode[slot].mon_kernel[1];
     }
     KnMonWatch& W = T.w[w];
     woff[w] = wo;
@@ -1067,7 +1067,7 @@ extern "C" int knpemi_monitor_eval(knpemi_handle* h, int sub, int model, double 
   KnMonWatch& W = T.w[0];
   int slot = -1;
   if (int rc = mon_watch(h, fn, sub, model, mask, v_index, ion_param, &W, &slot)) return rc;
-  const KnOdeModel& m = h->ode[slot];
+  const KnOdeModel& m = h->sweeps.ode[slot];
   const size_t nq = (size_t)W.nq, nb = (size_t)popcount((int)(mask & 0x7FFFFFFFu)) + (mask >> 31);
   if (n != nb * nq) return kn_fail(KNPEMI_EINVAL, fn + ": length is not (bits set) * (membrane dofs)");
   KN_HIP(hipSetDevice(h->device));
@@ -1131,7 +1131,7 @@ extern "C" int knpemi_snapshot_set(knpemi_handle* h, int n_watch, const int32_t*
         if (sub < 1 || sub >= h->n_sub) return kn_fail(KNPEMI_EINVAL, who + ": a state lives on the membrane of a cell (sub >= 1)");
         const int model = ix / KNPEMI_SNAPSHOT_STATE_STRIDE, state = ix % KNPEMI_SNAPSHOT_STATE_STRIDE;
         if (ix < 0 || model >= h->n_models[sub]) return kn_fail(KNPEMI_EINVAL, who + ": membrane model index out of range");
-        const KnOdeModel& m = h->ode[h->moff[sub] + model];
+        const KnOdeModel& m = h->sweeps.ode[h->moff[sub] + model];
         if (!m.bound || !m.d_states) return kn_fail(KNPEMI_EINVAL, who + ": membrane model not bound (knpemi_ode_bind)");
         if (state >= m.n_states) return kn_fail(KNPEMI_EINVAL, who + ": state index out of range");
         if (m.nq != h->n_q[sub]) return kn_fail(KNPEMI_EINVAL, who + ": the state table does not cover the membrane dofs");

@@ -9,7 +9,7 @@
 #include "membrane_models.h"
 
 // ---- launch arguments ---------------------------------------------------------------------------------------------
-// the tables of a sweep, as their owner describes them (knpemi_handle: a KnOdeModel; knpemi_dg: its membrane nodes)
+// the tables of a sweep, as a slot of KnSweeps describes them
 struct OdeTables {
   int nq, q0, NQtot, model_slot;
   double* states;
@@ -24,7 +24,7 @@ struct OdePde {
 };
 // every field of an OdeArgs is set here or value-initialised; `pde` NULL: a standalone advance
 OdeArgs kn_ode_args(const OdeTables& T, double t0, double dt, double rtol, double atol, const OdePde* pde);
-OdeDev kn_ode_dev(const knpemi_handle* h);
+inline OdeDev kn_ode_dev(const KnSweeps& sw) { return OdeDev{sw.rec, sw.q2e, sw.q2i, sw.phiM, sw.Ich}; }
 
 // ---- shipped models -----------------------------------------------------------------------------------------------
 template <class M, int L>
@@ -43,9 +43,11 @@ void with_model(int model_id, F&& f) {
 }
 
 // ---- the sweeps ---------------------------------------------------------------------------------------------------
-// kernels_ode.hip: one entry per kernel shape, integrator and model source chosen inside
-int kn_ode_step(knpemi_handle* h, int slot, double t0, double dt, double rtol, double atol, const OdePde& pde);
-int kn_ode_advance(knpemi_handle* h, int slot, double t0, double dt, int n_steps, double rtol, double atol,
+// kernels_ode.hip: one entry per kernel shape, integrator and model source chosen inside.  On the caller's stream `st`;
+// the step is bracketed into the owner's profiling slot prof_slot (< 0: none).
+int kn_ode_step(KnSweeps& sw, hipStream_t st, int prof_slot, int slot, double t0, double dt, double rtol, double atol,
+                const OdePde& pde);
+int kn_ode_advance(KnSweeps& sw, hipStream_t st, int slot, double t0, double dt, int n_steps, double rtol, double atol,
                    const int32_t* rec_idx, int n_rec, int every, double* history, const knpemi_ode_ss* ss,
                    int32_t* steps_taken, int32_t* failed_step);
 // The step of model `slot` and the potential system's A, P and volume part of b (knpemi_assemble_emi with emi_flags |
@@ -58,9 +60,6 @@ int kn_ode_step_emi(knpemi_handle* h, int slot, double t0, double dt, double rto
 bool kn_sweep_emi_rows_ok(const knpemi_handle* h);
 int kn_launch_sweep_emi(knpemi_handle* h, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef, int n_sweep,
                         int emi_flags, int* launched);
-// the LSODA step of a shipped model over a caller-described table (the DG variant: membrane nodes of the broken space)
-int kn_launch_ode_raw(hipStream_t st, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef);
-int kn_lsoda_coef_upload(std::vector<void*>& owner, const void** out);   // LsodaCoef tables on the device, owned by `owner`
 // kernels_ode_fixed.hip: the fixed-step kernels of the shipped models (m.method, m.n_substeps)
 int kn_launch_ode_fixed_step(hipStream_t st, const KnOdeModel& m, const OdeDev& dv, const OdeArgs& a);
 int kn_launch_ode_fixed_advance(hipStream_t st, const KnOdeModel& m, const OdeArgs& a, const OdeAdvArgs& v);
@@ -74,9 +73,20 @@ int kn_rtc_launch(hipStream_t st, hipFunction_t fn, unsigned grid, const A& a, c
   return kn_rtc_launch(st, fn, grid, &p, sizeof(p));
 }
 
-// ---- upkeep shared by the two owners of a sweep ---------------------------------------------------------------------
-// reads, resets and sums the per-workgroup partials: st = {rhs evaluations, steps, failures}
-int kn_ode_read_stats(hipStream_t st, unsigned long long* d_stats, int n_blocks, unsigned long long out[3]);
+// ---- upkeep of a slot, one body under knpemi_ode_* and knpemi_dg_ode_* (kernels_ode.hip) -----------------------------
+// `who` starts the error texts: the entry point.
+// a shipped model may be bound to `slot`: known id, the counts are Model::NS and Model::NP, slot still free
+int kn_ode_check_shipped(const KnSweeps& sw, int slot, int model_id, int n_states, int n_params, const std::string& who);
+// what a step exchanges with the PDE fields: the 3 * n_ions parameter columns of the ions and V's state column
+int kn_ode_check_exchange(const KnSweeps& sw, int slot, const int32_t* ion_param, int v_index, const std::string& who);
+// binds `slot`: its nq dofs from q0 on, zeroed states and parameters, the statistics partials
+int kn_ode_alloc_tables(KnSweeps& sw, hipStream_t st, int slot, int q0, int nq, int model_id, int n_states, int n_params);
+// host tables [dof][column], either may be NULL
+int kn_ode_set_tables(KnSweeps& sw, hipStream_t st, int slot, const double* states, const double* params);
+int kn_ode_get_tables(KnSweeps& sw, hipStream_t st, int slot, double* states, double* params);
+// reads, resets and sums the per-workgroup partials: out = {rhs evaluations, steps, failures}; KNPEMI_EODE, out filled,
+// when a dof failed (`where` e.g. "at least one membrane dof")
+int kn_ode_stats(KnSweeps& sw, hipStream_t st, int slot, const std::string& where, unsigned long long out[3]);
 // the message of a failed sweep; `where` e.g. "3 membrane dof(s)"
 inline std::string kn_ode_failure(bool lsoda, const std::string& where) {
   return lsoda ? "LSODA failed on " + where + " (odeSolver.py:121 `assert success`)"
