@@ -6,7 +6,10 @@ time loop :341-372): per step the membrane ODEs, the EMI solve, the KNP solve an
 update, through the knpemi API.  The mesh comes from the in-memory generator or from the XDMF file `make_mesh_2D.py` writes (`--mesh-file`);
 ADIOS2 checkpoints are replaced by a compressed `.npz` of the final fields (I/O is outside the hot path).
 
-    python run_2D.py [--res 1] [--steps 10] [--iterative]
+    python run_2D.py [--res 1] [--steps 10] [--iterative] [--cell-type quadrilateral]
+
+`--cell-type quadrilateral` runs the same rectangle on Q1 squares (one keyword of `dolfinx.mesh.create_rectangle` in the
+reference's mesh script); a mesh file with a `Quadrilateral` topology works through `--mesh-file`.
 """
 import argparse
 import os
@@ -130,8 +133,10 @@ def monitor_state(s):
 
 def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_file=None, series=None,
                  ode_method="lsoda", ode_substeps=None, events=None, event_threshold=-20e-3, fluxes=None, exchange=None,
-                 maps=None, maps_threshold=None, monitor=None):
-    """series: path of a .npz with the time series at the figures' points (figure_observables), or None.
+                 maps=None, maps_threshold=None, monitor=None, cell_type=None):
+    """cell_type: "quadrilateral" generates the 2-D mesh on quadrilaterals (None: the kind's default cells; a mesh file
+    brings its own).
+    series: path of a .npz with the time series at the figures' points (figure_observables), or None.
     ode_method / ode_substeps: the membrane integrator (MembraneModel.set_integrator); the reference's drivers name the
     sub-step count `n_steps_ODE` (run_2D.py:176).
     events: path of a .npz with the membrane events of cell 1 (knpemi.MembraneEvents: upward crossings of
@@ -144,7 +149,13 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
     maps_threshold, in mM -- default: 0.001 mM above the initial ECS concentration, which the ECS next to the stimulated end
     passes within the first 20 steps -- and peak / trough of phi_M), or None.
     monitor: path of a .npz with the series of the membrane monitors (membrane_monitors), or None."""
-    s = Setup(kind, res, g_syn=g_syn, mesh_data=read_mesh(mesh_file) if mesh_file else None)
+    mesh_data = read_mesh(mesh_file) if mesh_file else None
+    if mesh_data is None and cell_type not in (None, "triangle"):
+        if kind != "2d":
+            raise ValueError("--cell-type selects the cells of the generated 2-D mesh")
+        from knpemi.fem import make_mesh_2D
+        mesh_data = make_mesh_2D(res, cell_type=cell_type)
+    s = Setup(kind, res, g_syn=g_syn, mesh_data=mesh_data)
     obs = figure_observables(s) if series else None
     ev = membrane_events(s, event_threshold) if events else None
     fl = ion_fluxes(s) if fluxes else None
@@ -206,9 +217,13 @@ def solve_system(kind, res, n_steps, direct=True, g_syn=10.0, out=None, mesh_fil
     return s, num_it_emi, num_it_knp
 
 
-def build_parser(res=1, steps=10, mesh_script="make_mesh_2D.py"):
+def build_parser(res=1, steps=10, mesh_script="make_mesh_2D.py", cell_types=None):
+    """cell_types: the choices of --cell-type (the first is the default), or None: no such option."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=res)
+    if cell_types:
+        ap.add_argument("--cell-type", choices=list(cell_types), default=cell_types[0],
+                        help="cells of the generated mesh (a --mesh-file brings its own)")
     ap.add_argument("--steps", type=int, default=steps)
     ap.add_argument("--iterative", action="store_true")
     ap.add_argument("--mesh-file", default=None, help=f"XDMF mesh written by {mesh_script} (default: generate)")
@@ -229,6 +244,9 @@ def build_parser(res=1, steps=10, mesh_script="make_mesh_2D.py"):
     return ap
 
 
+CELL_TYPES_2D = ("triangle", "quadrilateral")
+
+
 def recorder_arguments(a):
     """The recorder options of a parsed command line as keyword arguments of solve_system."""
     return dict(series=a.series, ode_method=a.ode_method, ode_substeps=a.ode_substeps, events=a.events,
@@ -237,9 +255,10 @@ def recorder_arguments(a):
 
 
 if __name__ == "__main__":
-    a = build_parser().parse_args()
+    a = build_parser(cell_types=CELL_TYPES_2D).parse_args()
     s, it_emi, it_knp = solve_system("2d", a.res, a.steps, direct=not a.iterative, mesh_file=a.mesh_file,
-                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), **recorder_arguments(a))
+                                     out=os.path.join(HERE, "results", f"2D_{a.res}.npz"), cell_type=a.cell_type,
+                                     **recorder_arguments(a))
     v = s.phi_M_prev[1].x._a
     print(f"phi_M after {a.steps} steps: min {v.min():.6f} V, max {v.max():.6f} V")
     print(f"average number of iterations emi solver: {sum(it_emi) / len(it_emi)}")

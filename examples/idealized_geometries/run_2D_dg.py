@@ -5,6 +5,9 @@ membrane ODEs at the facet nodes, both assemblies, both linear solves (CG / BiCG
 from the CSR the kernels fill instead.
 
     python run_2D_dg.py [--resolution 1] [--steps 100] [--host-solves]
+
+`--cell-type quadrilateral` is parsed, as in run_2D.py, and refused with the DG module's message: the DG variant has no
+quadrilateral kernels.
 """
 import argparse
 import os
@@ -34,9 +37,9 @@ def solve_singular(A, b):
 
 
 class DGRun:
-    def __init__(self, resolution=1, g_syn=10.0, dt=DT, device_solves=True, rtol=(1e-5, 1e-7)):
+    def __init__(self, resolution=1, g_syn=10.0, dt=DT, device_solves=True, rtol=(1e-5, 1e-7), cell_type="triangle"):
         self.device_solves, self.rtol, self.iterations = device_solves, rtol, []
-        mesh, ct, ft = make_mesh_2D(resolution)
+        mesh, ct, ft = make_mesh_2D(resolution, cell_type=cell_type)      # quadrilaterals: DGProblem refuses them
         self.dp = dp = DGProblem(mesh, ct, ft, [0, 1], [1])
         self.ions = [dict(name="K", z=1.0, D=[D_K] * 2), dict(name="Cl", z=-1.0, D=[D_CL] * 2), dict(name="Na", z=1.0, D=[D_NA] * 2)]
         dp.set_params(dict(dt=dt, F=FARADAY, psi=PSI, C_M=C_M), self.ions)
@@ -82,13 +85,18 @@ class DGRun:
         self.k += 1
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--resolution", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--host-solves", action="store_true")
-    a = ap.parse_args()
-    run = DGRun(a.resolution, device_solves=not a.host_solves)
+    ap.add_argument("--cell-type", choices=["triangle", "quadrilateral"], default="triangle")
+    return ap
+
+
+if __name__ == "__main__":
+    a = build_parser().parse_args()
+    run = DGRun(a.resolution, device_solves=not a.host_solves, cell_type=a.cell_type)
     for k in range(a.steps):
         run.step()
         if (k + 1) % 10 == 0:

@@ -32,12 +32,15 @@ extern "C" {
 #define KNPEMI_EODE (-4)     /* LSODA reported failure on at least one membrane dof
                                 (`assert success`, src/knpemi/odeSolver.py:121) */
 
-/* cell kinds (CG-1 on each): triangle / tetrahedron = P1, hexahedron = Q1
+/* cell kinds (CG-1 on each): triangle / tetrahedron = P1, hexahedron = Q1, quadrilateral = Q1 in 2-D (what
+ * dolfinx.mesh.create_rectangle(..., CellType.quadrilateral) gives; the conforming systems only, knpemi_dg_create
+ * refuses it)
  * (src/knpemi/emiWeakForm.py:66, examples/idealized_geometries/make_mesh_2D.py:53-55,
  *  make_mesh_3D.py:100-102) */
 #define KNPEMI_TRIANGLE 0
 #define KNPEMI_TETRAHEDRON 1
 #define KNPEMI_HEXAHEDRON 2
+#define KNPEMI_QUADRILATERAL 3
 
 /* membrane models shipped as device code (the reference's numba cfunc plug-ins):
  *   HH_SI  examples/idealized_geometries/mm_hh.py:139-227          (4 states, 22 parameters)
@@ -92,15 +95,17 @@ typedef struct knpemi_handle knpemi_handle;
  * and facet_q ("+" = ECS side, "-" = cell side; emiWeakForm.py:25-26). */
 typedef struct {
   int32_t gdim;                      /* 2 or 3 */
-  int32_t cell_kind;                 /* KNPEMI_TRIANGLE | TETRAHEDRON | HEXAHEDRON */
+  int32_t cell_kind;                 /* KNPEMI_TRIANGLE | TETRAHEDRON | HEXAHEDRON | QUADRILATERAL (gdim 2) */
   int32_t n_sub;                     /* sub-domains, ECS first */
   int32_t n_ions;                    /* K = 2..4; the last ion is eliminated (run_3D.py:255-256) */
   const int32_t* n_vert;             /* [n_sub] vertices (owned + ghost) of each sub-mesh */
   const int32_t* n_cell;             /* [n_sub] */
   const double* const* x;            /* [n_sub] -> n_vert*gdim, row-major */
-  const int32_t* const* cells;       /* [n_sub] -> n_cell*nv sub-mesh vertex ids (hexahedra: local vertex j at the reference
-                                        point whose coordinate along axis a is bit a of j; any of the 48 such orders of a
-                                        cell, left-handed ones included; a folded cell is refused) */
+  const int32_t* const* cells;       /* [n_sub] -> n_cell*nv sub-mesh vertex ids (hexahedra and quadrilaterals: local vertex j at
+                                        the reference point whose coordinate along axis a is bit a of j; any of the 48 (8)
+                                        such orders of a cell, left-handed ones included; a cell whose Jacobian determinant
+                                        changes sign between its corners -- counter-clockwise order, non-convex, degenerate --
+                                        is refused) */
   const int32_t* n_q;                /* [n_sub] membrane dofs of Q_sub (0 for the ECS) */
   const int32_t* n_facet;            /* [n_sub] membrane facets of the cell (0 for the ECS) */
   const int32_t* const* facet_e;     /* [n_sub] -> n_facet*nf ECS sub-mesh vertex ids */
@@ -119,7 +124,8 @@ typedef struct {
    * per grid cell).  When the vertices of every cell are corners of one grid cell (lattice coordinates within 1e-6 of
    * integers) and no Laplacian row is longer than 31, the row kernels take gradient products and volumes from a table of
    * the (at most eight) cell shapes and stage no coordinates; there is no fall-back to the first cell: all zero, or a cell
-   * that does not fit, keeps the general kernels. */
+   * that does not fit, keeps the general kernels.
+   * Quadrilaterals: ignored (there is no uniform-cell variant of their row kernels). */
   double uniform_cell[9];
 } knpemi_problem_desc;
 
@@ -338,7 +344,9 @@ int knpemi_debug_launch_chain(knpemi_handle* h, int kind, int n, int links, int 
 
 /* Diagnostics (no reference counterpart): which geometry specialisations knpemi_create selected for the row kernels.
  * *flags: bit 0 = lattice tetrahedra of a uniform grid (shape table, no coordinates staged), bit 1 = hexahedra that are all
- * parallelepipeds, bit 2 = ... and all the same box (uniform hexahedral kernels). */
+ * parallelepipeds or quadrilaterals that are all parallelograms (closed-form rows; KNPEMI_HEX_GENERAL=1 /
+ * KNPEMI_QUAD_GENERAL=1 force the quadrature kernels), bit 2 = ... and all the same box (uniform hexahedral kernels; never
+ * set for quadrilaterals). */
 int knpemi_debug_geometry(knpemi_handle* h, int* flags);
 
 /* Diagnostics (no reference counterpart): the sizes of the row-kernel layout knpemi_create built, so that a test can tell

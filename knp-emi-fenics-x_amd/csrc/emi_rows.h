@@ -182,10 +182,31 @@ __device__ __forceinline__ Rec5 lds_rec5(const double* recs, int i) {
 
 // one staged record from the 64-byte vertex record u (x y | z c3 | c0 c1 | c2 phi).  KS = 0: EMI (5 doubles),
 // KS >= 1: KNP with KS solved ions (4 + KS doubles).  fs / nvs: ECS source term (NULL when unused), v the vertex.
-template <int KS, bool UNI = false>
+// GD = 2 (quadrilaterals): the records without z -- EMI x y | kappa sigma (4 doubles), KNP x y f_0 .. f_{KS-1} phi (3 + KS).
+template <int KS, bool UNI = false, int GD = 3>
 __device__ __forceinline__ void write_staged(double* recs, int i, const double2 (&u)[4], double inv_dt, const double* fs0,
                                              int nvs, int v, const KnSubConst* scp) {
-  if constexpr (KS == 0) {
+  if constexpr (GD == 2) {
+    static_assert(!UNI, "2-D records carry their coordinates");
+    if constexpr (KS == 0) {
+      const double c0 = u[2].x, c1 = u[2].y, c2 = u[3].x, c3 = u[1].y;
+      const double kap = scp->kap[0] * c0 + scp->kap[1] * c1 + scp->kap[2] * c2 + scp->kap[3] * c3;
+      const double sig = scp->sig[0] * c0 + scp->sig[1] * c1 + scp->sig[2] * c2 + scp->sig[3] * c3;
+      double2* dst = reinterpret_cast<double2*>(recs + (size_t)i * 4);
+      dst[0] = double2{u[0].x, u[0].y}; dst[1] = double2{kap, sig};
+    } else {
+      const double cp[3] = {u[2].x, u[2].y, u[3].x};
+      double* d = recs + (size_t)i * (3 + KS);
+      d[0] = u[0].x; d[1] = u[0].y;
+#pragma unroll
+      for (int k = 0; k < KS; ++k) {
+        double f = cp[k] * inv_dt;
+        if (fs0) f += fs0[(size_t)k * nvs + v];
+        d[2 + k] = f;
+      }
+      d[2 + KS] = u[3].y;
+    }
+  } else if constexpr (KS == 0) {
     const double c0 = u[2].x, c1 = u[2].y, c2 = u[3].x, c3 = u[1].y;   // ions beyond K have kap = sig = 0 (and c = 0)
     const double kap = scp->kap[0] * c0 + scp->kap[1] * c1 + scp->kap[2] * c2 + scp->kap[3] * c3;
     const double sig = scp->sig[0] * c0 + scp->sig[1] * c1 + scp->sig[2] * c2 + scp->sig[3] * c3;
@@ -228,7 +249,7 @@ __device__ __forceinline__ void write_staged(double* recs, int i, const double2 
   }
 }
 
-template <int KS, bool UNI = false>
+template <int KS, bool UNI = false, int GD = 3>
 __device__ __forceinline__ void stage_records(const KnDev& D, const BlkInfo& B, double* recs, uint16_t* eloc, int tid,
                                               double inv_dt, const double* fs0, int nvs,
                                               const KnSubConst* scp = nullptr) {
@@ -248,12 +269,12 @@ __device__ __forceinline__ void stage_records(const KnDev& D, const BlkInfo& B, 
     }
 #pragma unroll
   for (int k = 0; k < KN_STAGE; ++k)
-    if (vv[k] >= 0) write_staged<KS, UNI>(recs, tid + k * KN_BLOCK, u[k], inv_dt, fs0, nvs, vv[k], scp);
+    if (vv[k] >= 0) write_staged<KS, UNI, GD>(recs, tid + k * KN_BLOCK, u[k], inv_dt, fs0, nvs, vv[k], scp);
   for (int i = tid + KN_STAGE * KN_BLOCK; i < B.nuniq; i += KN_BLOCK) {   // oversized blocks only
     const int v = D.blk_uverts[B.uoff + i];
     const double2* src = reinterpret_cast<const double2*>(D.VR + (size_t)v * KN_REC);
     const double2 uu[4] = {src[0], src[1], src[2], src[3]};
-    write_staged<KS, UNI>(recs, i, uu, inv_dt, fs0, nvs, v, scp);
+    write_staged<KS, UNI, GD>(recs, i, uu, inv_dt, fs0, nvs, v, scp);
   }
 }
 

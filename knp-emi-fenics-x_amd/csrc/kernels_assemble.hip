@@ -18,6 +18,8 @@
 // what the simplex EMI row block is made of (logical_block, the membrane part of an EMI row, the block descriptors and the
 // staging of the records, which the other row kernels here use too) and the block itself: shared with the fused launch
 #include "emi_rows.h"
+// element rows of the Q1 quadrilateral
+#include "quad_rows.h"
 
 namespace {
 
@@ -166,6 +168,14 @@ constexpr bool knp_rows_built(int L, int KS, int MEM) {
 constexpr bool knp_rows_hex_built(int L, int KS, int MEM) {
   return L == 4 ? KS >= 1 && KS <= 3 && MEM >= 0 && MEM <= 2 : (L == 1 || L == 2 || L == 8) && KS == 2 && MEM == 0;
 }
+// quadrilaterals: 2 lanes per row (the default) and 4, every ion count and membrane path with both; general cells and
+// parallelograms, no uniform-cell variant.  KS = 0: the EMI kernel
+constexpr bool rows_quad_built(int L, int KS, int MEM, int GEO) {
+  return (L == 2 || L == 4) && KS >= 0 && KS <= 3 && MEM >= 0 && MEM <= 2 && (GEO == 0 || GEO == 1);
+}
+// vertices per cell of a cell kind, and the kinds by their row kernels
+constexpr int kind_nv(int kind) { return kind == KNPEMI_TRIANGLE ? 3 : (kind == KNPEMI_HEXAHEDRON ? 8 : 4); }
+constexpr bool kind_simplex(int kind) { return kind == KNPEMI_TRIANGLE || kind == KNPEMI_TETRAHEDRON; }
 
 // one simplex EMI row block per workgroup (emi_rows.h).  UT: lattice tetrahedra of a uniform grid
 template <int GDIM, int LPR, bool UT = false>
@@ -962,6 +972,182 @@ __global__ __launch_bounds__(KN_BLOCK, GEO == 2 ? 4 : (GEO == 1 ? 3 : 2)) void k
   });
 }
 
+// =============================================================================================
+// Q1 quadrilaterals: the row-block scheme once more, with 2-D records (EMI x y kappa sigma, KNP x y f_0 .. phi) and the
+// element rows of quad_rows.h.  A (row, cell) pair is pair_cell (cell * 8 + the row vertex's local index) and ONE word of
+// four row-relative slot bytes; the membrane facets are intervals, the NF = 2 code of the triangles.
+// GEO: 0 general bilinear cells (2 x 2 quadrature), 1 every cell a parallelogram (closed forms in the frame of the row
+// vertex).  There is no uniform-cell variant.
+// =============================================================================================
+template <int LPR, int GEO>
+__global__ __launch_bounds__(KN_BLOCK) void emi_rows_quad_v2(KnDev D, const KnConsts* __restrict__ Cp, int acc_n, int rec_n,
+                                                             int want_p, int splitting) {
+  constexpr int NF = 2, RW = 4;
+  const KnConsts& C = *Cp;
+  extern __shared__ __align__(16) double lds[];
+  double* accA = lds;
+  double* recs = lds + (size_t)acc_n;
+  uint16_t* eloc = reinterpret_cast<uint16_t*>(recs + RW * (size_t)rec_n);
+  const int tid = threadIdx.x;
+  const int b = logical_block(blockIdx.x, D.nblocks);
+  const BlkInfo B = load_blk(D, b, tid >> 6);
+  const int s = B.sub, seglen = B.seglen;
+  const int rloc = tid / LPR, sub = tid % LPR;
+  const BlkRows<LPR, KN_CHUNK_SIMPLEX> rows(D, b);
+  bool valid;
+  const int g = rows.row(rloc, valid);
+  const int64_t base = (int64_t)B.slbase * KN_SLICE + (tid & 63);
+  const int np = B.np;
+  // first pair entry of this lane: issued before phase A so that its latency overlaps the staging
+  int pc0 = -1;
+  uint32_t sl0 = 0u;
+  if (valid && np > 0) {
+    pc0 = D.pair_cell[base];
+    sl0 = D.pair_slots[base];
+  }
+  const int4 ri = D.row_info[g];
+  for (int i = tid; i < seglen; i += KN_BLOCK) accA[i] = 0.0;
+  const KnSubConst& sc = C.sc[s];
+  stage_records<0, false, 2>(D, B, recs, eloc, tid, 0.0, nullptr, 0, &sc);
+  __syncthreads();
+
+  const bool cell_side = s > 0;
+  double bacc = 0.0, gam = 0.0;
+  if (valid) {
+    const int rowbase = ri.x, lap = ri.y & 0xFFFF, ne = (unsigned)ri.y >> 16, rL = ri.z;
+    auto do_pair = [&](int pc, uint32_t sl) {
+      const int li = pc & 3;
+      int slot[4];
+      // GEO 1: the frame of the row vertex, local vertex j ^ li takes position j
+#pragma unroll
+      for (int j = 0; j < 4; ++j) slot[j] = (int)((sl >> (8 * (GEO == 1 ? j ^ li : j))) & 255);
+      RecQ4 r[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = lds_recq4(recs, eloc[rL + slot[j]]);
+      double ra[4];
+      if constexpr (GEO == 1) quadcf::emi_row0(r, ra, bacc);
+      else quadq::emi_row(r, li, ra, bacc);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) unsafeAtomicAdd(&accA[lap + slot[j]], ra[j]);
+    };
+    if (pc0 >= 0) do_pair(pc0, sl0);
+    for (int p = 1; p < np; ++p) {
+      const int64_t ent = base + (int64_t)p * KN_SLICE;
+      const int pc = D.pair_cell[ent];
+      if (pc >= 0) do_pair(pc, D.pair_slots[ent]);
+    }
+    if (ne > 0) emi_membrane_row<NF>(D, C, ri.w, ne, sub, LPR, cell_side, rowbase, accA, splitting, gam);
+  }
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) { bacc += __shfl_xor(bacc, m); gam += __shfl_xor(gam, m); }
+  if (valid && sub == 0) D.b_emi[g] = bacc + gam;
+  __syncthreads();
+  rows.for_each_entry(tid, 0, [&](int i, int64_t gp) {
+    const double a = accA[i];
+    KN_ROW_STORE(a, &D.A_emi[gp]);
+    if (want_p) KN_ROW_STORE(cell_side ? a + D.P_mass[gp - D.pmass0] : a, &D.P_emi[gp]);
+  });
+}
+
+template <int LPR, int GEO, int KS, int MEM>
+__global__ __launch_bounds__(KN_BLOCK) void knp_rows_quad_v2(KnDev D, const KnConsts* __restrict__ Cp, int acc_n, int rec_n,
+                                                             int gam_n, int splitting) {
+  constexpr int RW = 3 + KS;
+  const KnConsts& C = *Cp;
+  extern __shared__ __align__(16) double lds[];
+  double* acc = lds;
+  double* recs = lds + (size_t)KS * acc_n;
+  double* gam = recs + (size_t)RW * rec_n + ((RW * rec_n) & 1);
+  uint16_t* eloc = reinterpret_cast<uint16_t*>(gam + (size_t)KS * gam_n);
+  const int tid = threadIdx.x;
+  const int b = logical_block(blockIdx.x, D.nblocks);
+  const BlkInfo B = load_blk(D, b, tid >> 6);
+  const int s = B.sub, nnzLb = B.nnzLb;
+  const int v0 = C.voff[s], nvs = C.voff[s + 1] - v0;
+  const double* fs0 = (D.fsrc && s == 0) ? D.fsrc : nullptr;
+  const int rloc = tid / LPR, sub = tid % LPR;
+  const BlkRows<LPR, KN_CHUNK_SIMPLEX> rows(D, b);
+  bool valid;
+  const int g = rows.row(rloc, valid);
+  const int64_t base = (int64_t)B.slbase * KN_SLICE + (tid & 63);
+  const int np = B.np;
+  int pc0 = -1;
+  uint32_t sl0 = 0u;
+  if (valid && np > 0) {
+    pc0 = D.pair_cell[base];
+    sl0 = D.pair_slots[base];
+  }
+  const int4 ri = D.row_info[g];
+  for (int i = tid; i < nnzLb; i += KN_BLOCK) {
+#pragma unroll
+    for (int k = 0; k < KS; ++k) acc[(size_t)k * acc_n + i] = 0.0;
+  }
+  stage_records<KS, false, 2>(D, B, recs, eloc, tid, C.inv_dt, fs0, nvs);
+  if constexpr (MEM == 1) membrane_entries_to_lds<2, KS>(D, C, B.me0, B.mne, s > 0, splitting, tid, gam);
+  __syncthreads();
+
+  const KnSubConst& sc = C.sc[s];
+  double bk[KS];
+#pragma unroll
+  for (int k = 0; k < KS; ++k) bk[k] = 0.0;
+  if (valid) {
+    const int rL = ri.z;
+    auto do_pair = [&](int pc, uint32_t sl) {
+      const int li = pc & 3;
+      int slot[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) slot[j] = (int)((sl >> (8 * (GEO == 1 ? j ^ li : j))) & 255);
+      RecQK<KS> r[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = lds_recqk<KS>(recs, eloc[rL + slot[j]]);
+      double M[4], S[4], Cc[4];
+      if constexpr (GEO == 1) quadcf::knp_row0(r, M, S, Cc);
+      else quadq::knp_row(r, li, M, S, Cc);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int k = 0; k < KS; ++k) {
+          unsafeAtomicAdd(&acc[(size_t)k * acc_n + rL + slot[j]], M[j] * C.inv_dt + sc.D[k] * S[j] + sc.zpsiD[k] * Cc[j]);
+          bk[k] += M[j] * r[j].f[k];
+        }
+      }
+    };
+    if (pc0 >= 0) do_pair(pc0, sl0);
+    for (int p = 1; p < np; ++p) {
+      const int64_t ent = base + (int64_t)p * KN_SLICE;
+      const int pc = D.pair_cell[ent];
+      if (pc >= 0) do_pair(pc, D.pair_slots[ent]);
+    }
+    {   // the row's LPR lanes share its membrane entries (the sums meet in the reduction below)
+      const int ne = (unsigned)ri.y >> 16;
+      for (int e = ri.w + sub; e < ri.w + ne; e += LPR) {
+        if constexpr (MEM == 2) membrane_entry_early<2, KS>(D, e, bk);
+        else {
+#pragma unroll
+          for (int k = 0; k < KS; ++k) bk[k] += MEM == 1 ? gam[(size_t)(e - B.me0) * KS + k] : D.gam_e[(size_t)KS * e + k];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) {
+#pragma unroll
+    for (int k = 0; k < KS; ++k) bk[k] += __shfl_xor(bk[k], m);
+  }
+  if (valid && sub == 0) {
+    const size_t bb = (size_t)KS * v0 + (size_t)(g - v0);
+#pragma unroll
+    for (int k = 0; k < KS; ++k) D.b_knp[bb + (size_t)k * nvs] = bk[k];
+  }
+  __syncthreads();
+  const int64_t subnnz0 = D.rowptrL[v0], subnnz = D.rowptrL[v0 + nvs] - subnnz0;
+  double* out0 = D.A_knp + (size_t)KS * subnnz0 - subnnz0;
+  rows.for_each_entry(tid, 1, [&](int i, int64_t gp) {
+#pragma unroll
+    for (int k = 0; k < KS; ++k) KN_ROW_STORE(acc[(size_t)k * acc_n + i], &out0[(size_t)k * subnnz + gp]);
+  });
+}
+
 // ---------------------------------------------------------------------------------------------
 // KNP membrane-facet kernel: the rational Robin/coupling integrand of knpWeakForm.py:168-214 with
 // degree-6 quadrature (tables staged in LDS).  One thread per (membrane facet, side): it evaluates the
@@ -1402,6 +1588,15 @@ int launch_nf(const knpemi_handle* h, const char* name, F&& f) {
 // finds the instantiation for the handle (nested kn_pick under the kernel's ..._built predicate) and hands its name, the
 // kernel (as a RowKernel<...>) and the arguments behind (D, consts) to `go` -- the raised dynamic-LDS limit, the profile bracket, the launch on
 // h->cur; no call of `go`: nothing is built for the handle, refused by name.  Last the launch check.  mem: knp_rows' MEM.
+inline const char* kn_cell_kind_name(int kind) {
+  switch (kind) {
+    case KNPEMI_TRIANGLE: return "triangles";
+    case KNPEMI_TETRAHEDRON: return "tetrahedra";
+    case KNPEMI_HEXAHEDRON: return "hexahedra";
+    case KNPEMI_QUADRILATERAL: return "quadrilaterals";
+  }
+  return "unknown cells";
+}
 template <auto KERNEL> struct RowKernel { static constexpr auto value = KERNEL; };
 template <class Pick>
 int launch_rows(knpemi_handle* h, int system, const KnRowShape& s, int mem, Pick&& pick) {
@@ -1424,7 +1619,7 @@ int launch_rows(knpemi_handle* h, int system, const KnRowShape& s, int mem, Pick
                    std::string(knp ? "knp_rows: unsupported lanes-per-row / ion-count / membrane-option combination: "
                                    : "emi_rows: bad lanes-per-row: ") +
                        std::to_string(h->lpr) + " lanes per row, " + std::to_string(h->K - 1) + " solved ion(s), " +
-                       path[mem] + " membrane path, " + (h->NV == 8 ? "hexahedra" : (h->gdim == 2 ? "triangles" : "tetrahedra")));
+                       path[mem] + " membrane path, " + kn_cell_kind_name(h->cell_kind));
   }
   return rc ? rc : kn_launch_check(name);
 }
@@ -1434,15 +1629,17 @@ int launch_rows(knpemi_handle* h, int system, const KnRowShape& s, int mem, Pick
 KnRowShape kn_rows_shape(const knpemi_handle* h, int system) {
   const bool knp = system == KN_ROWS_KNP;
   const size_t S = knp ? h->K - 1 : 1;   // fields a row block solves for: accumulators, and values per staged record
-  const bool lattice_tets = h->NV != 8 && h->gdim == 3 && h->tet_uniform && h->dev.tet_tab;
+  const bool hexa = h->cell_kind == KNPEMI_HEXAHEDRON, quad = h->cell_kind == KNPEMI_QUADRILATERAL;
+  const bool lattice_tets = h->cell_kind == KNPEMI_TETRAHEDRON && h->tet_uniform && h->dev.tet_tab;
   KnRowShape s;
   s.acc_n = ((knp ? h->lds_doubles_knp : h->lds_doubles_emi) + 1) & ~1;
   s.rec_n = h->lds_uniq_max;
   s.gam_n = knp && h->fuse_membrane ? std::max(1, h->lds_gam_max) : 0;
-  s.geo = h->NV == 8 ? (h->hex_uniform ? 2 : (h->hex_affine ? 1 : 0)) : (lattice_tets ? 2 : 0);
-  // accumulators | staged records (without coordinates where the cells are a lattice's) and a double of padding | the shape
-  // table of the lattice tetrahedra | fused membrane integrals | the entries' 16-bit locations
-  s.lds = (S * s.acc_n + (s.geo == 2 ? S + 1 : 4 + S) * (size_t)s.rec_n + 1 + (lattice_tets ? KN_TET_TAB : 0) +
+  s.geo = hexa ? (h->hex_uniform ? 2 : (h->hex_affine ? 1 : 0)) : (quad ? (h->hex_affine ? 1 : 0) : (lattice_tets ? 2 : 0));
+  // accumulators | staged records (without coordinates where the cells are a lattice's, with two on quadrilaterals) and a
+  // double of padding | the shape table of the lattice tetrahedra | fused membrane integrals | the entries' 16-bit locations
+  const size_t rec_w = s.geo == 2 ? S + 1 : (quad ? 3 + S : 4 + S);
+  s.lds = (S * s.acc_n + rec_w * (size_t)s.rec_n + 1 + (lattice_tets ? KN_TET_TAB : 0) +
            S * s.gam_n) * sizeof(double) + 2 * (size_t)h->lds_doubles_knp + 16;
   return s;
 }
@@ -1452,19 +1649,22 @@ int kn_launch_emi_rows(knpemi_handle* h, int flags) {
   const int want_p = (flags & KNPEMI_WANT_P) ? 1 : 0;
   const int split = ((flags & KNPEMI_NO_SPLITTING) ? 0 : 1) | ((flags & KNPEMI_SKIP_MEMBRANE_RHS) ? 2 : 0);
   const KnRowShape s = kn_rows_shape(h, KN_ROWS_EMI);
-  // vertices per cell (3, 4: simplices of dimension NV - 1, 8: hexahedra) x lanes per row x geometry variant
+  // cell kind (simplices of dimension NV - 1, hexahedra, quadrilaterals) x lanes per row x geometry variant
   const int rc = launch_rows(h, KN_ROWS_EMI, s, 0, [&](auto go) {
-    kn_pick<3, 4, 8>(h->NV, [&](auto nv) { kn_pick<1, 2, 4, 8>(h->lpr, [&](auto l) { kn_pick<0, 1, 2>(s.geo, [&](auto geo) {
-      constexpr int NV = decltype(nv)::value, L = decltype(l)::value, GEO = decltype(geo)::value;
-      if constexpr (NV == 8 && emi_rows_built(L))
+    kn_pick<KNPEMI_TRIANGLE, KNPEMI_TETRAHEDRON, KNPEMI_HEXAHEDRON, KNPEMI_QUADRILATERAL>(h->cell_kind, [&](auto kind) {
+      kn_pick<1, 2, 4, 8>(h->lpr, [&](auto l) { kn_pick<0, 1, 2>(s.geo, [&](auto geo) {
+      constexpr int KIND = decltype(kind)::value, NV = kind_nv(KIND), L = decltype(l)::value, GEO = decltype(geo)::value;
+      if constexpr (KIND == KNPEMI_HEXAHEDRON && emi_rows_built(L))
         go("emi_rows_hex_v2", RowKernel<emi_rows_hex_v2<L, GEO>>{}, s.acc_n, s.rec_n, want_p, split, h->hex_geo);
-      else if constexpr (NV != 8 && emi_rows_built(L) && simplex_geo_built(NV - 1, GEO))
+      else if constexpr (kind_simplex(KIND) && emi_rows_built(L) && simplex_geo_built(NV - 1, GEO))
         go("emi_rows_v2", RowKernel<emi_rows_v2<NV - 1, L, GEO == 2>>{}, s.acc_n, s.rec_n, want_p, split);
+      else if constexpr (KIND == KNPEMI_QUADRILATERAL && rows_quad_built(L, 0, 0, GEO))
+        go("emi_rows_quad_v2", RowKernel<emi_rows_quad_v2<L, GEO>>{}, s.acc_n, s.rec_n, want_p, split);
     }); }); });
   });
 #ifdef KN_ROW_STAMPS
   static int launches = 0;
-  if (h->NV != 8)
+  if (h->cell_kind == KNPEMI_TRIANGLE || h->cell_kind == KNPEMI_TETRAHEDRON)
     kn_stamps_report(&row_stamp_acc, 8, 5, 16, ++launches, h->dev.nblocks, "[row stamps]", "emi_rows_v2", "cycles", "workgroup");
 #endif
   return rc;
@@ -1477,14 +1677,17 @@ int kn_launch_knp_rows(knpemi_handle* h, int flags) {
   // the membrane integrals of b_knp: from knp_membrane_pre_kernel (2), evaluated in the row block (1), from gam_e (0)
   const int mem = (flags & KNPEMI_MEMBRANE_EARLY) ? 2 : (s.gam_n > 0 ? 1 : 0);
   return launch_rows(h, KN_ROWS_KNP, s, mem, [&](auto go) {
-    kn_pick<3, 4, 8>(h->NV, [&](auto nv) { kn_pick<1, 2, 4, 8>(h->lpr, [&](auto l) { kn_pick<0, 1, 2>(s.geo, [&](auto geo) {
+    kn_pick<KNPEMI_TRIANGLE, KNPEMI_TETRAHEDRON, KNPEMI_HEXAHEDRON, KNPEMI_QUADRILATERAL>(h->cell_kind, [&](auto kind) {
+      kn_pick<1, 2, 4, 8>(h->lpr, [&](auto l) { kn_pick<0, 1, 2>(s.geo, [&](auto geo) {
       kn_pick<1, 2, 3>(h->K - 1, [&](auto ks) { kn_pick<0, 1, 2>(mem, [&](auto m) {
-        constexpr int NV = decltype(nv)::value, L = decltype(l)::value, GEO = decltype(geo)::value;
+        constexpr int KIND = decltype(kind)::value, NV = kind_nv(KIND), L = decltype(l)::value, GEO = decltype(geo)::value;
         constexpr int KS = decltype(ks)::value, MEM = decltype(m)::value;
-        if constexpr (NV == 8 && knp_rows_hex_built(L, KS, MEM))
+        if constexpr (KIND == KNPEMI_HEXAHEDRON && knp_rows_hex_built(L, KS, MEM))
           go("knp_rows_hex_v2", RowKernel<knp_rows_hex_v2<L, GEO, KS, MEM>>{}, s.acc_n, s.rec_n, s.gam_n, split, h->hex_geo);
-        else if constexpr (NV != 8 && knp_rows_built(L, KS, MEM) && simplex_geo_built(NV - 1, GEO))
+        else if constexpr (kind_simplex(KIND) && knp_rows_built(L, KS, MEM) && simplex_geo_built(NV - 1, GEO))
           go("knp_rows_v2", RowKernel<knp_rows_v2<NV - 1, L, KS, MEM, GEO == 2>>{}, s.acc_n, s.rec_n, s.gam_n, split);
+        else if constexpr (KIND == KNPEMI_QUADRILATERAL && rows_quad_built(L, KS, MEM, GEO))
+          go("knp_rows_quad_v2", RowKernel<knp_rows_quad_v2<L, GEO, KS, MEM>>{}, s.acc_n, s.rec_n, s.gam_n, split);
       }); });
     }); }); });
   });

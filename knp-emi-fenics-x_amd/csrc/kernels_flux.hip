@@ -8,18 +8,19 @@
 //   c_k, g(u)   value and gradient, at the cell's centroid, of the P1 / Q1 interpolant of the nodal field
 //               (simplices: mean of the vertex values, constant gradient; hexahedra, tensor vertex order: mean of the
 //               eight values, reference derivative along t = 1/4 sum_v +-u_v with the sign from bit t of v, mapped by
-//               the Jacobian at the centre)
+//               the Jacobian at the centre; quadrilaterals, the same in 2-D: mean of the four values, reference
+//               derivative 1/2 sum_v +-u_v)
 //   J_diff  = -D_k^s g(c_k)
 //   J_drift = -z_k psi D_k^s c_k g(phi)          J = J_diff + J_drift
 //   i       = F sum_k z_k J_k, split the same way into i_diff and i_drift
-//   vol_T   = |det| / d! on simplices, |det J(centre)| on hexahedra (midpoint rule): the sign of det cancels, so
-//             left-handed cells give the same answer
+//   vol_T   = |det| / d! on simplices, |det J(centre)| on hexahedra and quadrilaterals (midpoint rule): the sign of det
+//             cancels, so left-handed cells give the same answer
 // from phi (slot 7) and c_prev / the eliminated ion's c (KN_CSLOT) as the records hold them: behind the end-of-step
 // update that is the new state.  The coordinates come from the same records, so lattice tetrahedra and uniform
 // hexahedra take no path of their own.
 //
-// Geometry, the same for the three cell kinds: with edge vectors E_t (simplices: x_t+1 - x_0; hexahedra: the columns
-// of the Jacobian at the centre) and the differences d_t of a field along them (u_t+1 - u_0; the reference
+// Geometry, the same for the four cell kinds: with edge vectors E_t (simplices: x_t+1 - x_0; hexahedra and
+// quadrilaterals: the columns of the Jacobian at the centre) and the differences d_t of a field along them (u_t+1 - u_0; the reference
 // derivatives), g = (sum_t d_t cof_t) / det, cof_0 = E_1 x E_2 and cyclic, det = E_0 . cof_0.  A hexahedron
 // accumulates the sum and the three signed face sums of all eight slots of the record as the records stream by (32
 // doubles); it never holds eight records.
@@ -69,8 +70,11 @@ struct FluxArgs {
 };
 
 template <int KIND> struct FluxCell {
-  static constexpr int GD = KIND == KNPEMI_TRIANGLE ? 2 : 3;
-  static constexpr int NV = KIND == KNPEMI_TRIANGLE ? 3 : KIND == KNPEMI_TETRAHEDRON ? 4 : 8;
+  static constexpr int GD = KIND == KNPEMI_TRIANGLE || KIND == KNPEMI_QUADRILATERAL ? 2 : 3;
+  static constexpr int NV = KIND == KNPEMI_TRIANGLE ? 3 : KIND == KNPEMI_HEXAHEDRON ? 8 : 4;
+  static constexpr bool TENSOR = KIND == KNPEMI_HEXAHEDRON || KIND == KNPEMI_QUADRILATERAL;
+  // |det| -> cell measure: 1 on the tensor cells (midpoint rule), 1 / d! on simplices
+  static constexpr double VOL = TENSOR ? 1.0 : (KIND == KNPEMI_TETRAHEDRON ? 1.0 / 6.0 : 0.5);
 };
 
 // the five fields of a record in the order phi, c_0 .. c_3 (KN_CSLOT)
@@ -98,7 +102,32 @@ __device__ inline void gather_cell(const int* __restrict__ cells, const double* 
       v[4 * i] = q.x; v[4 * i + 1] = q.y; v[4 * i + 2] = q.z; v[4 * i + 3] = q.w;
     }
   }
-  if constexpr (NV != 8) {
+  if constexpr (KIND == KNPEMI_QUADRILATERAL) {
+    double S[5] = {}, Dx[2][2] = {}, Du[5][2] = {};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const FluxRec r = load_record(VR, v[i]);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const bool up = (i >> t) & 1;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) Dx[t][a] += up ? r.x[a] : -r.x[a];
+#pragma unroll
+        for (int f = 0; f < 5; ++f) Du[f][t] += up ? r.u[f] : -r.u[f];
+      }
+#pragma unroll
+      for (int f = 0; f < 5; ++f) S[f] += r.u[f];
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a) E[t][a] = 0.5 * Dx[t][a];
+#pragma unroll
+      for (int f = 0; f < 5; ++f) d[f][t] = 0.5 * Du[f][t];
+    }
+#pragma unroll
+    for (int f = 0; f < 5; ++f) m[f] = 0.25 * S[f];
+  } else if constexpr (NV != 8) {
     const FluxRec r0 = load_record(VR, v[0]);
 #pragma unroll
     for (int f = 0; f < 5; ++f) m[f] = r0.u[f];
@@ -142,7 +171,7 @@ __device__ inline void gather_cell(const int* __restrict__ cells, const double* 
 
 template <int KIND, bool FIELDS, bool PART>
 __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
-  constexpr int GD = FluxCell<KIND>::GD, NV = FluxCell<KIND>::NV;
+  constexpr int GD = FluxCell<KIND>::GD;
   constexpr int PER_ION = 2 * GD + 1;
   __shared__ double sh[FLUX_WAVES][KN_FLUX_SLOTS];
   __shared__ int last;
@@ -183,7 +212,7 @@ __global__ __launch_bounds__(FLUX_THREADS) void flux_kernel(FluxArgs A) {
     det = E[0][0] * cof[0][0] + E[0][1] * cof[0][1] + E[0][2] * cof[0][2];
   }
   const double inv_det = 1.0 / det;
-  const double vol = rec ? fabs(det) * (NV == 8 ? 1.0 : NV == 4 ? 1.0 / 6.0 : 0.5) : 0.0;
+  const double vol = rec ? fabs(det) * FluxCell<KIND>::VOL : 0.0;
   auto grad = [&](int f, double (&g)[GD]) {
 #pragma unroll
     for (int a = 0; a < GD; ++a) {
@@ -299,7 +328,9 @@ int kn_launch_flux(knpemi_handle* h, int write_fields) {
   const bool fields = write_fields != 0;
   if (h->cell_kind == KNPEMI_TRIANGLE) launch<KNPEMI_TRIANGLE>(h, a, X.n_blk, fields);
   else if (h->cell_kind == KNPEMI_TETRAHEDRON) launch<KNPEMI_TETRAHEDRON>(h, a, X.n_blk, fields);
-  else launch<KNPEMI_HEXAHEDRON>(h, a, X.n_blk, fields);
+  else if (h->cell_kind == KNPEMI_HEXAHEDRON) launch<KNPEMI_HEXAHEDRON>(h, a, X.n_blk, fields);
+  else if (h->cell_kind == KNPEMI_QUADRILATERAL) launch<KNPEMI_QUADRILATERAL>(h, a, X.n_blk, fields);
+  else return kn_fail(KNPEMI_EINVAL, "flux_kernel: not built for this cell kind");
   return kn_launch_check("flux_kernel");
 }
 

@@ -65,8 +65,9 @@ int prepare_kernel(size_t dyn, bool* fits) {
 }  // namespace
 
 bool kn_sweep_emi_rows_ok(const knpemi_handle* h) {
-  // tetrahedra with four lanes per row (knpemi_create's choice for them), lattice and general
-  return h->NV == 4 && h->gdim == 3 && h->lpr == 4 && h->dev.nblocks > 0;
+  // tetrahedra with four lanes per row (knpemi_create's choice for them), lattice and general; by kind: a quadrilateral
+  // has four vertices too, and runs the two launches as triangles do
+  return h->cell_kind == KNPEMI_TETRAHEDRON && h->lpr == 4 && h->dev.nblocks > 0;
 }
 
 int kn_launch_sweep_emi(knpemi_handle* h, int model_id, const OdeDev& dv, const OdeArgs& a, const void* coef, int n_sweep,

@@ -89,8 +89,9 @@ static void kn_solver_attach(knpemi_handle* h) {
   for (KnAmg* G : {&sv.amg_emi, &sv.amg_knp}) {
     // stretched Q1 cells couple the two ends of an edge along the long direction positively: aggregate_apart keeps them
     // in different aggregates (config 2h: 9.35 / 3.95 -> 7.4 / 2.9 iterations per solve; on simplices the plain greedy
-    // pass is the better one, 5.3 / 2.35 against 5.75 / 2.6 at config 2)
-    G->cfg.positive_conflict = h->NV == 8;
+    // pass is the better one, 5.3 / 2.35 against 5.75 / 2.6 at config 2).  Quadrilaterals: no difference on square cells,
+    // 111 / 93 against 282 / 237 iterations over ten steps on 4 : 1 cells
+    G->cfg.positive_conflict = h->cell_kind == KNPEMI_HEXAHEDRON || h->cell_kind == KNPEMI_QUADRILATERAL;
     // prolongator smoothing along the large couplings only (KnAmgConfig::filter_theta): the operator complexity falls
     // from 2.5-2.8 to 1.5 on simplices, the iteration counts stay (995 k tets: 6.65 / 2.8 -> 6.75 / 2.85, 3.34 -> 2.37 ms
     // per step with solves).  "Large" is by magnitude: the big positive entries of stretched Q1 cells stay in the
@@ -120,6 +121,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   if (d->cell_kind == KNPEMI_TRIANGLE && d->gdim == 2) { NV = 3; NF = 2; }
   else if (d->cell_kind == KNPEMI_TETRAHEDRON && d->gdim == 3) { NV = 4; NF = 3; }
   else if (d->cell_kind == KNPEMI_HEXAHEDRON && d->gdim == 3) { NV = 8; NF = 4; }
+  else if (d->cell_kind == KNPEMI_QUADRILATERAL && d->gdim == 2) { NV = 4; NF = 2; }
   else return kn_fail(KNPEMI_EINVAL, "knpemi_create: cell_kind/gdim combination not supported");
 
   auto* h = new knpemi_handle();
@@ -134,6 +136,11 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   KN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   KN_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
   h->gdim = d->gdim; h->cell_kind = d->cell_kind; h->NV = NV; h->NF = NF;
+  // NV alone does not name the cell: 4 vertices are a tetrahedron or a quadrilateral.  What follows asks for the kind, or
+  // for "tensor cell" (Q1: pairs of cell + slot words, quadrature or closed forms) against "simplex" (P1: strip-ordered pairs)
+  const bool hexa = d->cell_kind == KNPEMI_HEXAHEDRON, quad = d->cell_kind == KNPEMI_QUADRILATERAL;
+  const bool tri = d->cell_kind == KNPEMI_TRIANGLE, tet = d->cell_kind == KNPEMI_TETRAHEDRON;
+  const bool tensor = hexa || quad;
   h->n_sub = d->n_sub; h->K = d->n_ions;
   const int S = d->n_sub, K = d->n_ions;
   h->n_vert.assign(d->n_vert, d->n_vert + S);
@@ -173,12 +180,19 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   // Any of the 48 such orders of a cell is taken, left-handed ones included; the trilinear map of a cell given in another
   // order (e.g. the counter-clockwise order of other formats) folds over, i.e. its Jacobian determinant changes sign
   // between the corners (kn_hex_tensor_order, the test of knpemi_dg_create too)
-  if (NV == 8)
+  if (hexa)
     for (int s = 0; s < S; ++s)
       for (int c = h->coff[s]; c < h->coff[s + 1]; ++c)
         if (!kn_hex_tensor_order(VR.data(), KN_REC, &cells[(size_t)c * 8]))
           return kn_fail(KNPEMI_EINVAL, "knpemi_create: hexahedron " + std::to_string(c - h->coff[s]) + " of sub-domain " +
                                             std::to_string(s) + " is degenerate or not in tensor-product vertex order");
+  // quadrilaterals: the same rule in 2-D, any of the 8 orders [v00, v10, v01, v11] of a cell (kn_quad_tensor_order)
+  if (quad)
+    for (int s = 0; s < S; ++s)
+      for (int c = h->coff[s]; c < h->coff[s + 1]; ++c)
+        if (!kn_quad_tensor_order(VR.data(), KN_REC, &cells[(size_t)c * 4]))
+          return kn_fail(KNPEMI_EINVAL, "knpemi_create: quadrilateral " + std::to_string(c - h->coff[s]) + " of sub-domain " +
+                                            std::to_string(s) + " is degenerate, not convex or not in tensor-product vertex order");
 
   // ---- vertex -> cell adjacency (counting sort) ---------------------------------------------------
   std::vector<int64_t> v2c_ptr(Ntot + 1, 0);
@@ -194,7 +208,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   // ---- Laplacian pattern -------------------------------------------------------------------------
   std::vector<int>& rowptrL = h->h_rowptrL; std::vector<int>& colindL = h->h_colindL;
   rowptrL.assign(Ntot + 1, 0);
-  colindL.reserve((size_t)Ntot * (NV == 8 ? 27 : (NV == 4 ? 15 : 7)));
+  colindL.reserve((size_t)Ntot * (hexa ? 27 : (tet ? 15 : (quad ? 9 : 7))));
   {
     std::vector<int> tmp;
     for (int g = 0; g < Ntot; ++g) {
@@ -274,7 +288,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   }
 
   // ---- hexahedra: is every cell a parallelepiped? (constant Jacobian -> specialised row kernels) -----
-  if (NV == 8) {
+  if (hexa) {
     bool affine = true;
     for (size_t c = 0; c < (size_t)nctot && affine; ++c) {
       const int* cv = &cells[c * 8];
@@ -346,9 +360,28 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
     }
   }
 
+  // ---- quadrilaterals: is every cell a parallelogram?  The same relative test on the two pairs of opposite edges.  There
+  // is no uniform-cell variant: uniform_cell is not looked at, hex_uniform stays false.
+  if (quad) {
+    bool affine = true;
+    for (size_t c = 0; c < (size_t)nctot && affine; ++c) {
+      const int* cv = &cells[c * 4];
+      double dev = 0.0, len = 0.0;
+      for (int t = 0; t < 2; ++t)
+        for (int a = 0; a < 2; ++a) {
+          const double e0 = VR[(size_t)cv[1 << t] * KN_REC + a] - VR[(size_t)cv[0] * KN_REC + a];
+          const double e1 = VR[(size_t)cv[3] * KN_REC + a] - VR[(size_t)cv[3 ^ (1 << t)] * KN_REC + a];
+          len += std::fabs(e0);
+          dev += std::fabs(e1 - e0);
+        }
+      affine = dev <= 1e-13 * len;
+    }
+    h->hex_affine = affine && getenv("KNPEMI_QUAD_GENERAL") == nullptr;
+  }
+
   // ---- static ICS mass of the preconditioner: P_emi = A_emi + int u v dx on the cell sub-domains ---------
   // (emiWeakForm.py:169-198).  The geometry never changes, so the mass entries are tabulated once (P1: closed
-  // form; Q1: the 2x2x2 Gauss rule) in the layout of the cell-side CSR rows and added when P is written.
+  // form; Q1: the 2x2x2 Gauss rule, 2x2 on quadrilaterals) in the layout of the cell-side CSR rows and added when P is written.
   const int64_t pmass0 = rowptr[h->voff[1]];
   std::vector<double> pmass((size_t)(rowptr[Ntot] - pmass0), 0.0);
   for (int sdm = 1; sdm < S; ++sdm)
@@ -358,9 +391,9 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
       for (int a = 0; a < NV; ++a)
         for (int t = 0; t < d->gdim; ++t) X[a][t] = VR[(size_t)cv[a] * KN_REC + t];
       double Me[8][8] = {};
-      if (NV == 3 || NV == 4) {
+      if (tri || tet) {
         double det;
-        if (NV == 3) {
+        if (tri) {
           det = (X[1][0] - X[0][0]) * (X[2][1] - X[0][1]) - (X[1][1] - X[0][1]) * (X[2][0] - X[0][0]);
         } else {
           const double ax = X[1][0] - X[0][0], ay = X[1][1] - X[0][1], az = X[1][2] - X[0][2];
@@ -368,9 +401,30 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
           const double cx = X[3][0] - X[0][0], cy = X[3][1] - X[0][1], cz = X[3][2] - X[0][2];
           det = ax * (by * cz - bz * cy) + ay * (bz * cx - bx * cz) + az * (bx * cy - by * cx);
         }
-        const double vol = std::fabs(det) / (NV == 3 ? 2.0 : 6.0), m = vol / ((d->gdim + 1) * (d->gdim + 2));
+        const double vol = std::fabs(det) / (tri ? 2.0 : 6.0), m = vol / ((d->gdim + 1) * (d->gdim + 2));
         for (int i = 0; i < NV; ++i)
           for (int j = 0; j < NV; ++j) Me[i][j] = i == j ? 2.0 * m : m;
+      } else if (quad) {
+        const double g0 = 0.5 - 0.28867513459481287, g1 = 0.5 + 0.28867513459481287;
+        for (int q = 0; q < 4; ++q) {
+          double N[4], J[2][2] = {};
+          for (int v = 0; v < 4; ++v) {
+            double f[2], df[2];
+            for (int ax = 0; ax < 2; ++ax) {
+              const double xq = ((q >> ax) & 1) ? g1 : g0;
+              const bool hi = (v >> ax) & 1;
+              f[ax] = hi ? xq : 1.0 - xq;
+              df[ax] = hi ? 1.0 : -1.0;
+            }
+            N[v] = f[0] * f[1];
+            const double dN[2] = {df[0] * f[1], f[0] * df[1]};
+            for (int a = 0; a < 2; ++a)
+              for (int t = 0; t < 2; ++t) J[a][t] += X[v][a] * dN[t];
+          }
+          const double wd = 0.25 * std::fabs(J[0][0] * J[1][1] - J[0][1] * J[1][0]);
+          for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) Me[i][j] += wd * N[i] * N[j];
+        }
       } else {
         const double g0 = 0.5 - 0.28867513459481287, g1 = 0.5 + 0.28867513459481287;
         for (int q = 0; q < 8; ++q) {
@@ -408,7 +462,9 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   {
     // simplices (v2 kernels stage 48 B per Laplacian entry in LDS): 64-row blocks for tetrahedra,
     // 128-row blocks for triangles; hexahedra: enough workgroups to fill the chip on small meshes
-    int lpr = NV == 3 ? 2 : 4;   // hexahedra: 8 heavy pairs per row, two per lane
+    // quadrilaterals: 4 incident cells and 9 entries per row of a structured mesh; 2 lanes (128-row blocks, as for
+    // triangles) against 4: DESIGN.md section 3.1
+    int lpr = (tri || quad) ? 2 : 4;   // hexahedra: 8 heavy pairs per row, two per lane
     if (const char* env = getenv("KNPEMI_LPR")) {
       int v = atoi(env);
       if (v == 1 || v == 2 || v == 4 || v == 8) lpr = v;
@@ -422,7 +478,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   // greedily by the number of Laplacian entries that connect them, so that the rows of a block share neighbours: on
   // the x-fastest numbering of the box meshes 64 consecutive rows are a line of vertices that touches 456 distinct
   // vertices, a bundle of pieces of neighbouring lines 230-270.  KNPEMI_BLOCK_CLASSIC=1: consecutive chunks.
-  const int CH = NV == 8 ? KN_CHUNK_HEX : KN_CHUNK_SIMPLEX, NR = RPB / CH;
+  const int CH = hexa ? KN_CHUNK_HEX : KN_CHUNK_SIMPLEX, NR = RPB / CH;   // quadrilaterals: the chunks of the triangles
   struct Chunk { int start, len, sub; };
   std::vector<Chunk> chunks;
   std::vector<int> chunk_of(Ntot, -1);
@@ -524,7 +580,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   };
   for (int b = 0; b < nblocks; ++b) blk_sub[b] = chunks[blocks[b][0]].sub;
   const int SPB = KN_BLOCK / KN_SLICE;  // slices (wavefronts) per block
-  const int SW = NV == 8 ? 2 : 1;
+  const int SW = hexa ? 2 : 1;   // slot words of a tensor cell's pair: 8 one-byte slots, or the 4 of a quadrilateral
   std::vector<int64_t> sl_ptr((size_t)nblocks * SPB + 1, 0);
   for (int b = 0; b < nblocks; ++b)
     for (int w = 0; w < SPB; ++w) {
@@ -535,7 +591,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
       }
       sl_ptr[(size_t)b * SPB + w + 1] = sl_ptr[(size_t)b * SPB + w] + mx * KN_SLICE;
     }
-  const bool simplex = NV != 8;
+  const bool simplex = !tensor;
   // ---- tetrahedra: is every cell a lattice tetrahedron of a uniform grid? ------------------------------------------
   // (the box meshes of the reference's 3-D driver split into tetrahedra, knpemi_problem_desc::uniform_cell: the vertices of a
   // cell are corners of ONE grid cell.)  Then a cell is one of a handful of shapes -- six for the Kuhn split -- whose gradient
@@ -544,7 +600,7 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   // the canonical number of each vertex (its rank among the cell's corner codes, 2 bits), which leaves 5 bits per slot.
   std::vector<uint8_t> tet_shape, tet_canon;      // per cell: shape; canonical numbers of the four vertices, 2 bits each
   std::vector<double> tet_tab;
-  if (NV == 4 && d->gdim == 3 && nctot > 0 && getenv("KNPEMI_TET_NOT_UNIFORM") == nullptr) {
+  if (tet && nctot > 0 && getenv("KNPEMI_TET_NOT_UNIFORM") == nullptr) {
     bool ok = false;
     for (int i = 0; i < 9; ++i) ok |= d->uniform_cell[i] != 0.0;
     int longest = 0;

@@ -82,8 +82,8 @@ struct KnDev {
                               // 5-6 of bytes 1-3 the canonical vertex number of the vertex in that byte
   const double* tet_tab;      // lattice tetrahedra of a uniform grid (knpemi_create): [8 shapes][4][4] gradient dot
                               // products of the canonical vertices, then [8] cell volumes; NULL otherwise
-  const int* pair_cell;       // hexahedra: cell*8 + local index, -1 = padding
-  const uint32_t* pair_slots; // hexahedra: 8 x uint8 slots in two consecutive words per entry
+  const int* pair_cell;       // hexahedra, quadrilaterals: cell*8 + local index, -1 = padding
+  const uint32_t* pair_slots; // hexahedra: 8 x uint8 slots in two consecutive words per entry; quadrilaterals: 4 in one word
   // EMI CSR (monolithic) and Laplacian-pattern CSR (KNP blocks share it per sub-domain)
   const int* rowptr; const int* colind; const uint8_t* lapoff;
   const int* rowptrL; const int* colindL;
@@ -686,6 +686,26 @@ inline bool kn_hex_tensor_order(const double* x, int x_stride, const int* cell8)
   return pos == 8 || neg == 8;
 }
 
+// The same for Q1 quadrilaterals, vertex v at x[v * x_stride .. + 1]: one of the 8 tensor orders, and the bilinear map does
+// not fold -- the Jacobian determinant at the four corners has one sign.  A cell in counter-clockwise order, a non-convex
+// and a degenerate one fail.
+inline bool kn_quad_tensor_order(const double* x, int x_stride, const int* cell4) {
+  int pos = 0, neg = 0;
+  for (int j = 0; j < 4; ++j) {
+    double e[2][2];
+    for (int a = 0; a < 2; ++a) {
+      const double* x0 = x + (size_t)cell4[j] * x_stride;
+      const double* x1 = x + (size_t)cell4[j ^ (1 << a)] * x_stride;
+      const double sgn = ((j >> a) & 1) ? -1.0 : 1.0;
+      for (int k = 0; k < 2; ++k) e[a][k] = sgn * (x1[k] - x0[k]);
+    }
+    const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+    pos += det > 0.0;
+    neg += det < 0.0;
+  }
+  return pos == 4 || neg == 4;
+}
+
 struct knpemi_handle : KnDevice {
   hipStream_t aux = nullptr;             // auxiliary stream (EMI matrix assembly beside the ODE sweep)
   hipStream_t aux2 = nullptr;            // second auxiliary stream (ODE sweeps of further membrane models)
@@ -702,7 +722,7 @@ struct knpemi_handle : KnDevice {
   KnDev dev{};
   int have_params = 0;
   int lpr = 1;                         // lanes per row of the row kernels (1, 2, 4 or 8)
-  bool hex_affine = false;             // every hexahedron is a parallelepiped (constant Jacobian)
+  bool hex_affine = false;             // every hexahedron is a parallelepiped / every quadrilateral a parallelogram (constant Jacobian)
   bool tet_uniform = false;            // tetrahedra: every cell a lattice tetrahedron of a uniform grid (dev.tet_tab)
   bool hex_uniform = false;            // ... and all of them are the same one: the geometry below is a constant of the mesh
   KnHexGeo hex_geo{};
@@ -891,11 +911,12 @@ void kn_record_free(knpemi_handle* h);    // every recorder's device memory (knp
 
 // kernel launchers (kernels_*.hip) ------------------------------------------------------------
 int kn_launch_emi_rows(knpemi_handle* h, int flags);
-// Launch shape of a row block, of either system (KN_ROWS_EMI, KN_ROWS_KNP) on simplices and hexahedra: accumulator
-// doubles per solved field, staged records, fused membrane integrals (KNP with KNPEMI_OPT_FUSE_MEMBRANE, else 0), the
-// geometry variant -- 2: lattice cells (tetrahedra or boxes of a uniform grid: records without coordinates), 1: affine
-// hexahedra, 0: general -- and the dynamic LDS bytes.  One rule for the four row kernels and for the row blocks of the fused
-// launch (kernels_sweep_emi.hip).
+// Launch shape of a row block, of either system (KN_ROWS_EMI, KN_ROWS_KNP) on simplices, hexahedra and quadrilaterals:
+// accumulator doubles per solved field, staged records, fused membrane integrals (KNP with KNPEMI_OPT_FUSE_MEMBRANE, else 0),
+// the geometry variant -- 2: lattice cells (tetrahedra or boxes of a uniform grid: records without coordinates), 1: affine
+// hexahedra / quadrilaterals, 0: general -- and the dynamic LDS bytes (records of gdim coordinates and the S fields, or the
+// S + 1 values of the lattice cells).  One rule for the six row kernels and for the row blocks of the fused launch
+// (kernels_sweep_emi.hip).
 enum { KN_ROWS_EMI = 0, KN_ROWS_KNP = 1 };
 struct KnRowShape { int acc_n = 0, rec_n = 0, gam_n = 0, geo = 0; size_t lds = 0; };
 KnRowShape kn_rows_shape(const knpemi_handle* h, int system);

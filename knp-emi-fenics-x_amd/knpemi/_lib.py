@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("KNPEMI_HIP_LIB") or os.path.join(_HERE, "libknpemi_hi
 
 OK, EINVAL, EHIP, ENOMEM, EODE, ESOLVE, EBUSY = 0, -1, -2, -3, -4, -5, -6
 PC_JACOBI, PC_AMG = 0, 1
-TRIANGLE, TETRAHEDRON, HEXAHEDRON = 0, 1, 2
+TRIANGLE, TETRAHEDRON, HEXAHEDRON, QUADRILATERAL = 0, 1, 2, 3
 MODEL_HH_SI, MODEL_HH_MV, MODEL_GLIAL = 0, 1, 2
 MAX_IONS, MAX_SUB, MAX_MODELS = 4, 8, 4
 F_PHI, F_C, F_C_PREV, F_C_ELIM, F_PHI_M, F_I_CH, F_SOURCE, F_ODE_STATE = range(8)

@@ -30,7 +30,8 @@ except ImportError:                     # pragma: no cover -- zlib is always the
         return (zlib.crc32(m) << 32) | zlib.adler32(m)
 from .fem.function import as_float
 
-_CELL_KIND = {"triangle": L.TRIANGLE, "tetrahedron": L.TETRAHEDRON, "hexahedron": L.HEXAHEDRON}
+_CELL_KIND = {"triangle": L.TRIANGLE, "tetrahedron": L.TETRAHEDRON, "hexahedron": L.HEXAHEDRON,
+              "quadrilateral": L.QUADRILATERAL}
 _MODEL_IDS = {"hh_si": L.MODEL_HH_SI, "hh_mv": L.MODEL_HH_MV, "glial": L.MODEL_GLIAL}
 
 

@@ -44,12 +44,15 @@ def _tag(mesh, interior_boxes, interior_tags, full_facet_tags=True):
     return ct, ft
 
 
-def make_mesh_2D(resolution_factor, comm=None):
+def make_mesh_2D(resolution_factor, comm=None, cell_type=CellType.triangle):
     """62 x 4 um rectangle, ICS = [1,61] x [1,3] um, triangles
-    (`make_mesh_2D.py:21-22,45-55`).  r = 0 has an empty ICS."""
+    (`make_mesh_2D.py:21-22,45-55`).  r = 0 has an empty ICS.
+    `cell_type="quadrilateral"`: the same rectangle, tags and membrane on 31 2^r x 2 2^r squares (one keyword of
+    `dolfinx.mesh.create_rectangle`)."""
     n = (31 * 2 ** resolution_factor, 2 * 2 ** resolution_factor)
-    mesh = create_rectangle(comm, [np.array([0.0, 0.0]), np.array([62.0e-6, 4.0e-6])], n,
-                            CellType.triangle)
+    if cell_type not in (CellType.triangle, CellType.quadrilateral):
+        raise ValueError(f"make_mesh_2D: triangle or quadrilateral cells, not {cell_type!r}")
+    mesh = create_rectangle(comm, [np.array([0.0, 0.0]), np.array([62.0e-6, 4.0e-6])], n, cell_type)
     ct, ft = _tag(mesh, [([1e-6, 1e-6], [61e-6, 3e-6])], [1])
     return mesh, ct, ft
 

@@ -15,16 +15,19 @@ integrals and maxima to a time series; the host reads either only when asked.
     ser = fl.series()                                 # "t", "0/K/diffusive" (n, gdim), "0/K/drift", "0/K/max", "0/current", ...
     f = fl.fields(0)                                  # "K/diffusive" (n_cell, gdim), ..., "current"
 
-Definitions, the same for triangles, tetrahedra and hexahedra.  For a cell T of sub-domain s and every ion
+Definitions, the same for triangles, tetrahedra, hexahedra and quadrilaterals.  For a cell T of sub-domain s and every ion
 k = 0 .. K-1, the eliminated one included:
 
   * c_k and g(u) are the value and the gradient, at the cell's centroid, of the P1 / Q1 interpolant of the nodal
     field.  Simplices: c_k is the mean of the vertex values and g the constant gradient.  Hexahedra (tensor vertex
     order, x[1 << t]): c_k is the mean of the eight values; the reference derivative along t is 1/4 sum_v +-u_v with
-    the sign taken from bit t of v, mapped by the Jacobian at the centre.
+    the sign taken from bit t of v, mapped by the Jacobian at the centre.  Quadrilaterals (tensor vertex order
+    [v00, v10, v01, v11]) are the same rule in 2-D: c_k is the mean of the four values, E_t = 1/2 sum_v +-x_v is
+    column t of the Jacobian at the centre, d_t = 1/2 sum_v +-u_v, and the gradient solves E g = d.
   * J_diff = -D_k^s g(c_k),  J_drift = -z_k psi D_k^s c_k g(phi),  J = J_diff + J_drift.
   * Current density i = F sum_k z_k J_k, split the same way into i_diff and i_drift.
-  * vol_T = |det| / d! on simplices and |det J(centre)| on hexahedra (the midpoint rule).  The orientation of a cell
+  * vol_T = |det| / d! on simplices and |det J(centre)| = |det E| on hexahedra and
+    quadrilaterals (the midpoint rule).  The orientation of a cell
     does not matter: left-handed cells give the same answer.
   * The fields are phi, c_prev of the solved ions and the eliminated ion's c as the device holds them: at the end of a
     step that is the new state.
@@ -60,13 +63,22 @@ def fold_depth():
     return lib_int("kn_flux_fold_depth")
 
 
+_TENSOR_DIM = {"hexahedron": 3, "quadrilateral": 2}
+
+
+def _tensor_signs(dim):
+    """sign[t, v] = +1 where bit t of local vertex v is set, and the weight 2 / 2^dim of a reference derivative."""
+    sign = np.array([[1.0 if (v >> t) & 1 else -1.0 for v in range(1 << dim)] for t in range(dim)])
+    return sign, 2.0 / (1 << dim)
+
+
 def cell_geometry(x, cells, cell_type):
-    """(E, vol) of every cell: E[c, t] is edge vector t (simplices: x_(t+1) - x_0; hexahedra: column t of the Jacobian at
-    the centre, 1/4 sum_v +-x_v), vol the cell's measure by the module docstring's rule."""
+    """(E, vol) of every cell: E[c, t] is edge vector t (simplices: x_(t+1) - x_0; hexahedra and quadrilaterals: column
+    t of the Jacobian at the centre, 1/4 resp. 1/2 sum_v +-x_v), vol the cell's measure by the module docstring's rule."""
     xc = x[cells]
-    if cell_type == "hexahedron":
-        sign = np.array([[1.0 if (v >> t) & 1 else -1.0 for v in range(8)] for t in range(3)])
-        E = 0.25 * np.einsum("tv,cva->cta", sign, xc)
+    if cell_type in _TENSOR_DIM:
+        sign, w = _tensor_signs(_TENSOR_DIM[cell_type])
+        E = w * np.einsum("tv,cva->cta", sign, xc)
         return E, np.abs(np.linalg.det(E))
     d = cells.shape[1] - 1
     E = xc[:, 1:] - xc[:, :1]
@@ -77,9 +89,9 @@ def cell_value_and_gradient(E, cells, cell_type, u):
     """(value, gradient) at the centroids of the interpolant of the nodal field u: the gradient solves E g = d with d
     the field's differences along the edge vectors."""
     uc = u[cells]
-    if cell_type == "hexahedron":
-        sign = np.array([[1.0 if (v >> t) & 1 else -1.0 for v in range(8)] for t in range(3)])
-        d = 0.25 * uc @ sign.T
+    if cell_type in _TENSOR_DIM:
+        sign, w = _tensor_signs(_TENSOR_DIM[cell_type])
+        d = w * uc @ sign.T
     else:
         d = uc[:, 1:] - uc[:, :1]
     return uc.mean(axis=1), np.linalg.solve(E, d[:, :, None])[:, :, 0]
