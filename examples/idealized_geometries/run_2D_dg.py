@@ -4,7 +4,12 @@ membrane ODEs at the facet nodes, both assemblies, both linear solves (CG / BiCG
 `knpemi_dg_solve_emi/knp`) and the end-of-step update on the GPU; `--host-solves` solves the two systems with SciPy
 from the CSR the kernels fill instead.
 
-    python run_2D_dg.py [--resolution 1] [--steps 100] [--host-solves]
+    python run_2D_dg.py [--resolution 1] [--steps 100] [--host-solves] [--series s.npz] [--events e.npz]
+
+`--series` records on the device, at the end of every step, phi and the ions at the ECS and ICS points of run_2D.py's
+`--series`, phi_M and the traces at its membrane point, the maximum and the average of K in the ECS and the jump seminorms
+of phi and of K in both sub-domains (`knpemi.dg_recording.DGObservables`); `--events` the upward crossings of -20 mV per
+membrane node (`DGMembraneEvents`, re-armed 20 mV below, the latest 8 times kept).
 
 `--cell-type quadrilateral` is parsed, as in run_2D.py, and refused with the DG module's message: the DG variant has no
 quadrilateral kernels.
@@ -25,6 +30,7 @@ import mm_hh                                                       # noqa: E402
 from setup_problem import (C_M, CL_E, CL_I, D_CL, D_K, D_NA, DT, FARADAY, K_E, K_I, NA_E, NA_I, PSI)  # noqa: E402
 from knpemi import _lib as L                                       # noqa: E402
 from knpemi.dg import DGProblem                                    # noqa: E402
+from knpemi.dg_recording import DGMembraneEvents, DGObservables    # noqa: E402
 from knpemi.fem.idealized import make_mesh_2D                      # noqa: E402
 
 
@@ -36,9 +42,16 @@ def solve_singular(A, b):
     return spla.splu(K).solve(np.concatenate([b, [0.0]]))[:n]
 
 
+FIGURE_POINTS = dict(ECS=(25e-6, 3.5e-6), ICS=(25e-6, 2e-6), mem=(25e-6, 3e-6))      # run_2D.py: FIGURE_POINTS[2], in m
+EVENT_THRESHOLD = -20e-3                                           # run_2D.py: --event-threshold
+
+
 class DGRun:
-    def __init__(self, resolution=1, g_syn=10.0, dt=DT, device_solves=True, rtol=(1e-5, 1e-7), cell_type="triangle"):
+    def __init__(self, resolution=1, g_syn=10.0, dt=DT, device_solves=True, rtol=(1e-5, 1e-7), cell_type="triangle",
+                 series=None, events=None):
+        """series / events: paths of the .npz files `save` writes (None: not recorded)."""
         self.device_solves, self.rtol, self.iterations = device_solves, rtol, []
+        self.series, self.events, self.obs, self.ev = series, events, None, None
         mesh, ct, ft = make_mesh_2D(resolution, cell_type=cell_type)      # quadrilaterals: DGProblem refuses them
         self.dp = dp = DGProblem(mesh, ct, ft, [0, 1], [1])
         self.ions = [dict(name="K", z=1.0, D=[D_K] * 2), dict(name="Cl", z=-1.0, D=[D_CL] * 2), dict(name="Na", z=1.0, D=[D_NA] * 2)]
@@ -63,6 +76,21 @@ class DGRun:
         if device_solves:
             dp.set_extrapolation(True)
         self.dt, self.time, self.k = dt, 0.0, 0
+        if series:
+            self.obs = obs = DGObservables(mesh, ct, ft, [0, 1], [1], [i["name"] for i in self.ions])
+            obs.point("ECS", FIGURE_POINTS["ECS"], tag=0)
+            obs.point("ICS", FIGURE_POINTS["ICS"], tag=1)
+            obs.membrane_point("mem", FIGURE_POINTS["mem"], 1)
+            obs.reduce("K_ecs_max", "c", 0, "max", ion="K")
+            obs.reduce("K_ecs_avg", "c", 0, "average", ion="K")
+            for tag, side in ((0, "ecs"), (1, "ics")):
+                obs.jump(f"J_phi_{side}", "phi", tag)
+                obs.jump(f"J_K_{side}", "c", tag, ion="K")
+            dp.observe(obs)
+        if events:
+            self.ev = ev = DGMembraneEvents(mesh, ft, [1])
+            ev.watch(EVENT_THRESHOLD, reset=EVENT_THRESHOLD - 20e-3, keep=8)
+            dp.detect(ev)
 
     def step(self):
         dp = self.dp
@@ -83,6 +111,13 @@ class DGRun:
         assert n_failed == 0                                         # odeSolver.py:121
         self.time += self.dt
         self.k += 1
+        dp.record(self.time)
+
+    def save(self):
+        if self.obs is not None:
+            self.obs.save(self.series)
+        if self.ev is not None:
+            self.ev.save(self.events)
 
 
 def build_parser():
@@ -91,15 +126,18 @@ def build_parser():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--host-solves", action="store_true")
     ap.add_argument("--cell-type", choices=["triangle", "quadrilateral"], default="triangle")
+    ap.add_argument("--series", metavar="PATH", default=None, help="time series of the observables and jump seminorms (.npz)")
+    ap.add_argument("--events", metavar="PATH", default=None, help="membrane events per membrane node (.npz)")
     return ap
 
 
 if __name__ == "__main__":
     a = build_parser().parse_args()
-    run = DGRun(a.resolution, device_solves=not a.host_solves, cell_type=a.cell_type)
+    run = DGRun(a.resolution, device_solves=not a.host_solves, cell_type=a.cell_type, series=a.series, events=a.events)
     for k in range(a.steps):
         run.step()
         if (k + 1) % 10 == 0:
             v = run.dp.get_membrane_potential()
             its = f"   iterations {run.iterations[-1]}" if run.iterations else ""
             print(f"t = {run.time * 1e3:5.1f} ms   phi_M: mean {v.mean() * 1e3:8.3f} mV, max {v.max() * 1e3:8.3f} mV{its}")
+    run.save()

@@ -1089,6 +1089,54 @@ int knpemi_dg_profile_read(knpemi_dg* h, int which, int64_t* launches, double* t
 /* HIP stream the handle enqueues on */
 void* knpemi_dg_stream(knpemi_dg* h);
 
+/* Observables of a DG run (knpemi.dg_recording.DGObservables): linear functionals and min / max reductions of the broken
+ * fields, and the jump seminorms the interior penalty controls, recorded on the device into a time-series buffer.  The
+ * table, the kernel, the buffer and the capacity / dropped-row / reset semantics are those of knpemi_observe_set ..
+ * knpemi_observe_clear; what differs is where a field lives.  Observable o reads the field spec[4o + 0]:
+ *   KNPEMI_DG_C with ion index spec[4o + 2] < K (the eliminated ion last; valid after knpemi_dg_update), KNPEMI_DG_PHI:
+ *     indices are broken dofs c * nv + j;
+ *   KNPEMI_DG_PHI_M: indices are membrane nodes f * nf + a;
+ *   KNPEMI_DG_JUMP: the jump seminorm of sub-domain spec[4o + 1] and of the concentration of ion spec[4o + 2] < K, or of the
+ *     potential with spec[4o + 2] == -1,
+ *         J_s(u) = sum over the interior facets F with both cells in s of  int_F (1 / h_F) [u]^2 dS,
+ *     1 / h_F the penalty weight of the assembly (simplices: the mean of the two cells' |grad lambda_opposite|; hexahedra:
+ *     point by point on the 2 x 2 Gauss rule the mean of the two cells' |grad xi_normal|).  Every facet counts once,
+ *     membrane and boundary facets never; a sub-domain without interior facets gives 0.  One KNPEMI_OBS_SUM entry with index
+ *     0 whose weight scales the value; no square root is taken.
+ * spec[4o + 1] is read for KNPEMI_DG_JUMP only.  Validated on the host: every index in range, every weight and
+ * denominator finite, every op known -- anything else is KNPEMI_EINVAL by name, and the previous table keeps recording. */
+#define KNPEMI_DG_JUMP 5
+int knpemi_dg_observe_set(knpemi_dg* h, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
+                          const double* w, const double* denom, int capacity);
+/* Enqueue the evaluation of every observable as one row on the handle's stream, behind whatever knpemi_dg_update and the
+ * membrane sweep have enqueued: dg_jump_kernel first when a jump seminorm is defined (one launch, every sub-domain and all
+ * K + 1 fields), then the observe launch.  Sums are formed in a fixed order: two identical runs give bit-identical rows.
+ * Nothing is synchronised.  KNPEMI_EINVAL before knpemi_dg_observe_set, after knpemi_dg_observe_clear and before
+ * knpemi_dg_set_params. */
+int knpemi_dg_observe_record(knpemi_dg* h);
+/* As knpemi_observe_read. */
+int knpemi_dg_observe_read(knpemi_dg* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
+/* Drop the table and the buffer (knpemi_dg_observe_record then fails with KNPEMI_EINVAL); knpemi_dg_destroy does the same. */
+int knpemi_dg_observe_clear(knpemi_dg* h);
+
+/* Membrane events of a DG run (knpemi.dg_recording.DGMembraneEvents): the per-dof state of knpemi_events_set for every
+ * membrane node (facet f, vertex a) = f * nf + a, one threshold and one reset <= threshold for all of them, ring length
+ * 0 <= keep <= KNPEMI_EVENTS_MAX_KEEP; anything else is KNPEMI_EINVAL.  Replaces any previous table and clears all state. */
+int knpemi_dg_events_set(knpemi_dg* h, double threshold, double reset, int keep);
+/* Enqueue one record at time t on the handle's stream (after knpemi_dg_update or knpemi_dg_ode_step): one launch over the
+ * membrane nodes, nothing synchronised, by the rules stated at knpemi_events_record.  KNPEMI_EINVAL before
+ * knpemi_dg_events_set, before knpemi_dg_set_params, and when t is not finite or not greater than the previous record's t. */
+int knpemi_dg_events_record(knpemi_dg* h, double t);
+/* Synchronise and copy out the maps: n_mem_nodes entries each, ring as [keep][n_mem_nodes] in slot order; every pointer
+ * may be NULL.  KNPEMI_EINVAL before knpemi_dg_events_set. */
+int knpemi_dg_events_read(knpemi_dg* h, int32_t* count, double* t_first, double* t_last, double* v_peak, double* t_peak,
+                          double* ring);
+/* All state back to "before the first record"; the table stays.  Enqueue only. */
+int knpemi_dg_events_reset(knpemi_dg* h);
+/* Drop the table and the state buffers (knpemi_dg_events_record then fails with KNPEMI_EINVAL); knpemi_dg_destroy does the
+ * same. */
+int knpemi_dg_events_clear(knpemi_dg* h);
+
 #ifdef __cplusplus
 }
 #endif

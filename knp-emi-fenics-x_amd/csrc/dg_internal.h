@@ -104,6 +104,52 @@ __device__ __forceinline__ int dg_block_index(int b, int chunk) { return (b & 7)
 
 }  // namespace kn_dg
 
+// The jump seminorms of a record (kernels_dg_record.hip): per sub-domain the K concentrations at slots 0 .. K - 1 and the
+// potential at slot KN_MAXK of `tab`, which dg_jump_kernel fills and a KNPEMI_DG_JUMP observable reads.  Allocated in the
+// owner's `allocs` by the first knpemi_dg_observe_set that defines one.
+#define KN_DG_JSLOTS (KN_MAXK + 1)
+struct KnDgJump {
+  double* tab = nullptr;               // [KN_MAXSUB][KN_DG_JSLOTS]
+  double* part = nullptr;              // [n_blk][n_sub * KN_DG_JSLOTS] workgroup partials
+  unsigned long long* ctl = nullptr;   // [4]: the ticket of record_tail.h
+  int n_blk = 0;
+};
+int kn_dg_jump_blocks(int n_cell, int NV);
+// one launch on the owner's main stream: every sub-domain, every field
+int kn_dg_launch_jump(KnDevice* own, const kn_dg::DgDev& D, int NV, int n_sub, int box, const KnDgJump& J);
+
+struct knpemi_dg : KnDevice {
+  int NV = 0, K = 0, n_sub = 0;
+  int NFC = 0, NFV = 0;            // facets per cell, vertices per facet (hexahedra: 6 and 4)
+  int hex_box = 0;                 // hexahedra: every cell is an orthogonal parallelepiped (box-mesh kernels)
+  kn_dg::DgDev dev{};
+  kn_dg::DgConsts consts{};
+  kn_dg::DgConsts* d_consts = nullptr;
+  int have_params = 0;
+  std::vector<int> h_rowptr, h_colind, h_q2e, h_q2i;
+  double* d_fsrc = nullptr;
+  const int* d_colind = nullptr;
+  // (prof: brackets of the two assembly kernels, 0 = EMI, 1 = KNP, on the main stream -- knpemi_dg_profile)
+  // membrane ODE sweep over the membrane nodes: one slot, offset 0 (view: knpemi_dg_create), and what that slot exchanges
+  // with the fields, fixed at knpemi_dg_ode_bind: V's state column and the ions' parameter columns
+  KnSweeps sweeps{this};
+  int sweep_v = 0;
+  int32_t sweep_ion_param[3 * KN_MAXK] = {0};
+  // device solves (knpemi_dg_solve_emi / knpemi_dg_solve_knp): the Krylov + AMG code of the CG path on the DG systems
+  std::vector<int> aux_of;         // continuous P1 dof (sub-domain, mesh vertex) of every broken dof
+  int n_aux = 0;
+  KnSolver solver{this};           // views and configuration: dg_solver, on first use
+  double* d_csol = nullptr;        // [K-1][n_dofs] solved concentrations; != NULL: the solver is set up
+  int extrapolate = 0;             // knpemi_dg_set_extrapolation
+  // The recorders (knpemi_record.hip: knpemi_dg_observe_*, knpemi_dg_events_*): the state, the kernels and the series
+  // routines of the CG path's, each freed by its clear, both by kn_dg_record_free.
+  knpemi_handle::KnObserve obs;
+  knpemi_handle::KnEvents events;
+  KnDgJump jump;
+  bool obs_jump = false;           // the installed observables read `jump.tab`: a record launches dg_jump_kernel first
+};
+void kn_dg_record_free(knpemi_dg* h);   // every recorder's device memory (knpemi_record.hip); knpemi_dg_destroy
+
 // The DG kernels are built for 3, 4 and 8 vertices per cell and KS = K - 1 = 1..3 solved ions; the launchers pick the
 // instantiation with kn_pick and answer anything else (unreachable with a handle knpemi_dg_create made) with this
 inline int kn_dg_not_built(const char* kernel, int NV, int KS) {

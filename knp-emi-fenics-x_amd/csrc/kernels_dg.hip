@@ -701,30 +701,7 @@ __global__ void dg_slot_kernel(double* rec, int slot, double* buf, int n, int to
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-struct knpemi_dg : KnDevice {
-  int NV = 0, K = 0, n_sub = 0;
-  int NFC = 0, NFV = 0;            // facets per cell, vertices per facet (hexahedra: 6 and 4)
-  int hex_box = 0;                 // hexahedra: every cell is an orthogonal parallelepiped (box-mesh kernels)
-  DgDev dev{};
-  DgConsts consts{};
-  DgConsts* d_consts = nullptr;
-  int have_params = 0;
-  std::vector<int> h_rowptr, h_colind, h_q2e, h_q2i;
-  double* d_fsrc = nullptr;
-  const int* d_colind = nullptr;
-  // (prof: brackets of the two assembly kernels, 0 = EMI, 1 = KNP, on the main stream -- knpemi_dg_profile)
-  // membrane ODE sweep over the membrane nodes: one slot, offset 0 (view: knpemi_dg_create), and what that slot exchanges
-  // with the fields, fixed at knpemi_dg_ode_bind: V's state column and the ions' parameter columns
-  KnSweeps sweeps{this};
-  int sweep_v = 0;
-  int32_t sweep_ion_param[3 * KN_MAXK] = {0};
-  // device solves (knpemi_dg_solve_emi / knpemi_dg_solve_knp): the Krylov + AMG code of the CG path on the DG systems
-  std::vector<int> aux_of;         // continuous P1 dof (sub-domain, mesh vertex) of every broken dof
-  int n_aux = 0;
-  KnSolver solver{this};           // views and configuration: dg_solver, on first use
-  double* d_csol = nullptr;        // [K-1][n_dofs] solved concentrations; != NULL: the solver is set up
-  int extrapolate = 0;             // knpemi_dg_set_extrapolation
-};
+// (struct knpemi_dg: dg_internal.h)
 
 namespace {
 
@@ -771,6 +748,7 @@ extern "C" void knpemi_dg_destroy(knpemi_dg* h) {
   (void)hipSetDevice(h->device);
   kn_solver_free(h->solver);
   kn_sweeps_free(h->sweeps);
+  kn_dg_record_free(h);
   kn_device_close(h);
   delete h;
 }

@@ -101,26 +101,25 @@ __global__ __launch_bounds__(EV_THREADS) void events_reset_kernel(EvArgs A) {
   for (int k = 0; k < A.keep; ++k) A.ring[(size_t)k * A.nq_tot + q] = nan;
 }
 
-EvArgs ev_args(knpemi_handle* h, int first, double t, double t_prev) {
-  const auto& E = h->events;
-  return EvArgs{E.n_grid, E.keep, first, (size_t)h->dev.NQtot, t, t_prev, E.tab, h->dev.phiM, E.v_prev, E.armed,
+EvArgs ev_args(const knpemi_handle::KnEvents& E, const KnEvSamples& V, int first, double t, double t_prev) {
+  return EvArgs{E.n_grid, E.keep, first, (size_t)V.nq_tot, t, t_prev, E.tab, V.phiM, E.v_prev, E.armed,
                 E.count, E.t_first, E.t_last, E.v_peak, E.t_peak, E.ring};
 }
 
 }  // namespace
 
-int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev) {
-  const auto& E = h->events;
+int kn_launch_events_record(KnDevice* own, const knpemi_handle::KnEvents& E, const KnEvSamples& V, int first, double t,
+                            double t_prev) {
   if (E.n_grid == 0) return KNPEMI_OK;
   hipLaunchKernelGGL(events_record_kernel, dim3((E.n_grid + EV_THREADS - 1) / EV_THREADS), dim3(EV_THREADS), 0,
-                     h->stream, ev_args(h, first, t, t_prev));
+                     own->stream, ev_args(E, V, first, t, t_prev));
   return kn_launch_check("events_record_kernel");
 }
 
-int kn_launch_events_reset(knpemi_handle* h) {
-  const int n = h->dev.NQtot;
+int kn_launch_events_reset(KnDevice* own, const knpemi_handle::KnEvents& E, const KnEvSamples& V) {
+  const int n = V.nq_tot;
   if (n == 0) return KNPEMI_OK;
-  hipLaunchKernelGGL(events_reset_kernel, dim3((n + EV_THREADS - 1) / EV_THREADS), dim3(EV_THREADS), 0, h->stream,
-                     ev_args(h, 0, 0.0, 0.0));
+  hipLaunchKernelGGL(events_reset_kernel, dim3((n + EV_THREADS - 1) / EV_THREADS), dim3(EV_THREADS), 0, own->stream,
+                     ev_args(E, V, 0, 0.0, 0.0));
   return kn_launch_check("events_reset_kernel");
 }

@@ -148,12 +148,11 @@ __global__ __launch_bounds__(OBS_THREADS) void record_combine_kernel(CombineArgs
 
 }  // namespace
 
-int kn_launch_observe(knpemi_handle* h) {
-  const auto& O = h->obs;
+int kn_launch_observe(KnDevice* own, const knpemi_handle::KnObserve& O) {
   if (O.n_blk == 0 && !O.slots.xbuf) return KNPEMI_OK;
   ObsArgs a{O.n_obs, O.ser.capacity, O.n_blk, O.blk, O.blk_ptr, O.op, O.stride, O.base, O.denom, O.idx, O.w, O.part, O.ser.ctl,
             O.ser.rows, O.slots.xbuf ? O.slots.xbuf + (size_t)O.slots.rank * O.n_obs : nullptr};
-  hipLaunchKernelGGL(observe_kernel, dim3(std::max(O.n_blk, 1)), dim3(OBS_THREADS), 0, h->stream, a);
+  hipLaunchKernelGGL(observe_kernel, dim3(std::max(O.n_blk, 1)), dim3(OBS_THREADS), 0, own->stream, a);
   return kn_launch_check("observe_kernel");
 }
 

@@ -927,7 +927,9 @@ int kn_launch_knp_membrane(knpemi_handle* h, int flags);
 int kn_launch_emi_writeback_membrane(knpemi_handle* h, const double* x, const double* part, int np, double inv_n, double* mean_out);
 int kn_launch_membrane_mass(knpemi_handle* h, int n_entries, const int* d_entry_row, double* d_out);
 int kn_launch_update_pde(knpemi_handle* h);
-int kn_launch_observe(knpemi_handle* h);
+// the observables of either handle on the owner's main stream: the table holds the field addresses, so the launch needs
+// nothing else of the handle
+int kn_launch_observe(KnDevice* own, const knpemi_handle::KnObserve& O);
 int kn_launch_observe_combine(knpemi_handle* h);
 // the combine launch of a partitioned record (kernels_observe.hip): op / denom of the observables, or op == nullptr and
 // col_max of a watch table (sums and maxima from 0; both NULL: every column a sum).  keep_nan: minimum and maximum keep a NaN
@@ -935,8 +937,12 @@ int kn_launch_observe_combine(knpemi_handle* h);
 int kn_launch_record_combine(knpemi_handle* h, const char* who, int n_cols, int capacity, int world, int rank, const int* op,
                              const double* denom, const uint8_t* col_max, double* xbuf, unsigned long long* ctl, double* rows,
                              bool keep_nan = false);
-int kn_launch_events_record(knpemi_handle* h, int first, double t, double t_prev);
-int kn_launch_events_reset(knpemi_handle* h);
+// the membrane events of either handle on the owner's main stream; the view of the samples is the owner's: phi_M over its
+// concatenated membrane dofs (knpemi_handle: dev.phiM, dev.NQtot; knpemi_dg: the membrane nodes)
+struct KnEvSamples { const double* phiM; int nq_tot; };
+int kn_launch_events_record(KnDevice* own, const knpemi_handle::KnEvents& E, const KnEvSamples& V, int first, double t,
+                            double t_prev);
+int kn_launch_events_reset(KnDevice* own, const knpemi_handle::KnEvents& E, const KnEvSamples& V);
 int kn_launch_maps_record(knpemi_handle* h, double t, double t_prev);
 int kn_launch_maps_reset(knpemi_handle* h);
 int kn_launch_snapshot_pack(knpemi_handle* h, char* frame);

@@ -14,6 +14,11 @@
 // buffer, slots_sum sums the buffer over the ranks, and record_combine_kernel (kernels_observe.hip) folds the slots in
 // rank order and appends the row), the clock of the recorders that integrate between two records (KnRecordClock: events, maps) and the per-item
 // fields (KnItemFields: fluxes, exchange, monitors).
+//
+// The observables and the membrane events also record on a DG handle (knpemi_dg_observe_*, knpemi_dg_events_*, at the end
+// of this file): the routines they need take the owner (KnDevice*: device, main stream) and are generic over the handle
+// type that holds the recorder's state; what differs per handle is where a field lives (observe_build's `locate`) and
+// which array the events sample (KnEvSamples).
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -21,6 +26,7 @@
 #include <vector>
 
 #include "knpemi_internal.h"
+#include "dg_internal.h"
 
 int kn_observe_chunk();
 extern "C" int kn_flux_chunk();
@@ -39,13 +45,13 @@ int series_alloc(std::vector<void*>& owner, hipStream_t st, int capacity, int n_
 }
 
 // a new series: rows written and rows dropped back to 0, stream-ordered (no synchronisation)
-int series_rewind(knpemi_handle* h, KnSeries& S) {
+int series_rewind(KnDevice* h, KnSeries& S) {
   KN_HIP(hipMemsetAsync(S.ctl, 0, 2 * sizeof(unsigned long long), h->stream));
   return KNPEMI_OK;
 }
 
 // knpemi_*_read: the first min(n_rows, rows written) rows and the two counters; reset: rewind, synchronised
-int series_read(knpemi_handle* h, KnSeries& S, bool set, const char* fn, const char* none, int n_rows, double* out,
+int series_read(KnDevice* h, KnSeries& S, bool set, const char* fn, const char* none, int n_rows, double* out,
                 int64_t* rows, int64_t* overflow, int reset) {
   if (!set) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": " + none);
   if (n_rows < 0 || (n_rows > 0 && !out)) return kn_fail(KNPEMI_EINVAL, std::string(fn) + ": bad output buffer");
@@ -81,8 +87,8 @@ void recorder_free(knpemi_handle::KnSnap& S) {
   kn_free_all(S.allocs);
   S = knpemi_handle::KnSnap{};
 }
-template <class R>
-int recorder_clear(knpemi_handle* h, R knpemi_handle::*which) {
+template <class H, class R>
+int recorder_clear(H* h, R H::*which) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   KN_HIP(hipSetDevice(h->device));
   KN_HIP(hipStreamSynchronize(h->stream));
@@ -97,8 +103,8 @@ template <class R>
 struct New : R {
   ~New() { recorder_free(static_cast<R&>(*this)); }
 };
-template <class R>
-int recorder_install(knpemi_handle* h, R knpemi_handle::*which, New<R>& next) {
+template <class H, class R>
+int recorder_install(H* h, R H::*which, New<R>& next) {
   KN_HIP(hipStreamSynchronize(h->stream));
   recorder_free(h->*which);
   h->*which = next;
@@ -169,13 +175,13 @@ void kn_record_free(knpemi_handle* h) {
 // observables (kernels_observe.hip)
 // ---------------------------------------------------------------------------------------------------
 namespace {
-// knpemi_observe_set and, with `part`, knpemi_observe_set_partitioned, whose table may hold observables without entries
-int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
-                const double* w, const double* denom, int capacity, const KnRankSlots* part = nullptr) {
-  const std::string fn(who);
-  const bool partitioned = part != nullptr;
-  if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
-  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+// The table of knpemi_observe_set, knpemi_observe_set_partitioned (`partitioned`: an observable may have no entries) and
+// knpemi_dg_observe_set, validated on the host and built in O for recorder_install.  locate(o, field, sub, ix, &loc): where
+// observable o's field lives on the owner's device, or the owner's refusal; finite: weights and denominators must be finite.
+template <class Locate>
+int observe_build(KnDevice* own, const std::string& fn, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
+                  const double* w, const double* denom, int capacity, bool partitioned, bool finite, Locate locate,
+                  knpemi_handle::KnObserve& O) {
   if (n_obs < 1 || capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": n_obs and capacity must be positive");
   if (ptr[0] != 0) return kn_fail(KNPEMI_EINVAL, fn + ": ptr[0] must be 0");
   if (ptr[n_obs] > 0 && (!idx || !w)) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
@@ -190,18 +196,22 @@ int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spe
     if ((partitioned ? ptr[o + 1] < ptr[o] : ptr[o + 1] <= ptr[o]) || ptr[o + 1] > (int64_t)INT32_MAX)
       return kn_fail(KNPEMI_EINVAL, fn + ": observable " + std::to_string(o) + (partitioned ? " has a bad entry range" : " has no entries"));
     KnFieldLoc L;
-    int rc = kn_locate(h, field, sub, ix, &L);
+    int rc = locate(o, field, sub, ix, &L);
     if (rc) return rc;
-    for (int64_t e = ptr[o]; e < ptr[o + 1]; ++e)        // every read of the kernel stays inside the field
+    if (finite && !std::isfinite(denom[o]))
+      return kn_fail(KNPEMI_EINVAL, fn + ": denominator of observable " + std::to_string(o) + " is not finite");
+    for (int64_t e = ptr[o]; e < ptr[o + 1]; ++e) {      // every read of the kernel stays inside the field
       if (idx[e] < 0 || (size_t)idx[e] >= L.n)
         return kn_fail(KNPEMI_EINVAL, fn + ": index out of range in observable " + std::to_string(o));
+      if (finite && !std::isfinite(w[e]))
+        return kn_fail(KNPEMI_EINVAL, fn + ": weight of observable " + std::to_string(o) + " is not finite");
+    }
     op[o] = oo; stride[o] = L.stride; base[o] = L.base;
     for (int64_t e = ptr[o]; e < ptr[o + 1]; e += chunk)
       blk.push_back(make_int4(o, (int)e, (int)std::min<int64_t>(e + chunk, ptr[o + 1]), 0));
     blk_ptr.push_back((int)blk.size());
   }
-  KN_HIP(hipSetDevice(h->device));
-  New<knpemi_handle::KnObserve> O;
+  KN_HIP(hipSetDevice(own->device));
   const size_t ne = (size_t)ptr[n_obs];
   int rc;
   auto& A = O.allocs;
@@ -211,8 +221,22 @@ int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spe
       || (rc = kn_upload(A, reinterpret_cast<const int*>(idx), ne, &O.idx)) || (rc = kn_upload(A, w, ne, &O.w)))
     return rc;
   if (kn_alloc(A, blk.size(), &O.part)) return kn_fail(KNPEMI_ENOMEM, fn + ": partials");
-  if (series_alloc(A, h->stream, capacity, n_obs, &O.ser)) return kn_fail(KNPEMI_ENOMEM, fn + ": buffer");
+  if (series_alloc(A, own->stream, capacity, n_obs, &O.ser)) return kn_fail(KNPEMI_ENOMEM, fn + ": buffer");
   O.n_obs = n_obs; O.n_blk = (int)blk.size();
+  return KNPEMI_OK;
+}
+
+// knpemi_observe_set and, with `part`, knpemi_observe_set_partitioned, whose table may hold observables without entries
+int observe_set(knpemi_handle* h, const char* who, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
+                const double* w, const double* denom, int capacity, const KnRankSlots* part = nullptr) {
+  const std::string fn(who);
+  const bool partitioned = part != nullptr;
+  if (!h || !spec || !ptr || !denom || (!partitioned && (!idx || !w))) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (h->ode_only) return kn_fail(KNPEMI_EINVAL, fn + ": a handle of knpemi_ode_create has no fields");
+  New<knpemi_handle::KnObserve> O;
+  auto locate = [&](int, int field, int sub, int ix, KnFieldLoc* L) { return kn_locate(h, field, sub, ix, L); };
+  int rc = observe_build(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, partitioned, false, locate, O);
+  if (rc) return rc;
   if (part && (rc = slots_attach(h, &O.slots, *part, n_obs))) return rc;
   return recorder_install(h, &knpemi_handle::obs, O);
 }
@@ -239,7 +263,7 @@ extern "C" int knpemi_observe_record(knpemi_handle* h) {
   auto& O = h->obs;
   if (O.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_observe_record: no observables set");
   KN_HIP(hipSetDevice(h->device));
-  int rc = kn_launch_observe(h);
+  int rc = kn_launch_observe(h, O);
   if (rc || !O.slots.xbuf) return rc;
   // partitioned: this rank's slots are written; sum the exchange buffer over the ranks, then fold and append
   if ((rc = slots_sum(h, "knpemi_observe_record", O.slots, O.n_obs))) return rc;
@@ -257,6 +281,42 @@ extern "C" int knpemi_observe_clear(knpemi_handle* h) { return recorder_clear(h,
 // ---------------------------------------------------------------------------------------------------
 // membrane events (kernels_events.hip)
 // ---------------------------------------------------------------------------------------------------
+namespace {
+// the table and the state arrays over the owner's nq concatenated membrane dofs, in E for recorder_install
+int events_build(const KnEvTab& T, size_t nq, int keep, const bool* watched, knpemi_handle::KnEvents& E) {
+  auto& A = E.allocs;
+  int rc;
+  if ((rc = kn_upload(A, &T, 1, &E.tab)) || (rc = kn_alloc(A, nq, &E.v_prev)) || (rc = kn_alloc(A, nq, &E.armed))
+      || (rc = kn_alloc(A, nq, &E.count)) || (rc = kn_alloc(A, nq, &E.t_first)) || (rc = kn_alloc(A, nq, &E.t_last))
+      || (rc = kn_alloc(A, nq, &E.v_peak)) || (rc = kn_alloc(A, nq, &E.t_peak))
+      || (rc = kn_alloc(A, nq * (size_t)keep, &E.ring)))
+    return rc;
+  E.n_watch = T.n_watch; E.keep = keep; E.n_grid = T.gstart[T.n_watch];
+  std::copy(watched, watched + KN_MAXSUB, E.watched);
+  return KNPEMI_OK;
+}
+// the maps of the nq dofs from q0 on, of nq_tot, synchronised; every pointer may be NULL
+int events_copy_out(KnDevice* own, const knpemi_handle::KnEvents& E, size_t q0, size_t nq, size_t nq_tot, int32_t* count,
+                    double* t_first, double* t_last, double* v_peak, double* t_peak, double* ring) {
+  KN_HIP(hipSetDevice(own->device));
+  if (nq) {
+    auto copy = [&](auto* host, const auto* dev, size_t n) -> int {
+      if (host) KN_HIP(hipMemcpyAsync(host, dev, n * sizeof(*host), hipMemcpyDeviceToHost, own->stream));
+      return KNPEMI_OK;
+    };
+    int rc;
+    if ((rc = copy(count, E.count + q0, nq)) || (rc = copy(t_first, E.t_first + q0, nq))
+        || (rc = copy(t_last, E.t_last + q0, nq)) || (rc = copy(v_peak, E.v_peak + q0, nq))
+        || (rc = copy(t_peak, E.t_peak + q0, nq)))
+      return rc;
+    for (int k = 0; ring && k < E.keep; ++k)          // row k of the ring: this piece of [keep][nq_tot]
+      if ((rc = copy(ring + (size_t)k * nq, E.ring + (size_t)k * nq_tot + q0, nq))) return rc;
+  }
+  KN_HIP(hipStreamSynchronize(own->stream));
+  return KNPEMI_OK;
+}
+}  // namespace
+
 extern "C" int knpemi_events_set(knpemi_handle* h, int n_watch, const int32_t* sub, const double* threshold,
                                  const double* reset, int keep) {
   const std::string fn = "knpemi_events_set";
@@ -281,18 +341,10 @@ extern "C" int knpemi_events_set(knpemi_handle* h, int n_watch, const int32_t* s
   T.n_watch = n_watch;
   KN_HIP(hipSetDevice(h->device));
   New<knpemi_handle::KnEvents> E;
-  auto& A = E.allocs;
-  const size_t nq = (size_t)h->dev.NQtot;
   int rc;
-  if ((rc = kn_upload(A, &T, 1, &E.tab)) || (rc = kn_alloc(A, nq, &E.v_prev)) || (rc = kn_alloc(A, nq, &E.armed))
-      || (rc = kn_alloc(A, nq, &E.count)) || (rc = kn_alloc(A, nq, &E.t_first)) || (rc = kn_alloc(A, nq, &E.t_last))
-      || (rc = kn_alloc(A, nq, &E.v_peak)) || (rc = kn_alloc(A, nq, &E.t_peak))
-      || (rc = kn_alloc(A, nq * (size_t)keep, &E.ring)))
-    return rc;
-  E.n_watch = n_watch; E.keep = keep; E.n_grid = T.gstart[n_watch];
-  std::copy(watched, watched + KN_MAXSUB, E.watched);
+  if ((rc = events_build(T, (size_t)h->dev.NQtot, keep, watched, E))) return rc;
   if ((rc = recorder_install(h, &knpemi_handle::events, E))) return rc;
-  if ((rc = kn_launch_events_reset(h))) recorder_free(h->events);
+  if ((rc = kn_launch_events_reset(h, h->events, {h->dev.phiM, h->dev.NQtot}))) recorder_free(h->events);
   return rc;
 }
 
@@ -302,7 +354,7 @@ extern "C" int knpemi_events_record(knpemi_handle* h, double t) {
   if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_record: no events set (knpemi_events_set)");
   if (int rc = clock_accept(E.clock, "knpemi_events_record", t)) return rc;
   KN_HIP(hipSetDevice(h->device));
-  if (int rc = kn_launch_events_record(h, E.clock.have_prev ? 0 : 1, t, E.clock.t_prev)) return rc;
+  if (int rc = kn_launch_events_record(h, E, {h->dev.phiM, h->dev.NQtot}, E.clock.have_prev ? 0 : 1, t, E.clock.t_prev)) return rc;
   clock_advance(E.clock, t);
   return KNPEMI_OK;
 }
@@ -314,23 +366,8 @@ extern "C" int knpemi_events_read(knpemi_handle* h, int sub, int32_t* count, dou
   if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: no events set (knpemi_events_set)");
   if (sub < 1 || sub >= h->n_sub || !E.watched[sub])
     return kn_fail(KNPEMI_EINVAL, "knpemi_events_read: sub-domain is not watched");
-  KN_HIP(hipSetDevice(h->device));
-  const size_t q0 = (size_t)h->qoff[sub], nq = (size_t)h->n_q[sub], nq_tot = (size_t)h->dev.NQtot;
-  if (nq) {
-    auto copy = [&](auto* host, const auto* dev, size_t n) -> int {
-      if (host) KN_HIP(hipMemcpyAsync(host, dev, n * sizeof(*host), hipMemcpyDeviceToHost, h->stream));
-      return KNPEMI_OK;
-    };
-    int rc;
-    if ((rc = copy(count, E.count + q0, nq)) || (rc = copy(t_first, E.t_first + q0, nq))
-        || (rc = copy(t_last, E.t_last + q0, nq)) || (rc = copy(v_peak, E.v_peak + q0, nq))
-        || (rc = copy(t_peak, E.t_peak + q0, nq)))
-      return rc;
-    for (int k = 0; ring && k < E.keep; ++k)          // row k of the ring: this sub-domain's piece of [keep][NQtot]
-      if ((rc = copy(ring + (size_t)k * nq, E.ring + (size_t)k * nq_tot + q0, nq))) return rc;
-  }
-  KN_HIP(hipStreamSynchronize(h->stream));
-  return KNPEMI_OK;
+  return events_copy_out(h, E, (size_t)h->qoff[sub], (size_t)h->n_q[sub], (size_t)h->dev.NQtot, count, t_first, t_last, v_peak,
+                         t_peak, ring);
 }
 
 extern "C" int knpemi_events_reset(knpemi_handle* h) {
@@ -339,7 +376,7 @@ extern "C" int knpemi_events_reset(knpemi_handle* h) {
   if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_events_reset: no events set (knpemi_events_set)");
   KN_HIP(hipSetDevice(h->device));
   clock_restart(E.clock);
-  return kn_launch_events_reset(h);
+  return kn_launch_events_reset(h, E, {h->dev.phiM, h->dev.NQtot});
 }
 
 extern "C" int knpemi_events_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::events); }
@@ -1326,3 +1363,139 @@ extern "C" int kn_snapshot_pack_only(knpemi_handle* h, int n) {
     if (int rc = kn_launch_snapshot_pack(h, S.dev[(size_t)(S.seq % S.depth)])) return rc;
   return KNPEMI_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// the DG handle's recorders (knpemi_dg_observe_*, knpemi_dg_events_*): the state, the install rule, the series routines
+// and the kernels above, on the fields of a knpemi_dg; the jump seminorms are kernels_dg_record.hip's
+// ---------------------------------------------------------------------------------------------------
+void kn_dg_record_free(knpemi_dg* h) {
+  kn_free_all(h->obs.allocs);
+  kn_free_all(h->events.allocs);
+}
+
+namespace {
+KnEvSamples dg_samples(const knpemi_dg* h) { return {h->dev.phiM, h->dev.nq}; }
+
+// the table, the partials and the ticket of dg_jump_kernel: once per handle, in its `allocs`
+int dg_jump_alloc(knpemi_dg* h) {
+  KnDgJump& J = h->jump;
+  if (J.tab) return KNPEMI_OK;
+  KnDgJump N;
+  N.n_blk = kn_dg_jump_blocks(h->dev.n_cell, h->NV);
+  int rc;
+  if ((rc = kn_zeros(h->allocs, h->stream, (size_t)KN_MAXSUB * KN_DG_JSLOTS, &N.tab))
+      || (rc = kn_zeros(h->allocs, h->stream, (size_t)N.n_blk * h->n_sub * KN_DG_JSLOTS, &N.part))
+      || (rc = kn_zeros(h->allocs, h->stream, 4, &N.ctl)))
+    return rc;
+  J = N;
+  return KNPEMI_OK;
+}
+}  // namespace
+
+extern "C" int knpemi_dg_observe_set(knpemi_dg* h, int n_obs, const int32_t* spec, const int64_t* ptr, const int32_t* idx,
+                                     const double* w, const double* denom, int capacity) {
+  const std::string fn = "knpemi_dg_observe_set";
+  if (!h || !spec || !ptr || !denom || !idx || !w) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  KN_HIP(hipSetDevice(h->device));
+  bool jump = false;
+  for (int o = 0; o < n_obs; ++o) jump = jump || spec[4 * o] == KNPEMI_DG_JUMP;
+  if (jump)
+    if (int rc = dg_jump_alloc(h)) return rc;
+  const kn_dg::DgDev& D = h->dev;
+  auto locate = [&](int o, int field, int sub, int ix, KnFieldLoc* L) {
+    const std::string who = fn + ": observable " + std::to_string(o);
+    switch (field) {
+      case KNPEMI_DG_C:
+        if (ix < 0 || ix >= h->K) return kn_fail(KNPEMI_EINVAL, who + ": ion index out of range");
+        *L = {D.rec + KN_CSLOT(ix), KN_REC, (size_t)D.n_dof};
+        return KNPEMI_OK;
+      case KNPEMI_DG_PHI: *L = {D.rec + 7, KN_REC, (size_t)D.n_dof}; return KNPEMI_OK;
+      case KNPEMI_DG_PHI_M: *L = {D.phiM, 1, (size_t)D.nq}; return KNPEMI_OK;
+      case KNPEMI_DG_JUMP:
+        if (sub < 0 || sub >= h->n_sub) return kn_fail(KNPEMI_EINVAL, who + ": bad sub-domain index");
+        if (ix < -1 || ix >= h->K) return kn_fail(KNPEMI_EINVAL, who + ": ion index out of range (-1: the potential)");
+        if (spec[4 * o + 3] != KNPEMI_OBS_SUM) return kn_fail(KNPEMI_EINVAL, who + ": a jump seminorm is a KNPEMI_OBS_SUM entry");
+        *L = {h->jump.tab + (size_t)sub * KN_DG_JSLOTS + (ix < 0 ? KN_MAXK : ix), 1, 1};
+        return KNPEMI_OK;
+    }
+    return kn_fail(KNPEMI_EINVAL, who + ": unknown field (KNPEMI_DG_C, _PHI, _PHI_M or _JUMP)");
+  };
+  New<knpemi_handle::KnObserve> O;
+  if (int rc = observe_build(h, fn, n_obs, spec, ptr, idx, w, denom, capacity, false, true, locate, O)) return rc;
+  if (int rc = recorder_install(h, &knpemi_dg::obs, O)) return rc;
+  h->obs_jump = jump;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_dg_observe_record(knpemi_dg* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (h->obs.n_obs == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_observe_record: no observables set (knpemi_dg_observe_set)");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_observe_record: knpemi_dg_set_params has not been called");
+  KN_HIP(hipSetDevice(h->device));
+  if (h->obs_jump)
+    if (int rc = kn_dg_launch_jump(h, h->dev, h->NV, h->n_sub, h->hex_box, h->jump)) return rc;
+  return kn_launch_observe(h, h->obs);
+}
+
+extern "C" int knpemi_dg_observe_read(knpemi_dg* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  return series_read(h, h->obs.ser, h->obs.n_obs != 0, "knpemi_dg_observe_read", "no observables set (knpemi_dg_observe_set)",
+                     n_rows, out, rows, overflow, reset);
+}
+
+extern "C" int knpemi_dg_observe_clear(knpemi_dg* h) {
+  if (int rc = recorder_clear(h, &knpemi_dg::obs)) return rc;
+  h->obs_jump = false;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_dg_events_set(knpemi_dg* h, double threshold, double reset, int keep) {
+  const std::string fn = "knpemi_dg_events_set";
+  if (!h) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (keep < 0 || keep > KNPEMI_EVENTS_MAX_KEEP) return kn_fail(KNPEMI_EINVAL, fn + ": keep must be in 0..KNPEMI_EVENTS_MAX_KEEP");
+  if (!(reset <= threshold)) return kn_fail(KNPEMI_EINVAL, fn + ": reset must not exceed the threshold");
+  if (h->dev.nq == 0) return kn_fail(KNPEMI_EINVAL, fn + ": the mesh has no membrane facets");
+  // one segment: every membrane node, in node order
+  KnEvTab T{};
+  bool watched[KN_MAXSUB] = {};
+  T.n_watch = 1; T.gstart[1] = h->dev.nq; T.q0[0] = 0; T.sub[0] = 0;
+  T.threshold[0] = threshold; T.reset[0] = reset;
+  watched[0] = true;
+  KN_HIP(hipSetDevice(h->device));
+  New<knpemi_handle::KnEvents> E;
+  int rc;
+  if ((rc = events_build(T, (size_t)h->dev.nq, keep, watched, E))) return rc;
+  if ((rc = recorder_install(h, &knpemi_dg::events, E))) return rc;
+  if ((rc = kn_launch_events_reset(h, h->events, dg_samples(h)))) recorder_free(h->events);
+  return rc;
+}
+
+extern "C" int knpemi_dg_events_record(knpemi_dg* h, double t) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_events_record: no events set (knpemi_dg_events_set)");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_events_record: knpemi_dg_set_params has not been called");
+  if (int rc = clock_accept(E.clock, "knpemi_dg_events_record", t)) return rc;
+  KN_HIP(hipSetDevice(h->device));
+  if (int rc = kn_launch_events_record(h, E, dg_samples(h), E.clock.have_prev ? 0 : 1, t, E.clock.t_prev)) return rc;
+  clock_advance(E.clock, t);
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_dg_events_read(knpemi_dg* h, int32_t* count, double* t_first, double* t_last, double* v_peak,
+                                     double* t_peak, double* ring) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (h->events.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_events_read: no events set (knpemi_dg_events_set)");
+  return events_copy_out(h, h->events, 0, (size_t)h->dev.nq, (size_t)h->dev.nq, count, t_first, t_last, v_peak, t_peak, ring);
+}
+
+extern "C" int knpemi_dg_events_reset(knpemi_dg* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& E = h->events;
+  if (E.n_watch == 0) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_events_reset: no events set (knpemi_dg_events_set)");
+  KN_HIP(hipSetDevice(h->device));
+  clock_restart(E.clock);
+  return kn_launch_events_reset(h, E, dg_samples(h));
+}
+
+extern "C" int knpemi_dg_events_clear(knpemi_dg* h) { return recorder_clear(h, &knpemi_dg::events); }

@@ -93,7 +93,7 @@ class DGParams(C.Structure):
     ]
 
 
-DG_C, DG_PHI, DG_PHI_M, DG_I_CH, DG_SOURCE = range(5)
+DG_C, DG_PHI, DG_PHI_M, DG_I_CH, DG_SOURCE, DG_JUMP = range(6)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
@@ -286,6 +286,17 @@ SIGNATURES = {
     "knpemi_dg_set_distributed": (C.c_int, [C.c_void_p, c_u8_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "knpemi_dg_vec_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "knpemi_dg_vec_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "knpemi_dg_observe_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.POINTER(C.c_int64), c_int_p, c_dbl_p, c_dbl_p,
+                                        C.c_int]),
+    "knpemi_dg_observe_record": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_observe_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.c_int]),
+    "knpemi_dg_observe_clear": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_events_set": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "knpemi_dg_events_record": (C.c_int, [C.c_void_p, C.c_double]),
+    "knpemi_dg_events_read": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+    "knpemi_dg_events_reset": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_events_clear": (C.c_int, [C.c_void_p]),
 }
 
 

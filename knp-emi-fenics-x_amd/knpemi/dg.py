@@ -24,6 +24,31 @@ from . import _lib as L
 _KIND = {"triangle": L.TRIANGLE, "tetrahedron": L.TETRAHEDRON, "hexahedron": L.HEXAHEDRON}
 
 
+def cell_subdomains(ct, subdomain_tags):
+    """Sub-domain index of every cell from the cell MeshTags `ct` (or a dense array) and the cell tags in sub-domain order."""
+    cell_tags = np.asarray(ct.dense() if hasattr(ct, "dense") else ct)
+    tag_to_sub = {int(t): i for i, t in enumerate(subdomain_tags)}
+    try:
+        return np.array([tag_to_sub[int(t)] for t in cell_tags], np.int32)
+    except KeyError as e:
+        raise ValueError(f"cell tag {e} is not in subdomain_tags") from None
+
+
+def membrane_facets(mesh, ft, membrane_tags):
+    """(vertex ids (nmf, nf) int32, facet tags (nmf,)) of the facets of `mesh` that the facet MeshTags `ft` (or a dense
+    array) tag with one of `membrane_tags`, in increasing facet order: the membrane facets of the DG handle."""
+    if hasattr(ft, "indices"):
+        sel = np.isin(ft.values, list(membrane_tags))
+        fidx = np.sort(ft.indices[sel])
+        order = np.argsort(ft.indices[sel], kind="stable")
+        tags = np.asarray(ft.values[sel])[order]
+    else:
+        dense = np.asarray(ft)
+        fidx = np.flatnonzero(np.isin(dense, list(membrane_tags)))
+        tags = dense[fidx]
+    return np.ascontiguousarray(mesh.facets[fidx], np.int32).reshape(-1, mesh.facets.shape[1]), tags
+
+
 class DGProblem:
     def __init__(self, mesh, ct, ft, subdomain_tags, membrane_tags, n_ions=3, device=0):
         """`ct`, `ft`: cell and facet MeshTags of `mesh` (or dense arrays); `subdomain_tags`: cell tags in sub-domain
@@ -35,23 +60,11 @@ class DGProblem:
         self.nv = mesh.cells.shape[1]
         self.nf = mesh.facets.shape[1]                      # vertices per facet
         self.K = int(n_ions)
-        cell_tags = np.asarray(ct.dense() if hasattr(ct, "dense") else ct)
-        tag_to_sub = {int(t): i for i, t in enumerate(subdomain_tags)}
-        try:
-            self.cell_sub = np.array([tag_to_sub[int(t)] for t in cell_tags], np.int32)
-        except KeyError as e:
-            raise ValueError(f"cell tag {e} is not in subdomain_tags") from None
+        self.cell_sub = cell_subdomains(ct, subdomain_tags)
         self.n_sub = len(subdomain_tags)
-        if hasattr(ft, "indices"):
-            sel = np.isin(ft.values, list(membrane_tags))
-            fidx = np.sort(ft.indices[sel])
-            order = np.argsort(ft.indices[sel], kind="stable")
-            self.mem_tags = np.asarray(ft.values[sel])[order]
-        else:
-            dense = np.asarray(ft)
-            fidx = np.flatnonzero(np.isin(dense, list(membrane_tags)))
-            self.mem_tags = dense[fidx]
-        self.mem_facets = np.ascontiguousarray(mesh.facets[fidx], np.int32).reshape(-1, self.nf)
+        self.mem_facets, self.mem_tags = membrane_facets(mesh, ft, membrane_tags)
+        self.taps = []                                      # the attached recorders (knpemi.recording.Tap): observe, detect
+        self.n_records = 0
         self.n_cells = mesh.num_cells
         self.n = self.n_cells * self.nv
         self.nmf = self.mem_facets.shape[0]
@@ -250,6 +263,59 @@ class DGProblem:
         L.check(self.lib.knpemi_dg_time_kernel(self.h, which, 0 if splitting_scheme else L.NO_SPLITTING, reps, C.byref(ms)))
         return ms.value
 
+    # -- recorders (knpemi.dg_recording) -----------------------------------------------------------------------
+    def _may_attach(self, name, every, capacity, busy):
+        if every < 1 or (capacity is not None and capacity < 1):
+            raise ValueError("every and capacity must be positive")
+        if any(n == name for n, _ in self.taps):
+            raise RuntimeError(busy)
+
+    def observe(self, obs, every=1, capacity=1024, t0=0.0):
+        """Record the observables `obs` (knpemi.dg_recording.DGObservables) on the device at every `every`-th call of
+        `record(t)`: the jump launch when a jump seminorm is defined, then the observe launch, on the handle's stream
+        behind the update and the sweep, nothing synchronised.  Rows collect in a device buffer of `capacity` rows and
+        drain into `obs` (one synchronisation) when the buffer is full and when `obs.series()` is called."""
+        from .recording import Tap
+        lib, h = self.lib, self.h
+        self._may_attach("observe", every, capacity, "this problem records observables already")
+        if obs._drain is not None:
+            raise RuntimeError("these observables are attached to a problem already")
+
+        def read(n, buf):
+            rows, over = C.c_int64(), C.c_int64()
+            L.check(lib.knpemi_dg_observe_read(h, n, None if buf is None else L.dptr(buf), C.byref(rows), C.byref(over), 1))
+            return rows.value, over.value
+        obs.upload(self, capacity)
+        self.taps.append(("observe", Tap(obs, "DG observables", every, lambda t, f: L.check(lib.knpemi_dg_observe_record(h)),
+                                         t0, capacity=capacity, read=read, n_cols=obs.n_cols, rewind=lambda: read(0, None))))
+
+    def detect(self, ev, every=1, t0=0.0):
+        """Record the membrane events `ev` (knpemi.dg_recording.DGMembraneEvents) on the device at every `every`-th call
+        of `record(t)`: one launch over the membrane nodes; `ev.maps()` reads the maps back."""
+        from .recording import Tap
+        lib, h = self.lib, self.h
+        self._may_attach("detect", every, None, "this problem records membrane events already")
+
+        def rewind():
+            L.check(lib.knpemi_dg_events_reset(h))
+            ev.reset_host()
+        ev._attach(self)
+        self.taps.append(("detect", Tap(ev, "DG membrane events", every,
+                                        lambda t, f: L.check(lib.knpemi_dg_events_record(h, float(t))), t0, rewind=rewind)))
+
+    def record(self, t):
+        """One record at time t (the end of a step, after `update`): every attached recorder that is due enqueues its
+        launch."""
+        self.n_records += 1
+        for _, tap in self.taps:
+            tap.tick_at(self.n_records, t)
+
+    def reset_recorders(self):
+        """A new series and new maps: on the device, in the pending lists and in the recorders; the record count restarts."""
+        for _, tap in self.taps:
+            tap.reset()
+        self.n_records = 0
+
 
 class DGSlab:
     """One rank's part of the DG problem on `make_mesh_3D(r, cell, l)` (cell = "tetrahedron": broken P1 on the 6-tet split,
@@ -296,6 +362,15 @@ class DGSlab:
     @property
     def mode(self):
         return "not attached" if self.transport is None else self.transport.mode
+
+    _NO_RECORDS = ("DGSlab.{}: records of a cell-partitioned DG run are not built -- a rank's sums, extrema and jump "
+                   "seminorms would count its ghost cells a second time; record on a single-rank DGProblem")
+
+    def observe(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RECORDS.format("observe"))
+
+    def detect(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RECORDS.format("detect"))
 
     def attach(self):
         from .fem.transport import Transport, dg_endpoint

@@ -321,9 +321,12 @@ class Tap:
             raise NotImplementedError(self.partition_refusal)
 
     def tick(self, k, dt):
+        self.tick_at(k, self.t0 + (k + self.offset) * dt)
+
+    def tick_at(self, k, t):
+        """`tick` for a caller that keeps the clock itself (`DGProblem.record(t)`): record k is due as above, at time t."""
         if not self.enabled or (k + self.offset) % self.every:
             return
-        t = self.t0 + (k + self.offset) * dt
         self.record(t, 1 if self.fields else 0)
         if self.read is not None:
             self.pending.append(t)
