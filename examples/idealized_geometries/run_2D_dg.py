@@ -4,12 +4,14 @@ membrane ODEs at the facet nodes, both assemblies, both linear solves (CG / BiCG
 `knpemi_dg_solve_emi/knp`) and the end-of-step update on the GPU; `--host-solves` solves the two systems with SciPy
 from the CSR the kernels fill instead.
 
-    python run_2D_dg.py [--resolution 1] [--steps 100] [--host-solves] [--series s.npz] [--events e.npz]
+    python run_2D_dg.py [--resolution 1] [--steps 100] [--host-solves] [--series s.npz] [--events e.npz] [--balance b.npz]
 
 `--series` records on the device, at the end of every step, phi and the ions at the ECS and ICS points of run_2D.py's
 `--series`, phi_M and the traces at its membrane point, the maximum and the average of K in the ECS and the jump seminorms
 of phi and of K in both sub-domains (`knpemi.dg_recording.DGObservables`); `--events` the upward crossings of -20 mV per
-membrane node (`DGMembraneEvents`, re-armed 20 mV below, the latest 8 times kept).
+membrane node (`DGMembraneEvents`, re-armed 20 mV below, the latest 8 times kept); `--balance` the per-cell ion balance
+(`knpemi.dg_balance.DGIonBalance`): per sub-domain and ion the mass, the summed outflow, the penalty share and the largest
+conservation defect, per membrane tag the ion transfer on both sides and the currents, and the cell table of the last step.
 
 `--cell-type quadrilateral` is parsed, as in run_2D.py, and refused with the DG module's message: the DG variant has no
 quadrilateral kernels.
@@ -30,6 +32,7 @@ import mm_hh                                                       # noqa: E402
 from setup_problem import (C_M, CL_E, CL_I, D_CL, D_K, D_NA, DT, FARADAY, K_E, K_I, NA_E, NA_I, PSI)  # noqa: E402
 from knpemi import _lib as L                                       # noqa: E402
 from knpemi.dg import DGProblem                                    # noqa: E402
+from knpemi.dg_balance import DGIonBalance                         # noqa: E402
 from knpemi.dg_recording import DGMembraneEvents, DGObservables    # noqa: E402
 from knpemi.fem.idealized import make_mesh_2D                      # noqa: E402
 
@@ -48,10 +51,11 @@ EVENT_THRESHOLD = -20e-3                                           # run_2D.py: 
 
 class DGRun:
     def __init__(self, resolution=1, g_syn=10.0, dt=DT, device_solves=True, rtol=(1e-5, 1e-7), cell_type="triangle",
-                 series=None, events=None):
-        """series / events: paths of the .npz files `save` writes (None: not recorded)."""
+                 series=None, events=None, balance=None):
+        """series / events / balance: paths of the .npz files `save` writes (None: not recorded)."""
         self.device_solves, self.rtol, self.iterations = device_solves, rtol, []
         self.series, self.events, self.obs, self.ev = series, events, None, None
+        self.balance, self.bal = balance, None
         mesh, ct, ft = make_mesh_2D(resolution, cell_type=cell_type)      # quadrilaterals: DGProblem refuses them
         self.dp = dp = DGProblem(mesh, ct, ft, [0, 1], [1])
         self.ions = [dict(name="K", z=1.0, D=[D_K] * 2), dict(name="Cl", z=-1.0, D=[D_CL] * 2), dict(name="Na", z=1.0, D=[D_NA] * 2)]
@@ -91,6 +95,9 @@ class DGRun:
             self.ev = ev = DGMembraneEvents(mesh, ft, [1])
             ev.watch(EVENT_THRESHOLD, reset=EVENT_THRESHOLD - 20e-3, keep=8)
             dp.detect(ev)
+        if balance:
+            self.bal = DGIonBalance(mesh, ct, ft, [0, 1], [1], [i["name"] for i in self.ions])
+            dp.balance(self.bal)
 
     def step(self):
         dp = self.dp
@@ -99,12 +106,14 @@ class DGRun:
         if self.device_solves:                                       # pdeSolver.py:24-35,99-110 (rtol 1e-5 / 1e-7)
             it_emi = dp.solve_emi(rtol=self.rtol[0])[0]
             dp.assemble_knp()
+            dp.record_membrane()                                     # the ion balance's first launch, when one is due
             it_knp = dp.solve_knp(rtol=self.rtol[1], update=True)[0]
             self.iterations.append((it_emi, it_knp))
         else:
             phi = solve_singular(dp.matrix(0), dp.rhs(0))
             dp.set_potential(phi)
             dp.assemble_knp()
+            dp.record_membrane()
             c_new = np.stack([spla.splu(dp.matrix(1 + k).tocsc()).solve(dp.rhs(1 + k)) for k in range(2)])
             dp.update(c_new)
         n_rhs, n_steps, n_failed = dp.ode_stats()
@@ -118,6 +127,8 @@ class DGRun:
             self.obs.save(self.series)
         if self.ev is not None:
             self.ev.save(self.events)
+        if self.bal is not None:
+            self.bal.save(self.balance)
 
 
 def build_parser():
@@ -128,12 +139,14 @@ def build_parser():
     ap.add_argument("--cell-type", choices=["triangle", "quadrilateral"], default="triangle")
     ap.add_argument("--series", metavar="PATH", default=None, help="time series of the observables and jump seminorms (.npz)")
     ap.add_argument("--events", metavar="PATH", default=None, help="membrane events per membrane node (.npz)")
+    ap.add_argument("--balance", metavar="PATH", default=None, help="per-cell ion balance: series and last cell table (.npz)")
     return ap
 
 
 if __name__ == "__main__":
     a = build_parser().parse_args()
-    run = DGRun(a.resolution, device_solves=not a.host_solves, cell_type=a.cell_type, series=a.series, events=a.events)
+    run = DGRun(a.resolution, device_solves=not a.host_solves, cell_type=a.cell_type, series=a.series, events=a.events,
+                balance=a.balance)
     for k in range(a.steps):
         run.step()
         if (k + 1) % 10 == 0:

@@ -1137,6 +1137,47 @@ int knpemi_dg_events_reset(knpemi_dg* h);
  * same. */
 int knpemi_dg_events_clear(knpemi_dg* h);
 
+/* The per-cell ion balance of a DG run (knpemi.dg_balance.DGIonBalance): what the scheme conserves cell by cell.  Testing
+ * the system of solved ion k with the indicator of a cell T leaves
+ *     (m_T,k(new) - m_T,k(old)) / dt + out_T,k = mem_T,k + src_T,k  (+ the cell's share of the solve's residual),
+ * m_T,k = int_T c_k, out_T,k the numerical outflow of the assembly through the interior facets of T in its three parts
+ *     cons  = - int_F {D_k grad c_k} . n_T,   pen = int_F (gamma / h_F) {D_k} [c_k],   drift = int_F beta_F c_k^up
+ * (beta_F = -z_k psi {D_k grad phi} . n_T, upwind side T when beta_F > 0; every ingredient as the assembly kernels take it;
+ * membrane and boundary facets contribute nothing), mem_T,k the integral over the cell's membrane facets of
+ *     j_k^s = (I_ch,k + alpha_k^s (I_cap - S I_ch,tot)) / (F z_k),  I_cap = C_M ([phi] - phi_M) / dt,
+ * counted positive INTO T (s: the cell's own side; S = 1 with the splitting scheme; the assembly's degree-6 facet rule), and
+ * src_T,k = int_T f_k on ECS cells.  cons, pen, drift, mem and the masses are kept for all K ions, src and the defect
+ *     defect_T,k = (m_new - m_old) / dt + cons + pen + drift - mem - src
+ * for the K - 1 solved ones (0 for the eliminated ion).
+ *
+ * knpemi_dg_balance_set installs the recorder: a series buffer of `capacity` rows, the cell table, and for every membrane
+ * facet the index facet_tag[f] < n_tags (<= 8) of its tag (NULL allowed without membrane facets).  want_cells == 0: the
+ * end-of-step launch does not write its columns of the cell table and knpemi_dg_balance_cells is refused.  Anything else is
+ * KNPEMI_EINVAL by name, and the previous recorder keeps recording.
+ * A row: [n_sub][K](sum_T m_new, sum_T out, sum_T |pen|, max_T |defect|), then [n_tags](K x sum_F int j_k^e, K x sum_F int
+ * j_k^i, int I_cap, int I_ch,tot, area). */
+int knpemi_dg_balance_set(knpemi_dg* h, int capacity, int want_cells, int n_tags, const int32_t* facet_tag);
+/* Between knpemi_dg_assemble_knp and the solve of the concentrations (old concentrations, new potential, old phi_M, I_ch on
+ * the device): one launch on the handle's stream writes mem, m_old and src of every cell and the membrane tags' sums; the
+ * splitting scheme is that of the last knpemi_dg_assemble_knp.  Nothing is synchronised.  KNPEMI_EINVAL before
+ * knpemi_dg_balance_set and before knpemi_dg_set_params. */
+int knpemi_dg_balance_record_membrane(knpemi_dg* h);
+/* At the end of the step, after knpemi_dg_update (new concentrations): one launch writes the outflow parts, m_new and the
+ * defect (dt: that of knpemi_dg_set_params) and appends the row; t, the time of the record, must be finite -- the row carries
+ * no time, the caller keeps it.  Sums are formed in a fixed order without floating-point atomics: two identical runs give
+ * bit-identical rows and tables.  KNPEMI_EINVAL, by name: before knpemi_dg_balance_set, before knpemi_dg_set_params, and
+ * when no knpemi_dg_balance_record_membrane came since the last record. */
+int knpemi_dg_balance_record(knpemi_dg* h, double t);
+/* As knpemi_observe_read. */
+int knpemi_dg_balance_read(knpemi_dg* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset);
+/* Synchronise and copy out the cell table of the last record: [n_cells][K][mem, cons, pen, drift, m_old, m_new, src, defect].
+ * KNPEMI_EINVAL before the first record and when the recorder was set with want_cells == 0. */
+int knpemi_dg_balance_cells(knpemi_dg* h, double* out);
+/* A new series; a pending knpemi_dg_balance_record_membrane is forgotten.  Enqueue only. */
+int knpemi_dg_balance_reset(knpemi_dg* h);
+/* Drop the recorder (knpemi_dg_balance_record then fails with KNPEMI_EINVAL); knpemi_dg_destroy does the same. */
+int knpemi_dg_balance_clear(knpemi_dg* h);
+
 #ifdef __cplusplus
 }
 #endif

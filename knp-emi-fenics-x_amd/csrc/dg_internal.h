@@ -98,6 +98,109 @@ __device__ __forceinline__ double fast_rsqrt(double a) {
   return y * fma(-0.5 * a * y, y, 1.5);
 }
 
+// -- simplices: the affine geometry of a cell (kernels_dg.hip, kernels_dg_balance.hip)
+template <int NV>
+struct Geo {
+  double g[NV][NV - 1];   // gradients of the barycentric coordinates
+  double vol;
+};
+
+template <int GD>
+__device__ __forceinline__ double dot(const double (&a)[GD], const double (&b)[GD]) {
+  double s = a[0] * b[0];
+#pragma unroll
+  for (int d = 1; d < GD; ++d) s += a[d] * b[d];
+  return s;
+}
+
+template <int NV>
+__device__ __forceinline__ void geometry(const double (&X)[NV][NV - 1], Geo<NV>& G) {
+  if constexpr (NV == 3) {
+    const double e1x = X[1][0] - X[0][0], e1y = X[1][1] - X[0][1];
+    const double e2x = X[2][0] - X[0][0], e2y = X[2][1] - X[0][1];
+    const double det = e1x * e2y - e1y * e2x, inv = fast_rcp(det);
+    G.g[1][0] = e2y * inv; G.g[1][1] = -e2x * inv;
+    G.g[2][0] = -e1y * inv; G.g[2][1] = e1x * inv;
+    G.g[0][0] = -(G.g[1][0] + G.g[2][0]); G.g[0][1] = -(G.g[1][1] + G.g[2][1]);
+    G.vol = 0.5 * fabs(det);
+  } else {
+    double e[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) e[a][d] = X[a + 1][d] - X[0][d];
+    double cr[3][3];   // cr[a] = e[a+1] x e[a+2]
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int b = (a + 1) % 3, c = (a + 2) % 3;
+      cr[a][0] = e[b][1] * e[c][2] - e[b][2] * e[c][1];
+      cr[a][1] = e[b][2] * e[c][0] - e[b][0] * e[c][2];
+      cr[a][2] = e[b][0] * e[c][1] - e[b][1] * e[c][0];
+    }
+    const double det = e[0][0] * cr[0][0] + e[0][1] * cr[0][1] + e[0][2] * cr[0][2], inv = fast_rcp(det);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      G.g[1][d] = cr[0][d] * inv; G.g[2][d] = cr[1][d] * inv; G.g[3][d] = cr[2][d] * inv;
+      G.g[0][d] = -(G.g[1][d] + G.g[2][d] + G.g[3][d]);
+    }
+    G.vol = fabs(det) * (1.0 / 6.0);
+  }
+}
+
+// -- hexahedra: the frame aligned with a facet (kernels_dg_hex.hip says what it is; kernels_dg_balance.hip)
+constexpr double HX_G0 = 0.21132486540518711775, HX_G1 = 0.78867513459481288225;   // 2-point Gauss on [0, 1]
+
+struct Vec3 {
+  double x, y, z;
+};
+__device__ __forceinline__ Vec3 cross(const Vec3& a, const Vec3& b) {
+  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ double dot3(const Vec3& a, const Vec3& b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+
+// tangents, surface element, outward unit normal of T and the depth-frame numbers of T and N at facet point p
+struct FacetFrame {
+  double A, aTs, aTt, cT, aNs, aNt, cN, N[4], ds[4], dt[4];
+};
+__device__ __forceinline__ void hx_shapes(int p, double (&N)[4], double (&ds)[4], double (&dt)[4]) {
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    const double ws = ((m ^ p) & 1) ? HX_G0 : HX_G1, wt = (((m ^ p) >> 1) & 1) ? HX_G0 : HX_G1;
+    N[m] = ws * wt;
+    ds[m] = (m & 1) ? wt : -wt;
+    dt[m] = (m >> 1) ? ws : -ws;
+  }
+}
+__device__ __forceinline__ void hx_frame(int p, const double (&xm)[4][3], const double (&dT)[4][3], const double (&dN)[4][3],
+                                         bool have_n, FacetFrame& F) {
+  hx_shapes(p, F.N, F.ds, F.dt);
+  Vec3 ts{0, 0, 0}, tt{0, 0, 0}, eT{0, 0, 0}, eN{0, 0, 0};
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    ts.x += F.ds[m] * xm[m][0]; ts.y += F.ds[m] * xm[m][1]; ts.z += F.ds[m] * xm[m][2];
+    tt.x += F.dt[m] * xm[m][0]; tt.y += F.dt[m] * xm[m][1]; tt.z += F.dt[m] * xm[m][2];
+    eT.x += F.N[m] * dT[m][0]; eT.y += F.N[m] * dT[m][1]; eT.z += F.N[m] * dT[m][2];
+    eN.x += F.N[m] * dN[m][0]; eN.y += F.N[m] * dN[m][1]; eN.z += F.N[m] * dN[m][2];
+  }
+  const Vec3 cr = cross(ts, tt);
+  const double a2 = dot3(cr, cr), ra = fast_rsqrt(a2);
+  F.A = a2 * ra;
+  const double detT = dot3(cr, eT);
+  const double nu = detT > 0.0 ? -ra : ra;            // n = nu cr points away from T
+  const Vec3 n{nu * cr.x, nu * cr.y, nu * cr.z};
+  const double riT = fast_rcp(detT);
+  F.cT = dot3(cr, n) * riT;
+  F.aTs = dot3(cross(tt, eT), n) * riT;
+  F.aTt = dot3(cross(eT, ts), n) * riT;
+  F.cN = F.aNs = F.aNt = 0.0;
+  if (have_n) {
+    const double riN = fast_rcp(dot3(cr, eN));
+    F.cN = dot3(cr, n) * riN;
+    F.aNs = dot3(cross(tt, eN), n) * riN;
+    F.aNt = dot3(cross(eN, ts), n) * riN;
+  }
+}
+
 // Workgroups are dealt to the 8 XCDs round robin; give every XCD a contiguous run of cells so that the neighbour
 // records a workgroup reads are mostly the ones its XCD's L2 already holds.  Bijection on [0, 8 * chunk).
 __device__ __forceinline__ int dg_block_index(int b, int chunk) { return (b & 7) * chunk + (b >> 3); }
@@ -117,6 +220,33 @@ struct KnDgJump {
 int kn_dg_jump_blocks(int n_cell, int NV);
 // one launch on the owner's main stream: every sub-domain, every field
 int kn_dg_launch_jump(KnDevice* own, const kn_dg::DgDev& D, int NV, int n_sub, int box, const KnDgJump& J);
+
+// The per-cell ion balance (kernels_dg_balance.hip; knpemi_dg_balance_*).  Per cell and ion the table holds KN_DG_BCOLS
+// numbers; dg_balance_membrane_kernel writes mem, m_old and src between the assembly and the solve of the concentrations,
+// dg_balance_flux_kernel the rest at the end of the step, and appends the series row
+//   [n_sub][K][mass, outflow, penalty, defect_max] [n_tag][K j^e | K j^i | capacitive, channel, area].
+#define KN_DG_BCOLS 8                      // mem cons pen drift m_old m_new src defect
+#define KN_DG_BSLOTS 4                     // per sub-domain and ion: sum m_new, sum out, sum |pen|, max |defect|
+#define KN_DG_BTAG (2 * KN_MAXK + 3)       // per membrane tag: j^e and j^i of the KN_MAXK ions, int I_cap, int I_ch,tot, area
+#define KN_DG_MAXTAG 8
+struct KnDgBalance {
+  std::vector<void*> allocs;
+  knpemi_handle::KnSeries ser;         // ctl[2] is the ticket of the flux launch
+  double* cells = nullptr;             // [K][KN_DG_BCOLS][n_cell]: consecutive lanes (cells) write consecutive addresses
+  double* part = nullptr;              // [n_blk][n_sub * K * KN_DG_BSLOTS] workgroup partials of the flux launch
+  double* mpart = nullptr;             // [n_blk][n_tag * KN_DG_BTAG] ... of the membrane launch
+  double* tagtab = nullptr;            // [n_tag * KN_DG_BTAG] the membrane launch's sums, read by the flux launch's row
+  unsigned long long* mctl = nullptr;  // [4]: the ticket of the membrane launch
+  const int* facet_tag = nullptr;      // [n_mem_facets] index into the tags
+  int n_blk = 0, n_tag = 0, want_cells = 0;
+  bool set = false;
+  bool membrane = false;               // a membrane launch came since the last record
+  bool recorded = false;               // the table is complete: a record has been enqueued
+};
+int kn_dg_balance_blocks(int n_cell, int NV);
+struct knpemi_dg;
+int kn_dg_launch_balance_membrane(knpemi_dg* h, int splitting);
+int kn_dg_launch_balance_flux(knpemi_dg* h);
 
 struct knpemi_dg : KnDevice {
   int NV = 0, K = 0, n_sub = 0;
@@ -147,6 +277,8 @@ struct knpemi_dg : KnDevice {
   knpemi_handle::KnEvents events;
   KnDgJump jump;
   bool obs_jump = false;           // the installed observables read `jump.tab`: a record launches dg_jump_kernel first
+  KnDgBalance balance;
+  int knp_flags = 0;               // flags of the last knpemi_dg_assemble_knp: the balance's membrane launch follows its splitting
 };
 void kn_dg_record_free(knpemi_dg* h);   // every recorder's device memory (knpemi_record.hip); knpemi_dg_destroy
 

@@ -38,53 +38,8 @@ namespace {
 
 using namespace kn_dg;
 
-template <int NV>
-struct Geo {
-  double g[NV][NV - 1];   // gradients of the barycentric coordinates
-  double vol;
-};
-
-template <int GD>
-__device__ __forceinline__ double dot(const double (&a)[GD], const double (&b)[GD]) {
-  double s = a[0] * b[0];
-#pragma unroll
-  for (int d = 1; d < GD; ++d) s += a[d] * b[d];
-  return s;
-}
-
-template <int NV>
-__device__ __forceinline__ void geometry(const double (&X)[NV][NV - 1], Geo<NV>& G) {
-  if constexpr (NV == 3) {
-    const double e1x = X[1][0] - X[0][0], e1y = X[1][1] - X[0][1];
-    const double e2x = X[2][0] - X[0][0], e2y = X[2][1] - X[0][1];
-    const double det = e1x * e2y - e1y * e2x, inv = fast_rcp(det);
-    G.g[1][0] = e2y * inv; G.g[1][1] = -e2x * inv;
-    G.g[2][0] = -e1y * inv; G.g[2][1] = e1x * inv;
-    G.g[0][0] = -(G.g[1][0] + G.g[2][0]); G.g[0][1] = -(G.g[1][1] + G.g[2][1]);
-    G.vol = 0.5 * fabs(det);
-  } else {
-    double e[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int d = 0; d < 3; ++d) e[a][d] = X[a + 1][d] - X[0][d];
-    double cr[3][3];   // cr[a] = e[a+1] x e[a+2]
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int b = (a + 1) % 3, c = (a + 2) % 3;
-      cr[a][0] = e[b][1] * e[c][2] - e[b][2] * e[c][1];
-      cr[a][1] = e[b][2] * e[c][0] - e[b][0] * e[c][2];
-      cr[a][2] = e[b][0] * e[c][1] - e[b][1] * e[c][0];
-    }
-    const double det = e[0][0] * cr[0][0] + e[0][1] * cr[0][1] + e[0][2] * cr[0][2], inv = fast_rcp(det);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      G.g[1][d] = cr[0][d] * inv; G.g[2][d] = cr[1][d] * inv; G.g[3][d] = cr[2][d] * inv;
-      G.g[0][d] = -(G.g[1][d] + G.g[2][d] + G.g[3][d]);
-    }
-    G.vol = fabs(det) * (1.0 / 6.0);
-  }
-}
+// (Geo, dot, geometry -- the gradients of the barycentric coordinates -- are in dg_internal.h: kernels_dg_balance.hip takes
+// them too)
 
 // position of every block of the row: the cell itself and the neighbours in increasing cell order
 template <int NV>
@@ -1119,6 +1074,7 @@ extern "C" int knpemi_dg_assemble_knp(knpemi_dg* h, int flags) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_knp: null handle");
   if (!h->have_params) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_assemble_knp: knpemi_dg_set_params has not been called");
   KN_HIP(hipSetDevice(h->device));
+  h->knp_flags = flags;
   return launch_knp(h, flags);
 }
 

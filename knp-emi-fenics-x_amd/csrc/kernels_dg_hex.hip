@@ -48,7 +48,6 @@ constexpr int HX_TASKS = HX_CELLS * HX_NFC;         // (cell, facet) pairs per w
 constexpr int HX_FS_EMI = 49;                       // doubles per facet summary (12 per point, odd pitch)
 constexpr int HX_VG = 25;                           // per volume point: the 8 physical gradients (24) + weight * |det|
 constexpr int HX_SCR = 10;                          // scratch pitch of the block transposition (even: 16-byte reads)
-constexpr double HX_G0 = 0.21132486540518711775, HX_G1 = 0.78867513459481288225;   // 2-point Gauss on [0, 1]
 
 __host__ __device__ constexpr int hx_ax1(int a) { return a == 0 ? 1 : 0; }
 __host__ __device__ constexpr int hx_ax2(int a) { return a == 2 ? 1 : 2; }
@@ -57,14 +56,6 @@ __host__ __device__ constexpr int hx_facet_vertex(int a, int b, int m) {
 }
 // value at a Gauss point of the 1-D shape function of a vertex: the far one (G0) when the bits differ
 __host__ __device__ constexpr double hx_w(int bit) { return bit ? HX_G0 : HX_G1; }
-
-struct Vec3 {
-  double x, y, z;
-};
-__device__ __forceinline__ Vec3 cross(const Vec3& a, const Vec3& b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ double dot3(const Vec3& a, const Vec3& b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
 // position of the row's blocks: the cell itself and its neighbours in increasing cell order
 __device__ __forceinline__ void hx_slots(int T, const int (&nb)[HX_NFC], int& slot_self, int (&slot)[HX_NFC]) {
@@ -79,48 +70,7 @@ __device__ __forceinline__ void hx_slots(int T, const int (&nb)[HX_NFC], int& sl
   }
 }
 
-// tangents, surface element, outward unit normal of T and the depth-frame numbers of T and N at facet point p
-struct FacetFrame {
-  double A, aTs, aTt, cT, aNs, aNt, cN, N[4], ds[4], dt[4];
-};
-__device__ __forceinline__ void hx_shapes(int p, double (&N)[4], double (&ds)[4], double (&dt)[4]) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const double ws = ((m ^ p) & 1) ? HX_G0 : HX_G1, wt = (((m ^ p) >> 1) & 1) ? HX_G0 : HX_G1;
-    N[m] = ws * wt;
-    ds[m] = (m & 1) ? wt : -wt;
-    dt[m] = (m >> 1) ? ws : -ws;
-  }
-}
-__device__ __forceinline__ void hx_frame(int p, const double (&xm)[4][3], const double (&dT)[4][3], const double (&dN)[4][3],
-                                         bool have_n, FacetFrame& F) {
-  hx_shapes(p, F.N, F.ds, F.dt);
-  Vec3 ts{0, 0, 0}, tt{0, 0, 0}, eT{0, 0, 0}, eN{0, 0, 0};
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    ts.x += F.ds[m] * xm[m][0]; ts.y += F.ds[m] * xm[m][1]; ts.z += F.ds[m] * xm[m][2];
-    tt.x += F.dt[m] * xm[m][0]; tt.y += F.dt[m] * xm[m][1]; tt.z += F.dt[m] * xm[m][2];
-    eT.x += F.N[m] * dT[m][0]; eT.y += F.N[m] * dT[m][1]; eT.z += F.N[m] * dT[m][2];
-    eN.x += F.N[m] * dN[m][0]; eN.y += F.N[m] * dN[m][1]; eN.z += F.N[m] * dN[m][2];
-  }
-  const Vec3 cr = cross(ts, tt);
-  const double a2 = dot3(cr, cr), ra = fast_rsqrt(a2);
-  F.A = a2 * ra;
-  const double detT = dot3(cr, eT);
-  const double nu = detT > 0.0 ? -ra : ra;            // n = nu cr points away from T
-  const Vec3 n{nu * cr.x, nu * cr.y, nu * cr.z};
-  const double riT = fast_rcp(detT);
-  F.cT = dot3(cr, n) * riT;
-  F.aTs = dot3(cross(tt, eT), n) * riT;
-  F.aTt = dot3(cross(eT, ts), n) * riT;
-  F.cN = F.aNs = F.aNt = 0.0;
-  if (have_n) {
-    const double riN = fast_rcp(dot3(cr, eN));
-    F.cN = dot3(cr, n) * riN;
-    F.aNs = dot3(cross(tt, eN), n) * riN;
-    F.aNt = dot3(cross(eN, ts), n) * riN;
-  }
-}
+// (the facet-aligned frame -- FacetFrame, hx_shapes, hx_frame -- is in dg_internal.h: kernels_dg_balance.hip takes it too)
 
 // the physical gradients of the 8 basis functions and weight * |det J| of the cell at volume Gauss point p (runtime):
 // out[3 j + d] = d phi_j / d x_d, out[24] = |det| / 8.  Computed once per (cell, point) by the lane whose vertex has the

@@ -1371,6 +1371,7 @@ extern "C" int kn_snapshot_pack_only(knpemi_handle* h, int n) {
 void kn_dg_record_free(knpemi_dg* h) {
   kn_free_all(h->obs.allocs);
   kn_free_all(h->events.allocs);
+  kn_free_all(h->balance.allocs);
 }
 
 namespace {
@@ -1499,3 +1500,93 @@ extern "C" int knpemi_dg_events_reset(knpemi_dg* h) {
 }
 
 extern "C" int knpemi_dg_events_clear(knpemi_dg* h) { return recorder_clear(h, &knpemi_dg::events); }
+
+// ---------------------------------------------------------------------------------------------------
+// the per-cell ion balance of a DG run (kernels_dg_balance.hip)
+// ---------------------------------------------------------------------------------------------------
+extern "C" int knpemi_dg_balance_set(knpemi_dg* h, int capacity, int want_cells, int n_tags, const int32_t* facet_tag) {
+  const std::string fn = "knpemi_dg_balance_set";
+  if (!h) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  const int nmf = h->dev.nq / h->NFV;
+  if (capacity < 1) return kn_fail(KNPEMI_EINVAL, fn + ": capacity must be positive");
+  if (n_tags < 0 || n_tags > KN_DG_MAXTAG) return kn_fail(KNPEMI_EINVAL, fn + ": 0 to " + std::to_string(KN_DG_MAXTAG) + " membrane tags");
+  if (nmf > 0 && (n_tags < 1 || !facet_tag)) return kn_fail(KNPEMI_EINVAL, fn + ": the mesh has membrane facets: a tag index per facet is required");
+  for (int i = 0; i < nmf; ++i)
+    if (facet_tag[i] < 0 || facet_tag[i] >= n_tags)
+      return kn_fail(KNPEMI_EINVAL, fn + ": tag index of membrane facet " + std::to_string(i) + " out of range");
+  KN_HIP(hipSetDevice(h->device));
+  New<KnDgBalance> B;
+  const int K = h->K, ns = h->n_sub * K * KN_DG_BSLOTS;
+  B.n_blk = kn_dg_balance_blocks(h->dev.n_cell, h->NV);
+  B.n_tag = n_tags;
+  B.want_cells = want_cells != 0;
+  int rc;
+  if ((rc = series_alloc(B.allocs, h->stream, capacity, ns + n_tags * (2 * K + 3), &B.ser))
+      || (rc = kn_zeros(B.allocs, h->stream, (size_t)h->dev.n_cell * K * KN_DG_BCOLS, &B.cells))
+      || (rc = kn_zeros(B.allocs, h->stream, (size_t)B.n_blk * ns, &B.part))
+      || (rc = kn_zeros(B.allocs, h->stream, (size_t)B.n_blk * n_tags * KN_DG_BTAG, &B.mpart))
+      || (rc = kn_zeros(B.allocs, h->stream, (size_t)KN_DG_MAXTAG * KN_DG_BTAG, &B.tagtab))
+      || (rc = kn_zeros(B.allocs, h->stream, 4, &B.mctl))
+      || (rc = kn_upload(B.allocs, facet_tag, (size_t)nmf, &B.facet_tag)))
+    return rc;
+  B.set = true;
+  return recorder_install(h, &knpemi_dg::balance, B);
+}
+
+namespace {
+int balance_ready(knpemi_dg* h, const std::string& fn) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (!h->balance.set) return kn_fail(KNPEMI_EINVAL, fn + ": no balance set (knpemi_dg_balance_set)");
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, fn + ": knpemi_dg_set_params has not been called");
+  return KNPEMI_OK;
+}
+}  // namespace
+
+extern "C" int knpemi_dg_balance_record_membrane(knpemi_dg* h) {
+  if (int rc = balance_ready(h, "knpemi_dg_balance_record_membrane")) return rc;
+  KN_HIP(hipSetDevice(h->device));
+  if (int rc = kn_dg_launch_balance_membrane(h, !(h->knp_flags & KNPEMI_NO_SPLITTING))) return rc;
+  h->balance.membrane = true;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_dg_balance_record(knpemi_dg* h, double t) {
+  const std::string fn = "knpemi_dg_balance_record";
+  if (int rc = balance_ready(h, fn)) return rc;
+  if (!h->balance.membrane)
+    return kn_fail(KNPEMI_EINVAL, fn + ": no knpemi_dg_balance_record_membrane since the last record");
+  if (!std::isfinite(t)) return kn_fail(KNPEMI_EINVAL, fn + ": t must be finite");
+  KN_HIP(hipSetDevice(h->device));
+  if (int rc = kn_dg_launch_balance_flux(h)) return rc;
+  h->balance.membrane = false;
+  h->balance.recorded = true;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_dg_balance_read(knpemi_dg* h, int n_rows, double* out, int64_t* rows, int64_t* overflow, int reset) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  return series_read(h, h->balance.ser, h->balance.set, "knpemi_dg_balance_read", "no balance set (knpemi_dg_balance_set)",
+                     n_rows, out, rows, overflow, reset);
+}
+
+extern "C" int knpemi_dg_balance_cells(knpemi_dg* h, double* out) {
+  const std::string fn = "knpemi_dg_balance_cells";
+  if (!h || !out) return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  const KnDgBalance& B = h->balance;
+  if (!B.set) return kn_fail(KNPEMI_EINVAL, fn + ": no balance set (knpemi_dg_balance_set)");
+  if (!B.want_cells) return kn_fail(KNPEMI_EINVAL, fn + ": the balance was set without the cell table (want_cells = 0)");
+  if (!B.recorded) return kn_fail(KNPEMI_EINVAL, fn + ": no record yet (knpemi_dg_balance_record)");
+  KN_HIP(hipSetDevice(h->device));
+  return kn_table_download(h->stream, B.cells, out, h->dev.n_cell, h->K * KN_DG_BCOLS);      // device: [K][columns][n_cell]
+}
+
+extern "C" int knpemi_dg_balance_reset(knpemi_dg* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  KnDgBalance& B = h->balance;
+  if (!B.set) return kn_fail(KNPEMI_EINVAL, "knpemi_dg_balance_reset: no balance set (knpemi_dg_balance_set)");
+  KN_HIP(hipSetDevice(h->device));
+  B.membrane = B.recorded = false;
+  return series_rewind(h, B.ser);
+}
+
+extern "C" int knpemi_dg_balance_clear(knpemi_dg* h) { return recorder_clear(h, &knpemi_dg::balance); }

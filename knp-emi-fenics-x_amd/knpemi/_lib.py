@@ -297,6 +297,14 @@ SIGNATURES = {
     "knpemi_dg_events_read": (C.c_int, [C.c_void_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "knpemi_dg_events_reset": (C.c_int, [C.c_void_p]),
     "knpemi_dg_events_clear": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_balance_set": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p]),
+    "knpemi_dg_balance_record_membrane": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_balance_record": (C.c_int, [C.c_void_p, C.c_double]),
+    "knpemi_dg_balance_read": (C.c_int, [C.c_void_p, C.c_int, c_dbl_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.c_int]),
+    "knpemi_dg_balance_cells": (C.c_int, [C.c_void_p, c_dbl_p]),
+    "knpemi_dg_balance_reset": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_balance_clear": (C.c_int, [C.c_void_p]),
 }
 
 

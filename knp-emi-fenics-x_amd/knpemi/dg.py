@@ -63,8 +63,9 @@ class DGProblem:
         self.cell_sub = cell_subdomains(ct, subdomain_tags)
         self.n_sub = len(subdomain_tags)
         self.mem_facets, self.mem_tags = membrane_facets(mesh, ft, membrane_tags)
-        self.taps = []                                      # the attached recorders (knpemi.recording.Tap): observe, detect
+        self.taps = []                                      # the attached recorders (knpemi.recording.Tap): observe, detect, balance
         self.n_records = 0
+        self.ion_params = None                              # (F, [z_k]) of the last set_params
         self.n_cells = mesh.num_cells
         self.n = self.n_cells * self.nv
         self.nmf = self.mem_facets.shape[0]
@@ -116,6 +117,7 @@ class DGProblem:
             for s in range(self.n_sub):
                 p.rho[s] = val(rho[1][s])
         L.check(self.lib.knpemi_dg_set_params(self.h, C.byref(p)))
+        self.ion_params = (p.F, [p.z[k] for k in range(self.K)])
 
     def _set(self, field, idx, a, n):
         a = np.ascontiguousarray(a, np.float64).reshape(-1)
@@ -303,6 +305,31 @@ class DGProblem:
         self.taps.append(("detect", Tap(ev, "DG membrane events", every,
                                         lambda t, f: L.check(lib.knpemi_dg_events_record(h, float(t))), t0, rewind=rewind)))
 
+    def balance(self, bal, every=1, capacity=1024, t0=0.0, want_cells=True):
+        """Record the per-cell ion balance `bal` (knpemi.dg_balance.DGIonBalance) on the device at every `every`-th call of
+        `record(t)`.  A recorded step takes two launches on the handle's stream, nothing synchronised: `record_membrane()`
+        between `assemble_knp` and the solve of the concentrations, and the record itself at the end of the step.  Rows
+        drain as those of `observe`; `bal.cells()` reads the cell table of the last record (want_cells=False: no table)."""
+        from .recording import Tap
+        lib, h = self.lib, self.h
+        self._may_attach("balance", every, capacity, "this problem records an ion balance already")
+
+        def read(n, buf):
+            rows, over = C.c_int64(), C.c_int64()
+            L.check(lib.knpemi_dg_balance_read(h, n, None if buf is None else L.dptr(buf), C.byref(rows), C.byref(over), 1))
+            return rows.value, over.value
+        bal._attach(self, capacity, want_cells)
+        self.taps.append(("balance", Tap(bal, "DG ion balance", every, lambda t, f: L.check(lib.knpemi_dg_balance_record(h, float(t))),
+                                         t0, capacity=capacity, read=read, n_cols=bal.n_cols,
+                                         rewind=lambda: L.check(lib.knpemi_dg_balance_reset(h)))))
+
+    def record_membrane(self):
+        """Between `assemble_knp` and the solve of the concentrations: the first launch of the ion balance, when one is
+        attached and the next `record(t)` is a record of it; nothing otherwise."""
+        for name, tap in self.taps:
+            if name == "balance" and tap.enabled and (self.n_records + 1 + tap.offset) % tap.every == 0:
+                L.check(self.lib.knpemi_dg_balance_record_membrane(self.h))
+
     def record(self, t):
         """One record at time t (the end of a step, after `update`): every attached recorder that is due enqueues its
         launch."""
@@ -371,6 +398,9 @@ class DGSlab:
 
     def detect(self, *args, **kwargs):
         raise NotImplementedError(self._NO_RECORDS.format("detect"))
+
+    def balance(self, *args, **kwargs):
+        raise NotImplementedError(self._NO_RECORDS.format("balance"))
 
     def attach(self):
         from .fem.transport import Transport, dg_endpoint

@@ -1,7 +1,9 @@
 """Times one record of the DG recorders on the idealized 3D meshes of tools/dg_time.py: the observe launch alone (points,
 reductions over both sub-domains, a membrane point), the jump launch (dg_jump_kernel: every sub-domain, all K + 1 fields) and
 the events launch, beside the two assembly kernels of a DG step measured in the same process, and the bytes the jump kernel
-must move.  Prints one JSON line per mesh; --out appends them to a file.
+must move; and the two launches of the per-cell ion balance (knpemi.dg_balance): the membrane launch alone, the pair of a
+record, the bytes each must move, and a step of the device's own work (both assemblies, the update) with and without them.
+Prints one JSON line per mesh; --out appends them to a file.
 
     python tools/dg_record_time.py [-r 1] [-l 2] [--reps 50] [--out profiles/dg_record.json]
 """
@@ -22,6 +24,70 @@ def jump_bytes(dp):
     nfc = 6 if dp.nv == 8 else dp.nv
     tasks = dp.n_cells * nfc
     return dp.n * 64 + tasks * 8 + dp.n_cells + (tasks + 255) // 256 * dp.n_sub * 5 * 8
+
+
+def balance_bytes(dp, which):
+    """HBM bytes one launch of the ion balance must move (which = 0: membrane launch, 1: flux launch): every dof record
+    once, the facet tables, the cells' sub-domains, and its columns of the cell table (64 bytes per cell and ion: the
+    membrane launch writes 3 of the 8 doubles, the flux launch reads those and writes the other 5)."""
+    nfc = 6 if dp.nv == 8 else dp.nv
+    tasks = dp.n_cells * nfc
+    if which == 0:
+        return dp.n * 64 + tasks * 4 + dp.nmf * 2 * 8 + dp.n_cells + dp.n_cells * dp.K * 24 + dp.nmf * dp.nf * (dp.K + 1) * 8
+    return dp.n * 64 + tasks * 8 + dp.n_cells + dp.n_cells * dp.K * 64 + (dp.n_cells * 24 if dp.nv == 8 else 0)
+
+
+def balance_times(dp, mesh, ct, ft, reps):
+    """Microseconds of the membrane launch alone, of the pair of a record, and of a step of the device's own work without
+    the solves (both assemblies, the end-of-step update on a device buffer) with and without the two launches in it."""
+    import numpy as np
+    import torch
+    from knpemi import _lib as L
+    from knpemi.dg_balance import DGIonBalance
+    bal = DGIonBalance(mesh, ct, ft, [0, 1], [1], ["Na", "K", "Cl"])
+    dp.balance(bal, capacity=4 * reps + 8)
+    c = torch.tensor(np.stack([dp.get_concentration(k).ravel() for k in range(dp.K - 1)]), device=f"cuda:{dp.device}")
+    torch.cuda.synchronize()
+
+    def timed(body):
+        body(0)
+        dp.sync()
+        t0 = time.perf_counter()
+        for k in range(reps):
+            body(1 + k)
+        dp.sync()
+        return (time.perf_counter() - t0) / reps * 1e6
+
+    def membrane(k):
+        L.check(dp.lib.knpemi_dg_balance_record_membrane(dp.h))
+
+    def pair(k):
+        dp.record_membrane()
+        dp.record(float(k))
+
+    def step(recorded):
+        def body(k):
+            dp.assemble_emi()
+            dp.assemble_knp()
+            if recorded:
+                dp.record_membrane()
+            dp.update_device(c.data_ptr())
+            if recorded:
+                dp.record(float(k))
+        return body
+    out = dict(balance_membrane_us=timed(membrane))
+    dp.reset_recorders()
+    out["balance_pair_us"] = timed(pair)
+    dp.reset_recorders()
+    # alternate the two versions of the step, twice: the spread between equal runs is part of the result
+    plain, recorded = [], []
+    for _ in range(2):
+        plain.append(timed(step(False)))
+        dp.reset_recorders()
+        recorded.append(timed(step(True)))
+        dp.reset_recorders()
+    out.update(step_us=plain, step_recorded_us=recorded)
+    return out
 
 
 def per_record_us(dp, reps):
@@ -71,6 +137,11 @@ def measure(cell, general, r, l, reps):
                        emi_kernel_us=dp.time_kernel(0, 20) * 1e3, knp_kernel_us=dp.time_kernel(1, 20) * 1e3,
                        jump_bytes=jump_bytes(dp))
         del dp
+    dp = init_fields(DGProblem(mesh, ct, ft, [0, 1], [1]))
+    out.update(balance_times(dp, mesh, ct, ft, reps))
+    out.update(balance_membrane_bytes=balance_bytes(dp, 0), balance_flux_bytes=balance_bytes(dp, 1))
+    out["balance_flux_us"] = out["balance_pair_us"] - out["balance_membrane_us"]
+    del dp
     out.update(observe_us=times["observe"], jump_us=times["observe+jump"] - times["observe"], events_us=times["events"])
     out["jump_GBps"] = out["jump_bytes"] / max(out["jump_us"], 1e-9) / 1e3
     out["jump_over_assembly"] = out["jump_us"] / (out["emi_kernel_us"] + out["knp_kernel_us"])
@@ -84,6 +155,7 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    import torch  # noqa: F401  (before the library is loaded, as bench.py does: the process then has one HIP runtime)
     for cell, general in (("tetrahedron", False), ("hexahedron", False), ("hexahedron", True)):
         line = json.dumps(measure(cell, general, a.r, a.l, a.reps))
         print(line, flush=True)
