@@ -1241,11 +1241,6 @@ __device__ __forceinline__ void knp_membrane_block(const KnDev& D, const KnConst
                                                    const double* __restrict__ phi_x, double* qt) {
   const int nq = D.nq_gamma;
   const int ntab = nq * (1 + NF + (NF == 4 ? 2 * NF : 0));
-  for (int i = threadIdx.x; i < ntab; i += blockDim.x) qt[i] = D.qtab[i];
-  __syncthreads();
-  const double* qw = qt;
-  const double* qN = qt + nq;
-  const double* qdN = qt + nq * (1 + NF);
   const int gt = bid * blockDim.x + threadIdx.x;
   const int t = gt / KN_MEM_LQ, lq = gt % KN_MEM_LQ;
   // lanes past the last (facet, side) repeat the last one and drop their results: the shuffles below see whole groups
@@ -1254,16 +1249,28 @@ __device__ __forceinline__ void knp_membrane_block(const KnDev& D, const KnConst
   const int KS = C.K - 1;
   const int fg = tt >> 1;
   const bool cell_side = tt & 1;
+  // Two memory round trips before the quadrature.  The first: everything whose address the thread index gives -- the table,
+  // the facet's model and indices, the entries its integrals go to.  The second: the facet's data, for every facet -- one
+  // without a model loads with slot 0 (always allocated) and drops what it loaded -- issued before the barrier that
+  // publishes the table, so that the barrier is not a third.
   const int ms = D.fmodel[fg];
-  const int* pos = D.gam_pos + (size_t)tt * NF;   // entry of (facet, side, local vertex) in the membrane row lists
+  const FacetIdx<NF> ix = load_facet_idx<NF>(D, fg);
+  int pos[NF];   // entry of (facet, side, local vertex) in the membrane row lists
+#pragma unroll
+  for (int a = 0; a < NF; ++a) pos[a] = D.gam_pos[(size_t)tt * NF + a];
+  for (int i = threadIdx.x; i < ntab; i += blockDim.x) qt[i] = D.qtab[i];
+  FacetData<NF> f;
+  load_facet<NF>(D, C, ix, cell_side, ms < 0 ? 0 : ms, f, phi_x);
+  __syncthreads();
+  const double* qw = qt;
+  const double* qN = qt + nq;
+  const double* qdN = qt + nq * (1 + NF);
   double acc[NF][KN_MAXK - 1];
 #pragma unroll
   for (int a = 0; a < NF; ++a)
 #pragma unroll
     for (int k = 0; k < KN_MAXK - 1; ++k) acc[a][k] = 0.0;
   if (ms >= 0) {
-    FacetData<NF> f;
-    load_facet<NF>(D, C, fg, cell_side, ms, f, phi_x);
     for (int q = lq; q < nq; q += KN_MEM_LQ) {
       double fk[KN_MAXK - 1];
       facet_point<NF>(f, C, q, qw, qN, qdN, splitting, fk);
@@ -1348,26 +1355,32 @@ __global__ __launch_bounds__(256) void knp_membrane_pre_kernel(KnDev D, const Kn
   extern __shared__ double qt[];
   const int nq = D.nq_gamma;
   const int ntab = nq * (1 + NF + (NF == 4 ? 2 * NF : 0));
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  // as in knp_membrane_block: what the thread index addresses beside the table, the facet's data before the barrier
+  const bool live = t < 2 * D.nftot;
+  const int tt = live ? t : 2 * D.nftot - 1;
+  const int KS = C.K - 1, GS = (1 + NF) * KS;
+  const int fg = tt >> 1;
+  const bool cell_side = tt & 1;
+  const int ms = D.fmodel[fg];
+  const FacetIdx<NF> ix = load_facet_idx<NF>(D, fg);
+  int pos[NF];
+#pragma unroll
+  for (int a = 0; a < NF; ++a) pos[a] = D.gam_pos[(size_t)tt * NF + a];
   for (int i = threadIdx.x; i < ntab; i += blockDim.x) qt[i] = D.qtab[i];
+  FacetData<NF> f;
+  load_facet<NF>(D, C, ix, cell_side, ms < 0 ? 0 : ms, f);
   __syncthreads();
   const double* qw = qt;
   const double* qN = qt + nq;
   const double* qdN = qt + nq * (1 + NF);
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 2 * D.nftot) return;
-  const int KS = C.K - 1, GS = (1 + NF) * KS;
-  const int fg = t >> 1;
-  const bool cell_side = t & 1;
-  const int ms = D.fmodel[fg];
-  const int* pos = D.gam_pos + (size_t)t * NF;
+  if (!live) return;
   if (ms < 0) {
 #pragma unroll
     for (int a = 0; a < NF; ++a)
       for (int j = 0; j < GS; ++j) D.gpre[(size_t)GS * pos[a] + j] = 0.0;
     return;
   }
-  FacetData<NF> f;
-  load_facet<NF>(D, C, fg, cell_side, ms, f);
   double P[NF][KN_MAXK - 1], W[NF][NF][KN_MAXK - 1];
 #pragma unroll
   for (int a = 0; a < NF; ++a)

@@ -20,6 +20,16 @@ __device__ __forceinline__ Rec load_rec(const double* __restrict__ VR, int v) {
   return r;
 }
 
+// the record without its last component (phi is left unset)
+__device__ __forceinline__ Rec load_rec_nophi(const double* __restrict__ VR, int v) {
+  const double4* p = reinterpret_cast<const double4*>(VR) + 2 * (size_t)v;
+  const double4 a = p[0];
+  const double2 b = *reinterpret_cast<const double2*>(p + 1);
+  Rec r;
+  r.x = a.x; r.y = a.y; r.z = a.z; r.c[0] = b.x; r.c[1] = b.y; r.c[2] = VR[(size_t)v * KN_REC + 6]; r.c[3] = a.w;
+  return r;
+}
+
 // measure of a simplex facet: the length of an interval, the area of a triangle
 template <int NF>
 __device__ __forceinline__ double facet_measure(const Rec (&p)[NF]) {
@@ -60,20 +70,41 @@ struct FacetData {
   bool cell_side;
 };
 
-// phi_x != NULL: the potential is taken from that vector (one value per vertex, e.g. the solver's solution before it is
-// written into the records -- a constant shift of it cancels in the jump) instead of the records' component 7
+// The indices of a facet -- the vertices of its two sides and its Q dofs.  They depend on the facet alone, so a caller
+// that knows its facet early (knp_membrane_block) fetches them beside its other first loads and the facet's data are one
+// memory round trip behind them, not two.
 template <int NF>
-__device__ __forceinline__ void load_facet(const KnDev& D, const KnConsts& C, int fg, bool cell_side, int ms,
-                                           FacetData<NF>& f, const double* __restrict__ phi_x = nullptr) {
-  const int K = C.K;
-  int si = 0;  // sub-domain of the cell side of this facet
+struct FacetIdx { int vi[NF], ve[NF], q[NF]; };
+
+template <int NF>
+__device__ __forceinline__ FacetIdx<NF> load_facet_idx(const KnDev& D, int fg) {
+  FacetIdx<NF> ix;
 #pragma unroll
   for (int bb = 0; bb < NF; ++bb) {
-    const int vi = D.fi[(size_t)fg * NF + bb], ve = D.fe[(size_t)fg * NF + bb];
-    f.pe[bb] = load_rec(D.VR, ve);
-    f.pi[bb] = load_rec(D.VR, vi);
-    if (phi_x) { f.pe[bb].phi = phi_x[ve]; f.pi[bb].phi = phi_x[vi]; }
-    const int q = D.fq[(size_t)fg * NF + bb];
+    ix.vi[bb] = D.fi[(size_t)fg * NF + bb];
+    ix.ve[bb] = D.fe[(size_t)fg * NF + bb];
+    ix.q[bb] = D.fq[(size_t)fg * NF + bb];
+  }
+  return ix;
+}
+
+// phi_x != NULL: the potential is taken from that vector (one value per vertex, e.g. the solver's solution before it is
+// written into the records -- a constant shift of it cancels in the jump) instead of the records' component 7.
+// ms: a model slot in range (a caller that loads for a facet without a model passes slot 0 and drops the result).
+template <int NF>
+__device__ __forceinline__ void load_facet(const KnDev& D, const KnConsts& C, const FacetIdx<NF>& ix, bool cell_side, int ms,
+                                           FacetData<NF>& f, const double* __restrict__ phi_x = nullptr) {
+  const int K = C.K;
+#pragma unroll
+  for (int bb = 0; bb < NF; ++bb) {
+    const int vi = ix.vi[bb], ve = ix.ve[bb];
+    // the potential through a chosen address, not loaded with the record and overwritten: the dead half of that 16-byte
+    // load would be a register the compiler reuses at once, and waits for the load to do so
+    f.pe[bb] = load_rec_nophi(D.VR, ve);
+    f.pi[bb] = load_rec_nophi(D.VR, vi);
+    f.pe[bb].phi = *(phi_x ? phi_x + ve : D.VR + (size_t)ve * KN_REC + 7);
+    f.pi[bb].phi = *(phi_x ? phi_x + vi : D.VR + (size_t)vi * KN_REC + 7);
+    const int q = ix.q[bb];
     f.pm[bb] = D.phiM[q];
     const double* ich = D.Ich + (size_t)ms * KN_MAXK * D.NQtot + q;
     double it = 0.0;
@@ -83,13 +114,21 @@ __device__ __forceinline__ void load_facet(const KnDev& D, const KnConsts& C, in
       it += f.Ik[bb][k];
     }
     f.It[bb] = it;
-    if (bb == 0) for (int tt = 1; tt < C.n_sub; ++tt) si += vi >= C.voff[tt];
   }
+  int si = 0;  // sub-domain of the cell side of this facet
+  for (int tt = 1; tt < C.n_sub; ++tt) si += ix.vi[0] >= C.voff[tt];
   f.so = &C.sc[cell_side ? si : 0];
   f.meas = 0.0;
   if constexpr (NF != 4) f.meas = facet_measure<NF>(f.pe);
   f.sgn = cell_side ? 1.0 : -1.0;
   f.cell_side = cell_side;
+}
+
+// the same by the facet's number, for the callers that learn it late: indices, then data
+template <int NF>
+__device__ __forceinline__ void load_facet(const KnDev& D, const KnConsts& C, int fg, bool cell_side, int ms,
+                                           FacetData<NF>& f, const double* __restrict__ phi_x = nullptr) {
+  load_facet<NF>(D, C, load_facet_idx<NF>(D, fg), cell_side, ms, f, phi_x);
 }
 
 // The fields of the integrand at quadrature point q of one (facet, side): the own side's concentrations cq, the channel
