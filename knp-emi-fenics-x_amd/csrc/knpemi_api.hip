@@ -231,8 +231,23 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
   std::vector<int> q2e(NQtot), q2i(NQtot);
   std::vector<std::pair<int, int>> coup;  // (row, col)
   std::vector<std::pair<int, int>> ment;  // (row, facet*8 + a)
+  // does one cell hold all NF vertices fv[0..NF)?  (global vertex ids: the cells at an ECS vertex are ECS cells, those at
+  // a vertex of sub-domain s cells of s, so the vertex range names the side)
+  auto one_cell_holds = [&](const int* fv) {
+    for (int a = 1; a < NF; ++a)
+      if (std::find(fv, fv + a, fv[a]) != fv + a) return false;      // a repeated vertex: no facet at all
+    for (int64_t p = v2c_ptr[fv[0]]; p < v2c_ptr[fv[0] + 1]; ++p) {
+      const int* cv = &cells[(size_t)(v2c[p] >> 3) * NV];
+      int found = 1;
+      for (int a = 1; a < NF; ++a) found += std::find(cv, cv + NV, fv[a]) != cv + NV;
+      if (found == NF) return true;
+    }
+    return false;
+  };
   for (int s = 1; s < S; ++s) {
     for (int q = 0; q < h->n_q[s]; ++q) {
+      if (d->q_to_e[s][q] < 0 || d->q_to_e[s][q] >= h->n_vert[0] || d->q_to_i[s][q] < 0 || d->q_to_i[s][q] >= h->n_vert[s])
+        return kn_fail(KNPEMI_EINVAL, "membrane vertex index out of range");
       q2e[h->qoff[s] + q] = d->q_to_e[s][q] + h->voff[0];
       q2i[h->qoff[s] + q] = d->q_to_i[s][q] + h->voff[s];
     }
@@ -250,6 +265,15 @@ extern "C" int knpemi_create(const knpemi_problem_desc* d, int device, knpemi_ha
         fi[(size_t)fg * NF + a] = i + h->voff[s];
         fq[(size_t)fg * NF + a] = q + h->qoff[s];
       }
+      // a membrane facet of s is a facet of an ECS cell and of a cell of s.  That its vertices exist on both sides does
+      // not say so: a facet between two cells has them on both sides wherever they lie on the rim of the contact, and
+      // would couple ECS rows to a membrane that no ECS cell touches.
+      if (!one_cell_holds(&fe[(size_t)fg * NF]))
+        return kn_fail(KNPEMI_EINVAL, "knpemi_create: membrane facet " + std::to_string(f) + " of sub-domain " +
+                                          std::to_string(s) + " is not a facet of an ECS cell");
+      if (!one_cell_holds(&fi[(size_t)fg * NF]))
+        return kn_fail(KNPEMI_EINVAL, "knpemi_create: membrane facet " + std::to_string(f) + " of sub-domain " +
+                                          std::to_string(s) + " is not a facet of a cell of that sub-domain");
       for (int a = 0; a < NF; ++a) {
         ment.emplace_back(fe[(size_t)fg * NF + a], fg * 8 + a);
         ment.emplace_back(fi[(size_t)fg * NF + a], fg * 8 + a);

@@ -42,6 +42,31 @@ def _ptr_array(arrays, ctype):
     return arr
 
 
+def check_membrane_facets(mesh, subdomain_list):
+    """A membrane facet of sub-domain s is a facet of one ECS cell and of one cell of s.  Looking its vertices up in both
+    sub-meshes (flatten_problem) does not prove that: a tagged facet between two cells passes whenever all its vertices
+    lie on the rim of the contact, where the ECS has them too -- and would couple ECS rows to a membrane that no ECS cell
+    touches.  So the cells of every parent facet are asked for their tags; the refusal names the facet and the tags."""
+    tags = list(subdomain_list.keys())
+    cell_tag = np.full(mesh.num_cells, -1, np.int64)
+    for t in tags:
+        cell_tag[subdomain_list[t]["mesh_sub"].parent_entities] = t
+    ptr, f2c, _ = mesh.facet_cells()
+    for t in tags[1:]:
+        pf = np.asarray(subdomain_list[t]["mesh_mem"].parent_entities, np.int64)
+        two = ptr[pf + 1] - ptr[pf] == 2
+        first, second = np.full(len(pf), -1, np.int64), np.full(len(pf), -1, np.int64)
+        first[two] = cell_tag[f2c[ptr[pf[two]]]]
+        second[two] = cell_tag[f2c[ptr[pf[two]] + 1]]
+        bad = np.flatnonzero(~two | (np.minimum(first, second) != 0) | (np.maximum(first, second) != t))
+        if len(bad):
+            f = int(pf[bad[0]])
+            found = [int(cell_tag[c]) for c in f2c[ptr[f]:ptr[f + 1]]]
+            raise RuntimeError(f"membrane facet {f} of sub-domain {t} is not shared by an ECS cell and a cell of "
+                               f"sub-domain {t}: its cells carry the tags {found} ({len(bad)} such facets; "
+                               "Facet is assumed to be an interior facet, utils.py:46)")
+
+
 def flatten_problem(mesh, ft, subdomain_list):
     """Plain-array description of the problem (the contents of knpemi_problem_desc).
 
@@ -62,6 +87,7 @@ def flatten_problem(mesh, ft, subdomain_list):
             raise ValueError("sub-mesh cell type differs from the parent mesh")
         out["x"].append(np.ascontiguousarray(m.x, np.float64))
         out["cells"].append(np.ascontiguousarray(m.cells, np.int32))
+    check_membrane_facets(mesh, subdomain_list)
     for sd in subs[1:]:
         mem = sd["mesh_mem"]
         ics = sd["mesh_sub"]

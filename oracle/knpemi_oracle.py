@@ -213,6 +213,25 @@ class OracleProblem:
             fv = facets[sel]
             ftag = facet_tags[sel]
             qv = np.unique(fv)
+            # A membrane facet of `tag` is a facet of exactly one ECS cell and of exactly one cell of `tag`.  That its
+            # vertices exist on both sides (below) does not say so: a tagged facet between two cells has them on both
+            # sides wherever they lie on the rim of the contact.  Count, per tagged facet, the cells of each side that
+            # hold all its vertices (facet x vertex incidence times vertex x cell incidence).
+            if fv.shape[0]:
+                nf = fv.shape[1]
+                inc_f = sp.csr_matrix((np.ones(fv.size), (np.repeat(np.arange(fv.shape[0]), nf), fv.ravel())),
+                                      shape=(fv.shape[0], x.shape[0]))
+                for side in (0, tag):
+                    sel_c = cells[cell_tags == side]
+                    inc_c = sp.csr_matrix((np.ones(sel_c.size), (np.repeat(np.arange(sel_c.shape[0]), sel_c.shape[1]),
+                                                                 sel_c.ravel())), shape=(sel_c.shape[0], x.shape[0]))
+                    common = (inc_f @ inc_c.T).tocsr()
+                    holders = np.asarray((common == nf).sum(axis=1)).ravel() if common.nnz else np.zeros(fv.shape[0], int)
+                    bad = np.flatnonzero(holders != 1)
+                    if bad.size:
+                        raise ValueError(f"membrane facet {int(bad[0])} of sub-domain {tag} (vertices "
+                                         f"{fv[bad[0]].tolist()}) is a facet of {int(holders[bad[0]])} cells tagged {side}, "
+                                         f"not of one ({bad.size} such facets)")
             for side in (0, tag):  # every membrane vertex exists on both sides
                 assert np.all(np.isin(qv, self.sub[side]["pv"]))
             self.mem[tag] = dict(
