@@ -5,6 +5,7 @@ membrane ODEs at the facet nodes, both assemblies, both linear solves (CG / BiCG
 from the CSR the kernels fill instead.
 
     python run_2D_dg.py [--resolution 1] [--steps 100] [--host-solves] [--series s.npz] [--events e.npz] [--balance b.npz]
+                        [--snapshots DIR [--save-every N] [--snapshot-form vertex|broken|cell_mean]]
 
 `--series` records on the device, at the end of every step, phi and the ions at the ECS and ICS points of run_2D.py's
 `--series`, phi_M and the traces at its membrane point, the maximum and the average of K in the ECS and the jump seminorms
@@ -12,6 +13,10 @@ of phi and of K in both sub-domains (`knpemi.dg_recording.DGObservables`); `--ev
 membrane node (`DGMembraneEvents`, re-armed 20 mV below, the latest 8 times kept); `--balance` the per-cell ion balance
 (`knpemi.dg_balance.DGIonBalance`): per sub-domain and ion the mass, the summed outflow, the penalty share and the largest
 conservation defect, per membrane tag the ion transfer on both sides and the currents, and the cell table of the last step.
+`--snapshots DIR` saves the fields every `--save-every` steps without stopping the run (`knpemi.dg_snapshots.DGSnapshots`):
+phi and every ion per sub-domain and phi_M of the membrane, packed on the device in the form `--snapshot-form` -- "vertex"
+(one value per mesh vertex, the layout of the reference's results_sub_<tag>.xdmf / results_mem_<tag>.xdmf), "broken" (every
+dof, on the exploded mesh) or "cell_mean" -- into DIR/step_%06d.npz and, for the two nodal forms, XDMF time series.
 
 `--cell-type quadrilateral` is parsed, as in run_2D.py, and refused with the DG module's message: the DG variant has no
 quadrilateral kernels.
@@ -34,6 +39,7 @@ from knpemi import _lib as L                                       # noqa: E402
 from knpemi.dg import DGProblem                                    # noqa: E402
 from knpemi.dg_balance import DGIonBalance                         # noqa: E402
 from knpemi.dg_recording import DGMembraneEvents, DGObservables    # noqa: E402
+from knpemi.dg_snapshots import DGSnapshots, DGXdmfSink, NpzSink   # noqa: E402
 from knpemi.fem.idealized import make_mesh_2D                      # noqa: E402
 
 
@@ -51,11 +57,14 @@ EVENT_THRESHOLD = -20e-3                                           # run_2D.py: 
 
 class DGRun:
     def __init__(self, resolution=1, g_syn=10.0, dt=DT, device_solves=True, rtol=(1e-5, 1e-7), cell_type="triangle",
-                 series=None, events=None, balance=None):
-        """series / events / balance: paths of the .npz files `save` writes (None: not recorded)."""
+                 series=None, events=None, balance=None, snapshots=None, save_every=1, snapshot_form="vertex", sinks=None):
+        """series / events / balance: paths of the .npz files `save` writes (None: not recorded).  snapshots: the directory
+        of the field files (None: no fields saved), one frame every `save_every` steps in the form `snapshot_form`; sinks:
+        the sinks to use instead of the files (a list; `snapshots` may then be any true value)."""
         self.device_solves, self.rtol, self.iterations = device_solves, rtol, []
         self.series, self.events, self.obs, self.ev = series, events, None, None
         self.balance, self.bal = balance, None
+        self.snap = None
         mesh, ct, ft = make_mesh_2D(resolution, cell_type=cell_type)      # quadrilaterals: DGProblem refuses them
         self.dp = dp = DGProblem(mesh, ct, ft, [0, 1], [1])
         self.ions = [dict(name="K", z=1.0, D=[D_K] * 2), dict(name="Cl", z=-1.0, D=[D_CL] * 2), dict(name="Na", z=1.0, D=[D_NA] * 2)]
@@ -98,6 +107,14 @@ class DGRun:
         if balance:
             self.bal = DGIonBalance(mesh, ct, ft, [0, 1], [1], [i["name"] for i in self.ions])
             dp.balance(self.bal)
+        if snapshots:
+            self.snap = snap = DGSnapshots(mesh, ct, ft, [0, 1], [1], [i["name"] for i in self.ions])
+            snap.watch_results(form=snapshot_form)
+            if sinks is None:
+                sinks = [NpzSink(snapshots)] + ([] if snapshot_form == "cell_mean" else [DGXdmfSink(snap, snapshots)])
+            for s in sinks:
+                snap.add_sink(s)
+            dp.snapshot(snap, every=save_every)           # behind the other recorders: attached last
 
     def step(self):
         dp = self.dp
@@ -129,6 +146,8 @@ class DGRun:
             self.ev.save(self.events)
         if self.bal is not None:
             self.bal.save(self.balance)
+        if self.snap is not None:
+            self.snap.close()
 
 
 def build_parser():
@@ -140,13 +159,16 @@ def build_parser():
     ap.add_argument("--series", metavar="PATH", default=None, help="time series of the observables and jump seminorms (.npz)")
     ap.add_argument("--events", metavar="PATH", default=None, help="membrane events per membrane node (.npz)")
     ap.add_argument("--balance", metavar="PATH", default=None, help="per-cell ion balance: series and last cell table (.npz)")
+    ap.add_argument("--snapshots", metavar="DIR", default=None, help="field files: step_%%06d.npz and XDMF time series")
+    ap.add_argument("--save-every", type=int, default=1, help="steps between two saved frames")
+    ap.add_argument("--snapshot-form", choices=["vertex", "broken", "cell_mean"], default="vertex")
     return ap
 
 
 if __name__ == "__main__":
     a = build_parser().parse_args()
     run = DGRun(a.resolution, device_solves=not a.host_solves, cell_type=a.cell_type, series=a.series, events=a.events,
-                balance=a.balance)
+                balance=a.balance, snapshots=a.snapshots, save_every=a.save_every, snapshot_form=a.snapshot_form)
     for k in range(a.steps):
         run.step()
         if (k + 1) % 10 == 0:

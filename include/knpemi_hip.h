@@ -1178,6 +1178,56 @@ int knpemi_dg_balance_reset(knpemi_dg* h);
 /* Drop the recorder (knpemi_dg_balance_record then fails with KNPEMI_EINVAL); knpemi_dg_destroy does the same. */
 int knpemi_dg_balance_clear(knpemi_dg* h);
 
+/* Field snapshots of a DG run (knpemi.dg_snapshots.DGSnapshots): the frames, the ring, the copy stream and the rules of
+ * knpemi_snapshot_* above, on the fields of a DG handle.  A DG field is broken -- a mesh vertex carries one dof per cell that
+ * touches it -- so a watch also names a FORM, and a space is (sub-domain or membrane tag, form):
+ *   KNPEMI_DG_SNAP_BROKEN     bulk: one value per dof (cell, local vertex), in the cell order of the sub-domain; membrane: one
+ *                             per membrane node (facet, a) of the tag;
+ *   KNPEMI_DG_SNAP_CELL_MEAN  bulk only: one value per cell, the nodal values summed in local-vertex order 0 .. nv - 1 and
+ *                             divided by nv (the integral mean on simplices and on parallelepiped hexahedra);
+ *   KNPEMI_DG_SNAP_VERTEX     one value per mesh vertex the space touches, in increasing vertex id: the coincident dofs
+ *                             (membrane: the nodes of the tag at that vertex) summed in increasing order and divided by
+ *                             their number -- what results_sub_<tag>.xdmf / results_mem_<tag>.xdmf of the reference hold
+ *                             (run_stim_duration.py:52-90).
+ * A sum starts from its first entry; then additions in list order and one IEEE double division: a frame is a bit-exact
+ * function of the fields.
+ * A watch is spec[w] = {quantity, tag, ion-or-state, form, dtype}: KNPEMI_DG_C (ion < K, the eliminated one last) and
+ * KNPEMI_DG_PHI over sub-domain index `tag`; KNPEMI_DG_PHI_M, KNPEMI_DG_I_CH (ion < K) and KNPEMI_DG_ODE_STATE (a state
+ * column of the table bound with knpemi_dg_ode_bind) over the membrane tag with index `tag`; dtype 0 stores the double,
+ * KNPEMI_SNAPSHOT_F32 (float)v.  The handle knows neither the tags of the membrane facets nor the mesh vertices, so the
+ * caller gives the spaces: space[p] = {kind (0: cells of a sub-domain, 1: a membrane tag), tag, form, n_items} and the list
+ * list[list_off[p] .. list_off[p + 1]) -- broken: the n_items dofs (nodes); cell_mean: the n_items cells; vertex: vptr
+ * [n_items + 1] (vptr[0] = 0, increasing) followed by the vptr[n_items] dofs (nodes), ascending within a vertex.  Every
+ * entry is checked against the fields' lengths.  Selection j belongs to space sel_space[j] (an index into `space`) and
+ * lists ascending distinct items, as in knpemi_snapshot_set.  Frame layout as there; knpemi_dg_snapshot_layout reports it.
+ * The first call creates the copy stream and the ring (knpemi_dg_create does not).  A refused call names the reason
+ * (KNPEMI_EINVAL: null arguments, an unknown quantity, form or dtype, a watch whose (kind, tag, form) is no given space, an
+ * ion or state out of range, a state watch before knpemi_dg_ode_bind, a watch or space listed twice, a list entry out of
+ * range, a bad selection, depth < 1, too many watches or spaces) and leaves the previous recorder recording. */
+#define KNPEMI_DG_ODE_STATE 6
+#define KNPEMI_DG_SNAP_BROKEN 0
+#define KNPEMI_DG_SNAP_CELL_MEAN 1
+#define KNPEMI_DG_SNAP_VERTEX 2
+#define KNPEMI_DG_SNAPSHOT_MAX_SPACE 40
+int knpemi_dg_snapshot_set(knpemi_dg* h, int n_watch, const int32_t* spec, int n_space, const int32_t* space,
+                           const int64_t* list_off, const int32_t* list, int n_space_sel, const int32_t* sel_space,
+                           const int64_t* sel_off, const int32_t* sel_idx, int depth);
+/* As knpemi_snapshot_layout. */
+int knpemi_dg_snapshot_layout(knpemi_dg* h, int64_t* offset, int64_t* n_items, int64_t* frame_bytes);
+/* As knpemi_snapshot_record: ONE pack launch on the handle's stream, then the copy on the copy stream; nothing waits for the
+ * host.  KNPEMI_EINVAL, by name: before knpemi_dg_snapshot_set, before knpemi_dg_set_params, and when t is not finite or
+ * does not exceed the previous record's.  A slot IN FLIGHT: KNPEMI_EBUSY, nothing enqueued, nothing changed. */
+int knpemi_dg_snapshot_record(knpemi_dg* h, double t);
+/* As knpemi_snapshot_take. */
+int knpemi_dg_snapshot_take(knpemi_dg* h, int wait, void* out, size_t bytes, double* t, int64_t* seq);
+/* The number of frames IN FLIGHT (0 before knpemi_dg_snapshot_set). */
+int knpemi_dg_snapshot_pending(knpemi_dg* h);
+/* Wait for the copy stream, free every slot, restart seq at 0 and forget the previous record's time; the table stays. */
+int knpemi_dg_snapshot_reset(knpemi_dg* h);
+/* Synchronise both streams and drop the table, the ring, the copy stream and the events (knpemi_dg_snapshot_record then
+ * fails with KNPEMI_EINVAL); knpemi_dg_destroy does the same. */
+int knpemi_dg_snapshot_clear(knpemi_dg* h);
+
 #ifdef __cplusplus
 }
 #endif

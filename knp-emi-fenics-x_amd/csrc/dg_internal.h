@@ -248,6 +248,47 @@ struct knpemi_dg;
 int kn_dg_launch_balance_membrane(knpemi_dg* h, int splitting);
 int kn_dg_launch_balance_flux(knpemi_dg* h);
 
+// Field snapshots of a DG run (kernels_dg_snapshot.hip; knpemi_dg_snapshot_*).  A space is (sub-domain or membrane tag,
+// form); every workgroup of the pack launch belongs to one space (bstart), the watches of space p are w[wstart[p] ..
+// wstart[p + 1]).  Space p stores n_items[p] items; with a selection sel[p] lane i takes item sel[p][i], else item i.
+//   form KNPEMI_DG_SNAP_BROKEN     an item is one source entry: the broken dof (bulk[p]) or the membrane node src[p][item],
+//                                  or first[p] + item where the list is one ascending run (src[p] == NULL);
+//        KNPEMI_DG_SNAP_CELL_MEAN  an item is a cell (src / first as above): its nv[p] dofs cell * nv .. in local order;
+//        KNPEMI_DG_SNAP_VERTEX     an item is a mesh vertex: the entries vdof[p][vptr[p][item] .. vptr[p][item + 1]), ascending.
+// A bulk watch takes slot `slot` (3 .. 7) of the dof records, a membrane watch reads `dense` (phi_M, a row of I_ch, a column
+// of the state table).  The value of an item is its entries summed in list order, starting from the first, divided by their
+// number (one IEEE division; none for the broken form); f32: (float) of it.
+struct KnDgSnapTab {
+  int n_space, n_watch;
+  int bstart[KNPEMI_DG_SNAPSHOT_MAX_SPACE + 1];
+  int wstart[KNPEMI_DG_SNAPSHOT_MAX_SPACE + 1];
+  int n_items[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  int form[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  int bulk[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  int first[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  int nv[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  const int* sel[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  const int* src[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  const int* vptr[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  const int* vdof[KNPEMI_DG_SNAPSHOT_MAX_SPACE];
+  KnSnapWatch w[KNPEMI_SNAPSHOT_MAX_WATCH];
+};
+// the recorder: the table, its lists and the ring (KnFrameRing), created by the first knpemi_dg_snapshot_set -- a run that
+// does not save opens no copy stream; recorder_free(KnDgSnap&) (knpemi_record.hip) frees what is not in `allocs`
+struct KnDgSnap : KnFrameRing {
+  int n_watch = 0, n_blk = 0;
+  KnDgSnapTab host{};                  // the table as uploaded
+  int slot_of[KNPEMI_SNAPSHOT_MAX_WATCH] = {};       // watch of knpemi_dg_snapshot_set -> entry of the table
+  long long items_of[KNPEMI_SNAPSHOT_MAX_WATCH] = {};
+  KnDgSnapTab* tab = nullptr;
+  long long move_bytes = 0;            // what one launch must move by the algorithm (kn_dg_snapshot_bytes)
+  bool clock_set = false;              // a frame has been recorded since the set-up or the last reset, at t_prev
+  double t_prev = 0.0;
+  std::vector<void*> allocs;
+};
+// one pack launch on the owner's main stream into `frame` (a device frame of the ring)
+int kn_dg_launch_snapshot_pack(KnDevice* own, const KnDgSnap& S, const double* rec, char* frame);
+
 struct knpemi_dg : KnDevice {
   int NV = 0, K = 0, n_sub = 0;
   int NFC = 0, NFV = 0;            // facets per cell, vertices per facet (hexahedra: 6 and 4)
@@ -278,7 +319,8 @@ struct knpemi_dg : KnDevice {
   KnDgJump jump;
   bool obs_jump = false;           // the installed observables read `jump.tab`: a record launches dg_jump_kernel first
   KnDgBalance balance;
-  int knp_flags = 0;               // flags of the last knpemi_dg_assemble_knp: the balance's membrane launch follows its splitting
+  KnDgSnap snap;
+  int knp_flags = 0;              // flags of the last knpemi_dg_assemble_knp: the balance's membrane launch follows its splitting
 };
 void kn_dg_record_free(knpemi_dg* h);   // every recorder's device memory (knpemi_record.hip); knpemi_dg_destroy
 

@@ -213,6 +213,21 @@ struct KnSnapTab {
   KnSnapWatch w[KNPEMI_SNAPSHOT_MAX_WATCH];
 };
 
+// The ring of a snapshot recorder, on either handle (knpemi_record.hip: ring_*): `depth` slots -- a device frame, a pinned
+// host frame and a "copied" event each -- fed by a copy stream of its own.  Slot seq % depth takes frame seq; the frames
+// [tail, seq) are IN FLIGHT, so a slot is FREE exactly when seq - tail < depth.  The device frames live in the recorder's
+// `allocs`; the stream, the events and the pinned frames do not: ring_free frees them.
+struct KnFrameRing {
+  int depth = 0;
+  size_t frame_bytes = 0;
+  hipStream_t copy = nullptr;
+  hipEvent_t ev_packed = nullptr;      // the pack launch's end on the main stream; the copy stream waits for it
+  std::vector<char*> dev, pinned;      // [depth] frames
+  std::vector<hipEvent_t> copied;      // [depth]
+  std::vector<double> t_of;            // [depth] the time of the frame a slot holds
+  int64_t seq = 0, tail = 0;
+};
+
 // (the table of the membrane monitors, KnMonTab: monitor_table.h, shared with the run-time compiled monitor programs)
 
 struct KnOdeModel {
@@ -863,24 +878,15 @@ struct knpemi_handle : KnDevice {
     double* col_denom = nullptr;         // [n_cols]
     std::vector<void*> allocs;
   } mon;
-  // field snapshots (knpemi_snapshot_set, kernels_snapshot.hip): the table, the selections, and a ring of `depth` slots --
-  // a device frame, a pinned host frame and a "copied" event each -- fed by a copy stream of its own.  Slot seq % depth
-  // takes frame seq; the frames [tail, seq) are IN FLIGHT, so a slot is FREE exactly when seq - tail < depth.  The
-  // stream, the events and the pinned frames are not in `allocs`: recorder_free(KnSnap&) (knpemi_record.hip) frees them.
-  struct KnSnap {
-    int n_watch = 0, n_blk = 0, depth = 0;
+  // field snapshots (knpemi_snapshot_set, kernels_snapshot.hip): the table, the selections, and the ring (KnFrameRing);
+  // recorder_free(KnSnap&) (knpemi_record.hip) frees what of the ring is not in `allocs`.
+  struct KnSnap : KnFrameRing {
+    int n_watch = 0, n_blk = 0;
     KnSnapTab host{};                    // the table as uploaded
     int slot_of[KNPEMI_SNAPSHOT_MAX_WATCH] = {};       // watch of knpemi_snapshot_set -> entry of the table
     long long items_of[KNPEMI_SNAPSHOT_MAX_WATCH] = {};
     KnSnapTab* tab = nullptr;
-    size_t frame_bytes = 0;
     long long move_bytes = 0;            // what one launch must move by the algorithm (kn_snapshot_bytes)
-    hipStream_t copy = nullptr;
-    hipEvent_t ev_packed = nullptr;      // the pack launch's end on the main stream; the copy stream waits for it
-    std::vector<char*> dev, pinned;      // [depth] frames
-    std::vector<hipEvent_t> copied;      // [depth]
-    std::vector<double> t_of;            // [depth] the time of the frame a slot holds
-    int64_t seq = 0, tail = 0;
     std::vector<void*> allocs;
   } snap;
   int knp_flags = 0;                 // flags of the last knpemi_assemble_knp: the splitting scheme the exchange records with

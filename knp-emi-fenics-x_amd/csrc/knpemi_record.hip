@@ -18,7 +18,9 @@
 // The observables and the membrane events also record on a DG handle (knpemi_dg_observe_*, knpemi_dg_events_*, at the end
 // of this file): the routines they need take the owner (KnDevice*: device, main stream) and are generic over the handle
 // type that holds the recorder's state; what differs per handle is where a field lives (observe_build's `locate`) and
-// which array the events sample (KnEvSamples).
+// which array the events sample (KnEvSamples).  The field snapshots of both handles (knpemi_snapshot_*, knpemi_dg_snapshot_*)
+// share the ring -- copy stream, pinned frames, take -- as KnFrameRing and the ring_* routines; the tables and the pack
+// kernels are each handle's own.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -76,16 +78,24 @@ void recorder_free(R& rec) {
   kn_free_all(rec.allocs);
   rec = R{};
 }
-// the snapshots own more than device memory: the copy stream (waited for first: a copy may be in flight), the events and
-// the pinned frames
+// the snapshots of either handle own more than device memory: the copy stream (waited for first: a copy may be in
+// flight), the events and the pinned frames of their ring
+void ring_free(KnFrameRing& R) {
+  if (R.copy) (void)hipStreamSynchronize(R.copy);
+  for (hipEvent_t e : R.copied) (void)hipEventDestroy(e);
+  if (R.ev_packed) (void)hipEventDestroy(R.ev_packed);
+  for (char* p : R.pinned) (void)hipHostFree(p);
+  if (R.copy) (void)hipStreamDestroy(R.copy);
+}
 void recorder_free(knpemi_handle::KnSnap& S) {
-  if (S.copy) (void)hipStreamSynchronize(S.copy);
-  for (hipEvent_t e : S.copied) (void)hipEventDestroy(e);
-  if (S.ev_packed) (void)hipEventDestroy(S.ev_packed);
-  for (char* p : S.pinned) (void)hipHostFree(p);
-  if (S.copy) (void)hipStreamDestroy(S.copy);
+  ring_free(S);
   kn_free_all(S.allocs);
   S = knpemi_handle::KnSnap{};
+}
+void recorder_free(KnDgSnap& S) {
+  ring_free(S);
+  kn_free_all(S.allocs);
+  S = KnDgSnap{};
 }
 template <class H, class R>
 int recorder_clear(H* h, R H::*which) {
@@ -1134,6 +1144,75 @@ extern "C" int knpemi_monitor_eval(knpemi_handle* h, int sub, int model, double 
 namespace {
 const char* const SNAP_NONE = "no snapshots set (knpemi_snapshot_set)";
 size_t snap_align(size_t n) { return (n + KNPEMI_SNAPSHOT_ALIGN - 1) / KNPEMI_SNAPSHOT_ALIGN * KNPEMI_SNAPSHOT_ALIGN; }
+
+// -- the ring of a snapshot recorder (KnFrameRing), on either handle: `own` gives the device and the main stream, `fn` the
+// entry point's name for the error texts
+// the copy stream, the "packed" event and `depth` slots of R.frame_bytes; the device frames go to `allocs`.  A return
+// before the end leaves what exists to the owner's recorder_free
+int ring_alloc(KnFrameRing& R, std::vector<void*>& allocs, int depth) {
+  R.depth = depth;
+  KN_HIP(hipStreamCreateWithFlags(&R.copy, hipStreamNonBlocking));
+  KN_HIP(hipEventCreateWithFlags(&R.ev_packed, hipEventDisableTiming));
+  R.t_of.assign((size_t)depth, 0.0);
+  for (int s = 0; s < depth; ++s) {
+    char* d = nullptr;
+    if (int rc = kn_alloc(allocs, R.frame_bytes, &d)) return rc;
+    R.dev.push_back(d);
+    void* host = nullptr;
+    KN_HIP(hipHostMalloc(&host, R.frame_bytes, hipHostMallocDefault));
+    R.pinned.push_back(static_cast<char*>(host));
+    hipEvent_t e = nullptr;
+    KN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    R.copied.push_back(e);
+  }
+  return KNPEMI_OK;
+}
+bool ring_full(const KnFrameRing& R) { return R.seq - R.tail >= R.depth; }
+// frame seq at time t into slot seq % depth, which is FREE: the host has taken its previous frame, so that copy is done
+// and the device frame may be overwritten.  pack(frame) enqueues the pack launch on the main stream; behind it the copy
+// stream takes the frame to pinned memory.  Nothing is synchronised
+template <class Pack>
+int ring_record(KnDevice* own, KnFrameRing& R, double t, Pack pack) {
+  const size_t slot = (size_t)(R.seq % R.depth);
+  if (int rc = pack(R.dev[slot])) return rc;
+  KN_HIP(hipEventRecord(R.ev_packed, own->stream));
+  KN_HIP(hipStreamWaitEvent(R.copy, R.ev_packed, 0));
+  KN_HIP(hipMemcpyAsync(R.pinned[slot], R.dev[slot], R.frame_bytes, hipMemcpyDeviceToHost, R.copy));
+  KN_HIP(hipEventRecord(R.copied[slot], R.copy));
+  R.t_of[slot] = t;
+  ++R.seq;
+  return KNPEMI_OK;
+}
+// the oldest frame in flight into `out`; 1 with nothing in flight, KNPEMI_EBUSY (wait == 0) while its copy runs
+int ring_take(KnDevice* own, KnFrameRing& R, const std::string& fn, const char* layout_call, int wait, void* out, size_t bytes,
+              double* t, int64_t* seq) {
+  if (R.tail == R.seq) return 1;
+  if (!out || bytes != R.frame_bytes) return kn_fail(KNPEMI_EINVAL, fn + ": the buffer must hold one frame (" + layout_call + ")");
+  KN_HIP(hipSetDevice(own->device));
+  const size_t slot = (size_t)(R.tail % R.depth);
+  if (!wait) {
+    const hipError_t e = hipEventQuery(R.copied[slot]);
+    if (e == hipErrorNotReady) {
+      (void)hipGetLastError();      // not an error: the next launch check must not see it
+      return kn_fail(KNPEMI_EBUSY, fn + ": the oldest frame's copy has not finished");
+    }
+    KN_HIP(e);
+  } else {
+    KN_HIP(hipEventSynchronize(R.copied[slot]));
+  }
+  std::memcpy(out, R.pinned[slot], bytes);
+  if (t) *t = R.t_of[slot];
+  if (seq) *seq = R.tail;
+  ++R.tail;
+  return KNPEMI_OK;
+}
+// wait for the copy stream, free every slot, restart seq at 0
+int ring_reset(KnDevice* own, KnFrameRing& R) {
+  KN_HIP(hipSetDevice(own->device));
+  KN_HIP(hipStreamSynchronize(R.copy));
+  R.seq = R.tail = 0;
+  return KNPEMI_OK;
+}
 }  // namespace
 
 extern "C" int knpemi_snapshot_set(knpemi_handle* h, int n_watch, const int32_t* spec, int n_space_sel, const int32_t* sel_space,
@@ -1254,23 +1333,9 @@ extern "C" int knpemi_snapshot_set(knpemi_handle* h, int n_watch, const int32_t*
   T.n_watch = n_watch;
   N.n_watch = n_watch;
   N.n_blk = T.bstart[T.n_space];
-  N.depth = depth;
   if (int rc = kn_upload(N.allocs, &T, 1, &N.tab)) return rc;
   // the ring; a return from here on frees what exists of it (recorder_free)
-  KN_HIP(hipStreamCreateWithFlags(&N.copy, hipStreamNonBlocking));
-  KN_HIP(hipEventCreateWithFlags(&N.ev_packed, hipEventDisableTiming));
-  N.t_of.assign((size_t)depth, 0.0);
-  for (int s = 0; s < depth; ++s) {
-    char* d = nullptr;
-    if (int rc = kn_alloc(N.allocs, N.frame_bytes, &d)) return rc;
-    N.dev.push_back(d);
-    void* host = nullptr;
-    KN_HIP(hipHostMalloc(&host, N.frame_bytes, hipHostMallocDefault));
-    N.pinned.push_back(static_cast<char*>(host));
-    hipEvent_t e = nullptr;
-    KN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    N.copied.push_back(e);
-  }
+  if (int rc = ring_alloc(N, N.allocs, depth)) return rc;
   return recorder_install(h, &knpemi_handle::snap, N);
 }
 
@@ -1291,21 +1356,12 @@ extern "C" int knpemi_snapshot_record(knpemi_handle* h, double t) {
   auto& S = h->snap;
   if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_snapshot_record: ") + SNAP_NONE);
   if (!std::isfinite(t)) return kn_fail(KNPEMI_EINVAL, "knpemi_snapshot_record: t must be finite");
-  if (S.seq - S.tail >= S.depth)
+  if (ring_full(S))
     return kn_fail(KNPEMI_EBUSY, "knpemi_snapshot_record: every slot is in flight (knpemi_snapshot_take frees the oldest)");
   KN_HIP(hipSetDevice(h->device));
-  const size_t slot = (size_t)(S.seq % S.depth);
-  // the pack reads phi_M, I_ch and the state tables, which the ODE sweeps may write on the auxiliary streams.  The slot is
-  // FREE: the host has taken its previous frame, so that copy is done and the device frame may be overwritten
+  // the pack reads phi_M, I_ch and the state tables, which the ODE sweeps may write on the auxiliary streams
   if (int rc = kn_wait_ode_joins(h)) return rc;
-  if (int rc = kn_launch_snapshot_pack(h, S.dev[slot])) return rc;
-  KN_HIP(hipEventRecord(S.ev_packed, h->stream));
-  KN_HIP(hipStreamWaitEvent(S.copy, S.ev_packed, 0));
-  KN_HIP(hipMemcpyAsync(S.pinned[slot], S.dev[slot], S.frame_bytes, hipMemcpyDeviceToHost, S.copy));
-  KN_HIP(hipEventRecord(S.copied[slot], S.copy));
-  S.t_of[slot] = t;
-  ++S.seq;
-  return KNPEMI_OK;
+  return ring_record(h, S, t, [&](char* frame) { return kn_launch_snapshot_pack(h, frame); });
 }
 
 extern "C" int knpemi_snapshot_take(knpemi_handle* h, int wait, void* out, size_t bytes, double* t, int64_t* seq) {
@@ -1313,25 +1369,7 @@ extern "C" int knpemi_snapshot_take(knpemi_handle* h, int wait, void* out, size_
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   auto& S = h->snap;
   if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + SNAP_NONE);
-  if (S.tail == S.seq) return 1;
-  if (!out || bytes != S.frame_bytes) return kn_fail(KNPEMI_EINVAL, fn + ": the buffer must hold one frame (knpemi_snapshot_layout)");
-  KN_HIP(hipSetDevice(h->device));
-  const size_t slot = (size_t)(S.tail % S.depth);
-  if (!wait) {
-    const hipError_t e = hipEventQuery(S.copied[slot]);
-    if (e == hipErrorNotReady) {
-      (void)hipGetLastError();      // not an error: the next launch check must not see it
-      return kn_fail(KNPEMI_EBUSY, fn + ": the oldest frame's copy has not finished");
-    }
-    KN_HIP(e);
-  } else {
-    KN_HIP(hipEventSynchronize(S.copied[slot]));
-  }
-  std::memcpy(out, S.pinned[slot], bytes);
-  if (t) *t = S.t_of[slot];
-  if (seq) *seq = S.tail;
-  ++S.tail;
-  return KNPEMI_OK;
+  return ring_take(h, S, fn, "knpemi_snapshot_layout", wait, out, bytes, t, seq);
 }
 
 extern "C" int knpemi_snapshot_pending(knpemi_handle* h) { return h ? (int)(h->snap.seq - h->snap.tail) : 0; }
@@ -1340,10 +1378,7 @@ extern "C" int knpemi_snapshot_reset(knpemi_handle* h) {
   if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
   auto& S = h->snap;
   if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_snapshot_reset: ") + SNAP_NONE);
-  KN_HIP(hipSetDevice(h->device));
-  KN_HIP(hipStreamSynchronize(S.copy));
-  S.seq = S.tail = 0;
-  return KNPEMI_OK;
+  return ring_reset(h, S);
 }
 
 extern "C" int knpemi_snapshot_clear(knpemi_handle* h) { return recorder_clear(h, &knpemi_handle::snap); }
@@ -1357,7 +1392,7 @@ extern "C" long long kn_snapshot_bytes(knpemi_handle* h) { return h ? h->snap.mo
 extern "C" int kn_snapshot_pack_only(knpemi_handle* h, int n) {
   if (!h || h->snap.n_watch == 0 || n < 0) return kn_fail(KNPEMI_EINVAL, std::string("kn_snapshot_pack_only: ") + SNAP_NONE);
   auto& S = h->snap;
-  if (S.seq - S.tail >= S.depth) return kn_fail(KNPEMI_EBUSY, "kn_snapshot_pack_only: every slot is in flight");
+  if (ring_full(S)) return kn_fail(KNPEMI_EBUSY, "kn_snapshot_pack_only: every slot is in flight");
   KN_HIP(hipSetDevice(h->device));
   for (int i = 0; i < n; ++i)
     if (int rc = kn_launch_snapshot_pack(h, S.dev[(size_t)(S.seq % S.depth)])) return rc;
@@ -1372,6 +1407,7 @@ void kn_dg_record_free(knpemi_dg* h) {
   kn_free_all(h->obs.allocs);
   kn_free_all(h->events.allocs);
   kn_free_all(h->balance.allocs);
+  recorder_free(h->snap);
 }
 
 namespace {
@@ -1590,3 +1626,249 @@ extern "C" int knpemi_dg_balance_reset(knpemi_dg* h) {
 }
 
 extern "C" int knpemi_dg_balance_clear(knpemi_dg* h) { return recorder_clear(h, &knpemi_dg::balance); }
+
+// ---------------------------------------------------------------------------------------------------
+// field snapshots of a DG run (kernels_dg_snapshot.hip): the table is the DG handle's, the ring the conforming path's
+// ---------------------------------------------------------------------------------------------------
+namespace {
+const char* const DG_SNAP_NONE = "no snapshots set (knpemi_dg_snapshot_set)";
+}  // namespace
+
+extern "C" int knpemi_dg_snapshot_set(knpemi_dg* h, int n_watch, const int32_t* spec, int n_space, const int32_t* space,
+                                      const int64_t* list_off, const int32_t* list, int n_space_sel, const int32_t* sel_space,
+                                      const int64_t* sel_off, const int32_t* sel_idx, int depth) {
+  const std::string fn = "knpemi_dg_snapshot_set";
+  if (!h || !spec || !space || !list_off || !list || (n_space_sel > 0 && (!sel_space || !sel_off || !sel_idx)))
+    return kn_fail(KNPEMI_EINVAL, fn + ": null argument");
+  if (n_watch < 1 || n_watch > KNPEMI_SNAPSHOT_MAX_WATCH)
+    return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_SNAPSHOT_MAX_WATCH watches");
+  if (n_space < 1 || n_space > KNPEMI_DG_SNAPSHOT_MAX_SPACE)
+    return kn_fail(KNPEMI_EINVAL, fn + ": 1 to KNPEMI_DG_SNAPSHOT_MAX_SPACE spaces");
+  if (depth < 1 || depth > (1 << 16)) return kn_fail(KNPEMI_EINVAL, fn + ": depth must be positive (and at most 65536)");
+  if (n_space_sel < 0 || n_space_sel > n_space) return kn_fail(KNPEMI_EINVAL, fn + ": bad number of selections");
+  const kn_dg::DgDev& D = h->dev;
+  // the spaces: every entry the kernel will read is checked here, against the fields' lengths
+  if (list_off[0] != 0) return kn_fail(KNPEMI_EINVAL, fn + ": list_off[0] must be 0");
+  long long entries[KNPEMI_DG_SNAPSHOT_MAX_SPACE] = {};      // source entries one launch reads per watch of the space
+  for (int p = 0; p < n_space; ++p) {
+    const int32_t mem = space[4 * p], tag = space[4 * p + 1], form = space[4 * p + 2], n = space[4 * p + 3];
+    const std::string who = fn + ": space " + std::to_string(p);
+    if (mem != 0 && mem != 1) return kn_fail(KNPEMI_EINVAL, who + ": the kind is 0 (cells of a sub-domain) or 1 (a membrane tag)");
+    if (form != KNPEMI_DG_SNAP_BROKEN && form != KNPEMI_DG_SNAP_CELL_MEAN && form != KNPEMI_DG_SNAP_VERTEX)
+      return kn_fail(KNPEMI_EINVAL, who + ": unknown form (broken, cell_mean or vertex)");
+    if (mem && form == KNPEMI_DG_SNAP_CELL_MEAN) return kn_fail(KNPEMI_EINVAL, who + ": a membrane quantity has no cell_mean form");
+    if (tag < 0 || (!mem && tag >= h->n_sub)) return kn_fail(KNPEMI_EINVAL, who + ": unknown tag (sub-domain index out of range)");
+    for (int u = 0; u < p; ++u)
+      if (std::equal(space + 4 * u, space + 4 * u + 3, space + 4 * p)) return kn_fail(KNPEMI_EINVAL, who + " is listed twice");
+    if (n < 1) return kn_fail(KNPEMI_EINVAL, who + " has no items");
+    const int64_t lo = list_off[p], len = list_off[p + 1] - lo;
+    const int64_t n_src = mem ? D.nq : (form == KNPEMI_DG_SNAP_CELL_MEAN ? D.n_cell : D.n_dof);
+    if (len < 0 || lo + len > (int64_t)INT32_MAX) return kn_fail(KNPEMI_EINVAL, who + ": bad list range");
+    const int32_t* a = list + lo;
+    if (form != KNPEMI_DG_SNAP_VERTEX) {
+      if (len != n) return kn_fail(KNPEMI_EINVAL, who + ": the list must hold one entry per item");
+      for (int64_t e = 0; e < len; ++e)
+        if (a[e] < 0 || a[e] >= n_src) return kn_fail(KNPEMI_EINVAL, who + ": list entry out of range");
+      entries[p] = form == KNPEMI_DG_SNAP_CELL_MEAN ? (long long)n * h->NV : n;
+    } else {
+      if (len < (int64_t)n + 1 || a[0] != 0 || (int64_t)a[n] != len - (n + 1))
+        return kn_fail(KNPEMI_EINVAL, who + ": the list must hold vptr [n_items + 1] and then vptr[n_items] entries");
+      const int32_t* v = a + n + 1;
+      for (int i = 0; i < n; ++i) {
+        if (a[i + 1] <= a[i] || a[i + 1] > a[n]) return kn_fail(KNPEMI_EINVAL, who + ": a vertex without entries, or vptr not increasing");
+        for (int e = a[i]; e < a[i + 1]; ++e)
+          if (v[e] < 0 || v[e] >= n_src || (e > a[i] && v[e] <= v[e - 1]))
+            return kn_fail(KNPEMI_EINVAL, who + ": the entries of a vertex must be ascending, distinct and in range");
+      }
+      entries[p] = a[n];
+    }
+  }
+  // the watches
+  int space_of[KNPEMI_SNAPSHOT_MAX_WATCH], per_space[KNPEMI_DG_SNAPSHOT_MAX_SPACE] = {};
+  KnSnapWatch src[KNPEMI_SNAPSHOT_MAX_WATCH];
+  for (int w = 0; w < n_watch; ++w) {
+    const int32_t q = spec[5 * w], tag = spec[5 * w + 1], ix = spec[5 * w + 2], form = spec[5 * w + 3], fl = spec[5 * w + 4];
+    const std::string who = fn + ": watch " + std::to_string(w);
+    KnSnapWatch& W = src[w];
+    W = KnSnapWatch{};
+    bool mem = true;
+    switch (q) {
+      case KNPEMI_DG_C:
+        if (ix < 0 || ix >= h->K) return kn_fail(KNPEMI_EINVAL, who + ": ion index out of range");
+        W.slot = KN_CSLOT(ix); mem = false;
+        break;
+      case KNPEMI_DG_PHI: W.slot = 7; mem = false; break;
+      case KNPEMI_DG_PHI_M: W.dense = D.phiM; break;
+      case KNPEMI_DG_I_CH:
+        if (ix < 0 || ix >= h->K) return kn_fail(KNPEMI_EINVAL, who + ": ion index out of range");
+        W.dense = D.Ich + (size_t)ix * D.nq;
+        break;
+      case KNPEMI_DG_ODE_STATE: {
+        const KnOdeModel& m = h->sweeps.ode[0];
+        if (!m.bound || !m.d_states) return kn_fail(KNPEMI_EINVAL, who + ": no membrane model bound (knpemi_dg_ode_bind)");
+        if (ix < 0 || ix >= m.n_states) return kn_fail(KNPEMI_EINVAL, who + ": state index out of range");
+        if (m.nq != D.nq) return kn_fail(KNPEMI_EINVAL, who + ": the state table does not cover the membrane nodes");
+        W.dense = m.d_states + (size_t)ix * m.nq;
+        break;
+      }
+      default:
+        return kn_fail(KNPEMI_EINVAL, who + ": unknown quantity (KNPEMI_DG_C, _PHI, _PHI_M, _I_CH or _ODE_STATE)");
+    }
+    if (fl & ~KNPEMI_SNAPSHOT_F32) return kn_fail(KNPEMI_EINVAL, who + ": unknown dtype bits");
+    for (int u = 0; u < w; ++u)
+      if (std::equal(spec + 5 * u, spec + 5 * u + 5, spec + 5 * w)) return kn_fail(KNPEMI_EINVAL, who + " is listed twice");
+    int p = 0;
+    while (p < n_space && !(space[4 * p] == (mem ? 1 : 0) && space[4 * p + 1] == tag && space[4 * p + 2] == form)) ++p;
+    if (p == n_space)
+      return kn_fail(KNPEMI_EINVAL, who + ": unknown tag or form: no space (" + (mem ? "membrane tag " : "sub-domain ") +
+                                        std::to_string(tag) + ", form " + std::to_string(form) + ") is given");
+    W.f32 = (fl & KNPEMI_SNAPSHOT_F32) ? 1 : 0;
+    space_of[w] = p;
+    ++per_space[p];
+  }
+  // the selections: ascending distinct items of a watched space, one list per space at most
+  const int32_t* sel_of[KNPEMI_DG_SNAPSHOT_MAX_SPACE] = {};
+  int sel_n[KNPEMI_DG_SNAPSHOT_MAX_SPACE] = {};
+  for (int j = 0; j < n_space_sel; ++j) {
+    const int sp = sel_space[j];
+    const std::string who = fn + ": selection " + std::to_string(j);
+    if (sp < 0 || sp >= n_space || !per_space[sp]) return kn_fail(KNPEMI_EINVAL, who + ": not a watched space");
+    if (sel_of[sp]) return kn_fail(KNPEMI_EINVAL, who + ": the space has a selection already");
+    const int64_t lo = sel_off[j], hi = sel_off[j + 1], n_src = space[4 * sp + 3];
+    if (lo < 0 || hi <= lo || hi - lo > n_src) return kn_fail(KNPEMI_EINVAL, who + ": empty, or longer than the space");
+    for (int64_t e = lo; e < hi; ++e)
+      if (sel_idx[e] < 0 || sel_idx[e] >= n_src || (e > lo && sel_idx[e] <= sel_idx[e - 1]))
+        return kn_fail(KNPEMI_EINVAL, who + ": indices must be ascending, distinct and inside the space");
+    sel_of[sp] = sel_idx + lo;
+    sel_n[sp] = (int)(hi - lo);
+  }
+  // the frame: the watches in the order given, each at a multiple of KNPEMI_SNAPSHOT_ALIGN
+  New<KnDgSnap> N;
+  KnDgSnapTab& T = N.host;
+  size_t end = 0;
+  for (int w = 0; w < n_watch; ++w) {
+    const int p = space_of[w];
+    const size_t n = sel_of[p] ? (size_t)sel_n[p] : (size_t)space[4 * p + 3];
+    src[w].off = (long long)snap_align(end);
+    end = (size_t)src[w].off + n * (src[w].f32 ? 4 : 8);
+    N.items_of[w] = (long long)n;
+  }
+  N.frame_bytes = std::max<size_t>(snap_align(end), KNPEMI_SNAPSHOT_ALIGN);
+  KN_HIP(hipSetDevice(h->device));
+  // the table, grouped by space; the spaces nothing watches are left out
+  int k = 0;
+  for (int sp = 0; sp < n_space; ++sp) {
+    if (!per_space[sp]) continue;
+    const int p = T.n_space++;
+    const int32_t mem = space[4 * sp], form = space[4 * sp + 2], n = space[4 * sp + 3];
+    const int32_t* a = list + list_off[sp];
+    T.n_items[p] = sel_of[sp] ? sel_n[sp] : n;
+    T.form[p] = form;
+    T.bulk[p] = mem ? 0 : 1;
+    T.nv[p] = h->NV;
+    T.bstart[p + 1] = T.bstart[p] + (T.n_items[p] + 255) / 256;
+    T.wstart[p] = k;
+    const double frac = (double)T.n_items[p] / (double)n;      // of the space's entries, with a selection (an estimate)
+    const long long n_read = (long long)((double)entries[sp] * frac);
+    long long idx_bytes = sel_of[sp] ? 4LL * sel_n[sp] : 0;
+    if (sel_of[sp])
+      if (int rc = kn_upload(N.allocs, sel_of[sp], (size_t)sel_n[sp], &T.sel[p])) return rc;
+    if (form == KNPEMI_DG_SNAP_VERTEX) {
+      if (int rc = kn_upload(N.allocs, a, (size_t)n + 1, &T.vptr[p])) return rc;
+      if (int rc = kn_upload(N.allocs, a + n + 1, (size_t)a[n], &T.vdof[p])) return rc;
+      idx_bytes += 4LL * T.n_items[p] + 4LL * n_read;
+    } else {
+      bool run = true;      // one ascending run: first + item, no list on the device
+      for (int i = 1; i < n && run; ++i) run = a[i] == a[0] + i;
+      T.first[p] = a[0];
+      if (!run) {
+        if (int rc = kn_upload(N.allocs, a, (size_t)n, &T.src[p])) return rc;
+        idx_bytes += 4LL * T.n_items[p];
+      }
+    }
+    int n_w = 0;
+    for (int w = 0; w < n_watch; ++w) {
+      if (space_of[w] != sp) continue;
+      T.w[k] = src[w];
+      N.move_bytes += (src[w].f32 ? 4LL : 8LL) * T.n_items[p];
+      N.slot_of[w] = k++;
+      ++n_w;
+    }
+    // read: 40 bytes of every record once per space, 8 per entry and watch of a membrane space, and the index lists
+    N.move_bytes += (mem ? 8LL * n_w : 40LL) * n_read + idx_bytes;
+    T.wstart[p + 1] = k;
+  }
+  T.n_watch = n_watch;
+  N.n_watch = n_watch;
+  N.n_blk = T.bstart[T.n_space];
+  if (int rc = kn_upload(N.allocs, &T, 1, &N.tab)) return rc;
+  // the ring; a return from here on frees what exists of it (recorder_free)
+  if (int rc = ring_alloc(N, N.allocs, depth)) return rc;
+  return recorder_install(h, &knpemi_dg::snap, N);
+}
+
+extern "C" int knpemi_dg_snapshot_layout(knpemi_dg* h, int64_t* offset, int64_t* n_items, int64_t* frame_bytes) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  const auto& S = h->snap;
+  if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_dg_snapshot_layout: ") + DG_SNAP_NONE);
+  for (int w = 0; w < S.n_watch; ++w) {
+    if (offset) offset[w] = (int64_t)S.host.w[S.slot_of[w]].off;
+    if (n_items) n_items[w] = (int64_t)S.items_of[w];
+  }
+  if (frame_bytes) *frame_bytes = (int64_t)S.frame_bytes;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_dg_snapshot_record(knpemi_dg* h, double t) {
+  const std::string fn = "knpemi_dg_snapshot_record";
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& S = h->snap;
+  if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + DG_SNAP_NONE);
+  if (!h->have_params) return kn_fail(KNPEMI_EINVAL, fn + ": knpemi_dg_set_params has not been called");
+  if (!std::isfinite(t) || (S.clock_set && !(t > S.t_prev)))
+    return kn_fail(KNPEMI_EINVAL, fn + ": t must be finite and greater than the previous record's");
+  if (ring_full(S))
+    return kn_fail(KNPEMI_EBUSY, fn + ": every slot is in flight (knpemi_dg_snapshot_take frees the oldest)");
+  KN_HIP(hipSetDevice(h->device));
+  // the membrane sweep of a DG handle runs on the main stream: the pack launch is behind it without a join
+  if (int rc = ring_record(h, S, t, [&](char* frame) { return kn_dg_launch_snapshot_pack(h, S, h->dev.rec, frame); })) return rc;
+  S.clock_set = true;
+  S.t_prev = t;
+  return KNPEMI_OK;
+}
+
+extern "C" int knpemi_dg_snapshot_take(knpemi_dg* h, int wait, void* out, size_t bytes, double* t, int64_t* seq) {
+  const std::string fn = "knpemi_dg_snapshot_take";
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  if (h->snap.n_watch == 0) return kn_fail(KNPEMI_EINVAL, fn + ": " + DG_SNAP_NONE);
+  return ring_take(h, h->snap, fn, "knpemi_dg_snapshot_layout", wait, out, bytes, t, seq);
+}
+
+extern "C" int knpemi_dg_snapshot_pending(knpemi_dg* h) { return h ? (int)(h->snap.seq - h->snap.tail) : 0; }
+
+extern "C" int knpemi_dg_snapshot_reset(knpemi_dg* h) {
+  if (!h) return kn_fail(KNPEMI_EINVAL, "null handle");
+  auto& S = h->snap;
+  if (S.n_watch == 0) return kn_fail(KNPEMI_EINVAL, std::string("knpemi_dg_snapshot_reset: ") + DG_SNAP_NONE);
+  S.clock_set = false;
+  return ring_reset(h, S);
+}
+
+extern "C" int knpemi_dg_snapshot_clear(knpemi_dg* h) { return recorder_clear(h, &knpemi_dg::snap); }
+
+// the bytes one pack launch moves by the algorithm: 40 read per gathered record of a bulk space, 8 per gathered entry of
+// every membrane watch, the index lists (selection, source list, vptr and vdof: 4 each) and the 4 or 8 written per item of
+// every watch
+extern "C" long long kn_dg_snapshot_bytes(knpemi_dg* h) { return h ? h->snap.move_bytes : 0; }
+
+// tools/dg_snapshot_time.py: n pack launches back to back into the device frame of the next slot, which must be FREE; no
+// copy, no frame recorded
+extern "C" int kn_dg_snapshot_pack_only(knpemi_dg* h, int n) {
+  if (!h || h->snap.n_watch == 0 || n < 0) return kn_fail(KNPEMI_EINVAL, std::string("kn_dg_snapshot_pack_only: ") + DG_SNAP_NONE);
+  auto& S = h->snap;
+  if (ring_full(S)) return kn_fail(KNPEMI_EBUSY, "kn_dg_snapshot_pack_only: every slot is in flight");
+  KN_HIP(hipSetDevice(h->device));
+  for (int i = 0; i < n; ++i)
+    if (int rc = kn_dg_launch_snapshot_pack(h, S, h->dev.rec, S.dev[(size_t)(S.seq % S.depth)])) return rc;
+  return KNPEMI_OK;
+}

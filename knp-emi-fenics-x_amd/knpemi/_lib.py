@@ -94,6 +94,9 @@ class DGParams(C.Structure):
 
 
 DG_C, DG_PHI, DG_PHI_M, DG_I_CH, DG_SOURCE, DG_JUMP = range(6)
+DG_ODE_STATE = 6                                        # knpemi_dg_snapshot_set: a state column of the bound table
+DG_SNAP_BROKEN, DG_SNAP_CELL_MEAN, DG_SNAP_VERTEX = range(3)
+DG_SNAPSHOT_MAX_SPACE = 40
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int)
@@ -305,6 +308,14 @@ SIGNATURES = {
     "knpemi_dg_balance_cells": (C.c_int, [C.c_void_p, c_dbl_p]),
     "knpemi_dg_balance_reset": (C.c_int, [C.c_void_p]),
     "knpemi_dg_balance_clear": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_snapshot_set": (C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_int, c_int_p, C.POINTER(C.c_int64), c_int_p,
+                                         C.c_int, c_int_p, C.POINTER(C.c_int64), c_int_p, C.c_int]),
+    "knpemi_dg_snapshot_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "knpemi_dg_snapshot_record": (C.c_int, [C.c_void_p, C.c_double]),
+    "knpemi_dg_snapshot_take": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, c_dbl_p, C.POINTER(C.c_int64)]),
+    "knpemi_dg_snapshot_pending": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_snapshot_reset": (C.c_int, [C.c_void_p]),
+    "knpemi_dg_snapshot_clear": (C.c_int, [C.c_void_p]),
 }
 
 

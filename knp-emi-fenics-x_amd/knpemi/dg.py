@@ -63,7 +63,7 @@ class DGProblem:
         self.cell_sub = cell_subdomains(ct, subdomain_tags)
         self.n_sub = len(subdomain_tags)
         self.mem_facets, self.mem_tags = membrane_facets(mesh, ft, membrane_tags)
-        self.taps = []                                      # the attached recorders (knpemi.recording.Tap): observe, detect, balance
+        self.taps = []                                      # the attached recorders (knpemi.recording.Tap): observe, detect, balance, snapshot
         self.n_records = 0
         self.ion_params = None                              # (F, [z_k]) of the last set_params
         self.n_cells = mesh.num_cells
@@ -323,6 +323,21 @@ class DGProblem:
                                          t0, capacity=capacity, read=read, n_cols=bal.n_cols,
                                          rewind=lambda: L.check(lib.knpemi_dg_balance_reset(h)))))
 
+    def snapshot(self, snap, every=1, depth=4, t0=0.0):
+        """Snapshot the watched fields of `snap` (knpemi.dg_snapshots.DGSnapshots) at every `every`-th call of `record(t)`:
+        one pack launch on the handle's stream, behind the update and the recorders attached before, then the copy of the
+        frame to pinned host memory on a stream of its own (created here, at the first attachment); nothing waits for the
+        host.  The ring holds `depth` frames; a record first hands the frames whose copy is done to the writer, and only
+        a full ring makes it wait, for the oldest frame alone (`snap.stalls`).  `snap.flush()` brings every recorded
+        frame to the sinks; a frame carries the record number as its step."""
+        from .recording import Tap
+        self._may_attach("snapshot", every, None, "this problem takes field snapshots already")
+        if depth < 1:
+            raise ValueError("depth must be positive")
+        snap._attach(self, int(depth))
+        self.taps.append(("snapshot", Tap(snap, "DG field snapshots", every,
+                                          lambda t, f: L.check(snap._tick(t, self.n_records)), t0, rewind=snap._rewind)))
+
     def record_membrane(self):
         """Between `assemble_knp` and the solve of the concentrations: the first launch of the ion balance, when one is
         attached and the next `record(t)` is a record of it; nothing otherwise."""
@@ -401,6 +416,11 @@ class DGSlab:
 
     def balance(self, *args, **kwargs):
         raise NotImplementedError(self._NO_RECORDS.format("balance"))
+
+    def snapshot(self, *args, **kwargs):
+        raise NotImplementedError("DGSlab.snapshot: snapshots of a cell-partitioned DG run are not built -- a rank's frames "
+                                  "would hold its ghost cells, and the vertex averages at a cut would miss the neighbour's "
+                                  "dofs; snapshot a single-rank DGProblem")
 
     def attach(self):
         from .fem.transport import Transport, dg_endpoint

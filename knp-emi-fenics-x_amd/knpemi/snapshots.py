@@ -214,6 +214,11 @@ class _Writer:
 
 
 class Snapshots:
+    _ABI = "knpemi_snapshot_"             # the entry points of the ring: knpemi.dg_snapshots.DGSnapshots names the DG handle's
+
+    def _abi(self, name):
+        return getattr(self._dev[0], self._ABI + name)
+
     def __init__(self, mesh, ct, ft, subdomain_list, ion_list, sink=None, writer="thread"):
         """sink: a callable `sink(t, k, frame)` or a list of them (`add_sink` adds more); writer: "thread" (one daemon
         thread behind a bounded queue) or "inline" (the sinks run on the stepping thread)."""
@@ -512,7 +517,7 @@ class Snapshots:
         watches, nbytes = self._layout
         buf = np.empty(nbytes, np.uint8)      # a buffer of its own per frame: the writer's queue holds views of it
         t, seq = C.c_double(), C.c_int64()
-        rc = lib.knpemi_snapshot_take(h, 1 if wait else 0, buf.ctypes.data_as(C.c_void_p), nbytes, C.byref(t), C.byref(seq))
+        rc = self._abi("take")(h, 1 if wait else 0, buf.ctypes.data_as(C.c_void_p), nbytes, C.byref(t), C.byref(seq))
         if rc == 1:
             return None
         if rc == L.EBUSY:
@@ -532,11 +537,12 @@ class Snapshots:
             if r is None or r is _BUSY:
                 break
             self._w.put(r)
-        rc = lib.knpemi_snapshot_record(h, float(t))
+        record = self._abi("record")
+        rc = record(h, float(t))
         if rc == L.EBUSY:
             self._w.put(self._take(True))
             self.stalls += 1
-            rc = lib.knpemi_snapshot_record(h, float(t))
+            rc = record(h, float(t))
         if rc == L.OK:
             self._ks.append(int(k))
         return rc
@@ -544,7 +550,7 @@ class Snapshots:
     def _rewind(self):
         """A new run: frames in flight are discarded, the frames already queued reach the sinks, the counters restart."""
         lib, h = self._dev
-        L.check(lib.knpemi_snapshot_reset(h))
+        L.check(self._abi("reset")(h))
         self._ks, self._t_of = [], {}
         self._w.drain()
         self._w.delivered = self._w.waits = 0
