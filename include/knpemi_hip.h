@@ -336,6 +336,74 @@ int knpemi_debug_ode_stamps(knpemi_handle* h, int sub, int model, uint64_t* out,
  * 1: kn_exp(a), 2: kn_powr(a, b), 3: kn_log(a).  a, b, out: n doubles each (b is ignored by ops 1 and 3). */
 int knpemi_debug_math(int op, int n, const double* a, const double* b, double* out);
 
+/* Diagnostics (no reference counterpart): runs ONE kernel of the device solves (csrc/kernels_krylov.hip, csrc/block_spmv.h,
+ * the device half of csrc/kernels_amg.hip) on host arrays, on the current device and the default stream, without a
+ * handle: upload, launch through the launch helper the solves themselves call (so grid, lanes per row and kernel choice
+ * are the solver's), check, copy back, free.  Tests hold each kernel to a plain reference of the same operation this way.
+ *
+ * buf[s]: host array of slot s (NULL: the kernel gets a null pointer where the slot is optional "?"), bytes[s] its size,
+ * out[s] != 0: copied back after the launch.  Every given array is uploaded first, so in/out arrays keep what the kernel
+ * leaves alone.  Index arrays (row pointers, columns, block columns, node lists) are checked against the sizes of the
+ * arrays they index before anything is launched.  n: rows / entries (> 0).  Slots (i = int32, d = double, u = uint8):
+ *  SPMV          ip: lanes per row (4, 16), columns.  0 rowptr i, 1 colind i, 2 vals d, 3 x d, 4 dinv? d, 5 b? d,
+ *                6 owned? u, 7 y d, 8 dinv_out? d
+ *  BLOCK_SPMV    n = rows; ip: NV, nbmax, unknowns of one system, kernel (-1: the process default, 0: row-wise, 1: cell-wise
+ *                where it is built).  0 rowptr i, 1 bcol i, 2 vals d, 3 x d, 4 b? d, 5 owned? u, 6 y d
+ *  DOTS          ip: nd, op (0 STORE3, 1 CG_INIT, 2 CG_PAP, 3 CG_RHO, 4 BI_RHO, 5 BI_ALPHA, 6 BI_OMEGA, 7 MEAN, 8 START),
+ *                d0, d1, d2, through red (0 / 1); dp: scale.  0..5 a0 b0 a1? b1? a2? b2? d, 6 sc d [16], 7 red? d [3].
+ *                The partial sums and the ticket live in one process-wide buffer that is kept between calls.
+ *  VEC           ip: op (0 RESID, 1 SHIFT, 2 CG_XR, 3 CG_P, 4 JACOBI, 5 BI_P, 6 BI_S, 7 COPY, 8 COPY_SHIFT).  0 sc d [16],
+ *                1 a d, 2 b? d, 3 c? d, 4 d? d
+ *  BICG_UPDATE   0 sc, 1 x, 2 r, 3 p, 4 s, 5 sres, 6 t, 7 dinv? (all d)
+ *  BICG_INIT     0 p d, 1 v d, 2 sc d [16]
+ *  MASK          ip: as_ones.  0 owned u, 1 a d
+ *  GHOST_IDENTITY 0 rowptr i, 1 colind i, 2 owned u, 3 vals d
+ *  DIAG_INV      0 rowptr i, 1 colind i, 2 vals d, 3 dinv d
+ *  SCATTER_SHIFT ip: stride.  0 src d, 1 dst d [n * stride], 2 sc d [16]
+ *  EXTRAPOLATE   ip: stride, have.  0 cur d [n * stride], 1 old d, 2 old2? d
+ *  KNP_ORDER     n = vertices of all sub-domains; ip: ks, n_sub, to_blocks, voff[0 .. n_sub].  0 x d [ks n], 1 csol d [ks n]
+ *  COARSE_RESTRICT n = length of r; ip: nl, rank, world.  0 r d, 1 agg_ptr i [nl + 1], 2 agg_idx i, 3 agg_wt d,
+ *                4 red d [8 + world nl]
+ *  COARSE_SOLVE  n = nl; ip: rank, nc.  0 inv d [nc nc], 1 red d [8 + nc], 2 zc d
+ *  COARSE_PROLONG ip: mode, pick, length of zc.  0 agg_of i, 1 agg_w d, 2 zc? d, 3 z d
+ *  AMG_SPMV      ip: mode (0 AX, 1 PRE, 2 ADD, 3 JAC, 4 RES), avg_row (picks 4 / 16 / 64 lanes), columns; dp: w.
+ *                0 rowptr i, 1 colind i, 2 vals d, 3 x? d, 4 r? d, 5 dinv? d, 6 y d, 7 xout? d
+ *  AMG_BLOCK_INV n = cells; ip: block size (3, 4, 8), nbmax, cells per system.  0 rowptr i, 1 colind i, 2 vals d,
+ *                3 bcol? i, 4 binv d
+ *  AMG_BLOCK_APPLY ip: block size; dp: w.  0 binv d, 1 v d, 2 x? d, 3 y d
+ *  AMG_DENSE     ip: nb, start[8], size[8], off[8].  0 Minv d, 1 r d, 2 x d
+ * KNPEMI_EINVAL (the message names the argument) for a null or short required array, n <= 0, an index out of range, or
+ * a lane count or block size that is not built; KNPEMI_EHIP without a device. */
+#define KNPEMI_LINALG_SPMV 0
+#define KNPEMI_LINALG_BLOCK_SPMV 1
+#define KNPEMI_LINALG_DOTS 2
+#define KNPEMI_LINALG_VEC 3
+#define KNPEMI_LINALG_BICG_UPDATE 4
+#define KNPEMI_LINALG_BICG_INIT 5
+#define KNPEMI_LINALG_MASK 6
+#define KNPEMI_LINALG_GHOST_IDENTITY 7
+#define KNPEMI_LINALG_DIAG_INV 8
+#define KNPEMI_LINALG_SCATTER_SHIFT 9
+#define KNPEMI_LINALG_EXTRAPOLATE 10
+#define KNPEMI_LINALG_KNP_ORDER 11
+#define KNPEMI_LINALG_COARSE_RESTRICT 12
+#define KNPEMI_LINALG_COARSE_SOLVE 13
+#define KNPEMI_LINALG_COARSE_PROLONG 14
+#define KNPEMI_LINALG_AMG_SPMV 20
+#define KNPEMI_LINALG_AMG_BLOCK_INV 21
+#define KNPEMI_LINALG_AMG_BLOCK_APPLY 22
+#define KNPEMI_LINALG_AMG_DENSE 23
+#define KNPEMI_LINALG_MAX_BUF 10
+typedef struct knpemi_debug_linalg_args {
+  int32_t n;
+  int32_t ip[28];
+  double dp[2];
+  void* buf[KNPEMI_LINALG_MAX_BUF];
+  uint64_t bytes[KNPEMI_LINALG_MAX_BUF];
+  int32_t out[KNPEMI_LINALG_MAX_BUF];
+} knpemi_debug_linalg_args;
+int knpemi_debug_linalg(int op, const knpemi_debug_linalg_args* args);
+
 /* Diagnostics (no reference counterpart): `links` dependent trivial kernels on the handle's stream, `reps` times, launched
  * one by one or replayed from a captured hipGraph; *us_per_kernel = host wall time per kernel.  kind 0: an empty one-wave
  * kernel, 1: y = x + 1 over n doubles, 2: the one-block start kernel of the fused Krylov loops.  What a dependent launch

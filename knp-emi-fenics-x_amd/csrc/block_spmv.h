@@ -93,13 +93,14 @@ inline bool block_spmv_by_cell() {
   return on;
 }
 
+// by_cell: the cell-wise kernel where one is built for (nv, nbmax); the default is the process's choice
 template <typename VT>
 inline void launch_block_spmv(hipStream_t st, const KnBlockCols& B, int rows, const int* rowptr, const VT* vals, const double* x,
-                              const double* b, double* y, const uint8_t* owned) {
-  if (B.nv == 8 && B.nbmax <= 7 && block_spmv_by_cell()) {
+                              const double* b, double* y, const uint8_t* owned, bool by_cell = block_spmv_by_cell()) {
+  if (B.nv == 8 && B.nbmax <= 7 && by_cell) {
     dim3 g(((size_t)rows * 8 + 255) / 256);
     hipLaunchKernelGGL((block_spmv_cell_kernel<8, 7, VT>), g, dim3(256), 0, st, rows, B.n, rowptr, B.bcol, B.nbmax, vals, x, b, y, owned);
-  } else if (B.nv == 4 && B.nbmax <= 5 && block_spmv_by_cell()) {
+  } else if (B.nv == 4 && B.nbmax <= 5 && by_cell) {
     dim3 g(((size_t)rows * 4 + 255) / 256);
     hipLaunchKernelGGL((block_spmv_cell_kernel<4, 5, VT>), g, dim3(256), 0, st, rows, B.n, rowptr, B.bcol, B.nbmax, vals, x, b, y, owned);
   } else if (B.nv == 8) {

@@ -195,12 +195,36 @@ void launch_spmv(hipStream_t st, int n, int avg_row, const int* rp, const int* c
   }
 }
 
+// y = (x ? x : 0) + w B^-1 v with blocks of `block` unknowns (3, 4, else 8).  On a stream and plain arguments, as the
+// two launches below: the cycle calls them with its hierarchy's members, knpemi_debug_linalg with a caller's arrays.
+void block_apply_launch(hipStream_t st, int block, const double* binv, double w, int n, const double* v, const double* x,
+                        double* y) {
+  dim3 g((n + 255) / 256);
+  if (block == 3) hipLaunchKernelGGL(amg_block_apply_kernel<3>, g, dim3(256), 0, st, n, binv, v, x, w, y);
+  else if (block == 4) hipLaunchKernelGGL(amg_block_apply_kernel<4>, g, dim3(256), 0, st, n, binv, v, x, w, y);
+  else hipLaunchKernelGGL(amg_block_apply_kernel<8>, g, dim3(256), 0, st, n, binv, v, x, w, y);
+}
+
 // y = (x ? x : 0) + omega_block B^-1 v on the finest level
 void block_apply(hipStream_t st, const KnAmg& G, int n, const double* v, const double* x, double* y) {
-  dim3 g((n + 255) / 256);
-  if (G.cfg.block == 3) hipLaunchKernelGGL(amg_block_apply_kernel<3>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
-  else if (G.cfg.block == 4) hipLaunchKernelGGL(amg_block_apply_kernel<4>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
-  else hipLaunchKernelGGL(amg_block_apply_kernel<8>, g, dim3(256), 0, st, n, G.binv, v, x, G.omega_block, y);
+  block_apply_launch(st, G.cfg.block, G.binv, G.omega_block, n, v, x, y);
+}
+
+// binv = the inverses of the nb diagonal blocks; false: no kernel is built for this block size
+bool block_inv_launch(hipStream_t st, int block, int nb, const int* rp, const int* ci, const double* vals, double* binv,
+                      const int* bc, int nbmax, int cps) {
+  dim3 g(((size_t)nb * 4 + 255) / 256), g8(((size_t)nb * 8 + 255) / 256);
+  if (block == 3) hipLaunchKernelGGL(amg_block_inv_kernel<3>, g, dim3(256), 0, st, nb, rp, ci, vals, binv, bc, nbmax, cps);
+  else if (block == 4) hipLaunchKernelGGL(amg_block_inv_kernel<4>, g, dim3(256), 0, st, nb, rp, ci, vals, binv, bc, nbmax, cps);
+  else if (block == 8) hipLaunchKernelGGL(amg_block_inv_kernel<8>, g8, dim3(256), 0, st, nb, rp, ci, vals, binv, bc, nbmax, cps);
+  else return false;
+  return true;
+}
+
+// x = Minv r on the dense coarsest level
+void dense_launch(hipStream_t st, int n, const double* Minv, const KnDenseBlocks& blk, const double* r, double* x) {
+  dim3 g(((size_t)n * 64 + 255) / 256);
+  hipLaunchKernelGGL(amg_dense_kernel, g, dim3(256), 0, st, n, Minv, blk, r, x);
 }
 
 // (blocking copies: the sources are temporaries of the set-up, which is host-bound anyway)
@@ -525,8 +549,7 @@ int kn_amg_apply(KnSolver& sv, KnAmg& G, const double* vals, const double* dinv0
     if (L.nc == 0) {
       double* dst = nl == 1 ? out : L.t;
       if (L.dense_inv) {
-        dim3 g(((size_t)L.n * 64 + 255) / 256);
-        hipLaunchKernelGGL(amg_dense_kernel, g, dim3(256), 0, st, L.n, L.dense_inv, L.dense_blk, rl, dst);
+        dense_launch(st, L.n, L.dense_inv, L.dense_blk, rl, dst);
       } else {   // Jacobi level: two damped sweeps from a zero guess
         launch_spmv<M_PRE>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, nullptr, rl, dinv, L.omega, xl == dst ? L.x : dst, xl);
         launch_spmv<M_JAC>(st, L.n, L.avg_row, L.A.rp, L.A.ci, Av, xl, rl, dinv, L.omega, dst);
@@ -560,13 +583,111 @@ int kn_amg_refresh(KnSolver& sv, KnAmg& G, const double* vals) {
   if (!G.built || G.cfg.block <= 0 || G.lev.empty() || G.lev[0].nc == 0) return KNPEMI_OK;
   const KnAmgLevel& L = G.lev[0];
   const int nb = L.n / G.cfg.block;
-  dim3 g(((size_t)nb * 4 + 255) / 256), g8(((size_t)nb * 8 + 255) / 256);
   const KnBlockCols& B = sv.bcols;
   const int* bc = (B.bcol && B.nv == G.cfg.block) ? B.bcol : nullptr;
   const int cps = bc ? B.n / B.nv : 1;
-  if (G.cfg.block == 3) hipLaunchKernelGGL(amg_block_inv_kernel<3>, g, dim3(256), 0, sv.own->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
-  else if (G.cfg.block == 4) hipLaunchKernelGGL(amg_block_inv_kernel<4>, g, dim3(256), 0, sv.own->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
-  else if (G.cfg.block == 8) hipLaunchKernelGGL(amg_block_inv_kernel<8>, g8, dim3(256), 0, sv.own->stream, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps);
-  else { kn_set_error("AMG: smoother blocks of 3, 4 or 8 unknowns only"); return KNPEMI_EINVAL; }
+  if (!block_inv_launch(sv.own->stream, G.cfg.block, nb, L.A.rp, L.A.ci, vals, G.binv, bc, B.nbmax, cps)) {
+    kn_set_error("AMG: smoother blocks of 3, 4 or 8 unknowns only");
+    return KNPEMI_EINVAL;
+  }
   return kn_launch_check("amg_block_inv_kernel");
+}
+
+// ---- diagnostics: the kernels above on a caller's host arrays (knpemi_debug_linalg, ops >= KNPEMI_LINALG_AMG_SPMV) --
+int kn_debug_linalg_amg(int op, const knpemi_debug_linalg_args& A) {
+  static const char* names[] = {"AMG_SPMV", "AMG_BLOCK_INV", "AMG_BLOCK_APPLY", "AMG_DENSE"};
+  KnDebugBufs B(A, names[op - KNPEMI_LINALG_AMG_SPMV]);
+  const int n = A.n;
+  const size_t N = (size_t)n, D = sizeof(double);
+  const int* ip = A.ip;
+  int rc = KNPEMI_OK;
+  KnDenseBlocks blk;
+  switch (op) {
+    case KNPEMI_LINALG_AMG_SPMV: {
+      const int mode = ip[0], ncols = ip[2];
+      if (mode < M_AX || mode > M_RES) return B.bad("mode (ip[0]) must be 0 .. 4");
+      if (ip[1] < 0) return B.bad("avg_row (ip[1]) must not be negative");
+      if (ncols <= 0) return B.bad("columns (ip[2]) must be positive");
+      if ((mode == M_PRE || mode == M_JAC) && ncols != n) return B.bad("columns (ip[2]): the smoothing modes need a square operator");
+      if ((rc = B.need(2, "vals", 0, D)) || (rc = B.check_rowptr(0, "rowptr", n, 2, D)) ||
+          (rc = B.check_range(1, "colind", (size_t)B.hi(0)[n], 0, ncols)) ||
+          (rc = B.need(3, "x", ncols, D, mode == M_PRE)) || (rc = B.need(4, "r", N, D, mode == M_AX || mode == M_ADD)) ||
+          (rc = B.need(5, "dinv", N, D, mode != M_PRE && mode != M_JAC)) || (rc = B.need(6, "y", N, D)) ||
+          (rc = B.need(7, "xout", N, D, mode != M_PRE))) return rc;
+      break;
+    }
+    case KNPEMI_LINALG_AMG_BLOCK_INV: {
+      const int bs = ip[0], nbmax = ip[1], cps = ip[2];
+      if (bs != 3 && bs != 4 && bs != 8) return B.bad("block size (ip[0]) must be 3, 4 or 8");
+      if (N * bs > (size_t)INT32_MAX) return B.bad("n: too many cells");
+      const int rows = n * bs;
+      if ((rc = B.need(2, "vals", 0, D)) || (rc = B.check_rowptr(0, "rowptr", rows, 2, D)) ||
+          (rc = B.need(4, "binv", N * bs * bs, D))) return rc;
+      if (A.buf[3]) {      // the diagonal block's position from the block list: every row holds whole blocks up to that one
+        if (nbmax < 1 || cps < 1) return B.bad("nbmax, cells per system (ip[1..2]) must be positive");
+        if ((rc = B.check_range(3, "bcol", (size_t)cps * nbmax, -1, cps))) return rc;
+        for (int c = 0; c < n; ++c) {
+          const int cl = c % cps;
+          int pos = 0;
+          for (int b = 0; b < nbmax; ++b) if (B.hi(3)[(size_t)cl * nbmax + b] == cl) pos = b;
+          for (int a = 0; a < bs; ++a)
+            if (B.hi(0)[c * bs + a + 1] - B.hi(0)[c * bs + a] < (pos + 1) * bs)
+              return B.bad("row " + std::to_string(c * bs + a) + " is shorter than its diagonal block's position");
+        }
+      } else if ((rc = B.need(1, "colind", (size_t)B.hi(0)[rows], sizeof(int)))) return rc;
+      break;
+    }
+    case KNPEMI_LINALG_AMG_BLOCK_APPLY: {
+      const int bs = ip[0];
+      if (bs != 3 && bs != 4 && bs != 8) return B.bad("block size (ip[0]) must be 3, 4 or 8");
+      if (n % bs) return B.bad("n must be a multiple of the block size");
+      if ((rc = B.need(0, "binv", N * bs, D)) || (rc = B.need(1, "v", N, D)) || (rc = B.need(2, "x", N, D, true)) ||
+          (rc = B.need(3, "y", N, D))) return rc;
+      break;
+    }
+    case KNPEMI_LINALG_AMG_DENSE: {
+      blk.nb = ip[0];
+      if (blk.nb < 1 || blk.nb > 8) return B.bad("nb (ip[0]) must be 1 .. 8");
+      size_t off = 0;
+      int start = 0;
+      for (int b = 0; b < blk.nb; ++b) {
+        blk.start[b] = ip[1 + b]; blk.size[b] = ip[9 + b]; blk.off[b] = ip[17 + b];
+        if (blk.size[b] < 1 || blk.start[b] != start || blk.off[b] < 0) return B.bad("blocks (ip[1 ..]): contiguous, non-empty");
+        start += blk.size[b];
+        off = std::max(off, (size_t)blk.off[b] + (size_t)blk.size[b] * blk.size[b]);
+      }
+      if (start != n) return B.bad("blocks (ip[1 ..]) must cover the n unknowns");
+      if ((rc = B.need(0, "Minv", off, D)) || (rc = B.need(1, "r", N, D)) || (rc = B.need(2, "x", N, D))) return rc;
+      break;
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return kn_fail(KNPEMI_EHIP, "knpemi_debug_linalg: no HIP device visible (the hot path has no CPU fallback)");
+  if ((rc = B.upload())) return rc;
+  hipStream_t st = nullptr;
+  const int *rp = B.p<int>(0), *ci = B.p<int>(1);
+  switch (op) {
+    case KNPEMI_LINALG_AMG_SPMV: {
+      const double *v = B.p<double>(2), *x = B.p<double>(3), *r = B.p<double>(4), *dinv = B.p<double>(5);
+      double *y = B.p<double>(6), *xout = B.p<double>(7);
+      switch (ip[0]) {
+        case M_AX: launch_spmv<M_AX>(st, n, ip[1], rp, ci, v, x, r, dinv, A.dp[0], y, xout); break;
+        case M_PRE: launch_spmv<M_PRE>(st, n, ip[1], rp, ci, v, x, r, dinv, A.dp[0], y, xout); break;
+        case M_ADD: launch_spmv<M_ADD>(st, n, ip[1], rp, ci, v, x, r, dinv, A.dp[0], y, xout); break;
+        case M_JAC: launch_spmv<M_JAC>(st, n, ip[1], rp, ci, v, x, r, dinv, A.dp[0], y, xout); break;
+        default: launch_spmv<M_RES>(st, n, ip[1], rp, ci, v, x, r, dinv, A.dp[0], y, xout); break;
+      }
+      break;
+    }
+    case KNPEMI_LINALG_AMG_BLOCK_INV:
+      (void)block_inv_launch(st, ip[0], n, rp, ci, B.p<double>(2), B.p<double>(4), B.p<int>(3), ip[1], ip[2]);
+      break;
+    case KNPEMI_LINALG_AMG_BLOCK_APPLY:
+      block_apply_launch(st, ip[0], B.p<double>(0), A.dp[0], n, B.p<double>(1), B.p<double>(2), B.p<double>(3));
+      break;
+    case KNPEMI_LINALG_AMG_DENSE: dense_launch(st, n, B.p<double>(0), blk, B.p<double>(1), B.p<double>(2)); break;
+  }
+  if ((rc = kn_launch_check(std::string("knpemi_debug_linalg(") + B.opname + ")"))) return rc;
+  return B.download();
 }

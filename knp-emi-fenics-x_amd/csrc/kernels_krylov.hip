@@ -350,8 +350,88 @@ int spmv_lanes(KnSolver& sv, int which, const int* rowptr, int n) {
 
 inline dim3 grid1(int n) { return dim3((n + 255) / 256); }
 
+// The launches of the plain kernels, on a stream and plain arguments: the solves below call them through their Ctx, and
+// knpemi_debug_linalg calls them on a caller's arrays, so the geometry a test sees is the geometry a solve runs.
+
+// lpr: 4, else 16 lanes per row
+void spmv_launch(hipStream_t st, int n, int lpr, const int* rowptr, const int* colind, const double* vals, const double* x,
+                 const double* dinv, double* y, const double* b, const uint8_t* owned, double* dinv_out) {
+  dim3 g(((size_t)n * lpr + 255) / 256);
+  if (lpr == 4) {
+    if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 4>), g, dim3(256), 0, st, n, rowptr, colind, vals, x, dinv, y,
+                                 (const double*)nullptr, owned);
+    else hipLaunchKernelGGL((spmv_kernel<false, 4>), g, dim3(256), 0, st, n, rowptr, colind, vals, x, dinv, y, b,
+                            owned, dinv_out);
+    return;
+  }
+  if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 16>), g, dim3(256), 0, st, n, rowptr, colind, vals, x, dinv, y,
+                               (const double*)nullptr, owned);
+  else hipLaunchKernelGGL((spmv_kernel<false, 16>), g, dim3(256), 0, st, n, rowptr, colind, vals, x, dinv, y, b,
+                          owned, dinv_out);
+}
+
+// partial: 3 * RED_BLOCKS partial sums and, behind them, the ticket counter (zero before the first launch)
+void dots_launch(hipStream_t st, int n, int nd, const double* a0, const double* b0, const double* a1, const double* b1,
+                 const double* a2, const double* b2, double* partial, double* sc, int op, int d0, int d1, int d2, double scale,
+                 double* red) {
+  // 16 entries per thread: every block costs ~50 ns at the ticket counter, whatever it sums
+  const int nb = std::min(RED_BLOCKS, (n + 16 * RED_THREADS - 1) / (16 * RED_THREADS));
+  hipLaunchKernelGGL(dots_kernel, dim3(nb), dim3(RED_THREADS), 0, st, n, nd, a0, b0, a1, b1, a2, b2, partial,
+                     reinterpret_cast<unsigned*>(partial + 3 * RED_BLOCKS), sc, op, d0, d1, d2, scale, red);
+}
+
+void dots_apply_launch(hipStream_t st, double* sc, const double* red, int op, int nd, int d0, int d1, int d2, double scale) {
+  hipLaunchKernelGGL(dots_apply_kernel, dim3(1), dim3(1), 0, st, sc, red, op, nd, d0, d1, d2, scale);
+}
+
+void mask_launch(hipStream_t st, int n, const uint8_t* owned, double* a, int as_ones) {
+  hipLaunchKernelGGL(mask_kernel, grid1(n), dim3(256), 0, st, n, owned, a, as_ones);
+}
+
+void vec_launch(hipStream_t st, int n, int op, const double* sc, double* a, double* b, const double* cc, const double* d) {
+  hipLaunchKernelGGL(vec_kernel, grid1(n), dim3(256), 0, st, n, op, sc, a, b, cc, d, (const double*)nullptr);
+}
+
+void ghost_identity_launch(hipStream_t st, int n, const int* rowptr, const int* colind, const uint8_t* owned, double* vals) {
+  hipLaunchKernelGGL(ghost_identity_kernel, grid1(n), dim3(256), 0, st, n, rowptr, colind, owned, vals);
+}
+
+void diag_inv_launch(hipStream_t st, int n, const int* rowptr, const int* colind, const double* vals, double* dinv) {
+  hipLaunchKernelGGL(diag_inv_kernel, grid1(n), dim3(256), 0, st, n, rowptr, colind, vals, dinv);
+}
+
+void scatter_shift_launch(hipStream_t st, const double* src, double* dst, int n, int stride, const double* sc) {
+  hipLaunchKernelGGL(scatter_shift_kernel, grid1(n), dim3(256), 0, st, src, dst, n, stride, sc);
+}
+
+void bicg_update_launch(hipStream_t st, int n, const double* sc, double* x, double* r, const double* p, const double* s,
+                        const double* sres, const double* t, const double* dinv) {
+  hipLaunchKernelGGL(bicg_update_kernel, grid1(n), dim3(256), 0, st, n, sc, x, r, p, s, sres, t, dinv);
+}
+
+void knp_order_launch(hipStream_t st, int ntot, int ks, int n_sub, const KnConsts* consts, double* x, double* csol, int to_blocks) {
+  hipLaunchKernelGGL(knp_order_kernel, grid1(ks * ntot), dim3(256), 0, st, ntot, ks, n_sub, consts, x, csol, to_blocks);
+}
+
+void extrapolate_launch(hipStream_t st, int n, double* cur, int stride, double* old, double* old2, int have) {
+  hipLaunchKernelGGL(extrapolate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, cur, stride, old, old2, have);
+}
+
+void coarse_restrict_launch(hipStream_t st, const double* r, const int* agg_ptr, const int* agg_idx, const double* agg_wt, int nl,
+                            int rank, int world, double* red) {
+  hipLaunchKernelGGL(coarse_restrict_kernel, dim3(nl), dim3(256), 0, st, r, agg_ptr, agg_idx, agg_wt, nl, rank, world, red);
+}
+
+void coarse_solve_launch(hipStream_t st, const double* inv, const double* red, int nl, int rank, int nc, double* zc) {
+  hipLaunchKernelGGL(coarse_solve_kernel, dim3(1), dim3(KN_COARSE_MAX), 0, st, inv, red, nl, rank, nc, zc);
+}
+
+void coarse_prolong_launch(hipStream_t st, int n, const int* agg_of, const double* agg_w, const double* zc, double* z, int mode,
+                           int pick) {
+  hipLaunchKernelGGL(coarse_prolong_kernel, grid1(n), dim3(256), 0, st, n, agg_of, agg_w, zc, z, mode, pick);
+}
+
 void spmv(Ctx& c, const double* x, double* y, const double* dinv, const double* b = nullptr, double* dinv_out = nullptr) {
-  dim3 g(((size_t)c.n * c.lpr + 255) / 256);
   if (c.owned) {   // the argument's ghost entries take their owners' values first
     const KnDist& d = c.sv.dist;
     if (int e = d.halo(d.ctx, const_cast<double*>(x), c.which)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
@@ -360,39 +440,26 @@ void spmv(Ctx& c, const double* x, double* y, const double* dinv, const double* 
     launch_block_spmv<double>(c.sv.own->stream, c.sv.bcols, c.n, c.rowptr, c.vals, x, b, y, c.owned);
     return;
   }
-  if (c.lpr == 4) {
-    if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 4>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y,
-                                 (const double*)nullptr, c.owned);
-    else hipLaunchKernelGGL((spmv_kernel<false, 4>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y, b,
-                            c.owned, dinv_out);
-    return;
-  }
-  if (dinv) hipLaunchKernelGGL((spmv_kernel<true, 16>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y,
-                               (const double*)nullptr, c.owned);
-  else hipLaunchKernelGGL((spmv_kernel<false, 16>), g, dim3(256), 0, c.sv.own->stream, c.n, c.rowptr, c.colind, c.vals, x, dinv, y, b,
-                          c.owned, dinv_out);
+  spmv_launch(c.sv.own->stream, c.n, c.lpr, c.rowptr, c.colind, c.vals, x, dinv, y, b, c.owned, dinv_out);
 }
 
 void dots(Ctx& c, int nd, const double* a0, const double* b0, const double* a1, const double* b1, const double* a2,
           const double* b2, int op, int d0 = 0, int d1 = 0, int d2 = 0, double scale = 1.0) {
-  // 16 entries per thread: every block costs ~50 ns at the ticket counter, whatever it sums
-  const int nb = std::min(RED_BLOCKS, (c.n + 16 * RED_THREADS - 1) / (16 * RED_THREADS));
   double* red = c.owned ? c.sv.dist.d_red : nullptr;
-  hipLaunchKernelGGL(dots_kernel, dim3(nb), dim3(RED_THREADS), 0, c.sv.own->stream, c.n, nd, a0, b0, a1, b1, a2, b2, c.partial,
-                     reinterpret_cast<unsigned*>(c.partial + 3 * RED_BLOCKS), c.sc, op, d0, d1, d2, scale, red);
+  dots_launch(c.sv.own->stream, c.n, nd, a0, b0, a1, b1, a2, b2, c.partial, c.sc, op, d0, d1, d2, scale, red);
   if (red) {   // every vector is zero on its ghost entries, so the local sums run over the owned unknowns only
     const KnDist& d = c.sv.dist;
     if (int e = d.allreduce(d.ctx, nd)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
-    hipLaunchKernelGGL(dots_apply_kernel, dim3(1), dim3(1), 0, c.sv.own->stream, c.sc, red, op, nd, d0, d1, d2, scale);
+    dots_apply_launch(c.sv.own->stream, c.sc, red, op, nd, d0, d1, d2, scale);
   }
 }
 
 void mask(const Ctx& c, double* a, int as_ones = 0) {
-  if (c.owned) hipLaunchKernelGGL(mask_kernel, grid1(c.n), dim3(256), 0, c.sv.own->stream, c.n, c.owned, a, as_ones);
+  if (c.owned) mask_launch(c.sv.own->stream, c.n, c.owned, a, as_ones);
 }
 
 void vec(const Ctx& c, int op, double* a, double* b, const double* cc, const double* d) {
-  hipLaunchKernelGGL(vec_kernel, grid1(c.n), dim3(256), 0, c.sv.own->stream, c.n, op, c.sc, a, b, cc, d, (const double*)nullptr);
+  vec_launch(c.sv.own->stream, c.n, op, c.sc, a, b, cc, d);
 }
 
 // the solver's scalars on the host: through a pinned buffer (a copy into pageable memory is staged by the runtime)
@@ -410,6 +477,10 @@ __global__ void bicg_init_kernel(int n, double* __restrict__ p, double* __restri
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { p[i] = 0.0; v[i] = 0.0; }
   if (i < S_N) sc[i] = (i == S_RHO || i == S_ALPHA || i == S_OMEGA) ? 1.0 : 0.0;
+}
+
+void bicg_init_launch(hipStream_t st, int n, double* p, double* v, double* sc) {
+  hipLaunchKernelGGL(bicg_init_kernel, grid1(std::max(n, (int)S_N)), dim3(256), 0, st, n, p, v, sc);
 }
 
 // Run `chunk` iterations of `body`: captured once into a hipGraph (the launch-bound inner loop of small
@@ -585,8 +656,7 @@ static int ensure_work(KnSolver& sv, size_t n) {
 static void coarse_restrict(Ctx& c, const double* r) {
   KnSolver& sv = c.sv;
   KnDist& d = sv.dist;
-  hipLaunchKernelGGL(coarse_restrict_kernel, dim3(d.nl), dim3(256), 0, sv.own->stream, r, d.d_agg_ptr, d.d_agg_idx, d.d_agg_wt, d.nl,
-                     d.rank, d.world, d.d_red);
+  coarse_restrict_launch(sv.own->stream, r, d.d_agg_ptr, d.d_agg_idx, d.d_agg_wt, d.nl, d.rank, d.world, d.d_red);
   if (int e = d.allreduce(d.ctx, KN_COARSE_OFF + d.nc)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
 }
 
@@ -608,8 +678,7 @@ static int coarse_setup(Ctx& c, double* work_phi, double* work_y) {
   for (int j = 0; j < nc; ++j) {
     const int rj = j / nl, aj = j % nl;
     // phi_j: 1 on the owned unknowns of aggregate aj of rank rj (ghost copies are filled by the SpMV's halo), 0 elsewhere
-    hipLaunchKernelGGL(coarse_prolong_kernel, grid1(c.n), dim3(256), 0, sv.own->stream, c.n, d.d_agg_of, d.d_agg_w,
-                       (const double*)nullptr, work_phi, 1, rj == d.rank ? aj : -2);
+    coarse_prolong_launch(sv.own->stream, c.n, d.d_agg_of, d.d_agg_w, nullptr, work_phi, 1, rj == d.rank ? aj : -2);
     spmv(c, work_phi, work_y, nullptr);
     coarse_restrict(c, work_y);
     if (int rc = kn_to_host(sv.own->stream, col.data(), d.d_red + KN_COARSE_OFF, nc)) return rc;
@@ -658,9 +727,8 @@ static void coarse_correct(Ctx& c, const double* r, double* z) {
   KnSolver& sv = c.sv;
   KnDist& d = sv.dist;
   coarse_restrict(c, r);
-  hipLaunchKernelGGL(coarse_solve_kernel, dim3(1), dim3(KN_COARSE_MAX), 0, sv.own->stream, d.d_coarse_inv, d.d_red, d.nl, d.rank, d.nc,
-                     d.d_coarse_z);
-  hipLaunchKernelGGL(coarse_prolong_kernel, grid1(c.n), dim3(256), 0, sv.own->stream, c.n, d.d_agg_of, d.d_agg_w, d.d_coarse_z, z, 0, 0);
+  coarse_solve_launch(sv.own->stream, d.d_coarse_inv, d.d_red, d.nl, d.rank, d.nc, d.d_coarse_z);
+  coarse_prolong_launch(sv.own->stream, c.n, d.d_agg_of, d.d_agg_w, d.d_coarse_z, z, 0, 0);
 }
 
 // Jacobi-PCG on A_emi x = b_emi, x = phi (KnSolver::phi: a component of the records, gathered into a contiguous vector first).
@@ -682,7 +750,7 @@ int kn_solve_emi(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
     c.which = KNPEMI_B_EMI;
     n_mean = dist.n_owned_global;
     for (uint8_t o : dist.h_owned_emi) has_ghosts |= !o;
-    hipLaunchKernelGGL(ghost_identity_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.owned, D.A);
+    ghost_identity_launch(sv.own->stream, n, c.rowptr, c.colind, c.owned, D.A);
   }
   if (sv.kry_ones_masked != (dist.on ? 1 : 0)) {   // `ones` counts the owned unknowns
     if (dist.on) mask(c, ones, 1);
@@ -707,7 +775,7 @@ int kn_solve_emi(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
       vec(c, V_COPY_SHIFT, b, nullptr, D.b, nullptr);
     }
     // (single rank: the inverse diagonal comes out of the first residual below)
-    if (dist.on) hipLaunchKernelGGL(diag_inv_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.vals, dinv);
+    if (dist.on) diag_inv_launch(sv.own->stream, n, c.rowptr, c.colind, c.vals, dinv);
     return KNPEMI_OK;
   };
   // solution orthogonal to constants, then into the phi component of the vertex records (ghosts included: they take
@@ -719,7 +787,7 @@ int kn_solve_emi(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
       vec(c, V_SHIFT, x, nullptr, nullptr, nullptr);
       if (int e = kn_launch_field_scatter(sv.own->stream, x, sv.phi, n, sv.phi_stride)) return e;
     } else if (n > 0) {
-      hipLaunchKernelGGL(scatter_shift_kernel, grid1(n), dim3(256), 0, sv.own->stream, x, sv.phi, n, sv.phi_stride, c.sc);
+      scatter_shift_launch(sv.own->stream, x, sv.phi, n, sv.phi_stride, c.sc);
     }
     return KNPEMI_OK;
   };
@@ -811,7 +879,7 @@ int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
   if (dist.on) {
     c.owned = dist.d_owned_knp;
     c.which = KNPEMI_B_KNP;
-    hipLaunchKernelGGL(ghost_identity_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.owned, D.A);
+    ghost_identity_launch(sv.own->stream, n, c.rowptr, c.colind, c.owned, D.A);
     mask(c, D.b);      // the ghost rows of the right-hand side are not assembled
   }
   // x0 = previous concentrations in the solver's order (first launch of the solve: with the fused loop it opens the
@@ -832,7 +900,7 @@ int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
   KnAmg& G = sv.amg_knp;
   const bool amg = sv.pc_knp == KNPEMI_PC_AMG;
   if (dist.on) {
-    hipLaunchKernelGGL(diag_inv_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.rowptr, c.colind, c.vals, dinv);
+    diag_inv_launch(sv.own->stream, n, c.rowptr, c.colind, c.vals, dinv);
     // Jacobi: the scaled SpMV A (dinv .* p) reads dinv on ghost columns, where the identity rows above left 1: take the
     // owners' 1 / a_ii instead, so that the recurrence residual stays b - A x (x is updated with the owners' dinv)
     if (!amg) if (int e = dist.halo(dist.ctx, dinv, KNPEMI_B_KNP)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
@@ -851,7 +919,7 @@ int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
     if (fused_planned && (rc = pre())) return rc;      // (the hierarchy did not qualify for the fused loop after all)
     spmv(c, x, r, nullptr, D.b, dist.on ? nullptr : dinv);   // r = b - A x
     vec(c, V_COPY, rhat, nullptr, r, nullptr);
-    hipLaunchKernelGGL(bicg_init_kernel, grid1(std::max(n, (int)S_N)), dim3(256), 0, sv.own->stream, n, p, v, c.sc);
+    bicg_init_launch(sv.own->stream, n, p, v, c.sc);
     dots(c, 2, r, r, D.b, D.b, nullptr, nullptr, OP_START);
     if ((rc = read_scalars(c, sc, S_N))) return rc;
     if ((rc = check_start("KNP BiCGStab", sc))) return rc;
@@ -876,11 +944,8 @@ int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
         spmv(c, shat, t, nullptr);
       } else spmv(c, s, t, dinv);                           // t = A M^-1 s
       dots(c, 2, t, s, t, t, nullptr, nullptr, OP_BI_OMEGA);
-      if (amg)
-        hipLaunchKernelGGL(bicg_update_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.sc, x, r, phat, shat, s, t,
-                           (const double*)nullptr);
-      else
-        hipLaunchKernelGGL(bicg_update_kernel, grid1(n), dim3(256), 0, sv.own->stream, n, c.sc, x, r, p, s, s, t, dinv);
+      if (amg) bicg_update_launch(sv.own->stream, n, c.sc, x, r, phat, shat, s, t, nullptr);
+      else bicg_update_launch(sv.own->stream, n, c.sc, x, r, p, s, s, t, dinv);
       dots(c, 1, r, r, nullptr, nullptr, nullptr, nullptr, OP_STORE3, S_RR);
     return rc;
   };
@@ -908,7 +973,7 @@ int kn_solve_knp(KnSolver& sv, double rtol, double atol, int maxit, int* iters, 
         return KNPEMI_ESOLVE;
       }
       vec(c, V_COPY, rhat, nullptr, r, nullptr);
-      hipLaunchKernelGGL(bicg_init_kernel, grid1(std::max(n, (int)S_N)), dim3(256), 0, sv.own->stream, n, p, v, c.sc);
+      bicg_init_launch(sv.own->stream, n, p, v, c.sc);
     }
   }
   if (dist.on) if (int e = dist.halo(dist.ctx, x, KNPEMI_B_KNP)) c.comm_rc = c.comm_rc ? c.comm_rc : e;
@@ -927,8 +992,7 @@ int kn_launch_knp_order(knpemi_handle* h, double* x, int to_blocks) {
   const KnDev& D = h->dev;
   const int n = (h->K - 1) * D.Ntot;
   if (n == 0) return KNPEMI_OK;
-  hipLaunchKernelGGL(knp_order_kernel, grid1(n), dim3(256), 0, h->stream, D.Ntot, h->K - 1, h->n_sub, h->d_consts, x, D.csol,
-                     to_blocks);
+  knp_order_launch(h->stream, D.Ntot, h->K - 1, h->n_sub, h->d_consts, x, D.csol, to_blocks);
   return kn_launch_check("knp_order_kernel");
 }
 
@@ -951,8 +1015,235 @@ int kn_extrapolate_guess(KnSolver& sv, int which) {
   // second and third solves of a run twice their iterations
   if (sv.guess_have[slot] < 0) { sv.guess_have[slot] = 0; return KNPEMI_OK; }
   double* cur = slot == 0 ? sv.phi : sv.csol;
-  hipLaunchKernelGGL(extrapolate_kernel, dim3((n + 255) / 256), dim3(256), 0, sv.own->stream, n, cur, slot == 0 ? sv.phi_stride : 1,
-                     sv.guess_old[slot], order >= 2 ? sv.guess_old[slot] + n : (double*)nullptr, sv.guess_have[slot]);
+  extrapolate_launch(sv.own->stream, n, cur, slot == 0 ? sv.phi_stride : 1, sv.guess_old[slot],
+                     order >= 2 ? sv.guess_old[slot] + n : (double*)nullptr, sv.guess_have[slot]);
   sv.guess_have[slot] = std::min(2, sv.guess_have[slot] + 1);
   return kn_launch_check("extrapolate_kernel");
+}
+
+// ---- diagnostics: one solver kernel on a caller's host arrays (knpemi_debug_linalg) ------------------------------
+namespace {
+
+// partial sums + ticket of the reductions, kept between calls as a solve keeps its workspace
+double* g_debug_partial = nullptr;
+
+int debug_partial(double** out) {
+  if (!g_debug_partial) {
+    const size_t bytes = (3 * RED_BLOCKS + 2) * sizeof(double);
+    KN_HIP(hipMalloc(reinterpret_cast<void**>(&g_debug_partial), bytes));
+    KN_HIP(hipMemset(g_debug_partial, 0, bytes));
+  }
+  *out = g_debug_partial;
+  return KNPEMI_OK;
+}
+
+const char* debug_opname(int op) {
+  static const char* names[] = {"SPMV", "BLOCK_SPMV", "DOTS", "VEC", "BICG_UPDATE", "BICG_INIT", "MASK", "GHOST_IDENTITY",
+                                "DIAG_INV", "SCATTER_SHIFT", "EXTRAPOLATE", "KNP_ORDER", "COARSE_RESTRICT", "COARSE_SOLVE",
+                                "COARSE_PROLONG"};
+  return op >= 0 && op <= KNPEMI_LINALG_COARSE_PROLONG ? names[op] : "?";
+}
+
+// CSR pattern of n rows and ncols columns in slots 0 (rowptr), 1 (colind); the values in slot 2
+int debug_check_csr(const KnDebugBufs& B, int n, int ncols) {
+  int rc;
+  if ((rc = B.need(2, "vals", 0, sizeof(double)))) return rc;
+  if ((rc = B.check_rowptr(0, "rowptr", n, 2, sizeof(double)))) return rc;
+  return B.check_range(1, "colind", (size_t)B.hi(0)[n], 0, ncols);
+}
+
+// what the block kernels read: whole cells of nv rows of equal length, a whole number of blocks each, and a block column
+// for every block
+int debug_check_blocks(const KnDebugBufs& B, int rows, int nv, int nbmax, int nsys) {
+  int rc;
+  if (nv != 3 && nv != 4 && nv != 8) return B.bad("NV (ip[0]) must be 3, 4 or 8");
+  if (nbmax < 1) return B.bad("nbmax (ip[1]) must be positive");
+  if (nsys <= 0 || nsys % nv || rows % nsys) return B.bad("unknowns of one system (ip[2]): a multiple of NV that divides the rows");
+  const int cells = nsys / nv;
+  if ((rc = B.need(2, "vals", 0, sizeof(double)))) return rc;
+  if ((rc = B.check_rowptr(0, "rowptr", rows, 2, sizeof(double)))) return rc;
+  if ((rc = B.check_range(1, "bcol", (size_t)cells * nbmax, -1, cells))) return rc;
+  const int* rp = B.hi(0);
+  for (int row = 0; row < rows; ++row) {
+    const int len = rp[row + 1] - rp[row], first = row - row % nv;
+    if (len % nv || len / nv > nbmax) return B.bad("row " + std::to_string(row) + ": not a whole number of blocks <= nbmax");
+    if (len != rp[first + 1] - rp[first]) return B.bad("row " + std::to_string(row) + ": the rows of a cell differ in length");
+    const int cl = (row % nsys) / nv;
+    for (int k = 0; k < len / nv; ++k)
+      if (B.hi(1)[(size_t)cl * nbmax + k] < 0) return B.bad("cell " + std::to_string(cl) + ": a block without a block column");
+  }
+  return KNPEMI_OK;
+}
+
+}  // namespace
+
+extern "C" int knpemi_debug_linalg(int op, const knpemi_debug_linalg_args* args) {
+  if (!args) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_linalg: args is null");
+  const knpemi_debug_linalg_args& A = *args;
+  const bool amg_op = op >= KNPEMI_LINALG_AMG_SPMV && op <= KNPEMI_LINALG_AMG_DENSE;
+  if (!amg_op && (op < 0 || op > KNPEMI_LINALG_COARSE_PROLONG)) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_linalg: unknown op");
+  if (A.n <= 0) return kn_fail(KNPEMI_EINVAL, "knpemi_debug_linalg: n must be positive");
+  if (amg_op) return kn_debug_linalg_amg(op, A);
+  KnDebugBufs B(A, debug_opname(op));
+  const int n = A.n;
+  const size_t N = (size_t)n, D = sizeof(double);
+  const int* ip = A.ip;
+  int rc = KNPEMI_OK;
+  KnConsts consts{};
+  // the arguments first: a refusal needs no device
+  switch (op) {
+    case KNPEMI_LINALG_SPMV:
+      if (ip[0] != 4 && ip[0] != 16) return B.bad("lanes per row (ip[0]) must be 4 or 16");
+      if (ip[1] <= 0) return B.bad("columns (ip[1]) must be positive");
+      if ((rc = debug_check_csr(B, n, ip[1])) || (rc = B.need(3, "x", ip[1], D)) || (rc = B.need(4, "dinv", ip[1], D, true)) ||
+          (rc = B.need(5, "b", N, D, true)) || (rc = B.need(6, "owned", N, 1, true)) || (rc = B.need(7, "y", N, D)) ||
+          (rc = B.need(8, "dinv_out", N, D, true))) return rc;
+      break;
+    case KNPEMI_LINALG_BLOCK_SPMV:
+      if (ip[3] < -1 || ip[3] > 1) return B.bad("kernel (ip[3]) must be -1, 0 or 1");
+      if ((rc = debug_check_blocks(B, n, ip[0], ip[1], ip[2])) || (rc = B.need(3, "x", N, D)) || (rc = B.need(4, "b", N, D, true)) ||
+          (rc = B.need(5, "owned", N, 1, true)) || (rc = B.need(6, "y", N, D))) return rc;
+      break;
+    case KNPEMI_LINALG_DOTS:
+      if (ip[0] < 1 || ip[0] > 3) return B.bad("nd (ip[0]) must be 1, 2 or 3");
+      if (ip[1] < OP_STORE3 || ip[1] > OP_START) return B.bad("op (ip[1]) is not a scalar step");
+      for (int k = 2; k <= 4; ++k) if (ip[k] < 0 || ip[k] >= S_N) return B.bad("d0, d1, d2 (ip[2..4]) must be scalar slots");
+      for (int k = 0; k < 2 * ip[0]; ++k) if ((rc = B.need(k, "a vector of the dot products", N, D))) return rc;
+      if ((rc = B.need(6, "sc", 16, D)) || (rc = B.need(7, "red", 3, D, !ip[5]))) return rc;
+      break;
+    case KNPEMI_LINALG_VEC: {
+      const int vop = ip[0];
+      if (vop < V_RESID || vop > V_COPY_SHIFT) return B.bad("op (ip[0]) is not a vector update");
+      const bool need_b = vop == V_CG_XR, need_c = vop != V_SHIFT;
+      const bool need_d = vop == V_RESID || vop == V_CG_XR || vop == V_JACOBI || vop == V_BI_P || vop == V_BI_S;
+      if ((rc = B.need(0, "sc", 16, D)) || (rc = B.need(1, "a", N, D)) || (rc = B.need(2, "b", N, D, !need_b)) ||
+          (rc = B.need(3, "c", N, D, !need_c)) || (rc = B.need(4, "d", N, D, !need_d))) return rc;
+      break;
+    }
+    case KNPEMI_LINALG_BICG_UPDATE:
+      if ((rc = B.need(0, "sc", 16, D))) return rc;
+      for (int s = 1; s <= 6; ++s) if ((rc = B.need(s, "x, r, p, s, sres or t", N, D))) return rc;
+      if ((rc = B.need(7, "dinv", N, D, true))) return rc;
+      break;
+    case KNPEMI_LINALG_BICG_INIT:
+      if ((rc = B.need(0, "p", N, D)) || (rc = B.need(1, "v", N, D)) || (rc = B.need(2, "sc", 16, D))) return rc;
+      break;
+    case KNPEMI_LINALG_MASK:
+      if ((rc = B.need(0, "owned", N, 1)) || (rc = B.need(1, "a", N, D))) return rc;
+      break;
+    case KNPEMI_LINALG_GHOST_IDENTITY:
+      if ((rc = B.need(3, "vals", 0, D)) || (rc = B.check_rowptr(0, "rowptr", n, 3, D)) ||
+          (rc = B.need(1, "colind", (size_t)B.hi(0)[n], sizeof(int))) || (rc = B.need(2, "owned", N, 1))) return rc;
+      break;
+    case KNPEMI_LINALG_DIAG_INV:
+      if ((rc = debug_check_csr(B, n, n)) || (rc = B.need(3, "dinv", N, D))) return rc;
+      break;
+    case KNPEMI_LINALG_SCATTER_SHIFT:
+      if (ip[0] < 1) return B.bad("stride (ip[0]) must be positive");
+      if ((rc = B.need(0, "src", N, D)) || (rc = B.need(1, "dst", N * ip[0], D)) || (rc = B.need(2, "sc", 16, D))) return rc;
+      break;
+    case KNPEMI_LINALG_EXTRAPOLATE:
+      if (ip[0] < 1) return B.bad("stride (ip[0]) must be positive");
+      if ((rc = B.need(0, "cur", N * ip[0], D)) || (rc = B.need(1, "old", N, D)) || (rc = B.need(2, "old2", N, D, true))) return rc;
+      break;
+    case KNPEMI_LINALG_KNP_ORDER: {
+      const int ks = ip[0], n_sub = ip[1];
+      if (ks < 1 || ks > 8) return B.bad("ks (ip[0]) must be 1 .. 8");
+      if (n_sub < 1 || n_sub > KN_MAXSUB) return B.bad("n_sub (ip[1]) must be 1 .. 8");
+      if (ip[3] != 0 || ip[3 + n_sub] != n) return B.bad("voff (ip[3 ..]) must run from 0 to n");
+      for (int s = 0; s < n_sub; ++s) if (ip[3 + s + 1] < ip[3 + s]) return B.bad("voff (ip[3 ..]) decreases");
+      consts.n_sub = n_sub; consts.K = ks + 1;
+      for (int s = 0; s <= n_sub; ++s) consts.voff[s] = ip[3 + s];
+      if ((rc = B.need(0, "x", N * ks, D)) || (rc = B.need(1, "csol", N * ks, D))) return rc;
+      break;
+    }
+    case KNPEMI_LINALG_COARSE_RESTRICT: {
+      const int nl = ip[0], rank = ip[1], world = ip[2];
+      if (nl < 1 || world < 1 || rank < 0 || rank >= world || world * nl > KN_COARSE_MAX)
+        return B.bad("nl, rank, world (ip[0..2]): 0 <= rank < world, 1 <= world nl <= 64");
+      if ((rc = B.need(0, "r", N, D)) || (rc = B.need(3, "agg_wt", 0, D)) || (rc = B.check_rowptr(1, "agg_ptr", nl, 3, D)) ||
+          (rc = B.check_range(2, "agg_idx", (size_t)B.hi(1)[nl], 0, n)) ||
+          (rc = B.need(4, "red", (size_t)KN_COARSE_OFF + world * nl, D))) return rc;
+      break;
+    }
+    case KNPEMI_LINALG_COARSE_SOLVE: {
+      const int rank = ip[0], nc = ip[1];
+      if (n > KN_COARSE_MAX || rank < 0 || nc > KN_COARSE_MAX || (rank + 1) * n > nc) return B.bad("nl (n), rank, nc (ip[0..1]): (rank + 1) nl <= nc <= 64");
+      if ((rc = B.need(0, "inv", (size_t)nc * nc, D)) || (rc = B.need(1, "red", (size_t)KN_COARSE_OFF + nc, D)) ||
+          (rc = B.need(2, "zc", N, D))) return rc;
+      break;
+    }
+    case KNPEMI_LINALG_COARSE_PROLONG: {
+      const int mode = ip[0], nz = ip[2];
+      if (mode != 0 && mode != 1) return B.bad("mode (ip[0]) must be 0 or 1");
+      if ((rc = B.need(1, "agg_w", N, D)) || (rc = B.need(3, "z", N, D))) return rc;
+      if (mode == 0) {
+        if (nz < 1) return B.bad("length of zc (ip[2]) must be positive");
+        if ((rc = B.need(2, "zc", nz, D)) || (rc = B.check_range(0, "agg_of", N, -1, nz))) return rc;
+        const double* w = static_cast<const double*>(A.buf[1]);
+        for (int i = 0; i < n; ++i)
+          if (B.hi(0)[i] >= 0 && w[i] > 0.0 && B.hi(0)[i] + 1 >= nz) return B.bad("agg_of: the upper node of an unknown lies past zc");
+      } else if ((rc = B.need(0, "agg_of", N, sizeof(int)))) return rc;
+      break;
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return kn_fail(KNPEMI_EHIP, "knpemi_debug_linalg: no HIP device visible (the hot path has no CPU fallback)");
+  if ((rc = B.upload())) return rc;
+  hipStream_t st = nullptr;
+  switch (op) {
+    case KNPEMI_LINALG_SPMV:
+      spmv_launch(st, n, ip[0], B.p<int>(0), B.p<int>(1), B.p<double>(2), B.p<double>(3), B.p<double>(4), B.p<double>(7),
+                  B.p<double>(5), B.p<uint8_t>(6), B.p<double>(8));
+      break;
+    case KNPEMI_LINALG_BLOCK_SPMV: {
+      KnBlockCols bc;
+      bc.bcol = B.p<int>(1); bc.nv = ip[0]; bc.nbmax = ip[1]; bc.n = ip[2];
+      if (ip[3] < 0) launch_block_spmv<double>(st, bc, n, B.p<int>(0), B.p<double>(2), B.p<double>(3), B.p<double>(4), B.p<double>(6), B.p<uint8_t>(5));
+      else launch_block_spmv<double>(st, bc, n, B.p<int>(0), B.p<double>(2), B.p<double>(3), B.p<double>(4), B.p<double>(6), B.p<uint8_t>(5), ip[3] == 1);
+      break;
+    }
+    case KNPEMI_LINALG_DOTS: {
+      double* partial = nullptr;
+      if ((rc = debug_partial(&partial))) return rc;
+      double* red = ip[5] ? B.p<double>(7) : nullptr;
+      dots_launch(st, n, ip[0], B.p<double>(0), B.p<double>(1), B.p<double>(2), B.p<double>(3), B.p<double>(4), B.p<double>(5), partial,
+                  B.p<double>(6), ip[1], ip[2], ip[3], ip[4], A.dp[0], red);
+      if (red) dots_apply_launch(st, B.p<double>(6), red, ip[1], ip[0], ip[2], ip[3], ip[4], A.dp[0]);
+      break;
+    }
+    case KNPEMI_LINALG_VEC:
+      vec_launch(st, n, ip[0], B.p<double>(0), B.p<double>(1), B.p<double>(2), B.p<double>(3), B.p<double>(4));
+      break;
+    case KNPEMI_LINALG_BICG_UPDATE:
+      bicg_update_launch(st, n, B.p<double>(0), B.p<double>(1), B.p<double>(2), B.p<double>(3), B.p<double>(4), B.p<double>(5),
+                         B.p<double>(6), B.p<double>(7));
+      break;
+    case KNPEMI_LINALG_BICG_INIT: bicg_init_launch(st, n, B.p<double>(0), B.p<double>(1), B.p<double>(2)); break;
+    case KNPEMI_LINALG_MASK: mask_launch(st, n, B.p<uint8_t>(0), B.p<double>(1), ip[0]); break;
+    case KNPEMI_LINALG_GHOST_IDENTITY: ghost_identity_launch(st, n, B.p<int>(0), B.p<int>(1), B.p<uint8_t>(2), B.p<double>(3)); break;
+    case KNPEMI_LINALG_DIAG_INV: diag_inv_launch(st, n, B.p<int>(0), B.p<int>(1), B.p<double>(2), B.p<double>(3)); break;
+    case KNPEMI_LINALG_SCATTER_SHIFT: scatter_shift_launch(st, B.p<double>(0), B.p<double>(1), n, ip[0], B.p<double>(2)); break;
+    case KNPEMI_LINALG_EXTRAPOLATE: extrapolate_launch(st, n, B.p<double>(0), ip[0], B.p<double>(1), B.p<double>(2), ip[1]); break;
+    case KNPEMI_LINALG_KNP_ORDER: {
+      KnConsts* dc = nullptr;
+      KN_HIP(hipMalloc(reinterpret_cast<void**>(&dc), sizeof(KnConsts)));
+      if (hipMemcpy(dc, &consts, sizeof(KnConsts), hipMemcpyHostToDevice) == hipSuccess) {
+        knp_order_launch(st, n, ip[0], ip[1], dc, B.p<double>(0), B.p<double>(1), ip[2]);
+        (void)hipDeviceSynchronize();
+      }
+      (void)hipFree(dc);
+      break;
+    }
+    case KNPEMI_LINALG_COARSE_RESTRICT:
+      coarse_restrict_launch(st, B.p<double>(0), B.p<int>(1), B.p<int>(2), B.p<double>(3), ip[0], ip[1], ip[2], B.p<double>(4));
+      break;
+    case KNPEMI_LINALG_COARSE_SOLVE: coarse_solve_launch(st, B.p<double>(0), B.p<double>(1), n, ip[0], ip[1], B.p<double>(2)); break;
+    case KNPEMI_LINALG_COARSE_PROLONG:
+      coarse_prolong_launch(st, n, B.p<int>(0), B.p<double>(1), B.p<double>(2), B.p<double>(3), ip[0], ip[1]);
+      break;
+  }
+  if ((rc = kn_launch_check(std::string("knpemi_debug_linalg(") + B.opname + ")"))) return rc;
+  return B.download();
 }

@@ -508,6 +508,61 @@ inline int kn_set_lds_limit(const void* kernel, size_t bytes) {
   return e == hipSuccess ? KNPEMI_OK
                          : kn_fail(KNPEMI_EHIP, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
 }
+// knpemi_debug_linalg: the device copies of the caller's arrays (upload of every given slot, copy-back of the slots
+// marked `out`, free), and the checks its dispatchers share.  The dispatch of an op lives in the translation unit that owns
+// the kernel: kernels_krylov.hip (the entry itself) and kernels_amg.hip (kn_debug_linalg_amg, ops >= KNPEMI_LINALG_AMG_SPMV).
+struct KnDebugBufs {
+  const knpemi_debug_linalg_args& A;
+  const char* opname;
+  void* d[KNPEMI_LINALG_MAX_BUF] = {};
+  KnDebugBufs(const knpemi_debug_linalg_args& a, const char* name) : A(a), opname(name) {}
+  ~KnDebugBufs() { for (void* p : d) if (p) (void)hipFree(p); }
+  KnDebugBufs(const KnDebugBufs&) = delete;
+  KnDebugBufs& operator=(const KnDebugBufs&) = delete;
+  int bad(const std::string& what) const { return kn_fail(KNPEMI_EINVAL, std::string("knpemi_debug_linalg(") + opname + "): " + what); }
+  // slot s holds at least `count` elements of `elem` bytes (required), or is absent (optional)
+  int need(int s, const char* name, size_t count, size_t elem, bool optional = false) const {
+    if (!A.buf[s]) return optional ? KNPEMI_OK : bad(std::string(name) + " (buf[" + std::to_string(s) + "]) is null");
+    if (A.bytes[s] < count * elem)
+      return bad(std::string(name) + " (buf[" + std::to_string(s) + "]) holds " + std::to_string(A.bytes[s]) + " bytes, " +
+                 std::to_string(count * elem) + " needed");
+    return KNPEMI_OK;
+  }
+  const int* hi(int s) const { return static_cast<const int*>(A.buf[s]); }
+  // row pointers of `rows` rows into an entry array of slot `s_entries` (elements of `elem` bytes)
+  int check_rowptr(int s, const char* name, int rows, int s_entries, size_t elem) const {
+    if (int rc = need(s, name, (size_t)rows + 1, sizeof(int))) return rc;
+    const int* rp = hi(s);
+    if (rp[0] < 0) return bad(std::string(name) + "[0] is negative");
+    for (int i = 0; i < rows; ++i) if (rp[i + 1] < rp[i]) return bad(std::string(name) + " decreases at row " + std::to_string(i));
+    if ((size_t)rp[rows] * elem > A.bytes[s_entries]) return bad(std::string(name) + " runs past the entries of buf[" + std::to_string(s_entries) + "]");
+    return KNPEMI_OK;
+  }
+  // the first `count` entries of slot s lie in [lo, hi)
+  int check_range(int s, const char* name, size_t count, int lo, int hi_) const {
+    if (int rc = need(s, name, count, sizeof(int))) return rc;
+    for (size_t i = 0; i < count; ++i)
+      if (hi(s)[i] < lo || hi(s)[i] >= hi_) return bad(std::string(name) + "[" + std::to_string(i) + "] = " + std::to_string(hi(s)[i]) + " is out of range");
+    return KNPEMI_OK;
+  }
+  int upload() {
+    for (int s = 0; s < KNPEMI_LINALG_MAX_BUF; ++s) {
+      if (!A.buf[s]) continue;
+      KN_HIP(hipMalloc(&d[s], A.bytes[s] ? A.bytes[s] : 8));      // (an empty array is still a non-null pointer)
+      if (A.bytes[s]) KN_HIP(hipMemcpy(d[s], A.buf[s], A.bytes[s], hipMemcpyHostToDevice));
+    }
+    return KNPEMI_OK;
+  }
+  int download() {
+    KN_HIP(hipDeviceSynchronize());
+    for (int s = 0; s < KNPEMI_LINALG_MAX_BUF; ++s)
+      if (d[s] && A.out[s]) KN_HIP(hipMemcpy(A.buf[s], d[s], A.bytes[s], hipMemcpyDeviceToHost));
+    return KNPEMI_OK;
+  }
+  template <class T> T* p(int s) const { return static_cast<T*>(d[s]); }
+};
+int kn_debug_linalg_amg(int op, const knpemi_debug_linalg_args& A);
+
 // Read-back of the diagnostic builds (KN_ROW_STAMPS, KN_DG_STAMPS, KN_HX_STAMPS): `symbol` is a __device__ array of 1024
 // slots, slot_stride counters apart, of which the first n_phases hold the ticks the kernel added up per phase.  On every
 // `every`-th launch (`launch` counts them from 1): synchronise, print the averages per unit (`n_units` workgroups or waves a

@@ -93,6 +93,20 @@ class DGParams(C.Structure):
     ]
 
 
+LINALG_MAX_BUF = 10
+(LINALG_SPMV, LINALG_BLOCK_SPMV, LINALG_DOTS, LINALG_VEC, LINALG_BICG_UPDATE, LINALG_BICG_INIT, LINALG_MASK,
+ LINALG_GHOST_IDENTITY, LINALG_DIAG_INV, LINALG_SCATTER_SHIFT, LINALG_EXTRAPOLATE, LINALG_KNP_ORDER,
+ LINALG_COARSE_RESTRICT, LINALG_COARSE_SOLVE, LINALG_COARSE_PROLONG) = range(15)
+LINALG_AMG_SPMV, LINALG_AMG_BLOCK_INV, LINALG_AMG_BLOCK_APPLY, LINALG_AMG_DENSE = range(20, 24)
+
+
+class DebugLinalgArgs(C.Structure):
+    """knpemi_debug_linalg_args: host arrays and parameters of one kernel run by knpemi_debug_linalg."""
+    _fields_ = [("n", C.c_int32), ("ip", C.c_int32 * 28), ("dp", C.c_double * 2),
+                ("buf", C.c_void_p * LINALG_MAX_BUF), ("bytes", C.c_uint64 * LINALG_MAX_BUF),
+                ("out", C.c_int32 * LINALG_MAX_BUF)]
+
+
 DG_C, DG_PHI, DG_PHI_M, DG_I_CH, DG_SOURCE, DG_JUMP = range(6)
 DG_ODE_STATE = 6                                        # knpemi_dg_snapshot_set: a state column of the bound table
 DG_SNAP_BROKEN, DG_SNAP_CELL_MEAN, DG_SNAP_VERTEX = range(3)
@@ -162,6 +176,7 @@ SIGNATURES = {
     "knpemi_ode_get_method": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "knpemi_debug_ode_stamps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int]),
     "knpemi_debug_math": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
+    "knpemi_debug_linalg": (C.c_int, [C.c_int, C.POINTER(DebugLinalgArgs)]),
     "knpemi_debug_launch_chain": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_dbl_p]),
     "knpemi_debug_geometry": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "knpemi_debug_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
